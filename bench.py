@@ -2,6 +2,7 @@
 """bench.py -- MCMC samples/sec (all replicas) + swap-accept rate on the BASELINE.json workload.
 
     python bench.py [--gpus N] [--steps K] [--warmup W] [--workload sunspot64|iris16|mackey64|ionosphere256|synthetic512]
+                    [--dump-outputs DIR]
 
 Workload at N = 1 (default `sunspot64`, the configuration BASELINE.json's metric is quoted on): Sunspot one-step-ahead
 regression, FNN [4,5,1], 64 replicas, Langevin-gradient proposals with probability 0.5 (lr 0.1), maxtemp 2, swap every 100 MH
@@ -287,6 +288,63 @@ def pmc_traffic(workload, kernel, steps_per_launch):
     return None, None
 
 
+# ------------------------------------------------------------------------------------------------ --dump-outputs
+DUMP_BYTES = 64 << 20
+
+
+def _kept(n, n_keep, seed):
+    """0 .. n-1, or a fixed, seeded, sorted sample of n_keep of them (at least one) when they do not all fit."""
+    if n_keep >= n:
+        return np.arange(n)
+    return np.sort(np.random.default_rng(seed).choice(n, max(int(n_keep), 1), replace=False))
+
+
+def _pos_w_rows(s, replicas, rows, chunk=DUMP_BYTES):
+    """pos_w [len(replicas), len(rows), P] of the sorted trace rows `rows`: one fetch per span of rows that fits `chunk` bytes."""
+    parts, i = [], 0
+    while i < len(rows):
+        j = i
+        while j + 1 < len(rows) and (rows[j + 1] - rows[i] + 1) * s.R * s.P * 4 <= chunk:
+            j += 1
+        span = s.traces(int(rows[i]), int(rows[j] - rows[i] + 1))["pos_w"]
+        parts.append(span[replicas][:, rows[i:j + 1] - rows[i]])
+        i = j + 1
+    return np.concatenate(parts, axis=1)
+
+
+def dump_outputs(s, out_dir, budget=DUMP_BYTES):
+    """What the last whole run handed its caller, as out_dir/<name>.npy (float32; counts and row numbers float64), `budget`
+    bytes at most: the chains' final state, the swap counters, the scalar traces [R, S] and pos_w [R, S, P].  Where all
+    replicas' weight vectors or all trace rows do not fit, a fixed, seeded sample of them is kept; replicas (of w and pos_w),
+    trace_rows and pos_w_rows say which."""
+    R, S, P = s.R, s.S, s.P
+    budget -= 4096                                                      # the .npy headers
+    st = s.state()
+    nsw, tot, rounds = s.swap_stats()
+    replicas = _kept(R, budget // 4 // (4 * P), seed=1)
+    out = {"w": st["w"][replicas], "replicas": replicas.astype(np.float64),
+           "swap_stats": np.array([nsw, tot, rounds], np.float64)}
+    for k in ("eta", "likelihood", "prior"):
+        out[k] = st[k]
+    for k in ("num_accepted", "langevin_count", "langevin_accepted"):
+        out[k] = st[k].astype(np.float64)
+    left = budget - sum(v.nbytes for v in out.values())
+    rows = _kept(S, left // 2 // (R * (5 * 4 + 8) + 8), seed=2)        # five float32 traces, accept as float64, the row number
+    tr = s.traces(pos_w=False)
+    for k in ("likeh", "rmse_train", "rmse_test", "acc_train", "acc_test"):
+        out[k] = tr[k][:, rows]
+    out["accept"] = tr["accept"][:, rows].astype(np.float64)
+    out["trace_rows"] = rows.astype(np.float64)
+    left = budget - sum(v.nbytes for v in out.values())
+    pos_rows = _kept(S, left // (len(replicas) * P * 4 + 8), seed=3)
+    out["pos_w"] = _pos_w_rows(s, replicas, pos_rows)
+    out["pos_w_rows"] = pos_rows.astype(np.float64)
+    os.makedirs(out_dir, exist_ok=True)
+    for k, v in out.items():
+        np.save(os.path.join(out_dir, k + ".npy"), np.ascontiguousarray(v))
+    return sum(v.nbytes for v in out.values())
+
+
 # ------------------------------------------------------------------------------------------------ N > 1 without a launcher
 def launch_plan(argv, n, master_port=None, environ=None, python=None, script=None):
     """What `python3 bench.py --gpus N` run bare starts: one command line + environment per rank (a pure function: the CPU test
@@ -349,6 +407,8 @@ def main():
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=100, help="timed whole runs")
     ap.add_argument("--warmup", type=int, default=10, help="untimed whole runs before them")
+    ap.add_argument("--dump-outputs", metavar="DIR", help="after the timed runs, write what the last one computed (rank 0's block "
+                    "of the ladder) as DIR/<name>.npy, 64 MB at most; the inputs are the same in every run with the same arguments")
     ap.add_argument("--workload", default="sunspot64", choices=list(WORKLOADS))
     ap.add_argument("--rw", action="store_true", help="random-walk proposals only (extra data point)")
     ap.add_argument("--replicas", type=int, default=0, help="replicas per GPU instead of the workload's own count (extra data point)")
@@ -374,6 +434,8 @@ def main():
                     help="N > 1: rccl = RCCL over xGMI inside libptnn; host = host-staged through gloo (rehearsal of the N > 1 code "
                          "path with every rank on GPU 0 of a one-GPU box; what it prints is not a measurement)")
     a = ap.parse_args()
+    if a.steps < 1 or a.warmup < 0:
+        ap.error("--steps must be at least 1 and --warmup at least 0")
     K, W, N = a.steps, a.warmup, a.gpus
     world = int(os.environ.get("WORLD_SIZE", "1"))
     rank = int(os.environ.get("RANK", "0"))
@@ -535,6 +597,9 @@ def main():
     nsw, tot, rounds = s.swap_stats()            # counters restart with every run: these are the last run's
     st = s.state()
     info = s.describe()
+    if a.dump_outputs and rank == 0:                 # before the extras below run the chains again
+        nbytes = dump_outputs(s, a.dump_outputs)
+        print(f"[bench] outputs of the last timed run: {nbytes} bytes in {a.dump_outputs}", file=sys.stderr, flush=True)
 
     # ---- untimed extras (rank 0): throughput of the half of a run the reference keeps after burn-in; dependent-chain analysis
     extras = {}

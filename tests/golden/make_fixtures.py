@@ -485,6 +485,27 @@ def gen_ladder(out):
     print("F7 ladder")
 
 
+# problem data: the files drivers.load_*_problem read, in the reference's layout, for tests/test_host_cpu.py
+def gen_problem_data(out):
+    """problem_data.tar.gz, byte for byte reproducible (sorted members, zero times and owners)."""
+    import gzip
+    import tarfile
+    sys.path.insert(0, ROOT)
+    import ptnn_amd  # noqa: F401
+    from ptnn_amd import drivers
+    files = [os.path.join("multicore-pt-regression", f) for name in ("Sunspot", "Mackey", "Lazer") for f in drivers.REG_FILES[name]]
+    files += [os.path.join("multicore-pt-classification", f) for name in ("Ionosphere", "Cancer", "iris", "winequality-red", "PenDigit")
+              for f in drivers.CLS_FILES[name][1]]
+    with gzip.GzipFile(os.path.join(out, "problem_data.tar.gz"), "wb", compresslevel=9, mtime=0) as gz, \
+            tarfile.open(fileobj=gz, mode="w", format=tarfile.PAX_FORMAT) as tar:
+        for rel in sorted(files):
+            info = tar.gettarinfo(os.path.join(REF, rel), arcname=rel)
+            info.mtime, info.uid, info.gid, info.uname, info.gname, info.mode = 0, 0, 0, "", "", 0o644
+            with open(os.path.join(REF, rel), "rb") as f:
+                tar.addfile(info, f)
+    print("problem data", len(files), "files")
+
+
 # --------------------------------------------------------------------------------------------
 # F9: statistical targets from long reference runs with the reference's OWN random numbers
 # --------------------------------------------------------------------------------------------
@@ -567,6 +588,7 @@ def main():
     if not a.only:                       # --only functions_<key> trajectory_<key> swap_trajectory_<key>: just those files (+ datasets.npz)
         gen_ladder(a.out)
         gen_cascade(a.out)
+        gen_problem_data(a.out)
     gen_functions(ds, a.out, a.only)
     gen_trajectories(ds, a.out, a.only)
     gen_swap_trajectories(ds, a.out, a.only)
