@@ -232,6 +232,58 @@ int ptnn_xchg_ptr(ptnn_handle *h, void **base, int *row_floats);
 int ptnn_swap_pack(ptnn_handle *h, int phantom);
 int ptnn_swap_apply_gathered(ptnn_handle *h, int phantom);
 
+/* ---- posterior predictive (the reference's drafts: fx_mu = fx.mean(axis=0) and np.percentile bands over the samples'
+ * network outputs, multicore-pt-classification/Misc_code/ldpt_classifier_multi.py:788-794; its run_chains() commented the
+ * per-sample outputs out, REG:244-245, 410-419, 785-837) ----
+ * Network outputs (REG: sigmoid output, REG:51-55; CLS: softmax of it, CLS:108-110) of a set of weight vectors on a set of input
+ * rows, reduced on the device.  The selected rows are collapsed into DISTINCT vectors with multiplicities (a rejected MH step
+ * repeats the previous vector, REG:417: runs of bitwise-equal consecutive rows of one chain, or of the TR_SRC row index with
+ * compact traces), each evaluated once.  Source: the handle's trace -- rows step0, step0 + thin, ... < step0 + nsteps of the local
+ * replicas listed (NULL = all, in order), same residency rules as ptnn_get_traces -- or, when w != NULL, n_w host vectors w [n_w, P]
+ * with optional multiplicities (NULL = 1 each; consecutive equal vectors merge as trace rows do).  M = the selected rows,
+ * repeats included (the sum of the multiplicities), at most 2^31 - 1.
+ * Inputs: x_source PTNN_PREDICT_X_HOST with x [n_rows, n_in] float32, or the handle's own train / test rows (n_rows must then be
+ * that set's size).  Outputs, any may be NULL: mean [n_rows, n_out] (the weighted mean, accumulated in double); order_stats
+ * [n_ranks, n_rows, n_out] = the exact fp32 value of 0-based rank ranks[k] in the expanded multiset of M values (no interpolation;
+ * n_ranks <= 16, 0 <= rank < M); vote [n_rows, n_out] (classification only) = the share of the M samples whose argmax class --
+ * of the returned probabilities, first index on a tie -- is that class; samples [M, n_rows, n_out] = every selected row's outputs,
+ * chain-major (the reference's fx_train_all / fx_test_all layout, REG:785-788); n_samples = M, n_distinct = distinct vectors.
+ * Runs on the handle's stream behind everything queued (a failed run surfaces as at ptnn_sync) and returns when done; columns are
+ * processed in blocks whose scratch stays under $PTNN_PREDICT_SCRATCH_BYTES (read per call, default 1 GiB), which changes no
+ * result.  Touches no chain state, tape, counter or trace row.  Not with a communicator attached (one GPU only). */
+#define PTNN_PREDICT_X_HOST 0
+#define PTNN_PREDICT_X_TRAIN 1
+#define PTNN_PREDICT_X_TEST 2
+#define PTNN_PREDICT_MAX_RANKS 16
+
+typedef struct ptnn_predict_spec {
+    int32_t struct_bytes;         /* = sizeof(ptnn_predict_spec): ABI guard */
+    /* source 1: the trace (used when w == NULL) */
+    const int32_t *replicas;      /* local replica indices, or NULL = all */
+    int32_t n_replicas;           /* entries of replicas (ignored when NULL) */
+    int32_t step0, nsteps, thin;  /* trace rows step0, step0 + thin, ... < step0 + nsteps (thin >= 1) */
+    /* source 2: host vectors */
+    const float *w;               /* [n_w, P] or NULL */
+    const int32_t *multiplicity;  /* [n_w] >= 0, or NULL = 1 each */
+    int64_t n_w;
+    /* inputs */
+    int32_t x_source;             /* PTNN_PREDICT_X_HOST | _TRAIN | _TEST */
+    int32_t n_rows;
+    const float *x;               /* [n_rows, n_in] (host rows only) */
+    /* order statistics */
+    const int64_t *ranks;         /* [n_ranks] */
+    int32_t n_ranks;
+    int32_t reserved_;            /* set 0 */
+    /* outputs */
+    double *mean;
+    float *order_stats;
+    double *vote;
+    float *samples;
+    int64_t *n_samples, *n_distinct;
+} ptnn_predict_spec;
+
+int ptnn_predict(ptnn_handle *h, const ptnn_predict_spec *spec);
+
 /* the HIP stream (hipStream_t) all of this handle's work is queued on: lets the caller order its collectives after the
  * segment / before the swap kernels on the device instead of synchronising the host */
 int ptnn_stream(ptnn_handle *h, void **hip_stream);

@@ -26,6 +26,23 @@ class Config(C.Structure):
     ]
 
 
+PREDICT_X_HOST, PREDICT_X_TRAIN, PREDICT_X_TEST = 0, 1, 2
+PREDICT_MAX_RANKS = 16
+
+
+class PredictSpec(C.Structure):
+    """ptnn_predict_spec (include/ptnn.h)."""
+    _fields_ = [
+        ("struct_bytes", C.c_int32),
+        ("replicas", C.POINTER(C.c_int32)), ("n_replicas", C.c_int32), ("step0", C.c_int32), ("nsteps", C.c_int32), ("thin", C.c_int32),
+        ("w", C.POINTER(C.c_float)), ("multiplicity", C.POINTER(C.c_int32)), ("n_w", C.c_int64),
+        ("x_source", C.c_int32), ("n_rows", C.c_int32), ("x", C.POINTER(C.c_float)),
+        ("ranks", C.POINTER(C.c_int64)), ("n_ranks", C.c_int32), ("reserved_", C.c_int32),
+        ("mean", C.POINTER(C.c_double)), ("order_stats", C.POINTER(C.c_float)), ("vote", C.POINTER(C.c_double)),
+        ("samples", C.POINTER(C.c_float)), ("n_samples", C.POINTER(C.c_int64)), ("n_distinct", C.POINTER(C.c_int64)),
+    ]
+
+
 def library_path():
     return os.environ.get("PTNN_LIBRARY", os.path.join(_HERE, "libptnn.so"))
 
@@ -103,6 +120,7 @@ SYMBOLS = {
     "ptnn_trace_image": (C.c_int, [C.c_void_p, C.POINTER(_fp), _ip, C.POINTER(_fp)]),
     "ptnn_trace_image_fetch": (C.c_int, [C.c_void_p, C.c_int, C.c_int]),
     "ptnn_trace_image_wait": (C.c_int, [C.c_void_p, C.c_int]),
+    "ptnn_predict": (C.c_int, [C.c_void_p, C.POINTER(PredictSpec)]),
 }
 
 
@@ -430,6 +448,73 @@ class Sampler:
         tau = None if tau_sq is None else _f32(np.broadcast_to(np.asarray(tau_sq, dtype=np.float32), (n,)))
         out = np.empty((n, 8), np.float32)
         self._check(self.lib.ptnn_evaluate(self.h, _ptr(w), _ptr(tau), n, _ptr(out)))
+        return out
+
+    def predict(self, x="test", *, replicas=None, step0=0, nsteps=None, thin=1, w=None, multiplicity=None, ranks=(), mean=True,
+                vote=False, samples=False):
+        """ptnn_predict: network outputs of the selected weight vectors on input rows, reduced on the device.  Source: the trace rows
+        step0, step0 + thin, ... < step0 + nsteps of `replicas` (None = all), or host vectors w [n, P] with optional integer
+        `multiplicity` [n].  x: "train", "test" or rows [n_rows, n_in].  -> dict(mean [n_rows, O] float64, order_stats
+        [len(ranks), n_rows, O] float32 (exact values of those 0-based ranks), vote [n_rows, O] float64 (classification), samples
+        [M, n_rows, O] float32, n_samples, n_distinct); what was not asked for is None."""
+        spec = PredictSpec()
+        spec.struct_bytes = C.sizeof(PredictSpec)
+        keep = []
+        if isinstance(x, str):
+            src = {"train": PREDICT_X_TRAIN, "test": PREDICT_X_TEST}.get(x)
+            if src is None:
+                raise ValueError(f"x must be 'train', 'test' or an array, not {x!r}")
+            spec.x_source = src
+            spec.n_rows = self.ntr if src == PREDICT_X_TRAIN else self.nte
+        else:
+            xa = _f32(x)
+            if xa.ndim != 2 or xa.shape[1] != self.cfg.n_in:
+                raise ValueError(f"x must be [n_rows, {self.cfg.n_in}] (n_in columns), got shape {xa.shape}")
+            keep.append(xa)
+            spec.x_source, spec.n_rows, spec.x = PREDICT_X_HOST, xa.shape[0], _ptr(xa)
+        n_rows, O = spec.n_rows, self.cfg.n_out
+        if w is not None:
+            wa = _f32(w)
+            if wa.ndim != 2 or wa.shape[1] != self.P:
+                raise ValueError(f"w must be [n, {self.P}], got shape {wa.shape}")
+            keep.append(wa)
+            spec.w, spec.n_w = _ptr(wa), wa.shape[0]
+            if multiplicity is not None:
+                mu = np.ascontiguousarray(multiplicity, dtype=np.int32)
+                if mu.shape != (wa.shape[0],):
+                    raise ValueError("multiplicity must have one entry per vector")
+                keep.append(mu)
+                spec.multiplicity = _ptr(mu, _ip)
+                M = int(mu.astype(np.int64).sum())
+            else:
+                M = wa.shape[0]
+        else:
+            if replicas is not None:
+                ra = np.ascontiguousarray(replicas, dtype=np.int32).reshape(-1)
+                keep.append(ra)
+                spec.replicas, spec.n_replicas = _ptr(ra, _ip), ra.size
+                nrep = ra.size
+            else:
+                nrep = self.R
+            spec.step0 = int(step0)
+            spec.nsteps = int(self.S - step0 if nsteps is None else nsteps)
+            spec.thin = int(thin)
+            M = nrep * max(0, -(-spec.nsteps // max(1, spec.thin)))
+        rk = np.ascontiguousarray(ranks, dtype=np.int64).reshape(-1)
+        keep.append(rk)
+        spec.ranks, spec.n_ranks = (_ptr(rk, C.POINTER(C.c_int64)) if rk.size else None), rk.size
+        out = dict(mean=np.empty((n_rows, O), np.float64) if mean else None,
+                   order_stats=np.empty((rk.size, n_rows, O), np.float32) if rk.size else None,
+                   vote=np.empty((n_rows, O), np.float64) if vote else None,
+                   samples=np.empty((max(M, 0), n_rows, O), np.float32) if samples else None)
+        spec.mean = _ptr(out["mean"], C.POINTER(C.c_double))
+        spec.order_stats = _ptr(out["order_stats"])
+        spec.vote = _ptr(out["vote"], C.POINTER(C.c_double))
+        spec.samples = _ptr(out["samples"])
+        ns, nd = C.c_int64(0), C.c_int64(0)
+        spec.n_samples, spec.n_distinct = C.pointer(ns), C.pointer(nd)
+        self._check(self.lib.ptnn_predict(self.h, C.byref(spec)))
+        out["n_samples"], out["n_distinct"] = ns.value, nd.value
         return out
 
     def langevin_gradient(self, w):

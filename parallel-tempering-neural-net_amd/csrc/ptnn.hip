@@ -1792,6 +1792,223 @@ int ptnn_checkpoint_load(ptnn_handle* h, const void* buf, int64_t bytes) {
     return 0;
 }
 
+// ---- posterior predictive (ptnn_dev_predict.hpp) ----
+}  // extern "C" (the scratch guard below is a class)
+
+namespace {
+struct DeviceScratch {            // every buffer of one ptnn_predict call, released on every return path
+    std::vector<void*> ptrs;
+    ~DeviceScratch() { for (void* p : ptrs) (void)hipFree(p); }
+    template <typename T> hipError_t alloc(T** p, size_t n) {
+        *p = nullptr;
+        if (n == 0) return hipSuccess;
+        void* q = nullptr;
+        const hipError_t e = hipMalloc(&q, n * sizeof(T));
+        if (e == hipSuccess) { ptrs.push_back(q); *p = static_cast<T*>(q); }
+        return e;
+    }
+};
+
+size_t predict_scratch_budget() {
+    const char* e = std::getenv("PTNN_PREDICT_SCRATCH_BYTES");
+    if (e && *e) {
+        const long long v = std::atoll(e);
+        if (v > 0) return (size_t)v;
+    }
+    return (size_t)1 << 30;
+}
+}  // namespace
+
+extern "C" {
+
+int ptnn_predict(ptnn_handle* h, const ptnn_predict_spec* spec) {
+    // argument checks first: none of them needs the handle or a device
+    if (!spec) return fail(-1, "null argument");
+    if (spec->struct_bytes != (int32_t)sizeof(ptnn_predict_spec))
+        return fail(-1, "ptnn_predict_spec.struct_bytes = %d, expected %d", spec->struct_bytes, (int)sizeof(ptnn_predict_spec));
+    const ptnn_predict_spec& s = *spec;
+    const bool host_src = s.w != nullptr;
+    if (host_src && s.n_w < 1) return fail(-1, "n_w = %lld host vectors: need at least one", (long long)s.n_w);
+    if (!host_src && s.thin < 1) return fail(-1, "thin = %d must be >= 1", s.thin);
+    if (!host_src && s.replicas && s.n_replicas < 1) return fail(-1, "n_replicas = %d with a replica list", s.n_replicas);
+    if (s.x_source != PTNN_PREDICT_X_HOST && s.x_source != PTNN_PREDICT_X_TRAIN && s.x_source != PTNN_PREDICT_X_TEST)
+        return fail(-1, "x_source = %d is not PTNN_PREDICT_X_HOST, _TRAIN or _TEST", s.x_source);
+    if (s.x_source == PTNN_PREDICT_X_HOST && !s.x) return fail(-1, "x_source PTNN_PREDICT_X_HOST needs x");
+    if (s.n_rows < 1) return fail(-1, "n_rows = %d must be >= 1", s.n_rows);
+    if (s.n_ranks < 0 || s.n_ranks > PTNN_PREDICT_MAX_RANKS) return fail(-1, "n_ranks = %d outside [0, %d]", s.n_ranks, PTNN_PREDICT_MAX_RANKS);
+    if (s.n_ranks > 0 && !s.ranks) return fail(-1, "n_ranks = %d but ranks is NULL", s.n_ranks);
+    if (s.order_stats && s.n_ranks == 0) return fail(-1, "order_stats requested without ranks");
+    if (int rc = check_ready(h)) return rc;
+    if (h->comm.kind != COMM_NONE) return fail(-3, "ptnn_predict serves one GPU: this handle has a communicator attached");
+    const int I = h->cfg.n_in, H = h->cfg.n_hidden, O = h->cfg.n_out, P = h->P, Rl = h->cfg.n_replicas_local, cap = h->cap;
+    if (s.vote && h->cfg.task != PTNN_TASK_CLS) return fail(-1, "vote: a regression has no classes");
+    if (s.x_source == PTNN_PREDICT_X_TRAIN && s.n_rows != h->Ntr) return fail(-1, "n_rows = %d but the train set has %d rows", s.n_rows, h->Ntr);
+    if (s.x_source == PTNN_PREDICT_X_TEST && s.n_rows != h->Nte) return fail(-1, "n_rows = %d but the test set has %d rows", s.n_rows, h->Nte);
+    // the selection
+    std::vector<int32_t> reps;
+    long long n_items = 0, M = 0;
+    int m = 0;
+    if (host_src) {
+        n_items = s.n_w;
+        if (s.multiplicity) {
+            for (int64_t k = 0; k < s.n_w; ++k) {
+                if (s.multiplicity[k] < 0) return fail(-1, "multiplicity[%lld] = %d is negative", (long long)k, s.multiplicity[k]);
+                M += s.multiplicity[k];
+            }
+        } else {
+            M = s.n_w;
+        }
+    } else {
+        const int S = h->cfg.n_samples;
+        const int step0 = s.step0, nsteps = s.nsteps;
+        if (step0 < 0 || nsteps < 1 || step0 + nsteps > S) return fail(-1, "trace range [%d, %d) outside [0, %d)", step0, step0 + nsteps, S);
+        if (step0 + nsteps > h->cur + 1) return fail(-1, "rows up to %d requested but only %d MH steps have been queued", step0 + nsteps - 1, h->cur);
+        if (step0 < h->first_row) return fail(-1, "rows below %d were produced before the checkpoint these chains were restored from", h->first_row);
+        if (step0 < h->cur + 1 - cap) return fail(-1, "row %d has already been overwritten in the trace ring (capacity %d, %d steps done)", step0, cap, h->cur);
+        if (s.replicas) {
+            for (int k = 0; k < s.n_replicas; ++k) {
+                if (s.replicas[k] < 0 || s.replicas[k] >= Rl) return fail(-1, "replica %d out of range [0, %d)", s.replicas[k], Rl);
+                reps.push_back(s.replicas[k]);
+            }
+        } else {
+            for (int r = 0; r < Rl; ++r) reps.push_back(r);
+        }
+        m = (nsteps + s.thin - 1) / s.thin;
+        n_items = (long long)reps.size() * m;
+        M = n_items;
+    }
+    if (M < 1) return fail(-1, "the selection holds no sample");
+    if (M > 0x7fffffffLL || n_items > 0x7fffffffLL) return fail(-1, "%lld samples: at most 2^31 - 1 per call", M);
+    for (int k = 0; k < s.n_ranks; ++k)
+        if (s.ranks[k] < 0 || s.ranks[k] >= M) return fail(-1, "rank %lld outside [0, %lld)", (long long)s.ranks[k], M);
+    if (s.n_samples) *s.n_samples = M;
+
+    HIP_TRY(hipSetDevice(h->cfg.device_id));
+    if (int rc = finish_stream(h)) return rc;          // behind everything queued; a failed run is refused here
+    hipStream_t st = h->stream;
+    DeviceScratch mem;
+    const int ncols = s.n_rows * O;
+    // inputs
+    const float* d_x = nullptr;
+    int xs = 0;
+    if (s.x_source == PTNN_PREDICT_X_HOST) {
+        float* d = nullptr;
+        HIP_TRY(mem.alloc(&d, (size_t)s.n_rows * I));
+        HIP_TRY(hipMemcpyAsync(d, s.x, (size_t)s.n_rows * I * sizeof(float), hipMemcpyHostToDevice, st));
+        d_x = d; xs = I;
+    } else {
+        d_x = h->d_data + (s.x_source == PTNN_PREDICT_X_TEST ? (size_t)h->Ntr * h->IPY : 0);
+        xs = h->IPY;
+    }
+    // stage a: items -> runs
+    long long* d_item_off = nullptr; long long* d_run_off = nullptr; long long* d_ranks = nullptr;
+    int *d_flag = nullptr, *d_item_run = nullptr, *d_run_cnt = nullptr, *d_nruns = nullptr, *d_weight = nullptr, *d_reps = nullptr;
+    float* d_w = nullptr;
+    HIP_TRY(mem.alloc(&d_item_off, (size_t)n_items));
+    HIP_TRY(mem.alloc(&d_run_off, (size_t)n_items));
+    HIP_TRY(mem.alloc(&d_flag, (size_t)n_items));
+    HIP_TRY(mem.alloc(&d_item_run, (size_t)n_items));
+    HIP_TRY(mem.alloc(&d_run_cnt, (size_t)n_items));
+    HIP_TRY(mem.alloc(&d_nruns, 2));                     // [0] runs, [1] error count of the compact-row resolution
+    HIP_TRY(hipMemsetAsync(d_run_cnt, 0, (size_t)n_items * sizeof(int), st));
+    HIP_TRY(hipMemsetAsync(d_nruns, 0, 2 * sizeof(int), st));
+    PredictSel sel{};
+    sel.P = P; sel.n_items = n_items; sel.item_off = d_item_off; sel.flag = d_flag; sel.error = d_nruns + 1;
+    const float* base = nullptr;
+    if (host_src) {
+        HIP_TRY(mem.alloc(&d_w, (size_t)n_items * P));
+        HIP_TRY(hipMemcpyAsync(d_w, s.w, (size_t)n_items * P * sizeof(float), hipMemcpyHostToDevice, st));
+        if (s.multiplicity) {
+            HIP_TRY(mem.alloc(&d_weight, (size_t)n_items));
+            HIP_TRY(hipMemcpyAsync(d_weight, s.multiplicity, (size_t)n_items * sizeof(int32_t), hipMemcpyHostToDevice, st));
+        }
+        sel.host = 1; sel.pos_w = d_w;
+        base = d_w;
+    } else {
+        HIP_TRY(mem.alloc(&d_reps, reps.size()));
+        HIP_TRY(hipMemcpyAsync(d_reps, reps.data(), reps.size() * sizeof(int32_t), hipMemcpyHostToDevice, st));
+        sel.host = 0; sel.pos_w = h->d_pos_w; sel.scal = h->d_scal; sel.replicas = d_reps; sel.cap = cap; sel.PW = h->PW;
+        sel.step0 = s.step0; sel.thin = s.thin; sel.m = m; sel.compact = h->compact ? 1 : 0;
+        base = h->d_pos_w;
+    }
+    hipLaunchKernelGGL(predict_runs_kernel, dim3((unsigned)((n_items + PRED_THREADS - 1) / PRED_THREADS)), dim3(PRED_THREADS), 0, st, sel);
+    HIP_TRY(hipGetLastError());
+    PredictScan sc{n_items, d_flag, d_item_off, d_weight, d_item_run, d_run_off, d_run_cnt, d_nruns};
+    hipLaunchKernelGGL(predict_scan_kernel, dim3(1), dim3(PRED_SCAN_THREADS), 0, st, sc);
+    HIP_TRY(hipGetLastError());
+    int runs[2] = {0, 0};
+    HIP_TRY(hipMemcpyAsync(runs, d_nruns, sizeof runs, hipMemcpyDeviceToHost, st));
+    if (int rc = wait_stream(h)) return rc;
+    if (runs[1]) return fail(-2, "%d selected compact trace rows refer to rows that are not resident (internal error)", runs[1]);
+    const int U = runs[0];
+    if (U < 1 || U > n_items) return fail(-2, "run-length pass found %d distinct vectors among %lld rows (internal error)", U, n_items);
+    if (s.n_distinct) *s.n_distinct = U;
+    // outputs on the device for every column; votes as integer counts (exact whatever the order)
+    double* d_mean = nullptr; float* d_ostat = nullptr; long long* d_votes = nullptr;
+    HIP_TRY(mem.alloc(&d_mean, (size_t)ncols));
+    if (s.n_ranks) {
+        HIP_TRY(mem.alloc(&d_ostat, (size_t)s.n_ranks * ncols));
+        HIP_TRY(mem.alloc(&d_ranks, (size_t)s.n_ranks));
+        HIP_TRY(hipMemcpyAsync(d_ranks, s.ranks, (size_t)s.n_ranks * sizeof(int64_t), hipMemcpyHostToDevice, st));
+    }
+    if (h->cfg.task == PTNN_TASK_CLS) HIP_TRY(mem.alloc(&d_votes, (size_t)ncols));
+    // stage b + c in blocks of rows: fx scratch U x (rows x O) floats under the budget
+    const size_t budget = predict_scratch_budget();
+    const size_t col_bytes = (size_t)U * sizeof(float);
+    long long rows_blk = (long long)(budget / (col_bytes * O));
+    rows_blk = std::max(1LL, std::min<long long>(rows_blk, s.n_rows));
+    float* d_fx = nullptr;
+    HIP_TRY(mem.alloc(&d_fx, (size_t)rows_blk * O * U));
+    const int PV = round_up4(P);
+    const int per_vec = PV + (PRED_THREADS / WAVE + 1) * O * WAVE;     // staged vector + partial sums + transposed tile, floats
+    int NV = std::max(1, std::min(PRED_MAX_NV, (48 * 1024 / 4) / per_vec));
+    const size_t lds = (size_t)NV * per_vec * sizeof(float);
+    if (lds > 152 * 1024) return fail(-3, "posterior predictive: a %d-parameter vector does not fit in LDS", P);
+    const void* fwd = reinterpret_cast<const void*>(h->shape->predict_fwd);
+    if (int rc = raise_lds_limit(fwd, lds)) return rc;
+    std::vector<int> item_run;
+    std::vector<float> fx_host;
+    if (s.samples) {
+        item_run.resize((size_t)n_items);
+        HIP_TRY(hipMemcpyAsync(item_run.data(), d_item_run, (size_t)n_items * sizeof(int), hipMemcpyDeviceToHost, st));
+    }
+    for (long long r0 = 0; r0 < s.n_rows; r0 += rows_blk) {
+        const int nr = (int)std::min<long long>(rows_blk, s.n_rows - r0);
+        PredictFwd fa{base, d_run_off, d_x, xs, (int)r0, nr, H, P, PV, U, NV, d_fx};
+        hipLaunchKernelGGL(h->shape->predict_fwd, dim3((unsigned)((U + NV - 1) / NV), (unsigned)((nr + WAVE - 1) / WAVE)), dim3(PRED_THREADS), lds, st, fa);
+        HIP_TRY(hipGetLastError());
+        PredictRed ra{d_fx, d_run_cnt, U, O, (int)r0 * O, ncols, M, s.n_ranks, d_ranks, d_mean, d_ostat, d_votes};
+        hipLaunchKernelGGL(predict_reduce_kernel, dim3((unsigned)(nr * O)), dim3(PRED_THREADS), 0, st, ra);
+        HIP_TRY(hipGetLastError());
+        if (s.samples) {
+            // every selected row gets its distinct vector's outputs, in the order of the selection (chain-major)
+            fx_host.resize((size_t)nr * O * U);
+            HIP_TRY(hipMemcpyAsync(fx_host.data(), d_fx, fx_host.size() * sizeof(float), hipMemcpyDeviceToHost, st));
+            if (int rc = wait_stream(h)) return rc;
+            long long out_row = 0;
+            for (long long i = 0; i < n_items; ++i) {
+                const int reps_i = (host_src && s.multiplicity) ? s.multiplicity[i] : 1;
+                const size_t u = (size_t)item_run[(size_t)i];
+                for (int k = 0; k < reps_i; ++k, ++out_row) {
+                    float* dst = s.samples + ((size_t)out_row * s.n_rows + r0) * O;
+                    for (int c = 0; c < nr * O; ++c) dst[c] = fx_host[(size_t)c * U + u];
+                }
+            }
+        }
+    }
+    std::vector<long long> votes_h;
+    if (s.mean) HIP_TRY(hipMemcpyAsync(s.mean, d_mean, (size_t)ncols * sizeof(double), hipMemcpyDeviceToHost, st));
+    if (s.order_stats) HIP_TRY(hipMemcpyAsync(s.order_stats, d_ostat, (size_t)s.n_ranks * ncols * sizeof(float), hipMemcpyDeviceToHost, st));
+    if (s.vote) {
+        votes_h.resize((size_t)ncols);
+        HIP_TRY(hipMemcpyAsync(votes_h.data(), d_votes, (size_t)ncols * sizeof(long long), hipMemcpyDeviceToHost, st));
+    }
+    if (int rc = wait_stream(h)) return rc;
+    if (s.vote)
+        for (int c = 0; c < ncols; ++c) s.vote[c] = (double)votes_h[(size_t)c] / (double)M;
+    return 0;
+}
+
 static int run_model(ptnn_handle* h, int mode, const float* w_in, const float* tau_sq, int n, float* out, size_t out_floats,
                      int a0, int a1) {
     if (!h) return fail(-1, "null handle");

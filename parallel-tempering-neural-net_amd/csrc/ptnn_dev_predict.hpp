@@ -1,0 +1,284 @@
+// ptnn_dev_predict.hpp -- posterior predictive over sampled weight vectors (ptnn_predict, include/ptnn.h).
+//
+// The reference's drafts take the network outputs of every post-burn-in sample on the train and test rows and reduce them to
+// a mean and 5 / 95 % percentile bands (multicore-pt-classification/Misc_code/ldpt_classifier_multi.py:788-794); its
+// run_chains() stopped producing those outputs "to save memory" (REG:244-245, 410-419, 785-837).  Three stages:
+//   a. predict_runs_kernel + predict_scan_kernel: the selected rows (trace rows of a list of chains, or uploaded vectors) are
+//      collapsed into DISTINCT vectors with integer multiplicities -- a rejected MH step repeats the previous vector (REG:417),
+//      so most selected rows repeat the one before; the output depends on w only, so one evaluation per run is exact.
+//   b. predict_forward_kernel<TASK, I, O> (per shape, Shape::predict_fwd): fx[col][u] = ForwardPass of distinct vector u on
+//      output column col = row * O + o of a block of input rows (REG:51-55 / CLS:49-55; CLS: softmax of it, CLS:108-110).
+//   c. predict_reduce_kernel: one work-group per column -- weighted mean (double), exact weighted order statistics (radix select
+//      on the order-preserving key of the fp32 value), and for classification the class-vote counts.
+// Nothing here writes chain state, tapes, counters or trace rows.
+
+constexpr int PRED_THREADS = 256;        // forward and reduce kernels: 4 waves
+constexpr int PRED_SCAN_THREADS = 1024;  // the scan: one work-group
+constexpr int PRED_MAX_RANKS = 16;
+constexpr int PRED_MAX_NV = 16;          // distinct vectors per forward work-group
+
+// what the forward kernel needs (the host fills it; ptnn.hip: ptnn_predict)
+struct PredictFwd {
+    const float* base;          // vectors: d_pos_w rows or the uploaded host vectors
+    const long long* run_off;   // [U] float offset of distinct vector u in base
+    const float* x;             // input rows, x_0 .. x_{I-1} at x + row * xs
+    int xs;                     // row stride of x (floats)
+    int row0, nrows;            // rows [row0, row0 + nrows) of x form this block of columns
+    int H, P, PV;               // hidden units, parameters, LDS stride of a staged vector (P rounded up to 4)
+    int U, NV;                  // distinct vectors, vectors staged per work-group
+    float* fx;                  // [nrows * O][U] column-major
+};
+
+template <int TASK, int I, int O>
+__global__ void __launch_bounds__(PRED_THREADS) predict_forward_kernel(const PredictFwd a) {
+    extern __shared__ __attribute__((aligned(16))) float smem[];
+    const int tid = threadIdx.x, lane = tid & (WAVE - 1);
+    const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+    constexpr int NWAVE = PRED_THREADS / WAVE;
+    const int NV = a.NV, PV = a.PV, H = a.H;
+    const int u0 = blockIdx.x * NV;
+    const int nv = min(NV, a.U - u0);
+    const int r0 = blockIdx.y * WAVE;
+    float* sv = smem;                                   // [NV][PV] the staged vectors
+    float* red = sv + (size_t)NV * PV;                  // [NWAVE][NV][O][64] partial output sums, one per wave's hidden slice
+    float* fin = red + (size_t)NWAVE * NV * O * WAVE;   // [64 * O][NV] finished outputs, the tile transposed for the store
+    for (int v = 0; v < nv; ++v) {
+        const float* src = a.base + a.run_off[u0 + v];
+        for (int k = tid; k < a.P; k += PRED_THREADS) sv[v * PV + k] = src[k];
+    }
+    // one lane per input row, the row's inputs in registers (a lane past the last row computes row 0 and stores nothing)
+    const int row = r0 + lane;
+    const bool live = row < a.nrows;
+    const float* xr = a.x + (size_t)(a.row0 + (live ? row : 0)) * a.xs;
+    float x[I];
+#pragma unroll
+    for (int i = 0; i < I; ++i) x[i] = xr[i];
+    __syncthreads();
+    // wave `wave` takes the hidden units h = wave, wave + 4, ...: every weight read is wave-uniform (an LDS broadcast)
+    for (int v = 0; v < nv; ++v) {
+        const float* W1 = sv + v * PV;                  // [I][H]  (decode: w = W1, W2, B1, B2)
+        const float* W2 = W1 + I * H;                   // [H][O]
+        const float* B1 = W2 + H * O;
+        float acc[O];
+#pragma unroll
+        for (int o = 0; o < O; ++o) acc[o] = 0.0f;
+        for (int h = wave; h < H; h += NWAVE) {
+            float z = 0.0f;
+#pragma unroll
+            for (int i = 0; i < I; ++i) z = fmaf(x[i], W1[i * H + h], z);
+            const float hid = 1.0f / (1.0f + expf(-(z - B1[h])));        // bias subtracted (Q1)
+#pragma unroll
+            for (int o = 0; o < O; ++o) acc[o] = fmaf(hid, W2[h * O + o], acc[o]);
+        }
+#pragma unroll
+        for (int o = 0; o < O; ++o) red[(((size_t)wave * NV + v) * O + o) * WAVE + lane] = acc[o];
+    }
+    __syncthreads();
+    // the four partial sums in a fixed order, the output sigmoid (Q2), classification: softmax (CLS:108-110)
+    for (int idx = tid; idx < nv * WAVE; idx += PRED_THREADS) {
+        const int v = idx / WAVE, l = idx % WAVE;
+        const float* B2 = sv + v * PV + I * a.H + a.H * O + a.H;
+        float out[O];
+#pragma unroll
+        for (int o = 0; o < O; ++o) {
+            float s = red[(((size_t)0 * NV + v) * O + o) * WAVE + l];
+#pragma unroll
+            for (int w = 1; w < NWAVE; ++w) s += red[(((size_t)w * NV + v) * O + o) * WAVE + l];
+            out[o] = 1.0f / (1.0f + expf(-(s - B2[o])));
+        }
+        if (TASK == TASK_CLS) {
+            float e[O], sum = 0.0f;
+#pragma unroll
+            for (int o = 0; o < O; ++o) { e[o] = expf(out[o]); sum += e[o]; }
+#pragma unroll
+            for (int o = 0; o < O; ++o) out[o] = e[o] / sum;
+        }
+#pragma unroll
+        for (int o = 0; o < O; ++o) fin[(size_t)(l * O + o) * NV + v] = out[o];
+    }
+    __syncthreads();
+    // column-major store: column r0 * O + c of the block gets NV consecutive floats
+    for (int idx = tid; idx < WAVE * O * NV; idx += PRED_THREADS) {
+        const int c = idx / NV, v = idx % NV;
+        if (v < nv && r0 + c / O < a.nrows) a.fx[(size_t)(r0 * O + c) * a.U + u0 + v] = fin[idx];
+    }
+}
+
+#ifndef PTNN_SHAPE_TU      // shape-independent kernels: defined in the main translation unit only
+
+// stage a, part 1: per selected item, where its vector is and whether it starts a new run
+struct PredictSel {
+    // trace source (items = n_chains x m selected rows, chain-major)
+    const float* pos_w;         // d_pos_w [Rl][cap][PW]
+    const float* scal;          // d_scal [Rl][cap][TR_COUNT] (compact traces: TR_SRC)
+    const int* replicas;        // [n_chains] local replica indices
+    int cap, PW, step0, thin, m, compact;
+    // host source (items = uploaded vectors [n][P], dense)
+    int host;
+    int P;
+    long long n_items;
+    long long* item_off;        // out: float offset of the item's vector
+    int* flag;                  // out: 1 = the item starts a run
+    int* error;                 // out: != 0 = a compact row referred to a row that is not resident (internal error)
+};
+
+__global__ void __launch_bounds__(PRED_THREADS) predict_runs_kernel(const PredictSel s) {
+    const long long i = (long long)blockIdx.x * PRED_THREADS + threadIdx.x;
+    if (i >= s.n_items) return;
+    if (s.host) {
+        const float* w = s.pos_w + i * s.P;
+        int differs = i == 0;
+        for (int k = 0; k < s.P && !differs; ++k) differs = __float_as_uint(w[k]) != __float_as_uint(w[k - s.P]);
+        s.item_off[i] = i * s.P;
+        s.flag[i] = differs;
+        return;
+    }
+    const int c = (int)(i / s.m), j = (int)(i % s.m);
+    const long long rep = s.replicas[c];
+    auto resolve = [&](int jj, int* src_out) -> long long {
+        const int step = s.step0 + jj * s.thin;
+        const int slot = step % s.cap;
+        if (!s.compact) { *src_out = step; return (rep * s.cap + slot) * (long long)s.PW; }
+        int src = __float_as_int(s.scal[(rep * s.cap + slot) * TR_COUNT + TR_SRC]);
+        if (src < 0 || src > step) { atomicAdd(s.error, 1); src = step; }   // keeps the address inside the ring
+        *src_out = src;
+        return (rep * s.cap + src % s.cap) * (long long)s.PW;
+    };
+    int src = 0, src_prev = 0;
+    const long long off = resolve(j, &src);
+    int differs = j == 0;
+    if (!differs) {
+        const long long off_prev = resolve(j - 1, &src_prev);
+        if (s.compact) differs = src != src_prev;
+        else {
+            const float* a = s.pos_w + off;
+            const float* b = s.pos_w + off_prev;
+            for (int k = 0; k < s.P && !differs; ++k) differs = __float_as_uint(a[k]) != __float_as_uint(b[k]);
+        }
+    }
+    s.item_off[i] = off;
+    s.flag[i] = differs;
+}
+
+// stage a, part 2 (one work-group): run index of every item, the offset and multiplicity of every run, the number of runs
+struct PredictScan {
+    long long n_items;
+    const int* flag;
+    const long long* item_off;
+    const int* weight;          // [n_items] multiplicity of the item, or null (1 each)
+    int* item_run;              // out: run index of the item
+    long long* run_off;         // out: [U] vector offset of the run
+    int* run_cnt;               // out: [U] multiplicity (zeroed by the caller)
+    int* n_runs;                // out: U
+};
+
+__global__ void __launch_bounds__(PRED_SCAN_THREADS) predict_scan_kernel(const PredictScan s) {
+    __shared__ long long part[PRED_SCAN_THREADS];
+    const int tid = threadIdx.x;
+    const long long per = (s.n_items + PRED_SCAN_THREADS - 1) / PRED_SCAN_THREADS;
+    const long long lo = min(s.n_items, per * tid), hi = min(s.n_items, lo + per);
+    long long c = 0;
+    for (long long i = lo; i < hi; ++i) c += s.flag[i];
+    part[tid] = c;
+    __syncthreads();
+    for (int d = 1; d < PRED_SCAN_THREADS; d <<= 1) {      // inclusive scan of the per-thread run starts
+        const long long add = tid >= d ? part[tid - d] : 0;
+        __syncthreads();
+        part[tid] += add;
+        __syncthreads();
+    }
+    long long r = part[tid] - c - 1;                        // index of the run in progress before this thread's first item
+    for (long long i = lo; i < hi; ++i) {
+        if (s.flag[i]) { ++r; s.run_off[r] = s.item_off[i]; }
+        s.item_run[i] = (int)r;
+        atomicAdd(&s.run_cnt[r], s.weight ? s.weight[i] : 1);
+    }
+    if (tid == PRED_SCAN_THREADS - 1) *s.n_runs = (int)part[tid];
+}
+
+// stage c: one work-group per output column of a block
+struct PredictRed {
+    const float* fx;            // [ncols][U]
+    const int* cnt;             // [U]
+    int U, O, col0;             // col0: global index of the block's first column
+    int ncols_total;            // columns of the whole request (n_rows * O)
+    long long M;                // selected rows, repeats included
+    int n_ranks;
+    const long long* ranks;     // [n_ranks] 0-based ranks in the expanded multiset
+    double* mean;               // [ncols_total]
+    float* ostat;               // [n_ranks][ncols_total]
+    long long* votes;           // [ncols_total] samples whose argmax is this column's class, or null (regression)
+};
+
+__device__ __forceinline__ unsigned pred_key(float f) {         // order-preserving uint32 key of an fp32 value
+    const unsigned u = __float_as_uint(f);
+    return (u & 0x80000000u) ? ~u : (u | 0x80000000u);
+}
+__device__ __forceinline__ float pred_unkey(unsigned k) {
+    return __uint_as_float((k & 0x80000000u) ? (k & 0x7fffffffu) : ~k);
+}
+
+__global__ void __launch_bounds__(PRED_THREADS) predict_reduce_kernel(const PredictRed r) {
+    __shared__ double dsum[PRED_THREADS];
+    __shared__ long long vsum[PRED_THREADS];
+    __shared__ unsigned hist[PRED_MAX_RANKS][256];
+    __shared__ unsigned prefix[PRED_MAX_RANKS];
+    __shared__ long long krem[PRED_MAX_RANKS];
+    const int tid = threadIdx.x, col = blockIdx.x;
+    const float* f = r.fx + (size_t)col * r.U;
+    // weighted mean in double, a fixed summation order for a given U
+    double s = 0.0;
+    long long votes = 0;
+    const int o = col % r.O;
+    const float* row_base = r.fx + (size_t)(col - o) * r.U;  // column of class 0 of the same row
+    for (int u = tid; u < r.U; u += PRED_THREADS) {
+        const int c = r.cnt[u];
+        s += (double)c * (double)f[u];
+        if (r.votes) {
+            int best = 0;
+            float bv = row_base[u];
+            for (int q = 1; q < r.O; ++q) {
+                const float v = row_base[(size_t)q * r.U + u];
+                if (v > bv) { bv = v; best = q; }                   // first index wins a tie (np.argmax)
+            }
+            if (best == o) votes += c;
+        }
+    }
+    dsum[tid] = s;
+    vsum[tid] = votes;
+    if (tid < r.n_ranks) { prefix[tid] = 0u; krem[tid] = r.ranks[tid]; }
+    __syncthreads();
+    for (int d = PRED_THREADS / 2; d > 0; d >>= 1) {
+        if (tid < d) { dsum[tid] += dsum[tid + d]; vsum[tid] += vsum[tid + d]; }
+        __syncthreads();
+    }
+    if (tid == 0) {
+        r.mean[r.col0 + col] = dsum[0] / (double)r.M;
+        if (r.votes) r.votes[r.col0 + col] = vsum[0];
+    }
+    // exact order statistics: 4 passes of 8 bits over the keys, one LDS histogram of multiplicities per target rank
+    for (int pass = 0; pass < 4; ++pass) {
+        const int shift = 24 - 8 * pass;
+        for (int k = tid; k < r.n_ranks * 256; k += PRED_THREADS) hist[k >> 8][k & 255] = 0u;
+        __syncthreads();
+        for (int u = tid; u < r.U; u += PRED_THREADS) {
+            const unsigned key = pred_key(f[u]);
+            const unsigned c = (unsigned)r.cnt[u];
+            for (int t = 0; t < r.n_ranks; ++t)
+                if (pass == 0 || (key >> (shift + 8)) == (prefix[t] >> (shift + 8))) atomicAdd(&hist[t][(key >> shift) & 255u], c);
+        }
+        __syncthreads();
+        if (tid < r.n_ranks) {
+            long long k = krem[tid], cum = 0;
+            for (int b = 0; b < 256; ++b) {
+                const long long hcount = hist[tid][b];
+                if (k < cum + hcount) { prefix[tid] |= (unsigned)b << shift; krem[tid] = k - cum; break; }
+                cum += hcount;
+            }
+        }
+        __syncthreads();
+    }
+    if (tid < r.n_ranks) r.ostat[(size_t)tid * r.ncols_total + r.col0 + col] = pred_unkey(prefix[tid]);
+}
+
+#endif  // PTNN_SHAPE_TU

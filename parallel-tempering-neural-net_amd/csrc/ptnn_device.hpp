@@ -144,5 +144,6 @@ struct SegDyn {
 #include "ptnn_dev_wide.hpp"                 // wide nets (64 < H <= 512): sgd_sweep_wide, matrix-core forward, segment_wide_body, model_wide_kernel; then swap_block and the non-template kernels
 #include "ptnn_dev_tree.hpp"                 // prefetching tree schedule (segment_tree_body), with its own swap rounds inside a launch
 #include "ptnn_dev_kernels.hpp"              // model_kernel, persistent_loop, the __global__ segment kernels, the per-shape table
+#include "ptnn_dev_predict.hpp"              // posterior predictive: run-length pass over the selected rows, forward pass, per-column reduction
 
 }  // namespace ptnn

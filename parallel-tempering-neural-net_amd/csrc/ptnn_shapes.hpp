@@ -29,5 +29,6 @@ struct Shape {
     int loops;              // which kernels carry the interval loop of a persistent launch: bit 0 seg, bit 1 pack (wide: always; spec, tree: never)
     int split_ch, split_kr; // split-operand forward pass (SplitK<I>): 16-byte chunks per image row (0: not available for this n_in), fp32 k-steps
     seg_fn packm;           // 9 <= H <= 16: packed schedule over several CUs per replica
+    void (*predict_fwd)(const PredictFwd);   // posterior predictive: network outputs of distinct vectors x input rows (every H)
 };
 }  // namespace ptnn

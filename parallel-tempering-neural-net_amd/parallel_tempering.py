@@ -14,6 +14,7 @@ as a second kernel; this module only configures the run, fetches the traces and 
 import math
 import os
 import time
+from collections import namedtuple
 from concurrent.futures import ThreadPoolExecutor
 
 import numpy as np
@@ -55,6 +56,42 @@ def overlap_cuts(S, swap_interval, chunks):
     n_int = max(1, (S - 1) // si)
     K = max(1, min(int(chunks), n_int))
     return sorted({min(S - 1, si * max(1, round(n_int * (c + 1) / K))) for c in range(K - 1)} | {S - 1})
+
+
+def percentile_ranks(n, percentiles):
+    """np.percentile(..., method="linear") of n values reduced to ranks: for each percentile p the two 0-based ranks of the sorted
+    values it interpolates between and its weight gamma, with numpy 2.x's arithmetic (q = p / 100, virtual index (n - 1) q, floor,
+    clamped to [0, n - 1]).  -> list of (lo, hi, gamma)."""
+    out = []
+    for p in percentiles:
+        q = np.true_divide(np.float64(p), np.float64(100))
+        vi = np.float64(n - 1) * q
+        lo = np.floor(vi)
+        gamma = vi - lo
+        if vi >= n - 1:
+            lo_i = hi_i = n - 1
+        elif vi < 0:
+            lo_i = hi_i = 0
+        else:
+            lo_i, hi_i = int(lo), int(lo) + 1
+        out.append((lo_i, hi_i, gamma))
+    return out
+
+
+def lerp_percentile(a, b, gamma):
+    """numpy's _lerp of the order statistics a (rank lo) and b (rank hi), float64, including its t >= 0.5 branch."""
+    a = np.asarray(a, dtype=np.float64)
+    b = np.asarray(b, dtype=np.float64)
+    diff = np.subtract(b, a)
+    res = np.add(a, diff * gamma)
+    if gamma >= 0.5:
+        res = np.subtract(b, diff * (1 - gamma))
+    return res
+
+
+# posterior_predictive's result: mean [n_rows, n_out] float64; percentiles {p: [n_rows, n_out] float64}; vote [n_rows, n_out] and
+# pred_class [n_rows] (classification, else None); samples [n_samples, n_rows, n_out] float32 or None; n_samples; n_distinct
+Predictive = namedtuple("Predictive", "mean percentiles vote pred_class samples n_samples n_distinct")
 
 
 class ParallelTemperingBase:
@@ -126,6 +163,7 @@ class ParallelTemperingBase:
         self.timings = {}
         self._sampler = None
         self._w0 = None
+        self._finished = False
 
     # ------------------------------------------------------------------ ladder (REG:529-636)
     def default_beta_ladder(self, ndim, ntemps, Tmax):
@@ -190,6 +228,7 @@ class ParallelTemperingBase:
             self._sampler = _lib.Sampler(device_id=dev, n_replicas_local=self.num_chains, first_global_replica=0, **config)
         self._sampler.set_data(train, test)
         self._sampler.set_state(self._w0, self.temperatures)
+        self._finished = False
         if self.swap_rule == 1 or self.label_swap:
             self._sampler.set_ladder(self.temperatures)
         self._img = None
@@ -282,6 +321,7 @@ class ParallelTemperingBase:
                                           files_and_results_s=t5 - t2, overlapped=False))
 
     def _finish_run(self, out, timings):
+        self._finished = True
         nlaunch, kms = self._sampler.kernel_time()
         self.timings = dict(timings, segment_launches=nlaunch, segment_kernel_ms=kms,
                             samples_per_s=self.num_chains * (self.NumSamples - 1) / max(timings["sampling_s"], 1e-12))
@@ -451,6 +491,87 @@ class ParallelTemperingBase:
                     _lib.savetxt(*j)
         return (posterior, fx_train_all, fx_test_all, rmse_train, rmse_test, acc_train, acc_test, likelihood_vec,
                 accept_vec, accept)
+
+    # ------------------------------------------------------------------ posterior predictive (not in the reference's run_chains)
+    def posterior_predictive(self, x="test", *, burn_in=None, chains="all", thin=1, percentiles=(5, 95), weights=None,
+                             return_samples=False):
+        """Predictions with uncertainty from the sampled chains, computed on the GPU: what the reference's drafts derive from
+        fx_train_all / fx_test_all (fx_mu = fx.mean(axis=0), np.percentile bands; Misc_code/ldpt_classifier_multi.py:788-794).
+
+        The sample set is by default the columns of the posterior matrix run_chains() returns: every chain's trace rows from
+        int(NumSamples * burn_in) on.  `chains`: "all", "cold" (the temperature-1 chain) or a list of chain indices; `thin`: every
+        thin-th row.  `weights`: weight vectors instead of the trace -- [n, num_param] (e.g. run_chains()[0].T), or a pair
+        (vectors, integer multiplicities); works whenever the handle exists.  `x`: "train", "test" or an array whose first n_in
+        columns are the inputs.  Percentiles follow np.percentile(method="linear") exactly: the device returns the exact order
+        statistics, the interpolation is numpy's arithmetic.  -> Predictive(mean, percentiles, vote, pred_class, samples,
+        n_samples, n_distinct); outputs are [n_rows, n_out], samples [n_samples, n_rows, n_out] in chain-major order."""
+        if self._sampler is None:
+            raise ValueError("posterior_predictive needs the chains' device handle: call initialize_chains() and run_chains() first")
+        if not isinstance(self._sampler, _lib.Sampler):
+            raise ValueError("posterior_predictive runs on one GPU: a ladder sharded over several devices is not supported")
+        I = int(self.topology[0])
+        if isinstance(x, str):
+            if x not in ("train", "test"):
+                raise ValueError(f"x must be 'train', 'test' or an array, not {x!r}")
+            xs = x
+        else:
+            xa = np.asarray(x)
+            if xa.ndim != 2 or xa.shape[1] < I:
+                raise ValueError(f"x must be 2-D with at least n_in = {I} columns, got shape {xa.shape}")
+            xs = np.ascontiguousarray(xa[:, :I], dtype=np.float32)
+        pcts = list(percentiles)
+        if any(not (0 <= p <= 100) for p in pcts):
+            raise ValueError(f"percentiles must lie in [0, 100], got {pcts}")
+        kw = {}
+        if weights is not None:
+            mult = None
+            if isinstance(weights, tuple):
+                weights, mult = weights
+            w = np.asarray(weights)
+            P = self.num_param
+            if w.ndim != 2 or P not in w.shape:
+                raise ValueError(f"weights must be [n, {P}] vectors (or their transpose), got shape {w.shape}")
+            if w.shape[1] != P:
+                w = w.T
+            kw = dict(w=w, multiplicity=mult)
+            M = int(np.sum(np.asarray(mult, dtype=np.int64))) if mult is not None else w.shape[0]
+        else:
+            S = self.NumSamples
+            if self.label_swap:
+                raise ValueError("label_swap=True: trace rows are kept per chain slot, not per temperature; pass weights=")
+            if 0 < self.trace_capacity < S:
+                raise ValueError(f"trace_capacity = {self.trace_capacity} < NumSamples = {S}: the rows have been streamed off "
+                                 f"the device; pass weights=")
+            if not self._finished:
+                raise ValueError("no finished run_chains() on this object: the trace is incomplete; pass weights=")
+            b = self.burn_in if burn_in is None else burn_in
+            step0 = int(S * b)
+            if chains == "all":
+                reps = None
+            elif chains == "cold":
+                reps = [int(np.argmin(self.temperatures))]
+            else:
+                reps = [int(c) for c in chains]
+                if not reps or min(reps) < 0 or max(reps) >= self.num_chains:
+                    raise ValueError(f"chains {chains!r}: indices must lie in [0, {self.num_chains})")
+            kw = dict(replicas=reps, step0=step0, nsteps=S - step0, thin=int(thin))
+            nrep = self.num_chains if reps is None else len(reps)
+            M = nrep * max(0, -(-(S - step0) // max(1, int(thin))))
+        if M < 1:
+            raise ValueError("the selection holds no sample")
+        spots = percentile_ranks(M, pcts)
+        ranks = sorted({r for lo, hi, _ in spots for r in (lo, hi)})
+        if len(ranks) > _lib.PREDICT_MAX_RANKS:
+            raise ValueError(f"{len(pcts)} percentiles need {len(ranks)} order statistics: at most {_lib.PREDICT_MAX_RANKS} per call")
+        cls = self.task == TASK_CLS
+        out = self._sampler.predict(xs, ranks=ranks, vote=cls, samples=bool(return_samples), **kw)
+        pos = {r: k for k, r in enumerate(ranks)}
+        os_ = out["order_stats"]
+        bands = {p: lerp_percentile(os_[pos[lo]], os_[pos[hi]], g) for p, (lo, hi, g) in zip(pcts, spots)}
+        mean = out["mean"]
+        return Predictive(mean=mean, percentiles=bands, vote=out["vote"] if cls else None,
+                          pred_class=np.argmax(mean, axis=1) if cls else None, samples=out["samples"],
+                          n_samples=out["n_samples"], n_distinct=out["n_distinct"])
 
     def make_directory(self, directory):
         if not os.path.exists(directory):
