@@ -70,34 +70,60 @@ const Shape* find_shape(int task, int I, int O) {
 
 inline int round_up4(int v) { return (v + 3) & ~3; }
 
+constexpr size_t LDS_MAX = 160 * 1024;          // LDS of one work-group
+constexpr size_t LDS_CEILING = 152 * 1024;      // largest dynamic-LDS ceiling the runtime accepts (just below LDS_MAX it refuses)
+
+enum SegKind { SEG_COOP, SEG_SPEC, SEG_PACK, SEG_PACKM, SEG_TREE, SEG_WIDE, SEG_WIDE_RES, SEG_KINDS };   // the segment kernels
+
+struct SegKernel {
+    const char* name;       // ptnn_describe's "kernel"
+    const char* label;      // ... and "schedule" (wide nets over several work-groups: "speculative-wide")
+    seg_fn Shape::*fn;
+    bool per_group;         // the grid has `groups` work-groups per replica (else one)
+};
+const SegKernel g_seg[SEG_KINDS] = {
+    {"segment_kernel", "cooperative", &Shape::seg, false},
+    {"segment_spec_kernel", "speculative", &Shape::spec, true},
+    {"segment_pack_kernel", "packed-speculative", &Shape::pack, false},             // one CU per replica
+    {"segment_packm_kernel", "packed-speculative", &Shape::packm, true},
+    {"segment_tree_kernel", "prefetching-tree", &Shape::tree, true},
+    {"segment_wide_kernel", "cooperative-wide", &Shape::seg_wide, true},
+    {"segment_wide_res_kernel", "cooperative-wide", &Shape::seg_wide_res, true},
+};
+
+// What ptnn_set_data decided: the segment kernel, its launch shape and the buffers it needs (plan_launch)
+struct LaunchPlan {
+    SegKind kind = SEG_COOP;
+    int threads = 64, model_threads = 64;       // segment kernel; model_kernel / model_wide_kernel (ptnn_evaluate and friends)
+    size_t seg_lds = 0, model_lds = 0;
+    int groups = 1;                 // work-groups (CUs) per replica; tree: 2^depth - 1
+    int pk_nred = 3;                // packed schedules: lane-group width 2^3 (H <= 8) or 2^4 hidden units
+    int fw_mfma = 0;                // forward pass on the matrix cores: 1 exact fp32, 2 split bf16 operands
+    bool xy_global = false;         // split forward pass: no room for the row-major data image in LDS, its rare readers go to global memory
+    bool tree_ahead = false;        // tree: room in LDS for two sets of tapes
+    bool compact = false;           // wide nets with all trace rows resident: rejected steps record a row index, no pos_w row
+    int blocks_per_cu = 0;          // occupancy of the segment kernel as the runtime reports it (0 = not queried)
+    bool persistent = false;        // all work-groups of the grid are resident: ptnn_run queues ONE launch, swap rounds inside
+    // bytes of the buffers the plan needs (0 = none): multi-group exchange slots / rows / verdicts, in-launch swap granules, wide scratch
+    size_t xslots = 0, xw = 0, xverdict = 0, xswap = 0, wide_scratch = 0;
+    bool wide() const { return kind == SEG_WIDE || kind == SEG_WIDE_RES; }
+    int grid(int replicas) const { return replicas * (g_seg[kind].per_group ? groups : 1); }
+};
+
 }  // namespace
 
 struct ptnn_handle {
     ptnn_config cfg{};
     const Shape* shape = nullptr;
     hipStream_t stream = nullptr;
-    int P = 0, PS = 0, PW = 0, IPY = 0, FWS = 0, Ntr = 0, Nte = 0, nthreads = 64;
-    size_t seg_lds = 0, model_lds = 0;
-    int model_threads = 64;
-    bool speculative = false;
-    bool wide = false;              // 64 < H: vectors in HBM, one thread per hidden unit
-    bool wide_res = false;          // ... with the state and the proposal resident in LDS (matrix-core layout, 2 vectors fit)
-    bool compact = false;           // wide nets with all trace rows resident: rejected steps record a row index, no pos_w row
-    bool persistent = false;        // all work-groups of the grid are resident: ptnn_run queues ONE launch, swap rounds inside
+    int P = 0, PS = 0, PW = 0, IPY = 0, FWS = 0, Ntr = 0, Nte = 0;
+    LaunchPlan plan;
     unsigned* d_barrier = nullptr;  // grid barrier of the persistent launch: one slot per work-group
     int barrier_slots = 0;
-    bool packed = false;            // H <= 16: packed speculative schedule on one CU
-    bool tree = false;              // prefetching tree schedule: groups = 2^depth - 1 work-groups per replica
-    bool tree_ahead = false;        // ... with room in LDS for two sets of tapes
-    int pk_nred = 3;                // its lane-group width: 2^3 (H <= 8) or 2^4 hidden units
     float* d_wide_scratch = nullptr;
     float* d_xt = nullptr;          // transposed data image for the MFMA forward pass
-    void* d_xs = nullptr;           // wide nets: the data image split into three bf16 levels (split-operand forward pass)
+    uint16_t* d_xs = nullptr;       // wide nets: the data image split into three bf16 levels (split-operand forward pass)
     int Npad = 0;
-    int fw_mfma = 0;                // cooperative / tree schedule: forward pass on the matrix cores (24 <= H <= 64, I >= 6): 1 exact fp32, 2 split bf16 operands (cooperative only)
-    bool xy_global = false;         // split forward pass: no room for the row-major data image in LDS, its rare readers go to global memory
-    int groups = 1;                 // work-groups (CUs) per replica in the speculative schedule
-    int blocks_per_cu = 0;          // occupancy of the segment kernel as the runtime reports it (0 = not queried)
     unsigned epoch_base = 0;
     int num_cus = 0;
     unsigned long long *d_xslots = nullptr, *d_xw = nullptr, *d_xverdict = nullptr, *d_xswap = nullptr;
@@ -169,21 +195,19 @@ struct ptnn_handle {
         p.L_handoff = d_L_handoff; p.L_final = d_L_final;
         p.L_raw = (cfg.swap_rule == 1) ? d_L_raw : nullptr; p.prior_post = d_prior_post;
         p.tr_pos_w = d_pos_w; p.tr_scal = d_scal; p.PW = PW;
-        p.G = groups; p.epoch_base = epoch_base; p.xslots = d_xslots; p.xw = d_xw; p.xverdict = d_xverdict; p.error_flag = d_error; p.stamps = d_stamps; p.wide_scratch = d_wide_scratch; p.noise_shared = cfg.shared_noise ? 1 : 0; p.pk_nred = pk_nred; p.xt = d_xt; p.xs = reinterpret_cast<const uint4*>(d_xs); p.Npad = Npad; p.fw_mfma = fw_mfma; p.xy_global = xy_global ? 1 : 0; p.forward_bf16 = cfg.forward_bf16 == 1 ? 1 : 0; p.tree_ahead = tree_ahead ? 1 : 0; p.compact = compact ? 1 : 0;
+        p.G = plan.groups; p.epoch_base = epoch_base; p.xslots = d_xslots; p.xw = d_xw; p.xverdict = d_xverdict; p.error_flag = d_error; p.stamps = d_stamps; p.wide_scratch = d_wide_scratch; p.noise_shared = cfg.shared_noise ? 1 : 0; p.pk_nred = plan.pk_nred; p.xt = d_xt; p.xs = reinterpret_cast<const uint4*>(d_xs); p.Npad = Npad; p.fw_mfma = plan.fw_mfma; p.xy_global = plan.xy_global ? 1 : 0; p.forward_bf16 = cfg.forward_bf16 == 1 ? 1 : 0; p.tree_ahead = plan.tree_ahead ? 1 : 0; p.compact = plan.compact ? 1 : 0;
         {
             // records through the XCD's L2: asked for only where xcd_block (ptnn_device.hpp) can put a replica's work-groups on one XCD --
             // a grid of 8 k blocks with k a multiple of the groups per replica; elsewhere the in-kernel handshake could only time out
-            const char* e = std::getenv("PTNN_XCD_GRANULES");
-            const int grid_ = cfg.n_replicas_local * groups;
-            const bool can = groups > 1 && (grid_ & 7) == 0 && ((grid_ >> 3) % groups) == 0;
-            p.xcd_granules = ((e && e[0] == '0') || cfg.shared_device || !can) ? 0 : 1;
+            const int grid_ = cfg.n_replicas_local * plan.groups;
+            const bool can = plan.groups > 1 && (grid_ & 7) == 0 && ((grid_ >> 3) % plan.groups) == 0;
+            p.xcd_granules = (cfg.shared_device || !can) ? 0 : 1;
         }
         p.xswap = d_xswap;
         // wide nets over several work-groups: a window of 16 steps lets the groups balance Langevin (10 units) against random-walk
         // (1) steps (measured on config 5: 8 steps 0.680 M, 12: 0.692 M, 16: 0.698 M samples/s; wide nets accept 1 - 5 %, so little of
         // a window is thrown away); random-walk-only runs have nothing to balance and a longer window only wastes what follows an accept
-        p.wide_window = cfg.use_langevin ? 16 : groups;
-        if (const char* e = std::getenv("PTNN_WIDE_WINDOW")) p.wide_window = std::atoi(e);   // experiments
+        p.wide_window = cfg.use_langevin ? 16 : plan.groups;
         return p;
     }
 };
@@ -200,14 +224,7 @@ inline bool swap_trigger(const ptnn_config& c, int i) {
     return ((i + 1) % c.swap_interval) == 0;
 }
 
-// the segment kernel the schedule resolved to
-seg_fn segment_function(const ptnn_handle* h) {
-    const Shape* sh = h->shape;
-    if (h->wide) return h->wide_res ? sh->seg_wide_res : sh->seg_wide;
-    if (h->tree) return sh->tree;
-    if (h->packed) return h->groups > 1 ? sh->packm : sh->pack;
-    return h->speculative ? sh->spec : sh->seg;
-}
+seg_fn segment_function(const Shape* sh, SegKind k) { return sh->*g_seg[k].fn; }
 
 void collect_timing(ptnn_handle* h) {
     for (size_t k = 0; k < h->timing_used; ++k) {
@@ -251,7 +268,7 @@ int launch_segment(ptnn_handle* h, int begin, int end, bool swap_inside = false,
     PersistParams pp{};
     pp.end = end; pp.swap_inside = swap_inside ? 1 : 0; pp.task = h->cfg.task; pp.si = h->cfg.swap_interval;
     pp.round0 = h->rounds_done; pp.flip0 = h->flip; pp.lflip0 = h->lflip;
-    const int grid = h->cfg.n_replicas_local * ((h->speculative || h->tree || h->wide) ? h->groups : 1);   // packed: groups > 1 only for the multi-CU variant
+    const int grid = h->plan.grid(h->cfg.n_replicas_local);
     pp.nblocks = grid; pp.barrier = h->d_barrier;
     for (int b = 0; b < 2; ++b) {
         pp.state[b] = h->d_state[b]; pp.gd[b] = h->d_gd_w[b]; pp.gd_valid[b] = h->d_gd_valid[b];
@@ -286,7 +303,7 @@ int launch_segment(ptnn_handle* h, int begin, int end, bool swap_inside = false,
         ev = &h->timing[h->timing_used++];
         HIP_TRY(hipEventRecord(ev->first, h->stream));
     }
-    hipLaunchKernelGGL(segment_function(h), dim3(grid), dim3(h->nthreads), h->seg_lds, h->stream, p, pp, begin);
+    hipLaunchKernelGGL(segment_function(h->shape, h->plan.kind), dim3(grid), dim3(h->plan.threads), h->plan.seg_lds, h->stream, p, pp, begin);
     h->epoch_base += (unsigned)(end - begin) + 1u + (swap_inside ? (unsigned)((end - begin) / h->cfg.swap_interval + 2) : 0u);   // granule tags never repeat across launches
     HIP_TRY(hipGetLastError());
     if (ev) HIP_TRY(hipEventRecord(ev->second, h->stream));
@@ -380,58 +397,386 @@ int finish_stream(ptnn_handle* h) {
     return 0;
 }
 
-// One launch per run needs every work-group of the grid resident at once (they meet at grid barriers) and room in LDS for the
-// cascade of a swap round.  Decided per handle once the schedule is known.  Taken by default where it is measured to pay: one
-// work-group per replica (packed, cooperative, one-group wide: one barrier per round; Sunspot + 2.6 %, Ionosphere + 0.2 %); with
-// several work-groups per replica a round needs a second rendezvous and the launch boundary it replaces is cheaper (Iris tree
-// - 5 %, Mackey-Glass - 2 %, profiles/r03_persistent_ab.json).  $PTNN_PERSISTENT=0: never; =1: wherever resident.
+// wide nets: the split-operand forward pass (SplitK, eval_rows_mfma_wsplit) unless the caller asked for bf16 or exact fp32 operands
+bool wide_split(const ptnn_handle& h) {
+    const int H = h.cfg.n_hidden;
+    return H > WAVE && H % 32 == 0 && h.shape->split_ch > 0 && h.cfg.forward_bf16 == 0;
+}
+
+// LDS of the split-operand images of the cooperative / tree forward pass
+size_t split_lds_bytes(const ptnn_handle& h, int Npad) {
+    return (split_lds_floats(h.shape->split_ch, h.shape->split_kr, h.cfg.n_out, h.cfg.n_hidden, Npad) + 4) * sizeof(float);
+}
+
+// exchange buffers of the multi-group schedules (segment_spec_body's layout): slots, rows of `row_groups` x 2 vectors, verdicts
+void plan_exchange(const ptnn_handle& h, int row_groups, LaunchPlan& plan) {
+    const size_t Rl = h.cfg.n_replicas_local, g = sizeof(unsigned long long);
+    plan.xslots = Rl * 2 * MAX_SLOTS * SL_COUNT * g;
+    plan.xw = Rl * 2 * row_groups * 2 * h.PS * g;
+    plan.xverdict = Rl * 2 * MAX_SLOTS * g;
+}
+
 // Granules of the swap rounds a multi-group launch runs by itself (ptnn_device.hpp: segment_tree_body, segment_pack_body<MULTI>): two
 // parities of swap_xchg_granules(R, row); only when the whole ladder is on this handle (a sharded ladder exchanges through its communicator)
-int alloc_swap_granules(ptnn_handle* h, int row) {
-    if (h->d_xswap) { HIP_TRY(hipFree(h->d_xswap)); h->d_xswap = nullptr; }
-    if (h->cfg.n_replicas_local != h->cfg.n_replicas_global) return 0;
-    const size_t n = 2 * swap_xchg_granules(h->cfg.n_replicas_global, row);
-    HIP_TRY(hipMalloc(&h->d_xswap, n * sizeof(unsigned long long)));
-    HIP_TRY(hipMemset(h->d_xswap, 0, n * sizeof(unsigned long long)));
+size_t swap_granule_bytes(const ptnn_handle& h, int row) {
+    if (h.cfg.n_replicas_local != h.cfg.n_replicas_global) return 0;
+    return 2 * swap_xchg_granules(h.cfg.n_replicas_global, row) * sizeof(unsigned long long);
+}
+
+// Wide net (64 < H): one thread per hidden unit, vectors in HBM, only the packed forward image + scratch in LDS.  Matrix-core layout
+// (H a multiple of 32): the state vector joins the proposal in LDS when both fit.
+int plan_wide(const ptnn_handle& h, LaunchPlan& plan) {
+    const int H = h.cfg.n_hidden, Rl = h.cfg.n_replicas_local;
+    plan.fw_mfma = wide_split(h) ? 2 : 0;
+    const size_t lds_res = wide_lds_floats(H, h.FWS, h.cfg.n_out, h.PS, true) * sizeof(float);
+    plan.kind = (H % 32 == 0 && lds_res <= LDS_CEILING) ? SEG_WIDE_RES : SEG_WIDE;
+    const size_t lds = plan.kind == SEG_WIDE_RES ? lds_res : wide_lds_floats(H, h.FWS, h.cfg.n_out, h.PS) * sizeof(float);
+    if (lds > LDS_MAX) return fail(-3, "wide net needs %zu B of LDS (> 160 KiB)", lds);
+    if (h.cfg.schedule == PTNN_SCHED_SPECULATIVE || h.cfg.schedule == PTNN_SCHED_PACKED || h.cfg.schedule == PTNN_SCHED_TREE)
+        return fail(-3, "schedules 2-4 are built for n_hidden <= 64; a wide net speculates over work-groups through groups_per_replica");
+    plan.compact = h.cap == h.cfg.n_samples;
+    plan.threads = plan.model_threads = ((H + WAVE - 1) / WAVE) * WAVE;
+    plan.seg_lds = plan.model_lds = lds;
+    // Speculation over work-groups (one per CU): group g computes step i + g; all Rl x G groups must be resident (they wait for each
+    // other's verdicts).  groups_per_replica 1, 2 or 4; 0 = as many of 4, 2 as are resident, else 1.
+    const void* fn = reinterpret_cast<const void*>(segment_function(h.shape, plan.kind));
+    if (int rc = raise_lds_limit(fn, lds)) return rc;
+    const int want = h.cfg.groups_per_replica;
+    if (want != 0 && want != 1 && want != 2 && want != 4) return fail(-1, "wide nets: groups_per_replica must be 0 (auto), 1, 2 or 4");
+    int per_cu = 0;
+    HIP_TRY(hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, fn, plan.threads, lds));
+    plan.blocks_per_cu = per_cu;
+    const long long cap = (long long)per_cu * h.num_cus;
+    if (want > 1) {
+        if ((long long)Rl * want > cap)
+            return fail(-3, "%d replicas x %d work-groups cannot all be resident: %d work-group(s) of %d threads with %zu B of LDS fit "
+                            "on each of the %d CUs", Rl, want, per_cu, plan.threads, lds, h.num_cus);
+        plan.groups = want;
+    } else if (want == 0 && !h.cfg.shared_device) {     // (work-groups that wait for each other want the GPU to themselves)
+        if ((long long)Rl * 4 <= cap) plan.groups = 4;
+        else if ((long long)Rl * 2 <= cap) plan.groups = 2;
+    }
+    plan.wide_scratch = (size_t)Rl * plan.groups * 5 * h.PS * sizeof(float);
+    if (plan.groups > 1) plan_exchange(h, plan.groups, plan);
     return 0;
 }
 
-int resolve_persistent(ptnn_handle* h) {
-    h->persistent = false;
+// Packed speculative: all slots of a round on one CU, the SGD epochs of the slots in the lane groups of two waves: 16 slots in groups
+// of 8 lanes for n_hidden <= 8, 8 slots in groups of 16 lanes for n_hidden <= 16.  Taken automatically for Langevin runs of such nets
+// (faster than 4 CUs per replica on a quarter of the GPU, and more than twice the throughput once there are more replicas than CUs);
+// random-walk-only runs have no epochs to pack and keep the multi-CU speculative schedule.  Leaves the plan alone when not taken.
+int plan_packed(const ptnn_handle& h, int Nall, int sched, LaunchPlan& plan) {
+    const ptnn_config& c = h.cfg;
+    const int H = c.n_hidden, Rl = c.n_replicas_local;
+    const size_t pk = pack_lds_floats(Nall, h.IPY, h.PS, H, h.FWS, pack_slots(plan.pk_nred)) * sizeof(float);
+    const bool fits = H <= 16 && pk <= LDS_MAX;
+    if (sched == PTNN_SCHED_PACKED && !fits)
+        return fail(-3, "the packed schedule needs n_hidden <= 16 and %zu B of LDS <= 160 KiB", pk);
+    // 16-lane groups give 8 slots per round on one CU.  With CUs to spare the packed round runs on 2 or 4 CUs per replica (16 / 32
+    // slots per round, segment_packm_kernel): Mackey-Glass 4-10-1, 64 replicas needs 18.7 / 13.6 / 11.6 rounds per swap interval
+    // with 8 / 16 / 32 slots (profiles/r03_window_sim.jsonl) and a packed round is shorter than the multi-CU speculative one (the
+    // forward passes run beside the epochs).  groups_per_replica = 1, 2, 4 decides otherwise.
+    int G = 1;
+    const size_t pkm = pack_multi_lds_floats(Nall, h.IPY, h.PS, H, h.FWS, pack_slots(plan.pk_nred)) * sizeof(float);
+    if (fits && pkm <= LDS_MAX && c.use_langevin && !c.shared_device && (sched == PTNN_SCHED_PACKED || c.schedule == PTNN_SCHED_AUTO) &&
+        c.waves_per_replica == 0) {
+        const int want = c.groups_per_replica;
+        if (want == 2 || want == 4) G = want;                       // (8-lane groups: on request only -- 16 slots on one CU already)
+        else if (want == 0 && plan.pk_nred == 4) { if (Rl * 4 <= h.num_cus) G = 4; else if (Rl * 2 <= h.num_cus) G = 2; }
+    }
+    const bool pays = (H <= 8) || G > 1 || Rl * 4 > h.num_cus;
+    if (sched != PTNN_SCHED_PACKED &&
+        !(c.schedule == PTNN_SCHED_AUTO && sched == PTNN_SCHED_SPECULATIVE && fits && pays && c.use_langevin && c.waves_per_replica == 0 &&
+          (c.groups_per_replica == 0 || G > 1)))
+        return 0;
+    plan.kind = G > 1 ? SEG_PACKM : SEG_PACK;
+    plan.groups = G;
+    // eight waves (forward passes two to a SIMD) while every replica has a CU to itself, four beyond that; an explicit
+    // waves_per_replica of 4 or 8 decides otherwise
+    const int pkw = (c.waves_per_replica == 4 || c.waves_per_replica == 8) ? c.waves_per_replica : (Rl <= h.num_cus ? PK_WAVES : 4);
+    plan.threads = (G > 1 ? PK_WAVES : pkw) * WAVE;
+    plan.seg_lds = G > 1 ? pkm : pk;
+    if (G > 1) {
+        plan_exchange(h, G, plan);
+        plan.xswap = swap_granule_bytes(h, 2 * h.PS + 8);         // in-launch swap rounds: state + cached gradient + flag
+    }
+    return 0;
+}
+
+// Speculative over work-groups.  Two waves on one SIMD slow each other ~1.65x (the SGD sweep is VALU-issue bound), so speculation
+// depth comes from more CUs first: G work-groups of 4 waves (one per SIMD) per replica while R*G <= number of CUs, and 8 waves on a
+// single CU otherwise.  Leaves the plan alone (the cooperative schedule) when the automatic choice finds no room in LDS.
+int plan_speculative(const ptnn_handle& h, int Nall, LaunchPlan& plan) {
+    const ptnn_config& c = h.cfg;
+    const int Rl = c.n_replicas_local, nw = c.waves_per_replica;
+    int G = 1;
+    if (c.groups_per_replica > 0) G = c.groups_per_replica;
+    else if (!c.shared_device) { while (G < 4 && Rl * (G * 2) <= h.num_cus) G *= 2; }
+    if (G != 1 && G != 2 && G != 4 && G != 8) return fail(-1, "groups_per_replica must be 0 (auto), 1, 2, 4 or 8");
+    auto lds = [&](int k) { return spec_lds_floats(Nall, h.IPY, h.PS, c.n_hidden, h.FWS, k, G) * sizeof(float); };
+    int k = nw ? nw : (G > 1 ? 4 : 8);
+    while (k > 1 && lds(k) > LDS_MAX) k >>= 1;
+    if (nw && k != nw) {
+        if (c.schedule == PTNN_SCHED_AUTO) k = 0;      // auto: fall back to the cooperative schedule
+        else return fail(-3, "speculative schedule with %d waves needs more than 160 KiB of LDS", nw);
+    }
+    if (k * G > MAX_SLOTS) return fail(-1, "waves x groups must not exceed %d", MAX_SLOTS);
+    if (k == 0 || lds(k) > LDS_MAX) return 0;
+    plan.kind = SEG_SPEC; plan.threads = k * 64; plan.groups = G; plan.seg_lds = lds(k);
+    if (G > 1) {
+        // The work-groups of one replica wait for each other inside the kernel, so all Rl x G of them must be resident at once: ask
+        // the runtime how many blocks of THIS kernel (its registers, this LDS size, this block size) fit on a CU instead of guessing,
+        // and refuse the configuration otherwise (a non-resident partner would be a bounded spin and an error from ptnn_sync).  The
+        // count is for a GPU this handle has to itself: other handles or processes on the same device take CUs this query does not see.
+        const void* fn = reinterpret_cast<const void*>(h.shape->spec);
+        if (int rc = raise_lds_limit(fn, plan.seg_lds)) return rc;
+        int per_cu = 0;
+        HIP_TRY(hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, fn, plan.threads, plan.seg_lds));
+        plan.blocks_per_cu = per_cu;
+        if ((long long)Rl * G > (long long)per_cu * h.num_cus)
+            return fail(-3, "%d replicas x %d work-groups cannot all be resident: %d work-group(s) of %d threads with %zu B "
+                            "of LDS fit on each of the %d CUs; use fewer groups_per_replica or the packed schedule",
+                        Rl, G, per_cu, plan.threads, plan.seg_lds, h.num_cus);
+        plan_exchange(h, MAX_SLOTS, plan);
+    }
+    return 0;
+}
+
+// Cooperative: one work-group per replica, the forward pass row-parallel over its waves
+void plan_cooperative(const ptnn_handle& h, int Nall, int Npad, LaunchPlan& plan) {
+    const ptnn_config& c = h.cfg;
+    const int I = c.n_in, H = c.n_hidden, lg = c.use_langevin;
+    plan.threads = c.waves_per_replica ? c.waves_per_replica * 64 : plan.model_threads;
+    const size_t seg_lds = lds_floats(Nall, h.IPY, h.PS, H, h.FWS, lg != 0) * sizeof(float);
+    plan.seg_lds = seg_lds;
+    // a hidden layer that fills most of a 32-unit tile and at least three k-steps: forward pass on the matrix cores
+    // (the VALU pass re-reads the weights from LDS with broadcast reads and is bound by the LDS pipe at this size)
+    const size_t extra = (mfma_coop_lds_floats(I, c.n_out, H, Npad) + 4) * sizeof(float);
+    if (!(H >= 24 && I >= 6 && seg_lds + extra <= LDS_MAX)) return;
+    plan.fw_mfma = 1;
+    plan.seg_lds = seg_lds + extra;
+    // Split bf16 operands (ptnn_device.hpp, SplitK): the default where the matrix cores are used, unless the caller asked for
+    // the exact fp32 instruction (forward_bf16 = 2: bit-identical to the VALU schedules) or the images do not fit.  They take
+    // more LDS than the transposed fp32 image; a random-walk launch may give up the row-major data image for them (its only
+    // readers left are the chain start and the SGD epochs of a Langevin launch, which therefore keeps it).
+    if (h.shape->split_ch <= 0 || c.forward_bf16 == 2) return;
+    const size_t with_xy = seg_lds + split_lds_bytes(h, Npad);
+    const size_t without_xy = lds_floats(Nall, h.IPY, h.PS, H, h.FWS, lg != 0, false) * sizeof(float) + split_lds_bytes(h, Npad);
+    if (with_xy <= LDS_MAX) { plan.fw_mfma = 2; plan.xy_global = false; plan.seg_lds = with_xy; }
+    else if (!lg && without_xy <= LDS_MAX) { plan.fw_mfma = 2; plan.xy_global = true; plan.seg_lds = without_xy; }
+}
+
+// Prefetching tree: 2^D - 1 work-groups per replica, all of them resident (they wait for each other's records).  Explicit:
+// groups_per_replica = 3, 7, 15 or 31 (0: deepest that fits); auto: deepest of 31 / 15 / 7 / 3 that fits (31 nodes: five steps per
+// round; Iris 16 x 31 = 496 work-groups, two to a CU: 11.8 M against 11.4 M samples/s with 15), none -> the plan stays cooperative.
+int plan_tree(const ptnn_handle& h, int Nall, int Npad, bool explicit_tree, LaunchPlan& plan) {
+    const ptnn_config& c = h.cfg;
+    const int I = c.n_in, H = c.n_hidden, Rl = c.n_replicas_local, want = c.groups_per_replica;
+    if (explicit_tree && want != 0 && want != 3 && want != 7 && want != 15 && want != 31)
+        return fail(-1, "tree schedule: groups_per_replica must be 0 (auto), 3, 7, 15 or 31");
+    const int threads = c.waves_per_replica ? c.waves_per_replica * 64 : plan.model_threads;
+    // same forward pass as the cooperative schedule would run (matrix cores or not): a deeper tree that has no room for the
+    // transposed data image is not taken
+    const size_t mfma_lds = (mfma_coop_lds_floats(I, c.n_out, H, Npad) + 4) * sizeof(float);
+    const bool mfma = H >= 24 && I >= 6 && lds_floats(Nall, h.IPY, h.PS, H, h.FWS, false) * sizeof(float) + mfma_lds <= LDS_MAX;
+    // the split-operand forward pass of the cooperative kernel (same arithmetic: the tree commits the cooperative chain bit for
+    // bit either way), when its images fit next to the shallowest tree
+    const bool split = mfma && h.shape->split_ch > 0 && c.forward_bf16 != 2 &&
+                       tree_lds_floats(Nall, h.IPY, h.PS, H, h.FWS, 2, false, true) * sizeof(float) + split_lds_bytes(h, Npad) <= LDS_CEILING;
+    const size_t extra = !mfma ? 0 : split ? split_lds_bytes(h, Npad) : mfma_lds;
+    const void* fn = reinterpret_cast<const void*>(h.shape->tree);
+    for (int G = (explicit_tree && want) ? want : TREE_MAX_NODES; G >= 3; G = (G - 1) / 2) {
+        const int Dp = tree_depth(G);
+        // two sets of tapes (the next round's drawn while the records travel) when they fit
+        const bool ahead = tree_lds_floats(Nall, h.IPY, h.PS, H, h.FWS, Dp, true, mfma) * sizeof(float) + extra <= LDS_CEILING;
+        const size_t lds = tree_lds_floats(Nall, h.IPY, h.PS, H, h.FWS, Dp, ahead, mfma) * sizeof(float) + extra;
+        // (the runtime may refuse a dynamic-LDS ceiling just below 160 KiB: such a depth does not fit either)
+        if (lds <= LDS_MAX && raise_lds_limit(fn, lds) == 0) {   // (raise_lds_limit clears a refused ceiling's error)
+            int per_cu = 0;
+            HIP_TRY(hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, fn, threads, lds));
+            if ((long long)Rl * G <= (long long)per_cu * h.num_cus) {
+                plan.kind = SEG_TREE; plan.threads = threads; plan.groups = G; plan.seg_lds = lds; plan.blocks_per_cu = per_cu;
+                plan.fw_mfma = mfma ? (split ? 2 : 1) : 0; plan.xy_global = false; plan.tree_ahead = ahead;
+                plan.xslots = (size_t)Rl * 2 * (TREE_MAX_NODES + 1) * TREE_REC * sizeof(unsigned long long);
+                plan.xswap = swap_granule_bytes(h, h.PS);        // the in-launch swap rounds
+                return 0;
+            }
+        }
+        if (explicit_tree && want) break;
+    }
+    if (explicit_tree)
+        return fail(-3, "tree schedule: %d replicas x %d work-groups of %d threads cannot all be resident on %d CUs (or need more than "
+                        "160 KiB of LDS)", Rl, want ? want : 3, threads, h.num_cus);
+    return 0;
+}
+
+// One launch per run needs every work-group of the grid resident at once (they meet at grid barriers) and room in LDS for the
+// cascade of a swap round.  Taken by default where it is measured to pay: one work-group per replica (packed, cooperative,
+// one-group wide: one barrier per round; Sunspot + 2.6 %, Ionosphere + 0.2 %); with several work-groups per replica a round needs a
+// second rendezvous and the launch boundary it replaces is cheaper (Iris tree - 5 %, Mackey-Glass - 2 %,
+// profiles/r03_persistent_ab.json).  $PTNN_PERSISTENT=0: never; =1: wherever resident.
+int plan_persistent(const ptnn_handle& h, LaunchPlan& plan) {
+    const ptnn_config& c = h.cfg;
     const char* e = std::getenv("PTNN_PERSISTENT");
-    if ((e && e[0] == '0') || h->cfg.shared_device) return 0;     // grid barriers want every work-group resident: not on a shared GPU
-    const int G = ((h->speculative || h->tree || h->wide) ? h->groups : 1);
+    if ((e && e[0] == '0') || c.shared_device) return 0;     // grid barriers want every work-group resident: not on a shared GPU
+    const bool forced = e && e[0] == '1';
+    const int R = c.n_replicas_global;
     // The prefetching tree runs its swap rounds inside the launch by itself (segment_tree_body: the root groups exchange scalars and
     // state rows as granules, no grid barrier): the reference's cascade without label swapping, a ladder that is not sharded, and as
     // many replicas as the cascade has room for in the record area of LDS.  One launch per run then, unless $PTNN_PERSISTENT=0.
-    const bool whole = h->cfg.swap_rule == 0 && !h->cfg.label_swap && h->d_xswap != nullptr && h->cfg.n_replicas_local == h->cfg.n_replicas_global;
-    const bool tree_inside = h->tree && whole && h->cfg.n_replicas_global <= TREE_PERSIST_MAX_R;
+    const bool whole = c.swap_rule == 0 && !c.label_swap && plan.xswap > 0 && c.n_replicas_local == R;
+    const bool tree_inside = plan.kind == SEG_TREE && whole && R <= TREE_PERSIST_MAX_R;
     // ... and so does the packed round over several CUs (segment_pack_body<MULTI>; the cascade's 3 R + 1 floats live in the slots' area)
-    const bool packm_inside = h->packed && h->groups > 1 && whole &&
-                              (size_t)(3 * h->cfg.n_replicas_global + 1) <= (size_t)pack_slots(h->pk_nred) * pack_slot_floats(h->PS);
+    const bool packm_inside = plan.kind == SEG_PACKM && whole && (size_t)(3 * R + 1) <= (size_t)pack_slots(plan.pk_nred) * pack_slot_floats(h.PS);
     const bool own_rounds = tree_inside || packm_inside;
-    if (G > 1 && !own_rounds && !(e && e[0] == '1')) return 0;
+    if (plan.grid(1) > 1 && !own_rounds && !forced) return 0;
     // One barrier per round (G == 1) leaves the posted scalars single-buffered: a work-group that has left the barrier reads all R of
     // them into LDS at once (cascade_lds), and the next write to any of them comes a whole swap interval later, at the end of the
     // writer's next interval.  The invariant "no resident work-group falls a whole interval behind between leaving a barrier and its
     // next few loads" holds with orders of magnitude to spare for intervals of tens of microseconds; for intervals of a few MH steps
     // of a small net it is not worth relying on: those runs take one launch per interval (a kernel boundary orders everything).
-    if (h->cfg.swap_interval < 8 && !own_rounds && !(e && e[0] == '1')) return 0;
+    if (c.swap_interval < 8 && !own_rounds && !forced) return 0;
     // kernels compiled without the interval loop (ptnn_device.hpp: persistent_loop<false>)
-    if ((h->speculative && !h->packed) || (h->tree && !tree_inside) || (h->packed && h->groups > 1 && !packm_inside)) return 0;
-    if (h->packed && h->groups == 1 && !(h->shape->loops & 2)) return 0;
-    if (!h->wide && !h->packed && !h->speculative && !h->tree && !(h->shape->loops & 1)) return 0;
-    const size_t swap_lds = (size_t)(3 * h->cfg.n_replicas_global + 1) * sizeof(float);
-    if (swap_lds > h->seg_lds) {
-        if (swap_lds > 152 * 1024) return 0;
-        h->seg_lds = swap_lds;
+    if (plan.kind == SEG_SPEC || (plan.kind == SEG_TREE && !tree_inside) || (plan.kind == SEG_PACKM && !packm_inside)) return 0;
+    if (plan.kind == SEG_PACK && !(h.shape->loops & 2)) return 0;
+    if (plan.kind == SEG_COOP && !(h.shape->loops & 1)) return 0;
+    const size_t swap_lds = (size_t)(3 * R + 1) * sizeof(float);
+    if (swap_lds > plan.seg_lds) {
+        if (swap_lds > LDS_CEILING) return 0;
+        plan.seg_lds = swap_lds;
     }
-    const void* fn = reinterpret_cast<const void*>(segment_function(h));
-    if (int rc = raise_lds_limit(fn, h->seg_lds)) return rc;
+    const void* fn = reinterpret_cast<const void*>(segment_function(h.shape, plan.kind));
+    if (int rc = raise_lds_limit(fn, plan.seg_lds)) return rc;
     int per_cu = 0;
-    HIP_TRY(hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, fn, h->nthreads, h->seg_lds));
-    const long long grid = (long long)h->cfg.n_replicas_local * ((h->speculative || h->tree || h->wide) ? h->groups : 1);
-    h->persistent = grid <= (long long)per_cu * h->num_cus;
+    HIP_TRY(hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, fn, plan.threads, plan.seg_lds));
+    plan.persistent = (long long)plan.grid(c.n_replicas_local) <= (long long)per_cu * h.num_cus;
+    return 0;
+}
+
+// The launch plan of a handle for a data set of Nall rows: a function of the config, the data shape and the device ($PTNN_PERSISTENT
+// aside).  Queries the runtime (occupancy, dynamic-LDS ceilings), never writes to the handle; 0 or the refusal.
+int plan_launch(const ptnn_handle& h, int Nall, int Npad, LaunchPlan& plan) {
+    const ptnn_config& c = h.cfg;
+    plan = LaunchPlan{};
+    if (c.n_hidden > WAVE) {
+        if (int rc = plan_wide(h, plan)) return rc;
+    } else {
+        // LDS budget: the data set, the state vectors and the packed forward weights live in LDS for the whole launch
+        plan.model_lds = lds_floats(Nall, h.IPY, h.PS, c.n_hidden, h.FWS) * sizeof(float);
+        if (plan.model_lds > LDS_MAX)
+            return fail(-3, "replica working set needs %zu B of LDS (> 160 KiB): data %d rows x %d floats, P = %d", plan.model_lds, Nall,
+                        h.IPY, h.P);
+        // schedule: speculative pays when MH acceptance is low (regression chains: 1-15 %) or the step is dominated by the
+        // sequential SGD sweep; cooperative when one step's row-parallel forward pass is the bulk of the work
+        int sched = c.schedule;
+        if (sched == PTNN_SCHED_AUTO) sched = (c.task == PTNN_TASK_REG || c.use_langevin) ? PTNN_SCHED_SPECULATIVE : PTNN_SCHED_COOPERATIVE;
+        if (sched != PTNN_SCHED_COOPERATIVE && sched != PTNN_SCHED_SPECULATIVE && sched != PTNN_SCHED_PACKED && sched != PTNN_SCHED_TREE)
+            return fail(-1, "unknown schedule %d", sched);
+        if (sched == PTNN_SCHED_TREE && (c.task != PTNN_TASK_CLS || c.use_langevin))
+            return fail(-3, "the prefetching tree schedule is built for random-walk classification runs");
+        plan.pk_nred = (c.n_hidden <= 8) ? 3 : 4;
+        if (int rc = plan_packed(h, Nall, sched, plan)) return rc;
+        if (plan.kind != SEG_COOP) sched = PTNN_SCHED_PACKED;
+        const int nw = c.waves_per_replica;
+        if (nw != 0 && nw != 1 && nw != 2 && nw != 4 && nw != 8) return fail(-1, "waves_per_replica must be 0 (auto), 1, 2, 4 or 8");
+        int pow2 = 1;
+        while (pow2 < (Nall + 63) / 64) pow2 <<= 1;
+        plan.model_threads = std::min(pow2, 8) * 64;
+        if (sched == PTNN_SCHED_SPECULATIVE) {
+            if (int rc = plan_speculative(h, Nall, plan)) return rc;
+            if (plan.kind == SEG_COOP) sched = PTNN_SCHED_COOPERATIVE;
+        }
+        if (sched == PTNN_SCHED_COOPERATIVE) plan_cooperative(h, Nall, Npad, plan);
+        const bool auto_tree = sched == PTNN_SCHED_COOPERATIVE && c.schedule == PTNN_SCHED_AUTO && c.task == PTNN_TASK_CLS &&
+                               !c.use_langevin && c.groups_per_replica == 0 && c.waves_per_replica == 0 && !c.shared_device;
+        if (sched == PTNN_SCHED_TREE || auto_tree)
+            if (int rc = plan_tree(h, Nall, Npad, sched == PTNN_SCHED_TREE, plan)) return rc;
+    }
+    if (int rc = raise_lds_limit(reinterpret_cast<const void*>(segment_function(h.shape, plan.kind)), plan.seg_lds)) return rc;
+    if (int rc = raise_lds_limit(reinterpret_cast<const void*>(plan.wide() ? h.shape->model_wide : h.shape->model), plan.model_lds)) return rc;
+    return plan_persistent(h, plan);
+}
+
+// Host images of a data set: row-major {x, y, d} rows (xy), transposed (xt), split into bf16 levels (xs: wide nets, else empty)
+struct DataImages {
+    int ntr = 0, nte = 0, Npad = 0;
+    std::vector<float> xy, xt;
+    std::vector<uint16_t> xs;
+};
+
+int pack_data(const ptnn_handle& h, const float* train, int ntr, const float* test, int nte, int ncols, DataImages& img) {
+    const int I = h.cfg.n_in, IPY = h.IPY, Nall = ntr + nte;
+    img.ntr = ntr; img.nte = nte;
+    std::vector<float>& packed = img.xy;
+    packed.assign((size_t)(Nall + 2) * IPY, 0.0f);                 // two zero rows: look-ahead of the SGD sweep
+    for (int n = 0; n < Nall; ++n) {
+        const float* row = (n < ntr) ? train + (size_t)n * ncols : test + (size_t)(n - ntr) * ncols;
+        for (int c = 0; c <= I; ++c) packed[(size_t)n * IPY + c] = row[c];
+        if (n > 0) {                                                 // see sgd_sweep: z[n] = zpart + lhd[n-1] * (1 + x[n].x[n-1])
+            float d = 1.0f;
+            for (int c = 0; c < I; ++c) d = std::fmaf(row[c], packed[(size_t)(n - 1) * IPY + c], d);
+            packed[(size_t)n * IPY + I + 1] = d;
+        }
+        if (h.cfg.task == PTNN_TASK_CLS) {
+            const float y = row[I];
+            if (!(y >= 0.0f) || y >= (float)h.cfg.n_out || y != std::floor(y))
+                return fail(-1, "class label %g in row %d is not an integer in [0, %d)", (double)y, n, h.cfg.n_out);
+        }
+    }
+    // transposed image Xt[k][Npad] for the MFMA forward passes (rows = data rows are the lanes of the B operand)
+    const int Npad = img.Npad = (Nall + 31) & ~31;
+    img.xt.assign((size_t)I * Npad, 0.0f);
+    for (int n = 0; n < Nall; ++n)
+        for (int k = 0; k < I; ++k) img.xt[(size_t)k * Npad + n] = packed[(size_t)n * IPY + k];
+    if (wide_split(h)) {
+        // split-operand forward pass of the wide kernels: x = hi + mid + lo, three bf16 roundings (nearest even; x - hi and
+        // x - hi - mid are exact in fp32), rows of 8 * CH bf16, k contiguous
+        const int KBF = 8 * h.shape->split_ch;
+        auto bf16 = [](float f) -> uint32_t { uint32_t u; std::memcpy(&u, &f, 4); return (u + 0x7FFFu + ((u >> 16) & 1u)) >> 16; };
+        auto back = [](uint32_t b) -> float { const uint32_t u = b << 16; float f; std::memcpy(&f, &u, 4); return f; };
+        img.xs.assign((size_t)3 * Npad * KBF, 0);
+        for (int n = 0; n < Nall; ++n)
+            for (int k = 0; k < I && k < KBF; ++k) {
+                const float x = packed[(size_t)n * IPY + k];
+                const uint32_t hi = bf16(x);
+                const float r1 = x - back(hi);
+                const uint32_t mid = bf16(r1);
+                const float r2 = r1 - back(mid);
+                const uint32_t lo = bf16(r2);
+                img.xs[((size_t)0 * Npad + n) * KBF + k] = (uint16_t)hi;
+                img.xs[((size_t)1 * Npad + n) * KBF + k] = (uint16_t)mid;
+                img.xs[((size_t)2 * Npad + n) * KBF + k] = (uint16_t)lo;
+            }
+    }
+    return 0;
+}
+
+// free *ptr, then allocate `bytes` (0: none) and fill them from the host (src) or with zeros (zero)
+template <class T>
+int replace_buffer(T*& ptr, size_t bytes, bool zero, const void* src = nullptr) {
+    if (ptr) { HIP_TRY(hipFree(ptr)); ptr = nullptr; }
+    if (bytes == 0) return 0;
+    HIP_TRY(hipMalloc(&ptr, bytes));
+    if (src) HIP_TRY(hipMemcpy(ptr, src, bytes, hipMemcpyHostToDevice));
+    else if (zero) HIP_TRY(hipMemset(ptr, 0, bytes));
+    return 0;
+}
+
+// Upload the images and allocate the plan's buffers; a failed allocation leaves the handle without data (it refuses to run)
+int apply_plan(ptnn_handle* h, const DataImages& img, const LaunchPlan& plan) {
+    h->have_data = false;
+    if (int rc = replace_buffer(h->d_data, img.xy.size() * sizeof(float), false, img.xy.data())) return rc;
+    if (int rc = replace_buffer(h->d_xt, img.xt.size() * sizeof(float), false, img.xt.data())) return rc;
+    if (int rc = replace_buffer(h->d_xs, img.xs.size() * sizeof(uint16_t), false, img.xs.data())) return rc;
+    if (int rc = replace_buffer(h->d_wide_scratch, plan.wide_scratch, false)) return rc;
+    if (int rc = replace_buffer(h->d_xslots, plan.xslots, true)) return rc;
+    if (int rc = replace_buffer(h->d_xw, plan.xw, true)) return rc;
+    if (int rc = replace_buffer(h->d_xverdict, plan.xverdict, true)) return rc;
+    if (int rc = replace_buffer(h->d_xswap, plan.xswap, true)) return rc;
+    if (plan.xslots) h->epoch_base = 1;                 // fresh granules: tag 0 = never written
+    h->Ntr = img.ntr; h->Nte = img.nte; h->Npad = img.Npad;
+    h->plan = plan;
+    h->have_data = true;
     return 0;
 }
 
@@ -590,363 +935,15 @@ int ptnn_destroy(ptnn_handle* h) {
 
 int ptnn_set_data(ptnn_handle* h, const float* train, int ntr, const float* test, int nte, int ncols) {
     if (!h || !train || !test) return fail(-1, "null argument");
-    const int I = h->cfg.n_in;
-    if (ncols < I + 1) return fail(-1, "data needs at least n_in + 1 = %d columns, got %d", I + 1, ncols);
+    if (ncols < h->cfg.n_in + 1) return fail(-1, "data needs at least n_in + 1 = %d columns, got %d", h->cfg.n_in + 1, ncols);
     if (ntr < 1 || nte < 1) return fail(-1, "empty data set");
     HIP_TRY(hipSetDevice(h->cfg.device_id));
-    const int Nall = ntr + nte;
-    const int IPY = h->IPY;
-    std::vector<float> packed((size_t)(Nall + 2) * IPY, 0.0f);      // two zero rows: look-ahead of the SGD sweep
-    for (int n = 0; n < Nall; ++n) {
-        const float* row = (n < ntr) ? train + (size_t)n * ncols : test + (size_t)(n - ntr) * ncols;
-        for (int c = 0; c <= I; ++c) packed[(size_t)n * IPY + c] = row[c];
-        if (n > 0) {                                                 // see sgd_sweep: z[n] = zpart + lhd[n-1] * (1 + x[n].x[n-1])
-            float d = 1.0f;
-            for (int c = 0; c < I; ++c) d = std::fmaf(row[c], packed[(size_t)(n - 1) * IPY + c], d);
-            packed[(size_t)n * IPY + I + 1] = d;
-        }
-        if (h->cfg.task == PTNN_TASK_CLS) {
-            const float y = row[I];
-            if (!(y >= 0.0f) || y >= (float)h->cfg.n_out || y != std::floor(y))
-                return fail(-1, "class label %g in row %d is not an integer in [0, %d)", (double)y, n, h->cfg.n_out);
-        }
-    }
-    const int H = h->cfg.n_hidden;
-    // transposed image Xt[k][Npad] for the MFMA forward passes (rows = data rows are the lanes of the B operand)
-    h->Npad = (Nall + 31) & ~31;
-    {
-        std::vector<float> xt((size_t)I * h->Npad, 0.0f);
-        for (int n = 0; n < Nall; ++n)
-            for (int k = 0; k < I; ++k) xt[(size_t)k * h->Npad + n] = packed[(size_t)n * IPY + k];
-        if (h->d_xt) { HIP_TRY(hipFree(h->d_xt)); h->d_xt = nullptr; }
-        HIP_TRY(hipMalloc(&h->d_xt, xt.size() * sizeof(float)));
-        HIP_TRY(hipMemcpy(h->d_xt, xt.data(), xt.size() * sizeof(float), hipMemcpyHostToDevice));
-    }
-    h->fw_mfma = 0; h->xy_global = false;
-    if (h->d_xs) { HIP_TRY(hipFree(h->d_xs)); h->d_xs = nullptr; }
-    if (H > WAVE && H % 32 == 0 && h->shape->split_ch > 0 && h->cfg.forward_bf16 == 0) {
-        // split-operand forward pass of the wide kernels (ptnn_device.hpp, SplitK / eval_rows_mfma_wsplit): x = hi + mid + lo, three
-        // bf16 roundings (nearest even; x - hi and x - hi - mid are exact in fp32), rows of 8 * CH bf16, k contiguous
-        const char* fs = std::getenv("PTNN_FW_SPLIT");
-        if (!(fs && fs[0] == '0')) {
-            const int CH = h->shape->split_ch, KBF = 8 * CH;
-            auto bf16 = [](float f) -> uint32_t { uint32_t u; std::memcpy(&u, &f, 4); return (u + 0x7FFFu + ((u >> 16) & 1u)) >> 16; };
-            auto back = [](uint32_t b) -> float { const uint32_t u = b << 16; float f; std::memcpy(&f, &u, 4); return f; };
-            std::vector<uint16_t> xs((size_t)3 * h->Npad * KBF, 0);
-            for (int n = 0; n < Nall; ++n)
-                for (int k = 0; k < I && k < KBF; ++k) {
-                    const float x = packed[(size_t)n * IPY + k];
-                    const uint32_t hi = bf16(x);
-                    const float r1 = x - back(hi);
-                    const uint32_t mid = bf16(r1);
-                    const float r2 = r1 - back(mid);
-                    const uint32_t lo = bf16(r2);
-                    xs[((size_t)0 * h->Npad + n) * KBF + k] = (uint16_t)hi;
-                    xs[((size_t)1 * h->Npad + n) * KBF + k] = (uint16_t)mid;
-                    xs[((size_t)2 * h->Npad + n) * KBF + k] = (uint16_t)lo;
-                }
-            HIP_TRY(hipMalloc(&h->d_xs, xs.size() * sizeof(uint16_t)));
-            HIP_TRY(hipMemcpy(h->d_xs, xs.data(), xs.size() * sizeof(uint16_t), hipMemcpyHostToDevice));
-            h->fw_mfma = 2;
-        }
-    }
-    if (H > WAVE) {
-        // wide net: one thread per hidden unit, vectors in HBM, only the packed forward image + scratch in LDS
-        // matrix-core layout (H a multiple of 32): the state vector joins the proposal in LDS when both fit (ceilings just below
-        // 160 KiB are refused by the runtime); $PTNN_WIDE_RES=0 keeps the streaming kernel (A/B measurements)
-        const size_t lds_res = wide_lds_floats(H, h->FWS, h->cfg.n_out, h->PS, true) * sizeof(float);
-        const char* res_env = std::getenv("PTNN_WIDE_RES");
-        h->wide_res = (H % 32 == 0) && lds_res <= 152 * 1024 && !(res_env && res_env[0] == '0');
-        const size_t lds = h->wide_res ? lds_res : wide_lds_floats(H, h->FWS, h->cfg.n_out, h->PS) * sizeof(float);
-        if (lds > 160 * 1024) return fail(-3, "wide net needs %zu B of LDS (> 160 KiB)", lds);
-        {
-            const char* ce = std::getenv("PTNN_COMPACT_TRACES");
-            h->compact = h->cap == h->cfg.n_samples && !(ce && ce[0] == '0');
-        }
-        if (h->cfg.schedule == PTNN_SCHED_SPECULATIVE || h->cfg.schedule == PTNN_SCHED_PACKED || h->cfg.schedule == PTNN_SCHED_TREE)
-            return fail(-3, "schedules 2-4 are built for n_hidden <= 64; a wide net speculates over work-groups through groups_per_replica");
-        h->wide = true; h->speculative = false; h->groups = 1;
-        h->nthreads = ((H + WAVE - 1) / WAVE) * WAVE;
-        h->model_threads = h->nthreads;
-        h->seg_lds = h->model_lds = lds;
-        h->Ntr = ntr; h->Nte = nte;
-        if (h->d_data) { HIP_TRY(hipFree(h->d_data)); h->d_data = nullptr; }
-        HIP_TRY(hipMalloc(&h->d_data, packed.size() * sizeof(float)));
-        HIP_TRY(hipMemcpy(h->d_data, packed.data(), packed.size() * sizeof(float), hipMemcpyHostToDevice));
-        if (int rc = raise_lds_limit(reinterpret_cast<const void*>(segment_function(h)), lds)) return rc;
-        if (int rc = raise_lds_limit(reinterpret_cast<const void*>(h->shape->model_wide), lds)) return rc;
-        {
-            // Speculation over work-groups (one per CU): group g computes step i + g; all Rl x G groups must be resident (they wait
-            // for each other's verdicts).  groups_per_replica 1, 2 or 4; 0 = as many of 4, 2 as are resident, else 1.
-            const int Rl = h->cfg.n_replicas_local;
-            const int want = h->cfg.groups_per_replica;
-            if (want != 0 && want != 1 && want != 2 && want != 4) return fail(-1, "wide nets: groups_per_replica must be 0 (auto), 1, 2 or 4");
-            int per_cu = 0;
-            HIP_TRY(hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, reinterpret_cast<const void*>(segment_function(h)), h->nthreads, lds));
-            h->blocks_per_cu = per_cu;
-            const long long cap = (long long)per_cu * h->num_cus;
-            int G = 1;
-            if (want > 1) {
-                if ((long long)Rl * want > cap)
-                    return fail(-3, "%d replicas x %d work-groups cannot all be resident: %d work-group(s) of %d threads with %zu B of LDS fit "
-                                    "on each of the %d CUs", Rl, want, per_cu, h->nthreads, lds, h->num_cus);
-                G = want;
-            } else if (want == 0 && !h->cfg.shared_device) {     // (work-groups that wait for each other want the GPU to themselves)
-                if ((long long)Rl * 4 <= cap) G = 4;
-                else if ((long long)Rl * 2 <= cap) G = 2;
-            }
-            h->groups = G;
-            if (h->d_wide_scratch) { HIP_TRY(hipFree(h->d_wide_scratch)); h->d_wide_scratch = nullptr; }
-            HIP_TRY(hipMalloc(&h->d_wide_scratch, (size_t)Rl * G * 5 * h->PS * sizeof(float)));
-            if (h->d_xslots) { HIP_TRY(hipFree(h->d_xslots)); h->d_xslots = nullptr; }
-            if (h->d_xw) { HIP_TRY(hipFree(h->d_xw)); h->d_xw = nullptr; }
-            if (h->d_xverdict) { HIP_TRY(hipFree(h->d_xverdict)); h->d_xverdict = nullptr; }
-            if (G > 1) {
-                const size_t ns = (size_t)Rl * 2 * MAX_SLOTS * SL_COUNT, nx = (size_t)Rl * 2 * G * 2 * h->PS, nvd = (size_t)Rl * 2 * MAX_SLOTS;
-                HIP_TRY(hipMalloc(&h->d_xslots, ns * sizeof(unsigned long long)));
-                HIP_TRY(hipMalloc(&h->d_xw, nx * sizeof(unsigned long long)));
-                HIP_TRY(hipMalloc(&h->d_xverdict, nvd * sizeof(unsigned long long)));
-                HIP_TRY(hipMemset(h->d_xslots, 0, ns * sizeof(unsigned long long)));
-                HIP_TRY(hipMemset(h->d_xw, 0, nx * sizeof(unsigned long long)));
-                HIP_TRY(hipMemset(h->d_xverdict, 0, nvd * sizeof(unsigned long long)));
-                h->epoch_base = 1;                              // tag 0 = never written
-            }
-        }
-        if (int rc = resolve_persistent(h)) return rc;
-        h->have_data = true;
-        return 0;
-    }
-    // LDS budget: the data set, the state vectors and the packed forward weights live in LDS for the whole launch
-    const size_t coop_lds = lds_floats(Nall, IPY, h->PS, H, h->FWS) * sizeof(float);
-    const size_t LDS_MAX = 160 * 1024;
-    if (coop_lds > LDS_MAX)
-        return fail(-3, "replica working set needs %zu B of LDS (> 160 KiB): data %d rows x %d floats, P = %d", coop_lds, Nall,
-                    IPY, h->P);
-    h->model_lds = coop_lds;
-    // schedule: speculative pays when MH acceptance is low (regression chains: 1-15 %) or the step is dominated by the
-    // sequential SGD sweep; cooperative when one step's row-parallel forward pass is the bulk of the work
-    int sched = h->cfg.schedule;
-    if (sched == PTNN_SCHED_AUTO)
-        sched = (h->cfg.task == PTNN_TASK_REG || h->cfg.use_langevin) ? PTNN_SCHED_SPECULATIVE : PTNN_SCHED_COOPERATIVE;
-    if (sched != PTNN_SCHED_COOPERATIVE && sched != PTNN_SCHED_SPECULATIVE && sched != PTNN_SCHED_PACKED && sched != PTNN_SCHED_TREE)
-        return fail(-1, "unknown schedule %d", sched);
-    if (sched == PTNN_SCHED_TREE && (h->cfg.task != PTNN_TASK_CLS || h->cfg.use_langevin))
-        return fail(-3, "the prefetching tree schedule is built for random-walk classification runs");
-    h->packed = false; h->tree = false;
-    {
-        // packed speculative: all slots of a round on one CU, the SGD epochs of the slots in the lane groups of two waves:
-        // 16 slots in groups of 8 lanes for n_hidden <= 8, 8 slots in groups of 16 lanes for n_hidden <= 16.  Taken
-        // automatically for Langevin runs of such nets (faster than 4 CUs per replica on a quarter of the GPU, and more than
-        // twice the throughput once there are more replicas than CUs); random-walk-only runs have no epochs to pack and keep
-        // the multi-CU speculative schedule.
-        h->pk_nred = (H <= 8) ? 3 : 4;
-        const size_t pk = pack_lds_floats(Nall, IPY, h->PS, H, h->FWS, pack_slots(h->pk_nred)) * sizeof(float);
-        const bool fits = H <= 16 && pk <= LDS_MAX;
-        if (sched == PTNN_SCHED_PACKED && !fits)
-            return fail(-3, "the packed schedule needs n_hidden <= 16 and %zu B of LDS <= 160 KiB", pk);
-        // 16-lane groups give 8 slots per round on one CU.  With CUs to spare the packed round runs on 2 or 4 CUs per replica (16 / 32
-        // slots per round, segment_packm_kernel): Mackey-Glass 4-10-1, 64 replicas needs 18.7 / 13.6 / 11.6 rounds per swap interval
-        // with 8 / 16 / 32 slots (profiles/r03_window_sim.jsonl) and a packed round is shorter than the multi-CU speculative one (the
-        // forward passes run beside the epochs).  groups_per_replica = 1, 2, 4 decides otherwise; $PTNN_PACK_MULTI=0 keeps one CU.
-        int pack_groups = 1;
-        const size_t pkm = pack_multi_lds_floats(Nall, IPY, h->PS, H, h->FWS, pack_slots(h->pk_nred)) * sizeof(float);
-        const char* pm_env = std::getenv("PTNN_PACK_MULTI");
-        if (fits && pkm <= LDS_MAX && h->cfg.use_langevin && !h->cfg.shared_device && !(pm_env && pm_env[0] == '0') &&
-            (sched == PTNN_SCHED_PACKED || h->cfg.schedule == PTNN_SCHED_AUTO) && h->cfg.waves_per_replica == 0) {
-            const int Rl_ = h->cfg.n_replicas_local, want = h->cfg.groups_per_replica;
-            if (want == 2 || want == 4) pack_groups = want;                       // (8-lane groups: on request only -- 16 slots on one CU already)
-            else if (want == 0 && h->pk_nred == 4) { if (Rl_ * 4 <= h->num_cus) pack_groups = 4; else if (Rl_ * 2 <= h->num_cus) pack_groups = 2; }
-        }
-        const bool pays = (H <= 8) || pack_groups > 1 || h->cfg.n_replicas_local * 4 > h->num_cus;
-        if (sched == PTNN_SCHED_PACKED ||
-            (h->cfg.schedule == PTNN_SCHED_AUTO && sched == PTNN_SCHED_SPECULATIVE && fits && pays && h->cfg.use_langevin &&
-             h->cfg.waves_per_replica == 0 && (h->cfg.groups_per_replica == 0 || pack_groups > 1))) {
-            h->packed = true; h->speculative = true; h->groups = pack_groups;
-            // eight waves (forward passes two to a SIMD) while every replica has a CU to itself, four beyond that; an explicit
-            // waves_per_replica of 4 or 8 decides otherwise
-            const int pkw = (h->cfg.waves_per_replica == 4 || h->cfg.waves_per_replica == 8) ? h->cfg.waves_per_replica
-                            : (h->cfg.n_replicas_local <= h->num_cus ? PK_WAVES : 4);
-            h->nthreads = (pack_groups > 1) ? PK_WAVES * WAVE : pkw * WAVE;
-            h->seg_lds = (pack_groups > 1) ? pkm : pk;
-            sched = PTNN_SCHED_PACKED;
-            if (pack_groups > 1) {                              // exchange buffers of the multi-CU variant (segment_spec_body's layout)
-                const int Rl_ = h->cfg.n_replicas_local;
-                if (h->d_xslots) { HIP_TRY(hipFree(h->d_xslots)); h->d_xslots = nullptr; }
-                if (h->d_xw) { HIP_TRY(hipFree(h->d_xw)); h->d_xw = nullptr; }
-                if (h->d_xverdict) { HIP_TRY(hipFree(h->d_xverdict)); h->d_xverdict = nullptr; }
-                const size_t ns = (size_t)Rl_ * 2 * MAX_SLOTS * SL_COUNT, nx = (size_t)Rl_ * 2 * pack_groups * 2 * h->PS, nvd = (size_t)Rl_ * 2 * MAX_SLOTS;
-                HIP_TRY(hipMalloc(&h->d_xslots, ns * sizeof(unsigned long long)));
-                HIP_TRY(hipMalloc(&h->d_xw, nx * sizeof(unsigned long long)));
-                HIP_TRY(hipMalloc(&h->d_xverdict, nvd * sizeof(unsigned long long)));
-                HIP_TRY(hipMemset(h->d_xslots, 0, ns * sizeof(unsigned long long)));
-                HIP_TRY(hipMemset(h->d_xw, 0, nx * sizeof(unsigned long long)));
-                HIP_TRY(hipMemset(h->d_xverdict, 0, nvd * sizeof(unsigned long long)));
-                if (int rc = alloc_swap_granules(h, 2 * h->PS + 8)) return rc;     // in-launch swap rounds: state + cached gradient + flag
-                h->epoch_base = 1;                              // tag 0 = never written
-            }
-        }
-    }
-    int nw = h->cfg.waves_per_replica;
-    if (nw != 0 && nw != 1 && nw != 2 && nw != 4 && nw != 8)
-        return fail(-1, "waves_per_replica must be 0 (auto), 1, 2, 4 or 8");
-    int coop_nw = (Nall + 63) / 64, pow2 = 1;
-    while (pow2 < coop_nw) pow2 <<= 1;
-    coop_nw = std::min(pow2, 8);
-    h->model_threads = coop_nw * 64;
-    if (sched == PTNN_SCHED_SPECULATIVE) {
-        h->packed = false;
-        // Two waves on one SIMD slow each other ~1.65x (the SGD sweep is VALU-issue bound), so speculation depth comes
-        // from more CUs first: G work-groups of 4 waves (one per SIMD) per replica while R*G <= number of CUs, and
-        // 8 waves on a single CU otherwise.
-        const int Rl = h->cfg.n_replicas_local;
-        int G = 1;
-        if (h->cfg.groups_per_replica > 0) G = h->cfg.groups_per_replica;
-        else if (!h->cfg.shared_device) { while (G < 4 && Rl * (G * 2) <= h->num_cus) G *= 2; }
-        if (G != 1 && G != 2 && G != 4 && G != 8) return fail(-1, "groups_per_replica must be 0 (auto), 1, 2, 4 or 8");
-        int k = nw ? nw : (G > 1 ? 4 : 8);
-        while (k > 1 && spec_lds_floats(Nall, IPY, h->PS, H, h->FWS, k, G) * sizeof(float) > LDS_MAX) k >>= 1;
-        if (nw && k != nw) {
-            if (h->cfg.schedule == PTNN_SCHED_AUTO) k = 0;      // auto: fall back to the cooperative schedule below
-            else return fail(-3, "speculative schedule with %d waves needs more than 160 KiB of LDS", nw);
-        }
-        if (k * G > MAX_SLOTS) return fail(-1, "waves x groups must not exceed %d", MAX_SLOTS);
-        if (k == 0 || spec_lds_floats(Nall, IPY, h->PS, H, h->FWS, k, G) * sizeof(float) > LDS_MAX) sched = PTNN_SCHED_COOPERATIVE;
-        else {
-            h->speculative = true; h->nthreads = k * 64; h->groups = G;
-            h->seg_lds = spec_lds_floats(Nall, IPY, h->PS, H, h->FWS, k, G) * sizeof(float);
-            if (G > 1) {
-                // The work-groups of one replica wait for each other inside the kernel, so all Rl x G of them must be
-                // resident at once: ask the runtime how many blocks of THIS kernel (its registers, this LDS size, this block
-                // size) fit on a CU instead of guessing, and refuse the configuration otherwise (a non-resident partner would
-                // be a bounded spin and an error from ptnn_sync).  The count is for a GPU this handle has to itself: other
-                // handles or processes on the same device take CUs this query does not see.
-                const void* fn = reinterpret_cast<const void*>(h->shape->spec);
-                if (int rc = raise_lds_limit(fn, h->seg_lds)) return rc;
-                int per_cu = 0;
-                HIP_TRY(hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, fn, h->nthreads, h->seg_lds));
-                h->blocks_per_cu = per_cu;
-                if ((long long)Rl * G > (long long)per_cu * h->num_cus)
-                    return fail(-3, "%d replicas x %d work-groups cannot all be resident: %d work-group(s) of %d threads with %zu B "
-                                    "of LDS fit on each of the %d CUs; use fewer groups_per_replica or the packed schedule",
-                                Rl, G, per_cu, h->nthreads, h->seg_lds, h->num_cus);
-            }
-            if (h->d_xslots) { HIP_TRY(hipFree(h->d_xslots)); h->d_xslots = nullptr; }
-            if (h->d_xw) { HIP_TRY(hipFree(h->d_xw)); h->d_xw = nullptr; }
-            if (h->d_xverdict) { HIP_TRY(hipFree(h->d_xverdict)); h->d_xverdict = nullptr; }
-            if (G > 1) {
-                const size_t ns = (size_t)Rl * 2 * MAX_SLOTS * SL_COUNT, nx = (size_t)Rl * 2 * MAX_SLOTS * 2 * h->PS;
-                HIP_TRY(hipMalloc(&h->d_xslots, ns * sizeof(unsigned long long)));
-                HIP_TRY(hipMalloc(&h->d_xw, nx * sizeof(unsigned long long)));
-                HIP_TRY(hipMemset(h->d_xslots, 0, ns * sizeof(unsigned long long)));
-                HIP_TRY(hipMemset(h->d_xw, 0, nx * sizeof(unsigned long long)));
-                HIP_TRY(hipMalloc(&h->d_xverdict, (size_t)Rl * 2 * MAX_SLOTS * sizeof(unsigned long long)));
-                HIP_TRY(hipMemset(h->d_xverdict, 0, (size_t)Rl * 2 * MAX_SLOTS * sizeof(unsigned long long)));
-                h->epoch_base = 1;                              // tag 0 = never written
-            }
-        }
-    }
-    if (sched == PTNN_SCHED_COOPERATIVE) {
-        h->speculative = false;
-        h->nthreads = (nw ? nw : coop_nw) * 64;
-        const size_t seg_lds = lds_floats(Nall, IPY, h->PS, H, h->FWS, h->cfg.use_langevin != 0) * sizeof(float);
-        h->seg_lds = seg_lds;
-        // a hidden layer that fills most of a 32-unit tile and at least three k-steps: forward pass on the matrix cores
-        // (the VALU pass re-reads the weights from LDS with broadcast reads and is bound by the LDS pipe at this size)
-        const size_t extra = (mfma_coop_lds_floats(I, h->cfg.n_out, H, h->Npad) + 4) * sizeof(float);
-        h->fw_mfma = (H >= 24 && I >= 6 && seg_lds + extra <= LDS_MAX) ? 1 : 0;
-        if (h->fw_mfma) h->seg_lds = seg_lds + extra;
-        // Split bf16 operands (ptnn_device.hpp, SplitK): the default where the matrix cores are used, unless the caller asked for
-        // the exact fp32 instruction (forward_bf16 = 2: bit-identical to the VALU schedules) or the images do not fit.  They take
-        // more LDS than the transposed fp32 image; a random-walk launch may give up the row-major data image for them (its only
-        // readers left are the chain start and the SGD epochs of a Langevin launch, which therefore keeps it).
-        const char* fs = std::getenv("PTNN_FW_SPLIT");
-        if (h->fw_mfma && h->shape->split_ch > 0 && h->cfg.forward_bf16 != 2 && !(fs && fs[0] == '0')) {
-            const int CH = h->shape->split_ch, KR = h->shape->split_kr, Hpad = ((H + 31) >> 5) << 5;
-            const size_t sfl = (size_t)3 * h->Npad * CH * 4 + (size_t)2 * KR * h->Npad + (size_t)h->Npad + (size_t)3 * Hpad * CH * 4 +
-                               (size_t)(Hpad >> 5) * h->Npad * h->cfg.n_out + 4;
-            const size_t with_xy = seg_lds + sfl * sizeof(float);
-            const size_t without_xy = lds_floats(Nall, IPY, h->PS, H, h->FWS, h->cfg.use_langevin != 0, false) * sizeof(float) + sfl * sizeof(float);
-            if (with_xy <= LDS_MAX) { h->fw_mfma = 2; h->xy_global = false; h->seg_lds = with_xy; }
-            else if (!h->cfg.use_langevin && without_xy <= LDS_MAX) { h->fw_mfma = 2; h->xy_global = true; h->seg_lds = without_xy; }
-        }
-    }
-    if (sched == PTNN_SCHED_TREE || (sched == PTNN_SCHED_COOPERATIVE && h->cfg.schedule == PTNN_SCHED_AUTO && h->cfg.task == PTNN_TASK_CLS &&
-                                     !h->cfg.use_langevin && h->cfg.groups_per_replica == 0 && h->cfg.waves_per_replica == 0 &&
-                                     !h->cfg.shared_device)) {
-        // Prefetching tree: 2^D - 1 work-groups per replica, all of them resident (they wait for each other's records).
-        // Explicit: groups_per_replica = 3, 7, 15 or 31 (0: deepest that fits); auto: deepest of 31 / 15 / 7 / 3 that fits (31 nodes:
-        // five steps per round; Iris 16 x 31 = 496 work-groups, two to a CU: 11.8 M against 11.4 M samples/s with 15),
-        // none -> the cooperative schedule stays.
-        const bool explicit_tree = sched == PTNN_SCHED_TREE;
-        const int Rl = h->cfg.n_replicas_local;
-        const int want = h->cfg.groups_per_replica;
-        if (explicit_tree && want != 0 && want != 3 && want != 7 && want != 15 && want != 31)
-            return fail(-1, "tree schedule: groups_per_replica must be 0 (auto), 3, 7, 15 or 31");
-        h->nthreads = (nw ? nw : coop_nw) * 64;
-        size_t extra = (mfma_coop_lds_floats(I, h->cfg.n_out, H, h->Npad) + 4) * sizeof(float);
-        const bool coop_mfma = H >= 24 && I >= 6 && lds_floats(Nall, IPY, h->PS, H, h->FWS, false) * sizeof(float) + extra <= LDS_MAX;
-        // the split-operand forward pass of the cooperative kernel (same arithmetic: the tree commits the cooperative chain bit for
-        // bit either way), when its images fit next to the shallowest tree
-        bool tree_split = false;
-        {
-            const char* fs = std::getenv("PTNN_FW_SPLIT");
-            if (coop_mfma && h->shape->split_ch > 0 && h->cfg.forward_bf16 != 2 && !(fs && fs[0] == '0')) {
-                const int CH = h->shape->split_ch, KR = h->shape->split_kr, Hpad = ((H + 31) >> 5) << 5;
-                const size_t sfl = (size_t)3 * h->Npad * CH * 4 + (size_t)2 * KR * h->Npad + (size_t)h->Npad + (size_t)3 * Hpad * CH * 4 +
-                                   (size_t)(Hpad >> 5) * h->Npad * h->cfg.n_out + 4;
-                if (tree_lds_floats(Nall, IPY, h->PS, H, h->FWS, 2, false, true) * sizeof(float) + sfl * sizeof(float) <= 152 * 1024) {
-                    tree_split = true;
-                    extra = sfl * sizeof(float);
-                }
-            }
-        }
-        int chosen = 0;
-        size_t chosen_lds = 0;
-        bool chosen_mfma = false;
-        const void* fn = reinterpret_cast<const void*>(h->shape->tree);
-        for (int G = (explicit_tree && want) ? want : TREE_MAX_NODES; G >= 3; G = (G - 1) / 2) {
-            const int Dp = tree_depth(G);
-            // two sets of tapes (the next round's drawn while the records travel) when they fit
-            const size_t ceiling = 152 * 1024;                  // dynamic-LDS ceilings just below 160 KiB are refused by the runtime
-            bool ah = tree_lds_floats(Nall, IPY, h->PS, H, h->FWS, Dp, true, coop_mfma) * sizeof(float) + (coop_mfma ? extra : 0) <= ceiling;
-            size_t lds = tree_lds_floats(Nall, IPY, h->PS, H, h->FWS, Dp, ah, coop_mfma) * sizeof(float);
-            // same forward pass as the cooperative schedule would run (matrix cores or not): a deeper tree that has no room
-            // for the transposed data image is not taken
-            const bool mf = coop_mfma;
-            if (mf) lds += extra;
-            // (the runtime may refuse a dynamic-LDS ceiling just below 160 KiB: such a depth does not fit either)
-            const bool fits = lds <= LDS_MAX && raise_lds_limit(fn, lds) == 0;
-            if (!fits) (void)hipGetLastError();                 // a refused ceiling must not surface at the next launch
-            if (fits) {
-                int per_cu = 0;
-                HIP_TRY(hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, fn, h->nthreads, lds));
-                if ((long long)Rl * G <= (long long)per_cu * h->num_cus) { chosen = G; chosen_lds = lds; chosen_mfma = mf; h->tree_ahead = ah; h->blocks_per_cu = per_cu; break; }
-            }
-            if (explicit_tree && want) break;
-        }
-        if (chosen) {
-            h->tree = true; h->speculative = false; h->groups = chosen; h->seg_lds = chosen_lds; h->fw_mfma = chosen_mfma ? (tree_split ? 2 : 1) : 0; h->xy_global = false;
-            if (h->d_xslots) { HIP_TRY(hipFree(h->d_xslots)); h->d_xslots = nullptr; }
-            const size_t ng = (size_t)Rl * 2 * (TREE_MAX_NODES + 1) * TREE_REC;
-            HIP_TRY(hipMalloc(&h->d_xslots, ng * sizeof(unsigned long long)));
-            HIP_TRY(hipMemset(h->d_xslots, 0, ng * sizeof(unsigned long long)));
-            // granules of the in-launch swap rounds (two parities), when the whole ladder is on this handle
-            if (int rc = alloc_swap_granules(h, h->PS)) return rc;
-            h->epoch_base = 1;                                  // tag 0 = never written
-        } else if (explicit_tree) {
-            return fail(-3, "tree schedule: %d replicas x %d work-groups of %d threads cannot all be resident on %d CUs (or need more than "
-                            "160 KiB of LDS)", Rl, want ? want : 3, h->nthreads, h->num_cus);
-        }
-    }
-    h->Ntr = ntr; h->Nte = nte;
-    if (h->d_data) { HIP_TRY(hipFree(h->d_data)); h->d_data = nullptr; }
-    HIP_TRY(hipMalloc(&h->d_data, packed.size() * sizeof(float)));
-    HIP_TRY(hipMemcpy(h->d_data, packed.data(), packed.size() * sizeof(float), hipMemcpyHostToDevice));
-    if (int rc = raise_lds_limit(reinterpret_cast<const void*>(segment_function(h)), h->seg_lds)) return rc;
-    if (int rc = raise_lds_limit(reinterpret_cast<const void*>(h->shape->model), h->model_lds)) return rc;
-    if (int rc = resolve_persistent(h)) return rc;
-    h->have_data = true;
-    return 0;
+    // a refused data set (-1, -3) leaves the handle as it was
+    DataImages img;
+    if (int rc = pack_data(*h, train, ntr, test, nte, ncols, img)) return rc;
+    LaunchPlan plan;
+    if (int rc = plan_launch(*h, ntr + nte, img.Npad, plan)) return rc;
+    return apply_plan(h, img, plan);
 }
 
 int ptnn_set_state(ptnn_handle* h, const float* w0, const float* temperatures) {
@@ -1067,7 +1064,7 @@ int ptnn_run(ptnn_handle* h, int n_steps) {
     if (h->cap < S && end - h->drained > h->cap - 1)
         return fail(-6, "trace ring of %d rows would overflow: rows from %d on have not been fetched; call ptnn_get_traces "
                         "first or run fewer steps", h->cap, h->drained + 1);
-    if (h->persistent && !sharded && h->cur < end) {
+    if (h->plan.persistent && !sharded && h->cur < end) {
         // every work-group of the grid is resident: ONE launch runs all the intervals up to `end`, the swap rounds between them
         // inside the kernel (persistent_loop in ptnn_device.hpp); what is left to do here is the bookkeeping of those rounds
         int n_ho = 0;
@@ -1458,13 +1455,13 @@ int ptnn_get_traces(ptnn_handle* h, int step0, int nsteps, float* pos_w, float* 
     };
     std::vector<float> rows;
     const bool want_scalars = likeh || rmse_train || rmse_test || acc_train || acc_test || accept_count;
-    if (want_scalars || (pos_w && h->compact)) {
+    if (want_scalars || (pos_w && h->plan.compact)) {
         // the scalars of a step sit in one 32-byte row on the device (one sector per step instead of seven); the per-file
         // arrays of the reference's layout (REG:454-481) are split out below
         rows.resize((size_t)Rl * nsteps * TR_COUNT);
         HIP_TRY(copy2d(rows.data(), h->d_scal, sizeof(float), TR_COUNT));
     }
-    if (pos_w && h->compact) {
+    if (pos_w && h->plan.compact) {
         // compact traces (wide nets, every row resident): a rejected step wrote no pos_w row, only the index of the row it
         // repeats (pos_w[i+1] = pos_w[i], REG:417).  Fetch every distinct source row once and fill the repeats in on the host.
         const size_t PW = h->PW;
@@ -1546,7 +1543,7 @@ int ptnn_trace_image(ptnn_handle* h, float** pos_w, int32_t* row_floats, float**
     if (!pos_w || !row_floats || !rows) return fail(-1, "null argument");
     const int S = h->cfg.n_samples, Rl = h->cfg.n_replicas_local;
     if (h->cap != S) return fail(-1, "trace images need every row resident (trace_capacity 0 or >= n_samples; this handle keeps a ring of %d)", h->cap);
-    if (h->compact) return fail(-1, "trace images are not available with compact traces (wide nets): fetch with ptnn_get_traces");
+    if (h->plan.compact) return fail(-1, "trace images are not available with compact traces (wide nets): fetch with ptnn_get_traces");
     HIP_TRY(hipSetDevice(h->cfg.device_id));
     if (!h->h_img_pos) {
         // all three or none: a half-made set must not be handed out by the next call
@@ -1772,7 +1769,7 @@ int ptnn_checkpoint_load(ptnn_handle* h, const void* buf, int64_t bytes) {
     if (int rc = put(h->d_label[0], sizeof(int) * R)) return rc;
     if (int rc = put(h->d_slot_of[0], sizeof(int) * R)) return rc;
     HIP_TRY(hipMemcpy(h->d_state[1], h->d_state[0], sizeof(float) * Rl * PS, hipMemcpyDeviceToDevice));
-    if (h->compact) {
+    if (h->plan.compact) {
         // compact traces: the rows a later rejected step may repeat are not on this device -- put the recorded row of every chain
         // into trace row hd.cur (the last one before the checkpoint) and point the chains at it
         HIP_TRY(hipMemcpy2D(h->d_pos_w + (size_t)(hd.cur % h->cap) * h->PW, (size_t)h->cap * h->PW * sizeof(float), h->d_rec_w,
@@ -1928,7 +1925,7 @@ int ptnn_predict(ptnn_handle* h, const ptnn_predict_spec* spec) {
         HIP_TRY(mem.alloc(&d_reps, reps.size()));
         HIP_TRY(hipMemcpyAsync(d_reps, reps.data(), reps.size() * sizeof(int32_t), hipMemcpyHostToDevice, st));
         sel.host = 0; sel.pos_w = h->d_pos_w; sel.scal = h->d_scal; sel.replicas = d_reps; sel.cap = cap; sel.PW = h->PW;
-        sel.step0 = s.step0; sel.thin = s.thin; sel.m = m; sel.compact = h->compact ? 1 : 0;
+        sel.step0 = s.step0; sel.thin = s.thin; sel.m = m; sel.compact = h->plan.compact ? 1 : 0;
         base = h->d_pos_w;
     }
     hipLaunchKernelGGL(predict_runs_kernel, dim3((unsigned)((n_items + PRED_THREADS - 1) / PRED_THREADS)), dim3(PRED_THREADS), 0, st, sel);
@@ -2029,7 +2026,7 @@ static int run_model(ptnn_handle* h, int mode, const float* w_in, const float* t
     HIP_TRY(hipMemsetAsync(d_out, 0, out_floats * sizeof(float), h->stream));
     const SegParams p = h->seg_params();
     // mode 4 (ptnn_time_tree_round): ONE input row, but 9 blocks -- blocks 0 and 8 share an XCD under the round-robin dispatch
-    hipLaunchKernelGGL(h->wide ? h->shape->model_wide : h->shape->model, dim3(mode == 4 ? 9 : n), dim3(h->model_threads), h->model_lds, h->stream, p,
+    hipLaunchKernelGGL(h->plan.wide() ? h->shape->model_wide : h->shape->model, dim3(mode == 4 ? 9 : n), dim3(h->plan.model_threads), h->plan.model_lds, h->stream, p,
                        mode, d_w, d_tau, d_out, a0, a1);
     HIP_TRY(hipGetLastError());
     if (int rc = wait_stream(h)) return rc;
@@ -2065,13 +2062,13 @@ int ptnn_time_sgd_epoch(ptnn_handle* h, const float* w, int reps, double* ms_per
     };
     ms_per_epoch[0] = ticks(0) / (double)khz / (double)reps;
     // wide nets (n_hidden > 64): [1] = a PAIR of epochs through one row loop (sgd_sweep_wide_pair); narrow nets: 0
-    ms_per_epoch[1] = h->wide ? ticks(2) / (double)khz / (double)reps : 0.0;
+    ms_per_epoch[1] = h->plan.wide() ? ticks(2) / (double)khz / (double)reps : 0.0;
     return 0;
 }
 
 int ptnn_time_tree_round(ptnn_handle* h, const float* w, int reps, int xcd_local, double* ms) {
     if (!h || !w || !ms || reps < 1) return fail(-1, "bad argument");
-    if (h->wide) return fail(-3, "the prefetching tree runs nets of up to 64 hidden units");
+    if (h->plan.wide()) return fail(-3, "the prefetching tree runs nets of up to 64 hidden units");
     float out[64] = {0.f};
     if (int rc = run_model(h, 4, w, nullptr, 1, out, 64, reps, xcd_local ? 1 : 0)) return rc;
     int khz = 0;
@@ -2092,7 +2089,7 @@ int ptnn_time_tree_round(ptnn_handle* h, const float* w, int reps, int xcd_local
 int ptnn_tape(ptnn_handle* h, int replica, int step, float* noise, float* scal) {
     if (!h || !noise || !scal) return fail(-1, "null argument");
     // narrow nets return {noise[P], scal[3]}; the wide kernel writes whole float4s: {noise[PS], scal[3]}
-    const size_t off = h->wide ? (size_t)h->PS : (size_t)h->P;
+    const size_t off = h->plan.wide() ? (size_t)h->PS : (size_t)h->P;
     std::vector<float> buf(off + 3);
     if (int rc = run_model(h, 2, nullptr, nullptr, 1, buf.data(), buf.size(), replica, step)) return rc;
     std::memcpy(noise, buf.data(), h->P * sizeof(float));
@@ -2103,27 +2100,29 @@ int ptnn_tape(ptnn_handle* h, int replica, int step, float* noise, float* scal) 
 int ptnn_describe(ptnn_handle* h, char* buf, int nbytes) {
     if (!h || !buf || nbytes < 1) return fail(-1, "bad argument");
     if (!h->have_data) return fail(-1, "ptnn_set_data has not been called (the schedule depends on the data set)");
-    const char* kern = h->wide ? (h->wide_res ? "segment_wide_res_kernel" : "segment_wide_kernel") : (h->tree ? "segment_tree_kernel" : (h->packed ? (h->groups > 1 ? "segment_packm_kernel" : "segment_pack_kernel") : (h->speculative ? "segment_spec_kernel" : "segment_kernel")));
-    const void* fn = reinterpret_cast<const void*>(segment_function(h));
+    const LaunchPlan& pl = h->plan;
+    const void* fn = reinterpret_cast<const void*>(segment_function(h->shape, pl.kind));
     HIP_TRY(hipSetDevice(h->cfg.device_id));
     int per_cu = 0;
-    HIP_TRY(hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, fn, h->nthreads, h->seg_lds));
+    HIP_TRY(hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, fn, pl.threads, pl.seg_lds));
     hipFuncAttributes fa{};
     HIP_TRY(hipFuncGetAttributes(&fa, fn));
-    const int grid = h->cfg.n_replicas_local * ((h->speculative || h->tree || h->wide) ? h->groups : 1);
-    // tree: the steps committed per round (its depth)
-    const int slots = h->tree ? tree_depth(h->groups) : (h->wide ? (h->groups > 1 && h->cfg.use_langevin ? 8 : h->groups) : !h->speculative ? 1 : (h->packed ? pack_slots(h->pk_nred) * h->groups : h->groups * (h->nthreads / WAVE)));
+    const int slots = pl.kind == SEG_COOP ? 1
+                    : pl.kind == SEG_SPEC ? pl.groups * (pl.threads / WAVE)
+                    : pl.kind == SEG_TREE ? tree_depth(pl.groups)                              // the steps committed per round
+                    : pl.wide() ? (pl.groups > 1 && h->cfg.use_langevin ? 8 : pl.groups)
+                    : pack_slots(pl.pk_nred) * pl.groups;
     const int n = std::snprintf(buf, (size_t)nbytes,
                                 "{\"kernel\": \"ptnn::%s<%d,%d,%d>\", \"schedule\": \"%s\", \"grid_blocks\": %d, \"block_threads\": %d, "
                                 "\"lds_bytes\": %zu, \"groups_per_replica\": %d, \"slots_per_round\": %d, \"num_cus\": %d, "
                                 "\"blocks_per_cu\": %d, \"vgprs\": %d, \"scratch_bytes\": %zu, \"forward_mfma\": %d, \"exchange\": \"%s\", \"lds_resident_state\": %d, \"compact_traces\": %d, \"launches\": \"%s\"}",
-                                kern, h->cfg.task, h->cfg.n_in, h->cfg.n_out,
-                                h->wide ? (h->groups > 1 ? "speculative-wide" : "cooperative-wide") : (h->tree ? "prefetching-tree" : (h->packed ? "packed-speculative" : (h->speculative ? "speculative" : "cooperative"))),
-                                grid, h->nthreads, h->seg_lds, h->groups, slots, h->num_cus, per_cu, fa.numRegs, (size_t)fa.localSizeBytes,
-                                h->fw_mfma ? h->fw_mfma : ((h->wide && h->cfg.n_hidden % 32 == 0) ? 1 : 0),
+                                g_seg[pl.kind].name, h->cfg.task, h->cfg.n_in, h->cfg.n_out,
+                                pl.wide() && pl.groups > 1 ? "speculative-wide" : g_seg[pl.kind].label,
+                                pl.grid(h->cfg.n_replicas_local), pl.threads, pl.seg_lds, pl.groups, slots, h->num_cus, per_cu, fa.numRegs, (size_t)fa.localSizeBytes,
+                                pl.fw_mfma ? pl.fw_mfma : ((pl.wide() && h->cfg.n_hidden % 32 == 0) ? 1 : 0),
                                 h->comm.kind == COMM_NONE ? "none" : (h->cfg.label_swap ? "labels" : (resolved_xchg_mode(h) == PTNN_XCHG_GATHER ? "gather" : "boundary")),
-                                h->wide_res ? 1 : 0, h->compact ? 1 : 0,
-                                (h->persistent && h->comm.kind == COMM_NONE) ? "one per ptnn_run (swap rounds inside)" : "one per swap interval");
+                                pl.kind == SEG_WIDE_RES ? 1 : 0, pl.compact ? 1 : 0,
+                                (pl.persistent && h->comm.kind == COMM_NONE) ? "one per ptnn_run (swap rounds inside)" : "one per swap interval");
     if (n < 0 || n >= nbytes) return fail(-1, "buffer of %d bytes is too small for the description", nbytes);
     return n;
 }

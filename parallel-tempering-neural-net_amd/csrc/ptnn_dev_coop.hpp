@@ -55,12 +55,14 @@ template <int I> struct SplitK {
     static constexpr bool OK = (KB == 1 || KB == 2 || KB == 4);
 };
 // LDS floats of the split images: data {3 levels x Npad rows}, remainder columns (fp32, transposed), labels, weights
-// {3 levels x Hpad rows}, per-tile partial sums
+// {3 levels x Hpad rows}, per-tile partial sums.  CH, KR: SplitK<I>'s chunks per row and fp32 k-steps (the host sizes LDS with it)
+__host__ __device__ inline size_t split_lds_floats(int CH, int KR, int O, int H, int Npad) {
+    const int Hpad = ((H + 31) >> 5) << 5;
+    return (size_t)3 * Npad * CH * 4 + (size_t)2 * KR * Npad + (size_t)Npad + (size_t)3 * Hpad * CH * 4 + (size_t)(Hpad >> 5) * Npad * O;
+}
 template <int I>
 __host__ __device__ inline size_t mfma_split_lds_floats(int O, int H, int Npad) {
-    typedef SplitK<I> K;
-    const int Hpad = ((H + 31) >> 5) << 5;
-    return (size_t)3 * Npad * K::CH * 4 + (size_t)2 * K::KR * Npad + (size_t)Npad + (size_t)3 * Hpad * K::CH * 4 + (size_t)(Hpad >> 5) * Npad * O;
+    return split_lds_floats(SplitK<I>::CH, SplitK<I>::KR, O, H, Npad);
 }
 struct SplitLds { uint4* xs; float* xr; float* ylab; uint4* as; float* part; };
 template <int I>

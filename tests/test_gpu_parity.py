@@ -1098,6 +1098,37 @@ def test_prefetching_tree_refusals_and_auto_choice():
 
 
 @pytest.mark.gpu
+def test_refused_set_data_leaves_the_handle_as_it_was():
+    """A set_data call that is refused (here: a data set too large for LDS) changes nothing: the handle keeps its data, its
+    schedule (Ionosphere cooperative with the split-operand forward pass) and its buffers, and runs exactly as a fresh handle
+    given the same data and state."""
+    from ptnn_amd import _lib, ladder, philox
+    d = ds()
+    train, test = d["ions_train"], d["ions_test"]
+    topo, R = (34, 50, 2), 8
+    kw = dict(R_local=R, R_global=R, first=0, S=40, si=10, use_lg=False, lr=0.01, seed=3, schedule=1)
+    P = topo[0] * topo[1] + topo[1] * topo[2] + topo[1] + topo[2]
+    w0 = np.stack([philox.initial_weights(3, r, P) for r in range(R)])
+    T = ladder.temperatures(R, 10)
+    s = parity.make_sampler(1, topo, train, test, **kw)
+    before = s.describe()
+    assert before["forward_mfma"] == 2, before
+    big = np.tile(train, (2000 // len(train) + 1, 1))[:2000]
+    with pytest.raises(_lib.PtnnError, match="working set"):
+        s.set_data(big, test)
+    assert s.describe() == before
+    out = []
+    for smp in (s, parity.make_sampler(1, topo, train, test, **kw)):
+        smp.set_state(w0, T); smp.run(-1); smp.sync()
+        out.append((smp.traces(), smp.swap_stats(), smp.swap_log().copy()))
+        smp.close()
+    (tr_a, st_a, log_a), (tr_b, st_b, log_b) = out
+    assert st_a == st_b and np.array_equal(log_a, log_b)
+    for k in tr_a:
+        assert np.array_equal(tr_a[k], tr_b[k], equal_nan=True), k
+
+
+@pytest.mark.gpu
 def test_prefetching_tree_streams_and_resumes():
     """The tree schedule under the run-time features of the boundary: a trace ring drained in windows whose chunk sizes cut
     rounds short anywhere (7, 1, 13 steps), a checkpoint taken in the middle of a swap interval and restored into a fresh
