@@ -284,6 +284,54 @@ typedef struct ptnn_predict_spec {
 
 int ptnn_predict(ptnn_handle *h, const ptnn_predict_spec *spec);
 
+/* ---- convergence diagnostics (nothing in the reference: it reports no R-hat, effective sample size or Monte Carlo error) ----
+ * Classic split-R-hat and split-ESS (Gelman et al., BDA3 11.4-11.5; Geyer's initial monotone sequence as in the Stan Reference
+ * Manual; not rank-normalised), with the index arithmetic of DESIGN.md section 12.  A quantity is a weight or a scalar trace
+ * column; its C selected chains of n >= 4 draws each are split into their first and last h = n / 2 draws (an odd n drops the
+ * middle draw): M = 2C split chains.  Draws are fp32, every mean, product and sum is double.
+ * Source: the handle's trace -- rows step0, step0 + thin, ... < step0 + nsteps of the local replicas listed (NULL = all, in
+ * order), the residency, checkpoint and ring rules and error texts of ptnn_predict; compact traces resolve the vector through its
+ * TR_SRC row -- or, when draws != NULL, host draws [n_chains, n_draws, n_quantities].  Quantities of the trace source: the weights
+ * params[n_params] (NULL = all P; a list with n_params = 0 = none), then the scalar columns whose bit (1 << PTNN_TR_*) is set in
+ * `scalars`, in PTNN_TR_ order (LIKEH, RMSE_TR, RMSE_TE, ACC_TR, ACC_TE; regression: ACC_TR holds eta = log tau^2, see
+ * ptnn_get_trace_rows).  Outputs, any may be NULL, quantity-major in that order: mean [Q] and var [Q] (every selected draw pooled,
+ * ddof 1); r_hat [Q] (NaN where every draw is equal, +inf where every split chain is constant but they differ); ess [Q] (NaN where
+ * every draw is equal); trunc_lag [Q] (max_t of the pair loop); ess_chain [C, Q] (the same estimator on each chain alone, M = 2);
+ * rho [n_lags, Q] (the raw combined autocorrelation rho_t for t < n_lags <= h, before the positivity and monotone edits).
+ * Runs on the handle's stream behind everything queued and returns when done; quantities are processed in blocks whose scratch
+ * stays under $PTNN_CONVERGENCE_SCRATCH_BYTES (read per call, default 1 GiB), which changes no result.  Touches no chain state,
+ * tape, counter or trace row.  Not with a communicator attached (one GPU only). */
+#define PTNN_TR_LIKEH 0
+#define PTNN_TR_RMSE_TR 1
+#define PTNN_TR_RMSE_TE 2
+#define PTNN_TR_ACC_TR 3
+#define PTNN_TR_ACC_TE 4
+#define PTNN_TR_ACCEPT 5
+#define PTNN_TR_LOGALPHA 6
+#define PTNN_TR_SRC 7
+
+typedef struct ptnn_convergence_spec {
+    int32_t struct_bytes;         /* = sizeof(ptnn_convergence_spec): ABI guard */
+    /* source 1: the trace (used when draws == NULL) */
+    const int32_t *replicas;      /* local replica indices, or NULL = all */
+    int32_t n_replicas;           /* entries of replicas (ignored when NULL) */
+    int32_t step0, nsteps, thin;  /* trace rows step0, step0 + thin, ... < step0 + nsteps (thin >= 1) */
+    const int32_t *params;        /* weight indices, or NULL = all P */
+    int32_t n_params;             /* entries of params (ignored when NULL) */
+    int32_t scalars;              /* bit mask over PTNN_TR_LIKEH .. PTNN_TR_ACC_TE */
+    /* source 2: host draws */
+    const float *draws;           /* [n_chains, n_draws, n_quantities] or NULL */
+    int32_t n_chains, n_draws, n_quantities;
+    int32_t n_lags;               /* rows of rho (0 = none) */
+    /* outputs */
+    double *mean, *var, *r_hat, *ess;
+    int32_t *trunc_lag;
+    double *ess_chain;            /* [C, Q] */
+    double *rho;                  /* [n_lags, Q] */
+} ptnn_convergence_spec;
+
+int ptnn_convergence(ptnn_handle *h, const ptnn_convergence_spec *spec);
+
 /* the HIP stream (hipStream_t) all of this handle's work is queued on: lets the caller order its collectives after the
  * segment / before the swap kernels on the device instead of synchronising the host */
 int ptnn_stream(ptnn_handle *h, void **hip_stream);

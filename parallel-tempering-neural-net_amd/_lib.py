@@ -43,6 +43,23 @@ class PredictSpec(C.Structure):
     ]
 
 
+# scalar trace columns (PTNN_TR_* of include/ptnn.h) that ptnn_convergence takes as quantities
+TR_LIKEH, TR_RMSE_TR, TR_RMSE_TE, TR_ACC_TR, TR_ACC_TE, TR_ACCEPT, TR_LOGALPHA, TR_SRC = range(8)
+
+
+class ConvergenceSpec(C.Structure):
+    """ptnn_convergence_spec (include/ptnn.h)."""
+    _fields_ = [
+        ("struct_bytes", C.c_int32),
+        ("replicas", C.POINTER(C.c_int32)), ("n_replicas", C.c_int32), ("step0", C.c_int32), ("nsteps", C.c_int32), ("thin", C.c_int32),
+        ("params", C.POINTER(C.c_int32)), ("n_params", C.c_int32), ("scalars", C.c_int32),
+        ("draws", C.POINTER(C.c_float)), ("n_chains", C.c_int32), ("n_draws", C.c_int32), ("n_quantities", C.c_int32),
+        ("n_lags", C.c_int32),
+        ("mean", C.POINTER(C.c_double)), ("var", C.POINTER(C.c_double)), ("r_hat", C.POINTER(C.c_double)), ("ess", C.POINTER(C.c_double)),
+        ("trunc_lag", C.POINTER(C.c_int32)), ("ess_chain", C.POINTER(C.c_double)), ("rho", C.POINTER(C.c_double)),
+    ]
+
+
 def library_path():
     return os.environ.get("PTNN_LIBRARY", os.path.join(_HERE, "libptnn.so"))
 
@@ -121,6 +138,7 @@ SYMBOLS = {
     "ptnn_trace_image_fetch": (C.c_int, [C.c_void_p, C.c_int, C.c_int]),
     "ptnn_trace_image_wait": (C.c_int, [C.c_void_p, C.c_int]),
     "ptnn_predict": (C.c_int, [C.c_void_p, C.POINTER(PredictSpec)]),
+    "ptnn_convergence": (C.c_int, [C.c_void_p, C.POINTER(ConvergenceSpec)]),
 }
 
 
@@ -515,6 +533,60 @@ class Sampler:
         spec.n_samples, spec.n_distinct = C.pointer(ns), C.pointer(nd)
         self._check(self.lib.ptnn_predict(self.h, C.byref(spec)))
         out["n_samples"], out["n_distinct"] = ns.value, nd.value
+        return out
+
+    def convergence(self, *, replicas=None, step0=0, nsteps=None, thin=1, params=None, scalars=(), draws=None, per_chain=False,
+                    n_lags=0):
+        """ptnn_convergence: split-R-hat and split-ESS on the device.  Source: the trace rows step0, step0 + thin, ... < step0 + nsteps
+        of `replicas` (None = all) -- quantities: the weights `params` (None = all P), then the scalar columns `scalars` (TR_LIKEH ..
+        TR_ACC_TE) in TR_ order -- or host draws [C, n, Q].  -> dict(mean, var, r_hat, ess [Q] float64, trunc_lag [Q] int32,
+        ess_chain [C, Q] float64 (per_chain), rho [n_lags, Q] float64 (n_lags > 0), n_chains, n_draws); what was not asked for is None."""
+        spec = ConvergenceSpec()
+        spec.struct_bytes = C.sizeof(ConvergenceSpec)
+        keep = []
+        if draws is not None:
+            da = _f32(draws)
+            if da.ndim != 3:
+                raise ValueError(f"draws must be [n_chains, n_draws, n_quantities], got shape {da.shape}")
+            keep.append(da)
+            spec.draws = _ptr(da)
+            nc, nd, Q = da.shape
+            spec.n_chains, spec.n_draws, spec.n_quantities = nc, nd, Q
+        else:
+            if replicas is not None:
+                ra = np.ascontiguousarray(replicas, dtype=np.int32).reshape(-1)
+                keep.append(ra)
+                spec.replicas, spec.n_replicas = _ptr(ra, _ip), ra.size
+                nc = ra.size
+            else:
+                nc = self.R
+            spec.step0 = int(step0)
+            spec.nsteps = int(self.S - step0 if nsteps is None else nsteps)
+            spec.thin = int(thin)
+            nd = max(0, -(-spec.nsteps // max(1, spec.thin)))
+            if params is not None:
+                pa = np.ascontiguousarray(params, dtype=np.int32).reshape(-1)
+                keep.append(pa)
+                spec.params = pa.ctypes.data_as(_ip)              # a list, even an empty one (= no weight)
+                spec.n_params = pa.size
+                n_par = pa.size
+            else:
+                n_par = self.P
+            mask = 0
+            for col in scalars:
+                mask |= 1 << int(col)
+            spec.scalars = mask
+            Q = n_par + sum(1 for c in range(8) if mask >> c & 1)
+        Q = max(int(Q), 0)
+        out = dict(mean=np.empty(Q), var=np.empty(Q), r_hat=np.empty(Q), ess=np.empty(Q), trunc_lag=np.empty(Q, np.int32),
+                   ess_chain=np.empty((max(nc, 0), Q)) if per_chain else None,
+                   rho=np.empty((int(n_lags), Q)) if n_lags else None)
+        for k in ("mean", "var", "r_hat", "ess", "ess_chain", "rho"):
+            setattr(spec, k, _ptr(out[k], C.POINTER(C.c_double)))
+        spec.trunc_lag = _ptr(out["trunc_lag"], _ip)
+        spec.n_lags = int(n_lags)
+        self._check(self.lib.ptnn_convergence(self.h, C.byref(spec)))
+        out["n_chains"], out["n_draws"] = int(nc), int(nd)
         return out
 
     def langevin_gradient(self, w):

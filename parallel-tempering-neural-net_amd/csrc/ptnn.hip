@@ -1806,13 +1806,34 @@ struct DeviceScratch {            // every buffer of one ptnn_predict call, rele
     }
 };
 
-size_t predict_scratch_budget() {
-    const char* e = std::getenv("PTNN_PREDICT_SCRATCH_BYTES");
+size_t scratch_budget(const char* var) {    // $var bytes, default 1 GiB
+    const char* e = std::getenv(var);
     if (e && *e) {
         const long long v = std::atoll(e);
         if (v > 0) return (size_t)v;
     }
     return (size_t)1 << 30;
+}
+// the trace rows step0, step0 + thin, ... < step0 + nsteps of the listed local replicas (NULL = all): the residency, checkpoint
+// and ring rules of ptnn_get_traces; *reps = the chains, *m = rows per chain.  Shared by ptnn_predict and ptnn_convergence.
+int select_trace_rows(const ptnn_handle* h, const int32_t* replicas, int n_replicas, int step0, int nsteps, int thin,
+                      std::vector<int32_t>* reps, int* m) {
+    const int S = h->cfg.n_samples, Rl = h->cfg.n_replicas_local, cap = h->cap;
+    if (step0 < 0 || nsteps < 1 || step0 + nsteps > S) return fail(-1, "trace range [%d, %d) outside [0, %d)", step0, step0 + nsteps, S);
+    if (step0 + nsteps > h->cur + 1) return fail(-1, "rows up to %d requested but only %d MH steps have been queued", step0 + nsteps - 1, h->cur);
+    if (step0 < h->first_row) return fail(-1, "rows below %d were produced before the checkpoint these chains were restored from", h->first_row);
+    if (step0 < h->cur + 1 - cap) return fail(-1, "row %d has already been overwritten in the trace ring (capacity %d, %d steps done)", step0, cap, h->cur);
+    reps->clear();
+    if (replicas) {
+        for (int k = 0; k < n_replicas; ++k) {
+            if (replicas[k] < 0 || replicas[k] >= Rl) return fail(-1, "replica %d out of range [0, %d)", replicas[k], Rl);
+            reps->push_back(replicas[k]);
+        }
+    } else {
+        for (int r = 0; r < Rl; ++r) reps->push_back(r);
+    }
+    *m = (nsteps + thin - 1) / thin;
+    return 0;
 }
 }  // namespace
 
@@ -1837,7 +1858,7 @@ int ptnn_predict(ptnn_handle* h, const ptnn_predict_spec* spec) {
     if (s.order_stats && s.n_ranks == 0) return fail(-1, "order_stats requested without ranks");
     if (int rc = check_ready(h)) return rc;
     if (h->comm.kind != COMM_NONE) return fail(-3, "ptnn_predict serves one GPU: this handle has a communicator attached");
-    const int I = h->cfg.n_in, H = h->cfg.n_hidden, O = h->cfg.n_out, P = h->P, Rl = h->cfg.n_replicas_local, cap = h->cap;
+    const int I = h->cfg.n_in, H = h->cfg.n_hidden, O = h->cfg.n_out, P = h->P, cap = h->cap;
     if (s.vote && h->cfg.task != PTNN_TASK_CLS) return fail(-1, "vote: a regression has no classes");
     if (s.x_source == PTNN_PREDICT_X_TRAIN && s.n_rows != h->Ntr) return fail(-1, "n_rows = %d but the train set has %d rows", s.n_rows, h->Ntr);
     if (s.x_source == PTNN_PREDICT_X_TEST && s.n_rows != h->Nte) return fail(-1, "n_rows = %d but the test set has %d rows", s.n_rows, h->Nte);
@@ -1856,21 +1877,7 @@ int ptnn_predict(ptnn_handle* h, const ptnn_predict_spec* spec) {
             M = s.n_w;
         }
     } else {
-        const int S = h->cfg.n_samples;
-        const int step0 = s.step0, nsteps = s.nsteps;
-        if (step0 < 0 || nsteps < 1 || step0 + nsteps > S) return fail(-1, "trace range [%d, %d) outside [0, %d)", step0, step0 + nsteps, S);
-        if (step0 + nsteps > h->cur + 1) return fail(-1, "rows up to %d requested but only %d MH steps have been queued", step0 + nsteps - 1, h->cur);
-        if (step0 < h->first_row) return fail(-1, "rows below %d were produced before the checkpoint these chains were restored from", h->first_row);
-        if (step0 < h->cur + 1 - cap) return fail(-1, "row %d has already been overwritten in the trace ring (capacity %d, %d steps done)", step0, cap, h->cur);
-        if (s.replicas) {
-            for (int k = 0; k < s.n_replicas; ++k) {
-                if (s.replicas[k] < 0 || s.replicas[k] >= Rl) return fail(-1, "replica %d out of range [0, %d)", s.replicas[k], Rl);
-                reps.push_back(s.replicas[k]);
-            }
-        } else {
-            for (int r = 0; r < Rl; ++r) reps.push_back(r);
-        }
-        m = (nsteps + s.thin - 1) / s.thin;
+        if (int rc = select_trace_rows(h, s.replicas, s.n_replicas, s.step0, s.nsteps, s.thin, &reps, &m)) return rc;
         n_items = (long long)reps.size() * m;
         M = n_items;
     }
@@ -1950,7 +1957,7 @@ int ptnn_predict(ptnn_handle* h, const ptnn_predict_spec* spec) {
     }
     if (h->cfg.task == PTNN_TASK_CLS) HIP_TRY(mem.alloc(&d_votes, (size_t)ncols));
     // stage b + c in blocks of rows: fx scratch U x (rows x O) floats under the budget
-    const size_t budget = predict_scratch_budget();
+    const size_t budget = scratch_budget("PTNN_PREDICT_SCRATCH_BYTES");
     const size_t col_bytes = (size_t)U * sizeof(float);
     long long rows_blk = (long long)(budget / (col_bytes * O));
     rows_blk = std::max(1LL, std::min<long long>(rows_blk, s.n_rows));
@@ -2003,6 +2010,171 @@ int ptnn_predict(ptnn_handle* h, const ptnn_predict_spec* spec) {
     if (int rc = wait_stream(h)) return rc;
     if (s.vote)
         for (int c = 0; c < ncols; ++c) s.vote[c] = (double)votes_h[(size_t)c] / (double)M;
+    return 0;
+}
+
+// ---- convergence diagnostics (ptnn_dev_convergence.hpp) ----
+static_assert(PTNN_TR_LIKEH == TR_LIKEH && PTNN_TR_ACC_TE == TR_ACC_TE && PTNN_TR_ACCEPT == TR_ACCEPT && PTNN_TR_SRC == TR_SRC, "ptnn.h TR order");
+
+int ptnn_convergence(ptnn_handle* h, const ptnn_convergence_spec* spec) {
+    // argument checks first: none of them needs the handle or a device
+    if (!spec) return fail(-1, "null argument");
+    if (spec->struct_bytes != (int32_t)sizeof(ptnn_convergence_spec))
+        return fail(-1, "ptnn_convergence_spec.struct_bytes = %d, expected %d", spec->struct_bytes, (int)sizeof(ptnn_convergence_spec));
+    const ptnn_convergence_spec& s = *spec;
+    const bool host_src = s.draws != nullptr;
+    constexpr int scalar_cols = (1 << TR_LIKEH) | (1 << TR_RMSE_TR) | (1 << TR_RMSE_TE) | (1 << TR_ACC_TR) | (1 << TR_ACC_TE);
+    if (host_src) {
+        if (s.n_chains < 1) return fail(-1, "n_chains = %d must be >= 1", s.n_chains);
+        if (s.n_draws < 4) return fail(-1, "n_draws = %d: the split chains need at least 4 draws per chain", s.n_draws);
+        if (s.n_quantities < 1) return fail(-1, "n_quantities = %d must be >= 1", s.n_quantities);
+    } else {
+        if (s.thin < 1) return fail(-1, "thin = %d must be >= 1", s.thin);
+        if (s.replicas && s.n_replicas < 1) return fail(-1, "n_replicas = %d with a replica list", s.n_replicas);
+        if (s.params && s.n_params < 0) return fail(-1, "n_params = %d with a parameter list", s.n_params);
+        if (s.scalars & ~scalar_cols)
+            return fail(-1, "scalars = 0x%x: only TR_LIKEH, TR_RMSE_TR, TR_RMSE_TE, TR_ACC_TR and TR_ACC_TE are quantities "
+                            "(not TR_ACCEPT, TR_LOGALPHA or TR_SRC)", (unsigned)s.scalars);
+    }
+    if (s.n_lags < 0) return fail(-1, "n_lags = %d must be >= 0", s.n_lags);
+    if (s.n_lags > 0 && !s.rho) return fail(-1, "n_lags = %d but rho is NULL", s.n_lags);
+    if (s.rho && s.n_lags == 0) return fail(-1, "rho requested with n_lags = 0");
+    if (int rc = check_ready(h)) return rc;
+    if (h->comm.kind != COMM_NONE) return fail(-3, "ptnn_convergence serves one GPU: this handle has a communicator attached");
+    const int P = h->P, cap = h->cap;
+    // the selection: chains, draws per chain, the column of every quantity
+    std::vector<int32_t> reps;
+    std::vector<int> qcol;
+    int C = 0, n = 0;
+    if (host_src) {
+        C = s.n_chains; n = s.n_draws;
+        for (int q = 0; q < s.n_quantities; ++q) qcol.push_back(q);
+    } else {
+        if (int rc = select_trace_rows(h, s.replicas, s.n_replicas, s.step0, s.nsteps, s.thin, &reps, &n)) return rc;
+        C = (int)reps.size();
+        if (n < 4) return fail(-1, "%d draws per chain selected: the split chains need at least 4", n);
+        if (s.params) {
+            for (int k = 0; k < s.n_params; ++k) {
+                if (s.params[k] < 0 || s.params[k] >= P) return fail(-1, "parameter %d out of range [0, %d)", s.params[k], P);
+                qcol.push_back(s.params[k]);
+            }
+        } else {
+            for (int p = 0; p < P; ++p) qcol.push_back(p);
+        }
+        for (int c = 0; c < TR_COUNT; ++c)
+            if (s.scalars & (1 << c)) qcol.push_back(-1 - c);
+        if (qcol.empty()) return fail(-1, "no quantity selected");
+    }
+    const int hl = n / 2, M = 2 * C, Q = (int)qcol.size();
+    if (s.n_lags > hl) return fail(-1, "n_lags = %d exceeds the split-chain length %d", s.n_lags, hl);
+    const bool per_chain = s.ess_chain != nullptr;
+    const int NS = 1 + (per_chain ? C : 0);
+
+    HIP_TRY(hipSetDevice(h->cfg.device_id));
+    if (int rc = finish_stream(h)) return rc;          // behind everything queued; a failed run is refused here
+    hipStream_t st = h->stream;
+    DeviceScratch mem;
+    int *d_qcol = nullptr, *d_reps = nullptr, *d_error = nullptr;
+    float* d_draws = nullptr;
+    HIP_TRY(mem.alloc(&d_qcol, (size_t)Q));
+    HIP_TRY(hipMemcpyAsync(d_qcol, qcol.data(), (size_t)Q * sizeof(int), hipMemcpyHostToDevice, st));
+    HIP_TRY(mem.alloc(&d_error, 1));
+    HIP_TRY(hipMemsetAsync(d_error, 0, sizeof(int), st));
+    ConvGather ga{};
+    if (host_src) {
+        const size_t nd = (size_t)C * n * Q;
+        HIP_TRY(mem.alloc(&d_draws, nd));
+        HIP_TRY(hipMemcpyAsync(d_draws, s.draws, nd * sizeof(float), hipMemcpyHostToDevice, st));
+        ga.host = 1; ga.draws = d_draws; ga.Qh = Q;
+    } else {
+        HIP_TRY(mem.alloc(&d_reps, reps.size()));
+        HIP_TRY(hipMemcpyAsync(d_reps, reps.data(), reps.size() * sizeof(int32_t), hipMemcpyHostToDevice, st));
+        ga.host = 0; ga.pos_w = h->d_pos_w; ga.scal = h->d_scal; ga.replicas = d_reps; ga.cap = cap; ga.PW = h->PW;
+        ga.step0 = s.step0; ga.thin = s.thin; ga.compact = h->plan.compact ? 1 : 0;
+    }
+    ga.C = C; ga.n = n; ga.h = hl; ga.error = d_error;
+    // outputs of every quantity
+    double *d_mean = nullptr, *d_var = nullptr, *d_rhat = nullptr, *d_ess = nullptr, *d_essc = nullptr, *d_rho = nullptr;
+    int* d_trunc = nullptr;
+    HIP_TRY(mem.alloc(&d_mean, (size_t)Q));
+    HIP_TRY(mem.alloc(&d_var, (size_t)Q));
+    HIP_TRY(mem.alloc(&d_rhat, (size_t)Q));
+    HIP_TRY(mem.alloc(&d_ess, (size_t)Q));
+    HIP_TRY(mem.alloc(&d_trunc, (size_t)Q));
+    if (per_chain) HIP_TRY(mem.alloc(&d_essc, (size_t)C * Q));
+    if (s.n_lags) HIP_TRY(mem.alloc(&d_rho, (size_t)s.n_lags * Q));
+    // blocks of quantities: the scratch of one quantity, every stage's
+    const size_t per_q = sizeof(double) * ((size_t)M * hl + 2 * (size_t)M + 2 * (size_t)C + 2 + (size_t)CONV_MAX_LAGS * C)
+                       + sizeof(ConvSeq) * NS + sizeof(int) * (3 + (per_chain ? (size_t)C : 0));
+    const int Qb = (int)std::max<size_t>(1, std::min<size_t>(scratch_budget("PTNN_CONVERGENCE_SCRATCH_BYTES") / per_q, (size_t)Q));
+    double *d_x = nullptr, *d_smean = nullptr, *d_ssq = nullptr, *d_csum = nullptr, *d_cm2 = nullptr, *d_pmean = nullptr, *d_pvar = nullptr;
+    double* d_chain = nullptr;
+    ConvSeq* d_seq = nullptr;
+    int *d_full = nullptr, *d_copen = nullptr, *d_any = nullptr, *d_open = nullptr;
+    HIP_TRY(mem.alloc(&d_x, (size_t)Qb * M * hl));
+    HIP_TRY(mem.alloc(&d_smean, (size_t)Qb * M));
+    HIP_TRY(mem.alloc(&d_ssq, (size_t)Qb * M));
+    HIP_TRY(mem.alloc(&d_csum, (size_t)Qb * C));
+    HIP_TRY(mem.alloc(&d_cm2, (size_t)Qb * C));
+    HIP_TRY(mem.alloc(&d_pmean, (size_t)Qb));
+    HIP_TRY(mem.alloc(&d_pvar, (size_t)Qb));
+    HIP_TRY(mem.alloc(&d_chain, (size_t)CONV_MAX_LAGS * C * Qb));
+    HIP_TRY(mem.alloc(&d_seq, (size_t)Qb * NS));
+    HIP_TRY(mem.alloc(&d_full, (size_t)Qb));
+    if (per_chain) HIP_TRY(mem.alloc(&d_copen, (size_t)Qb * C));
+    HIP_TRY(mem.alloc(&d_any, (size_t)Qb));
+    HIP_TRY(mem.alloc(&d_open, (size_t)Qb));
+    std::vector<int> any_h((size_t)Qb), open_h((size_t)Qb);
+    for (int q0 = 0; q0 < Q; q0 += Qb) {
+        const int nq = std::min(Qb, Q - q0);
+        // 1. gather and moments
+        ga.qcol = d_qcol + q0; ga.nq = nq; ga.x = d_x; ga.smean = d_smean; ga.ssq = d_ssq; ga.csum = d_csum; ga.cm2 = d_cm2;
+        hipLaunchKernelGGL(conv_gather_kernel, dim3((unsigned)C, (unsigned)((nq + CONV_TILE - 1) / CONV_TILE)), dim3(CONV_THREADS), 0, st, ga);
+        HIP_TRY(hipGetLastError());
+        // 2. W, var+ and the state of every sequence
+        ConvMoments mo{d_smean, d_ssq, d_csum, d_cm2, nq, C, n, hl, NS, d_seq, d_pmean, d_pvar};
+        const long long nseq = (long long)nq * NS;
+        hipLaunchKernelGGL(conv_moments_kernel, dim3((unsigned)((nseq + CONV_THREADS - 1) / CONV_THREADS)), dim3(CONV_THREADS), 0, st, mo);
+        HIP_TRY(hipGetLastError());
+        HIP_TRY(hipMemsetAsync(d_full, 1, (size_t)nq * sizeof(int), st));             // non-zero: every sequence starts open
+        if (per_chain) HIP_TRY(hipMemsetAsync(d_copen, 1, (size_t)nq * C * sizeof(int), st));
+        int n_open = nq;
+        for (int k = 0; k < nq; ++k) open_h[(size_t)k] = k;
+        HIP_TRY(hipMemcpyAsync(d_open, open_h.data(), (size_t)nq * sizeof(int), hipMemcpyHostToDevice, st));
+        // 3. blocks of lags, each twice the last, for the quantities with a sequence still open
+        for (int t0 = 0, nl = CONV_LAG_TILE; n_open > 0 && t0 < hl; t0 += nl, nl = std::min(2 * nl, CONV_MAX_LAGS)) {
+            nl = std::min(nl, (hl - t0 + CONV_LAG_TILE - 1) / CONV_LAG_TILE * CONV_LAG_TILE);
+            ConvLags la{d_x, C, hl, d_open, n_open, d_full, d_copen, t0, d_chain};
+            hipLaunchKernelGGL(conv_lags_kernel, dim3((unsigned)((n_open + CONV_TILE - 1) / CONV_TILE), (unsigned)(nl / CONV_LAG_TILE), (unsigned)C), dim3(CONV_THREADS), 0, st, la);
+            HIP_TRY(hipGetLastError());
+            ConvStep sp{d_chain, d_open, n_open, C, hl, NS, t0, nl, s.n_lags, Q, q0, d_seq, d_full, d_copen, d_any, d_rho};
+            hipLaunchKernelGGL(conv_step_kernel, dim3((unsigned)n_open), dim3(WAVE), 0, st, sp);
+            HIP_TRY(hipGetLastError());
+            HIP_TRY(hipMemcpyAsync(any_h.data(), d_any, (size_t)nq * sizeof(int), hipMemcpyDeviceToHost, st));
+            if (int rc = wait_stream(h)) return rc;
+            const int was_open = n_open;
+            n_open = 0;
+            for (int k = 0; k < was_open; ++k)
+                if (any_h[(size_t)open_h[(size_t)k]]) open_h[(size_t)n_open++] = open_h[(size_t)k];
+            if (n_open) HIP_TRY(hipMemcpyAsync(d_open, open_h.data(), (size_t)n_open * sizeof(int), hipMemcpyHostToDevice, st));
+        }
+        if (n_open) return fail(-2, "%d quantities still open after every lag (internal error)", n_open);
+        // 4. tau, ess, r_hat
+        ConvFinish fi{d_seq, d_pmean, d_pvar, nq, NS, C, hl, Q, q0, d_mean, d_var, d_rhat, d_ess, d_essc, d_trunc};
+        hipLaunchKernelGGL(conv_finish_kernel, dim3((unsigned)((nseq + CONV_THREADS - 1) / CONV_THREADS)), dim3(CONV_THREADS), 0, st, fi);
+        HIP_TRY(hipGetLastError());
+    }
+    int err = 0;
+    HIP_TRY(hipMemcpyAsync(&err, d_error, sizeof(int), hipMemcpyDeviceToHost, st));
+    if (s.mean) HIP_TRY(hipMemcpyAsync(s.mean, d_mean, (size_t)Q * sizeof(double), hipMemcpyDeviceToHost, st));
+    if (s.var) HIP_TRY(hipMemcpyAsync(s.var, d_var, (size_t)Q * sizeof(double), hipMemcpyDeviceToHost, st));
+    if (s.r_hat) HIP_TRY(hipMemcpyAsync(s.r_hat, d_rhat, (size_t)Q * sizeof(double), hipMemcpyDeviceToHost, st));
+    if (s.ess) HIP_TRY(hipMemcpyAsync(s.ess, d_ess, (size_t)Q * sizeof(double), hipMemcpyDeviceToHost, st));
+    if (s.trunc_lag) HIP_TRY(hipMemcpyAsync(s.trunc_lag, d_trunc, (size_t)Q * sizeof(int32_t), hipMemcpyDeviceToHost, st));
+    if (per_chain) HIP_TRY(hipMemcpyAsync(s.ess_chain, d_essc, (size_t)C * Q * sizeof(double), hipMemcpyDeviceToHost, st));
+    if (s.n_lags) HIP_TRY(hipMemcpyAsync(s.rho, d_rho, (size_t)s.n_lags * Q * sizeof(double), hipMemcpyDeviceToHost, st));
+    if (int rc = wait_stream(h)) return rc;
+    if (err) return fail(-2, "%d selected compact trace rows refer to rows that are not resident (internal error)", err);
     return 0;
 }
 

@@ -106,6 +106,20 @@ __global__ void __launch_bounds__(PRED_THREADS) predict_forward_kernel(const Pre
 
 #ifndef PTNN_SHAPE_TU      // shape-independent kernels: defined in the main translation unit only
 
+// Where trace row `step` of local replica `rep` keeps its vector: the float offset in d_pos_w [Rl][cap][PW] -- its own ring slot,
+// or with compact traces the row its TR_SRC names (a rejected step wrote no vector).  *src_out = the step whose row that is; a
+// TR_SRC outside [0, step] is counted in *error and the step's own slot used, which keeps the address inside the ring.  Shared by
+// ptnn_predict (predict_runs_kernel) and ptnn_convergence (conv_gather_kernel).
+__device__ __forceinline__ long long trace_vector_offset(const float* scal, long long rep, int cap, int PW, int step, int compact,
+                                                         int* error, int* src_out) {
+    const int slot = step % cap;
+    if (!compact) { *src_out = step; return (rep * cap + slot) * (long long)PW; }
+    int src = __float_as_int(scal[(rep * cap + slot) * TR_COUNT + TR_SRC]);
+    if (src < 0 || src > step) { atomicAdd(error, 1); src = step; }   // keeps the address inside the ring
+    *src_out = src;
+    return (rep * cap + src % cap) * (long long)PW;
+}
+
 // stage a, part 1: per selected item, where its vector is and whether it starts a new run
 struct PredictSel {
     // trace source (items = n_chains x m selected rows, chain-major)
@@ -136,13 +150,7 @@ __global__ void __launch_bounds__(PRED_THREADS) predict_runs_kernel(const Predic
     const int c = (int)(i / s.m), j = (int)(i % s.m);
     const long long rep = s.replicas[c];
     auto resolve = [&](int jj, int* src_out) -> long long {
-        const int step = s.step0 + jj * s.thin;
-        const int slot = step % s.cap;
-        if (!s.compact) { *src_out = step; return (rep * s.cap + slot) * (long long)s.PW; }
-        int src = __float_as_int(s.scal[(rep * s.cap + slot) * TR_COUNT + TR_SRC]);
-        if (src < 0 || src > step) { atomicAdd(s.error, 1); src = step; }   // keeps the address inside the ring
-        *src_out = src;
-        return (rep * s.cap + src % s.cap) * (long long)s.PW;
+        return trace_vector_offset(s.scal, rep, s.cap, s.PW, s.step0 + jj * s.thin, s.compact, s.error, src_out);
     };
     int src = 0, src_prev = 0;
     const long long off = resolve(j, &src);

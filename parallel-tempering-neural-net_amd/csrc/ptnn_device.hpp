@@ -145,5 +145,8 @@ struct SegDyn {
 #include "ptnn_dev_tree.hpp"                 // prefetching tree schedule (segment_tree_body), with its own swap rounds inside a launch
 #include "ptnn_dev_kernels.hpp"              // model_kernel, persistent_loop, the __global__ segment kernels, the per-shape table
 #include "ptnn_dev_predict.hpp"              // posterior predictive: run-length pass over the selected rows, forward pass, per-column reduction
+#ifndef PTNN_SHAPE_TU
+#include "ptnn_dev_convergence.hpp"          // convergence diagnostics: split-R-hat, split-ESS over trace columns (main translation unit only)
+#endif
 
 }  // namespace ptnn

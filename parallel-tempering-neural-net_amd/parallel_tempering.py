@@ -94,6 +94,15 @@ def lerp_percentile(a, b, gamma):
 Predictive = namedtuple("Predictive", "mean percentiles vote pred_class samples n_samples n_distinct")
 
 
+# convergence_diagnostics' result: names [Q]; mean, sd, r_hat, ess, mcse_mean [Q] float64; ess_chain [n_chains, Q] or None; rho
+# [n_lags, Q] or None; trunc_lag [Q] int32; n_chains, n_draws
+Convergence = namedtuple("Convergence", "names mean sd r_hat ess mcse_mean ess_chain rho trunc_lag n_chains n_draws")
+
+# scalar trace columns convergence_diagnostics takes by name (a regression's acc_train slot holds eta = log tau^2)
+_SCALAR_COLS = {"likelihood": _lib.TR_LIKEH, "rmse_train": _lib.TR_RMSE_TR, "rmse_test": _lib.TR_RMSE_TE, "acc_train": _lib.TR_ACC_TR,
+                "eta": _lib.TR_ACC_TR, "acc_test": _lib.TR_ACC_TE}
+
+
 class ParallelTemperingBase:
     task = None                       # set by the two drop-in subclasses
     rmse_fmt = None                   # REG '%1.8f' (REG:462-464), CLS '%1.2f' (CLS:473-475)
@@ -572,6 +581,74 @@ class ParallelTemperingBase:
         return Predictive(mean=mean, percentiles=bands, vote=out["vote"] if cls else None,
                           pred_class=np.argmax(mean, axis=1) if cls else None, samples=out["samples"],
                           n_samples=out["n_samples"], n_distinct=out["n_distinct"])
+
+    # ------------------------------------------------------------------ convergence diagnostics (not in the reference)
+    def convergence_diagnostics(self, *, burn_in=None, chains="all", thin=1, params=None, scalars=("likelihood",), per_chain=False,
+                                n_lags=0, draws=None):
+        """Split-R-hat, split-ESS and the Monte Carlo standard error of the mean of weights and scalar traces, computed on the GPU
+        from the traces it already holds (classic split-R-hat / split-ESS with Geyer's initial monotone sequence, BDA3 11.4-11.5,
+        not rank-normalised).
+
+        The draws are by default those of the posterior matrix run_chains() returns: every chain's trace rows from
+        int(NumSamples * burn_in) on.  `chains`: "all", "cold" (the temperature-1 chain) or a list of chain indices; `thin`: every
+        thin-th row.  The default chains="all" pools every temperature, as the reference's pos_w does, so R-hat over a ladder also
+        measures the spread between temperatures; chains="cold" with per_chain=True gives the posterior's own figure (a single
+        chain's split-R-hat compares its two halves).  `params`: weight indices (None = all, [] = none); `scalars`: names among
+        likelihood, rmse_train, rmse_test, acc_train, acc_test (regression: eta, the log tau^2 trace, instead of acc_train).
+        `per_chain`: also the ESS of each chain alone; `n_lags`: also the raw combined autocorrelation rho_t, t < n_lags.
+        `draws`: host draws [n_chains, n_draws, Q] instead of the trace (names q0 ..); works whenever the handle exists.
+        -> Convergence(names, mean, sd, r_hat, ess, mcse_mean = sd / sqrt(ess), ess_chain, rho, trunc_lag, n_chains, n_draws)."""
+        if self._sampler is None:
+            raise ValueError("convergence_diagnostics needs the chains' device handle: call initialize_chains() and run_chains() first")
+        if not isinstance(self._sampler, _lib.Sampler):
+            raise ValueError("convergence_diagnostics runs on one GPU: a ladder sharded over several devices is not supported")
+        if draws is not None:
+            d = np.asarray(draws)
+            if d.ndim != 3:
+                raise ValueError(f"draws must be [n_chains, n_draws, n_quantities], got shape {d.shape}")
+            names = [f"q{k}" for k in range(d.shape[2])]
+            out = self._sampler.convergence(draws=d, per_chain=per_chain, n_lags=n_lags)
+        else:
+            S = self.NumSamples
+            if self.label_swap:
+                raise ValueError("label_swap=True: trace rows are kept per chain slot, not per temperature; pass draws=")
+            if 0 < self.trace_capacity < S:
+                raise ValueError(f"trace_capacity = {self.trace_capacity} < NumSamples = {S}: the rows have been streamed off "
+                                 f"the device; pass draws=")
+            if not self._finished:
+                raise ValueError("no finished run_chains() on this object: the trace is incomplete; pass draws=")
+            b = self.burn_in if burn_in is None else burn_in
+            step0 = int(S * b)
+            if chains == "all":
+                reps = None
+            elif chains == "cold":
+                reps = [int(np.argmin(self.temperatures))]
+            else:
+                reps = [int(c) for c in chains]
+                if not reps or min(reps) < 0 or max(reps) >= self.num_chains:
+                    raise ValueError(f"chains {chains!r}: indices must lie in [0, {self.num_chains})")
+            P = self.num_param
+            pidx = None if params is None else [int(p) for p in params]
+            if pidx is not None and any(not (0 <= p < P) for p in pidx):
+                raise ValueError(f"params: weight indices must lie in [0, {P})")
+            reg = self.task != TASK_CLS
+            cols = {}
+            for nm in scalars:
+                if nm not in _SCALAR_COLS or (nm == "eta" and not reg) or (nm == "acc_train" and reg):
+                    allowed = ["likelihood", "rmse_train", "rmse_test", "eta" if reg else "acc_train", "acc_test"]
+                    raise ValueError(f"scalar {nm!r}: one of {allowed}")
+                cols[_SCALAR_COLS[nm]] = nm
+            names = [f"w{p}" for p in (range(P) if pidx is None else pidx)] + [cols[c] for c in sorted(cols)]
+            if not names:
+                raise ValueError("no quantity selected: give params and/or scalars")
+            out = self._sampler.convergence(replicas=reps, step0=step0, nsteps=S - step0, thin=int(thin), params=pidx,
+                                            scalars=sorted(cols), per_chain=per_chain, n_lags=n_lags)
+        sd = np.sqrt(out["var"])
+        with np.errstate(invalid="ignore", divide="ignore"):
+            mcse = sd / np.sqrt(out["ess"])
+        return Convergence(names=names, mean=out["mean"], sd=sd, r_hat=out["r_hat"], ess=out["ess"], mcse_mean=mcse,
+                           ess_chain=out["ess_chain"], rho=out["rho"], trunc_lag=out["trunc_lag"], n_chains=out["n_chains"],
+                           n_draws=out["n_draws"])
 
     def make_directory(self, directory):
         if not os.path.exists(directory):
