@@ -332,6 +332,58 @@ typedef struct ptnn_convergence_spec {
 
 int ptnn_convergence(ptnn_handle *h, const ptnn_convergence_spec *spec);
 
+/* ---- predictive accuracy (nothing in the reference: it compares topologies by RMSE / accuracy only, result.txt) ----
+ * Per data row n: the log pointwise predictive density lppd_n, the WAIC penalty p_waic_n (sample variance of the pointwise
+ * log-likelihood, ddof 1), and the PSIS-LOO estimate elpd_loo_n with its Pareto shape khat_n (Vehtari, Gelman & Gabry 2017;
+ * Pareto smoothing with the Zhang & Stephens 2009 fit and its weakly informative prior), over the expanded multiset of S samples
+ * (a sample with multiplicity c counts c times); DESIGN.md section 13 states every formula.  The pointwise log-likelihood is
+ * untempered: regression ll = -log(2 pi tau^2) / 2 - (y - f)^2 / (2 tau^2) with tau^2 = exp(eta) (REG:200-204), classification
+ * ll = log p_y of the softmax outputs (CLS:209-222); f / p are the fp32 outputs of ptnn_predict's forward pass, everything after
+ * it is double.
+ * Sources: (1) the handle's trace, selected as ptnn_predict selects it (same rules and error texts); a regression takes eta from
+ * the TR_ACC_TR slot of the row that holds the vector (TR_SRC with compact traces), and a row before its chain's first accepted
+ * MH step (no eta recorded yet) is refused.  (2) host vectors w [n_w, P] with eta [n_w] (regression; ignored for classification)
+ * and optional multiplicities.  (3) a host pointwise log-likelihood loglik [n_w, n_rows] (finite doubles) with optional
+ * multiplicities: no forward pass.  Consecutive samples equal in w and eta bits are one distinct sample; the results depend on
+ * the multiset only (bitwise: trace, host vectors, expanded or (distinct, multiplicity), any block size).
+ * Data (sources 1, 2): x_source _TRAIN / _TEST (the handle's rows and targets) or _HOST with x [n_rows, n_in + 1] (last column
+ * the target; classification: an integer label in [0, n_out)).  r_eff > 0: the relative efficiency of the PSIS tail length
+ * M = ceil(min(0.2 S, 3 sqrt(S / r_eff))), at most PTNN_ELPD_TAIL_CAP.  Outputs, any may be NULL: lppd, p_waic, elpd_loo, khat
+ * [n_rows] (khat = +inf where the tail holds <= 4 samples, no smoothing); tail_len [n_rows] (expanded tail count T);
+ * loglik_out [S, n_rows] (the pointwise log-likelihood, expanded, chain-major as ptnn_predict's samples; sources 1, 2);
+ * n_samples = S; n_distinct = distinct samples.
+ * Runs on the handle's stream behind everything queued and returns when done; rows are processed in blocks whose scratch stays
+ * under $PTNN_ELPD_SCRATCH_BYTES (read per call, default 1 GiB), which changes no result.  Touches no chain state, tape, counter
+ * or trace row.  Not with a communicator attached (one GPU only). */
+#define PTNN_ELPD_TAIL_CAP 4096
+
+typedef struct ptnn_elpd_spec {
+    int32_t struct_bytes;         /* = sizeof(ptnn_elpd_spec): ABI guard */
+    /* source 1: the trace (used when w == NULL and loglik == NULL) */
+    const int32_t *replicas;      /* local replica indices, or NULL = all */
+    int32_t n_replicas;           /* entries of replicas (ignored when NULL) */
+    int32_t step0, nsteps, thin;  /* trace rows step0, step0 + thin, ... < step0 + nsteps (thin >= 1) */
+    /* source 2: host vectors */
+    const float *w;               /* [n_w, P] or NULL */
+    const float *eta;             /* [n_w] log tau^2 (regression) */
+    /* source 3: host pointwise log-likelihood */
+    const double *loglik;         /* [n_w, n_rows] or NULL */
+    const int32_t *multiplicity;  /* sources 2, 3: [n_w] >= 0, or NULL = 1 each */
+    int64_t n_w;
+    /* data (sources 1, 2) */
+    int32_t x_source;             /* PTNN_PREDICT_X_HOST | _TRAIN | _TEST */
+    int32_t n_rows;
+    const float *x;               /* [n_rows, n_in + 1] (host rows only) */
+    double r_eff;                 /* > 0; 1 = independent draws */
+    /* outputs */
+    double *lppd, *p_waic, *elpd_loo, *khat;
+    int64_t *tail_len;
+    double *loglik_out;
+    int64_t *n_samples, *n_distinct;
+} ptnn_elpd_spec;
+
+int ptnn_elpd(ptnn_handle *h, const ptnn_elpd_spec *spec);
+
 /* the HIP stream (hipStream_t) all of this handle's work is queued on: lets the caller order its collectives after the
  * segment / before the swap kernels on the device instead of synchronising the host */
 int ptnn_stream(ptnn_handle *h, void **hip_stream);

@@ -60,6 +60,24 @@ class ConvergenceSpec(C.Structure):
     ]
 
 
+class ElpdSpec(C.Structure):
+    """ptnn_elpd_spec (include/ptnn.h)."""
+    _fields_ = [
+        ("struct_bytes", C.c_int32),
+        ("replicas", C.POINTER(C.c_int32)), ("n_replicas", C.c_int32), ("step0", C.c_int32), ("nsteps", C.c_int32), ("thin", C.c_int32),
+        ("w", C.POINTER(C.c_float)), ("eta", C.POINTER(C.c_float)), ("loglik", C.POINTER(C.c_double)),
+        ("multiplicity", C.POINTER(C.c_int32)), ("n_w", C.c_int64),
+        ("x_source", C.c_int32), ("n_rows", C.c_int32), ("x", C.POINTER(C.c_float)),
+        ("r_eff", C.c_double),
+        ("lppd", C.POINTER(C.c_double)), ("p_waic", C.POINTER(C.c_double)), ("elpd_loo", C.POINTER(C.c_double)),
+        ("khat", C.POINTER(C.c_double)), ("tail_len", C.POINTER(C.c_int64)), ("loglik_out", C.POINTER(C.c_double)),
+        ("n_samples", C.POINTER(C.c_int64)), ("n_distinct", C.POINTER(C.c_int64)),
+    ]
+
+
+ELPD_TAIL_CAP = 4096
+
+
 def library_path():
     return os.environ.get("PTNN_LIBRARY", os.path.join(_HERE, "libptnn.so"))
 
@@ -139,6 +157,7 @@ SYMBOLS = {
     "ptnn_trace_image_wait": (C.c_int, [C.c_void_p, C.c_int]),
     "ptnn_predict": (C.c_int, [C.c_void_p, C.POINTER(PredictSpec)]),
     "ptnn_convergence": (C.c_int, [C.c_void_p, C.POINTER(ConvergenceSpec)]),
+    "ptnn_elpd": (C.c_int, [C.c_void_p, C.POINTER(ElpdSpec)]),
 }
 
 
@@ -587,6 +606,88 @@ class Sampler:
         spec.n_lags = int(n_lags)
         self._check(self.lib.ptnn_convergence(self.h, C.byref(spec)))
         out["n_chains"], out["n_draws"] = int(nc), int(nd)
+        return out
+
+    def elpd(self, data="test", *, replicas=None, step0=0, nsteps=None, thin=1, w=None, eta=None, loglik=None, multiplicity=None,
+             r_eff=1.0, loglik_out=False):
+        """ptnn_elpd: per data row lppd, p_waic, PSIS-LOO elpd and its Pareto k-hat, on the device.  Source: the trace rows step0,
+        step0 + thin, ... < step0 + nsteps of `replicas` (None = all), host vectors w [n, P] with eta [n] (regression), or a host
+        pointwise log-likelihood loglik [n, n_rows] float64; sources 2 and 3 take optional integer `multiplicity` [n].  data:
+        "train", "test" or rows [n_rows, n_in + 1] (last column the target; ignored with loglik).  -> dict(lppd, p_waic, elpd_loo,
+        khat [n_rows] float64, tail_len [n_rows] int64, loglik [S, n_rows] float64 (loglik_out), n_samples, n_distinct)."""
+        spec = ElpdSpec()
+        spec.struct_bytes = C.sizeof(ElpdSpec)
+        keep = []
+        dp = C.POINTER(C.c_double)
+        if loglik is not None:
+            la = np.ascontiguousarray(loglik, dtype=np.float64)
+            if la.ndim != 2:
+                raise ValueError(f"loglik must be [n_samples, n_rows], got shape {la.shape}")
+            keep.append(la)
+            spec.loglik, spec.n_w, spec.n_rows = la.ctypes.data_as(dp), la.shape[0], la.shape[1]
+            spec.x_source = PREDICT_X_HOST
+            n_host = la.shape[0]
+        else:
+            if isinstance(data, str):
+                src = {"train": PREDICT_X_TRAIN, "test": PREDICT_X_TEST}.get(data)
+                if src is None:
+                    raise ValueError(f"data must be 'train', 'test' or an array, not {data!r}")
+                spec.x_source = src
+                spec.n_rows = self.ntr if src == PREDICT_X_TRAIN else self.nte
+            else:
+                xa = _f32(data)
+                if xa.ndim != 2 or xa.shape[1] != self.cfg.n_in + 1:
+                    raise ValueError(f"data must be [n_rows, {self.cfg.n_in + 1}] (n_in inputs and the target), got shape {xa.shape}")
+                keep.append(xa)
+                spec.x_source, spec.n_rows, spec.x = PREDICT_X_HOST, xa.shape[0], _ptr(xa)
+            n_host = None
+            if w is not None:
+                wa = _f32(w)
+                if wa.ndim != 2 or wa.shape[1] != self.P:
+                    raise ValueError(f"w must be [n, {self.P}], got shape {wa.shape}")
+                keep.append(wa)
+                spec.w, spec.n_w = _ptr(wa), wa.shape[0]
+                n_host = wa.shape[0]
+                if eta is not None:
+                    ea = _f32(np.reshape(eta, -1))
+                    if ea.shape != (wa.shape[0],):
+                        raise ValueError("eta must have one entry per vector")
+                    keep.append(ea)
+                    spec.eta = _ptr(ea)
+        if n_host is not None:
+            if multiplicity is not None:
+                mu = np.ascontiguousarray(multiplicity, dtype=np.int32)
+                if mu.shape != (n_host,):
+                    raise ValueError("multiplicity must have one entry per sample")
+                keep.append(mu)
+                spec.multiplicity = _ptr(mu, _ip)
+                S = int(mu.astype(np.int64).sum())
+            else:
+                S = n_host
+        else:
+            if replicas is not None:
+                ra = np.ascontiguousarray(replicas, dtype=np.int32).reshape(-1)
+                keep.append(ra)
+                spec.replicas, spec.n_replicas = _ptr(ra, _ip), ra.size
+                nrep = ra.size
+            else:
+                nrep = self.R
+            spec.step0 = int(step0)
+            spec.nsteps = int(self.S - step0 if nsteps is None else nsteps)
+            spec.thin = int(thin)
+            S = nrep * max(0, -(-spec.nsteps // max(1, spec.thin)))
+        spec.r_eff = float(r_eff)
+        n_rows = spec.n_rows
+        out = dict(lppd=np.empty(n_rows), p_waic=np.empty(n_rows), elpd_loo=np.empty(n_rows), khat=np.empty(n_rows),
+                   tail_len=np.empty(n_rows, np.int64), loglik=np.empty((max(S, 0), n_rows)) if loglik_out else None)
+        for k in ("lppd", "p_waic", "elpd_loo", "khat"):
+            setattr(spec, k, out[k].ctypes.data_as(dp))
+        spec.tail_len = out["tail_len"].ctypes.data_as(C.POINTER(C.c_int64))
+        spec.loglik_out = out["loglik"].ctypes.data_as(dp) if loglik_out else None
+        ns, nd = C.c_int64(0), C.c_int64(0)
+        spec.n_samples, spec.n_distinct = C.pointer(ns), C.pointer(nd)
+        self._check(self.lib.ptnn_elpd(self.h, C.byref(spec)))
+        out["n_samples"], out["n_distinct"] = ns.value, nd.value
         return out
 
     def langevin_gradient(self, w):

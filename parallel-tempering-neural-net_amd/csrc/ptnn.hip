@@ -2178,6 +2178,245 @@ int ptnn_convergence(ptnn_handle* h, const ptnn_convergence_spec* spec) {
     return 0;
 }
 
+// ---- predictive accuracy (ptnn_dev_elpd.hpp) ----
+static_assert(PTNN_ELPD_TAIL_CAP == ELPD_TAIL_CAP, "ptnn.h tail capacity");
+
+int ptnn_elpd(ptnn_handle* h, const ptnn_elpd_spec* spec) {
+    // argument checks first: none of them needs the handle or a device
+    if (!spec) return fail(-1, "null argument");
+    if (spec->struct_bytes != (int32_t)sizeof(ptnn_elpd_spec))
+        return fail(-1, "ptnn_elpd_spec.struct_bytes = %d, expected %d", spec->struct_bytes, (int)sizeof(ptnn_elpd_spec));
+    const ptnn_elpd_spec& s = *spec;
+    const bool ll_src = s.loglik != nullptr, host_src = s.w != nullptr;
+    if (ll_src && host_src) return fail(-1, "give host vectors w or a host loglik, not both");
+    if (!(s.r_eff > 0.0) || !std::isfinite(s.r_eff)) return fail(-1, "r_eff = %g must be a finite number > 0", s.r_eff);
+    if ((ll_src || host_src) && s.n_w < 1) return fail(-1, "n_w = %lld host samples: need at least one", (long long)s.n_w);
+    if (!ll_src && !host_src && s.nsteps < 1)
+        return fail(-1, "no source: nsteps = %d trace rows, and neither host vectors w nor a host loglik", s.nsteps);
+    if (!ll_src && !host_src && s.thin < 1) return fail(-1, "thin = %d must be >= 1", s.thin);
+    if (!ll_src && !host_src && s.replicas && s.n_replicas < 1) return fail(-1, "n_replicas = %d with a replica list", s.n_replicas);
+    if (s.n_rows < 1) return fail(-1, "n_rows = %d must be >= 1", s.n_rows);
+    if (!ll_src) {
+        if (s.x_source != PTNN_PREDICT_X_HOST && s.x_source != PTNN_PREDICT_X_TRAIN && s.x_source != PTNN_PREDICT_X_TEST)
+            return fail(-1, "x_source = %d is not PTNN_PREDICT_X_HOST, _TRAIN or _TEST", s.x_source);
+        if (s.x_source == PTNN_PREDICT_X_HOST && !s.x) return fail(-1, "x_source PTNN_PREDICT_X_HOST needs x");
+    }
+    if (ll_src && s.loglik_out) return fail(-1, "loglik_out: the log-likelihood is the input of this source");
+    // the sample count of the host sources
+    long long n_items = 0, S = 0;
+    if (ll_src || host_src) {
+        n_items = s.n_w;
+        if (s.multiplicity) {
+            for (int64_t k = 0; k < s.n_w; ++k) {
+                if (s.multiplicity[k] < 0) return fail(-1, "multiplicity[%lld] = %d is negative", (long long)k, s.multiplicity[k]);
+                S += s.multiplicity[k];
+            }
+        } else {
+            S = s.n_w;
+        }
+    }
+    if (ll_src)
+        for (long long k = 0; k < n_items * s.n_rows; ++k)
+            if (!std::isfinite(s.loglik[k])) return fail(-1, "loglik[%lld, %lld] = %g is not finite", k / s.n_rows, k % s.n_rows, s.loglik[k]);
+    if (int rc = check_ready(h)) return rc;
+    if (h->comm.kind != COMM_NONE) return fail(-3, "ptnn_elpd serves one GPU: this handle has a communicator attached");
+    const int I = h->cfg.n_in, H = h->cfg.n_hidden, O = h->cfg.n_out, P = h->P, cap = h->cap;
+    const bool reg = h->cfg.task == PTNN_TASK_REG;
+    if (host_src && reg && !s.eta) return fail(-1, "a regression's host vectors need eta = log tau^2 (one per vector)");
+    if (!ll_src && s.x_source == PTNN_PREDICT_X_TRAIN && s.n_rows != h->Ntr) return fail(-1, "n_rows = %d but the train set has %d rows", s.n_rows, h->Ntr);
+    if (!ll_src && s.x_source == PTNN_PREDICT_X_TEST && s.n_rows != h->Nte) return fail(-1, "n_rows = %d but the test set has %d rows", s.n_rows, h->Nte);
+    if (!ll_src && s.x_source == PTNN_PREDICT_X_HOST && !reg)
+        for (int n = 0; n < s.n_rows; ++n) {
+            const float yv = s.x[(size_t)n * (I + 1) + I];
+            if (!(yv >= 0.0f) || yv >= (float)O || yv != std::floor(yv))
+                return fail(-1, "class label %g in row %d is not an integer in [0, %d)", (double)yv, n, O);
+        }
+    // the selection
+    std::vector<int32_t> reps;
+    int m = 0;
+    if (!ll_src && !host_src) {
+        if (int rc = select_trace_rows(h, s.replicas, s.n_replicas, s.step0, s.nsteps, s.thin, &reps, &m)) return rc;
+        n_items = (long long)reps.size() * m;
+        S = n_items;
+    }
+    if (S < 2) return fail(-1, "the selection holds %lld samples: p_waic (a variance, ddof 1) needs at least 2", S);
+    if (S > 0x7fffffffLL || n_items > 0x7fffffffLL) return fail(-1, "%lld samples: at most 2^31 - 1 per call", S);
+    const long long M = (long long)std::ceil(std::min(0.2 * (double)S, 3.0 * std::sqrt((double)S / s.r_eff)));
+    if (M > ELPD_TAIL_CAP)
+        return fail(-1, "%lld samples with r_eff = %g need a PSIS tail of M = %lld > %d samples: select fewer samples (thin=, chains=) "
+                        "or give a larger r_eff", S, s.r_eff, M, ELPD_TAIL_CAP);
+    if (s.n_samples) *s.n_samples = S;
+
+    HIP_TRY(hipSetDevice(h->cfg.device_id));
+    if (int rc = finish_stream(h)) return rc;          // behind everything queued; a failed run is refused here
+    hipStream_t st = h->stream;
+    DeviceScratch mem;
+    const int n_rows = s.n_rows;
+    double *d_lppd = nullptr, *d_pwaic = nullptr, *d_loo = nullptr, *d_khat = nullptr;
+    long long* d_tail = nullptr;
+    HIP_TRY(mem.alloc(&d_lppd, (size_t)n_rows));
+    HIP_TRY(mem.alloc(&d_pwaic, (size_t)n_rows));
+    HIP_TRY(mem.alloc(&d_loo, (size_t)n_rows));
+    HIP_TRY(mem.alloc(&d_khat, (size_t)n_rows));
+    HIP_TRY(mem.alloc(&d_tail, (size_t)n_rows));
+    ElpdRed ra{};
+    ra.O = O; ra.S = S; ra.M = (int)M;
+    ra.lppd = d_lppd; ra.p_waic = d_pwaic; ra.elpd_loo = d_loo; ra.khat = d_khat; ra.tail_len = d_tail;
+    auto copy_out = [&]() -> int {
+        const std::pair<double*, double*> outs[] = {{s.lppd, d_lppd}, {s.p_waic, d_pwaic}, {s.elpd_loo, d_loo}, {s.khat, d_khat}};
+        for (const auto& o : outs)
+            if (o.first) HIP_TRY(hipMemcpyAsync(o.first, o.second, (size_t)n_rows * sizeof(double), hipMemcpyDeviceToHost, st));
+        if (s.tail_len) HIP_TRY(hipMemcpyAsync(s.tail_len, d_tail, (size_t)n_rows * sizeof(long long), hipMemcpyDeviceToHost, st));
+        return wait_stream(h);
+    };
+
+    if (ll_src) {
+        // source 3: every host sample is its own entry (repeats need no merging: the reduction depends on the multiset only)
+        double* d_ll = nullptr;
+        int* d_cnt = nullptr;
+        HIP_TRY(mem.alloc(&d_ll, (size_t)n_items * n_rows));
+        HIP_TRY(hipMemcpyAsync(d_ll, s.loglik, (size_t)n_items * n_rows * sizeof(double), hipMemcpyHostToDevice, st));
+        HIP_TRY(mem.alloc(&d_cnt, (size_t)n_items));
+        if (s.multiplicity) {
+            HIP_TRY(hipMemcpyAsync(d_cnt, s.multiplicity, (size_t)n_items * sizeof(int32_t), hipMemcpyHostToDevice, st));
+        } else {
+            std::vector<int32_t> ones((size_t)n_items, 1);
+            HIP_TRY(hipMemcpyAsync(d_cnt, ones.data(), ones.size() * sizeof(int32_t), hipMemcpyHostToDevice, st));
+            if (int rc = wait_stream(h)) return rc;          // `ones` dies at the end of this block
+        }
+        ra.mode = ELPD_HOST; ra.ll = d_ll; ra.ll_stride = n_rows; ra.cnt = d_cnt; ra.U = (int)n_items; ra.row0 = 0;
+        hipLaunchKernelGGL(elpd_reduce_kernel, dim3((unsigned)n_rows), dim3(ELPD_THREADS), 0, st, ra);
+        HIP_TRY(hipGetLastError());
+        if (s.n_distinct) *s.n_distinct = n_items;
+        return copy_out();
+    }
+
+    // data rows and targets
+    const float* d_x = nullptr;
+    int xs = 0;
+    if (s.x_source == PTNN_PREDICT_X_HOST) {
+        float* d = nullptr;
+        HIP_TRY(mem.alloc(&d, (size_t)n_rows * (I + 1)));
+        HIP_TRY(hipMemcpyAsync(d, s.x, (size_t)n_rows * (I + 1) * sizeof(float), hipMemcpyHostToDevice, st));
+        d_x = d; xs = I + 1;
+    } else {
+        d_x = h->d_data + (s.x_source == PTNN_PREDICT_X_TEST ? (size_t)h->Ntr * h->IPY : 0);
+        xs = h->IPY;
+    }
+    // stage a: items -> distinct (w, eta) samples
+    long long *d_item_off = nullptr, *d_run_off = nullptr;
+    int *d_flag = nullptr, *d_item_run = nullptr, *d_run_cnt = nullptr, *d_nruns = nullptr, *d_weight = nullptr, *d_reps = nullptr;
+    float *d_w = nullptr, *d_item_eta = nullptr, *d_run_eta = nullptr, *d_heta = nullptr;
+    HIP_TRY(mem.alloc(&d_item_off, (size_t)n_items));
+    HIP_TRY(mem.alloc(&d_run_off, (size_t)n_items));
+    HIP_TRY(mem.alloc(&d_flag, (size_t)n_items));
+    HIP_TRY(mem.alloc(&d_item_run, (size_t)n_items));
+    HIP_TRY(mem.alloc(&d_run_cnt, (size_t)n_items));
+    HIP_TRY(mem.alloc(&d_item_eta, (size_t)n_items));
+    HIP_TRY(mem.alloc(&d_run_eta, (size_t)n_items));
+    HIP_TRY(mem.alloc(&d_nruns, 4));                     // [0] runs, [1] unresolved compact rows, [2] rows without eta, [3] first such chain
+    HIP_TRY(hipMemsetAsync(d_run_cnt, 0, (size_t)n_items * sizeof(int), st));
+    HIP_TRY(hipMemsetAsync(d_nruns, 0, 3 * sizeof(int), st));
+    HIP_TRY(hipMemsetAsync(d_nruns + 3, 0x7f, sizeof(int), st));
+    ElpdSel sel{};
+    sel.reg = reg ? 1 : 0; sel.P = P; sel.n_items = n_items; sel.item_off = d_item_off; sel.item_eta = d_item_eta; sel.flag = d_flag;
+    sel.error = d_nruns + 1;
+    const float* base = nullptr;
+    if (host_src) {
+        HIP_TRY(mem.alloc(&d_w, (size_t)n_items * P));
+        HIP_TRY(hipMemcpyAsync(d_w, s.w, (size_t)n_items * P * sizeof(float), hipMemcpyHostToDevice, st));
+        if (reg) {
+            HIP_TRY(mem.alloc(&d_heta, (size_t)n_items));
+            HIP_TRY(hipMemcpyAsync(d_heta, s.eta, (size_t)n_items * sizeof(float), hipMemcpyHostToDevice, st));
+        }
+        if (s.multiplicity) {
+            HIP_TRY(mem.alloc(&d_weight, (size_t)n_items));
+            HIP_TRY(hipMemcpyAsync(d_weight, s.multiplicity, (size_t)n_items * sizeof(int32_t), hipMemcpyHostToDevice, st));
+        }
+        sel.host = 1; sel.pos_w = d_w; sel.host_eta = d_heta;
+        base = d_w;
+    } else {
+        HIP_TRY(mem.alloc(&d_reps, reps.size()));
+        HIP_TRY(hipMemcpyAsync(d_reps, reps.data(), reps.size() * sizeof(int32_t), hipMemcpyHostToDevice, st));
+        sel.host = 0; sel.pos_w = h->d_pos_w; sel.scal = h->d_scal; sel.replicas = d_reps; sel.st_i = h->d_st_i; sel.cap = cap;
+        sel.PW = h->PW; sel.step0 = s.step0; sel.thin = s.thin; sel.m = m; sel.compact = h->plan.compact ? 1 : 0; sel.cur = h->cur;
+        base = h->d_pos_w;
+    }
+    const unsigned item_blocks = (unsigned)((n_items + ELPD_THREADS - 1) / ELPD_THREADS);
+    hipLaunchKernelGGL(elpd_runs_kernel, dim3(item_blocks), dim3(ELPD_THREADS), 0, st, sel);
+    HIP_TRY(hipGetLastError());
+    PredictScan sc{n_items, d_flag, d_item_off, d_weight, d_item_run, d_run_off, d_run_cnt, d_nruns};
+    hipLaunchKernelGGL(predict_scan_kernel, dim3(1), dim3(PRED_SCAN_THREADS), 0, st, sc);
+    HIP_TRY(hipGetLastError());
+    hipLaunchKernelGGL(elpd_run_eta_kernel, dim3(item_blocks), dim3(ELPD_THREADS), 0, st, n_items, (const int*)d_flag,
+                       (const int*)d_item_run, (const float*)d_item_eta, d_run_eta);
+    HIP_TRY(hipGetLastError());
+    int runs[4] = {0, 0, 0, 0};
+    HIP_TRY(hipMemcpyAsync(runs, d_nruns, sizeof runs, hipMemcpyDeviceToHost, st));
+    if (int rc = wait_stream(h)) return rc;
+    if (runs[1]) return fail(-2, "%d selected compact trace rows refer to rows that are not resident (internal error)", runs[1]);
+    if (runs[2]) {
+        const int c = runs[3] >= 0 && runs[3] < (int)reps.size() ? runs[3] : 0;
+        return fail(-1, "%d selected trace rows precede their chain's first accepted MH step (chain %d, local replica %d, among "
+                        "others): no eta = log tau^2 was recorded for them; start the selection later (a larger burn_in)",
+                    runs[2], c, reps.empty() ? 0 : reps[(size_t)c]);
+    }
+    const int U = runs[0];
+    if (U < 1 || U > n_items) return fail(-2, "run-length pass found %d distinct samples among %lld rows (internal error)", U, n_items);
+    if (s.n_distinct) *s.n_distinct = U;
+    // stage b + c in blocks of rows: fx scratch U x (rows x O) floats (+ U x rows doubles for loglik_out) under the budget
+    const size_t budget = scratch_budget("PTNN_ELPD_SCRATCH_BYTES");
+    const size_t row_bytes = (size_t)U * (sizeof(float) * O + (s.loglik_out ? sizeof(double) : 0));
+    long long rows_blk = (long long)(budget / row_bytes);
+    rows_blk = std::max(1LL, std::min<long long>(rows_blk, n_rows));
+    float* d_fx = nullptr;
+    double* d_llb = nullptr;
+    HIP_TRY(mem.alloc(&d_fx, (size_t)rows_blk * O * U));
+    if (s.loglik_out) HIP_TRY(mem.alloc(&d_llb, (size_t)rows_blk * U));
+    const int PV = round_up4(P);
+    const int per_vec = PV + (PRED_THREADS / WAVE + 1) * O * WAVE;     // as ptnn_predict: staged vector + partial sums + tile
+    const int NV = std::max(1, std::min(PRED_MAX_NV, (48 * 1024 / 4) / per_vec));
+    const size_t lds = (size_t)NV * per_vec * sizeof(float);
+    if (lds > 152 * 1024) return fail(-3, "predictive accuracy: a %d-parameter vector does not fit in LDS", P);
+    if (int rc = raise_lds_limit(reinterpret_cast<const void*>(h->shape->predict_fwd), lds)) return rc;
+    std::vector<int> item_run;
+    std::vector<double> ll_host;
+    if (s.loglik_out) {
+        item_run.resize((size_t)n_items);
+        HIP_TRY(hipMemcpyAsync(item_run.data(), d_item_run, (size_t)n_items * sizeof(int), hipMemcpyDeviceToHost, st));
+    }
+    ra.mode = reg ? ELPD_REG : ELPD_CLS; ra.fx = d_fx; ra.eta = d_run_eta; ra.y = d_x + I; ra.ys = xs; ra.cnt = d_run_cnt; ra.U = U;
+    ra.ll_out = d_llb;
+    for (long long r0 = 0; r0 < n_rows; r0 += rows_blk) {
+        const int nr = (int)std::min<long long>(rows_blk, n_rows - r0);
+        PredictFwd fa{base, d_run_off, d_x, xs, (int)r0, nr, H, P, PV, U, NV, d_fx};
+        hipLaunchKernelGGL(h->shape->predict_fwd, dim3((unsigned)((U + NV - 1) / NV), (unsigned)((nr + WAVE - 1) / WAVE)), dim3(PRED_THREADS), lds, st, fa);
+        HIP_TRY(hipGetLastError());
+        ra.row0 = (int)r0;
+        hipLaunchKernelGGL(elpd_reduce_kernel, dim3((unsigned)nr), dim3(ELPD_THREADS), 0, st, ra);
+        HIP_TRY(hipGetLastError());
+        if (s.loglik_out) {
+            const long long n_ll = (long long)nr * U;
+            hipLaunchKernelGGL(elpd_loglik_kernel, dim3((unsigned)((n_ll + ELPD_THREADS - 1) / ELPD_THREADS)), dim3(ELPD_THREADS), 0, st, ra, nr);
+            HIP_TRY(hipGetLastError());
+            ll_host.resize((size_t)n_ll);
+            HIP_TRY(hipMemcpyAsync(ll_host.data(), d_llb, ll_host.size() * sizeof(double), hipMemcpyDeviceToHost, st));
+            if (int rc = wait_stream(h)) return rc;
+            // every selected sample gets its distinct sample's log-likelihood, in the order of the selection (chain-major)
+            long long out_row = 0;
+            for (long long i = 0; i < n_items; ++i) {
+                const int reps_i = (host_src && s.multiplicity) ? s.multiplicity[i] : 1;
+                const size_t u = (size_t)item_run[(size_t)i];
+                for (int k = 0; k < reps_i; ++k, ++out_row) {
+                    double* dst = s.loglik_out + (size_t)out_row * n_rows + r0;
+                    for (int c = 0; c < nr; ++c) dst[c] = ll_host[(size_t)c * U + u];
+                }
+            }
+        }
+    }
+    return copy_out();
+}
+
 static int run_model(ptnn_handle* h, int mode, const float* w_in, const float* tau_sq, int n, float* out, size_t out_floats,
                      int a0, int a1) {
     if (!h) return fail(-1, "null handle");

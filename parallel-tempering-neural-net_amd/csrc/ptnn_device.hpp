@@ -147,6 +147,7 @@ struct SegDyn {
 #include "ptnn_dev_predict.hpp"              // posterior predictive: run-length pass over the selected rows, forward pass, per-column reduction
 #ifndef PTNN_SHAPE_TU
 #include "ptnn_dev_convergence.hpp"          // convergence diagnostics: split-R-hat, split-ESS over trace columns (main translation unit only)
+#include "ptnn_dev_elpd.hpp"                 // predictive accuracy: lppd, WAIC, PSIS-LOO per data row (main translation unit only)
 #endif
 
 }  // namespace ptnn

@@ -14,6 +14,7 @@ as a second kernel; this module only configures the run, fetches the traces and 
 import math
 import os
 import time
+import warnings
 from collections import namedtuple
 from concurrent.futures import ThreadPoolExecutor
 
@@ -97,6 +98,31 @@ Predictive = namedtuple("Predictive", "mean percentiles vote pred_class samples 
 # convergence_diagnostics' result: names [Q]; mean, sd, r_hat, ess, mcse_mean [Q] float64; ess_chain [n_chains, Q] or None; rho
 # [n_lags, Q] or None; trunc_lag [Q] int32; n_chains, n_draws
 Convergence = namedtuple("Convergence", "names mean sd r_hat ess mcse_mean ess_chain rho trunc_lag n_chains n_draws")
+
+# predictive_accuracy's result: totals elpd_loo, se_elpd_loo, p_loo, elpd_waic, se_elpd_waic, p_waic, lppd, se_lppd (float);
+# pointwise lppd_i, elpd_loo_i, p_waic_i, khat [n_rows] float64; good_k (the k-hat threshold for this S); n_high_k (rows above
+# it); log_lik [n_samples, n_rows] float64 or None; n_samples; n_distinct
+PredictiveAccuracy = namedtuple("PredictiveAccuracy", "elpd_loo se_elpd_loo p_loo elpd_waic se_elpd_waic p_waic lppd se_lppd "
+                                "lppd_i elpd_loo_i p_waic_i khat good_k n_high_k log_lik n_samples n_distinct")
+
+
+def _se_total(x):
+    """Standard error of a sum of pointwise values: sqrt(N var(x, ddof 1)) (Vehtari, Gelman & Gabry 2017, eq. 23)."""
+    x = np.asarray(x, dtype=np.float64)
+    return float(np.sqrt(x.size * np.var(x, ddof=1))) if x.size > 1 else float("nan")
+
+
+def elpd_compare(a, b):
+    """The elpd difference of two PredictiveAccuracy results on the same data rows, a - b, with the paired standard error
+    sqrt(N var(a_i - b_i, ddof 1)).  -> dict(elpd_loo_diff, se_loo_diff, elpd_waic_diff, se_waic_diff); host arithmetic only."""
+    la, lb = np.asarray(a.elpd_loo_i, np.float64), np.asarray(b.elpd_loo_i, np.float64)
+    if la.shape != lb.shape:
+        raise ValueError(f"the two results cover different rows: {la.shape[0]} vs {lb.shape[0]}")
+    wa = np.asarray(a.lppd_i, np.float64) - np.asarray(a.p_waic_i, np.float64)
+    wb = np.asarray(b.lppd_i, np.float64) - np.asarray(b.p_waic_i, np.float64)
+    return dict(elpd_loo_diff=float(np.sum(la) - np.sum(lb)), se_loo_diff=_se_total(la - lb),
+                elpd_waic_diff=float(np.sum(wa) - np.sum(wb)), se_waic_diff=_se_total(wa - wb))
+
 
 # scalar trace columns convergence_diagnostics takes by name (a regression's acc_train slot holds eta = log tau^2)
 _SCALAR_COLS = {"likelihood": _lib.TR_LIKEH, "rmse_train": _lib.TR_RMSE_TR, "rmse_test": _lib.TR_RMSE_TE, "acc_train": _lib.TR_ACC_TR,
@@ -649,6 +675,103 @@ class ParallelTemperingBase:
         return Convergence(names=names, mean=out["mean"], sd=sd, r_hat=out["r_hat"], ess=out["ess"], mcse_mean=mcse,
                            ess_chain=out["ess_chain"], rho=out["rho"], trunc_lag=out["trunc_lag"], n_chains=out["n_chains"],
                            n_draws=out["n_draws"])
+
+    # ------------------------------------------------------------------ predictive accuracy (not in the reference)
+    def predictive_accuracy(self, data="train", *, burn_in=None, chains="all", thin=1, weights=None, eta=None, loglik=None,
+                            r_eff=1.0, return_pointwise=False):
+        """How well the sampled model predicts, as the expected log pointwise predictive density (elpd), computed on the GPU from
+        the traces it already holds: the figure to compare two models by -- e.g. 5 vs 10 hidden units, or
+        Langevin vs random-walk proposals -- with elpd_compare().
+
+        data="train": elpd_loo is the PSIS-LOO estimate of the elpd of a new data point from the training rows (Pareto smoothed
+        importance sampling leave-one-out; khat is the Pareto shape per row, rows with khat > good_k make the estimate unreliable,
+        and a warning says so), elpd_waic the WAIC estimate, lppd the in-sample fit they correct by p_loo / p_waic.  data="test"
+        (or rows [n_rows, >= n_in + 1], the column after the inputs the target): lppd is itself the held-out log predictive
+        density of those rows -- the direct measure; elpd_loo / elpd_waic then estimate how each row would fare had it been left
+        out of a fit it was never in.  The log-likelihood is untempered (regression: Gaussian with tau^2 = exp(eta) of each
+        sample; classification: log of the softmax probability of the true class).
+
+        The sample set is by default the columns of the posterior matrix run_chains() returns: every chain's trace rows from
+        int(NumSamples * burn_in) on.  `chains`: "all", "cold" (the temperature-1 chain) or a list of chain indices; `thin`: every
+        thin-th row.  As in pos_w, rows before the temperature switch (the reference's pt_samples = 0.6 NumSamples) are draws of
+        the tempered chains; chains="all" pools every temperature.  A regression needs each row's eta, which the trace records
+        only from a chain's first accepted step on: a selection that reaches earlier rows is refused (use a larger burn_in).
+        `weights`: weight vectors instead of the trace -- [n, num_param] or a pair (vectors, integer multiplicities), with `eta`
+        [n] (regression); `loglik`: a pointwise log-likelihood [n_samples, n_rows] (or a pair with multiplicities) instead of
+        both.  r_eff: relative efficiency of the draws for the PSIS tail length.  return_pointwise: also log_lik [S, n_rows].
+        -> PredictiveAccuracy; totals are sums over rows, se_* = sqrt(N var(pointwise, ddof 1))."""
+        if self._sampler is None:
+            raise ValueError("predictive_accuracy needs the chains' device handle: call initialize_chains() and run_chains() first")
+        if not isinstance(self._sampler, _lib.Sampler):
+            raise ValueError("predictive_accuracy runs on one GPU: a ladder sharded over several devices is not supported")
+        I = int(self.topology[0])
+        kw = {}
+        if loglik is not None:
+            mult = None
+            if isinstance(loglik, tuple):
+                loglik, mult = loglik
+            kw = dict(loglik=np.asarray(loglik, dtype=np.float64), multiplicity=mult)
+            ds = "test"
+        else:
+            if isinstance(data, str):
+                if data not in ("train", "test"):
+                    raise ValueError(f"data must be 'train', 'test' or an array, not {data!r}")
+                ds = data
+            else:
+                xa = np.asarray(data)
+                if xa.ndim != 2 or xa.shape[1] < I + 1:
+                    raise ValueError(f"data must be 2-D with at least n_in + 1 = {I + 1} columns (inputs, target), got shape {xa.shape}")
+                ds = np.ascontiguousarray(xa[:, :I + 1], dtype=np.float32)
+            if weights is not None:
+                mult = None
+                if isinstance(weights, tuple):
+                    weights, mult = weights
+                w = np.asarray(weights)
+                P = self.num_param
+                if w.ndim != 2 or P not in w.shape:
+                    raise ValueError(f"weights must be [n, {P}] vectors (or their transpose), got shape {w.shape}")
+                if w.shape[1] != P:
+                    w = w.T
+                if self.task != TASK_CLS and eta is None:
+                    raise ValueError("a regression's weights need eta = log tau^2, one per vector (Sampler.eta_trace())")
+                kw = dict(w=w, eta=None if self.task == TASK_CLS else eta, multiplicity=mult)
+        if not kw:
+            S = self.NumSamples
+            if self.label_swap:
+                raise ValueError("label_swap=True: trace rows are kept per chain slot, not per temperature; pass weights=")
+            if 0 < self.trace_capacity < S:
+                raise ValueError(f"trace_capacity = {self.trace_capacity} < NumSamples = {S}: the rows have been streamed off "
+                                 f"the device; pass weights=")
+            if not self._finished:
+                raise ValueError("no finished run_chains() on this object: the trace is incomplete; pass weights=")
+            b = self.burn_in if burn_in is None else burn_in
+            step0 = int(S * b)
+            if chains == "all":
+                reps = None
+            elif chains == "cold":
+                reps = [int(np.argmin(self.temperatures))]
+            else:
+                reps = [int(c) for c in chains]
+                if not reps or min(reps) < 0 or max(reps) >= self.num_chains:
+                    raise ValueError(f"chains {chains!r}: indices must lie in [0, {self.num_chains})")
+            kw = dict(replicas=reps, step0=step0, nsteps=S - step0, thin=int(thin))
+        out = self._sampler.elpd(ds, r_eff=r_eff, loglik_out=bool(return_pointwise) and loglik is None, **kw)
+        lppd_i, p_waic_i, loo_i, khat = out["lppd"], out["p_waic"], out["elpd_loo"], out["khat"]
+        waic_i = lppd_i - p_waic_i
+        n_s = out["n_samples"]
+        good_k = min(1.0 - 1.0 / math.log10(n_s), 0.7)
+        high = np.isfinite(khat) & (khat > good_k)
+        n_high = int(np.count_nonzero(high))
+        if n_high:
+            warnings.warn(f"{n_high} of {khat.size} rows have a Pareto k-hat above {good_k:.2f}: the PSIS-LOO estimate is "
+                          f"unreliable for them", stacklevel=2)
+        elpd_loo = float(np.sum(loo_i))
+        return PredictiveAccuracy(elpd_loo=elpd_loo, se_elpd_loo=_se_total(loo_i), p_loo=float(np.sum(lppd_i)) - elpd_loo,
+                                  elpd_waic=float(np.sum(waic_i)), se_elpd_waic=_se_total(waic_i), p_waic=float(np.sum(p_waic_i)),
+                                  lppd=float(np.sum(lppd_i)), se_lppd=_se_total(lppd_i), lppd_i=lppd_i, elpd_loo_i=loo_i,
+                                  p_waic_i=p_waic_i, khat=khat, good_k=good_k, n_high_k=n_high,
+                                  log_lik=(loglik if loglik is not None else out["loglik"]) if return_pointwise else None,
+                                  n_samples=n_s, n_distinct=out["n_distinct"])
 
     def make_directory(self, directory):
         if not os.path.exists(directory):
