@@ -384,6 +384,64 @@ typedef struct ptnn_elpd_spec {
 
 int ptnn_elpd(ptnn_handle *h, const ptnn_elpd_spec *spec);
 
+/* ---- recursive multi-step forecasts (nothing in the reference: it scores one-step predictions of the test rows only) ----
+ * A regression net with n_out == 1 fitted to windows of one series is the one-step map x[t+1] = f_w(x[t-I+1 .. t]), I = n_in.
+ * From an origin window (I inputs) step k = 1 .. horizon of a trajectory is y_k = f_w(window_{k-1}) -- exactly ptnn_predict's
+ * forward pass, sigmoid output (REG:51-55) -- plus, with noise on, exp(eta_w / 2) z_k (tau^2 = exp(eta), the REG likelihood's
+ * observation variance, REG:200-204); window_k = (window_{k-1}[1:], y_k), the noisy y_k when noise is on.
+ * Sample set: selected as ptnn_predict selects it -- the handle's trace (same rules and error texts) or host vectors w [n_w, P]
+ * with optional multiplicities; M = the selected rows, repeats included.  Noise off: trajectories depend on w only, one per
+ * distinct vector (merged as ptnn_predict merges them), weighted by its multiplicity; seed is ignored.  Noise on: every selected
+ * occurrence is its own trajectory, index i = its position in the chain-major selection (c * m + j; host vectors: after
+ * expanding the multiplicities), with z_k = box_muller of philox4x32_10(k / 4, i, origin, 4, seed), component k % 4 (0-based k;
+ * philox.py: normals(horizon, i, origin, STREAM_FORECAST, seed)[k]); eta comes from the TR_ACC_TR slot of the row that holds the
+ * vector (trace; a row before its chain's first accepted MH step has none and is refused) or from eta [n_w] (host vectors).
+ * Origins: origin_source PTNN_FORECAST_ORIGIN_HOST with origins [n_origins, n_in] float32, or the handle's train / test inputs
+ * (n_origins must be that set's size).  Outputs, any may be NULL, column c = origin * horizon + k: mean [n_origins, horizon]
+ * (weighted, accumulated in double); order_stats [n_ranks, n_origins, horizon] (exact fp32 values of 0-based ranks of the
+ * expanded multiset of M values, n_ranks <= 16); samples [M, n_origins, horizon] (chain-major, as ptnn_predict's samples);
+ * n_samples = M; n_trajectories = trajectories per origin.  With noise off and horizon step 1 every output equals ptnn_predict's
+ * on the origin rows, bitwise.
+ * Refused: a classification task or n_out != 1, horizon < 1, more than 2^31 - 1 columns, n_ranks > 16, host vectors without eta
+ * or trace rows without a recorded eta when noise is on, an attached communicator.
+ * Runs on the handle's stream behind everything queued and returns when done; origins and horizon steps are processed in
+ * blocks whose scratch stays under $PTNN_FORECAST_SCRATCH_BYTES (read per call, default 1 GiB), the windows carried from one
+ * horizon block to the next, which changes no result.  Touches no chain state, tape, counter or trace row. */
+#define PTNN_FORECAST_ORIGIN_HOST 0
+#define PTNN_FORECAST_ORIGIN_TRAIN 1
+#define PTNN_FORECAST_ORIGIN_TEST 2
+
+typedef struct ptnn_forecast_spec {
+    int32_t struct_bytes;         /* = sizeof(ptnn_forecast_spec): ABI guard */
+    /* source 1: the trace (used when w == NULL) */
+    const int32_t *replicas;      /* local replica indices, or NULL = all */
+    int32_t n_replicas;           /* entries of replicas (ignored when NULL) */
+    int32_t step0, nsteps, thin;  /* trace rows step0, step0 + thin, ... < step0 + nsteps (thin >= 1) */
+    /* source 2: host vectors */
+    const float *w;               /* [n_w, P] or NULL */
+    const int32_t *multiplicity;  /* [n_w] >= 0, or NULL = 1 each */
+    const float *eta;             /* [n_w] log tau^2 (noise on) */
+    int64_t n_w;
+    /* origins */
+    int32_t origin_source;        /* PTNN_FORECAST_ORIGIN_HOST | _TRAIN | _TEST */
+    int32_t n_origins;
+    const float *origins;         /* [n_origins, n_in] (host origins only) */
+    int32_t horizon;              /* >= 1 */
+    int32_t noise;                /* 0 / 1 */
+    uint64_t seed;                /* noise on only */
+    /* order statistics */
+    const int64_t *ranks;         /* [n_ranks] */
+    int32_t n_ranks;
+    int32_t reserved_;            /* set 0 */
+    /* outputs */
+    double *mean;
+    float *order_stats;
+    float *samples;
+    int64_t *n_samples, *n_trajectories;
+} ptnn_forecast_spec;
+
+int ptnn_forecast(ptnn_handle *h, const ptnn_forecast_spec *spec);
+
 /* the HIP stream (hipStream_t) all of this handle's work is queued on: lets the caller order its collectives after the
  * segment / before the swap kernels on the device instead of synchronising the host */
 int ptnn_stream(ptnn_handle *h, void **hip_stream);

@@ -77,6 +77,22 @@ class ElpdSpec(C.Structure):
 
 ELPD_TAIL_CAP = 4096
 
+FORECAST_ORIGIN_HOST, FORECAST_ORIGIN_TRAIN, FORECAST_ORIGIN_TEST = 0, 1, 2
+
+
+class ForecastSpec(C.Structure):
+    """ptnn_forecast_spec (include/ptnn.h)."""
+    _fields_ = [
+        ("struct_bytes", C.c_int32),
+        ("replicas", C.POINTER(C.c_int32)), ("n_replicas", C.c_int32), ("step0", C.c_int32), ("nsteps", C.c_int32), ("thin", C.c_int32),
+        ("w", C.POINTER(C.c_float)), ("multiplicity", C.POINTER(C.c_int32)), ("eta", C.POINTER(C.c_float)), ("n_w", C.c_int64),
+        ("origin_source", C.c_int32), ("n_origins", C.c_int32), ("origins", C.POINTER(C.c_float)),
+        ("horizon", C.c_int32), ("noise", C.c_int32), ("seed", C.c_uint64),
+        ("ranks", C.POINTER(C.c_int64)), ("n_ranks", C.c_int32), ("reserved_", C.c_int32),
+        ("mean", C.POINTER(C.c_double)), ("order_stats", C.POINTER(C.c_float)), ("samples", C.POINTER(C.c_float)),
+        ("n_samples", C.POINTER(C.c_int64)), ("n_trajectories", C.POINTER(C.c_int64)),
+    ]
+
 
 def library_path():
     return os.environ.get("PTNN_LIBRARY", os.path.join(_HERE, "libptnn.so"))
@@ -158,6 +174,7 @@ SYMBOLS = {
     "ptnn_predict": (C.c_int, [C.c_void_p, C.POINTER(PredictSpec)]),
     "ptnn_convergence": (C.c_int, [C.c_void_p, C.POINTER(ConvergenceSpec)]),
     "ptnn_elpd": (C.c_int, [C.c_void_p, C.POINTER(ElpdSpec)]),
+    "ptnn_forecast": (C.c_int, [C.c_void_p, C.POINTER(ForecastSpec)]),
 }
 
 
@@ -688,6 +705,79 @@ class Sampler:
         spec.n_samples, spec.n_distinct = C.pointer(ns), C.pointer(nd)
         self._check(self.lib.ptnn_elpd(self.h, C.byref(spec)))
         out["n_samples"], out["n_distinct"] = ns.value, nd.value
+        return out
+
+    def forecast(self, horizon, origins="test", *, replicas=None, step0=0, nsteps=None, thin=1, w=None, multiplicity=None, eta=None,
+                 noise=False, seed=0, ranks=(), mean=True, samples=False):
+        """ptnn_forecast: recursive multi-step forecasts of the one-step map f_w from origin windows, on the device.  Source: the
+        trace rows step0, step0 + thin, ... < step0 + nsteps of `replicas` (None = all), or host vectors w [n, P] with optional
+        integer `multiplicity` [n] and eta [n] (noise on).  origins: "train", "test" or windows [n_origins, n_in].  noise: add
+        exp(eta / 2) z_k to every step (Philox stream STREAM_FORECAST of `seed`).  -> dict(mean [n_origins, horizon] float64,
+        order_stats [len(ranks), n_origins, horizon] float32, samples [M, n_origins, horizon] float32, n_samples, n_trajectories);
+        what was not asked for is None."""
+        spec = ForecastSpec()
+        spec.struct_bytes = C.sizeof(ForecastSpec)
+        keep = []
+        if isinstance(origins, str):
+            src = {"train": FORECAST_ORIGIN_TRAIN, "test": FORECAST_ORIGIN_TEST}.get(origins)
+            if src is None:
+                raise ValueError(f"origins must be 'train', 'test' or an array, not {origins!r}")
+            spec.origin_source = src
+            spec.n_origins = self.ntr if src == FORECAST_ORIGIN_TRAIN else self.nte
+        else:
+            xa = _f32(origins)
+            if xa.ndim != 2 or xa.shape[1] != self.cfg.n_in:
+                raise ValueError(f"origins must be [n_origins, {self.cfg.n_in}] (n_in columns), got shape {xa.shape}")
+            keep.append(xa)
+            spec.origin_source, spec.n_origins, spec.origins = FORECAST_ORIGIN_HOST, xa.shape[0], _ptr(xa)
+        spec.horizon, spec.noise, spec.seed = int(horizon), 1 if noise else 0, int(seed) & 0xFFFFFFFFFFFFFFFF
+        n_org, hz = spec.n_origins, max(int(horizon), 0)
+        if w is not None:
+            wa = _f32(w)
+            if wa.ndim != 2 or wa.shape[1] != self.P:
+                raise ValueError(f"w must be [n, {self.P}], got shape {wa.shape}")
+            keep.append(wa)
+            spec.w, spec.n_w = _ptr(wa), wa.shape[0]
+            if eta is not None:
+                ea = _f32(np.reshape(eta, -1))
+                if ea.shape != (wa.shape[0],):
+                    raise ValueError("eta must have one entry per vector")
+                keep.append(ea)
+                spec.eta = _ptr(ea)
+            if multiplicity is not None:
+                mu = np.ascontiguousarray(multiplicity, dtype=np.int32)
+                if mu.shape != (wa.shape[0],):
+                    raise ValueError("multiplicity must have one entry per vector")
+                keep.append(mu)
+                spec.multiplicity = _ptr(mu, _ip)
+                M = int(mu.astype(np.int64).sum())
+            else:
+                M = wa.shape[0]
+        else:
+            if replicas is not None:
+                ra = np.ascontiguousarray(replicas, dtype=np.int32).reshape(-1)
+                keep.append(ra)
+                spec.replicas, spec.n_replicas = _ptr(ra, _ip), ra.size
+                nrep = ra.size
+            else:
+                nrep = self.R
+            spec.step0 = int(step0)
+            spec.nsteps = int(self.S - step0 if nsteps is None else nsteps)
+            spec.thin = int(thin)
+            M = nrep * max(0, -(-spec.nsteps // max(1, spec.thin)))
+        rk = np.ascontiguousarray(ranks, dtype=np.int64).reshape(-1)
+        keep.append(rk)
+        spec.ranks, spec.n_ranks = (_ptr(rk, C.POINTER(C.c_int64)) if rk.size else None), rk.size
+        out = dict(mean=np.empty((n_org, hz), np.float64) if mean else None,
+                   order_stats=np.empty((rk.size, n_org, hz), np.float32) if rk.size else None,
+                   samples=np.empty((max(M, 0), n_org, hz), np.float32) if samples else None)
+        spec.mean = _ptr(out["mean"], C.POINTER(C.c_double))
+        spec.order_stats = _ptr(out["order_stats"])
+        spec.samples = _ptr(out["samples"])
+        ns, nt = C.c_int64(0), C.c_int64(0)
+        spec.n_samples, spec.n_trajectories = C.pointer(ns), C.pointer(nt)
+        self._check(self.lib.ptnn_forecast(self.h, C.byref(spec)))
+        out["n_samples"], out["n_trajectories"] = ns.value, nt.value
         return out
 
     def langevin_gradient(self, w):

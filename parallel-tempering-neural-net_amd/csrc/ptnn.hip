@@ -2417,6 +2417,271 @@ int ptnn_elpd(ptnn_handle* h, const ptnn_elpd_spec* spec) {
     return copy_out();
 }
 
+// ---- recursive forecasts (ptnn_dev_forecast.hpp) ----
+int ptnn_forecast(ptnn_handle* h, const ptnn_forecast_spec* spec) {
+    // argument checks first: none of them needs the handle or a device
+    if (!spec) return fail(-1, "null argument");
+    if (spec->struct_bytes != (int32_t)sizeof(ptnn_forecast_spec))
+        return fail(-1, "ptnn_forecast_spec.struct_bytes = %d, expected %d", spec->struct_bytes, (int)sizeof(ptnn_forecast_spec));
+    const ptnn_forecast_spec& s = *spec;
+    const bool host_src = s.w != nullptr, noise = s.noise != 0;
+    if (host_src && s.n_w < 1) return fail(-1, "n_w = %lld host vectors: need at least one", (long long)s.n_w);
+    if (!host_src && s.thin < 1) return fail(-1, "thin = %d must be >= 1", s.thin);
+    if (!host_src && s.replicas && s.n_replicas < 1) return fail(-1, "n_replicas = %d with a replica list", s.n_replicas);
+    if (s.origin_source != PTNN_FORECAST_ORIGIN_HOST && s.origin_source != PTNN_FORECAST_ORIGIN_TRAIN &&
+        s.origin_source != PTNN_FORECAST_ORIGIN_TEST)
+        return fail(-1, "origin_source = %d is not PTNN_FORECAST_ORIGIN_HOST, _TRAIN or _TEST", s.origin_source);
+    if (s.origin_source == PTNN_FORECAST_ORIGIN_HOST && !s.origins) return fail(-1, "origin_source PTNN_FORECAST_ORIGIN_HOST needs origins");
+    if (s.n_origins < 1) return fail(-1, "n_origins = %d must be >= 1", s.n_origins);
+    if (s.horizon < 1) return fail(-1, "horizon = %d must be >= 1", s.horizon);
+    const long long ncols = (long long)s.n_origins * s.horizon;
+    if (ncols > 0x7fffffffLL) return fail(-1, "%d origins x horizon %d = %lld columns: at most 2^31 - 1 per call", s.n_origins, s.horizon, ncols);
+    if (s.n_ranks < 0 || s.n_ranks > PTNN_PREDICT_MAX_RANKS) return fail(-1, "n_ranks = %d outside [0, %d]", s.n_ranks, PTNN_PREDICT_MAX_RANKS);
+    if (s.n_ranks > 0 && !s.ranks) return fail(-1, "n_ranks = %d but ranks is NULL", s.n_ranks);
+    if (s.order_stats && s.n_ranks == 0) return fail(-1, "order_stats requested without ranks");
+    if (noise && host_src && !s.eta) return fail(-1, "noise: host vectors need eta = log tau^2 (one per vector)");
+    if (int rc = check_ready(h)) return rc;
+    if (h->comm.kind != COMM_NONE) return fail(-3, "ptnn_forecast serves one GPU: this handle has a communicator attached");
+    if (h->cfg.task != PTNN_TASK_REG || h->cfg.n_out != 1)
+        return fail(-1, "forecasting needs a regression net with n_out == 1 (a one-step map of one series); this handle is a %s "
+                        "net with n_out = %d", h->cfg.task == PTNN_TASK_REG ? "regression" : "classification", h->cfg.n_out);
+    const int I = h->cfg.n_in, H = h->cfg.n_hidden, P = h->P, cap = h->cap, hz = s.horizon;
+    if (s.origin_source == PTNN_FORECAST_ORIGIN_TRAIN && s.n_origins != h->Ntr)
+        return fail(-1, "n_origins = %d but the train set has %d rows", s.n_origins, h->Ntr);
+    if (s.origin_source == PTNN_FORECAST_ORIGIN_TEST && s.n_origins != h->Nte)
+        return fail(-1, "n_origins = %d but the test set has %d rows", s.n_origins, h->Nte);
+    // the selection
+    std::vector<int32_t> reps;
+    long long n_items = 0, M = 0;
+    int m = 0;
+    if (host_src) {
+        n_items = s.n_w;
+        if (s.multiplicity) {
+            for (int64_t k = 0; k < s.n_w; ++k) {
+                if (s.multiplicity[k] < 0) return fail(-1, "multiplicity[%lld] = %d is negative", (long long)k, s.multiplicity[k]);
+                M += s.multiplicity[k];
+            }
+        } else {
+            M = s.n_w;
+        }
+    } else {
+        if (int rc = select_trace_rows(h, s.replicas, s.n_replicas, s.step0, s.nsteps, s.thin, &reps, &m)) return rc;
+        n_items = (long long)reps.size() * m;
+        M = n_items;
+    }
+    if (M < 1) return fail(-1, "the selection holds no sample");
+    if (M > 0x7fffffffLL || n_items > 0x7fffffffLL) return fail(-1, "%lld samples: at most 2^31 - 1 per call", M);
+    for (int k = 0; k < s.n_ranks; ++k)
+        if (s.ranks[k] < 0 || s.ranks[k] >= M) return fail(-1, "rank %lld outside [0, %lld)", (long long)s.ranks[k], M);
+    if (s.n_samples) *s.n_samples = M;
+
+    HIP_TRY(hipSetDevice(h->cfg.device_id));
+    if (int rc = finish_stream(h)) return rc;          // behind everything queued; a failed run is refused here
+    hipStream_t st = h->stream;
+    DeviceScratch mem;
+    // origins
+    const float* d_x = nullptr;
+    int xs = 0;
+    if (s.origin_source == PTNN_FORECAST_ORIGIN_HOST) {
+        float* d = nullptr;
+        HIP_TRY(mem.alloc(&d, (size_t)s.n_origins * I));
+        HIP_TRY(hipMemcpyAsync(d, s.origins, (size_t)s.n_origins * I * sizeof(float), hipMemcpyHostToDevice, st));
+        d_x = d; xs = I;
+    } else {
+        d_x = h->d_data + (s.origin_source == PTNN_FORECAST_ORIGIN_TEST ? (size_t)h->Ntr * h->IPY : 0);
+        xs = h->IPY;
+    }
+    // stage a: items -> trajectories (noise off: distinct vectors; noise on: every occurrence)
+    long long* d_item_off = nullptr; long long* d_run_off = nullptr; long long* d_ranks = nullptr;
+    int *d_flag = nullptr, *d_item_run = nullptr, *d_cnt = nullptr, *d_nruns = nullptr, *d_weight = nullptr, *d_reps = nullptr;
+    float *d_w = nullptr, *d_heta = nullptr, *d_eta = nullptr;
+    const float* base = nullptr;
+    int U = 0;
+    if (!noise) {
+        HIP_TRY(mem.alloc(&d_item_off, (size_t)n_items));
+        HIP_TRY(mem.alloc(&d_run_off, (size_t)n_items));
+        HIP_TRY(mem.alloc(&d_flag, (size_t)n_items));
+        HIP_TRY(mem.alloc(&d_item_run, (size_t)n_items));
+        HIP_TRY(mem.alloc(&d_cnt, (size_t)n_items));
+        HIP_TRY(mem.alloc(&d_nruns, 2));                 // [0] runs, [1] error count of the compact-row resolution
+        HIP_TRY(hipMemsetAsync(d_cnt, 0, (size_t)n_items * sizeof(int), st));
+        HIP_TRY(hipMemsetAsync(d_nruns, 0, 2 * sizeof(int), st));
+        PredictSel sel{};
+        sel.P = P; sel.n_items = n_items; sel.item_off = d_item_off; sel.flag = d_flag; sel.error = d_nruns + 1;
+        if (host_src) {
+            HIP_TRY(mem.alloc(&d_w, (size_t)n_items * P));
+            HIP_TRY(hipMemcpyAsync(d_w, s.w, (size_t)n_items * P * sizeof(float), hipMemcpyHostToDevice, st));
+            if (s.multiplicity) {
+                HIP_TRY(mem.alloc(&d_weight, (size_t)n_items));
+                HIP_TRY(hipMemcpyAsync(d_weight, s.multiplicity, (size_t)n_items * sizeof(int32_t), hipMemcpyHostToDevice, st));
+            }
+            sel.host = 1; sel.pos_w = d_w;
+            base = d_w;
+        } else {
+            HIP_TRY(mem.alloc(&d_reps, reps.size()));
+            HIP_TRY(hipMemcpyAsync(d_reps, reps.data(), reps.size() * sizeof(int32_t), hipMemcpyHostToDevice, st));
+            sel.host = 0; sel.pos_w = h->d_pos_w; sel.scal = h->d_scal; sel.replicas = d_reps; sel.cap = cap; sel.PW = h->PW;
+            sel.step0 = s.step0; sel.thin = s.thin; sel.m = m; sel.compact = h->plan.compact ? 1 : 0;
+            base = h->d_pos_w;
+        }
+        hipLaunchKernelGGL(predict_runs_kernel, dim3((unsigned)((n_items + PRED_THREADS - 1) / PRED_THREADS)), dim3(PRED_THREADS), 0, st, sel);
+        HIP_TRY(hipGetLastError());
+        PredictScan sc{n_items, d_flag, d_item_off, d_weight, d_item_run, d_run_off, d_cnt, d_nruns};
+        hipLaunchKernelGGL(predict_scan_kernel, dim3(1), dim3(PRED_SCAN_THREADS), 0, st, sc);
+        HIP_TRY(hipGetLastError());
+        int runs[2] = {0, 0};
+        HIP_TRY(hipMemcpyAsync(runs, d_nruns, sizeof runs, hipMemcpyDeviceToHost, st));
+        if (int rc = wait_stream(h)) return rc;
+        if (runs[1]) return fail(-2, "%d selected compact trace rows refer to rows that are not resident (internal error)", runs[1]);
+        U = runs[0];
+        if (U < 1 || U > n_items) return fail(-2, "run-length pass found %d distinct vectors among %lld rows (internal error)", U, n_items);
+    } else {
+        // host multiplicities are expanded: occurrence i is trajectory i
+        std::vector<float> w_exp, eta_exp;
+        const float* hw = s.w;
+        const float* he = s.eta;
+        if (host_src && s.multiplicity) {
+            w_exp.reserve((size_t)M * P);
+            eta_exp.reserve((size_t)M);
+            for (int64_t k = 0; k < s.n_w; ++k)
+                for (int c = 0; c < s.multiplicity[k]; ++c) {
+                    w_exp.insert(w_exp.end(), s.w + (size_t)k * P, s.w + (size_t)(k + 1) * P);
+                    eta_exp.push_back(s.eta[k]);
+                }
+            hw = w_exp.data(); he = eta_exp.data();
+            n_items = M;
+        }
+        HIP_TRY(mem.alloc(&d_item_off, (size_t)n_items));
+        HIP_TRY(mem.alloc(&d_eta, (size_t)n_items));
+        HIP_TRY(mem.alloc(&d_flag, (size_t)n_items));
+        HIP_TRY(mem.alloc(&d_cnt, (size_t)n_items));
+        HIP_TRY(mem.alloc(&d_nruns, 3));                 // [0] unresolved compact rows, [1] rows without eta, [2] first such chain
+        HIP_TRY(hipMemsetD32Async(d_cnt, 1, (size_t)n_items, st));
+        HIP_TRY(hipMemsetAsync(d_nruns, 0, 2 * sizeof(int), st));
+        HIP_TRY(hipMemsetAsync(d_nruns + 2, 0x7f, sizeof(int), st));
+        ElpdSel sel{};
+        sel.reg = 1; sel.P = P; sel.n_items = n_items; sel.item_off = d_item_off; sel.item_eta = d_eta; sel.flag = d_flag;
+        sel.error = d_nruns;
+        if (host_src) {
+            HIP_TRY(mem.alloc(&d_w, (size_t)n_items * P));
+            HIP_TRY(hipMemcpyAsync(d_w, hw, (size_t)n_items * P * sizeof(float), hipMemcpyHostToDevice, st));
+            HIP_TRY(mem.alloc(&d_heta, (size_t)n_items));
+            HIP_TRY(hipMemcpyAsync(d_heta, he, (size_t)n_items * sizeof(float), hipMemcpyHostToDevice, st));
+            sel.host = 1; sel.pos_w = d_w; sel.host_eta = d_heta;
+            base = d_w;
+        } else {
+            HIP_TRY(mem.alloc(&d_reps, reps.size()));
+            HIP_TRY(hipMemcpyAsync(d_reps, reps.data(), reps.size() * sizeof(int32_t), hipMemcpyHostToDevice, st));
+            sel.host = 0; sel.pos_w = h->d_pos_w; sel.scal = h->d_scal; sel.replicas = d_reps; sel.st_i = h->d_st_i; sel.cap = cap;
+            sel.PW = h->PW; sel.step0 = s.step0; sel.thin = s.thin; sel.m = m; sel.compact = h->plan.compact ? 1 : 0; sel.cur = h->cur;
+            base = h->d_pos_w;
+        }
+        hipLaunchKernelGGL(elpd_runs_kernel, dim3((unsigned)((n_items + ELPD_THREADS - 1) / ELPD_THREADS)), dim3(ELPD_THREADS), 0, st, sel);
+        HIP_TRY(hipGetLastError());
+        int err[3] = {0, 0, 0};
+        HIP_TRY(hipMemcpyAsync(err, d_nruns, sizeof err, hipMemcpyDeviceToHost, st));
+        if (int rc = wait_stream(h)) return rc;          // also keeps w_exp / eta_exp alive until the copies are done
+        if (err[0]) return fail(-2, "%d selected compact trace rows refer to rows that are not resident (internal error)", err[0]);
+        if (err[1]) {
+            const int c = err[2] >= 0 && err[2] < (int)reps.size() ? err[2] : 0;
+            return fail(-1, "noise: %d selected trace rows precede their chain's first accepted MH step (chain %d, local replica %d, "
+                            "among others): no eta = log tau^2 was recorded for them; start the selection later (a larger burn_in)",
+                        err[1], c, reps.empty() ? 0 : reps[(size_t)c]);
+        }
+        d_run_off = d_item_off;
+        U = (int)n_items;
+    }
+    if (s.n_trajectories) *s.n_trajectories = U;
+    // outputs on the device for every column
+    double* d_mean = nullptr; float* d_ostat = nullptr;
+    HIP_TRY(mem.alloc(&d_mean, (size_t)ncols));
+    if (s.n_ranks) {
+        HIP_TRY(mem.alloc(&d_ostat, (size_t)s.n_ranks * ncols));
+        HIP_TRY(mem.alloc(&d_ranks, (size_t)s.n_ranks));
+        HIP_TRY(hipMemcpyAsync(d_ranks, s.ranks, (size_t)s.n_ranks * sizeof(int64_t), hipMemcpyHostToDevice, st));
+    }
+    // stage b + c in blocks of origins and horizon steps: fx 4 U ob hb bytes, + 4 U I bytes of carried windows when the horizon
+    // is split (only with one origin per block: the columns of a block are then always contiguous)
+    const size_t budget = scratch_budget("PTNN_FORECAST_SCRATCH_BYTES");
+    const size_t traj_bytes = (size_t)U * sizeof(float);
+    long long ob = 1, hb = hz;
+    if (budget >= traj_bytes * hz) {
+        ob = std::max(1LL, std::min<long long>((long long)(budget / (traj_bytes * hz)), s.n_origins));
+    } else {
+        const long long fit = (long long)(budget / traj_bytes) - I;
+        hb = std::max(1LL, std::min<long long>(fit, hz));
+    }
+    ob = std::min<long long>(ob, 65535LL * WAVE);        // grid.y of the split layout
+    const bool split_h = hb < hz;
+    float *d_fx = nullptr, *d_win = nullptr;
+    HIP_TRY(mem.alloc(&d_fx, (size_t)ob * hb * U));
+    if (split_h) HIP_TRY(mem.alloc(&d_win, (size_t)U * I));
+    // the layout: a function of the shape alone (P), never of the budget
+    const int layout = P <= FC_LANE_MAX_P ? FC_LANE : FC_SPLIT;
+    const size_t lds = layout == FC_LANE ? (size_t)(FC_THREADS / WAVE) * P * WAVE * sizeof(float)
+                                         : (size_t)(round_up4(P) + 2 * (FC_THREADS / WAVE) * WAVE) * sizeof(float);
+    if (lds > 152 * 1024) return fail(-3, "forecast: a %d-parameter vector does not fit in LDS", P);
+    if (int rc = raise_lds_limit(reinterpret_cast<const void*>(h->shape->forecast_fwd), lds)) return rc;
+    // samples: the trajectory of every selected row, chain-major
+    std::vector<int> row_traj;
+    std::vector<float> fx_host;
+    if (s.samples) {
+        row_traj.resize((size_t)M);
+        if (noise) {
+            for (long long i = 0; i < M; ++i) row_traj[(size_t)i] = (int)i;
+        } else {
+            std::vector<int> item_run((size_t)n_items);
+            HIP_TRY(hipMemcpyAsync(item_run.data(), d_item_run, (size_t)n_items * sizeof(int), hipMemcpyDeviceToHost, st));
+            if (int rc = wait_stream(h)) return rc;
+            long long row = 0;
+            for (long long i = 0; i < n_items; ++i) {
+                const int reps_i = (host_src && s.multiplicity) ? s.multiplicity[i] : 1;
+                for (int k = 0; k < reps_i; ++k) row_traj[(size_t)row++] = item_run[(size_t)i];
+            }
+        }
+    }
+    ForecastFwd fa{};
+    fa.base = base; fa.run_off = d_run_off; fa.eta = noise ? d_eta : nullptr; fa.x = d_x; fa.xs = xs; fa.horizon = hz; fa.win = d_win;
+    fa.H = H; fa.P = P; fa.U = U; fa.layout = layout; fa.noise = noise ? 1 : 0;
+    fa.seed_lo = (uint32_t)(s.seed & 0xffffffffu); fa.seed_hi = (uint32_t)(s.seed >> 32); fa.fx = d_fx;
+    for (long long r0 = 0; r0 < s.n_origins; r0 += ob) {
+        const int nr = (int)std::min<long long>(ob, s.n_origins - r0);
+        for (long long k0 = 0; k0 < hz; k0 += hb) {
+            const int nk = (int)std::min<long long>(hb, hz - k0);
+            fa.r0 = (int)r0; fa.nr = nr; fa.k0 = (int)k0; fa.hb = nk;
+            dim3 grid;
+            if (layout == FC_LANE) {
+                const long long gx = (U + FC_THREADS - 1) / FC_THREADS;
+                grid = dim3((unsigned)gx, (unsigned)std::max(1LL, std::min<long long>((512 + gx - 1) / gx, nr)));
+            } else {
+                grid = dim3((unsigned)U, (unsigned)((nr + WAVE - 1) / WAVE));
+            }
+            hipLaunchKernelGGL(h->shape->forecast_fwd, grid, dim3(FC_THREADS), lds, st, fa);
+            HIP_TRY(hipGetLastError());
+            const long long col0 = r0 * hz + k0;             // the block's columns are contiguous (see above)
+            PredictRed ra{d_fx, d_cnt, U, 1, (int)col0, (int)ncols, M, s.n_ranks, d_ranks, d_mean, d_ostat, nullptr};
+            hipLaunchKernelGGL(predict_reduce_kernel, dim3((unsigned)(nr * nk)), dim3(PRED_THREADS), 0, st, ra);
+            HIP_TRY(hipGetLastError());
+            if (s.samples) {
+                fx_host.resize((size_t)nr * nk * U);
+                HIP_TRY(hipMemcpyAsync(fx_host.data(), d_fx, fx_host.size() * sizeof(float), hipMemcpyDeviceToHost, st));
+                if (int rc = wait_stream(h)) return rc;
+                for (long long row = 0; row < M; ++row) {
+                    const size_t u = (size_t)row_traj[(size_t)row];
+                    for (int rl = 0; rl < nr; ++rl) {
+                        float* dst = s.samples + ((size_t)row * s.n_origins + r0 + rl) * hz + k0;
+                        const float* src = fx_host.data() + (size_t)rl * nk * U + u;
+                        for (int k = 0; k < nk; ++k) dst[k] = src[(size_t)k * U];
+                    }
+                }
+            }
+        }
+    }
+    if (s.mean) HIP_TRY(hipMemcpyAsync(s.mean, d_mean, (size_t)ncols * sizeof(double), hipMemcpyDeviceToHost, st));
+    if (s.order_stats) HIP_TRY(hipMemcpyAsync(s.order_stats, d_ostat, (size_t)s.n_ranks * ncols * sizeof(float), hipMemcpyDeviceToHost, st));
+    return wait_stream(h);
+}
+
 static int run_model(ptnn_handle* h, int mode, const float* w_in, const float* tau_sq, int n, float* out, size_t out_floats,
                      int a0, int a1) {
     if (!h) return fail(-1, "null handle");

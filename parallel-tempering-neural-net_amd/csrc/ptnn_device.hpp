@@ -50,6 +50,7 @@ constexpr float LOG_2PI = 1.8378770664093453f;
 
 // Philox4x32-10 streams (specification shared with oracle/ptnn_oracle.py)
 constexpr uint32_t STREAM_STEP = 0, STREAM_WNOISE = 1, STREAM_SWAP = 2, STREAM_INIT = 3;
+constexpr uint32_t STREAM_FORECAST = 4;   // observation noise of ptnn_forecast (counter: step / 4, trajectory, origin)
 
 // per-replica float state (st_f) and int state (st_i) slots
 enum { SF_LIK = 0, SF_PRIOR, SF_TAU_LAST, SF_REC_RMSE_TR, SF_REC_RMSE_TE, SF_REC_ACC_TR, SF_REC_ACC_TE, SF_COUNT = 8 };
@@ -145,6 +146,7 @@ struct SegDyn {
 #include "ptnn_dev_tree.hpp"                 // prefetching tree schedule (segment_tree_body), with its own swap rounds inside a launch
 #include "ptnn_dev_kernels.hpp"              // model_kernel, persistent_loop, the __global__ segment kernels, the per-shape table
 #include "ptnn_dev_predict.hpp"              // posterior predictive: run-length pass over the selected rows, forward pass, per-column reduction
+#include "ptnn_dev_forecast.hpp"             // recursive multi-step forecasts: the per-shape recursive forward pass
 #ifndef PTNN_SHAPE_TU
 #include "ptnn_dev_convergence.hpp"          // convergence diagnostics: split-R-hat, split-ESS over trace columns (main translation unit only)
 #include "ptnn_dev_elpd.hpp"                 // predictive accuracy: lppd, WAIC, PSIS-LOO per data row (main translation unit only)

@@ -30,5 +30,6 @@ struct Shape {
     int split_ch, split_kr; // split-operand forward pass (SplitK<I>): 16-byte chunks per image row (0: not available for this n_in), fp32 k-steps
     seg_fn packm;           // 9 <= H <= 16: packed schedule over several CUs per replica
     void (*predict_fwd)(const PredictFwd);   // posterior predictive: network outputs of distinct vectors x input rows (every H)
+    void (*forecast_fwd)(const ForecastFwd); // recursive forecasts: trajectories x origins x horizon steps (REG, n_out == 1; else empty)
 };
 }  // namespace ptnn

@@ -106,6 +106,11 @@ PredictiveAccuracy = namedtuple("PredictiveAccuracy", "elpd_loo se_elpd_loo p_lo
                                 "lppd_i elpd_loo_i p_waic_i khat good_k n_high_k log_lik n_samples n_distinct")
 
 
+# forecast's result: mean [n_origins, horizon] float64; percentiles {p: [n_origins, horizon] float64}; samples [n_samples,
+# n_origins, horizon] float32 or None; n_samples; n_trajectories (per origin)
+Forecast = namedtuple("Forecast", "mean percentiles samples n_samples n_trajectories")
+
+
 def _se_total(x):
     """Standard error of a sum of pointwise values: sqrt(N var(x, ddof 1)) (Vehtari, Gelman & Gabry 2017, eq. 23)."""
     x = np.asarray(x, dtype=np.float64)
@@ -772,6 +777,100 @@ class ParallelTemperingBase:
                                   p_waic_i=p_waic_i, khat=khat, good_k=good_k, n_high_k=n_high,
                                   log_lik=(loglik if loglik is not None else out["loglik"]) if return_pointwise else None,
                                   n_samples=n_s, n_distinct=out["n_distinct"])
+
+    # ------------------------------------------------------------------ recursive forecasts (not in the reference)
+    def forecast(self, horizon, origin="end", *, burn_in=None, chains="all", thin=1, percentiles=(5, 95), noise=False, seed=None,
+                 weights=None, eta=None, return_samples=False):
+        """Multi-step forecasts past the data with their uncertainty, computed on the GPU from the sampled chains (DESIGN.md
+        section 14).  The fitted net is a one-step map x[t+1] = f(x[t-n_in+1 .. t]); each of `horizon` steps feeds its output back
+        as the newest input, for every posterior sample, and the spread across samples gives the bands.
+
+        `origin`: "end" -- the window right after the data, testdata[-1, 1:n_in+1]; this assumes the rows are consecutive windows
+        of one series with delay 1 (each row's inputs are the previous row's shifted by one, its target the next value), as the
+        shipped Data_OneStepAhead series and drivers.takens_embedding build them; "test" / "train" -- every row's inputs, one
+        forecast per row (rolling origins); or an array whose first n_in columns are the origin windows.  noise=False: each sample
+        runs the deterministic map; noise=True: each step also adds the sample's observation noise exp(eta / 2) z (tau^2 =
+        exp(eta), the likelihood's variance), fed back with it, drawn from the Philox stream STREAM_FORECAST of `seed` (None = the
+        object's seed).  The sample set is by default the columns of the posterior matrix run_chains() returns: every chain's
+        trace rows from int(NumSamples * burn_in) on.  `chains`: "all", "cold" (the temperature-1 chain) or a list of chain
+        indices; `thin`: every thin-th row.  With noise the trace's eta is recorded only from a chain's first accepted step on: a
+        selection that reaches earlier rows is refused.  `weights`: weight vectors instead of the trace -- [n, num_param] or a
+        pair (vectors, integer multiplicities), with `eta` [n] when noise is on.  Percentiles follow np.percentile(method="linear")
+        exactly.  -> Forecast(mean, percentiles, samples, n_samples, n_trajectories); outputs are [n_origins, horizon] (one origin
+        for "end"), samples [n_samples, n_origins, horizon] in chain-major order.  Regression nets with one output only."""
+        if self._sampler is None:
+            raise ValueError("forecast needs the chains' device handle: call initialize_chains() and run_chains() first")
+        if not isinstance(self._sampler, _lib.Sampler):
+            raise ValueError("forecast runs on one GPU: a ladder sharded over several devices is not supported")
+        if self.task == TASK_CLS or int(self.topology[2]) != 1:
+            raise ValueError("forecast needs a regression net with one output (a one-step map of one series)")
+        I = int(self.topology[0])
+        if isinstance(origin, str):
+            if origin == "end":
+                last = np.asarray(self.testdata)[-1]
+                org = np.ascontiguousarray(np.asarray(last[1:I + 1], dtype=np.float32).reshape(1, I))
+            elif origin in ("train", "test"):
+                org = origin
+            else:
+                raise ValueError(f"origin must be 'end', 'train', 'test' or an array, not {origin!r}")
+        else:
+            oa = np.asarray(origin)
+            if oa.ndim != 2 or oa.shape[1] < I:
+                raise ValueError(f"origin must be 2-D with at least n_in = {I} columns, got shape {oa.shape}")
+            org = np.ascontiguousarray(oa[:, :I], dtype=np.float32)
+        pcts = list(percentiles)
+        if any(not (0 <= p <= 100) for p in pcts):
+            raise ValueError(f"percentiles must lie in [0, 100], got {pcts}")
+        kw = {}
+        if weights is not None:
+            mult = None
+            if isinstance(weights, tuple):
+                weights, mult = weights
+            w = np.asarray(weights)
+            P = self.num_param
+            if w.ndim != 2 or P not in w.shape:
+                raise ValueError(f"weights must be [n, {P}] vectors (or their transpose), got shape {w.shape}")
+            if w.shape[1] != P:
+                w = w.T
+            if noise and eta is None:
+                raise ValueError("noise=True with weights= needs eta = log tau^2, one per vector (Sampler.eta_trace())")
+            kw = dict(w=w, multiplicity=mult, eta=eta if noise else None)
+            M = int(np.sum(np.asarray(mult, dtype=np.int64))) if mult is not None else w.shape[0]
+        else:
+            S = self.NumSamples
+            if self.label_swap:
+                raise ValueError("label_swap=True: trace rows are kept per chain slot, not per temperature; pass weights=")
+            if 0 < self.trace_capacity < S:
+                raise ValueError(f"trace_capacity = {self.trace_capacity} < NumSamples = {S}: the rows have been streamed off "
+                                 f"the device; pass weights=")
+            if not self._finished:
+                raise ValueError("no finished run_chains() on this object: the trace is incomplete; pass weights=")
+            b = self.burn_in if burn_in is None else burn_in
+            step0 = int(S * b)
+            if chains == "all":
+                reps = None
+            elif chains == "cold":
+                reps = [int(np.argmin(self.temperatures))]
+            else:
+                reps = [int(c) for c in chains]
+                if not reps or min(reps) < 0 or max(reps) >= self.num_chains:
+                    raise ValueError(f"chains {chains!r}: indices must lie in [0, {self.num_chains})")
+            kw = dict(replicas=reps, step0=step0, nsteps=S - step0, thin=int(thin))
+            nrep = self.num_chains if reps is None else len(reps)
+            M = nrep * max(0, -(-(S - step0) // max(1, int(thin))))
+        if M < 1:
+            raise ValueError("the selection holds no sample")
+        spots = percentile_ranks(M, pcts)
+        ranks = sorted({r for lo, hi, _ in spots for r in (lo, hi)})
+        if len(ranks) > _lib.PREDICT_MAX_RANKS:
+            raise ValueError(f"{len(pcts)} percentiles need {len(ranks)} order statistics: at most {_lib.PREDICT_MAX_RANKS} per call")
+        out = self._sampler.forecast(int(horizon), org, noise=bool(noise), seed=self.seed if seed is None else int(seed),
+                                     ranks=ranks, samples=bool(return_samples), **kw)
+        pos = {r: k for k, r in enumerate(ranks)}
+        os_ = out["order_stats"]
+        bands = {p: lerp_percentile(os_[pos[lo]], os_[pos[hi]], g) for p, (lo, hi, g) in zip(pcts, spots)}
+        return Forecast(mean=out["mean"], percentiles=bands, samples=out["samples"], n_samples=out["n_samples"],
+                        n_trajectories=out["n_trajectories"])
 
     def make_directory(self, directory):
         if not os.path.exists(directory):
