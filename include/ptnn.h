@@ -249,8 +249,9 @@ int ptnn_swap_apply_gathered(ptnn_handle *h, int phantom);
  * of the returned probabilities, first index on a tie -- is that class; samples [M, n_rows, n_out] = every selected row's outputs,
  * chain-major (the reference's fx_train_all / fx_test_all layout, REG:785-788); n_samples = M, n_distinct = distinct vectors.
  * Runs on the handle's stream behind everything queued (a failed run surfaces as at ptnn_sync) and returns when done; columns are
- * processed in blocks whose scratch stays under $PTNN_PREDICT_SCRATCH_BYTES (read per call, default 1 GiB), which changes no
- * result.  Touches no chain state, tape, counter or trace row.  Not with a communicator attached (one GPU only). */
+ * processed in blocks whose scratch stays under $PTNN_PREDICT_SCRATCH_BYTES (read per call, default 1 GiB) and of at most
+ * 65535 x 64 rows, which changes no result.  Touches no chain state, tape, counter or trace row.  Not with a communicator
+ * attached (one GPU only). */
 #define PTNN_PREDICT_X_HOST 0
 #define PTNN_PREDICT_X_TRAIN 1
 #define PTNN_PREDICT_X_TEST 2
@@ -353,8 +354,8 @@ int ptnn_convergence(ptnn_handle *h, const ptnn_convergence_spec *spec);
  * loglik_out [S, n_rows] (the pointwise log-likelihood, expanded, chain-major as ptnn_predict's samples; sources 1, 2);
  * n_samples = S; n_distinct = distinct samples.
  * Runs on the handle's stream behind everything queued and returns when done; rows are processed in blocks whose scratch stays
- * under $PTNN_ELPD_SCRATCH_BYTES (read per call, default 1 GiB), which changes no result.  Touches no chain state, tape, counter
- * or trace row.  Not with a communicator attached (one GPU only). */
+ * under $PTNN_ELPD_SCRATCH_BYTES (read per call, default 1 GiB) and of at most 65535 x 64 rows, which changes no result.
+ * Touches no chain state, tape, counter or trace row.  Not with a communicator attached (one GPU only). */
 #define PTNN_ELPD_TAIL_CAP 4096
 
 typedef struct ptnn_elpd_spec {

@@ -1960,6 +1960,7 @@ int ptnn_predict(ptnn_handle* h, const ptnn_predict_spec* spec) {
     const size_t budget = scratch_budget("PTNN_PREDICT_SCRATCH_BYTES");
     const size_t col_bytes = (size_t)U * sizeof(float);
     long long rows_blk = (long long)(budget / (col_bytes * O));
+    rows_blk = std::min<long long>(rows_blk, 65535LL * WAVE);       // grid.y of the forward pass: one 64-row tile per work-group
     rows_blk = std::max(1LL, std::min<long long>(rows_blk, s.n_rows));
     float* d_fx = nullptr;
     HIP_TRY(mem.alloc(&d_fx, (size_t)rows_blk * O * U));
@@ -2368,6 +2369,7 @@ int ptnn_elpd(ptnn_handle* h, const ptnn_elpd_spec* spec) {
     const size_t budget = scratch_budget("PTNN_ELPD_SCRATCH_BYTES");
     const size_t row_bytes = (size_t)U * (sizeof(float) * O + (s.loglik_out ? sizeof(double) : 0));
     long long rows_blk = (long long)(budget / row_bytes);
+    rows_blk = std::min<long long>(rows_blk, 65535LL * WAVE);       // grid.y of the forward pass, as ptnn_predict
     rows_blk = std::max(1LL, std::min<long long>(rows_blk, n_rows));
     float* d_fx = nullptr;
     double* d_llb = nullptr;
