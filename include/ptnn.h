@@ -443,6 +443,63 @@ typedef struct ptnn_forecast_spec {
 
 int ptnn_forecast(ptnn_handle *h, const ptnn_forecast_spec *spec);
 
+/* ---- log evidence (nothing in the reference: its ladder follows ptemcee's default_beta_ladder, REG:529-536, whose hottest
+ * rung "looks like the prior" for ptemcee's thermodynamic-integration estimate, which the reference never computes) ----
+ * Per rung k (draws at beta_k = 1 / T_k): statistics of the full-data log-likelihood U(w) over the rung's draws, and the same
+ * over draws of the normalised prior N(0, sigma_squared I_P); the host turns them into thermodynamic-integration (TI) and
+ * stepping-stone (SS) estimates of log Z (DESIGN.md section 15 states every formula).  Classification: U = sum_n log p_{y_n}
+ * (CLS:209-222, the per-row values ptnn_elpd sums), b = 0.  Regression (eta = log tau^2 integrated out of the improper 1 / tau^2
+ * prior): U = -(N / 2) log SSE, b = -log SSE, SSE = sum_n (y_n - f_n)^2 over the N training rows; SSE = 0 is refused.  f / p are
+ * the fp32 outputs of ptnn_predict's forward pass on the training rows; every sum after it is double, in row order.
+ * Sources: (1) the handle's trace, selected as ptnn_predict selects it (same rules and error texts): each listed replica is one
+ * rung, its rows step0, step0 + thin, ... its draws.  (2) host vectors w [n_rungs, n_per_rung, P] with optional multiplicities
+ * [n_rungs, n_per_rung].  (3) host U [n_rungs, n_per_rung] (finite doubles) with optional multiplicities: no forward pass.
+ * A rung's draws are its rows expanded by their multiplicities, in order; every rung needs at least 4 (the split ESS).
+ * Per rung, outputs [n_rungs], any may be NULL: u_mean, u_var (ddof 1), u_ess (the split-ESS of ptnn_convergence on the rung's
+ * U draws, in fp32, as one chain); with d [n_rungs] given: log_stone = log mean exp(d_k U) (exact maximum) and stone_relvar =
+ * var(exp(d_k U), ddof 1) / mean^2; n_draws [n_rungs] the expanded draw counts; u_out [sum n_draws] every draw's U, rung after rung
+ * (sources 1, 2); n_distinct = distinct vectors evaluated (sources 1, 2; runs merged as ptnn_predict merges them).
+ * Prior (n_prior > 0; needs n_a in [1, PTNN_EVIDENCE_MAX_A]): draw i is w = sigma z, sigma = sqrt(sigma_squared) in fp32, z_k
+ * = box_muller of philox4x32_10(k / 4, i, 0, 5, seed), component k % 4 (philox.py: prior_weights(seed, i, P, sigma)); per
+ * exponent a_j, outputs [n_a]: prior_log_mean_exp = log mean exp(b + a_j U) (exact maximum), prior_kish_ess = (sum w)^2 /
+ * sum w^2, prior_u_mean / prior_u_var = the mean and (population) variance of U weighted by w = exp(b + a_j U); u_prior_out
+ * [n_prior] every prior draw's U.
+ * Runs on the handle's stream behind everything queued and returns when done; training rows and prior draws are processed in
+ * blocks whose scratch stays under $PTNN_EVIDENCE_SCRATCH_BYTES (read per call, default 1 GiB), which changes no result.
+ * Touches no chain state, tape, counter or trace row.  Not with a communicator attached (one GPU only). */
+#define PTNN_EVIDENCE_MAX_A 4
+
+typedef struct ptnn_evidence_spec {
+    int32_t struct_bytes;         /* = sizeof(ptnn_evidence_spec): ABI guard */
+    /* source 1: the trace (used when w == NULL and u == NULL); each replica is a rung */
+    const int32_t *replicas;      /* local replica indices, or NULL = all */
+    int32_t n_replicas;           /* entries of replicas (ignored when NULL) */
+    int32_t step0, nsteps, thin;  /* trace rows step0, step0 + thin, ... < step0 + nsteps (thin >= 1) */
+    /* source 2: host vectors; source 3: host U */
+    const float *w;               /* [n_rungs, n_per_rung, P] or NULL */
+    const double *u;              /* [n_rungs, n_per_rung] or NULL */
+    const int32_t *multiplicity;  /* sources 2, 3: [n_rungs, n_per_rung] >= 0, or NULL = 1 each */
+    int32_t n_rungs;              /* sources 2, 3 */
+    int32_t reserved_;            /* set 0 */
+    int64_t n_per_rung;           /* sources 2, 3 */
+    const double *d;              /* [n_rungs] stone exponents, or NULL */
+    /* prior draws */
+    int64_t n_prior;              /* 0 = none */
+    uint64_t seed;
+    const double *a;              /* [n_a] exponents */
+    int32_t n_a;
+    int32_t reserved2_;           /* set 0 */
+    /* outputs */
+    double *u_mean, *u_var, *u_ess, *log_stone, *stone_relvar;               /* [n_rungs] */
+    int64_t *n_draws;                                                        /* [n_rungs] */
+    double *prior_log_mean_exp, *prior_kish_ess, *prior_u_mean, *prior_u_var; /* [n_a] */
+    double *u_out;                                                           /* [sum n_draws] */
+    double *u_prior_out;                                                     /* [n_prior] */
+    int64_t *n_distinct;
+} ptnn_evidence_spec;
+
+int ptnn_evidence(ptnn_handle *h, const ptnn_evidence_spec *spec);
+
 /* the HIP stream (hipStream_t) all of this handle's work is queued on: lets the caller order its collectives after the
  * segment / before the swap kernels on the device instead of synchronising the host */
 int ptnn_stream(ptnn_handle *h, void **hip_stream);

@@ -94,6 +94,25 @@ class ForecastSpec(C.Structure):
     ]
 
 
+class EvidenceSpec(C.Structure):
+    """ptnn_evidence_spec (include/ptnn.h)."""
+    _fields_ = [
+        ("struct_bytes", C.c_int32),
+        ("replicas", C.POINTER(C.c_int32)), ("n_replicas", C.c_int32), ("step0", C.c_int32), ("nsteps", C.c_int32), ("thin", C.c_int32),
+        ("w", C.POINTER(C.c_float)), ("u", C.POINTER(C.c_double)), ("multiplicity", C.POINTER(C.c_int32)),
+        ("n_rungs", C.c_int32), ("reserved_", C.c_int32), ("n_per_rung", C.c_int64), ("d", C.POINTER(C.c_double)),
+        ("n_prior", C.c_int64), ("seed", C.c_uint64), ("a", C.POINTER(C.c_double)), ("n_a", C.c_int32), ("reserved2_", C.c_int32),
+        ("u_mean", C.POINTER(C.c_double)), ("u_var", C.POINTER(C.c_double)), ("u_ess", C.POINTER(C.c_double)),
+        ("log_stone", C.POINTER(C.c_double)), ("stone_relvar", C.POINTER(C.c_double)), ("n_draws", C.POINTER(C.c_int64)),
+        ("prior_log_mean_exp", C.POINTER(C.c_double)), ("prior_kish_ess", C.POINTER(C.c_double)),
+        ("prior_u_mean", C.POINTER(C.c_double)), ("prior_u_var", C.POINTER(C.c_double)),
+        ("u_out", C.POINTER(C.c_double)), ("u_prior_out", C.POINTER(C.c_double)), ("n_distinct", C.POINTER(C.c_int64)),
+    ]
+
+
+EVIDENCE_MAX_A = 4
+
+
 def library_path():
     return os.environ.get("PTNN_LIBRARY", os.path.join(_HERE, "libptnn.so"))
 
@@ -175,6 +194,7 @@ SYMBOLS = {
     "ptnn_convergence": (C.c_int, [C.c_void_p, C.POINTER(ConvergenceSpec)]),
     "ptnn_elpd": (C.c_int, [C.c_void_p, C.POINTER(ElpdSpec)]),
     "ptnn_forecast": (C.c_int, [C.c_void_p, C.POINTER(ForecastSpec)]),
+    "ptnn_evidence": (C.c_int, [C.c_void_p, C.POINTER(EvidenceSpec)]),
 }
 
 
@@ -778,6 +798,87 @@ class Sampler:
         spec.n_samples, spec.n_trajectories = C.pointer(ns), C.pointer(nt)
         self._check(self.lib.ptnn_forecast(self.h, C.byref(spec)))
         out["n_samples"], out["n_trajectories"] = ns.value, nt.value
+        return out
+
+    def evidence(self, *, replicas=None, step0=0, nsteps=None, thin=1, w=None, u=None, multiplicity=None, d=None, n_prior=0, seed=0,
+                 a=(), u_out=False, u_prior_out=False):
+        """ptnn_evidence: per-rung statistics of the full-data log-likelihood U and of prior draws, on the device.  Source: the
+        trace rows step0, step0 + thin, ... < step0 + nsteps of `replicas` (None = all; one rung each), host vectors w
+        [K, n, P], or a host U [K, n] float64; sources 2 and 3 take optional integer `multiplicity` [K, n].  d [K]: stone
+        exponents; n_prior draws of the prior (Philox stream STREAM_PRIOR of `seed`) with exponents a (at most 4).
+        -> dict(u_mean, u_var, u_ess, log_stone, stone_relvar [K] float64, n_draws [K] int64, prior_log_mean_exp,
+        prior_kish_ess, prior_u_mean, prior_u_var [n_a] float64, u [sum n_draws] float64 (u_out), u_prior [n_prior] float64
+        (u_prior_out), n_distinct)."""
+        spec = EvidenceSpec()
+        spec.struct_bytes = C.sizeof(EvidenceSpec)
+        keep = []
+        dp = C.POINTER(C.c_double)
+        if u is not None:
+            ua = np.ascontiguousarray(u, dtype=np.float64)
+            if ua.ndim != 2:
+                raise ValueError(f"u must be [n_rungs, n_per_rung], got shape {ua.shape}")
+            keep.append(ua)
+            spec.u, spec.n_rungs, spec.n_per_rung = ua.ctypes.data_as(dp), ua.shape[0], ua.shape[1]
+            host = ua.shape
+        elif w is not None:
+            wa = _f32(w)
+            if wa.ndim != 3 or wa.shape[2] != self.P:
+                raise ValueError(f"w must be [n_rungs, n_per_rung, {self.P}], got shape {wa.shape}")
+            keep.append(wa)
+            spec.w, spec.n_rungs, spec.n_per_rung = _ptr(wa), wa.shape[0], wa.shape[1]
+            host = wa.shape[:2]
+        else:
+            host = None
+            if replicas is not None:
+                ra = np.ascontiguousarray(replicas, dtype=np.int32).reshape(-1)
+                keep.append(ra)
+                spec.replicas, spec.n_replicas = _ptr(ra, _ip), ra.size
+                K = ra.size
+            else:
+                K = self.R
+            spec.step0 = int(step0)
+            spec.nsteps = int(self.S - step0 if nsteps is None else nsteps)
+            spec.thin = int(thin)
+            per = max(0, -(-spec.nsteps // max(1, spec.thin)))
+            total = K * per
+        if host is not None:
+            K = host[0]
+            if multiplicity is not None:
+                mu = np.ascontiguousarray(multiplicity, dtype=np.int32)
+                if mu.shape != tuple(host):
+                    raise ValueError(f"multiplicity must be [n_rungs, n_per_rung] = {tuple(host)}, got shape {mu.shape}")
+                keep.append(mu)
+                spec.multiplicity = _ptr(mu, _ip)
+                total = int(np.maximum(mu, 0).astype(np.int64).sum())
+            else:
+                total = host[0] * host[1]
+        if d is not None:
+            da = np.ascontiguousarray(d, dtype=np.float64).reshape(-1)
+            if da.size != K:
+                raise ValueError(f"d must have one exponent per rung ({K}), got {da.size}")
+            keep.append(da)
+            spec.d = da.ctypes.data_as(dp)
+        aa = np.ascontiguousarray(a, dtype=np.float64).reshape(-1)
+        keep.append(aa)
+        spec.n_prior, spec.seed, spec.n_a = int(n_prior), int(seed) & 0xFFFFFFFFFFFFFFFF, aa.size
+        spec.a = aa.ctypes.data_as(dp) if aa.size else None
+        out = {k: np.full(K, np.nan) for k in ("u_mean", "u_var", "u_ess", "log_stone", "stone_relvar")}
+        out["n_draws"] = np.zeros(K, np.int64)
+        for k in ("prior_log_mean_exp", "prior_kish_ess", "prior_u_mean", "prior_u_var"):
+            out[k] = np.full(aa.size, np.nan)
+        for k in ("u_mean", "u_var", "u_ess", "prior_log_mean_exp", "prior_kish_ess", "prior_u_mean", "prior_u_var"):
+            setattr(spec, k, out[k].ctypes.data_as(dp))
+        if d is not None:
+            spec.log_stone, spec.stone_relvar = out["log_stone"].ctypes.data_as(dp), out["stone_relvar"].ctypes.data_as(dp)
+        spec.n_draws = out["n_draws"].ctypes.data_as(C.POINTER(C.c_int64))
+        out["u"] = np.empty(max(total, 0)) if u_out else None
+        out["u_prior"] = np.empty(max(int(n_prior), 0)) if u_prior_out else None
+        spec.u_out = out["u"].ctypes.data_as(dp) if u_out else None
+        spec.u_prior_out = out["u_prior"].ctypes.data_as(dp) if u_prior_out else None
+        nd = C.c_int64(0)
+        spec.n_distinct = C.pointer(nd)
+        self._check(self.lib.ptnn_evidence(self.h, C.byref(spec)))
+        out["n_distinct"] = nd.value
         return out
 
     def langevin_gradient(self, w):

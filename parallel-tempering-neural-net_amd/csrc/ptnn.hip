@@ -2017,6 +2017,105 @@ int ptnn_predict(ptnn_handle* h, const ptnn_predict_spec* spec) {
 // ---- convergence diagnostics (ptnn_dev_convergence.hpp) ----
 static_assert(PTNN_TR_LIKEH == TR_LIKEH && PTNN_TR_ACC_TE == TR_ACC_TE && PTNN_TR_ACCEPT == TR_ACCEPT && PTNN_TR_SRC == TR_SRC, "ptnn.h TR order");
 
+// split-R-hat / split-ESS of Q quantities over C chains of n draws, gathered by `ga` (its source fields set: trace rows, or
+// draws [C][n][Q] in device memory); outputs are host arrays, any may be null.  Shared by ptnn_convergence and ptnn_evidence.
+static int conv_drive(ptnn_handle* h, DeviceScratch& mem, ConvGather ga, const std::vector<int>& qcol, int C, int n, int n_lags,
+                      double* mean, double* var, double* r_hat, double* ess, int32_t* trunc_lag, double* ess_chain, double* rho) {
+    const int hl = n / 2, M = 2 * C, Q = (int)qcol.size();
+    const bool per_chain = ess_chain != nullptr;
+    const int NS = 1 + (per_chain ? C : 0);
+    hipStream_t st = h->stream;
+    int *d_qcol = nullptr, *d_error = nullptr;
+    HIP_TRY(mem.alloc(&d_qcol, (size_t)Q));
+    HIP_TRY(hipMemcpyAsync(d_qcol, qcol.data(), (size_t)Q * sizeof(int), hipMemcpyHostToDevice, st));
+    HIP_TRY(mem.alloc(&d_error, 1));
+    HIP_TRY(hipMemsetAsync(d_error, 0, sizeof(int), st));
+    ga.C = C; ga.n = n; ga.h = hl; ga.error = d_error;
+    // outputs of every quantity
+    double *d_mean = nullptr, *d_var = nullptr, *d_rhat = nullptr, *d_ess = nullptr, *d_essc = nullptr, *d_rho = nullptr;
+    int* d_trunc = nullptr;
+    HIP_TRY(mem.alloc(&d_mean, (size_t)Q));
+    HIP_TRY(mem.alloc(&d_var, (size_t)Q));
+    HIP_TRY(mem.alloc(&d_rhat, (size_t)Q));
+    HIP_TRY(mem.alloc(&d_ess, (size_t)Q));
+    HIP_TRY(mem.alloc(&d_trunc, (size_t)Q));
+    if (per_chain) HIP_TRY(mem.alloc(&d_essc, (size_t)C * Q));
+    if (n_lags) HIP_TRY(mem.alloc(&d_rho, (size_t)n_lags * Q));
+    // blocks of quantities: the scratch of one quantity, every stage's
+    const size_t per_q = sizeof(double) * ((size_t)M * hl + 2 * (size_t)M + 2 * (size_t)C + 2 + (size_t)CONV_MAX_LAGS * C)
+                       + sizeof(ConvSeq) * NS + sizeof(int) * (3 + (per_chain ? (size_t)C : 0));
+    const int Qb = (int)std::max<size_t>(1, std::min<size_t>(scratch_budget("PTNN_CONVERGENCE_SCRATCH_BYTES") / per_q, (size_t)Q));
+    double *d_x = nullptr, *d_smean = nullptr, *d_ssq = nullptr, *d_csum = nullptr, *d_cm2 = nullptr, *d_pmean = nullptr, *d_pvar = nullptr;
+    double* d_chain = nullptr;
+    ConvSeq* d_seq = nullptr;
+    int *d_full = nullptr, *d_copen = nullptr, *d_any = nullptr, *d_open = nullptr;
+    HIP_TRY(mem.alloc(&d_x, (size_t)Qb * M * hl));
+    HIP_TRY(mem.alloc(&d_smean, (size_t)Qb * M));
+    HIP_TRY(mem.alloc(&d_ssq, (size_t)Qb * M));
+    HIP_TRY(mem.alloc(&d_csum, (size_t)Qb * C));
+    HIP_TRY(mem.alloc(&d_cm2, (size_t)Qb * C));
+    HIP_TRY(mem.alloc(&d_pmean, (size_t)Qb));
+    HIP_TRY(mem.alloc(&d_pvar, (size_t)Qb));
+    HIP_TRY(mem.alloc(&d_chain, (size_t)CONV_MAX_LAGS * C * Qb));
+    HIP_TRY(mem.alloc(&d_seq, (size_t)Qb * NS));
+    HIP_TRY(mem.alloc(&d_full, (size_t)Qb));
+    if (per_chain) HIP_TRY(mem.alloc(&d_copen, (size_t)Qb * C));
+    HIP_TRY(mem.alloc(&d_any, (size_t)Qb));
+    HIP_TRY(mem.alloc(&d_open, (size_t)Qb));
+    std::vector<int> any_h((size_t)Qb), open_h((size_t)Qb);
+    for (int q0 = 0; q0 < Q; q0 += Qb) {
+        const int nq = std::min(Qb, Q - q0);
+        // 1. gather and moments
+        ga.qcol = d_qcol + q0; ga.nq = nq; ga.x = d_x; ga.smean = d_smean; ga.ssq = d_ssq; ga.csum = d_csum; ga.cm2 = d_cm2;
+        hipLaunchKernelGGL(conv_gather_kernel, dim3((unsigned)C, (unsigned)((nq + CONV_TILE - 1) / CONV_TILE)), dim3(CONV_THREADS), 0, st, ga);
+        HIP_TRY(hipGetLastError());
+        // 2. W, var+ and the state of every sequence
+        ConvMoments mo{d_smean, d_ssq, d_csum, d_cm2, nq, C, n, hl, NS, d_seq, d_pmean, d_pvar};
+        const long long nseq = (long long)nq * NS;
+        hipLaunchKernelGGL(conv_moments_kernel, dim3((unsigned)((nseq + CONV_THREADS - 1) / CONV_THREADS)), dim3(CONV_THREADS), 0, st, mo);
+        HIP_TRY(hipGetLastError());
+        HIP_TRY(hipMemsetAsync(d_full, 1, (size_t)nq * sizeof(int), st));             // non-zero: every sequence starts open
+        if (per_chain) HIP_TRY(hipMemsetAsync(d_copen, 1, (size_t)nq * C * sizeof(int), st));
+        int n_open = nq;
+        for (int k = 0; k < nq; ++k) open_h[(size_t)k] = k;
+        HIP_TRY(hipMemcpyAsync(d_open, open_h.data(), (size_t)nq * sizeof(int), hipMemcpyHostToDevice, st));
+        // 3. blocks of lags, each twice the last, for the quantities with a sequence still open
+        for (int t0 = 0, nl = CONV_LAG_TILE; n_open > 0 && t0 < hl; t0 += nl, nl = std::min(2 * nl, CONV_MAX_LAGS)) {
+            nl = std::min(nl, (hl - t0 + CONV_LAG_TILE - 1) / CONV_LAG_TILE * CONV_LAG_TILE);
+            ConvLags la{d_x, C, hl, d_open, n_open, d_full, d_copen, t0, d_chain};
+            hipLaunchKernelGGL(conv_lags_kernel, dim3((unsigned)((n_open + CONV_TILE - 1) / CONV_TILE), (unsigned)(nl / CONV_LAG_TILE), (unsigned)C), dim3(CONV_THREADS), 0, st, la);
+            HIP_TRY(hipGetLastError());
+            ConvStep sp{d_chain, d_open, n_open, C, hl, NS, t0, nl, n_lags, Q, q0, d_seq, d_full, d_copen, d_any, d_rho};
+            hipLaunchKernelGGL(conv_step_kernel, dim3((unsigned)n_open), dim3(WAVE), 0, st, sp);
+            HIP_TRY(hipGetLastError());
+            HIP_TRY(hipMemcpyAsync(any_h.data(), d_any, (size_t)nq * sizeof(int), hipMemcpyDeviceToHost, st));
+            if (int rc = wait_stream(h)) return rc;
+            const int was_open = n_open;
+            n_open = 0;
+            for (int k = 0; k < was_open; ++k)
+                if (any_h[(size_t)open_h[(size_t)k]]) open_h[(size_t)n_open++] = open_h[(size_t)k];
+            if (n_open) HIP_TRY(hipMemcpyAsync(d_open, open_h.data(), (size_t)n_open * sizeof(int), hipMemcpyHostToDevice, st));
+        }
+        if (n_open) return fail(-2, "%d quantities still open after every lag (internal error)", n_open);
+        // 4. tau, ess, r_hat
+        ConvFinish fi{d_seq, d_pmean, d_pvar, nq, NS, C, hl, Q, q0, d_mean, d_var, d_rhat, d_ess, d_essc, d_trunc};
+        hipLaunchKernelGGL(conv_finish_kernel, dim3((unsigned)((nseq + CONV_THREADS - 1) / CONV_THREADS)), dim3(CONV_THREADS), 0, st, fi);
+        HIP_TRY(hipGetLastError());
+    }
+    int err = 0;
+    HIP_TRY(hipMemcpyAsync(&err, d_error, sizeof(int), hipMemcpyDeviceToHost, st));
+    if (mean) HIP_TRY(hipMemcpyAsync(mean, d_mean, (size_t)Q * sizeof(double), hipMemcpyDeviceToHost, st));
+    if (var) HIP_TRY(hipMemcpyAsync(var, d_var, (size_t)Q * sizeof(double), hipMemcpyDeviceToHost, st));
+    if (r_hat) HIP_TRY(hipMemcpyAsync(r_hat, d_rhat, (size_t)Q * sizeof(double), hipMemcpyDeviceToHost, st));
+    if (ess) HIP_TRY(hipMemcpyAsync(ess, d_ess, (size_t)Q * sizeof(double), hipMemcpyDeviceToHost, st));
+    if (trunc_lag) HIP_TRY(hipMemcpyAsync(trunc_lag, d_trunc, (size_t)Q * sizeof(int32_t), hipMemcpyDeviceToHost, st));
+    if (per_chain) HIP_TRY(hipMemcpyAsync(ess_chain, d_essc, (size_t)C * Q * sizeof(double), hipMemcpyDeviceToHost, st));
+    if (n_lags) HIP_TRY(hipMemcpyAsync(rho, d_rho, (size_t)n_lags * Q * sizeof(double), hipMemcpyDeviceToHost, st));
+    if (int rc = wait_stream(h)) return rc;
+    if (err) return fail(-2, "%d selected compact trace rows refer to rows that are not resident (internal error)", err);
+    return 0;
+}
+
 int ptnn_convergence(ptnn_handle* h, const ptnn_convergence_spec* spec) {
     // argument checks first: none of them needs the handle or a device
     if (!spec) return fail(-1, "null argument");
@@ -2066,21 +2165,15 @@ int ptnn_convergence(ptnn_handle* h, const ptnn_convergence_spec* spec) {
             if (s.scalars & (1 << c)) qcol.push_back(-1 - c);
         if (qcol.empty()) return fail(-1, "no quantity selected");
     }
-    const int hl = n / 2, M = 2 * C, Q = (int)qcol.size();
+    const int hl = n / 2, Q = (int)qcol.size();
     if (s.n_lags > hl) return fail(-1, "n_lags = %d exceeds the split-chain length %d", s.n_lags, hl);
-    const bool per_chain = s.ess_chain != nullptr;
-    const int NS = 1 + (per_chain ? C : 0);
 
     HIP_TRY(hipSetDevice(h->cfg.device_id));
     if (int rc = finish_stream(h)) return rc;          // behind everything queued; a failed run is refused here
     hipStream_t st = h->stream;
     DeviceScratch mem;
-    int *d_qcol = nullptr, *d_reps = nullptr, *d_error = nullptr;
+    int* d_reps = nullptr;
     float* d_draws = nullptr;
-    HIP_TRY(mem.alloc(&d_qcol, (size_t)Q));
-    HIP_TRY(hipMemcpyAsync(d_qcol, qcol.data(), (size_t)Q * sizeof(int), hipMemcpyHostToDevice, st));
-    HIP_TRY(mem.alloc(&d_error, 1));
-    HIP_TRY(hipMemsetAsync(d_error, 0, sizeof(int), st));
     ConvGather ga{};
     if (host_src) {
         const size_t nd = (size_t)C * n * Q;
@@ -2093,90 +2186,7 @@ int ptnn_convergence(ptnn_handle* h, const ptnn_convergence_spec* spec) {
         ga.host = 0; ga.pos_w = h->d_pos_w; ga.scal = h->d_scal; ga.replicas = d_reps; ga.cap = cap; ga.PW = h->PW;
         ga.step0 = s.step0; ga.thin = s.thin; ga.compact = h->plan.compact ? 1 : 0;
     }
-    ga.C = C; ga.n = n; ga.h = hl; ga.error = d_error;
-    // outputs of every quantity
-    double *d_mean = nullptr, *d_var = nullptr, *d_rhat = nullptr, *d_ess = nullptr, *d_essc = nullptr, *d_rho = nullptr;
-    int* d_trunc = nullptr;
-    HIP_TRY(mem.alloc(&d_mean, (size_t)Q));
-    HIP_TRY(mem.alloc(&d_var, (size_t)Q));
-    HIP_TRY(mem.alloc(&d_rhat, (size_t)Q));
-    HIP_TRY(mem.alloc(&d_ess, (size_t)Q));
-    HIP_TRY(mem.alloc(&d_trunc, (size_t)Q));
-    if (per_chain) HIP_TRY(mem.alloc(&d_essc, (size_t)C * Q));
-    if (s.n_lags) HIP_TRY(mem.alloc(&d_rho, (size_t)s.n_lags * Q));
-    // blocks of quantities: the scratch of one quantity, every stage's
-    const size_t per_q = sizeof(double) * ((size_t)M * hl + 2 * (size_t)M + 2 * (size_t)C + 2 + (size_t)CONV_MAX_LAGS * C)
-                       + sizeof(ConvSeq) * NS + sizeof(int) * (3 + (per_chain ? (size_t)C : 0));
-    const int Qb = (int)std::max<size_t>(1, std::min<size_t>(scratch_budget("PTNN_CONVERGENCE_SCRATCH_BYTES") / per_q, (size_t)Q));
-    double *d_x = nullptr, *d_smean = nullptr, *d_ssq = nullptr, *d_csum = nullptr, *d_cm2 = nullptr, *d_pmean = nullptr, *d_pvar = nullptr;
-    double* d_chain = nullptr;
-    ConvSeq* d_seq = nullptr;
-    int *d_full = nullptr, *d_copen = nullptr, *d_any = nullptr, *d_open = nullptr;
-    HIP_TRY(mem.alloc(&d_x, (size_t)Qb * M * hl));
-    HIP_TRY(mem.alloc(&d_smean, (size_t)Qb * M));
-    HIP_TRY(mem.alloc(&d_ssq, (size_t)Qb * M));
-    HIP_TRY(mem.alloc(&d_csum, (size_t)Qb * C));
-    HIP_TRY(mem.alloc(&d_cm2, (size_t)Qb * C));
-    HIP_TRY(mem.alloc(&d_pmean, (size_t)Qb));
-    HIP_TRY(mem.alloc(&d_pvar, (size_t)Qb));
-    HIP_TRY(mem.alloc(&d_chain, (size_t)CONV_MAX_LAGS * C * Qb));
-    HIP_TRY(mem.alloc(&d_seq, (size_t)Qb * NS));
-    HIP_TRY(mem.alloc(&d_full, (size_t)Qb));
-    if (per_chain) HIP_TRY(mem.alloc(&d_copen, (size_t)Qb * C));
-    HIP_TRY(mem.alloc(&d_any, (size_t)Qb));
-    HIP_TRY(mem.alloc(&d_open, (size_t)Qb));
-    std::vector<int> any_h((size_t)Qb), open_h((size_t)Qb);
-    for (int q0 = 0; q0 < Q; q0 += Qb) {
-        const int nq = std::min(Qb, Q - q0);
-        // 1. gather and moments
-        ga.qcol = d_qcol + q0; ga.nq = nq; ga.x = d_x; ga.smean = d_smean; ga.ssq = d_ssq; ga.csum = d_csum; ga.cm2 = d_cm2;
-        hipLaunchKernelGGL(conv_gather_kernel, dim3((unsigned)C, (unsigned)((nq + CONV_TILE - 1) / CONV_TILE)), dim3(CONV_THREADS), 0, st, ga);
-        HIP_TRY(hipGetLastError());
-        // 2. W, var+ and the state of every sequence
-        ConvMoments mo{d_smean, d_ssq, d_csum, d_cm2, nq, C, n, hl, NS, d_seq, d_pmean, d_pvar};
-        const long long nseq = (long long)nq * NS;
-        hipLaunchKernelGGL(conv_moments_kernel, dim3((unsigned)((nseq + CONV_THREADS - 1) / CONV_THREADS)), dim3(CONV_THREADS), 0, st, mo);
-        HIP_TRY(hipGetLastError());
-        HIP_TRY(hipMemsetAsync(d_full, 1, (size_t)nq * sizeof(int), st));             // non-zero: every sequence starts open
-        if (per_chain) HIP_TRY(hipMemsetAsync(d_copen, 1, (size_t)nq * C * sizeof(int), st));
-        int n_open = nq;
-        for (int k = 0; k < nq; ++k) open_h[(size_t)k] = k;
-        HIP_TRY(hipMemcpyAsync(d_open, open_h.data(), (size_t)nq * sizeof(int), hipMemcpyHostToDevice, st));
-        // 3. blocks of lags, each twice the last, for the quantities with a sequence still open
-        for (int t0 = 0, nl = CONV_LAG_TILE; n_open > 0 && t0 < hl; t0 += nl, nl = std::min(2 * nl, CONV_MAX_LAGS)) {
-            nl = std::min(nl, (hl - t0 + CONV_LAG_TILE - 1) / CONV_LAG_TILE * CONV_LAG_TILE);
-            ConvLags la{d_x, C, hl, d_open, n_open, d_full, d_copen, t0, d_chain};
-            hipLaunchKernelGGL(conv_lags_kernel, dim3((unsigned)((n_open + CONV_TILE - 1) / CONV_TILE), (unsigned)(nl / CONV_LAG_TILE), (unsigned)C), dim3(CONV_THREADS), 0, st, la);
-            HIP_TRY(hipGetLastError());
-            ConvStep sp{d_chain, d_open, n_open, C, hl, NS, t0, nl, s.n_lags, Q, q0, d_seq, d_full, d_copen, d_any, d_rho};
-            hipLaunchKernelGGL(conv_step_kernel, dim3((unsigned)n_open), dim3(WAVE), 0, st, sp);
-            HIP_TRY(hipGetLastError());
-            HIP_TRY(hipMemcpyAsync(any_h.data(), d_any, (size_t)nq * sizeof(int), hipMemcpyDeviceToHost, st));
-            if (int rc = wait_stream(h)) return rc;
-            const int was_open = n_open;
-            n_open = 0;
-            for (int k = 0; k < was_open; ++k)
-                if (any_h[(size_t)open_h[(size_t)k]]) open_h[(size_t)n_open++] = open_h[(size_t)k];
-            if (n_open) HIP_TRY(hipMemcpyAsync(d_open, open_h.data(), (size_t)n_open * sizeof(int), hipMemcpyHostToDevice, st));
-        }
-        if (n_open) return fail(-2, "%d quantities still open after every lag (internal error)", n_open);
-        // 4. tau, ess, r_hat
-        ConvFinish fi{d_seq, d_pmean, d_pvar, nq, NS, C, hl, Q, q0, d_mean, d_var, d_rhat, d_ess, d_essc, d_trunc};
-        hipLaunchKernelGGL(conv_finish_kernel, dim3((unsigned)((nseq + CONV_THREADS - 1) / CONV_THREADS)), dim3(CONV_THREADS), 0, st, fi);
-        HIP_TRY(hipGetLastError());
-    }
-    int err = 0;
-    HIP_TRY(hipMemcpyAsync(&err, d_error, sizeof(int), hipMemcpyDeviceToHost, st));
-    if (s.mean) HIP_TRY(hipMemcpyAsync(s.mean, d_mean, (size_t)Q * sizeof(double), hipMemcpyDeviceToHost, st));
-    if (s.var) HIP_TRY(hipMemcpyAsync(s.var, d_var, (size_t)Q * sizeof(double), hipMemcpyDeviceToHost, st));
-    if (s.r_hat) HIP_TRY(hipMemcpyAsync(s.r_hat, d_rhat, (size_t)Q * sizeof(double), hipMemcpyDeviceToHost, st));
-    if (s.ess) HIP_TRY(hipMemcpyAsync(s.ess, d_ess, (size_t)Q * sizeof(double), hipMemcpyDeviceToHost, st));
-    if (s.trunc_lag) HIP_TRY(hipMemcpyAsync(s.trunc_lag, d_trunc, (size_t)Q * sizeof(int32_t), hipMemcpyDeviceToHost, st));
-    if (per_chain) HIP_TRY(hipMemcpyAsync(s.ess_chain, d_essc, (size_t)C * Q * sizeof(double), hipMemcpyDeviceToHost, st));
-    if (s.n_lags) HIP_TRY(hipMemcpyAsync(s.rho, d_rho, (size_t)s.n_lags * Q * sizeof(double), hipMemcpyDeviceToHost, st));
-    if (int rc = wait_stream(h)) return rc;
-    if (err) return fail(-2, "%d selected compact trace rows refer to rows that are not resident (internal error)", err);
-    return 0;
+    return conv_drive(h, mem, ga, qcol, C, n, s.n_lags, s.mean, s.var, s.r_hat, s.ess, s.trunc_lag, s.ess_chain, s.rho);
 }
 
 // ---- predictive accuracy (ptnn_dev_elpd.hpp) ----
@@ -2682,6 +2692,295 @@ int ptnn_forecast(ptnn_handle* h, const ptnn_forecast_spec* spec) {
     if (s.mean) HIP_TRY(hipMemcpyAsync(s.mean, d_mean, (size_t)ncols * sizeof(double), hipMemcpyDeviceToHost, st));
     if (s.order_stats) HIP_TRY(hipMemcpyAsync(s.order_stats, d_ostat, (size_t)s.n_ranks * ncols * sizeof(float), hipMemcpyDeviceToHost, st));
     return wait_stream(h);
+}
+
+// ---- log evidence (ptnn_dev_evidence.hpp) ----
+static_assert(PTNN_EVIDENCE_MAX_A == EVID_MAX_A, "ptnn.h prior exponents");
+
+int ptnn_evidence(ptnn_handle* h, const ptnn_evidence_spec* spec) {
+    // argument checks first: none of them needs the handle or a device
+    if (!spec) return fail(-1, "null argument");
+    if (spec->struct_bytes != (int32_t)sizeof(ptnn_evidence_spec))
+        return fail(-1, "ptnn_evidence_spec.struct_bytes = %d, expected %d", spec->struct_bytes, (int)sizeof(ptnn_evidence_spec));
+    const ptnn_evidence_spec& s = *spec;
+    const bool u_src = s.u != nullptr, host_src = s.w != nullptr;
+    if (u_src && host_src) return fail(-1, "give host vectors w or a host U, not both");
+    if (u_src || host_src) {
+        if (s.n_rungs < 1) return fail(-1, "n_rungs = %d must be >= 1", s.n_rungs);
+        if (s.n_per_rung < 1) return fail(-1, "n_per_rung = %lld must be >= 1", (long long)s.n_per_rung);
+    } else {
+        if (s.nsteps < 1) return fail(-1, "no source: nsteps = %d trace rows, and neither host vectors w nor a host U", s.nsteps);
+        if (s.thin < 1) return fail(-1, "thin = %d must be >= 1", s.thin);
+        if (s.replicas && s.n_replicas < 1) return fail(-1, "n_replicas = %d with a replica list", s.n_replicas);
+    }
+    if (s.n_prior < 0) return fail(-1, "n_prior = %lld must be >= 0", (long long)s.n_prior);
+    if (s.n_prior > 0x7fffffffLL) return fail(-1, "n_prior = %lld: at most 2^31 - 1 prior draws per call", (long long)s.n_prior);
+    if (s.n_prior > 0 && (s.n_a < 1 || s.n_a > EVID_MAX_A || !s.a))
+        return fail(-1, "n_prior = %lld prior draws need 1 to %d exponents a (n_a = %d)", (long long)s.n_prior, EVID_MAX_A, s.n_a);
+    if (s.n_prior > 0)
+        for (int j = 0; j < s.n_a; ++j)
+            if (!std::isfinite(s.a[j])) return fail(-1, "a[%d] = %g is not finite", j, s.a[j]);
+    if (s.n_prior == 0 && s.u_prior_out) return fail(-1, "u_prior_out requested with n_prior = 0");
+    if (u_src && s.u_out) return fail(-1, "u_out: U is the input of this source");
+    if (u_src && s.n_distinct) *s.n_distinct = 0;
+    // host sources: items, their multiplicities, the draws of every rung
+    long long n_items = 0;
+    std::vector<long long> off;                        // [K + 1] expanded draws of rung k at [off[k], off[k + 1])
+    std::vector<int32_t> item_of;                      // expanded draw -> item (multiplicities only)
+    if (u_src || host_src) {
+        const long long K = s.n_rungs, n = s.n_per_rung;
+        if (K * n > 0x7fffffffLL) return fail(-1, "%lld host rows: at most 2^31 - 1 per call", K * n);
+        n_items = K * n;
+        off.assign((size_t)K + 1, 0);
+        for (long long k = 0; k < K; ++k) {
+            long long c = 0;
+            for (long long i = 0; i < n; ++i) {
+                const long long it = k * n + i;
+                const int mu = s.multiplicity ? s.multiplicity[it] : 1;
+                if (mu < 0) return fail(-1, "multiplicity[%lld, %lld] = %d is negative", k, i, mu);
+                c += mu;
+                if (s.multiplicity) for (int r = 0; r < mu; ++r) item_of.push_back((int32_t)it);
+                if (u_src && mu > 0 && !std::isfinite(s.u[it])) return fail(-1, "u[%lld, %lld] = %g is not finite", k, i, s.u[it]);
+            }
+            off[(size_t)k + 1] = off[(size_t)k] + c;
+            if (off[(size_t)k + 1] > 0x7fffffffLL) return fail(-1, "more than 2^31 - 1 expanded draws");
+        }
+    }
+    if (int rc = check_ready(h)) return rc;
+    if (h->comm.kind != COMM_NONE) return fail(-3, "ptnn_evidence serves one GPU: this handle has a communicator attached");
+    const int I = h->cfg.n_in, H = h->cfg.n_hidden, O = h->cfg.n_out, P = h->P, N = h->Ntr;
+    const bool reg = h->cfg.task == PTNN_TASK_REG;
+    // the trace selection: one rung per chain
+    std::vector<int32_t> reps;
+    int m = 0;
+    if (!u_src && !host_src) {
+        if (int rc = select_trace_rows(h, s.replicas, s.n_replicas, s.step0, s.nsteps, s.thin, &reps, &m)) return rc;
+        n_items = (long long)reps.size() * m;
+        if (n_items > 0x7fffffffLL) return fail(-1, "%lld trace rows: at most 2^31 - 1 per call", n_items);
+        off.assign(reps.size() + 1, 0);
+        for (size_t k = 0; k < reps.size(); ++k) off[k + 1] = off[k] + m;
+    }
+    const int K = (int)off.size() - 1;
+    for (int k = 0; k < K; ++k)
+        if (off[(size_t)k + 1] - off[(size_t)k] < 4)
+            return fail(-1, "rung %d holds %lld draws: the split ESS needs at least 4 per rung", k, off[(size_t)k + 1] - off[(size_t)k]);
+    if (s.d)
+        for (int k = 0; k < K; ++k)
+            if (!std::isfinite(s.d[k])) return fail(-1, "d[%d] = %g is not finite", k, s.d[k]);
+    const long long n_draws = off[(size_t)K];
+    if (s.n_draws)
+        for (int k = 0; k < K; ++k) s.n_draws[k] = off[(size_t)k + 1] - off[(size_t)k];
+
+    HIP_TRY(hipSetDevice(h->cfg.device_id));
+    if (int rc = finish_stream(h)) return rc;          // behind everything queued; a failed run is refused here
+    hipStream_t st = h->stream;
+    DeviceScratch mem;
+    const size_t budget = scratch_budget("PTNN_EVIDENCE_SCRATCH_BYTES");
+    // the forward pass of predict_fwd on the training rows
+    const int PV = round_up4(P);
+    const int per_vec = PV + (PRED_THREADS / WAVE + 1) * O * WAVE;     // as ptnn_predict: staged vector + partial sums + tile
+    const int NV = std::max(1, std::min(PRED_MAX_NV, (48 * 1024 / 4) / per_vec));
+    const size_t lds = (size_t)NV * per_vec * sizeof(float);
+    if (lds > 152 * 1024) return fail(-3, "log evidence: a %d-parameter vector does not fit in LDS", P);
+    if (int rc = raise_lds_limit(reinterpret_cast<const void*>(h->shape->predict_fwd), lds)) return rc;
+    const float* d_x = h->d_data;                      // training rows
+    const int xs = h->IPY;
+    int* d_err = nullptr;                              // [0] SSE = 0, [1] unresolved compact rows, [2], [3] (elpd_runs_kernel)
+    HIP_TRY(mem.alloc(&d_err, 4));
+    HIP_TRY(hipMemsetAsync(d_err, 0, 4 * sizeof(int), st));
+    // U (and b) of `nv` vectors at base + run_off[u]: rows in blocks of rows_blk, fx scratch `fx` of rows_blk x O x nv floats
+    auto eval_u = [&](const float* base, const long long* run_off, int nv, long long rows_blk, float* fx, double* acc, double* u_out,
+                      double* b_out) -> int {
+        HIP_TRY(hipMemsetAsync(acc, 0, (size_t)nv * sizeof(double), st));
+        const unsigned ub = (unsigned)((nv + EVID_THREADS - 1) / EVID_THREADS);
+        for (long long r0 = 0; r0 < N; r0 += rows_blk) {
+            const int nr = (int)std::min<long long>(rows_blk, N - r0);
+            PredictFwd fa{base, run_off, d_x, xs, (int)r0, nr, H, P, PV, nv, NV, fx};
+            hipLaunchKernelGGL(h->shape->predict_fwd, dim3((unsigned)((nv + NV - 1) / NV), (unsigned)((nr + WAVE - 1) / WAVE)), dim3(PRED_THREADS), lds, st, fa);
+            HIP_TRY(hipGetLastError());
+            EvidRows ra{fx, d_x + (size_t)r0 * xs + I, xs, nr, O, nv, reg ? 1 : 0, acc};
+            hipLaunchKernelGGL(evid_rows_kernel, dim3(ub), dim3(EVID_THREADS), 0, st, ra);
+            HIP_TRY(hipGetLastError());
+        }
+        hipLaunchKernelGGL(evid_finish_kernel, dim3(ub), dim3(EVID_THREADS), 0, st, nv, reg ? 1 : 0, N, (const double*)acc, u_out, b_out, d_err);
+        HIP_TRY(hipGetLastError());
+        return 0;
+    };
+    const long long row_cap = 65535LL * WAVE;          // grid.y of the forward pass, as ptnn_predict
+    auto rows_for = [&](long long nv, size_t avail) -> long long {
+        const long long r = (long long)(avail / ((size_t)nv * O * sizeof(float)));
+        return std::max(1LL, std::min<long long>({r, (long long)N, row_cap}));
+    };
+    auto sse_check = [&]() -> int {
+        int e[4] = {0, 0, 0, 0};
+        HIP_TRY(hipMemcpyAsync(e, d_err, sizeof e, hipMemcpyDeviceToHost, st));
+        if (int rc = wait_stream(h)) return rc;
+        if (e[0]) return fail(-1, "%d weight vectors fit the %d training rows exactly (SSE = 0): U = -(N / 2) log SSE is infinite", e[0], N);
+        if (e[1]) return fail(-2, "%d selected compact trace rows refer to rows that are not resident (internal error)", e[1]);
+        return 0;
+    };
+
+    // ---- the rungs: U of every draw
+    double* d_udraw = nullptr;
+    if (K > 0) HIP_TRY(mem.alloc(&d_udraw, (size_t)n_draws));
+    int* d_item_of = nullptr;
+    if (!item_of.empty()) {
+        HIP_TRY(mem.alloc(&d_item_of, item_of.size()));
+        HIP_TRY(hipMemcpyAsync(d_item_of, item_of.data(), item_of.size() * sizeof(int32_t), hipMemcpyHostToDevice, st));
+    }
+    const unsigned draw_blocks = (unsigned)((n_draws + EVID_THREADS - 1) / EVID_THREADS);
+    if (u_src) {
+        double* d_u = nullptr;
+        HIP_TRY(mem.alloc(&d_u, (size_t)n_items));
+        HIP_TRY(hipMemcpyAsync(d_u, s.u, (size_t)n_items * sizeof(double), hipMemcpyHostToDevice, st));
+        hipLaunchKernelGGL(evid_expand_kernel, dim3(draw_blocks), dim3(EVID_THREADS), 0, st, n_draws, (const int*)d_item_of,
+                           (const int*)nullptr, (const double*)d_u, d_udraw);
+        HIP_TRY(hipGetLastError());
+    } else {
+        // stage a: items -> distinct vectors
+        long long *d_item_off = nullptr, *d_run_off = nullptr;
+        int *d_flag = nullptr, *d_item_run = nullptr, *d_run_cnt = nullptr, *d_nruns = nullptr, *d_reps = nullptr;
+        float *d_w = nullptr, *d_item_eta = nullptr;
+        HIP_TRY(mem.alloc(&d_item_off, (size_t)n_items));
+        HIP_TRY(mem.alloc(&d_run_off, (size_t)n_items));
+        HIP_TRY(mem.alloc(&d_flag, (size_t)n_items));
+        HIP_TRY(mem.alloc(&d_item_run, (size_t)n_items));
+        HIP_TRY(mem.alloc(&d_run_cnt, (size_t)n_items));
+        HIP_TRY(mem.alloc(&d_item_eta, (size_t)n_items));
+        HIP_TRY(mem.alloc(&d_nruns, 1));
+        HIP_TRY(hipMemsetAsync(d_run_cnt, 0, (size_t)n_items * sizeof(int), st));
+        HIP_TRY(hipMemsetAsync(d_nruns, 0, sizeof(int), st));
+        ElpdSel sel{};
+        sel.reg = 0; sel.P = P; sel.n_items = n_items; sel.item_off = d_item_off; sel.item_eta = d_item_eta; sel.flag = d_flag;
+        sel.error = d_err + 1;
+        const float* base = nullptr;
+        if (host_src) {
+            HIP_TRY(mem.alloc(&d_w, (size_t)n_items * P));
+            HIP_TRY(hipMemcpyAsync(d_w, s.w, (size_t)n_items * P * sizeof(float), hipMemcpyHostToDevice, st));
+            sel.host = 1; sel.pos_w = d_w;
+            base = d_w;
+        } else {
+            HIP_TRY(mem.alloc(&d_reps, reps.size()));
+            HIP_TRY(hipMemcpyAsync(d_reps, reps.data(), reps.size() * sizeof(int32_t), hipMemcpyHostToDevice, st));
+            sel.host = 0; sel.pos_w = h->d_pos_w; sel.scal = h->d_scal; sel.replicas = d_reps; sel.st_i = h->d_st_i; sel.cap = h->cap;
+            sel.PW = h->PW; sel.step0 = s.step0; sel.thin = s.thin; sel.m = m; sel.compact = h->plan.compact ? 1 : 0; sel.cur = h->cur;
+            base = h->d_pos_w;
+        }
+        const unsigned item_blocks = (unsigned)((n_items + ELPD_THREADS - 1) / ELPD_THREADS);
+        hipLaunchKernelGGL(elpd_runs_kernel, dim3(item_blocks), dim3(ELPD_THREADS), 0, st, sel);
+        HIP_TRY(hipGetLastError());
+        PredictScan sc{n_items, d_flag, d_item_off, nullptr, d_item_run, d_run_off, d_run_cnt, d_nruns};
+        hipLaunchKernelGGL(predict_scan_kernel, dim3(1), dim3(PRED_SCAN_THREADS), 0, st, sc);
+        HIP_TRY(hipGetLastError());
+        int U = 0;
+        HIP_TRY(hipMemcpyAsync(&U, d_nruns, sizeof(int), hipMemcpyDeviceToHost, st));
+        if (int rc = wait_stream(h)) return rc;
+        if (U < 1 || U > n_items) return fail(-2, "run-length pass found %d distinct vectors among %lld rows (internal error)", U, n_items);
+        if (s.n_distinct) *s.n_distinct = U;
+        // stages b, c: U of every distinct vector, rows in blocks under the budget
+        const long long rows_blk = rows_for(U, budget);
+        float* d_fx = nullptr;
+        double *d_acc = nullptr, *d_udist = nullptr;
+        HIP_TRY(mem.alloc(&d_fx, (size_t)rows_blk * O * U));
+        HIP_TRY(mem.alloc(&d_acc, (size_t)U));
+        HIP_TRY(mem.alloc(&d_udist, (size_t)U));
+        if (int rc = eval_u(base, d_run_off, U, rows_blk, d_fx, d_acc, d_udist, nullptr)) return rc;
+        hipLaunchKernelGGL(evid_expand_kernel, dim3(draw_blocks), dim3(EVID_THREADS), 0, st, n_draws, (const int*)d_item_of,
+                           (const int*)d_item_run, (const double*)d_udist, d_udraw);
+        HIP_TRY(hipGetLastError());
+        if (int rc = sse_check()) return rc;
+    }
+    // stage d: per-rung moments and stones
+    long long* d_off = nullptr;
+    double *d_mean = nullptr, *d_var = nullptr, *d_d = nullptr, *d_ls = nullptr, *d_rv = nullptr;
+    HIP_TRY(mem.alloc(&d_off, off.size()));
+    HIP_TRY(hipMemcpyAsync(d_off, off.data(), off.size() * sizeof(long long), hipMemcpyHostToDevice, st));
+    HIP_TRY(mem.alloc(&d_mean, (size_t)K));
+    HIP_TRY(mem.alloc(&d_var, (size_t)K));
+    if (s.d) {
+        HIP_TRY(mem.alloc(&d_d, (size_t)K));
+        HIP_TRY(hipMemcpyAsync(d_d, s.d, (size_t)K * sizeof(double), hipMemcpyHostToDevice, st));
+        HIP_TRY(mem.alloc(&d_ls, (size_t)K));
+        HIP_TRY(mem.alloc(&d_rv, (size_t)K));
+    }
+    EvidRung rg{d_udraw, d_off, d_d, d_mean, d_var, d_ls, d_rv};
+    hipLaunchKernelGGL(evid_rung_kernel, dim3((unsigned)K), dim3(EVID_THREADS), 0, st, rg);
+    HIP_TRY(hipGetLastError());
+    if (s.u_mean) HIP_TRY(hipMemcpyAsync(s.u_mean, d_mean, (size_t)K * sizeof(double), hipMemcpyDeviceToHost, st));
+    if (s.u_var) HIP_TRY(hipMemcpyAsync(s.u_var, d_var, (size_t)K * sizeof(double), hipMemcpyDeviceToHost, st));
+    if (s.d && s.log_stone) HIP_TRY(hipMemcpyAsync(s.log_stone, d_ls, (size_t)K * sizeof(double), hipMemcpyDeviceToHost, st));
+    if (s.d && s.stone_relvar) HIP_TRY(hipMemcpyAsync(s.stone_relvar, d_rv, (size_t)K * sizeof(double), hipMemcpyDeviceToHost, st));
+    if (s.u_out) HIP_TRY(hipMemcpyAsync(s.u_out, d_udraw, (size_t)n_draws * sizeof(double), hipMemcpyDeviceToHost, st));
+    if (int rc = wait_stream(h)) return rc;
+    // the split ESS of every rung's U draws (one chain each), by the convergence kernels: rungs of equal length in one pass
+    if (s.u_ess) {
+        std::vector<char> done((size_t)K, 0);
+        for (int k0 = 0; k0 < K; ++k0) {
+            if (done[(size_t)k0]) continue;
+            const long long nk = off[(size_t)k0 + 1] - off[(size_t)k0];
+            std::vector<int> rung, qcol;
+            for (int k = k0; k < K; ++k)
+                if (!done[(size_t)k] && off[(size_t)k + 1] - off[(size_t)k] == nk) { rung.push_back(k); done[(size_t)k] = 1; }
+            const int Q = (int)rung.size();
+            for (int q = 0; q < Q; ++q) qcol.push_back(q);
+            DeviceScratch cm;
+            int* d_rung = nullptr;
+            float* d_draws = nullptr;
+            HIP_TRY(cm.alloc(&d_rung, (size_t)Q));
+            HIP_TRY(hipMemcpyAsync(d_rung, rung.data(), (size_t)Q * sizeof(int), hipMemcpyHostToDevice, st));
+            HIP_TRY(cm.alloc(&d_draws, (size_t)Q * nk));
+            hipLaunchKernelGGL(evid_conv_kernel, dim3((unsigned)(((long long)Q * nk + EVID_THREADS - 1) / EVID_THREADS)), dim3(EVID_THREADS), 0, st,
+                               Q, (int)nk, (const long long*)d_off, (const int*)d_rung, (const double*)d_udraw, d_draws);
+            HIP_TRY(hipGetLastError());
+            ConvGather ga{};
+            ga.host = 1; ga.draws = d_draws; ga.Qh = Q;
+            std::vector<double> ess((size_t)Q);
+            if (int rc = conv_drive(h, cm, ga, qcol, 1, (int)nk, 0, nullptr, nullptr, nullptr, ess.data(), nullptr, nullptr, nullptr)) return rc;
+            for (int q = 0; q < Q; ++q) s.u_ess[rung[(size_t)q]] = ess[(size_t)q];
+        }
+    }
+    if (s.n_prior == 0) return 0;
+
+    // ---- stage e: prior draws in blocks of nb vectors (vector + forward scratch of every training row under the budget)
+    const long long NP = s.n_prior;
+    const size_t per_draw = (size_t)P * sizeof(float) + 4 * sizeof(double) + (size_t)std::min<long long>(N, row_cap) * O * sizeof(float);
+    const long long nb = std::max(1LL, std::min<long long>((long long)(budget / per_draw), NP));
+    const size_t fixed = (size_t)nb * ((size_t)P * sizeof(float) + 4 * sizeof(double));
+    const long long rows_blk = rows_for(nb, budget > fixed ? budget - fixed : 0);
+    double *d_pu = nullptr, *d_pb = nullptr, *d_acc = nullptr, *d_a = nullptr;
+    float *d_pw = nullptr, *d_fx = nullptr;
+    long long* d_poff = nullptr;
+    HIP_TRY(mem.alloc(&d_pu, (size_t)NP));
+    HIP_TRY(mem.alloc(&d_pb, (size_t)NP));
+    HIP_TRY(mem.alloc(&d_pw, (size_t)nb * P));
+    HIP_TRY(mem.alloc(&d_poff, (size_t)nb));
+    HIP_TRY(mem.alloc(&d_acc, (size_t)nb));
+    HIP_TRY(mem.alloc(&d_fx, (size_t)rows_blk * O * nb));
+    const float sigma = (float)std::sqrt((double)h->cfg.sigma_squared);
+    const uint32_t slo = (uint32_t)(s.seed & 0xffffffffu), shi = (uint32_t)(s.seed >> 32);
+    const int nq = (P + 3) / 4;
+    for (long long d0 = 0; d0 < NP; d0 += nb) {
+        const int b = (int)std::min<long long>(nb, NP - d0);
+        hipLaunchKernelGGL(evid_prior_kernel, dim3((unsigned)(((long long)b * nq + EVID_THREADS - 1) / EVID_THREADS)), dim3(EVID_THREADS), 0, st,
+                           d0, b, P, sigma, slo, shi, d_pw, d_poff);
+        HIP_TRY(hipGetLastError());
+        if (int rc = eval_u(d_pw, d_poff, b, rows_blk, d_fx, d_acc, d_pu + d0, d_pb + d0)) return rc;
+    }
+    HIP_TRY(mem.alloc(&d_a, (size_t)s.n_a));
+    HIP_TRY(hipMemcpyAsync(d_a, s.a, (size_t)s.n_a * sizeof(double), hipMemcpyHostToDevice, st));
+    double* d_pr = nullptr;
+    HIP_TRY(mem.alloc(&d_pr, (size_t)4 * s.n_a));
+    EvidPriorRed pr{d_pu, d_pb, NP, d_a, d_pr, d_pr + s.n_a, d_pr + 2 * s.n_a, d_pr + 3 * s.n_a};
+    hipLaunchKernelGGL(evid_prior_reduce_kernel, dim3((unsigned)s.n_a), dim3(EVID_THREADS), 0, st, pr);
+    HIP_TRY(hipGetLastError());
+    std::vector<double> prh((size_t)4 * s.n_a);
+    HIP_TRY(hipMemcpyAsync(prh.data(), d_pr, prh.size() * sizeof(double), hipMemcpyDeviceToHost, st));
+    if (s.u_prior_out) HIP_TRY(hipMemcpyAsync(s.u_prior_out, d_pu, (size_t)NP * sizeof(double), hipMemcpyDeviceToHost, st));
+    if (int rc = sse_check()) return rc;
+    double* outs[4] = {s.prior_log_mean_exp, s.prior_kish_ess, s.prior_u_mean, s.prior_u_var};
+    for (int o = 0; o < 4; ++o)
+        if (outs[o]) std::copy(prh.begin() + (size_t)o * s.n_a, prh.begin() + (size_t)(o + 1) * s.n_a, outs[o]);
+    return 0;
 }
 
 static int run_model(ptnn_handle* h, int mode, const float* w_in, const float* tau_sq, int n, float* out, size_t out_floats,

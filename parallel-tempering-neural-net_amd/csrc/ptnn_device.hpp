@@ -150,6 +150,7 @@ struct SegDyn {
 #ifndef PTNN_SHAPE_TU
 #include "ptnn_dev_convergence.hpp"          // convergence diagnostics: split-R-hat, split-ESS over trace columns (main translation unit only)
 #include "ptnn_dev_elpd.hpp"                 // predictive accuracy: lppd, WAIC, PSIS-LOO per data row (main translation unit only)
+#include "ptnn_dev_evidence.hpp"             // log evidence: per-rung statistics of the full-data log-likelihood, prior draws (main translation unit only)
 #endif
 
 }  // namespace ptnn

@@ -110,6 +110,81 @@ PredictiveAccuracy = namedtuple("PredictiveAccuracy", "elpd_loo se_elpd_loo p_lo
 # n_origins, horizon] float32 or None; n_samples; n_trajectories (per origin)
 Forecast = namedtuple("Forecast", "mean percentiles samples n_samples n_trajectories")
 
+# log_evidence's result: the stepping-stone and thermodynamic-integration estimates of log Z with their standard errors
+# (float); ti_discretisation (float); betas [K+1] ascending, 0 first (the prior); u_mean, u_mcse, ess [K+1] (entry 0: the prior's
+# self-normalised mean of U, its MCSE and Kish ESS); log_stones [K] (stone k takes beta_k to beta_{k+1}, stone 0 from the prior);
+# prior_kish_ess (of the first stone's weights); n_draws [K+1] (entry 0: prior draws); n_distinct; u_draws [K] arrays of every
+# rung's U draws and u_prior_draws [n_prior] (return_draws) or None
+Evidence = namedtuple("Evidence", "log_z_ss se_log_z_ss log_z_ti se_log_z_ti ti_discretisation betas u_mean u_mcse ess log_stones "
+                      "prior_kish_ess n_draws n_distinct u_draws u_prior_draws")
+
+
+def evidence_log_c(task, n_rows):
+    """The constant of the evidence: 0 for a classification; for a regression, whose eta = log tau^2 is
+    integrated out of the improper 1 / tau^2 prior, log 2 + lgamma(N / 2 + 1) - (N / 2) log pi over N training rows."""
+    if task == TASK_CLS:
+        return 0.0
+    n = float(n_rows)
+    return math.log(2.0) + math.lgamma(n / 2.0 + 1.0) - (n / 2.0) * math.log(math.pi)
+
+
+def _trapezoid(b, u):
+    """Trapezoid weights over the points b (ascending) and the integral sum w_k u_k."""
+    w = np.zeros(b.size)
+    d = np.diff(b)
+    w[:-1] += d / 2.0
+    w[1:] += d / 2.0
+    return w, float(np.dot(w, u))
+
+
+def evidence_from_rungs(betas, u_mean, u_var, ess, log_stones, stone_relvar, *, prior_log_mean_exp_b, prior_u_mean, prior_u_var,
+                        prior_kish_ess_b, prior_log_mean_exp_first, prior_kish_ess_first, n_prior, log_c=0.0):
+    """log Z from per-rung statistics; host arithmetic only.
+
+    betas [K] ascending with betas[-1] == 1; per rung: u_mean, u_var (ddof 1), ess of its U draws; log_stones[k] = log mean
+    exp((betas[k+1] - betas[k]) U) over rung k's draws and stone_relvar[k] the relative variance of those exp-terms (entry K-1
+    unused).  The prior (beta = 0) from n_prior independent draws: prior_log_mean_exp_b = log E[e^b], prior_u_mean / prior_u_var
+    the mean and variance of U weighted by e^b with Kish ESS prior_kish_ess_b; prior_log_mean_exp_first = log E[e^{b + betas[0]
+    U}] with Kish ESS prior_kish_ess_first.  Returns dict(log_z_ti, se_log_z_ti, ti_discretisation, log_z_ss, se_log_z_ss,
+    betas, u_mean, u_mcse, ess) with the prior prepended to the last four."""
+    b = np.asarray(betas, np.float64).reshape(-1)
+    K = b.size
+    if K < 1 or b[-1] != 1.0 or b[0] <= 0.0 or np.any(np.diff(b) <= 0.0):
+        raise ValueError(f"betas must rise strictly from above 0 to exactly 1, got {b}")
+    um, uv, es = (np.asarray(v, np.float64).reshape(-1) for v in (u_mean, u_var, ess))
+    ls, rv = np.asarray(log_stones, np.float64).reshape(-1), np.asarray(stone_relvar, np.float64).reshape(-1)
+    n = float(n_prior)
+    # the prior's point: a self-normalised mean of U, and log E[e^b] (independent draws: Kish ESS; var of a log-mean = 1/kish - 1/n)
+    bb = np.concatenate([[0.0], b])
+    uu = np.concatenate([[float(prior_u_mean)], um])
+    # a rung whose draws are all equal has variance 0 and no ESS (NaN): its term is known exactly; a rung whose split halves are
+    # each constant has no finite ESS either: it counts as one draw
+    ed = np.where(np.isfinite(es) & (es > 0.0), es, 1.0)
+    var_mean = np.concatenate([[float(prior_u_var) / float(prior_kish_ess_b)], np.where(uv > 0.0, uv / ed, 0.0)])
+    var_stones = np.where(rv[:K - 1] > 0.0, rv[:K - 1] / ed[:K - 1], 0.0)
+    w, integral = _trapezoid(bb, uu)
+    var_lme_b = max(1.0 / float(prior_kish_ess_b) - 1.0 / n, 0.0)
+    log_z_ti = float(log_c) + float(prior_log_mean_exp_b) + integral
+    se_ti = math.sqrt(var_lme_b + float(np.dot(w * w, var_mean)))
+    keep = np.zeros(K + 1, bool)                         # every other point, both ends kept
+    keep[::2] = True
+    keep[-1] = True
+    _, integral_half = _trapezoid(bb[keep], uu[keep])
+    disc = abs(integral - integral_half)
+    # stepping stones: the first from the prior, stone k (k < K - 1) from rung k's draws
+    var_first = max(1.0 / float(prior_kish_ess_first) - 1.0 / n, 0.0)
+    log_z_ss = float(log_c) + float(prior_log_mean_exp_first) + float(np.sum(ls[:K - 1]))
+    se_ss = math.sqrt(var_first + float(np.sum(var_stones)))
+    return dict(log_z_ti=log_z_ti, se_log_z_ti=se_ti, ti_discretisation=disc, log_z_ss=log_z_ss, se_log_z_ss=se_ss, betas=bb,
+                u_mean=uu, u_mcse=np.sqrt(var_mean), ess=np.concatenate([[float(prior_kish_ess_b)], es]))
+
+
+def evidence_compare(a, b):
+    """The log Bayes factor of two Evidence results, log Z_a - log Z_b, with SE sqrt(se_a^2 + se_b^2) (independent runs; for a
+    regression both must be fitted to the same training rows).  -> dict(log_bf_ss, se_log_bf_ss, log_bf_ti, se_log_bf_ti)."""
+    return dict(log_bf_ss=float(a.log_z_ss - b.log_z_ss), se_log_bf_ss=math.hypot(a.se_log_z_ss, b.se_log_z_ss),
+                log_bf_ti=float(a.log_z_ti - b.log_z_ti), se_log_bf_ti=math.hypot(a.se_log_z_ti, b.se_log_z_ti))
+
 
 def _se_total(x):
     """Standard error of a sum of pointwise values: sqrt(N var(x, ddof 1)) (Vehtari, Gelman & Gabry 2017, eq. 23)."""
@@ -871,6 +946,106 @@ class ParallelTemperingBase:
         bands = {p: lerp_percentile(os_[pos[lo]], os_[pos[hi]], g) for p, (lo, hi, g) in zip(pcts, spots)}
         return Forecast(mean=out["mean"], percentiles=bands, samples=out["samples"], n_samples=out["n_samples"],
                         n_trajectories=out["n_trajectories"])
+
+    # ------------------------------------------------------------------ log evidence (not in the reference)
+    def log_evidence(self, *, burn_in=None, thin=1, prior_draws=1 << 20, seed=None, weights=None, return_draws=False):
+        """The marginal likelihood log Z of the model, for Bayes factors between topologies (evidence_compare), computed on the GPU
+        from every rung of the ladder.  Rung k samples the power posterior pi(w) L(w)^beta_k, beta_k =
+        1 / float32(T_k); with U(w) the untempered full-data log-likelihood (a regression's tau^2 integrated out), log Z is
+        estimated by thermodynamic integration over the rungs (trapezoid rule, the prior as beta = 0; ti_discretisation the
+        ptemcee estimate |TI - TI over every other rung|) and by stepping stones (Xie et al. 2011).  A regression's evidence is
+        relative to the improper 1 / tau^2 prior: it cancels in Bayes factors between models fitted to the same training rows.
+
+        The draws of rung k are its trace rows from int(NumSamples * burn_in) up to the temperature switch (the reference's
+        pt_samples = 0.6 NumSamples, after which every chain runs at T = 1) or to NumSamples; `thin`: every thin-th row.  The
+        prior's point and first stone come from `prior_draws` draws of N(0, sigma^2 I) (Philox stream STREAM_PRIOR of `seed`,
+        None = the object's seed).  `weights`: (betas [K], vectors [K, n, num_param]) instead of the trace.  Standard errors
+        take each rung's split-ESS of U; they assume independent rungs.  return_draws: also every draw's U.  -> Evidence.
+
+        The estimate is exact only when the tempered chains sample the power posterior: random-walk proposals, swap_rule=1,
+        shared_noise=False and a large integer maxtemp (so that the hottest rung is close to the prior); a warning names the
+        settings that break this."""
+        if self._sampler is None:
+            raise ValueError("log_evidence needs the chains' device handle: call initialize_chains() and run_chains() first")
+        if not isinstance(self._sampler, _lib.Sampler):
+            raise ValueError("log_evidence runs on one GPU: a ladder sharded over several devices is not supported")
+        S = self.NumSamples
+        n_prior = int(prior_draws)
+        if n_prior < 2:
+            raise ValueError(f"prior_draws = {n_prior}: the prior's point needs at least 2 draws")
+        if weights is not None:
+            if not isinstance(weights, tuple) or len(weights) != 2:
+                raise ValueError("weights must be a pair (betas [K], vectors [K, n, num_param])")
+            bw, w = weights
+            betas = np.asarray(bw, np.float64).reshape(-1)
+            w = np.asarray(w)
+            if w.ndim != 3 or w.shape[0] != betas.size or w.shape[2] != self.num_param:
+                raise ValueError(f"weights: vectors must be [K = {betas.size}, n, {self.num_param}], got shape {w.shape}")
+            if w.shape[1] < 4:
+                raise ValueError(f"weights: {w.shape[1]} draws per rung: the split ESS needs at least 4")
+            order = np.argsort(betas, kind="stable")
+            kw = dict(w=w[order])
+        else:
+            if self.label_swap:
+                raise ValueError("label_swap=True: trace rows are kept per chain slot, not per temperature; pass weights=")
+            if 0 < self.trace_capacity < S:
+                raise ValueError(f"trace_capacity = {self.trace_capacity} < NumSamples = {S}: the rows have been streamed off "
+                                 f"the device; pass weights=")
+            if not self._finished:
+                raise ValueError("no finished run_chains() on this object: the trace is incomplete; pass weights=")
+            betas = np.array([1.0 / float(np.float32(T)) for T in self.temperatures])
+            order = np.argsort(betas, kind="stable")
+            b = self.burn_in if burn_in is None else burn_in
+            step0 = int(S * b)
+            sw = self._pt_switch_step()
+            end = sw if sw >= 0 else S
+            per = max(0, -(-(end - step0) // max(1, int(thin))))
+            if per < 4:
+                raise ValueError(f"the window [{step0}, {end}) of every rung (burn_in = {b}, up to the temperature switch) holds "
+                                 f"{per} draws at thin = {int(thin)}: at least 4 are needed (a smaller burn_in or more samples)")
+            kw = dict(replicas=[int(r) for r in order], step0=step0, nsteps=end - step0, thin=int(thin))
+        bs = betas[order]
+        if np.any(np.diff(bs) == 0.0):
+            raise ValueError(f"duplicate temperatures in the ladder: {sorted(set(bs[np.flatnonzero(np.diff(bs) == 0.0)].tolist()))} "
+                             f"(as betas): the rungs must be distinct")
+        if bs[-1] != 1.0:
+            raise ValueError(f"the coldest rung has beta = {bs[-1]!r}: log Z needs a rung at temperature 1")
+        causes = []
+        if self.use_langevin_gradients is True and self.langevin_prob > 0:
+            causes.append("Langevin proposals at T != 1 (the Hastings term is divided by T)")
+        if self.swap_rule == 0:
+            causes.append("swap_rule=0 (the reference's cascade uses stale likelihoods)")
+        if self.shared_noise:
+            causes.append("shared_noise=True (the rungs are correlated, so the standard errors are not valid)")
+        if causes:
+            warnings.warn("log_evidence: the tempered chains do not sample the power posterior exactly: " + "; ".join(causes)
+                          + ". An exact estimate needs random-walk proposals, swap_rule=1, shared_noise=False and a large "
+                          "integer maxtemp", stacklevel=2)
+        d = np.append(np.diff(bs), 0.0)
+        out = self._sampler.evidence(d=d, n_prior=n_prior, seed=self.seed if seed is None else int(seed), a=[0.0, float(bs[0])],
+                                     u_out=bool(return_draws), u_prior_out=bool(return_draws), **kw)
+        N = int(np.asarray(self.traindata).shape[0])
+        r = evidence_from_rungs(bs, out["u_mean"], out["u_var"], out["u_ess"], out["log_stone"], out["stone_relvar"],
+                                prior_log_mean_exp_b=out["prior_log_mean_exp"][0], prior_u_mean=out["prior_u_mean"][0],
+                                prior_u_var=out["prior_u_var"][0], prior_kish_ess_b=out["prior_kish_ess"][0],
+                                prior_log_mean_exp_first=out["prior_log_mean_exp"][1], prior_kish_ess_first=out["prior_kish_ess"][1],
+                                n_prior=n_prior, log_c=evidence_log_c(self.task, N))
+        kish = float(out["prior_kish_ess"][1])
+        if kish < 0.01 * n_prior:
+            warnings.warn(f"log_evidence: the first stepping stone's prior draws have a Kish ESS of {kish:.1f} of {n_prior} "
+                          f"(below 1 %): the hottest rung (beta = {bs[0]:.4g}) is far from the prior; raise maxtemp", stacklevel=2)
+        gap = abs(r["log_z_ti"] - r["log_z_ss"])
+        if gap > 3.0 * math.hypot(r["se_log_z_ti"], r["se_log_z_ss"]) + r["ti_discretisation"]:
+            warnings.warn(f"log_evidence: thermodynamic integration ({r['log_z_ti']:.4f}) and stepping stones ({r['log_z_ss']:.4f}) "
+                          f"disagree by more than their errors: more rungs, more samples or a hotter ladder", stacklevel=2)
+        u_draws = None
+        if return_draws:
+            u_draws = np.split(out["u"], np.cumsum(out["n_draws"])[:-1])
+        return Evidence(log_z_ss=r["log_z_ss"], se_log_z_ss=r["se_log_z_ss"], log_z_ti=r["log_z_ti"], se_log_z_ti=r["se_log_z_ti"],
+                        ti_discretisation=r["ti_discretisation"], betas=r["betas"], u_mean=r["u_mean"], u_mcse=r["u_mcse"],
+                        ess=r["ess"], log_stones=np.concatenate([[out["prior_log_mean_exp"][1]], out["log_stone"][:-1]]),
+                        prior_kish_ess=kish, n_draws=np.concatenate([[n_prior], out["n_draws"]]), n_distinct=out["n_distinct"],
+                        u_draws=u_draws, u_prior_draws=out["u_prior"] if return_draws else None)
 
     def make_directory(self, directory):
         if not os.path.exists(directory):
