@@ -1,5 +1,6 @@
 """ctypes binding of libptnn.so (include/ptnn.h).  No fallback: a missing library or device raises PtnnError."""
 import ctypes as C
+import math
 import os
 
 import numpy as np
@@ -524,6 +525,65 @@ class Sampler:
         self._check(self.lib.ptnn_evaluate(self.h, _ptr(w), _ptr(tau), n, _ptr(out)))
         return out
 
+    def _rows(self, spec, keep, x, name, cols, fields=("x_source", "n_rows", "x")):
+        """A rows argument of an analysis call: "train", "test" or an array [n, cols[0]] (cols[1] says what the columns are)
+        -> the spec's source, count and pointer fields (named by `fields`)."""
+        src_f, n_f, ptr_f = fields
+        if isinstance(x, str):
+            src = {"train": PREDICT_X_TRAIN, "test": PREDICT_X_TEST}.get(x)
+            if src is None:
+                raise ValueError(f"{name} must be 'train', 'test' or an array, not {x!r}")
+            setattr(spec, src_f, src)
+            setattr(spec, n_f, self.ntr if src == PREDICT_X_TRAIN else self.nte)
+        else:
+            xa = _f32(x)
+            if xa.ndim != 2 or xa.shape[1] != cols[0]:
+                raise ValueError(f"{name} must be [{n_f}, {cols[0]}] ({cols[1]}), got shape {xa.shape}")
+            keep.append(xa)
+            setattr(spec, src_f, PREDICT_X_HOST)
+            setattr(spec, n_f, xa.shape[0])
+            setattr(spec, ptr_f, _ptr(xa))
+
+    def _trace_source(self, spec, keep, replicas, step0, nsteps, thin):
+        """The trace rows step0, step0 + thin, ... < step0 + nsteps of `replicas` (None = all) -> (chains, rows per chain)."""
+        nrep = self.R
+        if replicas is not None:
+            ra = np.ascontiguousarray(replicas, dtype=np.int32).reshape(-1)
+            keep.append(ra)
+            spec.replicas, spec.n_replicas = _ptr(ra, _ip), ra.size
+            nrep = ra.size
+        spec.step0 = int(step0)
+        spec.nsteps = int(self.S - step0 if nsteps is None else nsteps)
+        spec.thin = int(thin)
+        return nrep, max(0, -(-spec.nsteps // max(1, spec.thin)))
+
+    def _host_vectors(self, spec, keep, w, eta=None):
+        """Host vectors w [n, P] and their eta [n] (optional) -> n."""
+        wa = _f32(w)
+        if wa.ndim != 2 or wa.shape[1] != self.P:
+            raise ValueError(f"w must be [n, {self.P}], got shape {wa.shape}")
+        keep.append(wa)
+        spec.w, spec.n_w = _ptr(wa), wa.shape[0]
+        if eta is not None:
+            ea = _f32(np.reshape(eta, -1))
+            if ea.shape != (wa.shape[0],):
+                raise ValueError("eta must have one entry per vector")
+            keep.append(ea)
+            spec.eta = _ptr(ea)
+        return wa.shape[0]
+
+    @staticmethod
+    def _multiplicity(spec, keep, multiplicity, shape, message):
+        """Integer multiplicities of the host items (None = 1 each) -> the sample count; `message` may name {want} and {got}."""
+        if multiplicity is None:
+            return int(np.prod(shape))
+        mu = np.ascontiguousarray(multiplicity, dtype=np.int32)
+        if mu.shape != tuple(shape):
+            raise ValueError(message.format(want=tuple(shape), got=mu.shape))
+        keep.append(mu)
+        spec.multiplicity = _ptr(mu, _ip)
+        return int(np.maximum(mu, 0).astype(np.int64).sum())
+
     def predict(self, x="test", *, replicas=None, step0=0, nsteps=None, thin=1, w=None, multiplicity=None, ranks=(), mean=True,
                 vote=False, samples=False):
         """ptnn_predict: network outputs of the selected weight vectors on input rows, reduced on the device.  Source: the trace rows
@@ -534,46 +594,13 @@ class Sampler:
         spec = PredictSpec()
         spec.struct_bytes = C.sizeof(PredictSpec)
         keep = []
-        if isinstance(x, str):
-            src = {"train": PREDICT_X_TRAIN, "test": PREDICT_X_TEST}.get(x)
-            if src is None:
-                raise ValueError(f"x must be 'train', 'test' or an array, not {x!r}")
-            spec.x_source = src
-            spec.n_rows = self.ntr if src == PREDICT_X_TRAIN else self.nte
-        else:
-            xa = _f32(x)
-            if xa.ndim != 2 or xa.shape[1] != self.cfg.n_in:
-                raise ValueError(f"x must be [n_rows, {self.cfg.n_in}] (n_in columns), got shape {xa.shape}")
-            keep.append(xa)
-            spec.x_source, spec.n_rows, spec.x = PREDICT_X_HOST, xa.shape[0], _ptr(xa)
+        self._rows(spec, keep, x, "x", (self.cfg.n_in, "n_in columns"))
         n_rows, O = spec.n_rows, self.cfg.n_out
         if w is not None:
-            wa = _f32(w)
-            if wa.ndim != 2 or wa.shape[1] != self.P:
-                raise ValueError(f"w must be [n, {self.P}], got shape {wa.shape}")
-            keep.append(wa)
-            spec.w, spec.n_w = _ptr(wa), wa.shape[0]
-            if multiplicity is not None:
-                mu = np.ascontiguousarray(multiplicity, dtype=np.int32)
-                if mu.shape != (wa.shape[0],):
-                    raise ValueError("multiplicity must have one entry per vector")
-                keep.append(mu)
-                spec.multiplicity = _ptr(mu, _ip)
-                M = int(mu.astype(np.int64).sum())
-            else:
-                M = wa.shape[0]
+            n = self._host_vectors(spec, keep, w)
+            M = self._multiplicity(spec, keep, multiplicity, (n,), "multiplicity must have one entry per vector")
         else:
-            if replicas is not None:
-                ra = np.ascontiguousarray(replicas, dtype=np.int32).reshape(-1)
-                keep.append(ra)
-                spec.replicas, spec.n_replicas = _ptr(ra, _ip), ra.size
-                nrep = ra.size
-            else:
-                nrep = self.R
-            spec.step0 = int(step0)
-            spec.nsteps = int(self.S - step0 if nsteps is None else nsteps)
-            spec.thin = int(thin)
-            M = nrep * max(0, -(-spec.nsteps // max(1, spec.thin)))
+            M = math.prod(self._trace_source(spec, keep, replicas, step0, nsteps, thin))
         rk = np.ascontiguousarray(ranks, dtype=np.int64).reshape(-1)
         keep.append(rk)
         spec.ranks, spec.n_ranks = (_ptr(rk, C.POINTER(C.c_int64)) if rk.size else None), rk.size
@@ -609,17 +636,7 @@ class Sampler:
             nc, nd, Q = da.shape
             spec.n_chains, spec.n_draws, spec.n_quantities = nc, nd, Q
         else:
-            if replicas is not None:
-                ra = np.ascontiguousarray(replicas, dtype=np.int32).reshape(-1)
-                keep.append(ra)
-                spec.replicas, spec.n_replicas = _ptr(ra, _ip), ra.size
-                nc = ra.size
-            else:
-                nc = self.R
-            spec.step0 = int(step0)
-            spec.nsteps = int(self.S - step0 if nsteps is None else nsteps)
-            spec.thin = int(thin)
-            nd = max(0, -(-spec.nsteps // max(1, spec.thin)))
+            nc, nd = self._trace_source(spec, keep, replicas, step0, nsteps, thin)
             if params is not None:
                 pa = np.ascontiguousarray(params, dtype=np.int32).reshape(-1)
                 keep.append(pa)
@@ -665,54 +682,12 @@ class Sampler:
             spec.x_source = PREDICT_X_HOST
             n_host = la.shape[0]
         else:
-            if isinstance(data, str):
-                src = {"train": PREDICT_X_TRAIN, "test": PREDICT_X_TEST}.get(data)
-                if src is None:
-                    raise ValueError(f"data must be 'train', 'test' or an array, not {data!r}")
-                spec.x_source = src
-                spec.n_rows = self.ntr if src == PREDICT_X_TRAIN else self.nte
-            else:
-                xa = _f32(data)
-                if xa.ndim != 2 or xa.shape[1] != self.cfg.n_in + 1:
-                    raise ValueError(f"data must be [n_rows, {self.cfg.n_in + 1}] (n_in inputs and the target), got shape {xa.shape}")
-                keep.append(xa)
-                spec.x_source, spec.n_rows, spec.x = PREDICT_X_HOST, xa.shape[0], _ptr(xa)
-            n_host = None
-            if w is not None:
-                wa = _f32(w)
-                if wa.ndim != 2 or wa.shape[1] != self.P:
-                    raise ValueError(f"w must be [n, {self.P}], got shape {wa.shape}")
-                keep.append(wa)
-                spec.w, spec.n_w = _ptr(wa), wa.shape[0]
-                n_host = wa.shape[0]
-                if eta is not None:
-                    ea = _f32(np.reshape(eta, -1))
-                    if ea.shape != (wa.shape[0],):
-                        raise ValueError("eta must have one entry per vector")
-                    keep.append(ea)
-                    spec.eta = _ptr(ea)
+            self._rows(spec, keep, data, "data", (self.cfg.n_in + 1, "n_in inputs and the target"))
+            n_host = None if w is None else self._host_vectors(spec, keep, w, eta)
         if n_host is not None:
-            if multiplicity is not None:
-                mu = np.ascontiguousarray(multiplicity, dtype=np.int32)
-                if mu.shape != (n_host,):
-                    raise ValueError("multiplicity must have one entry per sample")
-                keep.append(mu)
-                spec.multiplicity = _ptr(mu, _ip)
-                S = int(mu.astype(np.int64).sum())
-            else:
-                S = n_host
+            S = self._multiplicity(spec, keep, multiplicity, (n_host,), "multiplicity must have one entry per sample")
         else:
-            if replicas is not None:
-                ra = np.ascontiguousarray(replicas, dtype=np.int32).reshape(-1)
-                keep.append(ra)
-                spec.replicas, spec.n_replicas = _ptr(ra, _ip), ra.size
-                nrep = ra.size
-            else:
-                nrep = self.R
-            spec.step0 = int(step0)
-            spec.nsteps = int(self.S - step0 if nsteps is None else nsteps)
-            spec.thin = int(thin)
-            S = nrep * max(0, -(-spec.nsteps // max(1, spec.thin)))
+            S = math.prod(self._trace_source(spec, keep, replicas, step0, nsteps, thin))
         spec.r_eff = float(r_eff)
         n_rows = spec.n_rows
         out = dict(lppd=np.empty(n_rows), p_waic=np.empty(n_rows), elpd_loo=np.empty(n_rows), khat=np.empty(n_rows),
@@ -738,53 +713,14 @@ class Sampler:
         spec = ForecastSpec()
         spec.struct_bytes = C.sizeof(ForecastSpec)
         keep = []
-        if isinstance(origins, str):
-            src = {"train": FORECAST_ORIGIN_TRAIN, "test": FORECAST_ORIGIN_TEST}.get(origins)
-            if src is None:
-                raise ValueError(f"origins must be 'train', 'test' or an array, not {origins!r}")
-            spec.origin_source = src
-            spec.n_origins = self.ntr if src == FORECAST_ORIGIN_TRAIN else self.nte
-        else:
-            xa = _f32(origins)
-            if xa.ndim != 2 or xa.shape[1] != self.cfg.n_in:
-                raise ValueError(f"origins must be [n_origins, {self.cfg.n_in}] (n_in columns), got shape {xa.shape}")
-            keep.append(xa)
-            spec.origin_source, spec.n_origins, spec.origins = FORECAST_ORIGIN_HOST, xa.shape[0], _ptr(xa)
+        self._rows(spec, keep, origins, "origins", (self.cfg.n_in, "n_in columns"), ("origin_source", "n_origins", "origins"))
         spec.horizon, spec.noise, spec.seed = int(horizon), 1 if noise else 0, int(seed) & 0xFFFFFFFFFFFFFFFF
         n_org, hz = spec.n_origins, max(int(horizon), 0)
         if w is not None:
-            wa = _f32(w)
-            if wa.ndim != 2 or wa.shape[1] != self.P:
-                raise ValueError(f"w must be [n, {self.P}], got shape {wa.shape}")
-            keep.append(wa)
-            spec.w, spec.n_w = _ptr(wa), wa.shape[0]
-            if eta is not None:
-                ea = _f32(np.reshape(eta, -1))
-                if ea.shape != (wa.shape[0],):
-                    raise ValueError("eta must have one entry per vector")
-                keep.append(ea)
-                spec.eta = _ptr(ea)
-            if multiplicity is not None:
-                mu = np.ascontiguousarray(multiplicity, dtype=np.int32)
-                if mu.shape != (wa.shape[0],):
-                    raise ValueError("multiplicity must have one entry per vector")
-                keep.append(mu)
-                spec.multiplicity = _ptr(mu, _ip)
-                M = int(mu.astype(np.int64).sum())
-            else:
-                M = wa.shape[0]
+            n = self._host_vectors(spec, keep, w, eta)
+            M = self._multiplicity(spec, keep, multiplicity, (n,), "multiplicity must have one entry per vector")
         else:
-            if replicas is not None:
-                ra = np.ascontiguousarray(replicas, dtype=np.int32).reshape(-1)
-                keep.append(ra)
-                spec.replicas, spec.n_replicas = _ptr(ra, _ip), ra.size
-                nrep = ra.size
-            else:
-                nrep = self.R
-            spec.step0 = int(step0)
-            spec.nsteps = int(self.S - step0 if nsteps is None else nsteps)
-            spec.thin = int(thin)
-            M = nrep * max(0, -(-spec.nsteps // max(1, spec.thin)))
+            M = math.prod(self._trace_source(spec, keep, replicas, step0, nsteps, thin))
         rk = np.ascontiguousarray(ranks, dtype=np.int64).reshape(-1)
         keep.append(rk)
         spec.ranks, spec.n_ranks = (_ptr(rk, C.POINTER(C.c_int64)) if rk.size else None), rk.size
@@ -829,29 +765,12 @@ class Sampler:
             host = wa.shape[:2]
         else:
             host = None
-            if replicas is not None:
-                ra = np.ascontiguousarray(replicas, dtype=np.int32).reshape(-1)
-                keep.append(ra)
-                spec.replicas, spec.n_replicas = _ptr(ra, _ip), ra.size
-                K = ra.size
-            else:
-                K = self.R
-            spec.step0 = int(step0)
-            spec.nsteps = int(self.S - step0 if nsteps is None else nsteps)
-            spec.thin = int(thin)
-            per = max(0, -(-spec.nsteps // max(1, spec.thin)))
+            K, per = self._trace_source(spec, keep, replicas, step0, nsteps, thin)
             total = K * per
         if host is not None:
             K = host[0]
-            if multiplicity is not None:
-                mu = np.ascontiguousarray(multiplicity, dtype=np.int32)
-                if mu.shape != tuple(host):
-                    raise ValueError(f"multiplicity must be [n_rungs, n_per_rung] = {tuple(host)}, got shape {mu.shape}")
-                keep.append(mu)
-                spec.multiplicity = _ptr(mu, _ip)
-                total = int(np.maximum(mu, 0).astype(np.int64).sum())
-            else:
-                total = host[0] * host[1]
+            total = self._multiplicity(spec, keep, multiplicity, tuple(host),
+                                       "multiplicity must be [n_rungs, n_per_rung] = {want}, got shape {got}")
         if d is not None:
             da = np.ascontiguousarray(d, dtype=np.float64).reshape(-1)
             if da.size != K:

@@ -1789,11 +1789,11 @@ int ptnn_checkpoint_load(ptnn_handle* h, const void* buf, int64_t bytes) {
     return 0;
 }
 
-// ---- posterior predictive (ptnn_dev_predict.hpp) ----
+// ---- the posterior analysis calls: predict, convergence, elpd, forecast, evidence ----
 }  // extern "C" (the scratch guard below is a class)
 
 namespace {
-struct DeviceScratch {            // every buffer of one ptnn_predict call, released on every return path
+struct DeviceScratch {            // every buffer of one analysis call, released on every return path
     std::vector<void*> ptrs;
     ~DeviceScratch() { for (void* p : ptrs) (void)hipFree(p); }
     template <typename T> hipError_t alloc(T** p, size_t n) {
@@ -1804,7 +1804,15 @@ struct DeviceScratch {            // every buffer of one ptnn_predict call, rele
         if (e == hipSuccess) { ptrs.push_back(q); *p = static_cast<T*>(q); }
         return e;
     }
+    template <typename T> hipError_t upload(T** p, const T* src, size_t n, hipStream_t st) {     // alloc + copy of n host values
+        const hipError_t e = alloc(p, n);
+        return e != hipSuccess ? e : hipMemcpyAsync(*p, src, n * sizeof(T), hipMemcpyHostToDevice, st);
+    }
 };
+
+template <typename T> hipError_t fetch(T* dst, const T* src, size_t n, hipStream_t st) {   // an output the caller asked for (non-null)
+    return dst ? hipMemcpyAsync(dst, src, n * sizeof(T), hipMemcpyDeviceToHost, st) : hipSuccess;
+}
 
 size_t scratch_budget(const char* var) {    // $var bytes, default 1 GiB
     const char* e = std::getenv(var);
@@ -1814,8 +1822,27 @@ size_t scratch_budget(const char* var) {    // $var bytes, default 1 GiB
     }
     return (size_t)1 << 30;
 }
+
+// the first check of every analysis call: the spec itself
+template <class Spec> int check_spec(const Spec* spec, const char* name) {
+    if (!spec) return fail(-1, "null argument");
+    if (spec->struct_bytes != (int32_t)sizeof(Spec)) return fail(-1, "%s.struct_bytes = %d, expected %d", name, spec->struct_bytes, (int)sizeof(Spec));
+    return 0;
+}
+// the handle of an analysis call (after the argument checks): ready, and one GPU
+int check_handle(ptnn_handle* h, const char* fn) {
+    if (int rc = check_ready(h)) return rc;
+    if (h->comm.kind != COMM_NONE) return fail(-3, "%s serves one GPU: this handle has a communicator attached", fn);
+    return 0;
+}
+// the device work of an analysis call starts behind everything queued; a failed run is refused here
+int start_device(ptnn_handle* h) {
+    HIP_TRY(hipSetDevice(h->cfg.device_id));
+    return finish_stream(h);
+}
+
 // the trace rows step0, step0 + thin, ... < step0 + nsteps of the listed local replicas (NULL = all): the residency, checkpoint
-// and ring rules of ptnn_get_traces; *reps = the chains, *m = rows per chain.  Shared by ptnn_predict and ptnn_convergence.
+// and ring rules of ptnn_get_traces; *reps = the chains, *m = rows per chain.
 int select_trace_rows(const ptnn_handle* h, const int32_t* replicas, int n_replicas, int step0, int nsteps, int thin,
                       std::vector<int32_t>* reps, int* m) {
     const int S = h->cfg.n_samples, Rl = h->cfg.n_replicas_local, cap = h->cap;
@@ -1835,179 +1862,298 @@ int select_trace_rows(const ptnn_handle* h, const int32_t* replicas, int n_repli
     *m = (nsteps + thin - 1) / thin;
     return 0;
 }
+
+// The weight vectors an analysis call reads, from the fields every spec names alike: host vectors w [n_w][P] (with eta [n_w] and
+// integer multiplicities [n_w], each optional), or the trace rows of select_trace_rows.
+struct SampleSource {
+    bool host;                      // host vectors (ptnn_elpd: also a host loglik); else trace rows
+    const float* w;
+    const float* eta;
+    int64_t n_w;
+    const int32_t* multiplicity;
+    const int32_t* replicas;
+    int n_replicas, step0, nsteps, thin;
+    std::vector<int32_t> reps;      // trace: the chains
+    int m = 0;                      // trace: rows per chain
+    long long n_items = 0, M = 0;   // host vectors or trace rows; samples, multiplicities counted
+    const int32_t* weights() const { return host ? multiplicity : nullptr; }
+};
+template <class Spec> SampleSource source_of(const Spec& s, bool host, const float* eta) {
+    return SampleSource{host, s.w, eta, s.n_w, s.multiplicity, s.replicas, s.n_replicas, s.step0, s.nsteps, s.thin};
+}
+// the checks that need no handle; `unit` names a host item in the message
+int check_source(const SampleSource& src, const char* unit) {
+    if (src.host) return src.n_w < 1 ? fail(-1, "n_w = %lld host %s: need at least one", (long long)src.n_w, unit) : 0;
+    if (src.thin < 1) return fail(-1, "thin = %d must be >= 1", src.thin);
+    if (src.replicas && src.n_replicas < 1) return fail(-1, "n_replicas = %d with a replica list", src.n_replicas);
+    return 0;
+}
+// n_items and M: host multiplicities summed (no handle needed), or the trace rows selected
+int count_samples(const ptnn_handle* h, SampleSource& src) {
+    if (src.host) {
+        src.n_items = src.n_w;
+        src.M = src.multiplicity ? 0 : src.n_w;
+        for (int64_t k = 0; src.multiplicity && k < src.n_w; ++k) {
+            if (src.multiplicity[k] < 0) return fail(-1, "multiplicity[%lld] = %d is negative", (long long)k, src.multiplicity[k]);
+            src.M += src.multiplicity[k];
+        }
+        return 0;
+    }
+    if (int rc = select_trace_rows(h, src.replicas, src.n_replicas, src.step0, src.nsteps, src.thin, &src.reps, &src.m)) return rc;
+    src.n_items = src.M = (long long)src.reps.size() * src.m;
+    return 0;
+}
+int sample_limit(const SampleSource& src) {
+    if (src.M > 0x7fffffffLL || src.n_items > 0x7fffffffLL) return fail(-1, "%lld samples: at most 2^31 - 1 per call", src.M);
+    return 0;
+}
+
+// Stage a: the items of a source collapse into distinct samples -- maximal runs of bitwise-equal consecutive vectors of one chain
+// or of the host list -- with integer multiplicities (sample_runs_kernel, predict_scan_kernel).  `eta`: the samples are (w, eta)
+// -- a regression's eta is read, compared and checked, a classification's is 0 -- and every run gets its eta
+// (elpd_run_eta_kernel).  Without `merge` every item is a sample of its own with count 1 (forecast with noise: every occurrence
+// is its own trajectory).
+struct Distinct {
+    const float* base = nullptr;    // the vectors: d_pos_w rows or the uploaded host vectors
+    long long* run_off = nullptr;   // [U] float offset of sample u in base
+    int* run_cnt = nullptr;         // [U] its multiplicity
+    int* item_run = nullptr;        // [n_items] the sample of every item (merge)
+    float* run_eta = nullptr;       // [U] its eta (eta)
+    int U = 0;
+};
+int distinct_samples(ptnn_handle* h, DeviceScratch& mem, const SampleSource& src, bool eta, bool merge, Distinct* d) {
+    const long long n = src.n_items;
+    const bool reg = eta && h->cfg.task == PTNN_TASK_REG;
+    hipStream_t st = h->stream;
+    long long* item_off = nullptr;
+    int *flag = nullptr, *err = nullptr, *weight = nullptr, *reps = nullptr;
+    float *item_eta = nullptr, *w = nullptr, *host_eta = nullptr;
+    HIP_TRY(mem.alloc(&item_off, (size_t)n));
+    HIP_TRY(mem.alloc(&flag, (size_t)n));
+    HIP_TRY(mem.alloc(&d->run_cnt, (size_t)n));
+    HIP_TRY(mem.alloc(&err, 4));        // [0] runs, [1] unresolved compact rows, [2] rows without eta, [3] the first such chain
+    if (eta) HIP_TRY(mem.alloc(&item_eta, (size_t)n));
+    if (merge) {
+        HIP_TRY(mem.alloc(&d->run_off, (size_t)n));
+        HIP_TRY(mem.alloc(&d->item_run, (size_t)n));
+        if (eta) HIP_TRY(mem.alloc(&d->run_eta, (size_t)n));
+        HIP_TRY(hipMemsetAsync(d->run_cnt, 0, (size_t)n * sizeof(int), st));
+    } else {
+        d->run_off = item_off;
+        d->run_eta = item_eta;
+        HIP_TRY(hipMemsetD32Async(d->run_cnt, 1, (size_t)n, st));
+    }
+    HIP_TRY(hipMemsetAsync(err, 0, 3 * sizeof(int), st));
+    if (eta) HIP_TRY(hipMemsetAsync(err + 3, 0x7f, sizeof(int), st));
+    SampleSel sel{};
+    sel.reg = reg ? 1 : 0; sel.P = h->P; sel.n_items = n; sel.item_off = item_off; sel.item_eta = item_eta; sel.flag = flag;
+    sel.error = err + 1;
+    if (src.host) {
+        HIP_TRY(mem.upload(&w, src.w, (size_t)n * h->P, st));
+        if (reg) HIP_TRY(mem.upload(&host_eta, src.eta, (size_t)n, st));
+        if (merge && src.multiplicity) HIP_TRY(mem.upload(&weight, src.multiplicity, (size_t)n, st));
+        sel.host = 1; sel.pos_w = w; sel.host_eta = host_eta;
+    } else {
+        HIP_TRY(mem.upload(&reps, src.reps.data(), src.reps.size(), st));
+        sel.host = 0; sel.pos_w = h->d_pos_w; sel.scal = h->d_scal; sel.replicas = reps; sel.st_i = h->d_st_i; sel.cap = h->cap;
+        sel.PW = h->PW; sel.step0 = src.step0; sel.thin = src.thin; sel.m = src.m; sel.compact = h->plan.compact ? 1 : 0; sel.cur = h->cur;
+    }
+    d->base = sel.pos_w;
+    const unsigned item_blocks = (unsigned)((n + PRED_THREADS - 1) / PRED_THREADS);
+    hipLaunchKernelGGL(sample_runs_kernel, dim3(item_blocks), dim3(PRED_THREADS), 0, st, sel);
+    HIP_TRY(hipGetLastError());
+    if (merge) {
+        PredictScan sc{n, flag, item_off, weight, d->item_run, d->run_off, d->run_cnt, err};
+        hipLaunchKernelGGL(predict_scan_kernel, dim3(1), dim3(PRED_SCAN_THREADS), 0, st, sc);
+        HIP_TRY(hipGetLastError());
+        if (eta) {
+            hipLaunchKernelGGL(elpd_run_eta_kernel, dim3(item_blocks), dim3(ELPD_THREADS), 0, st, n, (const int*)flag,
+                               (const int*)d->item_run, (const float*)item_eta, d->run_eta);
+            HIP_TRY(hipGetLastError());
+        }
+    }
+    int e[4] = {0, 0, 0, 0};
+    HIP_TRY(hipMemcpyAsync(e, err, sizeof e, hipMemcpyDeviceToHost, st));
+    if (int rc = wait_stream(h)) return rc;          // also keeps the host arrays of `src` alive until the copies are done
+    if (e[1]) return fail(-2, "%d selected compact trace rows refer to rows that are not resident (internal error)", e[1]);
+    if (e[2]) {
+        const int c = e[3] >= 0 && e[3] < (int)src.reps.size() ? e[3] : 0;
+        return fail(-1, "%s%d selected trace rows precede their chain's first accepted MH step (chain %d, local replica %d, among "
+                        "others): no eta = log tau^2 was recorded for them; start the selection later (a larger burn_in)",
+                    merge ? "" : "noise: ", e[2], c, src.reps.empty() ? 0 : src.reps[(size_t)c]);
+    }
+    d->U = merge ? e[0] : (int)n;
+    if (d->U < 1 || d->U > n) return fail(-2, "run-length pass found %d distinct samples among %lld rows (internal error)", d->U, n);
+    return 0;
+}
+// the sample of every item on the host, for the selection-order outputs (queued: valid after the next wait_stream)
+int item_runs(ptnn_handle* h, const Distinct& d, long long n_items, std::vector<int>* out) {
+    out->resize((size_t)n_items);
+    if (!d.item_run) {
+        for (long long i = 0; i < n_items; ++i) (*out)[(size_t)i] = (int)i;
+        return 0;
+    }
+    HIP_TRY(hipMemcpyAsync(out->data(), d.item_run, (size_t)n_items * sizeof(int), hipMemcpyDeviceToHost, h->stream));
+    return 0;
+}
+// A block of per-sample outputs blk [ncols][U] on the device, expanded to the selection's order (chain-major, item i `mult[i]`
+// times, null: once): selected sample `row` gets its columns at out + row * row_stride + col0.
+template <typename T>
+int scatter_samples(ptnn_handle* h, const T* blk, int ncols, int U, const std::vector<int>& item_run, const int32_t* mult, T* out,
+                    size_t row_stride, size_t col0) {
+    std::vector<T> hb((size_t)ncols * U);
+    HIP_TRY(hipMemcpyAsync(hb.data(), blk, hb.size() * sizeof(T), hipMemcpyDeviceToHost, h->stream));
+    if (int rc = wait_stream(h)) return rc;
+    size_t row = 0;
+    for (size_t i = 0; i < item_run.size(); ++i) {
+        const size_t u = (size_t)item_run[i];
+        for (int k = 0, reps = mult ? mult[i] : 1; k < reps; ++k, ++row) {
+            T* dst = out + row * row_stride + col0;
+            for (int c = 0; c < ncols; ++c) dst[c] = hb[(size_t)c * U + u];
+        }
+    }
+    return 0;
+}
+
+// Input rows of an analysis call: `source` PTNN_PREDICT_X_HOST with host rows, or the handle's train / test set
+static_assert(PTNN_FORECAST_ORIGIN_HOST == PTNN_PREDICT_X_HOST && PTNN_FORECAST_ORIGIN_TRAIN == PTNN_PREDICT_X_TRAIN &&
+              PTNN_FORECAST_ORIGIN_TEST == PTNN_PREDICT_X_TEST, "ptnn.h row sources");
+struct RowSource {
+    int source;
+    const float* host;
+    int n;
+    const char *field, *prefix, *arg, *count;   // names in the messages: "x_source", "PTNN_PREDICT_X", "x", "n_rows"
+};
+int check_rows(const RowSource& r) {        // no handle needed
+    if (r.source != PTNN_PREDICT_X_HOST && r.source != PTNN_PREDICT_X_TRAIN && r.source != PTNN_PREDICT_X_TEST)
+        return fail(-1, "%s = %d is not %s_HOST, _TRAIN or _TEST", r.field, r.source, r.prefix);
+    if (r.source == PTNN_PREDICT_X_HOST && !r.host) return fail(-1, "%s %s_HOST needs %s", r.field, r.prefix, r.arg);
+    return 0;
+}
+int fit_rows(const ptnn_handle* h, const RowSource& r) {
+    if (r.source == PTNN_PREDICT_X_TRAIN && r.n != h->Ntr) return fail(-1, "%s = %d but the train set has %d rows", r.count, r.n, h->Ntr);
+    if (r.source == PTNN_PREDICT_X_TEST && r.n != h->Nte) return fail(-1, "%s = %d but the test set has %d rows", r.count, r.n, h->Nte);
+    return 0;
+}
+// the rows on the device: the host rows (`width` floats each) uploaded, or the data set; row k at *x + k * *xs
+int upload_rows(ptnn_handle* h, DeviceScratch& mem, const RowSource& r, int width, const float** x, int* xs) {
+    if (r.source == PTNN_PREDICT_X_HOST) {
+        float* d = nullptr;
+        HIP_TRY(mem.upload(&d, r.host, (size_t)r.n * width, h->stream));
+        *x = d; *xs = width;
+    } else {
+        *x = h->d_data + (r.source == PTNN_PREDICT_X_TEST ? (size_t)h->Ntr * h->IPY : 0);
+        *xs = h->IPY;
+    }
+    return 0;
+}
+
+// Stage b of predict, elpd and evidence: the per-shape predict_fwd, NV distinct vectors staged in LDS per work-group
+struct ForwardPlan {
+    int PV = 0, NV = 0;
+    size_t lds = 0;
+    int init(const ptnn_handle* h, const char* what) {
+        const int P = h->P;
+        PV = round_up4(P);
+        const int per_vec = PV + (PRED_THREADS / WAVE + 1) * h->cfg.n_out * WAVE;   // staged vector + partial sums + transposed tile
+        NV = std::max(1, std::min(PRED_MAX_NV, (48 * 1024 / 4) / per_vec));
+        lds = (size_t)NV * per_vec * sizeof(float);
+        if (lds > 152 * 1024) return fail(-3, "%s: a %d-parameter vector does not fit in LDS", what, P);
+        return raise_lds_limit(reinterpret_cast<const void*>(h->shape->predict_fwd), lds);
+    }
+    // fx [nr * O][U] = the outputs of vectors base + run_off[u] on rows [r0, r0 + nr) of x
+    int launch(const ptnn_handle* h, const float* base, const long long* run_off, const float* x, int xs, int r0, int nr, int U, float* fx) const {
+        PredictFwd fa{base, run_off, x, xs, r0, nr, h->cfg.n_hidden, h->P, PV, U, NV, fx};
+        hipLaunchKernelGGL(h->shape->predict_fwd, dim3((unsigned)((U + NV - 1) / NV), (unsigned)((nr + WAVE - 1) / WAVE)), dim3(PRED_THREADS), lds,
+                           h->stream, fa);
+        HIP_TRY(hipGetLastError());
+        return 0;
+    }
+};
+// rows per block of the forward pass: `budget` bytes of scratch at `row_bytes` per row, and at most 65535 work-groups of WAVE
+// rows (grid.y of predict_fwd)
+long long row_block(size_t budget, size_t row_bytes, long long n_rows) {
+    return std::max(1LL, std::min<long long>({(long long)(budget / row_bytes), 65535LL * WAVE, n_rows}));
+}
+
+// the order statistics of predict and forecast: ranks [n_ranks] in the expanded multiset of M samples
+int check_ranks(int n_ranks, const int64_t* ranks, const void* order_stats) {
+    if (n_ranks < 0 || n_ranks > PTNN_PREDICT_MAX_RANKS) return fail(-1, "n_ranks = %d outside [0, %d]", n_ranks, PTNN_PREDICT_MAX_RANKS);
+    if (n_ranks > 0 && !ranks) return fail(-1, "n_ranks = %d but ranks is NULL", n_ranks);
+    if (order_stats && n_ranks == 0) return fail(-1, "order_stats requested without ranks");
+    return 0;
+}
+int check_rank_values(int n_ranks, const int64_t* ranks, long long M) {
+    for (int k = 0; k < n_ranks; ++k)
+        if (ranks[k] < 0 || ranks[k] >= M) return fail(-1, "rank %lld outside [0, %lld)", (long long)ranks[k], M);
+    return 0;
+}
 }  // namespace
 
 extern "C" {
 
+// ---- posterior predictive (ptnn_dev_predict.hpp) ----
 int ptnn_predict(ptnn_handle* h, const ptnn_predict_spec* spec) {
     // argument checks first: none of them needs the handle or a device
-    if (!spec) return fail(-1, "null argument");
-    if (spec->struct_bytes != (int32_t)sizeof(ptnn_predict_spec))
-        return fail(-1, "ptnn_predict_spec.struct_bytes = %d, expected %d", spec->struct_bytes, (int)sizeof(ptnn_predict_spec));
+    if (int rc = check_spec(spec, "ptnn_predict_spec")) return rc;
     const ptnn_predict_spec& s = *spec;
-    const bool host_src = s.w != nullptr;
-    if (host_src && s.n_w < 1) return fail(-1, "n_w = %lld host vectors: need at least one", (long long)s.n_w);
-    if (!host_src && s.thin < 1) return fail(-1, "thin = %d must be >= 1", s.thin);
-    if (!host_src && s.replicas && s.n_replicas < 1) return fail(-1, "n_replicas = %d with a replica list", s.n_replicas);
-    if (s.x_source != PTNN_PREDICT_X_HOST && s.x_source != PTNN_PREDICT_X_TRAIN && s.x_source != PTNN_PREDICT_X_TEST)
-        return fail(-1, "x_source = %d is not PTNN_PREDICT_X_HOST, _TRAIN or _TEST", s.x_source);
-    if (s.x_source == PTNN_PREDICT_X_HOST && !s.x) return fail(-1, "x_source PTNN_PREDICT_X_HOST needs x");
+    SampleSource src = source_of(s, s.w != nullptr, nullptr);
+    const RowSource rows{s.x_source, s.x, s.n_rows, "x_source", "PTNN_PREDICT_X", "x", "n_rows"};
+    if (int rc = check_source(src, "vectors")) return rc;
+    if (int rc = check_rows(rows)) return rc;
     if (s.n_rows < 1) return fail(-1, "n_rows = %d must be >= 1", s.n_rows);
-    if (s.n_ranks < 0 || s.n_ranks > PTNN_PREDICT_MAX_RANKS) return fail(-1, "n_ranks = %d outside [0, %d]", s.n_ranks, PTNN_PREDICT_MAX_RANKS);
-    if (s.n_ranks > 0 && !s.ranks) return fail(-1, "n_ranks = %d but ranks is NULL", s.n_ranks);
-    if (s.order_stats && s.n_ranks == 0) return fail(-1, "order_stats requested without ranks");
-    if (int rc = check_ready(h)) return rc;
-    if (h->comm.kind != COMM_NONE) return fail(-3, "ptnn_predict serves one GPU: this handle has a communicator attached");
-    const int I = h->cfg.n_in, H = h->cfg.n_hidden, O = h->cfg.n_out, P = h->P, cap = h->cap;
+    if (int rc = check_ranks(s.n_ranks, s.ranks, s.order_stats)) return rc;
+    if (int rc = check_handle(h, "ptnn_predict")) return rc;
+    const int I = h->cfg.n_in, O = h->cfg.n_out;
     if (s.vote && h->cfg.task != PTNN_TASK_CLS) return fail(-1, "vote: a regression has no classes");
-    if (s.x_source == PTNN_PREDICT_X_TRAIN && s.n_rows != h->Ntr) return fail(-1, "n_rows = %d but the train set has %d rows", s.n_rows, h->Ntr);
-    if (s.x_source == PTNN_PREDICT_X_TEST && s.n_rows != h->Nte) return fail(-1, "n_rows = %d but the test set has %d rows", s.n_rows, h->Nte);
-    // the selection
-    std::vector<int32_t> reps;
-    long long n_items = 0, M = 0;
-    int m = 0;
-    if (host_src) {
-        n_items = s.n_w;
-        if (s.multiplicity) {
-            for (int64_t k = 0; k < s.n_w; ++k) {
-                if (s.multiplicity[k] < 0) return fail(-1, "multiplicity[%lld] = %d is negative", (long long)k, s.multiplicity[k]);
-                M += s.multiplicity[k];
-            }
-        } else {
-            M = s.n_w;
-        }
-    } else {
-        if (int rc = select_trace_rows(h, s.replicas, s.n_replicas, s.step0, s.nsteps, s.thin, &reps, &m)) return rc;
-        n_items = (long long)reps.size() * m;
-        M = n_items;
-    }
+    if (int rc = fit_rows(h, rows)) return rc;
+    if (int rc = count_samples(h, src)) return rc;
+    const long long M = src.M;
     if (M < 1) return fail(-1, "the selection holds no sample");
-    if (M > 0x7fffffffLL || n_items > 0x7fffffffLL) return fail(-1, "%lld samples: at most 2^31 - 1 per call", M);
-    for (int k = 0; k < s.n_ranks; ++k)
-        if (s.ranks[k] < 0 || s.ranks[k] >= M) return fail(-1, "rank %lld outside [0, %lld)", (long long)s.ranks[k], M);
+    if (int rc = sample_limit(src)) return rc;
+    if (int rc = check_rank_values(s.n_ranks, s.ranks, M)) return rc;
     if (s.n_samples) *s.n_samples = M;
 
-    HIP_TRY(hipSetDevice(h->cfg.device_id));
-    if (int rc = finish_stream(h)) return rc;          // behind everything queued; a failed run is refused here
+    if (int rc = start_device(h)) return rc;
     hipStream_t st = h->stream;
     DeviceScratch mem;
     const int ncols = s.n_rows * O;
-    // inputs
     const float* d_x = nullptr;
     int xs = 0;
-    if (s.x_source == PTNN_PREDICT_X_HOST) {
-        float* d = nullptr;
-        HIP_TRY(mem.alloc(&d, (size_t)s.n_rows * I));
-        HIP_TRY(hipMemcpyAsync(d, s.x, (size_t)s.n_rows * I * sizeof(float), hipMemcpyHostToDevice, st));
-        d_x = d; xs = I;
-    } else {
-        d_x = h->d_data + (s.x_source == PTNN_PREDICT_X_TEST ? (size_t)h->Ntr * h->IPY : 0);
-        xs = h->IPY;
-    }
-    // stage a: items -> runs
-    long long* d_item_off = nullptr; long long* d_run_off = nullptr; long long* d_ranks = nullptr;
-    int *d_flag = nullptr, *d_item_run = nullptr, *d_run_cnt = nullptr, *d_nruns = nullptr, *d_weight = nullptr, *d_reps = nullptr;
-    float* d_w = nullptr;
-    HIP_TRY(mem.alloc(&d_item_off, (size_t)n_items));
-    HIP_TRY(mem.alloc(&d_run_off, (size_t)n_items));
-    HIP_TRY(mem.alloc(&d_flag, (size_t)n_items));
-    HIP_TRY(mem.alloc(&d_item_run, (size_t)n_items));
-    HIP_TRY(mem.alloc(&d_run_cnt, (size_t)n_items));
-    HIP_TRY(mem.alloc(&d_nruns, 2));                     // [0] runs, [1] error count of the compact-row resolution
-    HIP_TRY(hipMemsetAsync(d_run_cnt, 0, (size_t)n_items * sizeof(int), st));
-    HIP_TRY(hipMemsetAsync(d_nruns, 0, 2 * sizeof(int), st));
-    PredictSel sel{};
-    sel.P = P; sel.n_items = n_items; sel.item_off = d_item_off; sel.flag = d_flag; sel.error = d_nruns + 1;
-    const float* base = nullptr;
-    if (host_src) {
-        HIP_TRY(mem.alloc(&d_w, (size_t)n_items * P));
-        HIP_TRY(hipMemcpyAsync(d_w, s.w, (size_t)n_items * P * sizeof(float), hipMemcpyHostToDevice, st));
-        if (s.multiplicity) {
-            HIP_TRY(mem.alloc(&d_weight, (size_t)n_items));
-            HIP_TRY(hipMemcpyAsync(d_weight, s.multiplicity, (size_t)n_items * sizeof(int32_t), hipMemcpyHostToDevice, st));
-        }
-        sel.host = 1; sel.pos_w = d_w;
-        base = d_w;
-    } else {
-        HIP_TRY(mem.alloc(&d_reps, reps.size()));
-        HIP_TRY(hipMemcpyAsync(d_reps, reps.data(), reps.size() * sizeof(int32_t), hipMemcpyHostToDevice, st));
-        sel.host = 0; sel.pos_w = h->d_pos_w; sel.scal = h->d_scal; sel.replicas = d_reps; sel.cap = cap; sel.PW = h->PW;
-        sel.step0 = s.step0; sel.thin = s.thin; sel.m = m; sel.compact = h->plan.compact ? 1 : 0;
-        base = h->d_pos_w;
-    }
-    hipLaunchKernelGGL(predict_runs_kernel, dim3((unsigned)((n_items + PRED_THREADS - 1) / PRED_THREADS)), dim3(PRED_THREADS), 0, st, sel);
-    HIP_TRY(hipGetLastError());
-    PredictScan sc{n_items, d_flag, d_item_off, d_weight, d_item_run, d_run_off, d_run_cnt, d_nruns};
-    hipLaunchKernelGGL(predict_scan_kernel, dim3(1), dim3(PRED_SCAN_THREADS), 0, st, sc);
-    HIP_TRY(hipGetLastError());
-    int runs[2] = {0, 0};
-    HIP_TRY(hipMemcpyAsync(runs, d_nruns, sizeof runs, hipMemcpyDeviceToHost, st));
-    if (int rc = wait_stream(h)) return rc;
-    if (runs[1]) return fail(-2, "%d selected compact trace rows refer to rows that are not resident (internal error)", runs[1]);
-    const int U = runs[0];
-    if (U < 1 || U > n_items) return fail(-2, "run-length pass found %d distinct vectors among %lld rows (internal error)", U, n_items);
+    if (int rc = upload_rows(h, mem, rows, I, &d_x, &xs)) return rc;
+    Distinct d;
+    if (int rc = distinct_samples(h, mem, src, false, true, &d)) return rc;
+    const int U = d.U;
     if (s.n_distinct) *s.n_distinct = U;
     // outputs on the device for every column; votes as integer counts (exact whatever the order)
-    double* d_mean = nullptr; float* d_ostat = nullptr; long long* d_votes = nullptr;
+    double* d_mean = nullptr; float* d_ostat = nullptr; long long* d_votes = nullptr; long long* d_ranks = nullptr;
     HIP_TRY(mem.alloc(&d_mean, (size_t)ncols));
     if (s.n_ranks) {
         HIP_TRY(mem.alloc(&d_ostat, (size_t)s.n_ranks * ncols));
-        HIP_TRY(mem.alloc(&d_ranks, (size_t)s.n_ranks));
-        HIP_TRY(hipMemcpyAsync(d_ranks, s.ranks, (size_t)s.n_ranks * sizeof(int64_t), hipMemcpyHostToDevice, st));
+        HIP_TRY(mem.upload(&d_ranks, (const long long*)s.ranks, (size_t)s.n_ranks, st));
     }
     if (h->cfg.task == PTNN_TASK_CLS) HIP_TRY(mem.alloc(&d_votes, (size_t)ncols));
     // stage b + c in blocks of rows: fx scratch U x (rows x O) floats under the budget
-    const size_t budget = scratch_budget("PTNN_PREDICT_SCRATCH_BYTES");
-    const size_t col_bytes = (size_t)U * sizeof(float);
-    long long rows_blk = (long long)(budget / (col_bytes * O));
-    rows_blk = std::min<long long>(rows_blk, 65535LL * WAVE);       // grid.y of the forward pass: one 64-row tile per work-group
-    rows_blk = std::max(1LL, std::min<long long>(rows_blk, s.n_rows));
+    const long long rows_blk = row_block(scratch_budget("PTNN_PREDICT_SCRATCH_BYTES"), (size_t)U * sizeof(float) * O, s.n_rows);
     float* d_fx = nullptr;
     HIP_TRY(mem.alloc(&d_fx, (size_t)rows_blk * O * U));
-    const int PV = round_up4(P);
-    const int per_vec = PV + (PRED_THREADS / WAVE + 1) * O * WAVE;     // staged vector + partial sums + transposed tile, floats
-    int NV = std::max(1, std::min(PRED_MAX_NV, (48 * 1024 / 4) / per_vec));
-    const size_t lds = (size_t)NV * per_vec * sizeof(float);
-    if (lds > 152 * 1024) return fail(-3, "posterior predictive: a %d-parameter vector does not fit in LDS", P);
-    const void* fwd = reinterpret_cast<const void*>(h->shape->predict_fwd);
-    if (int rc = raise_lds_limit(fwd, lds)) return rc;
+    ForwardPlan fwd;
+    if (int rc = fwd.init(h, "posterior predictive")) return rc;
     std::vector<int> item_run;
-    std::vector<float> fx_host;
-    if (s.samples) {
-        item_run.resize((size_t)n_items);
-        HIP_TRY(hipMemcpyAsync(item_run.data(), d_item_run, (size_t)n_items * sizeof(int), hipMemcpyDeviceToHost, st));
-    }
+    if (s.samples) if (int rc = item_runs(h, d, src.n_items, &item_run)) return rc;
     for (long long r0 = 0; r0 < s.n_rows; r0 += rows_blk) {
         const int nr = (int)std::min<long long>(rows_blk, s.n_rows - r0);
-        PredictFwd fa{base, d_run_off, d_x, xs, (int)r0, nr, H, P, PV, U, NV, d_fx};
-        hipLaunchKernelGGL(h->shape->predict_fwd, dim3((unsigned)((U + NV - 1) / NV), (unsigned)((nr + WAVE - 1) / WAVE)), dim3(PRED_THREADS), lds, st, fa);
-        HIP_TRY(hipGetLastError());
-        PredictRed ra{d_fx, d_run_cnt, U, O, (int)r0 * O, ncols, M, s.n_ranks, d_ranks, d_mean, d_ostat, d_votes};
+        if (int rc = fwd.launch(h, d.base, d.run_off, d_x, xs, (int)r0, nr, U, d_fx)) return rc;
+        PredictRed ra{d_fx, d.run_cnt, U, O, (int)r0 * O, ncols, M, s.n_ranks, d_ranks, d_mean, d_ostat, d_votes};
         hipLaunchKernelGGL(predict_reduce_kernel, dim3((unsigned)(nr * O)), dim3(PRED_THREADS), 0, st, ra);
         HIP_TRY(hipGetLastError());
-        if (s.samples) {
-            // every selected row gets its distinct vector's outputs, in the order of the selection (chain-major)
-            fx_host.resize((size_t)nr * O * U);
-            HIP_TRY(hipMemcpyAsync(fx_host.data(), d_fx, fx_host.size() * sizeof(float), hipMemcpyDeviceToHost, st));
-            if (int rc = wait_stream(h)) return rc;
-            long long out_row = 0;
-            for (long long i = 0; i < n_items; ++i) {
-                const int reps_i = (host_src && s.multiplicity) ? s.multiplicity[i] : 1;
-                const size_t u = (size_t)item_run[(size_t)i];
-                for (int k = 0; k < reps_i; ++k, ++out_row) {
-                    float* dst = s.samples + ((size_t)out_row * s.n_rows + r0) * O;
-                    for (int c = 0; c < nr * O; ++c) dst[c] = fx_host[(size_t)c * U + u];
-                }
-            }
-        }
+        if (s.samples)
+            if (int rc = scatter_samples(h, d_fx, nr * O, U, item_run, src.weights(), s.samples, (size_t)s.n_rows * O, (size_t)r0 * O)) return rc;
     }
-    std::vector<long long> votes_h;
-    if (s.mean) HIP_TRY(hipMemcpyAsync(s.mean, d_mean, (size_t)ncols * sizeof(double), hipMemcpyDeviceToHost, st));
-    if (s.order_stats) HIP_TRY(hipMemcpyAsync(s.order_stats, d_ostat, (size_t)s.n_ranks * ncols * sizeof(float), hipMemcpyDeviceToHost, st));
-    if (s.vote) {
-        votes_h.resize((size_t)ncols);
-        HIP_TRY(hipMemcpyAsync(votes_h.data(), d_votes, (size_t)ncols * sizeof(long long), hipMemcpyDeviceToHost, st));
-    }
+    std::vector<long long> votes_h(s.vote ? (size_t)ncols : 0);
+    HIP_TRY(fetch(s.mean, d_mean, (size_t)ncols, st));
+    HIP_TRY(fetch(s.order_stats, d_ostat, (size_t)s.n_ranks * ncols, st));
+    HIP_TRY(fetch(s.vote ? votes_h.data() : nullptr, d_votes, (size_t)ncols, st));
     if (int rc = wait_stream(h)) return rc;
     if (s.vote)
         for (int c = 0; c < ncols; ++c) s.vote[c] = (double)votes_h[(size_t)c] / (double)M;
@@ -2026,8 +2172,7 @@ static int conv_drive(ptnn_handle* h, DeviceScratch& mem, ConvGather ga, const s
     const int NS = 1 + (per_chain ? C : 0);
     hipStream_t st = h->stream;
     int *d_qcol = nullptr, *d_error = nullptr;
-    HIP_TRY(mem.alloc(&d_qcol, (size_t)Q));
-    HIP_TRY(hipMemcpyAsync(d_qcol, qcol.data(), (size_t)Q * sizeof(int), hipMemcpyHostToDevice, st));
+    HIP_TRY(mem.upload(&d_qcol, qcol.data(), (size_t)Q, st));
     HIP_TRY(mem.alloc(&d_error, 1));
     HIP_TRY(hipMemsetAsync(d_error, 0, sizeof(int), st));
     ga.C = C; ga.n = n; ga.h = hl; ga.error = d_error;
@@ -2118,9 +2263,7 @@ static int conv_drive(ptnn_handle* h, DeviceScratch& mem, ConvGather ga, const s
 
 int ptnn_convergence(ptnn_handle* h, const ptnn_convergence_spec* spec) {
     // argument checks first: none of them needs the handle or a device
-    if (!spec) return fail(-1, "null argument");
-    if (spec->struct_bytes != (int32_t)sizeof(ptnn_convergence_spec))
-        return fail(-1, "ptnn_convergence_spec.struct_bytes = %d, expected %d", spec->struct_bytes, (int)sizeof(ptnn_convergence_spec));
+    if (int rc = check_spec(spec, "ptnn_convergence_spec")) return rc;
     const ptnn_convergence_spec& s = *spec;
     const bool host_src = s.draws != nullptr;
     constexpr int scalar_cols = (1 << TR_LIKEH) | (1 << TR_RMSE_TR) | (1 << TR_RMSE_TE) | (1 << TR_ACC_TR) | (1 << TR_ACC_TE);
@@ -2139,8 +2282,7 @@ int ptnn_convergence(ptnn_handle* h, const ptnn_convergence_spec* spec) {
     if (s.n_lags < 0) return fail(-1, "n_lags = %d must be >= 0", s.n_lags);
     if (s.n_lags > 0 && !s.rho) return fail(-1, "n_lags = %d but rho is NULL", s.n_lags);
     if (s.rho && s.n_lags == 0) return fail(-1, "rho requested with n_lags = 0");
-    if (int rc = check_ready(h)) return rc;
-    if (h->comm.kind != COMM_NONE) return fail(-3, "ptnn_convergence serves one GPU: this handle has a communicator attached");
+    if (int rc = check_handle(h, "ptnn_convergence")) return rc;
     const int P = h->P, cap = h->cap;
     // the selection: chains, draws per chain, the column of every quantity
     std::vector<int32_t> reps;
@@ -2168,8 +2310,7 @@ int ptnn_convergence(ptnn_handle* h, const ptnn_convergence_spec* spec) {
     const int hl = n / 2, Q = (int)qcol.size();
     if (s.n_lags > hl) return fail(-1, "n_lags = %d exceeds the split-chain length %d", s.n_lags, hl);
 
-    HIP_TRY(hipSetDevice(h->cfg.device_id));
-    if (int rc = finish_stream(h)) return rc;          // behind everything queued; a failed run is refused here
+    if (int rc = start_device(h)) return rc;
     hipStream_t st = h->stream;
     DeviceScratch mem;
     int* d_reps = nullptr;
@@ -2177,12 +2318,10 @@ int ptnn_convergence(ptnn_handle* h, const ptnn_convergence_spec* spec) {
     ConvGather ga{};
     if (host_src) {
         const size_t nd = (size_t)C * n * Q;
-        HIP_TRY(mem.alloc(&d_draws, nd));
-        HIP_TRY(hipMemcpyAsync(d_draws, s.draws, nd * sizeof(float), hipMemcpyHostToDevice, st));
+        HIP_TRY(mem.upload(&d_draws, s.draws, nd, st));
         ga.host = 1; ga.draws = d_draws; ga.Qh = Q;
     } else {
-        HIP_TRY(mem.alloc(&d_reps, reps.size()));
-        HIP_TRY(hipMemcpyAsync(d_reps, reps.data(), reps.size() * sizeof(int32_t), hipMemcpyHostToDevice, st));
+        HIP_TRY(mem.upload(&d_reps, reps.data(), reps.size(), st));
         ga.host = 0; ga.pos_w = h->d_pos_w; ga.scal = h->d_scal; ga.replicas = d_reps; ga.cap = cap; ga.PW = h->PW;
         ga.step0 = s.step0; ga.thin = s.thin; ga.compact = h->plan.compact ? 1 : 0;
     }
@@ -2194,72 +2333,50 @@ static_assert(PTNN_ELPD_TAIL_CAP == ELPD_TAIL_CAP, "ptnn.h tail capacity");
 
 int ptnn_elpd(ptnn_handle* h, const ptnn_elpd_spec* spec) {
     // argument checks first: none of them needs the handle or a device
-    if (!spec) return fail(-1, "null argument");
-    if (spec->struct_bytes != (int32_t)sizeof(ptnn_elpd_spec))
-        return fail(-1, "ptnn_elpd_spec.struct_bytes = %d, expected %d", spec->struct_bytes, (int)sizeof(ptnn_elpd_spec));
+    if (int rc = check_spec(spec, "ptnn_elpd_spec")) return rc;
     const ptnn_elpd_spec& s = *spec;
     const bool ll_src = s.loglik != nullptr, host_src = s.w != nullptr;
+    SampleSource src = source_of(s, ll_src || host_src, s.eta);
+    const RowSource rows{s.x_source, s.x, s.n_rows, "x_source", "PTNN_PREDICT_X", "x", "n_rows"};
     if (ll_src && host_src) return fail(-1, "give host vectors w or a host loglik, not both");
     if (!(s.r_eff > 0.0) || !std::isfinite(s.r_eff)) return fail(-1, "r_eff = %g must be a finite number > 0", s.r_eff);
-    if ((ll_src || host_src) && s.n_w < 1) return fail(-1, "n_w = %lld host samples: need at least one", (long long)s.n_w);
-    if (!ll_src && !host_src && s.nsteps < 1)
+    if (!src.host && s.nsteps < 1)
         return fail(-1, "no source: nsteps = %d trace rows, and neither host vectors w nor a host loglik", s.nsteps);
-    if (!ll_src && !host_src && s.thin < 1) return fail(-1, "thin = %d must be >= 1", s.thin);
-    if (!ll_src && !host_src && s.replicas && s.n_replicas < 1) return fail(-1, "n_replicas = %d with a replica list", s.n_replicas);
+    if (int rc = check_source(src, "samples")) return rc;
     if (s.n_rows < 1) return fail(-1, "n_rows = %d must be >= 1", s.n_rows);
-    if (!ll_src) {
-        if (s.x_source != PTNN_PREDICT_X_HOST && s.x_source != PTNN_PREDICT_X_TRAIN && s.x_source != PTNN_PREDICT_X_TEST)
-            return fail(-1, "x_source = %d is not PTNN_PREDICT_X_HOST, _TRAIN or _TEST", s.x_source);
-        if (s.x_source == PTNN_PREDICT_X_HOST && !s.x) return fail(-1, "x_source PTNN_PREDICT_X_HOST needs x");
-    }
+    if (!ll_src)
+        if (int rc = check_rows(rows)) return rc;
     if (ll_src && s.loglik_out) return fail(-1, "loglik_out: the log-likelihood is the input of this source");
     // the sample count of the host sources
-    long long n_items = 0, S = 0;
-    if (ll_src || host_src) {
-        n_items = s.n_w;
-        if (s.multiplicity) {
-            for (int64_t k = 0; k < s.n_w; ++k) {
-                if (s.multiplicity[k] < 0) return fail(-1, "multiplicity[%lld] = %d is negative", (long long)k, s.multiplicity[k]);
-                S += s.multiplicity[k];
-            }
-        } else {
-            S = s.n_w;
-        }
-    }
+    if (src.host)
+        if (int rc = count_samples(nullptr, src)) return rc;
     if (ll_src)
-        for (long long k = 0; k < n_items * s.n_rows; ++k)
+        for (long long k = 0; k < src.n_items * s.n_rows; ++k)
             if (!std::isfinite(s.loglik[k])) return fail(-1, "loglik[%lld, %lld] = %g is not finite", k / s.n_rows, k % s.n_rows, s.loglik[k]);
-    if (int rc = check_ready(h)) return rc;
-    if (h->comm.kind != COMM_NONE) return fail(-3, "ptnn_elpd serves one GPU: this handle has a communicator attached");
-    const int I = h->cfg.n_in, H = h->cfg.n_hidden, O = h->cfg.n_out, P = h->P, cap = h->cap;
+    if (int rc = check_handle(h, "ptnn_elpd")) return rc;
+    const int I = h->cfg.n_in, O = h->cfg.n_out;
     const bool reg = h->cfg.task == PTNN_TASK_REG;
     if (host_src && reg && !s.eta) return fail(-1, "a regression's host vectors need eta = log tau^2 (one per vector)");
-    if (!ll_src && s.x_source == PTNN_PREDICT_X_TRAIN && s.n_rows != h->Ntr) return fail(-1, "n_rows = %d but the train set has %d rows", s.n_rows, h->Ntr);
-    if (!ll_src && s.x_source == PTNN_PREDICT_X_TEST && s.n_rows != h->Nte) return fail(-1, "n_rows = %d but the test set has %d rows", s.n_rows, h->Nte);
+    if (!ll_src)
+        if (int rc = fit_rows(h, rows)) return rc;
     if (!ll_src && s.x_source == PTNN_PREDICT_X_HOST && !reg)
         for (int n = 0; n < s.n_rows; ++n) {
             const float yv = s.x[(size_t)n * (I + 1) + I];
             if (!(yv >= 0.0f) || yv >= (float)O || yv != std::floor(yv))
                 return fail(-1, "class label %g in row %d is not an integer in [0, %d)", (double)yv, n, O);
         }
-    // the selection
-    std::vector<int32_t> reps;
-    int m = 0;
-    if (!ll_src && !host_src) {
-        if (int rc = select_trace_rows(h, s.replicas, s.n_replicas, s.step0, s.nsteps, s.thin, &reps, &m)) return rc;
-        n_items = (long long)reps.size() * m;
-        S = n_items;
-    }
+    if (!src.host)
+        if (int rc = count_samples(h, src)) return rc;
+    const long long n_items = src.n_items, S = src.M;
     if (S < 2) return fail(-1, "the selection holds %lld samples: p_waic (a variance, ddof 1) needs at least 2", S);
-    if (S > 0x7fffffffLL || n_items > 0x7fffffffLL) return fail(-1, "%lld samples: at most 2^31 - 1 per call", S);
+    if (int rc = sample_limit(src)) return rc;
     const long long M = (long long)std::ceil(std::min(0.2 * (double)S, 3.0 * std::sqrt((double)S / s.r_eff)));
     if (M > ELPD_TAIL_CAP)
         return fail(-1, "%lld samples with r_eff = %g need a PSIS tail of M = %lld > %d samples: select fewer samples (thin=, chains=) "
                         "or give a larger r_eff", S, s.r_eff, M, ELPD_TAIL_CAP);
     if (s.n_samples) *s.n_samples = S;
 
-    HIP_TRY(hipSetDevice(h->cfg.device_id));
-    if (int rc = finish_stream(h)) return rc;          // behind everything queued; a failed run is refused here
+    if (int rc = start_device(h)) return rc;
     hipStream_t st = h->stream;
     DeviceScratch mem;
     const int n_rows = s.n_rows;
@@ -2274,10 +2391,11 @@ int ptnn_elpd(ptnn_handle* h, const ptnn_elpd_spec* spec) {
     ra.O = O; ra.S = S; ra.M = (int)M;
     ra.lppd = d_lppd; ra.p_waic = d_pwaic; ra.elpd_loo = d_loo; ra.khat = d_khat; ra.tail_len = d_tail;
     auto copy_out = [&]() -> int {
-        const std::pair<double*, double*> outs[] = {{s.lppd, d_lppd}, {s.p_waic, d_pwaic}, {s.elpd_loo, d_loo}, {s.khat, d_khat}};
-        for (const auto& o : outs)
-            if (o.first) HIP_TRY(hipMemcpyAsync(o.first, o.second, (size_t)n_rows * sizeof(double), hipMemcpyDeviceToHost, st));
-        if (s.tail_len) HIP_TRY(hipMemcpyAsync(s.tail_len, d_tail, (size_t)n_rows * sizeof(long long), hipMemcpyDeviceToHost, st));
+        HIP_TRY(fetch(s.lppd, d_lppd, (size_t)n_rows, st));
+        HIP_TRY(fetch(s.p_waic, d_pwaic, (size_t)n_rows, st));
+        HIP_TRY(fetch(s.elpd_loo, d_loo, (size_t)n_rows, st));
+        HIP_TRY(fetch(s.khat, d_khat, (size_t)n_rows, st));
+        HIP_TRY(fetch((long long*)s.tail_len, d_tail, (size_t)n_rows, st));
         return wait_stream(h);
     };
 
@@ -2285,16 +2403,11 @@ int ptnn_elpd(ptnn_handle* h, const ptnn_elpd_spec* spec) {
         // source 3: every host sample is its own entry (repeats need no merging: the reduction depends on the multiset only)
         double* d_ll = nullptr;
         int* d_cnt = nullptr;
-        HIP_TRY(mem.alloc(&d_ll, (size_t)n_items * n_rows));
-        HIP_TRY(hipMemcpyAsync(d_ll, s.loglik, (size_t)n_items * n_rows * sizeof(double), hipMemcpyHostToDevice, st));
-        HIP_TRY(mem.alloc(&d_cnt, (size_t)n_items));
-        if (s.multiplicity) {
-            HIP_TRY(hipMemcpyAsync(d_cnt, s.multiplicity, (size_t)n_items * sizeof(int32_t), hipMemcpyHostToDevice, st));
-        } else {
-            std::vector<int32_t> ones((size_t)n_items, 1);
-            HIP_TRY(hipMemcpyAsync(d_cnt, ones.data(), ones.size() * sizeof(int32_t), hipMemcpyHostToDevice, st));
+        HIP_TRY(mem.upload(&d_ll, s.loglik, (size_t)n_items * n_rows, st));
+        std::vector<int32_t> ones(s.multiplicity ? 0 : (size_t)n_items, 1);
+        HIP_TRY(mem.upload(&d_cnt, s.multiplicity ? s.multiplicity : ones.data(), (size_t)n_items, st));
+        if (!s.multiplicity)
             if (int rc = wait_stream(h)) return rc;          // `ones` dies at the end of this block
-        }
         ra.mode = ELPD_HOST; ra.ll = d_ll; ra.ll_stride = n_rows; ra.cnt = d_cnt; ra.U = (int)n_items; ra.row0 = 0;
         hipLaunchKernelGGL(elpd_reduce_kernel, dim3((unsigned)n_rows), dim3(ELPD_THREADS), 0, st, ra);
         HIP_TRY(hipGetLastError());
@@ -2305,105 +2418,28 @@ int ptnn_elpd(ptnn_handle* h, const ptnn_elpd_spec* spec) {
     // data rows and targets
     const float* d_x = nullptr;
     int xs = 0;
-    if (s.x_source == PTNN_PREDICT_X_HOST) {
-        float* d = nullptr;
-        HIP_TRY(mem.alloc(&d, (size_t)n_rows * (I + 1)));
-        HIP_TRY(hipMemcpyAsync(d, s.x, (size_t)n_rows * (I + 1) * sizeof(float), hipMemcpyHostToDevice, st));
-        d_x = d; xs = I + 1;
-    } else {
-        d_x = h->d_data + (s.x_source == PTNN_PREDICT_X_TEST ? (size_t)h->Ntr * h->IPY : 0);
-        xs = h->IPY;
-    }
+    if (int rc = upload_rows(h, mem, rows, I + 1, &d_x, &xs)) return rc;
     // stage a: items -> distinct (w, eta) samples
-    long long *d_item_off = nullptr, *d_run_off = nullptr;
-    int *d_flag = nullptr, *d_item_run = nullptr, *d_run_cnt = nullptr, *d_nruns = nullptr, *d_weight = nullptr, *d_reps = nullptr;
-    float *d_w = nullptr, *d_item_eta = nullptr, *d_run_eta = nullptr, *d_heta = nullptr;
-    HIP_TRY(mem.alloc(&d_item_off, (size_t)n_items));
-    HIP_TRY(mem.alloc(&d_run_off, (size_t)n_items));
-    HIP_TRY(mem.alloc(&d_flag, (size_t)n_items));
-    HIP_TRY(mem.alloc(&d_item_run, (size_t)n_items));
-    HIP_TRY(mem.alloc(&d_run_cnt, (size_t)n_items));
-    HIP_TRY(mem.alloc(&d_item_eta, (size_t)n_items));
-    HIP_TRY(mem.alloc(&d_run_eta, (size_t)n_items));
-    HIP_TRY(mem.alloc(&d_nruns, 4));                     // [0] runs, [1] unresolved compact rows, [2] rows without eta, [3] first such chain
-    HIP_TRY(hipMemsetAsync(d_run_cnt, 0, (size_t)n_items * sizeof(int), st));
-    HIP_TRY(hipMemsetAsync(d_nruns, 0, 3 * sizeof(int), st));
-    HIP_TRY(hipMemsetAsync(d_nruns + 3, 0x7f, sizeof(int), st));
-    ElpdSel sel{};
-    sel.reg = reg ? 1 : 0; sel.P = P; sel.n_items = n_items; sel.item_off = d_item_off; sel.item_eta = d_item_eta; sel.flag = d_flag;
-    sel.error = d_nruns + 1;
-    const float* base = nullptr;
-    if (host_src) {
-        HIP_TRY(mem.alloc(&d_w, (size_t)n_items * P));
-        HIP_TRY(hipMemcpyAsync(d_w, s.w, (size_t)n_items * P * sizeof(float), hipMemcpyHostToDevice, st));
-        if (reg) {
-            HIP_TRY(mem.alloc(&d_heta, (size_t)n_items));
-            HIP_TRY(hipMemcpyAsync(d_heta, s.eta, (size_t)n_items * sizeof(float), hipMemcpyHostToDevice, st));
-        }
-        if (s.multiplicity) {
-            HIP_TRY(mem.alloc(&d_weight, (size_t)n_items));
-            HIP_TRY(hipMemcpyAsync(d_weight, s.multiplicity, (size_t)n_items * sizeof(int32_t), hipMemcpyHostToDevice, st));
-        }
-        sel.host = 1; sel.pos_w = d_w; sel.host_eta = d_heta;
-        base = d_w;
-    } else {
-        HIP_TRY(mem.alloc(&d_reps, reps.size()));
-        HIP_TRY(hipMemcpyAsync(d_reps, reps.data(), reps.size() * sizeof(int32_t), hipMemcpyHostToDevice, st));
-        sel.host = 0; sel.pos_w = h->d_pos_w; sel.scal = h->d_scal; sel.replicas = d_reps; sel.st_i = h->d_st_i; sel.cap = cap;
-        sel.PW = h->PW; sel.step0 = s.step0; sel.thin = s.thin; sel.m = m; sel.compact = h->plan.compact ? 1 : 0; sel.cur = h->cur;
-        base = h->d_pos_w;
-    }
-    const unsigned item_blocks = (unsigned)((n_items + ELPD_THREADS - 1) / ELPD_THREADS);
-    hipLaunchKernelGGL(elpd_runs_kernel, dim3(item_blocks), dim3(ELPD_THREADS), 0, st, sel);
-    HIP_TRY(hipGetLastError());
-    PredictScan sc{n_items, d_flag, d_item_off, d_weight, d_item_run, d_run_off, d_run_cnt, d_nruns};
-    hipLaunchKernelGGL(predict_scan_kernel, dim3(1), dim3(PRED_SCAN_THREADS), 0, st, sc);
-    HIP_TRY(hipGetLastError());
-    hipLaunchKernelGGL(elpd_run_eta_kernel, dim3(item_blocks), dim3(ELPD_THREADS), 0, st, n_items, (const int*)d_flag,
-                       (const int*)d_item_run, (const float*)d_item_eta, d_run_eta);
-    HIP_TRY(hipGetLastError());
-    int runs[4] = {0, 0, 0, 0};
-    HIP_TRY(hipMemcpyAsync(runs, d_nruns, sizeof runs, hipMemcpyDeviceToHost, st));
-    if (int rc = wait_stream(h)) return rc;
-    if (runs[1]) return fail(-2, "%d selected compact trace rows refer to rows that are not resident (internal error)", runs[1]);
-    if (runs[2]) {
-        const int c = runs[3] >= 0 && runs[3] < (int)reps.size() ? runs[3] : 0;
-        return fail(-1, "%d selected trace rows precede their chain's first accepted MH step (chain %d, local replica %d, among "
-                        "others): no eta = log tau^2 was recorded for them; start the selection later (a larger burn_in)",
-                    runs[2], c, reps.empty() ? 0 : reps[(size_t)c]);
-    }
-    const int U = runs[0];
-    if (U < 1 || U > n_items) return fail(-2, "run-length pass found %d distinct samples among %lld rows (internal error)", U, n_items);
+    Distinct d;
+    if (int rc = distinct_samples(h, mem, src, true, true, &d)) return rc;
+    const int U = d.U;
     if (s.n_distinct) *s.n_distinct = U;
     // stage b + c in blocks of rows: fx scratch U x (rows x O) floats (+ U x rows doubles for loglik_out) under the budget
-    const size_t budget = scratch_budget("PTNN_ELPD_SCRATCH_BYTES");
-    const size_t row_bytes = (size_t)U * (sizeof(float) * O + (s.loglik_out ? sizeof(double) : 0));
-    long long rows_blk = (long long)(budget / row_bytes);
-    rows_blk = std::min<long long>(rows_blk, 65535LL * WAVE);       // grid.y of the forward pass, as ptnn_predict
-    rows_blk = std::max(1LL, std::min<long long>(rows_blk, n_rows));
+    const long long rows_blk = row_block(scratch_budget("PTNN_ELPD_SCRATCH_BYTES"),
+                                         (size_t)U * (sizeof(float) * O + (s.loglik_out ? sizeof(double) : 0)), n_rows);
     float* d_fx = nullptr;
     double* d_llb = nullptr;
     HIP_TRY(mem.alloc(&d_fx, (size_t)rows_blk * O * U));
     if (s.loglik_out) HIP_TRY(mem.alloc(&d_llb, (size_t)rows_blk * U));
-    const int PV = round_up4(P);
-    const int per_vec = PV + (PRED_THREADS / WAVE + 1) * O * WAVE;     // as ptnn_predict: staged vector + partial sums + tile
-    const int NV = std::max(1, std::min(PRED_MAX_NV, (48 * 1024 / 4) / per_vec));
-    const size_t lds = (size_t)NV * per_vec * sizeof(float);
-    if (lds > 152 * 1024) return fail(-3, "predictive accuracy: a %d-parameter vector does not fit in LDS", P);
-    if (int rc = raise_lds_limit(reinterpret_cast<const void*>(h->shape->predict_fwd), lds)) return rc;
+    ForwardPlan fwd;
+    if (int rc = fwd.init(h, "predictive accuracy")) return rc;
     std::vector<int> item_run;
-    std::vector<double> ll_host;
-    if (s.loglik_out) {
-        item_run.resize((size_t)n_items);
-        HIP_TRY(hipMemcpyAsync(item_run.data(), d_item_run, (size_t)n_items * sizeof(int), hipMemcpyDeviceToHost, st));
-    }
-    ra.mode = reg ? ELPD_REG : ELPD_CLS; ra.fx = d_fx; ra.eta = d_run_eta; ra.y = d_x + I; ra.ys = xs; ra.cnt = d_run_cnt; ra.U = U;
+    if (s.loglik_out) if (int rc = item_runs(h, d, n_items, &item_run)) return rc;
+    ra.mode = reg ? ELPD_REG : ELPD_CLS; ra.fx = d_fx; ra.eta = d.run_eta; ra.y = d_x + I; ra.ys = xs; ra.cnt = d.run_cnt; ra.U = U;
     ra.ll_out = d_llb;
     for (long long r0 = 0; r0 < n_rows; r0 += rows_blk) {
         const int nr = (int)std::min<long long>(rows_blk, n_rows - r0);
-        PredictFwd fa{base, d_run_off, d_x, xs, (int)r0, nr, H, P, PV, U, NV, d_fx};
-        hipLaunchKernelGGL(h->shape->predict_fwd, dim3((unsigned)((U + NV - 1) / NV), (unsigned)((nr + WAVE - 1) / WAVE)), dim3(PRED_THREADS), lds, st, fa);
-        HIP_TRY(hipGetLastError());
+        if (int rc = fwd.launch(h, d.base, d.run_off, d_x, xs, (int)r0, nr, U, d_fx)) return rc;
         ra.row0 = (int)r0;
         hipLaunchKernelGGL(elpd_reduce_kernel, dim3((unsigned)nr), dim3(ELPD_THREADS), 0, st, ra);
         HIP_TRY(hipGetLastError());
@@ -2411,19 +2447,7 @@ int ptnn_elpd(ptnn_handle* h, const ptnn_elpd_spec* spec) {
             const long long n_ll = (long long)nr * U;
             hipLaunchKernelGGL(elpd_loglik_kernel, dim3((unsigned)((n_ll + ELPD_THREADS - 1) / ELPD_THREADS)), dim3(ELPD_THREADS), 0, st, ra, nr);
             HIP_TRY(hipGetLastError());
-            ll_host.resize((size_t)n_ll);
-            HIP_TRY(hipMemcpyAsync(ll_host.data(), d_llb, ll_host.size() * sizeof(double), hipMemcpyDeviceToHost, st));
-            if (int rc = wait_stream(h)) return rc;
-            // every selected sample gets its distinct sample's log-likelihood, in the order of the selection (chain-major)
-            long long out_row = 0;
-            for (long long i = 0; i < n_items; ++i) {
-                const int reps_i = (host_src && s.multiplicity) ? s.multiplicity[i] : 1;
-                const size_t u = (size_t)item_run[(size_t)i];
-                for (int k = 0; k < reps_i; ++k, ++out_row) {
-                    double* dst = s.loglik_out + (size_t)out_row * n_rows + r0;
-                    for (int c = 0; c < nr; ++c) dst[c] = ll_host[(size_t)c * U + u];
-                }
-            }
+            if (int rc = scatter_samples(h, (const double*)d_llb, nr, U, item_run, src.weights(), s.loglik_out, (size_t)n_rows, (size_t)r0)) return rc;
         }
     }
     return copy_out();
@@ -2432,185 +2456,62 @@ int ptnn_elpd(ptnn_handle* h, const ptnn_elpd_spec* spec) {
 // ---- recursive forecasts (ptnn_dev_forecast.hpp) ----
 int ptnn_forecast(ptnn_handle* h, const ptnn_forecast_spec* spec) {
     // argument checks first: none of them needs the handle or a device
-    if (!spec) return fail(-1, "null argument");
-    if (spec->struct_bytes != (int32_t)sizeof(ptnn_forecast_spec))
-        return fail(-1, "ptnn_forecast_spec.struct_bytes = %d, expected %d", spec->struct_bytes, (int)sizeof(ptnn_forecast_spec));
+    if (int rc = check_spec(spec, "ptnn_forecast_spec")) return rc;
     const ptnn_forecast_spec& s = *spec;
     const bool host_src = s.w != nullptr, noise = s.noise != 0;
-    if (host_src && s.n_w < 1) return fail(-1, "n_w = %lld host vectors: need at least one", (long long)s.n_w);
-    if (!host_src && s.thin < 1) return fail(-1, "thin = %d must be >= 1", s.thin);
-    if (!host_src && s.replicas && s.n_replicas < 1) return fail(-1, "n_replicas = %d with a replica list", s.n_replicas);
-    if (s.origin_source != PTNN_FORECAST_ORIGIN_HOST && s.origin_source != PTNN_FORECAST_ORIGIN_TRAIN &&
-        s.origin_source != PTNN_FORECAST_ORIGIN_TEST)
-        return fail(-1, "origin_source = %d is not PTNN_FORECAST_ORIGIN_HOST, _TRAIN or _TEST", s.origin_source);
-    if (s.origin_source == PTNN_FORECAST_ORIGIN_HOST && !s.origins) return fail(-1, "origin_source PTNN_FORECAST_ORIGIN_HOST needs origins");
+    SampleSource src = source_of(s, host_src, s.eta);
+    const RowSource rows{s.origin_source, s.origins, s.n_origins, "origin_source", "PTNN_FORECAST_ORIGIN", "origins", "n_origins"};
+    if (int rc = check_source(src, "vectors")) return rc;
+    if (int rc = check_rows(rows)) return rc;
     if (s.n_origins < 1) return fail(-1, "n_origins = %d must be >= 1", s.n_origins);
     if (s.horizon < 1) return fail(-1, "horizon = %d must be >= 1", s.horizon);
     const long long ncols = (long long)s.n_origins * s.horizon;
     if (ncols > 0x7fffffffLL) return fail(-1, "%d origins x horizon %d = %lld columns: at most 2^31 - 1 per call", s.n_origins, s.horizon, ncols);
-    if (s.n_ranks < 0 || s.n_ranks > PTNN_PREDICT_MAX_RANKS) return fail(-1, "n_ranks = %d outside [0, %d]", s.n_ranks, PTNN_PREDICT_MAX_RANKS);
-    if (s.n_ranks > 0 && !s.ranks) return fail(-1, "n_ranks = %d but ranks is NULL", s.n_ranks);
-    if (s.order_stats && s.n_ranks == 0) return fail(-1, "order_stats requested without ranks");
+    if (int rc = check_ranks(s.n_ranks, s.ranks, s.order_stats)) return rc;
     if (noise && host_src && !s.eta) return fail(-1, "noise: host vectors need eta = log tau^2 (one per vector)");
-    if (int rc = check_ready(h)) return rc;
-    if (h->comm.kind != COMM_NONE) return fail(-3, "ptnn_forecast serves one GPU: this handle has a communicator attached");
+    if (int rc = check_handle(h, "ptnn_forecast")) return rc;
     if (h->cfg.task != PTNN_TASK_REG || h->cfg.n_out != 1)
         return fail(-1, "forecasting needs a regression net with n_out == 1 (a one-step map of one series); this handle is a %s "
                         "net with n_out = %d", h->cfg.task == PTNN_TASK_REG ? "regression" : "classification", h->cfg.n_out);
-    const int I = h->cfg.n_in, H = h->cfg.n_hidden, P = h->P, cap = h->cap, hz = s.horizon;
-    if (s.origin_source == PTNN_FORECAST_ORIGIN_TRAIN && s.n_origins != h->Ntr)
-        return fail(-1, "n_origins = %d but the train set has %d rows", s.n_origins, h->Ntr);
-    if (s.origin_source == PTNN_FORECAST_ORIGIN_TEST && s.n_origins != h->Nte)
-        return fail(-1, "n_origins = %d but the test set has %d rows", s.n_origins, h->Nte);
-    // the selection
-    std::vector<int32_t> reps;
-    long long n_items = 0, M = 0;
-    int m = 0;
-    if (host_src) {
-        n_items = s.n_w;
-        if (s.multiplicity) {
-            for (int64_t k = 0; k < s.n_w; ++k) {
-                if (s.multiplicity[k] < 0) return fail(-1, "multiplicity[%lld] = %d is negative", (long long)k, s.multiplicity[k]);
-                M += s.multiplicity[k];
-            }
-        } else {
-            M = s.n_w;
-        }
-    } else {
-        if (int rc = select_trace_rows(h, s.replicas, s.n_replicas, s.step0, s.nsteps, s.thin, &reps, &m)) return rc;
-        n_items = (long long)reps.size() * m;
-        M = n_items;
-    }
+    const int I = h->cfg.n_in, P = h->P, hz = s.horizon;
+    if (int rc = fit_rows(h, rows)) return rc;
+    if (int rc = count_samples(h, src)) return rc;
+    const long long M = src.M;
     if (M < 1) return fail(-1, "the selection holds no sample");
-    if (M > 0x7fffffffLL || n_items > 0x7fffffffLL) return fail(-1, "%lld samples: at most 2^31 - 1 per call", M);
-    for (int k = 0; k < s.n_ranks; ++k)
-        if (s.ranks[k] < 0 || s.ranks[k] >= M) return fail(-1, "rank %lld outside [0, %lld)", (long long)s.ranks[k], M);
+    if (int rc = sample_limit(src)) return rc;
+    if (int rc = check_rank_values(s.n_ranks, s.ranks, M)) return rc;
     if (s.n_samples) *s.n_samples = M;
 
-    HIP_TRY(hipSetDevice(h->cfg.device_id));
-    if (int rc = finish_stream(h)) return rc;          // behind everything queued; a failed run is refused here
+    if (int rc = start_device(h)) return rc;
     hipStream_t st = h->stream;
     DeviceScratch mem;
     // origins
     const float* d_x = nullptr;
     int xs = 0;
-    if (s.origin_source == PTNN_FORECAST_ORIGIN_HOST) {
-        float* d = nullptr;
-        HIP_TRY(mem.alloc(&d, (size_t)s.n_origins * I));
-        HIP_TRY(hipMemcpyAsync(d, s.origins, (size_t)s.n_origins * I * sizeof(float), hipMemcpyHostToDevice, st));
-        d_x = d; xs = I;
-    } else {
-        d_x = h->d_data + (s.origin_source == PTNN_FORECAST_ORIGIN_TEST ? (size_t)h->Ntr * h->IPY : 0);
-        xs = h->IPY;
-    }
-    // stage a: items -> trajectories (noise off: distinct vectors; noise on: every occurrence)
-    long long* d_item_off = nullptr; long long* d_run_off = nullptr; long long* d_ranks = nullptr;
-    int *d_flag = nullptr, *d_item_run = nullptr, *d_cnt = nullptr, *d_nruns = nullptr, *d_weight = nullptr, *d_reps = nullptr;
-    float *d_w = nullptr, *d_heta = nullptr, *d_eta = nullptr;
-    const float* base = nullptr;
-    int U = 0;
-    if (!noise) {
-        HIP_TRY(mem.alloc(&d_item_off, (size_t)n_items));
-        HIP_TRY(mem.alloc(&d_run_off, (size_t)n_items));
-        HIP_TRY(mem.alloc(&d_flag, (size_t)n_items));
-        HIP_TRY(mem.alloc(&d_item_run, (size_t)n_items));
-        HIP_TRY(mem.alloc(&d_cnt, (size_t)n_items));
-        HIP_TRY(mem.alloc(&d_nruns, 2));                 // [0] runs, [1] error count of the compact-row resolution
-        HIP_TRY(hipMemsetAsync(d_cnt, 0, (size_t)n_items * sizeof(int), st));
-        HIP_TRY(hipMemsetAsync(d_nruns, 0, 2 * sizeof(int), st));
-        PredictSel sel{};
-        sel.P = P; sel.n_items = n_items; sel.item_off = d_item_off; sel.flag = d_flag; sel.error = d_nruns + 1;
-        if (host_src) {
-            HIP_TRY(mem.alloc(&d_w, (size_t)n_items * P));
-            HIP_TRY(hipMemcpyAsync(d_w, s.w, (size_t)n_items * P * sizeof(float), hipMemcpyHostToDevice, st));
-            if (s.multiplicity) {
-                HIP_TRY(mem.alloc(&d_weight, (size_t)n_items));
-                HIP_TRY(hipMemcpyAsync(d_weight, s.multiplicity, (size_t)n_items * sizeof(int32_t), hipMemcpyHostToDevice, st));
+    if (int rc = upload_rows(h, mem, rows, I, &d_x, &xs)) return rc;
+    // stage a: items -> trajectories (noise off: distinct vectors; noise on: every occurrence, host multiplicities expanded)
+    std::vector<float> w_exp, eta_exp;
+    if (noise && host_src && s.multiplicity) {
+        w_exp.reserve((size_t)M * P);
+        eta_exp.reserve((size_t)M);
+        for (int64_t k = 0; k < s.n_w; ++k)
+            for (int c = 0; c < s.multiplicity[k]; ++c) {
+                w_exp.insert(w_exp.end(), s.w + (size_t)k * P, s.w + (size_t)(k + 1) * P);
+                eta_exp.push_back(s.eta[k]);
             }
-            sel.host = 1; sel.pos_w = d_w;
-            base = d_w;
-        } else {
-            HIP_TRY(mem.alloc(&d_reps, reps.size()));
-            HIP_TRY(hipMemcpyAsync(d_reps, reps.data(), reps.size() * sizeof(int32_t), hipMemcpyHostToDevice, st));
-            sel.host = 0; sel.pos_w = h->d_pos_w; sel.scal = h->d_scal; sel.replicas = d_reps; sel.cap = cap; sel.PW = h->PW;
-            sel.step0 = s.step0; sel.thin = s.thin; sel.m = m; sel.compact = h->plan.compact ? 1 : 0;
-            base = h->d_pos_w;
-        }
-        hipLaunchKernelGGL(predict_runs_kernel, dim3((unsigned)((n_items + PRED_THREADS - 1) / PRED_THREADS)), dim3(PRED_THREADS), 0, st, sel);
-        HIP_TRY(hipGetLastError());
-        PredictScan sc{n_items, d_flag, d_item_off, d_weight, d_item_run, d_run_off, d_cnt, d_nruns};
-        hipLaunchKernelGGL(predict_scan_kernel, dim3(1), dim3(PRED_SCAN_THREADS), 0, st, sc);
-        HIP_TRY(hipGetLastError());
-        int runs[2] = {0, 0};
-        HIP_TRY(hipMemcpyAsync(runs, d_nruns, sizeof runs, hipMemcpyDeviceToHost, st));
-        if (int rc = wait_stream(h)) return rc;
-        if (runs[1]) return fail(-2, "%d selected compact trace rows refer to rows that are not resident (internal error)", runs[1]);
-        U = runs[0];
-        if (U < 1 || U > n_items) return fail(-2, "run-length pass found %d distinct vectors among %lld rows (internal error)", U, n_items);
-    } else {
-        // host multiplicities are expanded: occurrence i is trajectory i
-        std::vector<float> w_exp, eta_exp;
-        const float* hw = s.w;
-        const float* he = s.eta;
-        if (host_src && s.multiplicity) {
-            w_exp.reserve((size_t)M * P);
-            eta_exp.reserve((size_t)M);
-            for (int64_t k = 0; k < s.n_w; ++k)
-                for (int c = 0; c < s.multiplicity[k]; ++c) {
-                    w_exp.insert(w_exp.end(), s.w + (size_t)k * P, s.w + (size_t)(k + 1) * P);
-                    eta_exp.push_back(s.eta[k]);
-                }
-            hw = w_exp.data(); he = eta_exp.data();
-            n_items = M;
-        }
-        HIP_TRY(mem.alloc(&d_item_off, (size_t)n_items));
-        HIP_TRY(mem.alloc(&d_eta, (size_t)n_items));
-        HIP_TRY(mem.alloc(&d_flag, (size_t)n_items));
-        HIP_TRY(mem.alloc(&d_cnt, (size_t)n_items));
-        HIP_TRY(mem.alloc(&d_nruns, 3));                 // [0] unresolved compact rows, [1] rows without eta, [2] first such chain
-        HIP_TRY(hipMemsetD32Async(d_cnt, 1, (size_t)n_items, st));
-        HIP_TRY(hipMemsetAsync(d_nruns, 0, 2 * sizeof(int), st));
-        HIP_TRY(hipMemsetAsync(d_nruns + 2, 0x7f, sizeof(int), st));
-        ElpdSel sel{};
-        sel.reg = 1; sel.P = P; sel.n_items = n_items; sel.item_off = d_item_off; sel.item_eta = d_eta; sel.flag = d_flag;
-        sel.error = d_nruns;
-        if (host_src) {
-            HIP_TRY(mem.alloc(&d_w, (size_t)n_items * P));
-            HIP_TRY(hipMemcpyAsync(d_w, hw, (size_t)n_items * P * sizeof(float), hipMemcpyHostToDevice, st));
-            HIP_TRY(mem.alloc(&d_heta, (size_t)n_items));
-            HIP_TRY(hipMemcpyAsync(d_heta, he, (size_t)n_items * sizeof(float), hipMemcpyHostToDevice, st));
-            sel.host = 1; sel.pos_w = d_w; sel.host_eta = d_heta;
-            base = d_w;
-        } else {
-            HIP_TRY(mem.alloc(&d_reps, reps.size()));
-            HIP_TRY(hipMemcpyAsync(d_reps, reps.data(), reps.size() * sizeof(int32_t), hipMemcpyHostToDevice, st));
-            sel.host = 0; sel.pos_w = h->d_pos_w; sel.scal = h->d_scal; sel.replicas = d_reps; sel.st_i = h->d_st_i; sel.cap = cap;
-            sel.PW = h->PW; sel.step0 = s.step0; sel.thin = s.thin; sel.m = m; sel.compact = h->plan.compact ? 1 : 0; sel.cur = h->cur;
-            base = h->d_pos_w;
-        }
-        hipLaunchKernelGGL(elpd_runs_kernel, dim3((unsigned)((n_items + ELPD_THREADS - 1) / ELPD_THREADS)), dim3(ELPD_THREADS), 0, st, sel);
-        HIP_TRY(hipGetLastError());
-        int err[3] = {0, 0, 0};
-        HIP_TRY(hipMemcpyAsync(err, d_nruns, sizeof err, hipMemcpyDeviceToHost, st));
-        if (int rc = wait_stream(h)) return rc;          // also keeps w_exp / eta_exp alive until the copies are done
-        if (err[0]) return fail(-2, "%d selected compact trace rows refer to rows that are not resident (internal error)", err[0]);
-        if (err[1]) {
-            const int c = err[2] >= 0 && err[2] < (int)reps.size() ? err[2] : 0;
-            return fail(-1, "noise: %d selected trace rows precede their chain's first accepted MH step (chain %d, local replica %d, "
-                            "among others): no eta = log tau^2 was recorded for them; start the selection later (a larger burn_in)",
-                        err[1], c, reps.empty() ? 0 : reps[(size_t)c]);
-        }
-        d_run_off = d_item_off;
-        U = (int)n_items;
+        src.w = w_exp.data(); src.eta = eta_exp.data(); src.multiplicity = nullptr;
+        src.n_items = M;
     }
+    Distinct d;
+    if (int rc = distinct_samples(h, mem, src, noise, !noise, &d)) return rc;
+    const int U = d.U;
     if (s.n_trajectories) *s.n_trajectories = U;
     // outputs on the device for every column
-    double* d_mean = nullptr; float* d_ostat = nullptr;
+    double* d_mean = nullptr; float* d_ostat = nullptr; long long* d_ranks = nullptr;
     HIP_TRY(mem.alloc(&d_mean, (size_t)ncols));
     if (s.n_ranks) {
         HIP_TRY(mem.alloc(&d_ostat, (size_t)s.n_ranks * ncols));
-        HIP_TRY(mem.alloc(&d_ranks, (size_t)s.n_ranks));
-        HIP_TRY(hipMemcpyAsync(d_ranks, s.ranks, (size_t)s.n_ranks * sizeof(int64_t), hipMemcpyHostToDevice, st));
+        HIP_TRY(mem.upload(&d_ranks, (const long long*)s.ranks, (size_t)s.n_ranks, st));
     }
     // stage b + c in blocks of origins and horizon steps: fx 4 U ob hb bytes, + 4 U I bytes of carried windows when the horizon
     // is split (only with one origin per block: the columns of a block are then always contiguous)
@@ -2635,26 +2536,11 @@ int ptnn_forecast(ptnn_handle* h, const ptnn_forecast_spec* spec) {
     if (lds > 152 * 1024) return fail(-3, "forecast: a %d-parameter vector does not fit in LDS", P);
     if (int rc = raise_lds_limit(reinterpret_cast<const void*>(h->shape->forecast_fwd), lds)) return rc;
     // samples: the trajectory of every selected row, chain-major
-    std::vector<int> row_traj;
-    std::vector<float> fx_host;
-    if (s.samples) {
-        row_traj.resize((size_t)M);
-        if (noise) {
-            for (long long i = 0; i < M; ++i) row_traj[(size_t)i] = (int)i;
-        } else {
-            std::vector<int> item_run((size_t)n_items);
-            HIP_TRY(hipMemcpyAsync(item_run.data(), d_item_run, (size_t)n_items * sizeof(int), hipMemcpyDeviceToHost, st));
-            if (int rc = wait_stream(h)) return rc;
-            long long row = 0;
-            for (long long i = 0; i < n_items; ++i) {
-                const int reps_i = (host_src && s.multiplicity) ? s.multiplicity[i] : 1;
-                for (int k = 0; k < reps_i; ++k) row_traj[(size_t)row++] = item_run[(size_t)i];
-            }
-        }
-    }
+    std::vector<int> item_run;
+    if (s.samples) if (int rc = item_runs(h, d, src.n_items, &item_run)) return rc;
     ForecastFwd fa{};
-    fa.base = base; fa.run_off = d_run_off; fa.eta = noise ? d_eta : nullptr; fa.x = d_x; fa.xs = xs; fa.horizon = hz; fa.win = d_win;
-    fa.H = H; fa.P = P; fa.U = U; fa.layout = layout; fa.noise = noise ? 1 : 0;
+    fa.base = d.base; fa.run_off = d.run_off; fa.eta = d.run_eta; fa.x = d_x; fa.xs = xs; fa.horizon = hz; fa.win = d_win;
+    fa.H = h->cfg.n_hidden; fa.P = P; fa.U = U; fa.layout = layout; fa.noise = noise ? 1 : 0;
     fa.seed_lo = (uint32_t)(s.seed & 0xffffffffu); fa.seed_hi = (uint32_t)(s.seed >> 32); fa.fx = d_fx;
     for (long long r0 = 0; r0 < s.n_origins; r0 += ob) {
         const int nr = (int)std::min<long long>(ob, s.n_origins - r0);
@@ -2671,26 +2557,15 @@ int ptnn_forecast(ptnn_handle* h, const ptnn_forecast_spec* spec) {
             hipLaunchKernelGGL(h->shape->forecast_fwd, grid, dim3(FC_THREADS), lds, st, fa);
             HIP_TRY(hipGetLastError());
             const long long col0 = r0 * hz + k0;             // the block's columns are contiguous (see above)
-            PredictRed ra{d_fx, d_cnt, U, 1, (int)col0, (int)ncols, M, s.n_ranks, d_ranks, d_mean, d_ostat, nullptr};
+            PredictRed ra{d_fx, d.run_cnt, U, 1, (int)col0, (int)ncols, M, s.n_ranks, d_ranks, d_mean, d_ostat, nullptr};
             hipLaunchKernelGGL(predict_reduce_kernel, dim3((unsigned)(nr * nk)), dim3(PRED_THREADS), 0, st, ra);
             HIP_TRY(hipGetLastError());
-            if (s.samples) {
-                fx_host.resize((size_t)nr * nk * U);
-                HIP_TRY(hipMemcpyAsync(fx_host.data(), d_fx, fx_host.size() * sizeof(float), hipMemcpyDeviceToHost, st));
-                if (int rc = wait_stream(h)) return rc;
-                for (long long row = 0; row < M; ++row) {
-                    const size_t u = (size_t)row_traj[(size_t)row];
-                    for (int rl = 0; rl < nr; ++rl) {
-                        float* dst = s.samples + ((size_t)row * s.n_origins + r0 + rl) * hz + k0;
-                        const float* src = fx_host.data() + (size_t)rl * nk * U + u;
-                        for (int k = 0; k < nk; ++k) dst[k] = src[(size_t)k * U];
-                    }
-                }
-            }
+            if (s.samples)
+                if (int rc = scatter_samples(h, d_fx, nr * nk, U, item_run, src.weights(), s.samples, (size_t)ncols, (size_t)col0)) return rc;
         }
     }
-    if (s.mean) HIP_TRY(hipMemcpyAsync(s.mean, d_mean, (size_t)ncols * sizeof(double), hipMemcpyDeviceToHost, st));
-    if (s.order_stats) HIP_TRY(hipMemcpyAsync(s.order_stats, d_ostat, (size_t)s.n_ranks * ncols * sizeof(float), hipMemcpyDeviceToHost, st));
+    HIP_TRY(fetch(s.mean, d_mean, (size_t)ncols, st));
+    HIP_TRY(fetch(s.order_stats, d_ostat, (size_t)s.n_ranks * ncols, st));
     return wait_stream(h);
 }
 
@@ -2699,19 +2574,18 @@ static_assert(PTNN_EVIDENCE_MAX_A == EVID_MAX_A, "ptnn.h prior exponents");
 
 int ptnn_evidence(ptnn_handle* h, const ptnn_evidence_spec* spec) {
     // argument checks first: none of them needs the handle or a device
-    if (!spec) return fail(-1, "null argument");
-    if (spec->struct_bytes != (int32_t)sizeof(ptnn_evidence_spec))
-        return fail(-1, "ptnn_evidence_spec.struct_bytes = %d, expected %d", spec->struct_bytes, (int)sizeof(ptnn_evidence_spec));
+    if (int rc = check_spec(spec, "ptnn_evidence_spec")) return rc;
     const ptnn_evidence_spec& s = *spec;
     const bool u_src = s.u != nullptr, host_src = s.w != nullptr;
+    // host vectors [K][n][P] as one list of K n items (their [K, n] multiplicities are applied to U, below), or one rung per chain
+    SampleSource src{host_src, s.w, nullptr, (int64_t)s.n_rungs * s.n_per_rung, nullptr, s.replicas, s.n_replicas, s.step0, s.nsteps, s.thin};
     if (u_src && host_src) return fail(-1, "give host vectors w or a host U, not both");
     if (u_src || host_src) {
         if (s.n_rungs < 1) return fail(-1, "n_rungs = %d must be >= 1", s.n_rungs);
         if (s.n_per_rung < 1) return fail(-1, "n_per_rung = %lld must be >= 1", (long long)s.n_per_rung);
     } else {
         if (s.nsteps < 1) return fail(-1, "no source: nsteps = %d trace rows, and neither host vectors w nor a host U", s.nsteps);
-        if (s.thin < 1) return fail(-1, "thin = %d must be >= 1", s.thin);
-        if (s.replicas && s.n_replicas < 1) return fail(-1, "n_replicas = %d with a replica list", s.n_replicas);
+        if (int rc = check_source(src, "vectors")) return rc;
     }
     if (s.n_prior < 0) return fail(-1, "n_prior = %lld must be >= 0", (long long)s.n_prior);
     if (s.n_prior > 0x7fffffffLL) return fail(-1, "n_prior = %lld: at most 2^31 - 1 prior draws per call", (long long)s.n_prior);
@@ -2724,13 +2598,12 @@ int ptnn_evidence(ptnn_handle* h, const ptnn_evidence_spec* spec) {
     if (u_src && s.u_out) return fail(-1, "u_out: U is the input of this source");
     if (u_src && s.n_distinct) *s.n_distinct = 0;
     // host sources: items, their multiplicities, the draws of every rung
-    long long n_items = 0;
     std::vector<long long> off;                        // [K + 1] expanded draws of rung k at [off[k], off[k + 1])
     std::vector<int32_t> item_of;                      // expanded draw -> item (multiplicities only)
     if (u_src || host_src) {
         const long long K = s.n_rungs, n = s.n_per_rung;
         if (K * n > 0x7fffffffLL) return fail(-1, "%lld host rows: at most 2^31 - 1 per call", K * n);
-        n_items = K * n;
+        src.n_items = K * n;
         off.assign((size_t)K + 1, 0);
         for (long long k = 0; k < K; ++k) {
             long long c = 0;
@@ -2746,20 +2619,17 @@ int ptnn_evidence(ptnn_handle* h, const ptnn_evidence_spec* spec) {
             if (off[(size_t)k + 1] > 0x7fffffffLL) return fail(-1, "more than 2^31 - 1 expanded draws");
         }
     }
-    if (int rc = check_ready(h)) return rc;
-    if (h->comm.kind != COMM_NONE) return fail(-3, "ptnn_evidence serves one GPU: this handle has a communicator attached");
-    const int I = h->cfg.n_in, H = h->cfg.n_hidden, O = h->cfg.n_out, P = h->P, N = h->Ntr;
+    if (int rc = check_handle(h, "ptnn_evidence")) return rc;
+    const int I = h->cfg.n_in, O = h->cfg.n_out, P = h->P, N = h->Ntr;
     const bool reg = h->cfg.task == PTNN_TASK_REG;
     // the trace selection: one rung per chain
-    std::vector<int32_t> reps;
-    int m = 0;
     if (!u_src && !host_src) {
-        if (int rc = select_trace_rows(h, s.replicas, s.n_replicas, s.step0, s.nsteps, s.thin, &reps, &m)) return rc;
-        n_items = (long long)reps.size() * m;
-        if (n_items > 0x7fffffffLL) return fail(-1, "%lld trace rows: at most 2^31 - 1 per call", n_items);
-        off.assign(reps.size() + 1, 0);
-        for (size_t k = 0; k < reps.size(); ++k) off[k + 1] = off[k] + m;
+        if (int rc = count_samples(h, src)) return rc;
+        if (src.n_items > 0x7fffffffLL) return fail(-1, "%lld trace rows: at most 2^31 - 1 per call", src.n_items);
+        off.assign(src.reps.size() + 1, 0);
+        for (size_t k = 0; k < src.reps.size(); ++k) off[k + 1] = off[k] + src.m;
     }
+    const long long n_items = src.n_items;
     const int K = (int)off.size() - 1;
     for (int k = 0; k < K; ++k)
         if (off[(size_t)k + 1] - off[(size_t)k] < 4)
@@ -2771,23 +2641,18 @@ int ptnn_evidence(ptnn_handle* h, const ptnn_evidence_spec* spec) {
     if (s.n_draws)
         for (int k = 0; k < K; ++k) s.n_draws[k] = off[(size_t)k + 1] - off[(size_t)k];
 
-    HIP_TRY(hipSetDevice(h->cfg.device_id));
-    if (int rc = finish_stream(h)) return rc;          // behind everything queued; a failed run is refused here
+    if (int rc = start_device(h)) return rc;
     hipStream_t st = h->stream;
     DeviceScratch mem;
     const size_t budget = scratch_budget("PTNN_EVIDENCE_SCRATCH_BYTES");
     // the forward pass of predict_fwd on the training rows
-    const int PV = round_up4(P);
-    const int per_vec = PV + (PRED_THREADS / WAVE + 1) * O * WAVE;     // as ptnn_predict: staged vector + partial sums + tile
-    const int NV = std::max(1, std::min(PRED_MAX_NV, (48 * 1024 / 4) / per_vec));
-    const size_t lds = (size_t)NV * per_vec * sizeof(float);
-    if (lds > 152 * 1024) return fail(-3, "log evidence: a %d-parameter vector does not fit in LDS", P);
-    if (int rc = raise_lds_limit(reinterpret_cast<const void*>(h->shape->predict_fwd), lds)) return rc;
+    ForwardPlan fwd;
+    if (int rc = fwd.init(h, "log evidence")) return rc;
     const float* d_x = h->d_data;                      // training rows
     const int xs = h->IPY;
-    int* d_err = nullptr;                              // [0] SSE = 0, [1] unresolved compact rows, [2], [3] (elpd_runs_kernel)
-    HIP_TRY(mem.alloc(&d_err, 4));
-    HIP_TRY(hipMemsetAsync(d_err, 0, 4 * sizeof(int), st));
+    int* d_sse0 = nullptr;                             // weight vectors with SSE = 0 (evid_finish_kernel)
+    HIP_TRY(mem.alloc(&d_sse0, 1));
+    HIP_TRY(hipMemsetAsync(d_sse0, 0, sizeof(int), st));
     // U (and b) of `nv` vectors at base + run_off[u]: rows in blocks of rows_blk, fx scratch `fx` of rows_blk x O x nv floats
     auto eval_u = [&](const float* base, const long long* run_off, int nv, long long rows_blk, float* fx, double* acc, double* u_out,
                       double* b_out) -> int {
@@ -2795,28 +2660,21 @@ int ptnn_evidence(ptnn_handle* h, const ptnn_evidence_spec* spec) {
         const unsigned ub = (unsigned)((nv + EVID_THREADS - 1) / EVID_THREADS);
         for (long long r0 = 0; r0 < N; r0 += rows_blk) {
             const int nr = (int)std::min<long long>(rows_blk, N - r0);
-            PredictFwd fa{base, run_off, d_x, xs, (int)r0, nr, H, P, PV, nv, NV, fx};
-            hipLaunchKernelGGL(h->shape->predict_fwd, dim3((unsigned)((nv + NV - 1) / NV), (unsigned)((nr + WAVE - 1) / WAVE)), dim3(PRED_THREADS), lds, st, fa);
-            HIP_TRY(hipGetLastError());
+            if (int rc = fwd.launch(h, base, run_off, d_x, xs, (int)r0, nr, nv, fx)) return rc;
             EvidRows ra{fx, d_x + (size_t)r0 * xs + I, xs, nr, O, nv, reg ? 1 : 0, acc};
             hipLaunchKernelGGL(evid_rows_kernel, dim3(ub), dim3(EVID_THREADS), 0, st, ra);
             HIP_TRY(hipGetLastError());
         }
-        hipLaunchKernelGGL(evid_finish_kernel, dim3(ub), dim3(EVID_THREADS), 0, st, nv, reg ? 1 : 0, N, (const double*)acc, u_out, b_out, d_err);
+        hipLaunchKernelGGL(evid_finish_kernel, dim3(ub), dim3(EVID_THREADS), 0, st, nv, reg ? 1 : 0, N, (const double*)acc, u_out, b_out, d_sse0);
         HIP_TRY(hipGetLastError());
         return 0;
     };
-    const long long row_cap = 65535LL * WAVE;          // grid.y of the forward pass, as ptnn_predict
-    auto rows_for = [&](long long nv, size_t avail) -> long long {
-        const long long r = (long long)(avail / ((size_t)nv * O * sizeof(float)));
-        return std::max(1LL, std::min<long long>({r, (long long)N, row_cap}));
-    };
+    auto rows_for = [&](long long nv, size_t avail) { return row_block(avail, (size_t)nv * O * sizeof(float), N); };
     auto sse_check = [&]() -> int {
-        int e[4] = {0, 0, 0, 0};
-        HIP_TRY(hipMemcpyAsync(e, d_err, sizeof e, hipMemcpyDeviceToHost, st));
+        int e = 0;
+        HIP_TRY(hipMemcpyAsync(&e, d_sse0, sizeof e, hipMemcpyDeviceToHost, st));
         if (int rc = wait_stream(h)) return rc;
-        if (e[0]) return fail(-1, "%d weight vectors fit the %d training rows exactly (SSE = 0): U = -(N / 2) log SSE is infinite", e[0], N);
-        if (e[1]) return fail(-2, "%d selected compact trace rows refer to rows that are not resident (internal error)", e[1]);
+        if (e) return fail(-1, "%d weight vectors fit the %d training rows exactly (SSE = 0): U = -(N / 2) log SSE is infinite", e, N);
         return 0;
     };
 
@@ -2824,58 +2682,19 @@ int ptnn_evidence(ptnn_handle* h, const ptnn_evidence_spec* spec) {
     double* d_udraw = nullptr;
     if (K > 0) HIP_TRY(mem.alloc(&d_udraw, (size_t)n_draws));
     int* d_item_of = nullptr;
-    if (!item_of.empty()) {
-        HIP_TRY(mem.alloc(&d_item_of, item_of.size()));
-        HIP_TRY(hipMemcpyAsync(d_item_of, item_of.data(), item_of.size() * sizeof(int32_t), hipMemcpyHostToDevice, st));
-    }
+    if (!item_of.empty()) HIP_TRY(mem.upload(&d_item_of, item_of.data(), item_of.size(), st));
     const unsigned draw_blocks = (unsigned)((n_draws + EVID_THREADS - 1) / EVID_THREADS);
     if (u_src) {
         double* d_u = nullptr;
-        HIP_TRY(mem.alloc(&d_u, (size_t)n_items));
-        HIP_TRY(hipMemcpyAsync(d_u, s.u, (size_t)n_items * sizeof(double), hipMemcpyHostToDevice, st));
+        HIP_TRY(mem.upload(&d_u, s.u, (size_t)n_items, st));
         hipLaunchKernelGGL(evid_expand_kernel, dim3(draw_blocks), dim3(EVID_THREADS), 0, st, n_draws, (const int*)d_item_of,
                            (const int*)nullptr, (const double*)d_u, d_udraw);
         HIP_TRY(hipGetLastError());
     } else {
         // stage a: items -> distinct vectors
-        long long *d_item_off = nullptr, *d_run_off = nullptr;
-        int *d_flag = nullptr, *d_item_run = nullptr, *d_run_cnt = nullptr, *d_nruns = nullptr, *d_reps = nullptr;
-        float *d_w = nullptr, *d_item_eta = nullptr;
-        HIP_TRY(mem.alloc(&d_item_off, (size_t)n_items));
-        HIP_TRY(mem.alloc(&d_run_off, (size_t)n_items));
-        HIP_TRY(mem.alloc(&d_flag, (size_t)n_items));
-        HIP_TRY(mem.alloc(&d_item_run, (size_t)n_items));
-        HIP_TRY(mem.alloc(&d_run_cnt, (size_t)n_items));
-        HIP_TRY(mem.alloc(&d_item_eta, (size_t)n_items));
-        HIP_TRY(mem.alloc(&d_nruns, 1));
-        HIP_TRY(hipMemsetAsync(d_run_cnt, 0, (size_t)n_items * sizeof(int), st));
-        HIP_TRY(hipMemsetAsync(d_nruns, 0, sizeof(int), st));
-        ElpdSel sel{};
-        sel.reg = 0; sel.P = P; sel.n_items = n_items; sel.item_off = d_item_off; sel.item_eta = d_item_eta; sel.flag = d_flag;
-        sel.error = d_err + 1;
-        const float* base = nullptr;
-        if (host_src) {
-            HIP_TRY(mem.alloc(&d_w, (size_t)n_items * P));
-            HIP_TRY(hipMemcpyAsync(d_w, s.w, (size_t)n_items * P * sizeof(float), hipMemcpyHostToDevice, st));
-            sel.host = 1; sel.pos_w = d_w;
-            base = d_w;
-        } else {
-            HIP_TRY(mem.alloc(&d_reps, reps.size()));
-            HIP_TRY(hipMemcpyAsync(d_reps, reps.data(), reps.size() * sizeof(int32_t), hipMemcpyHostToDevice, st));
-            sel.host = 0; sel.pos_w = h->d_pos_w; sel.scal = h->d_scal; sel.replicas = d_reps; sel.st_i = h->d_st_i; sel.cap = h->cap;
-            sel.PW = h->PW; sel.step0 = s.step0; sel.thin = s.thin; sel.m = m; sel.compact = h->plan.compact ? 1 : 0; sel.cur = h->cur;
-            base = h->d_pos_w;
-        }
-        const unsigned item_blocks = (unsigned)((n_items + ELPD_THREADS - 1) / ELPD_THREADS);
-        hipLaunchKernelGGL(elpd_runs_kernel, dim3(item_blocks), dim3(ELPD_THREADS), 0, st, sel);
-        HIP_TRY(hipGetLastError());
-        PredictScan sc{n_items, d_flag, d_item_off, nullptr, d_item_run, d_run_off, d_run_cnt, d_nruns};
-        hipLaunchKernelGGL(predict_scan_kernel, dim3(1), dim3(PRED_SCAN_THREADS), 0, st, sc);
-        HIP_TRY(hipGetLastError());
-        int U = 0;
-        HIP_TRY(hipMemcpyAsync(&U, d_nruns, sizeof(int), hipMemcpyDeviceToHost, st));
-        if (int rc = wait_stream(h)) return rc;
-        if (U < 1 || U > n_items) return fail(-2, "run-length pass found %d distinct vectors among %lld rows (internal error)", U, n_items);
+        Distinct d;
+        if (int rc = distinct_samples(h, mem, src, false, true, &d)) return rc;
+        const int U = d.U;
         if (s.n_distinct) *s.n_distinct = U;
         // stages b, c: U of every distinct vector, rows in blocks under the budget
         const long long rows_blk = rows_for(U, budget);
@@ -2884,33 +2703,31 @@ int ptnn_evidence(ptnn_handle* h, const ptnn_evidence_spec* spec) {
         HIP_TRY(mem.alloc(&d_fx, (size_t)rows_blk * O * U));
         HIP_TRY(mem.alloc(&d_acc, (size_t)U));
         HIP_TRY(mem.alloc(&d_udist, (size_t)U));
-        if (int rc = eval_u(base, d_run_off, U, rows_blk, d_fx, d_acc, d_udist, nullptr)) return rc;
+        if (int rc = eval_u(d.base, d.run_off, U, rows_blk, d_fx, d_acc, d_udist, nullptr)) return rc;
         hipLaunchKernelGGL(evid_expand_kernel, dim3(draw_blocks), dim3(EVID_THREADS), 0, st, n_draws, (const int*)d_item_of,
-                           (const int*)d_item_run, (const double*)d_udist, d_udraw);
+                           (const int*)d.item_run, (const double*)d_udist, d_udraw);
         HIP_TRY(hipGetLastError());
         if (int rc = sse_check()) return rc;
     }
     // stage d: per-rung moments and stones
     long long* d_off = nullptr;
     double *d_mean = nullptr, *d_var = nullptr, *d_d = nullptr, *d_ls = nullptr, *d_rv = nullptr;
-    HIP_TRY(mem.alloc(&d_off, off.size()));
-    HIP_TRY(hipMemcpyAsync(d_off, off.data(), off.size() * sizeof(long long), hipMemcpyHostToDevice, st));
+    HIP_TRY(mem.upload(&d_off, off.data(), off.size(), st));
     HIP_TRY(mem.alloc(&d_mean, (size_t)K));
     HIP_TRY(mem.alloc(&d_var, (size_t)K));
     if (s.d) {
-        HIP_TRY(mem.alloc(&d_d, (size_t)K));
-        HIP_TRY(hipMemcpyAsync(d_d, s.d, (size_t)K * sizeof(double), hipMemcpyHostToDevice, st));
+        HIP_TRY(mem.upload(&d_d, s.d, (size_t)K, st));
         HIP_TRY(mem.alloc(&d_ls, (size_t)K));
         HIP_TRY(mem.alloc(&d_rv, (size_t)K));
     }
     EvidRung rg{d_udraw, d_off, d_d, d_mean, d_var, d_ls, d_rv};
     hipLaunchKernelGGL(evid_rung_kernel, dim3((unsigned)K), dim3(EVID_THREADS), 0, st, rg);
     HIP_TRY(hipGetLastError());
-    if (s.u_mean) HIP_TRY(hipMemcpyAsync(s.u_mean, d_mean, (size_t)K * sizeof(double), hipMemcpyDeviceToHost, st));
-    if (s.u_var) HIP_TRY(hipMemcpyAsync(s.u_var, d_var, (size_t)K * sizeof(double), hipMemcpyDeviceToHost, st));
-    if (s.d && s.log_stone) HIP_TRY(hipMemcpyAsync(s.log_stone, d_ls, (size_t)K * sizeof(double), hipMemcpyDeviceToHost, st));
-    if (s.d && s.stone_relvar) HIP_TRY(hipMemcpyAsync(s.stone_relvar, d_rv, (size_t)K * sizeof(double), hipMemcpyDeviceToHost, st));
-    if (s.u_out) HIP_TRY(hipMemcpyAsync(s.u_out, d_udraw, (size_t)n_draws * sizeof(double), hipMemcpyDeviceToHost, st));
+    HIP_TRY(fetch(s.u_mean, d_mean, (size_t)K, st));
+    HIP_TRY(fetch(s.u_var, d_var, (size_t)K, st));
+    HIP_TRY(fetch(s.d ? s.log_stone : nullptr, d_ls, (size_t)K, st));
+    HIP_TRY(fetch(s.d ? s.stone_relvar : nullptr, d_rv, (size_t)K, st));
+    HIP_TRY(fetch(s.u_out, d_udraw, (size_t)n_draws, st));
     if (int rc = wait_stream(h)) return rc;
     // the split ESS of every rung's U draws (one chain each), by the convergence kernels: rungs of equal length in one pass
     if (s.u_ess) {
@@ -2943,7 +2760,7 @@ int ptnn_evidence(ptnn_handle* h, const ptnn_evidence_spec* spec) {
 
     // ---- stage e: prior draws in blocks of nb vectors (vector + forward scratch of every training row under the budget)
     const long long NP = s.n_prior;
-    const size_t per_draw = (size_t)P * sizeof(float) + 4 * sizeof(double) + (size_t)std::min<long long>(N, row_cap) * O * sizeof(float);
+    const size_t per_draw = (size_t)P * sizeof(float) + 4 * sizeof(double) + (size_t)std::min<long long>(N, 65535LL * WAVE) * O * sizeof(float);
     const long long nb = std::max(1LL, std::min<long long>((long long)(budget / per_draw), NP));
     const size_t fixed = (size_t)nb * ((size_t)P * sizeof(float) + 4 * sizeof(double));
     const long long rows_blk = rows_for(nb, budget > fixed ? budget - fixed : 0);

@@ -1,8 +1,9 @@
 // ptnn_dev_elpd.hpp -- predictive accuracy of the sampled chains (ptnn_elpd, include/ptnn.h): per data row
 // the log pointwise predictive density, the WAIC penalty and the PSIS-LOO estimate with its Pareto shape k-hat.
-//   a. elpd_runs_kernel + predict_scan_kernel + elpd_run_eta_kernel: the selected rows collapse into distinct (w, eta) samples
-//      with multiplicities; a regression's eta comes from the TR_ACC_TR slot of the row that holds the vector, and rows before
-//      their chain's first accepted step (no eta recorded yet) are counted so that the host can refuse them.
+//   a. sample_runs_kernel (ptnn_dev_predict.hpp, with reg) + predict_scan_kernel + elpd_run_eta_kernel: the selected rows
+//      collapse into distinct (w, eta) samples with multiplicities; a regression's eta comes from the TR_ACC_TR slot of the row
+//      that holds the vector, and rows before their chain's first accepted step (no eta recorded yet) are counted so that the
+//      host can refuse them.
 //   b. the per-shape predict_forward_kernel of ptnn_dev_predict.hpp, unchanged (all n_out columns of a row are computed).
 //   c. elpd_reduce_kernel: one work-group per data row; ll is formed on the fly from the fp32 outputs, everything after is double.
 // Every sum over samples is a 128-bit fixed-point sum of terms scaled by the row's exact maximum (integer addition: the result
@@ -16,73 +17,6 @@ constexpr int ELPD_TAIL_CAP = 4096;       // distinct tail entries in LDS (inclu
 constexpr int ELPD_MAX_GRID = 30 + 64;    // m = 30 + floor(sqrt(T)), T <= ELPD_TAIL_CAP
 constexpr int ELPD_PER_THREAD = ELPD_TAIL_CAP / ELPD_THREADS;
 enum { ELPD_REG = 0, ELPD_CLS = 1, ELPD_HOST = 2 };
-
-// stage a, part 1: per selected item, where its vector is, its eta, whether it starts a run, whether its eta is valid
-struct ElpdSel {
-    // trace source (items = n_chains x m selected rows, chain-major)
-    const float* pos_w;         // d_pos_w [Rl][cap][PW]
-    const float* scal;          // d_scal [Rl][cap][TR_COUNT]
-    const int* replicas;        // [n_chains] local replica indices
-    const int* st_i;            // d_st_i [Rl][SI_COUNT]: SI_NACC = accepted steps so far (the last row's successor)
-    int cap, PW, step0, thin, m, compact, cur;   // cur: MH steps done = the last trace row
-    // host source (items = uploaded vectors [n][P] and their eta [n])
-    int host;
-    const float* host_eta;
-    int reg, P;
-    long long n_items;
-    long long* item_off;        // out: float offset of the item's vector
-    float* item_eta;            // out: the item's eta (regression)
-    int* flag;                  // out: 1 = the item starts a run
-    int* error;                 // out: [0] unresolved compact rows (internal error), [1] rows without eta, [2] first such chain
-};
-
-__global__ void __launch_bounds__(ELPD_THREADS) elpd_runs_kernel(const ElpdSel s) {
-    const long long i = (long long)blockIdx.x * ELPD_THREADS + threadIdx.x;
-    if (i >= s.n_items) return;
-    if (s.host) {
-        const float* w = s.pos_w + i * s.P;
-        int differs = i == 0;
-        for (int k = 0; k < s.P && !differs; ++k) differs = __float_as_uint(w[k]) != __float_as_uint(w[k - s.P]);
-        const float eta = s.reg ? s.host_eta[i] : 0.0f;
-        if (s.reg && !differs) differs = __float_as_uint(eta) != __float_as_uint(s.host_eta[i - 1]);
-        s.item_off[i] = i * s.P;
-        s.item_eta[i] = eta;
-        s.flag[i] = differs;
-        return;
-    }
-    const int c = (int)(i / s.m), j = (int)(i % s.m);
-    const long long rep = s.replicas[c];
-    auto eta_of = [&](int src) -> float {
-        return s.reg ? s.scal[(rep * s.cap + src % s.cap) * TR_COUNT + TR_ACC_TR] : 0.0f;
-    };
-    const int step = s.step0 + j * s.thin;
-    int src = 0, src_prev = 0;
-    const long long off = trace_vector_offset(s.scal, rep, s.cap, s.PW, step, s.compact, s.error, &src);
-    const float eta = eta_of(src);
-    int differs = j == 0;
-    if (!differs) {
-        const long long off_prev = trace_vector_offset(s.scal, rep, s.cap, s.PW, step - s.thin, s.compact, s.error, &src_prev);
-        if (s.compact) differs = src != src_prev;
-        else {
-            const float* a = s.pos_w + off;
-            const float* b = s.pos_w + off_prev;
-            for (int k = 0; k < s.P && !differs; ++k) differs = __float_as_uint(a[k]) != __float_as_uint(b[k]);
-        }
-        if (s.reg && !differs) differs = __float_as_uint(eta) != __float_as_uint(eta_of(src_prev));
-    }
-    if (s.reg) {
-        // row r (after MH step r - 1) holds a recorded eta once some step <= r - 1 was accepted: the count AFTER step r - 1 is the
-        // TR_ACCEPT of row r + 1 (written before step r's decision, REG:380), or the chain's counter when r is the last row
-        auto accepted_before = [&](int row) -> int {
-            return __float_as_int(s.scal[(rep * s.cap + row % s.cap) * TR_COUNT + TR_ACCEPT]);
-        };
-        const int after = step < s.cur ? accepted_before(step + 1) : s.st_i[rep * SI_COUNT + SI_NACC];
-        if (after < 1) { atomicAdd(&s.error[1], 1); atomicMin(&s.error[2], c); }
-    }
-    s.item_off[i] = off;
-    s.item_eta[i] = eta;
-    s.flag[i] = differs;
-}
 
 // stage a, part 3: the eta of every run (after predict_scan_kernel)
 __global__ void __launch_bounds__(ELPD_THREADS) elpd_run_eta_kernel(long long n_items, const int* flag, const int* item_run,

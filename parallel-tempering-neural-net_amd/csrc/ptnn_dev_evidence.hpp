@@ -1,7 +1,7 @@
 // ptnn_dev_evidence.hpp -- the log evidence log Z of the sampled ladder (ptnn_evidence, include/ptnn.h):
 // per-rung statistics of the full-data log-likelihood U(w) over each rung's draws, and the same over draws of the prior, which
 // the host turns into thermodynamic-integration and stepping-stone estimates.
-//   a. elpd_runs_kernel (reg = 0: U needs w only) + predict_scan_kernel: the selected rows collapse into distinct vectors.
+//   a. sample_runs_kernel (reg = 0: U needs w only) + predict_scan_kernel: the selected rows collapse into distinct vectors.
 //   b. the per-shape predict_forward_kernel of ptnn_dev_predict.hpp, unchanged, on the training rows.
 //   c. evid_rows_kernel: one lane per distinct vector adds its rows' terms in row order into a double -- log p_y (classification)
 //      or (y - f)^2 (regression, the SSE) -- carried across row blocks, so any block size gives the same bits;

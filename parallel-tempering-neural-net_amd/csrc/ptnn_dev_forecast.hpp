@@ -1,8 +1,8 @@
 // ptnn_dev_forecast.hpp -- recursive multi-step forecasts of a one-step regression map (ptnn_forecast, include/ptnn.h;
 // DESIGN.md section 14).  A trained REG net with n_out == 1 is the map x[t+1] = f_w(x[t-I+1 .. t]); step k = 1 .. h of a
 // trajectory is y_k = f_w(window_{k-1}) (+ exp(eta / 2) z_k with noise on), window_k = (window_{k-1}[1:], y_k).
-//   a. the selection: noise off -- predict_runs_kernel + predict_scan_kernel (distinct vectors with multiplicities, one
-//      trajectory each); noise on -- elpd_runs_kernel (every occurrence its own trajectory, with its eta).  Both unchanged.
+//   a. the selection: noise off -- sample_runs_kernel + predict_scan_kernel (distinct vectors with multiplicities, one
+//      trajectory each); noise on -- sample_runs_kernel with the eta (every occurrence its own trajectory).  Both unchanged.
 //   b. forecast_forward_kernel<TASK, I, O> (per shape, Shape::forecast_fwd): fx[col][u] = y of trajectory u at column
 //      col = origin * hb + k of a block of origins and horizon steps; the windows are carried from one horizon block to the next.
 //   c. predict_reduce_kernel, unchanged.

@@ -3,7 +3,7 @@
 // The reference's drafts take the network outputs of every post-burn-in sample on the train and test rows and reduce them to
 // a mean and 5 / 95 % percentile bands (multicore-pt-classification/Misc_code/ldpt_classifier_multi.py:788-794); its
 // run_chains() stopped producing those outputs "to save memory" (REG:244-245, 410-419, 785-837).  Three stages:
-//   a. predict_runs_kernel + predict_scan_kernel: the selected rows (trace rows of a list of chains, or uploaded vectors) are
+//   a. sample_runs_kernel + predict_scan_kernel: the selected rows (trace rows of a list of chains, or uploaded vectors) are
 //      collapsed into DISTINCT vectors with integer multiplicities -- a rejected MH step repeats the previous vector (REG:417),
 //      so most selected rows repeat the one before; the output depends on w only, so one evaluation per run is exact.
 //   b. predict_forward_kernel<TASK, I, O> (per shape, Shape::predict_fwd): fx[col][u] = ForwardPass of distinct vector u on
@@ -109,7 +109,7 @@ __global__ void __launch_bounds__(PRED_THREADS) predict_forward_kernel(const Pre
 // Where trace row `step` of local replica `rep` keeps its vector: the float offset in d_pos_w [Rl][cap][PW] -- its own ring slot,
 // or with compact traces the row its TR_SRC names (a rejected step wrote no vector).  *src_out = the step whose row that is; a
 // TR_SRC outside [0, step] is counted in *error and the step's own slot used, which keeps the address inside the ring.  Shared by
-// ptnn_predict (predict_runs_kernel) and ptnn_convergence (conv_gather_kernel).
+// sample_runs_kernel and conv_gather_kernel.
 __device__ __forceinline__ long long trace_vector_offset(const float* scal, long long rep, int cap, int PW, int step, int compact,
                                                          int* error, int* src_out) {
     const int slot = step % cap;
@@ -120,51 +120,71 @@ __device__ __forceinline__ long long trace_vector_offset(const float* scal, long
     return (rep * cap + src % cap) * (long long)PW;
 }
 
-// stage a, part 1: per selected item, where its vector is and whether it starts a new run
-struct PredictSel {
+// stage a, part 1: per selected item, where its vector is, whether it starts a run; with reg also its eta, compared with the
+// previous item's and checked for validity.  Shared by every analysis call that reads weight vectors (ptnn.hip: distinct_samples).
+struct SampleSel {
     // trace source (items = n_chains x m selected rows, chain-major)
     const float* pos_w;         // d_pos_w [Rl][cap][PW]
-    const float* scal;          // d_scal [Rl][cap][TR_COUNT] (compact traces: TR_SRC)
+    const float* scal;          // d_scal [Rl][cap][TR_COUNT] (compact traces: TR_SRC; reg: TR_ACC_TR, TR_ACCEPT)
     const int* replicas;        // [n_chains] local replica indices
-    int cap, PW, step0, thin, m, compact;
-    // host source (items = uploaded vectors [n][P], dense)
+    const int* st_i;            // d_st_i [Rl][SI_COUNT]: SI_NACC = accepted steps so far (the last row's successor; reg only)
+    int cap, PW, step0, thin, m, compact, cur;   // cur: MH steps done = the last trace row
+    // host source (items = uploaded vectors [n][P], dense, and with reg their eta [n])
     int host;
-    int P;
+    const float* host_eta;
+    int reg, P;                 // reg: a sample is (w, eta), a regression's eta = log tau^2
     long long n_items;
     long long* item_off;        // out: float offset of the item's vector
+    float* item_eta;            // out: the item's eta (0 without reg), or null: not stored
     int* flag;                  // out: 1 = the item starts a run
-    int* error;                 // out: != 0 = a compact row referred to a row that is not resident (internal error)
+    int* error;                 // out: [0] unresolved compact rows (internal error); reg: [1] rows without eta, [2] first such chain
 };
 
-__global__ void __launch_bounds__(PRED_THREADS) predict_runs_kernel(const PredictSel s) {
+__global__ void __launch_bounds__(PRED_THREADS) sample_runs_kernel(const SampleSel s) {
     const long long i = (long long)blockIdx.x * PRED_THREADS + threadIdx.x;
     if (i >= s.n_items) return;
     if (s.host) {
         const float* w = s.pos_w + i * s.P;
         int differs = i == 0;
         for (int k = 0; k < s.P && !differs; ++k) differs = __float_as_uint(w[k]) != __float_as_uint(w[k - s.P]);
+        const float eta = s.reg ? s.host_eta[i] : 0.0f;
+        if (s.reg && !differs) differs = __float_as_uint(eta) != __float_as_uint(s.host_eta[i - 1]);
         s.item_off[i] = i * s.P;
+        if (s.item_eta) s.item_eta[i] = eta;
         s.flag[i] = differs;
         return;
     }
     const int c = (int)(i / s.m), j = (int)(i % s.m);
     const long long rep = s.replicas[c];
-    auto resolve = [&](int jj, int* src_out) -> long long {
-        return trace_vector_offset(s.scal, rep, s.cap, s.PW, s.step0 + jj * s.thin, s.compact, s.error, src_out);
+    auto eta_of = [&](int src) -> float {
+        return s.reg ? s.scal[(rep * s.cap + src % s.cap) * TR_COUNT + TR_ACC_TR] : 0.0f;
     };
+    const int step = s.step0 + j * s.thin;
     int src = 0, src_prev = 0;
-    const long long off = resolve(j, &src);
+    const long long off = trace_vector_offset(s.scal, rep, s.cap, s.PW, step, s.compact, s.error, &src);
+    const float eta = eta_of(src);
     int differs = j == 0;
     if (!differs) {
-        const long long off_prev = resolve(j - 1, &src_prev);
+        const long long off_prev = trace_vector_offset(s.scal, rep, s.cap, s.PW, step - s.thin, s.compact, s.error, &src_prev);
         if (s.compact) differs = src != src_prev;
         else {
             const float* a = s.pos_w + off;
             const float* b = s.pos_w + off_prev;
             for (int k = 0; k < s.P && !differs; ++k) differs = __float_as_uint(a[k]) != __float_as_uint(b[k]);
         }
+        if (s.reg && !differs) differs = __float_as_uint(eta) != __float_as_uint(eta_of(src_prev));
+    }
+    if (s.reg) {
+        // row r (after MH step r - 1) holds a recorded eta once some step <= r - 1 was accepted: the count AFTER step r - 1 is the
+        // TR_ACCEPT of row r + 1 (written before step r's decision, REG:380), or the chain's counter when r is the last row
+        auto accepted_before = [&](int row) -> int {
+            return __float_as_int(s.scal[(rep * s.cap + row % s.cap) * TR_COUNT + TR_ACCEPT]);
+        };
+        const int after = step < s.cur ? accepted_before(step + 1) : s.st_i[rep * SI_COUNT + SI_NACC];
+        if (after < 1) { atomicAdd(&s.error[1], 1); atomicMin(&s.error[2], c); }
     }
     s.item_off[i] = off;
+    if (s.item_eta) s.item_eta[i] = eta;
     s.flag[i] = differs;
 }
 

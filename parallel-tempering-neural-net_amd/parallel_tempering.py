@@ -608,6 +608,69 @@ class ParallelTemperingBase:
                 accept_vec, accept)
 
     # ------------------------------------------------------------------ posterior predictive (not in the reference's run_chains)
+    # ------------------------------------------------------------------ what the posterior analysis calls share
+    def _need_sampler(self, name):
+        if self._sampler is None:
+            raise ValueError(f"{name} needs the chains' device handle: call initialize_chains() and run_chains() first")
+        if not isinstance(self._sampler, _lib.Sampler):
+            raise ValueError(f"{name} runs on one GPU: a ladder sharded over several devices is not supported")
+
+    def _check_trace(self, alt):
+        """The trace of a finished run is on the device, one chain per temperature; `alt` names the host-data argument."""
+        S = self.NumSamples
+        if self.label_swap:
+            raise ValueError(f"label_swap=True: trace rows are kept per chain slot, not per temperature; pass {alt}=")
+        if 0 < self.trace_capacity < S:
+            raise ValueError(f"trace_capacity = {self.trace_capacity} < NumSamples = {S}: the rows have been streamed off "
+                             f"the device; pass {alt}=")
+        if not self._finished:
+            raise ValueError(f"no finished run_chains() on this object: the trace is incomplete; pass {alt}=")
+
+    def _trace_selection(self, burn_in, chains, thin, alt="weights"):
+        """Every selected chain's trace rows from int(NumSamples * burn_in) on, every thin-th -> (Sampler source keywords,
+        sample count)."""
+        self._check_trace(alt)
+        S = self.NumSamples
+        b = self.burn_in if burn_in is None else burn_in
+        step0 = int(S * b)
+        if chains == "all":
+            reps = None
+        elif chains == "cold":
+            reps = [int(np.argmin(self.temperatures))]
+        else:
+            reps = [int(c) for c in chains]
+            if not reps or min(reps) < 0 or max(reps) >= self.num_chains:
+                raise ValueError(f"chains {chains!r}: indices must lie in [0, {self.num_chains})")
+        nrep = self.num_chains if reps is None else len(reps)
+        return dict(replicas=reps, step0=step0, nsteps=S - step0, thin=int(thin)), nrep * max(0, -(-(S - step0) // max(1, int(thin))))
+
+    def _weights(self, weights):
+        """weights=: vectors [n, num_param] (or their transpose), or a pair (vectors, integer multiplicities) -> (w, mult)."""
+        mult = None
+        if isinstance(weights, tuple):
+            weights, mult = weights
+        w = np.asarray(weights)
+        P = self.num_param
+        if w.ndim != 2 or P not in w.shape:
+            raise ValueError(f"weights must be [n, {P}] vectors (or their transpose), got shape {w.shape}")
+        return (w if w.shape[1] == P else w.T), mult
+
+    @staticmethod
+    def _band_ranks(M, pcts):
+        """The order statistics np.percentile's linear interpolation needs for `pcts` of M samples -> (spots, ranks)."""
+        if M < 1:
+            raise ValueError("the selection holds no sample")
+        spots = percentile_ranks(M, pcts)
+        ranks = sorted({r for lo, hi, _ in spots for r in (lo, hi)})
+        if len(ranks) > _lib.PREDICT_MAX_RANKS:
+            raise ValueError(f"{len(pcts)} percentiles need {len(ranks)} order statistics: at most {_lib.PREDICT_MAX_RANKS} per call")
+        return spots, ranks
+
+    @staticmethod
+    def _bands(order_stats, pcts, spots, ranks):
+        pos = {r: k for k, r in enumerate(ranks)}
+        return {p: lerp_percentile(order_stats[pos[lo]], order_stats[pos[hi]], g) for p, (lo, hi, g) in zip(pcts, spots)}
+
     def posterior_predictive(self, x="test", *, burn_in=None, chains="all", thin=1, percentiles=(5, 95), weights=None,
                              return_samples=False):
         """Predictions with uncertainty from the sampled chains, computed on the GPU: what the reference's drafts derive from
@@ -620,10 +683,7 @@ class ParallelTemperingBase:
         columns are the inputs.  Percentiles follow np.percentile(method="linear") exactly: the device returns the exact order
         statistics, the interpolation is numpy's arithmetic.  -> Predictive(mean, percentiles, vote, pred_class, samples,
         n_samples, n_distinct); outputs are [n_rows, n_out], samples [n_samples, n_rows, n_out] in chain-major order."""
-        if self._sampler is None:
-            raise ValueError("posterior_predictive needs the chains' device handle: call initialize_chains() and run_chains() first")
-        if not isinstance(self._sampler, _lib.Sampler):
-            raise ValueError("posterior_predictive runs on one GPU: a ladder sharded over several devices is not supported")
+        self._need_sampler("posterior_predictive")
         I = int(self.topology[0])
         if isinstance(x, str):
             if x not in ("train", "test"):
@@ -637,52 +697,16 @@ class ParallelTemperingBase:
         pcts = list(percentiles)
         if any(not (0 <= p <= 100) for p in pcts):
             raise ValueError(f"percentiles must lie in [0, 100], got {pcts}")
-        kw = {}
         if weights is not None:
-            mult = None
-            if isinstance(weights, tuple):
-                weights, mult = weights
-            w = np.asarray(weights)
-            P = self.num_param
-            if w.ndim != 2 or P not in w.shape:
-                raise ValueError(f"weights must be [n, {P}] vectors (or their transpose), got shape {w.shape}")
-            if w.shape[1] != P:
-                w = w.T
+            w, mult = self._weights(weights)
             kw = dict(w=w, multiplicity=mult)
             M = int(np.sum(np.asarray(mult, dtype=np.int64))) if mult is not None else w.shape[0]
         else:
-            S = self.NumSamples
-            if self.label_swap:
-                raise ValueError("label_swap=True: trace rows are kept per chain slot, not per temperature; pass weights=")
-            if 0 < self.trace_capacity < S:
-                raise ValueError(f"trace_capacity = {self.trace_capacity} < NumSamples = {S}: the rows have been streamed off "
-                                 f"the device; pass weights=")
-            if not self._finished:
-                raise ValueError("no finished run_chains() on this object: the trace is incomplete; pass weights=")
-            b = self.burn_in if burn_in is None else burn_in
-            step0 = int(S * b)
-            if chains == "all":
-                reps = None
-            elif chains == "cold":
-                reps = [int(np.argmin(self.temperatures))]
-            else:
-                reps = [int(c) for c in chains]
-                if not reps or min(reps) < 0 or max(reps) >= self.num_chains:
-                    raise ValueError(f"chains {chains!r}: indices must lie in [0, {self.num_chains})")
-            kw = dict(replicas=reps, step0=step0, nsteps=S - step0, thin=int(thin))
-            nrep = self.num_chains if reps is None else len(reps)
-            M = nrep * max(0, -(-(S - step0) // max(1, int(thin))))
-        if M < 1:
-            raise ValueError("the selection holds no sample")
-        spots = percentile_ranks(M, pcts)
-        ranks = sorted({r for lo, hi, _ in spots for r in (lo, hi)})
-        if len(ranks) > _lib.PREDICT_MAX_RANKS:
-            raise ValueError(f"{len(pcts)} percentiles need {len(ranks)} order statistics: at most {_lib.PREDICT_MAX_RANKS} per call")
+            kw, M = self._trace_selection(burn_in, chains, thin)
+        spots, ranks = self._band_ranks(M, pcts)
         cls = self.task == TASK_CLS
         out = self._sampler.predict(xs, ranks=ranks, vote=cls, samples=bool(return_samples), **kw)
-        pos = {r: k for k, r in enumerate(ranks)}
-        os_ = out["order_stats"]
-        bands = {p: lerp_percentile(os_[pos[lo]], os_[pos[hi]], g) for p, (lo, hi, g) in zip(pcts, spots)}
+        bands = self._bands(out["order_stats"], pcts, spots, ranks)
         mean = out["mean"]
         return Predictive(mean=mean, percentiles=bands, vote=out["vote"] if cls else None,
                           pred_class=np.argmax(mean, axis=1) if cls else None, samples=out["samples"],
@@ -704,10 +728,7 @@ class ParallelTemperingBase:
         `per_chain`: also the ESS of each chain alone; `n_lags`: also the raw combined autocorrelation rho_t, t < n_lags.
         `draws`: host draws [n_chains, n_draws, Q] instead of the trace (names q0 ..); works whenever the handle exists.
         -> Convergence(names, mean, sd, r_hat, ess, mcse_mean = sd / sqrt(ess), ess_chain, rho, trunc_lag, n_chains, n_draws)."""
-        if self._sampler is None:
-            raise ValueError("convergence_diagnostics needs the chains' device handle: call initialize_chains() and run_chains() first")
-        if not isinstance(self._sampler, _lib.Sampler):
-            raise ValueError("convergence_diagnostics runs on one GPU: a ladder sharded over several devices is not supported")
+        self._need_sampler("convergence_diagnostics")
         if draws is not None:
             d = np.asarray(draws)
             if d.ndim != 3:
@@ -715,24 +736,7 @@ class ParallelTemperingBase:
             names = [f"q{k}" for k in range(d.shape[2])]
             out = self._sampler.convergence(draws=d, per_chain=per_chain, n_lags=n_lags)
         else:
-            S = self.NumSamples
-            if self.label_swap:
-                raise ValueError("label_swap=True: trace rows are kept per chain slot, not per temperature; pass draws=")
-            if 0 < self.trace_capacity < S:
-                raise ValueError(f"trace_capacity = {self.trace_capacity} < NumSamples = {S}: the rows have been streamed off "
-                                 f"the device; pass draws=")
-            if not self._finished:
-                raise ValueError("no finished run_chains() on this object: the trace is incomplete; pass draws=")
-            b = self.burn_in if burn_in is None else burn_in
-            step0 = int(S * b)
-            if chains == "all":
-                reps = None
-            elif chains == "cold":
-                reps = [int(np.argmin(self.temperatures))]
-            else:
-                reps = [int(c) for c in chains]
-                if not reps or min(reps) < 0 or max(reps) >= self.num_chains:
-                    raise ValueError(f"chains {chains!r}: indices must lie in [0, {self.num_chains})")
+            kw, _ = self._trace_selection(burn_in, chains, thin, alt="draws")
             P = self.num_param
             pidx = None if params is None else [int(p) for p in params]
             if pidx is not None and any(not (0 <= p < P) for p in pidx):
@@ -747,8 +751,7 @@ class ParallelTemperingBase:
             names = [f"w{p}" for p in (range(P) if pidx is None else pidx)] + [cols[c] for c in sorted(cols)]
             if not names:
                 raise ValueError("no quantity selected: give params and/or scalars")
-            out = self._sampler.convergence(replicas=reps, step0=step0, nsteps=S - step0, thin=int(thin), params=pidx,
-                                            scalars=sorted(cols), per_chain=per_chain, n_lags=n_lags)
+            out = self._sampler.convergence(params=pidx, scalars=sorted(cols), per_chain=per_chain, n_lags=n_lags, **kw)
         sd = np.sqrt(out["var"])
         with np.errstate(invalid="ignore", divide="ignore"):
             mcse = sd / np.sqrt(out["ess"])
@@ -780,10 +783,7 @@ class ParallelTemperingBase:
         [n] (regression); `loglik`: a pointwise log-likelihood [n_samples, n_rows] (or a pair with multiplicities) instead of
         both.  r_eff: relative efficiency of the draws for the PSIS tail length.  return_pointwise: also log_lik [S, n_rows].
         -> PredictiveAccuracy; totals are sums over rows, se_* = sqrt(N var(pointwise, ddof 1))."""
-        if self._sampler is None:
-            raise ValueError("predictive_accuracy needs the chains' device handle: call initialize_chains() and run_chains() first")
-        if not isinstance(self._sampler, _lib.Sampler):
-            raise ValueError("predictive_accuracy runs on one GPU: a ladder sharded over several devices is not supported")
+        self._need_sampler("predictive_accuracy")
         I = int(self.topology[0])
         kw = {}
         if loglik is not None:
@@ -803,38 +803,12 @@ class ParallelTemperingBase:
                     raise ValueError(f"data must be 2-D with at least n_in + 1 = {I + 1} columns (inputs, target), got shape {xa.shape}")
                 ds = np.ascontiguousarray(xa[:, :I + 1], dtype=np.float32)
             if weights is not None:
-                mult = None
-                if isinstance(weights, tuple):
-                    weights, mult = weights
-                w = np.asarray(weights)
-                P = self.num_param
-                if w.ndim != 2 or P not in w.shape:
-                    raise ValueError(f"weights must be [n, {P}] vectors (or their transpose), got shape {w.shape}")
-                if w.shape[1] != P:
-                    w = w.T
+                w, mult = self._weights(weights)
                 if self.task != TASK_CLS and eta is None:
                     raise ValueError("a regression's weights need eta = log tau^2, one per vector (Sampler.eta_trace())")
                 kw = dict(w=w, eta=None if self.task == TASK_CLS else eta, multiplicity=mult)
         if not kw:
-            S = self.NumSamples
-            if self.label_swap:
-                raise ValueError("label_swap=True: trace rows are kept per chain slot, not per temperature; pass weights=")
-            if 0 < self.trace_capacity < S:
-                raise ValueError(f"trace_capacity = {self.trace_capacity} < NumSamples = {S}: the rows have been streamed off "
-                                 f"the device; pass weights=")
-            if not self._finished:
-                raise ValueError("no finished run_chains() on this object: the trace is incomplete; pass weights=")
-            b = self.burn_in if burn_in is None else burn_in
-            step0 = int(S * b)
-            if chains == "all":
-                reps = None
-            elif chains == "cold":
-                reps = [int(np.argmin(self.temperatures))]
-            else:
-                reps = [int(c) for c in chains]
-                if not reps or min(reps) < 0 or max(reps) >= self.num_chains:
-                    raise ValueError(f"chains {chains!r}: indices must lie in [0, {self.num_chains})")
-            kw = dict(replicas=reps, step0=step0, nsteps=S - step0, thin=int(thin))
+            kw, _ = self._trace_selection(burn_in, chains, thin)
         out = self._sampler.elpd(ds, r_eff=r_eff, loglik_out=bool(return_pointwise) and loglik is None, **kw)
         lppd_i, p_waic_i, loo_i, khat = out["lppd"], out["p_waic"], out["elpd_loo"], out["khat"]
         waic_i = lppd_i - p_waic_i
@@ -873,10 +847,7 @@ class ParallelTemperingBase:
         pair (vectors, integer multiplicities), with `eta` [n] when noise is on.  Percentiles follow np.percentile(method="linear")
         exactly.  -> Forecast(mean, percentiles, samples, n_samples, n_trajectories); outputs are [n_origins, horizon] (one origin
         for "end"), samples [n_samples, n_origins, horizon] in chain-major order.  Regression nets with one output only."""
-        if self._sampler is None:
-            raise ValueError("forecast needs the chains' device handle: call initialize_chains() and run_chains() first")
-        if not isinstance(self._sampler, _lib.Sampler):
-            raise ValueError("forecast runs on one GPU: a ladder sharded over several devices is not supported")
+        self._need_sampler("forecast")
         if self.task == TASK_CLS or int(self.topology[2]) != 1:
             raise ValueError("forecast needs a regression net with one output (a one-step map of one series)")
         I = int(self.topology[0])
@@ -896,55 +867,18 @@ class ParallelTemperingBase:
         pcts = list(percentiles)
         if any(not (0 <= p <= 100) for p in pcts):
             raise ValueError(f"percentiles must lie in [0, 100], got {pcts}")
-        kw = {}
         if weights is not None:
-            mult = None
-            if isinstance(weights, tuple):
-                weights, mult = weights
-            w = np.asarray(weights)
-            P = self.num_param
-            if w.ndim != 2 or P not in w.shape:
-                raise ValueError(f"weights must be [n, {P}] vectors (or their transpose), got shape {w.shape}")
-            if w.shape[1] != P:
-                w = w.T
+            w, mult = self._weights(weights)
             if noise and eta is None:
                 raise ValueError("noise=True with weights= needs eta = log tau^2, one per vector (Sampler.eta_trace())")
             kw = dict(w=w, multiplicity=mult, eta=eta if noise else None)
             M = int(np.sum(np.asarray(mult, dtype=np.int64))) if mult is not None else w.shape[0]
         else:
-            S = self.NumSamples
-            if self.label_swap:
-                raise ValueError("label_swap=True: trace rows are kept per chain slot, not per temperature; pass weights=")
-            if 0 < self.trace_capacity < S:
-                raise ValueError(f"trace_capacity = {self.trace_capacity} < NumSamples = {S}: the rows have been streamed off "
-                                 f"the device; pass weights=")
-            if not self._finished:
-                raise ValueError("no finished run_chains() on this object: the trace is incomplete; pass weights=")
-            b = self.burn_in if burn_in is None else burn_in
-            step0 = int(S * b)
-            if chains == "all":
-                reps = None
-            elif chains == "cold":
-                reps = [int(np.argmin(self.temperatures))]
-            else:
-                reps = [int(c) for c in chains]
-                if not reps or min(reps) < 0 or max(reps) >= self.num_chains:
-                    raise ValueError(f"chains {chains!r}: indices must lie in [0, {self.num_chains})")
-            kw = dict(replicas=reps, step0=step0, nsteps=S - step0, thin=int(thin))
-            nrep = self.num_chains if reps is None else len(reps)
-            M = nrep * max(0, -(-(S - step0) // max(1, int(thin))))
-        if M < 1:
-            raise ValueError("the selection holds no sample")
-        spots = percentile_ranks(M, pcts)
-        ranks = sorted({r for lo, hi, _ in spots for r in (lo, hi)})
-        if len(ranks) > _lib.PREDICT_MAX_RANKS:
-            raise ValueError(f"{len(pcts)} percentiles need {len(ranks)} order statistics: at most {_lib.PREDICT_MAX_RANKS} per call")
+            kw, M = self._trace_selection(burn_in, chains, thin)
+        spots, ranks = self._band_ranks(M, pcts)
         out = self._sampler.forecast(int(horizon), org, noise=bool(noise), seed=self.seed if seed is None else int(seed),
                                      ranks=ranks, samples=bool(return_samples), **kw)
-        pos = {r: k for k, r in enumerate(ranks)}
-        os_ = out["order_stats"]
-        bands = {p: lerp_percentile(os_[pos[lo]], os_[pos[hi]], g) for p, (lo, hi, g) in zip(pcts, spots)}
-        return Forecast(mean=out["mean"], percentiles=bands, samples=out["samples"], n_samples=out["n_samples"],
+        return Forecast(mean=out["mean"], percentiles=self._bands(out["order_stats"], pcts, spots, ranks), samples=out["samples"], n_samples=out["n_samples"],
                         n_trajectories=out["n_trajectories"])
 
     # ------------------------------------------------------------------ log evidence (not in the reference)
@@ -965,10 +899,7 @@ class ParallelTemperingBase:
         The estimate is exact only when the tempered chains sample the power posterior: random-walk proposals, swap_rule=1,
         shared_noise=False and a large integer maxtemp (so that the hottest rung is close to the prior); a warning names the
         settings that break this."""
-        if self._sampler is None:
-            raise ValueError("log_evidence needs the chains' device handle: call initialize_chains() and run_chains() first")
-        if not isinstance(self._sampler, _lib.Sampler):
-            raise ValueError("log_evidence runs on one GPU: a ladder sharded over several devices is not supported")
+        self._need_sampler("log_evidence")
         S = self.NumSamples
         n_prior = int(prior_draws)
         if n_prior < 2:
@@ -986,13 +917,7 @@ class ParallelTemperingBase:
             order = np.argsort(betas, kind="stable")
             kw = dict(w=w[order])
         else:
-            if self.label_swap:
-                raise ValueError("label_swap=True: trace rows are kept per chain slot, not per temperature; pass weights=")
-            if 0 < self.trace_capacity < S:
-                raise ValueError(f"trace_capacity = {self.trace_capacity} < NumSamples = {S}: the rows have been streamed off "
-                                 f"the device; pass weights=")
-            if not self._finished:
-                raise ValueError("no finished run_chains() on this object: the trace is incomplete; pass weights=")
+            self._check_trace("weights")
             betas = np.array([1.0 / float(np.float32(T)) for T in self.temperatures])
             order = np.argsort(betas, kind="stable")
             b = self.burn_in if burn_in is None else burn_in
