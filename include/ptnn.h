@@ -122,6 +122,30 @@ int ptnn_set_state(ptnn_handle *h, const float *w0, const float *temperatures);
 /* all R_global temperatures (needed by swap_rule 1 only) */
 int ptnn_set_ladder(ptnn_handle *h, const float *temperatures_global);
 
+/* Ladder adaptation during burn-in (swap_rule 1 only; Vousden, Farr & Mandel 2016 with fixed endpoints).
+ * Swap round t < rounds moves the log-gaps s_k = log(T_k+1 - T_k) by kappa(t) (a_k(t) - mean_k a_k(t)), kappa(t) = kappa0 t0 / (t + t0),
+ * a_k(t) = min(1, exp((1/T_k - 1/T_k+1)(L_k+1 - L_k))) the acceptance of EVERY adjacent pair under the round's ladder, then
+ * rescales the gaps so that T_0 = 1 and T_R-1 = the ladder's last temperature stay where they are.  The new ladder is used
+ * from the next interval on; from round `rounds` on it is frozen.  Every rule-1 round records its a_k(t).
+ * Call after ptnn_set_ladder (which drops a spec set before it) and before the first step; ptnn_set_state restarts the
+ * adaptation from the initial ladder.  Refused: swap_rule != 1, no ladder, a ladder that does not start at exactly 1 or is not
+ * strictly increasing, rounds outside [0, swap rounds of the run], a last adapted round that hands off after pt_switch_step,
+ * kappa0 or t0 not finite and > 0, a call after steps have run.  Checkpoints carry the spec, the log-gaps and both records. */
+typedef struct ptnn_ladder_adapt_spec {
+    int32_t struct_bytes;  /* = sizeof(ptnn_ladder_adapt_spec): ABI guard */
+    int32_t rounds;        /* A: swap rounds that move the ladder; 0 = fixed ladder, acceptances recorded only */
+    double kappa0, t0;     /* kappa(t) = kappa0 * t0 / (t + t0) */
+} ptnn_ladder_adapt_spec;
+int ptnn_set_ladder_adaptation(ptnn_handle *h, const ptnn_ladder_adapt_spec *spec);
+/* ladders [A+1][R_global] (row t = the ladder of round t's test, row A the frozen one; rows of rounds not run yet are NaN),
+ * accept [rounds recorded][R_global-1] = a_k(t), room for n_samples / swap_interval + 2 rows; either may be NULL.
+ * *rounds_recorded = the rounds run so far.  The arrays are those of this handle (every block of a ladder holds the same). */
+int ptnn_get_ladder_history(ptnn_handle *h, float *ladders, float *accept, int32_t *rounds_recorded);
+/* the adaptation this handle runs (after ptnn_checkpoint_load: the checkpoint's): 1 and *spec filled, or 0 without one.
+ * Size the buffers of ptnn_get_ladder_history from spec->rounds.  A checkpoint whose spec differs from the one set on the handle,
+ * or that has none while the handle has one, is refused by ptnn_checkpoint_load. */
+int ptnn_get_ladder_adaptation(ptnn_handle *h, ptnn_ladder_adapt_spec *spec);
+
 /* Advances every local replica by up to n_steps MH steps (ptReplica.run loop body, REG:313-437) and performs the
  * swap rounds that fall inside (ParallelTempering.swap_procedure + round loop, REG:659-690, 719-752), including the
  * phantom last round when the chain end is reached.  n_steps < 0 = run to the end.  A handle that owns only a

@@ -114,6 +114,11 @@ class EvidenceSpec(C.Structure):
 EVIDENCE_MAX_A = 4
 
 
+class LadderAdaptSpec(C.Structure):
+    """ptnn_ladder_adapt_spec (include/ptnn.h)."""
+    _fields_ = [("struct_bytes", C.c_int32), ("rounds", C.c_int32), ("kappa0", C.c_double), ("t0", C.c_double)]
+
+
 def library_path():
     return os.environ.get("PTNN_LIBRARY", os.path.join(_HERE, "libptnn.so"))
 
@@ -140,6 +145,9 @@ SYMBOLS = {
     "ptnn_set_data": (C.c_int, [C.c_void_p, _fp, C.c_int, _fp, C.c_int, C.c_int]),
     "ptnn_set_state": (C.c_int, [C.c_void_p, _fp, _fp]),
     "ptnn_set_ladder": (C.c_int, [C.c_void_p, _fp]),
+    "ptnn_set_ladder_adaptation": (C.c_int, [C.c_void_p, C.POINTER(LadderAdaptSpec)]),
+    "ptnn_get_ladder_history": (C.c_int, [C.c_void_p, _fp, _fp, _ip]),
+    "ptnn_get_ladder_adaptation": (C.c_int, [C.c_void_p, C.POINTER(LadderAdaptSpec)]),
     "ptnn_run": (C.c_int, [C.c_void_p, C.c_int]),
     "ptnn_sync": (C.c_int, [C.c_void_p]),
     "ptnn_steps_done": (C.c_int, [C.c_void_p]),
@@ -319,6 +327,33 @@ class Sampler:
         if t.shape != (self.cfg.n_replicas_global,):
             raise ValueError("temperatures_global must have n_replicas_global entries")
         self._check(self.lib.ptnn_set_ladder(self.h, _ptr(t)))
+
+    def set_ladder_adaptation(self, rounds, kappa0, t0):
+        """Adapt the ladder over the first `rounds` swap rounds (swap_rule 1; ptnn_set_ladder_adaptation); rounds = 0 records the
+        per-pair acceptances only."""
+        spec = LadderAdaptSpec(C.sizeof(LadderAdaptSpec), int(rounds), float(kappa0), float(t0))
+        self._check(self.lib.ptnn_set_ladder_adaptation(self.h, C.byref(spec)))
+
+    def ladder_adaptation(self):
+        """(rounds, kappa0, t0) of the adaptation the handle runs (a restored checkpoint's), or None."""
+        spec = LadderAdaptSpec()
+        if self._check(self.lib.ptnn_get_ladder_adaptation(self.h, C.byref(spec))) == 0:
+            return None
+        return spec.rounds, spec.kappa0, spec.t0
+
+    def ladder_history(self):
+        """(ladders [A+1, R_global] float32, accept [rounds run, R_global-1] float32): the ladder of every adapted round (row A =
+        the frozen one) and a_k(t) of every round."""
+        Rg = self.cfg.n_replicas_global
+        spec = self.ladder_adaptation()              # the handle's own A: the buffer is sized from what the library will copy
+        if spec is None:
+            raise PtnnError("no ladder adaptation on this handle (set_ladder_adaptation)")
+        A = spec[0]
+        lad = np.empty((A + 1, Rg), np.float32)
+        acc = np.empty((self.S // self.cfg.swap_interval + 2, Rg - 1), np.float32)
+        n = C.c_int32()
+        self._check(self.lib.ptnn_get_ladder_history(self.h, _ptr(lad), _ptr(acc), C.byref(n)))
+        return lad, acc[:n.value].copy()
 
     def run(self, n_steps=-1):
         self._check(self.lib.ptnn_run(self.h, int(n_steps)))

@@ -151,6 +151,15 @@ struct ptnn_handle {
     float *d_L_handoff = nullptr, *d_L_final = nullptr;
     float *d_L_raw = nullptr, *d_prior_post = nullptr, *d_temps_global = nullptr;   // swap_rule 1
     bool have_ladder = false;
+    // ladder adaptation during burn-in (ptnn_set_ladder_adaptation, ptnn_dev_ladder.hpp): histories on the device, the initial
+    // ladder and log-gaps on the host (a restart starts from them again)
+    bool have_adapt = false;
+    ptnn_ladder_adapt_spec adapt{};
+    float* d_lad_hist = nullptr;    // [A+1][R]
+    double* d_lad_s = nullptr;      // [2][R-1]
+    float* d_lad_acc = nullptr;     // [max_rounds][R-1]
+    std::vector<float> lad_T0;
+    std::vector<double> lad_s0;
     int *d_label[2] = {nullptr, nullptr}, *d_slot_of[2] = {nullptr, nullptr};   // label_swap: slot <-> temperature maps, ping-pong
     int lflip = 0;
     float *d_pos_w = nullptr;       // [Rl][cap][PW]
@@ -256,6 +265,48 @@ void fill_swap_params(ptnn_handle* h, bool phantom, SwapParams& sp) {
     sp.label_next = h->d_label[h->lflip ^ 1]; sp.slot_next = h->d_slot_of[h->lflip ^ 1];
     sp.temps_local = h->d_temps;
     sp.progress = nullptr;
+    if (h->have_adapt) {
+        const int R = h->cfg.n_replicas_global;
+        sp.lad_hist = h->d_lad_hist; sp.lad_s = h->d_lad_s; sp.lad_acc = h->d_lad_acc; sp.lad_out = h->d_temps_global;
+        sp.lad_A = h->adapt.rounds; sp.lad_acc_cap = h->max_rounds;
+        sp.lad_kappa0 = h->adapt.kappa0; sp.lad_t0 = h->adapt.t0;
+        sp.temps_global = h->d_lad_hist + (size_t)std::min(h->rounds_done, h->adapt.rounds) * R;   // the ladder of this round
+    } else {
+        sp.lad_hist = nullptr; sp.lad_s = nullptr; sp.lad_acc = nullptr; sp.lad_out = nullptr;
+        sp.lad_A = 0; sp.lad_acc_cap = 0; sp.lad_kappa0 = 0.0; sp.lad_t0 = 0.0;
+    }
+}
+
+// drop the adaptation buffers (ptnn_set_ladder, a new spec, a checkpoint without one)
+void ladder_adapt_release(ptnn_handle* h) {
+    for (void* p : {(void*)h->d_lad_hist, (void*)h->d_lad_s, (void*)h->d_lad_acc})
+        if (p) (void)hipFree(p);
+    h->d_lad_hist = nullptr; h->d_lad_s = nullptr; h->d_lad_acc = nullptr;
+    h->have_adapt = false; h->adapt = ptnn_ladder_adapt_spec{};
+    h->lad_T0.clear(); h->lad_s0.clear();
+}
+
+int ladder_adapt_alloc(ptnn_handle* h, const ptnn_ladder_adapt_spec& spec) {
+    ladder_adapt_release(h);
+    const size_t R = h->cfg.n_replicas_global;
+    HIP_TRY(hipMalloc(&h->d_lad_hist, (size_t)(spec.rounds + 1) * R * sizeof(float)));
+    HIP_TRY(hipMalloc(&h->d_lad_s, 2 * (R - 1) * sizeof(double)));
+    HIP_TRY(hipMalloc(&h->d_lad_acc, (size_t)h->max_rounds * (R - 1) * sizeof(float)));
+    h->adapt = spec; h->have_adapt = true;
+    return 0;
+}
+
+// the adaptation back at its start: ladder row 0 = the initial ladder (also in d_temps_global), s = its log-gaps, rows not yet
+// written are NaN
+int ladder_adapt_reset(ptnn_handle* h) {
+    const size_t R = h->cfg.n_replicas_global;
+    HIP_TRY(hipMemsetAsync(h->d_lad_hist, 0xff, (size_t)(h->adapt.rounds + 1) * R * sizeof(float), h->stream));
+    HIP_TRY(hipMemsetAsync(h->d_lad_acc, 0xff, (size_t)h->max_rounds * (R - 1) * sizeof(float), h->stream));
+    HIP_TRY(hipMemcpyAsync(h->d_lad_hist, h->lad_T0.data(), R * sizeof(float), hipMemcpyHostToDevice, h->stream));
+    HIP_TRY(hipMemcpyAsync(h->d_temps_global, h->lad_T0.data(), R * sizeof(float), hipMemcpyHostToDevice, h->stream));
+    HIP_TRY(hipMemcpyAsync(h->d_lad_s, h->lad_s0.data(), (R - 1) * sizeof(double), hipMemcpyHostToDevice, h->stream));
+    HIP_TRY(hipStreamSynchronize(h->stream));            // the host vectors are pageable and may change later
+    return 0;
 }
 
 // MH steps [begin, end) in one launch.  swap_inside: the swap rounds between the intervals run inside it (persistent launch:
@@ -923,6 +974,7 @@ int ptnn_destroy(ptnn_handle* h) {
     if (h->h_stage) (void)hipHostFree(h->h_stage);
     if (h->d_stage) (void)hipFree(h->d_stage);
     if (h->d_xchg) (void)hipFree(h->d_xchg);
+    ladder_adapt_release(h);
     for (auto& ev : h->timing) { (void)hipEventDestroy(ev.first); (void)hipEventDestroy(ev.second); }
     if (h->copy_stream) { (void)hipStreamSynchronize(h->copy_stream); (void)hipStreamDestroy(h->copy_stream); }
     for (auto& ev : h->img_events) (void)hipEventDestroy(ev);
@@ -973,6 +1025,8 @@ int ptnn_set_state(ptnn_handle* h, const float* w0, const float* temperatures) {
     q.counters = h->d_counters;
     hipLaunchKernelGGL(chain_reset_kernel, dim3(Rl), dim3(256), 0, h->stream, q);
     HIP_TRY(hipGetLastError());
+    if (h->have_adapt)
+        if (int rc = ladder_adapt_reset(h)) return rc;
     h->flip = 0; h->cur = 0; h->rounds_done = 0; h->finalized = false; h->drained = 0; h->first_row = 0; h->lflip = 0;
     if (!h->comm.failed) { h->failed = false; h->failure.clear(); }   // a restart clears a failed run (a failed communicator stays failed)
     h->h_progress[0] = h->h_progress[1] = 0;
@@ -983,8 +1037,70 @@ int ptnn_set_state(ptnn_handle* h, const float* w0, const float* temperatures) {
 int ptnn_set_ladder(ptnn_handle* h, const float* temperatures_global) {
     if (!h || !temperatures_global) return fail(-1, "null argument");
     HIP_TRY(hipSetDevice(h->cfg.device_id));
+    if (h->have_adapt) {                                     // a new ladder drops the adaptation: set it again
+        if (int rc = wait_stream(h)) return rc;
+        ladder_adapt_release(h);
+    }
     HIP_TRY(hipMemcpy(h->d_temps_global, temperatures_global, h->cfg.n_replicas_global * sizeof(float), hipMemcpyHostToDevice));
     h->have_ladder = true;
+    return 0;
+}
+
+int ptnn_set_ladder_adaptation(ptnn_handle* h, const ptnn_ladder_adapt_spec* spec) {
+    if (!h || !spec) return fail(-1, "null argument");
+    if (spec->struct_bytes != (int32_t)sizeof(ptnn_ladder_adapt_spec))
+        return fail(-1, "ptnn_ladder_adapt_spec.struct_bytes = %d, this library expects %zu", spec->struct_bytes, sizeof(ptnn_ladder_adapt_spec));
+    const ptnn_config& c = h->cfg;
+    if (c.swap_rule != 1)
+        return fail(-1, "ladder adaptation needs swap_rule 1: the reference's cascade (swap_rule 0) has no per-pair Metropolis "
+                        "acceptance to equalise");
+    if (!h->have_ladder) return fail(-1, "call ptnn_set_ladder before ptnn_set_ladder_adaptation");
+    if (h->cur > 0 || h->rounds_done > 0) return fail(-1, "ptnn_set_ladder_adaptation after MH steps have run: restart the chains (ptnn_set_state) first");
+    if (!(std::isfinite(spec->kappa0) && spec->kappa0 > 0.0) || !(std::isfinite(spec->t0) && spec->t0 > 0.0))
+        return fail(-1, "kappa0 = %g and t0 = %g must be finite and > 0", spec->kappa0, spec->t0);
+    const int R = c.n_replicas_global, S = c.n_samples, si = c.swap_interval;
+    // the hand-off step of every swap round (Q10), as the runs find them
+    std::vector<int> hand;
+    for (int i = 0; i < S - 1; ++i)
+        if (swap_trigger(c, i)) hand.push_back(i);
+    const int A = spec->rounds;
+    if (A < 0 || A > (int)hand.size())
+        return fail(-1, "rounds = %d: the run has %zu swap rounds (n_samples %d, swap_interval %d)", A, hand.size(), S, si);
+    if (A > 0 && c.pt_switch_step >= 0 && hand[A - 1] > c.pt_switch_step)
+        return fail(-1, "rounds = %d: the last adapted round hands off after step %d, past the temperature switch at step %d "
+                        "(every chain runs at T = 1 from there)", A, hand[A - 1], c.pt_switch_step);
+    HIP_TRY(hipSetDevice(c.device_id));
+    if (int rc = wait_stream(h)) return rc;
+    std::vector<float> T(R);
+    HIP_TRY(hipMemcpy(T.data(), h->d_temps_global, R * sizeof(float), hipMemcpyDeviceToHost));
+    if (R < 2 || T[0] != 1.0f) return fail(-1, "the ladder must start at exactly 1 (T_0 = %g) and have at least two rungs", R ? (double)T[0] : 0.0);
+    for (int k = 0; k + 1 < R; ++k)
+        if (!(T[k + 1] > T[k]) || !std::isfinite(T[k + 1]))
+            return fail(-1, "the ladder is not strictly increasing and finite: T_%d = %g, T_%d = %g", k, (double)T[k], k + 1, (double)T[k + 1]);
+    if (int rc = ladder_adapt_alloc(h, *spec)) return rc;
+    h->lad_T0 = T;
+    h->lad_s0.resize(R - 1);
+    for (int k = 0; k + 1 < R; ++k) h->lad_s0[k] = std::log((double)T[k + 1] - (double)T[k]);
+    return ladder_adapt_reset(h);
+}
+
+int ptnn_get_ladder_adaptation(ptnn_handle* h, ptnn_ladder_adapt_spec* spec) {
+    if (!h || !spec) return fail(-1, "null argument");
+    if (!h->have_adapt) return 0;
+    *spec = h->adapt;
+    return 1;
+}
+
+int ptnn_get_ladder_history(ptnn_handle* h, float* ladders, float* accept, int32_t* rounds_recorded) {
+    if (!h) return fail(-1, "null argument");
+    if (!h->have_adapt) return fail(-1, "no ladder adaptation on this handle (ptnn_set_ladder_adaptation)");
+    HIP_TRY(hipSetDevice(h->cfg.device_id));
+    if (int rc = finish_stream(h)) return rc;
+    const size_t R = h->cfg.n_replicas_global;
+    const int n = std::min(h->rounds_done, h->max_rounds);
+    if (ladders) HIP_TRY(hipMemcpy(ladders, h->d_lad_hist, (size_t)(h->adapt.rounds + 1) * R * sizeof(float), hipMemcpyDeviceToHost));
+    if (accept && n > 0) HIP_TRY(hipMemcpy(accept, h->d_lad_acc, (size_t)n * (R - 1) * sizeof(float), hipMemcpyDeviceToHost));
+    if (rounds_recorded) *rounds_recorded = n;
     return 0;
 }
 
@@ -1669,10 +1785,16 @@ struct CkHeader {
 };
 constexpr uint32_t CK_MAGIC = 0x4b435450u;      // "PTCK"
 
+// ladder adaptation (header word `reserved` = 1): the spec, both log-gap rows, the ladder history and the recorded acceptances
+size_t ck_adapt_bytes(size_t R, int A, size_t logr) {
+    return sizeof(ptnn_ladder_adapt_spec) + sizeof(double) * 2 * (R - 1) + sizeof(float) * ((size_t)(A + 1) * R + logr * (R - 1));
+}
+
 size_t ck_bytes(const ptnn_handle* h) {
     const size_t Rl = h->cfg.n_replicas_local, R = h->cfg.n_replicas_global, PS = h->PS;
     const size_t logr = (size_t)std::min(h->rounds_done, h->max_rounds);
-    return sizeof(CkHeader) + sizeof(float) * (3 * Rl * PS + Rl * SF_COUNT + Rl + 5 * R) + sizeof(int) * (Rl + Rl * SI_COUNT + logr * R + 2 * R);
+    return sizeof(CkHeader) + sizeof(float) * (3 * Rl * PS + Rl * SF_COUNT + Rl + 5 * R) + sizeof(int) * (Rl + Rl * SI_COUNT + logr * R + 2 * R) +
+           (h->have_adapt ? ck_adapt_bytes(R, h->adapt.rounds, logr) : 0);
 }
 
 bool same_chain(const ptnn_config& a, const ptnn_config& b) {
@@ -1703,6 +1825,7 @@ int ptnn_checkpoint_save(ptnn_handle* h, void* buf, int64_t bytes) {
     hd.magic = CK_MAGIC; hd.version = 3; hd.cfg = h->cfg; hd.P = h->P; hd.PS = h->PS; hd.cur = h->cur;
     hd.rounds_done = h->rounds_done; hd.finalized = h->finalized ? 1 : 0; hd.have_ladder = h->have_ladder ? 1 : 0;
     hd.log_rounds = std::min(h->rounds_done, h->max_rounds);
+    hd.reserved = h->have_adapt ? 1 : 0;
     HIP_TRY(hipMemcpy(hd.counters, h->d_counters, sizeof(hd.counters), hipMemcpyDeviceToHost));
     char* q = static_cast<char*>(buf);
     std::memcpy(q, &hd, sizeof(hd)); q += sizeof(hd);
@@ -1726,6 +1849,12 @@ int ptnn_checkpoint_save(ptnn_handle* h, void* buf, int64_t bytes) {
     if (int rc = get(h->d_src_log, sizeof(int) * (size_t)hd.log_rounds * R)) return rc;
     if (int rc = get(h->d_label[h->lflip], sizeof(int) * R)) return rc;          // slot <-> temperature maps (identity unless label_swap)
     if (int rc = get(h->d_slot_of[h->lflip], sizeof(int) * R)) return rc;
+    if (h->have_adapt) {
+        std::memcpy(q, &h->adapt, sizeof(h->adapt)); q += sizeof(h->adapt);
+        if (int rc = get(h->d_lad_s, sizeof(double) * 2 * (R - 1))) return rc;
+        if (int rc = get(h->d_lad_hist, sizeof(float) * (size_t)(h->adapt.rounds + 1) * R)) return rc;
+        if (int rc = get(h->d_lad_acc, sizeof(float) * (size_t)hd.log_rounds * (R - 1))) return rc;
+    }
     return 0;
 }
 
@@ -1745,6 +1874,23 @@ int ptnn_checkpoint_load(ptnn_handle* h, const void* buf, int64_t bytes) {
                         sizeof(int) * (Rl + Rl * SI_COUNT + (size_t)hd.log_rounds * R + 2 * R);
     if ((size_t)bytes < need) return fail(-1, "truncated checkpoint: %lld < %zu bytes", (long long)bytes, need);
     if (hd.log_rounds > h->max_rounds) return fail(-1, "checkpoint holds more swap rounds than this handle can log");
+    if (hd.reserved != 0 && hd.reserved != 1) return fail(-1, "not a libptnn checkpoint (unknown trailer %d)", hd.reserved);
+    ptnn_ladder_adapt_spec ad{};
+    if (hd.reserved == 1) {
+        if ((size_t)bytes < need + sizeof(ad)) return fail(-1, "truncated checkpoint: no ladder adaptation spec");
+        std::memcpy(&ad, static_cast<const char*>(buf) + need, sizeof(ad));
+        if (ad.struct_bytes != (int32_t)sizeof(ad) || ad.rounds < 0 || ad.rounds > h->max_rounds)
+            return fail(-1, "the checkpoint's ladder adaptation spec is not valid here");
+        if (h->have_adapt && (h->adapt.rounds != ad.rounds || h->adapt.kappa0 != ad.kappa0 || h->adapt.t0 != ad.t0))
+            return fail(-1, "the checkpoint adapts the ladder over %d rounds (kappa0 %g, t0 %g), this handle over %d (kappa0 %g, t0 %g): "
+                            "set the same adaptation, or none, before loading it", ad.rounds, ad.kappa0, ad.t0, h->adapt.rounds,
+                        h->adapt.kappa0, h->adapt.t0);
+        const size_t full = need + ck_adapt_bytes(R, ad.rounds, (size_t)hd.log_rounds);
+        if ((size_t)bytes < full) return fail(-1, "truncated checkpoint: %lld < %zu bytes", (long long)bytes, full);
+    } else if (h->have_adapt) {
+        return fail(-1, "the checkpoint was written without ladder adaptation, this handle adapts the ladder: clear it first "
+                        "(ptnn_set_ladder)");
+    }
     const char* q = static_cast<const char*>(buf) + sizeof(CkHeader);
     auto put = [&](void* dev, size_t n) -> int {
         if (n) HIP_TRY(hipMemcpy(dev, q, n, hipMemcpyHostToDevice));
@@ -1768,6 +1914,20 @@ int ptnn_checkpoint_load(ptnn_handle* h, const void* buf, int64_t bytes) {
     h->lflip = 0;
     if (int rc = put(h->d_label[0], sizeof(int) * R)) return rc;
     if (int rc = put(h->d_slot_of[0], sizeof(int) * R)) return rc;
+    if (hd.reserved == 1) {
+        // the adaptation travels with the chains: spec, log-gaps and both records as they were
+        if (int rc = ladder_adapt_alloc(h, ad)) return rc;
+        q += sizeof(ad);
+        if (int rc = put(h->d_lad_s, sizeof(double) * 2 * (R - 1))) return rc;
+        if (int rc = put(h->d_lad_hist, sizeof(float) * (size_t)(ad.rounds + 1) * R)) return rc;
+        HIP_TRY(hipMemset(h->d_lad_acc, 0xff, (size_t)h->max_rounds * (R - 1) * sizeof(float)));
+        if (int rc = put(h->d_lad_acc, sizeof(float) * (size_t)hd.log_rounds * (R - 1))) return rc;
+        // a restart of this handle (ptnn_set_state) starts from the checkpoint's initial ladder, row 0 of its history
+        h->lad_T0.resize(R);
+        HIP_TRY(hipMemcpy(h->lad_T0.data(), h->d_lad_hist, R * sizeof(float), hipMemcpyDeviceToHost));
+        h->lad_s0.resize(R - 1);
+        for (size_t k = 0; k + 1 < R; ++k) h->lad_s0[k] = std::log((double)h->lad_T0[k + 1] - (double)h->lad_T0[k]);
+    }
     HIP_TRY(hipMemcpy(h->d_state[1], h->d_state[0], sizeof(float) * Rl * PS, hipMemcpyDeviceToDevice));
     if (h->plan.compact) {
         // compact traces: the rows a later rejected step may repeat are not on this device -- put the recorded row of every chain

@@ -220,6 +220,7 @@ __device__ __forceinline__ void persistent_loop(const SegParams& p0, const int s
             sp.label_cur = pp->label[lflip]; sp.slot_cur = pp->slot_of[lflip];
             sp.label_next = pp->label[lflip ^ 1]; sp.slot_next = pp->slot_of[lflip ^ 1];
             sp.canonical = (p.switch_step >= 0 && cur - 1 >= p.switch_step) ? 1 : 0;
+            if (sp.lad_hist) sp.temps_global = sp.lad_hist + (size_t)min(round, sp.lad_A) * sp.R;     // ladder of this round
             swap_block(sp, round, 3, xcd_block(p.G) / p.G, smem);
         }
         if (pp->sp.label_mode) lflip ^= 1; else flip ^= 1;

@@ -145,6 +145,14 @@ struct SwapParams {
     float* temps_local;        // [Rl] temperature of the local slots (what the segment kernels read)
     int* progress;             // pinned host word (or null): block 0 stores round + 1 when the round is through -- what the bounded
                                // waits of a communicator handle watch (ptnn.hip: wait_stream)
+    // ladder adaptation during burn-in (swap_rule 1, ptnn_set_ladder_adaptation; ptnn_dev_ladder.hpp): null lad_hist = off, and
+    // then temps_global is the fixed ladder; otherwise temps_global is row min(round, lad_A) of lad_hist
+    float* lad_hist;           // [A+1][R]
+    double* lad_s;             // [2][R-1]
+    float* lad_acc;            // [lad_acc_cap][R-1]
+    float* lad_out;            // [R]
+    int lad_A, lad_acc_cap;
+    double lad_kappa0, lad_t0;
 };
 __host__ __device__ inline int xchg_row_floats(int PS) { return (2 * PS + 4 + 3) & ~3; }
 

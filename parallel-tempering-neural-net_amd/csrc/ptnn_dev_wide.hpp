@@ -1152,6 +1152,8 @@ __global__ void __launch_bounds__(MAX_THREADS) model_wide_kernel(const SegParams
 
 #pragma clang fp contract(off)
 
+#include "ptnn_dev_ladder.hpp"
+
 // One block's share of a swap round: the cascade (every block recomputes it in LDS), then block b's row.  mode bit 0: apply the
 // local moves; bit 1: count the round and log it (block 0); bit 2: the source rows come from the gathered exchange buffer.
 __device__ __forceinline__ void swap_block(const SwapParams& sp, const int round, const int mode, const int b, float* smem) {
@@ -1159,6 +1161,11 @@ __device__ __forceinline__ void swap_block(const SwapParams& sp, const int round
     float* sU = smem + sp.R;
     int* sSrc = reinterpret_cast<int*>(smem + 2 * sp.R);
     const int nsw = cascade_lds(sp, round, sL, sU, sSrc);
+    // ladder adaptation (swap_rule 1 only): a_k(t) in sL, and while the ladder moves (moved) the new one in sU -- the round's own
+    // test above used the old one; the local slots take their new temperatures below
+    const bool moved = sp.lad_hist && (mode & 1) &&
+                       ladder_round(sp.R, round, b, sp.label_mode, sp.slot_cur, sp.temps_global, sp.L_raw, sp.L_stride, sp.lad_A,
+                                    sp.lad_acc_cap, sp.lad_kappa0, sp.lad_t0, sp.lad_hist, sp.lad_s, sp.lad_acc, sp.lad_out, sL, sU);
     if (sp.label_mode) {
         // temperature t is handed to the chain that held temperature src[t]: only the maps change
         if (mode & 1) {
@@ -1169,7 +1176,13 @@ __device__ __forceinline__ void swap_block(const SwapParams& sp, const int round
                 if (sSrc[t] == t_old) sL[0] = __int_as_float(t);           // exactly one t has src[t] == t_old (a permutation)
             __syncthreads();
             t_new = __float_as_int(sL[0]);
-            if (threadIdx.x == 0 && t_new != t_old) {
+            if (moved) {
+                if (threadIdx.x == 0) {
+                    const float Tn = sU[t_new];
+                    sp.temps_local[b] = Tn;
+                    if (!sp.canonical) sp.st_f[(size_t)b * SF_COUNT + SF_LIK] = sp.L_raw[(size_t)g * sp.L_stride] / Tn;
+                }
+            } else if (threadIdx.x == 0 && t_new != t_old) {
                 const float To = sp.temps_global[t_old], Tn = sp.temps_global[t_new];
                 sp.temps_local[b] = Tn;
                 // the chain keeps its own likelihood; while the chains are tempered it is re-tempered for the new temperature
@@ -1211,7 +1224,15 @@ __device__ __forceinline__ void swap_block(const SwapParams& sp, const int round
             valid = sp.gd_valid_cur[sl];
         }
         if (threadIdx.x == 0) sp.gd_valid_next[b] = valid;
-        if (sp.rule == 1 && s != k && threadIdx.x == 0) {
+        if (moved) {
+            // every slot is re-tempered for its new temperature, the moved states bring their prior along
+            if (threadIdx.x == 0) {
+                const float lraw = sp.L_raw[(size_t)s * sp.L_stride], Tn = sU[k];
+                sp.temps_local[b] = Tn;
+                sp.st_f[(size_t)b * SF_COUNT + SF_LIK] = sp.canonical ? lraw : lraw / Tn;
+                if (s != k) sp.st_f[(size_t)b * SF_COUNT + SF_PRIOR] = sp.prior_post[(size_t)s * sp.L_stride];
+            }
+        } else if (sp.rule == 1 && s != k && threadIdx.x == 0) {
             // the arriving state brings its own likelihood (re-tempered for this slot) and prior
             const float lraw = sp.L_raw[(size_t)s * sp.L_stride];
             sp.st_f[(size_t)b * SF_COUNT + SF_LIK] = sp.canonical ? lraw : lraw / sp.temps_global[k];

@@ -357,6 +357,12 @@ class LadderGroup:
     def set_ladder(self, temperatures_global):
         self._each(lambda k: self.shards[k].set_ladder(temperatures_global))
 
+    def set_ladder_adaptation(self, rounds, kappa0, t0):
+        self._each(lambda k: self.shards[k].set_ladder_adaptation(rounds, kappa0, t0))
+
+    def ladder_history(self):
+        return self.shards[0].ladder_history()              # every block computes the same ladder
+
     # ---- running: every block advances by the same number of steps; the swap rounds inside exchange through the communicator
     def run(self, n_steps=-1):
         self._each(lambda k: self.shards[k].run(n_steps))

@@ -50,6 +50,63 @@ def stitch_by_temperature(tr, swap_log, handoff_steps, S):
     return out, holder
 
 
+def ladder_stats_from_log(src_log, rule, first_round, n_moves=None):
+    """Per-pair swap acceptance and round trips of the walkers from a swap log (Sampler.swap_log(): row r = src of round r, slot k
+    received the state / label of slot src[k]), over rounds first_round .. n_moves - 1 (n_moves None = every row; a rule-0 run
+    that ended with the phantom round passes the number of hand-off rounds, the phantom moves nothing).  Pair k is proposed in
+    every round under rule 0 and in the rounds of its parity (k % 2 == r % 2) under rule 1, and accepted when src[k] == k + 1.
+    A walker (a state under state moves, a chain under label swapping) at index j goes to the k with src[k] == j; a round trip
+    is index 0 -> R-1 -> 0, timed from its last visit of 0 before it reached R-1.
+    -> dict(pair_accept [R-1] (NaN where nothing was proposed), accepted [R-1], proposed [R-1], round_trips [R] (per walker,
+    walker w starts at index w), mean_round_trip_rounds (NaN without a trip))."""
+    log = np.asarray(src_log, dtype=np.int64)
+    if log.ndim != 2 or log.shape[1] < 2:
+        raise ValueError(f"src_log must be [rounds, R >= 2], got shape {log.shape}")
+    if int(rule) not in (0, 1):
+        raise ValueError(f"rule must be 0 or 1, got {rule}")
+    n = log.shape[0] if n_moves is None else min(int(n_moves), log.shape[0])
+    R = log.shape[1]
+    k = np.arange(R - 1)
+    acc = np.zeros(R - 1, np.int64)
+    prop = np.zeros(R - 1, np.int64)
+    pos = np.arange(R)                          # pos[w] = index of walker w
+    state = np.zeros(R, np.int64)               # 0: not at 0 yet, 1: left 0 heading up, 2: reached R-1 heading down
+    start = np.zeros(R, np.int64)
+    trips = np.zeros(R, np.int64)
+    durations = []
+    first = int(first_round)
+
+    def visit(r):
+        for w in range(R):
+            if pos[w] == 0:
+                if state[w] == 2:
+                    trips[w] += 1
+                    durations.append(r - start[w])
+                state[w], start[w] = 1, r
+            elif pos[w] == R - 1 and state[w] == 1:
+                state[w] = 2
+    for r in range(n):
+        src = log[r]
+        if r >= first:
+            if r == first:
+                visit(r)                        # where the walkers stand when the counting starts
+            on = np.ones(R - 1, bool) if int(rule) == 0 else (k % 2 == r % 2)
+            prop += on
+            acc += on & (src[:-1] == k + 1)
+        inv = np.empty(R, np.int64)
+        inv[src] = np.arange(R)                 # the walker at index j moves to the k with src[k] == j
+        pos = inv[pos]
+        if r >= first:
+            visit(r + 1)
+    with np.errstate(invalid="ignore", divide="ignore"):
+        pa = np.where(prop > 0, acc / np.maximum(prop, 1), np.nan)
+    return dict(pair_accept=pa, accepted=acc, proposed=prop, round_trips=trips,
+                mean_round_trip_rounds=float(np.mean(durations)) if durations else float("nan"))
+
+
+LADDER_KAPPA0, LADDER_T0 = 0.05, 1000.0  # defaults of adapt_ladder=True (measured: DESIGN.md section 16, profiles/ladder_probe_effect.jsonl)
+
+
 def overlap_cuts(S, swap_interval, chunks):
     """MH-step counts at which an overlapped run_chains() ends its launches: at most `chunks` launches of whole swap intervals
     (near-equal), strictly increasing, the last one at S - 1 (all steps; ptnn_run then also runs the phantom round if one is due)."""
@@ -216,7 +273,8 @@ class ParallelTemperingBase:
     def __init__(self, use_langevin_gradients, learn_rate, traindata, testdata, topology, num_chains, maxtemp,
                  NumSample, swap_interval, langevin_prob, path, *, seed=None, device=None, devices=None, exchange="auto",
                  transport=None, waves_per_replica=0, schedule=0, groups_per_replica=0, trace_capacity=0, swap_rule=0,
-                 label_swap=False, shared_noise=True, write_files=True, io_threads=None, forward_bf16=0, overlap_chunks=8):
+                 label_swap=False, shared_noise=True, write_files=True, io_threads=None, forward_bf16=0, overlap_chunks=8,
+                 adapt_ladder=False):
         # FNN chain variables (REG:491-494)
         self.traindata = traindata
         self.testdata = testdata
@@ -274,6 +332,22 @@ class ParallelTemperingBase:
         # run_chains() cuts the run into this many launches and lets the trace rows of each leave for the host -- and into the
         # per-chain files -- while the next is being sampled (one GPU, every row resident); 0: download and write after the last step
         self.overlap_chunks = int(overlap_chunks)
+        # adapt the ladder during burn-in (swap_rule 1): True = every swap round that hands off before
+        # int(burn_in * NumSamples) and not past the temperature switch, kappa0 / t0 the defaults; dict(rounds=, kappa0=, t0=)
+        # overrides them.  After run_chains() `temperatures` is the frozen ladder, `ladder_history` every adapted one.
+        if adapt_ladder is not False and adapt_ladder is not None:
+            if self.swap_rule != 1:
+                raise ValueError("adapt_ladder needs swap_rule=1: the reference's cascade (swap_rule=0) has no per-pair Metropolis "
+                                 "acceptance to equalise")
+            if adapt_ladder is not True:
+                if not isinstance(adapt_ladder, dict) or set(adapt_ladder) - {"rounds", "kappa0", "t0"}:
+                    raise ValueError("adapt_ladder must be True, False or a dict with the keys rounds, kappa0, t0")
+                for key in ("kappa0", "t0"):
+                    v = adapt_ladder.get(key)
+                    if v is not None and not (math.isfinite(float(v)) and float(v) > 0):
+                        raise ValueError(f"adapt_ladder: {key} = {v} must be finite and > 0")
+        self.adapt_ladder = adapt_ladder if adapt_ladder not in (False, None) else False
+        self.ladder_history = None
         self._img = None
         self.timings = {}
         self._sampler = None
@@ -305,7 +379,8 @@ class ParallelTemperingBase:
             raise ValueError("w0 must be [num_chains, num_param]")
         self._w0 = w0
         if self._sampler is not None:
-            self._sampler.set_state(self._w0, self.temperatures)
+            # a restart begins at the initial ladder again (ptnn_set_state restarts the adaptation from it)
+            self._sampler.set_state(self._w0, self._ladder0 if self.ladder_history is not None else self.temperatures)
 
     def _pt_switch_step(self):
         # `i == pt_samples` with pt_samples = samples * 0.6 compares an int with a float (REG:301,320): it fires
@@ -313,11 +388,43 @@ class ParallelTemperingBase:
         pt_samples = self.NumSamples * 0.6
         return int(pt_samples) if pt_samples == int(pt_samples) else -1
 
+    def _ladder_adapt_spec(self):
+        """(rounds, kappa0, t0) of adapt_ladder, or None; the refusals that need no GPU."""
+        if self.adapt_ladder is False:
+            return None
+        hand = self._handoff_steps()
+        sw = self._pt_switch_step()
+        spec = {} if self.adapt_ladder is True else dict(self.adapt_ladder)
+        kappa0 = float(spec.get("kappa0", LADDER_KAPPA0))
+        t0 = float(spec.get("t0", LADDER_T0))
+        if spec.get("rounds") is None:
+            step0 = int(self.burn_in * self.NumSamples)
+            A = sum(1 for i in hand if i < step0 and (sw < 0 or i <= sw))
+            if A < 2:
+                raise ValueError(f"adapt_ladder: {A} swap round(s) hand off inside the burn-in (before step {step0}, "
+                                 f"swap_interval {self.swap_interval}): at least 2 are needed (a longer burn_in or more samples)")
+        else:
+            A = int(spec["rounds"])
+            if A < 0 or A > len(hand):
+                raise ValueError(f"adapt_ladder: rounds = {A}: the run has {len(hand)} swap rounds")
+            if A > 0 and sw >= 0 and hand[A - 1] > sw:
+                raise ValueError(f"adapt_ladder: rounds = {A}: the last adapted round hands off after step {hand[A - 1]}, past "
+                                 f"the temperature switch at step {sw}")
+        return A, kappa0, t0
+
+    def _freeze_step(self):
+        """First MH step that runs on the frozen ladder (0 without adaptation)."""
+        spec = self._ladder_adapt_spec()
+        if spec is None or spec[0] == 0:
+            return 0
+        return self._handoff_steps()[spec[0] - 1] + 1
+
     def _configure(self):
         I, H, O = (int(v) for v in self.topology)
         S = self.NumSamples
         if self.swap_interval < 1:
             raise ZeroDivisionError("integer division or modulo by zero")      # `i % self.swap_interval` (REG:427)
+        adapt = self._ladder_adapt_spec()
         train = np.asarray(self.traindata, dtype=np.float64)
         test = np.asarray(self.testdata, dtype=np.float64)
         if train.ndim != 2 or train.shape[1] <= I:
@@ -346,6 +453,10 @@ class ParallelTemperingBase:
         self._finished = False
         if self.swap_rule == 1 or self.label_swap:
             self._sampler.set_ladder(self.temperatures)
+        if adapt is not None:
+            self._sampler.set_ladder_adaptation(*adapt)
+        self._ladder0 = list(self.temperatures)
+        self.ladder_history = None
         self._img = None
         # (the images are pinned host memory the size of the device's trace arrays: taken up to 1 GiB, above that the resident path)
         image_bytes = self.num_chains * S * (self.num_param + 24) * 4
@@ -437,6 +548,17 @@ class ParallelTemperingBase:
 
     def _finish_run(self, out, timings):
         self._finished = True
+        if self.adapt_ladder is not False:
+            # the rows after the freeze were sampled at the frozen ladder (the files keep the names of the initial one)
+            lad, _ = self._sampler.ladder_history()
+            self.ladder_history = lad
+            A = lad.shape[0] - 1
+            frozen = lad[min(A, self.rounds)]
+            if not np.all(np.diff(frozen) > 0):
+                # float32 rounding of nearly collapsed gaps (a kappa0 far too large): the rungs are no longer distinct
+                warnings.warn(f"the adapted ladder is not strictly increasing in float32: {frozen.tolist()}; use a smaller kappa0",
+                              stacklevel=2)
+            self.temperatures = [float(T) for T in frozen]
         nlaunch, kms = self._sampler.kernel_time()
         self.timings = dict(timings, segment_launches=nlaunch, segment_kernel_ms=kms,
                             samples_per_s=self.num_chains * (self.NumSamples - 1) / max(timings["sampling_s"], 1e-12))
@@ -609,6 +731,26 @@ class ParallelTemperingBase:
 
     # ------------------------------------------------------------------ posterior predictive (not in the reference's run_chains)
     # ------------------------------------------------------------------ what the posterior analysis calls share
+    def ladder_diagnostics(self, burn_in=None):
+        """How the ladder works, over the swap rounds that hand off at or after int(NumSamples * burn_in) (None = the object's
+        burn_in): dict(temperatures = the (frozen) ladder, pair_accept [R-1] = accepted / proposed per adjacent pair,
+        pair_accept_rb [R-1] = mean Rao-Blackwellised acceptance a_k of those rounds (None without adapt_ladder), round_trips [R]
+        per walker (index 0 -> R-1 -> 0), mean_round_trip_rounds, history = the ladder history (None without adapt_ladder))."""
+        if self._sampler is None or not self._finished:
+            raise ValueError("ladder_diagnostics needs a finished run: call initialize_chains() and run_chains() first")
+        b = self.burn_in if burn_in is None else burn_in
+        step0 = int(self.NumSamples * b)
+        hand = self._handoff_steps()
+        first = sum(1 for i in hand if i < step0)
+        st = ladder_stats_from_log(self._sampler.swap_log(), self.swap_rule, first, n_moves=len(hand))
+        rb = None
+        if self.adapt_ladder is not False:
+            _, acc = self._sampler.ladder_history()
+            rows = acc[first:len(hand)]
+            rb = rows.astype(np.float64).mean(axis=0) if rows.shape[0] else np.full(self.num_chains - 1, np.nan)
+        return dict(temperatures=np.asarray(self.temperatures, np.float64), pair_accept=st["pair_accept"], pair_accept_rb=rb,
+                    round_trips=st["round_trips"], mean_round_trip_rounds=st["mean_round_trip_rounds"], history=self.ladder_history)
+
     def _need_sampler(self, name):
         if self._sampler is None:
             raise ValueError(f"{name} needs the chains' device handle: call initialize_chains() and run_chains() first")
@@ -922,6 +1064,9 @@ class ParallelTemperingBase:
             order = np.argsort(betas, kind="stable")
             b = self.burn_in if burn_in is None else burn_in
             step0 = int(S * b)
+            if step0 < self._freeze_step():
+                raise ValueError(f"the window starts at step {step0} (burn_in = {b}), before the adapted ladder froze at step "
+                                 f"{self._freeze_step()}: the rungs moved inside it (a larger burn_in)")
             sw = self._pt_switch_step()
             end = sw if sw >= 0 else S
             per = max(0, -(-(end - step0) // max(1, int(thin))))
