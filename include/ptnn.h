@@ -524,6 +524,62 @@ typedef struct ptnn_evidence_spec {
 
 int ptnn_evidence(ptnn_handle *h, const ptnn_evidence_spec *spec);
 
+/* ---- calibration and proper scores of the predictive distribution (nothing in the reference: it reports RMSE / accuracy) ----
+ * Regression (n_out == 1): the predictive distribution of y on data row n is the mixture (1/S) sum_s c_s N(f_s, tau_s^2) over
+ * the expanded multiset of S samples (a sample with multiplicity c counts c times), tau_s^2 = exp(eta_s); per row, with the
+ * row's target y: pit = (1/S) sum c Phi((y - f) / tau); pred_mean = (1/S) sum c f; pred_sd = sqrt((1/S) sum c (tau^2 + (f -
+ * pred_mean)^2)); crps = (1/S) sum_s c_s A(y - f_s, tau_s^2) - (1 / (2 S^2)) sum_s sum_t c_s c_t A(f_s - f_t, tau_s^2 + tau_t^2),
+ * A(m, v) = m (2 Phi(m / sqrt v) - 1) + 2 sqrt(v) phi(m / sqrt v) (Grimit et al. 2006; the double sum includes s = t);
+ * quantiles [k][n] = a root z of (1/S) sum c Phi((z - f) / tau) = levels_p[k], bisected in double from the bracket [min (f + tau
+ * levels_z[k]), max (f + tau levels_z[k])] until the midpoint is an end point; levels_z[k] = Phi^-1(levels_p[k]) is the
+ * caller's.  Classification: p_mean [n_rows, n_out] = (1/S) sum c p, bitwise ptnn_predict's mean for the same selection.
+ * f / p are the fp32 outputs of ptnn_predict's forward pass, everything after it is double; DESIGN.md section 17.
+ * Sources: (1) the handle's trace and (2) host vectors w [n_w, P] with eta [n_w] (regression) and optional multiplicities,
+ * selected, merged and refused exactly as ptnn_elpd's sources 1 and 2 (same rules and error texts, the rows without a recorded
+ * eta included).  Data as ptnn_elpd: x_source _TRAIN / _TEST or _HOST with x [n_rows, n_in + 1] (last column the target).
+ * The results depend on the multiset of samples only (bitwise: trace, host vectors, expanded or (distinct, multiplicity), any
+ * block size): every sum is an exact integer sum of fixed-point terms.
+ * pair_term != 0 computes crps, U^2 / 2 evaluations of A per row over the U distinct samples: refused when U exceeds
+ * PTNN_CALIB_MAX_DISTINCT (select fewer samples, or pair_term = 0, which leaves crps untouched and has no such cap).
+ * Outputs, any may be NULL: pit, crps, pred_mean, pred_sd [n_rows]; quantiles [n_levels, n_rows]; p_mean [n_rows, n_out];
+ * n_samples = S; n_distinct = U.  Refused: pit / crps / pred_mean / pred_sd / quantiles or pair_term on a classification or
+ * with n_out != 1, p_mean on a regression, n_levels outside [0, PTNN_CALIB_MAX_LEVELS], a level outside (0, 1), crps without
+ * pair_term, quantiles without levels.
+ * Runs on the handle's stream behind everything queued and returns when done; rows are processed in blocks whose scratch stays
+ * under $PTNN_CALIB_SCRATCH_BYTES (read per call, default 1 GiB) and of at most 65535 x 64 rows, which changes no result.
+ * Touches no chain state, tape, counter or trace row.  Not with a communicator attached (one GPU only). */
+#define PTNN_CALIB_MAX_LEVELS 16
+#define PTNN_CALIB_MAX_DISTINCT 65536
+
+typedef struct ptnn_calibration_spec {
+    int32_t struct_bytes;         /* = sizeof(ptnn_calibration_spec): ABI guard */
+    /* source 1: the trace (used when w == NULL) */
+    const int32_t *replicas;      /* local replica indices, or NULL = all */
+    int32_t n_replicas;           /* entries of replicas (ignored when NULL) */
+    int32_t step0, nsteps, thin;  /* trace rows step0, step0 + thin, ... < step0 + nsteps (thin >= 1) */
+    /* source 2: host vectors */
+    const float *w;               /* [n_w, P] or NULL */
+    const float *eta;             /* [n_w] log tau^2 (regression) */
+    const int32_t *multiplicity;  /* [n_w] >= 0, or NULL = 1 each */
+    int64_t n_w;
+    /* data */
+    int32_t x_source;             /* PTNN_PREDICT_X_HOST | _TRAIN | _TEST */
+    int32_t n_rows;
+    const float *x;               /* [n_rows, n_in + 1] (host rows only) */
+    /* quantile levels (regression) */
+    const double *levels_p;       /* [n_levels] in (0, 1) */
+    const double *levels_z;       /* [n_levels] Phi^-1(levels_p) */
+    int32_t n_levels;             /* <= PTNN_CALIB_MAX_LEVELS */
+    int32_t pair_term;            /* 0 / 1: the CRPS with its pair term (regression) */
+    /* outputs */
+    double *pit, *crps, *pred_mean, *pred_sd;
+    double *quantiles;
+    double *p_mean;
+    int64_t *n_samples, *n_distinct;
+} ptnn_calibration_spec;
+
+int ptnn_calibration(ptnn_handle *h, const ptnn_calibration_spec *spec);
+
 /* the HIP stream (hipStream_t) all of this handle's work is queued on: lets the caller order its collectives after the
  * segment / before the swap kernels on the device instead of synchronising the host */
 int ptnn_stream(ptnn_handle *h, void **hip_stream);

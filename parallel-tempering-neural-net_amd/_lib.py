@@ -2,6 +2,7 @@
 import ctypes as C
 import math
 import os
+from statistics import NormalDist
 
 import numpy as np
 
@@ -114,6 +115,24 @@ class EvidenceSpec(C.Structure):
 EVIDENCE_MAX_A = 4
 
 
+class CalibrationSpec(C.Structure):
+    """ptnn_calibration_spec (include/ptnn.h)."""
+    _fields_ = [
+        ("struct_bytes", C.c_int32),
+        ("replicas", C.POINTER(C.c_int32)), ("n_replicas", C.c_int32), ("step0", C.c_int32), ("nsteps", C.c_int32), ("thin", C.c_int32),
+        ("w", C.POINTER(C.c_float)), ("eta", C.POINTER(C.c_float)), ("multiplicity", C.POINTER(C.c_int32)), ("n_w", C.c_int64),
+        ("x_source", C.c_int32), ("n_rows", C.c_int32), ("x", C.POINTER(C.c_float)),
+        ("levels_p", C.POINTER(C.c_double)), ("levels_z", C.POINTER(C.c_double)), ("n_levels", C.c_int32), ("pair_term", C.c_int32),
+        ("pit", C.POINTER(C.c_double)), ("crps", C.POINTER(C.c_double)), ("pred_mean", C.POINTER(C.c_double)),
+        ("pred_sd", C.POINTER(C.c_double)), ("quantiles", C.POINTER(C.c_double)), ("p_mean", C.POINTER(C.c_double)),
+        ("n_samples", C.POINTER(C.c_int64)), ("n_distinct", C.POINTER(C.c_int64)),
+    ]
+
+
+CALIB_MAX_LEVELS = 16
+CALIB_MAX_DISTINCT = 65536
+
+
 class LadderAdaptSpec(C.Structure):
     """ptnn_ladder_adapt_spec (include/ptnn.h)."""
     _fields_ = [("struct_bytes", C.c_int32), ("rounds", C.c_int32), ("kappa0", C.c_double), ("t0", C.c_double)]
@@ -204,6 +223,7 @@ SYMBOLS = {
     "ptnn_elpd": (C.c_int, [C.c_void_p, C.POINTER(ElpdSpec)]),
     "ptnn_forecast": (C.c_int, [C.c_void_p, C.POINTER(ForecastSpec)]),
     "ptnn_evidence": (C.c_int, [C.c_void_p, C.POINTER(EvidenceSpec)]),
+    "ptnn_calibration": (C.c_int, [C.c_void_p, C.POINTER(CalibrationSpec)]),
 }
 
 
@@ -734,6 +754,51 @@ class Sampler:
         ns, nd = C.c_int64(0), C.c_int64(0)
         spec.n_samples, spec.n_distinct = C.pointer(ns), C.pointer(nd)
         self._check(self.lib.ptnn_elpd(self.h, C.byref(spec)))
+        out["n_samples"], out["n_distinct"] = ns.value, nd.value
+        return out
+
+    def calibration(self, data="test", *, replicas=None, step0=0, nsteps=None, thin=1, w=None, eta=None, multiplicity=None,
+                    quantiles=(), crps=True):
+        """ptnn_calibration: the predictive distribution of the targets, scored per data row on the device.  Source: the trace rows
+        step0, step0 + thin, ... < step0 + nsteps of `replicas` (None = all), or host vectors w [n, P] with eta [n] (regression)
+        and optional integer `multiplicity` [n].  data: "train", "test" or rows [n_rows, n_in + 1] (last column the target).
+        Regression -> dict(pit, pred_mean, pred_sd [n_rows] float64, crps [n_rows] (crps=True: the all-pairs term), quantiles
+        [len(quantiles), n_rows] of the levels `quantiles` in (0, 1)); classification -> dict(p_mean [n_rows, n_out]); both
+        n_samples, n_distinct; what does not apply is None."""
+        spec = CalibrationSpec()
+        spec.struct_bytes = C.sizeof(CalibrationSpec)
+        keep = []
+        dp = C.POINTER(C.c_double)
+        self._rows(spec, keep, data, "data", (self.cfg.n_in + 1, "n_in inputs and the target"))
+        if w is not None:
+            n = self._host_vectors(spec, keep, w, eta)
+            self._multiplicity(spec, keep, multiplicity, (n,), "multiplicity must have one entry per sample")
+        else:
+            self._trace_source(spec, keep, replicas, step0, nsteps, thin)
+        n_rows, reg = spec.n_rows, self.cfg.task == TASK_REG
+        lp = np.ascontiguousarray(quantiles, dtype=np.float64).reshape(-1)
+        if lp.size > CALIB_MAX_LEVELS:
+            raise ValueError(f"{lp.size} quantile levels: at most {CALIB_MAX_LEVELS} per call")
+        if lp.size and not (np.all(lp > 0.0) and np.all(lp < 1.0)):
+            raise ValueError(f"quantile levels must lie in (0, 1), got {lp.tolist()}")
+        if lp.size and not reg:
+            raise ValueError("quantiles: a classification has no predictive quantiles")
+        lz = np.array([NormalDist().inv_cdf(float(p)) for p in lp], dtype=np.float64)
+        keep += [lp, lz]
+        out = dict(pit=None, crps=None, pred_mean=None, pred_sd=None, quantiles=None, p_mean=None)
+        if reg:
+            out.update(pit=np.empty(n_rows), pred_mean=np.empty(n_rows), pred_sd=np.empty(n_rows),
+                       crps=np.empty(n_rows) if crps else None, quantiles=np.empty((lp.size, n_rows)) if lp.size else None)
+            spec.pair_term = 1 if crps else 0
+            if lp.size:
+                spec.levels_p, spec.levels_z, spec.n_levels = lp.ctypes.data_as(dp), lz.ctypes.data_as(dp), lp.size
+        else:
+            out.update(p_mean=np.empty((n_rows, self.cfg.n_out)))
+        for k, v in out.items():
+            setattr(spec, k, v.ctypes.data_as(dp) if v is not None else None)
+        ns, nd = C.c_int64(0), C.c_int64(0)
+        spec.n_samples, spec.n_distinct = C.pointer(ns), C.pointer(nd)
+        self._check(self.lib.ptnn_calibration(self.h, C.byref(spec)))
         out["n_samples"], out["n_distinct"] = ns.value, nd.value
         return out
 

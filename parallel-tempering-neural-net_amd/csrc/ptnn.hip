@@ -2960,6 +2960,136 @@ int ptnn_evidence(ptnn_handle* h, const ptnn_evidence_spec* spec) {
     return 0;
 }
 
+// ---- calibration (ptnn_dev_calibration.hpp) ----
+static_assert(PTNN_CALIB_MAX_LEVELS == CALIB_MAX_LEVELS && PTNN_CALIB_MAX_DISTINCT == CALIB_MAX_DISTINCT, "ptnn.h calibration limits");
+
+int ptnn_calibration(ptnn_handle* h, const ptnn_calibration_spec* spec) {
+    // argument checks first: none of them needs the handle or a device
+    if (int rc = check_spec(spec, "ptnn_calibration_spec")) return rc;
+    const ptnn_calibration_spec& s = *spec;
+    const bool host_src = s.w != nullptr;
+    SampleSource src = source_of(s, host_src, s.eta);
+    const RowSource rows{s.x_source, s.x, s.n_rows, "x_source", "PTNN_PREDICT_X", "x", "n_rows"};
+    if (!src.host && s.nsteps < 1) return fail(-1, "no source: nsteps = %d trace rows and no host vectors w", s.nsteps);
+    if (int rc = check_source(src, "samples")) return rc;
+    if (s.n_rows < 1) return fail(-1, "n_rows = %d must be >= 1", s.n_rows);
+    if (int rc = check_rows(rows)) return rc;
+    if (s.n_levels < 0 || s.n_levels > CALIB_MAX_LEVELS) return fail(-1, "n_levels = %d outside [0, %d]", s.n_levels, CALIB_MAX_LEVELS);
+    if (s.n_levels > 0 && (!s.levels_p || !s.levels_z || !s.quantiles))
+        return fail(-1, "n_levels = %d needs levels_p, levels_z and quantiles", s.n_levels);
+    if (s.quantiles && s.n_levels == 0) return fail(-1, "quantiles requested without levels");
+    for (int k = 0; k < s.n_levels; ++k)
+        if (!(s.levels_p[k] > 0.0 && s.levels_p[k] < 1.0) || !std::isfinite(s.levels_z[k]))
+            return fail(-1, "levels_p[%d] = %g (levels_z %g): a quantile level lies in (0, 1)", k, s.levels_p[k], s.levels_z[k]);
+    if (s.crps && !s.pair_term) return fail(-1, "crps requested without pair_term");
+    if (src.host)
+        if (int rc = count_samples(nullptr, src)) return rc;
+    if (int rc = check_handle(h, "ptnn_calibration")) return rc;
+    const int I = h->cfg.n_in, O = h->cfg.n_out;
+    const bool reg = h->cfg.task == PTNN_TASK_REG;
+    const bool reg_out = s.pit || s.crps || s.pred_mean || s.pred_sd || s.quantiles || s.pair_term;
+    if (reg_out && (!reg || O != 1))
+        return fail(-1, "pit, crps, pred_mean, pred_sd and quantiles need a regression net with n_out == 1; this handle is a %s net "
+                        "with n_out = %d", reg ? "regression" : "classification", O);
+    if (s.p_mean && reg) return fail(-1, "p_mean: a regression has no class probabilities");
+    if (host_src && reg && !s.eta) return fail(-1, "a regression's host vectors need eta = log tau^2 (one per vector)");
+    if (int rc = fit_rows(h, rows)) return rc;
+    if (!src.host)
+        if (int rc = count_samples(h, src)) return rc;
+    const long long S = src.M;
+    if (S < 1) return fail(-1, "the selection holds no sample");
+    if (int rc = sample_limit(src)) return rc;
+    if (s.n_samples) *s.n_samples = S;
+
+    if (int rc = start_device(h)) return rc;
+    hipStream_t st = h->stream;
+    DeviceScratch mem;
+    const int n_rows = s.n_rows;
+    const float* d_x = nullptr;
+    int xs = 0;
+    if (int rc = upload_rows(h, mem, rows, I + 1, &d_x, &xs)) return rc;
+    // stage a: items -> distinct (w, eta) samples (a classification's: distinct w, as ptnn_predict's)
+    Distinct d;
+    if (int rc = distinct_samples(h, mem, src, reg, true, &d)) return rc;
+    const int U = d.U;
+    if (s.n_distinct) *s.n_distinct = U;
+    if (s.pair_term && U > CALIB_MAX_DISTINCT)
+        return fail(-1, "%d distinct samples: the pair term of the CRPS takes at most %d (U^2 / 2 terms per data row); select fewer "
+                        "samples (thin=, chains=) or leave the CRPS out (crps=False)", U, CALIB_MAX_DISTINCT);
+    const long long rows_blk = row_block(scratch_budget("PTNN_CALIB_SCRATCH_BYTES"), (size_t)U * sizeof(float) * O, n_rows);
+    float* d_fx = nullptr;
+    HIP_TRY(mem.alloc(&d_fx, (size_t)rows_blk * O * U));
+    ForwardPlan fwd;
+    if (int rc = fwd.init(h, "calibration")) return rc;
+
+    if (!reg) {
+        double* d_mean = nullptr;
+        HIP_TRY(mem.alloc(&d_mean, (size_t)n_rows * O));
+        for (long long r0 = 0; r0 < n_rows; r0 += rows_blk) {
+            const int nr = (int)std::min<long long>(rows_blk, n_rows - r0);
+            if (int rc = fwd.launch(h, d.base, d.run_off, d_x, xs, (int)r0, nr, U, d_fx)) return rc;
+            PredictRed ra{d_fx, d.run_cnt, U, O, (int)r0 * O, n_rows * O, S, 0, nullptr, d_mean, nullptr, nullptr};
+            hipLaunchKernelGGL(predict_reduce_kernel, dim3((unsigned)(nr * O)), dim3(PRED_THREADS), 0, st, ra);
+            HIP_TRY(hipGetLastError());
+        }
+        HIP_TRY(fetch(s.p_mean, d_mean, (size_t)n_rows * O, st));
+        return wait_stream(h);
+    }
+
+    double *d_tau2 = nullptr, *d_tau = nullptr, *d_itau = nullptr;
+    double *d_pit = nullptr, *d_crps = nullptr, *d_mean = nullptr, *d_sd = nullptr, *d_q = nullptr, *d_t1 = nullptr, *d_bound = nullptr;
+    unsigned long long* d_limbs = nullptr;
+    HIP_TRY(mem.alloc(&d_tau2, (size_t)U));
+    HIP_TRY(mem.alloc(&d_tau, (size_t)U));
+    HIP_TRY(mem.alloc(&d_itau, (size_t)U));
+    HIP_TRY(mem.alloc(&d_pit, (size_t)n_rows));
+    HIP_TRY(mem.alloc(&d_mean, (size_t)n_rows));
+    HIP_TRY(mem.alloc(&d_sd, (size_t)n_rows));
+    if (s.n_levels) HIP_TRY(mem.alloc(&d_q, (size_t)s.n_levels * n_rows));
+    if (s.pair_term) {
+        HIP_TRY(mem.alloc(&d_crps, (size_t)n_rows));
+        HIP_TRY(mem.alloc(&d_t1, (size_t)n_rows));
+        HIP_TRY(mem.alloc(&d_bound, (size_t)n_rows));
+        HIP_TRY(mem.alloc(&d_limbs, (size_t)n_rows * 4));
+        HIP_TRY(hipMemsetAsync(d_limbs, 0, (size_t)n_rows * 4 * sizeof(unsigned long long), st));
+    }
+    hipLaunchKernelGGL(calib_tau_kernel, dim3((unsigned)((U + CALIB_THREADS - 1) / CALIB_THREADS)), dim3(CALIB_THREADS), 0, st, U,
+                       (const float*)d.run_eta, d_tau2, d_tau, d_itau);
+    HIP_TRY(hipGetLastError());
+    CalibRow ra{};
+    ra.fx = d_fx; ra.tau2 = d_tau2; ra.tau = d_tau; ra.itau = d_itau; ra.cnt = d.run_cnt; ra.y = d_x + I; ra.ys = xs; ra.U = U;
+    ra.n_rows = n_rows; ra.S = S; ra.n_levels = s.n_levels; ra.pair = s.pair_term ? 1 : 0;
+    for (int k = 0; k < s.n_levels; ++k) { ra.p[k] = s.levels_p[k]; ra.z[k] = s.levels_z[k]; }
+    ra.pit = d_pit; ra.pred_mean = d_mean; ra.pred_sd = d_sd; ra.quantiles = d_q; ra.term1 = d_t1; ra.pair_bound = d_bound;
+    const int n_tiles = (U + CALIB_THREADS - 1) / CALIB_THREADS;
+    CalibPair pa{d_fx, d_tau2, d.run_cnt, d_bound, U, 0, 0, n_tiles, d_limbs};
+    const unsigned n_tri = (unsigned)((long long)n_tiles * (n_tiles + 1) / 2);
+    for (long long r0 = 0; r0 < n_rows; r0 += rows_blk) {
+        const int nr = (int)std::min<long long>(rows_blk, n_rows - r0);
+        if (int rc = fwd.launch(h, d.base, d.run_off, d_x, xs, (int)r0, nr, U, d_fx)) return rc;
+        ra.row0 = (int)r0;
+        hipLaunchKernelGGL(calib_row_kernel, dim3((unsigned)nr), dim3(CALIB_THREADS), 0, st, ra);
+        HIP_TRY(hipGetLastError());
+        // the pair term of this block's rows, at most 65535 rows (grid.y) per launch
+        for (int q0 = 0; s.pair_term && q0 < nr; q0 += 65535) {
+            pa.row0 = (int)r0; pa.r0 = q0;
+            hipLaunchKernelGGL(calib_pair_kernel, dim3(n_tri, (unsigned)std::min(65535, nr - q0)), dim3(CALIB_THREADS), 0, st, pa);
+            HIP_TRY(hipGetLastError());
+        }
+    }
+    if (s.pair_term) {
+        hipLaunchKernelGGL(calib_finish_kernel, dim3((unsigned)((n_rows + CALIB_THREADS - 1) / CALIB_THREADS)), dim3(CALIB_THREADS), 0, st,
+                           n_rows, (const unsigned long long*)d_limbs, (const double*)d_t1, (const double*)d_bound, S, d_crps);
+        HIP_TRY(hipGetLastError());
+    }
+    HIP_TRY(fetch(s.pit, d_pit, (size_t)n_rows, st));
+    HIP_TRY(fetch(s.pred_mean, d_mean, (size_t)n_rows, st));
+    HIP_TRY(fetch(s.pred_sd, d_sd, (size_t)n_rows, st));
+    HIP_TRY(fetch(s.quantiles, d_q, (size_t)s.n_levels * n_rows, st));
+    HIP_TRY(fetch(s.crps, d_crps, (size_t)n_rows, st));
+    return wait_stream(h);
+}
+
 static int run_model(ptnn_handle* h, int mode, const float* w_in, const float* tau_sq, int n, float* out, size_t out_floats,
                      int a0, int a1) {
     if (!h) return fail(-1, "null handle");

@@ -151,6 +151,7 @@ struct SegDyn {
 #include "ptnn_dev_convergence.hpp"          // convergence diagnostics: split-R-hat, split-ESS over trace columns (main translation unit only)
 #include "ptnn_dev_elpd.hpp"                 // predictive accuracy: lppd, WAIC, PSIS-LOO per data row (main translation unit only)
 #include "ptnn_dev_evidence.hpp"             // log evidence: per-rung statistics of the full-data log-likelihood, prior draws (main translation unit only)
+#include "ptnn_dev_calibration.hpp"          // calibration: PIT, quantiles and CRPS of the predictive mixture per data row (main translation unit only)
 #endif
 
 }  // namespace ptnn

@@ -261,6 +261,104 @@ def elpd_compare(a, b):
                 elpd_waic_diff=float(np.sum(wa) - np.sum(wb)), se_waic_diff=_se_total(wa - wb))
 
 
+# predictive_calibration's result.  Regression: crps, se_crps (float; None with crps=False); crps_i, pit, pred_mean, pred_sd
+# [n_rows] float64; pit_hist [bins] counts of the PIT in equal-width bins of (0, 1); coverage {level: share of rows inside the
+# central interval of that level}; quantiles {p: [n_rows]}; intervals {(p_lo, p_hi): dict(level, width, score)} for every
+# symmetric pair of quantiles.  Classification: brier, log_score (means), brier_i, log_score_i [n_rows]; p_mean [n_rows, n_out];
+# confidence, correct [n_rows]; reliability dict(edges, count, confidence, accuracy) over `bins` confidence bins; ece, mce.
+# What does not apply to the task is None.  n_samples; n_distinct
+Calibration = namedtuple("Calibration", "crps se_crps crps_i pit pit_hist coverage quantiles intervals pred_mean pred_sd "
+                         "brier log_score brier_i log_score_i p_mean confidence correct reliability ece mce n_samples n_distinct")
+
+
+def check_probability_levels(name, values, limit=None):
+    """Levels strictly inside (0, 1), at most `limit` of them -> list of float."""
+    v = [float(x) for x in values]
+    if limit is not None and len(v) > limit:
+        raise ValueError(f"{len(v)} {name}: at most {limit} per call")
+    if any(not (0.0 < x < 1.0) for x in v):
+        raise ValueError(f"{name} must lie in (0, 1), got {v}")
+    return v
+
+
+def pit_coverage(pit, levels=(0.5, 0.8, 0.9, 0.95)):
+    """Share of rows whose target lies inside the central predictive interval of each level q: (1 - q) / 2 <= pit <= (1 + q) / 2
+    (exact: no quantile is needed).  -> {q: share}."""
+    pit = np.asarray(pit, dtype=np.float64)
+    return {q: float(np.mean((pit >= (1.0 - q) / 2.0) & (pit <= (1.0 + q) / 2.0))) for q in check_probability_levels("levels", levels)}
+
+
+def pit_histogram(pit, bins=10):
+    """Counts of the PIT values in `bins` equal-width bins of (0, 1) (np.histogram: uniform when the model is calibrated)."""
+    return np.histogram(np.asarray(pit, dtype=np.float64), int(bins), (0.0, 1.0))[0]
+
+
+def interval_scores(levels, quantiles, y):
+    """For every symmetric pair (a / 2, 1 - a / 2) among the quantile `levels` (quantiles [len(levels), n_rows], targets y): the
+    mean width u - l and the mean interval score (u - l) + (2 / a) (l - y)_+ + (2 / a) (y - u)_+ (Gneiting & Raftery 2007).
+    -> {(p_lo, p_hi): dict(level = 1 - a, width, score)}."""
+    lv = [float(p) for p in levels]
+    q = np.asarray(quantiles, dtype=np.float64).reshape(len(lv), -1)
+    y = np.asarray(y, dtype=np.float64).reshape(-1)
+    out = {}
+    for i, lo in enumerate(lv):
+        for j, hi in enumerate(lv):
+            if lo < hi and abs(lo + hi - 1.0) <= 1e-12:
+                a = 2.0 * lo
+                l, u = q[i], q[j]
+                score = (u - l) + (2.0 / a) * np.maximum(l - y, 0.0) + (2.0 / a) * np.maximum(y - u, 0.0)
+                out[(lo, hi)] = dict(level=1.0 - a, width=float(np.mean(u - l)), score=float(np.mean(score)))
+    return out
+
+
+def crps_summary(crps_i):
+    """-> (mean CRPS, its standard error sd(ddof 1) / sqrt(N))."""
+    c = np.asarray(crps_i, dtype=np.float64)
+    return float(np.mean(c)), (float(np.std(c, ddof=1) / math.sqrt(c.size)) if c.size > 1 else float("nan"))
+
+
+def reliability_table(confidence, correct, bins=10):
+    """Reliability of a classifier's confidence over `bins` equal-width bins of [0, 1] (a value on an edge goes to the upper bin,
+    1.0 to the last) -> dict(edges [bins + 1], count [bins], confidence, accuracy [bins] (nan in an empty bin), ece = sum_b
+    (count_b / N) |accuracy_b - confidence_b|, mce = the largest gap over the non-empty bins)."""
+    bins = int(bins)
+    if bins < 1:
+        raise ValueError(f"bins = {bins} must be >= 1")
+    conf = np.asarray(confidence, dtype=np.float64).reshape(-1)
+    hit = np.asarray(correct, dtype=np.float64).reshape(-1)
+    edges = np.arange(bins + 1) / bins
+    idx = np.clip(np.searchsorted(edges, conf, side="right") - 1, 0, bins - 1)
+    count = np.bincount(idx, minlength=bins)
+    with np.errstate(invalid="ignore", divide="ignore"):
+        mconf = np.bincount(idx, weights=conf, minlength=bins) / count
+        acc = np.bincount(idx, weights=hit, minlength=bins) / count
+    full = count > 0
+    gap = np.abs(acc[full] - mconf[full])
+    return dict(edges=edges, count=count, confidence=mconf, accuracy=acc,
+                ece=float(np.sum(count[full] / conf.size * gap)), mce=float(np.max(gap)) if gap.size else float("nan"))
+
+
+def classification_scores(p_mean, y, bins=10):
+    """Proper scores and reliability of predictive class probabilities p_mean [n_rows, n_out] against labels y: brier_i = sum_k
+    (p_k - 1[y = k])^2, log_score_i = -log p_y, confidence = max_k p_k, correct = (argmax == y) (first index on a tie), and
+    reliability_table() of the last two.  -> dict(brier_i, log_score_i, confidence, correct, reliability, ece, mce)."""
+    p = np.asarray(p_mean, dtype=np.float64)
+    lab = np.asarray(y).reshape(-1).astype(np.int64)
+    if p.ndim != 2 or p.shape[0] != lab.size:
+        raise ValueError(f"p_mean {p.shape} and {lab.size} labels do not match")
+    if lab.size and (lab.min() < 0 or lab.max() >= p.shape[1]):
+        raise ValueError(f"labels must lie in [0, {p.shape[1]})")
+    rows = np.arange(lab.size)
+    onehot = np.zeros_like(p)
+    onehot[rows, lab] = 1.0
+    with np.errstate(divide="ignore"):
+        log_score = -np.log(p[rows, lab])
+    conf, correct = np.max(p, axis=1), np.argmax(p, axis=1) == lab
+    rel = reliability_table(conf, correct, bins)
+    return dict(brier_i=np.sum((p - onehot) ** 2, axis=1), log_score_i=log_score, confidence=conf, correct=correct,
+                reliability={k: rel[k] for k in ("edges", "count", "confidence", "accuracy")}, ece=rel["ece"], mce=rel["mce"])
+
+
 # scalar trace columns convergence_diagnostics takes by name (a regression's acc_train slot holds eta = log tau^2)
 _SCALAR_COLS = {"likelihood": _lib.TR_LIKEH, "rmse_train": _lib.TR_RMSE_TR, "rmse_test": _lib.TR_RMSE_TE, "acc_train": _lib.TR_ACC_TR,
                 "eta": _lib.TR_ACC_TR, "acc_test": _lib.TR_ACC_TE}
@@ -968,6 +1066,64 @@ class ParallelTemperingBase:
                                   p_waic_i=p_waic_i, khat=khat, good_k=good_k, n_high_k=n_high,
                                   log_lik=(loglik if loglik is not None else out["loglik"]) if return_pointwise else None,
                                   n_samples=n_s, n_distinct=out["n_distinct"])
+
+    # ------------------------------------------------------------------ calibration (not in the reference)
+    def predictive_calibration(self, data="test", *, burn_in=None, chains="all", thin=1, weights=None, eta=None,
+                               quantiles=(0.05, 0.95), levels=(0.5, 0.8, 0.9, 0.95), bins=10, crps=True):
+        """Is the predictive band right?  Calibration and proper scores of the predictive distribution of the targets, computed
+        on the GPU from the sampled chains.
+
+        Regression: the predictive distribution of y on a row is the mixture (1/S) sum_s N(f_s(x), tau_s^2) with each sample's
+        own observation noise tau_s^2 = exp(eta_s) -- not the band of the mean function that posterior_predictive() returns.
+        Per row: pit = F(y) (uniform on (0, 1) when the model is calibrated; pit_hist), pred_mean, pred_sd, the quantiles of y
+        at the levels `quantiles` (at most 16, in (0, 1)), and crps_i, the continuous ranked probability score (closed form of a
+        Gaussian mixture; a sum over all pairs of distinct samples, refused above 65536 of them: thin=, chains= or crps=False).
+        coverage[q]: the share of rows inside the central interval of level q, from the PIT; intervals: the mean width and
+        interval score of every symmetric pair of quantiles.  Classification: p_mean, the Brier and log scores, and the
+        reliability table of the confidence max_k p_mean over `bins` bins with its expected / maximum calibration error.
+
+        Samples, `chains`, `thin`, `weights` (with `eta` for a regression) and `data` as predictive_accuracy().
+        -> Calibration."""
+        I = int(self.topology[0])
+        cls = self.task == TASK_CLS
+        qs = check_probability_levels("quantiles", quantiles, _lib.CALIB_MAX_LEVELS)
+        lv = check_probability_levels("levels", levels)
+        if int(bins) < 1:
+            raise ValueError(f"bins = {bins} must be >= 1")
+        if isinstance(data, str):
+            if data not in ("train", "test"):
+                raise ValueError(f"data must be 'train', 'test' or an array, not {data!r}")
+            ds = data
+            y = np.asarray(self.traindata if data == "train" else self.testdata)[:, I]
+        else:
+            xa = np.asarray(data)
+            if xa.ndim != 2 or xa.shape[1] < I + 1:
+                raise ValueError(f"data must be 2-D with at least n_in + 1 = {I + 1} columns (inputs, target), got shape {xa.shape}")
+            ds = np.ascontiguousarray(xa[:, :I + 1], dtype=np.float32)
+            y = ds[:, I]
+        if weights is not None:
+            w, mult = self._weights(weights)
+            if not cls and eta is None:
+                raise ValueError("a regression's weights need eta = log tau^2, one per vector (Sampler.eta_trace())")
+            kw = dict(w=w, eta=None if cls else eta, multiplicity=mult)
+        self._need_sampler("predictive_calibration")
+        if weights is None:
+            kw, _ = self._trace_selection(burn_in, chains, thin)
+        out = self._sampler.calibration(ds, quantiles=() if cls else qs, crps=bool(crps) and not cls, **kw)
+        none = dict.fromkeys(Calibration._fields)
+        none.update(n_samples=out["n_samples"], n_distinct=out["n_distinct"])
+        if cls:
+            sc = classification_scores(out["p_mean"], y, bins)
+            none.update(sc, p_mean=out["p_mean"], brier=float(np.mean(sc["brier_i"])), log_score=float(np.mean(sc["log_score_i"])))
+            return Calibration(**none)
+        y32 = np.asarray(y, dtype=np.float32).astype(np.float64)              # the targets as the device reads them
+        q = out["quantiles"]
+        none.update(crps_i=out["crps"], pit=out["pit"], pit_hist=pit_histogram(out["pit"], bins), coverage=pit_coverage(out["pit"], lv),
+                    quantiles={p: q[k] for k, p in enumerate(qs)}, intervals=interval_scores(qs, q, y32) if qs else {},
+                    pred_mean=out["pred_mean"], pred_sd=out["pred_sd"])
+        if out["crps"] is not None:
+            none["crps"], none["se_crps"] = crps_summary(out["crps"])
+        return Calibration(**none)
 
     # ------------------------------------------------------------------ recursive forecasts (not in the reference)
     def forecast(self, horizon, origin="end", *, burn_in=None, chains="all", thin=1, percentiles=(5, 95), noise=False, seed=None,
