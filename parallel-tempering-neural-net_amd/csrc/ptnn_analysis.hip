@@ -1,0 +1,1159 @@
+// ptnn_analysis.hip -- the posterior analysis calls of libptnn.so: predict, convergence, elpd, forecast, evidence, calibration,
+// and the sample-selection path they share.  The shape-independent analysis kernels are defined in this object: it includes them.
+#include "ptnn_shapes.hpp"
+namespace ptnn {
+#include "ptnn_dev_select.hpp"               // sample selection (run-length pass over the selected rows) and the per-column predictive reduction
+#include "ptnn_dev_convergence.hpp"          // convergence diagnostics: split-R-hat, split-ESS over trace columns
+#include "ptnn_dev_elpd.hpp"                 // predictive accuracy: lppd, WAIC, PSIS-LOO per data row
+#include "ptnn_dev_evidence.hpp"             // log evidence: per-rung statistics of the full-data log-likelihood, prior draws
+#include "ptnn_dev_calibration.hpp"          // calibration: PIT, quantiles and CRPS of the predictive mixture per data row
+}  // namespace ptnn
+#include "ptnn_host.hpp"
+
+#include <algorithm>
+#include <cmath>
+#include <cstdlib>
+#include <cstring>
+#include <vector>
+
+using namespace ptnn;
+
+namespace {
+struct DeviceScratch {            // every buffer of one analysis call, released on every return path
+    std::vector<void*> ptrs;
+    ~DeviceScratch() { for (void* p : ptrs) (void)hipFree(p); }
+    template <typename T> hipError_t alloc(T** p, size_t n) {
+        *p = nullptr;
+        if (n == 0) return hipSuccess;
+        void* q = nullptr;
+        const hipError_t e = hipMalloc(&q, n * sizeof(T));
+        if (e == hipSuccess) { ptrs.push_back(q); *p = static_cast<T*>(q); }
+        return e;
+    }
+    template <typename T> hipError_t upload(T** p, const T* src, size_t n, hipStream_t st) {     // alloc + copy of n host values
+        const hipError_t e = alloc(p, n);
+        return e != hipSuccess ? e : hipMemcpyAsync(*p, src, n * sizeof(T), hipMemcpyHostToDevice, st);
+    }
+};
+
+template <typename T> hipError_t fetch(T* dst, const T* src, size_t n, hipStream_t st) {   // an output the caller asked for (non-null)
+    return dst ? hipMemcpyAsync(dst, src, n * sizeof(T), hipMemcpyDeviceToHost, st) : hipSuccess;
+}
+
+size_t scratch_budget(const char* var) {    // $var bytes, default 1 GiB
+    const char* e = std::getenv(var);
+    if (e && *e) {
+        const long long v = std::atoll(e);
+        if (v > 0) return (size_t)v;
+    }
+    return (size_t)1 << 30;
+}
+
+// the first check of every analysis call: the spec itself
+template <class Spec> int check_spec(const Spec* spec, const char* name) {
+    if (!spec) return fail(-1, "null argument");
+    if (spec->struct_bytes != (int32_t)sizeof(Spec)) return fail(-1, "%s.struct_bytes = %d, expected %d", name, spec->struct_bytes, (int)sizeof(Spec));
+    return 0;
+}
+// the handle of an analysis call (after the argument checks): ready, and one GPU
+int check_handle(ptnn_handle* h, const char* fn) {
+    if (int rc = check_ready(h)) return rc;
+    if (h->comm.kind != COMM_NONE) return fail(-3, "%s serves one GPU: this handle has a communicator attached", fn);
+    return 0;
+}
+// the device work of an analysis call starts behind everything queued; a failed run is refused here
+int start_device(ptnn_handle* h) {
+    HIP_TRY(hipSetDevice(h->cfg.device_id));
+    return finish_stream(h);
+}
+
+// the trace rows step0, step0 + thin, ... < step0 + nsteps of the listed local replicas (NULL = all): the residency, checkpoint
+// and ring rules of ptnn_get_traces; *reps = the chains, *m = rows per chain.
+int select_trace_rows(const ptnn_handle* h, const int32_t* replicas, int n_replicas, int step0, int nsteps, int thin,
+                      std::vector<int32_t>* reps, int* m) {
+    const int S = h->cfg.n_samples, Rl = h->cfg.n_replicas_local, cap = h->cap;
+    if (step0 < 0 || nsteps < 1 || step0 + nsteps > S) return fail(-1, "trace range [%d, %d) outside [0, %d)", step0, step0 + nsteps, S);
+    if (step0 + nsteps > h->cur + 1) return fail(-1, "rows up to %d requested but only %d MH steps have been queued", step0 + nsteps - 1, h->cur);
+    if (step0 < h->first_row) return fail(-1, "rows below %d were produced before the checkpoint these chains were restored from", h->first_row);
+    if (step0 < h->cur + 1 - cap) return fail(-1, "row %d has already been overwritten in the trace ring (capacity %d, %d steps done)", step0, cap, h->cur);
+    reps->clear();
+    if (replicas) {
+        for (int k = 0; k < n_replicas; ++k) {
+            if (replicas[k] < 0 || replicas[k] >= Rl) return fail(-1, "replica %d out of range [0, %d)", replicas[k], Rl);
+            reps->push_back(replicas[k]);
+        }
+    } else {
+        for (int r = 0; r < Rl; ++r) reps->push_back(r);
+    }
+    *m = (nsteps + thin - 1) / thin;
+    return 0;
+}
+
+// The weight vectors an analysis call reads, from the fields every spec names alike: host vectors w [n_w][P] (with eta [n_w] and
+// integer multiplicities [n_w], each optional), or the trace rows of select_trace_rows.
+struct SampleSource {
+    bool host;                      // host vectors (ptnn_elpd: also a host loglik); else trace rows
+    const float* w;
+    const float* eta;
+    int64_t n_w;
+    const int32_t* multiplicity;
+    const int32_t* replicas;
+    int n_replicas, step0, nsteps, thin;
+    std::vector<int32_t> reps;      // trace: the chains
+    int m = 0;                      // trace: rows per chain
+    long long n_items = 0, M = 0;   // host vectors or trace rows; samples, multiplicities counted
+    const int32_t* weights() const { return host ? multiplicity : nullptr; }
+};
+template <class Spec> SampleSource source_of(const Spec& s, bool host, const float* eta) {
+    return SampleSource{host, s.w, eta, s.n_w, s.multiplicity, s.replicas, s.n_replicas, s.step0, s.nsteps, s.thin};
+}
+// the checks that need no handle; `unit` names a host item in the message
+int check_source(const SampleSource& src, const char* unit) {
+    if (src.host) return src.n_w < 1 ? fail(-1, "n_w = %lld host %s: need at least one", (long long)src.n_w, unit) : 0;
+    if (src.thin < 1) return fail(-1, "thin = %d must be >= 1", src.thin);
+    if (src.replicas && src.n_replicas < 1) return fail(-1, "n_replicas = %d with a replica list", src.n_replicas);
+    return 0;
+}
+// n_items and M: host multiplicities summed (no handle needed), or the trace rows selected
+int count_samples(const ptnn_handle* h, SampleSource& src) {
+    if (src.host) {
+        src.n_items = src.n_w;
+        src.M = src.multiplicity ? 0 : src.n_w;
+        for (int64_t k = 0; src.multiplicity && k < src.n_w; ++k) {
+            if (src.multiplicity[k] < 0) return fail(-1, "multiplicity[%lld] = %d is negative", (long long)k, src.multiplicity[k]);
+            src.M += src.multiplicity[k];
+        }
+        return 0;
+    }
+    if (int rc = select_trace_rows(h, src.replicas, src.n_replicas, src.step0, src.nsteps, src.thin, &src.reps, &src.m)) return rc;
+    src.n_items = src.M = (long long)src.reps.size() * src.m;
+    return 0;
+}
+int sample_limit(const SampleSource& src) {
+    if (src.M > 0x7fffffffLL || src.n_items > 0x7fffffffLL) return fail(-1, "%lld samples: at most 2^31 - 1 per call", src.M);
+    return 0;
+}
+
+// Stage a: the items of a source collapse into distinct samples -- maximal runs of bitwise-equal consecutive vectors of one chain
+// or of the host list -- with integer multiplicities (sample_runs_kernel, predict_scan_kernel).  `eta`: the samples are (w, eta)
+// -- a regression's eta is read, compared and checked, a classification's is 0 -- and every run gets its eta
+// (elpd_run_eta_kernel).  Without `merge` every item is a sample of its own with count 1 (forecast with noise: every occurrence
+// is its own trajectory).
+struct Distinct {
+    const float* base = nullptr;    // the vectors: d_pos_w rows or the uploaded host vectors
+    long long* run_off = nullptr;   // [U] float offset of sample u in base
+    int* run_cnt = nullptr;         // [U] its multiplicity
+    int* item_run = nullptr;        // [n_items] the sample of every item (merge)
+    float* run_eta = nullptr;       // [U] its eta (eta)
+    int U = 0;
+};
+int distinct_samples(ptnn_handle* h, DeviceScratch& mem, const SampleSource& src, bool eta, bool merge, Distinct* d) {
+    const long long n = src.n_items;
+    const bool reg = eta && h->cfg.task == PTNN_TASK_REG;
+    hipStream_t st = h->stream;
+    long long* item_off = nullptr;
+    int *flag = nullptr, *err = nullptr, *weight = nullptr, *reps = nullptr;
+    float *item_eta = nullptr, *w = nullptr, *host_eta = nullptr;
+    HIP_TRY(mem.alloc(&item_off, (size_t)n));
+    HIP_TRY(mem.alloc(&flag, (size_t)n));
+    HIP_TRY(mem.alloc(&d->run_cnt, (size_t)n));
+    HIP_TRY(mem.alloc(&err, 4));        // [0] runs, [1] unresolved compact rows, [2] rows without eta, [3] the first such chain
+    if (eta) HIP_TRY(mem.alloc(&item_eta, (size_t)n));
+    if (merge) {
+        HIP_TRY(mem.alloc(&d->run_off, (size_t)n));
+        HIP_TRY(mem.alloc(&d->item_run, (size_t)n));
+        if (eta) HIP_TRY(mem.alloc(&d->run_eta, (size_t)n));
+        HIP_TRY(hipMemsetAsync(d->run_cnt, 0, (size_t)n * sizeof(int), st));
+    } else {
+        d->run_off = item_off;
+        d->run_eta = item_eta;
+        HIP_TRY(hipMemsetD32Async(d->run_cnt, 1, (size_t)n, st));
+    }
+    HIP_TRY(hipMemsetAsync(err, 0, 3 * sizeof(int), st));
+    if (eta) HIP_TRY(hipMemsetAsync(err + 3, 0x7f, sizeof(int), st));
+    SampleSel sel{};
+    sel.reg = reg ? 1 : 0; sel.P = h->P; sel.n_items = n; sel.item_off = item_off; sel.item_eta = item_eta; sel.flag = flag;
+    sel.error = err + 1;
+    if (src.host) {
+        HIP_TRY(mem.upload(&w, src.w, (size_t)n * h->P, st));
+        if (reg) HIP_TRY(mem.upload(&host_eta, src.eta, (size_t)n, st));
+        if (merge && src.multiplicity) HIP_TRY(mem.upload(&weight, src.multiplicity, (size_t)n, st));
+        sel.host = 1; sel.pos_w = w; sel.host_eta = host_eta;
+    } else {
+        HIP_TRY(mem.upload(&reps, src.reps.data(), src.reps.size(), st));
+        sel.host = 0; sel.pos_w = h->d_pos_w; sel.scal = h->d_scal; sel.replicas = reps; sel.st_i = h->d_st_i; sel.cap = h->cap;
+        sel.PW = h->PW; sel.step0 = src.step0; sel.thin = src.thin; sel.m = src.m; sel.compact = h->plan.compact ? 1 : 0; sel.cur = h->cur;
+    }
+    d->base = sel.pos_w;
+    const unsigned item_blocks = (unsigned)((n + PRED_THREADS - 1) / PRED_THREADS);
+    hipLaunchKernelGGL(sample_runs_kernel, dim3(item_blocks), dim3(PRED_THREADS), 0, st, sel);
+    HIP_TRY(hipGetLastError());
+    if (merge) {
+        PredictScan sc{n, flag, item_off, weight, d->item_run, d->run_off, d->run_cnt, err};
+        hipLaunchKernelGGL(predict_scan_kernel, dim3(1), dim3(PRED_SCAN_THREADS), 0, st, sc);
+        HIP_TRY(hipGetLastError());
+        if (eta) {
+            hipLaunchKernelGGL(elpd_run_eta_kernel, dim3(item_blocks), dim3(ELPD_THREADS), 0, st, n, (const int*)flag,
+                               (const int*)d->item_run, (const float*)item_eta, d->run_eta);
+            HIP_TRY(hipGetLastError());
+        }
+    }
+    int e[4] = {0, 0, 0, 0};
+    HIP_TRY(hipMemcpyAsync(e, err, sizeof e, hipMemcpyDeviceToHost, st));
+    if (int rc = wait_stream(h)) return rc;          // also keeps the host arrays of `src` alive until the copies are done
+    if (e[1]) return fail(-2, "%d selected compact trace rows refer to rows that are not resident (internal error)", e[1]);
+    if (e[2]) {
+        const int c = e[3] >= 0 && e[3] < (int)src.reps.size() ? e[3] : 0;
+        return fail(-1, "%s%d selected trace rows precede their chain's first accepted MH step (chain %d, local replica %d, among "
+                        "others): no eta = log tau^2 was recorded for them; start the selection later (a larger burn_in)",
+                    merge ? "" : "noise: ", e[2], c, src.reps.empty() ? 0 : src.reps[(size_t)c]);
+    }
+    d->U = merge ? e[0] : (int)n;
+    if (d->U < 1 || d->U > n) return fail(-2, "run-length pass found %d distinct samples among %lld rows (internal error)", d->U, n);
+    return 0;
+}
+// the sample of every item on the host, for the selection-order outputs (queued: valid after the next wait_stream)
+int item_runs(ptnn_handle* h, const Distinct& d, long long n_items, std::vector<int>* out) {
+    out->resize((size_t)n_items);
+    if (!d.item_run) {
+        for (long long i = 0; i < n_items; ++i) (*out)[(size_t)i] = (int)i;
+        return 0;
+    }
+    HIP_TRY(hipMemcpyAsync(out->data(), d.item_run, (size_t)n_items * sizeof(int), hipMemcpyDeviceToHost, h->stream));
+    return 0;
+}
+// A block of per-sample outputs blk [ncols][U] on the device, expanded to the selection's order (chain-major, item i `mult[i]`
+// times, null: once): selected sample `row` gets its columns at out + row * row_stride + col0.
+template <typename T>
+int scatter_samples(ptnn_handle* h, const T* blk, int ncols, int U, const std::vector<int>& item_run, const int32_t* mult, T* out,
+                    size_t row_stride, size_t col0) {
+    std::vector<T> hb((size_t)ncols * U);
+    HIP_TRY(hipMemcpyAsync(hb.data(), blk, hb.size() * sizeof(T), hipMemcpyDeviceToHost, h->stream));
+    if (int rc = wait_stream(h)) return rc;
+    size_t row = 0;
+    for (size_t i = 0; i < item_run.size(); ++i) {
+        const size_t u = (size_t)item_run[i];
+        for (int k = 0, reps = mult ? mult[i] : 1; k < reps; ++k, ++row) {
+            T* dst = out + row * row_stride + col0;
+            for (int c = 0; c < ncols; ++c) dst[c] = hb[(size_t)c * U + u];
+        }
+    }
+    return 0;
+}
+
+// Input rows of an analysis call: `source` PTNN_PREDICT_X_HOST with host rows, or the handle's train / test set
+static_assert(PTNN_FORECAST_ORIGIN_HOST == PTNN_PREDICT_X_HOST && PTNN_FORECAST_ORIGIN_TRAIN == PTNN_PREDICT_X_TRAIN &&
+              PTNN_FORECAST_ORIGIN_TEST == PTNN_PREDICT_X_TEST, "ptnn.h row sources");
+struct RowSource {
+    int source;
+    const float* host;
+    int n;
+    const char *field, *prefix, *arg, *count;   // names in the messages: "x_source", "PTNN_PREDICT_X", "x", "n_rows"
+};
+int check_rows(const RowSource& r) {        // no handle needed
+    if (r.source != PTNN_PREDICT_X_HOST && r.source != PTNN_PREDICT_X_TRAIN && r.source != PTNN_PREDICT_X_TEST)
+        return fail(-1, "%s = %d is not %s_HOST, _TRAIN or _TEST", r.field, r.source, r.prefix);
+    if (r.source == PTNN_PREDICT_X_HOST && !r.host) return fail(-1, "%s %s_HOST needs %s", r.field, r.prefix, r.arg);
+    return 0;
+}
+int fit_rows(const ptnn_handle* h, const RowSource& r) {
+    if (r.source == PTNN_PREDICT_X_TRAIN && r.n != h->Ntr) return fail(-1, "%s = %d but the train set has %d rows", r.count, r.n, h->Ntr);
+    if (r.source == PTNN_PREDICT_X_TEST && r.n != h->Nte) return fail(-1, "%s = %d but the test set has %d rows", r.count, r.n, h->Nte);
+    return 0;
+}
+// the rows on the device: the host rows (`width` floats each) uploaded, or the data set; row k at *x + k * *xs
+int upload_rows(ptnn_handle* h, DeviceScratch& mem, const RowSource& r, int width, const float** x, int* xs) {
+    if (r.source == PTNN_PREDICT_X_HOST) {
+        float* d = nullptr;
+        HIP_TRY(mem.upload(&d, r.host, (size_t)r.n * width, h->stream));
+        *x = d; *xs = width;
+    } else {
+        *x = h->d_data + (r.source == PTNN_PREDICT_X_TEST ? (size_t)h->Ntr * h->IPY : 0);
+        *xs = h->IPY;
+    }
+    return 0;
+}
+
+// Stage b of predict, elpd and evidence: the per-shape predict_fwd, NV distinct vectors staged in LDS per work-group
+struct ForwardPlan {
+    int PV = 0, NV = 0;
+    size_t lds = 0;
+    int init(const ptnn_handle* h, const char* what) {
+        const int P = h->P;
+        PV = round_up4(P);
+        const int per_vec = PV + (PRED_THREADS / WAVE + 1) * h->cfg.n_out * WAVE;   // staged vector + partial sums + transposed tile
+        NV = std::max(1, std::min(PRED_MAX_NV, (48 * 1024 / 4) / per_vec));
+        lds = (size_t)NV * per_vec * sizeof(float);
+        if (lds > LDS_CEILING) return fail(-3, "%s: a %d-parameter vector does not fit in LDS", what, P);
+        return raise_lds_limit(reinterpret_cast<const void*>(h->shape->predict_fwd), lds);
+    }
+    // fx [nr * O][U] = the outputs of vectors base + run_off[u] on rows [r0, r0 + nr) of x
+    int launch(const ptnn_handle* h, const float* base, const long long* run_off, const float* x, int xs, int r0, int nr, int U, float* fx) const {
+        PredictFwd fa{base, run_off, x, xs, r0, nr, h->cfg.n_hidden, h->P, PV, U, NV, fx};
+        hipLaunchKernelGGL(h->shape->predict_fwd, dim3((unsigned)((U + NV - 1) / NV), (unsigned)((nr + WAVE - 1) / WAVE)), dim3(PRED_THREADS), lds,
+                           h->stream, fa);
+        HIP_TRY(hipGetLastError());
+        return 0;
+    }
+};
+// rows per block of the forward pass: `budget` bytes of scratch at `row_bytes` per row, and at most 65535 work-groups of WAVE
+// rows (grid.y of predict_fwd)
+long long row_block(size_t budget, size_t row_bytes, long long n_rows) {
+    return std::max(1LL, std::min<long long>({(long long)(budget / row_bytes), 65535LL * WAVE, n_rows}));
+}
+
+// the order statistics of predict and forecast: ranks [n_ranks] in the expanded multiset of M samples
+int check_ranks(int n_ranks, const int64_t* ranks, const void* order_stats) {
+    if (n_ranks < 0 || n_ranks > PTNN_PREDICT_MAX_RANKS) return fail(-1, "n_ranks = %d outside [0, %d]", n_ranks, PTNN_PREDICT_MAX_RANKS);
+    if (n_ranks > 0 && !ranks) return fail(-1, "n_ranks = %d but ranks is NULL", n_ranks);
+    if (order_stats && n_ranks == 0) return fail(-1, "order_stats requested without ranks");
+    return 0;
+}
+int check_rank_values(int n_ranks, const int64_t* ranks, long long M) {
+    for (int k = 0; k < n_ranks; ++k)
+        if (ranks[k] < 0 || ranks[k] >= M) return fail(-1, "rank %lld outside [0, %lld)", (long long)ranks[k], M);
+    return 0;
+}
+}  // namespace
+
+extern "C" {
+
+// ---- posterior predictive (ptnn_dev_predict.hpp) ----
+int ptnn_predict(ptnn_handle* h, const ptnn_predict_spec* spec) {
+    // argument checks first: none of them needs the handle or a device
+    if (int rc = check_spec(spec, "ptnn_predict_spec")) return rc;
+    const ptnn_predict_spec& s = *spec;
+    SampleSource src = source_of(s, s.w != nullptr, nullptr);
+    const RowSource rows{s.x_source, s.x, s.n_rows, "x_source", "PTNN_PREDICT_X", "x", "n_rows"};
+    if (int rc = check_source(src, "vectors")) return rc;
+    if (int rc = check_rows(rows)) return rc;
+    if (s.n_rows < 1) return fail(-1, "n_rows = %d must be >= 1", s.n_rows);
+    if (int rc = check_ranks(s.n_ranks, s.ranks, s.order_stats)) return rc;
+    if (int rc = check_handle(h, "ptnn_predict")) return rc;
+    const int I = h->cfg.n_in, O = h->cfg.n_out;
+    if (s.vote && h->cfg.task != PTNN_TASK_CLS) return fail(-1, "vote: a regression has no classes");
+    if (int rc = fit_rows(h, rows)) return rc;
+    if (int rc = count_samples(h, src)) return rc;
+    const long long M = src.M;
+    if (M < 1) return fail(-1, "the selection holds no sample");
+    if (int rc = sample_limit(src)) return rc;
+    if (int rc = check_rank_values(s.n_ranks, s.ranks, M)) return rc;
+    if (s.n_samples) *s.n_samples = M;
+
+    if (int rc = start_device(h)) return rc;
+    hipStream_t st = h->stream;
+    DeviceScratch mem;
+    const int ncols = s.n_rows * O;
+    const float* d_x = nullptr;
+    int xs = 0;
+    if (int rc = upload_rows(h, mem, rows, I, &d_x, &xs)) return rc;
+    Distinct d;
+    if (int rc = distinct_samples(h, mem, src, false, true, &d)) return rc;
+    const int U = d.U;
+    if (s.n_distinct) *s.n_distinct = U;
+    // outputs on the device for every column; votes as integer counts (exact whatever the order)
+    double* d_mean = nullptr; float* d_ostat = nullptr; long long* d_votes = nullptr; long long* d_ranks = nullptr;
+    HIP_TRY(mem.alloc(&d_mean, (size_t)ncols));
+    if (s.n_ranks) {
+        HIP_TRY(mem.alloc(&d_ostat, (size_t)s.n_ranks * ncols));
+        HIP_TRY(mem.upload(&d_ranks, (const long long*)s.ranks, (size_t)s.n_ranks, st));
+    }
+    if (h->cfg.task == PTNN_TASK_CLS) HIP_TRY(mem.alloc(&d_votes, (size_t)ncols));
+    // stage b + c in blocks of rows: fx scratch U x (rows x O) floats under the budget
+    const long long rows_blk = row_block(scratch_budget("PTNN_PREDICT_SCRATCH_BYTES"), (size_t)U * sizeof(float) * O, s.n_rows);
+    float* d_fx = nullptr;
+    HIP_TRY(mem.alloc(&d_fx, (size_t)rows_blk * O * U));
+    ForwardPlan fwd;
+    if (int rc = fwd.init(h, "posterior predictive")) return rc;
+    std::vector<int> item_run;
+    if (s.samples) if (int rc = item_runs(h, d, src.n_items, &item_run)) return rc;
+    for (long long r0 = 0; r0 < s.n_rows; r0 += rows_blk) {
+        const int nr = (int)std::min<long long>(rows_blk, s.n_rows - r0);
+        if (int rc = fwd.launch(h, d.base, d.run_off, d_x, xs, (int)r0, nr, U, d_fx)) return rc;
+        PredictRed ra{d_fx, d.run_cnt, U, O, (int)r0 * O, ncols, M, s.n_ranks, d_ranks, d_mean, d_ostat, d_votes};
+        hipLaunchKernelGGL(predict_reduce_kernel, dim3((unsigned)(nr * O)), dim3(PRED_THREADS), 0, st, ra);
+        HIP_TRY(hipGetLastError());
+        if (s.samples)
+            if (int rc = scatter_samples(h, d_fx, nr * O, U, item_run, src.weights(), s.samples, (size_t)s.n_rows * O, (size_t)r0 * O)) return rc;
+    }
+    std::vector<long long> votes_h(s.vote ? (size_t)ncols : 0);
+    HIP_TRY(fetch(s.mean, d_mean, (size_t)ncols, st));
+    HIP_TRY(fetch(s.order_stats, d_ostat, (size_t)s.n_ranks * ncols, st));
+    HIP_TRY(fetch(s.vote ? votes_h.data() : nullptr, d_votes, (size_t)ncols, st));
+    if (int rc = wait_stream(h)) return rc;
+    if (s.vote)
+        for (int c = 0; c < ncols; ++c) s.vote[c] = (double)votes_h[(size_t)c] / (double)M;
+    return 0;
+}
+
+// ---- convergence diagnostics (ptnn_dev_convergence.hpp) ----
+static_assert(PTNN_TR_LIKEH == TR_LIKEH && PTNN_TR_ACC_TE == TR_ACC_TE && PTNN_TR_ACCEPT == TR_ACCEPT && PTNN_TR_SRC == TR_SRC, "ptnn.h TR order");
+
+// split-R-hat / split-ESS of Q quantities over C chains of n draws, gathered by `ga` (its source fields set: trace rows, or
+// draws [C][n][Q] in device memory); outputs are host arrays, any may be null.  Shared by ptnn_convergence and ptnn_evidence.
+static int conv_drive(ptnn_handle* h, DeviceScratch& mem, ConvGather ga, const std::vector<int>& qcol, int C, int n, int n_lags,
+                      double* mean, double* var, double* r_hat, double* ess, int32_t* trunc_lag, double* ess_chain, double* rho) {
+    const int hl = n / 2, M = 2 * C, Q = (int)qcol.size();
+    const bool per_chain = ess_chain != nullptr;
+    const int NS = 1 + (per_chain ? C : 0);
+    hipStream_t st = h->stream;
+    int *d_qcol = nullptr, *d_error = nullptr;
+    HIP_TRY(mem.upload(&d_qcol, qcol.data(), (size_t)Q, st));
+    HIP_TRY(mem.alloc(&d_error, 1));
+    HIP_TRY(hipMemsetAsync(d_error, 0, sizeof(int), st));
+    ga.C = C; ga.n = n; ga.h = hl; ga.error = d_error;
+    // outputs of every quantity
+    double *d_mean = nullptr, *d_var = nullptr, *d_rhat = nullptr, *d_ess = nullptr, *d_essc = nullptr, *d_rho = nullptr;
+    int* d_trunc = nullptr;
+    HIP_TRY(mem.alloc(&d_mean, (size_t)Q));
+    HIP_TRY(mem.alloc(&d_var, (size_t)Q));
+    HIP_TRY(mem.alloc(&d_rhat, (size_t)Q));
+    HIP_TRY(mem.alloc(&d_ess, (size_t)Q));
+    HIP_TRY(mem.alloc(&d_trunc, (size_t)Q));
+    if (per_chain) HIP_TRY(mem.alloc(&d_essc, (size_t)C * Q));
+    if (n_lags) HIP_TRY(mem.alloc(&d_rho, (size_t)n_lags * Q));
+    // blocks of quantities: the scratch of one quantity, every stage's
+    const size_t per_q = sizeof(double) * ((size_t)M * hl + 2 * (size_t)M + 2 * (size_t)C + 2 + (size_t)CONV_MAX_LAGS * C)
+                       + sizeof(ConvSeq) * NS + sizeof(int) * (3 + (per_chain ? (size_t)C : 0));
+    const int Qb = (int)std::max<size_t>(1, std::min<size_t>(scratch_budget("PTNN_CONVERGENCE_SCRATCH_BYTES") / per_q, (size_t)Q));
+    double *d_x = nullptr, *d_smean = nullptr, *d_ssq = nullptr, *d_csum = nullptr, *d_cm2 = nullptr, *d_pmean = nullptr, *d_pvar = nullptr;
+    double* d_chain = nullptr;
+    ConvSeq* d_seq = nullptr;
+    int *d_full = nullptr, *d_copen = nullptr, *d_any = nullptr, *d_open = nullptr;
+    HIP_TRY(mem.alloc(&d_x, (size_t)Qb * M * hl));
+    HIP_TRY(mem.alloc(&d_smean, (size_t)Qb * M));
+    HIP_TRY(mem.alloc(&d_ssq, (size_t)Qb * M));
+    HIP_TRY(mem.alloc(&d_csum, (size_t)Qb * C));
+    HIP_TRY(mem.alloc(&d_cm2, (size_t)Qb * C));
+    HIP_TRY(mem.alloc(&d_pmean, (size_t)Qb));
+    HIP_TRY(mem.alloc(&d_pvar, (size_t)Qb));
+    HIP_TRY(mem.alloc(&d_chain, (size_t)CONV_MAX_LAGS * C * Qb));
+    HIP_TRY(mem.alloc(&d_seq, (size_t)Qb * NS));
+    HIP_TRY(mem.alloc(&d_full, (size_t)Qb));
+    if (per_chain) HIP_TRY(mem.alloc(&d_copen, (size_t)Qb * C));
+    HIP_TRY(mem.alloc(&d_any, (size_t)Qb));
+    HIP_TRY(mem.alloc(&d_open, (size_t)Qb));
+    std::vector<int> any_h((size_t)Qb), open_h((size_t)Qb);
+    for (int q0 = 0; q0 < Q; q0 += Qb) {
+        const int nq = std::min(Qb, Q - q0);
+        // 1. gather and moments
+        ga.qcol = d_qcol + q0; ga.nq = nq; ga.x = d_x; ga.smean = d_smean; ga.ssq = d_ssq; ga.csum = d_csum; ga.cm2 = d_cm2;
+        hipLaunchKernelGGL(conv_gather_kernel, dim3((unsigned)C, (unsigned)((nq + CONV_TILE - 1) / CONV_TILE)), dim3(CONV_THREADS), 0, st, ga);
+        HIP_TRY(hipGetLastError());
+        // 2. W, var+ and the state of every sequence
+        ConvMoments mo{d_smean, d_ssq, d_csum, d_cm2, nq, C, n, hl, NS, d_seq, d_pmean, d_pvar};
+        const long long nseq = (long long)nq * NS;
+        hipLaunchKernelGGL(conv_moments_kernel, dim3((unsigned)((nseq + CONV_THREADS - 1) / CONV_THREADS)), dim3(CONV_THREADS), 0, st, mo);
+        HIP_TRY(hipGetLastError());
+        HIP_TRY(hipMemsetAsync(d_full, 1, (size_t)nq * sizeof(int), st));             // non-zero: every sequence starts open
+        if (per_chain) HIP_TRY(hipMemsetAsync(d_copen, 1, (size_t)nq * C * sizeof(int), st));
+        int n_open = nq;
+        for (int k = 0; k < nq; ++k) open_h[(size_t)k] = k;
+        HIP_TRY(hipMemcpyAsync(d_open, open_h.data(), (size_t)nq * sizeof(int), hipMemcpyHostToDevice, st));
+        // 3. blocks of lags, each twice the last, for the quantities with a sequence still open
+        for (int t0 = 0, nl = CONV_LAG_TILE; n_open > 0 && t0 < hl; t0 += nl, nl = std::min(2 * nl, CONV_MAX_LAGS)) {
+            nl = std::min(nl, (hl - t0 + CONV_LAG_TILE - 1) / CONV_LAG_TILE * CONV_LAG_TILE);
+            ConvLags la{d_x, C, hl, d_open, n_open, d_full, d_copen, t0, d_chain};
+            hipLaunchKernelGGL(conv_lags_kernel, dim3((unsigned)((n_open + CONV_TILE - 1) / CONV_TILE), (unsigned)(nl / CONV_LAG_TILE), (unsigned)C), dim3(CONV_THREADS), 0, st, la);
+            HIP_TRY(hipGetLastError());
+            ConvStep sp{d_chain, d_open, n_open, C, hl, NS, t0, nl, n_lags, Q, q0, d_seq, d_full, d_copen, d_any, d_rho};
+            hipLaunchKernelGGL(conv_step_kernel, dim3((unsigned)n_open), dim3(WAVE), 0, st, sp);
+            HIP_TRY(hipGetLastError());
+            HIP_TRY(hipMemcpyAsync(any_h.data(), d_any, (size_t)nq * sizeof(int), hipMemcpyDeviceToHost, st));
+            if (int rc = wait_stream(h)) return rc;
+            const int was_open = n_open;
+            n_open = 0;
+            for (int k = 0; k < was_open; ++k)
+                if (any_h[(size_t)open_h[(size_t)k]]) open_h[(size_t)n_open++] = open_h[(size_t)k];
+            if (n_open) HIP_TRY(hipMemcpyAsync(d_open, open_h.data(), (size_t)n_open * sizeof(int), hipMemcpyHostToDevice, st));
+        }
+        if (n_open) return fail(-2, "%d quantities still open after every lag (internal error)", n_open);
+        // 4. tau, ess, r_hat
+        ConvFinish fi{d_seq, d_pmean, d_pvar, nq, NS, C, hl, Q, q0, d_mean, d_var, d_rhat, d_ess, d_essc, d_trunc};
+        hipLaunchKernelGGL(conv_finish_kernel, dim3((unsigned)((nseq + CONV_THREADS - 1) / CONV_THREADS)), dim3(CONV_THREADS), 0, st, fi);
+        HIP_TRY(hipGetLastError());
+    }
+    int err = 0;
+    HIP_TRY(hipMemcpyAsync(&err, d_error, sizeof(int), hipMemcpyDeviceToHost, st));
+    if (mean) HIP_TRY(hipMemcpyAsync(mean, d_mean, (size_t)Q * sizeof(double), hipMemcpyDeviceToHost, st));
+    if (var) HIP_TRY(hipMemcpyAsync(var, d_var, (size_t)Q * sizeof(double), hipMemcpyDeviceToHost, st));
+    if (r_hat) HIP_TRY(hipMemcpyAsync(r_hat, d_rhat, (size_t)Q * sizeof(double), hipMemcpyDeviceToHost, st));
+    if (ess) HIP_TRY(hipMemcpyAsync(ess, d_ess, (size_t)Q * sizeof(double), hipMemcpyDeviceToHost, st));
+    if (trunc_lag) HIP_TRY(hipMemcpyAsync(trunc_lag, d_trunc, (size_t)Q * sizeof(int32_t), hipMemcpyDeviceToHost, st));
+    if (per_chain) HIP_TRY(hipMemcpyAsync(ess_chain, d_essc, (size_t)C * Q * sizeof(double), hipMemcpyDeviceToHost, st));
+    if (n_lags) HIP_TRY(hipMemcpyAsync(rho, d_rho, (size_t)n_lags * Q * sizeof(double), hipMemcpyDeviceToHost, st));
+    if (int rc = wait_stream(h)) return rc;
+    if (err) return fail(-2, "%d selected compact trace rows refer to rows that are not resident (internal error)", err);
+    return 0;
+}
+
+int ptnn_convergence(ptnn_handle* h, const ptnn_convergence_spec* spec) {
+    // argument checks first: none of them needs the handle or a device
+    if (int rc = check_spec(spec, "ptnn_convergence_spec")) return rc;
+    const ptnn_convergence_spec& s = *spec;
+    const bool host_src = s.draws != nullptr;
+    constexpr int scalar_cols = (1 << TR_LIKEH) | (1 << TR_RMSE_TR) | (1 << TR_RMSE_TE) | (1 << TR_ACC_TR) | (1 << TR_ACC_TE);
+    if (host_src) {
+        if (s.n_chains < 1) return fail(-1, "n_chains = %d must be >= 1", s.n_chains);
+        if (s.n_draws < 4) return fail(-1, "n_draws = %d: the split chains need at least 4 draws per chain", s.n_draws);
+        if (s.n_quantities < 1) return fail(-1, "n_quantities = %d must be >= 1", s.n_quantities);
+    } else {
+        if (s.thin < 1) return fail(-1, "thin = %d must be >= 1", s.thin);
+        if (s.replicas && s.n_replicas < 1) return fail(-1, "n_replicas = %d with a replica list", s.n_replicas);
+        if (s.params && s.n_params < 0) return fail(-1, "n_params = %d with a parameter list", s.n_params);
+        if (s.scalars & ~scalar_cols)
+            return fail(-1, "scalars = 0x%x: only TR_LIKEH, TR_RMSE_TR, TR_RMSE_TE, TR_ACC_TR and TR_ACC_TE are quantities "
+                            "(not TR_ACCEPT, TR_LOGALPHA or TR_SRC)", (unsigned)s.scalars);
+    }
+    if (s.n_lags < 0) return fail(-1, "n_lags = %d must be >= 0", s.n_lags);
+    if (s.n_lags > 0 && !s.rho) return fail(-1, "n_lags = %d but rho is NULL", s.n_lags);
+    if (s.rho && s.n_lags == 0) return fail(-1, "rho requested with n_lags = 0");
+    if (int rc = check_handle(h, "ptnn_convergence")) return rc;
+    const int P = h->P, cap = h->cap;
+    // the selection: chains, draws per chain, the column of every quantity
+    std::vector<int32_t> reps;
+    std::vector<int> qcol;
+    int C = 0, n = 0;
+    if (host_src) {
+        C = s.n_chains; n = s.n_draws;
+        for (int q = 0; q < s.n_quantities; ++q) qcol.push_back(q);
+    } else {
+        if (int rc = select_trace_rows(h, s.replicas, s.n_replicas, s.step0, s.nsteps, s.thin, &reps, &n)) return rc;
+        C = (int)reps.size();
+        if (n < 4) return fail(-1, "%d draws per chain selected: the split chains need at least 4", n);
+        if (s.params) {
+            for (int k = 0; k < s.n_params; ++k) {
+                if (s.params[k] < 0 || s.params[k] >= P) return fail(-1, "parameter %d out of range [0, %d)", s.params[k], P);
+                qcol.push_back(s.params[k]);
+            }
+        } else {
+            for (int p = 0; p < P; ++p) qcol.push_back(p);
+        }
+        for (int c = 0; c < TR_COUNT; ++c)
+            if (s.scalars & (1 << c)) qcol.push_back(-1 - c);
+        if (qcol.empty()) return fail(-1, "no quantity selected");
+    }
+    const int hl = n / 2, Q = (int)qcol.size();
+    if (s.n_lags > hl) return fail(-1, "n_lags = %d exceeds the split-chain length %d", s.n_lags, hl);
+
+    if (int rc = start_device(h)) return rc;
+    hipStream_t st = h->stream;
+    DeviceScratch mem;
+    int* d_reps = nullptr;
+    float* d_draws = nullptr;
+    ConvGather ga{};
+    if (host_src) {
+        const size_t nd = (size_t)C * n * Q;
+        HIP_TRY(mem.upload(&d_draws, s.draws, nd, st));
+        ga.host = 1; ga.draws = d_draws; ga.Qh = Q;
+    } else {
+        HIP_TRY(mem.upload(&d_reps, reps.data(), reps.size(), st));
+        ga.host = 0; ga.pos_w = h->d_pos_w; ga.scal = h->d_scal; ga.replicas = d_reps; ga.cap = cap; ga.PW = h->PW;
+        ga.step0 = s.step0; ga.thin = s.thin; ga.compact = h->plan.compact ? 1 : 0;
+    }
+    return conv_drive(h, mem, ga, qcol, C, n, s.n_lags, s.mean, s.var, s.r_hat, s.ess, s.trunc_lag, s.ess_chain, s.rho);
+}
+
+// ---- predictive accuracy (ptnn_dev_elpd.hpp) ----
+static_assert(PTNN_ELPD_TAIL_CAP == ELPD_TAIL_CAP, "ptnn.h tail capacity");
+
+int ptnn_elpd(ptnn_handle* h, const ptnn_elpd_spec* spec) {
+    // argument checks first: none of them needs the handle or a device
+    if (int rc = check_spec(spec, "ptnn_elpd_spec")) return rc;
+    const ptnn_elpd_spec& s = *spec;
+    const bool ll_src = s.loglik != nullptr, host_src = s.w != nullptr;
+    SampleSource src = source_of(s, ll_src || host_src, s.eta);
+    const RowSource rows{s.x_source, s.x, s.n_rows, "x_source", "PTNN_PREDICT_X", "x", "n_rows"};
+    if (ll_src && host_src) return fail(-1, "give host vectors w or a host loglik, not both");
+    if (!(s.r_eff > 0.0) || !std::isfinite(s.r_eff)) return fail(-1, "r_eff = %g must be a finite number > 0", s.r_eff);
+    if (!src.host && s.nsteps < 1)
+        return fail(-1, "no source: nsteps = %d trace rows, and neither host vectors w nor a host loglik", s.nsteps);
+    if (int rc = check_source(src, "samples")) return rc;
+    if (s.n_rows < 1) return fail(-1, "n_rows = %d must be >= 1", s.n_rows);
+    if (!ll_src)
+        if (int rc = check_rows(rows)) return rc;
+    if (ll_src && s.loglik_out) return fail(-1, "loglik_out: the log-likelihood is the input of this source");
+    // the sample count of the host sources
+    if (src.host)
+        if (int rc = count_samples(nullptr, src)) return rc;
+    if (ll_src)
+        for (long long k = 0; k < src.n_items * s.n_rows; ++k)
+            if (!std::isfinite(s.loglik[k])) return fail(-1, "loglik[%lld, %lld] = %g is not finite", k / s.n_rows, k % s.n_rows, s.loglik[k]);
+    if (int rc = check_handle(h, "ptnn_elpd")) return rc;
+    const int I = h->cfg.n_in, O = h->cfg.n_out;
+    const bool reg = h->cfg.task == PTNN_TASK_REG;
+    if (host_src && reg && !s.eta) return fail(-1, "a regression's host vectors need eta = log tau^2 (one per vector)");
+    if (!ll_src)
+        if (int rc = fit_rows(h, rows)) return rc;
+    if (!ll_src && s.x_source == PTNN_PREDICT_X_HOST && !reg)
+        for (int n = 0; n < s.n_rows; ++n) {
+            const float yv = s.x[(size_t)n * (I + 1) + I];
+            if (!(yv >= 0.0f) || yv >= (float)O || yv != std::floor(yv))
+                return fail(-1, "class label %g in row %d is not an integer in [0, %d)", (double)yv, n, O);
+        }
+    if (!src.host)
+        if (int rc = count_samples(h, src)) return rc;
+    const long long n_items = src.n_items, S = src.M;
+    if (S < 2) return fail(-1, "the selection holds %lld samples: p_waic (a variance, ddof 1) needs at least 2", S);
+    if (int rc = sample_limit(src)) return rc;
+    const long long M = (long long)std::ceil(std::min(0.2 * (double)S, 3.0 * std::sqrt((double)S / s.r_eff)));
+    if (M > ELPD_TAIL_CAP)
+        return fail(-1, "%lld samples with r_eff = %g need a PSIS tail of M = %lld > %d samples: select fewer samples (thin=, chains=) "
+                        "or give a larger r_eff", S, s.r_eff, M, ELPD_TAIL_CAP);
+    if (s.n_samples) *s.n_samples = S;
+
+    if (int rc = start_device(h)) return rc;
+    hipStream_t st = h->stream;
+    DeviceScratch mem;
+    const int n_rows = s.n_rows;
+    double *d_lppd = nullptr, *d_pwaic = nullptr, *d_loo = nullptr, *d_khat = nullptr;
+    long long* d_tail = nullptr;
+    HIP_TRY(mem.alloc(&d_lppd, (size_t)n_rows));
+    HIP_TRY(mem.alloc(&d_pwaic, (size_t)n_rows));
+    HIP_TRY(mem.alloc(&d_loo, (size_t)n_rows));
+    HIP_TRY(mem.alloc(&d_khat, (size_t)n_rows));
+    HIP_TRY(mem.alloc(&d_tail, (size_t)n_rows));
+    ElpdRed ra{};
+    ra.O = O; ra.S = S; ra.M = (int)M;
+    ra.lppd = d_lppd; ra.p_waic = d_pwaic; ra.elpd_loo = d_loo; ra.khat = d_khat; ra.tail_len = d_tail;
+    auto copy_out = [&]() -> int {
+        HIP_TRY(fetch(s.lppd, d_lppd, (size_t)n_rows, st));
+        HIP_TRY(fetch(s.p_waic, d_pwaic, (size_t)n_rows, st));
+        HIP_TRY(fetch(s.elpd_loo, d_loo, (size_t)n_rows, st));
+        HIP_TRY(fetch(s.khat, d_khat, (size_t)n_rows, st));
+        HIP_TRY(fetch((long long*)s.tail_len, d_tail, (size_t)n_rows, st));
+        return wait_stream(h);
+    };
+
+    if (ll_src) {
+        // source 3: every host sample is its own entry (repeats need no merging: the reduction depends on the multiset only)
+        double* d_ll = nullptr;
+        int* d_cnt = nullptr;
+        HIP_TRY(mem.upload(&d_ll, s.loglik, (size_t)n_items * n_rows, st));
+        std::vector<int32_t> ones(s.multiplicity ? 0 : (size_t)n_items, 1);
+        HIP_TRY(mem.upload(&d_cnt, s.multiplicity ? s.multiplicity : ones.data(), (size_t)n_items, st));
+        if (!s.multiplicity)
+            if (int rc = wait_stream(h)) return rc;          // `ones` dies at the end of this block
+        ra.mode = ELPD_HOST; ra.ll = d_ll; ra.ll_stride = n_rows; ra.cnt = d_cnt; ra.U = (int)n_items; ra.row0 = 0;
+        hipLaunchKernelGGL(elpd_reduce_kernel, dim3((unsigned)n_rows), dim3(ELPD_THREADS), 0, st, ra);
+        HIP_TRY(hipGetLastError());
+        if (s.n_distinct) *s.n_distinct = n_items;
+        return copy_out();
+    }
+
+    // data rows and targets
+    const float* d_x = nullptr;
+    int xs = 0;
+    if (int rc = upload_rows(h, mem, rows, I + 1, &d_x, &xs)) return rc;
+    // stage a: items -> distinct (w, eta) samples
+    Distinct d;
+    if (int rc = distinct_samples(h, mem, src, true, true, &d)) return rc;
+    const int U = d.U;
+    if (s.n_distinct) *s.n_distinct = U;
+    // stage b + c in blocks of rows: fx scratch U x (rows x O) floats (+ U x rows doubles for loglik_out) under the budget
+    const long long rows_blk = row_block(scratch_budget("PTNN_ELPD_SCRATCH_BYTES"),
+                                         (size_t)U * (sizeof(float) * O + (s.loglik_out ? sizeof(double) : 0)), n_rows);
+    float* d_fx = nullptr;
+    double* d_llb = nullptr;
+    HIP_TRY(mem.alloc(&d_fx, (size_t)rows_blk * O * U));
+    if (s.loglik_out) HIP_TRY(mem.alloc(&d_llb, (size_t)rows_blk * U));
+    ForwardPlan fwd;
+    if (int rc = fwd.init(h, "predictive accuracy")) return rc;
+    std::vector<int> item_run;
+    if (s.loglik_out) if (int rc = item_runs(h, d, n_items, &item_run)) return rc;
+    ra.mode = reg ? ELPD_REG : ELPD_CLS; ra.fx = d_fx; ra.eta = d.run_eta; ra.y = d_x + I; ra.ys = xs; ra.cnt = d.run_cnt; ra.U = U;
+    ra.ll_out = d_llb;
+    for (long long r0 = 0; r0 < n_rows; r0 += rows_blk) {
+        const int nr = (int)std::min<long long>(rows_blk, n_rows - r0);
+        if (int rc = fwd.launch(h, d.base, d.run_off, d_x, xs, (int)r0, nr, U, d_fx)) return rc;
+        ra.row0 = (int)r0;
+        hipLaunchKernelGGL(elpd_reduce_kernel, dim3((unsigned)nr), dim3(ELPD_THREADS), 0, st, ra);
+        HIP_TRY(hipGetLastError());
+        if (s.loglik_out) {
+            const long long n_ll = (long long)nr * U;
+            hipLaunchKernelGGL(elpd_loglik_kernel, dim3((unsigned)((n_ll + ELPD_THREADS - 1) / ELPD_THREADS)), dim3(ELPD_THREADS), 0, st, ra, nr);
+            HIP_TRY(hipGetLastError());
+            if (int rc = scatter_samples(h, (const double*)d_llb, nr, U, item_run, src.weights(), s.loglik_out, (size_t)n_rows, (size_t)r0)) return rc;
+        }
+    }
+    return copy_out();
+}
+
+// ---- recursive forecasts (ptnn_dev_forecast.hpp) ----
+int ptnn_forecast(ptnn_handle* h, const ptnn_forecast_spec* spec) {
+    // argument checks first: none of them needs the handle or a device
+    if (int rc = check_spec(spec, "ptnn_forecast_spec")) return rc;
+    const ptnn_forecast_spec& s = *spec;
+    const bool host_src = s.w != nullptr, noise = s.noise != 0;
+    SampleSource src = source_of(s, host_src, s.eta);
+    const RowSource rows{s.origin_source, s.origins, s.n_origins, "origin_source", "PTNN_FORECAST_ORIGIN", "origins", "n_origins"};
+    if (int rc = check_source(src, "vectors")) return rc;
+    if (int rc = check_rows(rows)) return rc;
+    if (s.n_origins < 1) return fail(-1, "n_origins = %d must be >= 1", s.n_origins);
+    if (s.horizon < 1) return fail(-1, "horizon = %d must be >= 1", s.horizon);
+    const long long ncols = (long long)s.n_origins * s.horizon;
+    if (ncols > 0x7fffffffLL) return fail(-1, "%d origins x horizon %d = %lld columns: at most 2^31 - 1 per call", s.n_origins, s.horizon, ncols);
+    if (int rc = check_ranks(s.n_ranks, s.ranks, s.order_stats)) return rc;
+    if (noise && host_src && !s.eta) return fail(-1, "noise: host vectors need eta = log tau^2 (one per vector)");
+    if (int rc = check_handle(h, "ptnn_forecast")) return rc;
+    if (h->cfg.task != PTNN_TASK_REG || h->cfg.n_out != 1)
+        return fail(-1, "forecasting needs a regression net with n_out == 1 (a one-step map of one series); this handle is a %s "
+                        "net with n_out = %d", h->cfg.task == PTNN_TASK_REG ? "regression" : "classification", h->cfg.n_out);
+    const int I = h->cfg.n_in, P = h->P, hz = s.horizon;
+    if (int rc = fit_rows(h, rows)) return rc;
+    if (int rc = count_samples(h, src)) return rc;
+    const long long M = src.M;
+    if (M < 1) return fail(-1, "the selection holds no sample");
+    if (int rc = sample_limit(src)) return rc;
+    if (int rc = check_rank_values(s.n_ranks, s.ranks, M)) return rc;
+    if (s.n_samples) *s.n_samples = M;
+
+    if (int rc = start_device(h)) return rc;
+    hipStream_t st = h->stream;
+    DeviceScratch mem;
+    // origins
+    const float* d_x = nullptr;
+    int xs = 0;
+    if (int rc = upload_rows(h, mem, rows, I, &d_x, &xs)) return rc;
+    // stage a: items -> trajectories (noise off: distinct vectors; noise on: every occurrence, host multiplicities expanded)
+    std::vector<float> w_exp, eta_exp;
+    if (noise && host_src && s.multiplicity) {
+        w_exp.reserve((size_t)M * P);
+        eta_exp.reserve((size_t)M);
+        for (int64_t k = 0; k < s.n_w; ++k)
+            for (int c = 0; c < s.multiplicity[k]; ++c) {
+                w_exp.insert(w_exp.end(), s.w + (size_t)k * P, s.w + (size_t)(k + 1) * P);
+                eta_exp.push_back(s.eta[k]);
+            }
+        src.w = w_exp.data(); src.eta = eta_exp.data(); src.multiplicity = nullptr;
+        src.n_items = M;
+    }
+    Distinct d;
+    if (int rc = distinct_samples(h, mem, src, noise, !noise, &d)) return rc;
+    const int U = d.U;
+    if (s.n_trajectories) *s.n_trajectories = U;
+    // outputs on the device for every column
+    double* d_mean = nullptr; float* d_ostat = nullptr; long long* d_ranks = nullptr;
+    HIP_TRY(mem.alloc(&d_mean, (size_t)ncols));
+    if (s.n_ranks) {
+        HIP_TRY(mem.alloc(&d_ostat, (size_t)s.n_ranks * ncols));
+        HIP_TRY(mem.upload(&d_ranks, (const long long*)s.ranks, (size_t)s.n_ranks, st));
+    }
+    // stage b + c in blocks of origins and horizon steps: fx 4 U ob hb bytes, + 4 U I bytes of carried windows when the horizon
+    // is split (only with one origin per block: the columns of a block are then always contiguous)
+    const size_t budget = scratch_budget("PTNN_FORECAST_SCRATCH_BYTES");
+    const size_t traj_bytes = (size_t)U * sizeof(float);
+    long long ob = 1, hb = hz;
+    if (budget >= traj_bytes * hz) {
+        ob = std::max(1LL, std::min<long long>((long long)(budget / (traj_bytes * hz)), s.n_origins));
+    } else {
+        const long long fit = (long long)(budget / traj_bytes) - I;
+        hb = std::max(1LL, std::min<long long>(fit, hz));
+    }
+    ob = std::min<long long>(ob, 65535LL * WAVE);        // grid.y of the split layout
+    const bool split_h = hb < hz;
+    float *d_fx = nullptr, *d_win = nullptr;
+    HIP_TRY(mem.alloc(&d_fx, (size_t)ob * hb * U));
+    if (split_h) HIP_TRY(mem.alloc(&d_win, (size_t)U * I));
+    // the layout: a function of the shape alone (P), never of the budget
+    const int layout = P <= FC_LANE_MAX_P ? FC_LANE : FC_SPLIT;
+    const size_t lds = layout == FC_LANE ? (size_t)(FC_THREADS / WAVE) * P * WAVE * sizeof(float)
+                                         : (size_t)(round_up4(P) + 2 * (FC_THREADS / WAVE) * WAVE) * sizeof(float);
+    if (lds > LDS_CEILING) return fail(-3, "forecast: a %d-parameter vector does not fit in LDS", P);
+    if (int rc = raise_lds_limit(reinterpret_cast<const void*>(h->shape->forecast_fwd), lds)) return rc;
+    // samples: the trajectory of every selected row, chain-major
+    std::vector<int> item_run;
+    if (s.samples) if (int rc = item_runs(h, d, src.n_items, &item_run)) return rc;
+    ForecastFwd fa{};
+    fa.base = d.base; fa.run_off = d.run_off; fa.eta = d.run_eta; fa.x = d_x; fa.xs = xs; fa.horizon = hz; fa.win = d_win;
+    fa.H = h->cfg.n_hidden; fa.P = P; fa.U = U; fa.layout = layout; fa.noise = noise ? 1 : 0;
+    fa.seed_lo = (uint32_t)(s.seed & 0xffffffffu); fa.seed_hi = (uint32_t)(s.seed >> 32); fa.fx = d_fx;
+    for (long long r0 = 0; r0 < s.n_origins; r0 += ob) {
+        const int nr = (int)std::min<long long>(ob, s.n_origins - r0);
+        for (long long k0 = 0; k0 < hz; k0 += hb) {
+            const int nk = (int)std::min<long long>(hb, hz - k0);
+            fa.r0 = (int)r0; fa.nr = nr; fa.k0 = (int)k0; fa.hb = nk;
+            dim3 grid;
+            if (layout == FC_LANE) {
+                const long long gx = (U + FC_THREADS - 1) / FC_THREADS;
+                grid = dim3((unsigned)gx, (unsigned)std::max(1LL, std::min<long long>((512 + gx - 1) / gx, nr)));
+            } else {
+                grid = dim3((unsigned)U, (unsigned)((nr + WAVE - 1) / WAVE));
+            }
+            hipLaunchKernelGGL(h->shape->forecast_fwd, grid, dim3(FC_THREADS), lds, st, fa);
+            HIP_TRY(hipGetLastError());
+            const long long col0 = r0 * hz + k0;             // the block's columns are contiguous (see above)
+            PredictRed ra{d_fx, d.run_cnt, U, 1, (int)col0, (int)ncols, M, s.n_ranks, d_ranks, d_mean, d_ostat, nullptr};
+            hipLaunchKernelGGL(predict_reduce_kernel, dim3((unsigned)(nr * nk)), dim3(PRED_THREADS), 0, st, ra);
+            HIP_TRY(hipGetLastError());
+            if (s.samples)
+                if (int rc = scatter_samples(h, d_fx, nr * nk, U, item_run, src.weights(), s.samples, (size_t)ncols, (size_t)col0)) return rc;
+        }
+    }
+    HIP_TRY(fetch(s.mean, d_mean, (size_t)ncols, st));
+    HIP_TRY(fetch(s.order_stats, d_ostat, (size_t)s.n_ranks * ncols, st));
+    return wait_stream(h);
+}
+
+// ---- log evidence (ptnn_dev_evidence.hpp) ----
+static_assert(PTNN_EVIDENCE_MAX_A == EVID_MAX_A, "ptnn.h prior exponents");
+
+int ptnn_evidence(ptnn_handle* h, const ptnn_evidence_spec* spec) {
+    // argument checks first: none of them needs the handle or a device
+    if (int rc = check_spec(spec, "ptnn_evidence_spec")) return rc;
+    const ptnn_evidence_spec& s = *spec;
+    const bool u_src = s.u != nullptr, host_src = s.w != nullptr;
+    // host vectors [K][n][P] as one list of K n items (their [K, n] multiplicities are applied to U, below), or one rung per chain
+    SampleSource src{host_src, s.w, nullptr, (int64_t)s.n_rungs * s.n_per_rung, nullptr, s.replicas, s.n_replicas, s.step0, s.nsteps, s.thin};
+    if (u_src && host_src) return fail(-1, "give host vectors w or a host U, not both");
+    if (u_src || host_src) {
+        if (s.n_rungs < 1) return fail(-1, "n_rungs = %d must be >= 1", s.n_rungs);
+        if (s.n_per_rung < 1) return fail(-1, "n_per_rung = %lld must be >= 1", (long long)s.n_per_rung);
+    } else {
+        if (s.nsteps < 1) return fail(-1, "no source: nsteps = %d trace rows, and neither host vectors w nor a host U", s.nsteps);
+        if (int rc = check_source(src, "vectors")) return rc;
+    }
+    if (s.n_prior < 0) return fail(-1, "n_prior = %lld must be >= 0", (long long)s.n_prior);
+    if (s.n_prior > 0x7fffffffLL) return fail(-1, "n_prior = %lld: at most 2^31 - 1 prior draws per call", (long long)s.n_prior);
+    if (s.n_prior > 0 && (s.n_a < 1 || s.n_a > EVID_MAX_A || !s.a))
+        return fail(-1, "n_prior = %lld prior draws need 1 to %d exponents a (n_a = %d)", (long long)s.n_prior, EVID_MAX_A, s.n_a);
+    if (s.n_prior > 0)
+        for (int j = 0; j < s.n_a; ++j)
+            if (!std::isfinite(s.a[j])) return fail(-1, "a[%d] = %g is not finite", j, s.a[j]);
+    if (s.n_prior == 0 && s.u_prior_out) return fail(-1, "u_prior_out requested with n_prior = 0");
+    if (u_src && s.u_out) return fail(-1, "u_out: U is the input of this source");
+    if (u_src && s.n_distinct) *s.n_distinct = 0;
+    // host sources: items, their multiplicities, the draws of every rung
+    std::vector<long long> off;                        // [K + 1] expanded draws of rung k at [off[k], off[k + 1])
+    std::vector<int32_t> item_of;                      // expanded draw -> item (multiplicities only)
+    if (u_src || host_src) {
+        const long long K = s.n_rungs, n = s.n_per_rung;
+        if (K * n > 0x7fffffffLL) return fail(-1, "%lld host rows: at most 2^31 - 1 per call", K * n);
+        src.n_items = K * n;
+        off.assign((size_t)K + 1, 0);
+        for (long long k = 0; k < K; ++k) {
+            long long c = 0;
+            for (long long i = 0; i < n; ++i) {
+                const long long it = k * n + i;
+                const int mu = s.multiplicity ? s.multiplicity[it] : 1;
+                if (mu < 0) return fail(-1, "multiplicity[%lld, %lld] = %d is negative", k, i, mu);
+                c += mu;
+                if (s.multiplicity) for (int r = 0; r < mu; ++r) item_of.push_back((int32_t)it);
+                if (u_src && mu > 0 && !std::isfinite(s.u[it])) return fail(-1, "u[%lld, %lld] = %g is not finite", k, i, s.u[it]);
+            }
+            off[(size_t)k + 1] = off[(size_t)k] + c;
+            if (off[(size_t)k + 1] > 0x7fffffffLL) return fail(-1, "more than 2^31 - 1 expanded draws");
+        }
+    }
+    if (int rc = check_handle(h, "ptnn_evidence")) return rc;
+    const int I = h->cfg.n_in, O = h->cfg.n_out, P = h->P, N = h->Ntr;
+    const bool reg = h->cfg.task == PTNN_TASK_REG;
+    // the trace selection: one rung per chain
+    if (!u_src && !host_src) {
+        if (int rc = count_samples(h, src)) return rc;
+        if (src.n_items > 0x7fffffffLL) return fail(-1, "%lld trace rows: at most 2^31 - 1 per call", src.n_items);
+        off.assign(src.reps.size() + 1, 0);
+        for (size_t k = 0; k < src.reps.size(); ++k) off[k + 1] = off[k] + src.m;
+    }
+    const long long n_items = src.n_items;
+    const int K = (int)off.size() - 1;
+    for (int k = 0; k < K; ++k)
+        if (off[(size_t)k + 1] - off[(size_t)k] < 4)
+            return fail(-1, "rung %d holds %lld draws: the split ESS needs at least 4 per rung", k, off[(size_t)k + 1] - off[(size_t)k]);
+    if (s.d)
+        for (int k = 0; k < K; ++k)
+            if (!std::isfinite(s.d[k])) return fail(-1, "d[%d] = %g is not finite", k, s.d[k]);
+    const long long n_draws = off[(size_t)K];
+    if (s.n_draws)
+        for (int k = 0; k < K; ++k) s.n_draws[k] = off[(size_t)k + 1] - off[(size_t)k];
+
+    if (int rc = start_device(h)) return rc;
+    hipStream_t st = h->stream;
+    DeviceScratch mem;
+    const size_t budget = scratch_budget("PTNN_EVIDENCE_SCRATCH_BYTES");
+    // the forward pass of predict_fwd on the training rows
+    ForwardPlan fwd;
+    if (int rc = fwd.init(h, "log evidence")) return rc;
+    const float* d_x = h->d_data;                      // training rows
+    const int xs = h->IPY;
+    int* d_sse0 = nullptr;                             // weight vectors with SSE = 0 (evid_finish_kernel)
+    HIP_TRY(mem.alloc(&d_sse0, 1));
+    HIP_TRY(hipMemsetAsync(d_sse0, 0, sizeof(int), st));
+    // U (and b) of `nv` vectors at base + run_off[u]: rows in blocks of rows_blk, fx scratch `fx` of rows_blk x O x nv floats
+    auto eval_u = [&](const float* base, const long long* run_off, int nv, long long rows_blk, float* fx, double* acc, double* u_out,
+                      double* b_out) -> int {
+        HIP_TRY(hipMemsetAsync(acc, 0, (size_t)nv * sizeof(double), st));
+        const unsigned ub = (unsigned)((nv + EVID_THREADS - 1) / EVID_THREADS);
+        for (long long r0 = 0; r0 < N; r0 += rows_blk) {
+            const int nr = (int)std::min<long long>(rows_blk, N - r0);
+            if (int rc = fwd.launch(h, base, run_off, d_x, xs, (int)r0, nr, nv, fx)) return rc;
+            EvidRows ra{fx, d_x + (size_t)r0 * xs + I, xs, nr, O, nv, reg ? 1 : 0, acc};
+            hipLaunchKernelGGL(evid_rows_kernel, dim3(ub), dim3(EVID_THREADS), 0, st, ra);
+            HIP_TRY(hipGetLastError());
+        }
+        hipLaunchKernelGGL(evid_finish_kernel, dim3(ub), dim3(EVID_THREADS), 0, st, nv, reg ? 1 : 0, N, (const double*)acc, u_out, b_out, d_sse0);
+        HIP_TRY(hipGetLastError());
+        return 0;
+    };
+    auto rows_for = [&](long long nv, size_t avail) { return row_block(avail, (size_t)nv * O * sizeof(float), N); };
+    auto sse_check = [&]() -> int {
+        int e = 0;
+        HIP_TRY(hipMemcpyAsync(&e, d_sse0, sizeof e, hipMemcpyDeviceToHost, st));
+        if (int rc = wait_stream(h)) return rc;
+        if (e) return fail(-1, "%d weight vectors fit the %d training rows exactly (SSE = 0): U = -(N / 2) log SSE is infinite", e, N);
+        return 0;
+    };
+
+    // ---- the rungs: U of every draw
+    double* d_udraw = nullptr;
+    if (K > 0) HIP_TRY(mem.alloc(&d_udraw, (size_t)n_draws));
+    int* d_item_of = nullptr;
+    if (!item_of.empty()) HIP_TRY(mem.upload(&d_item_of, item_of.data(), item_of.size(), st));
+    const unsigned draw_blocks = (unsigned)((n_draws + EVID_THREADS - 1) / EVID_THREADS);
+    if (u_src) {
+        double* d_u = nullptr;
+        HIP_TRY(mem.upload(&d_u, s.u, (size_t)n_items, st));
+        hipLaunchKernelGGL(evid_expand_kernel, dim3(draw_blocks), dim3(EVID_THREADS), 0, st, n_draws, (const int*)d_item_of,
+                           (const int*)nullptr, (const double*)d_u, d_udraw);
+        HIP_TRY(hipGetLastError());
+    } else {
+        // stage a: items -> distinct vectors
+        Distinct d;
+        if (int rc = distinct_samples(h, mem, src, false, true, &d)) return rc;
+        const int U = d.U;
+        if (s.n_distinct) *s.n_distinct = U;
+        // stages b, c: U of every distinct vector, rows in blocks under the budget
+        const long long rows_blk = rows_for(U, budget);
+        float* d_fx = nullptr;
+        double *d_acc = nullptr, *d_udist = nullptr;
+        HIP_TRY(mem.alloc(&d_fx, (size_t)rows_blk * O * U));
+        HIP_TRY(mem.alloc(&d_acc, (size_t)U));
+        HIP_TRY(mem.alloc(&d_udist, (size_t)U));
+        if (int rc = eval_u(d.base, d.run_off, U, rows_blk, d_fx, d_acc, d_udist, nullptr)) return rc;
+        hipLaunchKernelGGL(evid_expand_kernel, dim3(draw_blocks), dim3(EVID_THREADS), 0, st, n_draws, (const int*)d_item_of,
+                           (const int*)d.item_run, (const double*)d_udist, d_udraw);
+        HIP_TRY(hipGetLastError());
+        if (int rc = sse_check()) return rc;
+    }
+    // stage d: per-rung moments and stones
+    long long* d_off = nullptr;
+    double *d_mean = nullptr, *d_var = nullptr, *d_d = nullptr, *d_ls = nullptr, *d_rv = nullptr;
+    HIP_TRY(mem.upload(&d_off, off.data(), off.size(), st));
+    HIP_TRY(mem.alloc(&d_mean, (size_t)K));
+    HIP_TRY(mem.alloc(&d_var, (size_t)K));
+    if (s.d) {
+        HIP_TRY(mem.upload(&d_d, s.d, (size_t)K, st));
+        HIP_TRY(mem.alloc(&d_ls, (size_t)K));
+        HIP_TRY(mem.alloc(&d_rv, (size_t)K));
+    }
+    EvidRung rg{d_udraw, d_off, d_d, d_mean, d_var, d_ls, d_rv};
+    hipLaunchKernelGGL(evid_rung_kernel, dim3((unsigned)K), dim3(EVID_THREADS), 0, st, rg);
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(fetch(s.u_mean, d_mean, (size_t)K, st));
+    HIP_TRY(fetch(s.u_var, d_var, (size_t)K, st));
+    HIP_TRY(fetch(s.d ? s.log_stone : nullptr, d_ls, (size_t)K, st));
+    HIP_TRY(fetch(s.d ? s.stone_relvar : nullptr, d_rv, (size_t)K, st));
+    HIP_TRY(fetch(s.u_out, d_udraw, (size_t)n_draws, st));
+    if (int rc = wait_stream(h)) return rc;
+    // the split ESS of every rung's U draws (one chain each), by the convergence kernels: rungs of equal length in one pass
+    if (s.u_ess) {
+        std::vector<char> done((size_t)K, 0);
+        for (int k0 = 0; k0 < K; ++k0) {
+            if (done[(size_t)k0]) continue;
+            const long long nk = off[(size_t)k0 + 1] - off[(size_t)k0];
+            std::vector<int> rung, qcol;
+            for (int k = k0; k < K; ++k)
+                if (!done[(size_t)k] && off[(size_t)k + 1] - off[(size_t)k] == nk) { rung.push_back(k); done[(size_t)k] = 1; }
+            const int Q = (int)rung.size();
+            for (int q = 0; q < Q; ++q) qcol.push_back(q);
+            DeviceScratch cm;
+            int* d_rung = nullptr;
+            float* d_draws = nullptr;
+            HIP_TRY(cm.alloc(&d_rung, (size_t)Q));
+            HIP_TRY(hipMemcpyAsync(d_rung, rung.data(), (size_t)Q * sizeof(int), hipMemcpyHostToDevice, st));
+            HIP_TRY(cm.alloc(&d_draws, (size_t)Q * nk));
+            hipLaunchKernelGGL(evid_conv_kernel, dim3((unsigned)(((long long)Q * nk + EVID_THREADS - 1) / EVID_THREADS)), dim3(EVID_THREADS), 0, st,
+                               Q, (int)nk, (const long long*)d_off, (const int*)d_rung, (const double*)d_udraw, d_draws);
+            HIP_TRY(hipGetLastError());
+            ConvGather ga{};
+            ga.host = 1; ga.draws = d_draws; ga.Qh = Q;
+            std::vector<double> ess((size_t)Q);
+            if (int rc = conv_drive(h, cm, ga, qcol, 1, (int)nk, 0, nullptr, nullptr, nullptr, ess.data(), nullptr, nullptr, nullptr)) return rc;
+            for (int q = 0; q < Q; ++q) s.u_ess[rung[(size_t)q]] = ess[(size_t)q];
+        }
+    }
+    if (s.n_prior == 0) return 0;
+
+    // ---- stage e: prior draws in blocks of nb vectors (vector + forward scratch of every training row under the budget)
+    const long long NP = s.n_prior;
+    const size_t per_draw = (size_t)P * sizeof(float) + 4 * sizeof(double) + (size_t)std::min<long long>(N, 65535LL * WAVE) * O * sizeof(float);
+    const long long nb = std::max(1LL, std::min<long long>((long long)(budget / per_draw), NP));
+    const size_t fixed = (size_t)nb * ((size_t)P * sizeof(float) + 4 * sizeof(double));
+    const long long rows_blk = rows_for(nb, budget > fixed ? budget - fixed : 0);
+    double *d_pu = nullptr, *d_pb = nullptr, *d_acc = nullptr, *d_a = nullptr;
+    float *d_pw = nullptr, *d_fx = nullptr;
+    long long* d_poff = nullptr;
+    HIP_TRY(mem.alloc(&d_pu, (size_t)NP));
+    HIP_TRY(mem.alloc(&d_pb, (size_t)NP));
+    HIP_TRY(mem.alloc(&d_pw, (size_t)nb * P));
+    HIP_TRY(mem.alloc(&d_poff, (size_t)nb));
+    HIP_TRY(mem.alloc(&d_acc, (size_t)nb));
+    HIP_TRY(mem.alloc(&d_fx, (size_t)rows_blk * O * nb));
+    const float sigma = (float)std::sqrt((double)h->cfg.sigma_squared);
+    const uint32_t slo = (uint32_t)(s.seed & 0xffffffffu), shi = (uint32_t)(s.seed >> 32);
+    const int nq = (P + 3) / 4;
+    for (long long d0 = 0; d0 < NP; d0 += nb) {
+        const int b = (int)std::min<long long>(nb, NP - d0);
+        hipLaunchKernelGGL(evid_prior_kernel, dim3((unsigned)(((long long)b * nq + EVID_THREADS - 1) / EVID_THREADS)), dim3(EVID_THREADS), 0, st,
+                           d0, b, P, sigma, slo, shi, d_pw, d_poff);
+        HIP_TRY(hipGetLastError());
+        if (int rc = eval_u(d_pw, d_poff, b, rows_blk, d_fx, d_acc, d_pu + d0, d_pb + d0)) return rc;
+    }
+    HIP_TRY(mem.alloc(&d_a, (size_t)s.n_a));
+    HIP_TRY(hipMemcpyAsync(d_a, s.a, (size_t)s.n_a * sizeof(double), hipMemcpyHostToDevice, st));
+    double* d_pr = nullptr;
+    HIP_TRY(mem.alloc(&d_pr, (size_t)4 * s.n_a));
+    EvidPriorRed pr{d_pu, d_pb, NP, d_a, d_pr, d_pr + s.n_a, d_pr + 2 * s.n_a, d_pr + 3 * s.n_a};
+    hipLaunchKernelGGL(evid_prior_reduce_kernel, dim3((unsigned)s.n_a), dim3(EVID_THREADS), 0, st, pr);
+    HIP_TRY(hipGetLastError());
+    std::vector<double> prh((size_t)4 * s.n_a);
+    HIP_TRY(hipMemcpyAsync(prh.data(), d_pr, prh.size() * sizeof(double), hipMemcpyDeviceToHost, st));
+    if (s.u_prior_out) HIP_TRY(hipMemcpyAsync(s.u_prior_out, d_pu, (size_t)NP * sizeof(double), hipMemcpyDeviceToHost, st));
+    if (int rc = sse_check()) return rc;
+    double* outs[4] = {s.prior_log_mean_exp, s.prior_kish_ess, s.prior_u_mean, s.prior_u_var};
+    for (int o = 0; o < 4; ++o)
+        if (outs[o]) std::copy(prh.begin() + (size_t)o * s.n_a, prh.begin() + (size_t)(o + 1) * s.n_a, outs[o]);
+    return 0;
+}
+
+// ---- calibration (ptnn_dev_calibration.hpp) ----
+static_assert(PTNN_CALIB_MAX_LEVELS == CALIB_MAX_LEVELS && PTNN_CALIB_MAX_DISTINCT == CALIB_MAX_DISTINCT, "ptnn.h calibration limits");
+
+int ptnn_calibration(ptnn_handle* h, const ptnn_calibration_spec* spec) {
+    // argument checks first: none of them needs the handle or a device
+    if (int rc = check_spec(spec, "ptnn_calibration_spec")) return rc;
+    const ptnn_calibration_spec& s = *spec;
+    const bool host_src = s.w != nullptr;
+    SampleSource src = source_of(s, host_src, s.eta);
+    const RowSource rows{s.x_source, s.x, s.n_rows, "x_source", "PTNN_PREDICT_X", "x", "n_rows"};
+    if (!src.host && s.nsteps < 1) return fail(-1, "no source: nsteps = %d trace rows and no host vectors w", s.nsteps);
+    if (int rc = check_source(src, "samples")) return rc;
+    if (s.n_rows < 1) return fail(-1, "n_rows = %d must be >= 1", s.n_rows);
+    if (int rc = check_rows(rows)) return rc;
+    if (s.n_levels < 0 || s.n_levels > CALIB_MAX_LEVELS) return fail(-1, "n_levels = %d outside [0, %d]", s.n_levels, CALIB_MAX_LEVELS);
+    if (s.n_levels > 0 && (!s.levels_p || !s.levels_z || !s.quantiles))
+        return fail(-1, "n_levels = %d needs levels_p, levels_z and quantiles", s.n_levels);
+    if (s.quantiles && s.n_levels == 0) return fail(-1, "quantiles requested without levels");
+    for (int k = 0; k < s.n_levels; ++k)
+        if (!(s.levels_p[k] > 0.0 && s.levels_p[k] < 1.0) || !std::isfinite(s.levels_z[k]))
+            return fail(-1, "levels_p[%d] = %g (levels_z %g): a quantile level lies in (0, 1)", k, s.levels_p[k], s.levels_z[k]);
+    if (s.crps && !s.pair_term) return fail(-1, "crps requested without pair_term");
+    if (src.host)
+        if (int rc = count_samples(nullptr, src)) return rc;
+    if (int rc = check_handle(h, "ptnn_calibration")) return rc;
+    const int I = h->cfg.n_in, O = h->cfg.n_out;
+    const bool reg = h->cfg.task == PTNN_TASK_REG;
+    const bool reg_out = s.pit || s.crps || s.pred_mean || s.pred_sd || s.quantiles || s.pair_term;
+    if (reg_out && (!reg || O != 1))
+        return fail(-1, "pit, crps, pred_mean, pred_sd and quantiles need a regression net with n_out == 1; this handle is a %s net "
+                        "with n_out = %d", reg ? "regression" : "classification", O);
+    if (s.p_mean && reg) return fail(-1, "p_mean: a regression has no class probabilities");
+    if (host_src && reg && !s.eta) return fail(-1, "a regression's host vectors need eta = log tau^2 (one per vector)");
+    if (int rc = fit_rows(h, rows)) return rc;
+    if (!src.host)
+        if (int rc = count_samples(h, src)) return rc;
+    const long long S = src.M;
+    if (S < 1) return fail(-1, "the selection holds no sample");
+    if (int rc = sample_limit(src)) return rc;
+    if (s.n_samples) *s.n_samples = S;
+
+    if (int rc = start_device(h)) return rc;
+    hipStream_t st = h->stream;
+    DeviceScratch mem;
+    const int n_rows = s.n_rows;
+    const float* d_x = nullptr;
+    int xs = 0;
+    if (int rc = upload_rows(h, mem, rows, I + 1, &d_x, &xs)) return rc;
+    // stage a: items -> distinct (w, eta) samples (a classification's: distinct w, as ptnn_predict's)
+    Distinct d;
+    if (int rc = distinct_samples(h, mem, src, reg, true, &d)) return rc;
+    const int U = d.U;
+    if (s.n_distinct) *s.n_distinct = U;
+    if (s.pair_term && U > CALIB_MAX_DISTINCT)
+        return fail(-1, "%d distinct samples: the pair term of the CRPS takes at most %d (U^2 / 2 terms per data row); select fewer "
+                        "samples (thin=, chains=) or leave the CRPS out (crps=False)", U, CALIB_MAX_DISTINCT);
+    const long long rows_blk = row_block(scratch_budget("PTNN_CALIB_SCRATCH_BYTES"), (size_t)U * sizeof(float) * O, n_rows);
+    float* d_fx = nullptr;
+    HIP_TRY(mem.alloc(&d_fx, (size_t)rows_blk * O * U));
+    ForwardPlan fwd;
+    if (int rc = fwd.init(h, "calibration")) return rc;
+
+    if (!reg) {
+        double* d_mean = nullptr;
+        HIP_TRY(mem.alloc(&d_mean, (size_t)n_rows * O));
+        for (long long r0 = 0; r0 < n_rows; r0 += rows_blk) {
+            const int nr = (int)std::min<long long>(rows_blk, n_rows - r0);
+            if (int rc = fwd.launch(h, d.base, d.run_off, d_x, xs, (int)r0, nr, U, d_fx)) return rc;
+            PredictRed ra{d_fx, d.run_cnt, U, O, (int)r0 * O, n_rows * O, S, 0, nullptr, d_mean, nullptr, nullptr};
+            hipLaunchKernelGGL(predict_reduce_kernel, dim3((unsigned)(nr * O)), dim3(PRED_THREADS), 0, st, ra);
+            HIP_TRY(hipGetLastError());
+        }
+        HIP_TRY(fetch(s.p_mean, d_mean, (size_t)n_rows * O, st));
+        return wait_stream(h);
+    }
+
+    double *d_tau2 = nullptr, *d_tau = nullptr, *d_itau = nullptr;
+    double *d_pit = nullptr, *d_crps = nullptr, *d_mean = nullptr, *d_sd = nullptr, *d_q = nullptr, *d_t1 = nullptr, *d_bound = nullptr;
+    unsigned long long* d_limbs = nullptr;
+    HIP_TRY(mem.alloc(&d_tau2, (size_t)U));
+    HIP_TRY(mem.alloc(&d_tau, (size_t)U));
+    HIP_TRY(mem.alloc(&d_itau, (size_t)U));
+    HIP_TRY(mem.alloc(&d_pit, (size_t)n_rows));
+    HIP_TRY(mem.alloc(&d_mean, (size_t)n_rows));
+    HIP_TRY(mem.alloc(&d_sd, (size_t)n_rows));
+    if (s.n_levels) HIP_TRY(mem.alloc(&d_q, (size_t)s.n_levels * n_rows));
+    if (s.pair_term) {
+        HIP_TRY(mem.alloc(&d_crps, (size_t)n_rows));
+        HIP_TRY(mem.alloc(&d_t1, (size_t)n_rows));
+        HIP_TRY(mem.alloc(&d_bound, (size_t)n_rows));
+        HIP_TRY(mem.alloc(&d_limbs, (size_t)n_rows * 4));
+        HIP_TRY(hipMemsetAsync(d_limbs, 0, (size_t)n_rows * 4 * sizeof(unsigned long long), st));
+    }
+    hipLaunchKernelGGL(calib_tau_kernel, dim3((unsigned)((U + CALIB_THREADS - 1) / CALIB_THREADS)), dim3(CALIB_THREADS), 0, st, U,
+                       (const float*)d.run_eta, d_tau2, d_tau, d_itau);
+    HIP_TRY(hipGetLastError());
+    CalibRow ra{};
+    ra.fx = d_fx; ra.tau2 = d_tau2; ra.tau = d_tau; ra.itau = d_itau; ra.cnt = d.run_cnt; ra.y = d_x + I; ra.ys = xs; ra.U = U;
+    ra.n_rows = n_rows; ra.S = S; ra.n_levels = s.n_levels; ra.pair = s.pair_term ? 1 : 0;
+    for (int k = 0; k < s.n_levels; ++k) { ra.p[k] = s.levels_p[k]; ra.z[k] = s.levels_z[k]; }
+    ra.pit = d_pit; ra.pred_mean = d_mean; ra.pred_sd = d_sd; ra.quantiles = d_q; ra.term1 = d_t1; ra.pair_bound = d_bound;
+    const int n_tiles = (U + CALIB_THREADS - 1) / CALIB_THREADS;
+    CalibPair pa{d_fx, d_tau2, d.run_cnt, d_bound, U, 0, 0, n_tiles, d_limbs};
+    const unsigned n_tri = (unsigned)((long long)n_tiles * (n_tiles + 1) / 2);
+    for (long long r0 = 0; r0 < n_rows; r0 += rows_blk) {
+        const int nr = (int)std::min<long long>(rows_blk, n_rows - r0);
+        if (int rc = fwd.launch(h, d.base, d.run_off, d_x, xs, (int)r0, nr, U, d_fx)) return rc;
+        ra.row0 = (int)r0;
+        hipLaunchKernelGGL(calib_row_kernel, dim3((unsigned)nr), dim3(CALIB_THREADS), 0, st, ra);
+        HIP_TRY(hipGetLastError());
+        // the pair term of this block's rows, at most 65535 rows (grid.y) per launch
+        for (int q0 = 0; s.pair_term && q0 < nr; q0 += 65535) {
+            pa.row0 = (int)r0; pa.r0 = q0;
+            hipLaunchKernelGGL(calib_pair_kernel, dim3(n_tri, (unsigned)std::min(65535, nr - q0)), dim3(CALIB_THREADS), 0, st, pa);
+            HIP_TRY(hipGetLastError());
+        }
+    }
+    if (s.pair_term) {
+        hipLaunchKernelGGL(calib_finish_kernel, dim3((unsigned)((n_rows + CALIB_THREADS - 1) / CALIB_THREADS)), dim3(CALIB_THREADS), 0, st,
+                           n_rows, (const unsigned long long*)d_limbs, (const double*)d_t1, (const double*)d_bound, S, d_crps);
+        HIP_TRY(hipGetLastError());
+    }
+    HIP_TRY(fetch(s.pit, d_pit, (size_t)n_rows, st));
+    HIP_TRY(fetch(s.pred_mean, d_mean, (size_t)n_rows, st));
+    HIP_TRY(fetch(s.pred_sd, d_sd, (size_t)n_rows, st));
+    HIP_TRY(fetch(s.quantiles, d_q, (size_t)s.n_levels * n_rows, st));
+    HIP_TRY(fetch(s.crps, d_crps, (size_t)n_rows, st));
+    return wait_stream(h);
+}
+
+}  // extern "C"

@@ -1,4 +1,5 @@
-// ptnn_dev_calibration.hpp -- calibration and proper scores of the predictive distribution (ptnn_calibration, include/ptnn.h;
+// ptnn_dev_calibration.hpp -- part of ptnn_analysis.hip (textually included there, inside namespace ptnn; not a stand-alone header):
+// calibration and proper scores of the predictive distribution (ptnn_calibration, include/ptnn.h;
 // DESIGN.md section 17).  A regression's predictive distribution of y on a data row is the mixture (1/S) sum_s c_s N(f_s, tau_s^2)
 // over the U distinct (w, eta) samples with multiplicities c_s; per row: its PIT, mean, sd, quantiles and CRPS.
 //   a. + b. as ptnn_elpd: distinct_samples (run-length pass with the eta compare), the per-shape predict_forward_kernel.
@@ -6,12 +7,12 @@
 //      calib_row_kernel: one work-group per data row, the O(U) quantities and one bisection per quantile level.
 //      calib_pair_kernel: the pair term of the CRPS, rows x the triangle of (i-tile, j-tile) pairs over U.
 //      calib_finish_kernel: crps = first term - pair term.
-// A classification's p_mean is predict_reduce_kernel's mean (ptnn_dev_predict.hpp), unchanged.
+// A classification's p_mean is predict_reduce_kernel's mean (ptnn_dev_select.hpp), unchanged.
 // Every sum over samples is a 128-bit fixed-point sum of terms in [0, 1] (ptnn_dev_elpd.hpp: Fix128), scaled by a bound formed
 // from the row's exact extremes: integer addition, so a result depends on the multiset of samples only -- not on their order,
 // on how repeats are grouped, on the tiling or on the row block.  The pair kernel adds its work-groups' integer sums with
 // integer atomics (four 32-bit limbs in 64-bit words); no floating-point atomic anywhere.  fp64 throughout after f.
-// Nothing here writes chain state, tapes, counters or trace rows.  Shape-independent: main translation unit only.
+// Nothing here writes chain state, tapes, counters or trace rows.
 
 constexpr int CALIB_THREADS = 256;        // 4 waves; also the tile of the pair kernel (one i-sample per lane)
 constexpr int CALIB_MAX_LEVELS = 16;      // include/ptnn.h: PTNN_CALIB_MAX_LEVELS

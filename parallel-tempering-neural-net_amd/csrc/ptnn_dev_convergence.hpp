@@ -1,10 +1,11 @@
-// ptnn_dev_convergence.hpp -- convergence diagnostics of sampled traces: split-R-hat, split-ESS (ptnn_convergence, include/ptnn.h).
+// ptnn_dev_convergence.hpp -- part of ptnn_analysis.hip (textually included there, inside namespace ptnn; not a stand-alone header):
+// convergence diagnostics of sampled traces: split-R-hat, split-ESS (ptnn_convergence, include/ptnn.h).
 //
 // The estimator is classic split-R-hat / split-ESS (BDA3 sections 11.4-11.5) with Geyer's initial monotone sequence, in the
 // index arithmetic DESIGN.md section 12 spells out (and tests/convergence_ref.py restates in float64 numpy).  A quantity q (a
 // weight or a scalar trace column) has C selected chains of n >= 4 draws; each chain is split into its first and last h = n / 2
 // draws (the middle draw of an odd n is dropped): M = 2C split chains.  Draws are fp32; means, centring, products and every sum
-// are double.  Four stages, the host loop in ptnn.hip: ptnn_convergence drives them over blocks of quantities:
+// are double.  Four stages, the host loop in ptnn_analysis.hip: ptnn_convergence drives them over blocks of quantities:
 //   1. conv_gather_kernel: one work-group per (chain, tile of 64 quantities) gathers the chain's rows (trace rows resolved as
 //      ptnn_predict resolves them, trace_vector_offset; a tile is 64 consecutive floats of a row when the quantities are), writes
 //      the centred split chains x[q][j][i] in double through an LDS transpose, and the split means, sum of squares, chain sums.

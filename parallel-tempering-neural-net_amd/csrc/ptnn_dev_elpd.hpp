@@ -1,6 +1,7 @@
-// ptnn_dev_elpd.hpp -- predictive accuracy of the sampled chains (ptnn_elpd, include/ptnn.h): per data row
+// ptnn_dev_elpd.hpp -- part of ptnn_analysis.hip (textually included there, inside namespace ptnn; not a stand-alone header):
+// predictive accuracy of the sampled chains (ptnn_elpd, include/ptnn.h): per data row
 // the log pointwise predictive density, the WAIC penalty and the PSIS-LOO estimate with its Pareto shape k-hat.
-//   a. sample_runs_kernel (ptnn_dev_predict.hpp, with reg) + predict_scan_kernel + elpd_run_eta_kernel: the selected rows
+//   a. sample_runs_kernel (ptnn_dev_select.hpp, with reg) + predict_scan_kernel + elpd_run_eta_kernel: the selected rows
 //      collapse into distinct (w, eta) samples with multiplicities; a regression's eta comes from the TR_ACC_TR slot of the row
 //      that holds the vector, and rows before their chain's first accepted step (no eta recorded yet) are counted so that the
 //      host can refuse them.
@@ -10,7 +11,6 @@
 // depends on the multiset of samples only, not on their order or on how repeats are grouped), and the tail is sorted by its ll
 // key and merged before the Pareto fit.  So the trace, host vectors, expanded or (distinct, multiplicity) input and any block
 // size give bitwise-identical results.  Nothing here writes chain state, tapes, counters or trace rows.
-// Shape-independent: main translation unit only.
 
 constexpr int ELPD_THREADS = 256;         // 4 waves
 constexpr int ELPD_TAIL_CAP = 4096;       // distinct tail entries in LDS (include/ptnn.h: PTNN_ELPD_TAIL_CAP)

@@ -1,4 +1,5 @@
-// ptnn_dev_evidence.hpp -- the log evidence log Z of the sampled ladder (ptnn_evidence, include/ptnn.h):
+// ptnn_dev_evidence.hpp -- part of ptnn_analysis.hip (textually included there, inside namespace ptnn; not a stand-alone header):
+// the log evidence log Z of the sampled ladder (ptnn_evidence, include/ptnn.h):
 // per-rung statistics of the full-data log-likelihood U(w) over each rung's draws, and the same over draws of the prior, which
 // the host turns into thermodynamic-integration and stepping-stone estimates.
 //   a. sample_runs_kernel (reg = 0: U needs w only) + predict_scan_kernel: the selected rows collapse into distinct vectors.
@@ -12,7 +13,7 @@
 //   e. prior draws: evid_prior_kernel writes w = sigma z, z from Philox stream STREAM_PRIOR (counter (k / 4, draw, 0, 5)), into
 //      blocks of vectors that stages b and c evaluate; evid_prior_reduce_kernel reduces over all draws per exponent a_j.
 // Every reduction runs over a fixed index order with a fixed tree, so the results depend on the draws and their order only.
-// Nothing here writes chain state, tapes, counters or trace rows.  Shape-independent: main translation unit only.
+// Nothing here writes chain state, tapes, counters or trace rows.
 
 constexpr int EVID_THREADS = 256;          // 4 waves
 constexpr int EVID_MAX_A = 4;              // prior exponents per call (include/ptnn.h: PTNN_EVIDENCE_MAX_A)

@@ -14,7 +14,7 @@ constexpr int FC_THREADS = 256;          // 4 waves
 enum { FC_LANE = 0, FC_SPLIT = 1 };      // layouts: one trajectory per lane / one vector per work-group, hidden units over waves
 constexpr int FC_LANE_MAX_P = 96;        // the lane layout holds 4 waves x 64 vectors transposed: 4 * 96 * 64 * 4 B = 96 KiB
 
-// what the forward kernel needs (the host fills it; ptnn.hip: ptnn_forecast)
+// what the forward kernel needs (the host fills it; ptnn_analysis.hip: ptnn_forecast)
 struct ForecastFwd {
     const float* base;          // vectors: d_pos_w rows or the uploaded host vectors
     const long long* run_off;   // [U] float offset of trajectory u's vector in base

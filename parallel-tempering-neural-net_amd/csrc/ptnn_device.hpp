@@ -12,6 +12,10 @@
 // swap interval; the tree and the packed multi-CU body also run the swap rounds between their intervals), swap_block (one
 // work-group's share of a swap round), and at the end persistent_loop + the __global__ kernels: body, grid barrier, swap_block,
 // next interval -- one launch per run.  ptnn_diag.hpp is included by diagnostic builds only.
+// Everything included here is a template or inline, so every translation unit may include it.  A non-template __global__ kernel
+// lives in a part that exactly one translation unit includes, inside namespace ptnn after ptnn_shapes.hpp, and that object holds
+// it: ptnn_dev_swap.hpp in ptnn.hip; ptnn_dev_select.hpp, ptnn_dev_convergence.hpp, ptnn_dev_elpd.hpp, ptnn_dev_evidence.hpp and
+// ptnn_dev_calibration.hpp in ptnn_analysis.hip.
 //
 // Written for gfx950 only: wave size 64, DPP row operations, v_permlane{16,32}_swap.
 #pragma once
@@ -142,16 +146,10 @@ struct SegDyn {
 #include "ptnn_dev_coop.hpp"                 // cooperative schedule: matrix-core forward passes (exact fp32 / split bf16 operands) and segment_body
 #include "ptnn_dev_spec.hpp"                 // speculative schedules: slots, {tag, value} granules (agent scope / through an XCD's L2), the swap cascade, PersistParams, segment_spec_body
 #include "ptnn_dev_pack.hpp"                 // packed speculative schedule on one CU and over several (segment_pack_body), with its own swap rounds inside a launch
-#include "ptnn_dev_wide.hpp"                 // wide nets (64 < H <= 512): sgd_sweep_wide, matrix-core forward, segment_wide_body, model_wide_kernel; then swap_block and the non-template kernels
+#include "ptnn_dev_wide.hpp"                 // wide nets (64 < H <= 512): sgd_sweep_wide, matrix-core forward, segment_wide_body, model_wide_kernel; then swap_block
 #include "ptnn_dev_tree.hpp"                 // prefetching tree schedule (segment_tree_body), with its own swap rounds inside a launch
 #include "ptnn_dev_kernels.hpp"              // model_kernel, persistent_loop, the __global__ segment kernels, the per-shape table
-#include "ptnn_dev_predict.hpp"              // posterior predictive: run-length pass over the selected rows, forward pass, per-column reduction
+#include "ptnn_dev_predict.hpp"              // posterior predictive: the per-shape forward pass (selection and reduction: ptnn_dev_select.hpp)
 #include "ptnn_dev_forecast.hpp"             // recursive multi-step forecasts: the per-shape recursive forward pass
-#ifndef PTNN_SHAPE_TU
-#include "ptnn_dev_convergence.hpp"          // convergence diagnostics: split-R-hat, split-ESS over trace columns (main translation unit only)
-#include "ptnn_dev_elpd.hpp"                 // predictive accuracy: lppd, WAIC, PSIS-LOO per data row (main translation unit only)
-#include "ptnn_dev_evidence.hpp"             // log evidence: per-rung statistics of the full-data log-likelihood, prior draws (main translation unit only)
-#include "ptnn_dev_calibration.hpp"          // calibration: PIT, quantiles and CRPS of the predictive mixture per data row (main translation unit only)
-#endif
 
 }  // namespace ptnn

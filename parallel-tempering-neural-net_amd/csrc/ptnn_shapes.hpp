@@ -1,6 +1,6 @@
 // ptnn_shapes.hpp -- the compiled (task, n_in, n_out) shapes and the per-shape kernel table.
 // Every shape is its own translation unit (ptnn_shape.hip with -DPTNN_T/-DPTNN_I/-DPTNN_O), so that the build can compile them
-// in parallel; ptnn.hip only references the tables.
+// in parallel; ptnn.hip only references the tables (ptnn_analysis.hip and ptnn_checkpoint.hip reach them through the handle).
 //
 // REG: the shipped time series have 4 lag inputs (REG:916); 5 and 32 cover BASELINE.json's literal [5,H,1] and the synthetic
 // [32,H,1].  CLS: the reference's problem table (CLS:909-995): iris 4/3, ionosphere 34/2, cancer 9/2, wine 11/10, bank 20/2,

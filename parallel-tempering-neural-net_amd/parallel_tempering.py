@@ -530,8 +530,8 @@ class ParallelTemperingBase:
         lib = _lib.load_library()
         if not lib.ptnn_supports(self.task, I, H, O):
             raise _lib.PtnnError(f"no gfx950 kernel for task={self.task} topology={[I, H, O]} in {_lib.library_path()}: "
-                                 f"add X({self.task}, {I}, {O}) to PTNN_SHAPES (csrc/ptnn_shapes.hpp) and to SHAPES in "
-                                 f"__graft_entry__.py, then rebuild; n_hidden may be anything up to 512")
+                                 f"add X({self.task}, {I}, {O}) to PTNN_SHAPES (csrc/ptnn_shapes.hpp) and rebuild; "
+                                 f"n_hidden may be anything up to 512")
         config = dict(
             task=self.task, n_in=I, n_hidden=H, n_out=O, n_replicas_global=self.num_chains,
             n_samples=S, swap_interval=int(self.swap_interval), pt_switch_step=self._pt_switch_step(),

@@ -7,7 +7,11 @@ T=${1:-0}; I=${2:-4}; O=${3:-1}
 C=parallel-tempering-neural-net_amd/csrc
 DEF=${NOSTAMPS:+-DPTNN_NO_STAMPS_BUILD}; [ -z "$NOSTAMPS" ] && DEF=-DPTNN_STAMPS
 F="--offload-arch=gfx950 -O3 -std=c++17 -fPIC $DEF $EXTRA -DPTNN_SHAPES(X)=X($T,$I,$O)"
-/opt/rocm/bin/hipcc $F -c -o /tmp/ptnn_stamps_main.o $C/ptnn.hip
+HOST=""
+for U in ptnn ptnn_analysis ptnn_checkpoint ptnn_text; do
+    /opt/rocm/bin/hipcc $F -c -o /tmp/ptnn_stamps_$U.o $C/$U.hip
+    HOST="$HOST /tmp/ptnn_stamps_$U.o"
+done
 /opt/rocm/bin/hipcc $F -DPTNN_T=$T -DPTNN_I=$I -DPTNN_O=$O -DPTNN_SHAPE_SYMBOL=ptnn_shape_${T}_${I}_${O} -c -o /tmp/ptnn_stamps_shape.o $C/ptnn_shape.hip
-/opt/rocm/bin/hipcc --offload-arch=gfx950 -shared -fPIC -o profiles/tools/libptnn_stamps.so /tmp/ptnn_stamps_main.o /tmp/ptnn_stamps_shape.o
+/opt/rocm/bin/hipcc --offload-arch=gfx950 -shared -fPIC -o profiles/tools/libptnn_stamps.so $HOST /tmp/ptnn_stamps_shape.o
 echo built profiles/tools/libptnn_stamps.so

@@ -32,6 +32,13 @@ def test_header_and_library_agree(pt):
     assert lib.ptnn_abi_version() == 4
 
 
+def test_build_reads_every_shape():
+    """__graft_entry__.SHAPES is parsed from PTNN_SHAPES (csrc/ptnn_shapes.hpp): the parse must not drop a shape."""
+    import __graft_entry__
+    assert __graft_entry__.SHAPES == [(0, 4, 1), (0, 5, 1), (0, 32, 1), (1, 4, 3), (1, 34, 2), (1, 9, 2), (1, 11, 10), (1, 20, 2),
+                                      (1, 16, 10), (1, 6, 18)]
+
+
 def test_supports_table(pt):
     lib = pt.load_library()
     for task, I, H, O in [(0, 4, 5, 1), (0, 4, 10, 1), (0, 5, 5, 1), (1, 4, 12, 3), (1, 34, 50, 2), (1, 9, 12, 2),
