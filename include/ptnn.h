@@ -409,6 +409,59 @@ typedef struct ptnn_elpd_spec {
 
 int ptnn_elpd(ptnn_handle *h, const ptnn_elpd_spec *spec);
 
+/* ---- leave-future-out cross-validation of ordered rows (nothing in the reference: it compares by RMSE only) ----
+ * The question PSIS-LOO cannot answer for a time series: how well are rows i .. i + block - 1 predicted from rows 0 .. i - 1
+ * only (Buerkner, Gabry & Vehtari 2020)?  The data are n_rows ordered rows; the S samples (expanded multiset, as ptnn_elpd) are
+ * conditioned on rows [0, n_fit), 0 < n_fit <= n_rows -- the caller's statement.  With ll[s, n] the pointwise log-likelihood of
+ * ptnn_elpd and C[s, j] = the sum of ll[s, r] over r < j (double, ascending row order), an origin i (0 < i, i + block <= n_rows)
+ * has the log ratio lr_s = C[s, i] - C[s, n_fit] (rows added when i > n_fit, removed when i < n_fit) and the target
+ * t_s = C[s, i + block] - C[s, i]: the joint log density of the next `block` rows, each given its own observed inputs (block
+ * one-step predictions scored jointly, not a recursive block-step forecast).  (lw, khat, T) = the Pareto smoothing of
+ * ptnn_elpd applied to lr (same r_eff rule, cut, tail rule and cap) and elpd_lfo_i = logsumexp(lw + t); DESIGN.md section 18.
+ * An origin i == n_fit has every lr = 0: the weights are uniform, elpd_lfo_i = log mean exp t, khat = +inf, T = 0.
+ * Sources: the three of ptnn_elpd, selected, merged and refused alike -- (1) the trace, (2) host vectors w [n_w, P] with eta
+ * [n_w] (regression) and optional multiplicities, (3) a host loglik [n_w, n_rows] (finite doubles; no forward pass).  The
+ * results depend on the multiset of samples only (bitwise: trace, host vectors, expanded or (distinct, multiplicity), any
+ * scratch budget, the origins of one call or one call each).  Data (sources 1, 2): as ptnn_elpd, rows in time order.
+ * origins [n_origins]: any order, repeats allowed.  Outputs, any may be NULL: elpd_lfo, khat [n_origins] (khat = +inf where
+ * the tail holds <= 4 samples, no smoothing), tail_len [n_origins], loglik_out [S, n_rows] (sources 1, 2, as ptnn_elpd's),
+ * n_samples = S, n_distinct.
+ * Runs on the handle's stream behind everything queued and returns when done; the sums of the columns the origins need and the
+ * forward outputs of a block of rows stay under $PTNN_LFO_SCRATCH_BYTES (read per call, default 1 GiB; half each, at least one
+ * origin and one row), the origins going in several passes if need be, which changes no result.  Touches no chain state, tape,
+ * counter or trace row.  Not with a communicator attached (one GPU only). */
+typedef struct ptnn_lfo_spec {
+    int32_t struct_bytes;         /* = sizeof(ptnn_lfo_spec): ABI guard */
+    /* source 1: the trace (used when w == NULL and loglik == NULL) */
+    const int32_t *replicas;      /* local replica indices, or NULL = all */
+    int32_t n_replicas;           /* entries of replicas (ignored when NULL) */
+    int32_t step0, nsteps, thin;  /* trace rows step0, step0 + thin, ... < step0 + nsteps (thin >= 1) */
+    /* source 2: host vectors */
+    const float *w;               /* [n_w, P] or NULL */
+    const float *eta;             /* [n_w] log tau^2 (regression) */
+    /* source 3: host pointwise log-likelihood */
+    const double *loglik;         /* [n_w, n_rows] or NULL */
+    const int32_t *multiplicity;  /* sources 2, 3: [n_w] >= 0, or NULL = 1 each */
+    int64_t n_w;
+    /* data (sources 1, 2), in time order */
+    int32_t x_source;             /* PTNN_PREDICT_X_HOST | _TRAIN | _TEST */
+    int32_t n_rows;
+    const float *x;               /* [n_rows, n_in + 1] (host rows only) */
+    /* the fit and the origins */
+    int32_t n_fit;                /* the samples have seen rows [0, n_fit), 0 < n_fit <= n_rows */
+    int32_t block;                /* rows scored per origin, >= 1 */
+    const int32_t *origins;       /* [n_origins], 0 < i and i + block <= n_rows */
+    int32_t n_origins;
+    double r_eff;                 /* > 0; 1 = independent draws */
+    /* outputs */
+    double *elpd_lfo, *khat;
+    int64_t *tail_len;
+    double *loglik_out;
+    int64_t *n_samples, *n_distinct;
+} ptnn_lfo_spec;
+
+int ptnn_lfo(ptnn_handle *h, const ptnn_lfo_spec *spec);
+
 /* ---- recursive multi-step forecasts (nothing in the reference: it scores one-step predictions of the test rows only) ----
  * A regression net with n_out == 1 fitted to windows of one series is the one-step map x[t+1] = f_w(x[t-I+1 .. t]), I = n_in.
  * From an origin window (I inputs) step k = 1 .. horizon of a trajectory is y_k = f_w(window_{k-1}) -- exactly ptnn_predict's

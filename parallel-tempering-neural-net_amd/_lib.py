@@ -79,6 +79,21 @@ class ElpdSpec(C.Structure):
 
 ELPD_TAIL_CAP = 4096
 
+
+class LfoSpec(C.Structure):
+    """ptnn_lfo_spec (include/ptnn.h)."""
+    _fields_ = [
+        ("struct_bytes", C.c_int32),
+        ("replicas", C.POINTER(C.c_int32)), ("n_replicas", C.c_int32), ("step0", C.c_int32), ("nsteps", C.c_int32), ("thin", C.c_int32),
+        ("w", C.POINTER(C.c_float)), ("eta", C.POINTER(C.c_float)), ("loglik", C.POINTER(C.c_double)),
+        ("multiplicity", C.POINTER(C.c_int32)), ("n_w", C.c_int64),
+        ("x_source", C.c_int32), ("n_rows", C.c_int32), ("x", C.POINTER(C.c_float)),
+        ("n_fit", C.c_int32), ("block", C.c_int32), ("origins", C.POINTER(C.c_int32)), ("n_origins", C.c_int32),
+        ("r_eff", C.c_double),
+        ("elpd_lfo", C.POINTER(C.c_double)), ("khat", C.POINTER(C.c_double)), ("tail_len", C.POINTER(C.c_int64)),
+        ("loglik_out", C.POINTER(C.c_double)), ("n_samples", C.POINTER(C.c_int64)), ("n_distinct", C.POINTER(C.c_int64)),
+    ]
+
 FORECAST_ORIGIN_HOST, FORECAST_ORIGIN_TRAIN, FORECAST_ORIGIN_TEST = 0, 1, 2
 
 
@@ -221,6 +236,7 @@ SYMBOLS = {
     "ptnn_predict": (C.c_int, [C.c_void_p, C.POINTER(PredictSpec)]),
     "ptnn_convergence": (C.c_int, [C.c_void_p, C.POINTER(ConvergenceSpec)]),
     "ptnn_elpd": (C.c_int, [C.c_void_p, C.POINTER(ElpdSpec)]),
+    "ptnn_lfo": (C.c_int, [C.c_void_p, C.POINTER(LfoSpec)]),
     "ptnn_forecast": (C.c_int, [C.c_void_p, C.POINTER(ForecastSpec)]),
     "ptnn_evidence": (C.c_int, [C.c_void_p, C.POINTER(EvidenceSpec)]),
     "ptnn_calibration": (C.c_int, [C.c_void_p, C.POINTER(CalibrationSpec)]),
@@ -754,6 +770,48 @@ class Sampler:
         ns, nd = C.c_int64(0), C.c_int64(0)
         spec.n_samples, spec.n_distinct = C.pointer(ns), C.pointer(nd)
         self._check(self.lib.ptnn_elpd(self.h, C.byref(spec)))
+        out["n_samples"], out["n_distinct"] = ns.value, nd.value
+        return out
+
+    def lfo(self, data="train", *, n_fit, origins, block=1, replicas=None, step0=0, nsteps=None, thin=1, w=None, eta=None,
+            loglik=None, multiplicity=None, r_eff=1.0, loglik_out=False):
+        """ptnn_lfo: leave-future-out scores of ordered data rows, on the device.  The samples (the three sources of elpd()) are
+        conditioned on rows [0, n_fit); origin i scores rows [i, i + block) -- `block` one-step predictions, each from its own
+        observed inputs, scored jointly; not a recursive forecast -- from rows [0, i) by Pareto-smoothed importance weights.
+        data: "train", "test" or rows [n_rows, n_in + 1] in time order (ignored with loglik).  -> dict(elpd_lfo, khat [n_origins]
+        float64, tail_len [n_origins] int64, loglik [S, n_rows] float64 (loglik_out), n_samples, n_distinct)."""
+        spec = LfoSpec()
+        spec.struct_bytes = C.sizeof(LfoSpec)
+        keep = []
+        dp = C.POINTER(C.c_double)
+        if loglik is not None:
+            la = np.ascontiguousarray(loglik, dtype=np.float64)
+            if la.ndim != 2:
+                raise ValueError(f"loglik must be [n_samples, n_rows], got shape {la.shape}")
+            keep.append(la)
+            spec.loglik, spec.n_w, spec.n_rows = la.ctypes.data_as(dp), la.shape[0], la.shape[1]
+            spec.x_source = PREDICT_X_HOST
+            n_host = la.shape[0]
+        else:
+            self._rows(spec, keep, data, "data", (self.cfg.n_in + 1, "n_in inputs and the target"))
+            n_host = None if w is None else self._host_vectors(spec, keep, w, eta)
+        if n_host is not None:
+            S = self._multiplicity(spec, keep, multiplicity, (n_host,), "multiplicity must have one entry per sample")
+        else:
+            S = math.prod(self._trace_source(spec, keep, replicas, step0, nsteps, thin))
+        og = np.ascontiguousarray(origins, dtype=np.int32).reshape(-1)
+        keep.append(og)
+        spec.origins, spec.n_origins = (_ptr(og, _ip) if og.size else None), og.size
+        spec.n_fit, spec.block, spec.r_eff = int(n_fit), int(block), float(r_eff)
+        n_rows = spec.n_rows
+        out = dict(elpd_lfo=np.empty(og.size), khat=np.empty(og.size), tail_len=np.empty(og.size, np.int64),
+                   loglik=np.empty((max(S, 0), n_rows)) if loglik_out else None)
+        spec.elpd_lfo, spec.khat = out["elpd_lfo"].ctypes.data_as(dp), out["khat"].ctypes.data_as(dp)
+        spec.tail_len = out["tail_len"].ctypes.data_as(C.POINTER(C.c_int64))
+        spec.loglik_out = out["loglik"].ctypes.data_as(dp) if loglik_out else None
+        ns, nd = C.c_int64(0), C.c_int64(0)
+        spec.n_samples, spec.n_distinct = C.pointer(ns), C.pointer(nd)
+        self._check(self.lib.ptnn_lfo(self.h, C.byref(spec)))
         out["n_samples"], out["n_distinct"] = ns.value, nd.value
         return out
 

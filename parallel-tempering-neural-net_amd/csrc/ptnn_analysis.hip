@@ -1,10 +1,11 @@
-// ptnn_analysis.hip -- the posterior analysis calls of libptnn.so: predict, convergence, elpd, forecast, evidence, calibration,
+// ptnn_analysis.hip -- the posterior analysis calls of libptnn.so: predict, convergence, elpd, lfo, forecast, evidence, calibration,
 // and the sample-selection path they share.  The shape-independent analysis kernels are defined in this object: it includes them.
 #include "ptnn_shapes.hpp"
 namespace ptnn {
 #include "ptnn_dev_select.hpp"               // sample selection (run-length pass over the selected rows) and the per-column predictive reduction
 #include "ptnn_dev_convergence.hpp"          // convergence diagnostics: split-R-hat, split-ESS over trace columns
 #include "ptnn_dev_elpd.hpp"                 // predictive accuracy: lppd, WAIC, PSIS-LOO per data row
+#include "ptnn_dev_lfo.hpp"                  // leave-future-out cross-validation: running sums of ll, PSIS per origin
 #include "ptnn_dev_evidence.hpp"             // log evidence: per-rung statistics of the full-data log-likelihood, prior draws
 #include "ptnn_dev_calibration.hpp"          // calibration: PIT, quantiles and CRPS of the predictive mixture per data row
 }  // namespace ptnn
@@ -677,6 +678,171 @@ int ptnn_elpd(ptnn_handle* h, const ptnn_elpd_spec* spec) {
         }
     }
     return copy_out();
+}
+
+// ---- leave-future-out cross-validation (ptnn_dev_lfo.hpp) ----
+int ptnn_lfo(ptnn_handle* h, const ptnn_lfo_spec* spec) {
+    // argument checks first: none of them needs the handle or a device
+    if (int rc = check_spec(spec, "ptnn_lfo_spec")) return rc;
+    const ptnn_lfo_spec& s = *spec;
+    const bool ll_src = s.loglik != nullptr, host_src = s.w != nullptr;
+    SampleSource src = source_of(s, ll_src || host_src, s.eta);
+    const RowSource rows{s.x_source, s.x, s.n_rows, "x_source", "PTNN_PREDICT_X", "x", "n_rows"};
+    if (ll_src && host_src) return fail(-1, "give host vectors w or a host loglik, not both");
+    if (!(s.r_eff > 0.0) || !std::isfinite(s.r_eff)) return fail(-1, "r_eff = %g must be a finite number > 0", s.r_eff);
+    if (!src.host && s.nsteps < 1)
+        return fail(-1, "no source: nsteps = %d trace rows, and neither host vectors w nor a host loglik", s.nsteps);
+    if (int rc = check_source(src, "samples")) return rc;
+    if (s.n_rows < 1) return fail(-1, "n_rows = %d must be >= 1", s.n_rows);
+    if (s.block < 1) return fail(-1, "block = %d must be >= 1", s.block);
+    if (s.n_fit < 1 || s.n_fit > s.n_rows)
+        return fail(-1, "n_fit = %d outside [1, %d]: the samples are conditioned on rows [0, n_fit) of the %d rows", s.n_fit, s.n_rows, s.n_rows);
+    if (s.n_origins < 1 || !s.origins) return fail(-1, "n_origins = %d origins%s: need at least one", s.n_origins, s.origins ? "" : " (origins is NULL)");
+    for (int k = 0; k < s.n_origins; ++k) {
+        const long long i = s.origins[k];
+        if (i < 1 || i >= s.n_rows) return fail(-1, "origin %lld (origins[%d]) outside [1, %d): an origin predicts from the rows before it", i, k, s.n_rows);
+        if (i + s.block > s.n_rows)
+            return fail(-1, "origin %lld (origins[%d]) with block = %d: i + block > n_rows = %d", i, k, s.block, s.n_rows);
+    }
+    if (!ll_src)
+        if (int rc = check_rows(rows)) return rc;
+    if (ll_src && s.loglik_out) return fail(-1, "loglik_out: the log-likelihood is the input of this source");
+    if (src.host)
+        if (int rc = count_samples(nullptr, src)) return rc;
+    if (ll_src)
+        for (long long k = 0; k < src.n_items * s.n_rows; ++k)
+            if (!std::isfinite(s.loglik[k])) return fail(-1, "loglik[%lld, %lld] = %g is not finite", k / s.n_rows, k % s.n_rows, s.loglik[k]);
+    if (int rc = check_handle(h, "ptnn_lfo")) return rc;
+    const int I = h->cfg.n_in, O = h->cfg.n_out;
+    const bool reg = h->cfg.task == PTNN_TASK_REG;
+    if (host_src && reg && !s.eta) return fail(-1, "a regression's host vectors need eta = log tau^2 (one per vector)");
+    if (!ll_src)
+        if (int rc = fit_rows(h, rows)) return rc;
+    if (!ll_src && s.x_source == PTNN_PREDICT_X_HOST && !reg)
+        for (int n = 0; n < s.n_rows; ++n) {
+            const float yv = s.x[(size_t)n * (I + 1) + I];
+            if (!(yv >= 0.0f) || yv >= (float)O || yv != std::floor(yv))
+                return fail(-1, "class label %g in row %d is not an integer in [0, %d)", (double)yv, n, O);
+        }
+    if (!src.host)
+        if (int rc = count_samples(h, src)) return rc;
+    const long long n_items = src.n_items, S = src.M;
+    if (S < 2) return fail(-1, "the selection holds %lld samples: importance weights need at least 2", S);
+    if (int rc = sample_limit(src)) return rc;
+    const long long M = (long long)std::ceil(std::min(0.2 * (double)S, 3.0 * std::sqrt((double)S / s.r_eff)));
+    if (M > ELPD_TAIL_CAP)
+        return fail(-1, "%lld samples with r_eff = %g need a PSIS tail of M = %lld > %d samples: select fewer samples (thin=, chains=) "
+                        "or give a larger r_eff", S, s.r_eff, M, ELPD_TAIL_CAP);
+    if (s.n_samples) *s.n_samples = S;
+
+    if (int rc = start_device(h)) return rc;
+    hipStream_t st = h->stream;
+    DeviceScratch mem;
+    const int n_rows = s.n_rows, n_org = s.n_origins;
+    double *d_lfo = nullptr, *d_khat = nullptr;
+    long long* d_tail = nullptr;
+    HIP_TRY(mem.alloc(&d_lfo, (size_t)n_org));
+    HIP_TRY(mem.alloc(&d_khat, (size_t)n_org));
+    HIP_TRY(mem.alloc(&d_tail, (size_t)n_org));
+    if (int rc = raise_lds_limit(reinterpret_cast<const void*>(lfo_reduce_kernel), LFO_LDS_BYTES)) return rc;
+
+    // the samples: source 3 as it is (every host sample its own entry), else stage a
+    LfoAcc acc{};
+    ElpdRed& ra = acc.a;
+    ra.O = O; ra.S = S; ra.M = (int)M;
+    const float* d_x = nullptr;
+    int xs = 0, U = 0;
+    Distinct d;
+    if (ll_src) {
+        double* d_ll = nullptr;
+        int* d_cnt = nullptr;
+        HIP_TRY(mem.upload(&d_ll, s.loglik, (size_t)n_items * n_rows, st));
+        std::vector<int32_t> ones(s.multiplicity ? 0 : (size_t)n_items, 1);
+        HIP_TRY(mem.upload(&d_cnt, s.multiplicity ? s.multiplicity : ones.data(), (size_t)n_items, st));
+        if (!s.multiplicity)
+            if (int rc = wait_stream(h)) return rc;          // `ones` dies at the end of this block
+        U = (int)n_items;
+        ra.mode = ELPD_HOST; ra.ll = d_ll; ra.ll_stride = n_rows; ra.cnt = d_cnt;
+    } else {
+        if (int rc = upload_rows(h, mem, rows, I + 1, &d_x, &xs)) return rc;
+        if (int rc = distinct_samples(h, mem, src, true, true, &d)) return rc;
+        U = d.U;
+        ra.mode = reg ? ELPD_REG : ELPD_CLS; ra.eta = d.run_eta; ra.y = d_x + I; ra.ys = xs; ra.cnt = d.run_cnt;
+    }
+    ra.U = U;
+    if (s.n_distinct) *s.n_distinct = U;
+
+    // the budget: half for the sums C (the columns n_fit, i and i + block of a pass of origins), half for a block of rows
+    const size_t budget = scratch_budget("PTNN_LFO_SCRATCH_BYTES");
+    const long long cols_fit = (long long)((budget / 2) / ((size_t)U * sizeof(double)));
+    const int org_pass = (int)std::max(1LL, std::min<long long>((cols_fit - 1) / 2, n_org));
+    const int max_slots = 2 * org_pass + 1;
+    long long rows_blk = n_rows;
+    float* d_fx = nullptr;
+    double* d_llb = nullptr;
+    ForwardPlan fwd;
+    std::vector<int> item_run;
+    if (!ll_src) {
+        rows_blk = row_block(budget / 2, (size_t)U * (sizeof(float) * O + (s.loglik_out ? sizeof(double) : 0)), n_rows);
+        HIP_TRY(mem.alloc(&d_fx, (size_t)rows_blk * O * U));
+        if (s.loglik_out) HIP_TRY(mem.alloc(&d_llb, (size_t)rows_blk * U));
+        if (int rc = fwd.init(h, "leave-future-out")) return rc;
+        if (s.loglik_out) if (int rc = item_runs(h, d, n_items, &item_run)) return rc;
+        ra.fx = d_fx; ra.ll_out = d_llb;
+    }
+    double *d_C = nullptr, *d_carry = nullptr;
+    int *d_slot_of = nullptr, *d_org_slot = nullptr;
+    HIP_TRY(mem.alloc(&d_C, (size_t)max_slots * U));
+    HIP_TRY(mem.alloc(&d_carry, (size_t)U));
+    HIP_TRY(mem.alloc(&d_slot_of, (size_t)n_rows + 1));
+    HIP_TRY(mem.alloc(&d_org_slot, (size_t)2 * org_pass));
+    acc.slot_of = d_slot_of; acc.carry = d_carry; acc.C = d_C;
+    std::vector<int> slot_of((size_t)n_rows + 1), org_slot((size_t)2 * org_pass);
+    const unsigned acc_blocks = (unsigned)((U + ELPD_THREADS - 1) / ELPD_THREADS);
+
+    for (int o0 = 0; o0 < n_org; o0 += org_pass) {
+        const int no = std::min(org_pass, n_org - o0);
+        // the columns of this pass, and the last row any of them sums
+        std::fill(slot_of.begin(), slot_of.end(), -1);
+        int n_slots = 0, n_end = s.n_fit;
+        auto slot = [&](int j) { if (slot_of[(size_t)j] < 0) slot_of[(size_t)j] = n_slots++; return slot_of[(size_t)j]; };
+        const int fit_slot = slot(s.n_fit);
+        for (int k = 0; k < no; ++k) {
+            const int i = s.origins[o0 + k];
+            org_slot[(size_t)2 * k] = slot(i);
+            org_slot[(size_t)2 * k + 1] = slot(i + s.block);
+            n_end = std::max(n_end, i + s.block);
+        }
+        if (s.loglik_out && o0 == 0) n_end = n_rows;             // the pointwise output covers every row, once
+        HIP_TRY(hipMemcpyAsync(d_slot_of, slot_of.data(), slot_of.size() * sizeof(int), hipMemcpyHostToDevice, st));
+        HIP_TRY(hipMemcpyAsync(d_org_slot, org_slot.data(), (size_t)2 * no * sizeof(int), hipMemcpyHostToDevice, st));
+        HIP_TRY(hipMemsetAsync(d_carry, 0, (size_t)U * sizeof(double), st));
+        // stage b + c in blocks of rows, ascending
+        for (long long r0 = 0; r0 < n_end; r0 += rows_blk) {
+            const int nr = (int)std::min<long long>(rows_blk, n_end - r0);
+            if (!ll_src)
+                if (int rc = fwd.launch(h, d.base, d.run_off, d_x, xs, (int)r0, nr, U, d_fx)) return rc;
+            ra.row0 = (int)r0;
+            acc.nrows = nr;
+            hipLaunchKernelGGL(lfo_accum_kernel, dim3(acc_blocks), dim3(ELPD_THREADS), 0, st, acc);
+            HIP_TRY(hipGetLastError());
+            if (s.loglik_out && o0 == 0) {
+                const long long n_ll = (long long)nr * U;
+                hipLaunchKernelGGL(elpd_loglik_kernel, dim3((unsigned)((n_ll + ELPD_THREADS - 1) / ELPD_THREADS)), dim3(ELPD_THREADS), 0, st, ra, nr);
+                HIP_TRY(hipGetLastError());
+                if (int rc = scatter_samples(h, (const double*)d_llb, nr, U, item_run, src.weights(), s.loglik_out, (size_t)n_rows, (size_t)r0)) return rc;
+            }
+        }
+        // stage d: one work-group per origin of the pass
+        LfoRed lr{d_C, ra.cnt, d_org_slot, fit_slot, U, (int)M, S, d_lfo + o0, d_khat + o0, d_tail + o0};
+        hipLaunchKernelGGL(lfo_reduce_kernel, dim3((unsigned)no), dim3(ELPD_THREADS), LFO_LDS_BYTES, st, lr);
+        HIP_TRY(hipGetLastError());
+        if (int rc = wait_stream(h)) return rc;                  // slot_of and org_slot are rewritten by the next pass
+    }
+    HIP_TRY(fetch(s.elpd_lfo, d_lfo, (size_t)n_org, st));
+    HIP_TRY(fetch(s.khat, d_khat, (size_t)n_org, st));
+    HIP_TRY(fetch((long long*)s.tail_len, d_tail, (size_t)n_org, st));
+    return wait_stream(h);
 }
 
 // ---- recursive forecasts (ptnn_dev_forecast.hpp) ----

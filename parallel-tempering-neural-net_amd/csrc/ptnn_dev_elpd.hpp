@@ -7,6 +7,7 @@
 //      host can refuse them.
 //   b. the per-shape predict_forward_kernel of ptnn_dev_predict.hpp, unchanged (all n_out columns of a row are computed).
 //   c. elpd_reduce_kernel: one work-group per data row; ll is formed on the fly from the fp32 outputs, everything after is double.
+//      Its Pareto smoothing is psis_reduce, which lfo_reduce_kernel (ptnn_dev_lfo.hpp) shares.
 // Every sum over samples is a 128-bit fixed-point sum of terms scaled by the row's exact maximum (integer addition: the result
 // depends on the multiset of samples only, not on their order or on how repeats are grouped), and the tail is sorted by its ll
 // key and merged before the Pareto fit.  So the trace, host vectors, expanded or (distinct, multiplicity) input and any block
@@ -165,52 +166,23 @@ __device__ int block_excl_scan(int* buf, int v, int* total) {
     return incl - v;
 }
 
-__global__ void __launch_bounds__(ELPD_THREADS) elpd_reduce_kernel(const ElpdRed a) {
-    __shared__ ElpdShared sh;
+// The Pareto smoothing of stage c over U entries with multiplicities, shared by elpd_reduce_kernel and lfo_reduce_kernel
+// (ptnn_dev_lfo.hpp): the cut by radix select, the tail compacted into LDS, sorted and merged, gpdfit, and the two sums
+// *elpd = logsumexp(lw + t) - logsumexp(lw) over body samples and smoothed tail positions.  `Src` gives every entry:
+//   int count(u)                      multiplicity (0 = absent)
+//   void get(u, lw, t)                lw = lr - max(lr) <= 0 and the target t
+//   PAIR                              false: one stored word gives both (ptnn_elpd: lw = min(ll) - ll, t = ll); true: (lw, t)
+//                                     pairs, t kept in tval [ELPD_TAIL_CAP], entries ordered by lw, then t
+//   key(lw, t), second(t)             the stored words, ascending key = ascending lw
+//   decode(key, second, lw, t)        their values back
+// Every thread of the work-group calls it and gets the three results.
+template <class Src>
+__device__ void psis_reduce(ElpdShared& sh, unsigned long long* tval, const Src& src, int U, long long S_, int M, double* elpd,
+                            double* khat_out, long long* tail_out) {
     const int tid = threadIdx.x, lane = tid & (WAVE - 1), wave = tid >> 6;
-    const int r = blockIdx.x;
-    const double y = a.mode == ELPD_HOST ? 0.0 : (double)a.y[(size_t)(a.row0 + r) * a.ys];
-    const double S = (double)a.S;
     const double INF = __longlong_as_double(0x7ff0000000000000ll);
-
-    // pass 1: the extremes of ll
-    double mn = INF, mx = -INF;
-    for (int u = tid; u < a.U; u += ELPD_THREADS) {
-        if (a.cnt[u] == 0) continue;
-        const double l = elpd_ll(a, r, u, y);
-        mn = fmin(mn, l); mx = fmax(mx, l);
-    }
-    block_min_max(sh, mn, mx);
-    const double R = mx - mn;
-    // pass 2: sum c exp(ll - max) and sum c (ll - min) / R
-    Fix128 fe{0, 0}, fm{0, 0};
-    for (int u = tid; u < a.U; u += ELPD_THREADS) {
-        const unsigned c = (unsigned)a.cnt[u];
-        if (c == 0) continue;
-        const double l = elpd_ll(a, r, u, y);
-        fix_add(fe, exp(l - mx), c);
-        if (R > 0.0) fix_add(fm, (l - mn) / R, c);
-    }
-    const double se = block_fix_sum(sh, fe);
-    const double sm = block_fix_sum(sh, fm);
-    const double lppd = mx + log(se / S);
-    double mean = R > 0.0 ? mn + R * (sm / S) : mn;
-    mean = fmin(fmax(mean, mn), mx);
-    // pass 3: sum c (ll - mean)^2, each term scaled by the largest one
-    const double D = fmax((mx - mean) * (mx - mean), (mean - mn) * (mean - mn));
-    Fix128 fv{0, 0};
-    if (D > 0.0) {
-        for (int u = tid; u < a.U; u += ELPD_THREADS) {
-            const unsigned c = (unsigned)a.cnt[u];
-            if (c == 0) continue;
-            const double d = elpd_ll(a, r, u, y) - mean;
-            fix_add(fv, (d * d) / D, c);
-        }
-    }
-    const double p_waic = D > 0.0 ? D * block_fix_sum(sh, fv) / (S - 1.0) : 0.0;
-
-    // the cutoff: lw = lr - max(lr) = min(ll) - ll; the value at ascending expanded rank S - M - 1, by 8 passes of 8 bits
-    const long long rank = a.S - a.M - 1;
+    // the cutoff: the value of lw at ascending expanded rank S - M - 1, by 8 passes of 8 bits
+    const long long rank = S_ - M - 1;
     const double LOG_DBL_MIN = -708.39641853226408;             // log(DBL_MIN)
     double cut = LOG_DBL_MIN;
     if (rank >= 0) {
@@ -220,10 +192,12 @@ __global__ void __launch_bounds__(ELPD_THREADS) elpd_reduce_kernel(const ElpdRed
             const int shift = 56 - 8 * pass;
             for (int k = tid; k < 256; k += ELPD_THREADS) sh.hist[k] = 0u;
             __syncthreads();
-            for (int u = tid; u < a.U; u += ELPD_THREADS) {
-                const unsigned c = (unsigned)a.cnt[u];
+            for (int u = tid; u < U; u += ELPD_THREADS) {
+                const unsigned c = (unsigned)src.count(u);
                 if (c == 0) continue;
-                const unsigned long long key = elpd_key(mn - elpd_ll(a, r, u, y));
+                double lw, t;
+                src.get(u, lw, t);
+                const unsigned long long key = elpd_key(lw);
                 if (pass == 0 || (key >> (shift + 8)) == (prefix >> (shift + 8))) atomicAdd(&sh.hist[(key >> shift) & 255u], c);
             }
             __syncthreads();
@@ -242,18 +216,22 @@ __global__ void __launch_bounds__(ELPD_THREADS) elpd_reduce_kernel(const ElpdRed
         }
         cut = fmax(elpd_unkey(prefix), LOG_DBL_MIN);
     }
-    // the tail: samples with lw > cut, compacted as (~key(ll), count) into LDS; T = their expanded count
+    // the tail: samples with lw > cut, compacted as (stored words, count) into LDS; T = their expanded count
     if (tid == 0) sh.n_ent = 0;
     __syncthreads();
     long long t_part = 0;
-    for (int u = tid; u < a.U; u += ELPD_THREADS) {
-        const int c = a.cnt[u];
+    for (int u = tid; u < U; u += ELPD_THREADS) {
+        const int c = src.count(u);
         if (c == 0) continue;
-        const double l = elpd_ll(a, r, u, y);
-        if (mn - l > cut) {
+        double lw, t;
+        src.get(u, lw, t);
+        if (lw > cut) {
             t_part += c;
             const int slot = atomicAdd(&sh.n_ent, 1);
-            if (slot < ELPD_TAIL_CAP) { sh.tkey[slot] = ~elpd_key(l); sh.tpos[slot] = c; }
+            if (slot < ELPD_TAIL_CAP) {
+                sh.tkey[slot] = src.key(lw, t); sh.tpos[slot] = c;
+                if constexpr (Src::PAIR) tval[slot] = src.second(t);
+            }
         }
     }
     const long long T = block_sum_ll(sh, t_part);                // (barriers inside: n_ent is final)
@@ -262,10 +240,13 @@ __global__ void __launch_bounds__(ELPD_THREADS) elpd_reduce_kernel(const ElpdRed
     bool smooth = false;
     const double ecut = exp(cut);
     if (T > 4) {
-        // bitonic sort of the entries (padded to a power of two with the largest key), ascending key = ascending lw
+        // bitonic sort of the entries (padded to a power of two with the largest words), ascending = ascending lw
         int npow = 1;
         while (npow < n_ent) npow <<= 1;
-        for (int k = n_ent + tid; k < npow; k += ELPD_THREADS) { sh.tkey[k] = ~0ull; sh.tpos[k] = 0; }
+        for (int k = n_ent + tid; k < npow; k += ELPD_THREADS) {
+            sh.tkey[k] = ~0ull; sh.tpos[k] = 0;
+            if constexpr (Src::PAIR) tval[k] = ~0ull;
+        }
         __syncthreads();
         for (int size = 2; size <= npow; size <<= 1) {
             for (int stride = size >> 1; stride > 0; stride >>= 1) {
@@ -274,17 +255,20 @@ __global__ void __launch_bounds__(ELPD_THREADS) elpd_reduce_kernel(const ElpdRed
                     const int j = i + stride;
                     const bool up = (i & size) == 0;
                     const unsigned long long ki = sh.tkey[i], kj = sh.tkey[j];
-                    if ((ki > kj) == up) {
+                    bool above = ki > kj;
+                    if constexpr (Src::PAIR) above = above || (ki == kj && tval[i] > tval[j]);
+                    if (above == up) {
                         sh.tkey[i] = kj; sh.tkey[j] = ki;
                         const int ci = sh.tpos[i]; sh.tpos[i] = sh.tpos[j]; sh.tpos[j] = ci;
+                        if constexpr (Src::PAIR) { const unsigned long long vi = tval[i]; tval[i] = tval[j]; tval[j] = vi; }
                     }
                 }
                 __syncthreads();
             }
         }
-        // merge equal keys: thread tid owns entries [tid * per, (tid + 1) * per) of the sorted list
+        // merge equal entries: thread tid owns entries [tid * per, (tid + 1) * per) of the sorted list
         const int per = (npow + ELPD_THREADS - 1) / ELPD_THREADS;
-        unsigned long long kk[ELPD_PER_THREAD];
+        unsigned long long kk[ELPD_PER_THREAD], vv[Src::PAIR ? ELPD_PER_THREAD : 1];
         int cc[ELPD_PER_THREAD], hh[ELPD_PER_THREAD];
         int csum = 0, hsum = 0;
 #pragma unroll
@@ -293,7 +277,12 @@ __global__ void __launch_bounds__(ELPD_THREADS) elpd_reduce_kernel(const ElpdRed
             const bool live = q < per && i < n_ent;
             kk[q] = live ? sh.tkey[i] : 0ull;
             cc[q] = live ? sh.tpos[i] : 0;
-            hh[q] = live && (i == 0 || sh.tkey[i - 1] != kk[q]) ? 1 : 0;
+            bool head = live && (i == 0 || sh.tkey[i - 1] != kk[q]);
+            if constexpr (Src::PAIR) {
+                vv[q] = live ? tval[i] : 0ull;
+                head = head || (live && tval[i - 1] != vv[q]);     // (i > 0 here: i == 0 is a head already)
+            }
+            hh[q] = head ? 1 : 0;
             csum += cc[q]; hsum += hh[q];
         }
         int tot_c = 0, tot_h = 0;
@@ -301,14 +290,22 @@ __global__ void __launch_bounds__(ELPD_THREADS) elpd_reduce_kernel(const ElpdRed
         int grp = block_excl_scan(sh.scan1, hsum, &tot_h);      // (barriers inside: every entry has been read)
 #pragma unroll
         for (int q = 0; q < ELPD_PER_THREAD; ++q) {
-            if (hh[q]) { sh.tkey[grp] = kk[q]; sh.tpos[grp] = pos; ++grp; }
+            if (hh[q]) {
+                sh.tkey[grp] = kk[q]; sh.tpos[grp] = pos;
+                if constexpr (Src::PAIR) tval[grp] = vv[q];
+                ++grp;
+            }
             pos += cc[q];
         }
         if (tid == 0) { sh.tpos[tot_h] = tot_c; sh.n_grp = tot_h; }
         __syncthreads();
         const int G = sh.n_grp;
         const double n = (double)T;
-        auto x_of = [&](int g) -> double { return exp(mn - elpd_unkey(~sh.tkey[g])) - ecut; };
+        auto x_of = [&](int g) -> double {
+            double lw, t;
+            src.decode(sh.tkey[g], Src::PAIR ? tval[g] : 0ull, lw, t);
+            return exp(lw) - ecut;
+        };
         auto group_at = [&](long long p) -> int {                    // the distinct entry holding expanded position p
             int lo = 0, hi = G - 1;
             while (lo < hi) { const int mid = (lo + hi + 1) >> 1; if (sh.tpos[mid] <= p) lo = mid; else hi = mid - 1; }
@@ -369,48 +366,122 @@ __global__ void __launch_bounds__(ELPD_THREADS) elpd_reduce_kernel(const ElpdRed
         return v > 0.0 ? 0.0 : v;
     };
     const int G = smooth ? sh.n_grp : 0;
-    // pass 4: the largest lw and lw + ll, body samples and smoothed tail positions
+    auto t_at = [&](long long j) -> double {                        // the target of tail position j
+        int lo = 0, hi = G - 1;
+        while (lo < hi) { const int mid = (lo + hi + 1) >> 1; if (sh.tpos[mid] <= j) lo = mid; else hi = mid - 1; }
+        double lw, t;
+        src.decode(sh.tkey[lo], Src::PAIR ? tval[lo] : 0ull, lw, t);
+        return t;
+    };
+    // the largest lw and lw + t, body samples and smoothed tail positions
     double a1 = -INF, a2 = -INF;
-    for (int u = tid; u < a.U; u += ELPD_THREADS) {
-        if (a.cnt[u] == 0) continue;
-        const double l = elpd_ll(a, r, u, y), lw = mn - l;
+    for (int u = tid; u < U; u += ELPD_THREADS) {
+        if (src.count(u) == 0) continue;
+        double lw, l;
+        src.get(u, lw, l);
         if (smooth && lw > cut) continue;
         a1 = fmax(a1, lw); a2 = fmax(a2, lw + l);
     }
     for (long long j = tid; j < (smooth ? T : 0); j += ELPD_THREADS) {
-        int lo = 0, hi = G - 1;
-        while (lo < hi) { const int mid = (lo + hi + 1) >> 1; if (sh.tpos[mid] <= j) lo = mid; else hi = mid - 1; }
-        const double l = elpd_unkey(~sh.tkey[lo]), lw = lw_smooth(j);
+        const double l = t_at(j), lw = lw_smooth(j);
         a1 = fmax(a1, lw); a2 = fmax(a2, lw + l);
     }
     double na1 = -a1;
     block_min_max(sh, na1, a2);                                  // min of -a1 = -max of a1; max of a2
     a1 = -na1;
     const double b2 = a2;
-    // pass 5: sum c exp(lw - a1) and sum c exp(lw + ll - b2)
+    // sum c exp(lw - a1) and sum c exp(lw + t - b2)
     Fix128 fz{0, 0}, fl{0, 0};
-    for (int u = tid; u < a.U; u += ELPD_THREADS) {
-        const unsigned c = (unsigned)a.cnt[u];
+    for (int u = tid; u < U; u += ELPD_THREADS) {
+        const unsigned c = (unsigned)src.count(u);
         if (c == 0) continue;
-        const double l = elpd_ll(a, r, u, y), lw = mn - l;
+        double lw, l;
+        src.get(u, lw, l);
         if (smooth && lw > cut) continue;
         fix_add(fz, exp(lw - a1), c);
         fix_add(fl, exp(lw + l - b2), c);
     }
     for (long long j = tid; j < (smooth ? T : 0); j += ELPD_THREADS) {
-        int lo = 0, hi = G - 1;
-        while (lo < hi) { const int mid = (lo + hi + 1) >> 1; if (sh.tpos[mid] <= j) lo = mid; else hi = mid - 1; }
-        const double l = elpd_unkey(~sh.tkey[lo]), lw = lw_smooth(j);
+        const double l = t_at(j), lw = lw_smooth(j);
         fix_add(fz, exp(lw - a1), 1u);
         fix_add(fl, exp(lw + l - b2), 1u);
     }
     const double z = block_fix_sum(sh, fz);
     const double e = block_fix_sum(sh, fl);
+    *elpd = (b2 + log(e)) - (a1 + log(z));
+    *khat_out = khat;
+    *tail_out = T;
+}
+
+// ptnn_elpd's entries: the samples of one data row, lr = -ll and the target ll; the tail keeps ~key(ll)
+struct ElpdLooSrc {
+    const ElpdRed& a;
+    int r;
+    double y, mn;               // mn = min(ll) = -max(lr)
+    static constexpr bool PAIR = false;
+    __device__ __forceinline__ int count(int u) const { return a.cnt[u]; }
+    __device__ __forceinline__ void get(int u, double& lw, double& t) const { t = elpd_ll(a, r, u, y); lw = mn - t; }
+    __device__ __forceinline__ unsigned long long key(double, double t) const { return ~elpd_key(t); }
+    __device__ __forceinline__ unsigned long long second(double) const { return 0ull; }
+    __device__ __forceinline__ void decode(unsigned long long k, unsigned long long, double& lw, double& t) const {
+        t = elpd_unkey(~k); lw = mn - t;
+    }
+};
+
+__global__ void __launch_bounds__(ELPD_THREADS) elpd_reduce_kernel(const ElpdRed a) {
+    __shared__ ElpdShared sh;
+    const int tid = threadIdx.x;
+    const int r = blockIdx.x;
+    const double y = a.mode == ELPD_HOST ? 0.0 : (double)a.y[(size_t)(a.row0 + r) * a.ys];
+    const double S = (double)a.S;
+    const double INF = __longlong_as_double(0x7ff0000000000000ll);
+
+    // pass 1: the extremes of ll
+    double mn = INF, mx = -INF;
+    for (int u = tid; u < a.U; u += ELPD_THREADS) {
+        if (a.cnt[u] == 0) continue;
+        const double l = elpd_ll(a, r, u, y);
+        mn = fmin(mn, l); mx = fmax(mx, l);
+    }
+    block_min_max(sh, mn, mx);
+    const double R = mx - mn;
+    // pass 2: sum c exp(ll - max) and sum c (ll - min) / R
+    Fix128 fe{0, 0}, fm{0, 0};
+    for (int u = tid; u < a.U; u += ELPD_THREADS) {
+        const unsigned c = (unsigned)a.cnt[u];
+        if (c == 0) continue;
+        const double l = elpd_ll(a, r, u, y);
+        fix_add(fe, exp(l - mx), c);
+        if (R > 0.0) fix_add(fm, (l - mn) / R, c);
+    }
+    const double se = block_fix_sum(sh, fe);
+    const double sm = block_fix_sum(sh, fm);
+    const double lppd = mx + log(se / S);
+    double mean = R > 0.0 ? mn + R * (sm / S) : mn;
+    mean = fmin(fmax(mean, mn), mx);
+    // pass 3: sum c (ll - mean)^2, each term scaled by the largest one
+    const double D = fmax((mx - mean) * (mx - mean), (mean - mn) * (mean - mn));
+    Fix128 fv{0, 0};
+    if (D > 0.0) {
+        for (int u = tid; u < a.U; u += ELPD_THREADS) {
+            const unsigned c = (unsigned)a.cnt[u];
+            if (c == 0) continue;
+            const double d = elpd_ll(a, r, u, y) - mean;
+            fix_add(fv, (d * d) / D, c);
+        }
+    }
+    const double p_waic = D > 0.0 ? D * block_fix_sum(sh, fv) / (S - 1.0) : 0.0;
+
+    // the Pareto smoothing of lr = -ll (lw = lr - max(lr) = min(ll) - ll) with the target ll
+    const ElpdLooSrc src{a, r, y, mn};
+    double elpd_loo, khat;
+    long long T;
+    psis_reduce(sh, nullptr, src, a.U, a.S, a.M, &elpd_loo, &khat, &T);
     if (tid == 0) {
         const int n = a.row0 + r;
         if (a.lppd) a.lppd[n] = lppd;
         if (a.p_waic) a.p_waic[n] = p_waic;
-        if (a.elpd_loo) a.elpd_loo[n] = (b2 + log(e)) - (a1 + log(z));
+        if (a.elpd_loo) a.elpd_loo[n] = elpd_loo;
         if (a.khat) a.khat[n] = khat;
         if (a.tail_len) a.tail_len[n] = T;
     }

@@ -14,7 +14,7 @@
 // next interval -- one launch per run.  ptnn_diag.hpp is included by diagnostic builds only.
 // Everything included here is a template or inline, so every translation unit may include it.  A non-template __global__ kernel
 // lives in a part that exactly one translation unit includes, inside namespace ptnn after ptnn_shapes.hpp, and that object holds
-// it: ptnn_dev_swap.hpp in ptnn.hip; ptnn_dev_select.hpp, ptnn_dev_convergence.hpp, ptnn_dev_elpd.hpp, ptnn_dev_evidence.hpp and
+// it: ptnn_dev_swap.hpp in ptnn.hip; ptnn_dev_select.hpp, ptnn_dev_convergence.hpp, ptnn_dev_elpd.hpp, ptnn_dev_lfo.hpp, ptnn_dev_evidence.hpp and
 // ptnn_dev_calibration.hpp in ptnn_analysis.hip.
 //
 // Written for gfx950 only: wave size 64, DPP row operations, v_permlane{16,32}_swap.

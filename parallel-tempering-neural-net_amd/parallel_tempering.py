@@ -13,6 +13,8 @@ as a second kernel; this module only configures the run, fetches the traces and 
 """
 import math
 import os
+import shutil
+import tempfile
 import time
 import warnings
 from collections import namedtuple
@@ -250,8 +252,20 @@ def _se_total(x):
 
 
 def elpd_compare(a, b):
-    """The elpd difference of two PredictiveAccuracy results on the same data rows, a - b, with the paired standard error
-    sqrt(N var(a_i - b_i, ddof 1)).  -> dict(elpd_loo_diff, se_loo_diff, elpd_waic_diff, se_waic_diff); host arithmetic only."""
+    """The elpd difference of two results on the same data, a - b, with the paired standard error sqrt(N var(a_i - b_i, ddof 1)).
+    Two PredictiveAccuracy results over the same rows -> dict(elpd_loo_diff, se_loo_diff, elpd_waic_diff, se_waic_diff); two
+    LeaveFutureOut results over equal origins and block -> dict(elpd_lfo_diff, se_lfo_diff).  A mix of the two is refused: a
+    leave-one-out and a leave-future-out score answer different questions.  Host arithmetic only."""
+    lfo_a, lfo_b = isinstance(a, LeaveFutureOut), isinstance(b, LeaveFutureOut)
+    if lfo_a != lfo_b:
+        raise ValueError("elpd_compare needs two results of one kind: a LeaveFutureOut cannot be compared with a PredictiveAccuracy")
+    if lfo_a:
+        if a.block != b.block:
+            raise ValueError(f"the two results score different blocks: block = {a.block} vs {b.block}")
+        if not np.array_equal(np.asarray(a.origins), np.asarray(b.origins)):
+            raise ValueError(f"the two results cover different origins: {len(a.origins)} vs {len(b.origins)} (or other rows)")
+        da = np.asarray(a.elpd_lfo_i, np.float64) - np.asarray(b.elpd_lfo_i, np.float64)
+        return dict(elpd_lfo_diff=float(np.sum(a.elpd_lfo_i) - np.sum(b.elpd_lfo_i)), se_lfo_diff=_se_total(da))
     la, lb = np.asarray(a.elpd_loo_i, np.float64), np.asarray(b.elpd_loo_i, np.float64)
     if la.shape != lb.shape:
         raise ValueError(f"the two results cover different rows: {la.shape[0]} vs {lb.shape[0]}")
@@ -259,6 +273,85 @@ def elpd_compare(a, b):
     wb = np.asarray(b.lppd_i, np.float64) - np.asarray(b.p_waic_i, np.float64)
     return dict(elpd_loo_diff=float(np.sum(la) - np.sum(lb)), se_loo_diff=_se_total(la - lb),
                 elpd_waic_diff=float(np.sum(wa) - np.sum(wb)), se_waic_diff=_se_total(wa - wb))
+
+
+# leave_future_out's result: totals elpd_lfo, se_elpd_lfo (float; sqrt(n var(pointwise, ddof 1)) over the origins); per origin
+# (ascending) elpd_lfo_i, khat [n] float64, tail_len [n] int64, origins [n], fit_origin [n] (the fit that scored it: the rows
+# [0, fit_origin) it had seen), exact [n] bool (fit_origin == origin: no importance weights); refit_origins (in walk order);
+# n_refits; k_threshold; n_samples (of the first fit); block
+LeaveFutureOut = namedtuple("LeaveFutureOut", "elpd_lfo se_elpd_lfo elpd_lfo_i khat tail_len origins fit_origin exact refit_origins "
+                            "n_refits k_threshold n_samples block")
+
+
+def good_k(n_samples):
+    """The k-hat threshold of DESIGN.md section 13 for S samples: min(1 - 1 / log10(S), 0.7)."""
+    return min(1.0 - 1.0 / math.log10(n_samples), 0.7)
+
+
+def lfo_refit_seed(seed, origin):
+    """The seed of the sampler leave_future_out() refits on rows [0, origin): a function of the object's seed and the origin."""
+    return (int(seed) + 0x9E3779B97F4A7C15 * (int(origin) + 1)) % (1 << 64)
+
+
+def lfo_walk(origins, n_fit, first_fit, score, fit=None, *, k_threshold, max_refits=None):
+    """The walk of approximate leave-future-out cross-validation (Buerkner, Gabry & Vehtari 2020, algorithm 1), in both
+    directions.  `first_fit` has seen rows [0, n_fit).  Origins >= n_fit are walked forward (ascending) from it, origins < n_fit
+    backward (descending); each walk begins again at `first_fit`.  score(fit_object, its n_fit, origins) -> dict(elpd_lfo, khat,
+    tail_len) scores all remaining origins from the current fit; the origins before the first one (in walk order) whose khat
+    exceeds k_threshold (+inf, the khat of a tail of <= 4 samples, does; the origin at the fit itself is exact) are kept.  With fit(origin) -> fit_object (None: never refit) a fit on rows [0, origin) replaces the
+    current one, scores that origin exactly and the walk goes on from there; after `max_refits` refits (None = no bound) the
+    remaining origins are kept as scored, high khat included.  Needs no GPU: the two callables do the work.
+    -> dict(origins (ascending, repeats removed), elpd_lfo, khat, tail_len, fit_origin, exact, refit_origins, n_refits,
+    max_refits_hit)."""
+    og = sorted({int(i) for i in np.asarray(origins).reshape(-1)})
+    if not og:
+        raise ValueError("no origin to score")
+    if max_refits is not None and max_refits < 0:
+        raise ValueError(f"max_refits = {max_refits} must be >= 0 (or None)")
+    res = {i: None for i in og}
+    refit_origins = []
+    hit = False
+    for order in ([i for i in og if i >= n_fit], [i for i in reversed(og) if i < n_fit]):
+        cur, cur_fit, rest = first_fit, int(n_fit), order
+        while rest:
+            out = score(cur, cur_fit, rest)
+            kh = np.asarray(out["khat"], np.float64)
+            # +inf (a tail of <= 4 samples: raw weights, nothing to diagnose them by) exceeds every threshold, as does NaN;
+            # only the origin at the fit itself, whose weights are uniform, is exact whatever its khat says
+            high = np.flatnonzero(~(kh <= k_threshold) & (np.asarray(rest) != cur_fit))
+            stop = int(high[0]) if high.size else len(rest)
+            can_refit = fit is not None and stop < len(rest) and (max_refits is None or len(refit_origins) < max_refits)
+            if stop < len(rest) and fit is not None and not can_refit:
+                hit = True
+            keep = stop if can_refit else len(rest)
+            for k in range(keep):
+                res[rest[k]] = (float(out["elpd_lfo"][k]), float(kh[k]), int(out["tail_len"][k]), cur_fit)
+            if not can_refit:
+                break
+            rest = rest[stop:]
+            cur_fit = rest[0]
+            cur = fit(cur_fit)
+            refit_origins.append(cur_fit)
+    fit_origin = np.array([res[i][3] for i in og], np.int64)
+    oa = np.array(og, np.int64)
+    return dict(origins=oa, elpd_lfo=np.array([res[i][0] for i in og]), khat=np.array([res[i][1] for i in og]),
+                tail_len=np.array([res[i][2] for i in og], np.int64), fit_origin=fit_origin, exact=fit_origin == oa,
+                refit_origins=refit_origins, n_refits=len(refit_origins), max_refits_hit=hit)
+
+
+def lfo_origins(n_rows, n_fit, block, min_train=None):
+    """The origins leave_future_out() scores: min_train .. n_rows - block.  min_train=None: n_fit when rows follow the fit
+    (the sequential score of the rows after it), else n_rows // 2.  Refusals that need no GPU."""
+    if block < 1:
+        raise ValueError(f"block = {block} must be >= 1")
+    if not 0 < n_fit <= n_rows:
+        raise ValueError(f"n_fit = {n_fit} outside [1, {n_rows}]: the fit has seen rows [0, n_fit) of the {n_rows} rows")
+    L = (n_fit if n_fit < n_rows else n_rows // 2) if min_train is None else int(min_train)
+    if L < 1:
+        raise ValueError(f"min_train = {L} must be >= 1: an origin predicts from the rows before it")
+    if L + block > n_rows:
+        raise ValueError(f"min_train = {L} with block = {block} leaves no origin: i + block must be <= {n_rows} rows")
+    return np.arange(L, n_rows - block + 1, dtype=np.int64)
 
 
 # predictive_calibration's result.  Regression: crps, se_crps (float; None with crps=False); crps_i, pit, pred_mean, pred_sd
@@ -373,6 +466,12 @@ class ParallelTemperingBase:
                  transport=None, waves_per_replica=0, schedule=0, groups_per_replica=0, trace_capacity=0, swap_rule=0,
                  label_swap=False, shared_noise=True, write_files=True, io_threads=None, forward_bf16=0, overlap_chunks=8,
                  adapt_ladder=False):
+        # what leave_future_out() builds its refits from: the keyword arguments as given, and NumSample
+        self._ctor_kw = dict(device=device, devices=devices, exchange=exchange, transport=transport, waves_per_replica=waves_per_replica,
+                             schedule=schedule, groups_per_replica=groups_per_replica, trace_capacity=trace_capacity,
+                             swap_rule=swap_rule, label_swap=label_swap, shared_noise=shared_noise, io_threads=io_threads,
+                             forward_bf16=forward_bf16, overlap_chunks=overlap_chunks, adapt_ladder=adapt_ladder)
+        self._num_sample_arg = NumSample
         # FNN chain variables (REG:491-494)
         self.traindata = traindata
         self.testdata = testdata
@@ -1066,6 +1165,93 @@ class ParallelTemperingBase:
                                   p_waic_i=p_waic_i, khat=khat, good_k=good_k, n_high_k=n_high,
                                   log_lik=(loglik if loglik is not None else out["loglik"]) if return_pointwise else None,
                                   n_samples=n_s, n_distinct=out["n_distinct"])
+
+    # ------------------------------------------------------------------ leave-future-out cross-validation (not in the reference)
+    def _lfo_refit(self, rows, origin):
+        """A fresh sampler of this class and these constructor arguments fitted on rows [0, origin): no files, its own scratch
+        directory (removed after the run), seed lfo_refit_seed(seed, origin)."""
+        path = tempfile.mkdtemp(prefix="ptnn_lfo_")
+        try:
+            args = [self.use_langevin_gradients, self.learn_rate, rows[:origin], self.testdata, self.topology, self.num_chains,
+                    self.maxtemp, self._num_sample_arg, self.swap_interval]
+            if self.task != TASK_CLS:
+                args.append(self.langevin_prob)
+            pt = type(self)(*args, path, seed=lfo_refit_seed(self.seed, origin), write_files=False, **self._ctor_kw)
+            pt.initialize_chains(self.burn_in)
+            pt.run_chains()
+        finally:
+            shutil.rmtree(path, ignore_errors=True)
+        return pt
+
+    def leave_future_out(self, min_train=None, block=1, data="train", *, n_fit=None, refit=True, k_threshold=None, max_refits=None,
+                         burn_in=None, chains="all", thin=1, r_eff=1.0):
+        """Leave-future-out cross-validation of ordered rows on the GPU (Buerkner, Gabry & Vehtari 2020):
+        for every origin i, the log predictive density of rows i .. i + block - 1 from a posterior that has seen rows 0 .. i - 1
+        only -- the question to ask of a time series, where PSIS-LOO (predictive_accuracy) lets a row's neighbours, its future
+        included, inform its prediction.  `block` > 1 scores the next `block` rows jointly, each from its own observed inputs:
+        `block` one-step predictions, not a recursive `block`-step forecast (forecast() does those).
+
+        data="train": the training rows, which this object's chains have seen (n_fit = their count); origins min_train ..
+        N - block (min_train=None: N // 2), walked backward from the fit.  data="test": the training rows followed by the test
+        rows, n_fit = the training count, origins n_fit .. N - block walked forward: the sequential score of the test rows, row n
+        predicted by the posterior updated with the test rows before it -- what a deployed one-step forecaster does, and lppd
+        does not measure.  data=rows [N, >= n_in + 1] with n_fit= for anything else: the chains must have been fitted to
+        rows[:n_fit].  The sample set: burn_in, chains, thin, r_eff as in predictive_accuracy.
+
+        One device call scores every remaining origin from the current fit by Pareto-smoothed importance weights; the origins up
+        to the first (in walk order) whose k-hat exceeds k_threshold (default: good_k of the sample count) are kept.  refit=True:
+        a fresh sampler of this class and constructor arguments (no files, seed lfo_refit_seed(seed, origin): the result is
+        reproducible from `seed`) is fitted on rows [0, i), scores that origin exactly, and the walk goes on from it;
+        refit=callable(rows) -> a fitted ParallelTempering does the fit instead; refit=False never refits.  After max_refits
+        refits the remaining origins are returned with their high k-hat, and a warning says so.  -> LeaveFutureOut."""
+        self._need_sampler("leave_future_out")
+        I = int(self.topology[0])
+        if isinstance(data, str):
+            if data not in ("train", "test"):
+                raise ValueError(f"data must be 'train', 'test' or an array, not {data!r}")
+            if n_fit is not None:
+                raise ValueError("n_fit= goes with an array of rows: 'train' and 'test' fix it at the training count")
+            full = np.asarray(self.traindata) if data == "train" else np.vstack([np.asarray(self.traindata), np.asarray(self.testdata)])
+            n_fit = len(self.traindata)
+        else:
+            full = np.asarray(data)
+            if full.ndim != 2 or full.shape[1] < I + 1:
+                raise ValueError(f"data must be 2-D with at least n_in + 1 = {I + 1} columns (inputs, target), got shape {full.shape}")
+            if n_fit is None:
+                raise ValueError("an array of rows needs n_fit=: the chains have seen rows[:n_fit]")
+        rows = np.ascontiguousarray(full[:, :I + 1], dtype=np.float32)
+        block, n_fit = int(block), int(n_fit)
+        origins = lfo_origins(rows.shape[0], n_fit, block, min_train)
+        if refit is not True and refit is not False and not callable(refit):
+            raise ValueError("refit must be True, False or a callable(rows) -> a fitted ParallelTempering")
+        sel, n_s = self._trace_selection(burn_in, chains, thin)
+        if n_s < 2:
+            raise ValueError(f"the selection holds {n_s} samples: importance weights need at least 2")
+        if k_threshold is None:
+            k_threshold = good_k(n_s)
+
+        def score(pt, fit_rows, og):
+            kw, _ = pt._trace_selection(burn_in, chains, thin)
+            return pt._sampler.lfo(rows, n_fit=fit_rows, origins=og, block=block, r_eff=r_eff, **kw)
+
+        def fit(origin):
+            if refit is True:
+                return self._lfo_refit(full, origin)
+            pt = refit(full[:origin])
+            pt._need_sampler("leave_future_out (the refit)")
+            return pt
+
+        out = lfo_walk(origins, n_fit, self, score, fit if refit is not False else None, k_threshold=float(k_threshold),
+                       max_refits=max_refits)
+        high = ~(out["khat"] <= k_threshold) & ~out["exact"]
+        if np.any(high):
+            why = f"max_refits = {max_refits} was reached" if out["max_refits_hit"] else "refit=False"
+            warnings.warn(f"{int(np.count_nonzero(high))} of {high.size} origins have a Pareto k-hat above {k_threshold:.2f} "
+                          f"({why}): the PSIS-LFO estimate is unreliable for them", stacklevel=2)
+        return LeaveFutureOut(elpd_lfo=float(np.sum(out["elpd_lfo"])), se_elpd_lfo=_se_total(out["elpd_lfo"]), elpd_lfo_i=out["elpd_lfo"],
+                              khat=out["khat"], tail_len=out["tail_len"], origins=out["origins"], fit_origin=out["fit_origin"],
+                              exact=out["exact"], refit_origins=out["refit_origins"], n_refits=out["n_refits"],
+                              k_threshold=float(k_threshold), n_samples=n_s, block=block)
 
     # ------------------------------------------------------------------ calibration (not in the reference)
     def predictive_calibration(self, data="test", *, burn_in=None, chains="all", thin=1, weights=None, eta=None,
