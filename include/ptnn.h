@@ -633,6 +633,61 @@ typedef struct ptnn_calibration_spec {
 
 int ptnn_calibration(ptnn_handle *h, const ptnn_calibration_spec *spec);
 
+/* ---- input sensitivity (nothing in the reference: it reports no importance, sensitivity or saliency of its inputs) ----
+ * Which inputs the sampled nets respond to: the Jacobian of the network output with respect to the inputs, per sample and data
+ * row, reduced on the device.  With decode(w) = W1 [I,H], W2 [H,O], B1, B2, bias subtracted, sigmoid on both layers (REG:51-55):
+ *   z_h = sum_i x_i W1[i,h] - B1[h]    hid_h = sigmoid(z_h)    d_h  = hid_h (1 - hid_h)
+ *   a_o = sum_h hid_h W2[h,o] - B2[o]  s_o   = sigmoid(a_o)    ds_o = s_o (1 - s_o)
+ *   J[o,i] = ds_o sum_h W2[h,o] d_h W1[i,h]                    regression: g = J
+ *   classification (outputs p = softmax(s), CLS:108-110):      g[c,i] = p_c (J[c,i] - sum_o p_o J[o,i])
+ * g is fp32 (d and ds as e / (1 + e)^2 with e = exp(-|z|): no cancellation in a saturated unit); every sum after it is double;
+ * DESIGN.md section 19.  Sample set: selected as ptnn_predict selects it -- the handle's trace (same rules and error texts) or
+ * host vectors w [n_w, P] with optional multiplicities -- collapsed into distinct vectors as ptnn_predict collapses them; every
+ * output is over the expanded multiset of M samples.  Inputs: x_source / n_rows / x [n_rows, n_in] as ptnn_predict.
+ * Outputs, any may be NULL.  Per row n, output o, input i (index (n * n_out + o) * n_in + i): grad_mean [n_rows, n_out, n_in]
+ * (the weighted mean of g, accumulated in double); order_stats [n_ranks, n_rows, n_out, n_in] = the exact fp32 value of 0-based
+ * rank ranks[k] among the M values (ptnn_predict's rule, n_ranks <= 16); pos_count, neg_count [n_rows, n_out, n_in] = the samples
+ * with g > 0 and g < 0.  Per output o and input i, with a_s[o,i] = (1/n_rows) sum_n |g_s[n,o,i]| and q_s[o,i] = (1/n_rows)
+ * sum_n g_s[n,o,i]^2 of sample s (the row sums in double, in ascending row order): abs_mean, sq_mean [n_out, n_in] = the weighted
+ * means of a_s and q_s over the samples; abs_order_stats [n_ranks2, n_out, n_in] = the exact rank ranks2[k] of the fp32-rounded
+ * a_s among the M samples; sample_abs [M, n_out, n_in] = every selected row's a_s as fp32, chain-major; samples
+ * [M, n_rows, n_out, n_in] = every selected row's g, chain-major (ptnn_predict's samples layout); n_samples = M, n_distinct.
+ * Refused: n_rows < 1, an empty selection, a rank outside [0, M), n_rows x n_out x n_in > 2^31 - 1 columns, order statistics
+ * requested without ranks.  Runs on the handle's stream behind everything queued and returns when done; rows are processed in
+ * blocks whose scratch (4 U n_out n_in bytes per row) stays under $PTNN_SENSITIVITY_SCRATCH_BYTES (read per call, default 1 GiB)
+ * and of at most 65535 x 64 rows, which changes no result.  Touches no chain state, tape, counter or trace row.  Not with a
+ * communicator attached (one GPU only). */
+typedef struct ptnn_sensitivity_spec {
+    int32_t struct_bytes;         /* = sizeof(ptnn_sensitivity_spec): ABI guard */
+    /* source 1: the trace (used when w == NULL) */
+    const int32_t *replicas;      /* local replica indices, or NULL = all */
+    int32_t n_replicas;           /* entries of replicas (ignored when NULL) */
+    int32_t step0, nsteps, thin;  /* trace rows step0, step0 + thin, ... < step0 + nsteps (thin >= 1) */
+    /* source 2: host vectors */
+    const float *w;               /* [n_w, P] or NULL */
+    const int32_t *multiplicity;  /* [n_w] >= 0, or NULL = 1 each */
+    int64_t n_w;
+    /* inputs */
+    int32_t x_source;             /* PTNN_PREDICT_X_HOST | _TRAIN | _TEST */
+    int32_t n_rows;
+    const float *x;               /* [n_rows, n_in] (host rows only) */
+    /* order statistics: of g per (row, output, input), and of a_s per (output, input) */
+    const int64_t *ranks;         /* [n_ranks] */
+    const int64_t *ranks2;        /* [n_ranks2] */
+    int32_t n_ranks, n_ranks2;    /* each <= PTNN_PREDICT_MAX_RANKS */
+    /* outputs */
+    double *grad_mean;
+    float *order_stats;
+    int64_t *pos_count, *neg_count;
+    double *abs_mean, *sq_mean;
+    float *abs_order_stats;
+    float *sample_abs;
+    float *samples;
+    int64_t *n_samples, *n_distinct;
+} ptnn_sensitivity_spec;
+
+int ptnn_sensitivity(ptnn_handle *h, const ptnn_sensitivity_spec *spec);
+
 /* the HIP stream (hipStream_t) all of this handle's work is queued on: lets the caller order its collectives after the
  * segment / before the swap kernels on the device instead of synchronising the host */
 int ptnn_stream(ptnn_handle *h, void **hip_stream);

@@ -148,6 +148,22 @@ CALIB_MAX_LEVELS = 16
 CALIB_MAX_DISTINCT = 65536
 
 
+class SensitivitySpec(C.Structure):
+    """ptnn_sensitivity_spec (include/ptnn.h)."""
+    _fields_ = [
+        ("struct_bytes", C.c_int32),
+        ("replicas", C.POINTER(C.c_int32)), ("n_replicas", C.c_int32), ("step0", C.c_int32), ("nsteps", C.c_int32), ("thin", C.c_int32),
+        ("w", C.POINTER(C.c_float)), ("multiplicity", C.POINTER(C.c_int32)), ("n_w", C.c_int64),
+        ("x_source", C.c_int32), ("n_rows", C.c_int32), ("x", C.POINTER(C.c_float)),
+        ("ranks", C.POINTER(C.c_int64)), ("ranks2", C.POINTER(C.c_int64)), ("n_ranks", C.c_int32), ("n_ranks2", C.c_int32),
+        ("grad_mean", C.POINTER(C.c_double)), ("order_stats", C.POINTER(C.c_float)),
+        ("pos_count", C.POINTER(C.c_int64)), ("neg_count", C.POINTER(C.c_int64)),
+        ("abs_mean", C.POINTER(C.c_double)), ("sq_mean", C.POINTER(C.c_double)), ("abs_order_stats", C.POINTER(C.c_float)),
+        ("sample_abs", C.POINTER(C.c_float)), ("samples", C.POINTER(C.c_float)),
+        ("n_samples", C.POINTER(C.c_int64)), ("n_distinct", C.POINTER(C.c_int64)),
+    ]
+
+
 class LadderAdaptSpec(C.Structure):
     """ptnn_ladder_adapt_spec (include/ptnn.h)."""
     _fields_ = [("struct_bytes", C.c_int32), ("rounds", C.c_int32), ("kappa0", C.c_double), ("t0", C.c_double)]
@@ -240,6 +256,7 @@ SYMBOLS = {
     "ptnn_forecast": (C.c_int, [C.c_void_p, C.POINTER(ForecastSpec)]),
     "ptnn_evidence": (C.c_int, [C.c_void_p, C.POINTER(EvidenceSpec)]),
     "ptnn_calibration": (C.c_int, [C.c_void_p, C.POINTER(CalibrationSpec)]),
+    "ptnn_sensitivity": (C.c_int, [C.c_void_p, C.POINTER(SensitivitySpec)]),
 }
 
 
@@ -857,6 +874,47 @@ class Sampler:
         ns, nd = C.c_int64(0), C.c_int64(0)
         spec.n_samples, spec.n_distinct = C.pointer(ns), C.pointer(nd)
         self._check(self.lib.ptnn_calibration(self.h, C.byref(spec)))
+        out["n_samples"], out["n_distinct"] = ns.value, nd.value
+        return out
+
+    def sensitivity(self, x="test", *, replicas=None, step0=0, nsteps=None, thin=1, w=None, multiplicity=None, ranks=(), ranks2=(),
+                    sample_abs=False, samples=False):
+        """ptnn_sensitivity: the gradient g of the network outputs with respect to the inputs, for the selected weight vectors on
+        input rows, reduced on the device.  Source and x as predict().  -> dict(grad_mean [n_rows, O, I] float64, order_stats
+        [len(ranks), n_rows, O, I] float32 (exact values of those 0-based ranks of g), pos_count, neg_count [n_rows, O, I] int64
+        (samples with g > 0, g < 0), abs_mean, sq_mean [O, I] float64 (means over samples of the row means of |g| and g^2),
+        abs_order_stats [len(ranks2), O, I] float32 (exact ranks of the per-sample row mean of |g|), sample_abs [M, O, I] float32,
+        samples [M, n_rows, O, I] float32, n_samples, n_distinct); what was not asked for is None."""
+        spec = SensitivitySpec()
+        spec.struct_bytes = C.sizeof(SensitivitySpec)
+        keep = []
+        self._rows(spec, keep, x, "x", (self.cfg.n_in, "n_in columns"))
+        n_rows, O, I = spec.n_rows, self.cfg.n_out, self.cfg.n_in
+        if w is not None:
+            n = self._host_vectors(spec, keep, w)
+            M = self._multiplicity(spec, keep, multiplicity, (n,), "multiplicity must have one entry per vector")
+        else:
+            M = math.prod(self._trace_source(spec, keep, replicas, step0, nsteps, thin))
+        i64p = C.POINTER(C.c_int64)
+        rk = np.ascontiguousarray(ranks, dtype=np.int64).reshape(-1)
+        rk2 = np.ascontiguousarray(ranks2, dtype=np.int64).reshape(-1)
+        keep += [rk, rk2]
+        spec.ranks, spec.n_ranks = (_ptr(rk, i64p) if rk.size else None), rk.size
+        spec.ranks2, spec.n_ranks2 = (_ptr(rk2, i64p) if rk2.size else None), rk2.size
+        out = dict(grad_mean=np.empty((n_rows, O, I), np.float64),
+                   order_stats=np.empty((rk.size, n_rows, O, I), np.float32) if rk.size else None,
+                   pos_count=np.empty((n_rows, O, I), np.int64), neg_count=np.empty((n_rows, O, I), np.int64),
+                   abs_mean=np.empty((O, I), np.float64), sq_mean=np.empty((O, I), np.float64),
+                   abs_order_stats=np.empty((rk2.size, O, I), np.float32) if rk2.size else None,
+                   sample_abs=np.empty((max(M, 0), O, I), np.float32) if sample_abs else None,
+                   samples=np.empty((max(M, 0), n_rows, O, I), np.float32) if samples else None)
+        types = dict(grad_mean=C.POINTER(C.c_double), abs_mean=C.POINTER(C.c_double), sq_mean=C.POINTER(C.c_double),
+                     pos_count=i64p, neg_count=i64p)
+        for k, v in out.items():
+            setattr(spec, k, _ptr(v, types.get(k, _fp)))
+        ns, nd = C.c_int64(0), C.c_int64(0)
+        spec.n_samples, spec.n_distinct = C.pointer(ns), C.pointer(nd)
+        self._check(self.lib.ptnn_sensitivity(self.h, C.byref(spec)))
         out["n_samples"], out["n_distinct"] = ns.value, nd.value
         return out
 

@@ -1,4 +1,4 @@
-// ptnn_analysis.hip -- the posterior analysis calls of libptnn.so: predict, convergence, elpd, lfo, forecast, evidence, calibration,
+// ptnn_analysis.hip -- the posterior analysis calls of libptnn.so: predict, convergence, elpd, lfo, forecast, evidence, calibration, sensitivity,
 // and the sample-selection path they share.  The shape-independent analysis kernels are defined in this object: it includes them.
 #include "ptnn_shapes.hpp"
 namespace ptnn {
@@ -8,6 +8,8 @@ namespace ptnn {
 #include "ptnn_dev_lfo.hpp"                  // leave-future-out cross-validation: running sums of ll, PSIS per origin
 #include "ptnn_dev_evidence.hpp"             // log evidence: per-rung statistics of the full-data log-likelihood, prior draws
 #include "ptnn_dev_calibration.hpp"          // calibration: PIT, quantiles and CRPS of the predictive mixture per data row
+#define PTNN_SENSITIVITY_REDUCTIONS
+#include "ptnn_dev_sensitivity.hpp"          // input sensitivity, second part: sign counts, row sums and their weighted means
 }  // namespace ptnn
 #include "ptnn_host.hpp"
 
@@ -303,6 +305,30 @@ long long row_block(size_t budget, size_t row_bytes, long long n_rows) {
     return std::max(1LL, std::min<long long>({(long long)(budget / row_bytes), 65535LL * WAVE, n_rows}));
 }
 
+// Stage b of sensitivity: the per-shape sens_fwd, NV distinct vectors staged in LDS per work-group beside their finished 64-row
+// gradient tiles (n_out * n_in * 64 floats each): as many vectors as 64 KiB hold, so that two work-groups share a CU
+struct SensPlan {
+    int PV = 0, NV = 0, VS = 0;
+    size_t lds = 0;
+    int init(const ptnn_handle* h) {
+        const int P = h->P, OI = h->cfg.n_out * h->cfg.n_in;
+        PV = round_up4(P);
+        NV = std::max(1, std::min(SENS_MAX_NV, (64 * 1024 / 4) / (PV + (OI + 1) * WAVE)));
+        VS = OI * WAVE + std::max(1, WAVE / NV);        // the pad: the vectors of one column land in different LDS banks
+        lds = (size_t)NV * (PV + VS) * sizeof(float);
+        if (lds > LDS_CEILING) return fail(-3, "input sensitivity: a %d-parameter vector does not fit in LDS", P);
+        return raise_lds_limit(reinterpret_cast<const void*>(h->shape->sens_fwd), lds);
+    }
+    // gx [nr * O * I][U] = the input gradients of vectors base + run_off[u] on rows [r0, r0 + nr) of x
+    int launch(const ptnn_handle* h, const float* base, const long long* run_off, const float* x, int xs, int r0, int nr, int U, float* gx) const {
+        SensFwd fa{base, run_off, x, xs, r0, nr, h->cfg.n_hidden, h->P, PV, U, NV, VS, gx};
+        hipLaunchKernelGGL(h->shape->sens_fwd, dim3((unsigned)((U + NV - 1) / NV), (unsigned)((nr + WAVE - 1) / WAVE)), dim3(SENS_THREADS), lds,
+                           h->stream, fa);
+        HIP_TRY(hipGetLastError());
+        return 0;
+    }
+};
+
 // the order statistics of predict and forecast: ranks [n_ranks] in the expanded multiset of M samples
 int check_ranks(int n_ranks, const int64_t* ranks, const void* order_stats) {
     if (n_ranks < 0 || n_ranks > PTNN_PREDICT_MAX_RANKS) return fail(-1, "n_ranks = %d outside [0, %d]", n_ranks, PTNN_PREDICT_MAX_RANKS);
@@ -385,6 +411,112 @@ int ptnn_predict(ptnn_handle* h, const ptnn_predict_spec* spec) {
     if (s.vote)
         for (int c = 0; c < ncols; ++c) s.vote[c] = (double)votes_h[(size_t)c] / (double)M;
     return 0;
+}
+
+// ---- input sensitivity (ptnn_dev_sensitivity.hpp) ----
+int ptnn_sensitivity(ptnn_handle* h, const ptnn_sensitivity_spec* spec) {
+    // argument checks first: none of them needs the handle or a device
+    if (int rc = check_spec(spec, "ptnn_sensitivity_spec")) return rc;
+    const ptnn_sensitivity_spec& s = *spec;
+    SampleSource src = source_of(s, s.w != nullptr, nullptr);
+    const RowSource rows{s.x_source, s.x, s.n_rows, "x_source", "PTNN_PREDICT_X", "x", "n_rows"};
+    if (int rc = check_source(src, "vectors")) return rc;
+    if (int rc = check_rows(rows)) return rc;
+    if (s.n_rows < 1) return fail(-1, "n_rows = %d must be >= 1", s.n_rows);
+    if (int rc = check_ranks(s.n_ranks, s.ranks, s.order_stats)) return rc;
+    if (int rc = check_ranks(s.n_ranks2, s.ranks2, s.abs_order_stats)) return rc;
+    if (int rc = check_handle(h, "ptnn_sensitivity")) return rc;
+    const int I = h->cfg.n_in, O = h->cfg.n_out, OI = O * I;
+    if (int rc = fit_rows(h, rows)) return rc;
+    const long long ncols_all = (long long)s.n_rows * OI;
+    if (ncols_all > 0x7fffffffLL)
+        return fail(-1, "%d rows x %d outputs x %d inputs = %lld columns: at most 2^31 - 1 per call", s.n_rows, O, I, ncols_all);
+    const int ncols = (int)ncols_all;
+    if (int rc = count_samples(h, src)) return rc;
+    const long long M = src.M;
+    if (M < 1) return fail(-1, "the selection holds no sample");
+    if (int rc = sample_limit(src)) return rc;
+    if (int rc = check_rank_values(s.n_ranks, s.ranks, M)) return rc;
+    if (int rc = check_rank_values(s.n_ranks2, s.ranks2, M)) return rc;
+    if (s.n_samples) *s.n_samples = M;
+
+    if (int rc = start_device(h)) return rc;
+    hipStream_t st = h->stream;
+    DeviceScratch mem;
+    const float* d_x = nullptr;
+    int xs = 0;
+    if (int rc = upload_rows(h, mem, rows, I, &d_x, &xs)) return rc;
+    Distinct d;
+    if (int rc = distinct_samples(h, mem, src, false, true, &d)) return rc;
+    const int U = d.U;
+    if (s.n_distinct) *s.n_distinct = U;
+    // outputs on the device for every column; the sign counts as integers (exact whatever the order)
+    double *d_mean = nullptr, *d_acc_abs = nullptr, *d_acc_sq = nullptr, *d_abs_mean = nullptr, *d_sq_mean = nullptr, *d_a32_mean = nullptr;
+    float *d_ostat = nullptr, *d_a32 = nullptr, *d_aostat = nullptr;
+    long long *d_pos = nullptr, *d_neg = nullptr, *d_ranks = nullptr, *d_ranks2 = nullptr;
+    HIP_TRY(mem.alloc(&d_mean, (size_t)ncols));
+    HIP_TRY(mem.alloc(&d_pos, (size_t)ncols));
+    HIP_TRY(mem.alloc(&d_neg, (size_t)ncols));
+    if (s.n_ranks) {
+        HIP_TRY(mem.alloc(&d_ostat, (size_t)s.n_ranks * ncols));
+        HIP_TRY(mem.upload(&d_ranks, (const long long*)s.ranks, (size_t)s.n_ranks, st));
+    }
+    if (s.n_ranks2) {
+        HIP_TRY(mem.alloc(&d_aostat, (size_t)s.n_ranks2 * OI));
+        HIP_TRY(mem.upload(&d_ranks2, (const long long*)s.ranks2, (size_t)s.n_ranks2, st));
+    }
+    // per (o, i) and distinct vector: the row sums of |g| and g^2, carried across the blocks of rows
+    HIP_TRY(mem.alloc(&d_acc_abs, (size_t)OI * U));
+    HIP_TRY(mem.alloc(&d_acc_sq, (size_t)OI * U));
+    HIP_TRY(mem.alloc(&d_a32, (size_t)OI * U));
+    HIP_TRY(mem.alloc(&d_abs_mean, (size_t)OI));
+    HIP_TRY(mem.alloc(&d_sq_mean, (size_t)OI));
+    HIP_TRY(mem.alloc(&d_a32_mean, (size_t)OI));
+    HIP_TRY(hipMemsetAsync(d_acc_abs, 0, (size_t)OI * U * sizeof(double), st));
+    HIP_TRY(hipMemsetAsync(d_acc_sq, 0, (size_t)OI * U * sizeof(double), st));
+    // the forward pass, the column reductions and the row sums in blocks of rows: gx scratch U x (rows x O x I) floats under the budget
+    const long long rows_blk = row_block(scratch_budget("PTNN_SENSITIVITY_SCRATCH_BYTES"), (size_t)U * sizeof(float) * OI, s.n_rows);
+    float* d_gx = nullptr;
+    HIP_TRY(mem.alloc(&d_gx, (size_t)rows_blk * OI * U));
+    SensPlan fwd;
+    if (int rc = fwd.init(h)) return rc;
+    std::vector<int> item_run;
+    if (s.samples || s.sample_abs) if (int rc = item_runs(h, d, src.n_items, &item_run)) return rc;
+    const dim3 rows_grid((unsigned)((U + PRED_THREADS - 1) / PRED_THREADS), (unsigned)OI);
+    for (long long r0 = 0; r0 < s.n_rows; r0 += rows_blk) {
+        const int nr = (int)std::min<long long>(rows_blk, s.n_rows - r0);
+        if (int rc = fwd.launch(h, d.base, d.run_off, d_x, xs, (int)r0, nr, U, d_gx)) return rc;
+        PredictRed ra{d_gx, d.run_cnt, U, 1, (int)(r0 * OI), ncols, M, s.n_ranks, d_ranks, d_mean, d_ostat, nullptr};
+        hipLaunchKernelGGL(predict_reduce_kernel, dim3((unsigned)(nr * OI)), dim3(PRED_THREADS), 0, st, ra);
+        HIP_TRY(hipGetLastError());
+        SensSign sa{d_gx, d.run_cnt, U, r0 * OI, d_pos, d_neg};
+        hipLaunchKernelGGL(sensitivity_sign_kernel, dim3((unsigned)(nr * OI)), dim3(PRED_THREADS), 0, st, sa);
+        HIP_TRY(hipGetLastError());
+        SensRows rw{d_gx, U, OI, nr, r0 + nr == s.n_rows ? 1 : 0, (double)s.n_rows, d_acc_abs, d_acc_sq, d_a32};
+        hipLaunchKernelGGL(sensitivity_rows_kernel, rows_grid, dim3(PRED_THREADS), 0, st, rw);
+        HIP_TRY(hipGetLastError());
+        if (s.samples)
+            if (int rc = scatter_samples(h, d_gx, nr * OI, U, item_run, src.weights(), s.samples, (size_t)ncols, (size_t)r0 * OI)) return rc;
+    }
+    // the global relevance: weighted means of the row sums (double), exact ranks of the fp32 a_s
+    SensMean ma{d_acc_abs, d_acc_sq, d.run_cnt, U, (double)s.n_rows, M, d_abs_mean, d_sq_mean};
+    hipLaunchKernelGGL(sensitivity_mean_kernel, dim3((unsigned)OI), dim3(PRED_THREADS), 0, st, ma);
+    HIP_TRY(hipGetLastError());
+    if (s.n_ranks2) {
+        PredictRed ra{d_a32, d.run_cnt, U, 1, 0, OI, M, s.n_ranks2, d_ranks2, d_a32_mean, d_aostat, nullptr};
+        hipLaunchKernelGGL(predict_reduce_kernel, dim3((unsigned)OI), dim3(PRED_THREADS), 0, st, ra);
+        HIP_TRY(hipGetLastError());
+    }
+    if (s.sample_abs)
+        if (int rc = scatter_samples(h, d_a32, OI, U, item_run, src.weights(), s.sample_abs, (size_t)OI, 0)) return rc;
+    HIP_TRY(fetch(s.grad_mean, d_mean, (size_t)ncols, st));
+    HIP_TRY(fetch(s.order_stats, d_ostat, (size_t)s.n_ranks * ncols, st));
+    HIP_TRY(fetch((long long*)s.pos_count, d_pos, (size_t)ncols, st));
+    HIP_TRY(fetch((long long*)s.neg_count, d_neg, (size_t)ncols, st));
+    HIP_TRY(fetch(s.abs_mean, d_abs_mean, (size_t)OI, st));
+    HIP_TRY(fetch(s.sq_mean, d_sq_mean, (size_t)OI, st));
+    HIP_TRY(fetch(s.abs_order_stats, d_aostat, (size_t)s.n_ranks2 * OI, st));
+    return wait_stream(h);
 }
 
 // ---- convergence diagnostics (ptnn_dev_convergence.hpp) ----

@@ -1,0 +1,247 @@
+// ptnn_dev_sensitivity.hpp -- part of ptnn_device.hpp (textually included there, inside namespace ptnn; not a stand-alone header):
+// input sensitivity of the sampled nets (ptnn_sensitivity, include/ptnn.h) -- the Jacobian of the network
+// output with respect to the inputs, per distinct weight vector and data row.  Nothing of the kind is in the reference.
+//
+//   z_h = sum_i x_i W1[i,h] - B1[h]     hid_h = sigmoid(z_h)     d_h  = hid_h (1 - hid_h)
+//   a_o = sum_h hid_h W2[h,o] - B2[o]   s_o   = sigmoid(a_o)     ds_o = s_o (1 - s_o)
+//   J[o,i] = ds_o sum_h W2[h,o] d_h W1[i,h]                      regression: g = J
+//   classification (p = softmax(s), CLS:108-110):                g[c,i] = p_c (J[c,i] - sum_o p_o J[o,i])
+//
+// The three stages of ptnn_dev_predict.hpp, with another stage b:
+//   b. sensitivity_forward_kernel<TASK, I, O> (per shape, Shape::sens_fwd): gx[col][u] = g of distinct vector u, column
+//      col = (row * O + o) * I + i of a block of input rows -- the layout of PredictFwd::fx, so stage c (predict_reduce_kernel) takes
+//      the gradient columns as it takes the outputs.
+//   then per block of rows sensitivity_sign_kernel (the weighted counts of g > 0 and g < 0 per column) and
+//   sensitivity_rows_kernel (|g| and g^2 summed over the rows, per vector and (o, i), in double, carried across the blocks), and
+//   at the end sensitivity_mean_kernel (the weighted means of those sums over the vectors).
+// Nothing here writes chain state, tapes, counters or trace rows.
+//
+// The file has two parts.  ptnn_device.hpp includes the first: the constants, SensFwd and the per-shape kernel, which the shape
+// translation units instantiate.  ptnn_analysis.hip includes the file again with PTNN_SENSITIVITY_REDUCTIONS defined and gets the
+// second: the shape-independent kernels, which that object holds.
+#ifndef PTNN_SENSITIVITY_REDUCTIONS
+
+constexpr int SENS_THREADS = 256;        // 4 waves
+constexpr int SENS_MAX_NV = 16;          // distinct vectors per forward work-group
+constexpr int SENS_ACC = 40;             // gradient accumulators a lane holds in one pass over the hidden units
+
+// The inputs are tiled: one pass over the hidden units carries S[o][i] for all O outputs and a chunk of IT inputs, at most SENS_ACC
+// accumulators (pendigit's 16 x 10 = 160 at once would leave a SIMD one wave).  NT passes, balanced: 34 x 2 -> 2 x 17,
+// 16 x 10 -> 4 x 4, 11 x 10 -> 4 + 4 + 3, 6 x 18 -> 3 x 2; every other compiled shape takes one pass.
+template <int I, int O> struct SensTile {
+    static constexpr int FIT = SENS_ACC / O < 1 ? 1 : (SENS_ACC / O < I ? SENS_ACC / O : I);
+    static constexpr int NT = (I + FIT - 1) / FIT;
+    static constexpr int IT = (I + NT - 1) / NT;
+};
+
+// what the forward kernel needs (the host fills it; ptnn_analysis.hip: ptnn_sensitivity)
+struct SensFwd {
+    const float* base;          // vectors: d_pos_w rows or the uploaded host vectors
+    const long long* run_off;   // [U] float offset of distinct vector u in base
+    const float* x;             // input rows, x_0 .. x_{I-1} at x + row * xs
+    int xs;                     // row stride of x (floats)
+    int row0, nrows;            // rows [row0, row0 + nrows) of x form this block of columns
+    int H, P, PV;               // hidden units, parameters, LDS stride of a staged vector (P rounded up to 4)
+    int U, NV;                  // distinct vectors, vectors staged per work-group
+    int VS;                     // LDS stride of a vector's finished tile: O * I * 64 + a pad that spreads the vectors over the banks
+    float* gx;                  // [nrows * O * I][U] column-major
+};
+
+// sigmoid(z) and its derivative without the cancellation 1 - sigmoid(z) of a saturated unit: e = exp(-|z|) <= 1,
+// sigmoid = (z >= 0 ? 1 : e) / (1 + e), derivative = e / (1 + e)^2 -- a few ulp at any saturation
+__device__ __forceinline__ void sigmoid_and_slope(float z, float* s, float* d) {
+    const float e = expf(-fabsf(z)), q = 1.0f + e;
+    *s = (z >= 0.0f ? 1.0f : e) / q;
+    *d = e / (q * q);
+}
+
+// One lane per input row with the row's inputs in registers, NV vectors staged in LDS, every weight read wave-uniform (an LDS
+// broadcast), as in predict_forward_kernel.  The work of a group is the nv x NT (vector, input tile) pairs; wave w takes the pairs
+// w, w + 4, ...  A pair is one pass over ALL hidden units in ascending order -- z_h and a_o are recomputed per tile, the sums are
+// never split across waves -- so a value does not depend on NV, on the block of rows or on which wave computed it.
+template <int TASK, int I, int O>
+__global__ void __launch_bounds__(SENS_THREADS) sensitivity_forward_kernel(const SensFwd a) {
+    extern __shared__ __attribute__((aligned(16))) float smem[];
+    constexpr int IT = SensTile<I, O>::IT, NT = SensTile<I, O>::NT, NWAVE = SENS_THREADS / WAVE, OI = O * I;
+    const int tid = threadIdx.x, lane = tid & (WAVE - 1);
+    const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+    const int NV = a.NV, PV = a.PV, H = a.H, VS = a.VS;
+    const int u0 = blockIdx.x * NV;
+    const int nv = min(NV, a.U - u0);
+    const int r0 = blockIdx.y * WAVE;
+    float* sv = smem;                                   // [NV][PV] the staged vectors
+    float* fin = sv + (size_t)NV * PV;                  // [NV][VS] finished gradients: fin[v * VS + (o * I + i) * 64 + lane]
+    for (int v = 0; v < nv; ++v) {
+        const float* src = a.base + a.run_off[u0 + v];
+        for (int k = tid; k < a.P; k += SENS_THREADS) sv[v * PV + k] = src[k];
+    }
+    // a lane past the last row computes row 0 and stores nothing
+    const int row = r0 + lane;
+    const bool live = row < a.nrows;
+    const float* xr = a.x + (size_t)(a.row0 + (live ? row : 0)) * a.xs;
+    float x[I];
+#pragma unroll
+    for (int i = 0; i < I; ++i) x[i] = xr[i];
+    __syncthreads();
+    for (int p = wave; p < nv * NT; p += NWAVE) {
+        const int v = p / NT, i0 = (p % NT) * IT;      // wave-uniform
+        const float* W1 = sv + v * PV;                  // [I][H]  (decode: w = W1, W2, B1, B2)
+        const float* W2 = W1 + I * H;                   // [H][O]
+        const float* B1 = W2 + H * O;
+        const float* B2 = B1 + H;
+        int w1row[IT];                                  // W1 rows of this tile; past the last input (11 = 4 + 4 + 3): the last row again, not stored
+#pragma unroll
+        for (int k = 0; k < IT; ++k) w1row[k] = min(i0 + k, I - 1) * H;
+        float S[O][IT], acc[O];
+#pragma unroll
+        for (int o = 0; o < O; ++o) {
+            acc[o] = 0.0f;
+#pragma unroll
+            for (int k = 0; k < IT; ++k) S[o][k] = 0.0f;
+        }
+        for (int h = 0; h < H; ++h) {
+            float z = 0.0f;
+#pragma unroll
+            for (int i = 0; i < I; ++i) z = fmaf(x[i], W1[i * H + h], z);
+            float hid, d;
+            sigmoid_and_slope(z - B1[h], &hid, &d);                       // bias subtracted (Q1)
+            float dw[IT];
+#pragma unroll
+            for (int k = 0; k < IT; ++k) dw[k] = d * W1[w1row[k] + h];
+#pragma unroll
+            for (int o = 0; o < O; ++o) {
+                const float w2 = W2[h * O + o];
+                acc[o] = fmaf(hid, w2, acc[o]);
+#pragma unroll
+                for (int k = 0; k < IT; ++k) S[o][k] = fmaf(w2, dw[k], S[o][k]);
+            }
+        }
+        // the output sigmoid (Q2) and its slope; classification: p = softmax(s) (CLS:108-110)
+        float ds[O], pc[O];
+#pragma unroll
+        for (int o = 0; o < O; ++o) sigmoid_and_slope(acc[o] - B2[o], &pc[o], &ds[o]);
+        if (TASK == TASK_CLS) {
+            float sum = 0.0f;
+#pragma unroll
+            for (int o = 0; o < O; ++o) { pc[o] = expf(pc[o]); sum += pc[o]; }
+#pragma unroll
+            for (int o = 0; o < O; ++o) pc[o] = pc[o] / sum;
+        }
+        float* out = fin + (size_t)v * VS + lane;
+#pragma unroll
+        for (int k = 0; k < IT; ++k) {
+            float J[O], m = 0.0f;
+#pragma unroll
+            for (int o = 0; o < O; ++o) {
+                J[o] = ds[o] * S[o][k];
+                m = fmaf(pc[o], J[o], m);
+            }
+            if (i0 + k < I) {
+#pragma unroll
+                for (int o = 0; o < O; ++o) out[(o * I + i0 + k) * WAVE] = TASK == TASK_CLS ? pc[o] * (J[o] - m) : J[o];
+            }
+        }
+    }
+    __syncthreads();
+    // column-major store: column (r0 + l) * O * I + oi of the block gets NV consecutive floats
+    for (int idx = tid; idx < OI * WAVE * NV; idx += SENS_THREADS) {
+        const int v = idx % NV, c = idx / NV, l = c % WAVE, oi = c / WAVE;
+        if (v < nv && r0 + l < a.nrows) a.gx[((size_t)(r0 + l) * OI + oi) * a.U + u0 + v] = fin[(size_t)v * VS + oi * WAVE + l];
+    }
+}
+
+#else  // PTNN_SENSITIVITY_REDUCTIONS: the shape-independent kernels (ptnn_analysis.hip, after ptnn_dev_select.hpp)
+
+// per column of a block: the samples, multiplicities counted, whose gradient is > 0 and < 0.  Integer counts: exact in any order.
+struct SensSign {
+    const float* gx;            // [ncols][U]
+    const int* cnt;             // [U]
+    int U;
+    long long col0;             // global index of the block's first column
+    long long* pos;             // [ncols_total]
+    long long* neg;
+};
+
+__global__ void __launch_bounds__(PRED_THREADS) sensitivity_sign_kernel(const SensSign r) {
+    __shared__ long long psum[PRED_THREADS], nsum[PRED_THREADS];
+    const int tid = threadIdx.x, col = blockIdx.x;
+    const float* f = r.gx + (size_t)col * r.U;
+    long long p = 0, n = 0;
+    for (int u = tid; u < r.U; u += PRED_THREADS) {
+        const float g = f[u];
+        const int c = r.cnt[u];
+        if (g > 0.0f) p += c;
+        if (g < 0.0f) n += c;
+    }
+    psum[tid] = p;
+    nsum[tid] = n;
+    __syncthreads();
+    for (int d = PRED_THREADS / 2; d > 0; d >>= 1) {
+        if (tid < d) { psum[tid] += psum[tid + d]; nsum[tid] += nsum[tid + d]; }
+        __syncthreads();
+    }
+    if (tid == 0) { r.pos[r.col0 + col] = psum[0]; r.neg[r.col0 + col] = nsum[0]; }
+}
+
+// per distinct vector u and (o, i): |g| and g^2 summed over the rows of a block in ascending order, in double, onto what the
+// earlier blocks left -- the sum over all rows is the same whatever the block size.  One thread per (u, oi), reads coalesced
+// along u.  After the last block: a_s = the mean of |g| over the n_total rows as fp32, for the rank pass.
+struct SensRows {
+    const float* gx;            // [nrows * OI][U]
+    int U, OI, nrows, last;
+    double n_total;
+    double* acc_abs;            // [OI][U], zeroed by the caller before the first block
+    double* acc_sq;
+    float* a32;                 // [OI][U]
+};
+
+__global__ void __launch_bounds__(PRED_THREADS) sensitivity_rows_kernel(const SensRows r) {
+    const int u = blockIdx.x * PRED_THREADS + threadIdx.x, oi = blockIdx.y;
+    if (u >= r.U) return;
+    const size_t k = (size_t)oi * r.U + u;
+    double sa = r.acc_abs[k], sq = r.acc_sq[k];
+    const float* g = r.gx + k;
+    const size_t stride = (size_t)r.OI * r.U;
+    for (int n = 0; n < r.nrows; ++n) {
+        const double v = (double)g[n * stride];
+        sa += fabs(v);
+        sq += v * v;
+    }
+    r.acc_abs[k] = sa;
+    r.acc_sq[k] = sq;
+    if (r.last) r.a32[k] = (float)(sa / r.n_total);
+}
+
+// per (o, i), one work-group: the weighted means over the distinct vectors of a_s and q_s (the row sums / n_total), in double, a
+// fixed summation order for a given U
+struct SensMean {
+    const double* acc_abs;      // [OI][U]
+    const double* acc_sq;
+    const int* cnt;             // [U]
+    int U;
+    double n_total;
+    long long M;
+    double* abs_mean;           // [OI]
+    double* sq_mean;
+};
+
+__global__ void __launch_bounds__(PRED_THREADS) sensitivity_mean_kernel(const SensMean r) {
+    __shared__ double asum[PRED_THREADS], qsum[PRED_THREADS];
+    const int tid = threadIdx.x, oi = blockIdx.x;
+    double sa = 0.0, sq = 0.0;
+    for (int u = tid; u < r.U; u += PRED_THREADS) {
+        const double c = (double)r.cnt[u];
+        sa += c * (r.acc_abs[(size_t)oi * r.U + u] / r.n_total);
+        sq += c * (r.acc_sq[(size_t)oi * r.U + u] / r.n_total);
+    }
+    asum[tid] = sa;
+    qsum[tid] = sq;
+    __syncthreads();
+    for (int d = PRED_THREADS / 2; d > 0; d >>= 1) {
+        if (tid < d) { asum[tid] += asum[tid + d]; qsum[tid] += qsum[tid + d]; }
+        __syncthreads();
+    }
+    if (tid == 0) { r.abs_mean[oi] = asum[0] / (double)r.M; r.sq_mean[oi] = qsum[0] / (double)r.M; }
+}
+
+#endif

@@ -17,4 +17,5 @@ extern "C" const Shape PTNN_SHAPE_SYMBOL = {PTNN_T, PTNN_I, PTNN_O,
                                             SplitK<PTNN_I>::OK ? SplitK<PTNN_I>::CH : 0, SplitK<PTNN_I>::KR,
                                             &segment_packm_kernel<PTNN_T, PTNN_I, PTNN_O>,
                                             &predict_forward_kernel<PTNN_T, PTNN_I, PTNN_O>,
-                                            &forecast_forward_kernel<PTNN_T, PTNN_I, PTNN_O>};
+                                            &forecast_forward_kernel<PTNN_T, PTNN_I, PTNN_O>,
+                                            &sensitivity_forward_kernel<PTNN_T, PTNN_I, PTNN_O>};

@@ -31,5 +31,6 @@ struct Shape {
     seg_fn packm;           // 9 <= H <= 16: packed schedule over several CUs per replica
     void (*predict_fwd)(const PredictFwd);   // posterior predictive: network outputs of distinct vectors x input rows (every H)
     void (*forecast_fwd)(const ForecastFwd); // recursive forecasts: trajectories x origins x horizon steps (REG, n_out == 1; else empty)
+    void (*sens_fwd)(const SensFwd);         // input sensitivity: d output / d input of distinct vectors x input rows (every H)
 };
 }  // namespace ptnn

@@ -154,6 +154,28 @@ def lerp_percentile(a, b, gamma):
 Predictive = namedtuple("Predictive", "mean percentiles vote pred_class samples n_samples n_distinct")
 
 
+# input_sensitivity's result, g = d output / d input: grad_mean, percentiles {p: ...}, prob_positive, prob_negative [n_rows, n_out,
+# n_in] float64; importance (mean over samples and rows of |g|), importance_rms, importance_percentiles {p: ...}, top_prob (the share
+# of the samples in which the input is the output's most important one) [n_out, n_in] float64; samples [n_samples, n_rows, n_out,
+# n_in] float32 or None; n_samples; n_distinct
+Sensitivity = namedtuple("Sensitivity", "grad_mean percentiles prob_positive prob_negative importance importance_rms "
+                         "importance_percentiles top_prob samples n_samples n_distinct")
+
+
+def top_share(a, counts=None):
+    """a [n, n_out, n_in]: per sample and output a non-negative score of every input; counts [n]: integer multiplicities (None = 1
+    each).  -> [n_out, n_in] float64: the share of the expanded samples in which input i has the largest score of output o
+    (np.argmax: the first index on a tie)."""
+    a = np.asarray(a)
+    n, O, I = a.shape
+    c = np.ones(n, np.int64) if counts is None else np.asarray(counts, dtype=np.int64).reshape(n)
+    best = np.argmax(a, axis=2)                                  # [n, n_out]
+    hits = np.zeros((O, I), np.int64)
+    for o in range(O):
+        hits[o] = np.bincount(best[:, o], weights=None if counts is None else c, minlength=I).astype(np.int64)
+    return hits / np.float64(c.sum())
+
+
 # convergence_diagnostics' result: names [Q]; mean, sd, r_hat, ess, mcse_mean [Q] float64; ess_chain [n_chains, Q] or None; rho
 # [n_lags, Q] or None; trunc_lag [Q] int32; n_chains, n_draws
 Convergence = namedtuple("Convergence", "names mean sd r_hat ess mcse_mean ess_chain rho trunc_lag n_chains n_draws")
@@ -1050,6 +1072,55 @@ class ParallelTemperingBase:
         return Predictive(mean=mean, percentiles=bands, vote=out["vote"] if cls else None,
                           pred_class=np.argmax(mean, axis=1) if cls else None, samples=out["samples"],
                           n_samples=out["n_samples"], n_distinct=out["n_distinct"])
+
+    # ------------------------------------------------------------------ input sensitivity (not in the reference)
+    def input_sensitivity(self, x="test", *, burn_in=None, chains="all", thin=1, weights=None, percentiles=(5, 95), return_samples=False):
+        """Which inputs the sampled nets respond to, and how sure the posterior is about it, computed on the GPU: the gradient
+        g[n, o, i] = d output_o / d input_i of every selected sample on every row of `x` (the outputs posterior_predictive returns:
+        the sigmoid output of a regression, the class probabilities of a classification), reduced over the
+        samples.  For the time-series nets the inputs are lags.
+
+        Sample set, `chains`, `thin`, `weights` and `x` as in posterior_predictive; percentiles follow np.percentile(method="linear")
+        exactly.  -> Sensitivity: per row, output and input the posterior grad_mean, percentiles[q], prob_positive and
+        prob_negative (the shares of the samples with g > 0 and g < 0); per output and input the global relevance -- with
+        a_s = the mean over the rows of |g| in sample s: importance = the mean of a_s, importance_percentiles[q] of a_s,
+        importance_rms = sqrt of the mean of g^2 over rows and samples, top_prob = the share of the samples in which this input
+        has the largest a_s of the output (first index on a tie); samples [n_samples, n_rows, n_out, n_in] (chain-major) on
+        request; n_samples, n_distinct."""
+        self._need_sampler("input_sensitivity")
+        I = int(self.topology[0])
+        if isinstance(x, str):
+            if x not in ("train", "test"):
+                raise ValueError(f"x must be 'train', 'test' or an array, not {x!r}")
+            xs = x
+        else:
+            xa = np.asarray(x)
+            if xa.ndim != 2 or xa.shape[1] < I:
+                raise ValueError(f"x must be 2-D with at least n_in = {I} columns, got shape {xa.shape}")
+            xs = np.ascontiguousarray(xa[:, :I], dtype=np.float32)
+        pcts = list(percentiles)
+        if any(not (0 <= p <= 100) for p in pcts):
+            raise ValueError(f"percentiles must lie in [0, 100], got {pcts}")
+        if weights is not None:
+            w, mult = self._weights(weights)
+            kw = dict(w=w, multiplicity=mult)
+            M = int(np.sum(np.asarray(mult, dtype=np.int64))) if mult is not None else w.shape[0]
+        else:
+            kw, M = self._trace_selection(burn_in, chains, thin)
+        spots, ranks = self._band_ranks(M, pcts)
+        out = self._sampler.sensitivity(xs, ranks=ranks, ranks2=ranks, sample_abs=True, samples=bool(return_samples), **kw)
+        # top_prob from the distinct samples: runs of equal consecutive rows of sample_abs with their lengths
+        sa = out["sample_abs"]
+        new = np.ones(sa.shape[0], bool)
+        new[1:] = np.any(sa[1:] != sa[:-1], axis=(1, 2))
+        starts = np.flatnonzero(new)
+        top = top_share(sa[starts], np.diff(np.append(starts, sa.shape[0])))
+        has = bool(ranks)
+        return Sensitivity(grad_mean=out["grad_mean"], percentiles=self._bands(out["order_stats"], pcts, spots, ranks) if has else {},
+                           prob_positive=out["pos_count"] / np.float64(M), prob_negative=out["neg_count"] / np.float64(M),
+                           importance=out["abs_mean"], importance_rms=np.sqrt(out["sq_mean"]),
+                           importance_percentiles=self._bands(out["abs_order_stats"], pcts, spots, ranks) if has else {},
+                           top_prob=top, samples=out["samples"], n_samples=out["n_samples"], n_distinct=out["n_distinct"])
 
     # ------------------------------------------------------------------ convergence diagnostics (not in the reference)
     def convergence_diagnostics(self, *, burn_in=None, chains="all", thin=1, params=None, scalars=("likelihood",), per_chain=False,
