@@ -688,6 +688,79 @@ typedef struct ptnn_sensitivity_spec {
 
 int ptnn_sensitivity(ptnn_handle *h, const ptnn_sensitivity_spec *spec);
 
+/* ---- posterior predictive checks (nothing in the reference: it never simulates data from the fitted model) ----
+ * Does data simulated from the fitted model look like the data?  (BDA3 ch. 6; Gelman, Meng & Stern 1996.)  Every selected
+ * occurrence of a sample draws one replicated data set y_rep on the data rows; a test quantity T is evaluated on y_rep and on
+ * the targets y, and p = P(T(y_rep, theta) >= T(y, theta)) is counted over the occurrences.  DESIGN.md section 20.
+ * Samples: selected, merged and refused exactly as ptnn_calibration's two sources (the trace, or host vectors w [n_w, P] with
+ * eta [n_w] for a regression and optional multiplicities; same rules and error texts, the rows without a recorded eta included).
+ * Data as ptnn_elpd: x_source _TRAIN / _TEST or _HOST with x [n_rows, n_in + 1] (last column the target); the rows are taken
+ * in the order given (for the time-series nets: time).  Every selected occurrence is its own replicate: occurrence i is
+ * position i of the chain-major selection, host vectors after expanding the multiplicities (ptnn_forecast's noise-on index);
+ * M = occurrences, U = distinct (w, eta).  The forward pass runs once per distinct vector (ptnn_predict's, fp32 f / p);
+ * everything after it is double.
+ * Draws: Philox stream 6 (philox.py: STREAM_PPC); the draw of occurrence i, row n is component n % 4 of
+ * philox4x32_10(n / 4, i, 0, 6, seed).
+ * Regression (n_out == 1): z[i,n] = the device's Box-Muller of that block (philox.normals(n_rows, i, 0, 6, seed)[n] up to
+ * fp32 rounding); y_rep[i,n] = f + tau z, tau = exp(eta / 2); standardised residuals e[i,n] = (y_n - f[i,n]) / tau_i of the data
+ * and z[i,n] of the replicate.  For a series v of N rows with mean m: sd = the population standard deviation;
+ * acf_k(v) = sum_{n >= k} (v_n - m)(v_{n-k} - m) / sum_n (v_n - m)^2.  Statistics, in this order:
+ *   0-3  mean, sd, min, max                 of y                      | of y_rep[i, .]        (T on the data is the same for every i)
+ *   4    chi2                               sum e^2                   | sum z^2
+ *   5    max_abs_resid                      max |e|                   | max |z|
+ *   6    ljung_box                          N (N + 2) sum_k acf_k(e)^2 / (N - k) over lags[] | the same on z
+ *   7+j  resid_acf[lags[j]]                 acf_k(e[i, .])            | acf_k(z[i, .])
+ * lags: at most PTNN_PPC_MAX_LAGS distinct lags, each in [1, n_rows - 1].  n_stats = 7 + n_lags.
+ * Classification: p = ptnn_predict's fp32 class probabilities widened to double, u = ((x >> 9) + 0.5) 2^-23 of the Philox
+ * component; y_rep[i,n] = the smallest class k with sum_{j<=k} p_j > u sum_j p_j (sums in class order; the last class when none
+ * does).  Statistics, each with label = y and with label = y_rep[i, .]: 0 deviance = -2 sum_n log p_label; 1 accuracy = the
+ * share of rows with label == argmax p (first index on a tie); 2+k class_count[k].  n_stats = 2 + n_out.
+ * Reduction over the occurrences, per statistic j: n_defined = the occurrences where both T are finite (the others are left
+ * out of everything); n_greater = #{T_rep > T_obs}; n_equal = #{T_rep == T_obs}; mean_obs, mean_rep, var_rep (population),
+ * double sums in an order fixed by M.  The caller forms p_value = (n_greater + n_equal / 2) / n_defined.
+ * Outputs, any may be NULL: n_defined, n_greater, n_equal, mean_obs, mean_rep, var_rep [n_stats]; t_obs, t_rep [M, n_stats]
+ * chain-major; z [M, n_rows] fp32, the exact normal draws (regression); y_rep [M, n_rows] int32 classes (classification);
+ * n_samples = M; n_distinct = U.
+ * Refused: n_rows < 2; 2^31 or more samples (ptnn_calibration's limit and text); a lag out of range or listed twice; lags or
+ * z on a classification; y_rep on a regression; a regression with n_out != 1; a regression with more rows than one wave's
+ * LDS holds as doubles (19456).
+ * Runs on the handle's stream behind everything queued and returns when done; the distinct vectors are processed in blocks
+ * whose scratch (4 n_rows n_out bytes per vector) stays under $PTNN_PPC_SCRATCH_BYTES (read per call, default 1 GiB): every
+ * block holds all rows, so all rows of an occurrence are reduced by one wave in one order and no block size changes a bit.
+ * Touches no chain state, tape, counter or trace row.  Not with a communicator attached (one GPU only). */
+#define PTNN_PPC_MAX_LAGS 16
+
+typedef struct ptnn_ppc_spec {
+    int32_t struct_bytes;         /* = sizeof(ptnn_ppc_spec): ABI guard */
+    /* source 1: the trace (used when w == NULL) */
+    const int32_t *replicas;      /* local replica indices, or NULL = all */
+    int32_t n_replicas;           /* entries of replicas (ignored when NULL) */
+    int32_t step0, nsteps, thin;  /* trace rows step0, step0 + thin, ... < step0 + nsteps (thin >= 1) */
+    /* source 2: host vectors */
+    const float *w;               /* [n_w, P] or NULL */
+    const float *eta;             /* [n_w] log tau^2 (regression) */
+    const int32_t *multiplicity;  /* [n_w] >= 0, or NULL = 1 each */
+    int64_t n_w;
+    /* data */
+    int32_t x_source;             /* PTNN_PREDICT_X_HOST | _TRAIN | _TEST */
+    int32_t n_rows;
+    const float *x;               /* [n_rows, n_in + 1] (host rows only) */
+    /* residual autocorrelation (regression) */
+    const int32_t *lags;          /* [n_lags] distinct, each in [1, n_rows - 1] */
+    int32_t n_lags;               /* <= PTNN_PPC_MAX_LAGS */
+    int32_t reserved_;            /* keeps the seed 8-byte aligned; set 0 */
+    uint64_t seed;                /* Philox key of the replicated data */
+    /* outputs */
+    int64_t *n_defined, *n_greater, *n_equal;
+    double *mean_obs, *mean_rep, *var_rep;
+    double *t_obs, *t_rep;
+    float *z;
+    int32_t *y_rep;
+    int64_t *n_samples, *n_distinct;
+} ptnn_ppc_spec;
+
+int ptnn_ppc(ptnn_handle *h, const ptnn_ppc_spec *spec);
+
 /* the HIP stream (hipStream_t) all of this handle's work is queued on: lets the caller order its collectives after the
  * segment / before the swap kernels on the device instead of synchronising the host */
 int ptnn_stream(ptnn_handle *h, void **hip_stream);

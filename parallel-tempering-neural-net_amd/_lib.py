@@ -164,6 +164,25 @@ class SensitivitySpec(C.Structure):
     ]
 
 
+class PpcSpec(C.Structure):
+    """ptnn_ppc_spec (include/ptnn.h)."""
+    _fields_ = [
+        ("struct_bytes", C.c_int32),
+        ("replicas", C.POINTER(C.c_int32)), ("n_replicas", C.c_int32), ("step0", C.c_int32), ("nsteps", C.c_int32), ("thin", C.c_int32),
+        ("w", C.POINTER(C.c_float)), ("eta", C.POINTER(C.c_float)), ("multiplicity", C.POINTER(C.c_int32)), ("n_w", C.c_int64),
+        ("x_source", C.c_int32), ("n_rows", C.c_int32), ("x", C.POINTER(C.c_float)),
+        ("lags", C.POINTER(C.c_int32)), ("n_lags", C.c_int32), ("reserved_", C.c_int32), ("seed", C.c_uint64),
+        ("n_defined", C.POINTER(C.c_int64)), ("n_greater", C.POINTER(C.c_int64)), ("n_equal", C.POINTER(C.c_int64)),
+        ("mean_obs", C.POINTER(C.c_double)), ("mean_rep", C.POINTER(C.c_double)), ("var_rep", C.POINTER(C.c_double)),
+        ("t_obs", C.POINTER(C.c_double)), ("t_rep", C.POINTER(C.c_double)),
+        ("z", C.POINTER(C.c_float)), ("y_rep", C.POINTER(C.c_int32)),
+        ("n_samples", C.POINTER(C.c_int64)), ("n_distinct", C.POINTER(C.c_int64)),
+    ]
+
+
+PPC_MAX_LAGS = 16
+
+
 class LadderAdaptSpec(C.Structure):
     """ptnn_ladder_adapt_spec (include/ptnn.h)."""
     _fields_ = [("struct_bytes", C.c_int32), ("rounds", C.c_int32), ("kappa0", C.c_double), ("t0", C.c_double)]
@@ -257,6 +276,7 @@ SYMBOLS = {
     "ptnn_evidence": (C.c_int, [C.c_void_p, C.POINTER(EvidenceSpec)]),
     "ptnn_calibration": (C.c_int, [C.c_void_p, C.POINTER(CalibrationSpec)]),
     "ptnn_sensitivity": (C.c_int, [C.c_void_p, C.POINTER(SensitivitySpec)]),
+    "ptnn_ppc": (C.c_int, [C.c_void_p, C.POINTER(PpcSpec)]),
 }
 
 
@@ -915,6 +935,46 @@ class Sampler:
         ns, nd = C.c_int64(0), C.c_int64(0)
         spec.n_samples, spec.n_distinct = C.pointer(ns), C.pointer(nd)
         self._check(self.lib.ptnn_sensitivity(self.h, C.byref(spec)))
+        out["n_samples"], out["n_distinct"] = ns.value, nd.value
+        return out
+
+    def ppc(self, data="train", *, replicas=None, step0=0, nsteps=None, thin=1, w=None, eta=None, multiplicity=None, lags=(), seed=0,
+            samples=True, draws=False):
+        """ptnn_ppc: posterior predictive checks on the device -- every selected occurrence draws one replicated data set (Philox
+        stream STREAM_PPC of `seed`), test quantities T are evaluated on it and on the data.  Source: the trace rows step0, step0 +
+        thin, ... < step0 + nsteps of `replicas` (None = all), or host vectors w [n, P] with eta [n] (regression) and optional
+        integer `multiplicity` [n].  data: "train", "test" or rows [n_rows, n_in + 1] in their order (last column the target).
+        lags: the residual autocorrelation lags of a regression.  -> dict(n_defined, n_greater, n_equal [n_stats] int64, mean_obs,
+        mean_rep, var_rep [n_stats] float64, t_obs, t_rep [M, n_stats] float64 (samples), z [M, n_rows] float32 (draws, regression),
+        y_rep [M, n_rows] int32 (draws, classification), n_samples, n_distinct); what was not asked for is None."""
+        spec = PpcSpec()
+        spec.struct_bytes = C.sizeof(PpcSpec)
+        keep = []
+        dp, i64p = C.POINTER(C.c_double), C.POINTER(C.c_int64)
+        self._rows(spec, keep, data, "data", (self.cfg.n_in + 1, "n_in inputs and the target"))
+        if w is not None:
+            n = self._host_vectors(spec, keep, w, eta)
+            M = self._multiplicity(spec, keep, multiplicity, (n,), "multiplicity must have one entry per sample")
+        else:
+            M = math.prod(self._trace_source(spec, keep, replicas, step0, nsteps, thin))
+        lg = np.ascontiguousarray(lags, dtype=np.int32).reshape(-1)
+        keep.append(lg)
+        spec.lags, spec.n_lags = (_ptr(lg, _ip) if lg.size else None), lg.size
+        spec.seed = int(seed) & 0xFFFFFFFFFFFFFFFF
+        reg = self.cfg.task == TASK_REG
+        n_stats = 7 + lg.size if reg else 2 + self.cfg.n_out
+        n_rows, M = spec.n_rows, max(M, 0)
+        out = dict(n_defined=np.zeros(n_stats, np.int64), n_greater=np.zeros(n_stats, np.int64), n_equal=np.zeros(n_stats, np.int64),
+                   mean_obs=np.empty(n_stats), mean_rep=np.empty(n_stats), var_rep=np.empty(n_stats),
+                   t_obs=np.empty((M, n_stats)) if samples else None, t_rep=np.empty((M, n_stats)) if samples else None,
+                   z=np.empty((M, n_rows), np.float32) if draws and reg else None,
+                   y_rep=np.empty((M, n_rows), np.int32) if draws and not reg else None)
+        types = dict(n_defined=i64p, n_greater=i64p, n_equal=i64p, z=_fp, y_rep=_ip)
+        for k, v in out.items():
+            setattr(spec, k, _ptr(v, types.get(k, dp)))
+        ns, nd = C.c_int64(0), C.c_int64(0)
+        spec.n_samples, spec.n_distinct = C.pointer(ns), C.pointer(nd)
+        self._check(self.lib.ptnn_ppc(self.h, C.byref(spec)))
         out["n_samples"], out["n_distinct"] = ns.value, nd.value
         return out
 

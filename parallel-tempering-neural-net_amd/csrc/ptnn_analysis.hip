@@ -1,4 +1,4 @@
-// ptnn_analysis.hip -- the posterior analysis calls of libptnn.so: predict, convergence, elpd, lfo, forecast, evidence, calibration, sensitivity,
+// ptnn_analysis.hip -- the posterior analysis calls of libptnn.so: predict, convergence, elpd, lfo, forecast, evidence, calibration, sensitivity, ppc,
 // and the sample-selection path they share.  The shape-independent analysis kernels are defined in this object: it includes them.
 #include "ptnn_shapes.hpp"
 namespace ptnn {
@@ -8,6 +8,7 @@ namespace ptnn {
 #include "ptnn_dev_lfo.hpp"                  // leave-future-out cross-validation: running sums of ll, PSIS per origin
 #include "ptnn_dev_evidence.hpp"             // log evidence: per-rung statistics of the full-data log-likelihood, prior draws
 #include "ptnn_dev_calibration.hpp"          // calibration: PIT, quantiles and CRPS of the predictive mixture per data row
+#include "ptnn_dev_ppc.hpp"                  // posterior predictive checks: replicated data and test quantities per occurrence
 #define PTNN_SENSITIVITY_REDUCTIONS
 #include "ptnn_dev_sensitivity.hpp"          // input sensitivity, second part: sign counts, row sums and their weighted means
 }  // namespace ptnn
@@ -1452,6 +1453,144 @@ int ptnn_calibration(ptnn_handle* h, const ptnn_calibration_spec* spec) {
     HIP_TRY(fetch(s.quantiles, d_q, (size_t)s.n_levels * n_rows, st));
     HIP_TRY(fetch(s.crps, d_crps, (size_t)n_rows, st));
     return wait_stream(h);
+}
+
+// ---- posterior predictive checks (ptnn_dev_ppc.hpp) ----
+static_assert(PTNN_PPC_MAX_LAGS == PPC_MAX_LAGS, "ptnn.h ppc limits");
+
+int ptnn_ppc(ptnn_handle* h, const ptnn_ppc_spec* spec) {
+    // argument checks first: none of them needs the handle or a device
+    if (int rc = check_spec(spec, "ptnn_ppc_spec")) return rc;
+    const ptnn_ppc_spec& s = *spec;
+    const bool host_src = s.w != nullptr;
+    SampleSource src = source_of(s, host_src, s.eta);
+    const RowSource rows{s.x_source, s.x, s.n_rows, "x_source", "PTNN_PREDICT_X", "x", "n_rows"};
+    if (!src.host && s.nsteps < 1) return fail(-1, "no source: nsteps = %d trace rows and no host vectors w", s.nsteps);
+    if (int rc = check_source(src, "samples")) return rc;
+    if (s.n_rows < 2) return fail(-1, "n_rows = %d: a posterior predictive check needs at least 2 data rows", s.n_rows);
+    if (int rc = check_rows(rows)) return rc;
+    if (s.n_lags < 0 || s.n_lags > PPC_MAX_LAGS) return fail(-1, "n_lags = %d outside [0, %d]", s.n_lags, PPC_MAX_LAGS);
+    if (s.n_lags > 0 && !s.lags) return fail(-1, "n_lags = %d but lags is NULL", s.n_lags);
+    for (int k = 0; k < s.n_lags; ++k) {
+        if (s.lags[k] < 1 || s.lags[k] > s.n_rows - 1)
+            return fail(-1, "lags[%d] = %d outside [1, n_rows - 1 = %d]", k, s.lags[k], s.n_rows - 1);
+        for (int j = 0; j < k; ++j)
+            if (s.lags[j] == s.lags[k]) return fail(-1, "lags[%d] = lags[%d] = %d: a lag may be listed once", j, k, s.lags[k]);
+    }
+    if (src.host)
+        if (int rc = count_samples(nullptr, src)) return rc;
+    if (int rc = check_handle(h, "ptnn_ppc")) return rc;
+    const int I = h->cfg.n_in, O = h->cfg.n_out;
+    const bool reg = h->cfg.task == PTNN_TASK_REG;
+    if (reg && O != 1) return fail(-1, "a regression's posterior predictive check needs n_out == 1; this handle has n_out = %d", O);
+    if (!reg && s.n_lags > 0) return fail(-1, "lags: a classification has no residual autocorrelation");
+    if (!reg && s.z) return fail(-1, "z: a classification draws classes, not normal deviates");
+    if (reg && s.y_rep) return fail(-1, "y_rep: a regression's replicate is f + tau z; request z");
+    if (host_src && reg && !s.eta) return fail(-1, "a regression's host vectors need eta = log tau^2 (one per vector)");
+    if (int rc = fit_rows(h, rows)) return rc;
+    if (!src.host)
+        if (int rc = count_samples(h, src)) return rc;
+    const long long M = src.M;
+    if (M < 1) return fail(-1, "the selection holds no sample");
+    if (int rc = sample_limit(src)) return rc;
+    const int N = s.n_rows;
+    const int n_stats = reg ? PPC_REG_FIXED + s.n_lags : PPC_CLS_FIXED + O;
+    // a wave keeps its series in LDS: N doubles (regression), one counter per class (classification)
+    const size_t wave_doubles = reg ? (size_t)N : (size_t)(O + 1) / 2;
+    if (wave_doubles * sizeof(double) > LDS_CEILING)
+        return fail(-1, "n_rows = %d: the residual series of a posterior predictive check is kept in LDS, at most %d rows", N,
+                    (int)(LDS_CEILING / sizeof(double)));
+    if ((long long)N > 65535LL * WAVE) return fail(-1, "n_rows = %d: at most %lld rows per call", N, 65535LL * WAVE);
+    if (s.n_samples) *s.n_samples = M;
+
+    if (int rc = start_device(h)) return rc;
+    hipStream_t st = h->stream;
+    DeviceScratch mem;
+    const float* d_x = nullptr;
+    int xs = 0;
+    if (int rc = upload_rows(h, mem, rows, I + 1, &d_x, &xs)) return rc;
+    // stage a: items -> distinct (w, eta) samples (a classification's: distinct w, as ptnn_predict's)
+    Distinct d;
+    if (int rc = distinct_samples(h, mem, src, reg, true, &d)) return rc;
+    const int U = d.U;
+    if (s.n_distinct) *s.n_distinct = U;
+    // the distinct vector of every occurrence, chain-major with the multiplicities expanded: non-decreasing
+    std::vector<int> item_run;
+    if (int rc = item_runs(h, d, src.n_items, &item_run)) return rc;
+    if (int rc = wait_stream(h)) return rc;
+    std::vector<int> occ_u;
+    occ_u.reserve((size_t)M);
+    const int32_t* mult = src.weights();
+    for (size_t k = 0; k < item_run.size(); ++k) {
+        if (item_run[k] < 0 || item_run[k] >= U || (!occ_u.empty() && item_run[k] < occ_u.back()))
+            return fail(-2, "run-length pass: item %lld belongs to run %d of %d (internal error)", (long long)k, item_run[k], U);
+        occ_u.insert(occ_u.end(), (size_t)(mult ? mult[k] : 1), item_run[k]);
+    }
+    if ((long long)occ_u.size() != M) return fail(-2, "%lld occurrences expanded, %lld counted (internal error)", (long long)occ_u.size(), M);
+    int* d_occ = nullptr;
+    HIP_TRY(mem.upload(&d_occ, occ_u.data(), (size_t)M, st));
+
+    double *d_tobs = nullptr, *d_trep = nullptr;
+    float* d_z = nullptr;
+    int* d_yrep = nullptr;
+    HIP_TRY(mem.alloc(&d_tobs, (size_t)U * n_stats));
+    HIP_TRY(mem.alloc(&d_trep, (size_t)M * n_stats));
+    if (s.z) HIP_TRY(mem.alloc(&d_z, (size_t)M * N));
+    if (s.y_rep) HIP_TRY(mem.alloc(&d_yrep, (size_t)M * N));
+    // blocks of distinct vectors, every one with all rows: fx scratch nu x (rows x O) floats under the budget
+    const long long vec_blk = std::max(1LL, std::min<long long>((long long)(scratch_budget("PTNN_PPC_SCRATCH_BYTES") /
+                                                                            ((size_t)N * O * sizeof(float))), U));
+    float* d_fx = nullptr;
+    HIP_TRY(mem.alloc(&d_fx, (size_t)vec_blk * N * O));
+    ForwardPlan fwd;
+    if (int rc = fwd.init(h, "posterior predictive check")) return rc;
+    const int waves = (int)std::max<size_t>(1, std::min<size_t>(PPC_THREADS / WAVE, (64 * 1024) / (wave_doubles * sizeof(double))));
+    const size_t lds = (size_t)waves * wave_doubles * sizeof(double);
+    const auto kernel = reg ? ppc_occurrence_kernel<true> : ppc_occurrence_kernel<false>;
+    if (int rc = raise_lds_limit(reinterpret_cast<const void*>(kernel), lds)) return rc;
+    PpcJob ja{};
+    ja.n_rows = N; ja.O = O; ja.fx = d_fx; ja.eta = d.run_eta; ja.y = d_x + I; ja.ys = xs;
+    ja.n_lags = s.n_lags;
+    for (int k = 0; k < s.n_lags; ++k) ja.lags[k] = s.lags[k];
+    ja.seed_lo = (uint32_t)(s.seed & 0xffffffffu); ja.seed_hi = (uint32_t)(s.seed >> 32);
+    ja.occ_u = d_occ; ja.n_stats = n_stats; ja.wave_doubles = (int)wave_doubles;
+    ja.t_obs = d_tobs; ja.t_rep = d_trep; ja.z = d_z; ja.y_rep = d_yrep;
+    for (long long u0 = 0; u0 < U; u0 += vec_blk) {
+        const int nu = (int)std::min<long long>(vec_blk, U - u0);
+        if (int rc = fwd.launch(h, d.base, d.run_off + u0, d_x, xs, 0, N, nu, d_fx)) return rc;
+        const long long i0 = std::lower_bound(occ_u.begin(), occ_u.end(), (int)u0) - occ_u.begin();
+        const long long i1 = std::lower_bound(occ_u.begin(), occ_u.end(), (int)(u0 + nu)) - occ_u.begin();
+        ja.nu = nu; ja.u0 = (int)u0; ja.i0 = i0; ja.n_occ = (int)(i1 - i0);
+        const long long jobs = (long long)nu + (i1 - i0);
+        hipLaunchKernelGGL(kernel, dim3((unsigned)((jobs + waves - 1) / waves)), dim3((unsigned)(waves * WAVE)), lds, st, ja);
+        HIP_TRY(hipGetLastError());
+    }
+    long long *d_nd = nullptr, *d_ng = nullptr, *d_ne = nullptr;
+    double *d_mo = nullptr, *d_mr = nullptr, *d_vr = nullptr;
+    HIP_TRY(mem.alloc(&d_nd, (size_t)n_stats));
+    HIP_TRY(mem.alloc(&d_ng, (size_t)n_stats));
+    HIP_TRY(mem.alloc(&d_ne, (size_t)n_stats));
+    HIP_TRY(mem.alloc(&d_mo, (size_t)n_stats));
+    HIP_TRY(mem.alloc(&d_mr, (size_t)n_stats));
+    HIP_TRY(mem.alloc(&d_vr, (size_t)n_stats));
+    PpcReduce ra{M, n_stats, d_occ, d_tobs, d_trep, d_nd, d_ng, d_ne, d_mo, d_mr, d_vr};
+    hipLaunchKernelGGL(ppc_reduce_kernel, dim3((unsigned)n_stats), dim3(PPC_THREADS), 0, st, ra);
+    HIP_TRY(hipGetLastError());
+    std::vector<double> tobs_h(s.t_obs ? (size_t)U * n_stats : 0);
+    HIP_TRY(fetch((long long*)s.n_defined, d_nd, (size_t)n_stats, st));
+    HIP_TRY(fetch((long long*)s.n_greater, d_ng, (size_t)n_stats, st));
+    HIP_TRY(fetch((long long*)s.n_equal, d_ne, (size_t)n_stats, st));
+    HIP_TRY(fetch(s.mean_obs, d_mo, (size_t)n_stats, st));
+    HIP_TRY(fetch(s.mean_rep, d_mr, (size_t)n_stats, st));
+    HIP_TRY(fetch(s.var_rep, d_vr, (size_t)n_stats, st));
+    HIP_TRY(fetch(s.t_obs ? tobs_h.data() : nullptr, d_tobs, (size_t)U * n_stats, st));
+    HIP_TRY(fetch(s.t_rep, d_trep, (size_t)M * n_stats, st));
+    HIP_TRY(fetch(s.z, d_z, (size_t)M * N, st));
+    HIP_TRY(fetch(s.y_rep, d_yrep, (size_t)M * N, st));
+    if (int rc = wait_stream(h)) return rc;
+    for (long long i = 0; s.t_obs && i < M; ++i)
+        std::copy_n(tobs_h.begin() + (size_t)occ_u[(size_t)i] * n_stats, n_stats, s.t_obs + (size_t)i * n_stats);
+    return 0;
 }
 
 }  // extern "C"

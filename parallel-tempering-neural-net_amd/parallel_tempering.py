@@ -474,6 +474,57 @@ def classification_scores(p_mean, y, bins=10):
                 reliability={k: rel[k] for k in ("edges", "count", "confidence", "accuracy")}, ece=rel["ece"], mce=rel["mce"])
 
 
+# What predictive_check() returns.  names: the statistics in the device's order; p_value, t_obs_mean, t_rep_mean, t_rep_sd,
+# n_defined: dicts by name -- p = P(T(y_rep, theta) >= T(y, theta)) with ties counted half, the means of T on the data and on the
+# replicates, the (population) sd of T on the replicates, and the occurrences where both T are finite (the others are left out of
+# all of them; p is nan when none is left).  t_obs, t_rep [n_samples, len(names)] float64, chain-major (return_samples, else
+# None).  n_samples: the occurrences, each with its own replicate; n_distinct
+PredictiveCheck = namedtuple("PredictiveCheck", "names p_value t_obs_mean t_rep_mean t_rep_sd n_defined t_obs t_rep n_samples n_distinct")
+
+PPC_REGRESSION_STATS = ("mean", "sd", "min", "max", "chi2", "max_abs_resid", "ljung_box")
+PPC_CLASSIFICATION_STATS = ("deviance", "accuracy")
+PPC_DEFAULT_LAGS = (1, 2, 3, 4, 5)         # predictive_check's lags when none are given (a classification: none)
+
+
+def ppc_check_lags(lags, n_rows):
+    """The residual autocorrelation lags of a check on n_rows rows: distinct integers in [1, n_rows - 1], at most 16 -> list."""
+    lg = [int(k) for k in lags]
+    if any(k != v for k, v in zip(lg, lags)):
+        raise ValueError(f"lags must be integers, got {list(lags)}")
+    if len(lg) > _lib.PPC_MAX_LAGS:
+        raise ValueError(f"{len(lg)} lags: at most {_lib.PPC_MAX_LAGS} per call")
+    if len(set(lg)) != len(lg):
+        raise ValueError(f"lags must be distinct, got {lg}")
+    if any(not (1 <= k <= n_rows - 1) for k in lg):
+        raise ValueError(f"lags must lie in [1, n_rows - 1 = {n_rows - 1}], got {lg}")
+    return lg
+
+
+def ppc_stat_names(task, *, lags=(), n_out=1):
+    """The statistics of a posterior predictive check in the device's order: a regression's (TASK_REG) with one resid_acf[k]
+    per lag, a classification's with one class_count[k] per class."""
+    if task == TASK_REG:
+        return list(PPC_REGRESSION_STATS) + [f"resid_acf[{int(k)}]" for k in lags]
+    return list(PPC_CLASSIFICATION_STATS) + [f"class_count[{k}]" for k in range(int(n_out))]
+
+
+def ppc_p_values(n_greater, n_equal, n_defined):
+    """p = (n_greater + n_equal / 2) / n_defined per statistic: ties count half (a discrete T, such as a class count, then has
+    a p-value centred on 1/2 under the model); nan where no occurrence is defined."""
+    g, e, d = (np.asarray(v, dtype=np.float64) for v in (n_greater, n_equal, n_defined))
+    with np.errstate(invalid="ignore", divide="ignore"):
+        return np.where(d > 0, (g + 0.5 * e) / d, np.nan)
+
+
+def ppc_flagged(check, alpha=0.05):
+    """The names of the statistics whose posterior predictive p-value lies outside [alpha / 2, 1 - alpha / 2], in the order of
+    check.names: the features of the data the fitted model does not reproduce.  An undefined p-value (nan) is not flagged."""
+    a = float(alpha)
+    if not (0.0 < a < 1.0):
+        raise ValueError(f"alpha = {alpha} must lie in (0, 1)")
+    return [n for n in check.names if check.p_value[n] < a / 2.0 or check.p_value[n] > 1.0 - a / 2.0]
+
+
 # scalar trace columns convergence_diagnostics takes by name (a regression's acc_train slot holds eta = log tau^2)
 _SCALAR_COLS = {"likelihood": _lib.TR_LIKEH, "rmse_train": _lib.TR_RMSE_TR, "rmse_test": _lib.TR_RMSE_TE, "acc_train": _lib.TR_ACC_TR,
                 "eta": _lib.TR_ACC_TR, "acc_test": _lib.TR_ACC_TE}
@@ -1381,6 +1432,65 @@ class ParallelTemperingBase:
         if out["crps"] is not None:
             none["crps"], none["se_crps"] = crps_summary(out["crps"])
         return Calibration(**none)
+
+    # ------------------------------------------------------------------ posterior predictive checks (not in the reference)
+    def predictive_check(self, data="train", *, burn_in=None, chains="all", thin=1, weights=None, eta=None, lags=PPC_DEFAULT_LAGS,
+                         seed=None, return_samples=False):
+        """Does data simulated from the fitted model look like the data?  Posterior predictive checks (BDA3 ch. 6), computed on the
+        GPU from the sampled chains.  Every selected sample draws one replicated data set y_rep on the rows
+        of `data`; a test quantity T is evaluated on y_rep and on the targets y; p_value = P(T(y_rep, theta) >= T(y, theta)) over
+        the samples.  A p-value near 0 or 1 (ppc_flagged) names a feature of the data the model does not reproduce.
+
+        Regression (one output): y_rep = f + tau z with the sample's own tau^2 = exp(eta).  mean, sd, min, max of the series;
+        chi2 = sum e^2 and max_abs_resid = max |e| of the standardised residuals e = (y - f) / tau (the replicate's are z);
+        resid_acf[k], their autocorrelation at every lag of `lags` (at most 16, in [1, n_rows - 1]; default 1 .. 5), and ljung_box over those
+        lags: the Gaussian likelihood assumes independent residuals, which a flat PIT histogram (predictive_calibration) does not
+        test.  The rows are taken in the order given -- for the time-series nets that is time.  Classification: y_rep is drawn
+        from the sample's class probabilities; deviance = -2 sum log p_label, accuracy against argmax p, class_count[k].
+
+        Samples, `chains`, `thin`, `weights` (with `eta` for a regression) and `data` as predictive_accuracy(); every occurrence
+        of a repeated sample (a rejected MH step) draws its own replicate.  `seed`: the Philox key of the draws (stream
+        STREAM_PPC; None = the object's seed).  -> PredictiveCheck; t_obs / t_rep with return_samples."""
+        I = int(self.topology[0])
+        cls = self.task == TASK_CLS
+        if isinstance(data, str):
+            if data not in ("train", "test"):
+                raise ValueError(f"data must be 'train', 'test' or an array, not {data!r}")
+            ds = data
+            n_rows = len(self.traindata if data == "train" else self.testdata)
+        else:
+            xa = np.asarray(data)
+            if xa.ndim != 2 or xa.shape[1] < I + 1:
+                raise ValueError(f"data must be 2-D with at least n_in + 1 = {I + 1} columns (inputs, target), got shape {xa.shape}")
+            ds = np.ascontiguousarray(xa[:, :I + 1], dtype=np.float32)
+            n_rows = ds.shape[0]
+        if n_rows < 2:
+            raise ValueError(f"{n_rows} data rows: a posterior predictive check needs at least 2")
+        if cls:
+            if lags is not PPC_DEFAULT_LAGS and lags is not None and len(lags):
+                raise ValueError("lags: a classification has no residual autocorrelation")
+            lg = []
+        else:
+            if int(self.topology[2]) != 1:
+                raise ValueError("predictive_check needs a regression net with one output, or a classification")
+            if lags is PPC_DEFAULT_LAGS:
+                lags = [k for k in PPC_DEFAULT_LAGS if k <= n_rows - 1]
+            lg = ppc_check_lags(() if lags is None else lags, n_rows)
+        if weights is not None:
+            w, mult = self._weights(weights)
+            if not cls and eta is None:
+                raise ValueError("a regression's weights need eta = log tau^2, one per vector (Sampler.eta_trace())")
+            kw = dict(w=w, eta=None if cls else eta, multiplicity=mult)
+        self._need_sampler("predictive_check")
+        if weights is None:
+            kw, _ = self._trace_selection(burn_in, chains, thin)
+        out = self._sampler.ppc(ds, lags=lg, seed=self.seed if seed is None else int(seed), samples=bool(return_samples), **kw)
+        names = ppc_stat_names(self.task, lags=lg, n_out=int(self.topology[2]))
+        p = ppc_p_values(out["n_greater"], out["n_equal"], out["n_defined"])
+        by = lambda v: dict(zip(names, (x.item() for x in np.asarray(v))))       # noqa: E731
+        return PredictiveCheck(names=names, p_value=by(p), t_obs_mean=by(out["mean_obs"]), t_rep_mean=by(out["mean_rep"]),
+                               t_rep_sd=by(np.sqrt(out["var_rep"])), n_defined=by(out["n_defined"]), t_obs=out["t_obs"],
+                               t_rep=out["t_rep"], n_samples=out["n_samples"], n_distinct=out["n_distinct"])
 
     # ------------------------------------------------------------------ recursive forecasts (not in the reference)
     def forecast(self, horizon, origin="end", *, burn_in=None, chains="all", thin=1, percentiles=(5, 95), noise=False, seed=None,

@@ -2,7 +2,7 @@
 
 Used by the host only for the initial weights w0 (stream 3), which the reference draws in the parent process
 with np.random.randn (pt_timeseries_regression.py:649).  Streams: 0 step scalars, 1 proposal noise, 2 swap
-uniforms, 3 initial weights, 4 the observation noise of forecasts (counter (step / 4, trajectory, origin, 4)), 5 prior draws of the log evidence (counter (k / 4, draw, 0, 5)); counter = (index, step|round, global replica, stream); key = (seed lo, seed hi);
+uniforms, 3 initial weights, 4 the observation noise of forecasts (counter (step / 4, trajectory, origin, 4)), 5 prior draws of the log evidence (counter (k / 4, draw, 0, 5)), 6 the replicated data of posterior predictive checks (counter (row / 4, occurrence, 0, 6)); counter = (index, step|round, global replica, stream); key = (seed lo, seed hi);
 uniform u = ((x >> 9) + 0.5) * 2^-23; normals by Box-Muller on (x0,x1) and (x2,x3).
 """
 import numpy as np
@@ -12,7 +12,7 @@ _M1 = np.uint64(0xCD9E8D57)
 _W0 = 0x9E3779B9
 _W1 = 0xBB67AE85
 _MASK = np.uint64(0xFFFFFFFF)
-STREAM_STEP, STREAM_WNOISE, STREAM_SWAP, STREAM_INIT, STREAM_FORECAST, STREAM_PRIOR = 0, 1, 2, 3, 4, 5
+STREAM_STEP, STREAM_WNOISE, STREAM_SWAP, STREAM_INIT, STREAM_FORECAST, STREAM_PRIOR, STREAM_PPC = 0, 1, 2, 3, 4, 5, 6
 
 
 def philox4x32(c0, c1, c2, c3, seed):
