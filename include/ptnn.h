@@ -761,6 +761,86 @@ typedef struct ptnn_ppc_spec {
 
 int ptnn_ppc(ptnn_handle *h, const ptnn_ppc_spec *spec);
 
+/* ---- power-scaling sensitivity (nothing in the reference: its prior constants are fixed and never questioned) ----
+ * How much do the conclusions depend on the prior, and do prior and data pull against each other?  (Kallioinen, Paananen,
+ * Buerkner & Vehtari 2023.)  The prior, or the likelihood, is raised to a power alpha near 1 by importance-reweighting the
+ * samples already drawn; the weights are Pareto smoothed; the distance each quantity's marginal moves is measured.  DESIGN.md
+ * section 21.
+ * Samples: selected, merged and refused exactly as ptnn_calibration's two sources (the trace, or host vectors w [n_w, P] with
+ * eta [n_w] for a regression and optional multiplicities; same rules and error texts).  M = occurrences (>= 2), U = distinct
+ * (w, eta) (a classification: distinct w); the base weight of distinct vector u is c_u / M, c_u its multiplicity.  A vector
+ * of multiplicity 0 takes no part in anything.
+ * Components, one double per distinct vector:
+ *   likelihood  l_u  = the sum over the TRAINING rows, in row order, of ptnn_elpd's pointwise log-likelihood (untempered, from
+ *                      the fp32 forward outputs) -- the training rows whatever rows the predictions are taken on;
+ *   prior       pi_u = prior_likelihood (REG:207-221, CLS:224-230) with the handle's sigma_squared, nu_1, nu_2:
+ *                      part1 - sum_p w_p^2 / (2 sigma^2) [ - (1 + nu_1) eta - nu_2 exp(-eta) for a regression ],
+ *                      part1 = -(cnt / 2) log sigma^2, cnt = I H + H + 2 (REG) or I H + H + O + H O (CLS); double arithmetic on
+ *                      the fp32 w and eta (ptnn_evaluate's column 5 to fp32 accuracy).
+ * Perturbations: delta > 0; sign 0 is alpha_minus = 1 / (1 + delta), sign 1 is alpha_plus = 1 + delta.  For component c and
+ * alpha the log ratio of an occurrence is lr = (alpha - 1) c_u.  (lw, khat, T) = the Pareto smoothing of ptnn_elpd applied to
+ * lr (same r_eff rule for the tail bound M_t = ceil(min(0.2 M, 3 sqrt(M / r_eff))) <= PTNN_ELPD_TAIL_CAP, cut, Zhang-Stephens
+ * fit and cap at 0; khat = +inf and no smoothing where the tail holds <= 4 samples); tail positions are ordered by lr, then by
+ * distinct index, the c_u positions of a vector being consecutive.  The smoothed weight of u is the sum of exp(lw) over its
+ * c_u positions; q = those weights normalised to sum 1.
+ * Quantities, fp32 values per distinct vector, in this order, of the groups asked for: PTNN_POWERSCALE_WEIGHTS w_0 .. w_{P-1};
+ * _ETA eta (regression only); _PREDICTIONS the n_rows * n_out forward outputs of ptnn_predict on the chosen rows (x_source
+ * _TRAIN / _TEST, or _HOST with x [n_rows, n_in]), row-major; _LOGLIK (float)l_u.  Q = their count.
+ * Distance of one quantity under one perturbation: the U values in ascending order (-0 before +0, then by distinct index);
+ * P_j, Q_j = the base and perturbed weights cumulated through position j (double, in that order); b_j = x_{j+1} - x_j;
+ * m_j = (P_j + Q_j) / 2; h(a, m) = a (log2 a - log2 m), h(0, .) = 0;
+ *   d2 = sum_{j < U-1} b_j [h(P_j, m_j) + h(Q_j, m_j)] / sum_{j < U-1} b_j (P_j + Q_j);
+ * the same on the survival side (the order reversed, values negated, weights cumulated from the top); d = sqrt of the larger d2,
+ * 0 where that is negative, and 0 where all values are equal.  Sensitivity D = (d(alpha_minus) + d(alpha_plus)) / (2 log2
+ * alpha_plus).  Moments per quantity: mean = sum q_u x_u, sd = sqrt(sum q_u (x_u - mean)^2), and the same with the base weights
+ * (two passes, double, in the sorted order).
+ * Outputs, any may be NULL, k = 2 * component + sign with component 0 = likelihood, 1 = prior: sens [2][Q]; dist, mean, sd
+ * [2][2][Q]; base_mean, base_sd [Q]; khat, tail_len [2][2]; logp: room for 2 * n_items doubles (n_items = n_w or the selected
+ * trace rows), written as [2][U]: l_u then pi_u; n_samples = M; n_distinct = U; n_quantities = Q.
+ * Refused: delta or r_eff not finite and > 0; no group, an unknown group bit, _ETA on a classification; M < 2; the PSIS tail
+ * bound above PTNN_ELPD_TAIL_CAP (ptnn_elpd's text); U > PTNN_POWERSCALE_MAX_DISTINCT (thin= lowers U); a component that is
+ * not finite for a selected sample; an attached communicator.
+ * Runs on the handle's stream behind everything queued and returns when done.  The quantities are ordered and measured in
+ * blocks whose scratch (8 * 2^ceil(log2 U) + 4 U bytes per quantity) stays under $PTNN_POWERSCALE_SCRATCH_BYTES (read per call,
+ * default 1 GiB; at least one quantity -- predictions: one row's n_out, which alone may exceed a budget smaller than that; the
+ * budget bounds these per-quantity buffers and the forward pass over the training rows, not the 32 U bytes of weights, the
+ * 2 U components and the outputs [Q]).  A block holds whole quantities with all U values, so
+ * no block size changes a bit; the results depend on the sequence of distinct samples and multiplicities only (bitwise: trace,
+ * host vectors, expanded or (distinct, multiplicity)).  Touches no chain state, tape, counter or trace row. */
+#define PTNN_POWERSCALE_WEIGHTS 1
+#define PTNN_POWERSCALE_ETA 2
+#define PTNN_POWERSCALE_PREDICTIONS 4
+#define PTNN_POWERSCALE_LOGLIK 8
+#define PTNN_POWERSCALE_MAX_DISTINCT 65536
+
+typedef struct ptnn_powerscale_spec {
+    int32_t struct_bytes;         /* = sizeof(ptnn_powerscale_spec): ABI guard */
+    /* source 1: the trace (used when w == NULL) */
+    const int32_t *replicas;      /* local replica indices, or NULL = all */
+    int32_t n_replicas;           /* entries of replicas (ignored when NULL) */
+    int32_t step0, nsteps, thin;  /* trace rows step0, step0 + thin, ... < step0 + nsteps (thin >= 1) */
+    /* source 2: host vectors */
+    const float *w;               /* [n_w, P] or NULL */
+    const float *eta;             /* [n_w] log tau^2 (regression) */
+    const int32_t *multiplicity;  /* [n_w] >= 0, or NULL = 1 each */
+    int64_t n_w;
+    /* the rows of the predictions group (ignored without it) */
+    int32_t x_source;             /* PTNN_PREDICT_X_HOST | _TRAIN | _TEST */
+    int32_t n_rows;
+    const float *x;               /* [n_rows, n_in] (host rows only) */
+    int32_t groups;               /* PTNN_POWERSCALE_* bits */
+    int32_t reserved_;            /* set 0 */
+    double delta;                 /* > 0 */
+    double r_eff;                 /* > 0; 1 = independent draws */
+    /* outputs */
+    double *sens, *dist, *mean, *sd, *base_mean, *base_sd, *khat;
+    int64_t *tail_len;
+    double *logp;
+    int64_t *n_samples, *n_distinct, *n_quantities;
+} ptnn_powerscale_spec;
+
+int ptnn_powerscale(ptnn_handle *h, const ptnn_powerscale_spec *spec);
+
 /* the HIP stream (hipStream_t) all of this handle's work is queued on: lets the caller order its collectives after the
  * segment / before the swap kernels on the device instead of synchronising the host */
 int ptnn_stream(ptnn_handle *h, void **hip_stream);

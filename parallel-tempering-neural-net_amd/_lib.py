@@ -183,6 +183,25 @@ class PpcSpec(C.Structure):
 PPC_MAX_LAGS = 16
 
 
+class PowerscaleSpec(C.Structure):
+    """ptnn_powerscale_spec (include/ptnn.h)."""
+    _fields_ = [
+        ("struct_bytes", C.c_int32),
+        ("replicas", C.POINTER(C.c_int32)), ("n_replicas", C.c_int32), ("step0", C.c_int32), ("nsteps", C.c_int32), ("thin", C.c_int32),
+        ("w", C.POINTER(C.c_float)), ("eta", C.POINTER(C.c_float)), ("multiplicity", C.POINTER(C.c_int32)), ("n_w", C.c_int64),
+        ("x_source", C.c_int32), ("n_rows", C.c_int32), ("x", C.POINTER(C.c_float)),
+        ("groups", C.c_int32), ("reserved_", C.c_int32), ("delta", C.c_double), ("r_eff", C.c_double),
+        ("sens", C.POINTER(C.c_double)), ("dist", C.POINTER(C.c_double)), ("mean", C.POINTER(C.c_double)), ("sd", C.POINTER(C.c_double)),
+        ("base_mean", C.POINTER(C.c_double)), ("base_sd", C.POINTER(C.c_double)), ("khat", C.POINTER(C.c_double)),
+        ("tail_len", C.POINTER(C.c_int64)), ("logp", C.POINTER(C.c_double)),
+        ("n_samples", C.POINTER(C.c_int64)), ("n_distinct", C.POINTER(C.c_int64)), ("n_quantities", C.POINTER(C.c_int64)),
+    ]
+
+
+POWERSCALE_GROUPS = {"weights": 1, "eta": 2, "predictions": 4, "loglik": 8}      # PTNN_POWERSCALE_*, in the order of the quantities
+POWERSCALE_MAX_DISTINCT = 65536
+
+
 class LadderAdaptSpec(C.Structure):
     """ptnn_ladder_adapt_spec (include/ptnn.h)."""
     _fields_ = [("struct_bytes", C.c_int32), ("rounds", C.c_int32), ("kappa0", C.c_double), ("t0", C.c_double)]
@@ -277,6 +296,7 @@ SYMBOLS = {
     "ptnn_calibration": (C.c_int, [C.c_void_p, C.POINTER(CalibrationSpec)]),
     "ptnn_sensitivity": (C.c_int, [C.c_void_p, C.POINTER(SensitivitySpec)]),
     "ptnn_ppc": (C.c_int, [C.c_void_p, C.POINTER(PpcSpec)]),
+    "ptnn_powerscale": (C.c_int, [C.c_void_p, C.POINTER(PowerscaleSpec)]),
 }
 
 
@@ -976,6 +996,48 @@ class Sampler:
         spec.n_samples, spec.n_distinct = C.pointer(ns), C.pointer(nd)
         self._check(self.lib.ptnn_ppc(self.h, C.byref(spec)))
         out["n_samples"], out["n_distinct"] = ns.value, nd.value
+        return out
+
+    def powerscale(self, x="test", *, groups=("weights", "eta", "predictions"), delta=0.01, r_eff=1.0, replicas=None, step0=0,
+                   nsteps=None, thin=1, w=None, eta=None, multiplicity=None):
+        """ptnn_powerscale: power-scaling sensitivity on the device -- the prior and the likelihood are raised to 1 / (1 + delta)
+        and 1 + delta by Pareto-smoothed importance weights, and the distance every quantity's marginal moves is measured.
+        Source: the trace rows step0, step0 + thin, ... < step0 + nsteps of `replicas` (None = all), or host vectors w [n, P] with
+        eta [n] (regression) and optional integer `multiplicity` [n].  groups: names of POWERSCALE_GROUPS; x: the rows of the
+        predictions, "train", "test" or rows [n_rows, n_in].  Axis 0 of sens is the component (likelihood, prior), axes 0, 1 of
+        dist / mean / sd / khat / tail_len the component and the sign (alpha_minus, alpha_plus).  -> dict(sens [2, Q], dist, mean,
+        sd [2, 2, Q], base_mean, base_sd [Q] float64, khat [2, 2] float64, tail_len [2, 2] int64, logp [2, U] float64 (the
+        components per distinct sample), n_samples, n_distinct, n_quantities)."""
+        spec = PowerscaleSpec()
+        spec.struct_bytes = C.sizeof(PowerscaleSpec)
+        keep = []
+        dp = C.POINTER(C.c_double)
+        mask = 0
+        for g in groups:
+            if g not in POWERSCALE_GROUPS:
+                raise ValueError(f"unknown group {g!r}: choose among {list(POWERSCALE_GROUPS)}")
+            mask |= POWERSCALE_GROUPS[g]
+        spec.groups = mask
+        O = self.cfg.n_out
+        if mask & POWERSCALE_GROUPS["predictions"]:
+            self._rows(spec, keep, x, "x", (self.cfg.n_in, "n_in columns"))
+        if w is not None:
+            n_items = self._host_vectors(spec, keep, w, eta)
+            self._multiplicity(spec, keep, multiplicity, (n_items,), "multiplicity must have one entry per sample")
+        else:
+            n_items = math.prod(self._trace_source(spec, keep, replicas, step0, nsteps, thin))
+        spec.delta, spec.r_eff = float(delta), float(r_eff)
+        Q = ((self.P if mask & 1 else 0) + (1 if mask & 2 else 0) + (spec.n_rows * O if mask & 4 else 0) + (1 if mask & 8 else 0))
+        out = dict(sens=np.empty((2, Q)), dist=np.empty((2, 2, Q)), mean=np.empty((2, 2, Q)), sd=np.empty((2, 2, Q)),
+                   base_mean=np.empty(Q), base_sd=np.empty(Q), khat=np.empty((2, 2)), tail_len=np.empty((2, 2), np.int64),
+                   logp=np.empty(2 * max(n_items, 1)))
+        for k, v in out.items():
+            setattr(spec, k, _ptr(v, C.POINTER(C.c_int64) if k == "tail_len" else dp))
+        ns, nd, nq = C.c_int64(0), C.c_int64(0), C.c_int64(0)
+        spec.n_samples, spec.n_distinct, spec.n_quantities = C.pointer(ns), C.pointer(nd), C.pointer(nq)
+        self._check(self.lib.ptnn_powerscale(self.h, C.byref(spec)))
+        out["logp"] = out["logp"][:2 * nd.value].reshape(2, nd.value).copy()
+        out["n_samples"], out["n_distinct"], out["n_quantities"] = ns.value, nd.value, nq.value
         return out
 
     def forecast(self, horizon, origins="test", *, replicas=None, step0=0, nsteps=None, thin=1, w=None, multiplicity=None, eta=None,

@@ -1,5 +1,5 @@
 // ptnn_analysis.hip -- the posterior analysis calls of libptnn.so: predict, convergence, elpd, lfo, forecast, evidence, calibration, sensitivity, ppc,
-// and the sample-selection path they share.  The shape-independent analysis kernels are defined in this object: it includes them.
+// powerscale, and the sample-selection path they share.  The shape-independent analysis kernels are defined in this object: it includes them.
 #include "ptnn_shapes.hpp"
 namespace ptnn {
 #include "ptnn_dev_select.hpp"               // sample selection (run-length pass over the selected rows) and the per-column predictive reduction
@@ -9,6 +9,7 @@ namespace ptnn {
 #include "ptnn_dev_evidence.hpp"             // log evidence: per-rung statistics of the full-data log-likelihood, prior draws
 #include "ptnn_dev_calibration.hpp"          // calibration: PIT, quantiles and CRPS of the predictive mixture per data row
 #include "ptnn_dev_ppc.hpp"                  // posterior predictive checks: replicated data and test quantities per occurrence
+#include "ptnn_dev_powerscale.hpp"           // power-scaling sensitivity: components, smoothed weights, order per quantity, distances
 #define PTNN_SENSITIVITY_REDUCTIONS
 #include "ptnn_dev_sensitivity.hpp"          // input sensitivity, second part: sign counts, row sums and their weighted means
 }  // namespace ptnn
@@ -1590,6 +1591,225 @@ int ptnn_ppc(ptnn_handle* h, const ptnn_ppc_spec* spec) {
     if (int rc = wait_stream(h)) return rc;
     for (long long i = 0; s.t_obs && i < M; ++i)
         std::copy_n(tobs_h.begin() + (size_t)occ_u[(size_t)i] * n_stats, n_stats, s.t_obs + (size_t)i * n_stats);
+    return 0;
+}
+
+// ---- power-scaling sensitivity (ptnn_dev_powerscale.hpp) ----
+static_assert(PTNN_POWERSCALE_MAX_DISTINCT == PS_MAX_DISTINCT, "ptnn.h powerscale limits");
+
+// one block of nq quantities whose sort words are in `keys`: order them, then the distances and moments of the four perturbations
+static int powerscale_block(ptnn_handle* h, unsigned long long* keys, int nq, int npow, PsDist da, int q0) {
+    hipStream_t st = h->stream;
+    const int tile = std::min(npow, PS_SORT_TILE);
+    const dim3 tiles((unsigned)(npow / tile), (unsigned)nq);
+    hipLaunchKernelGGL(powerscale_sort_lds_kernel, tiles, dim3(PS_THREADS), 0, st, keys, npow, tile, 2, tile);
+    HIP_TRY(hipGetLastError());
+    for (int size = 2 * tile; size <= npow; size <<= 1) {
+        for (int stride = size / 2; stride >= tile; stride >>= 1) {
+            hipLaunchKernelGGL(powerscale_sort_step_kernel, dim3((unsigned)((npow / 2 + PS_THREADS - 1) / PS_THREADS), (unsigned)nq),
+                               dim3(PS_THREADS), 0, st, keys, npow, size, stride);
+            HIP_TRY(hipGetLastError());
+        }
+        hipLaunchKernelGGL(powerscale_sort_lds_kernel, tiles, dim3(PS_THREADS), 0, st, keys, npow, tile, size, size);
+        HIP_TRY(hipGetLastError());
+    }
+    da.keys = keys; da.q0 = q0;
+    hipLaunchKernelGGL(powerscale_distance_kernel, dim3((unsigned)nq, 4), dim3(PS_THREADS), 0, st, da);
+    HIP_TRY(hipGetLastError());
+    return 0;
+}
+
+int ptnn_powerscale(ptnn_handle* h, const ptnn_powerscale_spec* spec) {
+    // argument checks first: none of them needs the handle or a device
+    if (int rc = check_spec(spec, "ptnn_powerscale_spec")) return rc;
+    const ptnn_powerscale_spec& s = *spec;
+    const bool host_src = s.w != nullptr;
+    SampleSource src = source_of(s, host_src, s.eta);
+    const RowSource rows{s.x_source, s.x, s.n_rows, "x_source", "PTNN_PREDICT_X", "x", "n_rows"};
+    constexpr int all_groups = PTNN_POWERSCALE_WEIGHTS | PTNN_POWERSCALE_ETA | PTNN_POWERSCALE_PREDICTIONS | PTNN_POWERSCALE_LOGLIK;
+    const bool g_w = s.groups & PTNN_POWERSCALE_WEIGHTS, g_eta = s.groups & PTNN_POWERSCALE_ETA,
+               g_pred = s.groups & PTNN_POWERSCALE_PREDICTIONS, g_ll = s.groups & PTNN_POWERSCALE_LOGLIK;
+    if (!(s.delta > 0.0) || !std::isfinite(s.delta)) return fail(-1, "delta = %g must be a finite number > 0", s.delta);
+    if (!(s.r_eff > 0.0) || !std::isfinite(s.r_eff)) return fail(-1, "r_eff = %g must be a finite number > 0", s.r_eff);
+    if (s.groups == 0 || (s.groups & ~all_groups))
+        return fail(-1, "groups = 0x%x: choose among PTNN_POWERSCALE_WEIGHTS, _ETA, _PREDICTIONS and _LOGLIK", (unsigned)s.groups);
+    if (!src.host && s.nsteps < 1) return fail(-1, "no source: nsteps = %d trace rows and no host vectors w", s.nsteps);
+    if (int rc = check_source(src, "samples")) return rc;
+    if (g_pred) {
+        if (s.n_rows < 1) return fail(-1, "n_rows = %d must be >= 1", s.n_rows);
+        if (int rc = check_rows(rows)) return rc;
+    }
+    if (src.host)
+        if (int rc = count_samples(nullptr, src)) return rc;
+    if (int rc = check_handle(h, "ptnn_powerscale")) return rc;
+    const int I = h->cfg.n_in, H = h->cfg.n_hidden, O = h->cfg.n_out, P = h->P, Ntr = h->Ntr;
+    const bool reg = h->cfg.task == PTNN_TASK_REG;
+    if (g_eta && !reg) return fail(-1, "PTNN_POWERSCALE_ETA: a classification has no eta");
+    if (host_src && reg && !s.eta) return fail(-1, "a regression's host vectors need eta = log tau^2 (one per vector)");
+    if (g_pred)
+        if (int rc = fit_rows(h, rows)) return rc;
+    if (!src.host)
+        if (int rc = count_samples(h, src)) return rc;
+    const long long M = src.M;
+    if (M < 2) return fail(-1, "the selection holds %lld samples: importance weights need at least 2", M);
+    if (int rc = sample_limit(src)) return rc;
+    const long long Mt = (long long)std::ceil(std::min(0.2 * (double)M, 3.0 * std::sqrt((double)M / s.r_eff)));
+    if (Mt > ELPD_TAIL_CAP)
+        return fail(-1, "%lld samples with r_eff = %g need a PSIS tail of M = %lld > %d samples: select fewer samples (thin=, chains=) "
+                        "or give a larger r_eff", M, s.r_eff, Mt, ELPD_TAIL_CAP);
+    const long long n_pred = g_pred ? (long long)s.n_rows * O : 0;
+    const long long Qll = (g_w ? P : 0) + (g_eta ? 1 : 0) + n_pred + (g_ll ? 1 : 0);
+    if (Qll > 0x7fffffffLL) return fail(-1, "%lld quantities: at most 2^31 - 1 per call", Qll);
+    const int Q = (int)Qll;
+    if (s.n_samples) *s.n_samples = M;
+    if (s.n_quantities) *s.n_quantities = Q;
+
+    if (int rc = start_device(h)) return rc;
+    hipStream_t st = h->stream;
+    DeviceScratch mem;
+    // stage a: items -> distinct (w, eta) samples (a classification's: distinct w)
+    Distinct d;
+    if (int rc = distinct_samples(h, mem, src, reg, true, &d)) return rc;
+    const int U = d.U;
+    if (s.n_distinct) *s.n_distinct = U;
+    if (U > PS_MAX_DISTINCT)
+        return fail(-1, "%d distinct samples: power-scaling orders every quantity over all of them, at most %d; thin= lowers the "
+                        "number of distinct samples", U, PS_MAX_DISTINCT);
+    const size_t budget = scratch_budget("PTNN_POWERSCALE_SCRATCH_BYTES");
+    ForwardPlan fwd;
+    if (int rc = fwd.init(h, "power-scaling sensitivity")) return rc;
+
+    // 1. the components: l_u over the training rows in blocks of rows, pi_u from w and eta
+    double* d_logp = nullptr;
+    HIP_TRY(mem.alloc(&d_logp, (size_t)2 * U));
+    HIP_TRY(hipMemsetAsync(d_logp, 0, (size_t)U * sizeof(double), st));
+    {
+        DeviceScratch tmp;
+        const long long rows_blk = row_block(budget, (size_t)U * (sizeof(float) * O + sizeof(double)), Ntr);
+        float* d_fx = nullptr;
+        double* d_llb = nullptr;
+        HIP_TRY(tmp.alloc(&d_fx, (size_t)rows_blk * O * U));
+        HIP_TRY(tmp.alloc(&d_llb, (size_t)rows_blk * U));
+        ElpdRed ra{};
+        ra.mode = reg ? ELPD_REG : ELPD_CLS; ra.fx = d_fx; ra.eta = d.run_eta; ra.y = h->d_data + I; ra.ys = h->IPY; ra.cnt = d.run_cnt;
+        ra.U = U; ra.O = O; ra.ll_out = d_llb;
+        for (long long r0 = 0; r0 < Ntr; r0 += rows_blk) {
+            const int nr = (int)std::min<long long>(rows_blk, Ntr - r0);
+            if (int rc = fwd.launch(h, d.base, d.run_off, h->d_data, h->IPY, (int)r0, nr, U, d_fx)) return rc;
+            ra.row0 = (int)r0;
+            const long long n_ll = (long long)nr * U;
+            hipLaunchKernelGGL(elpd_loglik_kernel, dim3((unsigned)((n_ll + ELPD_THREADS - 1) / ELPD_THREADS)), dim3(ELPD_THREADS), 0, st, ra, nr);
+            HIP_TRY(hipGetLastError());
+            hipLaunchKernelGGL(powerscale_loglik_kernel, dim3((unsigned)((U + PS_THREADS - 1) / PS_THREADS)), dim3(PS_THREADS), 0, st,
+                               (const double*)d_llb, nr, U, d_logp);
+            HIP_TRY(hipGetLastError());
+        }
+        if (int rc = wait_stream(h)) return rc;          // `tmp` is released here
+    }
+    const double sig2 = (double)h->cfg.sigma_squared;
+    const double cnt = reg ? (double)(I * H + H + 2) : (double)(I * H + H + O + H * O);
+    PsPrior pa{d.base, d.run_off, d.run_eta, U, P, reg ? 1 : 0, -1.0 * (cnt / 2.0) * std::log(sig2), 1.0 / (2.0 * sig2),
+               (double)h->cfg.nu_1, (double)h->cfg.nu_2, d_logp + U};
+    hipLaunchKernelGGL(powerscale_prior_kernel, dim3((unsigned)((U + PS_THREADS / WAVE - 1) / (PS_THREADS / WAVE))), dim3(PS_THREADS), 0, st, pa);
+    HIP_TRY(hipGetLastError());
+    std::vector<double> logp_h((size_t)2 * U);
+    std::vector<int> cnt_h((size_t)U);
+    HIP_TRY(hipMemcpyAsync(logp_h.data(), d_logp, logp_h.size() * sizeof(double), hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipMemcpyAsync(cnt_h.data(), d.run_cnt, cnt_h.size() * sizeof(int), hipMemcpyDeviceToHost, st));
+    if (int rc = wait_stream(h)) return rc;
+    for (int c = 0; c < 2; ++c)
+        for (int u = 0; u < U; ++u)
+            if (cnt_h[(size_t)u] > 0 && !std::isfinite(logp_h[(size_t)c * U + u]))
+                return fail(-1, "the %s component of distinct sample %d is %g: power-scaling needs finite log-%s values for every selected "
+                                "sample", c ? "prior" : "likelihood", u, logp_h[(size_t)c * U + u], c ? "prior" : "likelihood");
+    if (s.logp) std::copy(logp_h.begin(), logp_h.end(), s.logp);
+
+    // 2. the smoothed, normalised weights of the four perturbations
+    double *d_wt = nullptr, *d_tlw = nullptr, *d_khat = nullptr;
+    int *d_tu = nullptr, *d_live = nullptr;
+    long long* d_tail = nullptr;
+    HIP_TRY(mem.alloc(&d_wt, (size_t)4 * U));
+    HIP_TRY(mem.alloc(&d_tlw, (size_t)4 * ELPD_TAIL_CAP));
+    HIP_TRY(mem.alloc(&d_tu, (size_t)4 * ELPD_TAIL_CAP));
+    HIP_TRY(mem.alloc(&d_khat, 4));
+    HIP_TRY(mem.alloc(&d_tail, 4));
+    HIP_TRY(mem.alloc(&d_live, 1));
+    const double a_plus = 1.0 + s.delta, a_minus = 1.0 / (1.0 + s.delta);
+    if (int rc = raise_lds_limit(reinterpret_cast<const void*>(powerscale_smooth_kernel), LFO_LDS_BYTES)) return rc;
+    PsSmooth sa{d_logp, d.run_cnt, U, (int)Mt, M, {a_minus - 1.0, a_plus - 1.0}, d_wt, d_tlw, d_tu, d_khat, d_tail, d_live};
+    hipLaunchKernelGGL(powerscale_smooth_kernel, dim3(4), dim3(ELPD_THREADS), LFO_LDS_BYTES, st, sa);
+    HIP_TRY(hipGetLastError());
+
+    // 3, 4. the quantities in blocks of whole quantities
+    int npow = 2;
+    while (npow < U) npow <<= 1;
+    const size_t per_q = sizeof(unsigned long long) * (size_t)npow + sizeof(float) * (size_t)U;
+    const int Qb = (int)std::max<size_t>(1, std::min<size_t>({budget / per_q, (size_t)65535, (size_t)Q}));
+    const int rows_q = g_pred ? std::max(1, std::min(Qb / O, s.n_rows)) : 0;      // rows of predictions per block
+    const int cap_q = std::max(Qb, rows_q * O);
+    unsigned long long* d_keys = nullptr;
+    float* d_fx = nullptr;
+    double *d_dist = nullptr, *d_mean = nullptr, *d_sd = nullptr, *d_bmean = nullptr, *d_bsd = nullptr;
+    HIP_TRY(mem.alloc(&d_keys, (size_t)cap_q * npow));
+    if (g_pred) HIP_TRY(mem.alloc(&d_fx, (size_t)rows_q * O * U));
+    HIP_TRY(mem.alloc(&d_dist, (size_t)4 * Q));
+    HIP_TRY(mem.alloc(&d_mean, (size_t)4 * Q));
+    HIP_TRY(mem.alloc(&d_sd, (size_t)4 * Q));
+    HIP_TRY(mem.alloc(&d_bmean, (size_t)Q));
+    HIP_TRY(mem.alloc(&d_bsd, (size_t)Q));
+    PsDist da{};
+    da.cnt = d.run_cnt; da.wt = d_wt; da.n_live = d_live; da.U = U; da.npow = npow; da.Q = Q; da.M = (double)M;
+    da.dist = d_dist; da.mean = d_mean; da.sd = d_sd; da.base_mean = d_bmean; da.base_sd = d_bsd;
+    const unsigned key_blocks = (unsigned)((npow + PS_THREADS - 1) / PS_THREADS);
+    auto plain = [&](const float* v32, const double* v64, int nq, int q0) -> int {      // quantities that lie [quantity][vector]
+        PsKeys ka{v32, v64, d.run_cnt, U, npow, d_keys};
+        hipLaunchKernelGGL(powerscale_keys_kernel, dim3(key_blocks, (unsigned)nq), dim3(PS_THREADS), 0, st, ka);
+        HIP_TRY(hipGetLastError());
+        return powerscale_block(h, d_keys, nq, npow, da, q0);
+    };
+    int q_at = 0;
+    for (int p0 = 0; g_w && p0 < P; p0 += Qb) {
+        const int nq = std::min(Qb, P - p0);
+        PsGather ga{d.base, d.run_off, d.run_cnt, U, npow, p0, nq, d_keys};
+        hipLaunchKernelGGL(powerscale_gather_kernel, dim3((unsigned)(npow + PS_GATHER_TILE - 1) / PS_GATHER_TILE,
+                                                          (unsigned)(nq + PS_GATHER_TILE - 1) / PS_GATHER_TILE), dim3(PS_THREADS), 0, st, ga);
+        HIP_TRY(hipGetLastError());
+        if (int rc = powerscale_block(h, d_keys, nq, npow, da, q_at + p0)) return rc;
+    }
+    q_at += g_w ? P : 0;
+    if (g_eta) {
+        if (int rc = plain(d.run_eta, nullptr, 1, q_at)) return rc;
+        q_at += 1;
+    }
+    if (g_pred) {
+        const float* d_x = nullptr;
+        int xs = 0;
+        if (int rc = upload_rows(h, mem, rows, I, &d_x, &xs)) return rc;
+        for (int r0 = 0; r0 < s.n_rows; r0 += rows_q) {
+            const int nr = std::min(rows_q, s.n_rows - r0);
+            if (int rc = fwd.launch(h, d.base, d.run_off, d_x, xs, r0, nr, U, d_fx)) return rc;
+            if (int rc = plain(d_fx, nullptr, nr * O, q_at + r0 * O)) return rc;
+        }
+        q_at += (int)n_pred;
+    }
+    if (g_ll)
+        if (int rc = plain(nullptr, d_logp, 1, q_at)) return rc;
+
+    std::vector<double> dist_h(s.sens || s.dist ? (size_t)4 * Q : 0);
+    long long tail_h[4];
+    HIP_TRY(fetch(dist_h.empty() ? nullptr : dist_h.data(), d_dist, (size_t)4 * Q, st));
+    HIP_TRY(fetch(s.mean, d_mean, (size_t)4 * Q, st));
+    HIP_TRY(fetch(s.sd, d_sd, (size_t)4 * Q, st));
+    HIP_TRY(fetch(s.base_mean, d_bmean, (size_t)Q, st));
+    HIP_TRY(fetch(s.base_sd, d_bsd, (size_t)Q, st));
+    HIP_TRY(fetch(s.khat, d_khat, 4, st));
+    HIP_TRY(fetch(s.tail_len ? tail_h : nullptr, d_tail, 4, st));
+    if (int rc = wait_stream(h)) return rc;
+    if (s.tail_len) std::copy_n(tail_h, 4, s.tail_len);
+    if (s.dist) std::copy(dist_h.begin(), dist_h.end(), s.dist);
+    const double scale = 2.0 * std::log2(a_plus);
+    for (int c = 0; s.sens && c < 2; ++c)
+        for (int q = 0; q < Q; ++q) s.sens[(size_t)c * Q + q] = (dist_h[(size_t)(2 * c) * Q + q] + dist_h[(size_t)(2 * c + 1) * Q + q]) / scale;
     return 0;
 }
 

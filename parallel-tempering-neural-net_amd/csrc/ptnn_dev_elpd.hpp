@@ -175,6 +175,8 @@ __device__ int block_excl_scan(int* buf, int v, int* total) {
 //                                     pairs, t kept in tval [ELPD_TAIL_CAP], entries ordered by lw, then t
 //   key(lw, t), second(t)             the stored words, ascending key = ascending lw
 //   decode(key, second, lw, t)        their values back
+//   EMIT                              true (ptnn_powerscale): emit_body(u, lw) for every body entry and emit_tail(j, t, lw) for
+//                                     every smoothed tail position j receive the final log weights; false: nothing is compiled in
 // Every thread of the work-group calls it and gets the three results.
 template <class Src>
 __device__ void psis_reduce(ElpdShared& sh, unsigned long long* tval, const Src& src, int U, long long S_, int M, double* elpd,
@@ -398,11 +400,13 @@ __device__ void psis_reduce(ElpdShared& sh, unsigned long long* tval, const Src&
         double lw, l;
         src.get(u, lw, l);
         if (smooth && lw > cut) continue;
+        if constexpr (Src::EMIT) src.emit_body(u, lw);
         fix_add(fz, exp(lw - a1), c);
         fix_add(fl, exp(lw + l - b2), c);
     }
     for (long long j = tid; j < (smooth ? T : 0); j += ELPD_THREADS) {
         const double l = t_at(j), lw = lw_smooth(j);
+        if constexpr (Src::EMIT) src.emit_tail(j, l, lw);
         fix_add(fz, exp(lw - a1), 1u);
         fix_add(fl, exp(lw + l - b2), 1u);
     }
@@ -419,6 +423,7 @@ struct ElpdLooSrc {
     int r;
     double y, mn;               // mn = min(ll) = -max(lr)
     static constexpr bool PAIR = false;
+    static constexpr bool EMIT = false;
     __device__ __forceinline__ int count(int u) const { return a.cnt[u]; }
     __device__ __forceinline__ void get(int u, double& lw, double& t) const { t = elpd_ll(a, r, u, y); lw = mn - t; }
     __device__ __forceinline__ unsigned long long key(double, double t) const { return ~elpd_key(t); }

@@ -50,6 +50,7 @@ struct LfoSrc {
     const int* cnt;
     double lrmax;
     static constexpr bool PAIR = true;
+    static constexpr bool EMIT = false;
     __device__ __forceinline__ int count(int u) const { return cnt[u]; }
     __device__ __forceinline__ double lr(int u) const { return ci[u] - cf[u]; }
     __device__ __forceinline__ void get(int u, double& lw, double& t) const {

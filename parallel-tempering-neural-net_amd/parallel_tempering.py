@@ -525,6 +525,72 @@ def ppc_flagged(check, alpha=0.05):
     return [n for n in check.names if check.p_value[n] < a / 2.0 or check.p_value[n] > 1.0 - a / 2.0]
 
 
+# powerscale_sensitivity's result: names [Q]; prior, likelihood {name: D}; mean_shift, sd_ratio {(component, sign): {name: value}},
+# component "prior" / "likelihood", sign "-" (alpha = 1 / (1 + delta)) / "+" (alpha = 1 + delta): (perturbed mean - base mean) /
+# base sd and perturbed sd / base sd; khat {(component, sign): k-hat}; diagnosis {name: text}; delta; threshold; good_k
+PowerScaling = namedtuple("PowerScaling", "names prior likelihood mean_shift sd_ratio khat diagnosis delta threshold good_k n_samples "
+                          "n_distinct")
+POWERSCALE_DEFAULT_QUANTITIES = ("weights", "eta", "predictions")     # quantities=None; a classification's default leaves eta out
+POWERSCALE_COMPONENTS = ("likelihood", "prior")                        # the device's order
+POWERSCALE_SIGNS = ("-", "+")
+
+
+def powerscale_check_delta(delta):
+    """The perturbation size of a power-scaling call: a finite number > 0 -> float."""
+    d = float(delta)
+    if not (d > 0.0 and math.isfinite(d)):
+        raise ValueError(f"delta = {delta} must be a finite number > 0")
+    return d
+
+
+def powerscale_groups(quantities, task):
+    """The quantity groups of a power-scaling call in the device's order (weights, eta, predictions, loglik) -> list."""
+    if quantities is None:
+        quantities = [g for g in POWERSCALE_DEFAULT_QUANTITIES if g != "eta" or task == TASK_REG]
+    q = list(quantities)
+    for g in q:
+        if g not in _lib.POWERSCALE_GROUPS:
+            raise ValueError(f"unknown quantity group {g!r}: choose among {list(_lib.POWERSCALE_GROUPS)}")
+    if not q:
+        raise ValueError("no quantity group chosen")
+    if "eta" in q and task != TASK_REG:
+        raise ValueError("eta: a classification has no eta")
+    return [g for g in _lib.POWERSCALE_GROUPS if g in q]
+
+
+def powerscale_names(groups, *, n_param, n_rows=0, n_out=1, task=TASK_REG):
+    """The names of the quantities in the device's order: w[p]; eta; f[n] (regression) or p[n,k] (classification); loglik."""
+    names = []
+    for g in _lib.POWERSCALE_GROUPS:
+        if g not in groups:
+            continue
+        if g == "weights":
+            names += [f"w[{p}]" for p in range(int(n_param))]
+        elif g == "predictions":
+            names += ([f"f[{n}]" for n in range(int(n_rows))] if task == TASK_REG and int(n_out) == 1 else
+                      [f"{'f' if task == TASK_REG else 'p'}[{n},{k}]" for n in range(int(n_rows)) for k in range(int(n_out))])
+        else:
+            names.append(g)
+    return names
+
+
+def powerscale_diagnosis(prior, likelihood, threshold=0.05):
+    """The table of Kallioinen et al. (2023) for one quantity's two sensitivities at `threshold`."""
+    if prior >= threshold:
+        return "prior-data conflict" if likelihood >= threshold else "strong prior / weak likelihood"
+    return "-"
+
+
+def powerscale_flagged(result, threshold=0.05):
+    """The names of the quantities whose prior sensitivity reaches `threshold`, with their diagnosis at that threshold, in the
+    order of result.names -> list of (name, diagnosis)."""
+    t = float(threshold)
+    if not t > 0.0:
+        raise ValueError(f"threshold = {threshold} must be > 0")
+    out = [(n, powerscale_diagnosis(result.prior[n], result.likelihood[n], t)) for n in result.names]
+    return [(n, d) for n, d in out if d != "-"]
+
+
 # scalar trace columns convergence_diagnostics takes by name (a regression's acc_train slot holds eta = log tau^2)
 _SCALAR_COLS = {"likelihood": _lib.TR_LIKEH, "rmse_train": _lib.TR_RMSE_TR, "rmse_test": _lib.TR_RMSE_TE, "acc_train": _lib.TR_ACC_TR,
                 "eta": _lib.TR_ACC_TR, "acc_test": _lib.TR_ACC_TE}
@@ -1491,6 +1557,71 @@ class ParallelTemperingBase:
         return PredictiveCheck(names=names, p_value=by(p), t_obs_mean=by(out["mean_obs"]), t_rep_mean=by(out["mean_rep"]),
                                t_rep_sd=by(np.sqrt(out["var_rep"])), n_defined=by(out["n_defined"]), t_obs=out["t_obs"],
                                t_rep=out["t_rep"], n_samples=out["n_samples"], n_distinct=out["n_distinct"])
+
+    # ------------------------------------------------------------------ power-scaling sensitivity (not in the reference)
+    def powerscale_sensitivity(self, data="test", *, quantities=None, delta=0.01, burn_in=None, chains="all",
+                               thin=1, weights=None, eta=None, r_eff=None, threshold=0.05):
+        """How much do the conclusions depend on the prior, and do prior and data pull against each other?  Power-scaling
+        sensitivity (Kallioinen, Paananen, Buerkner & Vehtari 2023), computed on the GPU from one fit.
+        The prior (sigma_squared, nu_1, nu_2 of this object) and the likelihood of the training rows are each raised to the powers
+        1 / (1 + delta) and 1 + delta by importance-reweighting the samples; the weights are Pareto smoothed as
+        predictive_accuracy()'s; D = the distance the marginal of a quantity moves (a symmetrised, cumulative Jensen-Shannon
+        distance), per unit of log2 alpha.  diagnosis, at `threshold`: prior and likelihood both >= threshold: "prior-data
+        conflict"; prior only: "strong prior / weak likelihood"; else "-" (powerscale_flagged lists the others).
+
+        quantities: None = "weights", "eta" (regression) and "predictions"; else any of "weights" (every w[p]), "eta"
+        (regression), "predictions" (f[n], or p[n,k] of a classification, on
+        the rows of `data`: "train", "test" or rows with at least n_in columns) and "loglik" (the training log-likelihood).
+        Samples, `chains`, `thin`, `weights` (with `eta` for a regression) as predictive_accuracy(); r_eff as there (None: 1).
+        A k-hat above good_k(n_samples) means the reweighting is unreliable for that perturbation, and a warning says so.  With
+        Langevin proposals the chain is not an exact sampler of the stated posterior (section 15): the diagnostic describes the
+        samples it is given.  -> PowerScaling."""
+        delta = powerscale_check_delta(delta)
+        groups = powerscale_groups(quantities, self.task)
+        I, O = int(self.topology[0]), int(self.topology[2])
+        n_rows = 0
+        ds = "test"
+        if "predictions" in groups:
+            if isinstance(data, str):
+                if data not in ("train", "test"):
+                    raise ValueError(f"data must be 'train', 'test' or an array, not {data!r}")
+                ds = data
+                n_rows = len(self.traindata if data == "train" else self.testdata)
+            else:
+                xa = np.asarray(data)
+                if xa.ndim != 2 or xa.shape[1] < I:
+                    raise ValueError(f"data must be 2-D with at least n_in = {I} columns, got shape {xa.shape}")
+                ds = np.ascontiguousarray(xa[:, :I], dtype=np.float32)
+                n_rows = ds.shape[0]
+        cls = self.task == TASK_CLS
+        if weights is not None:
+            w, mult = self._weights(weights)
+            if not cls and eta is None:
+                raise ValueError("a regression's weights need eta = log tau^2, one per vector (Sampler.eta_trace())")
+            kw = dict(w=w, eta=None if cls else eta, multiplicity=mult)
+        self._need_sampler("powerscale_sensitivity")
+        if weights is None:
+            kw, _ = self._trace_selection(burn_in, chains, thin)
+        out = self._sampler.powerscale(ds, groups=groups, delta=float(delta), r_eff=1.0 if r_eff is None else float(r_eff), **kw)
+        names = powerscale_names(groups, n_param=self.num_param, n_rows=n_rows, n_out=O, task=self.task)
+        by = lambda v: dict(zip(names, (float(x) for x in v)))       # noqa: E731
+        lik, pri = by(out["sens"][0]), by(out["sens"][1])
+        bsd = out["base_sd"]
+        shift, ratio, khat = {}, {}, {}
+        with np.errstate(invalid="ignore", divide="ignore"):
+            for c, comp in enumerate(POWERSCALE_COMPONENTS):
+                for g, sign in enumerate(POWERSCALE_SIGNS):
+                    shift[comp, sign] = by((out["mean"][c, g] - out["base_mean"]) / bsd)
+                    ratio[comp, sign] = by(out["sd"][c, g] / bsd)
+                    khat[comp, sign] = float(out["khat"][c, g])
+        gk = good_k(out["n_samples"])
+        high = [f"{c} {g}" for (c, g), k in khat.items() if math.isfinite(k) and k > gk]
+        if high:
+            warnings.warn(f"the Pareto k-hat of the perturbations {high} is above {gk:.2f}: the power-scaled weights are "
+                          f"unreliable for them", stacklevel=2)
+        return PowerScaling(names=names, prior=pri, likelihood=lik, mean_shift=shift, sd_ratio=ratio, khat=khat,
+                            diagnosis={n: powerscale_diagnosis(pri[n], lik[n], threshold) for n in names}, delta=float(delta),
+                            threshold=float(threshold), good_k=gk, n_samples=out["n_samples"], n_distinct=out["n_distinct"])
 
     # ------------------------------------------------------------------ recursive forecasts (not in the reference)
     def forecast(self, horizon, origin="end", *, burn_in=None, chains="all", thin=1, percentiles=(5, 95), noise=False, seed=None,
