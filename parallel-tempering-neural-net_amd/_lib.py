@@ -31,12 +31,14 @@ class Config(C.Structure):
 PREDICT_X_HOST, PREDICT_X_TRAIN, PREDICT_X_TEST = 0, 1, 2
 PREDICT_MAX_RANKS = 16
 
+# the six leading fields of every analysis spec: its size, then the trace selection
+_SELECTION = [("struct_bytes", C.c_int32), ("replicas", C.POINTER(C.c_int32)), ("n_replicas", C.c_int32), ("step0", C.c_int32),
+              ("nsteps", C.c_int32), ("thin", C.c_int32)]
+
 
 class PredictSpec(C.Structure):
     """ptnn_predict_spec (include/ptnn.h)."""
-    _fields_ = [
-        ("struct_bytes", C.c_int32),
-        ("replicas", C.POINTER(C.c_int32)), ("n_replicas", C.c_int32), ("step0", C.c_int32), ("nsteps", C.c_int32), ("thin", C.c_int32),
+    _fields_ = _SELECTION + [
         ("w", C.POINTER(C.c_float)), ("multiplicity", C.POINTER(C.c_int32)), ("n_w", C.c_int64),
         ("x_source", C.c_int32), ("n_rows", C.c_int32), ("x", C.POINTER(C.c_float)),
         ("ranks", C.POINTER(C.c_int64)), ("n_ranks", C.c_int32), ("reserved_", C.c_int32),
@@ -51,9 +53,7 @@ TR_LIKEH, TR_RMSE_TR, TR_RMSE_TE, TR_ACC_TR, TR_ACC_TE, TR_ACCEPT, TR_LOGALPHA, 
 
 class ConvergenceSpec(C.Structure):
     """ptnn_convergence_spec (include/ptnn.h)."""
-    _fields_ = [
-        ("struct_bytes", C.c_int32),
-        ("replicas", C.POINTER(C.c_int32)), ("n_replicas", C.c_int32), ("step0", C.c_int32), ("nsteps", C.c_int32), ("thin", C.c_int32),
+    _fields_ = _SELECTION + [
         ("params", C.POINTER(C.c_int32)), ("n_params", C.c_int32), ("scalars", C.c_int32),
         ("draws", C.POINTER(C.c_float)), ("n_chains", C.c_int32), ("n_draws", C.c_int32), ("n_quantities", C.c_int32),
         ("n_lags", C.c_int32),
@@ -64,9 +64,7 @@ class ConvergenceSpec(C.Structure):
 
 class ElpdSpec(C.Structure):
     """ptnn_elpd_spec (include/ptnn.h)."""
-    _fields_ = [
-        ("struct_bytes", C.c_int32),
-        ("replicas", C.POINTER(C.c_int32)), ("n_replicas", C.c_int32), ("step0", C.c_int32), ("nsteps", C.c_int32), ("thin", C.c_int32),
+    _fields_ = _SELECTION + [
         ("w", C.POINTER(C.c_float)), ("eta", C.POINTER(C.c_float)), ("loglik", C.POINTER(C.c_double)),
         ("multiplicity", C.POINTER(C.c_int32)), ("n_w", C.c_int64),
         ("x_source", C.c_int32), ("n_rows", C.c_int32), ("x", C.POINTER(C.c_float)),
@@ -82,9 +80,7 @@ ELPD_TAIL_CAP = 4096
 
 class LfoSpec(C.Structure):
     """ptnn_lfo_spec (include/ptnn.h)."""
-    _fields_ = [
-        ("struct_bytes", C.c_int32),
-        ("replicas", C.POINTER(C.c_int32)), ("n_replicas", C.c_int32), ("step0", C.c_int32), ("nsteps", C.c_int32), ("thin", C.c_int32),
+    _fields_ = _SELECTION + [
         ("w", C.POINTER(C.c_float)), ("eta", C.POINTER(C.c_float)), ("loglik", C.POINTER(C.c_double)),
         ("multiplicity", C.POINTER(C.c_int32)), ("n_w", C.c_int64),
         ("x_source", C.c_int32), ("n_rows", C.c_int32), ("x", C.POINTER(C.c_float)),
@@ -99,9 +95,7 @@ FORECAST_ORIGIN_HOST, FORECAST_ORIGIN_TRAIN, FORECAST_ORIGIN_TEST = 0, 1, 2
 
 class ForecastSpec(C.Structure):
     """ptnn_forecast_spec (include/ptnn.h)."""
-    _fields_ = [
-        ("struct_bytes", C.c_int32),
-        ("replicas", C.POINTER(C.c_int32)), ("n_replicas", C.c_int32), ("step0", C.c_int32), ("nsteps", C.c_int32), ("thin", C.c_int32),
+    _fields_ = _SELECTION + [
         ("w", C.POINTER(C.c_float)), ("multiplicity", C.POINTER(C.c_int32)), ("eta", C.POINTER(C.c_float)), ("n_w", C.c_int64),
         ("origin_source", C.c_int32), ("n_origins", C.c_int32), ("origins", C.POINTER(C.c_float)),
         ("horizon", C.c_int32), ("noise", C.c_int32), ("seed", C.c_uint64),
@@ -113,9 +107,7 @@ class ForecastSpec(C.Structure):
 
 class EvidenceSpec(C.Structure):
     """ptnn_evidence_spec (include/ptnn.h)."""
-    _fields_ = [
-        ("struct_bytes", C.c_int32),
-        ("replicas", C.POINTER(C.c_int32)), ("n_replicas", C.c_int32), ("step0", C.c_int32), ("nsteps", C.c_int32), ("thin", C.c_int32),
+    _fields_ = _SELECTION + [
         ("w", C.POINTER(C.c_float)), ("u", C.POINTER(C.c_double)), ("multiplicity", C.POINTER(C.c_int32)),
         ("n_rungs", C.c_int32), ("reserved_", C.c_int32), ("n_per_rung", C.c_int64), ("d", C.POINTER(C.c_double)),
         ("n_prior", C.c_int64), ("seed", C.c_uint64), ("a", C.POINTER(C.c_double)), ("n_a", C.c_int32), ("reserved2_", C.c_int32),
@@ -132,9 +124,7 @@ EVIDENCE_MAX_A = 4
 
 class CalibrationSpec(C.Structure):
     """ptnn_calibration_spec (include/ptnn.h)."""
-    _fields_ = [
-        ("struct_bytes", C.c_int32),
-        ("replicas", C.POINTER(C.c_int32)), ("n_replicas", C.c_int32), ("step0", C.c_int32), ("nsteps", C.c_int32), ("thin", C.c_int32),
+    _fields_ = _SELECTION + [
         ("w", C.POINTER(C.c_float)), ("eta", C.POINTER(C.c_float)), ("multiplicity", C.POINTER(C.c_int32)), ("n_w", C.c_int64),
         ("x_source", C.c_int32), ("n_rows", C.c_int32), ("x", C.POINTER(C.c_float)),
         ("levels_p", C.POINTER(C.c_double)), ("levels_z", C.POINTER(C.c_double)), ("n_levels", C.c_int32), ("pair_term", C.c_int32),
@@ -150,9 +140,7 @@ CALIB_MAX_DISTINCT = 65536
 
 class SensitivitySpec(C.Structure):
     """ptnn_sensitivity_spec (include/ptnn.h)."""
-    _fields_ = [
-        ("struct_bytes", C.c_int32),
-        ("replicas", C.POINTER(C.c_int32)), ("n_replicas", C.c_int32), ("step0", C.c_int32), ("nsteps", C.c_int32), ("thin", C.c_int32),
+    _fields_ = _SELECTION + [
         ("w", C.POINTER(C.c_float)), ("multiplicity", C.POINTER(C.c_int32)), ("n_w", C.c_int64),
         ("x_source", C.c_int32), ("n_rows", C.c_int32), ("x", C.POINTER(C.c_float)),
         ("ranks", C.POINTER(C.c_int64)), ("ranks2", C.POINTER(C.c_int64)), ("n_ranks", C.c_int32), ("n_ranks2", C.c_int32),
@@ -166,9 +154,7 @@ class SensitivitySpec(C.Structure):
 
 class PpcSpec(C.Structure):
     """ptnn_ppc_spec (include/ptnn.h)."""
-    _fields_ = [
-        ("struct_bytes", C.c_int32),
-        ("replicas", C.POINTER(C.c_int32)), ("n_replicas", C.c_int32), ("step0", C.c_int32), ("nsteps", C.c_int32), ("thin", C.c_int32),
+    _fields_ = _SELECTION + [
         ("w", C.POINTER(C.c_float)), ("eta", C.POINTER(C.c_float)), ("multiplicity", C.POINTER(C.c_int32)), ("n_w", C.c_int64),
         ("x_source", C.c_int32), ("n_rows", C.c_int32), ("x", C.POINTER(C.c_float)),
         ("lags", C.POINTER(C.c_int32)), ("n_lags", C.c_int32), ("reserved_", C.c_int32), ("seed", C.c_uint64),
@@ -185,9 +171,7 @@ PPC_MAX_LAGS = 16
 
 class PowerscaleSpec(C.Structure):
     """ptnn_powerscale_spec (include/ptnn.h)."""
-    _fields_ = [
-        ("struct_bytes", C.c_int32),
-        ("replicas", C.POINTER(C.c_int32)), ("n_replicas", C.c_int32), ("step0", C.c_int32), ("nsteps", C.c_int32), ("thin", C.c_int32),
+    _fields_ = _SELECTION + [
         ("w", C.POINTER(C.c_float)), ("eta", C.POINTER(C.c_float)), ("multiplicity", C.POINTER(C.c_int32)), ("n_w", C.c_int64),
         ("x_source", C.c_int32), ("n_rows", C.c_int32), ("x", C.POINTER(C.c_float)),
         ("groups", C.c_int32), ("reserved_", C.c_int32), ("delta", C.c_double), ("r_eff", C.c_double),
@@ -325,6 +309,33 @@ def _f32(a):
 
 def _ptr(a, typ=_fp):
     return None if a is None else a.ctypes.data_as(typ)
+
+
+def _spec(cls):
+    """A zeroed spec structure of an analysis call, its struct_bytes set."""
+    spec = cls()
+    spec.struct_bytes = C.sizeof(cls)
+    return spec
+
+
+def _ranks(spec, keep, ranks, fields=("ranks", "n_ranks")):
+    """0-based ranks of order statistics -> the spec's pointer and count fields (named by `fields`); returns the count."""
+    rk = np.ascontiguousarray(ranks, dtype=np.int64).reshape(-1)
+    keep.append(rk)
+    setattr(spec, fields[0], _ptr(rk, C.POINTER(C.c_int64)) if rk.size else None)
+    setattr(spec, fields[1], rk.size)
+    return rk.size
+
+
+_POINTER_OF = {np.dtype(np.float64): C.POINTER(C.c_double), np.dtype(np.float32): _fp, np.dtype(np.int64): C.POINTER(C.c_int64),
+               np.dtype(np.int32): _ip}
+
+
+def _bind(spec, out, **fields):
+    """The output arrays of `out` -> the spec's pointer fields of the same names (`fields`: the field of a key named otherwise),
+    each typed by its array's dtype; None stays NULL."""
+    for k, v in out.items():
+        setattr(spec, fields.get(k, k), None if v is None else _ptr(v, _POINTER_OF[v.dtype]))
 
 
 def comm_unique_id():
@@ -712,6 +723,37 @@ class Sampler:
         spec.multiplicity = _ptr(mu, _ip)
         return int(np.maximum(mu, 0).astype(np.int64).sum())
 
+    def _samples(self, spec, keep, *, w, eta=None, multiplicity, replicas, step0, nsteps, thin, unit):
+        """The sample source of an analysis call: host vectors w [n, P] (eta [n] optional) with integer multiplicities (one
+        entry per `unit`), else the trace rows -> the sample count."""
+        if w is not None:
+            n = self._host_vectors(spec, keep, w, eta)
+            return self._multiplicity(spec, keep, multiplicity, (n,), f"multiplicity must have one entry per {unit}")
+        return math.prod(self._trace_source(spec, keep, replicas, step0, nsteps, thin))
+
+    def _pointwise_source(self, spec, keep, data, *, loglik, multiplicity, **source):
+        """The sources of elpd() and lfo(): a host loglik [n, n_rows], else data rows with host vectors or trace rows -> the
+        sample count."""
+        if loglik is None:
+            self._rows(spec, keep, data, "data", (self.cfg.n_in + 1, "n_in inputs and the target"))
+            return self._samples(spec, keep, multiplicity=multiplicity, unit="sample", **source)
+        la = np.ascontiguousarray(loglik, dtype=np.float64)
+        if la.ndim != 2:
+            raise ValueError(f"loglik must be [n_samples, n_rows], got shape {la.shape}")
+        keep.append(la)
+        spec.loglik, spec.n_w, spec.n_rows = _ptr(la, C.POINTER(C.c_double)), la.shape[0], la.shape[1]
+        spec.x_source = PREDICT_X_HOST
+        return self._multiplicity(spec, keep, multiplicity, (la.shape[0],), "multiplicity must have one entry per sample")
+
+    def _call(self, fn, spec, out, counters=("n_samples", "n_distinct")):
+        """One analysis call: the int64 counters the library reports attached, the return code checked -> `out` with their values."""
+        values = {name: C.c_int64(0) for name in counters}
+        for name, v in values.items():
+            setattr(spec, name, C.pointer(v))
+        self._check(fn(self.h, C.byref(spec)))
+        out.update((name, v.value) for name, v in values.items())
+        return out
+
     def predict(self, x="test", *, replicas=None, step0=0, nsteps=None, thin=1, w=None, multiplicity=None, ranks=(), mean=True,
                 vote=False, samples=False):
         """ptnn_predict: network outputs of the selected weight vectors on input rows, reduced on the device.  Source: the trace rows
@@ -719,32 +761,18 @@ class Sampler:
         `multiplicity` [n].  x: "train", "test" or rows [n_rows, n_in].  -> dict(mean [n_rows, O] float64, order_stats
         [len(ranks), n_rows, O] float32 (exact values of those 0-based ranks), vote [n_rows, O] float64 (classification), samples
         [M, n_rows, O] float32, n_samples, n_distinct); what was not asked for is None."""
-        spec = PredictSpec()
-        spec.struct_bytes = C.sizeof(PredictSpec)
-        keep = []
+        spec, keep = _spec(PredictSpec), []
         self._rows(spec, keep, x, "x", (self.cfg.n_in, "n_in columns"))
         n_rows, O = spec.n_rows, self.cfg.n_out
-        if w is not None:
-            n = self._host_vectors(spec, keep, w)
-            M = self._multiplicity(spec, keep, multiplicity, (n,), "multiplicity must have one entry per vector")
-        else:
-            M = math.prod(self._trace_source(spec, keep, replicas, step0, nsteps, thin))
-        rk = np.ascontiguousarray(ranks, dtype=np.int64).reshape(-1)
-        keep.append(rk)
-        spec.ranks, spec.n_ranks = (_ptr(rk, C.POINTER(C.c_int64)) if rk.size else None), rk.size
+        M = self._samples(spec, keep, w=w, multiplicity=multiplicity, replicas=replicas, step0=step0, nsteps=nsteps, thin=thin,
+                          unit="vector")
+        n_rk = _ranks(spec, keep, ranks)
         out = dict(mean=np.empty((n_rows, O), np.float64) if mean else None,
-                   order_stats=np.empty((rk.size, n_rows, O), np.float32) if rk.size else None,
+                   order_stats=np.empty((n_rk, n_rows, O), np.float32) if n_rk else None,
                    vote=np.empty((n_rows, O), np.float64) if vote else None,
                    samples=np.empty((max(M, 0), n_rows, O), np.float32) if samples else None)
-        spec.mean = _ptr(out["mean"], C.POINTER(C.c_double))
-        spec.order_stats = _ptr(out["order_stats"])
-        spec.vote = _ptr(out["vote"], C.POINTER(C.c_double))
-        spec.samples = _ptr(out["samples"])
-        ns, nd = C.c_int64(0), C.c_int64(0)
-        spec.n_samples, spec.n_distinct = C.pointer(ns), C.pointer(nd)
-        self._check(self.lib.ptnn_predict(self.h, C.byref(spec)))
-        out["n_samples"], out["n_distinct"] = ns.value, nd.value
-        return out
+        _bind(spec, out)
+        return self._call(self.lib.ptnn_predict, spec, out)
 
     def convergence(self, *, replicas=None, step0=0, nsteps=None, thin=1, params=None, scalars=(), draws=None, per_chain=False,
                     n_lags=0):
@@ -752,9 +780,7 @@ class Sampler:
         of `replicas` (None = all) -- quantities: the weights `params` (None = all P), then the scalar columns `scalars` (TR_LIKEH ..
         TR_ACC_TE) in TR_ order -- or host draws [C, n, Q].  -> dict(mean, var, r_hat, ess [Q] float64, trunc_lag [Q] int32,
         ess_chain [C, Q] float64 (per_chain), rho [n_lags, Q] float64 (n_lags > 0), n_chains, n_draws); what was not asked for is None."""
-        spec = ConvergenceSpec()
-        spec.struct_bytes = C.sizeof(ConvergenceSpec)
-        keep = []
+        spec, keep = _spec(ConvergenceSpec), []
         if draws is not None:
             da = _f32(draws)
             if da.ndim != 3:
@@ -782,11 +808,9 @@ class Sampler:
         out = dict(mean=np.empty(Q), var=np.empty(Q), r_hat=np.empty(Q), ess=np.empty(Q), trunc_lag=np.empty(Q, np.int32),
                    ess_chain=np.empty((max(nc, 0), Q)) if per_chain else None,
                    rho=np.empty((int(n_lags), Q)) if n_lags else None)
-        for k in ("mean", "var", "r_hat", "ess", "ess_chain", "rho"):
-            setattr(spec, k, _ptr(out[k], C.POINTER(C.c_double)))
-        spec.trunc_lag = _ptr(out["trunc_lag"], _ip)
+        _bind(spec, out)
         spec.n_lags = int(n_lags)
-        self._check(self.lib.ptnn_convergence(self.h, C.byref(spec)))
+        self._call(self.lib.ptnn_convergence, spec, out, counters=())
         out["n_chains"], out["n_draws"] = int(nc), int(nd)
         return out
 
@@ -797,38 +821,15 @@ class Sampler:
         pointwise log-likelihood loglik [n, n_rows] float64; sources 2 and 3 take optional integer `multiplicity` [n].  data:
         "train", "test" or rows [n_rows, n_in + 1] (last column the target; ignored with loglik).  -> dict(lppd, p_waic, elpd_loo,
         khat [n_rows] float64, tail_len [n_rows] int64, loglik [S, n_rows] float64 (loglik_out), n_samples, n_distinct)."""
-        spec = ElpdSpec()
-        spec.struct_bytes = C.sizeof(ElpdSpec)
-        keep = []
-        dp = C.POINTER(C.c_double)
-        if loglik is not None:
-            la = np.ascontiguousarray(loglik, dtype=np.float64)
-            if la.ndim != 2:
-                raise ValueError(f"loglik must be [n_samples, n_rows], got shape {la.shape}")
-            keep.append(la)
-            spec.loglik, spec.n_w, spec.n_rows = la.ctypes.data_as(dp), la.shape[0], la.shape[1]
-            spec.x_source = PREDICT_X_HOST
-            n_host = la.shape[0]
-        else:
-            self._rows(spec, keep, data, "data", (self.cfg.n_in + 1, "n_in inputs and the target"))
-            n_host = None if w is None else self._host_vectors(spec, keep, w, eta)
-        if n_host is not None:
-            S = self._multiplicity(spec, keep, multiplicity, (n_host,), "multiplicity must have one entry per sample")
-        else:
-            S = math.prod(self._trace_source(spec, keep, replicas, step0, nsteps, thin))
+        spec, keep = _spec(ElpdSpec), []
+        S = self._pointwise_source(spec, keep, data, loglik=loglik, w=w, eta=eta, multiplicity=multiplicity, replicas=replicas,
+                                   step0=step0, nsteps=nsteps, thin=thin)
         spec.r_eff = float(r_eff)
         n_rows = spec.n_rows
         out = dict(lppd=np.empty(n_rows), p_waic=np.empty(n_rows), elpd_loo=np.empty(n_rows), khat=np.empty(n_rows),
                    tail_len=np.empty(n_rows, np.int64), loglik=np.empty((max(S, 0), n_rows)) if loglik_out else None)
-        for k in ("lppd", "p_waic", "elpd_loo", "khat"):
-            setattr(spec, k, out[k].ctypes.data_as(dp))
-        spec.tail_len = out["tail_len"].ctypes.data_as(C.POINTER(C.c_int64))
-        spec.loglik_out = out["loglik"].ctypes.data_as(dp) if loglik_out else None
-        ns, nd = C.c_int64(0), C.c_int64(0)
-        spec.n_samples, spec.n_distinct = C.pointer(ns), C.pointer(nd)
-        self._check(self.lib.ptnn_elpd(self.h, C.byref(spec)))
-        out["n_samples"], out["n_distinct"] = ns.value, nd.value
-        return out
+        _bind(spec, out, loglik="loglik_out")
+        return self._call(self.lib.ptnn_elpd, spec, out)
 
     def lfo(self, data="train", *, n_fit, origins, block=1, replicas=None, step0=0, nsteps=None, thin=1, w=None, eta=None,
             loglik=None, multiplicity=None, r_eff=1.0, loglik_out=False):
@@ -837,25 +838,9 @@ class Sampler:
         observed inputs, scored jointly; not a recursive forecast -- from rows [0, i) by Pareto-smoothed importance weights.
         data: "train", "test" or rows [n_rows, n_in + 1] in time order (ignored with loglik).  -> dict(elpd_lfo, khat [n_origins]
         float64, tail_len [n_origins] int64, loglik [S, n_rows] float64 (loglik_out), n_samples, n_distinct)."""
-        spec = LfoSpec()
-        spec.struct_bytes = C.sizeof(LfoSpec)
-        keep = []
-        dp = C.POINTER(C.c_double)
-        if loglik is not None:
-            la = np.ascontiguousarray(loglik, dtype=np.float64)
-            if la.ndim != 2:
-                raise ValueError(f"loglik must be [n_samples, n_rows], got shape {la.shape}")
-            keep.append(la)
-            spec.loglik, spec.n_w, spec.n_rows = la.ctypes.data_as(dp), la.shape[0], la.shape[1]
-            spec.x_source = PREDICT_X_HOST
-            n_host = la.shape[0]
-        else:
-            self._rows(spec, keep, data, "data", (self.cfg.n_in + 1, "n_in inputs and the target"))
-            n_host = None if w is None else self._host_vectors(spec, keep, w, eta)
-        if n_host is not None:
-            S = self._multiplicity(spec, keep, multiplicity, (n_host,), "multiplicity must have one entry per sample")
-        else:
-            S = math.prod(self._trace_source(spec, keep, replicas, step0, nsteps, thin))
+        spec, keep = _spec(LfoSpec), []
+        S = self._pointwise_source(spec, keep, data, loglik=loglik, w=w, eta=eta, multiplicity=multiplicity, replicas=replicas,
+                                   step0=step0, nsteps=nsteps, thin=thin)
         og = np.ascontiguousarray(origins, dtype=np.int32).reshape(-1)
         keep.append(og)
         spec.origins, spec.n_origins = (_ptr(og, _ip) if og.size else None), og.size
@@ -863,14 +848,8 @@ class Sampler:
         n_rows = spec.n_rows
         out = dict(elpd_lfo=np.empty(og.size), khat=np.empty(og.size), tail_len=np.empty(og.size, np.int64),
                    loglik=np.empty((max(S, 0), n_rows)) if loglik_out else None)
-        spec.elpd_lfo, spec.khat = out["elpd_lfo"].ctypes.data_as(dp), out["khat"].ctypes.data_as(dp)
-        spec.tail_len = out["tail_len"].ctypes.data_as(C.POINTER(C.c_int64))
-        spec.loglik_out = out["loglik"].ctypes.data_as(dp) if loglik_out else None
-        ns, nd = C.c_int64(0), C.c_int64(0)
-        spec.n_samples, spec.n_distinct = C.pointer(ns), C.pointer(nd)
-        self._check(self.lib.ptnn_lfo(self.h, C.byref(spec)))
-        out["n_samples"], out["n_distinct"] = ns.value, nd.value
-        return out
+        _bind(spec, out, loglik="loglik_out")
+        return self._call(self.lib.ptnn_lfo, spec, out)
 
     def calibration(self, data="test", *, replicas=None, step0=0, nsteps=None, thin=1, w=None, eta=None, multiplicity=None,
                     quantiles=(), crps=True):
@@ -880,16 +859,11 @@ class Sampler:
         Regression -> dict(pit, pred_mean, pred_sd [n_rows] float64, crps [n_rows] (crps=True: the all-pairs term), quantiles
         [len(quantiles), n_rows] of the levels `quantiles` in (0, 1)); classification -> dict(p_mean [n_rows, n_out]); both
         n_samples, n_distinct; what does not apply is None."""
-        spec = CalibrationSpec()
-        spec.struct_bytes = C.sizeof(CalibrationSpec)
-        keep = []
+        spec, keep = _spec(CalibrationSpec), []
         dp = C.POINTER(C.c_double)
         self._rows(spec, keep, data, "data", (self.cfg.n_in + 1, "n_in inputs and the target"))
-        if w is not None:
-            n = self._host_vectors(spec, keep, w, eta)
-            self._multiplicity(spec, keep, multiplicity, (n,), "multiplicity must have one entry per sample")
-        else:
-            self._trace_source(spec, keep, replicas, step0, nsteps, thin)
+        self._samples(spec, keep, w=w, eta=eta, multiplicity=multiplicity, replicas=replicas, step0=step0, nsteps=nsteps, thin=thin,
+                      unit="sample")
         n_rows, reg = spec.n_rows, self.cfg.task == TASK_REG
         lp = np.ascontiguousarray(quantiles, dtype=np.float64).reshape(-1)
         if lp.size > CALIB_MAX_LEVELS:
@@ -909,13 +883,8 @@ class Sampler:
                 spec.levels_p, spec.levels_z, spec.n_levels = lp.ctypes.data_as(dp), lz.ctypes.data_as(dp), lp.size
         else:
             out.update(p_mean=np.empty((n_rows, self.cfg.n_out)))
-        for k, v in out.items():
-            setattr(spec, k, v.ctypes.data_as(dp) if v is not None else None)
-        ns, nd = C.c_int64(0), C.c_int64(0)
-        spec.n_samples, spec.n_distinct = C.pointer(ns), C.pointer(nd)
-        self._check(self.lib.ptnn_calibration(self.h, C.byref(spec)))
-        out["n_samples"], out["n_distinct"] = ns.value, nd.value
-        return out
+        _bind(spec, out)
+        return self._call(self.lib.ptnn_calibration, spec, out)
 
     def sensitivity(self, x="test", *, replicas=None, step0=0, nsteps=None, thin=1, w=None, multiplicity=None, ranks=(), ranks2=(),
                     sample_abs=False, samples=False):
@@ -925,38 +894,21 @@ class Sampler:
         (samples with g > 0, g < 0), abs_mean, sq_mean [O, I] float64 (means over samples of the row means of |g| and g^2),
         abs_order_stats [len(ranks2), O, I] float32 (exact ranks of the per-sample row mean of |g|), sample_abs [M, O, I] float32,
         samples [M, n_rows, O, I] float32, n_samples, n_distinct); what was not asked for is None."""
-        spec = SensitivitySpec()
-        spec.struct_bytes = C.sizeof(SensitivitySpec)
-        keep = []
+        spec, keep = _spec(SensitivitySpec), []
         self._rows(spec, keep, x, "x", (self.cfg.n_in, "n_in columns"))
         n_rows, O, I = spec.n_rows, self.cfg.n_out, self.cfg.n_in
-        if w is not None:
-            n = self._host_vectors(spec, keep, w)
-            M = self._multiplicity(spec, keep, multiplicity, (n,), "multiplicity must have one entry per vector")
-        else:
-            M = math.prod(self._trace_source(spec, keep, replicas, step0, nsteps, thin))
-        i64p = C.POINTER(C.c_int64)
-        rk = np.ascontiguousarray(ranks, dtype=np.int64).reshape(-1)
-        rk2 = np.ascontiguousarray(ranks2, dtype=np.int64).reshape(-1)
-        keep += [rk, rk2]
-        spec.ranks, spec.n_ranks = (_ptr(rk, i64p) if rk.size else None), rk.size
-        spec.ranks2, spec.n_ranks2 = (_ptr(rk2, i64p) if rk2.size else None), rk2.size
+        M = self._samples(spec, keep, w=w, multiplicity=multiplicity, replicas=replicas, step0=step0, nsteps=nsteps, thin=thin,
+                          unit="vector")
+        n_rk, n_rk2 = _ranks(spec, keep, ranks), _ranks(spec, keep, ranks2, ("ranks2", "n_ranks2"))
         out = dict(grad_mean=np.empty((n_rows, O, I), np.float64),
-                   order_stats=np.empty((rk.size, n_rows, O, I), np.float32) if rk.size else None,
+                   order_stats=np.empty((n_rk, n_rows, O, I), np.float32) if n_rk else None,
                    pos_count=np.empty((n_rows, O, I), np.int64), neg_count=np.empty((n_rows, O, I), np.int64),
                    abs_mean=np.empty((O, I), np.float64), sq_mean=np.empty((O, I), np.float64),
-                   abs_order_stats=np.empty((rk2.size, O, I), np.float32) if rk2.size else None,
+                   abs_order_stats=np.empty((n_rk2, O, I), np.float32) if n_rk2 else None,
                    sample_abs=np.empty((max(M, 0), O, I), np.float32) if sample_abs else None,
                    samples=np.empty((max(M, 0), n_rows, O, I), np.float32) if samples else None)
-        types = dict(grad_mean=C.POINTER(C.c_double), abs_mean=C.POINTER(C.c_double), sq_mean=C.POINTER(C.c_double),
-                     pos_count=i64p, neg_count=i64p)
-        for k, v in out.items():
-            setattr(spec, k, _ptr(v, types.get(k, _fp)))
-        ns, nd = C.c_int64(0), C.c_int64(0)
-        spec.n_samples, spec.n_distinct = C.pointer(ns), C.pointer(nd)
-        self._check(self.lib.ptnn_sensitivity(self.h, C.byref(spec)))
-        out["n_samples"], out["n_distinct"] = ns.value, nd.value
-        return out
+        _bind(spec, out)
+        return self._call(self.lib.ptnn_sensitivity, spec, out)
 
     def ppc(self, data="train", *, replicas=None, step0=0, nsteps=None, thin=1, w=None, eta=None, multiplicity=None, lags=(), seed=0,
             samples=True, draws=False):
@@ -967,16 +919,10 @@ class Sampler:
         lags: the residual autocorrelation lags of a regression.  -> dict(n_defined, n_greater, n_equal [n_stats] int64, mean_obs,
         mean_rep, var_rep [n_stats] float64, t_obs, t_rep [M, n_stats] float64 (samples), z [M, n_rows] float32 (draws, regression),
         y_rep [M, n_rows] int32 (draws, classification), n_samples, n_distinct); what was not asked for is None."""
-        spec = PpcSpec()
-        spec.struct_bytes = C.sizeof(PpcSpec)
-        keep = []
-        dp, i64p = C.POINTER(C.c_double), C.POINTER(C.c_int64)
+        spec, keep = _spec(PpcSpec), []
         self._rows(spec, keep, data, "data", (self.cfg.n_in + 1, "n_in inputs and the target"))
-        if w is not None:
-            n = self._host_vectors(spec, keep, w, eta)
-            M = self._multiplicity(spec, keep, multiplicity, (n,), "multiplicity must have one entry per sample")
-        else:
-            M = math.prod(self._trace_source(spec, keep, replicas, step0, nsteps, thin))
+        M = self._samples(spec, keep, w=w, eta=eta, multiplicity=multiplicity, replicas=replicas, step0=step0, nsteps=nsteps, thin=thin,
+                          unit="sample")
         lg = np.ascontiguousarray(lags, dtype=np.int32).reshape(-1)
         keep.append(lg)
         spec.lags, spec.n_lags = (_ptr(lg, _ip) if lg.size else None), lg.size
@@ -989,14 +935,8 @@ class Sampler:
                    t_obs=np.empty((M, n_stats)) if samples else None, t_rep=np.empty((M, n_stats)) if samples else None,
                    z=np.empty((M, n_rows), np.float32) if draws and reg else None,
                    y_rep=np.empty((M, n_rows), np.int32) if draws and not reg else None)
-        types = dict(n_defined=i64p, n_greater=i64p, n_equal=i64p, z=_fp, y_rep=_ip)
-        for k, v in out.items():
-            setattr(spec, k, _ptr(v, types.get(k, dp)))
-        ns, nd = C.c_int64(0), C.c_int64(0)
-        spec.n_samples, spec.n_distinct = C.pointer(ns), C.pointer(nd)
-        self._check(self.lib.ptnn_ppc(self.h, C.byref(spec)))
-        out["n_samples"], out["n_distinct"] = ns.value, nd.value
-        return out
+        _bind(spec, out)
+        return self._call(self.lib.ptnn_ppc, spec, out)
 
     def powerscale(self, x="test", *, groups=("weights", "eta", "predictions"), delta=0.01, r_eff=1.0, replicas=None, step0=0,
                    nsteps=None, thin=1, w=None, eta=None, multiplicity=None):
@@ -1008,10 +948,7 @@ class Sampler:
         dist / mean / sd / khat / tail_len the component and the sign (alpha_minus, alpha_plus).  -> dict(sens [2, Q], dist, mean,
         sd [2, 2, Q], base_mean, base_sd [Q] float64, khat [2, 2] float64, tail_len [2, 2] int64, logp [2, U] float64 (the
         components per distinct sample), n_samples, n_distinct, n_quantities)."""
-        spec = PowerscaleSpec()
-        spec.struct_bytes = C.sizeof(PowerscaleSpec)
-        keep = []
-        dp = C.POINTER(C.c_double)
+        spec, keep = _spec(PowerscaleSpec), []
         mask = 0
         for g in groups:
             if g not in POWERSCALE_GROUPS:
@@ -1021,23 +958,17 @@ class Sampler:
         O = self.cfg.n_out
         if mask & POWERSCALE_GROUPS["predictions"]:
             self._rows(spec, keep, x, "x", (self.cfg.n_in, "n_in columns"))
-        if w is not None:
-            n_items = self._host_vectors(spec, keep, w, eta)
-            self._multiplicity(spec, keep, multiplicity, (n_items,), "multiplicity must have one entry per sample")
-        else:
-            n_items = math.prod(self._trace_source(spec, keep, replicas, step0, nsteps, thin))
+        M = self._samples(spec, keep, w=w, eta=eta, multiplicity=multiplicity, replicas=replicas, step0=step0, nsteps=nsteps, thin=thin,
+                          unit="sample")
+        n_items = M if w is None else spec.n_w              # an item of multiplicity 0 is still a distinct sample
         spec.delta, spec.r_eff = float(delta), float(r_eff)
         Q = ((self.P if mask & 1 else 0) + (1 if mask & 2 else 0) + (spec.n_rows * O if mask & 4 else 0) + (1 if mask & 8 else 0))
         out = dict(sens=np.empty((2, Q)), dist=np.empty((2, 2, Q)), mean=np.empty((2, 2, Q)), sd=np.empty((2, 2, Q)),
                    base_mean=np.empty(Q), base_sd=np.empty(Q), khat=np.empty((2, 2)), tail_len=np.empty((2, 2), np.int64),
                    logp=np.empty(2 * max(n_items, 1)))
-        for k, v in out.items():
-            setattr(spec, k, _ptr(v, C.POINTER(C.c_int64) if k == "tail_len" else dp))
-        ns, nd, nq = C.c_int64(0), C.c_int64(0), C.c_int64(0)
-        spec.n_samples, spec.n_distinct, spec.n_quantities = C.pointer(ns), C.pointer(nd), C.pointer(nq)
-        self._check(self.lib.ptnn_powerscale(self.h, C.byref(spec)))
-        out["logp"] = out["logp"][:2 * nd.value].reshape(2, nd.value).copy()
-        out["n_samples"], out["n_distinct"], out["n_quantities"] = ns.value, nd.value, nq.value
+        _bind(spec, out)
+        self._call(self.lib.ptnn_powerscale, spec, out, counters=("n_samples", "n_distinct", "n_quantities"))
+        out["logp"] = out["logp"][:2 * out["n_distinct"]].reshape(2, out["n_distinct"]).copy()
         return out
 
     def forecast(self, horizon, origins="test", *, replicas=None, step0=0, nsteps=None, thin=1, w=None, multiplicity=None, eta=None,
@@ -1048,31 +979,18 @@ class Sampler:
         exp(eta / 2) z_k to every step (Philox stream STREAM_FORECAST of `seed`).  -> dict(mean [n_origins, horizon] float64,
         order_stats [len(ranks), n_origins, horizon] float32, samples [M, n_origins, horizon] float32, n_samples, n_trajectories);
         what was not asked for is None."""
-        spec = ForecastSpec()
-        spec.struct_bytes = C.sizeof(ForecastSpec)
-        keep = []
+        spec, keep = _spec(ForecastSpec), []
         self._rows(spec, keep, origins, "origins", (self.cfg.n_in, "n_in columns"), ("origin_source", "n_origins", "origins"))
         spec.horizon, spec.noise, spec.seed = int(horizon), 1 if noise else 0, int(seed) & 0xFFFFFFFFFFFFFFFF
         n_org, hz = spec.n_origins, max(int(horizon), 0)
-        if w is not None:
-            n = self._host_vectors(spec, keep, w, eta)
-            M = self._multiplicity(spec, keep, multiplicity, (n,), "multiplicity must have one entry per vector")
-        else:
-            M = math.prod(self._trace_source(spec, keep, replicas, step0, nsteps, thin))
-        rk = np.ascontiguousarray(ranks, dtype=np.int64).reshape(-1)
-        keep.append(rk)
-        spec.ranks, spec.n_ranks = (_ptr(rk, C.POINTER(C.c_int64)) if rk.size else None), rk.size
+        M = self._samples(spec, keep, w=w, eta=eta, multiplicity=multiplicity, replicas=replicas, step0=step0, nsteps=nsteps, thin=thin,
+                          unit="vector")
+        n_rk = _ranks(spec, keep, ranks)
         out = dict(mean=np.empty((n_org, hz), np.float64) if mean else None,
-                   order_stats=np.empty((rk.size, n_org, hz), np.float32) if rk.size else None,
+                   order_stats=np.empty((n_rk, n_org, hz), np.float32) if n_rk else None,
                    samples=np.empty((max(M, 0), n_org, hz), np.float32) if samples else None)
-        spec.mean = _ptr(out["mean"], C.POINTER(C.c_double))
-        spec.order_stats = _ptr(out["order_stats"])
-        spec.samples = _ptr(out["samples"])
-        ns, nt = C.c_int64(0), C.c_int64(0)
-        spec.n_samples, spec.n_trajectories = C.pointer(ns), C.pointer(nt)
-        self._check(self.lib.ptnn_forecast(self.h, C.byref(spec)))
-        out["n_samples"], out["n_trajectories"] = ns.value, nt.value
-        return out
+        _bind(spec, out)
+        return self._call(self.lib.ptnn_forecast, spec, out, counters=("n_samples", "n_trajectories"))
 
     def evidence(self, *, replicas=None, step0=0, nsteps=None, thin=1, w=None, u=None, multiplicity=None, d=None, n_prior=0, seed=0,
                  a=(), u_out=False, u_prior_out=False):
@@ -1083,9 +1001,7 @@ class Sampler:
         -> dict(u_mean, u_var, u_ess, log_stone, stone_relvar [K] float64, n_draws [K] int64, prior_log_mean_exp,
         prior_kish_ess, prior_u_mean, prior_u_var [n_a] float64, u [sum n_draws] float64 (u_out), u_prior [n_prior] float64
         (u_prior_out), n_distinct)."""
-        spec = EvidenceSpec()
-        spec.struct_bytes = C.sizeof(EvidenceSpec)
-        keep = []
+        spec, keep = _spec(EvidenceSpec), []
         dp = C.POINTER(C.c_double)
         if u is not None:
             ua = np.ascontiguousarray(u, dtype=np.float64)
@@ -1123,20 +1039,12 @@ class Sampler:
         out["n_draws"] = np.zeros(K, np.int64)
         for k in ("prior_log_mean_exp", "prior_kish_ess", "prior_u_mean", "prior_u_var"):
             out[k] = np.full(aa.size, np.nan)
-        for k in ("u_mean", "u_var", "u_ess", "prior_log_mean_exp", "prior_kish_ess", "prior_u_mean", "prior_u_var"):
-            setattr(spec, k, out[k].ctypes.data_as(dp))
-        if d is not None:
-            spec.log_stone, spec.stone_relvar = out["log_stone"].ctypes.data_as(dp), out["stone_relvar"].ctypes.data_as(dp)
-        spec.n_draws = out["n_draws"].ctypes.data_as(C.POINTER(C.c_int64))
         out["u"] = np.empty(max(total, 0)) if u_out else None
         out["u_prior"] = np.empty(max(int(n_prior), 0)) if u_prior_out else None
-        spec.u_out = out["u"].ctypes.data_as(dp) if u_out else None
-        spec.u_prior_out = out["u_prior"].ctypes.data_as(dp) if u_prior_out else None
-        nd = C.c_int64(0)
-        spec.n_distinct = C.pointer(nd)
-        self._check(self.lib.ptnn_evidence(self.h, C.byref(spec)))
-        out["n_distinct"] = nd.value
-        return out
+        _bind(spec, out, u="u_out", u_prior="u_prior_out")
+        if d is None:
+            spec.log_stone = spec.stone_relvar = None                   # no stones without exponents: they stay NaN
+        return self._call(self.lib.ptnn_evidence, spec, out, counters=("n_distinct",))
 
     def langevin_gradient(self, w):
         w = _f32(np.atleast_2d(w))

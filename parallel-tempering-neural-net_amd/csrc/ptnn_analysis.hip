@@ -45,6 +45,26 @@ template <typename T> hipError_t fetch(T* dst, const T* src, size_t n, hipStream
     return dst ? hipMemcpyAsync(dst, src, n * sizeof(T), hipMemcpyDeviceToHost, st) : hipSuccess;
 }
 
+// One kernel launch, the arguments converted to the kernel's parameter types -> hipGetLastError(): HIP_TRY(launch(...)), so that
+// a failed launch is reported where it happened
+template <typename... KA, typename... A>
+hipError_t launch(void (*kernel)(KA...), dim3 grid, dim3 block, size_t lds, hipStream_t st, A&&... args) {
+    hipLaunchKernelGGL(kernel, grid, block, lds, st, static_cast<KA>(args)...);
+    return hipGetLastError();
+}
+
+// [r0, r0 + nr) of every block of `blk` rows that covers `n` rows, ascending, given to f(r0, nr); the first non-zero return ends it
+template <class F> int each_block(long long n, long long blk, F f) {
+    for (long long r0 = 0; r0 < n; r0 += blk)
+        if (int rc = f(r0, (int)std::min<long long>(blk, n - r0))) return rc;
+    return 0;
+}
+
+void split_seed(uint64_t seed, uint32_t* lo, uint32_t* hi) {     // the two Philox key words of a spec's seed
+    *lo = (uint32_t)(seed & 0xffffffffu);
+    *hi = (uint32_t)(seed >> 32);
+}
+
 size_t scratch_budget(const char* var) {    // $var bytes, default 1 GiB
     const char* e = std::getenv(var);
     if (e && *e) {
@@ -112,8 +132,12 @@ struct SampleSource {
 template <class Spec> SampleSource source_of(const Spec& s, bool host, const float* eta) {
     return SampleSource{host, s.w, eta, s.n_w, s.multiplicity, s.replicas, s.n_replicas, s.step0, s.nsteps, s.thin};
 }
-// the checks that need no handle; `unit` names a host item in the message
-int check_source(const SampleSource& src, const char* unit) {
+// The checks that need no handle; `unit` names a host item in the message.  `required`: the call refuses an empty trace selection
+// without host items as "no source", and `third` names its other host source there, if it has one.
+int check_source(const SampleSource& src, const char* unit, bool required = false, const char* third = nullptr) {
+    if (required && !src.host && src.nsteps < 1)
+        return third ? fail(-1, "no source: nsteps = %d trace rows, and neither host vectors w nor a host %s", src.nsteps, third)
+                     : fail(-1, "no source: nsteps = %d trace rows and no host vectors w", src.nsteps);
     if (src.host) return src.n_w < 1 ? fail(-1, "n_w = %lld host %s: need at least one", (long long)src.n_w, unit) : 0;
     if (src.thin < 1) return fail(-1, "thin = %d must be >= 1", src.thin);
     if (src.replicas && src.n_replicas < 1) return fail(-1, "n_replicas = %d with a replica list", src.n_replicas);
@@ -134,8 +158,35 @@ int count_samples(const ptnn_handle* h, SampleSource& src) {
     src.n_items = src.M = (long long)src.reps.size() * src.m;
     return 0;
 }
-int sample_limit(const SampleSource& src) {
+// Before the handle: the host items of the calls whose host faults precede the handle's; their trace rows are counted in
+// select_samples (host_counted)
+int count_host_samples(SampleSource& src) { return src.host ? count_samples(nullptr, src) : 0; }
+// After the handle: the samples counted -- `host_counted`: the host items already were, before the handle -- at least one, or two
+// where `needs_two` says what for, and within the kernels' int indices
+int select_samples(const ptnn_handle* h, SampleSource& src, bool host_counted, const char* needs_two = nullptr) {
+    if (!(src.host && host_counted))
+        if (int rc = count_samples(h, src)) return rc;
+    if (needs_two && src.M < 2) return fail(-1, "the selection holds %lld samples: %s", src.M, needs_two);
+    if (src.M < 1) return fail(-1, "the selection holds no sample");
     if (src.M > 0x7fffffffLL || src.n_items > 0x7fffffffLL) return fail(-1, "%lld samples: at most 2^31 - 1 per call", src.M);
+    return 0;
+}
+// a regression's likelihood reads tau^2: host vectors come with their eta
+int need_eta(const ptnn_handle* h, const SampleSource& src) {
+    if (src.w && !src.eta && h->cfg.task == PTNN_TASK_REG) return fail(-1, "a regression's host vectors need eta = log tau^2 (one per vector)");
+    return 0;
+}
+
+// PSIS: the relative efficiency of the draws, and the tail length of S of them
+int check_r_eff(double r_eff) {
+    if (!(r_eff > 0.0) || !std::isfinite(r_eff)) return fail(-1, "r_eff = %g must be a finite number > 0", r_eff);
+    return 0;
+}
+int psis_tail(long long S, double r_eff, long long* M) {
+    *M = (long long)std::ceil(std::min(0.2 * (double)S, 3.0 * std::sqrt((double)S / r_eff)));
+    if (*M > ELPD_TAIL_CAP)
+        return fail(-1, "%lld samples with r_eff = %g need a PSIS tail of M = %lld > %d samples: select fewer samples (thin=, chains=) "
+                        "or give a larger r_eff", S, r_eff, *M, ELPD_TAIL_CAP);
     return 0;
 }
 
@@ -191,17 +242,11 @@ int distinct_samples(ptnn_handle* h, DeviceScratch& mem, const SampleSource& src
     }
     d->base = sel.pos_w;
     const unsigned item_blocks = (unsigned)((n + PRED_THREADS - 1) / PRED_THREADS);
-    hipLaunchKernelGGL(sample_runs_kernel, dim3(item_blocks), dim3(PRED_THREADS), 0, st, sel);
-    HIP_TRY(hipGetLastError());
+    HIP_TRY(launch(sample_runs_kernel, dim3(item_blocks), dim3(PRED_THREADS), 0, st, sel));
     if (merge) {
         PredictScan sc{n, flag, item_off, weight, d->item_run, d->run_off, d->run_cnt, err};
-        hipLaunchKernelGGL(predict_scan_kernel, dim3(1), dim3(PRED_SCAN_THREADS), 0, st, sc);
-        HIP_TRY(hipGetLastError());
-        if (eta) {
-            hipLaunchKernelGGL(elpd_run_eta_kernel, dim3(item_blocks), dim3(ELPD_THREADS), 0, st, n, (const int*)flag,
-                               (const int*)d->item_run, (const float*)item_eta, d->run_eta);
-            HIP_TRY(hipGetLastError());
-        }
+        HIP_TRY(launch(predict_scan_kernel, dim3(1), dim3(PRED_SCAN_THREADS), 0, st, sc));
+        if (eta) HIP_TRY(launch(elpd_run_eta_kernel, dim3(item_blocks), dim3(ELPD_THREADS), 0, st, n, flag, d->item_run, item_eta, d->run_eta));
     }
     int e[4] = {0, 0, 0, 0};
     HIP_TRY(hipMemcpyAsync(e, err, sizeof e, hipMemcpyDeviceToHost, st));
@@ -293,11 +338,10 @@ struct ForwardPlan {
         return raise_lds_limit(reinterpret_cast<const void*>(h->shape->predict_fwd), lds);
     }
     // fx [nr * O][U] = the outputs of vectors base + run_off[u] on rows [r0, r0 + nr) of x
-    int launch(const ptnn_handle* h, const float* base, const long long* run_off, const float* x, int xs, int r0, int nr, int U, float* fx) const {
+    int run(const ptnn_handle* h, const float* base, const long long* run_off, const float* x, int xs, int r0, int nr, int U, float* fx) const {
         PredictFwd fa{base, run_off, x, xs, r0, nr, h->cfg.n_hidden, h->P, PV, U, NV, fx};
-        hipLaunchKernelGGL(h->shape->predict_fwd, dim3((unsigned)((U + NV - 1) / NV), (unsigned)((nr + WAVE - 1) / WAVE)), dim3(PRED_THREADS), lds,
-                           h->stream, fa);
-        HIP_TRY(hipGetLastError());
+        HIP_TRY(launch(h->shape->predict_fwd, dim3((unsigned)((U + NV - 1) / NV), (unsigned)((nr + WAVE - 1) / WAVE)), dim3(PRED_THREADS), lds,
+                       h->stream, fa));
         return 0;
     }
 };
@@ -322,25 +366,85 @@ struct SensPlan {
         return raise_lds_limit(reinterpret_cast<const void*>(h->shape->sens_fwd), lds);
     }
     // gx [nr * O * I][U] = the input gradients of vectors base + run_off[u] on rows [r0, r0 + nr) of x
-    int launch(const ptnn_handle* h, const float* base, const long long* run_off, const float* x, int xs, int r0, int nr, int U, float* gx) const {
+    int run(const ptnn_handle* h, const float* base, const long long* run_off, const float* x, int xs, int r0, int nr, int U, float* gx) const {
         SensFwd fa{base, run_off, x, xs, r0, nr, h->cfg.n_hidden, h->P, PV, U, NV, VS, gx};
-        hipLaunchKernelGGL(h->shape->sens_fwd, dim3((unsigned)((U + NV - 1) / NV), (unsigned)((nr + WAVE - 1) / WAVE)), dim3(SENS_THREADS), lds,
-                           h->stream, fa);
-        HIP_TRY(hipGetLastError());
+        HIP_TRY(launch(h->shape->sens_fwd, dim3((unsigned)((U + NV - 1) / NV), (unsigned)((nr + WAVE - 1) / WAVE)), dim3(SENS_THREADS), lds,
+                       h->stream, fa));
         return 0;
     }
 };
 
-// the order statistics of predict and forecast: ranks [n_ranks] in the expanded multiset of M samples
-int check_ranks(int n_ranks, const int64_t* ranks, const void* order_stats) {
-    if (n_ranks < 0 || n_ranks > PTNN_PREDICT_MAX_RANKS) return fail(-1, "n_ranks = %d outside [0, %d]", n_ranks, PTNN_PREDICT_MAX_RANKS);
-    if (n_ranks > 0 && !ranks) return fail(-1, "n_ranks = %d but ranks is NULL", n_ranks);
-    if (order_stats && n_ranks == 0) return fail(-1, "order_stats requested without ranks");
+// The order statistics of predict, sensitivity and forecast: ranks [n] in the expanded multiset of M samples, the values of those
+// ranks in every column to the caller's order_stats
+struct RankOutputs {
+    int n;
+    const int64_t* ranks;
+    const void* order_stats;
+    long long* d_ranks = nullptr;
+    float* d_stats = nullptr;           // [n][ncols]
+    int check() const {                 // no handle needed
+        if (n < 0 || n > PTNN_PREDICT_MAX_RANKS) return fail(-1, "n_ranks = %d outside [0, %d]", n, PTNN_PREDICT_MAX_RANKS);
+        if (n > 0 && !ranks) return fail(-1, "n_ranks = %d but ranks is NULL", n);
+        if (order_stats && n == 0) return fail(-1, "order_stats requested without ranks");
+        return 0;
+    }
+    int check_values(long long M) const {
+        for (int k = 0; k < n; ++k)
+            if (ranks[k] < 0 || ranks[k] >= M) return fail(-1, "rank %lld outside [0, %lld)", (long long)ranks[k], M);
+        return 0;
+    }
+    int to_device(DeviceScratch& mem, size_t ncols, hipStream_t st) {
+        if (n == 0) return 0;
+        HIP_TRY(mem.alloc(&d_stats, (size_t)n * ncols));
+        HIP_TRY(mem.upload(&d_ranks, (const long long*)ranks, (size_t)n, st));
+        return 0;
+    }
+};
+
+// The pointwise log-likelihood of ptnn_elpd and ptnn_lfo (one Spec's fields are the other's): trace rows, host vectors (w, eta), or
+// a host loglik [n_w][n_rows].  The argument checks the two share, in three parts, since the order of the refusals is kept and
+// ptnn_lfo has checks of its own between them.
+template <class Spec> int pointwise_source(const Spec& s, const SampleSource& src) {
+    if (s.loglik && s.w) return fail(-1, "give host vectors w or a host loglik, not both");
+    if (int rc = check_r_eff(s.r_eff)) return rc;
+    if (int rc = check_source(src, "samples", true, "loglik")) return rc;
+    if (s.n_rows < 1) return fail(-1, "n_rows = %d must be >= 1", s.n_rows);
     return 0;
 }
-int check_rank_values(int n_ranks, const int64_t* ranks, long long M) {
-    for (int k = 0; k < n_ranks; ++k)
-        if (ranks[k] < 0 || ranks[k] >= M) return fail(-1, "rank %lld outside [0, %lld)", (long long)ranks[k], M);
+template <class Spec> int pointwise_rows(const Spec& s, SampleSource& src, const RowSource& rows) {   // ends with the host samples counted
+    if (!s.loglik)
+        if (int rc = check_rows(rows)) return rc;
+    if (s.loglik && s.loglik_out) return fail(-1, "loglik_out: the log-likelihood is the input of this source");
+    if (int rc = count_host_samples(src)) return rc;
+    if (s.loglik)
+        for (long long k = 0; k < src.n_items * s.n_rows; ++k)
+            if (!std::isfinite(s.loglik[k])) return fail(-1, "loglik[%lld, %lld] = %g is not finite", k / s.n_rows, k % s.n_rows, s.loglik[k]);
+    return 0;
+}
+template <class Spec> int pointwise_fit(const ptnn_handle* h, const Spec& s, const SampleSource& src, const RowSource& rows) {  // with the handle
+    const int I = h->cfg.n_in, O = h->cfg.n_out;
+    if (int rc = need_eta(h, src)) return rc;
+    if (s.loglik) return 0;
+    if (int rc = fit_rows(h, rows)) return rc;
+    if (s.x_source == PTNN_PREDICT_X_HOST && h->cfg.task != PTNN_TASK_REG)
+        for (int n = 0; n < s.n_rows; ++n) {
+            const float yv = s.x[(size_t)n * (I + 1) + I];
+            if (!(yv >= 0.0f) || yv >= (float)O || yv != std::floor(yv))
+                return fail(-1, "class label %g in row %d is not an integer in [0, %d)", (double)yv, n, O);
+        }
+    return 0;
+}
+// the host loglik on the device: every host sample is its own entry of `ra` (repeats need no merging: the reductions depend on the
+// multiset only)
+template <class Spec> int upload_loglik(ptnn_handle* h, DeviceScratch& mem, const Spec& s, long long n_items, ElpdRed* ra) {
+    double* d_ll = nullptr;
+    int* d_cnt = nullptr;
+    HIP_TRY(mem.upload(&d_ll, s.loglik, (size_t)n_items * s.n_rows, h->stream));
+    std::vector<int32_t> ones(s.multiplicity ? 0 : (size_t)n_items, 1);
+    HIP_TRY(mem.upload(&d_cnt, s.multiplicity ? s.multiplicity : ones.data(), (size_t)n_items, h->stream));
+    if (!s.multiplicity)
+        if (int rc = wait_stream(h)) return rc;          // `ones` dies at the end of this function
+    ra->mode = ELPD_HOST; ra->ll = d_ll; ra->ll_stride = s.n_rows; ra->cnt = d_cnt; ra->U = (int)n_items;
     return 0;
 }
 }  // namespace
@@ -354,19 +458,18 @@ int ptnn_predict(ptnn_handle* h, const ptnn_predict_spec* spec) {
     const ptnn_predict_spec& s = *spec;
     SampleSource src = source_of(s, s.w != nullptr, nullptr);
     const RowSource rows{s.x_source, s.x, s.n_rows, "x_source", "PTNN_PREDICT_X", "x", "n_rows"};
+    RankOutputs rk{s.n_ranks, s.ranks, s.order_stats};
     if (int rc = check_source(src, "vectors")) return rc;
     if (int rc = check_rows(rows)) return rc;
     if (s.n_rows < 1) return fail(-1, "n_rows = %d must be >= 1", s.n_rows);
-    if (int rc = check_ranks(s.n_ranks, s.ranks, s.order_stats)) return rc;
+    if (int rc = rk.check()) return rc;
     if (int rc = check_handle(h, "ptnn_predict")) return rc;
     const int I = h->cfg.n_in, O = h->cfg.n_out;
     if (s.vote && h->cfg.task != PTNN_TASK_CLS) return fail(-1, "vote: a regression has no classes");
     if (int rc = fit_rows(h, rows)) return rc;
-    if (int rc = count_samples(h, src)) return rc;
+    if (int rc = select_samples(h, src, false)) return rc;
     const long long M = src.M;
-    if (M < 1) return fail(-1, "the selection holds no sample");
-    if (int rc = sample_limit(src)) return rc;
-    if (int rc = check_rank_values(s.n_ranks, s.ranks, M)) return rc;
+    if (int rc = rk.check_values(M)) return rc;
     if (s.n_samples) *s.n_samples = M;
 
     if (int rc = start_device(h)) return rc;
@@ -381,12 +484,9 @@ int ptnn_predict(ptnn_handle* h, const ptnn_predict_spec* spec) {
     const int U = d.U;
     if (s.n_distinct) *s.n_distinct = U;
     // outputs on the device for every column; votes as integer counts (exact whatever the order)
-    double* d_mean = nullptr; float* d_ostat = nullptr; long long* d_votes = nullptr; long long* d_ranks = nullptr;
+    double* d_mean = nullptr; long long* d_votes = nullptr;
     HIP_TRY(mem.alloc(&d_mean, (size_t)ncols));
-    if (s.n_ranks) {
-        HIP_TRY(mem.alloc(&d_ostat, (size_t)s.n_ranks * ncols));
-        HIP_TRY(mem.upload(&d_ranks, (const long long*)s.ranks, (size_t)s.n_ranks, st));
-    }
+    if (int rc = rk.to_device(mem, (size_t)ncols, st)) return rc;
     if (h->cfg.task == PTNN_TASK_CLS) HIP_TRY(mem.alloc(&d_votes, (size_t)ncols));
     // stage b + c in blocks of rows: fx scratch U x (rows x O) floats under the budget
     const long long rows_blk = row_block(scratch_budget("PTNN_PREDICT_SCRATCH_BYTES"), (size_t)U * sizeof(float) * O, s.n_rows);
@@ -396,18 +496,15 @@ int ptnn_predict(ptnn_handle* h, const ptnn_predict_spec* spec) {
     if (int rc = fwd.init(h, "posterior predictive")) return rc;
     std::vector<int> item_run;
     if (s.samples) if (int rc = item_runs(h, d, src.n_items, &item_run)) return rc;
-    for (long long r0 = 0; r0 < s.n_rows; r0 += rows_blk) {
-        const int nr = (int)std::min<long long>(rows_blk, s.n_rows - r0);
-        if (int rc = fwd.launch(h, d.base, d.run_off, d_x, xs, (int)r0, nr, U, d_fx)) return rc;
-        PredictRed ra{d_fx, d.run_cnt, U, O, (int)r0 * O, ncols, M, s.n_ranks, d_ranks, d_mean, d_ostat, d_votes};
-        hipLaunchKernelGGL(predict_reduce_kernel, dim3((unsigned)(nr * O)), dim3(PRED_THREADS), 0, st, ra);
-        HIP_TRY(hipGetLastError());
-        if (s.samples)
-            if (int rc = scatter_samples(h, d_fx, nr * O, U, item_run, src.weights(), s.samples, (size_t)s.n_rows * O, (size_t)r0 * O)) return rc;
-    }
+    if (int rc = each_block(s.n_rows, rows_blk, [&](long long r0, int nr) -> int {
+        if (int rc = fwd.run(h, d.base, d.run_off, d_x, xs, (int)r0, nr, U, d_fx)) return rc;
+        PredictRed ra{d_fx, d.run_cnt, U, O, (int)r0 * O, ncols, M, s.n_ranks, rk.d_ranks, d_mean, rk.d_stats, d_votes};
+        HIP_TRY(launch(predict_reduce_kernel, dim3((unsigned)(nr * O)), dim3(PRED_THREADS), 0, st, ra));
+        return s.samples ? scatter_samples(h, d_fx, nr * O, U, item_run, src.weights(), s.samples, (size_t)s.n_rows * O, (size_t)r0 * O) : 0;
+    })) return rc;
     std::vector<long long> votes_h(s.vote ? (size_t)ncols : 0);
     HIP_TRY(fetch(s.mean, d_mean, (size_t)ncols, st));
-    HIP_TRY(fetch(s.order_stats, d_ostat, (size_t)s.n_ranks * ncols, st));
+    HIP_TRY(fetch(s.order_stats, rk.d_stats, (size_t)s.n_ranks * ncols, st));
     HIP_TRY(fetch(s.vote ? votes_h.data() : nullptr, d_votes, (size_t)ncols, st));
     if (int rc = wait_stream(h)) return rc;
     if (s.vote)
@@ -422,11 +519,12 @@ int ptnn_sensitivity(ptnn_handle* h, const ptnn_sensitivity_spec* spec) {
     const ptnn_sensitivity_spec& s = *spec;
     SampleSource src = source_of(s, s.w != nullptr, nullptr);
     const RowSource rows{s.x_source, s.x, s.n_rows, "x_source", "PTNN_PREDICT_X", "x", "n_rows"};
+    RankOutputs rk{s.n_ranks, s.ranks, s.order_stats}, rk2{s.n_ranks2, s.ranks2, s.abs_order_stats};
     if (int rc = check_source(src, "vectors")) return rc;
     if (int rc = check_rows(rows)) return rc;
     if (s.n_rows < 1) return fail(-1, "n_rows = %d must be >= 1", s.n_rows);
-    if (int rc = check_ranks(s.n_ranks, s.ranks, s.order_stats)) return rc;
-    if (int rc = check_ranks(s.n_ranks2, s.ranks2, s.abs_order_stats)) return rc;
+    if (int rc = rk.check()) return rc;
+    if (int rc = rk2.check()) return rc;
     if (int rc = check_handle(h, "ptnn_sensitivity")) return rc;
     const int I = h->cfg.n_in, O = h->cfg.n_out, OI = O * I;
     if (int rc = fit_rows(h, rows)) return rc;
@@ -434,12 +532,10 @@ int ptnn_sensitivity(ptnn_handle* h, const ptnn_sensitivity_spec* spec) {
     if (ncols_all > 0x7fffffffLL)
         return fail(-1, "%d rows x %d outputs x %d inputs = %lld columns: at most 2^31 - 1 per call", s.n_rows, O, I, ncols_all);
     const int ncols = (int)ncols_all;
-    if (int rc = count_samples(h, src)) return rc;
+    if (int rc = select_samples(h, src, false)) return rc;
     const long long M = src.M;
-    if (M < 1) return fail(-1, "the selection holds no sample");
-    if (int rc = sample_limit(src)) return rc;
-    if (int rc = check_rank_values(s.n_ranks, s.ranks, M)) return rc;
-    if (int rc = check_rank_values(s.n_ranks2, s.ranks2, M)) return rc;
+    if (int rc = rk.check_values(M)) return rc;
+    if (int rc = rk2.check_values(M)) return rc;
     if (s.n_samples) *s.n_samples = M;
 
     if (int rc = start_device(h)) return rc;
@@ -454,19 +550,13 @@ int ptnn_sensitivity(ptnn_handle* h, const ptnn_sensitivity_spec* spec) {
     if (s.n_distinct) *s.n_distinct = U;
     // outputs on the device for every column; the sign counts as integers (exact whatever the order)
     double *d_mean = nullptr, *d_acc_abs = nullptr, *d_acc_sq = nullptr, *d_abs_mean = nullptr, *d_sq_mean = nullptr, *d_a32_mean = nullptr;
-    float *d_ostat = nullptr, *d_a32 = nullptr, *d_aostat = nullptr;
-    long long *d_pos = nullptr, *d_neg = nullptr, *d_ranks = nullptr, *d_ranks2 = nullptr;
+    float* d_a32 = nullptr;
+    long long *d_pos = nullptr, *d_neg = nullptr;
     HIP_TRY(mem.alloc(&d_mean, (size_t)ncols));
     HIP_TRY(mem.alloc(&d_pos, (size_t)ncols));
     HIP_TRY(mem.alloc(&d_neg, (size_t)ncols));
-    if (s.n_ranks) {
-        HIP_TRY(mem.alloc(&d_ostat, (size_t)s.n_ranks * ncols));
-        HIP_TRY(mem.upload(&d_ranks, (const long long*)s.ranks, (size_t)s.n_ranks, st));
-    }
-    if (s.n_ranks2) {
-        HIP_TRY(mem.alloc(&d_aostat, (size_t)s.n_ranks2 * OI));
-        HIP_TRY(mem.upload(&d_ranks2, (const long long*)s.ranks2, (size_t)s.n_ranks2, st));
-    }
+    if (int rc = rk.to_device(mem, (size_t)ncols, st)) return rc;
+    if (int rc = rk2.to_device(mem, (size_t)OI, st)) return rc;
     // per (o, i) and distinct vector: the row sums of |g| and g^2, carried across the blocks of rows
     HIP_TRY(mem.alloc(&d_acc_abs, (size_t)OI * U));
     HIP_TRY(mem.alloc(&d_acc_sq, (size_t)OI * U));
@@ -485,39 +575,32 @@ int ptnn_sensitivity(ptnn_handle* h, const ptnn_sensitivity_spec* spec) {
     std::vector<int> item_run;
     if (s.samples || s.sample_abs) if (int rc = item_runs(h, d, src.n_items, &item_run)) return rc;
     const dim3 rows_grid((unsigned)((U + PRED_THREADS - 1) / PRED_THREADS), (unsigned)OI);
-    for (long long r0 = 0; r0 < s.n_rows; r0 += rows_blk) {
-        const int nr = (int)std::min<long long>(rows_blk, s.n_rows - r0);
-        if (int rc = fwd.launch(h, d.base, d.run_off, d_x, xs, (int)r0, nr, U, d_gx)) return rc;
-        PredictRed ra{d_gx, d.run_cnt, U, 1, (int)(r0 * OI), ncols, M, s.n_ranks, d_ranks, d_mean, d_ostat, nullptr};
-        hipLaunchKernelGGL(predict_reduce_kernel, dim3((unsigned)(nr * OI)), dim3(PRED_THREADS), 0, st, ra);
-        HIP_TRY(hipGetLastError());
+    if (int rc = each_block(s.n_rows, rows_blk, [&](long long r0, int nr) -> int {
+        if (int rc = fwd.run(h, d.base, d.run_off, d_x, xs, (int)r0, nr, U, d_gx)) return rc;
+        PredictRed ra{d_gx, d.run_cnt, U, 1, (int)(r0 * OI), ncols, M, s.n_ranks, rk.d_ranks, d_mean, rk.d_stats, nullptr};
+        HIP_TRY(launch(predict_reduce_kernel, dim3((unsigned)(nr * OI)), dim3(PRED_THREADS), 0, st, ra));
         SensSign sa{d_gx, d.run_cnt, U, r0 * OI, d_pos, d_neg};
-        hipLaunchKernelGGL(sensitivity_sign_kernel, dim3((unsigned)(nr * OI)), dim3(PRED_THREADS), 0, st, sa);
-        HIP_TRY(hipGetLastError());
+        HIP_TRY(launch(sensitivity_sign_kernel, dim3((unsigned)(nr * OI)), dim3(PRED_THREADS), 0, st, sa));
         SensRows rw{d_gx, U, OI, nr, r0 + nr == s.n_rows ? 1 : 0, (double)s.n_rows, d_acc_abs, d_acc_sq, d_a32};
-        hipLaunchKernelGGL(sensitivity_rows_kernel, rows_grid, dim3(PRED_THREADS), 0, st, rw);
-        HIP_TRY(hipGetLastError());
-        if (s.samples)
-            if (int rc = scatter_samples(h, d_gx, nr * OI, U, item_run, src.weights(), s.samples, (size_t)ncols, (size_t)r0 * OI)) return rc;
-    }
+        HIP_TRY(launch(sensitivity_rows_kernel, rows_grid, dim3(PRED_THREADS), 0, st, rw));
+        return s.samples ? scatter_samples(h, d_gx, nr * OI, U, item_run, src.weights(), s.samples, (size_t)ncols, (size_t)r0 * OI) : 0;
+    })) return rc;
     // the global relevance: weighted means of the row sums (double), exact ranks of the fp32 a_s
     SensMean ma{d_acc_abs, d_acc_sq, d.run_cnt, U, (double)s.n_rows, M, d_abs_mean, d_sq_mean};
-    hipLaunchKernelGGL(sensitivity_mean_kernel, dim3((unsigned)OI), dim3(PRED_THREADS), 0, st, ma);
-    HIP_TRY(hipGetLastError());
+    HIP_TRY(launch(sensitivity_mean_kernel, dim3((unsigned)OI), dim3(PRED_THREADS), 0, st, ma));
     if (s.n_ranks2) {
-        PredictRed ra{d_a32, d.run_cnt, U, 1, 0, OI, M, s.n_ranks2, d_ranks2, d_a32_mean, d_aostat, nullptr};
-        hipLaunchKernelGGL(predict_reduce_kernel, dim3((unsigned)OI), dim3(PRED_THREADS), 0, st, ra);
-        HIP_TRY(hipGetLastError());
+        PredictRed ra{d_a32, d.run_cnt, U, 1, 0, OI, M, s.n_ranks2, rk2.d_ranks, d_a32_mean, rk2.d_stats, nullptr};
+        HIP_TRY(launch(predict_reduce_kernel, dim3((unsigned)OI), dim3(PRED_THREADS), 0, st, ra));
     }
     if (s.sample_abs)
         if (int rc = scatter_samples(h, d_a32, OI, U, item_run, src.weights(), s.sample_abs, (size_t)OI, 0)) return rc;
     HIP_TRY(fetch(s.grad_mean, d_mean, (size_t)ncols, st));
-    HIP_TRY(fetch(s.order_stats, d_ostat, (size_t)s.n_ranks * ncols, st));
+    HIP_TRY(fetch(s.order_stats, rk.d_stats, (size_t)s.n_ranks * ncols, st));
     HIP_TRY(fetch((long long*)s.pos_count, d_pos, (size_t)ncols, st));
     HIP_TRY(fetch((long long*)s.neg_count, d_neg, (size_t)ncols, st));
     HIP_TRY(fetch(s.abs_mean, d_abs_mean, (size_t)OI, st));
     HIP_TRY(fetch(s.sq_mean, d_sq_mean, (size_t)OI, st));
-    HIP_TRY(fetch(s.abs_order_stats, d_aostat, (size_t)s.n_ranks2 * OI, st));
+    HIP_TRY(fetch(s.abs_order_stats, rk2.d_stats, (size_t)s.n_ranks2 * OI, st));
     return wait_stream(h);
 }
 
@@ -525,7 +608,9 @@ int ptnn_sensitivity(ptnn_handle* h, const ptnn_sensitivity_spec* spec) {
 static_assert(PTNN_TR_LIKEH == TR_LIKEH && PTNN_TR_ACC_TE == TR_ACC_TE && PTNN_TR_ACCEPT == TR_ACCEPT && PTNN_TR_SRC == TR_SRC, "ptnn.h TR order");
 
 // split-R-hat / split-ESS of Q quantities over C chains of n draws, gathered by `ga` (its source fields set: trace rows, or
-// draws [C][n][Q] in device memory); outputs are host arrays, any may be null.  Shared by ptnn_convergence and ptnn_evidence.
+// draws [C][n][Q] in device memory); outputs are host arrays, any may be null: an output is computed and copied exactly when its
+// pointer is given, so ess_chain selects the per-chain ESS and every caller gives rho exactly when n_lags > 0 (ptnn_convergence
+// checks it; ptnn_evidence passes neither).  Shared by ptnn_convergence and ptnn_evidence.
 static int conv_drive(ptnn_handle* h, DeviceScratch& mem, ConvGather ga, const std::vector<int>& qcol, int C, int n, int n_lags,
                       double* mean, double* var, double* r_hat, double* ess, int32_t* trunc_lag, double* ess_chain, double* rho) {
     const int hl = n / 2, M = 2 * C, Q = (int)qcol.size();
@@ -573,13 +658,11 @@ static int conv_drive(ptnn_handle* h, DeviceScratch& mem, ConvGather ga, const s
         const int nq = std::min(Qb, Q - q0);
         // 1. gather and moments
         ga.qcol = d_qcol + q0; ga.nq = nq; ga.x = d_x; ga.smean = d_smean; ga.ssq = d_ssq; ga.csum = d_csum; ga.cm2 = d_cm2;
-        hipLaunchKernelGGL(conv_gather_kernel, dim3((unsigned)C, (unsigned)((nq + CONV_TILE - 1) / CONV_TILE)), dim3(CONV_THREADS), 0, st, ga);
-        HIP_TRY(hipGetLastError());
+        HIP_TRY(launch(conv_gather_kernel, dim3((unsigned)C, (unsigned)((nq + CONV_TILE - 1) / CONV_TILE)), dim3(CONV_THREADS), 0, st, ga));
         // 2. W, var+ and the state of every sequence
         ConvMoments mo{d_smean, d_ssq, d_csum, d_cm2, nq, C, n, hl, NS, d_seq, d_pmean, d_pvar};
         const long long nseq = (long long)nq * NS;
-        hipLaunchKernelGGL(conv_moments_kernel, dim3((unsigned)((nseq + CONV_THREADS - 1) / CONV_THREADS)), dim3(CONV_THREADS), 0, st, mo);
-        HIP_TRY(hipGetLastError());
+        HIP_TRY(launch(conv_moments_kernel, dim3((unsigned)((nseq + CONV_THREADS - 1) / CONV_THREADS)), dim3(CONV_THREADS), 0, st, mo));
         HIP_TRY(hipMemsetAsync(d_full, 1, (size_t)nq * sizeof(int), st));             // non-zero: every sequence starts open
         if (per_chain) HIP_TRY(hipMemsetAsync(d_copen, 1, (size_t)nq * C * sizeof(int), st));
         int n_open = nq;
@@ -589,11 +672,10 @@ static int conv_drive(ptnn_handle* h, DeviceScratch& mem, ConvGather ga, const s
         for (int t0 = 0, nl = CONV_LAG_TILE; n_open > 0 && t0 < hl; t0 += nl, nl = std::min(2 * nl, CONV_MAX_LAGS)) {
             nl = std::min(nl, (hl - t0 + CONV_LAG_TILE - 1) / CONV_LAG_TILE * CONV_LAG_TILE);
             ConvLags la{d_x, C, hl, d_open, n_open, d_full, d_copen, t0, d_chain};
-            hipLaunchKernelGGL(conv_lags_kernel, dim3((unsigned)((n_open + CONV_TILE - 1) / CONV_TILE), (unsigned)(nl / CONV_LAG_TILE), (unsigned)C), dim3(CONV_THREADS), 0, st, la);
-            HIP_TRY(hipGetLastError());
+            HIP_TRY(launch(conv_lags_kernel, dim3((unsigned)((n_open + CONV_TILE - 1) / CONV_TILE), (unsigned)(nl / CONV_LAG_TILE), (unsigned)C),
+                           dim3(CONV_THREADS), 0, st, la));
             ConvStep sp{d_chain, d_open, n_open, C, hl, NS, t0, nl, n_lags, Q, q0, d_seq, d_full, d_copen, d_any, d_rho};
-            hipLaunchKernelGGL(conv_step_kernel, dim3((unsigned)n_open), dim3(WAVE), 0, st, sp);
-            HIP_TRY(hipGetLastError());
+            HIP_TRY(launch(conv_step_kernel, dim3((unsigned)n_open), dim3(WAVE), 0, st, sp));
             HIP_TRY(hipMemcpyAsync(any_h.data(), d_any, (size_t)nq * sizeof(int), hipMemcpyDeviceToHost, st));
             if (int rc = wait_stream(h)) return rc;
             const int was_open = n_open;
@@ -605,18 +687,17 @@ static int conv_drive(ptnn_handle* h, DeviceScratch& mem, ConvGather ga, const s
         if (n_open) return fail(-2, "%d quantities still open after every lag (internal error)", n_open);
         // 4. tau, ess, r_hat
         ConvFinish fi{d_seq, d_pmean, d_pvar, nq, NS, C, hl, Q, q0, d_mean, d_var, d_rhat, d_ess, d_essc, d_trunc};
-        hipLaunchKernelGGL(conv_finish_kernel, dim3((unsigned)((nseq + CONV_THREADS - 1) / CONV_THREADS)), dim3(CONV_THREADS), 0, st, fi);
-        HIP_TRY(hipGetLastError());
+        HIP_TRY(launch(conv_finish_kernel, dim3((unsigned)((nseq + CONV_THREADS - 1) / CONV_THREADS)), dim3(CONV_THREADS), 0, st, fi));
     }
     int err = 0;
     HIP_TRY(hipMemcpyAsync(&err, d_error, sizeof(int), hipMemcpyDeviceToHost, st));
-    if (mean) HIP_TRY(hipMemcpyAsync(mean, d_mean, (size_t)Q * sizeof(double), hipMemcpyDeviceToHost, st));
-    if (var) HIP_TRY(hipMemcpyAsync(var, d_var, (size_t)Q * sizeof(double), hipMemcpyDeviceToHost, st));
-    if (r_hat) HIP_TRY(hipMemcpyAsync(r_hat, d_rhat, (size_t)Q * sizeof(double), hipMemcpyDeviceToHost, st));
-    if (ess) HIP_TRY(hipMemcpyAsync(ess, d_ess, (size_t)Q * sizeof(double), hipMemcpyDeviceToHost, st));
-    if (trunc_lag) HIP_TRY(hipMemcpyAsync(trunc_lag, d_trunc, (size_t)Q * sizeof(int32_t), hipMemcpyDeviceToHost, st));
-    if (per_chain) HIP_TRY(hipMemcpyAsync(ess_chain, d_essc, (size_t)C * Q * sizeof(double), hipMemcpyDeviceToHost, st));
-    if (n_lags) HIP_TRY(hipMemcpyAsync(rho, d_rho, (size_t)n_lags * Q * sizeof(double), hipMemcpyDeviceToHost, st));
+    HIP_TRY(fetch(mean, d_mean, (size_t)Q, st));
+    HIP_TRY(fetch(var, d_var, (size_t)Q, st));
+    HIP_TRY(fetch(r_hat, d_rhat, (size_t)Q, st));
+    HIP_TRY(fetch(ess, d_ess, (size_t)Q, st));
+    HIP_TRY(fetch(trunc_lag, d_trunc, (size_t)Q, st));
+    HIP_TRY(fetch(ess_chain, d_essc, (size_t)C * Q, st));
+    HIP_TRY(fetch(rho, d_rho, (size_t)n_lags * Q, st));
     if (int rc = wait_stream(h)) return rc;
     if (err) return fail(-2, "%d selected compact trace rows refer to rows that are not resident (internal error)", err);
     return 0;
@@ -696,45 +777,19 @@ int ptnn_elpd(ptnn_handle* h, const ptnn_elpd_spec* spec) {
     // argument checks first: none of them needs the handle or a device
     if (int rc = check_spec(spec, "ptnn_elpd_spec")) return rc;
     const ptnn_elpd_spec& s = *spec;
-    const bool ll_src = s.loglik != nullptr, host_src = s.w != nullptr;
-    SampleSource src = source_of(s, ll_src || host_src, s.eta);
+    const bool ll_src = s.loglik != nullptr;
+    SampleSource src = source_of(s, ll_src || s.w != nullptr, s.eta);
     const RowSource rows{s.x_source, s.x, s.n_rows, "x_source", "PTNN_PREDICT_X", "x", "n_rows"};
-    if (ll_src && host_src) return fail(-1, "give host vectors w or a host loglik, not both");
-    if (!(s.r_eff > 0.0) || !std::isfinite(s.r_eff)) return fail(-1, "r_eff = %g must be a finite number > 0", s.r_eff);
-    if (!src.host && s.nsteps < 1)
-        return fail(-1, "no source: nsteps = %d trace rows, and neither host vectors w nor a host loglik", s.nsteps);
-    if (int rc = check_source(src, "samples")) return rc;
-    if (s.n_rows < 1) return fail(-1, "n_rows = %d must be >= 1", s.n_rows);
-    if (!ll_src)
-        if (int rc = check_rows(rows)) return rc;
-    if (ll_src && s.loglik_out) return fail(-1, "loglik_out: the log-likelihood is the input of this source");
-    // the sample count of the host sources
-    if (src.host)
-        if (int rc = count_samples(nullptr, src)) return rc;
-    if (ll_src)
-        for (long long k = 0; k < src.n_items * s.n_rows; ++k)
-            if (!std::isfinite(s.loglik[k])) return fail(-1, "loglik[%lld, %lld] = %g is not finite", k / s.n_rows, k % s.n_rows, s.loglik[k]);
+    if (int rc = pointwise_source(s, src)) return rc;
+    if (int rc = pointwise_rows(s, src, rows)) return rc;
     if (int rc = check_handle(h, "ptnn_elpd")) return rc;
     const int I = h->cfg.n_in, O = h->cfg.n_out;
     const bool reg = h->cfg.task == PTNN_TASK_REG;
-    if (host_src && reg && !s.eta) return fail(-1, "a regression's host vectors need eta = log tau^2 (one per vector)");
-    if (!ll_src)
-        if (int rc = fit_rows(h, rows)) return rc;
-    if (!ll_src && s.x_source == PTNN_PREDICT_X_HOST && !reg)
-        for (int n = 0; n < s.n_rows; ++n) {
-            const float yv = s.x[(size_t)n * (I + 1) + I];
-            if (!(yv >= 0.0f) || yv >= (float)O || yv != std::floor(yv))
-                return fail(-1, "class label %g in row %d is not an integer in [0, %d)", (double)yv, n, O);
-        }
-    if (!src.host)
-        if (int rc = count_samples(h, src)) return rc;
+    if (int rc = pointwise_fit(h, s, src, rows)) return rc;
+    if (int rc = select_samples(h, src, true, "p_waic (a variance, ddof 1) needs at least 2")) return rc;
     const long long n_items = src.n_items, S = src.M;
-    if (S < 2) return fail(-1, "the selection holds %lld samples: p_waic (a variance, ddof 1) needs at least 2", S);
-    if (int rc = sample_limit(src)) return rc;
-    const long long M = (long long)std::ceil(std::min(0.2 * (double)S, 3.0 * std::sqrt((double)S / s.r_eff)));
-    if (M > ELPD_TAIL_CAP)
-        return fail(-1, "%lld samples with r_eff = %g need a PSIS tail of M = %lld > %d samples: select fewer samples (thin=, chains=) "
-                        "or give a larger r_eff", S, s.r_eff, M, ELPD_TAIL_CAP);
+    long long M = 0;
+    if (int rc = psis_tail(S, s.r_eff, &M)) return rc;
     if (s.n_samples) *s.n_samples = S;
 
     if (int rc = start_device(h)) return rc;
@@ -761,17 +816,8 @@ int ptnn_elpd(ptnn_handle* h, const ptnn_elpd_spec* spec) {
     };
 
     if (ll_src) {
-        // source 3: every host sample is its own entry (repeats need no merging: the reduction depends on the multiset only)
-        double* d_ll = nullptr;
-        int* d_cnt = nullptr;
-        HIP_TRY(mem.upload(&d_ll, s.loglik, (size_t)n_items * n_rows, st));
-        std::vector<int32_t> ones(s.multiplicity ? 0 : (size_t)n_items, 1);
-        HIP_TRY(mem.upload(&d_cnt, s.multiplicity ? s.multiplicity : ones.data(), (size_t)n_items, st));
-        if (!s.multiplicity)
-            if (int rc = wait_stream(h)) return rc;          // `ones` dies at the end of this block
-        ra.mode = ELPD_HOST; ra.ll = d_ll; ra.ll_stride = n_rows; ra.cnt = d_cnt; ra.U = (int)n_items; ra.row0 = 0;
-        hipLaunchKernelGGL(elpd_reduce_kernel, dim3((unsigned)n_rows), dim3(ELPD_THREADS), 0, st, ra);
-        HIP_TRY(hipGetLastError());
+        if (int rc = upload_loglik(h, mem, s, n_items, &ra)) return rc;
+        HIP_TRY(launch(elpd_reduce_kernel, dim3((unsigned)n_rows), dim3(ELPD_THREADS), 0, st, ra));
         if (s.n_distinct) *s.n_distinct = n_items;
         return copy_out();
     }
@@ -798,19 +844,15 @@ int ptnn_elpd(ptnn_handle* h, const ptnn_elpd_spec* spec) {
     if (s.loglik_out) if (int rc = item_runs(h, d, n_items, &item_run)) return rc;
     ra.mode = reg ? ELPD_REG : ELPD_CLS; ra.fx = d_fx; ra.eta = d.run_eta; ra.y = d_x + I; ra.ys = xs; ra.cnt = d.run_cnt; ra.U = U;
     ra.ll_out = d_llb;
-    for (long long r0 = 0; r0 < n_rows; r0 += rows_blk) {
-        const int nr = (int)std::min<long long>(rows_blk, n_rows - r0);
-        if (int rc = fwd.launch(h, d.base, d.run_off, d_x, xs, (int)r0, nr, U, d_fx)) return rc;
+    if (int rc = each_block(n_rows, rows_blk, [&](long long r0, int nr) -> int {
+        if (int rc = fwd.run(h, d.base, d.run_off, d_x, xs, (int)r0, nr, U, d_fx)) return rc;
         ra.row0 = (int)r0;
-        hipLaunchKernelGGL(elpd_reduce_kernel, dim3((unsigned)nr), dim3(ELPD_THREADS), 0, st, ra);
-        HIP_TRY(hipGetLastError());
-        if (s.loglik_out) {
-            const long long n_ll = (long long)nr * U;
-            hipLaunchKernelGGL(elpd_loglik_kernel, dim3((unsigned)((n_ll + ELPD_THREADS - 1) / ELPD_THREADS)), dim3(ELPD_THREADS), 0, st, ra, nr);
-            HIP_TRY(hipGetLastError());
-            if (int rc = scatter_samples(h, (const double*)d_llb, nr, U, item_run, src.weights(), s.loglik_out, (size_t)n_rows, (size_t)r0)) return rc;
-        }
-    }
+        HIP_TRY(launch(elpd_reduce_kernel, dim3((unsigned)nr), dim3(ELPD_THREADS), 0, st, ra));
+        if (!s.loglik_out) return 0;
+        const long long n_ll = (long long)nr * U;
+        HIP_TRY(launch(elpd_loglik_kernel, dim3((unsigned)((n_ll + ELPD_THREADS - 1) / ELPD_THREADS)), dim3(ELPD_THREADS), 0, st, ra, nr));
+        return scatter_samples(h, d_llb, nr, U, item_run, src.weights(), s.loglik_out, (size_t)n_rows, (size_t)r0);
+    })) return rc;
     return copy_out();
 }
 
@@ -819,15 +861,10 @@ int ptnn_lfo(ptnn_handle* h, const ptnn_lfo_spec* spec) {
     // argument checks first: none of them needs the handle or a device
     if (int rc = check_spec(spec, "ptnn_lfo_spec")) return rc;
     const ptnn_lfo_spec& s = *spec;
-    const bool ll_src = s.loglik != nullptr, host_src = s.w != nullptr;
-    SampleSource src = source_of(s, ll_src || host_src, s.eta);
+    const bool ll_src = s.loglik != nullptr;
+    SampleSource src = source_of(s, ll_src || s.w != nullptr, s.eta);
     const RowSource rows{s.x_source, s.x, s.n_rows, "x_source", "PTNN_PREDICT_X", "x", "n_rows"};
-    if (ll_src && host_src) return fail(-1, "give host vectors w or a host loglik, not both");
-    if (!(s.r_eff > 0.0) || !std::isfinite(s.r_eff)) return fail(-1, "r_eff = %g must be a finite number > 0", s.r_eff);
-    if (!src.host && s.nsteps < 1)
-        return fail(-1, "no source: nsteps = %d trace rows, and neither host vectors w nor a host loglik", s.nsteps);
-    if (int rc = check_source(src, "samples")) return rc;
-    if (s.n_rows < 1) return fail(-1, "n_rows = %d must be >= 1", s.n_rows);
+    if (int rc = pointwise_source(s, src)) return rc;
     if (s.block < 1) return fail(-1, "block = %d must be >= 1", s.block);
     if (s.n_fit < 1 || s.n_fit > s.n_rows)
         return fail(-1, "n_fit = %d outside [1, %d]: the samples are conditioned on rows [0, n_fit) of the %d rows", s.n_fit, s.n_rows, s.n_rows);
@@ -838,35 +875,15 @@ int ptnn_lfo(ptnn_handle* h, const ptnn_lfo_spec* spec) {
         if (i + s.block > s.n_rows)
             return fail(-1, "origin %lld (origins[%d]) with block = %d: i + block > n_rows = %d", i, k, s.block, s.n_rows);
     }
-    if (!ll_src)
-        if (int rc = check_rows(rows)) return rc;
-    if (ll_src && s.loglik_out) return fail(-1, "loglik_out: the log-likelihood is the input of this source");
-    if (src.host)
-        if (int rc = count_samples(nullptr, src)) return rc;
-    if (ll_src)
-        for (long long k = 0; k < src.n_items * s.n_rows; ++k)
-            if (!std::isfinite(s.loglik[k])) return fail(-1, "loglik[%lld, %lld] = %g is not finite", k / s.n_rows, k % s.n_rows, s.loglik[k]);
+    if (int rc = pointwise_rows(s, src, rows)) return rc;
     if (int rc = check_handle(h, "ptnn_lfo")) return rc;
     const int I = h->cfg.n_in, O = h->cfg.n_out;
     const bool reg = h->cfg.task == PTNN_TASK_REG;
-    if (host_src && reg && !s.eta) return fail(-1, "a regression's host vectors need eta = log tau^2 (one per vector)");
-    if (!ll_src)
-        if (int rc = fit_rows(h, rows)) return rc;
-    if (!ll_src && s.x_source == PTNN_PREDICT_X_HOST && !reg)
-        for (int n = 0; n < s.n_rows; ++n) {
-            const float yv = s.x[(size_t)n * (I + 1) + I];
-            if (!(yv >= 0.0f) || yv >= (float)O || yv != std::floor(yv))
-                return fail(-1, "class label %g in row %d is not an integer in [0, %d)", (double)yv, n, O);
-        }
-    if (!src.host)
-        if (int rc = count_samples(h, src)) return rc;
+    if (int rc = pointwise_fit(h, s, src, rows)) return rc;
+    if (int rc = select_samples(h, src, true, "importance weights need at least 2")) return rc;
     const long long n_items = src.n_items, S = src.M;
-    if (S < 2) return fail(-1, "the selection holds %lld samples: importance weights need at least 2", S);
-    if (int rc = sample_limit(src)) return rc;
-    const long long M = (long long)std::ceil(std::min(0.2 * (double)S, 3.0 * std::sqrt((double)S / s.r_eff)));
-    if (M > ELPD_TAIL_CAP)
-        return fail(-1, "%lld samples with r_eff = %g need a PSIS tail of M = %lld > %d samples: select fewer samples (thin=, chains=) "
-                        "or give a larger r_eff", S, s.r_eff, M, ELPD_TAIL_CAP);
+    long long M = 0;
+    if (int rc = psis_tail(S, s.r_eff, &M)) return rc;
     if (s.n_samples) *s.n_samples = S;
 
     if (int rc = start_device(h)) return rc;
@@ -888,15 +905,8 @@ int ptnn_lfo(ptnn_handle* h, const ptnn_lfo_spec* spec) {
     int xs = 0, U = 0;
     Distinct d;
     if (ll_src) {
-        double* d_ll = nullptr;
-        int* d_cnt = nullptr;
-        HIP_TRY(mem.upload(&d_ll, s.loglik, (size_t)n_items * n_rows, st));
-        std::vector<int32_t> ones(s.multiplicity ? 0 : (size_t)n_items, 1);
-        HIP_TRY(mem.upload(&d_cnt, s.multiplicity ? s.multiplicity : ones.data(), (size_t)n_items, st));
-        if (!s.multiplicity)
-            if (int rc = wait_stream(h)) return rc;          // `ones` dies at the end of this block
-        U = (int)n_items;
-        ra.mode = ELPD_HOST; ra.ll = d_ll; ra.ll_stride = n_rows; ra.cnt = d_cnt;
+        if (int rc = upload_loglik(h, mem, s, n_items, &ra)) return rc;
+        U = ra.U;
     } else {
         if (int rc = upload_rows(h, mem, rows, I + 1, &d_x, &xs)) return rc;
         if (int rc = distinct_samples(h, mem, src, true, true, &d)) return rc;
@@ -952,25 +962,20 @@ int ptnn_lfo(ptnn_handle* h, const ptnn_lfo_spec* spec) {
         HIP_TRY(hipMemcpyAsync(d_org_slot, org_slot.data(), (size_t)2 * no * sizeof(int), hipMemcpyHostToDevice, st));
         HIP_TRY(hipMemsetAsync(d_carry, 0, (size_t)U * sizeof(double), st));
         // stage b + c in blocks of rows, ascending
-        for (long long r0 = 0; r0 < n_end; r0 += rows_blk) {
-            const int nr = (int)std::min<long long>(rows_blk, n_end - r0);
+        if (int rc = each_block(n_end, rows_blk, [&](long long r0, int nr) -> int {
             if (!ll_src)
-                if (int rc = fwd.launch(h, d.base, d.run_off, d_x, xs, (int)r0, nr, U, d_fx)) return rc;
+                if (int rc = fwd.run(h, d.base, d.run_off, d_x, xs, (int)r0, nr, U, d_fx)) return rc;
             ra.row0 = (int)r0;
             acc.nrows = nr;
-            hipLaunchKernelGGL(lfo_accum_kernel, dim3(acc_blocks), dim3(ELPD_THREADS), 0, st, acc);
-            HIP_TRY(hipGetLastError());
-            if (s.loglik_out && o0 == 0) {
-                const long long n_ll = (long long)nr * U;
-                hipLaunchKernelGGL(elpd_loglik_kernel, dim3((unsigned)((n_ll + ELPD_THREADS - 1) / ELPD_THREADS)), dim3(ELPD_THREADS), 0, st, ra, nr);
-                HIP_TRY(hipGetLastError());
-                if (int rc = scatter_samples(h, (const double*)d_llb, nr, U, item_run, src.weights(), s.loglik_out, (size_t)n_rows, (size_t)r0)) return rc;
-            }
-        }
+            HIP_TRY(launch(lfo_accum_kernel, dim3(acc_blocks), dim3(ELPD_THREADS), 0, st, acc));
+            if (!(s.loglik_out && o0 == 0)) return 0;
+            const long long n_ll = (long long)nr * U;
+            HIP_TRY(launch(elpd_loglik_kernel, dim3((unsigned)((n_ll + ELPD_THREADS - 1) / ELPD_THREADS)), dim3(ELPD_THREADS), 0, st, ra, nr));
+            return scatter_samples(h, d_llb, nr, U, item_run, src.weights(), s.loglik_out, (size_t)n_rows, (size_t)r0);
+        })) return rc;
         // stage d: one work-group per origin of the pass
         LfoRed lr{d_C, ra.cnt, d_org_slot, fit_slot, U, (int)M, S, d_lfo + o0, d_khat + o0, d_tail + o0};
-        hipLaunchKernelGGL(lfo_reduce_kernel, dim3((unsigned)no), dim3(ELPD_THREADS), LFO_LDS_BYTES, st, lr);
-        HIP_TRY(hipGetLastError());
+        HIP_TRY(launch(lfo_reduce_kernel, dim3((unsigned)no), dim3(ELPD_THREADS), LFO_LDS_BYTES, st, lr));
         if (int rc = wait_stream(h)) return rc;                  // slot_of and org_slot are rewritten by the next pass
     }
     HIP_TRY(fetch(s.elpd_lfo, d_lfo, (size_t)n_org, st));
@@ -987,13 +992,14 @@ int ptnn_forecast(ptnn_handle* h, const ptnn_forecast_spec* spec) {
     const bool host_src = s.w != nullptr, noise = s.noise != 0;
     SampleSource src = source_of(s, host_src, s.eta);
     const RowSource rows{s.origin_source, s.origins, s.n_origins, "origin_source", "PTNN_FORECAST_ORIGIN", "origins", "n_origins"};
+    RankOutputs rk{s.n_ranks, s.ranks, s.order_stats};
     if (int rc = check_source(src, "vectors")) return rc;
     if (int rc = check_rows(rows)) return rc;
     if (s.n_origins < 1) return fail(-1, "n_origins = %d must be >= 1", s.n_origins);
     if (s.horizon < 1) return fail(-1, "horizon = %d must be >= 1", s.horizon);
     const long long ncols = (long long)s.n_origins * s.horizon;
     if (ncols > 0x7fffffffLL) return fail(-1, "%d origins x horizon %d = %lld columns: at most 2^31 - 1 per call", s.n_origins, s.horizon, ncols);
-    if (int rc = check_ranks(s.n_ranks, s.ranks, s.order_stats)) return rc;
+    if (int rc = rk.check()) return rc;
     if (noise && host_src && !s.eta) return fail(-1, "noise: host vectors need eta = log tau^2 (one per vector)");
     if (int rc = check_handle(h, "ptnn_forecast")) return rc;
     if (h->cfg.task != PTNN_TASK_REG || h->cfg.n_out != 1)
@@ -1001,11 +1007,9 @@ int ptnn_forecast(ptnn_handle* h, const ptnn_forecast_spec* spec) {
                         "net with n_out = %d", h->cfg.task == PTNN_TASK_REG ? "regression" : "classification", h->cfg.n_out);
     const int I = h->cfg.n_in, P = h->P, hz = s.horizon;
     if (int rc = fit_rows(h, rows)) return rc;
-    if (int rc = count_samples(h, src)) return rc;
+    if (int rc = select_samples(h, src, false)) return rc;
     const long long M = src.M;
-    if (M < 1) return fail(-1, "the selection holds no sample");
-    if (int rc = sample_limit(src)) return rc;
-    if (int rc = check_rank_values(s.n_ranks, s.ranks, M)) return rc;
+    if (int rc = rk.check_values(M)) return rc;
     if (s.n_samples) *s.n_samples = M;
 
     if (int rc = start_device(h)) return rc;
@@ -1033,12 +1037,9 @@ int ptnn_forecast(ptnn_handle* h, const ptnn_forecast_spec* spec) {
     const int U = d.U;
     if (s.n_trajectories) *s.n_trajectories = U;
     // outputs on the device for every column
-    double* d_mean = nullptr; float* d_ostat = nullptr; long long* d_ranks = nullptr;
+    double* d_mean = nullptr;
     HIP_TRY(mem.alloc(&d_mean, (size_t)ncols));
-    if (s.n_ranks) {
-        HIP_TRY(mem.alloc(&d_ostat, (size_t)s.n_ranks * ncols));
-        HIP_TRY(mem.upload(&d_ranks, (const long long*)s.ranks, (size_t)s.n_ranks, st));
-    }
+    if (int rc = rk.to_device(mem, (size_t)ncols, st)) return rc;
     // stage b + c in blocks of origins and horizon steps: fx 4 U ob hb bytes, + 4 U I bytes of carried windows when the horizon
     // is split (only with one origin per block: the columns of a block are then always contiguous)
     const size_t budget = scratch_budget("PTNN_FORECAST_SCRATCH_BYTES");
@@ -1067,7 +1068,8 @@ int ptnn_forecast(ptnn_handle* h, const ptnn_forecast_spec* spec) {
     ForecastFwd fa{};
     fa.base = d.base; fa.run_off = d.run_off; fa.eta = d.run_eta; fa.x = d_x; fa.xs = xs; fa.horizon = hz; fa.win = d_win;
     fa.H = h->cfg.n_hidden; fa.P = P; fa.U = U; fa.layout = layout; fa.noise = noise ? 1 : 0;
-    fa.seed_lo = (uint32_t)(s.seed & 0xffffffffu); fa.seed_hi = (uint32_t)(s.seed >> 32); fa.fx = d_fx;
+    fa.fx = d_fx;
+    split_seed(s.seed, &fa.seed_lo, &fa.seed_hi);
     for (long long r0 = 0; r0 < s.n_origins; r0 += ob) {
         const int nr = (int)std::min<long long>(ob, s.n_origins - r0);
         for (long long k0 = 0; k0 < hz; k0 += hb) {
@@ -1080,18 +1082,16 @@ int ptnn_forecast(ptnn_handle* h, const ptnn_forecast_spec* spec) {
             } else {
                 grid = dim3((unsigned)U, (unsigned)((nr + WAVE - 1) / WAVE));
             }
-            hipLaunchKernelGGL(h->shape->forecast_fwd, grid, dim3(FC_THREADS), lds, st, fa);
-            HIP_TRY(hipGetLastError());
+            HIP_TRY(launch(h->shape->forecast_fwd, grid, dim3(FC_THREADS), lds, st, fa));
             const long long col0 = r0 * hz + k0;             // the block's columns are contiguous (see above)
-            PredictRed ra{d_fx, d.run_cnt, U, 1, (int)col0, (int)ncols, M, s.n_ranks, d_ranks, d_mean, d_ostat, nullptr};
-            hipLaunchKernelGGL(predict_reduce_kernel, dim3((unsigned)(nr * nk)), dim3(PRED_THREADS), 0, st, ra);
-            HIP_TRY(hipGetLastError());
+            PredictRed ra{d_fx, d.run_cnt, U, 1, (int)col0, (int)ncols, M, s.n_ranks, rk.d_ranks, d_mean, rk.d_stats, nullptr};
+            HIP_TRY(launch(predict_reduce_kernel, dim3((unsigned)(nr * nk)), dim3(PRED_THREADS), 0, st, ra));
             if (s.samples)
                 if (int rc = scatter_samples(h, d_fx, nr * nk, U, item_run, src.weights(), s.samples, (size_t)ncols, (size_t)col0)) return rc;
         }
     }
     HIP_TRY(fetch(s.mean, d_mean, (size_t)ncols, st));
-    HIP_TRY(fetch(s.order_stats, d_ostat, (size_t)s.n_ranks * ncols, st));
+    HIP_TRY(fetch(s.order_stats, rk.d_stats, (size_t)s.n_ranks * ncols, st));
     return wait_stream(h);
 }
 
@@ -1110,8 +1110,7 @@ int ptnn_evidence(ptnn_handle* h, const ptnn_evidence_spec* spec) {
         if (s.n_rungs < 1) return fail(-1, "n_rungs = %d must be >= 1", s.n_rungs);
         if (s.n_per_rung < 1) return fail(-1, "n_per_rung = %lld must be >= 1", (long long)s.n_per_rung);
     } else {
-        if (s.nsteps < 1) return fail(-1, "no source: nsteps = %d trace rows, and neither host vectors w nor a host U", s.nsteps);
-        if (int rc = check_source(src, "vectors")) return rc;
+        if (int rc = check_source(src, "vectors", true, "U")) return rc;
     }
     if (s.n_prior < 0) return fail(-1, "n_prior = %lld must be >= 0", (long long)s.n_prior);
     if (s.n_prior > 0x7fffffffLL) return fail(-1, "n_prior = %lld: at most 2^31 - 1 prior draws per call", (long long)s.n_prior);
@@ -1184,15 +1183,13 @@ int ptnn_evidence(ptnn_handle* h, const ptnn_evidence_spec* spec) {
                       double* b_out) -> int {
         HIP_TRY(hipMemsetAsync(acc, 0, (size_t)nv * sizeof(double), st));
         const unsigned ub = (unsigned)((nv + EVID_THREADS - 1) / EVID_THREADS);
-        for (long long r0 = 0; r0 < N; r0 += rows_blk) {
-            const int nr = (int)std::min<long long>(rows_blk, N - r0);
-            if (int rc = fwd.launch(h, base, run_off, d_x, xs, (int)r0, nr, nv, fx)) return rc;
+        if (int rc = each_block(N, rows_blk, [&](long long r0, int nr) -> int {
+            if (int rc = fwd.run(h, base, run_off, d_x, xs, (int)r0, nr, nv, fx)) return rc;
             EvidRows ra{fx, d_x + (size_t)r0 * xs + I, xs, nr, O, nv, reg ? 1 : 0, acc};
-            hipLaunchKernelGGL(evid_rows_kernel, dim3(ub), dim3(EVID_THREADS), 0, st, ra);
-            HIP_TRY(hipGetLastError());
-        }
-        hipLaunchKernelGGL(evid_finish_kernel, dim3(ub), dim3(EVID_THREADS), 0, st, nv, reg ? 1 : 0, N, (const double*)acc, u_out, b_out, d_sse0);
-        HIP_TRY(hipGetLastError());
+            HIP_TRY(launch(evid_rows_kernel, dim3(ub), dim3(EVID_THREADS), 0, st, ra));
+            return 0;
+        })) return rc;
+        HIP_TRY(launch(evid_finish_kernel, dim3(ub), dim3(EVID_THREADS), 0, st, nv, reg ? 1 : 0, N, acc, u_out, b_out, d_sse0));
         return 0;
     };
     auto rows_for = [&](long long nv, size_t avail) { return row_block(avail, (size_t)nv * O * sizeof(float), N); };
@@ -1213,9 +1210,7 @@ int ptnn_evidence(ptnn_handle* h, const ptnn_evidence_spec* spec) {
     if (u_src) {
         double* d_u = nullptr;
         HIP_TRY(mem.upload(&d_u, s.u, (size_t)n_items, st));
-        hipLaunchKernelGGL(evid_expand_kernel, dim3(draw_blocks), dim3(EVID_THREADS), 0, st, n_draws, (const int*)d_item_of,
-                           (const int*)nullptr, (const double*)d_u, d_udraw);
-        HIP_TRY(hipGetLastError());
+        HIP_TRY(launch(evid_expand_kernel, dim3(draw_blocks), dim3(EVID_THREADS), 0, st, n_draws, d_item_of, nullptr, d_u, d_udraw));
     } else {
         // stage a: items -> distinct vectors
         Distinct d;
@@ -1230,9 +1225,7 @@ int ptnn_evidence(ptnn_handle* h, const ptnn_evidence_spec* spec) {
         HIP_TRY(mem.alloc(&d_acc, (size_t)U));
         HIP_TRY(mem.alloc(&d_udist, (size_t)U));
         if (int rc = eval_u(d.base, d.run_off, U, rows_blk, d_fx, d_acc, d_udist, nullptr)) return rc;
-        hipLaunchKernelGGL(evid_expand_kernel, dim3(draw_blocks), dim3(EVID_THREADS), 0, st, n_draws, (const int*)d_item_of,
-                           (const int*)d.item_run, (const double*)d_udist, d_udraw);
-        HIP_TRY(hipGetLastError());
+        HIP_TRY(launch(evid_expand_kernel, dim3(draw_blocks), dim3(EVID_THREADS), 0, st, n_draws, d_item_of, d.item_run, d_udist, d_udraw));
         if (int rc = sse_check()) return rc;
     }
     // stage d: per-rung moments and stones
@@ -1247,8 +1240,7 @@ int ptnn_evidence(ptnn_handle* h, const ptnn_evidence_spec* spec) {
         HIP_TRY(mem.alloc(&d_rv, (size_t)K));
     }
     EvidRung rg{d_udraw, d_off, d_d, d_mean, d_var, d_ls, d_rv};
-    hipLaunchKernelGGL(evid_rung_kernel, dim3((unsigned)K), dim3(EVID_THREADS), 0, st, rg);
-    HIP_TRY(hipGetLastError());
+    HIP_TRY(launch(evid_rung_kernel, dim3((unsigned)K), dim3(EVID_THREADS), 0, st, rg));
     HIP_TRY(fetch(s.u_mean, d_mean, (size_t)K, st));
     HIP_TRY(fetch(s.u_var, d_var, (size_t)K, st));
     HIP_TRY(fetch(s.d ? s.log_stone : nullptr, d_ls, (size_t)K, st));
@@ -1272,9 +1264,8 @@ int ptnn_evidence(ptnn_handle* h, const ptnn_evidence_spec* spec) {
             HIP_TRY(cm.alloc(&d_rung, (size_t)Q));
             HIP_TRY(hipMemcpyAsync(d_rung, rung.data(), (size_t)Q * sizeof(int), hipMemcpyHostToDevice, st));
             HIP_TRY(cm.alloc(&d_draws, (size_t)Q * nk));
-            hipLaunchKernelGGL(evid_conv_kernel, dim3((unsigned)(((long long)Q * nk + EVID_THREADS - 1) / EVID_THREADS)), dim3(EVID_THREADS), 0, st,
-                               Q, (int)nk, (const long long*)d_off, (const int*)d_rung, (const double*)d_udraw, d_draws);
-            HIP_TRY(hipGetLastError());
+            HIP_TRY(launch(evid_conv_kernel, dim3((unsigned)(((long long)Q * nk + EVID_THREADS - 1) / EVID_THREADS)), dim3(EVID_THREADS), 0, st,
+                           Q, (int)nk, d_off, d_rung, d_udraw, d_draws));
             ConvGather ga{};
             ga.host = 1; ga.draws = d_draws; ga.Qh = Q;
             std::vector<double> ess((size_t)Q);
@@ -1300,13 +1291,13 @@ int ptnn_evidence(ptnn_handle* h, const ptnn_evidence_spec* spec) {
     HIP_TRY(mem.alloc(&d_acc, (size_t)nb));
     HIP_TRY(mem.alloc(&d_fx, (size_t)rows_blk * O * nb));
     const float sigma = (float)std::sqrt((double)h->cfg.sigma_squared);
-    const uint32_t slo = (uint32_t)(s.seed & 0xffffffffu), shi = (uint32_t)(s.seed >> 32);
+    uint32_t slo = 0, shi = 0;
+    split_seed(s.seed, &slo, &shi);
     const int nq = (P + 3) / 4;
     for (long long d0 = 0; d0 < NP; d0 += nb) {
         const int b = (int)std::min<long long>(nb, NP - d0);
-        hipLaunchKernelGGL(evid_prior_kernel, dim3((unsigned)(((long long)b * nq + EVID_THREADS - 1) / EVID_THREADS)), dim3(EVID_THREADS), 0, st,
-                           d0, b, P, sigma, slo, shi, d_pw, d_poff);
-        HIP_TRY(hipGetLastError());
+        HIP_TRY(launch(evid_prior_kernel, dim3((unsigned)(((long long)b * nq + EVID_THREADS - 1) / EVID_THREADS)), dim3(EVID_THREADS), 0, st,
+                       d0, b, P, sigma, slo, shi, d_pw, d_poff));
         if (int rc = eval_u(d_pw, d_poff, b, rows_blk, d_fx, d_acc, d_pu + d0, d_pb + d0)) return rc;
     }
     HIP_TRY(mem.alloc(&d_a, (size_t)s.n_a));
@@ -1314,11 +1305,10 @@ int ptnn_evidence(ptnn_handle* h, const ptnn_evidence_spec* spec) {
     double* d_pr = nullptr;
     HIP_TRY(mem.alloc(&d_pr, (size_t)4 * s.n_a));
     EvidPriorRed pr{d_pu, d_pb, NP, d_a, d_pr, d_pr + s.n_a, d_pr + 2 * s.n_a, d_pr + 3 * s.n_a};
-    hipLaunchKernelGGL(evid_prior_reduce_kernel, dim3((unsigned)s.n_a), dim3(EVID_THREADS), 0, st, pr);
-    HIP_TRY(hipGetLastError());
+    HIP_TRY(launch(evid_prior_reduce_kernel, dim3((unsigned)s.n_a), dim3(EVID_THREADS), 0, st, pr));
     std::vector<double> prh((size_t)4 * s.n_a);
     HIP_TRY(hipMemcpyAsync(prh.data(), d_pr, prh.size() * sizeof(double), hipMemcpyDeviceToHost, st));
-    if (s.u_prior_out) HIP_TRY(hipMemcpyAsync(s.u_prior_out, d_pu, (size_t)NP * sizeof(double), hipMemcpyDeviceToHost, st));
+    HIP_TRY(fetch(s.u_prior_out, d_pu, (size_t)NP, st));
     if (int rc = sse_check()) return rc;
     double* outs[4] = {s.prior_log_mean_exp, s.prior_kish_ess, s.prior_u_mean, s.prior_u_var};
     for (int o = 0; o < 4; ++o)
@@ -1333,11 +1323,9 @@ int ptnn_calibration(ptnn_handle* h, const ptnn_calibration_spec* spec) {
     // argument checks first: none of them needs the handle or a device
     if (int rc = check_spec(spec, "ptnn_calibration_spec")) return rc;
     const ptnn_calibration_spec& s = *spec;
-    const bool host_src = s.w != nullptr;
-    SampleSource src = source_of(s, host_src, s.eta);
+    SampleSource src = source_of(s, s.w != nullptr, s.eta);
     const RowSource rows{s.x_source, s.x, s.n_rows, "x_source", "PTNN_PREDICT_X", "x", "n_rows"};
-    if (!src.host && s.nsteps < 1) return fail(-1, "no source: nsteps = %d trace rows and no host vectors w", s.nsteps);
-    if (int rc = check_source(src, "samples")) return rc;
+    if (int rc = check_source(src, "samples", true)) return rc;
     if (s.n_rows < 1) return fail(-1, "n_rows = %d must be >= 1", s.n_rows);
     if (int rc = check_rows(rows)) return rc;
     if (s.n_levels < 0 || s.n_levels > CALIB_MAX_LEVELS) return fail(-1, "n_levels = %d outside [0, %d]", s.n_levels, CALIB_MAX_LEVELS);
@@ -1348,8 +1336,7 @@ int ptnn_calibration(ptnn_handle* h, const ptnn_calibration_spec* spec) {
         if (!(s.levels_p[k] > 0.0 && s.levels_p[k] < 1.0) || !std::isfinite(s.levels_z[k]))
             return fail(-1, "levels_p[%d] = %g (levels_z %g): a quantile level lies in (0, 1)", k, s.levels_p[k], s.levels_z[k]);
     if (s.crps && !s.pair_term) return fail(-1, "crps requested without pair_term");
-    if (src.host)
-        if (int rc = count_samples(nullptr, src)) return rc;
+    if (int rc = count_host_samples(src)) return rc;
     if (int rc = check_handle(h, "ptnn_calibration")) return rc;
     const int I = h->cfg.n_in, O = h->cfg.n_out;
     const bool reg = h->cfg.task == PTNN_TASK_REG;
@@ -1358,13 +1345,10 @@ int ptnn_calibration(ptnn_handle* h, const ptnn_calibration_spec* spec) {
         return fail(-1, "pit, crps, pred_mean, pred_sd and quantiles need a regression net with n_out == 1; this handle is a %s net "
                         "with n_out = %d", reg ? "regression" : "classification", O);
     if (s.p_mean && reg) return fail(-1, "p_mean: a regression has no class probabilities");
-    if (host_src && reg && !s.eta) return fail(-1, "a regression's host vectors need eta = log tau^2 (one per vector)");
+    if (int rc = need_eta(h, src)) return rc;
     if (int rc = fit_rows(h, rows)) return rc;
-    if (!src.host)
-        if (int rc = count_samples(h, src)) return rc;
+    if (int rc = select_samples(h, src, true)) return rc;
     const long long S = src.M;
-    if (S < 1) return fail(-1, "the selection holds no sample");
-    if (int rc = sample_limit(src)) return rc;
     if (s.n_samples) *s.n_samples = S;
 
     if (int rc = start_device(h)) return rc;
@@ -1391,13 +1375,12 @@ int ptnn_calibration(ptnn_handle* h, const ptnn_calibration_spec* spec) {
     if (!reg) {
         double* d_mean = nullptr;
         HIP_TRY(mem.alloc(&d_mean, (size_t)n_rows * O));
-        for (long long r0 = 0; r0 < n_rows; r0 += rows_blk) {
-            const int nr = (int)std::min<long long>(rows_blk, n_rows - r0);
-            if (int rc = fwd.launch(h, d.base, d.run_off, d_x, xs, (int)r0, nr, U, d_fx)) return rc;
+        if (int rc = each_block(n_rows, rows_blk, [&](long long r0, int nr) -> int {
+            if (int rc = fwd.run(h, d.base, d.run_off, d_x, xs, (int)r0, nr, U, d_fx)) return rc;
             PredictRed ra{d_fx, d.run_cnt, U, O, (int)r0 * O, n_rows * O, S, 0, nullptr, d_mean, nullptr, nullptr};
-            hipLaunchKernelGGL(predict_reduce_kernel, dim3((unsigned)(nr * O)), dim3(PRED_THREADS), 0, st, ra);
-            HIP_TRY(hipGetLastError());
-        }
+            HIP_TRY(launch(predict_reduce_kernel, dim3((unsigned)(nr * O)), dim3(PRED_THREADS), 0, st, ra));
+            return 0;
+        })) return rc;
         HIP_TRY(fetch(s.p_mean, d_mean, (size_t)n_rows * O, st));
         return wait_stream(h);
     }
@@ -1419,9 +1402,8 @@ int ptnn_calibration(ptnn_handle* h, const ptnn_calibration_spec* spec) {
         HIP_TRY(mem.alloc(&d_limbs, (size_t)n_rows * 4));
         HIP_TRY(hipMemsetAsync(d_limbs, 0, (size_t)n_rows * 4 * sizeof(unsigned long long), st));
     }
-    hipLaunchKernelGGL(calib_tau_kernel, dim3((unsigned)((U + CALIB_THREADS - 1) / CALIB_THREADS)), dim3(CALIB_THREADS), 0, st, U,
-                       (const float*)d.run_eta, d_tau2, d_tau, d_itau);
-    HIP_TRY(hipGetLastError());
+    HIP_TRY(launch(calib_tau_kernel, dim3((unsigned)((U + CALIB_THREADS - 1) / CALIB_THREADS)), dim3(CALIB_THREADS), 0, st, U, d.run_eta,
+                   d_tau2, d_tau, d_itau));
     CalibRow ra{};
     ra.fx = d_fx; ra.tau2 = d_tau2; ra.tau = d_tau; ra.itau = d_itau; ra.cnt = d.run_cnt; ra.y = d_x + I; ra.ys = xs; ra.U = U;
     ra.n_rows = n_rows; ra.S = S; ra.n_levels = s.n_levels; ra.pair = s.pair_term ? 1 : 0;
@@ -1430,24 +1412,20 @@ int ptnn_calibration(ptnn_handle* h, const ptnn_calibration_spec* spec) {
     const int n_tiles = (U + CALIB_THREADS - 1) / CALIB_THREADS;
     CalibPair pa{d_fx, d_tau2, d.run_cnt, d_bound, U, 0, 0, n_tiles, d_limbs};
     const unsigned n_tri = (unsigned)((long long)n_tiles * (n_tiles + 1) / 2);
-    for (long long r0 = 0; r0 < n_rows; r0 += rows_blk) {
-        const int nr = (int)std::min<long long>(rows_blk, n_rows - r0);
-        if (int rc = fwd.launch(h, d.base, d.run_off, d_x, xs, (int)r0, nr, U, d_fx)) return rc;
+    if (int rc = each_block(n_rows, rows_blk, [&](long long r0, int nr) -> int {
+        if (int rc = fwd.run(h, d.base, d.run_off, d_x, xs, (int)r0, nr, U, d_fx)) return rc;
         ra.row0 = (int)r0;
-        hipLaunchKernelGGL(calib_row_kernel, dim3((unsigned)nr), dim3(CALIB_THREADS), 0, st, ra);
-        HIP_TRY(hipGetLastError());
+        HIP_TRY(launch(calib_row_kernel, dim3((unsigned)nr), dim3(CALIB_THREADS), 0, st, ra));
         // the pair term of this block's rows, at most 65535 rows (grid.y) per launch
         for (int q0 = 0; s.pair_term && q0 < nr; q0 += 65535) {
             pa.row0 = (int)r0; pa.r0 = q0;
-            hipLaunchKernelGGL(calib_pair_kernel, dim3(n_tri, (unsigned)std::min(65535, nr - q0)), dim3(CALIB_THREADS), 0, st, pa);
-            HIP_TRY(hipGetLastError());
+            HIP_TRY(launch(calib_pair_kernel, dim3(n_tri, (unsigned)std::min(65535, nr - q0)), dim3(CALIB_THREADS), 0, st, pa));
         }
-    }
-    if (s.pair_term) {
-        hipLaunchKernelGGL(calib_finish_kernel, dim3((unsigned)((n_rows + CALIB_THREADS - 1) / CALIB_THREADS)), dim3(CALIB_THREADS), 0, st,
-                           n_rows, (const unsigned long long*)d_limbs, (const double*)d_t1, (const double*)d_bound, S, d_crps);
-        HIP_TRY(hipGetLastError());
-    }
+        return 0;
+    })) return rc;
+    if (s.pair_term)
+        HIP_TRY(launch(calib_finish_kernel, dim3((unsigned)((n_rows + CALIB_THREADS - 1) / CALIB_THREADS)), dim3(CALIB_THREADS), 0, st, n_rows,
+                       d_limbs, d_t1, d_bound, S, d_crps));
     HIP_TRY(fetch(s.pit, d_pit, (size_t)n_rows, st));
     HIP_TRY(fetch(s.pred_mean, d_mean, (size_t)n_rows, st));
     HIP_TRY(fetch(s.pred_sd, d_sd, (size_t)n_rows, st));
@@ -1463,11 +1441,9 @@ int ptnn_ppc(ptnn_handle* h, const ptnn_ppc_spec* spec) {
     // argument checks first: none of them needs the handle or a device
     if (int rc = check_spec(spec, "ptnn_ppc_spec")) return rc;
     const ptnn_ppc_spec& s = *spec;
-    const bool host_src = s.w != nullptr;
-    SampleSource src = source_of(s, host_src, s.eta);
+    SampleSource src = source_of(s, s.w != nullptr, s.eta);
     const RowSource rows{s.x_source, s.x, s.n_rows, "x_source", "PTNN_PREDICT_X", "x", "n_rows"};
-    if (!src.host && s.nsteps < 1) return fail(-1, "no source: nsteps = %d trace rows and no host vectors w", s.nsteps);
-    if (int rc = check_source(src, "samples")) return rc;
+    if (int rc = check_source(src, "samples", true)) return rc;
     if (s.n_rows < 2) return fail(-1, "n_rows = %d: a posterior predictive check needs at least 2 data rows", s.n_rows);
     if (int rc = check_rows(rows)) return rc;
     if (s.n_lags < 0 || s.n_lags > PPC_MAX_LAGS) return fail(-1, "n_lags = %d outside [0, %d]", s.n_lags, PPC_MAX_LAGS);
@@ -1478,8 +1454,7 @@ int ptnn_ppc(ptnn_handle* h, const ptnn_ppc_spec* spec) {
         for (int j = 0; j < k; ++j)
             if (s.lags[j] == s.lags[k]) return fail(-1, "lags[%d] = lags[%d] = %d: a lag may be listed once", j, k, s.lags[k]);
     }
-    if (src.host)
-        if (int rc = count_samples(nullptr, src)) return rc;
+    if (int rc = count_host_samples(src)) return rc;
     if (int rc = check_handle(h, "ptnn_ppc")) return rc;
     const int I = h->cfg.n_in, O = h->cfg.n_out;
     const bool reg = h->cfg.task == PTNN_TASK_REG;
@@ -1487,13 +1462,10 @@ int ptnn_ppc(ptnn_handle* h, const ptnn_ppc_spec* spec) {
     if (!reg && s.n_lags > 0) return fail(-1, "lags: a classification has no residual autocorrelation");
     if (!reg && s.z) return fail(-1, "z: a classification draws classes, not normal deviates");
     if (reg && s.y_rep) return fail(-1, "y_rep: a regression's replicate is f + tau z; request z");
-    if (host_src && reg && !s.eta) return fail(-1, "a regression's host vectors need eta = log tau^2 (one per vector)");
+    if (int rc = need_eta(h, src)) return rc;
     if (int rc = fit_rows(h, rows)) return rc;
-    if (!src.host)
-        if (int rc = count_samples(h, src)) return rc;
+    if (int rc = select_samples(h, src, true)) return rc;
     const long long M = src.M;
-    if (M < 1) return fail(-1, "the selection holds no sample");
-    if (int rc = sample_limit(src)) return rc;
     const int N = s.n_rows;
     const int n_stats = reg ? PPC_REG_FIXED + s.n_lags : PPC_CLS_FIXED + O;
     // a wave keeps its series in LDS: N doubles (regression), one counter per class (classification)
@@ -1553,18 +1525,17 @@ int ptnn_ppc(ptnn_handle* h, const ptnn_ppc_spec* spec) {
     ja.n_rows = N; ja.O = O; ja.fx = d_fx; ja.eta = d.run_eta; ja.y = d_x + I; ja.ys = xs;
     ja.n_lags = s.n_lags;
     for (int k = 0; k < s.n_lags; ++k) ja.lags[k] = s.lags[k];
-    ja.seed_lo = (uint32_t)(s.seed & 0xffffffffu); ja.seed_hi = (uint32_t)(s.seed >> 32);
+    split_seed(s.seed, &ja.seed_lo, &ja.seed_hi);
     ja.occ_u = d_occ; ja.n_stats = n_stats; ja.wave_doubles = (int)wave_doubles;
     ja.t_obs = d_tobs; ja.t_rep = d_trep; ja.z = d_z; ja.y_rep = d_yrep;
     for (long long u0 = 0; u0 < U; u0 += vec_blk) {
         const int nu = (int)std::min<long long>(vec_blk, U - u0);
-        if (int rc = fwd.launch(h, d.base, d.run_off + u0, d_x, xs, 0, N, nu, d_fx)) return rc;
+        if (int rc = fwd.run(h, d.base, d.run_off + u0, d_x, xs, 0, N, nu, d_fx)) return rc;
         const long long i0 = std::lower_bound(occ_u.begin(), occ_u.end(), (int)u0) - occ_u.begin();
         const long long i1 = std::lower_bound(occ_u.begin(), occ_u.end(), (int)(u0 + nu)) - occ_u.begin();
         ja.nu = nu; ja.u0 = (int)u0; ja.i0 = i0; ja.n_occ = (int)(i1 - i0);
         const long long jobs = (long long)nu + (i1 - i0);
-        hipLaunchKernelGGL(kernel, dim3((unsigned)((jobs + waves - 1) / waves)), dim3((unsigned)(waves * WAVE)), lds, st, ja);
-        HIP_TRY(hipGetLastError());
+        HIP_TRY(launch(kernel, dim3((unsigned)((jobs + waves - 1) / waves)), dim3((unsigned)(waves * WAVE)), lds, st, ja));
     }
     long long *d_nd = nullptr, *d_ng = nullptr, *d_ne = nullptr;
     double *d_mo = nullptr, *d_mr = nullptr, *d_vr = nullptr;
@@ -1575,8 +1546,7 @@ int ptnn_ppc(ptnn_handle* h, const ptnn_ppc_spec* spec) {
     HIP_TRY(mem.alloc(&d_mr, (size_t)n_stats));
     HIP_TRY(mem.alloc(&d_vr, (size_t)n_stats));
     PpcReduce ra{M, n_stats, d_occ, d_tobs, d_trep, d_nd, d_ng, d_ne, d_mo, d_mr, d_vr};
-    hipLaunchKernelGGL(ppc_reduce_kernel, dim3((unsigned)n_stats), dim3(PPC_THREADS), 0, st, ra);
-    HIP_TRY(hipGetLastError());
+    HIP_TRY(launch(ppc_reduce_kernel, dim3((unsigned)n_stats), dim3(PPC_THREADS), 0, st, ra));
     std::vector<double> tobs_h(s.t_obs ? (size_t)U * n_stats : 0);
     HIP_TRY(fetch((long long*)s.n_defined, d_nd, (size_t)n_stats, st));
     HIP_TRY(fetch((long long*)s.n_greater, d_ng, (size_t)n_stats, st));
@@ -1602,20 +1572,15 @@ static int powerscale_block(ptnn_handle* h, unsigned long long* keys, int nq, in
     hipStream_t st = h->stream;
     const int tile = std::min(npow, PS_SORT_TILE);
     const dim3 tiles((unsigned)(npow / tile), (unsigned)nq);
-    hipLaunchKernelGGL(powerscale_sort_lds_kernel, tiles, dim3(PS_THREADS), 0, st, keys, npow, tile, 2, tile);
-    HIP_TRY(hipGetLastError());
+    HIP_TRY(launch(powerscale_sort_lds_kernel, tiles, dim3(PS_THREADS), 0, st, keys, npow, tile, 2, tile));
     for (int size = 2 * tile; size <= npow; size <<= 1) {
-        for (int stride = size / 2; stride >= tile; stride >>= 1) {
-            hipLaunchKernelGGL(powerscale_sort_step_kernel, dim3((unsigned)((npow / 2 + PS_THREADS - 1) / PS_THREADS), (unsigned)nq),
-                               dim3(PS_THREADS), 0, st, keys, npow, size, stride);
-            HIP_TRY(hipGetLastError());
-        }
-        hipLaunchKernelGGL(powerscale_sort_lds_kernel, tiles, dim3(PS_THREADS), 0, st, keys, npow, tile, size, size);
-        HIP_TRY(hipGetLastError());
+        for (int stride = size / 2; stride >= tile; stride >>= 1)
+            HIP_TRY(launch(powerscale_sort_step_kernel, dim3((unsigned)((npow / 2 + PS_THREADS - 1) / PS_THREADS), (unsigned)nq), dim3(PS_THREADS),
+                           0, st, keys, npow, size, stride));
+        HIP_TRY(launch(powerscale_sort_lds_kernel, tiles, dim3(PS_THREADS), 0, st, keys, npow, tile, size, size));
     }
     da.keys = keys; da.q0 = q0;
-    hipLaunchKernelGGL(powerscale_distance_kernel, dim3((unsigned)nq, 4), dim3(PS_THREADS), 0, st, da);
-    HIP_TRY(hipGetLastError());
+    HIP_TRY(launch(powerscale_distance_kernel, dim3((unsigned)nq, 4), dim3(PS_THREADS), 0, st, da));
     return 0;
 }
 
@@ -1623,40 +1588,32 @@ int ptnn_powerscale(ptnn_handle* h, const ptnn_powerscale_spec* spec) {
     // argument checks first: none of them needs the handle or a device
     if (int rc = check_spec(spec, "ptnn_powerscale_spec")) return rc;
     const ptnn_powerscale_spec& s = *spec;
-    const bool host_src = s.w != nullptr;
-    SampleSource src = source_of(s, host_src, s.eta);
+    SampleSource src = source_of(s, s.w != nullptr, s.eta);
     const RowSource rows{s.x_source, s.x, s.n_rows, "x_source", "PTNN_PREDICT_X", "x", "n_rows"};
     constexpr int all_groups = PTNN_POWERSCALE_WEIGHTS | PTNN_POWERSCALE_ETA | PTNN_POWERSCALE_PREDICTIONS | PTNN_POWERSCALE_LOGLIK;
     const bool g_w = s.groups & PTNN_POWERSCALE_WEIGHTS, g_eta = s.groups & PTNN_POWERSCALE_ETA,
                g_pred = s.groups & PTNN_POWERSCALE_PREDICTIONS, g_ll = s.groups & PTNN_POWERSCALE_LOGLIK;
     if (!(s.delta > 0.0) || !std::isfinite(s.delta)) return fail(-1, "delta = %g must be a finite number > 0", s.delta);
-    if (!(s.r_eff > 0.0) || !std::isfinite(s.r_eff)) return fail(-1, "r_eff = %g must be a finite number > 0", s.r_eff);
+    if (int rc = check_r_eff(s.r_eff)) return rc;
     if (s.groups == 0 || (s.groups & ~all_groups))
         return fail(-1, "groups = 0x%x: choose among PTNN_POWERSCALE_WEIGHTS, _ETA, _PREDICTIONS and _LOGLIK", (unsigned)s.groups);
-    if (!src.host && s.nsteps < 1) return fail(-1, "no source: nsteps = %d trace rows and no host vectors w", s.nsteps);
-    if (int rc = check_source(src, "samples")) return rc;
+    if (int rc = check_source(src, "samples", true)) return rc;
     if (g_pred) {
         if (s.n_rows < 1) return fail(-1, "n_rows = %d must be >= 1", s.n_rows);
         if (int rc = check_rows(rows)) return rc;
     }
-    if (src.host)
-        if (int rc = count_samples(nullptr, src)) return rc;
+    if (int rc = count_host_samples(src)) return rc;
     if (int rc = check_handle(h, "ptnn_powerscale")) return rc;
     const int I = h->cfg.n_in, H = h->cfg.n_hidden, O = h->cfg.n_out, P = h->P, Ntr = h->Ntr;
     const bool reg = h->cfg.task == PTNN_TASK_REG;
     if (g_eta && !reg) return fail(-1, "PTNN_POWERSCALE_ETA: a classification has no eta");
-    if (host_src && reg && !s.eta) return fail(-1, "a regression's host vectors need eta = log tau^2 (one per vector)");
+    if (int rc = need_eta(h, src)) return rc;
     if (g_pred)
         if (int rc = fit_rows(h, rows)) return rc;
-    if (!src.host)
-        if (int rc = count_samples(h, src)) return rc;
+    if (int rc = select_samples(h, src, true, "importance weights need at least 2")) return rc;
     const long long M = src.M;
-    if (M < 2) return fail(-1, "the selection holds %lld samples: importance weights need at least 2", M);
-    if (int rc = sample_limit(src)) return rc;
-    const long long Mt = (long long)std::ceil(std::min(0.2 * (double)M, 3.0 * std::sqrt((double)M / s.r_eff)));
-    if (Mt > ELPD_TAIL_CAP)
-        return fail(-1, "%lld samples with r_eff = %g need a PSIS tail of M = %lld > %d samples: select fewer samples (thin=, chains=) "
-                        "or give a larger r_eff", M, s.r_eff, Mt, ELPD_TAIL_CAP);
+    long long Mt = 0;
+    if (int rc = psis_tail(M, s.r_eff, &Mt)) return rc;
     const long long n_pred = g_pred ? (long long)s.n_rows * O : 0;
     const long long Qll = (g_w ? P : 0) + (g_eta ? 1 : 0) + n_pred + (g_ll ? 1 : 0);
     if (Qll > 0x7fffffffLL) return fail(-1, "%lld quantities: at most 2^31 - 1 per call", Qll);
@@ -1693,25 +1650,21 @@ int ptnn_powerscale(ptnn_handle* h, const ptnn_powerscale_spec* spec) {
         ElpdRed ra{};
         ra.mode = reg ? ELPD_REG : ELPD_CLS; ra.fx = d_fx; ra.eta = d.run_eta; ra.y = h->d_data + I; ra.ys = h->IPY; ra.cnt = d.run_cnt;
         ra.U = U; ra.O = O; ra.ll_out = d_llb;
-        for (long long r0 = 0; r0 < Ntr; r0 += rows_blk) {
-            const int nr = (int)std::min<long long>(rows_blk, Ntr - r0);
-            if (int rc = fwd.launch(h, d.base, d.run_off, h->d_data, h->IPY, (int)r0, nr, U, d_fx)) return rc;
+        if (int rc = each_block(Ntr, rows_blk, [&](long long r0, int nr) -> int {
+            if (int rc = fwd.run(h, d.base, d.run_off, h->d_data, h->IPY, (int)r0, nr, U, d_fx)) return rc;
             ra.row0 = (int)r0;
             const long long n_ll = (long long)nr * U;
-            hipLaunchKernelGGL(elpd_loglik_kernel, dim3((unsigned)((n_ll + ELPD_THREADS - 1) / ELPD_THREADS)), dim3(ELPD_THREADS), 0, st, ra, nr);
-            HIP_TRY(hipGetLastError());
-            hipLaunchKernelGGL(powerscale_loglik_kernel, dim3((unsigned)((U + PS_THREADS - 1) / PS_THREADS)), dim3(PS_THREADS), 0, st,
-                               (const double*)d_llb, nr, U, d_logp);
-            HIP_TRY(hipGetLastError());
-        }
+            HIP_TRY(launch(elpd_loglik_kernel, dim3((unsigned)((n_ll + ELPD_THREADS - 1) / ELPD_THREADS)), dim3(ELPD_THREADS), 0, st, ra, nr));
+            HIP_TRY(launch(powerscale_loglik_kernel, dim3((unsigned)((U + PS_THREADS - 1) / PS_THREADS)), dim3(PS_THREADS), 0, st, d_llb, nr, U, d_logp));
+            return 0;
+        })) return rc;
         if (int rc = wait_stream(h)) return rc;          // `tmp` is released here
     }
     const double sig2 = (double)h->cfg.sigma_squared;
     const double cnt = reg ? (double)(I * H + H + 2) : (double)(I * H + H + O + H * O);
     PsPrior pa{d.base, d.run_off, d.run_eta, U, P, reg ? 1 : 0, -1.0 * (cnt / 2.0) * std::log(sig2), 1.0 / (2.0 * sig2),
                (double)h->cfg.nu_1, (double)h->cfg.nu_2, d_logp + U};
-    hipLaunchKernelGGL(powerscale_prior_kernel, dim3((unsigned)((U + PS_THREADS / WAVE - 1) / (PS_THREADS / WAVE))), dim3(PS_THREADS), 0, st, pa);
-    HIP_TRY(hipGetLastError());
+    HIP_TRY(launch(powerscale_prior_kernel, dim3((unsigned)((U + PS_THREADS / WAVE - 1) / (PS_THREADS / WAVE))), dim3(PS_THREADS), 0, st, pa));
     std::vector<double> logp_h((size_t)2 * U);
     std::vector<int> cnt_h((size_t)U);
     HIP_TRY(hipMemcpyAsync(logp_h.data(), d_logp, logp_h.size() * sizeof(double), hipMemcpyDeviceToHost, st));
@@ -1737,8 +1690,7 @@ int ptnn_powerscale(ptnn_handle* h, const ptnn_powerscale_spec* spec) {
     const double a_plus = 1.0 + s.delta, a_minus = 1.0 / (1.0 + s.delta);
     if (int rc = raise_lds_limit(reinterpret_cast<const void*>(powerscale_smooth_kernel), LFO_LDS_BYTES)) return rc;
     PsSmooth sa{d_logp, d.run_cnt, U, (int)Mt, M, {a_minus - 1.0, a_plus - 1.0}, d_wt, d_tlw, d_tu, d_khat, d_tail, d_live};
-    hipLaunchKernelGGL(powerscale_smooth_kernel, dim3(4), dim3(ELPD_THREADS), LFO_LDS_BYTES, st, sa);
-    HIP_TRY(hipGetLastError());
+    HIP_TRY(launch(powerscale_smooth_kernel, dim3(4), dim3(ELPD_THREADS), LFO_LDS_BYTES, st, sa));
 
     // 3, 4. the quantities in blocks of whole quantities
     int npow = 2;
@@ -1763,17 +1715,15 @@ int ptnn_powerscale(ptnn_handle* h, const ptnn_powerscale_spec* spec) {
     const unsigned key_blocks = (unsigned)((npow + PS_THREADS - 1) / PS_THREADS);
     auto plain = [&](const float* v32, const double* v64, int nq, int q0) -> int {      // quantities that lie [quantity][vector]
         PsKeys ka{v32, v64, d.run_cnt, U, npow, d_keys};
-        hipLaunchKernelGGL(powerscale_keys_kernel, dim3(key_blocks, (unsigned)nq), dim3(PS_THREADS), 0, st, ka);
-        HIP_TRY(hipGetLastError());
+        HIP_TRY(launch(powerscale_keys_kernel, dim3(key_blocks, (unsigned)nq), dim3(PS_THREADS), 0, st, ka));
         return powerscale_block(h, d_keys, nq, npow, da, q0);
     };
     int q_at = 0;
     for (int p0 = 0; g_w && p0 < P; p0 += Qb) {
         const int nq = std::min(Qb, P - p0);
         PsGather ga{d.base, d.run_off, d.run_cnt, U, npow, p0, nq, d_keys};
-        hipLaunchKernelGGL(powerscale_gather_kernel, dim3((unsigned)(npow + PS_GATHER_TILE - 1) / PS_GATHER_TILE,
-                                                          (unsigned)(nq + PS_GATHER_TILE - 1) / PS_GATHER_TILE), dim3(PS_THREADS), 0, st, ga);
-        HIP_TRY(hipGetLastError());
+        HIP_TRY(launch(powerscale_gather_kernel, dim3((unsigned)(npow + PS_GATHER_TILE - 1) / PS_GATHER_TILE,
+                                                      (unsigned)(nq + PS_GATHER_TILE - 1) / PS_GATHER_TILE), dim3(PS_THREADS), 0, st, ga));
         if (int rc = powerscale_block(h, d_keys, nq, npow, da, q_at + p0)) return rc;
     }
     q_at += g_w ? P : 0;
@@ -1785,11 +1735,10 @@ int ptnn_powerscale(ptnn_handle* h, const ptnn_powerscale_spec* spec) {
         const float* d_x = nullptr;
         int xs = 0;
         if (int rc = upload_rows(h, mem, rows, I, &d_x, &xs)) return rc;
-        for (int r0 = 0; r0 < s.n_rows; r0 += rows_q) {
-            const int nr = std::min(rows_q, s.n_rows - r0);
-            if (int rc = fwd.launch(h, d.base, d.run_off, d_x, xs, r0, nr, U, d_fx)) return rc;
-            if (int rc = plain(d_fx, nullptr, nr * O, q_at + r0 * O)) return rc;
-        }
+        if (int rc = each_block(s.n_rows, rows_q, [&](long long r0, int nr) -> int {
+            if (int rc = fwd.run(h, d.base, d.run_off, d_x, xs, (int)r0, nr, U, d_fx)) return rc;
+            return plain(d_fx, nullptr, nr * O, q_at + (int)r0 * O);
+        })) return rc;
         q_at += (int)n_pred;
     }
     if (g_ll)

@@ -1,0 +1,370 @@
+"""The argument checks of the ten posterior analysis calls, characterised (no GPU): every call checks its spec before it looks
+at the handle, so a NULL handle shows which fault a spec is refused for, with which return code and which ptnn_last_error()
+text.  CASES names, per call, faulty specs for every refusal that precedes the handle check -- pairs of simultaneous faults
+included, where the order of the checks decides which one is reported -- and valid specs, which reach the handle check.  One
+refusal is left out: ptnn_evidence's "more than 2^31 - 1 expanded draws" needs 8 GiB of host multiplicities to provoke.
+
+The expected values are tests/golden/analysis_errors.json, with the size and the (offset, size) of every field of the ten spec
+structures.  The file is recorded once, from a library built from the commit BEFORE a change to the analysis calls, never from the
+code under test:
+
+    PTNN_LIBRARY=<parent checkout>/parallel-tempering-neural-net_amd/libptnn.so python tests/test_analysis_errors_cpu.py --record
+"""
+import ctypes as C
+import json
+import math
+import os
+import sys
+
+import numpy as np
+import pytest
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+GOLDEN = os.path.join(ROOT, "tests", "golden", "analysis_errors.json")
+
+HOST, TRAIN = 0, 1                                       # PTNN_PREDICT_X_* / PTNN_FORECAST_ORIGIN_*
+f32 = lambda *shape: np.zeros(shape, np.float32)         # noqa: E731
+f64 = lambda *shape: np.full(shape, -1.0)                # noqa: E731
+i32 = lambda *v: np.array(v, np.int32)                   # noqa: E731
+i64 = lambda *v: np.array(v, np.int64)                   # noqa: E731
+
+
+def _nan_at(a, *idx):
+    a[idx] = math.nan
+    return a
+
+
+# ---- valid specs: the fields of a spec that passes every argument check (struct_bytes is set by the test) ----
+TRACE = dict(nsteps=8, thin=1)                                                     # trace rows of all chains
+ROWS = dict(x_source=TRAIN, n_rows=5)
+PREDICT = dict(TRACE, **ROWS)
+PREDICT_HOST = dict(w=f32(3, 4), n_w=3, x_source=HOST, x=f32(5, 4), n_rows=5)
+CONV = dict(TRACE)
+CONV_HOST = dict(draws=f32(2, 8, 3), n_chains=2, n_draws=8, n_quantities=3)
+ELPD = dict(TRACE, r_eff=1.0, **ROWS)
+ELPD_W = dict(w=f32(3, 4), n_w=3, r_eff=1.0, **ROWS)
+ELPD_LL = dict(loglik=f64(4, 6), n_w=4, n_rows=6, r_eff=1.0)
+LFO_ARGS = dict(n_fit=6, block=1, origins=i32(2, 4), n_origins=2)
+LFO = dict(TRACE, r_eff=1.0, x_source=TRAIN, n_rows=6, **LFO_ARGS)
+LFO_LL = dict(ELPD_LL, **LFO_ARGS)
+FORECAST = dict(TRACE, origin_source=TRAIN, n_origins=3, horizon=2)
+EVID = dict(TRACE)
+EVID_U = dict(u=f64(2, 4), n_rungs=2, n_per_rung=4)
+EVID_W = dict(w=f32(2, 4, 3), n_rungs=2, n_per_rung=4)
+PRIOR = dict(n_prior=10, a=np.array([0.5, 1.0]), n_a=2)
+CALIB = dict(TRACE, **ROWS)
+CALIB_W = dict(w=f32(3, 4), n_w=3, **ROWS)
+LEVELS = dict(n_levels=2, levels_p=np.array([0.1, 0.9]), levels_z=np.array([-1.28, 1.28]), quantiles=f64(2, 5))
+PPC = dict(TRACE, **ROWS)
+PPC_W = dict(w=f32(3, 4), n_w=3, **ROWS)
+PS = dict(TRACE, groups=1 | 4, delta=0.01, r_eff=1.0, **ROWS)
+PS_W = dict(w=f32(3, 4), n_w=3, groups=1 | 4, delta=0.01, r_eff=1.0, **ROWS)
+
+RANK_FAULTS = [
+    ("n_ranks_negative", dict(n_ranks=-1)),
+    ("n_ranks_above_max", dict(n_ranks=17)),
+    ("ranks_null", dict(n_ranks=2)),
+    ("order_stats_without_ranks", dict(order_stats=f32(5))),
+]
+TRACE_FAULTS = [
+    ("thin_zero", dict(thin=0)),
+    ("replica_list_empty", dict(replicas=i32(0), n_replicas=0)),
+]
+ROW_FAULTS = [
+    ("x_source_unknown", dict(x_source=7)),
+    ("x_host_null", dict(x_source=HOST)),
+]
+MULT_NEGATIVE = dict(multiplicity=i32(1, -2, 1))
+
+# (structure, entry point, [(case name, base fields, overriding fields)])
+CASES = {
+    "predict": ("PredictSpec", "ptnn_predict", [
+        ("valid_trace", PREDICT, {}),
+        ("valid_host", PREDICT_HOST, {}),
+        *[(n, PREDICT, f) for n, f in TRACE_FAULTS + ROW_FAULTS + RANK_FAULTS],
+        ("n_w_zero", PREDICT_HOST, dict(n_w=0)),
+        ("n_rows_zero", PREDICT, dict(n_rows=0)),
+        ("thin_zero_and_n_rows_zero", PREDICT, dict(thin=0, n_rows=0)),
+        ("x_source_unknown_and_n_rows_zero", PREDICT, dict(x_source=7, n_rows=0)),
+        ("n_rows_zero_and_n_ranks_negative", PREDICT, dict(n_rows=0, n_ranks=-1)),
+    ]),
+    "sensitivity": ("SensitivitySpec", "ptnn_sensitivity", [
+        ("valid_trace", PREDICT, {}),
+        ("valid_host", PREDICT_HOST, dict(ranks=i64(0, 2), n_ranks=2, ranks2=i64(1), n_ranks2=1)),
+        *[(n, PREDICT, f) for n, f in TRACE_FAULTS + ROW_FAULTS + RANK_FAULTS],
+        ("n_w_zero", PREDICT_HOST, dict(n_w=0)),
+        ("n_rows_zero", PREDICT, dict(n_rows=0)),
+        ("n_ranks2_negative", PREDICT, dict(n_ranks2=-1)),
+        ("n_ranks2_above_max", PREDICT, dict(n_ranks2=17)),
+        ("ranks2_null", PREDICT, dict(n_ranks2=2)),
+        ("abs_order_stats_without_ranks2", PREDICT, dict(abs_order_stats=f32(5))),
+        ("ranks_null_and_n_ranks2_negative", PREDICT, dict(n_ranks=3, n_ranks2=-1)),
+        ("thin_zero_and_x_source_unknown", PREDICT, dict(thin=0, x_source=7)),
+    ]),
+    "convergence": ("ConvergenceSpec", "ptnn_convergence", [
+        ("valid_trace", CONV, dict(scalars=1 | 2, n_lags=2, rho=f64(2, 6))),
+        ("valid_host", CONV_HOST, {}),
+        ("n_chains_zero", CONV_HOST, dict(n_chains=0)),
+        ("n_draws_three", CONV_HOST, dict(n_draws=3)),
+        ("n_quantities_zero", CONV_HOST, dict(n_quantities=0)),
+        ("n_chains_zero_and_n_draws_three", CONV_HOST, dict(n_chains=0, n_draws=3)),
+        *[(n, CONV, f) for n, f in TRACE_FAULTS],
+        ("n_params_negative", CONV, dict(params=i32(0), n_params=-1)),
+        ("scalars_not_a_quantity", CONV, dict(scalars=1 << 5)),
+        ("n_lags_negative", CONV, dict(n_lags=-1)),
+        ("rho_null", CONV, dict(n_lags=2)),
+        ("rho_without_lags", CONV, dict(rho=f64(4))),
+        ("thin_zero_and_n_lags_negative", CONV, dict(thin=0, n_lags=-1)),
+        ("n_quantities_zero_and_rho_null", CONV_HOST, dict(n_quantities=0, n_lags=1)),
+    ]),
+    "elpd": ("ElpdSpec", "ptnn_elpd", [
+        ("valid_trace", ELPD, {}),
+        ("valid_host", ELPD_W, dict(multiplicity=i32(1, 0, 2))),
+        ("valid_loglik", ELPD_LL, dict(x_source=7)),
+        ("w_and_loglik", ELPD_LL, dict(w=f32(4, 3))),
+        ("r_eff_zero", ELPD, dict(r_eff=0.0)),
+        ("r_eff_nan", ELPD, dict(r_eff=math.nan)),
+        ("r_eff_inf", ELPD, dict(r_eff=math.inf)),
+        ("no_source", ELPD, dict(nsteps=0)),
+        *[(n, ELPD, f) for n, f in TRACE_FAULTS + ROW_FAULTS],
+        ("n_w_zero", ELPD_W, dict(n_w=0)),
+        ("n_w_zero_loglik", ELPD_LL, dict(n_w=0)),
+        ("n_rows_zero", ELPD, dict(n_rows=0)),
+        ("loglik_out_with_loglik", ELPD_LL, dict(loglik_out=f64(4, 6))),
+        ("multiplicity_negative", ELPD_W, MULT_NEGATIVE),
+        ("loglik_not_finite", ELPD_LL, dict(loglik=_nan_at(f64(4, 6), 2, 5))),
+        ("loglik_infinite_first_entry", ELPD_LL, dict(loglik=np.full((4, 6), -math.inf))),
+        ("w_and_loglik_and_r_eff_zero", ELPD_LL, dict(w=f32(4, 3), r_eff=0.0)),
+        ("r_eff_zero_and_no_source", ELPD, dict(r_eff=0.0, nsteps=0)),
+        ("no_source_and_thin_zero", ELPD, dict(nsteps=0, thin=0)),
+        ("thin_zero_and_n_rows_zero", ELPD, dict(thin=0, n_rows=0)),
+        ("n_rows_zero_and_x_source_unknown", ELPD, dict(n_rows=0, x_source=7)),
+        ("loglik_out_and_loglik_not_finite", ELPD_LL, dict(loglik_out=f64(4, 6), loglik=_nan_at(f64(4, 6), 0, 0))),
+        ("multiplicity_negative_and_loglik_not_finite", ELPD_LL, dict(multiplicity=i32(1, 1, -1, 1), loglik=_nan_at(f64(4, 6), 0, 0))),
+    ]),
+    "lfo": ("LfoSpec", "ptnn_lfo", [
+        ("valid_trace", LFO, {}),
+        ("valid_host", LFO, dict(w=f32(3, 4), n_w=3, nsteps=0)),
+        ("valid_loglik", LFO_LL, {}),
+        ("w_and_loglik", LFO_LL, dict(w=f32(4, 3))),
+        ("r_eff_zero", LFO, dict(r_eff=0.0)),
+        ("no_source", LFO, dict(nsteps=0)),
+        *[(n, LFO, f) for n, f in TRACE_FAULTS + ROW_FAULTS],
+        ("n_w_zero", LFO_LL, dict(n_w=0)),
+        ("n_rows_zero", LFO, dict(n_rows=0)),
+        ("block_zero", LFO, dict(block=0)),
+        ("n_fit_zero", LFO, dict(n_fit=0)),
+        ("n_fit_above_n_rows", LFO, dict(n_fit=7)),
+        ("n_origins_zero", LFO, dict(n_origins=0)),
+        ("origins_null", LFO, dict(origins=None)),
+        ("origin_zero", LFO, dict(origins=i32(2, 0))),
+        ("origin_at_n_rows", LFO, dict(origins=i32(6, 2))),
+        ("origin_block_past_the_rows", LFO, dict(block=3)),
+        ("loglik_out_with_loglik", LFO_LL, dict(loglik_out=f64(4, 6))),
+        ("multiplicity_negative", LFO_LL, dict(multiplicity=i32(-1, 1, 1, 1))),
+        ("loglik_not_finite", LFO_LL, dict(loglik=_nan_at(f64(4, 6), 3, 1))),
+        ("r_eff_zero_and_block_zero", LFO, dict(r_eff=0.0, block=0)),
+        ("n_rows_zero_and_block_zero", LFO, dict(n_rows=0, block=0)),
+        ("block_zero_and_n_fit_zero", LFO, dict(block=0, n_fit=0)),
+        ("n_fit_zero_and_n_origins_zero", LFO, dict(n_fit=0, n_origins=0)),
+        ("origin_zero_and_x_source_unknown", LFO, dict(origins=i32(0, 2), x_source=7)),
+        ("x_host_null_and_multiplicity_negative", LFO, dict(w=f32(3, 4), n_w=3, x_source=HOST, **MULT_NEGATIVE)),
+    ]),
+    "forecast": ("ForecastSpec", "ptnn_forecast", [
+        ("valid_trace", FORECAST, dict(noise=1)),
+        ("valid_host", FORECAST, dict(w=f32(3, 4), n_w=3, eta=f32(3), noise=1, origin_source=HOST, origins=f32(3, 4))),
+        *[(n, FORECAST, f) for n, f in TRACE_FAULTS + RANK_FAULTS],
+        ("n_w_zero", FORECAST, dict(w=f32(3, 4), n_w=0)),
+        ("origin_source_unknown", FORECAST, dict(origin_source=-1)),
+        ("origins_host_null", FORECAST, dict(origin_source=HOST)),
+        ("n_origins_zero", FORECAST, dict(n_origins=0)),
+        ("horizon_zero", FORECAST, dict(horizon=0)),
+        ("too_many_columns", FORECAST, dict(n_origins=70000, horizon=70000)),
+        ("noise_without_eta", FORECAST, dict(w=f32(3, 4), n_w=3, noise=1)),
+        ("n_origins_zero_and_horizon_zero", FORECAST, dict(n_origins=0, horizon=0)),
+        ("horizon_zero_and_n_ranks_negative", FORECAST, dict(horizon=0, n_ranks=-1)),
+        ("ranks_null_and_noise_without_eta", FORECAST, dict(w=f32(3, 4), n_w=3, noise=1, n_ranks=1)),
+    ]),
+    "evidence": ("EvidenceSpec", "ptnn_evidence", [
+        ("valid_trace", EVID, PRIOR),
+        ("valid_host", EVID_W, dict(multiplicity=np.array([[1, 0, 2, 1], [4, 0, 0, 0]], np.int32))),
+        ("valid_u", EVID_U, dict(multiplicity=np.array([[1, 0, 2, 1], [4, 0, 0, 0]], np.int32), u=_nan_at(f64(2, 4), 1, 2))),
+        ("w_and_u", EVID_U, dict(w=f32(2, 4, 3))),
+        ("n_rungs_zero", EVID_U, dict(n_rungs=0)),
+        ("n_per_rung_zero", EVID_W, dict(n_per_rung=0)),
+        ("no_source", EVID, dict(nsteps=0)),
+        *[(n, EVID, f) for n, f in TRACE_FAULTS],
+        ("n_prior_negative", EVID, dict(n_prior=-1)),
+        ("n_prior_above_int32", EVID, dict(PRIOR, n_prior=1 << 31)),
+        ("n_a_zero", EVID, dict(PRIOR, n_a=0)),
+        ("n_a_above_max", EVID, dict(PRIOR, n_a=5)),
+        ("a_null", EVID, dict(n_prior=10, n_a=2)),
+        ("a_not_finite", EVID, dict(PRIOR, a=np.array([0.5, math.inf]))),
+        ("u_prior_out_without_prior", EVID, dict(u_prior_out=f64(4))),
+        ("u_out_with_u", EVID_U, dict(u_out=f64(8))),
+        ("too_many_host_rows", EVID_W, dict(n_rungs=2, n_per_rung=1 << 30)),
+        ("multiplicity_negative", EVID_U, dict(multiplicity=np.array([[1, 1, 1, 1], [1, -3, 1, 1]], np.int32))),
+        ("u_not_finite", EVID_U, dict(u=_nan_at(f64(2, 4), 1, 2))),
+        ("w_and_u_and_n_rungs_zero", EVID_U, dict(w=f32(2, 4, 3), n_rungs=0)),
+        ("n_rungs_zero_and_n_prior_negative", EVID_U, dict(n_rungs=0, n_prior=-1)),
+        ("no_source_and_thin_zero", EVID, dict(nsteps=0, thin=0)),
+        ("thin_zero_and_n_prior_negative", EVID, dict(thin=0, n_prior=-1)),
+        ("u_out_and_u_not_finite", EVID_U, dict(u_out=f64(8), u=_nan_at(f64(2, 4), 0, 0))),
+    ]),
+    "calibration": ("CalibrationSpec", "ptnn_calibration", [
+        ("valid_trace", CALIB, dict(LEVELS, pair_term=1, crps=f64(5))),
+        ("valid_host", CALIB_W, dict(multiplicity=i32(2, 0, 1))),
+        ("no_source", CALIB, dict(nsteps=0)),
+        *[(n, CALIB, f) for n, f in TRACE_FAULTS + ROW_FAULTS],
+        ("n_w_zero", CALIB_W, dict(n_w=0)),
+        ("n_rows_zero", CALIB, dict(n_rows=0)),
+        ("n_levels_negative", CALIB, dict(n_levels=-1)),
+        ("n_levels_above_max", CALIB, dict(LEVELS, n_levels=17)),
+        ("levels_z_null", CALIB, dict(LEVELS, levels_z=None)),
+        ("quantiles_null", CALIB, dict(LEVELS, quantiles=None)),
+        ("quantiles_without_levels", CALIB, dict(quantiles=f64(5))),
+        ("level_one", CALIB, dict(LEVELS, levels_p=np.array([0.1, 1.0]))),
+        ("level_z_infinite", CALIB, dict(LEVELS, levels_z=np.array([-math.inf, 1.28]))),
+        ("crps_without_pair_term", CALIB, dict(crps=f64(5))),
+        ("multiplicity_negative", CALIB_W, MULT_NEGATIVE),
+        ("no_source_and_n_rows_zero", CALIB, dict(nsteps=0, n_rows=0)),
+        ("n_rows_zero_and_x_source_unknown", CALIB, dict(n_rows=0, x_source=7)),
+        ("x_host_null_and_n_levels_negative", CALIB, dict(x_source=HOST, n_levels=-1)),
+        ("crps_without_pair_term_and_multiplicity_negative", CALIB_W, dict(MULT_NEGATIVE, crps=f64(5))),
+    ]),
+    "ppc": ("PpcSpec", "ptnn_ppc", [
+        ("valid_trace", PPC, dict(lags=i32(1, 4, 2), n_lags=3)),
+        ("valid_host", PPC_W, dict(multiplicity=i32(2, 0, 1))),
+        ("no_source", PPC, dict(nsteps=0)),
+        *[(n, PPC, f) for n, f in TRACE_FAULTS + ROW_FAULTS],
+        ("n_w_zero", PPC_W, dict(n_w=0)),
+        ("n_rows_one", PPC, dict(n_rows=1)),
+        ("n_lags_negative", PPC, dict(n_lags=-1)),
+        ("n_lags_above_max", PPC, dict(n_lags=17, lags=i32(*range(1, 18)))),
+        ("lags_null", PPC, dict(n_lags=2)),
+        ("lag_zero", PPC, dict(lags=i32(1, 0), n_lags=2)),
+        ("lag_at_n_rows", PPC, dict(lags=i32(5, 1), n_lags=2)),
+        ("lag_listed_twice", PPC, dict(lags=i32(1, 2, 1), n_lags=3)),
+        ("multiplicity_negative", PPC_W, MULT_NEGATIVE),
+        ("n_rows_one_and_x_source_unknown", PPC, dict(n_rows=1, x_source=7)),
+        ("lag_listed_twice_and_lag_zero", PPC, dict(lags=i32(2, 2, 0), n_lags=3)),
+        ("lags_null_and_multiplicity_negative", PPC_W, dict(MULT_NEGATIVE, n_lags=1)),
+    ]),
+    "powerscale": ("PowerscaleSpec", "ptnn_powerscale", [
+        ("valid_trace", PS, {}),
+        ("valid_host", PS_W, dict(multiplicity=i32(2, 0, 1))),
+        ("valid_without_predictions", PS, dict(groups=1 | 2 | 8, n_rows=0, x_source=7)),
+        ("delta_zero", PS, dict(delta=0.0)),
+        ("delta_nan", PS, dict(delta=math.nan)),
+        ("r_eff_zero", PS, dict(r_eff=0.0)),
+        ("r_eff_inf", PS, dict(r_eff=math.inf)),
+        ("groups_zero", PS, dict(groups=0)),
+        ("groups_unknown", PS, dict(groups=16)),
+        ("no_source", PS, dict(nsteps=0)),
+        *[(n, PS, f) for n, f in TRACE_FAULTS + ROW_FAULTS],
+        ("n_w_zero", PS_W, dict(n_w=0)),
+        ("n_rows_zero", PS, dict(n_rows=0)),
+        ("multiplicity_negative", PS_W, MULT_NEGATIVE),
+        ("delta_zero_and_r_eff_zero", PS, dict(delta=0.0, r_eff=0.0)),
+        ("r_eff_zero_and_groups_zero", PS, dict(r_eff=0.0, groups=0)),
+        ("groups_zero_and_no_source", PS, dict(groups=0, nsteps=0)),
+        ("thin_zero_and_n_rows_zero", PS, dict(thin=0, n_rows=0)),
+        ("x_source_unknown_and_multiplicity_negative", PS_W, dict(MULT_NEGATIVE, x_source=7)),
+    ]),
+}
+SPEC_FAULTS = ("null_spec", "struct_bytes_zero", "struct_bytes_off_by_one")       # the first check of every call
+POINTER_OF = {np.dtype(np.float32): C.c_float, np.dtype(np.float64): C.c_double, np.dtype(np.int32): C.c_int32,
+              np.dtype(np.int64): C.c_int64}
+
+
+def _lib():
+    sys.path.insert(0, ROOT)
+    import ptnn_amd  # noqa: F401
+    from ptnn_amd import _lib
+    return _lib
+
+
+def _build(cls, base, over):
+    """The structure with struct_bytes and the fields of `base` overridden by `over` -> (spec, the arrays it points to)."""
+    spec, keep, types = cls(), [], dict(cls._fields_)
+    spec.struct_bytes = C.sizeof(cls)
+    for name, v in {**base, **over}.items():
+        if isinstance(v, np.ndarray):
+            assert types[name] == C.POINTER(POINTER_OF[v.dtype]), (name, v.dtype)
+            keep.append(np.ascontiguousarray(v))
+            v = keep[-1].ctypes.data_as(types[name])
+        setattr(spec, name, v)
+    return spec, keep
+
+
+def _refusal(binding, lib, call, case):
+    """(return code, ptnn_last_error() text) of one case with a NULL handle."""
+    cls_name, fn, cases = CASES[call]
+    cls = getattr(binding, cls_name)
+    if case in SPEC_FAULTS:
+        spec, keep = _build(cls, {}, {})
+        spec.struct_bytes = dict(struct_bytes_zero=0, struct_bytes_off_by_one=C.sizeof(cls) + 1).get(case, 0)
+        arg = None if case == "null_spec" else C.byref(spec)
+    else:
+        (base, over), = [(b, o) for n, b, o in cases if n == case]
+        spec, keep = _build(cls, base, over)
+        arg = C.byref(spec)
+    rc = getattr(lib, fn)(None, arg)
+    return [rc, lib.ptnn_last_error().decode()]
+
+
+def _layout(binding):
+    return {cls_name: dict(sizeof=C.sizeof(getattr(binding, cls_name)),
+                           fields={n: [getattr(getattr(binding, cls_name), n).offset, getattr(getattr(binding, cls_name), n).size]
+                                   for n, _ in getattr(binding, cls_name)._fields_})
+            for cls_name, _, _ in CASES.values()}
+
+
+def _case_ids():
+    return [(call, case) for call, (_, _, cases) in CASES.items() for case in SPEC_FAULTS + tuple(n for n, _, _ in cases)]
+
+
+@pytest.fixture(scope="module")
+def binding():
+    import __graft_entry__
+    __graft_entry__.build()
+    return _lib()
+
+
+@pytest.fixture(scope="module")
+def golden():
+    return json.load(open(GOLDEN))
+
+
+def test_case_table_is_the_recorded_one(golden):
+    assert all(len({n for n, _, _ in CASES[call][2]}) == len(CASES[call][2]) for call in CASES)
+    assert {call: sorted(golden["errors"][call]) for call in golden["errors"]} == \
+        {call: sorted(case for c, case in _case_ids() if c == call) for call in CASES}
+
+
+@pytest.mark.parametrize("call, case", _case_ids(), ids=lambda v: v)
+def test_refusal_is_the_recorded_one(binding, golden, call, case):
+    got = _refusal(binding, binding.load_library(), call, case)
+    assert got == golden["errors"][call][case]
+    if case.startswith("valid"):
+        assert got[0] < 0 and "handle" in got[1].lower()                          # every argument check passed: the handle is next
+
+
+def test_structure_layouts_are_the_recorded_ones(binding, golden):
+    assert _layout(binding) == golden["layout"]
+
+
+if __name__ == "__main__":
+    if sys.argv[1:] != ["--record"]:
+        sys.exit("usage: PTNN_LIBRARY=<the parent commit's libptnn.so> python tests/test_analysis_errors_cpu.py --record")
+    if not os.environ.get("PTNN_LIBRARY"):
+        sys.exit("--record reads the library of the parent commit: set PTNN_LIBRARY to it")
+    b = _lib()
+    lb = b.load_library()
+    doc = dict(errors={call: {} for call in CASES}, layout=_layout(b))
+    for call_, case_ in _case_ids():
+        doc["errors"][call_][case_] = _refusal(b, lb, call_, case_)
+    with open(GOLDEN, "w") as f:
+        json.dump(doc, f, indent=1, sort_keys=True)
+        f.write("\n")
+    print(f"{sum(len(v) for v in doc['errors'].values())} cases recorded in {GOLDEN}")
