@@ -656,7 +656,9 @@ int pack_data(const ptnn_handle& h, const float* train, int ntr, const float* te
     const int I = h.cfg.n_in, IPY = h.IPY, Nall = ntr + nte;
     img.ntr = ntr; img.nte = nte;
     std::vector<float>& packed = img.xy;
-    packed.assign((size_t)(Nall + 2) * IPY, 0.0f);                 // two zero rows: look-ahead of the SGD sweep
+    packed.assign((size_t)(Nall + 2 + 4) * IPY, 0.0f);             // two zero rows: look-ahead of the SGD sweep (the kernels copy these
+                                                                   // Nall + 2 rows into LDS); four more for sweep_rows_reg41, whose scalar loads fetch
+                                                                   // the global image in pairs of rows up to row Ntr + 5
     for (int n = 0; n < Nall; ++n) {
         const float* row = (n < ntr) ? train + (size_t)n * ncols : test + (size_t)(n - ntr) * ncols;
         for (int c = 0; c <= I; ++c) packed[(size_t)n * IPY + c] = row[c];
