@@ -841,6 +841,84 @@ typedef struct ptnn_powerscale_spec {
 
 int ptnn_powerscale(ptnn_handle *h, const ptnn_powerscale_spec *spec);
 
+/* ---- prior predictive checks (nothing in the reference: its prior constants are literals nobody looks at) ----
+ * What does the prior imply, before any data is looked at?  (Gabry, Simpson, Vehtari, Betancourt & Gelman 2019.)  Weight
+ * vectors are drawn from the prior w ~ N(0, sigma_squared I), the network is evaluated on the rows, and the drawn functions
+ * are summarised: per row and output over the draws, and per draw over the rows.  DESIGN.md section 22.
+ * Everything is about f, the output ptnn_predict returns (the sigmoid output of a regression, the class probabilities of a
+ * classification): tau^2 has an improper prior (nu_1 = nu_2 = 0), so replicated data y is not defined under the prior.
+ * Draws: draw i (i = draw0 .. draw0 + n_draws - 1) at scale s is w = float32(sqrt(s)) * z_i, z_i[k] = the device's Box-Muller
+ * of component k % 4 of philox4x32_10(k / 4, i, 0, 5, seed): ptnn_evidence's prior vector (philox.prior_weights).  Every
+ * scale uses the same z (common random numbers): curves over the scale are smooth.  n_scales = 0: one scale, the handle's
+ * sigma_squared; else sigma_squared [n_scales], n_scales <= PTNN_PRIOR_MAX_SCALES, every one finite and > 0.  S = the scales.
+ * Rows: x_source _TRAIN / _TEST (with their targets), or _HOST with x [n_rows, n_in + has_target]: has_target != 0 says that
+ * column n_in is the target (a classification's: an integer in [0, n_out)).
+ * Per scale, row and output over the draws: mean (double); the exact order statistics of ranks[] (0-based ranks among the
+ * n_draws values, at most PTNN_PREDICT_MAX_RANKS) -- ptnn_predict's reduction with multiplicity 1, bit for bit; vote (the
+ * share of draws whose argmax is this class; classification); sat_count = the draws with f < eps or f > 1 - eps (compared in
+ * double), eps in (0, 0.5).
+ * Per scale and draw, statistics of the drawn function over the rows, double arithmetic on the fp32 outputs, rows in row order,
+ * centred sums in a second pass.  Regression (n_out == 1), n_stats = 7:
+ *   0 mean, 1 sd (population), 2 min, 3 max, 4 acf1 = sum_{r >= 1} (f_r - m)(f_{r-1} - m) / sum_r (f_r - m)^2,
+ *   5 rmse = sqrt(mean (y - f)^2) (needs the target), 6 saturated = the share of rows with f < eps or f > 1 - eps.
+ * Classification, n_stats = 4 + n_out, arg = the first class of the largest probability:
+ *   0 accuracy = the share of rows with y == arg, 1 log_score = mean of -log p_y (both need the target), 2 confidence = mean of
+ *   max_k p_k, 3 saturated = the share of rows with max_k p_k > 1 - eps, 4 + k class_share[k] = the share of rows with arg == k.
+ * A statistic that needs a target is NaN without one.  T(y), the data's counterpart: 0-4 of the target series (regression),
+ * the label shares 4 + k (classification); NaN for the others and without a target.
+ * Per scale and statistic over the draws: stat_mean, stat_sd (population; two passes, double, a tree fixed by n_draws), the
+ * order statistics of ranks[] of the statistic rounded to fp32, and the integer counts n_defined = the draws whose statistic is
+ * not NaN (the others are left out of everything), n_greater = #{T(f_i) > T(y)}, n_equal = #{T(f_i) == T(y)} (both 0 where
+ * T(y) is NaN).  Shares are counts divided by the same n_rows, so class_share compares as integer counts do.  The caller forms
+ * p = (n_greater + n_equal / 2) / n_defined.
+ * Outputs, any may be NULL: mean, vote [S, n_rows, n_out]; order_stats [S, n_ranks, n_rows, n_out] fp32; sat_count [S, n_rows,
+ * n_out]; t_obs [n_stats]; stat_mean, stat_sd, n_greater, n_equal, n_defined [S, n_stats]; stat_order_stats [S, n_ranks,
+ * n_stats] fp32; t_draw [S, n_draws, n_stats]; samples [S, n_draws, n_rows, n_out] fp32; weights [S, n_draws, P] fp32;
+ * n_stats; n_blocks = the blocks of draws one scale was generated in.  t_draw and samples are transposed on the host: asking
+ * for one costs, per scale, a host copy of its size (samples: the size of the scale's output matrix) and a wait for the stream.
+ * Refused: n_draws < 1; draw0 < 0 or draw0 + n_draws > 2^32 (the Philox counter); n_scales outside [0, PTNN_PRIOR_MAX_SCALES]
+ * or without sigma_squared; a scale that is not finite and > 0; eps outside (0, 0.5); more than PTNN_PREDICT_MAX_RANKS ranks,
+ * a rank outside [0, n_draws); vote on a regression; a regression with n_out != 1; a class label that is no integer in [0,
+ * n_out); 2^31 or more draws or columns; an attached communicator; and a selection whose one-scale output matrix 4 n_rows
+ * n_out n_draws bytes exceeds $PTNN_PRIOR_SCRATCH_BYTES (read per call, default 1 GiB) -- the text names the largest n_draws
+ * that fits: a prior predictive check needs thousands of draws, not millions.
+ * Runs on the handle's stream behind everything queued and returns when done.  The scales run one after another; the vectors
+ * of a scale are generated and evaluated in blocks of draws that take what the budget leaves beside the output matrix (4 P + 8
+ * + 4 n_rows n_out bytes per draw, at least one draw), and every reduction reads the whole matrix: no block size changes a
+ * bit, and draws [0, n) are draws [0, m) followed by draws [m, n) of a call with draw0 = m.  Works as soon as ptnn_set_data
+ * and ptnn_set_state have been called: it needs no trace.  Touches no chain state, tape, counter or trace row. */
+#define PTNN_PRIOR_MAX_SCALES 8
+
+typedef struct ptnn_prior_spec {
+    int32_t struct_bytes;         /* = sizeof(ptnn_prior_spec): ABI guard */
+    int32_t n_scales;             /* 0 = the handle's sigma_squared, else <= PTNN_PRIOR_MAX_SCALES */
+    const double *sigma_squared;  /* [n_scales], each finite and > 0 */
+    int64_t n_draws;              /* >= 1 */
+    int64_t draw0;                /* the first draw's Philox counter: >= 0, draw0 + n_draws <= 2^32 */
+    uint64_t seed;                /* Philox key of the draws */
+    /* rows */
+    int32_t x_source;             /* PTNN_PREDICT_X_HOST | _TRAIN | _TEST */
+    int32_t n_rows;
+    const float *x;               /* [n_rows, n_in + (has_target != 0)] (host rows only) */
+    int32_t has_target;           /* host rows: column n_in is the target */
+    int32_t n_ranks;              /* <= PTNN_PREDICT_MAX_RANKS */
+    const int64_t *ranks;         /* [n_ranks] 0-based ranks among the n_draws values */
+    double eps;                   /* saturation margin, in (0, 0.5) */
+    /* outputs */
+    double *mean;
+    float *order_stats;
+    double *vote;
+    int64_t *sat_count;
+    double *t_obs, *stat_mean, *stat_sd;
+    float *stat_order_stats;
+    int64_t *n_greater, *n_equal, *n_defined;
+    double *t_draw;
+    float *samples, *weights;
+    int64_t *n_stats, *n_blocks;
+} ptnn_prior_spec;
+
+int ptnn_prior_predictive(ptnn_handle *h, const ptnn_prior_spec *spec);
+
 /* the HIP stream (hipStream_t) all of this handle's work is queued on: lets the caller order its collectives after the
  * segment / before the swap kernels on the device instead of synchronising the host */
 int ptnn_stream(ptnn_handle *h, void **hip_stream);

@@ -186,6 +186,27 @@ POWERSCALE_GROUPS = {"weights": 1, "eta": 2, "predictions": 4, "loglik": 8}     
 POWERSCALE_MAX_DISTINCT = 65536
 
 
+class PriorSpec(C.Structure):
+    """ptnn_prior_spec (include/ptnn.h)."""
+    _fields_ = [
+        ("struct_bytes", C.c_int32), ("n_scales", C.c_int32), ("sigma_squared", C.POINTER(C.c_double)),
+        ("n_draws", C.c_int64), ("draw0", C.c_int64), ("seed", C.c_uint64),
+        ("x_source", C.c_int32), ("n_rows", C.c_int32), ("x", C.POINTER(C.c_float)),
+        ("has_target", C.c_int32), ("n_ranks", C.c_int32), ("ranks", C.POINTER(C.c_int64)), ("eps", C.c_double),
+        ("mean", C.POINTER(C.c_double)), ("order_stats", C.POINTER(C.c_float)), ("vote", C.POINTER(C.c_double)),
+        ("sat_count", C.POINTER(C.c_int64)),
+        ("t_obs", C.POINTER(C.c_double)), ("stat_mean", C.POINTER(C.c_double)), ("stat_sd", C.POINTER(C.c_double)),
+        ("stat_order_stats", C.POINTER(C.c_float)),
+        ("n_greater", C.POINTER(C.c_int64)), ("n_equal", C.POINTER(C.c_int64)), ("n_defined", C.POINTER(C.c_int64)),
+        ("t_draw", C.POINTER(C.c_double)), ("samples", C.POINTER(C.c_float)), ("weights", C.POINTER(C.c_float)),
+        ("n_stats", C.POINTER(C.c_int64)), ("n_blocks", C.POINTER(C.c_int64)),
+    ]
+
+
+PRIOR_MAX_SCALES = 8
+PRIOR_REG_STATS, PRIOR_CLS_FIXED = 7, 4       # statistics of a drawn function: a regression's; a classification's before class_share
+
+
 class LadderAdaptSpec(C.Structure):
     """ptnn_ladder_adapt_spec (include/ptnn.h)."""
     _fields_ = [("struct_bytes", C.c_int32), ("rounds", C.c_int32), ("kappa0", C.c_double), ("t0", C.c_double)]
@@ -281,6 +302,7 @@ SYMBOLS = {
     "ptnn_sensitivity": (C.c_int, [C.c_void_p, C.POINTER(SensitivitySpec)]),
     "ptnn_ppc": (C.c_int, [C.c_void_p, C.POINTER(PpcSpec)]),
     "ptnn_powerscale": (C.c_int, [C.c_void_p, C.POINTER(PowerscaleSpec)]),
+    "ptnn_prior_predictive": (C.c_int, [C.c_void_p, C.POINTER(PriorSpec)]),
 }
 
 
@@ -970,6 +992,42 @@ class Sampler:
         self._call(self.lib.ptnn_powerscale, spec, out, counters=("n_samples", "n_distinct", "n_quantities"))
         out["logp"] = out["logp"][:2 * out["n_distinct"]].reshape(2, out["n_distinct"]).copy()
         return out
+
+    def prior_predictive(self, x="train", *, n_draws, sigma_squared=None, draw0=0, seed=0, target=False, ranks=(), eps=0.01,
+                         t_draw=False, samples=False, weights=False):
+        """ptnn_prior_predictive: the network outputs of n_draws weight vectors drawn from the prior N(0, sigma_squared I), at
+        every scale of `sigma_squared` (None = the handle's, else up to 8 values) with the same normal deviates, reduced on the
+        device.  x: "train", "test" or rows [n_rows, n_in] (`target`: [n_rows, n_in + 1], the last column the target).  Draw i has
+        the Philox counter draw0 + i.  -> dict, S = the scales: mean, vote (classification) [S, n_rows, O] float64, order_stats
+        [S, len(ranks), n_rows, O] float32, sat_count [S, n_rows, O] int64 (draws with f < eps or f > 1 - eps); t_obs [n_stats];
+        stat_mean, stat_sd [S, n_stats] float64, stat_order_stats [S, len(ranks), n_stats] float32, n_greater, n_equal, n_defined
+        [S, n_stats] int64; t_draw [S, n_draws, n_stats] float64, samples [S, n_draws, n_rows, O] float32, weights [S, n_draws, P]
+        float32 (each on request, else None); n_stats, n_blocks."""
+        spec, keep = _spec(PriorSpec), []
+        I, O = self.cfg.n_in, self.cfg.n_out
+        self._rows(spec, keep, x, "x", (I + 1, "n_in inputs and the target") if target else (I, "n_in columns"))
+        spec.has_target = 1 if target else 0
+        if sigma_squared is not None:
+            sa = np.ascontiguousarray(sigma_squared, dtype=np.float64).reshape(-1)
+            keep.append(sa)
+            spec.sigma_squared, spec.n_scales = _ptr(sa, C.POINTER(C.c_double)), sa.size
+        S = max(1, spec.n_scales)
+        spec.n_draws, spec.draw0, spec.seed, spec.eps = int(n_draws), int(draw0), int(seed), float(eps)
+        n_rk = _ranks(spec, keep, ranks)
+        n_rows, n, cls = spec.n_rows, max(int(n_draws), 0), self.cfg.task == TASK_CLS
+        n_stats = PRIOR_CLS_FIXED + O if cls else PRIOR_REG_STATS
+        out = dict(mean=np.empty((S, n_rows, O), np.float64), order_stats=np.empty((S, n_rk, n_rows, O), np.float32) if n_rk else None,
+                   vote=np.empty((S, n_rows, O), np.float64) if cls else None, sat_count=np.empty((S, n_rows, O), np.int64),
+                   t_obs=np.empty(n_stats, np.float64), stat_mean=np.empty((S, n_stats), np.float64),
+                   stat_sd=np.empty((S, n_stats), np.float64),
+                   stat_order_stats=np.empty((S, n_rk, n_stats), np.float32) if n_rk else None,
+                   n_greater=np.empty((S, n_stats), np.int64), n_equal=np.empty((S, n_stats), np.int64),
+                   n_defined=np.empty((S, n_stats), np.int64),
+                   t_draw=np.empty((S, n, n_stats), np.float64) if t_draw else None,
+                   samples=np.empty((S, n, n_rows, O), np.float32) if samples else None,
+                   weights=np.empty((S, n, self.P), np.float32) if weights else None)
+        _bind(spec, out)
+        return self._call(self.lib.ptnn_prior_predictive, spec, out, counters=("n_stats", "n_blocks"))
 
     def forecast(self, horizon, origins="test", *, replicas=None, step0=0, nsteps=None, thin=1, w=None, multiplicity=None, eta=None,
                  noise=False, seed=0, ranks=(), mean=True, samples=False):

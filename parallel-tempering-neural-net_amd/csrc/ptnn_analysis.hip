@@ -1,5 +1,5 @@
 // ptnn_analysis.hip -- the posterior analysis calls of libptnn.so: predict, convergence, elpd, lfo, forecast, evidence, calibration, sensitivity, ppc,
-// powerscale, and the sample-selection path they share.  The shape-independent analysis kernels are defined in this object: it includes them.
+// powerscale, prior_predictive, and the sample-selection path they share.  The shape-independent analysis kernels are defined in this object: it includes them.
 #include "ptnn_shapes.hpp"
 namespace ptnn {
 #include "ptnn_dev_select.hpp"               // sample selection (run-length pass over the selected rows) and the per-column predictive reduction
@@ -10,6 +10,7 @@ namespace ptnn {
 #include "ptnn_dev_calibration.hpp"          // calibration: PIT, quantiles and CRPS of the predictive mixture per data row
 #include "ptnn_dev_ppc.hpp"                  // posterior predictive checks: replicated data and test quantities per occurrence
 #include "ptnn_dev_powerscale.hpp"           // power-scaling sensitivity: components, smoothed weights, order per quantity, distances
+#include "ptnn_dev_prior.hpp"                // prior predictive checks: saturation counts, statistics per drawn function and over the draws
 #define PTNN_SENSITIVITY_REDUCTIONS
 #include "ptnn_dev_sensitivity.hpp"          // input sensitivity, second part: sign counts, row sums and their weighted means
 }  // namespace ptnn
@@ -1759,6 +1760,155 @@ int ptnn_powerscale(ptnn_handle* h, const ptnn_powerscale_spec* spec) {
     const double scale = 2.0 * std::log2(a_plus);
     for (int c = 0; s.sens && c < 2; ++c)
         for (int q = 0; q < Q; ++q) s.sens[(size_t)c * Q + q] = (dist_h[(size_t)(2 * c) * Q + q] + dist_h[(size_t)(2 * c + 1) * Q + q]) / scale;
+    return 0;
+}
+
+// ---- prior predictive checks (ptnn_dev_prior.hpp) ----
+static_assert(PTNN_PRIOR_MAX_SCALES == PRIOR_MAX_SCALES, "ptnn.h prior limits");
+
+int ptnn_prior_predictive(ptnn_handle* h, const ptnn_prior_spec* spec) {
+    // argument checks first: none of them needs the handle or a device
+    if (int rc = check_spec(spec, "ptnn_prior_spec")) return rc;
+    const ptnn_prior_spec& s = *spec;
+    const RowSource rows{s.x_source, s.x, s.n_rows, "x_source", "PTNN_PREDICT_X", "x", "n_rows"};
+    RankOutputs rk{s.n_ranks, s.ranks, s.order_stats};
+    if (s.n_draws < 1) return fail(-1, "n_draws = %lld must be >= 1", (long long)s.n_draws);
+    if (s.draw0 < 0 || s.draw0 > (1LL << 32) || s.n_draws > (1LL << 32) - s.draw0)
+        return fail(-1, "draws [%lld, %lld + %lld) outside the Philox counter's [0, 2^32)", (long long)s.draw0, (long long)s.draw0,
+                    (long long)s.n_draws);
+    if (s.n_scales < 0 || s.n_scales > PRIOR_MAX_SCALES) return fail(-1, "n_scales = %d outside [0, %d]", s.n_scales, PRIOR_MAX_SCALES);
+    if (s.n_scales > 0 && !s.sigma_squared) return fail(-1, "n_scales = %d but sigma_squared is NULL", s.n_scales);
+    for (int k = 0; k < s.n_scales; ++k)
+        if (!(s.sigma_squared[k] > 0.0) || !std::isfinite(s.sigma_squared[k]))
+            return fail(-1, "sigma_squared[%d] = %g must be a finite number > 0", k, s.sigma_squared[k]);
+    if (!(s.eps > 0.0 && s.eps < 0.5)) return fail(-1, "eps = %g must lie in (0, 0.5)", s.eps);
+    if (int rc = check_rows(rows)) return rc;
+    if (s.n_rows < 1) return fail(-1, "n_rows = %d must be >= 1", s.n_rows);
+    if (int rc = rk.check()) return rc;
+    if (s.stat_order_stats && s.n_ranks == 0) return fail(-1, "stat_order_stats requested without ranks");
+    if (int rc = check_handle(h, "ptnn_prior_predictive")) return rc;
+    const int I = h->cfg.n_in, O = h->cfg.n_out, P = h->P, N = s.n_rows;
+    const bool reg = h->cfg.task == PTNN_TASK_REG;
+    if (reg && O != 1) return fail(-1, "a regression's prior predictive check needs n_out == 1; this handle has n_out = %d", O);
+    if (s.vote && reg) return fail(-1, "vote: a regression has no classes");
+    if (int rc = fit_rows(h, rows)) return rc;
+    const bool has_y = s.x_source != PTNN_PREDICT_X_HOST || s.has_target != 0;
+    if (s.x_source == PTNN_PREDICT_X_HOST && has_y && !reg)
+        for (int n = 0; n < N; ++n) {
+            const float yv = s.x[(size_t)n * (I + 1) + I];
+            if (!(yv >= 0.0f) || yv >= (float)O || yv != std::floor(yv))
+                return fail(-1, "class label %g in row %d is not an integer in [0, %d)", (double)yv, n, O);
+        }
+    const long long ncols_all = (long long)N * O, ND = s.n_draws;
+    if (ncols_all > 0x7fffffffLL) return fail(-1, "%d rows x %d outputs = %lld columns: at most 2^31 - 1 per call", N, O, ncols_all);
+    const int ncols = (int)ncols_all;
+    const size_t budget = scratch_budget("PTNN_PRIOR_SCRATCH_BYTES");
+    const long long fits = (long long)(budget / ((size_t)ncols * sizeof(float)));
+    if (ND > fits)
+        return fail(-1, "n_draws = %lld: the outputs of one scale, 4 x %d rows x %d outputs x n_draws bytes, exceed the scratch budget of "
+                        "%zu bytes ($PTNN_PRIOR_SCRATCH_BYTES); the largest n_draws that fits is %lld -- a prior predictive check needs "
+                        "thousands of draws, not millions", ND, N, O, budget, fits);
+    if (ND > 0x7fffffffLL) return fail(-1, "%lld draws: at most 2^31 - 1 per call", ND);
+    if (int rc = rk.check_values(ND)) return rc;
+    const int n_stats = reg ? PRIOR_REG_STATS : PRIOR_CLS_FIXED + O;
+    const int S = std::max(1, s.n_scales);
+    if (s.n_stats) *s.n_stats = n_stats;
+
+    if (int rc = start_device(h)) return rc;
+    hipStream_t st = h->stream;
+    DeviceScratch mem;
+    const float* d_x = nullptr;
+    int xs = 0;
+    if (int rc = upload_rows(h, mem, rows, I + (has_y ? 1 : 0), &d_x, &xs)) return rc;
+    const float* d_y = has_y ? d_x + I : nullptr;
+    // blocks of draws: what the budget leaves beside the scale's output matrix, at least one draw; rows in blocks of predict_fwd's grid
+    const long long rows_blk = std::min<long long>(N, 65535LL * WAVE);
+    const size_t per_draw = (size_t)P * sizeof(float) + sizeof(long long) + (size_t)rows_blk * O * sizeof(float);
+    const long long nb = std::max(1LL, std::min<long long>((long long)((budget - (size_t)ncols * ND * sizeof(float)) / per_draw), ND));
+    if (s.n_blocks) *s.n_blocks = (ND + nb - 1) / nb;
+    float *d_fx = nullptr, *d_fxb = nullptr, *d_pw = nullptr, *d_t32 = nullptr, *d_tos = nullptr;
+    long long *d_poff = nullptr, *d_votes = nullptr, *d_sat = nullptr, *d_cnt = nullptr, *d_tranks = nullptr;
+    int* d_ones = nullptr;
+    double *d_mean = nullptr, *d_t = nullptr, *d_tobs = nullptr, *d_tm = nullptr, *d_tmean = nullptr;
+    HIP_TRY(mem.alloc(&d_fx, (size_t)ncols * ND));
+    HIP_TRY(mem.alloc(&d_fxb, (size_t)rows_blk * O * nb));
+    HIP_TRY(mem.alloc(&d_pw, (size_t)nb * P));
+    HIP_TRY(mem.alloc(&d_poff, (size_t)nb));
+    HIP_TRY(mem.alloc(&d_ones, (size_t)ND));
+    HIP_TRY(hipMemsetD32Async(d_ones, 1, (size_t)ND, st));
+    HIP_TRY(mem.alloc(&d_mean, (size_t)ncols));
+    if (int rc = rk.to_device(mem, (size_t)ncols, st)) return rc;
+    if (!reg) HIP_TRY(mem.alloc(&d_votes, (size_t)ncols));
+    HIP_TRY(mem.alloc(&d_sat, (size_t)ncols));
+    HIP_TRY(mem.alloc(&d_t, (size_t)n_stats * ND));
+    HIP_TRY(mem.alloc(&d_t32, (size_t)n_stats * ND));
+    HIP_TRY(mem.alloc(&d_tobs, (size_t)n_stats));
+    HIP_TRY(mem.alloc(&d_tm, (size_t)2 * n_stats));            // stat_mean, stat_sd
+    HIP_TRY(mem.alloc(&d_tmean, (size_t)n_stats));             // predict_reduce_kernel's mean of the fp32 copy: not used
+    HIP_TRY(mem.alloc(&d_cnt, (size_t)3 * n_stats));           // n_greater, n_equal, n_defined
+    if (s.n_ranks) HIP_TRY(mem.alloc(&d_tos, (size_t)s.n_ranks * n_stats));
+    d_tranks = rk.d_ranks;
+    ForwardPlan fwd;
+    if (int rc = fwd.init(h, "prior predictive check")) return rc;
+    uint32_t slo = 0, shi = 0;
+    split_seed(s.seed, &slo, &shi);
+    const int nq = (P + 3) / 4;
+    HIP_TRY(launch(reg ? prior_target_kernel<true> : prior_target_kernel<false>, dim3(1), dim3(WAVE), 0, st, d_y, xs, N, O, d_tobs));
+    HIP_TRY(fetch(s.t_obs, d_tobs, (size_t)n_stats, st));
+    std::vector<int> identity(s.samples || s.t_draw ? (size_t)ND : 0);
+    for (size_t i = 0; i < identity.size(); ++i) identity[i] = (int)i;
+    std::vector<long long> votes_h(s.vote ? (size_t)ncols : 0);
+
+    for (int k = 0; k < S; ++k) {
+        const float sigma = (float)std::sqrt(s.n_scales ? s.sigma_squared[k] : (double)h->cfg.sigma_squared);
+        // stages a, b: the scale's outputs fx [ncols][ND], a block of draws at a time
+        for (long long d0 = 0; d0 < ND; d0 += nb) {
+            const int b = (int)std::min<long long>(nb, ND - d0);
+            HIP_TRY(launch(evid_prior_kernel, dim3((unsigned)(((long long)b * nq + EVID_THREADS - 1) / EVID_THREADS)), dim3(EVID_THREADS), 0, st,
+                           s.draw0 + d0, b, P, sigma, slo, shi, d_pw, d_poff));
+            if (s.weights)
+                HIP_TRY(hipMemcpyAsync(s.weights + ((size_t)k * ND + d0) * P, d_pw, (size_t)b * P * sizeof(float), hipMemcpyDeviceToHost, st));
+            if (int rc = each_block(N, rows_blk, [&](long long r0, int nr) -> int {
+                if (int rc = fwd.run(h, d_pw, d_poff, d_x, xs, (int)r0, nr, b, d_fxb)) return rc;
+                HIP_TRY(hipMemcpy2DAsync(d_fx + (size_t)r0 * O * ND + d0, (size_t)ND * sizeof(float), d_fxb, (size_t)b * sizeof(float),
+                                         (size_t)b * sizeof(float), (size_t)nr * O, hipMemcpyDeviceToDevice, st));
+                return 0;
+            })) return rc;
+        }
+        // stage c: every column over the draws
+        PredictRed ra{d_fx, d_ones, (int)ND, O, 0, ncols, ND, s.n_ranks, rk.d_ranks, d_mean, rk.d_stats, d_votes};
+        HIP_TRY(launch(predict_reduce_kernel, dim3((unsigned)ncols), dim3(PRED_THREADS), 0, st, ra));
+        HIP_TRY(launch(prior_saturation_kernel, dim3((unsigned)ncols), dim3(PRIOR_THREADS), 0, st, d_fx, ND, s.eps, d_sat));
+        // stage d: every draw over the rows; the order statistics of the fp32 copy
+        PriorFn fa{d_fx, ND, N, O, d_y, xs, s.eps, d_t, d_t32};
+        HIP_TRY(launch(reg ? prior_function_kernel<true> : prior_function_kernel<false>, dim3((unsigned)((ND + PRIOR_THREADS - 1) / PRIOR_THREADS)),
+                       dim3(PRIOR_THREADS), 0, st, fa));
+        if (s.n_ranks) {
+            PredictRed ta{d_t32, d_ones, (int)ND, 1, 0, n_stats, ND, s.n_ranks, d_tranks, d_tmean, d_tos, nullptr};
+            HIP_TRY(launch(predict_reduce_kernel, dim3((unsigned)n_stats), dim3(PRED_THREADS), 0, st, ta));
+        }
+        // stage e: every statistic over the draws
+        PriorStat sa{d_t, ND, d_tobs, d_tm, d_tm + n_stats, d_cnt, d_cnt + n_stats, d_cnt + 2 * n_stats};
+        HIP_TRY(launch(prior_stat_kernel, dim3((unsigned)n_stats), dim3(PRIOR_THREADS), 0, st, sa));
+        const size_t kc = (size_t)k * ncols, kt = (size_t)k * n_stats;
+        HIP_TRY(fetch(s.mean ? s.mean + kc : nullptr, d_mean, (size_t)ncols, st));
+        HIP_TRY(fetch(s.order_stats ? s.order_stats + kc * s.n_ranks : nullptr, rk.d_stats, (size_t)s.n_ranks * ncols, st));
+        HIP_TRY(fetch(s.vote ? votes_h.data() : nullptr, d_votes, (size_t)ncols, st));
+        HIP_TRY(fetch(s.sat_count ? (long long*)s.sat_count + kc : nullptr, d_sat, (size_t)ncols, st));
+        HIP_TRY(fetch(s.stat_mean ? s.stat_mean + kt : nullptr, d_tm, (size_t)n_stats, st));
+        HIP_TRY(fetch(s.stat_sd ? s.stat_sd + kt : nullptr, d_tm + n_stats, (size_t)n_stats, st));
+        HIP_TRY(fetch(s.stat_order_stats ? s.stat_order_stats + kt * s.n_ranks : nullptr, d_tos, (size_t)s.n_ranks * n_stats, st));
+        HIP_TRY(fetch(s.n_greater ? (long long*)s.n_greater + kt : nullptr, d_cnt, (size_t)n_stats, st));
+        HIP_TRY(fetch(s.n_equal ? (long long*)s.n_equal + kt : nullptr, d_cnt + n_stats, (size_t)n_stats, st));
+        HIP_TRY(fetch(s.n_defined ? (long long*)s.n_defined + kt : nullptr, d_cnt + 2 * n_stats, (size_t)n_stats, st));
+        if (s.t_draw)
+            if (int rc = scatter_samples(h, d_t, n_stats, (int)ND, identity, nullptr, s.t_draw + kt * ND, (size_t)n_stats, 0)) return rc;
+        if (s.samples)
+            if (int rc = scatter_samples(h, d_fx, ncols, (int)ND, identity, nullptr, s.samples + kc * ND, (size_t)ncols, 0)) return rc;
+        if (int rc = wait_stream(h)) return rc;
+        if (s.vote)
+            for (int c = 0; c < ncols; ++c) s.vote[kc + c] = (double)votes_h[(size_t)c] / (double)ND;
+    }
     return 0;
 }
 

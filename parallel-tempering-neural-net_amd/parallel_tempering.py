@@ -29,6 +29,9 @@ from .analysis import (  # noqa: F401
     lfo_origins, lfo_refit_seed, lfo_walk, percentile_ranks, pit_coverage, pit_histogram, powerscale_check_delta, powerscale_diagnosis,
     powerscale_flagged, powerscale_groups, powerscale_names, ppc_check_lags, ppc_flagged, ppc_p_values, ppc_stat_names, reliability_table,
     top_share)
+# the prior predictive check lives in prior.py; its result tuple and prior_flagged are importable from here
+from .prior import PriorAnalysis, check_prior_scale
+from .prior import PriorPredictive, prior_flagged  # noqa: F401
 
 
 def _text_round(a, fmt, threads=8):
@@ -122,7 +125,7 @@ def overlap_cuts(S, swap_interval, chunks):
     return sorted({min(S - 1, si * max(1, round(n_int * (c + 1) / K))) for c in range(K - 1)} | {S - 1})
 
 
-class ParallelTemperingBase(PosteriorAnalysis):
+class ParallelTemperingBase(PosteriorAnalysis, PriorAnalysis):
     task = None                       # set by the two drop-in subclasses
     rmse_fmt = None                   # REG '%1.8f' (REG:462-464), CLS '%1.2f' (CLS:473-475)
 
@@ -130,12 +133,14 @@ class ParallelTemperingBase(PosteriorAnalysis):
                  NumSample, swap_interval, langevin_prob, path, *, seed=None, device=None, devices=None, exchange="auto",
                  transport=None, waves_per_replica=0, schedule=0, groups_per_replica=0, trace_capacity=0, swap_rule=0,
                  label_swap=False, shared_noise=True, write_files=True, io_threads=None, forward_bf16=0, overlap_chunks=8,
-                 adapt_ladder=False):
+                 adapt_ladder=False, sigma_squared=25.0):
         # what leave_future_out() builds its refits from: the keyword arguments as given, and NumSample
         self._ctor_kw = dict(device=device, devices=devices, exchange=exchange, transport=transport, waves_per_replica=waves_per_replica,
                              schedule=schedule, groups_per_replica=groups_per_replica, trace_capacity=trace_capacity,
                              swap_rule=swap_rule, label_swap=label_swap, shared_noise=shared_noise, io_threads=io_threads,
                              forward_bf16=forward_bf16, overlap_chunks=overlap_chunks, adapt_ladder=adapt_ladder)
+        # the variance of the weights' normal prior (the reference's literal, REG:207-221); leave_future_out's refits carry it
+        self.sigma_squared = self._ctor_kw["sigma_squared"] = check_prior_scale("sigma_squared", sigma_squared)
         self._num_sample_arg = NumSample
         # FNN chain variables (REG:491-494)
         self.traindata = traindata
@@ -303,7 +308,7 @@ class ParallelTemperingBase(PosteriorAnalysis):
             schedule=self.schedule, groups_per_replica=self.groups_per_replica, trace_capacity=self.trace_capacity,
             swap_rule=self.swap_rule, shared_noise=int(self.shared_noise), label_swap=int(self.label_swap),
             forward_bf16=self.forward_bf16, l_prob=float(self.langevin_prob), learn_rate=float(self.learn_rate), step_w=0.025, step_eta=0.2,
-            sigma_squared=25.0, nu_1=0.0, nu_2=0.0, seed=self.seed)
+            sigma_squared=self.sigma_squared, nu_1=0.0, nu_2=0.0, seed=self.seed)
         if self.devices is not None and len(self.devices) > 1:
             from . import distributed
             self._sampler = distributed.LadderGroup(self.devices, exchange=self.exchange, transport=self.transport, **config)
