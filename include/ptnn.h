@@ -325,7 +325,8 @@ int ptnn_predict(ptnn_handle *h, const ptnn_predict_spec *spec);
  * rho [n_lags, Q] (the raw combined autocorrelation rho_t for t < n_lags <= h, before the positivity and monotone edits).
  * Runs on the handle's stream behind everything queued and returns when done; quantities are processed in blocks whose scratch
  * stays under $PTNN_CONVERGENCE_SCRATCH_BYTES (read per call, default 1 GiB), which changes no result.  Touches no chain state,
- * tape, counter or trace row.  Not with a communicator attached (one GPU only). */
+ * tape, counter or trace row.  Not with a communicator attached (one GPU only).  The rank-normalised family (bulk and tail
+ * R-hat and ESS, rank histograms) is the call of its own below, ptnn_rank_convergence. */
 #define PTNN_TR_LIKEH 0
 #define PTNN_TR_RMSE_TR 1
 #define PTNN_TR_RMSE_TE 2
@@ -356,6 +357,56 @@ typedef struct ptnn_convergence_spec {
 } ptnn_convergence_spec;
 
 int ptnn_convergence(ptnn_handle *h, const ptnn_convergence_spec *spec);
+
+/* ---- rank-normalised convergence diagnostics (nothing in the reference) ----
+ * The rank-normalised split-R-hat, bulk / tail / quantile ESS and per-chain rank histograms of Vehtari, Gelman, Simpson, Carpenter
+ * & Buerkner (2021), beside the classic figures above; DESIGN.md section 23 states every formula.  Sources, quantities, their
+ * order, the rules and the error texts are those of ptnn_convergence.  Of each of the C chains of n >= 4 draws the first and last
+ * h = n / 2 are kept and the S' = 2 C h kept draws of a quantity are pooled.  r is a draw's 1-based rank among them, ties (compared
+ * by value, -0 = +0) sharing the mean of the ranks they cover; z = Phi^-1((r - 3/8) / (S' + 1/4)) in double (Wichura's AS241,
+ * PPND16).  r_hat_bulk and ess_bulk are the split-R-hat and split-ESS of ptnn_convergence with the 2C split chains of z in place of
+ * the draws; r_hat_tail is that R-hat of the z-scores of f = |x - med|, med = (x_(S'/2-1) + x_(S'/2)) / 2 of the pooled order
+ * statistics (0-based).  For a probability p the indicator I = [x <= x_(lo)], lo = floor((S' - 1) p), is a 0 / 1 series whose
+ * split-ESS is ess_quantile; ess_tail is the smaller of those at 0.05 and 0.95 (NaN if either is), ess_median the one at 0.5, and
+ * probs[n_probs <= PTNN_RANK_MAX_PROBS] in (0, 1) names further ones.  rank_hist counts, per chain and quantity, the kept draws in
+ * bin ((2r - 2) n_bins) / (2 S') (integers), 2 <= n_bins <= PTNN_RANK_MAX_BINS: a chain's bins sum to 2h.  ess_bulk_chain and
+ * ess_tail_chain are ess_bulk and ess_tail of each chain alone, with ranks, median and quantiles over that chain's own 2h kept
+ * draws.  A quantity whose draws are all equal has NaN everywhere; one whose split chains are constant but differ has R-hat = +inf;
+ * a constant indicator has a NaN ESS; a quantity with a draw that is not finite has NaN for every figure and z, and zero counts.
+ * Outputs, any may be NULL (what is NULL is not computed), quantity-major: r_hat_bulk, r_hat_tail, ess_bulk, ess_tail, ess_median
+ * [Q]; ess_quantile [n_probs, Q]; ess_bulk_chain, ess_tail_chain [C, Q]; rank_hist [C, n_bins, Q]; z [C, 2h, Q], the bulk z-scores
+ * in the order of the kept draws.  Runs on the handle's stream behind everything queued and returns when done; quantities are
+ * processed in blocks whose scratch stays under $PTNN_CONVERGENCE_SCRATCH_BYTES (read per call, default 1 GiB), which changes no
+ * result.  At most 65535 chains and 2^29 pooled kept draws per quantity (more is refused).  Touches no chain state, tape, counter
+ * or trace row.  Not with a communicator attached (one GPU only). */
+#define PTNN_RANK_MAX_PROBS 16
+#define PTNN_RANK_MAX_BINS 64
+
+typedef struct ptnn_rank_convergence_spec {
+    int32_t struct_bytes;         /* = sizeof(ptnn_rank_convergence_spec): ABI guard */
+    /* source 1: the trace (used when draws == NULL) */
+    const int32_t *replicas;      /* local replica indices, or NULL = all */
+    int32_t n_replicas;           /* entries of replicas (ignored when NULL) */
+    int32_t step0, nsteps, thin;  /* trace rows step0, step0 + thin, ... < step0 + nsteps (thin >= 1) */
+    const int32_t *params;        /* weight indices, or NULL = all P */
+    int32_t n_params;             /* entries of params (ignored when NULL) */
+    int32_t scalars;              /* bit mask over PTNN_TR_LIKEH .. PTNN_TR_ACC_TE */
+    /* source 2: host draws */
+    const float *draws;           /* [n_chains, n_draws, n_quantities] or NULL */
+    int32_t n_chains, n_draws, n_quantities;
+    int32_t n_probs;              /* entries of probs */
+    const double *probs;          /* further quantile probabilities, each in (0, 1) */
+    int32_t n_bins;               /* bins of rank_hist */
+    int32_t reserved_;            /* set 0 */
+    /* outputs */
+    double *r_hat_bulk, *r_hat_tail, *ess_bulk, *ess_tail, *ess_median;
+    double *ess_quantile;         /* [n_probs, Q] */
+    double *ess_bulk_chain, *ess_tail_chain;   /* [C, Q] */
+    int64_t *rank_hist;           /* [C, n_bins, Q] */
+    double *z;                    /* [C, 2h, Q] */
+} ptnn_rank_convergence_spec;
+
+int ptnn_rank_convergence(ptnn_handle *h, const ptnn_rank_convergence_spec *spec);
 
 /* ---- predictive accuracy (nothing in the reference: it compares topologies by RMSE / accuracy only, result.txt) ----
  * Per data row n: the log pointwise predictive density lppd_n, the WAIC penalty p_waic_n (sample variance of the pointwise

@@ -62,6 +62,22 @@ class ConvergenceSpec(C.Structure):
     ]
 
 
+RANK_MAX_PROBS, RANK_MAX_BINS = 16, 64
+
+
+class RankConvergenceSpec(C.Structure):
+    """ptnn_rank_convergence_spec (include/ptnn.h)."""
+    _fields_ = _SELECTION + [
+        ("params", C.POINTER(C.c_int32)), ("n_params", C.c_int32), ("scalars", C.c_int32),
+        ("draws", C.POINTER(C.c_float)), ("n_chains", C.c_int32), ("n_draws", C.c_int32), ("n_quantities", C.c_int32),
+        ("n_probs", C.c_int32), ("probs", C.POINTER(C.c_double)), ("n_bins", C.c_int32), ("reserved_", C.c_int32),
+        ("r_hat_bulk", C.POINTER(C.c_double)), ("r_hat_tail", C.POINTER(C.c_double)), ("ess_bulk", C.POINTER(C.c_double)),
+        ("ess_tail", C.POINTER(C.c_double)), ("ess_median", C.POINTER(C.c_double)), ("ess_quantile", C.POINTER(C.c_double)),
+        ("ess_bulk_chain", C.POINTER(C.c_double)), ("ess_tail_chain", C.POINTER(C.c_double)), ("rank_hist", C.POINTER(C.c_int64)),
+        ("z", C.POINTER(C.c_double)),
+    ]
+
+
 class ElpdSpec(C.Structure):
     """ptnn_elpd_spec (include/ptnn.h)."""
     _fields_ = _SELECTION + [
@@ -294,6 +310,7 @@ SYMBOLS = {
     "ptnn_trace_image_wait": (C.c_int, [C.c_void_p, C.c_int]),
     "ptnn_predict": (C.c_int, [C.c_void_p, C.POINTER(PredictSpec)]),
     "ptnn_convergence": (C.c_int, [C.c_void_p, C.POINTER(ConvergenceSpec)]),
+    "ptnn_rank_convergence": (C.c_int, [C.c_void_p, C.POINTER(RankConvergenceSpec)]),
     "ptnn_elpd": (C.c_int, [C.c_void_p, C.POINTER(ElpdSpec)]),
     "ptnn_lfo": (C.c_int, [C.c_void_p, C.POINTER(LfoSpec)]),
     "ptnn_forecast": (C.c_int, [C.c_void_p, C.POINTER(ForecastSpec)]),
@@ -796,13 +813,9 @@ class Sampler:
         _bind(spec, out)
         return self._call(self.lib.ptnn_predict, spec, out)
 
-    def convergence(self, *, replicas=None, step0=0, nsteps=None, thin=1, params=None, scalars=(), draws=None, per_chain=False,
-                    n_lags=0):
-        """ptnn_convergence: split-R-hat and split-ESS on the device.  Source: the trace rows step0, step0 + thin, ... < step0 + nsteps
-        of `replicas` (None = all) -- quantities: the weights `params` (None = all P), then the scalar columns `scalars` (TR_LIKEH ..
-        TR_ACC_TE) in TR_ order -- or host draws [C, n, Q].  -> dict(mean, var, r_hat, ess [Q] float64, trunc_lag [Q] int32,
-        ess_chain [C, Q] float64 (per_chain), rho [n_lags, Q] float64 (n_lags > 0), n_chains, n_draws); what was not asked for is None."""
-        spec, keep = _spec(ConvergenceSpec), []
+    def _quantities(self, spec, keep, replicas, step0, nsteps, thin, params, scalars, draws):
+        """The quantities of convergence() and rank_convergence(): host draws [C, n, Q], else the trace rows with the weights `params`
+        (None = all P) and the scalar columns `scalars` -> (chains, draws per chain, quantities)."""
         if draws is not None:
             da = _f32(draws)
             if da.ndim != 3:
@@ -826,13 +839,44 @@ class Sampler:
                 mask |= 1 << int(col)
             spec.scalars = mask
             Q = n_par + sum(1 for c in range(8) if mask >> c & 1)
-        Q = max(int(Q), 0)
+        return nc, nd, max(int(Q), 0)
+
+    def convergence(self, *, replicas=None, step0=0, nsteps=None, thin=1, params=None, scalars=(), draws=None, per_chain=False,
+                    n_lags=0):
+        """ptnn_convergence: split-R-hat and split-ESS on the device.  Source: the trace rows step0, step0 + thin, ... < step0 + nsteps
+        of `replicas` (None = all) -- quantities: the weights `params` (None = all P), then the scalar columns `scalars` (TR_LIKEH ..
+        TR_ACC_TE) in TR_ order -- or host draws [C, n, Q].  -> dict(mean, var, r_hat, ess [Q] float64, trunc_lag [Q] int32,
+        ess_chain [C, Q] float64 (per_chain), rho [n_lags, Q] float64 (n_lags > 0), n_chains, n_draws); what was not asked for is None."""
+        spec, keep = _spec(ConvergenceSpec), []
+        nc, nd, Q = self._quantities(spec, keep, replicas, step0, nsteps, thin, params, scalars, draws)
         out = dict(mean=np.empty(Q), var=np.empty(Q), r_hat=np.empty(Q), ess=np.empty(Q), trunc_lag=np.empty(Q, np.int32),
                    ess_chain=np.empty((max(nc, 0), Q)) if per_chain else None,
                    rho=np.empty((int(n_lags), Q)) if n_lags else None)
         _bind(spec, out)
         spec.n_lags = int(n_lags)
         self._call(self.lib.ptnn_convergence, spec, out, counters=())
+        out["n_chains"], out["n_draws"] = int(nc), int(nd)
+        return out
+
+    def rank_convergence(self, *, replicas=None, step0=0, nsteps=None, thin=1, params=None, scalars=(), draws=None, probs=(), n_bins=20,
+                         per_chain=False, z=False):
+        """ptnn_rank_convergence: the rank-normalised split-R-hat, bulk / tail / quantile ESS and rank histograms on the device.  Sources
+        and quantities as convergence().  probs: further quantile probabilities in (0, 1), at most 16.  -> dict(r_hat_bulk, r_hat_tail,
+        ess_bulk, ess_tail, ess_median [Q], ess_quantile [len(probs), Q], ess_bulk_chain, ess_tail_chain [C, Q] (per_chain), all
+        float64; rank_hist [C, n_bins, Q] int64; z [C, 2 (n // 2), Q] float64, the bulk z-scores of the kept draws (z); n_chains,
+        n_draws); what was not asked for is None."""
+        spec, keep = _spec(RankConvergenceSpec), []
+        nc, nd, Q = self._quantities(spec, keep, replicas, step0, nsteps, thin, params, scalars, draws)
+        pr = np.ascontiguousarray(probs, dtype=np.float64).reshape(-1)
+        keep.append(pr)
+        spec.probs, spec.n_probs, spec.n_bins = _ptr(pr, C.POINTER(C.c_double)) if pr.size else None, pr.size, int(n_bins)
+        nc0, B = max(int(nc), 0), max(int(n_bins), 0)
+        out = dict(r_hat_bulk=np.empty(Q), r_hat_tail=np.empty(Q), ess_bulk=np.empty(Q), ess_tail=np.empty(Q), ess_median=np.empty(Q),
+                   ess_quantile=np.empty((pr.size, Q)) if pr.size else None,
+                   ess_bulk_chain=np.empty((nc0, Q)) if per_chain else None, ess_tail_chain=np.empty((nc0, Q)) if per_chain else None,
+                   rank_hist=np.empty((nc0, B, Q), np.int64), z=np.empty((nc0, 2 * (max(int(nd), 0) // 2), Q)) if z else None)
+        _bind(spec, out)
+        self._call(self.lib.ptnn_rank_convergence, spec, out, counters=())
         out["n_chains"], out["n_draws"] = int(nc), int(nd)
         return out
 

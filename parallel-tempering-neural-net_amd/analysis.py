@@ -1,5 +1,5 @@
 """The posterior analysis calls of the drop-in (none is in the reference): their host-only helpers and result tuples, and the
-class that holds the ten public methods.  Every method checks its arguments here, makes one low-level call of `_lib.Sampler`
+class that holds the eleven public methods.  Every method checks its arguments here, makes one low-level call of `_lib.Sampler`
 (the device does the work) and finishes the result with host arithmetic.
 """
 import math
@@ -83,6 +83,42 @@ def top_share(a, counts=None):
 # convergence_diagnostics' result: names [Q]; mean, sd, r_hat, ess, mcse_mean [Q] float64; ess_chain [n_chains, Q] or None; rho
 # [n_lags, Q] or None; trunc_lag [Q] int32; n_chains, n_draws
 Convergence = namedtuple("Convergence", "names mean sd r_hat ess mcse_mean ess_chain rho trunc_lag n_chains n_draws")
+
+# rank_diagnostics' result: names [Q]; r_hat = max(r_hat_bulk, r_hat_tail), r_hat_bulk, r_hat_tail, ess_bulk, ess_tail, ess_median
+# [Q] float64; ess_quantile {p: [Q]} for the probs asked for; ess_bulk_chain, ess_tail_chain [n_chains, Q] or None; rank_hist
+# [n_chains, bins, Q] int64; z [n_chains, 2 (n_draws // 2), Q] float64 or None; n_chains, n_draws
+RankConvergence = namedtuple("RankConvergence", "names r_hat r_hat_bulk r_hat_tail ess_bulk ess_tail ess_median ess_quantile "
+                             "ess_bulk_chain ess_tail_chain rank_hist z n_chains n_draws")
+
+
+def rank_check_bins(bins):
+    """The bins of a rank histogram: an integer in [2, 64] -> int."""
+    b = int(bins)
+    if b != bins or not 2 <= b <= _lib.RANK_MAX_BINS:
+        raise ValueError(f"bins = {bins!r} must be an integer in [2, {_lib.RANK_MAX_BINS}]")
+    return b
+
+
+def rank_uniformity(result):
+    """Chi-square statistics [n_chains, Q] of each chain's rank histogram against the uniform one: sum over the bins of
+    (count - e)^2 / e with e = the chain's kept draws / bins.  Under mixing, and without ties, a chain's statistic is roughly
+    chi-square with bins - 1 degrees of freedom; autocorrelation inflates it and ties (every rejected step repeats a row, and tied
+    draws share one average rank, hence one bin) make the reference distribution approximate, so read it as a ranking of chains
+    and quantities, not as a test.  nan where a quantity has no counts (a draw that is not finite)."""
+    hist = np.asarray(result.rank_hist, dtype=np.float64)
+    expect = hist.sum(axis=1, keepdims=True) / hist.shape[1]
+    with np.errstate(invalid="ignore", divide="ignore"):
+        return np.where(expect[:, 0] > 0, ((hist - expect) ** 2 / expect).sum(axis=1), np.nan)
+
+
+def rank_flagged(result, r_hat=1.01, ess_per_chain=100):
+    """The names whose r_hat exceeds `r_hat`, or whose ess_bulk or ess_tail lies below ess_per_chain * n_chains (the thresholds of
+    Vehtari et al. 2021); a figure that is nan is flagged."""
+    need = ess_per_chain * result.n_chains
+    with np.errstate(invalid="ignore"):
+        ok = (result.r_hat <= r_hat) & (result.ess_bulk >= need) & (result.ess_tail >= need)
+    return [nm for nm, good in zip(result.names, ok) if not good]
+
 
 # predictive_accuracy's result: totals elpd_loo, se_elpd_loo, p_loo, elpd_waic, se_elpd_waic, p_waic, lppd, se_lppd (float);
 # pointwise lppd_i, elpd_loo_i, p_waic_i, khat [n_rows] float64; good_k (the k-hat threshold for this S); n_high_k (rows above
@@ -504,7 +540,7 @@ _ETA_REFUSAL = "a regression's weights need eta = log tau^2, one per vector (Sam
 
 
 class PosteriorAnalysis:
-    """The ten posterior analysis methods, for `ParallelTemperingBase` to inherit.  They use the constructor's attributes
+    """The eleven posterior analysis methods, for `ParallelTemperingBase` to inherit.  They use the constructor's attributes
     (`task`, `topology`, `num_param`, `num_chains`, `NumSamples`, `traindata`, `testdata`, `temperatures`, `burn_in`, `seed`,
     `label_swap`, `trace_capacity`, `swap_rule`, `shared_noise`, `use_langevin_gradients`, `langevin_prob`, `_sampler`,
     `_finished`; leave_future_out's refit also the constructor arguments it kept) and, for log_evidence, the driver's
@@ -671,6 +707,32 @@ class PosteriorAnalysis:
                            top_prob=top, samples=out["samples"], n_samples=out["n_samples"], n_distinct=out["n_distinct"])
 
     # ------------------------------------------------------------------ convergence diagnostics (not in the reference)
+    def _convergence_quantities(self, method, burn_in, chains, thin, params, scalars, draws):
+        """The quantities of convergence_diagnostics and rank_diagnostics: host draws (names q0 ..), else the selected trace rows
+        with the weights `params` and the scalar traces `scalars` -> (names, Sampler source keywords)."""
+        self._need_sampler(method)
+        if draws is not None:
+            d = np.asarray(draws)
+            if d.ndim != 3:
+                raise ValueError(f"draws must be [n_chains, n_draws, n_quantities], got shape {d.shape}")
+            return [f"q{k}" for k in range(d.shape[2])], dict(draws=d)
+        kw, _ = self._trace_selection(burn_in, chains, thin, alt="draws")
+        P = self.num_param
+        pidx = None if params is None else [int(p) for p in params]
+        if pidx is not None and any(not (0 <= p < P) for p in pidx):
+            raise ValueError(f"params: weight indices must lie in [0, {P})")
+        reg = self.task != TASK_CLS
+        cols = {}
+        for nm in scalars:
+            if nm not in _SCALAR_COLS or (nm == "eta" and not reg) or (nm == "acc_train" and reg):
+                allowed = ["likelihood", "rmse_train", "rmse_test", "eta" if reg else "acc_train", "acc_test"]
+                raise ValueError(f"scalar {nm!r}: one of {allowed}")
+            cols[_SCALAR_COLS[nm]] = nm
+        names = [f"w{p}" for p in (range(P) if pidx is None else pidx)] + [cols[c] for c in sorted(cols)]
+        if not names:
+            raise ValueError("no quantity selected: give params and/or scalars")
+        return names, dict(params=pidx, scalars=sorted(cols), **kw)
+
     def convergence_diagnostics(self, *, burn_in=None, chains="all", thin=1, params=None, scalars=("likelihood",), per_chain=False,
                                 n_lags=0, draws=None):
         """Split-R-hat, split-ESS and the Monte Carlo standard error of the mean of weights and scalar traces, computed on the GPU
@@ -686,36 +748,46 @@ class PosteriorAnalysis:
         `per_chain`: also the ESS of each chain alone; `n_lags`: also the raw combined autocorrelation rho_t, t < n_lags.
         `draws`: host draws [n_chains, n_draws, Q] instead of the trace (names q0 ..); works whenever the handle exists.
         -> Convergence(names, mean, sd, r_hat, ess, mcse_mean = sd / sqrt(ess), ess_chain, rho, trunc_lag, n_chains, n_draws)."""
-        self._need_sampler("convergence_diagnostics")
-        if draws is not None:
-            d = np.asarray(draws)
-            if d.ndim != 3:
-                raise ValueError(f"draws must be [n_chains, n_draws, n_quantities], got shape {d.shape}")
-            names = [f"q{k}" for k in range(d.shape[2])]
-            out = self._sampler.convergence(draws=d, per_chain=per_chain, n_lags=n_lags)
-        else:
-            kw, _ = self._trace_selection(burn_in, chains, thin, alt="draws")
-            P = self.num_param
-            pidx = None if params is None else [int(p) for p in params]
-            if pidx is not None and any(not (0 <= p < P) for p in pidx):
-                raise ValueError(f"params: weight indices must lie in [0, {P})")
-            reg = self.task != TASK_CLS
-            cols = {}
-            for nm in scalars:
-                if nm not in _SCALAR_COLS or (nm == "eta" and not reg) or (nm == "acc_train" and reg):
-                    allowed = ["likelihood", "rmse_train", "rmse_test", "eta" if reg else "acc_train", "acc_test"]
-                    raise ValueError(f"scalar {nm!r}: one of {allowed}")
-                cols[_SCALAR_COLS[nm]] = nm
-            names = [f"w{p}" for p in (range(P) if pidx is None else pidx)] + [cols[c] for c in sorted(cols)]
-            if not names:
-                raise ValueError("no quantity selected: give params and/or scalars")
-            out = self._sampler.convergence(params=pidx, scalars=sorted(cols), per_chain=per_chain, n_lags=n_lags, **kw)
+        names, source = self._convergence_quantities("convergence_diagnostics", burn_in, chains, thin, params, scalars, draws)
+        out = self._sampler.convergence(per_chain=per_chain, n_lags=n_lags, **source)
         sd = np.sqrt(out["var"])
         with np.errstate(invalid="ignore", divide="ignore"):
             mcse = sd / np.sqrt(out["ess"])
         return Convergence(names=names, mean=out["mean"], sd=sd, r_hat=out["r_hat"], ess=out["ess"], mcse_mean=mcse,
                            ess_chain=out["ess_chain"], rho=out["rho"], trunc_lag=out["trunc_lag"], n_chains=out["n_chains"],
                            n_draws=out["n_draws"])
+
+    def rank_diagnostics(self, *, burn_in=None, chains="all", thin=1, params=None, scalars=("likelihood",), per_chain=False, probs=(),
+                         bins=20, draws=None, return_z=False):
+        """The rank-normalised split-R-hat, the bulk and tail effective sample sizes and the per-chain rank histograms of weights
+        and scalar traces (Vehtari, Gelman, Simpson, Carpenter & Buerkner 2021), computed on the GPU from the
+        traces it already holds: the figures Stan, `posterior` and ArviZ report, beside the classic ones of convergence_diagnostics.
+
+        The pooled kept draws of a quantity (each chain's first and last half) are replaced by the normal scores z of their average
+        ranks, ties sharing a rank.  r_hat_bulk and ess_bulk are the split-R-hat and split-ESS of z; r_hat_tail is that R-hat of the
+        scores of |x - median|, which sees chains that agree in location but not in scale; r_hat is the larger.  ess_tail is the
+        smaller split-ESS of the indicators of the 5 % and 95 % quantiles, ess_median that of the median, `probs` asks for further
+        quantiles (at most 16, in (0, 1)).  None of them needs a finite variance.  rank_hist counts every chain's draws per `bins`
+        equal rank ranges (2 .. 64): under mixing each chain's histogram is flat (rank_uniformity); rank_flagged applies the
+        thresholds r_hat <= 1.01 and ESS >= 100 per chain.  A constant quantity has nan figures; one with a draw that is not
+        finite has nan figures and an empty histogram.
+
+        Selection (`burn_in`, `chains`, `thin`, `params`, `scalars`, `draws`), names and refusals are those of
+        convergence_diagnostics; chains="all" over a ladder also measures the spread between temperatures, chains="cold" with
+        per_chain=True gives the posterior's own figures: ess_bulk_chain and ess_tail_chain rank each chain's draws on their own.
+        `return_z`: also the bulk scores z [n_chains, 2 (n_draws // 2), Q] in the order of the kept draws, for rank plots.
+        -> RankConvergence(names, r_hat, r_hat_bulk, r_hat_tail, ess_bulk, ess_tail, ess_median, ess_quantile {p: [Q]},
+        ess_bulk_chain, ess_tail_chain, rank_hist, z, n_chains, n_draws)."""
+        names, source = self._convergence_quantities("rank_diagnostics", burn_in, chains, thin, params, scalars, draws)
+        pr = check_probability_levels("probs", probs, _lib.RANK_MAX_PROBS)
+        out = self._sampler.rank_convergence(probs=pr, n_bins=rank_check_bins(bins), per_chain=per_chain, z=return_z, **source)
+        with np.errstate(invalid="ignore"):
+            r_hat = np.where(np.isnan(out["r_hat_bulk"]) | np.isnan(out["r_hat_tail"]), np.nan, np.maximum(out["r_hat_bulk"], out["r_hat_tail"]))
+        return RankConvergence(names=names, r_hat=r_hat, r_hat_bulk=out["r_hat_bulk"], r_hat_tail=out["r_hat_tail"],
+                               ess_bulk=out["ess_bulk"], ess_tail=out["ess_tail"], ess_median=out["ess_median"],
+                               ess_quantile={p: out["ess_quantile"][k] for k, p in enumerate(pr)},
+                               ess_bulk_chain=out["ess_bulk_chain"], ess_tail_chain=out["ess_tail_chain"], rank_hist=out["rank_hist"],
+                               z=out["z"], n_chains=out["n_chains"], n_draws=out["n_draws"])
 
     # ------------------------------------------------------------------ predictive accuracy (not in the reference)
     def predictive_accuracy(self, data="train", *, burn_in=None, chains="all", thin=1, weights=None, eta=None, loglik=None,

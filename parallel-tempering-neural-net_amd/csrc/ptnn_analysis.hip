@@ -1,5 +1,5 @@
-// ptnn_analysis.hip -- the posterior analysis calls of libptnn.so: predict, convergence, elpd, lfo, forecast, evidence, calibration, sensitivity, ppc,
-// powerscale, prior_predictive, and the sample-selection path they share.  The shape-independent analysis kernels are defined in this object: it includes them.
+// ptnn_analysis.hip -- the posterior analysis calls of libptnn.so: predict, convergence, rank_convergence, elpd, lfo, forecast, evidence, calibration,
+// sensitivity, ppc, powerscale, prior_predictive, and the sample-selection path they share.  The shape-independent analysis kernels are defined in this object: it includes them.
 #include "ptnn_shapes.hpp"
 namespace ptnn {
 #include "ptnn_dev_select.hpp"               // sample selection (run-length pass over the selected rows) and the per-column predictive reduction
@@ -11,10 +11,12 @@ namespace ptnn {
 #include "ptnn_dev_ppc.hpp"                  // posterior predictive checks: replicated data and test quantities per occurrence
 #include "ptnn_dev_powerscale.hpp"           // power-scaling sensitivity: components, smoothed weights, order per quantity, distances
 #include "ptnn_dev_prior.hpp"                // prior predictive checks: saturation counts, statistics per drawn function and over the draws
+#include "ptnn_dev_rank.hpp"                 // rank-normalised convergence: sort words, average ranks, z-scores, indicators, rank histograms
 #define PTNN_SENSITIVITY_REDUCTIONS
 #include "ptnn_dev_sensitivity.hpp"          // input sensitivity, second part: sign counts, row sums and their weighted means
 }  // namespace ptnn
 #include "ptnn_host.hpp"
+#include "ptnn_rank_plan.hpp"               // the blocks of ptnn_rank_convergence: host arithmetic, checked on its own
 
 #include <algorithm>
 #include <cmath>
@@ -611,11 +613,16 @@ static_assert(PTNN_TR_LIKEH == TR_LIKEH && PTNN_TR_ACC_TE == TR_ACC_TE && PTNN_T
 // split-R-hat / split-ESS of Q quantities over C chains of n draws, gathered by `ga` (its source fields set: trace rows, or
 // draws [C][n][Q] in device memory); outputs are host arrays, any may be null: an output is computed and copied exactly when its
 // pointer is given, so ess_chain selects the per-chain ESS and every caller gives rho exactly when n_lags > 0 (ptnn_convergence
-// checks it; ptnn_evidence passes neither).  Shared by ptnn_convergence and ptnn_evidence.
+// checks it; ptnn_evidence passes neither).  Shared by ptnn_convergence, ptnn_evidence and ptnn_rank_convergence, whose `ga` names a
+// double series [C][n][Q] (ga.series) and which gives the scratch `budget` in bytes (0: $PTNN_CONVERGENCE_SCRATCH_BYTES); without ess,
+// trunc_lag, ess_chain and rho no lag sum is formed.
 static int conv_drive(ptnn_handle* h, DeviceScratch& mem, ConvGather ga, const std::vector<int>& qcol, int C, int n, int n_lags,
-                      double* mean, double* var, double* r_hat, double* ess, int32_t* trunc_lag, double* ess_chain, double* rho) {
+                      double* mean, double* var, double* r_hat, double* ess, int32_t* trunc_lag, double* ess_chain, double* rho,
+                      size_t budget = 0) {
     const int hl = n / 2, M = 2 * C, Q = (int)qcol.size();
     const bool per_chain = ess_chain != nullptr;
+    const bool lags = ess || trunc_lag || ess_chain || n_lags;
+    if (!budget) budget = scratch_budget("PTNN_CONVERGENCE_SCRATCH_BYTES");
     const int NS = 1 + (per_chain ? C : 0);
     hipStream_t st = h->stream;
     int *d_qcol = nullptr, *d_error = nullptr;
@@ -636,7 +643,7 @@ static int conv_drive(ptnn_handle* h, DeviceScratch& mem, ConvGather ga, const s
     // blocks of quantities: the scratch of one quantity, every stage's
     const size_t per_q = sizeof(double) * ((size_t)M * hl + 2 * (size_t)M + 2 * (size_t)C + 2 + (size_t)CONV_MAX_LAGS * C)
                        + sizeof(ConvSeq) * NS + sizeof(int) * (3 + (per_chain ? (size_t)C : 0));
-    const int Qb = (int)std::max<size_t>(1, std::min<size_t>(scratch_budget("PTNN_CONVERGENCE_SCRATCH_BYTES") / per_q, (size_t)Q));
+    const int Qb = (int)std::max<size_t>(1, std::min<size_t>(budget / per_q, (size_t)Q));
     double *d_x = nullptr, *d_smean = nullptr, *d_ssq = nullptr, *d_csum = nullptr, *d_cm2 = nullptr, *d_pmean = nullptr, *d_pvar = nullptr;
     double* d_chain = nullptr;
     ConvSeq* d_seq = nullptr;
@@ -659,14 +666,15 @@ static int conv_drive(ptnn_handle* h, DeviceScratch& mem, ConvGather ga, const s
         const int nq = std::min(Qb, Q - q0);
         // 1. gather and moments
         ga.qcol = d_qcol + q0; ga.nq = nq; ga.x = d_x; ga.smean = d_smean; ga.ssq = d_ssq; ga.csum = d_csum; ga.cm2 = d_cm2;
-        HIP_TRY(launch(conv_gather_kernel, dim3((unsigned)C, (unsigned)((nq + CONV_TILE - 1) / CONV_TILE)), dim3(CONV_THREADS), 0, st, ga));
+        HIP_TRY(launch(ga.series ? conv_gather_kernel<true> : conv_gather_kernel<false>, dim3((unsigned)C, (unsigned)((nq + CONV_TILE - 1) / CONV_TILE)),
+                       dim3(CONV_THREADS), 0, st, ga));
         // 2. W, var+ and the state of every sequence
         ConvMoments mo{d_smean, d_ssq, d_csum, d_cm2, nq, C, n, hl, NS, d_seq, d_pmean, d_pvar};
         const long long nseq = (long long)nq * NS;
         HIP_TRY(launch(conv_moments_kernel, dim3((unsigned)((nseq + CONV_THREADS - 1) / CONV_THREADS)), dim3(CONV_THREADS), 0, st, mo));
         HIP_TRY(hipMemsetAsync(d_full, 1, (size_t)nq * sizeof(int), st));             // non-zero: every sequence starts open
         if (per_chain) HIP_TRY(hipMemsetAsync(d_copen, 1, (size_t)nq * C * sizeof(int), st));
-        int n_open = nq;
+        int n_open = lags ? nq : 0;
         for (int k = 0; k < nq; ++k) open_h[(size_t)k] = k;
         HIP_TRY(hipMemcpyAsync(d_open, open_h.data(), (size_t)nq * sizeof(int), hipMemcpyHostToDevice, st));
         // 3. blocks of lags, each twice the last, for the quantities with a sequence still open
@@ -704,13 +712,12 @@ static int conv_drive(ptnn_handle* h, DeviceScratch& mem, ConvGather ga, const s
     return 0;
 }
 
-int ptnn_convergence(ptnn_handle* h, const ptnn_convergence_spec* spec) {
-    // argument checks first: none of them needs the handle or a device
-    if (int rc = check_spec(spec, "ptnn_convergence_spec")) return rc;
-    const ptnn_convergence_spec& s = *spec;
-    const bool host_src = s.draws != nullptr;
+// The quantities of ptnn_convergence and ptnn_rank_convergence (one Spec's source fields are the other's), in three parts, since
+// each call has checks of its own between them.  conv_check_source: the checks that need no handle.
+extern "C++" {
+template <class Spec> int conv_check_source(const Spec& s) {
     constexpr int scalar_cols = (1 << TR_LIKEH) | (1 << TR_RMSE_TR) | (1 << TR_RMSE_TE) | (1 << TR_ACC_TR) | (1 << TR_ACC_TE);
-    if (host_src) {
+    if (s.draws) {
         if (s.n_chains < 1) return fail(-1, "n_chains = %d must be >= 1", s.n_chains);
         if (s.n_draws < 4) return fail(-1, "n_draws = %d: the split chains need at least 4 draws per chain", s.n_draws);
         if (s.n_quantities < 1) return fail(-1, "n_quantities = %d must be >= 1", s.n_quantities);
@@ -722,53 +729,234 @@ int ptnn_convergence(ptnn_handle* h, const ptnn_convergence_spec* spec) {
             return fail(-1, "scalars = 0x%x: only TR_LIKEH, TR_RMSE_TR, TR_RMSE_TE, TR_ACC_TR and TR_ACC_TE are quantities "
                             "(not TR_ACCEPT, TR_LOGALPHA or TR_SRC)", (unsigned)s.scalars);
     }
+    return 0;
+}
+// the selection: chains, draws per chain, the column of every quantity
+struct ConvSelection {
+    std::vector<int32_t> reps;
+    std::vector<int> qcol;
+    int C = 0, n = 0;
+};
+template <class Spec> int conv_select(const ptnn_handle* h, const Spec& s, ConvSelection* sel) {
+    const int P = h->P;
+    if (s.draws) {
+        sel->C = s.n_chains; sel->n = s.n_draws;
+        for (int q = 0; q < s.n_quantities; ++q) sel->qcol.push_back(q);
+        return 0;
+    }
+    if (int rc = select_trace_rows(h, s.replicas, s.n_replicas, s.step0, s.nsteps, s.thin, &sel->reps, &sel->n)) return rc;
+    sel->C = (int)sel->reps.size();
+    if (sel->n < 4) return fail(-1, "%d draws per chain selected: the split chains need at least 4", sel->n);
+    if (s.params) {
+        for (int k = 0; k < s.n_params; ++k) {
+            if (s.params[k] < 0 || s.params[k] >= P) return fail(-1, "parameter %d out of range [0, %d)", s.params[k], P);
+            sel->qcol.push_back(s.params[k]);
+        }
+    } else {
+        for (int p = 0; p < P; ++p) sel->qcol.push_back(p);
+    }
+    for (int c = 0; c < TR_COUNT; ++c)
+        if (s.scalars & (1 << c)) sel->qcol.push_back(-1 - c);
+    if (sel->qcol.empty()) return fail(-1, "no quantity selected");
+    return 0;
+}
+// the source fields of the gather: the host draws uploaded, or the trace
+template <class Spec> int conv_source(ptnn_handle* h, DeviceScratch& mem, const Spec& s, const ConvSelection& sel, ConvGather* ga) {
+    hipStream_t st = h->stream;
+    if (s.draws) {
+        float* d_draws = nullptr;
+        const int Q = (int)sel.qcol.size();
+        HIP_TRY(mem.upload(&d_draws, s.draws, (size_t)sel.C * sel.n * Q, st));
+        ga->host = 1; ga->draws = d_draws; ga->Qh = Q;
+    } else {
+        int* d_reps = nullptr;
+        HIP_TRY(mem.upload(&d_reps, sel.reps.data(), sel.reps.size(), st));
+        ga->host = 0; ga->pos_w = h->d_pos_w; ga->scal = h->d_scal; ga->replicas = d_reps; ga->cap = h->cap; ga->PW = h->PW;
+        ga->step0 = s.step0; ga->thin = s.thin; ga->compact = h->plan.compact ? 1 : 0;
+    }
+    return 0;
+}
+}  // extern "C++"
+
+int ptnn_convergence(ptnn_handle* h, const ptnn_convergence_spec* spec) {
+    // argument checks first: none of them needs the handle or a device
+    if (int rc = check_spec(spec, "ptnn_convergence_spec")) return rc;
+    const ptnn_convergence_spec& s = *spec;
+    if (int rc = conv_check_source(s)) return rc;
     if (s.n_lags < 0) return fail(-1, "n_lags = %d must be >= 0", s.n_lags);
     if (s.n_lags > 0 && !s.rho) return fail(-1, "n_lags = %d but rho is NULL", s.n_lags);
     if (s.rho && s.n_lags == 0) return fail(-1, "rho requested with n_lags = 0");
     if (int rc = check_handle(h, "ptnn_convergence")) return rc;
-    const int P = h->P, cap = h->cap;
-    // the selection: chains, draws per chain, the column of every quantity
-    std::vector<int32_t> reps;
-    std::vector<int> qcol;
-    int C = 0, n = 0;
-    if (host_src) {
-        C = s.n_chains; n = s.n_draws;
-        for (int q = 0; q < s.n_quantities; ++q) qcol.push_back(q);
-    } else {
-        if (int rc = select_trace_rows(h, s.replicas, s.n_replicas, s.step0, s.nsteps, s.thin, &reps, &n)) return rc;
-        C = (int)reps.size();
-        if (n < 4) return fail(-1, "%d draws per chain selected: the split chains need at least 4", n);
-        if (s.params) {
-            for (int k = 0; k < s.n_params; ++k) {
-                if (s.params[k] < 0 || s.params[k] >= P) return fail(-1, "parameter %d out of range [0, %d)", s.params[k], P);
-                qcol.push_back(s.params[k]);
-            }
-        } else {
-            for (int p = 0; p < P; ++p) qcol.push_back(p);
-        }
-        for (int c = 0; c < TR_COUNT; ++c)
-            if (s.scalars & (1 << c)) qcol.push_back(-1 - c);
-        if (qcol.empty()) return fail(-1, "no quantity selected");
+    ConvSelection sel;
+    if (int rc = conv_select(h, s, &sel)) return rc;
+    if (s.n_lags > sel.n / 2) return fail(-1, "n_lags = %d exceeds the split-chain length %d", s.n_lags, sel.n / 2);
+
+    if (int rc = start_device(h)) return rc;
+    DeviceScratch mem;
+    ConvGather ga{};
+    if (int rc = conv_source(h, mem, s, sel, &ga)) return rc;
+    return conv_drive(h, mem, ga, sel.qcol, sel.C, sel.n, s.n_lags, s.mean, s.var, s.r_hat, s.ess, s.trunc_lag, s.ess_chain, s.rho);
+}
+
+// ---- rank-normalised convergence diagnostics (ptnn_dev_rank.hpp) ----
+static_assert(PTNN_RANK_MAX_BINS * 128 == RANK_HIST_LDS, "the LDS histogram holds 128 chains at the largest bin count");
+
+// the segmented bitonic sort of ptnn_dev_powerscale.hpp: every one of the `nseg` segments of npow words ascending
+static int sort_segments(ptnn_handle* h, unsigned long long* keys, int nseg, int npow) {
+    hipStream_t st = h->stream;
+    const int tile = std::min(npow, PS_SORT_TILE);
+    const dim3 tiles((unsigned)(npow / tile), (unsigned)nseg);
+    HIP_TRY(launch(powerscale_sort_lds_kernel, tiles, dim3(PS_THREADS), 0, st, keys, npow, tile, 2, tile));
+    for (int size = 2 * tile; size <= npow; size <<= 1) {
+        for (int stride = size / 2; stride >= tile; stride >>= 1)
+            HIP_TRY(launch(powerscale_sort_step_kernel, dim3((unsigned)((npow / 2 + PS_THREADS - 1) / PS_THREADS), (unsigned)nseg), dim3(PS_THREADS),
+                           0, st, keys, npow, size, stride));
+        HIP_TRY(launch(powerscale_sort_lds_kernel, tiles, dim3(PS_THREADS), 0, st, keys, npow, tile, size, size));
     }
-    const int hl = n / 2, Q = (int)qcol.size();
-    if (s.n_lags > hl) return fail(-1, "n_lags = %d exceeds the split-chain length %d", s.n_lags, hl);
+    return 0;
+}
+
+int ptnn_rank_convergence(ptnn_handle* h, const ptnn_rank_convergence_spec* spec) {
+    // argument checks first: none of them needs the handle or a device
+    if (int rc = check_spec(spec, "ptnn_rank_convergence_spec")) return rc;
+    const ptnn_rank_convergence_spec& s = *spec;
+    if (int rc = conv_check_source(s)) return rc;
+    if (s.n_probs < 0 || s.n_probs > PTNN_RANK_MAX_PROBS) return fail(-1, "n_probs = %d outside [0, %d]", s.n_probs, PTNN_RANK_MAX_PROBS);
+    if (s.n_probs > 0 && !s.probs) return fail(-1, "n_probs = %d but probs is NULL", s.n_probs);
+    for (int k = 0; k < s.n_probs; ++k)
+        if (!(s.probs[k] > 0.0 && s.probs[k] < 1.0)) return fail(-1, "probs[%d] = %g must lie in (0, 1)", k, s.probs[k]);
+    if (s.ess_quantile && s.n_probs == 0) return fail(-1, "ess_quantile requested with n_probs = 0");
+    if (s.n_bins < 2 || s.n_bins > PTNN_RANK_MAX_BINS) return fail(-1, "n_bins = %d outside [2, %d]", s.n_bins, PTNN_RANK_MAX_BINS);
+    if (int rc = check_handle(h, "ptnn_rank_convergence")) return rc;
+    ConvSelection sel;
+    if (int rc = conv_select(h, s, &sel)) return rc;
+    const int C = sel.C, n = sel.n, hl = n / 2, Q = (int)sel.qcol.size(), B = s.n_bins;
+    if (C > RANK_MAX_GRID_Y || 2LL * C * hl > RANK_MAX_POOLED)
+        return fail(-1, "%d chains of %d kept draws: at most 65535 chains and 2^29 pooled draws per quantity", C, 2 * hl);
+    const bool chain_out = s.ess_bulk_chain || s.ess_tail_chain;
+    const RankPlan plan = rank_plan(C, hl, Q, chain_out, scratch_budget("PTNN_CONVERGENCE_SCRATCH_BYTES"));
+    const int L = (int)plan.L, Qb = plan.Qb;
 
     if (int rc = start_device(h)) return rc;
     hipStream_t st = h->stream;
     DeviceScratch mem;
-    int* d_reps = nullptr;
-    float* d_draws = nullptr;
-    ConvGather ga{};
-    if (host_src) {
-        const size_t nd = (size_t)C * n * Q;
-        HIP_TRY(mem.upload(&d_draws, s.draws, nd, st));
-        ga.host = 1; ga.draws = d_draws; ga.Qh = Q;
-    } else {
-        HIP_TRY(mem.upload(&d_reps, reps.data(), reps.size(), st));
-        ga.host = 0; ga.pos_w = h->d_pos_w; ga.scal = h->d_scal; ga.replicas = d_reps; ga.cap = cap; ga.PW = h->PW;
-        ga.step0 = s.step0; ga.thin = s.thin; ga.compact = h->plan.compact ? 1 : 0;
+    RankGather ga{};
+    if (int rc = conv_source(h, mem, s, sel, &ga.src)) return rc;
+    int *d_qcol = nullptr, *d_error = nullptr, *d_bad = nullptr;
+    unsigned long long *d_keys = nullptr, *d_hist = nullptr;
+    double* d_ser = nullptr;
+    HIP_TRY(mem.upload(&d_qcol, sel.qcol.data(), (size_t)Q, st));
+    HIP_TRY(mem.alloc(&d_error, 1));
+    HIP_TRY(mem.alloc(&d_bad, (size_t)Q));
+    HIP_TRY(hipMemsetAsync(d_error, 0, sizeof(int), st));
+    HIP_TRY(hipMemsetAsync(d_bad, 0, (size_t)Q * sizeof(int), st));
+    if (s.rank_hist) {
+        HIP_TRY(mem.alloc(&d_hist, (size_t)C * B * Q));
+        HIP_TRY(hipMemsetAsync(d_hist, 0, (size_t)C * B * Q * sizeof(unsigned long long), st));
     }
-    return conv_drive(h, mem, ga, qcol, C, n, s.n_lags, s.mean, s.var, s.r_hat, s.ess, s.trunc_lag, s.ess_chain, s.rho);
+    HIP_TRY(mem.alloc(&d_keys, plan.key_words * Qb));
+    HIP_TRY(mem.alloc(&d_ser, (size_t)L * Qb));
+    ga.src.C = C; ga.src.n = n; ga.src.h = hl; ga.src.error = d_error;
+
+    // the probabilities of the indicator series: 0.05, 0.95 (ess_tail), 0.5 (ess_median), then the caller's
+    std::vector<double> probs{0.05, 0.95, 0.5};
+    probs.insert(probs.end(), s.probs, s.probs + s.n_probs);
+    const double nan = std::nan("");
+    std::vector<double> ess_q(probs.size() * (size_t)Q, nan), tmp;
+    std::vector<int> cols;
+    // one series of every segment of the block [q0, q0 + nq) -> its split-R-hat and split-ESS, to r_hat / ess [width] at q0 (the
+    // per-chain segments: chain-major, to [C][width])
+    auto series = [&](int q0, int nq, bool per_chain, int mode, int lo, double* r_hat, double* ess, size_t width) -> int {
+        const int nseg = per_chain ? nq * C : nq, Ls = per_chain ? 2 * hl : L;
+        RankSeries ra{d_keys, d_bad + q0, mode, lo, Ls, (int)(per_chain ? plan.npow_chain : plan.npow), nq, C, per_chain ? 1 : 0, d_ser,
+                      per_chain ? nullptr : d_hist, B, Q, q0};
+        // LDS for the histogram counters only where this launch counts and they fit (rank_series_kernel's `count && in_lds`)
+        const size_t lds = mode == RANK_BULK && ra.hist && C * B <= RANK_HIST_LDS ? (size_t)C * B * sizeof(int) : 0;
+        HIP_TRY(launch(rank_series_kernel, dim3((unsigned)((Ls + RANK_THREADS - 1) / RANK_THREADS), (unsigned)nseg), dim3(RANK_THREADS), lds, st, ra));
+        if (!r_hat && !ess) return 0;
+        ConvGather cg{};
+        cg.host = 1; cg.series = d_ser; cg.Qh = nseg;
+        cols.resize((size_t)nseg);
+        for (int k = 0; k < nseg; ++k) cols[(size_t)k] = k;
+        tmp.assign(2 * (size_t)nseg, nan);
+        DeviceScratch cm;                                   // conv_drive's buffers: released before the next series
+        if (int rc = conv_drive(h, cm, cg, cols, per_chain ? 1 : C, 2 * hl, 0, nullptr, nullptr, r_hat ? tmp.data() : nullptr,
+                                ess ? tmp.data() + nseg : nullptr, nullptr, nullptr, nullptr, plan.conv_budget)) return rc;
+        for (int c = 0; c < (per_chain ? C : 1); ++c)
+            for (int k = 0; k < nq; ++k) {
+                if (r_hat) r_hat[(size_t)c * width + q0 + k] = tmp[(size_t)c * nq + k];
+                if (ess) ess[(size_t)c * width + q0 + k] = tmp[(size_t)nseg + (size_t)c * nq + k];
+            }
+        return 0;
+    };
+    // a sort of the block's segments: the padding filled, the words gathered, every segment ordered
+    auto sorted = [&](int q0, int nq, bool per_chain) -> int {
+        const int nseg = per_chain ? nq * C : nq, npow = (int)(per_chain ? plan.npow_chain : plan.npow);
+        HIP_TRY(hipMemsetAsync(d_keys, 0xff, (size_t)nseg * npow * sizeof(unsigned long long), st));
+        ga.src.qcol = d_qcol + q0; ga.src.nq = nq; ga.per_chain = per_chain ? 1 : 0; ga.npow = npow; ga.keys = d_keys; ga.bad = d_bad + q0;
+        HIP_TRY(launch(rank_gather_kernel, dim3((unsigned)C, (unsigned)((nq + RANK_TILE - 1) / RANK_TILE)), dim3(RANK_THREADS), 0, st, ga));
+        return sort_segments(h, d_keys, nseg, npow);
+    };
+    std::vector<double> essc_q(chain_out && s.ess_tail_chain ? 2 * (size_t)C * Q : 0, nan);
+    const bool any_q = s.ess_tail || s.ess_median || s.ess_quantile;
+    if (s.r_hat_bulk || s.ess_bulk || s.r_hat_tail || s.z || s.rank_hist || any_q)
+        if (int rc = each_block(Q, Qb, [&](long long q0l, int nq) -> int {
+            const int q0 = (int)q0l;
+            if (int rc = sorted(q0, nq, false)) return rc;
+            if (s.r_hat_bulk || s.ess_bulk || s.z || s.rank_hist) {
+                if (int rc = series(q0, nq, false, RANK_BULK, 0, s.r_hat_bulk, s.ess_bulk, (size_t)Q)) return rc;
+                if (s.z) {
+                    HIP_TRY(hipMemcpy2DAsync(s.z + q0, (size_t)Q * sizeof(double), d_ser, (size_t)nq * sizeof(double), (size_t)nq * sizeof(double),
+                                             (size_t)L, hipMemcpyDeviceToHost, st));
+                    if (int rc = wait_stream(h)) return rc;
+                }
+            }
+            if (s.r_hat_tail)
+                if (int rc = series(q0, nq, false, RANK_FOLD, 0, s.r_hat_tail, nullptr, (size_t)Q)) return rc;
+            for (size_t k = 0; k < probs.size(); ++k) {
+                if (!(k < 2 ? s.ess_tail != nullptr : k == 2 ? s.ess_median != nullptr : s.ess_quantile != nullptr)) continue;
+                const int lo = (int)std::floor((double)(L - 1) * probs[k]);
+                if (int rc = series(q0, nq, false, RANK_INDICATOR, lo, nullptr, ess_q.data() + k * (size_t)Q, (size_t)Q)) return rc;
+            }
+            return 0;
+        })) return rc;
+    if (chain_out)
+        if (int rc = each_block(Q, plan.Qb_chain, [&](long long q0l, int nq) -> int {
+            const int q0 = (int)q0l, Lc = 2 * hl;
+            if (int rc = sorted(q0, nq, true)) return rc;
+            if (s.ess_bulk_chain)
+                if (int rc = series(q0, nq, true, RANK_BULK, 0, nullptr, s.ess_bulk_chain, (size_t)Q)) return rc;
+            for (size_t k = 0; k < 2 && s.ess_tail_chain; ++k) {
+                const int lo = (int)std::floor((double)(Lc - 1) * probs[k]);
+                if (int rc = series(q0, nq, true, RANK_INDICATOR, lo, nullptr, essc_q.data() + k * (size_t)C * Q, (size_t)Q)) return rc;
+            }
+            return 0;
+        })) return rc;
+    int err = 0;
+    std::vector<int> bad((size_t)Q);
+    HIP_TRY(hipMemcpyAsync(&err, d_error, sizeof(int), hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipMemcpyAsync(bad.data(), d_bad, (size_t)Q * sizeof(int), hipMemcpyDeviceToHost, st));
+    HIP_TRY(fetch((unsigned long long*)s.rank_hist, d_hist, (size_t)C * B * Q, st));
+    if (int rc = wait_stream(h)) return rc;
+    if (err) return fail(-2, "%d selected compact trace rows refer to rows that are not resident (internal error)", err);
+    // the smaller of two ESS, NaN if either is; a quantity with a draw that is not finite has NaN everywhere
+    auto lesser = [](double a, double b) { return std::isnan(a) || std::isnan(b) ? std::nan("") : std::min(a, b); };
+    for (int q = 0; q < Q; ++q) {
+        const bool ok = !bad[(size_t)q];
+        if (s.ess_tail) s.ess_tail[q] = ok ? lesser(ess_q[(size_t)q], ess_q[(size_t)Q + q]) : nan;
+        if (s.ess_median) s.ess_median[q] = ok ? ess_q[2 * (size_t)Q + q] : nan;
+        for (int k = 0; s.ess_quantile && k < s.n_probs; ++k) s.ess_quantile[(size_t)k * Q + q] = ok ? ess_q[(size_t)(3 + k) * Q + q] : nan;
+        for (int c = 0; c < C; ++c) {
+            const size_t o = (size_t)c * Q + q;
+            if (s.ess_tail_chain) s.ess_tail_chain[o] = ok ? lesser(essc_q[o], essc_q[(size_t)C * Q + o]) : nan;
+            if (s.ess_bulk_chain && !ok) s.ess_bulk_chain[o] = nan;
+        }
+        if (ok) continue;
+        if (s.r_hat_bulk) s.r_hat_bulk[q] = nan;
+        if (s.r_hat_tail) s.r_hat_tail[q] = nan;
+        if (s.ess_bulk) s.ess_bulk[q] = nan;
+    }
+    return 0;
 }
 
 // ---- predictive accuracy (ptnn_dev_elpd.hpp) ----
@@ -1570,18 +1758,9 @@ static_assert(PTNN_POWERSCALE_MAX_DISTINCT == PS_MAX_DISTINCT, "ptnn.h powerscal
 
 // one block of nq quantities whose sort words are in `keys`: order them, then the distances and moments of the four perturbations
 static int powerscale_block(ptnn_handle* h, unsigned long long* keys, int nq, int npow, PsDist da, int q0) {
-    hipStream_t st = h->stream;
-    const int tile = std::min(npow, PS_SORT_TILE);
-    const dim3 tiles((unsigned)(npow / tile), (unsigned)nq);
-    HIP_TRY(launch(powerscale_sort_lds_kernel, tiles, dim3(PS_THREADS), 0, st, keys, npow, tile, 2, tile));
-    for (int size = 2 * tile; size <= npow; size <<= 1) {
-        for (int stride = size / 2; stride >= tile; stride >>= 1)
-            HIP_TRY(launch(powerscale_sort_step_kernel, dim3((unsigned)((npow / 2 + PS_THREADS - 1) / PS_THREADS), (unsigned)nq), dim3(PS_THREADS),
-                           0, st, keys, npow, size, stride));
-        HIP_TRY(launch(powerscale_sort_lds_kernel, tiles, dim3(PS_THREADS), 0, st, keys, npow, tile, size, size));
-    }
+    if (int rc = sort_segments(h, keys, nq, npow)) return rc;
     da.keys = keys; da.q0 = q0;
-    HIP_TRY(launch(powerscale_distance_kernel, dim3((unsigned)nq, 4), dim3(PS_THREADS), 0, st, da));
+    HIP_TRY(launch(powerscale_distance_kernel, dim3((unsigned)nq, 4), dim3(PS_THREADS), 0, h->stream, da));
     return 0;
 }
 

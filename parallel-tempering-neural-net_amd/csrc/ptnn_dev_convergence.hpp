@@ -9,6 +9,7 @@
 //   1. conv_gather_kernel: one work-group per (chain, tile of 64 quantities) gathers the chain's rows (trace rows resolved as
 //      ptnn_predict resolves them, trace_vector_offset; a tile is 64 consecutive floats of a row when the quantities are), writes
 //      the centred split chains x[q][j][i] in double through an LDS transpose, and the split means, sum of squares, chain sums.
+//      conv_gather_kernel<true> reads a double series instead (the rank-normalised series of ptnn_dev_rank.hpp), same arithmetic.
 //   2. conv_moments_kernel: W, var+, r_hat, the pooled mean / variance, and the state of every ESS sequence.
 //   3. conv_lags_kernel: sum_i x_i x_{i+t} for a block of lags over the open quantities -- 64 quantities x 64 lags x one chain
 //      per work-group, the series staged in LDS in tiles of 32 draws, 16 consecutive lags per thread on a register window (FP64
@@ -54,6 +55,7 @@ struct ConvGather {
     double* csum;               // [nq][C] sum of the chain's n draws
     double* cm2;                // [nq][C] sum of squared deviations of the chain's n draws from their mean
     int* error;                 // a compact row referring to a row not resident (internal error)
+    const double* series;       // conv_gather_kernel<true>: a double series [C][n][Qh] in place of the fp32 sources (ptnn_dev_rank.hpp)
 };
 
 __device__ __forceinline__ float conv_load(const ConvGather& a, int c, int i, int col, int* err) {
@@ -64,8 +66,13 @@ __device__ __forceinline__ float conv_load(const ConvGather& a, int c, int i, in
     int src;
     return a.pos_w[trace_vector_offset(a.scal, rep, a.cap, a.PW, step, a.compact, err, &src) + col];
 }
+// the draw in double: the fp32 draw widened, or (SERIES) an element of the double series, which is never rounded to fp32
+template <bool SERIES> __device__ __forceinline__ double conv_value(const ConvGather& a, int c, int i, int col, int* err) {
+    if constexpr (SERIES) return a.series[((size_t)c * a.n + i) * a.Qh + col];
+    else return (double)conv_load(a, c, i, col, err);
+}
 
-__global__ void __launch_bounds__(CONV_THREADS) conv_gather_kernel(const ConvGather a) {
+template <bool SERIES = false> __global__ void __launch_bounds__(CONV_THREADS) conv_gather_kernel(const ConvGather a) {
     constexpr int NW = CONV_THREADS / WAVE;
     __shared__ double stage[CONV_TILE][CONV_TILE + 1];      // [quantity][draw] of a chunk of 64 draws: the transposed store
     __shared__ double red[3][NW][CONV_TILE];
@@ -77,7 +84,7 @@ __global__ void __launch_bounds__(CONV_THREADS) conv_gather_kernel(const ConvGat
     // pass 1: sums of the first half, the second half and the middle draw
     double s1 = 0.0, s2 = 0.0, sm = 0.0;
     for (int i = wave; i < n; i += NW) {
-        const double v = (double)conv_load(a, c, i, col, a.error);
+        const double v = conv_value<SERIES>(a, c, i, col, a.error);
         if (i < h) s1 += v; else if (i >= n - h) s2 += v; else sm += v;
     }
     red[0][wave][lane] = s1; red[1][wave][lane] = s2; red[2][wave][lane] = sm;
@@ -91,7 +98,7 @@ __global__ void __launch_bounds__(CONV_THREADS) conv_gather_kernel(const ConvGat
     for (int i0 = 0; i0 < n; i0 += CONV_TILE) {
         for (int r = wave; r < CONV_TILE && i0 + r < n; r += NW) {
             const int i = i0 + r;
-            const double v = (double)conv_load(a, c, i, col, a.error);
+            const double v = conv_value<SERIES>(a, c, i, col, a.error);
             double d = 0.0;
             if (i < h) { d = v - m1; q1 = fma(d, d, q1); }
             else if (i >= n - h) { d = v - m2; q2 = fma(d, d, q2); }

@@ -24,11 +24,11 @@ from . import _lib, ladder, philox
 from .analysis import (  # noqa: F401
     _SCALAR_COLS, _se_total, _trapezoid, POWERSCALE_COMPONENTS, POWERSCALE_DEFAULT_QUANTITIES, POWERSCALE_SIGNS, PPC_CLASSIFICATION_STATS, PPC_DEFAULT_LAGS,
     PPC_REGRESSION_STATS, TASK_CLS, TASK_REG, Calibration, Convergence, Evidence, Forecast, LeaveFutureOut, PosteriorAnalysis,
-    PowerScaling, Predictive, PredictiveAccuracy, PredictiveCheck, Sensitivity, check_probability_levels, classification_scores,
+    PowerScaling, Predictive, PredictiveAccuracy, PredictiveCheck, RankConvergence, Sensitivity, check_probability_levels, classification_scores,
     crps_summary, elpd_compare, evidence_compare, evidence_from_rungs, evidence_log_c, good_k, interval_scores, lerp_percentile,
     lfo_origins, lfo_refit_seed, lfo_walk, percentile_ranks, pit_coverage, pit_histogram, powerscale_check_delta, powerscale_diagnosis,
-    powerscale_flagged, powerscale_groups, powerscale_names, ppc_check_lags, ppc_flagged, ppc_p_values, ppc_stat_names, reliability_table,
-    top_share)
+    powerscale_flagged, powerscale_groups, powerscale_names, ppc_check_lags, ppc_flagged, ppc_p_values, ppc_stat_names, rank_check_bins, rank_flagged,
+    rank_uniformity, reliability_table, top_share)
 # the prior predictive check lives in prior.py; its result tuple and prior_flagged are importable from here
 from .prior import PriorAnalysis, check_prior_scale
 from .prior import PriorPredictive, prior_flagged  # noqa: F401
