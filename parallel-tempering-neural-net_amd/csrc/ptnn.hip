@@ -295,6 +295,12 @@ int ptnn::raise_lds_limit(const void* func, size_t bytes) {
     return 0;
 }
 
+// Whether a work-group of `fn` can have `bytes` of LDS: within LDS_MAX, and the runtime grants the ceiling (just below 160 KiB it
+// refuses; the refusal's error is cleared).  For the plans that have something smaller to go on with.
+static bool lds_accepted(seg_fn fn, size_t bytes) {
+    return bytes <= LDS_MAX && ptnn::raise_lds_limit(reinterpret_cast<const void*>(fn), bytes) == 0;
+}
+
 // Wait for everything queued on the handle's stream.  With an RCCL communicator attached the wait is bounded: a collective
 // whose peer never arrives would otherwise block the host for ever (the reference's parent at least polls is_alive() every
 // round, REG:721-727).  "No progress" = the stream is busy and the device has not completed a swap round (swap_kernel stores the
@@ -431,12 +437,24 @@ int plan_packed(const ptnn_handle& h, int Nall, int sched, LaunchPlan& plan) {
         const int want = c.groups_per_replica;
         if (want == 2 || want == 4) G = want;                       // (8-lane groups: on request only -- 16 slots on one CU already)
         else if (want == 0 && plan.pk_nred == 4) { if (Rl * 4 <= h.num_cus) G = 4; else if (Rl * 2 <= h.num_cus) G = 2; }
+        // The runtime refuses a dynamic-LDS ceiling just below 160 KiB (6-16-18 with 65 rows: 159.9 KiB over several CUs, next to
+        // the kernel's 256 B of static LDS): ask it.
+        // A refused automatic choice goes on with one CU per replica, a refused request is an error.
+        if (G > 1 && !lds_accepted(segment_function(h.shape, SEG_PACKM), pkm)) {
+            if (want == 2 || want == 4)
+                return fail(-3, "the packed round over %d CUs needs %zu B of LDS, which the runtime does not grant one work-group", want, pkm);
+            G = 1;
+        }
     }
     const bool pays = (H <= 8) || G > 1 || Rl * 4 > h.num_cus;
     if (sched != PTNN_SCHED_PACKED &&
         !(c.schedule == PTNN_SCHED_AUTO && sched == PTNN_SCHED_SPECULATIVE && fits && pays && c.use_langevin && c.waves_per_replica == 0 &&
           (c.groups_per_replica == 0 || G > 1)))
         return 0;
+    if (G == 1 && !lds_accepted(segment_function(h.shape, SEG_PACK), pk)) {
+        if (sched == PTNN_SCHED_PACKED) return fail(-3, "the packed schedule needs %zu B of LDS, which the runtime does not grant one work-group", pk);
+        return 0;
+    }
     plan.kind = G > 1 ? SEG_PACKM : SEG_PACK;
     plan.groups = G;
     // eight waves (forward passes two to a SIMD) while every replica has a CU to itself, four beyond that; an explicit
@@ -462,14 +480,16 @@ int plan_speculative(const ptnn_handle& h, int Nall, LaunchPlan& plan) {
     else if (!c.shared_device) { while (G < 4 && Rl * (G * 2) <= h.num_cus) G *= 2; }
     if (G != 1 && G != 2 && G != 4 && G != 8) return fail(-1, "groups_per_replica must be 0 (auto), 1, 2, 4 or 8");
     auto lds = [&](int k) { return spec_lds_floats(Nall, h.IPY, h.PS, c.n_hidden, h.FWS, k, G) * sizeof(float); };
+    const seg_fn spec = segment_function(h.shape, SEG_SPEC);
+    auto fits = [&](int k) { return lds_accepted(spec, lds(k)); };
     int k = nw ? nw : (G > 1 ? 4 : 8);
-    while (k > 1 && lds(k) > LDS_MAX) k >>= 1;
+    while (k > 1 && !fits(k)) k >>= 1;
     if (nw && k != nw) {
         if (c.schedule == PTNN_SCHED_AUTO) k = 0;      // auto: fall back to the cooperative schedule
         else return fail(-3, "speculative schedule with %d waves needs more than 160 KiB of LDS", nw);
     }
     if (k * G > MAX_SLOTS) return fail(-1, "waves x groups must not exceed %d", MAX_SLOTS);
-    if (k == 0 || lds(k) > LDS_MAX) return 0;
+    if (k == 0 || !fits(k)) return 0;
     plan.kind = SEG_SPEC; plan.threads = k * 64; plan.groups = G; plan.seg_lds = lds(k);
     if (G > 1) {
         // The work-groups of one replica wait for each other inside the kernel, so all Rl x G of them must be resident at once: ask
