@@ -510,19 +510,19 @@ __device__ __forceinline__ void segment_body(const SegParams& p, const SegDyn& d
     float* sf = p.st_f + (size_t)r * SF_COUNT;
     int* si = p.st_i + (size_t)r * SI_COUNT;
     float lik, prior_cur, tau_eta_last, rec_rmse_tr, rec_rmse_te, rec_acc_tr, rec_acc_te;
-    int nacc, gd_valid, lg_count;
+    int nacc, gd_valid, lg_count, lg_acc;
 
     if (step_begin == 0) {
         chain_startup<TASK, I, O>(p, l.xy, l.w_cur, l.fw, l.red, T, eta, lik, prior_cur);
         tau_eta_last = eta;
         rec_rmse_tr = rec_rmse_te = rec_acc_tr = rec_acc_te = 0.f;
-        nacc = 0; gd_valid = 0; lg_count = 0;
+        nacc = 0; gd_valid = 0; lg_count = 0; lg_acc = 0;
         __syncthreads();
     } else {
         lik = sf[SF_LIK]; prior_cur = sf[SF_PRIOR]; tau_eta_last = sf[SF_TAU_LAST];
         rec_rmse_tr = sf[SF_REC_RMSE_TR]; rec_rmse_te = sf[SF_REC_RMSE_TE];
         rec_acc_tr = sf[SF_REC_ACC_TR]; rec_acc_te = sf[SF_REC_ACC_TE];
-        nacc = si[SI_NACC]; gd_valid = dyn.gd_valid[r]; lg_count = si[SI_LG_COUNT];
+        nacc = si[SI_NACC]; gd_valid = dyn.gd_valid[r]; lg_count = si[SI_LG_COUNT]; lg_acc = si[SI_LG_ACC];
     }
 
     PTNN_DIAG(coop_begin);
@@ -649,6 +649,7 @@ __device__ __forceinline__ void segment_body(const SegParams& p, const SegDyn& d
                 finish_scores<TASK>(es, p.Ntr, p.Nte, rec_rmse_tr, rec_rmse_te, rec_acc_tr, rec_acc_te);   // REG: acc 0 (REG:403-404); CLS: accuracy (CLS:414-415)
                 if (TASK == TASK_REG) rec_acc_tr = eta;       // the regression's acc_train slot records eta (finish_eval<TASK, true>)
             }
+            lg_acc += lg ? 1 : 0;
             gd_valid = lg ? 1 : 0;                        // w_prop_gd is langevin_gradient(new w): keep it as the cache
             const int old_cur = o_cur;
             o_cur = o_prop; o_rec = o_prop; o_prop = old_cur;   // old_cur is neither the new current nor the new recorded vector
@@ -681,7 +682,7 @@ __device__ __forceinline__ void segment_body(const SegParams& p, const SegDyn& d
         sf[SF_LIK] = lik; sf[SF_PRIOR] = prior_cur; sf[SF_TAU_LAST] = tau_eta_last;
         sf[SF_REC_RMSE_TR] = rec_rmse_tr; sf[SF_REC_RMSE_TE] = rec_rmse_te;
         sf[SF_REC_ACC_TR] = rec_acc_tr; sf[SF_REC_ACC_TE] = rec_acc_te;
-        si[SI_NACC] = nacc; dyn.gd_valid[r] = gd_valid; si[SI_LG_COUNT] = lg_count;
+        si[SI_NACC] = nacc; dyn.gd_valid[r] = gd_valid; si[SI_LG_COUNT] = lg_count; si[SI_LG_ACC] = lg_acc;
         p.L_handoff[gid] = (TASK == TASK_REG) ? lik * T : lik;      // Q11
         p.L_final[gid] = lik;
         post_raw(p, gid, lik, prior_cur, T, step_begin + n_steps - 1);

@@ -122,7 +122,7 @@ __device__ __forceinline__ void segment_pack_body(const SegParams& p, const SegD
     const int end = step_begin + n_steps;
     const bool sweeping = p.use_lg != 0;
     // forward passes: waves 2,3(,6,7) while waves 0,1 sweep; all waves when there is nothing to sweep.  The host launches eight
-    // waves while every replica has a CU to itself and four beyond that (with 232 VGPRs two waves fit on a SIMD: an eight-wave
+    // waves while every replica has a CU to itself and four beyond that (with more than 128 and at most 256 VGPRs two waves fit on a SIMD: an eight-wave
     // work-group has the CU to itself, of four-wave ones two are resident -- 1024 replicas on one GPU: 105 M vs 91 M samples/s)
     const int nwaves = nthr >> 6;
     const int ev_n = sweeping ? (nwaves == PK_WAVES ? PK_FWD_WAVES : 2) : nwaves;
@@ -176,6 +176,14 @@ __device__ __forceinline__ void segment_pack_body(const SegParams& p, const SegD
         return ((cur + si_) / si_) * si_ - 1;
     };
     int ho_next = swap_inside ? next_handoff(step_begin) : 0x7fffffff;
+    // Commit of one CU's Langevin rounds: the sweep waves do only what the next epochs wait for -- flags, ballot, the accepted
+    // state -- and the forward waves write the trace rows, after the barrier the sweep waves leave through: they read the scalars of
+    // their rows before it (the next forward passes overwrite slots[]) and the pos_w rows from rec_w / rec_alt behind it, which
+    // nobody writes before the next commit, two barriers on.  The rows are stored before the round ends, so none is ever pending
+    // when the loop is left.  Thread tr_t of tr_n writes rows; everywhere else every thread does, before the barrier.
+    const bool split = !MULTI && sweeping && nwaves > PK_SWEEP_WAVES;
+    const int tr_n = split ? ev_n * WAVE : nthr;
+    const int cp_n = split ? PK_SWEEP_WAVES * WAVE : nthr;  // threads that copy the accepted state
     int nx = 0;                                             // swap rounds done inside this launch
     while (i < end && !failed) {
         if (MULTI) { epoch += 1; }
@@ -274,6 +282,7 @@ __device__ __forceinline__ void segment_pack_body(const SegParams& p, const SegD
             const bool on = s_ < k;
             float* sl = slots + (on ? s_ : 0) * SL_COUNT;
             float diff_prop = 0.0f;
+            STAMP_MH_OPERANDS(sl, s_scal(on ? s_ : 0), w_cur, l16);     // ... of which the reads that do not wait for the epochs
             if (sweeping && wave < 4) {
                 const float* pg = s_pgd(on ? s_ : 0);
                 float r1[4];
@@ -291,12 +300,14 @@ __device__ __forceinline__ void segment_pack_body(const SegParams& p, const SegD
             }
             const float logalpha = (sl[SL_LIKPROP] - lik) + (sl[SL_PRIORPROP] - prior_cur) + diff_prop;
             const float mh = (logalpha != logalpha) ? 1.0f : fminf(1.0f, expf_fast(logalpha));
+            STAMP_MH(1);                                    // ... up to the verdict
             if (on && l16 == 0) { sl[SL_ACCEPT] = (s_scal(s_)[1] < mh) ? 1.0f : 0.0f; sl[SL_LOGALPHA] = logalpha; }
         }
         __syncthreads();
         STAMP(5);                                           // MH
         // commit the prefix up to and including the first accepted step
         const bool f_acc = (lane < k) && (slots[lane * SL_COUNT + SL_ACCEPT] != 0.0f);
+        const bool f_lg_slot = !MULTI && (lane < k) && (slots[lane * SL_COUNT + SL_LG] != 0.0f);   // read with the accept flags
         const unsigned long long bal_acc = __ballot(f_acc);
         const int ml = bal_acc ? (__ffsll((long long)bal_acc) - 1) : -1;          // first accepted LOCAL slot, or none
         int m = (ml >= 0) ? s0 + ml : kt;                                           // first accepted step of the window (slot index)
@@ -348,38 +359,79 @@ __device__ __forceinline__ void segment_pack_body(const SegParams& p, const SegD
             }
             xpar ^= 1;
         }
+        STAMP_SUB(2);                                       // ... of which the flags and the ballot
         const int ncommit = (m < kt) ? m + 1 : kt;
         const int nloc = max(0, min(k, ncommit - s0));          // of them this work-group's own slots: it writes their trace rows
-        for (int item = tid; item < nloc * p.PW; item += nthr) { // trace rows: all (slot, element) pairs at once
-            const int s_ = (int)(((float)item + 0.5f) * inv_PW), e = item - s_ * p.PW;
-            int tp = tpos0 + s0 + s_;
-            if (tp >= p.trace_cap) tp -= p.trace_cap;
-            p.tr_pos_w[(trow + (size_t)tp) * (size_t)p.PW + e] = (e < P) ? ((s0 + s_ == m) ? s_prop(s_) : rec_w)[e] : 0.0f;
-        }
-        if (tid < nloc) {
-            const int s_ = tid;
-            const bool acc_me = (s0 + s_ == m);
-            const float* sl = slots + s_ * SL_COUNT;
-            int tp = tpos0 + s0 + s_;
-            if (tp >= p.trace_cap) tp -= p.trace_cap;
-            const size_t tpos = trow + (size_t)tp;
-            store_trace_row(p.tr_scal + tpos * TR_COUNT, (TASK == TASK_REG) ? sl[SL_LIKPROP] : sl[SL_LIKPROP] * sl[SL_ADAPT],
-                            acc_me ? sl[SL_RM_TR] : rec_rmse_tr, acc_me ? sl[SL_RM_TE] : rec_rmse_te,
-                            acc_me ? sl[SL_AC_TR] : rec_acc_tr, acc_me ? sl[SL_AC_TE] : rec_acc_te, nacc, sl[SL_LOGALPHA]);
+        // trace rows: all (slot, element) pairs at once, and a scalar row per slot.  The several-CU kernel keeps the code it had, to
+        // the letter (it compiles to the same instructions as before the commit was split: profiles/tools/compare_device_code.py).
+        const int tr_t = (MULTI || !split) ? tid : (ev_i >= 0 ? ev_i * WAVE + lane : -1);
+        auto pos_w_rows = [&](const float* row_acc, const float* row_rej) {
+            if constexpr (!MULTI) {                         // (discarded there, it captures nothing)
+                for (int item = tr_t; item < nloc * p.PW; item += tr_n) {
+                    const int s_ = (int)(((float)item + 0.5f) * inv_PW), e = item - s_ * p.PW;
+                    int tp = tpos0 + s0 + s_;
+                    if (tp >= p.trace_cap) tp -= p.trace_cap;
+                    p.tr_pos_w[(trow + (size_t)tp) * (size_t)p.PW + e] = (e < P) ? ((s0 + s_ == m) ? row_acc : row_rej)[e] : 0.0f;
+                }
+            }
+        };
+        const bool tr_row = tr_t >= 0 && tr_t < nloc;           // I write the scalar row of slot tr_t
+        float tr_likeh = 0.0f, tr_rm_tr = 0.0f, tr_rm_te = 0.0f, tr_ac_tr = 0.0f, tr_ac_te = 0.0f, tr_logalpha = 0.0f;
+        const int tr_nacc = nacc;
+        auto scalar_row = [&]() {
+            if constexpr (!MULTI) {
+                if (tr_row) {
+                    int tp = tpos0 + s0 + tr_t;
+                    if (tp >= p.trace_cap) tp -= p.trace_cap;
+                    store_trace_row(p.tr_scal + (trow + (size_t)tp) * TR_COUNT, tr_likeh, tr_rm_tr, tr_rm_te, tr_ac_tr, tr_ac_te, tr_nacc, tr_logalpha);
+                }
+            }
+        };
+        if constexpr (MULTI) {
+            for (int item = tid; item < nloc * p.PW; item += nthr) {
+                const int s_ = (int)(((float)item + 0.5f) * inv_PW), e = item - s_ * p.PW;
+                int tp = tpos0 + s0 + s_;
+                if (tp >= p.trace_cap) tp -= p.trace_cap;
+                p.tr_pos_w[(trow + (size_t)tp) * (size_t)p.PW + e] = (e < P) ? ((s0 + s_ == m) ? s_prop(s_) : rec_w)[e] : 0.0f;
+            }
+            if (tid < nloc) {
+                const int s_ = tid;
+                const bool acc_me = (s0 + s_ == m);
+                const float* sl = slots + s_ * SL_COUNT;
+                int tp = tpos0 + s0 + s_;
+                if (tp >= p.trace_cap) tp -= p.trace_cap;
+                const size_t tpos = trow + (size_t)tp;
+                store_trace_row(p.tr_scal + tpos * TR_COUNT, (TASK == TASK_REG) ? sl[SL_LIKPROP] : sl[SL_LIKPROP] * sl[SL_ADAPT],
+                                acc_me ? sl[SL_RM_TR] : rec_rmse_tr, acc_me ? sl[SL_RM_TE] : rec_rmse_te,
+                                acc_me ? sl[SL_AC_TR] : rec_acc_tr, acc_me ? sl[SL_AC_TE] : rec_acc_te, nacc, sl[SL_LOGALPHA]);
+            }
+        } else {
+            if (tr_row) {
+                const bool acc_me = (s0 + tr_t == m);
+                const float* sl = slots + tr_t * SL_COUNT;
+                tr_likeh = (TASK == TASK_REG) ? sl[SL_LIKPROP] : sl[SL_LIKPROP] * sl[SL_ADAPT];
+                tr_rm_tr = acc_me ? sl[SL_RM_TR] : rec_rmse_tr; tr_rm_te = acc_me ? sl[SL_RM_TE] : rec_rmse_te;
+                tr_ac_tr = acc_me ? sl[SL_AC_TR] : rec_acc_tr; tr_ac_te = acc_me ? sl[SL_AC_TE] : rec_acc_te;
+                tr_logalpha = sl[SL_LOGALPHA];
+            }
+            if (!split) {
+                pos_w_rows(s_prop(min(max(0, m - s0), PK_SLOTS - 1)), rec_w);
+                scalar_row();
+            }
         }
         if constexpr (MULTI) {
             // Langevin coins and the last proposed eta of the committed steps, from the tape (every work-group holds the whole
             // window's): the same expressions the forward waves evaluate for their own slots
             const int e_ = (i + lane) % RING;
-            const bool f_lg = sweeping && (lane < ncommit) && (ring_s[e_ * 4] < p.l_prob);
-            lg_count += __popcll(__ballot(f_lg));
+            const bool f_lg_tape = sweeping && (lane < ncommit) && (ring_s[e_ * 4] < p.l_prob);
+            lg_count += __popcll(__ballot(f_lg_tape));
             if (TASK == TASK_REG) tau_eta_last = uni_f(fmaf(p.step_eta, ring_s[((i + ncommit - 1) % RING) * 4 + 2], eta));
         } else {
-            const bool f_lg = (lane < k) && (slots[lane * SL_COUNT + SL_LG] != 0.0f);
-            const unsigned long long bal_lg = __ballot(f_lg);
+            const unsigned long long bal_lg = __ballot(f_lg_slot);
             lg_count += __popcll(bal_lg & ((1ull << ncommit) - 1ull));
             if (TASK == TASK_REG) tau_eta_last = uni_f(slots[(ncommit - 1) * SL_COUNT + SL_ETAPRO]);
         }
+        STAMP_SUB(3);                                       // ... up to the trace rows and the counts
         if (m < kt) {
             // no barrier between the trace rows above and this update: they read rec_w, the new recorded row goes to rec_alt
             nacc += 1;
@@ -388,14 +440,29 @@ __device__ __forceinline__ void segment_pack_body(const SegParams& p, const SegD
             rec_acc_tr = uni_f(sm[SL_AC_TR]); rec_acc_te = uni_f(sm[SL_AC_TE]);
             lg_acc += (sm[SL_LG] != 0.0f) ? 1 : 0;
             gd_valid = sweeping ? 1 : 0;
-            for (int e = tid; e < P; e += nthr) {
-                const float v = wacc[e];
-                w_cur[e] = v; rec_alt[e] = v;
-                if (sweeping) w_gd[e] = wacc[PS + e];
+            if constexpr (MULTI) {
+                for (int e = tid; e < P; e += nthr) {
+                    const float v = wacc[e];
+                    w_cur[e] = v; rec_alt[e] = v;
+                    if (sweeping) w_gd[e] = wacc[PS + e];
+                }
+            } else if (tid < cp_n) {
+                for (int e = tid; e < P; e += cp_n) {
+                    const float v = wacc[e];
+                    w_cur[e] = v; rec_alt[e] = v;
+                    if (sweeping) w_gd[e] = wacc[PS + e];
+                }
             }
             float* t_ = rec_w; rec_w = rec_alt; rec_alt = t_;
         }
+        STAMP_SUB(4);                                       // ... up to the state copy
         __syncthreads();
+        if constexpr (!MULTI) {
+            if (split && tr_t >= 0) {                       // the accepted step's row is the new rec_w, the rows before it the old one
+                pos_w_rows(rec_w, (m < kt) ? rec_alt : rec_w);
+                scalar_row();
+            }
+        }
         i += ncommit;
         tpos0 += ncommit;
         if (tpos0 >= p.trace_cap) tpos0 -= p.trace_cap;

@@ -34,13 +34,16 @@ namespace ptnn {
 constexpr int TASK_REG = 0;
 constexpr int TASK_CLS = 1;
 constexpr int WAVE = 64;
-// Diagnostic hooks.  The product build contains none of the diagnostic code: STAMP / FW_DBG / PTNN_DIAG expand to nothing.  A
+// Diagnostic hooks.  The product build contains none of the diagnostic code: STAMP / STAMP_SUB / STAMP_MH / FW_DBG / PTNN_DIAG expand to nothing.  A
 // diagnostic build (-DPTNN_STAMPS, profiles/tools/build_stamps.sh; never the product) includes ptnn_diag.hpp, which holds the
 // bodies: in-kernel cycle stamps per phase of a round, summed into SegParams::stamps and read back by ptnn_debug_stamps.
 #ifdef PTNN_STAMPS
 #include "ptnn_diag.hpp"
 #else
 #define STAMP(slot) do { } while (0)
+#define STAMP_SUB(slot) do { } while (0)
+#define STAMP_MH(slot) do { } while (0)
+#define STAMP_MH_OPERANDS(sl_, sc_, w_, l_) do { } while (0)
 #define FW_DBG(q_) do { } while (0)
 #define PTNN_DIAG(name)
 #endif

@@ -1,5 +1,5 @@
 // ptnn_diag.hpp -- DIAGNOSTIC BUILD ONLY (-DPTNN_STAMPS; profiles/tools/build_stamps.sh).  Never part of the product: ptnn_device.hpp
-// includes this file only when PTNN_STAMPS is defined, otherwise STAMP / FW_DBG / PTNN_DIAG expand to nothing.
+// includes this file only when PTNN_STAMPS is defined, otherwise STAMP / STAMP_SUB / STAMP_MH / FW_DBG / PTNN_DIAG expand to nothing.
 //
 // In-kernel cycle stamps: wave 0 of the first work-group of replica 0 adds up shader-clock cycles per phase of a round and writes
 // the sums to SegParams::stamps at the end of the launch (ptnn_debug_stamps reads and resets them; profiles/tools/stamps*.py print
@@ -17,6 +17,38 @@
             stamp_acc[slot] += t_ - stamp_last; stamp_last = t_;                             \
         }                                                                                    \
     } while (0)
+
+// A point inside a phase: the cycles from the phase's start (the last STAMP) up to here, every LDS read before it landed.  It does
+// not move the phase's start, so the phase table reads the same with and without such points.
+#define STAMP_SUB(slot)                                                                      \
+    do {                                                                                     \
+        if (stamp_on) {                                                                      \
+            const unsigned long long t_ = __builtin_amdgcn_s_memtime();                      \
+            __builtin_amdgcn_s_waitcnt(0xC07F);                                              \
+            stamp_sub[slot] += t_ - stamp_last;                                              \
+        }                                                                                    \
+    } while (0)
+
+// The two points inside Metropolis-Hastings, behind a switch of their own (-DPTNN_STAMPS_MH, e.g. EXTRA=-DPTNN_STAMPS_MH
+// build_stamps.sh): each drains the LDS queue in the middle of the phase, and the two cost it about 0.6 k cycles of 1.5 k, so a
+// plain -DPTNN_STAMPS build stamps the phase as it runs.  Point 0: what the verdict reads that does not wait for the epochs has
+// landed -- the slot's scalars sl_, the step's tape scalars sc_, w_cur w_ (l_: the lane within its 16-lane row) -- point 1: the
+// verdict is computed.
+#ifdef PTNN_STAMPS_MH
+#define STAMP_MH(slot) STAMP_SUB(slot)
+#define STAMP_MH_OPERANDS(sl_, sc_, w_, l_)                                                  \
+    do {                                                                                     \
+        if (stamp_on) {                                                                      \
+            const float a_ = (sl_)[SL_LIKPROP] + (sl_)[SL_PRIORPROP] + (sl_)[SL_LG] + (sl_)[SL_D2] + (sl_)[SL_ADAPT] + (sc_)[1] + \
+                             (w_)[l_] + (w_)[16 + (l_)];                                     \
+            asm volatile("" :: "v"(a_));                                                     \
+        }                                                                                    \
+        STAMP_SUB(0);                                                                        \
+    } while (0)
+#else
+#define STAMP_MH(slot) do { } while (0)
+#define STAMP_MH_OPERANDS(sl_, sc_, w_, l_) do { } while (0)
+#endif
 
 // cycles of the phases of eval_rows_mfma_coop / eval_rows_mfma_split (block 0, wave 0)
 static __device__ unsigned long long fw_dbg[8];
@@ -80,6 +112,7 @@ static __device__ unsigned long long fw_dbg[8];
 #define PTNN_DIAG_pack_begin \
     const bool stamp_on = (blockIdx.x == 0 && wave == 0); \
     unsigned long long stamp_acc[10] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0}; \
+    unsigned long long stamp_sub[5] = {0, 0, 0, 0, 0}; \
     unsigned long long stamp_last = __builtin_amdgcn_s_memtime(); \
     __builtin_amdgcn_s_waitcnt(0xC07F); \
     unsigned long long stamp_rounds = 0, stamp_eval = 0; \
@@ -97,6 +130,7 @@ static __device__ unsigned long long fw_dbg[8];
         atomicAdd(p.stamps + 9, stamp_rounds); \
         atomicAdd(p.stamps + 10, __builtin_amdgcn_s_memtime() - stamp_t0); \
     } \
+    if (stamp_on && lane == 0 && p.stamps) for (int q_ = 0; q_ < 5; ++q_) atomicAdd(p.stamps + 144 + q_, stamp_sub[q_]); \
     if (blockIdx.x == 0 && ev_i == 0 && lane == 0 && p.stamps) atomicAdd(p.stamps + 11, stamp_eval); \
     if (tid == 0 && p.stamps && r < 64) { \
         atomicAdd(p.stamps + 16 + 2 * r, __builtin_amdgcn_s_memtime() - stamp_t0); \

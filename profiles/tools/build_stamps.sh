@@ -1,6 +1,7 @@
 #!/bin/bash
 # Diagnostic build of libptnn with in-kernel cycle stamps (-DPTNN_STAMPS; NOSTAMPS=1: without them, e.g. for -DPTNN_ABLATE=k in $EXTRA), one shape only (default REG 4 -> 1; pass
 # "task I O" for another, e.g. `build_stamps.sh 1 34 2`).  Never the product.
+# EXTRA=-DPTNN_STAMPS_MH adds the two points inside the packed kernel's Metropolis-Hastings phase (they drain the LDS queue: ptnn_diag.hpp).
 set -e
 cd "$(dirname "$0")/../.."
 T=${1:-0}; I=${2:-4}; O=${3:-1}

@@ -20,6 +20,13 @@ print(f"{s.describe()['kernel']}: {dt*1e3/nint:.3f} ms/interval, replica 0 wave 
 for n, v in zip(names, st[:7]):
     print(f"    {n:26s} {v/max(rounds,1):9.0f} cyc/round  {100*v/tot:5.1f} %")
 print(f"    forward passes on wave 2: {st[11]/max(rounds,1):9.0f} cyc/round")
+# points inside MH and commit (STAMP_SUB): cycles from the phase's start, on wave 0; the two of MH only in a -DPTNN_STAMPS_MH build
+# (EXTRA=-DPTNN_STAMPS_MH build_stamps.sh), where they cost the phase about 0.6 k cycles
+subs = ["MH: operand reads that do not wait for the epoch", "MH: verdict computed", "commit: flags and ballot",
+        "commit: trace rows and counts", "commit: state copy"]
+for n, v in zip(subs, st[144:149]):
+    if v:
+        print(f"    {n:50s} {v/max(rounds,1):9.0f} cyc/round from the phase's start")
 per = np.array(st[16:16+128], dtype=np.float64).reshape(64, 2)
 print('   per-replica us/interval:', np.round(per[:, 0]/nint/2.4e3).astype(int).tolist())
 print('   per-replica rounds/interval:', np.round(per[:, 1]/nint, 1).tolist())
