@@ -2,6 +2,7 @@
 // sensitivity, ppc, powerscale, prior_predictive, and the sample-selection path they share.  The shape-independent analysis kernels are defined in this object: it includes them.
 #include "ptnn_shapes.hpp"
 namespace ptnn {
+#include "ptnn_dev_wg.hpp"                   // work-group reductions and scans of every kernel below (ptnn_device.hpp has included it: ladder_round)
 #include "ptnn_dev_select.hpp"               // sample selection (run-length pass over the selected rows) and the per-column predictive reduction
 #include "ptnn_dev_convergence.hpp"          // convergence diagnostics: split-R-hat, split-ESS over trace columns
 #include "ptnn_dev_elpd.hpp"                 // predictive accuracy: lppd, WAIC, PSIS-LOO per data row

@@ -8,7 +8,7 @@
 //      calib_pair_kernel: the pair term of the CRPS, rows x the triangle of (i-tile, j-tile) pairs over U.
 //      calib_finish_kernel: crps = first term - pair term.
 // A classification's p_mean is predict_reduce_kernel's mean (ptnn_dev_select.hpp), unchanged.
-// Every sum over samples is a 128-bit fixed-point sum of terms in [0, 1] (ptnn_dev_elpd.hpp: Fix128), scaled by a bound formed
+// Every sum over samples is a 128-bit fixed-point sum of terms in [0, 1] (Fix128; ptnn_dev_elpd.hpp: fix_add), scaled by a bound formed
 // from the row's exact extremes: integer addition, so a result depends on the multiset of samples only -- not on their order,
 // on how repeats are grouped, on the tiling or on the row block.  The pair kernel adds its work-groups' integer sums with
 // integer atomics (four 32-bit limbs in 64-bit words); no floating-point atomic anywhere.  fp64 throughout after f.
@@ -36,38 +36,10 @@ __global__ void __launch_bounds__(CALIB_THREADS) calib_tau_kernel(int U, const f
     tau2[u] = t2; tau[u] = t; itau[u] = 1.0 / t;
 }
 
-// block reductions over CALIB_THREADS threads (every thread gets the result; a barrier before and after), as ptnn_dev_elpd.hpp's
+// the storage of the block reductions over CALIB_THREADS threads (ptnn_dev_wg.hpp: wg_fix_sum, wg_min_max)
 struct CalibShared { unsigned long long r0[CALIB_THREADS], r1[CALIB_THREADS]; };
-__device__ double calib_fix_sum(CalibShared& sh, Fix128 a) {
-    const int tid = threadIdx.x;
-    __syncthreads();
-    sh.r0[tid] = a.lo; sh.r1[tid] = a.hi;
-    __syncthreads();
-    for (int d = CALIB_THREADS / 2; d > 0; d >>= 1) {
-        if (tid < d) {
-            const unsigned long long lo = sh.r0[tid] + sh.r0[tid + d];
-            sh.r1[tid] += sh.r1[tid + d] + (lo < sh.r0[tid] ? 1ull : 0ull);
-            sh.r0[tid] = lo;
-        }
-        __syncthreads();
-    }
-    const double v = ((double)sh.r1[0] * 0x1p64 + (double)sh.r0[0]) * 0x1p-62;
-    __syncthreads();
-    return v;
-}
 __device__ void calib_min_max(CalibShared& sh, double& mn, double& mx) {
-    const int tid = threadIdx.x;
-    double* a = reinterpret_cast<double*>(sh.r0);
-    double* b = reinterpret_cast<double*>(sh.r1);
-    __syncthreads();
-    a[tid] = mn; b[tid] = mx;
-    __syncthreads();
-    for (int d = CALIB_THREADS / 2; d > 0; d >>= 1) {
-        if (tid < d) { a[tid] = fmin(a[tid], a[tid + d]); b[tid] = fmax(b[tid], b[tid + d]); }
-        __syncthreads();
-    }
-    mn = a[0]; mx = b[0];
-    __syncthreads();
+    wg_min_max<CALIB_THREADS>(reinterpret_cast<double*>(sh.r0), reinterpret_cast<double*>(sh.r1), mn, mx);
 }
 
 struct CalibRow {
@@ -119,9 +91,9 @@ __global__ void __launch_bounds__(CALIB_THREADS) calib_row_kernel(const CalibRow
         if (R > 0.0) fix_add(fm, (fv - fmn) / R, c);
         if (a.pair) fix_add(fa, calib_A(d, 2.0 * a.tau2[u], a.itau[u] * CALIB_SQRT1_2) / B1, c);
     }
-    const double pit = calib_fix_sum(sh, fp) / S;
-    const double sm = calib_fix_sum(sh, fm);
-    const double t1 = a.pair ? B1 * (calib_fix_sum(sh, fa) / S) : 0.0;
+    const double pit = wg_fix_sum<CALIB_THREADS>(sh.r0, sh.r1, fp) / S;
+    const double sm = wg_fix_sum<CALIB_THREADS>(sh.r0, sh.r1, fm);
+    const double t1 = a.pair ? B1 * (wg_fix_sum<CALIB_THREADS>(sh.r0, sh.r1, fa) / S) : 0.0;
     double mean = R > 0.0 ? fmn + R * (sm / S) : fmn;
     mean = fmin(fmax(mean, fmn), fmx);
     // pass 3: the variance, centred on the mean
@@ -133,7 +105,7 @@ __global__ void __launch_bounds__(CALIB_THREADS) calib_row_kernel(const CalibRow
         const double d = (double)f[u] - mean;
         fix_add(fv2, (a.tau2[u] + d * d) / D, c);
     }
-    const double var = D * (calib_fix_sum(sh, fv2) / S);
+    const double var = D * (wg_fix_sum<CALIB_THREADS>(sh.r0, sh.r1, fv2) / S);
     if (tid == 0) {
         if (a.pit) a.pit[n] = pit;
         if (a.pred_mean) a.pred_mean[n] = mean;
@@ -163,7 +135,7 @@ __global__ void __launch_bounds__(CALIB_THREADS) calib_row_kernel(const CalibRow
                 if (c == 0) continue;
                 fix_add(fc, calib_Phi((mid - (double)f[u]) * a.itau[u]), c);
             }
-            const double F = calib_fix_sum(sh, fc) / S;
+            const double F = wg_fix_sum<CALIB_THREADS>(sh.r0, sh.r1, fc) / S;
             if (F < p) lo = mid; else hi = mid;
         }
         if (tid == 0) a.quantiles[(size_t)k * a.n_rows + n] = mid;
@@ -225,14 +197,7 @@ __global__ void __launch_bounds__(CALIB_THREADS) calib_pair_kernel(const CalibPa
     const unsigned long long k = (unsigned long long)ci * (ti == tj ? 1ull : 2ull);
     sh.r0[tid] = acc.lo * k; sh.r1[tid] = acc.hi * k + __umul64hi(acc.lo, k);
     __syncthreads();
-    for (int d = CALIB_THREADS / 2; d > 0; d >>= 1) {
-        if (tid < d) {
-            const unsigned long long s = sh.r0[tid] + sh.r0[tid + d];
-            sh.r1[tid] += sh.r1[tid + d] + (s < sh.r0[tid] ? 1ull : 0ull);
-            sh.r0[tid] = s;
-        }
-        __syncthreads();
-    }
+    wg_fix_tree<CALIB_THREADS>(sh.r0, sh.r1);
     if (tid < 4) {
         const unsigned long long w = (tid >> 1) ? sh.r1[0] : sh.r0[0];
         const unsigned long long limb = (tid & 1) ? (w >> 32) : (w & 0xffffffffull);

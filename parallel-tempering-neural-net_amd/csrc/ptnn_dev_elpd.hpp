@@ -68,8 +68,7 @@ __device__ __forceinline__ double elpd_unkey(unsigned long long k) {
     return __longlong_as_double((long long)((k & 0x8000000000000000ull) ? (k & 0x7fffffffffffffffull) : ~k));
 }
 
-// 128-bit fixed-point accumulator: a term t in [0, 1] counts floor(t * 2^62) units, c times -- exact integer sums
-struct Fix128 { unsigned long long lo, hi; };
+// 128-bit fixed-point accumulator (Fix128, ptnn_dev_wg.hpp): a term t in [0, 1] counts floor(t * 2^62) units, c times -- exact integer sums
 __device__ __forceinline__ void fix_add(Fix128& a, double t, unsigned c) {
     t = t > 0.0 ? (t < 1.0 ? t : 1.0) : 0.0;
     const unsigned long long v = (unsigned long long)(t * 0x1p62);
@@ -84,12 +83,6 @@ __device__ __forceinline__ double gpinv(double p, double k, double sigma) {
     return sigma * expm1(-k * log1p(-p)) / k;
 }
 
-__device__ __forceinline__ double wave_sum_d(double v) {   // fixed butterfly: the same order in every call
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o);
-    return v;
-}
-
 struct ElpdShared {
     unsigned long long tkey[ELPD_TAIL_CAP];    // tail: ~key(ll) (ascending = lw ascending), merged in place into distinct keys
     int tpos[ELPD_TAIL_CAP + 1];               // tail: counts, then each distinct key's first expanded position (tpos[G] = T)
@@ -102,51 +95,9 @@ struct ElpdShared {
     int n_ent, n_grp;
 };
 
-// block reductions (every thread gets the result; a barrier before and after)
-__device__ double block_fix_sum(ElpdShared& sh, Fix128 a) {
-    const int tid = threadIdx.x;
-    __syncthreads();
-    sh.r0[tid] = a.lo; sh.r1[tid] = a.hi;
-    __syncthreads();
-    for (int d = ELPD_THREADS / 2; d > 0; d >>= 1) {
-        if (tid < d) {
-            const unsigned long long lo = sh.r0[tid] + sh.r0[tid + d];
-            sh.r1[tid] += sh.r1[tid + d] + (lo < sh.r0[tid] ? 1ull : 0ull);
-            sh.r0[tid] = lo;
-        }
-        __syncthreads();
-    }
-    const double v = ((double)sh.r1[0] * 0x1p64 + (double)sh.r0[0]) * 0x1p-62;
-    __syncthreads();
-    return v;
-}
+// the extremes over the work-group through r0, r1 (every thread gets them; a barrier before and after)
 __device__ void block_min_max(ElpdShared& sh, double& mn, double& mx) {
-    const int tid = threadIdx.x;
-    double* a = reinterpret_cast<double*>(sh.r0);
-    double* b = reinterpret_cast<double*>(sh.r1);
-    __syncthreads();
-    a[tid] = mn; b[tid] = mx;
-    __syncthreads();
-    for (int d = ELPD_THREADS / 2; d > 0; d >>= 1) {
-        if (tid < d) { a[tid] = fmin(a[tid], a[tid + d]); b[tid] = fmax(b[tid], b[tid + d]); }
-        __syncthreads();
-    }
-    mn = a[0]; mx = b[0];
-    __syncthreads();
-}
-__device__ long long block_sum_ll(ElpdShared& sh, long long v) {
-    const int tid = threadIdx.x;
-    long long* a = reinterpret_cast<long long*>(sh.r0);
-    __syncthreads();
-    a[tid] = v;
-    __syncthreads();
-    for (int d = ELPD_THREADS / 2; d > 0; d >>= 1) {
-        if (tid < d) a[tid] += a[tid + d];
-        __syncthreads();
-    }
-    v = a[0];
-    __syncthreads();
-    return v;
+    wg_min_max<ELPD_THREADS>(reinterpret_cast<double*>(sh.r0), reinterpret_cast<double*>(sh.r1), mn, mx);
 }
 // exclusive scan of one int per thread in thread order; *total = the sum
 __device__ int block_excl_scan(int* buf, int v, int* total) {
@@ -154,12 +105,7 @@ __device__ int block_excl_scan(int* buf, int v, int* total) {
     __syncthreads();
     buf[tid] = v;
     __syncthreads();
-    for (int d = 1; d < ELPD_THREADS; d <<= 1) {
-        const int add = tid >= d ? buf[tid - d] : 0;
-        __syncthreads();
-        buf[tid] += add;
-        __syncthreads();
-    }
+    wg_incl_scan<ELPD_THREADS>(buf, tid);
     const int incl = buf[tid];
     *total = buf[ELPD_THREADS - 1];
     __syncthreads();
@@ -236,7 +182,7 @@ __device__ void psis_reduce(ElpdShared& sh, unsigned long long* tval, const Src&
             }
         }
     }
-    const long long T = block_sum_ll(sh, t_part);                // (barriers inside: n_ent is final)
+    const long long T = wg_sum<ELPD_THREADS>(reinterpret_cast<long long*>(sh.r0), t_part);   // (barriers inside: n_ent is final)
     const int n_ent = min(sh.n_ent, ELPD_TAIL_CAP);              // the host keeps T <= M <= ELPD_TAIL_CAP
     double khat = INF, sigma = 0.0;
     bool smooth = false;
@@ -324,7 +270,7 @@ __device__ void psis_reduce(ElpdShared& sh, unsigned long long* tval, const Src&
             const double b = sh.gb[i];
             double s = 0.0;
             for (int g = lane; g < G; g += WAVE) s += (double)(sh.tpos[g + 1] - sh.tpos[g]) * log1p(-b * x_of(g));
-            s = wave_sum_d(s);
+            s = wave_sum(s);
             if (lane == 0) {
                 const double k = s / n;
                 sh.gk[i] = n * (log(-b / k) - k - 1.0);               // the profile log-likelihood L[i]
@@ -350,7 +296,7 @@ __device__ void psis_reduce(ElpdShared& sh, unsigned long long* tval, const Src&
         const double bpost = sh.bc[0];
         double s = 0.0;
         for (int g = tid; g < G; g += ELPD_THREADS) s += (double)(sh.tpos[g + 1] - sh.tpos[g]) * log1p(-bpost * x_of(g));
-        s = wave_sum_d(s);
+        s = wave_sum(s);
         __syncthreads();
         if (lane == 0) reinterpret_cast<double*>(sh.r0)[wave] = s;
         __syncthreads();
@@ -410,8 +356,8 @@ __device__ void psis_reduce(ElpdShared& sh, unsigned long long* tval, const Src&
         fix_add(fz, exp(lw - a1), 1u);
         fix_add(fl, exp(lw + l - b2), 1u);
     }
-    const double z = block_fix_sum(sh, fz);
-    const double e = block_fix_sum(sh, fl);
+    const double z = wg_fix_sum<ELPD_THREADS>(sh.r0, sh.r1, fz);
+    const double e = wg_fix_sum<ELPD_THREADS>(sh.r0, sh.r1, fl);
     *elpd = (b2 + log(e)) - (a1 + log(z));
     *khat_out = khat;
     *tail_out = T;
@@ -459,8 +405,8 @@ __global__ void __launch_bounds__(ELPD_THREADS) elpd_reduce_kernel(const ElpdRed
         fix_add(fe, exp(l - mx), c);
         if (R > 0.0) fix_add(fm, (l - mn) / R, c);
     }
-    const double se = block_fix_sum(sh, fe);
-    const double sm = block_fix_sum(sh, fm);
+    const double se = wg_fix_sum<ELPD_THREADS>(sh.r0, sh.r1, fe);
+    const double sm = wg_fix_sum<ELPD_THREADS>(sh.r0, sh.r1, fm);
     const double lppd = mx + log(se / S);
     double mean = R > 0.0 ? mn + R * (sm / S) : mn;
     mean = fmin(fmax(mean, mn), mx);
@@ -475,7 +421,7 @@ __global__ void __launch_bounds__(ELPD_THREADS) elpd_reduce_kernel(const ElpdRed
             fix_add(fv, (d * d) / D, c);
         }
     }
-    const double p_waic = D > 0.0 ? D * block_fix_sum(sh, fv) / (S - 1.0) : 0.0;
+    const double p_waic = D > 0.0 ? D * wg_fix_sum<ELPD_THREADS>(sh.r0, sh.r1, fv) / (S - 1.0) : 0.0;
 
     // the Pareto smoothing of lr = -ll (lw = lr - max(lr) = min(ll) - ll) with the target ll
     const ElpdLooSrc src{a, r, y, mn};

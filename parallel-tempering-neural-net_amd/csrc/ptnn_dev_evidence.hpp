@@ -75,33 +75,6 @@ __global__ void __launch_bounds__(EVID_THREADS) evid_conv_kernel(int K, int n, c
     draws[j] = (float)u_draw[off[rung[q]] + i];
 }
 
-__device__ __forceinline__ double evid_block_sum(double v, double* red) {     // fixed tree; every thread gets the total
-    const int tid = threadIdx.x;
-    __syncthreads();
-    red[tid] = v;
-    __syncthreads();
-    for (int d = EVID_THREADS / 2; d > 0; d >>= 1) {
-        if (tid < d) red[tid] += red[tid + d];
-        __syncthreads();
-    }
-    const double s = red[0];
-    __syncthreads();
-    return s;
-}
-__device__ __forceinline__ double evid_block_max(double v, double* red) {
-    const int tid = threadIdx.x;
-    __syncthreads();
-    red[tid] = v;
-    __syncthreads();
-    for (int d = EVID_THREADS / 2; d > 0; d >>= 1) {
-        if (tid < d) red[tid] = fmax(red[tid], red[tid + d]);
-        __syncthreads();
-    }
-    const double s = red[0];
-    __syncthreads();
-    return s;
-}
-
 // stage d: one work-group per rung k over its draws u_draw[off[k] .. off[k + 1])
 struct EvidRung {
     const double* u_draw;
@@ -117,22 +90,22 @@ __global__ void __launch_bounds__(EVID_THREADS) evid_rung_kernel(const EvidRung 
     const long long n = a.off[k + 1] - a.off[k];
     double s = 0.0;
     for (long long i = tid; i < n; i += EVID_THREADS) s += x[i];
-    const double mean = evid_block_sum(s, red) / (double)n;
+    const double mean = wg_sum<EVID_THREADS>(red, s) / (double)n;
     double q = 0.0;
     for (long long i = tid; i < n; i += EVID_THREADS) { const double c = x[i] - mean; q += c * c; }
-    const double var = evid_block_sum(q, red) / (double)(n - 1);
+    const double var = wg_sum<EVID_THREADS>(red, q) / (double)(n - 1);
     if (tid == 0) { a.mean[k] = mean; a.var[k] = var; }
     if (!a.d) return;
     const double dk = a.d[k];
     double mx = -INFINITY;
     for (long long i = tid; i < n; i += EVID_THREADS) mx = fmax(mx, dk * x[i]);
-    mx = evid_block_max(mx, red);
+    mx = wg_max<EVID_THREADS>(red, mx);
     double e = 0.0;
     for (long long i = tid; i < n; i += EVID_THREADS) e += exp(dk * x[i] - mx);
-    const double me = evid_block_sum(e, red) / (double)n;
+    const double me = wg_sum<EVID_THREADS>(red, e) / (double)n;
     double ve = 0.0;
     for (long long i = tid; i < n; i += EVID_THREADS) { const double c = exp(dk * x[i] - mx) - me; ve += c * c; }
-    ve = evid_block_sum(ve, red) / (double)(n - 1);
+    ve = wg_sum<EVID_THREADS>(red, ve) / (double)(n - 1);
     if (tid == 0) { a.log_stone[k] = mx + log(me); a.relvar[k] = ve / (me * me); }
 }
 
@@ -171,21 +144,21 @@ __global__ void __launch_bounds__(EVID_THREADS) evid_prior_reduce_kernel(const E
     const double aj = r.a[j];
     double mx = -INFINITY;
     for (long long i = tid; i < r.n; i += EVID_THREADS) mx = fmax(mx, r.b[i] + aj * r.u[i]);
-    mx = evid_block_max(mx, red);
+    mx = wg_max<EVID_THREADS>(red, mx);
     double s0 = 0.0, s1 = 0.0, su = 0.0;
     for (long long i = tid; i < r.n; i += EVID_THREADS) {
         const double w = exp(r.b[i] + aj * r.u[i] - mx);
         s0 += w; s1 += w * w; su += w * r.u[i];
     }
-    s0 = evid_block_sum(s0, red);
-    s1 = evid_block_sum(s1, red);
-    const double mu = evid_block_sum(su, red) / s0;
+    s0 = wg_sum<EVID_THREADS>(red, s0);
+    s1 = wg_sum<EVID_THREADS>(red, s1);
+    const double mu = wg_sum<EVID_THREADS>(red, su) / s0;
     double sv = 0.0;
     for (long long i = tid; i < r.n; i += EVID_THREADS) {
         const double w = exp(r.b[i] + aj * r.u[i] - mx), c = r.u[i] - mu;
         sv += w * c * c;
     }
-    sv = evid_block_sum(sv, red);
+    sv = wg_sum<EVID_THREADS>(red, sv);
     if (tid == 0) {
         r.lme[j] = mx + log(s0 / (double)r.n);
         r.kish[j] = s0 * s0 / s1;

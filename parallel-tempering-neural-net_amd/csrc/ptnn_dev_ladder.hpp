@@ -38,7 +38,7 @@ __device__ __noinline__ bool ladder_round(const int R, const int round, const in
         const int lane = threadIdx.x;
         double part = 0.0;
         for (int k = lane; k < n; k += WAVE) part += (double)sA[k];
-        for (int o = WAVE / 2; o > 0; o >>= 1) part += __shfl_xor(part, o);     // a + b == b + a: every lane holds the same sum
+        part = wave_sum(part);                                                  // a + b == b + a: every lane holds the same sum
         const double abar = part / (double)n;
         const double kap = kappa0 * t0 / ((double)round + t0);
         const double* s_old = lad_s + (size_t)(round & 1) * n;

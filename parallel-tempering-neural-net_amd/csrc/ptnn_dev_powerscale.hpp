@@ -43,7 +43,7 @@ __global__ void __launch_bounds__(PS_THREADS) powerscale_prior_kernel(const PsPr
     const float* w = a.base + a.run_off[u];
     double s = 0.0;
     for (int p = lane; p < a.P; p += WAVE) { const double v = (double)w[p]; s += v * v; }
-    s = wave_sum_d(s);
+    s = wave_sum(s);
     if (lane == 0) {
         double pr = a.part1 - a.inv_2sig2 * s;
         if (a.reg) {
@@ -52,21 +52,6 @@ __global__ void __launch_bounds__(PS_THREADS) powerscale_prior_kernel(const PsPr
         }
         a.out[u] = pr;
     }
-}
-
-// fixed tree over one double per thread (every thread gets the sum; a barrier before and after)
-__device__ double ps_block_sum(double* buf, double v) {
-    const int tid = threadIdx.x;
-    __syncthreads();
-    buf[tid] = v;
-    __syncthreads();
-    for (int d = PS_THREADS / 2; d > 0; d >>= 1) {
-        if (tid < d) buf[tid] += buf[tid + d];
-        __syncthreads();
-    }
-    v = buf[0];
-    __syncthreads();
-    return v;
 }
 
 // 2. the Pareto smoothing of lr = (alpha - 1) c_u
@@ -125,7 +110,7 @@ __global__ void __launch_bounds__(ELPD_THREADS) powerscale_smooth_kernel(const P
         mn = fmin(mn, v); mx = fmax(mx, v);
     }
     block_min_max(sh, mn, mx);
-    live = block_sum_ll(sh, live);
+    live = wg_sum<ELPD_THREADS>(reinterpret_cast<long long*>(sh.r0), live);
     const PsSrc src{c, a.cnt, am1, mx, wt, tail_lw, tail_u};
     double e, khat;
     long long T;
@@ -144,7 +129,7 @@ __global__ void __launch_bounds__(ELPD_THREADS) powerscale_smooth_kernel(const P
     __syncthreads();
     double part = 0.0;
     for (int u = tid; u < a.U; u += ELPD_THREADS) part += wt[u];
-    const double total = ps_block_sum(reinterpret_cast<double*>(sh.r0), part);
+    const double total = wg_sum<ELPD_THREADS>(reinterpret_cast<double*>(sh.r0), part);
     for (int u = tid; u < a.U; u += ELPD_THREADS) wt[u] = wt[u] / total;
     if (tid == 0) {
         a.khat[k] = khat;
@@ -264,12 +249,7 @@ __device__ double ps_side(PsDistShared& sh, const unsigned long long* seg, const
     __syncthreads();
     sh.cp[tid] = sp; sh.cq[tid] = sq;
     __syncthreads();
-    for (int d = 1; d < PS_THREADS; d <<= 1) {                   // inclusive scan of the chunk sums: a fixed tree, 8 steps
-        const double ap = tid >= d ? sh.cp[tid - d] : 0.0, aq = tid >= d ? sh.cq[tid - d] : 0.0;
-        __syncthreads();
-        sh.cp[tid] += ap; sh.cq[tid] += aq;
-        __syncthreads();
-    }
+    wg_incl_scan<PS_THREADS>(sh.cp, sh.cq, tid);                 // inclusive scan of the chunk sums: a fixed tree, 8 steps
     double P = tid ? sh.cp[tid - 1] : 0.0, Q = tid ? sh.cq[tid - 1] : 0.0, num = 0.0, den = 0.0;   // exclusive prefixes
     for (int r = r0; r < r1 && r < n - 1; ++r) {
         const unsigned long long w0 = seg[rev ? n - 1 - r : r], w1 = seg[rev ? n - 2 - r : r + 1];
@@ -281,8 +261,8 @@ __device__ double ps_side(PsDistShared& sh, const unsigned long long* seg, const
         num += b * (ps_h(P, l2m) + ps_h(Q, l2m));
         den += b * (P + Q);
     }
-    num = ps_block_sum(sh.red, num);
-    den = ps_block_sum(sh.red, den);
+    num = wg_sum<PS_THREADS>(sh.red, num);
+    den = wg_sum<PS_THREADS>(sh.red, den);
     return num / den;
 }
 
@@ -302,8 +282,8 @@ __global__ void __launch_bounds__(PS_THREADS) powerscale_distance_kernel(const P
         const double x = (double)pred_unkey((unsigned)(w >> 32));
         mb += (double)a.cnt[u] / a.M * x; mw += wt[u] * x;
     }
-    mb = ps_block_sum(sh.red, mb);
-    mw = ps_block_sum(sh.red, mw);
+    mb = wg_sum<PS_THREADS>(sh.red, mb);
+    mw = wg_sum<PS_THREADS>(sh.red, mw);
     double vb = 0.0, vw = 0.0;
     for (int r = r0; r < r1; ++r) {
         const unsigned long long w = seg[r];
@@ -311,8 +291,8 @@ __global__ void __launch_bounds__(PS_THREADS) powerscale_distance_kernel(const P
         const double x = (double)pred_unkey((unsigned)(w >> 32));
         vb += (double)a.cnt[u] / a.M * ((x - mb) * (x - mb)); vw += wt[u] * ((x - mw) * (x - mw));
     }
-    vb = ps_block_sum(sh.red, vb);
-    vw = ps_block_sum(sh.red, vw);
+    vb = wg_sum<PS_THREADS>(sh.red, vb);
+    vw = wg_sum<PS_THREADS>(sh.red, vw);
     // the distance: 0 when every value is the same (no gap), else the larger of the two sides
     double d = 0.0;
     if (n > 1 && (seg[0] >> 32) != (seg[n - 1] >> 32) &&

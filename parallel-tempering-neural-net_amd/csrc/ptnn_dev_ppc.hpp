@@ -42,28 +42,6 @@ struct PpcJob {
     int* y_rep;                 // [M][n_rows] or null (classification)
 };
 
-// all-lanes butterfly reductions of one wave: every lane ends with the same bits (a + b and b + a are the same double)
-__device__ __forceinline__ double ppc_wave_sum(double v) {
-#pragma unroll
-    for (int m = WAVE / 2; m > 0; m >>= 1) v += __shfl_xor(v, m);
-    return v;
-}
-__device__ __forceinline__ double ppc_wave_min(double v) {
-#pragma unroll
-    for (int m = WAVE / 2; m > 0; m >>= 1) v = fmin(v, __shfl_xor(v, m));
-    return v;
-}
-__device__ __forceinline__ double ppc_wave_max(double v) {
-#pragma unroll
-    for (int m = WAVE / 2; m > 0; m >>= 1) v = fmax(v, __shfl_xor(v, m));
-    return v;
-}
-__device__ __forceinline__ long long ppc_wave_sum_i(long long v) {
-#pragma unroll
-    for (int m = WAVE / 2; m > 0; m >>= 1) v += __shfl_xor(v, m);
-    return v;
-}
-
 // statistics 0-3 of a series x(n), n < N, lane l holding n = l, l + 64, ...: mean, population sd (centred: a second pass), min, max
 template <class F>
 __device__ __forceinline__ void ppc_level_stats(F x, int N, int lane, double* out) {
@@ -73,14 +51,14 @@ __device__ __forceinline__ void ppc_level_stats(F x, int N, int lane, double* ou
         const double v = x(n);
         s += v; mn = fmin(mn, v); mx = fmax(mx, v);
     }
-    const double m = ppc_wave_sum(s) / (double)N;
+    const double m = wave_sum(s) / (double)N;
     double c = 0.0;
     for (int n = lane; n < N; n += WAVE) {
         const double d = x(n) - m;
         c += d * d;
     }
-    c = ppc_wave_sum(c);
-    mn = ppc_wave_min(mn); mx = ppc_wave_max(mx);
+    c = wave_sum(c);
+    mn = wave_min(mn); mx = wave_max(mx);
     if (m != m) { mn = m; mx = m; }                    // fmin / fmax drop a NaN; the mean does not
     if (lane == 0) { out[0] = m; out[1] = sqrt(c / (double)N); out[2] = mn; out[3] = mx; }
 }
@@ -92,9 +70,9 @@ __device__ __forceinline__ void ppc_resid_stats(const double* v, int N, const Pp
         const double x = v[n];
         s += x; q += x * x; mx = fmax(mx, fabs(x));
     }
-    const double m = ppc_wave_sum(s) / (double)N;
-    q = ppc_wave_sum(q);
-    mx = ppc_wave_max(mx);
+    const double m = wave_sum(s) / (double)N;
+    q = wave_sum(q);
+    mx = wave_max(mx);
     if (q != q) mx = q;
     double c0 = 0.0, ck[PPC_MAX_LAGS];
 #pragma unroll
@@ -106,12 +84,12 @@ __device__ __forceinline__ void ppc_resid_stats(const double* v, int N, const Pp
         for (int j = 0; j < PPC_MAX_LAGS; ++j)
             if (j < a.n_lags && n >= a.lags[j]) ck[j] += d * (v[n - a.lags[j]] - m);
     }
-    c0 = ppc_wave_sum(c0);
+    c0 = wave_sum(c0);
     double lb = 0.0;
 #pragma unroll
     for (int j = 0; j < PPC_MAX_LAGS; ++j) {
         if (j < a.n_lags) {
-            const double r = ppc_wave_sum(ck[j]) / c0;
+            const double r = wave_sum(ck[j]) / c0;
             lb += r * r / (double)(N - a.lags[j]);
             if (lane == 0) out[PPC_REG_FIXED + j] = r;
         }
@@ -217,8 +195,8 @@ __global__ void __launch_bounds__(PPC_THREADS) ppc_occurrence_kernel(const PpcJo
                 ppc_class_row(p, nu, O, label, arg, dev, hits, count);
             }
         }
-        dev = ppc_wave_sum(dev);
-        hits = ppc_wave_sum_i(hits);
+        dev = wave_sum(dev);
+        hits = wave_sum(hits);
         gsync<true>();
         if (lane == 0) { out[0] = dev; out[1] = (double)hits / (double)N; }
         for (int k = lane; k < O; k += WAVE) out[PPC_CLS_FIXED + k] = (double)count[k];
@@ -240,34 +218,6 @@ struct PpcReduce {
     double* var_rep;
 };
 
-// block sums over PPC_THREADS threads in a fixed tree; every thread gets the result
-__device__ double ppc_block_sum(double* sh, double v) {
-    const int tid = threadIdx.x;
-    __syncthreads();
-    sh[tid] = v;
-    __syncthreads();
-    for (int d = PPC_THREADS / 2; d > 0; d >>= 1) {
-        if (tid < d) sh[tid] += sh[tid + d];
-        __syncthreads();
-    }
-    const double r = sh[0];
-    __syncthreads();
-    return r;
-}
-__device__ long long ppc_block_sum_i(long long* sh, long long v) {
-    const int tid = threadIdx.x;
-    __syncthreads();
-    sh[tid] = v;
-    __syncthreads();
-    for (int d = PPC_THREADS / 2; d > 0; d >>= 1) {
-        if (tid < d) sh[tid] += sh[tid + d];
-        __syncthreads();
-    }
-    const long long r = sh[0];
-    __syncthreads();
-    return r;
-}
-
 // thread t takes the occurrences t, t + 256, ...: the order of every double sum is fixed by M; an occurrence whose T is not
 // finite on either side adds nothing anywhere
 __global__ void __launch_bounds__(PPC_THREADS) ppc_reduce_kernel(const PpcReduce a) {
@@ -282,15 +232,15 @@ __global__ void __launch_bounds__(PPC_THREADS) ppc_reduce_kernel(const PpcReduce
         ++nd; ng += tr > to; ne += tr == to;
         so += to; sr += tr;
     }
-    nd = ppc_block_sum_i(shi, nd); ng = ppc_block_sum_i(shi, ng); ne = ppc_block_sum_i(shi, ne);
-    const double mo = ppc_block_sum(shd, so) / (double)nd, mr = ppc_block_sum(shd, sr) / (double)nd;
+    nd = wg_sum<PPC_THREADS>(shi, nd); ng = wg_sum<PPC_THREADS>(shi, ng); ne = wg_sum<PPC_THREADS>(shi, ne);
+    const double mo = wg_sum<PPC_THREADS>(shd, so) / (double)nd, mr = wg_sum<PPC_THREADS>(shd, sr) / (double)nd;
     double c = 0.0;
     for (long long i = tid; i < a.M; i += PPC_THREADS) {
         const double to = a.t_obs[(size_t)a.occ_u[i] * a.n_stats + j], tr = a.t_rep[(size_t)i * a.n_stats + j];
         if (!(isfinite(to) && isfinite(tr))) continue;
         c += (tr - mr) * (tr - mr);
     }
-    c = ppc_block_sum(shd, c);
+    c = wg_sum<PPC_THREADS>(shd, c);
     if (tid == 0) {
         a.n_defined[j] = nd; a.n_greater[j] = ng; a.n_equal[j] = ne;
         a.mean_obs[j] = mo; a.mean_rep[j] = mr; a.var_rep[j] = c / (double)nd;

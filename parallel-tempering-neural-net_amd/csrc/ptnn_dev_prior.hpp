@@ -20,7 +20,6 @@ constexpr int PRIOR_MAX_SCALES = 8;       // include/ptnn.h: PTNN_PRIOR_MAX_SCAL
 constexpr int PRIOR_REG_STATS = 7;        // mean, sd, min, max, acf1, rmse, saturated
 constexpr int PRIOR_CLS_FIXED = 4;        // accuracy, log_score, confidence, saturated; then class_share per class
 constexpr int PRIOR_CLASS_GROUP = 16;     // classes whose counts one walk over the rows keeps in registers
-static_assert(PRIOR_THREADS == EVID_THREADS && PRIOR_THREADS == PPC_THREADS, "prior_stat_kernel uses their block sums");
 
 __device__ __forceinline__ double prior_nan() { return __longlong_as_double(0x7ff8000000000000ll); }
 
@@ -33,7 +32,7 @@ __global__ void __launch_bounds__(PRIOR_THREADS) prior_saturation_kernel(const f
         const double v = (double)f[u];
         c += (v < eps || v > 1.0 - eps) ? 1 : 0;
     }
-    c = ppc_block_sum_i(shi, c);
+    c = wg_sum<PRIOR_THREADS>(shi, c);
     if (threadIdx.x == 0) count[blockIdx.x] = c;
 }
 
@@ -177,15 +176,15 @@ __global__ void __launch_bounds__(PRIOR_THREADS) prior_stat_kernel(const PriorSt
         ++nd; ng += v > to; ne += v == to;
         s += v;
     }
-    nd = ppc_block_sum_i(shi, nd); ng = ppc_block_sum_i(shi, ng); ne = ppc_block_sum_i(shi, ne);
-    const double m = evid_block_sum(s, shd) / (double)nd;
+    nd = wg_sum<PRIOR_THREADS>(shi, nd); ng = wg_sum<PRIOR_THREADS>(shi, ng); ne = wg_sum<PRIOR_THREADS>(shi, ne);
+    const double m = wg_sum<PRIOR_THREADS>(shd, s) / (double)nd;
     double c = 0.0;
     for (long long i = tid; i < a.n; i += PRIOR_THREADS) {
         const double v = x[i];
         if (v != v) continue;
         c += (v - m) * (v - m);
     }
-    c = evid_block_sum(c, shd);
+    c = wg_sum<PRIOR_THREADS>(shd, c);
     if (tid == 0) {
         a.mean[j] = m; a.sd[j] = sqrt(c / (double)nd);
         a.n_greater[j] = ng; a.n_equal[j] = ne; a.n_defined[j] = nd;

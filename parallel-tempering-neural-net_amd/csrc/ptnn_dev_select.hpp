@@ -106,12 +106,7 @@ __global__ void __launch_bounds__(PRED_SCAN_THREADS) predict_scan_kernel(const P
     for (long long i = lo; i < hi; ++i) c += s.flag[i];
     part[tid] = c;
     __syncthreads();
-    for (int d = 1; d < PRED_SCAN_THREADS; d <<= 1) {      // inclusive scan of the per-thread run starts
-        const long long add = tid >= d ? part[tid - d] : 0;
-        __syncthreads();
-        part[tid] += add;
-        __syncthreads();
-    }
+    wg_incl_scan<PRED_SCAN_THREADS>(part, tid);            // inclusive scan of the per-thread run starts
     long long r = part[tid] - c - 1;                        // index of the run in progress before this thread's first item
     for (long long i = lo; i < hi; ++i) {
         if (s.flag[i]) { ++r; s.run_off[r] = s.item_off[i]; }
@@ -173,10 +168,7 @@ __global__ void __launch_bounds__(PRED_THREADS) predict_reduce_kernel(const Pred
     vsum[tid] = votes;
     if (tid < r.n_ranks) { prefix[tid] = 0u; krem[tid] = r.ranks[tid]; }
     __syncthreads();
-    for (int d = PRED_THREADS / 2; d > 0; d >>= 1) {
-        if (tid < d) { dsum[tid] += dsum[tid + d]; vsum[tid] += vsum[tid + d]; }
-        __syncthreads();
-    }
+    wg_tree<PRED_THREADS>([&](int i, int j) { dsum[i] += dsum[j]; vsum[i] += vsum[j]; });
     if (tid == 0) {
         r.mean[r.col0 + col] = dsum[0] / (double)r.M;
         if (r.votes) r.votes[r.col0 + col] = vsum[0];

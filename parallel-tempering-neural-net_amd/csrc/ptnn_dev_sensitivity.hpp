@@ -176,10 +176,7 @@ __global__ void __launch_bounds__(PRED_THREADS) sensitivity_sign_kernel(const Se
     psum[tid] = p;
     nsum[tid] = n;
     __syncthreads();
-    for (int d = PRED_THREADS / 2; d > 0; d >>= 1) {
-        if (tid < d) { psum[tid] += psum[tid + d]; nsum[tid] += nsum[tid + d]; }
-        __syncthreads();
-    }
+    wg_tree<PRED_THREADS>([&](int i, int j) { psum[i] += psum[j]; nsum[i] += nsum[j]; });
     if (tid == 0) { r.pos[r.col0 + col] = psum[0]; r.neg[r.col0 + col] = nsum[0]; }
 }
 
@@ -237,10 +234,7 @@ __global__ void __launch_bounds__(PRED_THREADS) sensitivity_mean_kernel(const Se
     asum[tid] = sa;
     qsum[tid] = sq;
     __syncthreads();
-    for (int d = PRED_THREADS / 2; d > 0; d >>= 1) {
-        if (tid < d) { asum[tid] += asum[tid + d]; qsum[tid] += qsum[tid + d]; }
-        __syncthreads();
-    }
+    wg_tree<PRED_THREADS>([&](int i, int j) { asum[i] += asum[j]; qsum[i] += qsum[j]; });
     if (tid == 0) { r.abs_mean[oi] = asum[0] / (double)r.M; r.sq_mean[oi] = qsum[0] / (double)r.M; }
 }
 

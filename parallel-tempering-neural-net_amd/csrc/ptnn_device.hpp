@@ -145,6 +145,7 @@ struct SegDyn {
 };
 
 #include "ptnn_dev_math.hpp"                 // scalar math, the Philox tape, wave reductions, LDS helpers, the hand-scheduled SGD rows of the 4-H-1 nets
+#include "ptnn_dev_wg.hpp"                   // fixed-order work-group trees and scans, the 64-lane butterfly: the analysis kernels and ladder_round
 #include "ptnn_dev_sweep_forward.hpp"        // R4/R5 the SGD epoch (sgd_sweep), R1-R3/R6/R7 forward image, eval_rows, likelihood / prior / proposal ratio, chain start-up
 #include "ptnn_dev_coop.hpp"                 // cooperative schedule: matrix-core forward passes (exact fp32 / split bf16 operands) and segment_body
 #include "ptnn_dev_spec.hpp"                 // speculative schedules: slots, {tag, value} granules (agent scope / through an XCD's L2), the swap cascade, PersistParams, segment_spec_body

@@ -1,0 +1,246 @@
+"""The work-group reductions and scans of the posterior-analysis kernels (csrc/ptnn_dev_wg.hpp) held BIT FOR BIT to the outputs
+recorded before they were gathered into one header (tests/golden/analysis_bits_parent.npz, written by
+profiles/tools/record_analysis_bits.py on the commit before that change): the helpers may change how the source reads, never an
+operation, its order or a barrier.
+
+One call each of predict, sensitivity, elpd, lfo, evidence, calibration, ppc, powerscale and prior_predictive on a regression
+net (4-5-1) and a classification net (4-12-3) with 24 data rows, from host-given samples: U distinct vectors with multiplicities
+2 .. 4, U = 100 (threads of the 256-wide trees hold the identity), 256 (one item per thread) and 300 (the strided second pass;
+the ragged last chunk of powerscale's prefix sums).  Every output of every call is compared as bits, a NaN with a NaN.  One
+headline output per call is also held to the float64 reference of that analysis's own GPU test at that test's tolerance, so a
+golden recorded from a broken build fails here on its own account."""
+import hashlib
+import tempfile
+
+import numpy as np
+import pytest
+
+import calibration_ref
+import elpd_ref
+import evidence_ref
+import lfo_ref
+import parity
+import prior_ref
+from parity import orc
+from test_gpu_analysis_shapes import _data, _vectors
+from test_gpu_calibration import _check_oracle_forward
+from test_gpu_elpd import ATOL, _oracle_ll
+from test_gpu_powerscale import check_oracle as powerscale_check_oracle
+from test_gpu_ppc import check_occurrences
+from test_gpu_predict import _outputs, _pt
+from test_gpu_sensitivity import _worst_ratio
+from test_prior_cpu import ATOL as PRIOR_ATOL, RTOL as PRIOR_RTOL
+
+pytestmark = pytest.mark.gpu
+
+GOLDEN_FILE = "analysis_bits_parent.npz"
+REG, CLS = orc.TASK_REG, orc.TASK_CLS
+NETS = {"reg": (REG, (4, 5, 1)), "cls": (CLS, (4, 12, 3))}
+US = (100, 256, 300)
+N_ROWS = 24
+CASES = [(net, U) for net in NETS for U in US]
+CALLS = ("predict", "sensitivity", "elpd", "lfo", "evidence", "calibration", "ppc", "powerscale", "prior_predictive")
+N_FIT, ORIGINS, BLOCK = 16, (8, 12, 16, 20), 2
+LAGS = (1, 2, 3)
+QUANTILES = (0.05, 0.5, 0.95)
+STONES = (0.3, 0.0)                   # evidence: two rungs of U / 2 vectors each
+PRIOR_A = (0.0, 0.5)
+SEED = 0x5EED_0000_0B17
+EPS = 0.01
+
+_HANDLES = {}
+
+
+def handle(net):
+    """(ParallelTempering object, its training rows): one per net for the whole module, 24 rows, no run (every sample is
+    host-given)."""
+    if net not in _HANDLES:
+        task, topo = NETS[net]
+        train, test = _data(task, topo, 11 + task, n_tr=N_ROWS, n_te=N_ROWS)
+        kw = dict(lr=0.01, maxtemp=10) if task == CLS else {}
+        tmp = tempfile.TemporaryDirectory()                           # (nothing is written: write_files=False)
+        _HANDLES[net] = (_pt(task, topo, train, test, 4, 20, tmp.name, **kw), train, tmp)
+    return _HANDLES[net][:2]
+
+
+def samples(net, U):
+    """(distinct vectors [U, P] fp32, eta [U] fp32 or None, multiplicities [U] in 2 .. 4)."""
+    task, topo = NETS[net]
+    w = _vectors(topo, U, 1000 * task + U, spread=0.2)
+    rng = np.random.default_rng(7 * U + task)
+    mult = rng.integers(2, 5, U).astype(np.int32)
+    eta = rng.normal(-3.0, 0.3, U).astype(np.float32) if task == REG else None
+    return w, eta, mult
+
+
+def run_calls(pt, net, U):
+    """{call: the binding's whole result} of the nine calls of one case."""
+    task, topo = NETS[net]
+    s = pt._sampler
+    w, eta, mult = samples(net, U)
+    M = int(mult.sum())
+    ranks = (0, M // 2, M - 1)
+    groups = [g for g in ("weights", "eta", "predictions", "loglik") if g != "eta" or task == REG]
+    out = {}
+    out["predict"] = s.predict("train", w=w, multiplicity=mult, ranks=ranks, vote=task == CLS)
+    out["sensitivity"] = s.sensitivity("train", w=w, multiplicity=mult, ranks=ranks, ranks2=ranks)
+    out["elpd"] = s.elpd("train", w=w, eta=eta, multiplicity=mult)
+    out["lfo"] = s.lfo("train", n_fit=N_FIT, origins=ORIGINS, block=BLOCK, w=w, eta=eta, multiplicity=mult)
+    out["evidence"] = s.evidence(w=w.reshape(2, U // 2, -1), multiplicity=mult.reshape(2, U // 2), d=STONES, n_prior=U, seed=SEED,
+                                 a=PRIOR_A, u_out=True, u_prior_out=True)
+    out["calibration"] = s.calibration("train", w=w, eta=eta, multiplicity=mult, quantiles=QUANTILES if task == REG else ())
+    out["ppc"] = s.ppc("train", w=w, eta=eta, multiplicity=mult, lags=LAGS if task == REG else (), seed=SEED, samples=False)
+    out["powerscale"] = s.powerscale("train", groups=groups, w=w, eta=eta, multiplicity=mult)
+    out["prior_predictive"] = s.prior_predictive("train", n_draws=U, seed=SEED, ranks=(0, U // 2, U - 1), eps=EPS, t_draw=True)
+    assert tuple(out) == CALLS
+    # the sort and the exclusive scan of psis_reduce run only with more than 4 tail entries
+    assert out["elpd"]["tail_len"].min() > 4 and out["lfo"]["tail_len"].max() > 4, (out["elpd"]["tail_len"], out["lfo"]["tail_len"])
+    return out
+
+
+def key(net, U, call, name):
+    return f"{net}_U{U}_{call}_{name}"
+
+
+def digest(net, U, train):
+    """The inputs of a case, as 32 bytes."""
+    h = hashlib.sha256()
+    for a in samples(net, U) + (np.asarray(train, np.float64),):
+        if a is not None:
+            h.update(np.ascontiguousarray(a).tobytes())
+    return np.frombuffer(h.digest(), np.uint8)
+
+
+def record():
+    """Everything the golden file holds: per case the digest of its inputs and every output of every call as it is (npz keeps the
+    bits of a float array); a count the binding returns as an int becomes an int64 array."""
+    rec = {}
+    for net, U in CASES:
+        pt, train = handle(net)
+        rec[key(net, U, "inputs", "sha256")] = digest(net, U, train)
+        for call, res in run_calls(pt, net, U).items():
+            for name, v in res.items():
+                if v is not None:
+                    rec[key(net, U, call, name)] = np.asarray(v)
+    return rec
+
+
+def same_bits(got, want):
+    """Element-wise: the same bits, or both NaN (a commuted fmax or add may pick the other payload)."""
+    got, want = np.ascontiguousarray(got), np.ascontiguousarray(want)
+    if got.shape != want.shape or got.dtype != want.dtype:
+        return np.zeros(1, bool)
+    if got.dtype.kind != "f":
+        return got == want
+    u = {4: np.uint32, 8: np.uint64}[got.dtype.itemsize]
+    return (got.view(u) == want.view(u)) | (np.isnan(got) & np.isnan(want))
+
+
+_GOLDEN = None
+
+
+def golden():
+    global _GOLDEN
+    if _GOLDEN is None:
+        _GOLDEN = parity.golden(GOLDEN_FILE)
+    return _GOLDEN
+
+
+def check_references(pt, net, U, train, out):
+    """One headline output per call against the float64 reference of that analysis's own GPU test, at its tolerance."""
+    task, topo = NETS[net]
+    I = topo[0]
+    s = pt._sampler
+    w, eta, mult = samples(net, U)
+    M = int(mult.sum())
+    c = mult.astype(np.float64)
+    X = train[:, :I]
+    y = train[:, I].astype(np.float32).astype(np.float64)
+    f_or = _outputs(task, X, w.T.astype(np.float64), topo)                               # [U, n_rows, O]
+    # predict (test_gpu_predict.py: the outputs within 1e-5 of the oracle's) -- the weighted mean of values within 1e-5
+    assert np.max(np.abs(out["predict"]["mean"] - np.tensordot(c, f_or, 1) / M)) <= 1e-5
+    # sensitivity (test_gpu_sensitivity.py: _worst_ratio's bound on every gradient, the mean against numpy) on a second call's samples
+    sens = s.sensitivity("train", w=w, multiplicity=mult, samples=True)
+    for k in ("grad_mean", "pos_count", "neg_count", "abs_mean", "sq_mean"):
+        assert same_bits(sens[k], out["sensitivity"][k]).all(), k
+    at = np.cumsum(mult) - mult
+    _worst_ratio(sens["samples"][at], X, w, topo, task)
+    np.testing.assert_allclose(out["sensitivity"]["grad_mean"], sens["samples"].astype(np.float64).mean(axis=0), rtol=1e-12, atol=0)
+    # elpd (test_gpu_elpd.py: _check_oracle)
+    ll = _oracle_ll(task, train, w.T, topo, eta)
+    r = elpd_ref.elpd_rows(ll, mult)
+    np.testing.assert_allclose(out["elpd"]["lppd"], r["lppd"], rtol=1e-5, atol=ATOL)
+    np.testing.assert_allclose(out["elpd"]["elpd_loo"], r["elpd_loo"], rtol=1e-5, atol=ATOL)
+    # lfo (test_gpu_lfo.py: _check_oracle)
+    r = lfo_ref.lfo_rows(ll, N_FIT, ORIGINS, BLOCK, multiplicity=mult)
+    K = np.abs(np.asarray(ORIGINS) - N_FIT) + BLOCK
+    assert np.all(np.abs(out["lfo"]["elpd_lfo"] - r["elpd_lfo"]) <= 1e-5 * np.abs(r["elpd_lfo"]) + ATOL * K)
+    # evidence (test_gpu_evidence.py: test_u_against_the_oracle)
+    ev = out["evidence"]
+    u = ev["u"]
+    np.testing.assert_allclose(u, np.repeat(evidence_ref.u_and_b_batched(task, train, w, topo)[0], mult), rtol=1e-5, atol=1e-4)
+    off = np.concatenate([[0], np.cumsum(mult.reshape(2, -1).sum(axis=1))])
+    for k in range(2):
+        st = evidence_ref.rung_stats(u[off[k]:off[k + 1]], STONES[k])
+        assert ev["n_draws"][k] == off[k + 1] - off[k]
+        assert ev["u_mean"][k] == pytest.approx(st["mean"], rel=1e-12)
+        assert ev["log_stone"][k] == pytest.approx(st["log_stone"], rel=1e-12, abs=1e-12)
+    up = ev["u_prior"]
+    bp = np.zeros(up.size) if task == CLS else 2.0 * up / N_ROWS
+    for j, a in enumerate(PRIOR_A):
+        p = evidence_ref.prior_stats(up, bp, a)
+        assert ev["prior_u_mean"][j] == pytest.approx(p["u_mean"], rel=1e-9)
+        assert ev["prior_kish_ess"][j] == pytest.approx(p["kish"], rel=1e-9)
+    # calibration (test_gpu_calibration.py: the CRPS against the oracle's forward pass; a classification's p_mean is predict's mean)
+    cal = out["calibration"]
+    if task == REG:
+        _, crps_or, _ = _check_oracle_forward(None, train, w.T, topo, eta, mult)
+        np.testing.assert_allclose(cal["crps"], crps_or, rtol=1e-5, atol=ATOL)
+        np.testing.assert_allclose(cal["pred_mean"], out["predict"]["mean"][:, 0], rtol=1e-12)
+        fx = s.predict("train", w=w, samples=True, mean=False)["samples"][:, :, 0]          # the device's own outputs [U, n_rows]
+        for k, p in enumerate(QUANTILES):
+            for n in range(N_ROWS):
+                assert abs(calibration_ref.mixture_cdf(cal["quantiles"][k][n], fx[:, n], eta, mult) - p) <= 1e-12, (p, n)
+    else:
+        assert np.array_equal(cal["p_mean"], out["predict"]["mean"])
+    # ppc (test_gpu_ppc.py: check_occurrences on the samples of a second call)
+    ppc = s.ppc("train", w=w, eta=eta, multiplicity=mult, lags=LAGS if task == REG else (), seed=SEED, samples=True)
+    for k in ("n_defined", "n_greater", "n_equal", "mean_obs", "mean_rep", "var_rep"):
+        assert same_bits(ppc[k], out["ppc"][k]).all(), k
+    check_occurrences(ppc)
+    assert ppc["n_defined"].max() == M
+    # powerscale (test_gpu_powerscale.py: check_oracle)
+    powerscale_check_oracle(pt, "train", w, eta, mult, out["powerscale"], groups=("weights", "eta", "predictions", "loglik"))
+    # prior_predictive (test_gpu_prior.py: check_statistics on the samples of a second call)
+    pr = s.prior_predictive("train", n_draws=U, seed=SEED, eps=EPS, t_draw=True, samples=True)
+    got = out["prior_predictive"]
+    assert same_bits(pr["t_draw"], got["t_draw"]).all()
+    t, _ = (prior_ref.regression if task == REG else prior_ref.classification)(pr["samples"][0], y, EPS)
+    np.testing.assert_allclose(got["t_draw"][0], t, rtol=PRIOR_RTOL, atol=PRIOR_ATOL)
+    want = prior_ref.summarise(got["t_draw"][0], got["t_obs"])
+    np.testing.assert_allclose(got["stat_mean"][0], want["mean"], rtol=PRIOR_RTOL, atol=PRIOR_ATOL)
+    np.testing.assert_allclose(got["stat_sd"][0], want["sd"], rtol=PRIOR_RTOL, atol=PRIOR_ATOL)
+    assert np.array_equal(got["n_defined"][0], want["n_defined"])
+    f32 = pr["samples"][0].astype(np.float64)
+    assert np.array_equal(got["sat_count"][0], np.sum((f32 < EPS) | (f32 > 1.0 - EPS), axis=0))
+
+
+@pytest.mark.parametrize("net,U", CASES, ids=[f"{n}-U{u}" for n, u in CASES])
+def test_outputs_equal_the_parent_commit(net, U):
+    g = golden()
+    pt, train = handle(net)
+    assert np.array_equal(digest(net, U, train), g[key(net, U, "inputs", "sha256")]), "the inputs are not the recorded ones"
+    out = run_calls(pt, net, U)
+    seen = set()
+    for call, res in out.items():
+        for name, v in res.items():
+            k = key(net, U, call, name)
+            if v is None:
+                assert k not in g, k
+                continue
+            seen.add(k)
+            got, want = np.asarray(v), g[k]
+            same = same_bits(got, want)
+            assert same.all(), f"{k}: {int((~same).sum())} of {same.size} values differ, first at {np.argwhere(~same)[0]}"
+    assert seen == {k for k in g if k.startswith(f"{net}_U{U}_") and "_inputs_" not in k}, "an output of the recording is missing"
+    check_references(pt, net, U, train, out)
