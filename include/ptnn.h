@@ -739,6 +739,76 @@ typedef struct ptnn_sensitivity_spec {
 
 int ptnn_sensitivity(ptnn_handle *h, const ptnn_sensitivity_spec *spec);
 
+/* ---- partial dependence and ICE curves (nothing in the reference: it never varies an input of a fitted net) ----
+ * What the sampled nets do as one input goes over a grid of values, the others held at the data rows (partial dependence, Friedman
+ * 2001; individual conditional expectation, Goldstein et al. 2015).  f is the output ptnn_predict returns (a regression's sigmoid
+ * output, a classification's p = softmax(s)).  For a selected sample s, data row n, selected input a with index j = inputs[a] and
+ * grid value v = grid[a, k]:
+ *   ICE_s[n, a, k, o] = f_o(w_s; x_n with x_n[j] := v)          fp32: z_h of the row as it is, then z_h + (v - x_j) W1[j,h]
+ *   PD_s[a, k, o]     = (1 / n_rows) sum_n ICE_s[n, a, k, o]    row sums in double, ascending row order, carried across row blocks
+ *   range_s[a, o]     = max_k PD32_s[a, k, o] - min_k PD32_s[a, k, o]   PD32 = PD_s rounded to fp32; the difference formed in
+ *                                                                       double (exact) and rounded to fp32 once
+ * DESIGN.md section 25.  Sample set: selected as ptnn_predict selects it -- the handle's trace (same rules and error texts) or host
+ * vectors w [n_w, P] with optional multiplicities -- collapsed into distinct vectors as ptnn_predict collapses them; every output
+ * is over the expanded multiset of M samples.  Rows: x_source / n_rows / x [n_rows, n_in] as ptnn_predict.  inputs [n_inputs] = the
+ * selected input indices in the caller's order, NULL = all of them, 0 .. n_in - 1 (n_inputs is then ignored); A = their number.
+ * grid [A, n_grid] = one row of grid values per selected input, 1 <= n_grid <= PTNN_PD_MAX_GRID; repeated and unsorted values
+ * are allowed.  ranks / n_ranks apply to ICE, ranks2 / n_ranks2 to PD_s and range_s (each <= PTNN_PREDICT_MAX_RANKS).
+ * Outputs, any may be NULL, and an output costs device work only when its pointer is given (without ice_mean, ice_order_stats and
+ * samples the reduction over the n_rows A G n_out ICE columns is not launched).  With G = n_grid, O = n_out and ICE column
+ * ((n A + a) G + k) O + o: ice_mean [n_rows, A, G, O] (the weighted mean, accumulated in double); ice_order_stats [n_ranks,
+ * n_rows, A, G, O] = the exact fp32 value of 0-based rank ranks[k] among the M values (ptnn_predict's rule); pd_mean [A, G, O] =
+ * the weighted mean over the samples of the double row means (a fixed order for a given list of distinct vectors);
+ * pd_order_stats [n_ranks2, A, G, O] = the exact rank ranks2[k] of PD32_s; range_mean [A, O] = the weighted mean of range_s;
+ * range_order_stats [n_ranks2, A, O]; sample_pd [M, A, G, O] = every selected row's PD32_s, chain-major; sample_range [M, A, O];
+ * samples [M, n_rows, A, G, O] = every selected row's ICE, chain-major (ptnn_predict's samples layout); n_samples = M, n_distinct.
+ * Refused: what ptnn_sensitivity refuses, n_grid outside [1, PTNN_PD_MAX_GRID], grid NULL, inputs with n_inputs < 1, a grid value
+ * that is not finite (with inputs == NULL the grid has n_in rows and is looked at with the handle), order statistics requested
+ * without ranks; with the handle: an input index outside [0, n_in) or given twice,
+ * n_rows x A x G x n_out > 2^31 - 1 columns, an empty selection, a rank outside [0, M).  Runs on the handle's stream behind
+ * everything queued and returns when done; rows are processed in blocks whose scratch (4 U A G n_out bytes per row) stays under
+ * $PTNN_PD_SCRATCH_BYTES (read per call, default 1 GiB) and of at most 65535 x 64 rows, which changes no result.  Touches no chain
+ * state, tape, counter or trace row.  Not with a communicator attached (one GPU only). */
+#define PTNN_PD_MAX_GRID 64
+
+typedef struct ptnn_pd_spec {
+    int32_t struct_bytes;         /* = sizeof(ptnn_pd_spec): ABI guard */
+    /* source 1: the trace (used when w == NULL) */
+    const int32_t *replicas;      /* local replica indices, or NULL = all */
+    int32_t n_replicas;           /* entries of replicas (ignored when NULL) */
+    int32_t step0, nsteps, thin;  /* trace rows step0, step0 + thin, ... < step0 + nsteps (thin >= 1) */
+    /* source 2: host vectors */
+    const float *w;               /* [n_w, P] or NULL */
+    const int32_t *multiplicity;  /* [n_w] >= 0, or NULL = 1 each */
+    int64_t n_w;
+    /* rows */
+    int32_t x_source;             /* PTNN_PREDICT_X_HOST | _TRAIN | _TEST */
+    int32_t n_rows;
+    const float *x;               /* [n_rows, n_in] (host rows only) */
+    /* the selected inputs and their grids */
+    const int32_t *inputs;        /* [n_inputs] distinct indices in [0, n_in), or NULL = 0 .. n_in - 1 */
+    int32_t n_inputs;             /* entries of inputs (ignored when NULL) */
+    int32_t n_grid;               /* G, 1 .. PTNN_PD_MAX_GRID */
+    const float *grid;            /* [A, n_grid] finite */
+    /* order statistics: of ICE per (row, input, grid value, output), and of PD32_s and range_s */
+    const int64_t *ranks;         /* [n_ranks] */
+    const int64_t *ranks2;        /* [n_ranks2] */
+    int32_t n_ranks, n_ranks2;    /* each <= PTNN_PREDICT_MAX_RANKS */
+    /* outputs */
+    double *ice_mean;
+    float *ice_order_stats;
+    double *pd_mean;
+    float *pd_order_stats;
+    double *range_mean;
+    float *range_order_stats;
+    float *sample_pd;
+    float *sample_range;
+    float *samples;
+    int64_t *n_samples, *n_distinct;
+} ptnn_pd_spec;
+
+int ptnn_partial_dependence(ptnn_handle *h, const ptnn_pd_spec *spec);
+
 /* ---- posterior predictive checks (nothing in the reference: it never simulates data from the fitted model) ----
  * Does data simulated from the fitted model look like the data?  (BDA3 ch. 6; Gelman, Meng & Stern 1996.)  Every selected
  * occurrence of a sample draws one replicated data set y_rep on the data rows; a test quantity T is evaluated on y_rep and on

@@ -168,6 +168,24 @@ class SensitivitySpec(C.Structure):
     ]
 
 
+class PdSpec(C.Structure):
+    """ptnn_pd_spec (include/ptnn.h)."""
+    _fields_ = _SELECTION + [
+        ("w", C.POINTER(C.c_float)), ("multiplicity", C.POINTER(C.c_int32)), ("n_w", C.c_int64),
+        ("x_source", C.c_int32), ("n_rows", C.c_int32), ("x", C.POINTER(C.c_float)),
+        ("inputs", C.POINTER(C.c_int32)), ("n_inputs", C.c_int32), ("n_grid", C.c_int32), ("grid", C.POINTER(C.c_float)),
+        ("ranks", C.POINTER(C.c_int64)), ("ranks2", C.POINTER(C.c_int64)), ("n_ranks", C.c_int32), ("n_ranks2", C.c_int32),
+        ("ice_mean", C.POINTER(C.c_double)), ("ice_order_stats", C.POINTER(C.c_float)),
+        ("pd_mean", C.POINTER(C.c_double)), ("pd_order_stats", C.POINTER(C.c_float)),
+        ("range_mean", C.POINTER(C.c_double)), ("range_order_stats", C.POINTER(C.c_float)),
+        ("sample_pd", C.POINTER(C.c_float)), ("sample_range", C.POINTER(C.c_float)), ("samples", C.POINTER(C.c_float)),
+        ("n_samples", C.POINTER(C.c_int64)), ("n_distinct", C.POINTER(C.c_int64)),
+    ]
+
+
+PD_MAX_GRID = 64
+
+
 class PpcSpec(C.Structure):
     """ptnn_ppc_spec (include/ptnn.h)."""
     _fields_ = _SELECTION + [
@@ -317,6 +335,7 @@ SYMBOLS = {
     "ptnn_evidence": (C.c_int, [C.c_void_p, C.POINTER(EvidenceSpec)]),
     "ptnn_calibration": (C.c_int, [C.c_void_p, C.POINTER(CalibrationSpec)]),
     "ptnn_sensitivity": (C.c_int, [C.c_void_p, C.POINTER(SensitivitySpec)]),
+    "ptnn_partial_dependence": (C.c_int, [C.c_void_p, C.POINTER(PdSpec)]),
     "ptnn_ppc": (C.c_int, [C.c_void_p, C.POINTER(PpcSpec)]),
     "ptnn_powerscale": (C.c_int, [C.c_void_p, C.POINTER(PowerscaleSpec)]),
     "ptnn_prior_predictive": (C.c_int, [C.c_void_p, C.POINTER(PriorSpec)]),
@@ -975,6 +994,45 @@ class Sampler:
                    samples=np.empty((max(M, 0), n_rows, O, I), np.float32) if samples else None)
         _bind(spec, out)
         return self._call(self.lib.ptnn_sensitivity, spec, out)
+
+    def partial_dependence(self, x="train", *, inputs=None, grid, replicas=None, step0=0, nsteps=None, thin=1, w=None, multiplicity=None,
+                           ranks=(), ranks2=(), ice_mean=False, sample_pd=False, sample_range=False, samples=False):
+        """ptnn_partial_dependence: the outputs of the selected weight vectors on the rows `x` with input inputs[a] set to
+        grid[a, k], reduced on the device.  Source and x as predict().  inputs: the selected input indices (None = all n_in);
+        grid [A, G] float32, one row per selected input.  ranks apply to ICE (its mean and order statistics are computed only with
+        ice_mean or ranks), ranks2 to the per-sample curve and its range.  -> dict(ice_mean [n_rows, A, G, O] float64,
+        ice_order_stats [len(ranks), n_rows, A, G, O] float32, pd_mean [A, G, O] float64, pd_order_stats [len(ranks2), A, G, O]
+        float32, range_mean [A, O] float64, range_order_stats [len(ranks2), A, O] float32, sample_pd [M, A, G, O], sample_range
+        [M, A, O], samples [M, n_rows, A, G, O] float32, n_samples, n_distinct); what was not asked for is None."""
+        spec, keep = _spec(PdSpec), []
+        self._rows(spec, keep, x, "x", (self.cfg.n_in, "n_in columns"))
+        n_rows, O = spec.n_rows, self.cfg.n_out
+        M = self._samples(spec, keep, w=w, multiplicity=multiplicity, replicas=replicas, step0=step0, nsteps=nsteps, thin=thin,
+                          unit="vector")
+        A = self.cfg.n_in
+        if inputs is not None:
+            ia = np.ascontiguousarray(inputs, dtype=np.int32).reshape(-1)
+            keep.append(ia)
+            spec.inputs, spec.n_inputs = _ptr(ia, _ip), ia.size
+            A = ia.size
+        ga = _f32(grid)
+        if ga.ndim != 2 or ga.shape[0] != A:
+            raise ValueError(f"grid must be [{A}, n_grid] (one row per selected input), got shape {ga.shape}")
+        keep.append(ga)
+        spec.grid, spec.n_grid = _ptr(ga), ga.shape[1]
+        G = ga.shape[1]
+        n_rk, n_rk2 = _ranks(spec, keep, ranks), _ranks(spec, keep, ranks2, ("ranks2", "n_ranks2"))
+        out = dict(ice_mean=np.empty((n_rows, A, G, O), np.float64) if ice_mean else None,
+                   ice_order_stats=np.empty((n_rk, n_rows, A, G, O), np.float32) if n_rk else None,
+                   pd_mean=np.empty((A, G, O), np.float64),
+                   pd_order_stats=np.empty((n_rk2, A, G, O), np.float32) if n_rk2 else None,
+                   range_mean=np.empty((A, O), np.float64),
+                   range_order_stats=np.empty((n_rk2, A, O), np.float32) if n_rk2 else None,
+                   sample_pd=np.empty((max(M, 0), A, G, O), np.float32) if sample_pd else None,
+                   sample_range=np.empty((max(M, 0), A, O), np.float32) if sample_range else None,
+                   samples=np.empty((max(M, 0), n_rows, A, G, O), np.float32) if samples else None)
+        _bind(spec, out)
+        return self._call(self.lib.ptnn_partial_dependence, spec, out)
 
     def ppc(self, data="train", *, replicas=None, step0=0, nsteps=None, thin=1, w=None, eta=None, multiplicity=None, lags=(), seed=0,
             samples=True, draws=False):

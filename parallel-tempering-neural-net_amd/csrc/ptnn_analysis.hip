@@ -1,5 +1,5 @@
 // ptnn_analysis.hip -- the posterior analysis calls of libptnn.so: predict, convergence, rank_convergence, elpd, lfo, forecast, evidence, calibration,
-// sensitivity, ppc, powerscale, prior_predictive, and the sample-selection path they share.  The shape-independent analysis kernels are defined in this object: it includes them.
+// sensitivity, partial_dependence, ppc, powerscale, prior_predictive, and the sample-selection path they share.  The shape-independent analysis kernels are defined in this object: it includes them.
 #include "ptnn_shapes.hpp"
 namespace ptnn {
 #include "ptnn_dev_wg.hpp"                   // work-group reductions and scans of every kernel below (ptnn_device.hpp has included it: ladder_round)
@@ -15,6 +15,8 @@ namespace ptnn {
 #include "ptnn_dev_rank.hpp"                 // rank-normalised convergence: sort words, average ranks, z-scores, indicators, rank histograms
 #define PTNN_SENSITIVITY_REDUCTIONS
 #include "ptnn_dev_sensitivity.hpp"          // input sensitivity, second part: sign counts, row sums and their weighted means
+#define PTNN_PD_REDUCTIONS
+#include "ptnn_dev_pd.hpp"                   // partial dependence, second part: row sums, ranges and the weighted means of the row means
 }  // namespace ptnn
 #include "ptnn_host.hpp"
 #include "ptnn_rank_plan.hpp"               // the blocks of ptnn_rank_convergence: host arithmetic, checked on its own
@@ -378,6 +380,41 @@ struct SensPlan {
     }
 };
 
+// Stage b of partial dependence: the per-shape pd_fwd.  A work-group stages NV distinct vectors in LDS beside their finished tiles
+// of one chunk: GC grid values of one selected input, n_out * GC * 64 floats each.  With GT = pd_grid_tile(n_out) grid values
+// per pass, a chunk starts as the whole tiles that PD_ACC columns hold (n_out = 1: 2 x 16 values, else one tile), cut to the grid,
+// so that a vector's tile stays near 10 KiB; NV = as many vectors as 64 KiB hold (two work-groups share a CU), at most 16.  Where
+// that leaves fewer than four (vector, tile) pairs for the four waves -- a vector above 16 KiB -- the chunk grows tile by tile
+// while the grid has more and the request stays under LDS_CEILING.  The largest compiled request is 34-512-2 with 64 grid values:
+// one vector of 18948 floats and a 64-value chunk, 108 816 B.
+struct PdPlan {
+    int PV = 0, NV = 0, VS = 0, GC = 0, NCH = 0, A = 0, G = 0;
+    size_t lds = 0;
+    int init(const ptnn_handle* h, int n_inputs, int n_grid) {
+        const int P = h->P, O = h->cfg.n_out, GT = pd_grid_tile(O), tiles = (n_grid + GT - 1) / GT;
+        A = n_inputs; G = n_grid;
+        PV = round_up4(P);
+        int ct = std::min(tiles, std::max(1, PD_ACC / (O * GT)));
+        const auto per_vec = [&](int t) { return PV + (std::min(t * GT, G) * O + 1) * WAVE; };
+        NV = std::max(1, std::min(PD_MAX_NV, (64 * 1024 / 4) / per_vec(ct)));
+        while (NV * ct < PD_THREADS / WAVE && ct < tiles && (size_t)NV * per_vec(ct + 1) * sizeof(float) <= LDS_CEILING) ++ct;
+        GC = std::min(ct * GT, G);
+        NCH = (G + GC - 1) / GC;
+        VS = GC * O * WAVE + std::max(1, WAVE / NV);    // the pad: the vectors of one column land in different LDS banks
+        lds = (size_t)NV * (PV + VS) * sizeof(float);
+        if (lds > LDS_CEILING) return fail(-3, "partial dependence: a %d-parameter vector does not fit in LDS", P);
+        return raise_lds_limit(reinterpret_cast<const void*>(h->shape->pd_fwd), lds);
+    }
+    // fx [nr * A * G * O][U] = the outputs of vectors base + run_off[u] on rows [r0, r0 + nr) of x, input inputs[a] set to grid[a, k]
+    int run(const ptnn_handle* h, const float* base, const long long* run_off, const float* x, int xs, int r0, int nr, int U,
+            const int* inputs, const float* grid, float* fx) const {
+        PdFwd fa{base, run_off, x, xs, r0, nr, h->cfg.n_hidden, h->P, PV, U, NV, VS, A, G, GC, NCH, inputs, grid, fx};
+        HIP_TRY(launch(h->shape->pd_fwd, dim3((unsigned)((U + NV - 1) / NV), (unsigned)((nr + WAVE - 1) / WAVE), (unsigned)(A * NCH)),
+                       dim3(PD_THREADS), lds, h->stream, fa));
+        return 0;
+    }
+};
+
 // The order statistics of predict, sensitivity and forecast: ranks [n] in the expanded multiset of M samples, the values of those
 // ranks in every column to the caller's order_stats
 struct RankOutputs {
@@ -605,6 +642,143 @@ int ptnn_sensitivity(ptnn_handle* h, const ptnn_sensitivity_spec* spec) {
     HIP_TRY(fetch(s.abs_mean, d_abs_mean, (size_t)OI, st));
     HIP_TRY(fetch(s.sq_mean, d_sq_mean, (size_t)OI, st));
     HIP_TRY(fetch(s.abs_order_stats, rk2.d_stats, (size_t)s.n_ranks2 * OI, st));
+    return wait_stream(h);
+}
+
+// ---- partial dependence and ICE curves (ptnn_dev_pd.hpp) ----
+static_assert(PTNN_PD_MAX_GRID == PD_MAX_GRID, "ptnn.h PTNN_PD_MAX_GRID");
+
+static int pd_check_grid(const float* grid, int A, int G) {
+    for (int a = 0; a < A; ++a)
+        for (int k = 0; k < G; ++k)
+            if (!std::isfinite(grid[(size_t)a * G + k]))
+                return fail(-1, "grid[%d, %d] = %g (input slot %d, position %d) is not finite", a, k, (double)grid[(size_t)a * G + k], a, k);
+    return 0;
+}
+
+int ptnn_partial_dependence(ptnn_handle* h, const ptnn_pd_spec* spec) {
+    // argument checks first: none of them needs the handle or a device (the grid of inputs == NULL has n_in rows: checked with the handle)
+    if (int rc = check_spec(spec, "ptnn_pd_spec")) return rc;
+    const ptnn_pd_spec& s = *spec;
+    SampleSource src = source_of(s, s.w != nullptr, nullptr);
+    const RowSource rows{s.x_source, s.x, s.n_rows, "x_source", "PTNN_PREDICT_X", "x", "n_rows"};
+    RankOutputs rk{s.n_ranks, s.ranks, s.ice_order_stats};
+    RankOutputs rk2{s.n_ranks2, s.ranks2, s.pd_order_stats ? (const void*)s.pd_order_stats : (const void*)s.range_order_stats};
+    if (int rc = check_source(src, "vectors")) return rc;
+    if (int rc = check_rows(rows)) return rc;
+    if (s.n_rows < 1) return fail(-1, "n_rows = %d must be >= 1", s.n_rows);
+    if (int rc = rk.check()) return rc;
+    if (int rc = rk2.check()) return rc;
+    if (s.n_grid < 1 || s.n_grid > PTNN_PD_MAX_GRID) return fail(-1, "n_grid = %d outside [1, %d]", s.n_grid, PTNN_PD_MAX_GRID);
+    if (!s.grid) return fail(-1, "grid is NULL: one row of n_grid values per selected input");
+    if (s.inputs && s.n_inputs < 1) return fail(-1, "n_inputs = %d with an input list", s.n_inputs);
+    if (s.inputs)
+        if (int rc = pd_check_grid(s.grid, s.n_inputs, s.n_grid)) return rc;
+    if (int rc = check_handle(h, "ptnn_partial_dependence")) return rc;
+    const int I = h->cfg.n_in, O = h->cfg.n_out, G = s.n_grid;
+    if (int rc = fit_rows(h, rows)) return rc;
+    std::vector<int32_t> inputs(s.inputs ? (size_t)s.n_inputs : (size_t)I);
+    for (size_t a = 0; a < inputs.size(); ++a) inputs[a] = s.inputs ? s.inputs[a] : (int32_t)a;
+    if (!s.inputs)
+        if (int rc = pd_check_grid(s.grid, I, G)) return rc;
+    std::vector<char> seen((size_t)I, 0);
+    for (size_t a = 0; a < inputs.size(); ++a) {
+        if (inputs[a] < 0 || inputs[a] >= I) return fail(-1, "inputs[%d] = %d outside [0, %d)", (int)a, inputs[a], I);
+        if (seen[(size_t)inputs[a]]) return fail(-1, "inputs[%d] = %d is given twice", (int)a, inputs[a]);
+        seen[(size_t)inputs[a]] = 1;
+    }
+    const int A = (int)inputs.size(), AGO = A * G * O, AO = A * O;
+    const long long ncols_all = (long long)s.n_rows * AGO;
+    if (ncols_all > 0x7fffffffLL)
+        return fail(-1, "%d rows x %d inputs x %d grid values x %d outputs = %lld columns: at most 2^31 - 1 per call", s.n_rows, A, G, O, ncols_all);
+    const int ncols = (int)ncols_all;
+    if (int rc = select_samples(h, src, false)) return rc;
+    const long long M = src.M;
+    if (int rc = rk.check_values(M)) return rc;
+    if (int rc = rk2.check_values(M)) return rc;
+    if (s.n_samples) *s.n_samples = M;
+
+    if (int rc = start_device(h)) return rc;
+    hipStream_t st = h->stream;
+    DeviceScratch mem;
+    const float* d_x = nullptr;
+    int xs = 0;
+    if (int rc = upload_rows(h, mem, rows, I, &d_x, &xs)) return rc;
+    int* d_inputs = nullptr;
+    float* d_grid = nullptr;
+    HIP_TRY(mem.upload(&d_inputs, (const int*)inputs.data(), (size_t)A, st));
+    HIP_TRY(mem.upload(&d_grid, s.grid, (size_t)A * G, st));
+    Distinct d;
+    if (int rc = distinct_samples(h, mem, src, false, true, &d)) return rc;
+    const int U = d.U;
+    if (s.n_distinct) *s.n_distinct = U;
+    // an output costs device work only when its pointer is given
+    const bool ice_red = s.ice_mean || s.ice_order_stats;
+    const bool want_range = s.range_mean || s.range_order_stats || s.sample_range;
+    if (!s.ice_order_stats) rk.n = 0;
+    const int nrk_pd = s.pd_order_stats ? s.n_ranks2 : 0, nrk_range = s.range_order_stats ? s.n_ranks2 : 0;
+    double *d_ice_mean = nullptr, *d_acc = nullptr, *d_pd_mean = nullptr, *d_pd32_mean = nullptr, *d_range_mean = nullptr;
+    float *d_pd32 = nullptr, *d_range = nullptr, *d_pd_stats = nullptr, *d_range_stats = nullptr;
+    long long* d_ranks2 = nullptr;
+    if (ice_red) HIP_TRY(mem.alloc(&d_ice_mean, (size_t)ncols));
+    if (int rc = rk.to_device(mem, (size_t)ncols, st)) return rc;
+    if (nrk_pd || nrk_range) HIP_TRY(mem.upload(&d_ranks2, (const long long*)s.ranks2, (size_t)s.n_ranks2, st));
+    // per (a, k, o) and distinct vector: the row sums of ICE, carried across the blocks of rows
+    HIP_TRY(mem.alloc(&d_acc, (size_t)AGO * U));
+    HIP_TRY(mem.alloc(&d_pd32, (size_t)AGO * U));
+    HIP_TRY(hipMemsetAsync(d_acc, 0, (size_t)AGO * U * sizeof(double), st));
+    // the forward pass, the column reductions and the row sums in blocks of rows: fx scratch U x (rows x A x G x O) floats under the budget
+    const long long rows_blk = row_block(scratch_budget("PTNN_PD_SCRATCH_BYTES"), (size_t)U * sizeof(float) * AGO, s.n_rows);
+    float* d_fx = nullptr;
+    HIP_TRY(mem.alloc(&d_fx, (size_t)rows_blk * AGO * U));
+    PdPlan fwd;
+    if (int rc = fwd.init(h, A, G)) return rc;
+    std::vector<int> item_run;
+    if (s.samples || s.sample_pd || s.sample_range) if (int rc = item_runs(h, d, src.n_items, &item_run)) return rc;
+    const unsigned ublocks = (unsigned)((U + PRED_THREADS - 1) / PRED_THREADS);
+    if (int rc = each_block(s.n_rows, rows_blk, [&](long long r0, int nr) -> int {
+        if (int rc = fwd.run(h, d.base, d.run_off, d_x, xs, (int)r0, nr, U, d_inputs, d_grid, d_fx)) return rc;
+        if (ice_red) {
+            PredictRed ra{d_fx, d.run_cnt, U, 1, (int)(r0 * AGO), ncols, M, rk.n, rk.d_ranks, d_ice_mean, rk.d_stats, nullptr};
+            HIP_TRY(launch(predict_reduce_kernel, dim3((unsigned)((long long)nr * AGO)), dim3(PRED_THREADS), 0, st, ra));
+        }
+        PdRows rw{d_fx, U, AGO, nr, r0 + nr == s.n_rows ? 1 : 0, (double)s.n_rows, d_acc, d_pd32};
+        HIP_TRY(launch(pd_rows_kernel, dim3(ublocks * (unsigned)AGO), dim3(PRED_THREADS), 0, st, rw));
+        return s.samples ? scatter_samples(h, d_fx, nr * AGO, U, item_run, src.weights(), s.samples, (size_t)ncols, (size_t)r0 * AGO) : 0;
+    })) return rc;
+    // the curve: weighted means of the double row means, exact ranks of PD32; its range per (a, o)
+    if (s.pd_mean) {
+        HIP_TRY(mem.alloc(&d_pd_mean, (size_t)AGO));
+        PdMean ma{d_acc, d.run_cnt, U, (double)s.n_rows, M, d_pd_mean};
+        HIP_TRY(launch(pd_mean_kernel, dim3((unsigned)AGO), dim3(PRED_THREADS), 0, st, ma));
+    }
+    if (nrk_pd) {
+        HIP_TRY(mem.alloc(&d_pd32_mean, (size_t)AGO));
+        HIP_TRY(mem.alloc(&d_pd_stats, (size_t)nrk_pd * AGO));
+        PredictRed ra{d_pd32, d.run_cnt, U, 1, 0, AGO, M, nrk_pd, d_ranks2, d_pd32_mean, d_pd_stats, nullptr};
+        HIP_TRY(launch(predict_reduce_kernel, dim3((unsigned)AGO), dim3(PRED_THREADS), 0, st, ra));
+    }
+    if (want_range) {
+        HIP_TRY(mem.alloc(&d_range, (size_t)AO * U));
+        PdRange rg{d_pd32, U, A, G, O, d_range};
+        HIP_TRY(launch(pd_range_kernel, dim3(ublocks * (unsigned)AO), dim3(PRED_THREADS), 0, st, rg));
+        if (s.range_mean || nrk_range) {
+            HIP_TRY(mem.alloc(&d_range_mean, (size_t)AO));
+            if (nrk_range) HIP_TRY(mem.alloc(&d_range_stats, (size_t)nrk_range * AO));
+            PredictRed ra{d_range, d.run_cnt, U, 1, 0, AO, M, nrk_range, d_ranks2, d_range_mean, d_range_stats, nullptr};
+            HIP_TRY(launch(predict_reduce_kernel, dim3((unsigned)AO), dim3(PRED_THREADS), 0, st, ra));
+        }
+    }
+    if (s.sample_pd)
+        if (int rc = scatter_samples(h, d_pd32, AGO, U, item_run, src.weights(), s.sample_pd, (size_t)AGO, 0)) return rc;
+    if (s.sample_range)
+        if (int rc = scatter_samples(h, d_range, AO, U, item_run, src.weights(), s.sample_range, (size_t)AO, 0)) return rc;
+    HIP_TRY(fetch(s.ice_mean, d_ice_mean, (size_t)ncols, st));
+    HIP_TRY(fetch(s.ice_order_stats, rk.d_stats, (size_t)rk.n * ncols, st));
+    HIP_TRY(fetch(s.pd_mean, d_pd_mean, (size_t)AGO, st));
+    HIP_TRY(fetch(s.pd_order_stats, d_pd_stats, (size_t)nrk_pd * AGO, st));
+    HIP_TRY(fetch(s.range_mean, d_range_mean, (size_t)AO, st));
+    HIP_TRY(fetch(s.range_order_stats, d_range_stats, (size_t)nrk_range * AO, st));
     return wait_stream(h);
 }
 

@@ -1,0 +1,225 @@
+// ptnn_dev_pd.hpp -- part of ptnn_device.hpp (textually included there, inside namespace ptnn; not a stand-alone header):
+// partial dependence and individual conditional expectation curves of the sampled nets (ptnn_partial_dependence, include/ptnn.h;
+// DESIGN.md section 25; Friedman 2001, Goldstein et al. 2015).  Nothing of the kind is in the reference.
+//
+//   ICE_s[n, a, k, o] = f_o(w_s; x_n with x_n[j] := v)      j = inputs[a], v = grid[a, k], f as ptnn_predict returns it
+//   z_h  = sum_i x_i W1[i,h] - B1[h]                         the row as it is, once per hidden unit
+//   zk_h = z_h + (v - x_j) W1[j,h]                           the substituted row is never rebuilt: one FMA per grid value
+//   hid  = sigmoid(zk_h)   a_o = sum_h hid W2[h,o] - B2[o]   s_o = sigmoid(a_o)   classification: p = softmax(s) (CLS:108-110)
+//
+// The three stages of ptnn_dev_predict.hpp, with another stage b:
+//   b. pd_forward_kernel<TASK, I, O> (per shape, Shape::pd_fwd): fx[col][u] = ICE of distinct vector u, column
+//      col = ((row * A + a) * G + k) * O + o of a block of input rows -- the layout of PredictFwd::fx, so stage c
+//      (predict_reduce_kernel, with O = 1 and no votes) takes the ICE columns as it takes the outputs.
+//   then per block of rows pd_rows_kernel (ICE summed over the rows per vector and (a, k, o), in double, carried across the blocks;
+//   after the last block PD32 = the row mean as fp32), and at the end pd_range_kernel (max_k - min_k of PD32 per vector and (a, o))
+//   and pd_mean_kernel (the weighted means of the double row means over the vectors).
+// Nothing here writes chain state, tapes, counters or trace rows, and nothing here uses an atomic.
+//
+// The invariant: a value of stage b is a function of (vector, row, input, grid value) alone.  It is one whole pass over the hidden
+// units in ascending order into accumulators of its own, so it does not depend on NV, on how the grid is cut into chunks, on the
+// tile slot the value falls in, on the block of rows or on the wave that computed it.
+//
+// The file has two parts.  ptnn_device.hpp includes the first: the constants, PdFwd and the per-shape kernel, which the shape
+// translation units instantiate.  ptnn_analysis.hip includes the file again with PTNN_PD_REDUCTIONS defined and gets the second:
+// the shape-independent kernels, which that object holds.
+#ifndef PTNN_PD_REDUCTIONS
+
+constexpr int PD_THREADS = 256;          // 4 waves
+constexpr int PD_MAX_NV = 16;            // distinct vectors per forward work-group
+constexpr int PD_MAX_GRID = 64;          // grid values per input (PTNN_PD_MAX_GRID)
+constexpr int PD_ACC = 40;               // output accumulators a lane holds in one pass over the hidden units
+constexpr int PD_MAX_GT = 16;
+
+// The grid values are tiled: one pass over the hidden units carries acc[o][k] for all O outputs and GT grid values, at most PD_ACC
+// accumulators: O = 1, 2 -> 16, O = 3 -> 13, O = 10 -> 4, O = 18 -> 2.  The host plans with the same function.
+constexpr int pd_grid_tile(int O) { return PD_ACC / O < 1 ? 1 : (PD_ACC / O < PD_MAX_GT ? PD_ACC / O : PD_MAX_GT); }
+
+// what the forward kernel needs (the host fills it; ptnn_analysis.hip: PdPlan)
+struct PdFwd {
+    const float* base;          // vectors: d_pos_w rows or the uploaded host vectors
+    const long long* run_off;   // [U] float offset of distinct vector u in base
+    const float* x;             // input rows, x_0 .. x_{I-1} at x + row * xs
+    int xs;                     // row stride of x (floats)
+    int row0, nrows;            // rows [row0, row0 + nrows) of x form this block of columns
+    int H, P, PV;               // hidden units, parameters, LDS stride of a staged vector (P rounded up to 4)
+    int U, NV;                  // distinct vectors, vectors staged per work-group
+    int VS;                     // LDS stride of a vector's finished tile: GC * O * 64 + a pad that spreads the vectors over the banks
+    int A, G;                   // selected inputs, grid values per input
+    int GC, NCH;                // grid values per chunk, chunks per input: blockIdx.z = a * NCH + chunk
+    const int* inputs;          // [A] input index j of slot a, in [0, I)
+    const float* grid;          // [A][G]
+    float* fx;                  // [nrows * A * G * O][U] column-major
+};
+
+// One lane per input row with the row's inputs in registers, NV vectors staged in LDS, every weight read wave-uniform (an LDS
+// broadcast), as in sensitivity_forward_kernel.  A work-group takes 64 rows, NV vectors and one chunk: a selected input with a run
+// of its grid values.  Its work is the nv x nt (vector, grid tile) pairs; wave w takes the pairs w, w + 4, ...  A pair is one pass
+// over ALL hidden units in ascending order: z_h from the row as it is (I FMAs), then per grid value of the tile one FMA, one
+// sigmoid and O FMAs.  A tile slot past the chunk's last grid value recomputes that value and stores nothing.
+template <int TASK, int I, int O>
+__global__ void __launch_bounds__(PD_THREADS) pd_forward_kernel(const PdFwd a) {
+    extern __shared__ __attribute__((aligned(16))) float smem[];
+    constexpr int GT = pd_grid_tile(O), NWAVE = PD_THREADS / WAVE;
+    const int tid = threadIdx.x, lane = tid & (WAVE - 1);
+    const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+    const int NV = a.NV, PV = a.PV, H = a.H, VS = a.VS, G = a.G;
+    const int u0 = blockIdx.x * NV;
+    const int nv = min(NV, a.U - u0);
+    const int r0 = blockIdx.y * WAVE;
+    const int ai = blockIdx.z / a.NCH, k0 = (blockIdx.z % a.NCH) * a.GC;
+    const int kc = min(a.GC, G - k0);                   // grid values of this chunk, >= 1
+    const int nt = (kc + GT - 1) / GT;
+    const int j = a.inputs[ai];
+    const float* gv = a.grid + (size_t)ai * G + k0;
+    float* sv = smem;                                   // [NV][PV] the staged vectors
+    float* fin = sv + (size_t)NV * PV;                  // [NV][VS] finished values: fin[v * VS + (kk * O + o) * 64 + lane]
+    for (int v = 0; v < nv; ++v) {
+        const float* src = a.base + a.run_off[u0 + v];
+        for (int k = tid; k < a.P; k += PD_THREADS) sv[v * PV + k] = src[k];
+    }
+    // a lane past the last row computes row 0 and stores nothing
+    const int row = r0 + lane;
+    const bool live = row < a.nrows;
+    const float* xr = a.x + (size_t)(a.row0 + (live ? row : 0)) * a.xs;
+    float x[I];
+#pragma unroll
+    for (int i = 0; i < I; ++i) x[i] = xr[i];
+    const float xj = xr[j];                             // the run-time index goes to memory, not to the register array
+    __syncthreads();
+    for (int p = wave; p < nv * nt; p += NWAVE) {
+        const int v = p / nt, t0 = (p % nt) * GT;       // wave-uniform
+        const float* W1 = sv + v * PV;                  // [I][H]  (decode: w = W1, W2, B1, B2)
+        const float* W2 = W1 + I * H;                   // [H][O]
+        const float* B1 = W2 + H * O;
+        const float* B2 = B1 + H;
+        const float* W1j = W1 + j * H;
+        float dv[GT], acc[O][GT];
+#pragma unroll
+        for (int k = 0; k < GT; ++k) {
+            dv[k] = gv[min(t0 + k, kc - 1)] - xj;
+#pragma unroll
+            for (int o = 0; o < O; ++o) acc[o][k] = 0.0f;
+        }
+        for (int h = 0; h < H; ++h) {
+            float z = 0.0f;
+#pragma unroll
+            for (int i = 0; i < I; ++i) z = fmaf(x[i], W1[i * H + h], z);
+            z -= B1[h];                                                     // bias subtracted (Q1)
+            const float w1j = W1j[h];
+            float w2[O];
+#pragma unroll
+            for (int o = 0; o < O; ++o) w2[o] = W2[h * O + o];
+#pragma unroll
+            for (int k = 0; k < GT; ++k) {
+                const float zk = fmaf(dv[k], w1j, z);
+                const float e = expf(-fabsf(zk));                           // as sigmoid_and_slope forms it: e <= 1
+                const float hid = (zk >= 0.0f ? 1.0f : e) / (1.0f + e);
+#pragma unroll
+                for (int o = 0; o < O; ++o) acc[o][k] = fmaf(hid, w2[o], acc[o][k]);
+            }
+        }
+        // the output sigmoid (Q2); classification: p = softmax(s) (CLS:108-110)
+        float* out = fin + (size_t)v * VS + lane;
+#pragma unroll
+        for (int k = 0; k < GT; ++k) {
+            float f[O];
+#pragma unroll
+            for (int o = 0; o < O; ++o) {
+                const float zo = acc[o][k] - B2[o];
+                const float e = expf(-fabsf(zo));
+                f[o] = (zo >= 0.0f ? 1.0f : e) / (1.0f + e);
+            }
+            if (TASK == TASK_CLS) {
+                float sum = 0.0f;
+#pragma unroll
+                for (int o = 0; o < O; ++o) { f[o] = expf(f[o]); sum += f[o]; }
+#pragma unroll
+                for (int o = 0; o < O; ++o) f[o] = f[o] / sum;
+            }
+            if (t0 + k < kc) {
+#pragma unroll
+                for (int o = 0; o < O; ++o) out[((t0 + k) * O + o) * WAVE] = f[o];
+            }
+        }
+    }
+    __syncthreads();
+    // column-major store: column ((r0 + l) * A + ai) * G * O + k0 * O + ko of the block gets NV consecutive floats
+    const size_t GO = (size_t)G * O;
+    for (int idx = tid; idx < kc * O * WAVE * NV; idx += PD_THREADS) {
+        const int v = idx % NV, c = idx / NV, l = c % WAVE, ko = c / WAVE;
+        if (v < nv && r0 + l < a.nrows)
+            a.fx[((((size_t)(r0 + l) * a.A + ai) * GO) + (size_t)k0 * O + ko) * a.U + u0 + v] = fin[(size_t)v * VS + ko * WAVE + l];
+    }
+}
+
+#else  // PTNN_PD_REDUCTIONS: the shape-independent kernels (ptnn_analysis.hip, after ptnn_dev_select.hpp)
+
+// per distinct vector u and column c = (a * G + k) * O + o of a row: ICE summed over the rows of a block in ascending order, in
+// double, onto what the earlier blocks left -- the sum over all rows is the same whatever the block size.  One thread per (u, c),
+// reads coalesced along u.  After the last block: PD32 = the mean over the n_total rows as fp32.
+struct PdRows {
+    const float* fx;            // [nrows * AGO][U]
+    int U, AGO, nrows, last;
+    double n_total;
+    double* acc;                // [AGO][U], zeroed by the caller before the first block
+    float* pd32;                // [AGO][U]
+};
+
+__global__ void __launch_bounds__(PRED_THREADS) pd_rows_kernel(const PdRows r) {
+    const int ublocks = (r.U + PRED_THREADS - 1) / PRED_THREADS;
+    const int u = (int)(blockIdx.x % ublocks) * PRED_THREADS + threadIdx.x, c = (int)(blockIdx.x / ublocks);
+    if (u >= r.U) return;
+    const size_t k = (size_t)c * r.U + u;
+    double s = r.acc[k];
+    const float* f = r.fx + k;
+    const size_t stride = (size_t)r.AGO * r.U;
+    for (int n = 0; n < r.nrows; ++n) s += (double)f[n * stride];
+    r.acc[k] = s;
+    if (r.last) r.pd32[k] = (float)(s / r.n_total);
+}
+
+// per distinct vector u and (a, o): range = max_k PD32 - min_k PD32, the difference formed in double (exact) and rounded once
+struct PdRange {
+    const float* pd32;          // [A * G * O][U]
+    int U, A, G, O;
+    float* range;               // [A * O][U]
+};
+
+__global__ void __launch_bounds__(PRED_THREADS) pd_range_kernel(const PdRange r) {
+    const int ublocks = (r.U + PRED_THREADS - 1) / PRED_THREADS;
+    const int u = (int)(blockIdx.x % ublocks) * PRED_THREADS + threadIdx.x, ao = (int)(blockIdx.x / ublocks);
+    if (u >= r.U) return;
+    const int ai = ao / r.O, o = ao % r.O;
+    const float* p = r.pd32 + ((size_t)ai * r.G * r.O + o) * r.U + u;
+    const size_t stride = (size_t)r.O * r.U;
+    float mx = p[0], mn = p[0];
+    for (int k = 1; k < r.G; ++k) {
+        const float v = p[k * stride];
+        mx = fmaxf(mx, v);
+        mn = fminf(mn, v);
+    }
+    r.range[(size_t)ao * r.U + u] = (float)((double)mx - (double)mn);
+}
+
+// per column c = (a * G + k) * O + o, one work-group: the weighted mean over the distinct vectors of the double row means, a
+// fixed summation order for a given U
+struct PdMean {
+    const double* acc;          // [AGO][U]
+    const int* cnt;             // [U]
+    int U;
+    double n_total;
+    long long M;
+    double* mean;               // [AGO]
+};
+
+__global__ void __launch_bounds__(PRED_THREADS) pd_mean_kernel(const PdMean r) {
+    __shared__ double buf[PRED_THREADS];
+    const int tid = threadIdx.x, c = blockIdx.x;
+    double s = 0.0;
+    for (int u = tid; u < r.U; u += PRED_THREADS) s += (double)r.cnt[u] * (r.acc[(size_t)c * r.U + u] / r.n_total);
+    s = wg_sum<PRED_THREADS>(buf, s);
+    if (tid == 0) r.mean[c] = s / (double)r.M;
+}
+
+#endif

@@ -18,4 +18,5 @@ extern "C" const Shape PTNN_SHAPE_SYMBOL = {PTNN_T, PTNN_I, PTNN_O,
                                             &segment_packm_kernel<PTNN_T, PTNN_I, PTNN_O>,
                                             &predict_forward_kernel<PTNN_T, PTNN_I, PTNN_O>,
                                             &forecast_forward_kernel<PTNN_T, PTNN_I, PTNN_O>,
-                                            &sensitivity_forward_kernel<PTNN_T, PTNN_I, PTNN_O>};
+                                            &sensitivity_forward_kernel<PTNN_T, PTNN_I, PTNN_O>,
+                                            &pd_forward_kernel<PTNN_T, PTNN_I, PTNN_O>};

@@ -32,5 +32,6 @@ struct Shape {
     void (*predict_fwd)(const PredictFwd);   // posterior predictive: network outputs of distinct vectors x input rows (every H)
     void (*forecast_fwd)(const ForecastFwd); // recursive forecasts: trajectories x origins x horizon steps (REG, n_out == 1; else empty)
     void (*sens_fwd)(const SensFwd);         // input sensitivity: d output / d input of distinct vectors x input rows (every H)
+    void (*pd_fwd)(const PdFwd);             // partial dependence: outputs of distinct vectors x input rows x substituted grid values (every H)
 };
 }  // namespace ptnn

@@ -32,6 +32,9 @@ from .analysis import (  # noqa: F401
 # the prior predictive check lives in prior.py; its result tuple and prior_flagged are importable from here
 from .prior import PriorAnalysis, check_prior_scale
 from .prior import PriorPredictive, prior_flagged  # noqa: F401
+# partial dependence and ICE curves live in effects.py; the result tuple and pd_grid are importable from here
+from .effects import EffectAnalysis
+from .effects import PartialDependence, pd_grid  # noqa: F401
 
 
 def _text_round(a, fmt, threads=8):
@@ -125,7 +128,7 @@ def overlap_cuts(S, swap_interval, chunks):
     return sorted({min(S - 1, si * max(1, round(n_int * (c + 1) / K))) for c in range(K - 1)} | {S - 1})
 
 
-class ParallelTemperingBase(PosteriorAnalysis, PriorAnalysis):
+class ParallelTemperingBase(PosteriorAnalysis, PriorAnalysis, EffectAnalysis):
     task = None                       # set by the two drop-in subclasses
     rmse_fmt = None                   # REG '%1.8f' (REG:462-464), CLS '%1.2f' (CLS:473-475)
 

@@ -1,0 +1,32 @@
+"""Cost probe: pd_forward_kernel beside predict_forward_kernel, Ionosphere shape 34-50-2, same (U, rows): all 34 inputs, 16 grid
+values.  Run under `rocprofv3 --kernel-trace --stats` for the per-kernel times; the library must have been built."""
+import os
+import sys
+import tempfile
+import time
+
+ROOT = os.path.dirname(os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+sys.path.insert(0, ROOT)
+sys.path.insert(0, os.path.join(ROOT, "tests"))
+import numpy as np  # noqa: E402
+from parity import orc  # noqa: E402
+from test_gpu_analysis_shapes import _data, _vectors  # noqa: E402
+from test_gpu_predict import _pt  # noqa: E402
+
+topo = (34, 50, 2)
+U = int(sys.argv[1]) if len(sys.argv) > 1 else 4000
+G = int(sys.argv[2]) if len(sys.argv) > 2 else 16
+train, test = _data(orc.TASK_CLS, topo, 1, n_tr=234, n_te=117)
+pt = _pt(orc.TASK_CLS, topo, train, test, 4, 20, tempfile.mkdtemp(), lr=0.01, maxtemp=10)
+W = _vectors(topo, U, 2)
+for rep in range(2):
+    t0 = time.perf_counter()
+    pp = pt.posterior_predictive("test", weights=W)
+    t1 = time.perf_counter()
+    pd = pt.partial_dependence("test", grid=G, weights=W)
+    t2 = time.perf_counter()
+    ice = pt.partial_dependence("test", grid=G, weights=W, ice=True)
+    t3 = time.perf_counter()
+    print(f"rep {rep}: U = {pd.n_distinct}, rows = {test.shape[0]}, inputs = {pd.inputs.size}, grid = {G}: predictive "
+          f"{1e3 * (t1 - t0):.2f} ms, partial dependence {1e3 * (t2 - t1):.2f} ms, with ICE bands {1e3 * (t3 - t2):.2f} ms")
+print("effect_range", np.round(pd.effect_range[:6, 0], 5), "top_prob", np.round(pd.top_prob[:6, 0], 3))
