@@ -283,16 +283,28 @@ __device__ __forceinline__ void lds_load(const float* __restrict__ p, float (&v)
           "s81", "s82", "s83", "s84", "s85", "s86", "s87", "s88", "s89", "s90", "s91", "s92", "s93", "s94", "s95", "s96", \
           "s97", "s98", "s99");
 
+// What the hand-scheduled loop derives from the learning rate alone: a = (lr log2 e)^-1/2 (sa), 1 / a (sb), -a (kb), -lr a (k1),
+// -lr (k2); kb and k1 wave-uniform.  Formed where the epoch is called from, at the call: formed once per launch at the top of the
+// packed kernel it made the forward passes of the same kernel slower (profiles/README.md), which the four-wave work-groups wait for.
+struct SweepConsts { float lr, sa, sb, kb, k1, k2; };
+__device__ __forceinline__ SweepConsts sweep_consts(float lr) {
+    auto uni = [](float v) { return __builtin_bit_cast(float, __builtin_amdgcn_readfirstlane(__builtin_bit_cast(int, v))); };
+    SweepConsts k;
+    k.lr = lr;
+    const float lr_u = uni(lr);
+    k.sa = __builtin_amdgcn_rsqf(LOG2E * lr_u);
+    k.sb = __builtin_amdgcn_sqrtf(LOG2E * lr_u);
+    k.kb = uni(-k.sa); k.k1 = uni(-lr_u * k.sa); k.k2 = -lr_u;
+    return k;
+}
+
 template <int NRED>
-__device__ __forceinline__ void sweep_rows_reg41(float (&w1)[4], float& nb1, float& w2, float& cl, float m0, float lr,
-                                                 float clr, const float* gdata, int iters) {
+__device__ __forceinline__ void sweep_rows_reg41(float (&w1)[4], float& nb1, float& w2, float& cl, float m0, float clr,
+                                                 const SweepConsts& k, const float* gdata, int iters) {
     const unsigned long long gp = (unsigned long long)(uintptr_t)gdata;
     const unsigned end_lo = (unsigned)gp + (unsigned)(iters >> 1) * 256u;   // low word of the running pointer after the last 8-row pass
     const unsigned four = (unsigned)iters & 1u;                              // one more pass of 4 rows behind the loop
-    const float lr_u = __builtin_bit_cast(float, __builtin_amdgcn_readfirstlane(__builtin_bit_cast(int, lr)));
-    const float sa = __builtin_amdgcn_rsqf(LOG2E * lr_u), sb = __builtin_amdgcn_sqrtf(LOG2E * lr_u);   // a, 1 / a
-    auto uni = [](float v) { return __builtin_bit_cast(float, __builtin_amdgcn_readfirstlane(__builtin_bit_cast(int, v))); };
-    const float kb = uni(-sa), k1 = uni(-lr_u * sa), k2 = -lr_u;
+    const float sa = k.sa, sb = k.sb, kb = k.kb, k1 = k.k1, k2 = k.k2;
     float o0, o1, o2, o3, onb, ow2, ocl;
     if constexpr (NRED == 3) {
         PTNN_SW_ASM("")

@@ -227,7 +227,8 @@ __device__ __forceinline__ void segment_pack_body(const SegParams& p, const SegD
                 pp.noise = ring_n; pp.scal = ring_s; pp.w_cur = w_cur; pp.w_gd = w_gd;
                 pp.pos0 = rpos0 + wave * PK_NG; if (pp.pos0 >= RING) pp.pos0 -= RING;
                 pp.ring = RING; pp.nstride = PS; pp.step_w = p.step_w; pp.l_prob = p.l_prob; pp.use_lg = 1;
-                sgd_sweep<TASK, I, O, PK_NRED, true>(nullptr, s_pgd(wave * PK_NG), xy, p.data, p.Ntr, H, p.lr, ng, (int)SLF, &pp);
+                PTNN_DIAG(pack_sweep_args)
+                sgd_sweep<TASK, I, O, PK_NRED, true>(nullptr, s_pgd(wave * PK_NG), xy, p.data, p.Ntr, H, sweep_consts(p.lr), ng, (int)SLF, &pp);
             }
         }
         STAMP(3);                                           // sweep

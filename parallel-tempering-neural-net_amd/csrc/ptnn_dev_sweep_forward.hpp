@@ -18,12 +18,13 @@ struct SweepProposals {
     int pos0, ring, nstride;
     float step_w, l_prob;
     int use_lg;
+    PTNN_DIAG(sweep_fields)
 };
 
 template <int TASK, int I, int O, int NRED, bool PROP = false>
 __device__ __forceinline__ void sgd_sweep(const float* __restrict__ w_in, float* __restrict__ w_out,
                                           const float* __restrict__ xy, const float* __restrict__ gdata, int Ntr, int H,
-                                          float lr, int ngroups = 1, int gstride = 0, const SweepProposals* pp = nullptr) {
+                                          const SweepConsts& k, int ngroups = 1, int gstride = 0, const SweepProposals* pp = nullptr) {
     // All weights are kept pre-multiplied by c = -log2(e): the pre-activation then IS the exponent of
     // sigmoid(z) = 1 / (1 + 2^(c z)), and every update rule keeps its shape with lr folded into two constants:
     //   W1' += lr (g' dh) x,  B1' -= lr g' dh      with g' = sum_o od W2'[.,o]  (= c g)
@@ -42,30 +43,66 @@ __device__ __forceinline__ void sgd_sweep(const float* __restrict__ w_in, float*
     if constexpr (!PROP) w_in += (size_t)(gact ? grp : 0) * gstride;
     w_out += (size_t)(gact ? grp : 0) * gstride;
     const int oW2 = I * H, oB1 = oW2 + H * O, oB2 = oB1 + H;
-    const float clr = C * lr;
+    const float clr = C * k.lr;
     const float m0 = (lane == 0) ? 1.0f : 0.0f;
     float w1[I], w2[O], cl[O];
-    const float* pnz = nullptr;
-    const float* pbase = nullptr;
-    float pstep = 0.0f;
-    if constexpr (PROP) {
-        int slot = pp->pos0 + (gact ? grp : 0);
-        if (slot >= pp->ring) slot -= pp->ring;
-        pnz = pp->noise + (size_t)slot * pp->nstride;
-        pbase = (pp->use_lg && pp->scal[slot * 4] < pp->l_prob) ? pp->w_gd : pp->w_cur;
-        pstep = pp->step_w;
+    // the reference's time-series nets (4 lags -> <= 16 hidden units -> 1 output): rows 0 .. 4 floor(Ntr/4) - 1 in a hand-scheduled
+    // loop (sweep_rows_reg41), whatever is left by the generic code below
+    constexpr bool REG41 = TASK == TASK_REG && I == 4 && O == 1 && (NRED == 3 || NRED == 4);
+    float b1;
+    if constexpr (REG41) {
+        // The lane's seven input elements -- W1[.][h], W2[h], B1[h], B2 -- are read through indices that are in range for every
+        // lane (hl, group 0 for an absent group) BEFORE anything is done with them, and act / lane == 0 are applied with selects
+        // afterwards: one LDS round trip in front of the row loop, where a read guarded by act ? .. : 0 compiles to a branch and a
+        // wait of its own.  A proposal reads its coin, its noise and BOTH bases in that round trip and selects the base by the
+        // coin, then forms fmaf(step_w, noise, base) as the proposal is written with.  (These nets only: read ahead like this,
+        // the many elements of a wide net's lane cost the other shapes registers, and some of them scratch.)
+        constexpr int NE = I + 2 * O + 1;
+        const int ei[NE] = {hl, H + hl, 2 * H + hl, 3 * H + hl, oW2 + hl, oB1 + hl, oB2};
+        float wv[NE];
+        if constexpr (PROP) {
+            int slot = pp->pos0 + (gact ? grp : 0);
+            if (slot >= pp->ring) slot -= pp->ring;
+            const float* pnz = pp->noise + (size_t)slot * pp->nstride;
+            const float coin = pp->scal[slot * 4];
+            float nz[NE], bc[NE], bg[NE];
+#pragma unroll
+            for (int j = 0; j < NE; ++j) { nz[j] = pnz[ei[j]]; bc[j] = pp->w_cur[ei[j]]; bg[j] = pp->w_gd[ei[j]]; }
+            const bool lg = pp->use_lg && coin < pp->l_prob;
+#pragma unroll
+            for (int j = 0; j < NE; ++j) wv[j] = fmaf(pp->step_w, nz[j], lg ? bg[j] : bc[j]);
+        } else {
+#pragma unroll
+            for (int j = 0; j < NE; ++j) wv[j] = w_in[ei[j]];
+        }
+#pragma unroll
+        for (int i = 0; i < I; ++i) w1[i] = act ? C * wv[i] : 0.0f;
+        w2[0] = act ? C * wv[I] : 0.0f;
+        b1 = act ? C * wv[I + 1] : -1.0e30f;                   // inactive lanes: exponent +1e30 -> hid == 0 exactly
+        cl[0] = (lane == 0) ? -C * wv[I + 2] : 0.0f;
+    } else {
+        const float* pnz = nullptr;
+        const float* pbase = nullptr;
+        float pstep = 0.0f;
+        if constexpr (PROP) {
+            int slot = pp->pos0 + (gact ? grp : 0);
+            if (slot >= pp->ring) slot -= pp->ring;
+            pnz = pp->noise + (size_t)slot * pp->nstride;
+            pbase = (pp->use_lg && pp->scal[slot * 4] < pp->l_prob) ? pp->w_gd : pp->w_cur;
+            pstep = pp->step_w;
+        }
+        auto win = [&](int e) -> float {
+            if constexpr (PROP) return fmaf(pstep, pnz[e], pbase[e]);
+            else return w_in[e];
+        };
+#pragma unroll
+        for (int i = 0; i < I; ++i) w1[i] = act ? C * win(i * H + hl) : 0.0f;
+#pragma unroll
+        for (int o = 0; o < O; ++o) w2[o] = act ? C * win(oW2 + hl * O + o) : 0.0f;
+        b1 = act ? C * win(oB1 + hl) : -1.0e30f;               // inactive lanes: exponent +1e30 -> hid == 0 exactly
+#pragma unroll
+        for (int o = 0; o < O; ++o) cl[o] = (lane == 0) ? -C * win(oB2 + o) : 0.0f;
     }
-    auto win = [&](int e) -> float {
-        if constexpr (PROP) return fmaf(pstep, pnz[e], pbase[e]);
-        else return w_in[e];
-    };
-#pragma unroll
-    for (int i = 0; i < I; ++i) w1[i] = act ? C * win(i * H + hl) : 0.0f;
-#pragma unroll
-    for (int o = 0; o < O; ++o) w2[o] = act ? C * win(oW2 + hl * O + o) : 0.0f;
-    float b1 = act ? C * win(oB1 + hl) : -1.0e30f;           // inactive lanes: exponent +1e30 -> hid == 0 exactly
-#pragma unroll
-    for (int o = 0; o < O; ++o) cl[o] = (lane == 0) ? -C * win(oB2 + o) : 0.0f;
 
     // A lone wave issues one instruction (of any kind) per 4 cycles, so the epoch costs (instructions per row) x 4 cycles
     // and every hazard slot (VALU -> DPP needs two, transcendental -> use one) that holds no useful instruction is lost.
@@ -84,16 +121,6 @@ __device__ __forceinline__ void sgd_sweep(const float* __restrict__ w_in, float*
         return z;
     };
     constexpr int IPY = sweep_row_stride(I);
-    int n = 0;
-    if constexpr (TASK == TASK_REG && I == 4 && O == 1 && (NRED == 3 || NRED == 4)) {
-        // the reference's time-series nets (4 lags -> <= 8 hidden units -> 1 output): rows 0 .. 4 floor(Ntr/4) - 1 in a
-        // hand-scheduled loop (sweep_rows_reg41), whatever is left by the generic code below
-        const int iters = Ntr / 4;
-        if (iters > 0) {
-            sweep_rows_reg41<NRED>(w1, nb1, w2[0], cl[0], m0, lr, clr, gdata, iters);
-            n = 4 * iters;
-        }
-    }
     if constexpr (I <= 8) {
         auto row_step = [&](const float (&xprev)[RW], const float (&x)[RW], const float (&xnext)[RW]) {
             const float z = fmaf(lhd_p, x[I + 1], zp);
@@ -104,7 +131,7 @@ __device__ __forceinline__ void sgd_sweep(const float* __restrict__ w_in, float*
             zp = zpart(xnext);
             const float hid = __builtin_amdgcn_rcpf(1.0f + e);
             const float dh = fmaf(-hid, hid, hid);                 // hid (1 - hid)
-            const float ldh = lr * dh;
+            const float ldh = k.lr * dh;
             float g = 0.0f;
             float lod[O];
     #pragma unroll
@@ -129,23 +156,37 @@ __device__ __forceinline__ void sgd_sweep(const float* __restrict__ w_in, float*
         // ring of four row buffers: previous, current, next, and the one being fetched (row n+2).  The data image carries
         // two padding rows, so the look-ahead never leaves it.
         float xa[RW], xb[RW], xc[RW], xd[RW];
+        int n = 0;
+        if constexpr (REG41) n = 4 * (Ntr / 4);
         const float* pr = xy + (size_t)n * IPY;
         lds_load<RW>(pr, xb);
         lds_load<RW>(pr + IPY, xc);
+        if constexpr (REG41) {
+            // the rows behind the hand-scheduled loop are requested in front of it -- their addresses do not wait for it -- so
+            // that they have landed when it ends
+            if (Ntr - n >= 2) lds_load<RW>(pr + 2 * IPY, xd);
+            if (n > 0) {
+                PTNN_DIAG(sweep_asm_begin)
+                sweep_rows_reg41<NRED>(w1, nb1, w2[0], cl[0], m0, clr, k, gdata, n >> 2);
+                PTNN_DIAG(sweep_asm_end)
+            }
+        }
     #pragma unroll
         for (int i = 0; i < RW; ++i) xa[i] = 0.0f;
         zp = zpart(xb);
         pr += 2 * IPY;
-        for (; n + 3 < Ntr; n += 4) {
-            lds_load<RW>(pr, xd);
-            row_step(xa, xb, xc);
-            lds_load<RW>(pr + IPY, xa);
-            row_step(xb, xc, xd);
-            lds_load<RW>(pr + 2 * IPY, xb);
-            row_step(xc, xd, xa);
-            lds_load<RW>(pr + 3 * IPY, xc);
-            row_step(xd, xa, xb);
-            pr += 4 * IPY;
+        if constexpr (!REG41) {                             // (REG41: fewer than four rows are left)
+            for (; n + 3 < Ntr; n += 4) {
+                lds_load<RW>(pr, xd);
+                row_step(xa, xb, xc);
+                lds_load<RW>(pr + IPY, xa);
+                row_step(xb, xc, xd);
+                lds_load<RW>(pr + 2 * IPY, xb);
+                row_step(xc, xd, xa);
+                lds_load<RW>(pr + 3 * IPY, xc);
+                row_step(xd, xa, xb);
+                pr += 4 * IPY;
+            }
         }
         // tail: up to three rows; afterwards the update of the very last row is still pending
         float xl[RW];
@@ -158,13 +199,13 @@ __device__ __forceinline__ void sgd_sweep(const float* __restrict__ w_in, float*
     #pragma unroll
             for (int i = 0; i < RW; ++i) xl[i] = xb[i];
         } else if (rem == 2) {
-            lds_load<RW>(pr, xd);
+            if constexpr (!REG41) lds_load<RW>(pr, xd);     // (REG41: requested above)
             row_step(xa, xb, xc);
             row_step(xb, xc, xd);
     #pragma unroll
             for (int i = 0; i < RW; ++i) xl[i] = xc[i];
         } else {
-            lds_load<RW>(pr, xd);
+            if constexpr (!REG41) lds_load<RW>(pr, xd);
             row_step(xa, xb, xc);
             lds_load<RW>(pr + IPY, xa);
             row_step(xb, xc, xd);
@@ -184,7 +225,7 @@ __device__ __forceinline__ void sgd_sweep(const float* __restrict__ w_in, float*
 #pragma unroll
             for (int i = 1; i < I; ++i) z = fmaf(x[i], w1[i], z);
             const float hid = __builtin_amdgcn_rcpf(1.0f + __builtin_amdgcn_exp2f(z));
-            const float ldh = lr * fmaf(-hid, hid, hid);
+            const float ldh = k.lr * fmaf(-hid, hid, hid);
             float g = 0.0f;
             float lod[O];
 #pragma unroll
@@ -241,10 +282,11 @@ __device__ __forceinline__ void sgd_sweep_select(const float* w_in, float* w_out
                                                  int H, float lr) {
     // (no 4-lane variant: the packed schedule runs nets of <= 8 hidden units in 8-lane groups, and every schedule must
     // commit the same chain bit for bit)
-    if (H <= 8) sgd_sweep<TASK, I, O, 3>(w_in, w_out, xy, gdata, Ntr, H, lr);
-    else if (H <= 16) sgd_sweep<TASK, I, O, 4>(w_in, w_out, xy, gdata, Ntr, H, lr);
-    else if (H <= 32) sgd_sweep<TASK, I, O, 5>(w_in, w_out, xy, gdata, Ntr, H, lr);
-    else sgd_sweep<TASK, I, O, 6>(w_in, w_out, xy, gdata, Ntr, H, lr);
+    const SweepConsts k = sweep_consts(lr);
+    if (H <= 8) sgd_sweep<TASK, I, O, 3>(w_in, w_out, xy, gdata, Ntr, H, k);
+    else if (H <= 16) sgd_sweep<TASK, I, O, 4>(w_in, w_out, xy, gdata, Ntr, H, k);
+    else if (H <= 32) sgd_sweep<TASK, I, O, 5>(w_in, w_out, xy, gdata, Ntr, H, k);
+    else sgd_sweep<TASK, I, O, 6>(w_in, w_out, xy, gdata, Ntr, H, k);
 }
 // The epoch is called out of line from the cooperative and the multi-CU speculative kernels: inlined (twice, four lane-group
 // variants each) its registers pushed the kernels' own loop state into scratch even in runs that never take a Langevin step --
@@ -258,8 +300,9 @@ template <int TASK, int I, int O>
 __device__ __attribute__((noinline)) void sgd_sweep_call(const float* w_in, float* w_out, const float* xy, const float* gdata,
                                                          int Ntr, int H, float lr) {
     if constexpr (TASK == TASK_REG && I == 4 && O == 1) {
-        if (H <= 32) sgd_sweep<TASK, I, O, 5>(w_in, w_out, xy, gdata, Ntr, H, lr);
-        else sgd_sweep<TASK, I, O, 6>(w_in, w_out, xy, gdata, Ntr, H, lr);
+        const SweepConsts k = sweep_consts(lr);
+        if (H <= 32) sgd_sweep<TASK, I, O, 5>(w_in, w_out, xy, gdata, Ntr, H, k);
+        else sgd_sweep<TASK, I, O, 6>(w_in, w_out, xy, gdata, Ntr, H, k);
     } else {
         sgd_sweep_select<TASK, I, O>(w_in, w_out, xy, gdata, Ntr, H, lr);
     }
@@ -268,8 +311,8 @@ template <int TASK, int I, int O>
 __device__ __forceinline__ void sgd_sweep_dispatch(const float* w_in, float* w_out, const float* xy, const float* gdata, int Ntr,
                                                    int H, float lr) {
     if constexpr (TASK == TASK_REG && I == 4 && O == 1) {
-        if (H <= 8) sgd_sweep<TASK, I, O, 3>(w_in, w_out, xy, gdata, Ntr, H, lr);
-        else if (H <= 16) sgd_sweep<TASK, I, O, 4>(w_in, w_out, xy, gdata, Ntr, H, lr);
+        if (H <= 8) sgd_sweep<TASK, I, O, 3>(w_in, w_out, xy, gdata, Ntr, H, sweep_consts(lr));
+        else if (H <= 16) sgd_sweep<TASK, I, O, 4>(w_in, w_out, xy, gdata, Ntr, H, sweep_consts(lr));
         else sgd_sweep_call<TASK, I, O>(w_in, w_out, xy, gdata, Ntr, H, lr);
     } else {
         sgd_sweep_call<TASK, I, O>(w_in, w_out, xy, gdata, Ntr, H, lr);

@@ -112,17 +112,41 @@ static __device__ unsigned long long fw_dbg[8];
 #define PTNN_DIAG_pack_begin \
     const bool stamp_on = (blockIdx.x == 0 && wave == 0); \
     unsigned long long stamp_acc[10] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0}; \
-    unsigned long long stamp_sub[5] = {0, 0, 0, 0, 0}; \
+    unsigned long long stamp_sub[7] = {0, 0, 0, 0, 0, 0, 0}; \
     unsigned long long stamp_last = __builtin_amdgcn_s_memtime(); \
     __builtin_amdgcn_s_waitcnt(0xC07F); \
-    unsigned long long stamp_rounds = 0, stamp_eval = 0; \
+    unsigned long long stamp_rounds = 0, stamp_eval = 0, stamp_arrive = 0; \
     const unsigned long long stamp_t0 = stamp_last;
 
 #define PTNN_DIAG_pack_eval_begin \
     const unsigned long long ev_t0 = __builtin_amdgcn_s_memtime();
 
+// Arrival at the barrier behind the forward passes: wave 0 (sweep) and the first forward wave each add up the clock they arrive at
+// (sums wrap; their difference does not), so (sum of wave 0) - (sum of the forward wave) over the rounds is the time the forward
+// wave waits there for the sweep waves: the slack a shorter sweep path can use.
 #define PTNN_DIAG_pack_eval_end \
-    if (ev_i == 0) stamp_eval += __builtin_amdgcn_s_memtime() - ev_t0;
+    { \
+        const unsigned long long ev_t1 = __builtin_amdgcn_s_memtime(); \
+        if (ev_i == 0) stamp_eval += ev_t1 - ev_t0; \
+        if (blockIdx.x == 0 && (ev_i == 0 || wave == 0)) stamp_arrive += ev_t1; \
+    }
+
+// The two points around the hand-scheduled row loop of the packed sweep (sgd_sweep<PROP>): cycles from the phase's start (STAMP(2))
+// to the first instruction of the asm block and to the first one behind it.  Each drains the LDS queue, like every STAMP_SUB.
+#define PTNN_DIAG_sweep_fields \
+    bool diag_on = false; unsigned long long diag_last = 0; unsigned long long* diag_sub = nullptr;
+#define PTNN_DIAG_pack_sweep_args \
+    pp.diag_on = stamp_on; pp.diag_last = stamp_last; pp.diag_sub = stamp_sub + 5;
+#define PTNN_DIAG_SWEEP_POINT(q_) \
+    if constexpr (PROP) { \
+        if (pp->diag_on) { \
+            const unsigned long long t_ = __builtin_amdgcn_s_memtime(); \
+            __builtin_amdgcn_s_waitcnt(0xC07F); \
+            pp->diag_sub[q_] += t_ - pp->diag_last; \
+        } \
+    }
+#define PTNN_DIAG_sweep_asm_begin PTNN_DIAG_SWEEP_POINT(0)
+#define PTNN_DIAG_sweep_asm_end PTNN_DIAG_SWEEP_POINT(1)
 
 #define PTNN_DIAG_pack_flush \
     if (stamp_on && lane == 0 && p.stamps) { \
@@ -131,7 +155,10 @@ static __device__ unsigned long long fw_dbg[8];
         atomicAdd(p.stamps + 10, __builtin_amdgcn_s_memtime() - stamp_t0); \
     } \
     if (stamp_on && lane == 0 && p.stamps) for (int q_ = 0; q_ < 5; ++q_) atomicAdd(p.stamps + 144 + q_, stamp_sub[q_]); \
-    if (blockIdx.x == 0 && ev_i == 0 && lane == 0 && p.stamps) atomicAdd(p.stamps + 11, stamp_eval); \
+    if (stamp_on && lane == 0 && p.stamps) {                /* 150 ..: the cooperative kernel's fw_dbg, which this kernel never writes */ \
+        atomicAdd(p.stamps + 150, stamp_sub[5]); atomicAdd(p.stamps + 151, stamp_sub[6]); atomicAdd(p.stamps + 152, stamp_arrive); \
+    } \
+    if (blockIdx.x == 0 && ev_i == 0 && lane == 0 && p.stamps) { atomicAdd(p.stamps + 11, stamp_eval); atomicAdd(p.stamps + 153, stamp_arrive); } \
     if (tid == 0 && p.stamps && r < 64) { \
         atomicAdd(p.stamps + 16 + 2 * r, __builtin_amdgcn_s_memtime() - stamp_t0); \
         atomicAdd(p.stamps + 17 + 2 * r, stamp_rounds); \

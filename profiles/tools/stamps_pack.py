@@ -2,7 +2,7 @@
 Sunspot 64 replicas, Langevin p = 0.5, one whole run of S = 10 000: replica 0 / wave 0."""
 import os, sys, time, numpy as np
 R = os.path.dirname(os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
-os.environ["PTNN_LIBRARY"] = os.path.join(R, "profiles/tools/libptnn_stamps.so")
+os.environ["PTNN_LIBRARY"] = os.environ.get("STAMPS_LIB", os.path.join(R, "profiles/tools/libptnn_stamps.so"))
 sys.path.insert(0, R)
 import bench
 import argparse
@@ -27,6 +27,13 @@ subs = ["MH: operand reads that do not wait for the epoch", "MH: verdict compute
 for n, v in zip(subs, st[144:149]):
     if v:
         print(f"    {n:50s} {v/max(rounds,1):9.0f} cyc/round from the phase's start")
+# the hand-scheduled row loop inside the sweep, and who waits for whom at the barrier behind the forward passes
+for n, v in zip(["sweep: first instruction of the asm block", "sweep: first instruction behind the asm block"], st[150:152]):
+    if v:
+        print(f"    {n:50s} {v/max(rounds,1):9.0f} cyc/round from the phase's start")
+slack = (int(st[152]) - int(st[153])) % (1 << 64)
+slack -= (1 << 64) if slack >= (1 << 63) else 0
+print(f"    forward wave 0 waits for sweep wave 0 at the barrier behind the forward passes: {slack/max(rounds,1):9.0f} cyc/round (negative: the sweep wave waits)")
 per = np.array(st[16:16+128], dtype=np.float64).reshape(64, 2)
 print('   per-replica us/interval:', np.round(per[:, 0]/nint/2.4e3).astype(int).tolist())
 print('   per-replica rounds/interval:', np.round(per[:, 1]/nint, 1).tolist())
