@@ -170,6 +170,7 @@ typedef struct {
     double eta, tau_pro, likelihood, prior_current;
     double last_logalpha, last_u, last_scale;
     double last_lik_cur, last_prior_cur;        /* the cached likelihood / prior the step's log alpha was formed with (after the R10 switch) */
+    double last_eta_pro;                        /* the eta the step proposed (REG; CLS: the chain's eta) */
     const double *train, *test;                 /* [N][ncols] row-major */
     double* w;                                  /* [P] current state */
     double *pos_w, *likeh, *accept_list, *rmse_train, *rmse_test, *acc_train, *acc_test;   /* traces: [S][P], [S][2], [S] ... */
@@ -266,7 +267,7 @@ int orc_replica_step(orc_replica* r, int i, int force) {
     r->accept_list[i + 1] = (double)r->num_accepted;               /* Q7: the count BEFORE this step (REG:380) */
     r->likeh[2 * (i + 1)] = (r->task == TASK_REG) ? lik_prop : lik_prop * r->adapttemp;     /* REG:391 / CLS:404 */
     r->last_logalpha = la; r->last_u = u; r->last_stale = r->lik_stale;
-    r->last_lik_cur = r->likelihood; r->last_prior_cur = r->prior_current;
+    r->last_lik_cur = r->likelihood; r->last_prior_cur = r->prior_current; r->last_eta_pro = eta_pro;
     r->last_scale = fabs(lik_prop) + fabs(r->likelihood) + fabs(prior_prop) + fabs(r->prior_current) +
                     (diff_prop != 0.0 ? (fabs(first) + fabs(second)) / r->adapttemp : 0.0);
     const int natural = (u < mh) ? 1 : 0;
@@ -294,59 +295,114 @@ int orc_replica_step(orc_replica* r, int i, int force) {
     return take;
 }
 
+/* out[j] = fmaf(a, x[j], b[j]) in float32 with ONE rounding (libm's fmaf): how every device schedule forms a proposal,
+ * w' = fmaf(step_w, noise, base) and eta' = fmaf(step_eta, n_eta, eta).  A float64 multiply-add rounded to float32 rounds twice
+ * and can differ in the last bit (tests/test_follow_ident_cpu.py constructs such cases). */
+void orc_fmaf(float a, const float* x, const float* b, float* out, int64_t n) {
+    for (int64_t j = 0; j < n; ++j) out[j] = fmaf(a, x[j], b[j]);
+}
+
+/* One MH step EVALUATED at a given proposal, nothing advanced: log alpha = (lik(w') - lik) + (prior(w') - prior) + diff_prop
+ * (REG:365-372) in float64 from the base state w, the proposal (w', eta'), the chain's cached likelihood / prior of w as they stood
+ * before the step (stale or not), the temperature of the step and, for a Langevin step (noise != NULL), first = -|w - sgd(w')|^2 /
+ * 2 step^2 with a float64 epoch of w' and second = -|noise|^2 / 2.  lik = the likeh_list entry of the step (REG:391 tempered /
+ * CLS:404 times adapttemp).  w_pgd [P], sc [2 H + 2 O]: scratch. */
+typedef struct { double la, scale, lik, lik_prop, prior_prop; } orc_eval;
+static orc_eval eval_at(const orc_replica* r, const double* w, const double* w_prop, double eta_pro, double lik_cur, double prior_cur,
+                        double adapttemp, const double* noise, double* w_pgd, double* sc) {
+    const int P = r->P;
+    const double tau = (r->task == TASK_REG) ? exp(eta_pro) : 1.0;
+    orc_eval e;
+    e.lik_prop = orc_likelihood(r->task, r->I, r->H, r->O, r->train, r->Ntr, r->ncols, w_prop, tau, adapttemp, NULL, NULL, NULL, sc);
+    e.prior_prop = orc_prior(r->task, r->I, r->H, r->O, r->sigma_sq, r->nu1, r->nu2, w_prop, tau);
+    double diff = 0.0, first = 0.0, second = 0.0;
+    if (noise) {
+        orc_langevin_gradient(r->task, r->I, r->H, r->O, r->train, r->Ntr, r->ncols, w_prop, r->lr, w_pgd, sc);
+        double a = 0.0, b = 0.0;
+        for (int j = 0; j < P; ++j) { const double dc = w[j] - w_pgd[j]; a += dc * dc; b += noise[j] * noise[j]; }
+        first = -0.5 * a / (r->step_w * r->step_w); second = -0.5 * b;
+        diff = (first - second) / adapttemp;
+    }
+    e.la = (e.lik_prop - lik_cur) + (e.prior_prop - prior_cur) + diff;
+    e.scale = fabs(e.lik_prop) + fabs(lik_cur) + fabs(e.prior_prop) + fabs(prior_cur) + (fabs(first) + fabs(second)) / adapttemp;
+    e.lik = (r->task == TASK_REG) ? e.lik_prop : e.lik_prop * adapttemp;
+    return e;
+}
+
+/* eval_at for callers outside: any step of a run, accepted or rejected, from the records orc_replica_run hands out (orc_step_rec)
+ * and a proposal of the caller's choice -- a device's own, rebuilt bit for bit from its tape (tests/parity.py).  `r` supplies the
+ * problem (net, data, lr, step_w, prior) and scratch; its chain is not touched.  out = {log alpha, scale, likeh entry}. */
+void orc_replica_eval_at(const orc_replica* r, const double* w, const double* w_prop, double eta_pro, double lik_cur, double prior_cur,
+                         double adapttemp, const double* noise /* NULL: random walk */, double out[3]) {
+    const orc_eval e = eval_at(r, w, w_prop, eta_pro, lik_cur, prior_cur, adapttemp, noise, r->scratch + 3 * r->P, r->scratch + 4 * r->P);
+    out[0] = e.la; out[1] = e.scale; out[2] = e.lik;
+}
+
+/* what orc_replica_eval_at needs of every step of a run, row (i - i0) each; any pointer may be NULL */
+typedef struct {
+    float* w_before;                             /* [n][P] the state the step started from (exact where it is an fp32 state) */
+    double *eta_before, *lik_cur, *prior_cur;    /* [n] its eta; the cached likelihood / prior log alpha was formed with */
+    double* adapttemp;                           /* [n] the temperature of the step */
+    int8_t* lg;                                  /* [n] the Langevin coin: 1 = the step drew a Langevin proposal */
+    double *w_prop, *eta_pro;                    /* [n][P], [n]: the chain's OWN float64 proposal */
+} orc_step_rec;
+
 /* steps [i0, i1) of one chain (the chains are independent between two swap rounds); force: NULL or one byte per step
  * (-1 / 0 / 1); per-step records (any may be NULL): log alpha, log u, scale, decided-on-a-stale-likelihood, natural decision */
 void orc_replica_run(orc_replica* r, int i0, int i1, const int8_t* force, double* logalpha, double* logu, double* scale,
                      int8_t* stale, int8_t* natural, const float* sync_w, int64_t sync_stride, const float* sync_eta, int64_t sync_eta_stride,
-                     double* la_sync, double* scale_sync, double* lik_sync) {
+                     double* la_sync, double* scale_sync, double* lik_sync, const orc_step_rec* rec) {
     /* sync_w (or NULL): the other implementation's recorded pos_w rows (float32), the row MH step i wrote (trace row i + 1) at
      * sync_w + (i - i0) * sync_stride; sync_eta (or NULL): its eta after step i at sync_eta[(i - i0) * sync_eta_stride].  After
-     * every ACCEPTED step the chain's state is set from them (orc_replica_set_state).  The chain's own trace rows keep its own
-     * float64 proposal, so comparing them with the other side's rows measures ONE step from a common state.
+     * every ACCEPTED step the chain's state is set from them (as orc_replica_set_state does).  The chain's own trace rows keep its
+     * own float64 proposal, so comparing them with the other side's rows measures ONE step from a common state.
      *
      * la_sync / scale_sync / lik_sync (or NULL; NaN on rejected steps): the accepted step RE-EVALUATED AT THE OTHER SIDE'S OWN
-     * PROPOSAL -- the recorded row is the proposal it accepted, so log alpha = (lik(w') - lik) + (prior(w') - prior) + diff_prop
-     * (REG:365-372) is formed here in float64 from exactly the inputs the other side had: the common state w, its proposal w' and
-     * eta', this chain's cached likelihood / prior of w, and for a Langevin step first = -|w - sgd(w')|^2 / 2 step^2 with this
-     * chain's float64 epoch of w', second = -|noise|^2 / 2.  What differs from the other side's recorded value is then the
+     * PROPOSAL -- the recorded row is the proposal it accepted, so eval_at forms log alpha in float64 from exactly the inputs the
+     * other side had: the common state w, its proposal w' and eta', this chain's cached likelihood / prior of w, and for a Langevin
+     * step this chain's float64 epoch of w' and its noise.  What differs from the other side's recorded value is then the
      * arithmetic of ONE evaluation (forward passes, sums, one SGD epoch), not the position of the proposal: with tau^2 ~ 1e-4 a
-     * proposal moved by half a float32 ulp already changes log alpha by 1e-4 .. 1e-2.  lik_sync = the likeh_list entry of that
-     * step at the other side's proposal (REG:391 tempered / CLS:404 times adapttemp). */
+     * proposal moved by half a float32 ulp already changes log alpha by 1e-4 .. 1e-2.  The REJECTED steps leave no proposal in
+     * the trace: `rec` hands out what orc_replica_eval_at needs to do the same for them from a rebuilt proposal. */
     const int P = r->P;
-    double* wtmp = sync_w ? (double*)malloc((size_t)2 * P * sizeof(double)) : NULL;
+    double* wtmp = (sync_w || rec) ? (double*)malloc((size_t)2 * P * sizeof(double)) : NULL;
     double* w_before = wtmp ? wtmp + P : NULL;
     for (int i = i0; i < i1; ++i) {
-        if (la_sync) la_sync[i - i0] = NAN;
-        if (scale_sync) scale_sync[i - i0] = NAN;
-        if (lik_sync) lik_sync[i - i0] = NAN;
-        if (sync_w) memcpy(w_before, r->w, (size_t)P * sizeof(double));
-        const int took = orc_replica_step(r, i, force ? (int)force[i - i0] : -1);
-        if (logalpha) logalpha[i - i0] = r->last_logalpha;
-        if (logu) logu[i - i0] = log(r->last_u);
-        if (scale) scale[i - i0] = r->last_scale;
-        if (stale) stale[i - i0] = (int8_t)r->last_stale;
-        if (natural) natural[i - i0] = (int8_t)r->last_natural;
+        const size_t k = (size_t)(i - i0);
+        if (la_sync) la_sync[k] = NAN;
+        if (scale_sync) scale_sync[k] = NAN;
+        if (lik_sync) lik_sync[k] = NAN;
+        if (w_before) memcpy(w_before, r->w, (size_t)P * sizeof(double));
+        const double eta_before = r->eta;
+        const int took = orc_replica_step(r, i, force ? (int)force[k] : -1);
+        if (logalpha) logalpha[k] = r->last_logalpha;
+        if (logu) logu[k] = log(r->last_u);
+        if (scale) scale[k] = r->last_scale;
+        if (stale) stale[k] = (int8_t)r->last_stale;
+        if (natural) natural[k] = (int8_t)r->last_natural;
+        if (rec) {
+            if (rec->w_before) for (int j = 0; j < P; ++j) rec->w_before[k * P + j] = (float)w_before[j];
+            if (rec->eta_before) rec->eta_before[k] = eta_before;
+            if (rec->lik_cur) rec->lik_cur[k] = r->last_lik_cur;
+            if (rec->prior_cur) rec->prior_cur[k] = r->last_prior_cur;
+            if (rec->adapttemp) rec->adapttemp[k] = r->adapttemp;
+            if (rec->lg) rec->lg[k] = (int8_t)r->last_lg;
+            if (rec->w_prop) memcpy(rec->w_prop + k * P, r->scratch + P, (size_t)P * sizeof(double));
+            if (rec->eta_pro) rec->eta_pro[k] = r->last_eta_pro;
+        }
         if (took && sync_w) {
-            const float* row = sync_w + (size_t)(i - i0) * (size_t)sync_stride;
+            const float* row = sync_w + k * (size_t)sync_stride;
             for (int j = 0; j < P; ++j) wtmp[j] = (double)row[j];
-            const double lik0 = r->last_lik_cur, pri0 = r->last_prior_cur;
-            orc_replica_set_state(r, wtmp, sync_eta ? (double)sync_eta[(size_t)(i - i0) * (size_t)sync_eta_stride] : NAN);
+            if (sync_eta && r->task == TASK_REG) r->eta = (double)sync_eta[k * (size_t)sync_eta_stride];
+            const orc_eval e = eval_at(r, w_before, wtmp, r->eta, r->last_lik_cur, r->last_prior_cur, r->adapttemp,
+                                       r->last_lg ? r->scratch : NULL, r->scratch + 3 * P, r->scratch + 4 * P);
+            /* the chain continues from the other side's state, likelihood and prior in float64 from it (orc_replica_set_state) */
+            memcpy(r->w, wtmp, (size_t)P * sizeof(double));
+            r->likelihood = e.lik_prop; r->prior_current = e.prior_prop; r->lik_stale = 0;
             if (r->task == TASK_REG) r->tau_pro = exp(r->eta);      /* the last proposed tau IS this accepted one (Q9 reads it at the switch) */
-            if (la_sync || scale_sync) {
-                double diff = 0.0, first = 0.0, second = 0.0;
-                if (r->last_lg) {
-                    double *noise = r->scratch, *w_pgd = noise + 3 * P, *sc = noise + 4 * P;
-                    orc_langevin_gradient(r->task, r->I, r->H, r->O, r->train, r->Ntr, r->ncols, wtmp, r->lr, w_pgd, sc);
-                    double a = 0.0, b = 0.0;
-                    for (int j = 0; j < P; ++j) { const double dc = w_before[j] - w_pgd[j]; a += dc * dc; b += noise[j] * noise[j]; }
-                    first = -0.5 * a / (r->step_w * r->step_w); second = -0.5 * b;
-                    diff = (first - second) / r->adapttemp;
-                }
-                if (la_sync) la_sync[i - i0] = (r->likelihood - lik0) + (r->prior_current - pri0) + diff;
-                if (scale_sync) scale_sync[i - i0] = fabs(r->likelihood) + fabs(lik0) + fabs(r->prior_current) + fabs(pri0) +
-                                                     (fabs(first) + fabs(second)) / r->adapttemp;
-            }
-            if (lik_sync) lik_sync[i - i0] = (r->task == TASK_REG) ? r->likelihood : r->likelihood * r->adapttemp;
+            if (la_sync) la_sync[k] = e.la;
+            if (scale_sync) scale_sync[k] = e.scale;
+            if (lik_sync) lik_sync[k] = e.lik;
         }
     }
     free(wtmp);

@@ -37,9 +37,14 @@ class _Rep(C.Structure):
                 [("seed", C.c_uint64)] +
                 [(n, C.c_double) for n in ("T", "adapttemp", "l_prob", "lr", "step_w", "step_eta", "sigma_sq", "nu1", "nu2", "pt_samples",
                                            "eta", "tau_pro", "likelihood", "prior_current", "last_logalpha", "last_u", "last_scale",
-                                           "last_lik_cur", "last_prior_cur")] +
+                                           "last_lik_cur", "last_prior_cur", "last_eta_pro")] +
                 [(n, _dp) for n in ("train", "test", "w", "pos_w", "likeh", "accept_list", "rmse_train", "rmse_test", "acc_train",
                                     "acc_test", "scratch")])
+
+
+class _StepRec(C.Structure):
+    """orc_step_rec: where orc_replica_run leaves what orc_replica_eval_at needs of every step."""
+    _fields_ = [(n, C.c_void_p) for n in ("w_before", "eta_before", "lik_cur", "prior_cur", "adapttemp", "lg", "w_prop", "eta_pro")]
 
 
 _lib = None
@@ -54,7 +59,9 @@ def lib():
         l_.orc_replica_step.argtypes = [C.POINTER(_Rep), C.c_int, C.c_int]
         l_.orc_replica_init.argtypes = [C.POINTER(_Rep)]
         l_.orc_replica_run.argtypes = [C.POINTER(_Rep), C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
-                                       C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p]
+                                       C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(_StepRec)]
+        l_.orc_replica_eval_at.argtypes = [C.POINTER(_Rep), _dp, _dp] + [C.c_double] * 4 + [_dp, _dp]
+        l_.orc_fmaf.argtypes = [C.c_float, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64]
         l_.orc_replica_set_state.argtypes = [C.POINTER(_Rep), _dp, C.c_double]
         l_.orc_likelihood.restype = C.c_double
         l_.orc_likelihood.argtypes = [C.c_int] * 4 + [_dp, C.c_int, C.c_int, _dp, C.c_double, C.c_double, _dp, _dp, _dp, _dp]
@@ -113,6 +120,16 @@ def w_noise(seed, replica, step, n):
     return out
 
 
+def fmaf(a, x, b):
+    """float32 fmaf(a, x[j], b[j]) with ONE rounding (C's fmaf), elementwise: the device's w' = fmaf(step_w, noise, base) and
+    eta' = fmaf(step_eta, n_eta, eta).  a: scalar; x, b: float32 arrays of one shape."""
+    x, b = (np.ascontiguousarray(v, dtype=np.float32) for v in (x, b))
+    assert x.shape == b.shape
+    out = np.empty_like(x)
+    lib().orc_fmaf(float(np.float32(a)), x.ctypes.data, b.ctypes.data, out.ctypes.data, x.size)
+    return out
+
+
 class CReplica:
     """One chain in C (orc_replica), with the attribute names of ptnn_oracle.Replica."""
 
@@ -152,14 +169,14 @@ class CReplica:
     # scalar state lives in the C struct
     def __getattr__(self, name):
         if name in ("eta", "tau_pro", "likelihood", "prior_current", "adapttemp", "T", "num_accepted", "langevin_count", "init_count",
-                    "last_logalpha", "last_u", "last_scale", "noise_gid"):
+                    "last_logalpha", "last_u", "last_scale", "noise_gid", "last_eta_pro"):
             return getattr(self.__dict__["c"], name)
         if name in ("lik_stale", "last_stale", "last_natural", "last_forced"):
             return bool(getattr(self.__dict__["c"], name))
         raise AttributeError(name)
 
     def __setattr__(self, name, value):
-        if name in ("eta", "likelihood", "prior_current", "adapttemp", "T", "noise_gid"):
+        if name in ("eta", "tau_pro", "likelihood", "prior_current", "adapttemp", "T", "noise_gid"):
             setattr(self.c, name, value)
         elif name == "lik_stale":
             self.c.lik_stale = int(bool(value))
@@ -175,11 +192,13 @@ class CReplica:
     def step(self, i, force=None):
         return bool(lib().orc_replica_step(C.byref(self.c), int(i), -1 if force is None else int(bool(force))))
 
-    def run(self, i0, i1, force=None, sync_w=None, sync_eta=None):
+    def run(self, i0, i1, force=None, sync_w=None, sync_eta=None, records=False):
         """Steps [i0, i1); force: None or int8 [i1 - i0] of -1 / 0 / 1.  sync_w: float32 [i1 - i0, >= P] (row k = the pos_w row
         another implementation recorded for MH step i0 + k), sync_eta: float32 [i1 - i0] (its eta after that step) or None:
         after every accepted step the chain continues from that state, likelihood and prior re-evaluated in float64
-        (orc_replica_set_state).  -> dict of per-step records."""
+        (orc_replica_set_state).  records: also what eval_at() needs of every step -- w_before float32 [n, P], eta_before,
+        lik_cur, prior_cur, adapttemp [n], lg int8 [n] (the Langevin coin) -- and the chain's own float64 proposal w_prop [n, P],
+        eta_pro [n].  -> dict of per-step records."""
         n = i1 - i0
         rec = dict(logalpha=np.empty(n), logu=np.empty(n), scale=np.empty(n), stale=np.empty(n, dtype=np.int8), natural=np.empty(n, dtype=np.int8))
         f = None if force is None else np.ascontiguousarray(force, dtype=np.int8)
@@ -196,10 +215,27 @@ class CReplica:
             # the accepted steps re-evaluated at the other side's own proposal (NaN on rejected steps): see orc_replica_run
             rec.update(la_sync=np.empty(n), scale_sync=np.empty(n), lik_sync=np.empty(n))
             extra = [rec[k].ctypes.data for k in ("la_sync", "scale_sync", "lik_sync")]
+        srec = None
+        if records:
+            rec.update(w_before=np.empty((n, self.P), dtype=np.float32), lg=np.empty(n, dtype=np.int8), w_prop=np.empty((n, self.P)),
+                       **{k: np.empty(n) for k in ("eta_before", "lik_cur", "prior_cur", "adapttemp", "eta_pro")})
+            srec = C.byref(_StepRec(**{k: rec[k].ctypes.data for k, _ in _StepRec._fields_}))
         lib().orc_replica_run(C.byref(self.c), int(i0), int(i1), None if f is None else f.ctypes.data, rec["logalpha"].ctypes.data,
                               rec["logu"].ctypes.data, rec["scale"].ctypes.data, rec["stale"].ctypes.data, rec["natural"].ctypes.data,
-                              sw, ss, se, es, *extra)
+                              sw, ss, se, es, *extra, srec)
         return rec
+
+    def eval_at(self, w, w_prop, eta_pro, lik_cur, prior_cur, adapttemp, noise=None):
+        """One MH step evaluated in float64 at a GIVEN proposal without advancing the chain (orc_replica_eval_at): base state w,
+        proposal (w_prop, eta_pro), the cached likelihood / prior of w the step decided on, its temperature, and for a Langevin
+        step its noise row.  -> (log alpha, scale, likeh entry), built as the accepted steps of a synced run() are."""
+        w, w_prop = _f64(w), _f64(w_prop)
+        assert w.shape == (self.P,) and w_prop.shape == (self.P,)
+        nz = None if noise is None else _f64(noise)
+        out = np.empty(3)
+        lib().orc_replica_eval_at(C.byref(self.c), _p(w), _p(w_prop), float(eta_pro), float(lik_cur), float(prior_cur), float(adapttemp),
+                                  None if nz is None else _p(nz), _p(out))
+        return tuple(out)
 
     def set_state(self, w, eta=None):
         """Continue from another implementation's state: (w, eta) replaced, the cached likelihood / prior re-evaluated from it in
