@@ -42,11 +42,24 @@ int ptnn::fail(int code, const char* fmt, ...) {
 #define X_DECL(T, I, O) extern "C" const ptnn::Shape ptnn_shape_##T##_##I##_##O;
 PTNN_SHAPES(X_DECL)
 #undef X_DECL
+// ... and one entry per fixed-width packed kernel, each in a translation unit of its own too (ptnn_shape.hip with -DPTNN_HC)
+#define X_DECL(T, I, O, H) extern "C" const ptnn::PackFixed ptnn_pack_fixed_##T##_##I##_##O##_##H;
+PTNN_PACK_FIXED(X_DECL)
+#undef X_DECL
+#define X_DECL(T, I, O, H) extern "C" const ptnn::PackFixed ptnn_packm_fixed_##T##_##I##_##O##_##H;
+PTNN_PACKM_FIXED(X_DECL)
+#undef X_DECL
 
 namespace {
 
 #define X_ENTRY(T, I, O) &ptnn_shape_##T##_##I##_##O,
 const Shape* const g_shapes[] = {PTNN_SHAPES(X_ENTRY)};
+#undef X_ENTRY
+#define X_ENTRY(T, I, O, H) &ptnn_pack_fixed_##T##_##I##_##O##_##H,
+const PackFixed* const g_pack_fixed[] = {PTNN_PACK_FIXED(X_ENTRY) nullptr};     // (the list may be empty: a diagnostic build of one shape)
+#undef X_ENTRY
+#define X_ENTRY(T, I, O, H) &ptnn_packm_fixed_##T##_##I##_##O##_##H,
+const PackFixed* const g_packm_fixed[] = {PTNN_PACKM_FIXED(X_ENTRY) nullptr};
 #undef X_ENTRY
 constexpr int MAX_HIDDEN = MAX_WAVES * WAVE;    // wide nets: one thread per hidden unit
 
@@ -123,6 +136,18 @@ inline bool swap_trigger(const ptnn_config& c, int i) {
 }
 
 seg_fn segment_function(const Shape* sh, SegKind k) { return sh->*g_seg[k].fn; }
+
+// the shape's packed kernel (multi: over several CUs) with the hidden width H compiled in, or null (PTNN_PACK_FIXED, PTNN_PACKM_FIXED)
+seg_fn pack_fixed_function(const Shape* sh, int H, bool multi) {
+    for (const PackFixed* const* f = multi ? g_packm_fixed : g_pack_fixed; *f; ++f)
+        if ((*f)->task == sh->task && (*f)->I == sh->I && (*f)->O == sh->O && (*f)->H == H) return (*f)->pack;
+    return nullptr;
+}
+// the kernel a plan launches
+seg_fn plan_function(const Shape* sh, const LaunchPlan& plan) {
+    const bool packed = plan.kind == SEG_PACK || plan.kind == SEG_PACKM;
+    return (packed && plan.pack_hc > 0) ? pack_fixed_function(sh, plan.pack_hc, plan.kind == SEG_PACKM) : segment_function(sh, plan.kind);
+}
 
 void collect_timing(ptnn_handle* h) {
     for (size_t k = 0; k < h->timing_used; ++k) {
@@ -247,7 +272,7 @@ int launch_segment(ptnn_handle* h, int begin, int end, bool swap_inside = false,
         ev = &h->timing[h->timing_used++];
         HIP_TRY(hipEventRecord(ev->first, h->stream));
     }
-    hipLaunchKernelGGL(segment_function(h->shape, h->plan.kind), dim3(grid), dim3(h->plan.threads), h->plan.seg_lds, h->stream, p, pp, begin);
+    hipLaunchKernelGGL(plan_function(h->shape, h->plan), dim3(grid), dim3(h->plan.threads), h->plan.seg_lds, h->stream, p, pp, begin);
     h->epoch_base += (unsigned)(end - begin) + 1u + (swap_inside ? (unsigned)((end - begin) / h->cfg.swap_interval + 2) : 0u);   // granule tags never repeat across launches
     HIP_TRY(hipGetLastError());
     if (ev) HIP_TRY(hipEventRecord(ev->second, h->stream));
@@ -430,6 +455,20 @@ int plan_packed(const ptnn_handle& h, int Nall, int sched, LaunchPlan& plan) {
     // slots per round, segment_packm_kernel): Mackey-Glass 4-10-1, 64 replicas needs 18.7 / 13.6 / 11.6 rounds per swap interval
     // with 8 / 16 / 32 slots (profiles/r03_window_sim.jsonl) and a packed round is shorter than the multi-CU speculative one (the
     // forward passes run beside the epochs).  groups_per_replica = 1, 2, 4 decides otherwise.
+    // The kernel with this hidden width compiled in where the shape has one (one CU: 4-5-1, 5-5-1; several: 4-10-1), unless
+    // $PTNN_PACK_FIXED_H=0 asks for the run-time-width kernels (the comparison path of the tests and of an A/B run).  The lengths such a
+    // kernel forms at compile time are ptnn_dims.hpp's, like the handle's: checked below, since the kernel would not notice.
+    const char* const fixed_env = std::getenv("PTNN_PACK_FIXED_H");
+    auto fixed = [&](bool multi) { return !(fixed_env && fixed_env[0] == '0') && pack_fixed_function(h.shape, H, multi) != nullptr; };
+    {
+        const int Pc = dims_P(c.n_in, H, c.n_out);
+        if ((fixed(false) || fixed(true)) &&
+            (h.P != Pc || h.PS != dims_PS(Pc) || h.PW != dims_PW(Pc) || h.FWS != dims_FWS(c.n_in, c.n_out) || h.IPY != dims_IPY(c.n_in) ||
+             plan.pk_nred != pack_nred(H)))
+            return fail(-3, "the handle's row lengths (P %d, PS %d, PW %d, FWS %d, IPY %d) are not the ones compiled into the fixed-width "
+                            "packed kernel of %d hidden units", h.P, h.PS, h.PW, h.FWS, h.IPY, H);
+    }
+    const seg_fn packm_fn = fixed(true) ? pack_fixed_function(h.shape, H, true) : segment_function(h.shape, SEG_PACKM);
     int G = 1;
     const size_t pkm = pack_multi_lds_floats(Nall, h.IPY, h.PS, H, h.FWS, pack_slots(plan.pk_nred)) * sizeof(float);
     if (fits && pkm <= LDS_MAX && c.use_langevin && !c.shared_device && (sched == PTNN_SCHED_PACKED || c.schedule == PTNN_SCHED_AUTO) &&
@@ -440,7 +479,7 @@ int plan_packed(const ptnn_handle& h, int Nall, int sched, LaunchPlan& plan) {
         // The runtime refuses a dynamic-LDS ceiling just below 160 KiB (6-16-18 with 65 rows: 159.9 KiB over several CUs, next to
         // the kernel's 256 B of static LDS): ask it.
         // A refused automatic choice goes on with one CU per replica, a refused request is an error.
-        if (G > 1 && !lds_accepted(segment_function(h.shape, SEG_PACKM), pkm)) {
+        if (G > 1 && !lds_accepted(packm_fn, pkm)) {
             if (want == 2 || want == 4)
                 return fail(-3, "the packed round over %d CUs needs %zu B of LDS, which the runtime does not grant one work-group", want, pkm);
             G = 1;
@@ -451,11 +490,13 @@ int plan_packed(const ptnn_handle& h, int Nall, int sched, LaunchPlan& plan) {
         !(c.schedule == PTNN_SCHED_AUTO && sched == PTNN_SCHED_SPECULATIVE && fits && pays && c.use_langevin && c.waves_per_replica == 0 &&
           (c.groups_per_replica == 0 || G > 1)))
         return 0;
-    if (G == 1 && !lds_accepted(segment_function(h.shape, SEG_PACK), pk)) {
+    const seg_fn pack_fn = fixed(false) ? pack_fixed_function(h.shape, H, false) : segment_function(h.shape, SEG_PACK);
+    if (G == 1 && !lds_accepted(pack_fn, pk)) {
         if (sched == PTNN_SCHED_PACKED) return fail(-3, "the packed schedule needs %zu B of LDS, which the runtime does not grant one work-group", pk);
         return 0;
     }
     plan.kind = G > 1 ? SEG_PACKM : SEG_PACK;
+    plan.pack_hc = fixed(G > 1) ? H : 0;
     plan.groups = G;
     // eight waves (forward passes two to a SIMD) while every replica has a CU to itself, four beyond that; an explicit
     // waves_per_replica of 4 or 8 decides otherwise
@@ -613,7 +654,7 @@ int plan_persistent(const ptnn_handle& h, LaunchPlan& plan) {
         if (swap_lds > LDS_CEILING) return 0;
         plan.seg_lds = swap_lds;
     }
-    const void* fn = reinterpret_cast<const void*>(segment_function(h.shape, plan.kind));
+    const void* fn = reinterpret_cast<const void*>(plan_function(h.shape, plan));
     if (int rc = raise_lds_limit(fn, plan.seg_lds)) return rc;
     int per_cu = 0;
     HIP_TRY(hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, fn, plan.threads, plan.seg_lds));
@@ -622,7 +663,7 @@ int plan_persistent(const ptnn_handle& h, LaunchPlan& plan) {
 }
 
 // The launch plan of a handle for a data set of Nall rows: a function of the config, the data shape and the device ($PTNN_PERSISTENT
-// aside).  Queries the runtime (occupancy, dynamic-LDS ceilings), never writes to the handle; 0 or the refusal.
+// and $PTNN_PACK_FIXED_H aside).  Queries the runtime (occupancy, dynamic-LDS ceilings), never writes to the handle; 0 or the refusal.
 int plan_launch(const ptnn_handle& h, int Nall, int Npad, LaunchPlan& plan) {
     const ptnn_config& c = h.cfg;
     plan = LaunchPlan{};
@@ -660,7 +701,7 @@ int plan_launch(const ptnn_handle& h, int Nall, int Npad, LaunchPlan& plan) {
         if (sched == PTNN_SCHED_TREE || auto_tree)
             if (int rc = plan_tree(h, Nall, Npad, sched == PTNN_SCHED_TREE, plan)) return rc;
     }
-    if (int rc = raise_lds_limit(reinterpret_cast<const void*>(segment_function(h.shape, plan.kind)), plan.seg_lds)) return rc;
+    if (int rc = raise_lds_limit(reinterpret_cast<const void*>(plan_function(h.shape, plan)), plan.seg_lds)) return rc;
     if (int rc = raise_lds_limit(reinterpret_cast<const void*>(plan.wide() ? h.shape->model_wide : h.shape->model), plan.model_lds)) return rc;
     return plan_persistent(h, plan);
 }
@@ -767,11 +808,11 @@ int create_buffers(ptnn_handle* h, const ptnn_config* cfg, const Shape* sh, cons
     h->num_cus = prop.multiProcessorCount;
     if (const char* ts = std::getenv("PTNN_TIMING_STRIDE")) h->timing_stride = std::atoi(ts);
     const int I = cfg->n_in, H = cfg->n_hidden, O = cfg->n_out;
-    h->P = I * H + H * O + H + O;
-    h->PS = round_up4(h->P + 1);
-    h->PW = (h->P + 15) & ~15;                             // pos_w trace rows: whole 64-byte sectors
-    h->IPY = round_up4(I + 2);                             // x[I], y, then 1 + x[n].x[n-1] for the pipelined SGD epoch
-    h->FWS = round_up4(I + 1 + O);
+    h->P = dims_P(I, H, O);
+    h->PS = dims_PS(h->P);                                 // ptnn_dims.hpp: the formulas a fixed-width kernel evaluates at compile time
+    h->PW = dims_PW(h->P);
+    h->IPY = dims_IPY(I);
+    h->FWS = dims_FWS(I, O);
     h->max_rounds = cfg->n_samples / cfg->swap_interval + 2;
     HIP_TRY(hipStreamCreateWithFlags(&h->stream, hipStreamNonBlocking));
     h->cap = (cfg->trace_capacity > 0 && cfg->trace_capacity < cfg->n_samples) ? cfg->trace_capacity : cfg->n_samples;
@@ -1788,8 +1829,10 @@ int ptnn_describe(ptnn_handle* h, char* buf, int nbytes) {
     if (!h || !buf || nbytes < 1) return fail(-1, "bad argument");
     if (!h->have_data) return fail(-1, "ptnn_set_data has not been called (the schedule depends on the data set)");
     const LaunchPlan& pl = h->plan;
-    const void* fn = reinterpret_cast<const void*>(segment_function(h->shape, pl.kind));
+    const void* fn = reinterpret_cast<const void*>(plan_function(h->shape, pl));
     HIP_TRY(hipSetDevice(h->cfg.device_id));
+    char width[16] = "";                                   // a compiled-in hidden width is the kernel's fourth template argument
+    if ((pl.kind == SEG_PACK || pl.kind == SEG_PACKM) && pl.pack_hc > 0) std::snprintf(width, sizeof width, ",%d", pl.pack_hc);
     int per_cu = 0;
     HIP_TRY(hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, fn, pl.threads, pl.seg_lds));
     hipFuncAttributes fa{};
@@ -1800,10 +1843,10 @@ int ptnn_describe(ptnn_handle* h, char* buf, int nbytes) {
                     : pl.wide() ? (pl.groups > 1 && h->cfg.use_langevin ? 8 : pl.groups)
                     : pack_slots(pl.pk_nred) * pl.groups;
     const int n = std::snprintf(buf, (size_t)nbytes,
-                                "{\"kernel\": \"ptnn::%s<%d,%d,%d>\", \"schedule\": \"%s\", \"grid_blocks\": %d, \"block_threads\": %d, "
+                                "{\"kernel\": \"ptnn::%s<%d,%d,%d%s>\", \"schedule\": \"%s\", \"grid_blocks\": %d, \"block_threads\": %d, "
                                 "\"lds_bytes\": %zu, \"groups_per_replica\": %d, \"slots_per_round\": %d, \"num_cus\": %d, "
                                 "\"blocks_per_cu\": %d, \"vgprs\": %d, \"scratch_bytes\": %zu, \"forward_mfma\": %d, \"exchange\": \"%s\", \"lds_resident_state\": %d, \"compact_traces\": %d, \"launches\": \"%s\"}",
-                                g_seg[pl.kind].name, h->cfg.task, h->cfg.n_in, h->cfg.n_out,
+                                g_seg[pl.kind].name, h->cfg.task, h->cfg.n_in, h->cfg.n_out, width,
                                 pl.wide() && pl.groups > 1 ? "speculative-wide" : g_seg[pl.kind].label,
                                 pl.grid(h->cfg.n_replicas_local), pl.threads, pl.seg_lds, pl.groups, slots, h->num_cus, per_cu, fa.numRegs, (size_t)fa.localSizeBytes,
                                 pl.fw_mfma ? pl.fw_mfma : ((pl.wide() && h->cfg.n_hidden % 32 == 0) ? 1 : 0),

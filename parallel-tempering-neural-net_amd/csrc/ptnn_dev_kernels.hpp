@@ -256,6 +256,16 @@ __global__ void __launch_bounds__(PK_WAVES * WAVE) segment_pack_kernel(const Seg
         else segment_pack_body<TASK, I, O, 3>(q, d, b, n);
     });
 }
+// The one-CU packed kernel with the hidden width HC compiled in (PackDims): an overload, so that the run-time-width kernel above keeps
+// its name and its code.  Instantiated for the entries of ptnn_shapes.hpp's PTNN_PACK_FIXED only; the lane-group size follows from HC,
+// so the branch on pk_nred is gone with the other one's copy of the body.
+template <int TASK, int I, int O, int HC>
+__global__ void __launch_bounds__(PK_WAVES * WAVE) segment_pack_kernel(const SegParams p, const PersistParams pp, const int step_begin) {
+    static_assert(HC > 0 && HC <= 16, "a packed net has at most 16 hidden units");
+    persistent_loop<pack_has_loop<TASK, I, O>()>(p, step_begin, [](const SegParams& q, const SegDyn& d, int b, int n) {
+        segment_pack_body<TASK, I, O, pack_nred(HC), false, HC>(q, d, b, n);
+    });
+}
 // the packed schedule over several CUs per replica (16-lane groups: 9 <= n_hidden <= 16): its own kernel, so that the one-CU kernel
 // (the benchmark's) keeps its registers and its code
 template <int TASK, int I, int O>
@@ -263,6 +273,14 @@ __global__ void __launch_bounds__(PK_WAVES * WAVE) segment_packm_kernel(const Se
     persistent_loop<false>(p, step_begin, [](const SegParams& q, const SegDyn& d, int b, int n) {
         if (q.pk_nred == 4) segment_pack_body<TASK, I, O, 4, true>(q, d, b, n);
         else segment_pack_body<TASK, I, O, 3, true>(q, d, b, n);
+    });
+}
+// ... and with the hidden width compiled in (PTNN_PACKM_FIXED), like segment_pack_kernel<TASK, I, O, HC>
+template <int TASK, int I, int O, int HC>
+__global__ void __launch_bounds__(PK_WAVES * WAVE) segment_packm_kernel(const SegParams p, const PersistParams pp, const int step_begin) {
+    static_assert(HC > 0 && HC <= 16, "a packed net has at most 16 hidden units");
+    persistent_loop<false>(p, step_begin, [](const SegParams& q, const SegDyn& d, int b, int n) {
+        segment_pack_body<TASK, I, O, pack_nred(HC), true, HC>(q, d, b, n);
     });
 }
 template <int TASK, int I, int O>

@@ -32,9 +32,29 @@ __host__ __device__ inline size_t pack_multi_lds_floats(int Nall, int IPY, int P
     return pack_lds_floats(Nall, IPY, PS, H, FWS, nslots) + pack_ring_floats(PS, (PK_MULTI_MAXG - 1) * nslots) + 2 * (size_t)PS + SL_COUNT + 8;
 }
 
-template <int TASK, int I, int O, int PK_NRED, bool MULTI = false>
+// The dimensions of the packed body as a policy: with HC == 0 the hidden width is a run-time value and every length comes from
+// SegParams (the host's ptnn_dims.hpp values); with HC > 0 the width is compiled in and the same formulas are evaluated at compile
+// time, so P, the strides and the lane-group size are literals in every loop bound, guard and address of the body and of what it
+// inlines.  The host launches such a kernel only for a handle whose values are these (plan_launch checks).
+template <int HC, int I, int O>
+struct PackDims {
+    static constexpr bool FIXED = HC > 0;
+    static constexpr int CP = dims_P(I, HC, O);
+    __device__ static __forceinline__ int H(const SegParams& p) { return FIXED ? HC : p.H; }
+    __device__ static __forceinline__ int P(const SegParams& p) { return FIXED ? CP : p.P; }
+    __device__ static __forceinline__ int PS(const SegParams& p) { return FIXED ? dims_PS(CP) : p.PS; }
+    __device__ static __forceinline__ int PW(const SegParams& p) { return FIXED ? dims_PW(CP) : p.PW; }
+    __device__ static __forceinline__ int FWS(const SegParams& p) { return FIXED ? dims_FWS(I, O) : p.FWS; }
+    __device__ static __forceinline__ int IPY(const SegParams& p) { return FIXED ? dims_IPY(I) : p.IPY; }
+};
+// lane-group exponent of a compiled-in width (the host's choice for a run-time one: plan_launch)
+__host__ __device__ constexpr int pack_nred(int H) { return H <= 8 ? 3 : 4; }
+
+template <int TASK, int I, int O, int PK_NRED, bool MULTI = false, int HC = 0>
 __device__ __forceinline__ void segment_pack_body(const SegParams& p, const SegDyn& dyn, const int step_begin, const int n_steps) {
     constexpr int PK_NG = WAVE >> PK_NRED, PK_SLOTS = pack_slots(PK_NRED);
+    using D = PackDims<HC, I, O>;
+    static_assert(HC == 0 || (HC <= (1 << PK_NRED) && pack_nred(HC) == PK_NRED), "a compiled-in width runs in its own lane-group size");
     extern __shared__ __attribute__((aligned(16))) float smem[];
     // MULTI: p.G work-groups (CUs) per replica, work-group grp owns slots [grp PK_SLOTS, (grp + 1) PK_SLOTS) of a window of KT steps;
     // all of them keep the chain state and apply the same commits (segment_spec_body's protocol: verdicts and the accepted step
@@ -47,9 +67,9 @@ __device__ __forceinline__ void segment_pack_body(const SegParams& p, const SegD
     const int tid = threadIdx.x, nthr = blockDim.x;
     const int wave = tid >> 6, lane = tid & 63;
     const int Nall = p.Ntr + p.Nte;
-    const int P = p.P, PS = p.PS, H = p.H;
+    const int P = D::P(p), PS = D::PS(p), H = D::H(p);     // (PW, FWS and IPY are read through D:: where they are used)
     float* q = smem;
-    float* xy = q; q += (Nall + 2) * p.IPY;
+    float* xy = q; q += (Nall + 2) * D::IPY(p);
     float* w_cur = q; q += PS;
     float* w_gd = q; q += PS;
     float* rec_w = q; q += PS;                              // last recorded pos_w row ...
@@ -65,8 +85,8 @@ __device__ __forceinline__ void segment_pack_body(const SegParams& p, const SegD
     constexpr int RING = (MULTI ? 2 * PK_MULTI_MAXG : 2) * PK_SLOTS;
     float* ring_n = q; q += (size_t)RING * PS;
     float* ring_s = q; q += (size_t)RING * 4;
-    float* my_fw = q + (size_t)wave * fw_floats(H, p.FWS);
-    q += (size_t)PK_WAVES * fw_floats(H, p.FWS);
+    float* my_fw = q + (size_t)wave * fw_floats(H, D::FWS(p));
+    q += (size_t)PK_WAVES * fw_floats(H, D::FWS(p));
     float* win_v = q; q += MULTI ? 2 * (size_t)PS : 0;      // MULTI: the accepted step of another work-group {proposal, its SGD epoch}
     float* win_s = q; q += MULTI ? SL_COUNT : 0;            //        its slot scalars
     float* gverd = q;                                       //        the groups' verdicts of this round (first accepted local slot, or -1)
@@ -82,7 +102,7 @@ __device__ __forceinline__ void segment_pack_body(const SegParams& p, const SegD
     {
         const float4* src = reinterpret_cast<const float4*>(p.data);
         float4* dst = reinterpret_cast<float4*>(xy);
-        for (int e = tid; e < ((Nall + 2) * p.IPY) >> 2; e += nthr) dst[e] = src[e];
+        for (int e = tid; e < ((Nall + 2) * D::IPY(p)) >> 2; e += nthr) dst[e] = src[e];
     }
     float* gw = dyn.w_state + (size_t)r * PS;
     for (int j = tid; j < PS; j += nthr) {
@@ -129,7 +149,7 @@ __device__ __forceinline__ void segment_pack_body(const SegParams& p, const SegD
     const int ev_i = !sweeping ? wave : ((wave & 3) >= 2 ? (wave & 1) + ((wave >> 2) << 1) : -1);   // my index among them, or -1
     int i = step_begin;
     int tpos0 = (step_begin + 1) % p.trace_cap;            // ring position of the trace row of step i
-    const float inv_PW = 1.0f / (float)p.PW;
+    const float inv_PW = 1.0f / (float)D::PW(p);            // trace row of an item of the pos_w store: item / PW by a multiply, or by a literal divisor
     // tape of steps [lo, hi) into the ring, by the waves [w0, w0 + nw): one Philox counter quad per lane, a wave covers
     // 64 / (quads per step) steps in one pass
     const int nq1 = ((P + 3) >> 2) + 1;                     // noise quads + the scalar quad
@@ -189,9 +209,9 @@ __device__ __forceinline__ void segment_pack_body(const SegParams& p, const SegD
         if (MULTI) { epoch += 1; }
         if (i == p.switch_step) {
             if (wave == 0) {
-                build_fw<I, O, true>(w_cur, my_fw, H, p.FWS);
+                build_fw<I, O, true>(w_cur, my_fw, H, D::FWS(p));
                 gsync<true>();
-                const EvalSums sc = eval_rows<TASK, I, O, true>(my_fw, xy, p.IPY, p.FWS, H, p.Ntr, Nall, nullptr);
+                const EvalSums sc = eval_rows<TASK, I, O, true>(my_fw, xy, D::IPY(p), D::FWS(p), H, p.Ntr, Nall, nullptr);
                 float l2, r1, r2, a1, a2;
                 finish_eval<TASK>(sc, p.Ntr, p.Nte, tau_eta_last, l2, r1, r2, a1, a2);
                 if (lane == 0) red[0] = l2;
@@ -248,9 +268,9 @@ __device__ __forceinline__ void segment_pack_body(const SegParams& p, const SegD
                     for (int e = lane; e < P; e += WAVE) pr[e] = fmaf(p.step_w, nz[e], base[e]);
                 }
                 gsync<true>();
-                build_fw<I, O, true>(s_prop(s_), my_fw, H, p.FWS);
+                build_fw<I, O, true>(s_prop(s_), my_fw, H, D::FWS(p));
                 gsync<true>();
-                const EvalSums es = eval_rows<TASK, I, O, true>(my_fw, xy, p.IPY, p.FWS, H, p.Ntr, Nall, nullptr);
+                const EvalSums es = eval_rows<TASK, I, O, true>(my_fw, xy, D::IPY(p), D::FWS(p), H, p.Ntr, Nall, nullptr);
                 float ll, rm_tr, rm_te, ac_tr, ac_te;
                 finish_eval<TASK, true>(es, p.Ntr, p.Nte, eta_pro, ll, rm_tr, rm_te, ac_tr, ac_te);
                 const float ssq = block_sumsq<true>(s_prop(s_), P, nullptr);
@@ -368,11 +388,11 @@ __device__ __forceinline__ void segment_pack_body(const SegParams& p, const SegD
         const int tr_t = (MULTI || !split) ? tid : (ev_i >= 0 ? ev_i * WAVE + lane : -1);
         auto pos_w_rows = [&](const float* row_acc, const float* row_rej) {
             if constexpr (!MULTI) {                         // (discarded there, it captures nothing)
-                for (int item = tr_t; item < nloc * p.PW; item += tr_n) {
-                    const int s_ = (int)(((float)item + 0.5f) * inv_PW), e = item - s_ * p.PW;
+                for (int item = tr_t; item < nloc * D::PW(p); item += tr_n) {
+                    const int s_ = D::FIXED ? (int)((unsigned)item / (unsigned)D::PW(p)) : (int)(((float)item + 0.5f) * inv_PW), e = item - s_ * D::PW(p);
                     int tp = tpos0 + s0 + s_;
                     if (tp >= p.trace_cap) tp -= p.trace_cap;
-                    p.tr_pos_w[(trow + (size_t)tp) * (size_t)p.PW + e] = (e < P) ? ((s0 + s_ == m) ? row_acc : row_rej)[e] : 0.0f;
+                    p.tr_pos_w[(trow + (size_t)tp) * (size_t)D::PW(p) + e] = (e < P) ? ((s0 + s_ == m) ? row_acc : row_rej)[e] : 0.0f;
                 }
             }
         };
@@ -389,11 +409,11 @@ __device__ __forceinline__ void segment_pack_body(const SegParams& p, const SegD
             }
         };
         if constexpr (MULTI) {
-            for (int item = tid; item < nloc * p.PW; item += nthr) {
-                const int s_ = (int)(((float)item + 0.5f) * inv_PW), e = item - s_ * p.PW;
+            for (int item = tid; item < nloc * D::PW(p); item += nthr) {
+                const int s_ = D::FIXED ? (int)((unsigned)item / (unsigned)D::PW(p)) : (int)(((float)item + 0.5f) * inv_PW), e = item - s_ * D::PW(p);
                 int tp = tpos0 + s0 + s_;
                 if (tp >= p.trace_cap) tp -= p.trace_cap;
-                p.tr_pos_w[(trow + (size_t)tp) * (size_t)p.PW + e] = (e < P) ? ((s0 + s_ == m) ? s_prop(s_) : rec_w)[e] : 0.0f;
+                p.tr_pos_w[(trow + (size_t)tp) * (size_t)D::PW(p) + e] = (e < P) ? ((s0 + s_ == m) ? s_prop(s_) : rec_w)[e] : 0.0f;
             }
             if (tid < nloc) {
                 const int s_ = tid;

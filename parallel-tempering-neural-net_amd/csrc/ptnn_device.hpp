@@ -22,6 +22,7 @@
 #include <type_traits>
 #include <hip/hip_runtime.h>
 #include <stdint.h>
+#include "ptnn_dims.hpp"
 
 // No implicit fused multiply-adds anywhere in the device code: whether `a * b + c` becomes one v_fma or a multiply and an add
 // would otherwise be decided per inlined copy by what surrounds it, and the same function could round differently in two kernels

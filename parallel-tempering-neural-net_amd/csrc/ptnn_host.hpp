@@ -4,6 +4,7 @@
 // and SegParams are only named), so the text side can use it without the kernels.
 #pragma once
 #include "ptnn_comm.hpp"
+#include "ptnn_dims.hpp"
 #include "../../include/ptnn.h"
 
 #include <cstdint>
@@ -31,8 +32,6 @@ int fail(int code, const char* fmt, ...);   // sets g_err, returns code
         }                                                                                                  \
     } while (0)
 
-inline int round_up4(int v) { return (v + 3) & ~3; }
-
 constexpr size_t LDS_MAX = 160 * 1024;          // LDS of one work-group
 constexpr size_t LDS_CEILING = 152 * 1024;      // largest dynamic-LDS ceiling the runtime accepts (just below LDS_MAX it refuses)
 
@@ -45,6 +44,7 @@ struct LaunchPlan {
     size_t seg_lds = 0, model_lds = 0;
     int groups = 1;                 // work-groups (CUs) per replica; tree: 2^depth - 1
     int pk_nred = 3;                // packed schedules: lane-group width 2^3 (H <= 8) or 2^4 hidden units
+    int pack_hc = 0;                // packed schedules: the hidden width compiled into the kernel taken (0: the run-time-width kernel)
     int fw_mfma = 0;                // forward pass on the matrix cores: 1 exact fp32, 2 split bf16 operands
     bool xy_global = false;         // split forward pass: no room for the row-major data image in LDS, its rare readers go to global memory
     bool tree_ahead = false;        // tree: room in LDS for two sets of tapes

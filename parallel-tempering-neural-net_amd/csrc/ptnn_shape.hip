@@ -8,6 +8,16 @@
 
 using namespace ptnn;
 
+#ifdef PTNN_HC
+// ... or, with -DPTNN_HC=<n_hidden> on top (and its own PTNN_SHAPE_SYMBOL, ptnn_pack_fixed_<T>_<I>_<O>_<H>), nothing but the shape's
+// packed kernel with that hidden width compiled in
+// (-DPTNN_HC_MULTI, ptnn_packm_fixed_<T>_<I>_<O>_<H>: the kernel over several CUs)
+#ifdef PTNN_HC_MULTI
+extern "C" const PackFixed PTNN_SHAPE_SYMBOL = {PTNN_T, PTNN_I, PTNN_O, PTNN_HC, &segment_packm_kernel<PTNN_T, PTNN_I, PTNN_O, PTNN_HC>};
+#else
+extern "C" const PackFixed PTNN_SHAPE_SYMBOL = {PTNN_T, PTNN_I, PTNN_O, PTNN_HC, &segment_pack_kernel<PTNN_T, PTNN_I, PTNN_O, PTNN_HC>};
+#endif
+#else
 extern "C" const Shape PTNN_SHAPE_SYMBOL = {PTNN_T, PTNN_I, PTNN_O,
                                             &segment_kernel<PTNN_T, PTNN_I, PTNN_O>, &segment_spec_kernel<PTNN_T, PTNN_I, PTNN_O>,
                                             &model_kernel<PTNN_T, PTNN_I, PTNN_O>, &segment_wide_kernel<PTNN_T, PTNN_I, PTNN_O>,
@@ -20,3 +30,4 @@ extern "C" const Shape PTNN_SHAPE_SYMBOL = {PTNN_T, PTNN_I, PTNN_O,
                                             &forecast_forward_kernel<PTNN_T, PTNN_I, PTNN_O>,
                                             &sensitivity_forward_kernel<PTNN_T, PTNN_I, PTNN_O>,
                                             &pd_forward_kernel<PTNN_T, PTNN_I, PTNN_O>};
+#endif
