@@ -1040,6 +1040,67 @@ typedef struct ptnn_prior_spec {
 
 int ptnn_prior_predictive(ptnn_handle *h, const ptnn_prior_spec *spec);
 
+/* ---- classification report (nothing in the reference: it reports acc_train / acc_test, one number per sample) ----
+ * How well a classifier separates its classes, per sampled net and for the pooled classifier: confusion counts, per-class
+ * precision / recall / F1 and one-vs-rest ROC-AUC.  Classification handles only; DESIGN.md section 26.
+ * Rows n = 0 .. N-1 with labels y_n in [0, K), K = n_out.  Samples: the expanded multiset of S selected rows, U distinct vectors
+ * with integer counts c_u, selected, merged and refused exactly as ptnn_predict's sources 1 and 2.  p_u[n, k] = the fp32
+ * probability ptnn_predict's forward pass returns; pred_u[n] = argmax_k p_u[n, k], first index on a tie (the rule of vote).
+ * Per distinct sample, exact integers: conf_u[i, j] = #{n: y_n = i, pred_u[n] = j} (int32), n_k = #{y_n = k}, col_u[k] = sum_i
+ * conf_u[i, k], and auc2_u[k] = sum_{n: y_n = k} sum_{m: y_m != k} (2 [p_u[n, k] > p_u[m, k]] + [p_u[n, k] == p_u[m, k]]) (int64,
+ * compared as fp32 values): twice the Mann-Whitney U statistic with ties counted half.
+ * Per distinct sample Q metric columns, each from those integers by one division in double (a mean: the sum of the quotients in
+ * class order divided by their count), stored as fp32, in this order: accuracy = tr(conf) / N; balanced_accuracy = the mean of
+ * recall over the classes with n_k > 0; macro_f1 = the mean of f1 over those classes; macro_auc = the mean of auc over the
+ * classes with 0 < n_k < N; precision[k] = conf[k, k] / col[k] (0 when col[k] = 0); recall[k] = conf[k, k] / n_k; f1[k] =
+ * 2 conf[k, k] / (n_k + col[k]); auc[k] = auc2[k] / (2 n_k (N - n_k)).  Q = 4 + 4 K, or 3 + 3 K with auc == 0 (no macro_auc, no
+ * auc[k]).  A column the data leave undefined -- recall and f1 of a class with n_k = 0, auc with n_k in {0, N}, a macro column
+ * with no class left -- is written as 0 (the caller knows them from the labels).
+ * Over the samples, as ptnn_predict reduces a column: metric_mean [Q] (weighted, accumulated in double), metric_order_stats
+ * [n_ranks, Q] (exact fp32 order statistics of the expanded multiset; n_ranks <= 16, 0 <= rank < S), confusion_sum [K, K] int64
+ * = sum_u c_u conf_u, sample_metrics [S, Q] fp32 and sample_confusion [S, K, K] int32, chain-major.  The pooled classifier:
+ * p_mean and vote [N, K] are bitwise ptnn_predict's mean and vote for the same selection; p_correct [N] = vote[n, y_n].
+ * Data as ptnn_elpd: x_source _TRAIN / _TEST or _HOST with x [n_rows, n_in + 1] (last column the label).  Outputs, any may be
+ * NULL.  Refused: a regression handle; a label that is not an integer in [0, K) (the first such row is named); n_ranks > 16 or a
+ * rank outside [0, S); auc != 0 with more than PTNN_REPORT_MAX_AUC_ROWS rows (a sample's scores of one class are ranked in one
+ * work-group's LDS; auc == 0 has no cap); more than 65535 x 64 rows.
+ * Runs on the handle's stream behind everything queued and returns when done.  The forward image [N K][U] is computed at once
+ * where it fits $PTNN_REPORT_SCRATCH_BYTES (read per call, default 1 GiB); else p_mean / vote come from ptnn_predict's blocks of
+ * rows and everything per sample from blocks of samples, which changes no result.  Touches no chain state, tape, counter or
+ * trace row.  Not with a communicator attached (one GPU only). */
+#define PTNN_REPORT_MAX_AUC_ROWS 16384
+
+typedef struct ptnn_class_report_spec {
+    int32_t struct_bytes;         /* = sizeof(ptnn_class_report_spec): ABI guard */
+    /* source 1: the trace (used when w == NULL) */
+    const int32_t *replicas;      /* local replica indices, or NULL = all */
+    int32_t n_replicas;           /* entries of replicas (ignored when NULL) */
+    int32_t step0, nsteps, thin;  /* trace rows step0, step0 + thin, ... < step0 + nsteps (thin >= 1) */
+    /* source 2: host vectors */
+    const float *w;               /* [n_w, P] or NULL */
+    const int32_t *multiplicity;  /* [n_w] >= 0, or NULL = 1 each */
+    int64_t n_w;
+    /* data */
+    int32_t x_source;             /* PTNN_PREDICT_X_HOST | _TRAIN | _TEST */
+    int32_t n_rows;
+    const float *x;               /* [n_rows, n_in + 1] (host rows only) */
+    /* order statistics of the metric columns */
+    const int64_t *ranks;         /* [n_ranks] */
+    int32_t n_ranks;
+    int32_t auc;                  /* 0 / 1: the auc columns */
+    /* outputs */
+    double *p_mean, *vote;        /* [n_rows, n_out] */
+    double *p_correct;            /* [n_rows] */
+    double *metric_mean;          /* [Q] */
+    float *metric_order_stats;    /* [n_ranks, Q] */
+    int64_t *confusion_sum;       /* [n_out, n_out] */
+    float *sample_metrics;        /* [S, Q] */
+    int32_t *sample_confusion;    /* [S, n_out, n_out] */
+    int64_t *n_samples, *n_distinct;
+} ptnn_class_report_spec;
+
+int ptnn_class_report(ptnn_handle *h, const ptnn_class_report_spec *spec);
+
 /* the HIP stream (hipStream_t) all of this handle's work is queued on: lets the caller order its collectives after the
  * segment / before the swap kernels on the device instead of synchronising the host */
 int ptnn_stream(ptnn_handle *h, void **hip_stream);

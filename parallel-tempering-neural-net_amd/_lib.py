@@ -241,6 +241,22 @@ PRIOR_MAX_SCALES = 8
 PRIOR_REG_STATS, PRIOR_CLS_FIXED = 7, 4       # statistics of a drawn function: a regression's; a classification's before class_share
 
 
+class ClassReportSpec(C.Structure):
+    """ptnn_class_report_spec (include/ptnn.h)."""
+    _fields_ = _SELECTION + [
+        ("w", C.POINTER(C.c_float)), ("multiplicity", C.POINTER(C.c_int32)), ("n_w", C.c_int64),
+        ("x_source", C.c_int32), ("n_rows", C.c_int32), ("x", C.POINTER(C.c_float)),
+        ("ranks", C.POINTER(C.c_int64)), ("n_ranks", C.c_int32), ("auc", C.c_int32),
+        ("p_mean", C.POINTER(C.c_double)), ("vote", C.POINTER(C.c_double)), ("p_correct", C.POINTER(C.c_double)),
+        ("metric_mean", C.POINTER(C.c_double)), ("metric_order_stats", C.POINTER(C.c_float)), ("confusion_sum", C.POINTER(C.c_int64)),
+        ("sample_metrics", C.POINTER(C.c_float)), ("sample_confusion", C.POINTER(C.c_int32)),
+        ("n_samples", C.POINTER(C.c_int64)), ("n_distinct", C.POINTER(C.c_int64)),
+    ]
+
+
+REPORT_MAX_AUC_ROWS = 16384
+
+
 class LadderAdaptSpec(C.Structure):
     """ptnn_ladder_adapt_spec (include/ptnn.h)."""
     _fields_ = [("struct_bytes", C.c_int32), ("rounds", C.c_int32), ("kappa0", C.c_double), ("t0", C.c_double)]
@@ -339,6 +355,7 @@ SYMBOLS = {
     "ptnn_ppc": (C.c_int, [C.c_void_p, C.POINTER(PpcSpec)]),
     "ptnn_powerscale": (C.c_int, [C.c_void_p, C.POINTER(PowerscaleSpec)]),
     "ptnn_prior_predictive": (C.c_int, [C.c_void_p, C.POINTER(PriorSpec)]),
+    "ptnn_class_report": (C.c_int, [C.c_void_p, C.POINTER(ClassReportSpec)]),
 }
 
 
@@ -970,6 +987,30 @@ class Sampler:
             out.update(p_mean=np.empty((n_rows, self.cfg.n_out)))
         _bind(spec, out)
         return self._call(self.lib.ptnn_calibration, spec, out)
+
+    def class_report(self, data="test", *, replicas=None, step0=0, nsteps=None, thin=1, w=None, multiplicity=None, ranks=(), auc=True,
+                     sample_confusion=False):
+        """ptnn_class_report: confusion counts, per-class precision / recall / F1 and one-vs-rest ROC-AUC of every selected sample
+        and of the pooled classifier, on the device (classification only).  Source: the trace rows step0, step0 + thin, ... <
+        step0 + nsteps of `replicas` (None = all), or host vectors w [n, P] with optional integer `multiplicity` [n].  data:
+        "train", "test" or rows [n_rows, n_in + 1] (last column the label).  With K = n_out and Q = 4 + 4 K metric columns (3 + 3 K
+        with auc=False; their order: include/ptnn.h) -> dict(p_mean, vote [n_rows, K] float64, p_correct [n_rows] float64,
+        metric_mean [Q] float64, metric_order_stats [len(ranks), Q] float32 (exact values of those 0-based ranks), confusion_sum
+        [K, K] int64, sample_metrics [S, Q] float32, sample_confusion [S, K, K] int32 or None, n_samples, n_distinct)."""
+        spec, keep = _spec(ClassReportSpec), []
+        self._rows(spec, keep, data, "data", (self.cfg.n_in + 1, "n_in inputs and the label"))
+        n_rows, K = spec.n_rows, self.cfg.n_out
+        S = self._samples(spec, keep, w=w, multiplicity=multiplicity, replicas=replicas, step0=step0, nsteps=nsteps, thin=thin,
+                          unit="vector")
+        n_rk = _ranks(spec, keep, ranks)
+        spec.auc = 1 if auc else 0
+        Q = (4 + 4 * K) if auc else (3 + 3 * K)
+        out = dict(p_mean=np.empty((n_rows, K), np.float64), vote=np.empty((n_rows, K), np.float64), p_correct=np.empty(n_rows, np.float64),
+                   metric_mean=np.empty(Q, np.float64), metric_order_stats=np.empty((n_rk, Q), np.float32) if n_rk else None,
+                   confusion_sum=np.empty((K, K), np.int64), sample_metrics=np.empty((max(S, 0), Q), np.float32),
+                   sample_confusion=np.empty((max(S, 0), K, K), np.int32) if sample_confusion else None)
+        _bind(spec, out)
+        return self._call(self.lib.ptnn_class_report, spec, out)
 
     def sensitivity(self, x="test", *, replicas=None, step0=0, nsteps=None, thin=1, w=None, multiplicity=None, ranks=(), ranks2=(),
                     sample_abs=False, samples=False):

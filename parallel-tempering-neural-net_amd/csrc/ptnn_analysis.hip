@@ -17,6 +17,7 @@ namespace ptnn {
 #include "ptnn_dev_sensitivity.hpp"          // input sensitivity, second part: sign counts, row sums and their weighted means
 #define PTNN_PD_REDUCTIONS
 #include "ptnn_dev_pd.hpp"                   // partial dependence, second part: row sums, ranges and the weighted means of the row means
+#include "ptnn_dev_report.hpp"               // classification report: confusion counts, Mann-Whitney counts and metric columns per sample
 }  // namespace ptnn
 #include "ptnn_host.hpp"
 #include "ptnn_rank_plan.hpp"               // the blocks of ptnn_rank_convergence: host arithmetic, checked on its own
@@ -317,6 +318,15 @@ int fit_rows(const ptnn_handle* h, const RowSource& r) {
     if (r.source == PTNN_PREDICT_X_TEST && r.n != h->Nte) return fail(-1, "%s = %d but the test set has %d rows", r.count, r.n, h->Nte);
     return 0;
 }
+// host rows x [n][I + 1] of a classification: the last column is a class, as ptnn_set_data checks the handle's own rows
+int check_labels(const float* x, int n_rows, int I, int O) {
+    for (int n = 0; n < n_rows; ++n) {
+        const float yv = x[(size_t)n * (I + 1) + I];
+        if (!(yv >= 0.0f) || yv >= (float)O || yv != std::floor(yv))
+            return fail(-1, "class label %g in row %d is not an integer in [0, %d)", (double)yv, n, O);
+    }
+    return 0;
+}
 // the rows on the device: the host rows (`width` floats each) uploaded, or the data set; row k at *x + k * *xs
 int upload_rows(ptnn_handle* h, DeviceScratch& mem, const RowSource& r, int width, const float** x, int* xs) {
     if (r.source == PTNN_PREDICT_X_HOST) {
@@ -467,12 +477,7 @@ template <class Spec> int pointwise_fit(const ptnn_handle* h, const Spec& s, con
     if (int rc = need_eta(h, src)) return rc;
     if (s.loglik) return 0;
     if (int rc = fit_rows(h, rows)) return rc;
-    if (s.x_source == PTNN_PREDICT_X_HOST && h->cfg.task != PTNN_TASK_REG)
-        for (int n = 0; n < s.n_rows; ++n) {
-            const float yv = s.x[(size_t)n * (I + 1) + I];
-            if (!(yv >= 0.0f) || yv >= (float)O || yv != std::floor(yv))
-                return fail(-1, "class label %g in row %d is not an integer in [0, %d)", (double)yv, n, O);
-        }
+    if (s.x_source == PTNN_PREDICT_X_HOST && h->cfg.task != PTNN_TASK_REG) return check_labels(s.x, s.n_rows, I, O);
     return 0;
 }
 // the host loglik on the device: every host sample is its own entry of `ra` (repeats need no merging: the reductions depend on the
@@ -2263,6 +2268,142 @@ int ptnn_prior_predictive(ptnn_handle* h, const ptnn_prior_spec* spec) {
         if (s.vote)
             for (int c = 0; c < ncols; ++c) s.vote[kc + c] = (double)votes_h[(size_t)c] / (double)ND;
     }
+    return 0;
+}
+
+// ---- classification report (ptnn_dev_report.hpp) ----
+static_assert(PTNN_REPORT_MAX_AUC_ROWS == REPORT_MAX_AUC_ROWS, "ptnn.h report limits");
+
+int ptnn_class_report(ptnn_handle* h, const ptnn_class_report_spec* spec) {
+    // argument checks first: none of them needs the handle or a device
+    if (int rc = check_spec(spec, "ptnn_class_report_spec")) return rc;
+    const ptnn_class_report_spec& s = *spec;
+    SampleSource src = source_of(s, s.w != nullptr, nullptr);
+    const RowSource rows{s.x_source, s.x, s.n_rows, "x_source", "PTNN_PREDICT_X", "x", "n_rows"};
+    RankOutputs rk{s.n_ranks, s.ranks, s.metric_order_stats};
+    if (int rc = check_source(src, "vectors")) return rc;
+    if (int rc = check_rows(rows)) return rc;
+    if (s.n_rows < 1) return fail(-1, "n_rows = %d must be >= 1", s.n_rows);
+    if (s.n_rows > 65535 * WAVE) return fail(-1, "n_rows = %d: at most 65535 x 64 rows per call", s.n_rows);
+    if (int rc = rk.check()) return rc;
+    if (s.auc && s.n_rows > REPORT_MAX_AUC_ROWS)
+        return fail(-1, "auc: %d rows, at most %d (the scores of one sample and class are ranked in LDS); auc = 0 (auc=False) has no cap",
+                    s.n_rows, REPORT_MAX_AUC_ROWS);
+    if (int rc = check_handle(h, "ptnn_class_report")) return rc;
+    const int I = h->cfg.n_in, K = h->cfg.n_out, KK = K * K, N = s.n_rows;
+    if (h->cfg.task != PTNN_TASK_CLS) return fail(-1, "ptnn_class_report: a regression has no classes");
+    if (int rc = fit_rows(h, rows)) return rc;
+    if (s.x_source == PTNN_PREDICT_X_HOST)
+        if (int rc = check_labels(s.x, N, I, K)) return rc;
+    if (int rc = select_samples(h, src, false)) return rc;
+    const long long M = src.M;
+    if (int rc = rk.check_values(M)) return rc;
+    if (s.n_samples) *s.n_samples = M;
+
+    if (int rc = start_device(h)) return rc;
+    hipStream_t st = h->stream;
+    DeviceScratch mem;
+    const int ncols = N * K, Q = s.auc ? 4 + 4 * K : 3 + 3 * K;
+    const float* d_x = nullptr;
+    int xs = 0;
+    if (int rc = upload_rows(h, mem, rows, I + 1, &d_x, &xs)) return rc;
+    Distinct d;
+    if (int rc = distinct_samples(h, mem, src, false, true, &d)) return rc;
+    const int U = d.U;
+    if (s.n_distinct) *s.n_distinct = U;
+    // the class of every row as an integer: the kernels' index, and on the host p_correct's
+    int* d_label = nullptr;
+    HIP_TRY(mem.alloc(&d_label, (size_t)N));
+    HIP_TRY(launch(report_labels_kernel, dim3((unsigned)((N + REPORT_THREADS - 1) / REPORT_THREADS)), dim3(REPORT_THREADS), 0, st, d_x + I, xs, N, K,
+                   d_label));
+    std::vector<int> label_h((size_t)N);
+    HIP_TRY(hipMemcpyAsync(label_h.data(), d_label, (size_t)N * sizeof(int), hipMemcpyDeviceToHost, st));
+    // per column of the pooled classifier, per sample, per metric
+    double *d_mean = nullptr, *d_mmean = nullptr;
+    long long *d_votes = nullptr, *d_auc2 = nullptr, *d_csum = nullptr;
+    int* d_conf = nullptr;
+    float* d_img = nullptr;
+    HIP_TRY(mem.alloc(&d_mean, (size_t)ncols));
+    HIP_TRY(mem.alloc(&d_votes, (size_t)ncols));
+    HIP_TRY(mem.alloc(&d_conf, (size_t)KK * U));
+    HIP_TRY(hipMemsetAsync(d_conf, 0, (size_t)KK * U * sizeof(int), st));
+    if (s.auc) HIP_TRY(mem.alloc(&d_auc2, (size_t)K * U));
+    HIP_TRY(mem.alloc(&d_img, (size_t)Q * U));
+    HIP_TRY(mem.alloc(&d_mmean, (size_t)Q));
+    HIP_TRY(mem.alloc(&d_csum, (size_t)KK));
+    if (int rc = rk.to_device(mem, (size_t)Q, st)) return rc;
+    // The forward image: all rows of all samples where that fits the budget; else the pooled classifier from ptnn_predict's blocks
+    // of rows, then everything per sample from blocks of samples (a sample's AUC needs all its rows at once)
+    const size_t budget = scratch_budget("PTNN_REPORT_SCRATCH_BYTES");
+    const size_t row_bytes = (size_t)U * sizeof(float) * K, sample_bytes = (size_t)N * sizeof(float) * K;
+    const bool one_pass = row_bytes * N <= budget;
+    const long long rows_blk = one_pass ? N : row_block(budget, row_bytes, N);
+    const long long u_blk = one_pass ? U : std::max<long long>(1, std::min<long long>(U, (long long)(budget / sample_bytes)));
+    float* d_fx = nullptr;
+    HIP_TRY(mem.alloc(&d_fx, std::max((size_t)rows_blk * K * U, (size_t)u_blk * N * K)));
+    ForwardPlan fwd;
+    if (int rc = fwd.init(h, "classification report")) return rc;
+    int TU = WAVE;
+    while (TU > 1 && (size_t)KK * TU * sizeof(int) > (size_t)REPORT_CONF_LDS) TU >>= 1;
+    const size_t conf_lds = (size_t)KK * TU * sizeof(int);
+    if (conf_lds > LDS_CEILING) return fail(-3, "classification report: the counts of %d classes do not fit in LDS", K);
+    if (int rc = raise_lds_limit(reinterpret_cast<const void*>(report_confusion_kernel), conf_lds)) return rc;
+    const int rows_per_group = std::max(WAVE, (N + 7) / 8);
+    int npow = 1;
+    while (npow < N) npow <<= 1;
+    const bool small = npow <= REPORT_SORT_SMALL;
+    const size_t auc_lds = ((size_t)npow + (small ? REPORT_THREADS : REPORT_SORT_THREADS)) * sizeof(unsigned long long);
+    if (s.auc && !small)
+        if (int rc = raise_lds_limit(reinterpret_cast<const void*>(report_auc_kernel<REPORT_SORT_THREADS>), auc_lds)) return rc;
+    // the integers of samples [u0, u0 + nb), whose outputs on all rows are d_fx [ncols][nb]
+    const auto count_block = [&](long long u0, int nb) -> int {
+        ReportConf ca{d_fx, d_label, N, K, nb, TU, rows_per_group, U, (int)u0, d_conf};
+        HIP_TRY(launch(report_confusion_kernel, dim3((unsigned)((nb + TU - 1) / TU), (unsigned)((N + rows_per_group - 1) / rows_per_group)),
+                       dim3(REPORT_THREADS), conf_lds, st, ca));
+        if (!s.auc) return 0;
+        ReportAuc aa{d_fx, d_label, N, K, nb, npow, U, (int)u0, d_auc2};
+        if (small) HIP_TRY(launch(report_auc_kernel<REPORT_THREADS>, dim3((unsigned)nb, (unsigned)K), dim3(REPORT_THREADS), auc_lds, st, aa));
+        else HIP_TRY(launch(report_auc_kernel<REPORT_SORT_THREADS>, dim3((unsigned)nb, (unsigned)K), dim3(REPORT_SORT_THREADS), auc_lds, st, aa));
+        return 0;
+    };
+    if (int rc = each_block(N, rows_blk, [&](long long r0, int nr) -> int {
+        if (int rc = fwd.run(h, d.base, d.run_off, d_x, xs, (int)r0, nr, U, d_fx)) return rc;
+        PredictRed ra{d_fx, d.run_cnt, U, K, (int)r0 * K, ncols, M, 0, nullptr, d_mean, nullptr, d_votes};
+        HIP_TRY(launch(predict_reduce_kernel, dim3((unsigned)(nr * K)), dim3(PRED_THREADS), 0, st, ra));
+        return one_pass ? count_block(0, U) : 0;
+    })) return rc;
+    if (!one_pass)
+        if (int rc = each_block(U, u_blk, [&](long long u0, int nb) -> int {
+            if (int rc = fwd.run(h, d.base, d.run_off + u0, d_x, xs, 0, N, nb, d_fx)) return rc;
+            return count_block(u0, nb);
+        })) return rc;
+    // the metric columns of every sample, reduced over the samples as ptnn_predict reduces a column of outputs
+    ReportMetrics ma{d_conf, d_auc2, U, K, N, d_img};
+    HIP_TRY(launch(report_metrics_kernel, dim3((unsigned)((U + REPORT_THREADS - 1) / REPORT_THREADS)), dim3(REPORT_THREADS), 0, st, ma));
+    PredictRed qa{d_img, d.run_cnt, U, 1, 0, Q, M, s.n_ranks, rk.d_ranks, d_mmean, rk.d_stats, nullptr};
+    HIP_TRY(launch(predict_reduce_kernel, dim3((unsigned)Q), dim3(PRED_THREADS), 0, st, qa));
+    HIP_TRY(launch(report_confusion_sum_kernel, dim3((unsigned)KK), dim3(REPORT_THREADS), 0, st, d_conf, d.run_cnt, U, d_csum));
+    const bool votes = s.vote || s.p_correct;
+    std::vector<long long> votes_h(votes ? (size_t)ncols : 0);
+    HIP_TRY(fetch(s.p_mean, d_mean, (size_t)ncols, st));
+    HIP_TRY(fetch(votes ? votes_h.data() : nullptr, d_votes, (size_t)ncols, st));
+    HIP_TRY(fetch(s.metric_mean, d_mmean, (size_t)Q, st));
+    HIP_TRY(fetch(s.metric_order_stats, rk.d_stats, (size_t)s.n_ranks * Q, st));
+    HIP_TRY(fetch((long long*)s.confusion_sum, d_csum, (size_t)KK, st));
+    if (s.sample_metrics || s.sample_confusion) {
+        std::vector<int> item_run;
+        if (int rc = item_runs(h, d, src.n_items, &item_run)) return rc;
+        if (int rc = wait_stream(h)) return rc;
+        if (s.sample_metrics)
+            if (int rc = scatter_samples(h, d_img, Q, U, item_run, src.weights(), s.sample_metrics, (size_t)Q, 0)) return rc;
+        if (s.sample_confusion)
+            if (int rc = scatter_samples(h, d_conf, KK, U, item_run, src.weights(), s.sample_confusion, (size_t)KK, 0)) return rc;
+    }
+    if (int rc = wait_stream(h)) return rc;
+    for (int n = 0; n < N; ++n)
+        if (label_h[(size_t)n] < 0) return fail(-2, "row %d of the handle's data has no class in [0, %d) (internal error)", n, K);
+    for (int c = 0; s.vote && c < ncols; ++c) s.vote[c] = (double)votes_h[(size_t)c] / (double)M;
+    for (int n = 0; s.p_correct && n < N; ++n) s.p_correct[n] = (double)votes_h[(size_t)n * K + label_h[(size_t)n]] / (double)M;
     return 0;
 }
 

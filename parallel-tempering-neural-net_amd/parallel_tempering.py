@@ -35,6 +35,9 @@ from .prior import PriorPredictive, prior_flagged  # noqa: F401
 # partial dependence and ICE curves live in effects.py; the result tuple and pd_grid are importable from here
 from .effects import EffectAnalysis
 from .effects import PartialDependence, pd_grid  # noqa: F401
+# the classification report lives in report.py; the result tuple and its host helpers are importable from here
+from .report import ReportAnalysis
+from .report import ClassificationReport, auc_pairs, confusion_matrix, report_names, roc_curve, scores_from_confusion  # noqa: F401
 
 
 def _text_round(a, fmt, threads=8):
@@ -128,7 +131,7 @@ def overlap_cuts(S, swap_interval, chunks):
     return sorted({min(S - 1, si * max(1, round(n_int * (c + 1) / K))) for c in range(K - 1)} | {S - 1})
 
 
-class ParallelTemperingBase(PosteriorAnalysis, PriorAnalysis, EffectAnalysis):
+class ParallelTemperingBase(PosteriorAnalysis, PriorAnalysis, EffectAnalysis, ReportAnalysis):
     task = None                       # set by the two drop-in subclasses
     rmse_fmt = None                   # REG '%1.8f' (REG:462-464), CLS '%1.2f' (CLS:473-475)
 
