@@ -1279,7 +1279,9 @@ class Sampler:
         return list(buf)
 
     def describe(self):
-        """What the handle launches (kernel, grid, LDS, occupancy) as a dict; see ptnn_describe."""
+        """What the handle launches (kernel, grid, LDS, occupancy) as a dict; see ptnn_describe.  "swap_rounds" says how a swap round
+        runs -- "pipelined (ring 4)" (replica k waits for replicas 0 .. k+1 only), "grid barrier", "in-kernel exchange" (tree, packed
+        over several CUs) or "between launches" -- and "swap_ring_depth" the rounds the pipelined path buffers (0 elsewhere)."""
         import json
         buf = C.create_string_buffer(2048)
         self._check(self.lib.ptnn_describe(self.h, buf, len(buf)))

@@ -227,6 +227,13 @@ int ladder_adapt_reset(ptnn_handle* h) {
     return 0;
 }
 
+// Do the in-launch swap rounds of this handle take the pipelined path now?  The plan says whether the kernel and the configuration
+// allow it; what can change after planning is asked here: a communicator (its rounds run between launches) and ladder adaptation
+// (it needs the whole round's statistics in one place).
+bool swap_pipelined(const ptnn_handle* h) {
+    return h->plan.persistent && h->plan.swap_pipeline && h->comm.kind == COMM_NONE && !h->have_adapt;
+}
+
 // MH steps [begin, end) in one launch.  swap_inside: the swap rounds between the intervals run inside it (persistent launch:
 // every work-group resident, grid barriers); otherwise [begin, end) is one interval and the caller queues swap_kernel behind it.
 int launch_segment(ptnn_handle* h, int begin, int end, bool swap_inside = false, bool round_follows = false) {
@@ -253,6 +260,27 @@ int launch_segment(ptnn_handle* h, int begin, int end, bool swap_inside = false,
             pp.barrier = h->d_barrier;
         }
         HIP_TRY(hipMemsetAsync(h->d_barrier, 0, (size_t)grid * sizeof(unsigned), h->stream));
+    }
+    pp.delay_replica = -1;
+    if (swap_inside && swap_pipelined(h)) {
+        // the ring of posted rows and the two counters per replica of the pipelined rounds (swap_handoff)
+        const int R = h->cfg.n_replicas_global;
+        const int row = swap_ring_row_floats(h->PS);
+        if (R > h->swap_ring_replicas) {
+            for (void* q : {(void*)h->d_swap_ring, (void*)h->d_swap_tags})
+                if (q) HIP_TRY(hipFree(q));
+            h->d_swap_ring = nullptr; h->d_swap_tags = nullptr; h->swap_ring_replicas = 0;
+            HIP_TRY(hipMalloc(&h->d_swap_ring, (size_t)SWAP_RING_DEPTH * R * (row + 1) * sizeof(float)));     // the rows, then the posted scalars
+            HIP_TRY(hipMalloc(&h->d_swap_tags, (size_t)2 * R * sizeof(unsigned)));
+            h->swap_ring_replicas = R;
+        }
+        HIP_TRY(hipMemsetAsync(h->d_swap_tags, 0, (size_t)2 * R * sizeof(unsigned), h->stream));
+        pp.pipeline = 1; pp.ring_row = row; pp.ring = h->d_swap_ring; pp.ring_L = h->d_swap_ring + (size_t)SWAP_RING_DEPTH * R * row; pp.ready = h->d_swap_tags; pp.taken = h->d_swap_tags + R;
+        if (h->plan.delay_replica >= 0 && h->plan.delay_us > 0) {
+            int khz = 0;
+            HIP_TRY(hipDeviceGetAttribute(&khz, hipDeviceAttributeWallClockRate, h->cfg.device_id));
+            if (khz > 0) { pp.delay_replica = h->plan.delay_replica; pp.delay_ticks = (unsigned)((long long)h->plan.delay_us * khz / 1000); }
+        }
     }
     // event pairs around a launch cost a pipeline bubble each; time every timing_stride-th launch only
     const bool timed = h->timing_stride > 0 && (h->launch_count++ % h->timing_stride) == 0;
@@ -659,6 +687,20 @@ int plan_persistent(const ptnn_handle& h, LaunchPlan& plan) {
     int per_cu = 0;
     HIP_TRY(hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, fn, plan.threads, plan.seg_lds));
     plan.persistent = (long long)plan.grid(c.n_replicas_local) <= (long long)per_cu * h.num_cus;
+    // Pipelined swap rounds (swap_handoff): the one-CU packed kernel, the reference's cascade, the chains themselves moving, the whole
+    // ladder on this device.  The cooperative and the wide kernels share the loop but keep the grid barrier: they have not been
+    // measured on the new path.  $PTNN_SWAP_PIPELINE=0: the barrier everywhere (the A/B switch).
+    const char* pe = std::getenv("PTNN_SWAP_PIPELINE");
+    plan.swap_pipeline = plan.persistent && !(pe && pe[0] == '0') && plan.kind == SEG_PACK && plan.grid(1) == 1 && c.swap_rule == 0 &&
+                         !c.label_swap && c.n_replicas_local == R;
+    // $PTNN_SWAP_DELAY="r:t" (tests): replica r idles t microseconds before it posts.  t is capped at SWAP_DELAY_MAX_US = 5000: a
+    // waiter gives up after SPIN_LIMIT = 2^22 polls of at least 0.5 us each (a sleep and a round trip to L2), i.e. not before two
+    // seconds, and the SWAP_RING_DEPTH + 2 = 6 delayed rounds a waiter can at most sit out in one wait come to 30 ms.
+    if (const char* de = std::getenv("PTNN_SWAP_DELAY")) {
+        constexpr int SWAP_DELAY_MAX_US = 5000;
+        int r = -1, t = 0;
+        if (std::sscanf(de, "%d:%d", &r, &t) == 2 && r >= 0 && r < R && t > 0) { plan.delay_replica = r; plan.delay_us = std::min(t, SWAP_DELAY_MAX_US); }
+    }
     return 0;
 }
 
@@ -926,7 +968,7 @@ int ptnn_destroy(ptnn_handle* h) {
         if (hipStreamQuery(h->stream) == hipErrorNotReady) return fail(-7, "the stream of a failed communicator did not drain: handle leaked");
     }
     void* ptrs[] = {h->d_data, h->d_state[0], h->d_state[1], h->d_rec_w, h->d_gd_w[0], h->d_gd_w[1], h->d_gd_valid[0], h->d_gd_valid[1], h->d_st_f, h->d_st_i, h->d_temps,
-                    h->d_L_handoff, h->d_L_final, h->d_L_raw, h->d_prior_post, h->d_temps_global, h->d_pos_w, h->d_scal, h->d_src, h->d_label[0], h->d_label[1], h->d_slot_of[0], h->d_slot_of[1], h->d_src_log, h->d_counters, h->d_error, h->d_xslots, h->d_xw, h->d_xverdict, h->d_xswap, h->d_stamps, h->d_wide_scratch, h->d_xt, h->d_xs, h->d_barrier};
+                    h->d_L_handoff, h->d_L_final, h->d_L_raw, h->d_prior_post, h->d_temps_global, h->d_pos_w, h->d_scal, h->d_src, h->d_label[0], h->d_label[1], h->d_slot_of[0], h->d_slot_of[1], h->d_src_log, h->d_counters, h->d_error, h->d_xslots, h->d_xw, h->d_xverdict, h->d_xswap, h->d_stamps, h->d_wide_scratch, h->d_xt, h->d_xs, h->d_barrier, h->d_swap_ring, h->d_swap_tags};
     for (void* p : ptrs)
         if (p) (void)hipFree(p);
     if (h->h_src) (void)hipHostFree(h->h_src);
@@ -1842,17 +1884,25 @@ int ptnn_describe(ptnn_handle* h, char* buf, int nbytes) {
                     : pl.kind == SEG_TREE ? tree_depth(pl.groups)                              // the steps committed per round
                     : pl.wide() ? (pl.groups > 1 && h->cfg.use_langevin ? 8 : pl.groups)
                     : pack_slots(pl.pk_nred) * pl.groups;
+    // how a swap round is run: inside the launch -- pipelined, at the grid barrier, or by the kernel's own granule exchange (tree,
+    // packed over several CUs) -- or by swap_kernel / the communicator between two launches
+    const bool inside = pl.persistent && h->comm.kind == COMM_NONE;
+    const bool pipelined = swap_pipelined(h);
+    const char* const swap_rounds = !inside ? "between launches" : pipelined ? "pipelined (ring 4)"
+                                    : (pl.kind == SEG_TREE || pl.kind == SEG_PACKM) ? "in-kernel exchange" : "grid barrier";
+    static_assert(SWAP_RING_DEPTH == 4, "describe() spells the ring depth out");
     const int n = std::snprintf(buf, (size_t)nbytes,
                                 "{\"kernel\": \"ptnn::%s<%d,%d,%d%s>\", \"schedule\": \"%s\", \"grid_blocks\": %d, \"block_threads\": %d, "
                                 "\"lds_bytes\": %zu, \"groups_per_replica\": %d, \"slots_per_round\": %d, \"num_cus\": %d, "
-                                "\"blocks_per_cu\": %d, \"vgprs\": %d, \"scratch_bytes\": %zu, \"forward_mfma\": %d, \"exchange\": \"%s\", \"lds_resident_state\": %d, \"compact_traces\": %d, \"launches\": \"%s\"}",
+                                "\"blocks_per_cu\": %d, \"vgprs\": %d, \"scratch_bytes\": %zu, \"forward_mfma\": %d, \"exchange\": \"%s\", \"lds_resident_state\": %d, \"compact_traces\": %d, \"launches\": \"%s\", \"swap_rounds\": \"%s\", \"swap_ring_depth\": %d}",
                                 g_seg[pl.kind].name, h->cfg.task, h->cfg.n_in, h->cfg.n_out, width,
                                 pl.wide() && pl.groups > 1 ? "speculative-wide" : g_seg[pl.kind].label,
                                 pl.grid(h->cfg.n_replicas_local), pl.threads, pl.seg_lds, pl.groups, slots, h->num_cus, per_cu, fa.numRegs, (size_t)fa.localSizeBytes,
                                 pl.fw_mfma ? pl.fw_mfma : ((pl.wide() && h->cfg.n_hidden % 32 == 0) ? 1 : 0),
                                 h->comm.kind == COMM_NONE ? "none" : (h->cfg.label_swap ? "labels" : (resolved_xchg_mode(h) == PTNN_XCHG_GATHER ? "gather" : "boundary")),
                                 pl.kind == SEG_WIDE_RES ? 1 : 0, pl.compact ? 1 : 0,
-                                (pl.persistent && h->comm.kind == COMM_NONE) ? "one per ptnn_run (swap rounds inside)" : "one per swap interval");
+                                (pl.persistent && h->comm.kind == COMM_NONE) ? "one per ptnn_run (swap rounds inside)" : "one per swap interval",
+                                swap_rounds, pipelined ? (int)SWAP_RING_DEPTH : 0);
     if (n < 0 || n >= nbytes) return fail(-1, "buffer of %d bytes is too small for the description", nbytes);
     return n;
 }

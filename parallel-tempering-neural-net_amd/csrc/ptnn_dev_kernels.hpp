@@ -125,6 +125,7 @@ __global__ void __launch_bounds__(MAX_THREADS) model_kernel(const SegParams p, c
 // has a single barrier (one work-group per replica): the posted scalars (L_handoff / L_final / L_raw) are single-buffered, every
 // work-group copies all of them into LDS right after the barrier (cascade_lds), and the next write to any of them is a whole swap
 // interval away.  The host only takes this shape for intervals of 8 MH steps or more (ptnn.hip: resolve_persistent).
+// The one-CU packed kernels can run the round without the barrier (swap_handoff below: tagged ring slots, no such invariant).
 // ------------------------------------------------------------------------------------------------
 // Grid barrier without a read-modify-write: every work-group owns one slot and stores the phase it has reached (distinct
 // addresses: nothing serialises -- 256 agent-scope atomic adds on ONE counter cost more than the launch boundary this replaces),
@@ -152,10 +153,124 @@ __device__ __forceinline__ bool grid_barrier(unsigned* slots, int nblocks, unsig
     return bad == 0;
 }
 
+// Wave 0 waits until words[0 .. n) have all reached `want` (lane = word, 64 at a time); bounded and abandoned on the error flag like
+// grid_barrier's poll.  Returns 1 on a timeout (in wave 0; the caller spreads it with __syncthreads_or).
+__device__ __forceinline__ int poll_reached(const unsigned* words, int n, unsigned want, int* error_flag) {
+    int bad = 0;
+    if (threadIdx.x < WAVE) {
+        unsigned spins = 0;
+        for (;;) {
+            bool here = true;
+            for (int j = threadIdx.x; j < n; j += WAVE)
+                here = here && (__hip_atomic_load(words + j, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) >= want);
+            if (__all(here)) break;
+            __builtin_amdgcn_s_sleep(4);
+            if (++spins > SPIN_LIMIT || __hip_atomic_load(error_flag, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) != 0) { bad = 1; break; }
+        }
+    }
+    return bad;
+}
+
+// A swap round without the grid barrier (one work-group per replica, the cascade rule, the whole ladder in this launch; the host
+// decides: PersistParams::pipeline).  The bubble pass only carries states UP the ladder: src[k] is a function of L[0 .. k+1] and
+// u[0 .. k], so replica k posts what the round may move (its state row, cached gradient, gd_valid and L_handoff) and waits for
+// replicas 0 .. k+1 alone -- not for the slowest of all R.  n counts the rounds of this launch.
+//   post   into slot n mod D of a ring of D = SWAP_RING_DEPTH rounds; once n >= D only after every replica has TAKEN round n - D
+//          (taken[j] >= n - D + 1 for all j: the row this overwrites has no reader left).  Then release, ready[k] = n + 1.
+//   wait   ready[j] >= n + 1 for j <= min(k+1, R-1), acquire.
+//   decide cascade_lds_prefix over those min(k+2, R) rungs: src[k] is the full cascade's.  Replica R-1 (and R-2) run all R rungs;
+//          replica R-1 keeps the books block 0 keeps on the barrier path.
+//   take   row src[k] of the slot -> state / gd / gd_valid [flip^1][k], as swap_block moves it; release, taken[k] = n + 1.
+// Nobody waits for a replica above k+1, and the posted scalars are read from the tagged slot, never from the single-buffered
+// L_handoff: the timing invariant of the barrier path is not needed here.  Progress: the replica furthest behind (round m) waits
+// for posts of round m, and a post of round m waits for takes of round m - D only, which everybody has behind them.
+__device__ __forceinline__ bool swap_handoff(persist_cptr pp, const int flip, const int round, const unsigned n, int* error_flag, float* smem) {
+    const int R = pp->sp.R, PS = pp->sp.PS, ROW = pp->ring_row;
+    const int k = blockIdx.x;
+    float* const slot = pp->ring + (size_t)(n % SWAP_RING_DEPTH) * R * ROW;
+    float* const slot_L = pp->ring_L + (size_t)(n % SWAP_RING_DEPTH) * R;
+    __syncthreads();                                                // the body's row and posted scalar are written
+    if (pp->delay_replica == k) {                                   // the tests' straggler: bounded by the clock and by the spin count
+        const unsigned long long t0 = wall_clock64();
+        for (unsigned s = 0; s < SPIN_LIMIT && wall_clock64() - t0 < (unsigned long long)pp->delay_ticks; ++s) __builtin_amdgcn_s_sleep(8);
+    }
+    if (n >= SWAP_RING_DEPTH) {
+        // the stores below are ordered behind this wait by the work-group barrier; nothing is read that the others wrote
+        if (__syncthreads_or(poll_reached(pp->taken, R, n - SWAP_RING_DEPTH + 1u, error_flag))) return false;
+    }
+    {
+        const float4* const w = reinterpret_cast<const float4*>(pp->state[flip] + (size_t)k * PS);
+        const float4* const g = reinterpret_cast<const float4*>(pp->gd[flip] + (size_t)k * PS);
+        float* const row = slot + (size_t)k * ROW;
+        for (int j = threadIdx.x; j < PS / 4; j += blockDim.x) {
+            reinterpret_cast<float4*>(row)[j] = w[j];
+            reinterpret_cast<float4*>(row + PS)[j] = g[j];
+        }
+        if (threadIdx.x == 0) {
+            reinterpret_cast<int*>(row)[2 * PS] = pp->gd_valid[flip][k];
+            slot_L[k] = pp->sp.L[pp->sp.first_global + k];
+        }
+    }
+    // every storing wave drains its stores, then one lane releases them to the agent and signals; the wait behind the fence stays
+    // (the compiler may merge the fence's own wait into an earlier one)
+    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "agent");          // this replica's row, visible on every XCD
+        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+        __hip_atomic_store(pp->ready + k, n + 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    }
+    const int Rp = min(k + 2, R);
+    const int bad = __syncthreads_or(poll_reached(pp->ready, Rp, n + 1u, error_flag));
+    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent");              // nothing cached from before the others posted
+    if (bad) return false;
+    float* const sL = smem;
+    float* const sU = smem + R;
+    int* const sSrc = reinterpret_cast<int*>(smem + 2 * R);
+    for (int j = threadIdx.x; j < Rp; j += blockDim.x) sL[j] = slot_L[j];
+#if defined(__HIP_DEVICE_COMPILE__)
+    const SwapParams sp = pp->sp;
+#else
+    const SwapParams sp{};
+#endif
+    const int nsw = cascade_lds_prefix(sp, Rp, round, sL, sU, sSrc, true);
+    if (k == R - 1) {                                               // the whole cascade: the books of the round
+        if (sp.src_out) for (int j = threadIdx.x; j < R; j += blockDim.x) sp.src_out[j] = sSrc[j];
+        if (sp.src_log && round < sp.log_capacity)
+            for (int j = threadIdx.x; j < R; j += blockDim.x) sp.src_log[(size_t)round * R + j] = sSrc[j];
+        if (threadIdx.x == 0) {
+            sp.counters[0] += nsw;
+            sp.counters[1] += R - 1;
+            if (sp.progress) __hip_atomic_store(sp.progress, round + 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
+        }
+    }
+    {
+        const float* const from = slot + (size_t)sSrc[k] * ROW;
+        float4* const w = reinterpret_cast<float4*>(pp->state[flip ^ 1] + (size_t)k * PS);
+        float4* const g = reinterpret_cast<float4*>(pp->gd[flip ^ 1] + (size_t)k * PS);
+        for (int j = threadIdx.x; j < PS / 4; j += blockDim.x) {
+            w[j] = reinterpret_cast<const float4*>(from)[j];
+            g[j] = reinterpret_cast<const float4*>(from + PS)[j];
+        }
+        if (threadIdx.x == 0) pp->gd_valid[flip ^ 1][k] = reinterpret_cast<const int*>(from)[2 * PS];
+    }
+    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+    __syncthreads();                                                // the row is out of the slot (and sSrc is free again)
+    if (threadIdx.x == 0) {
+        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "agent");
+        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+        __hip_atomic_store(pp->taken + k, n + 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    }
+    return true;
+}
+
 // LOOP = false: one interval per launch and nothing else (the two schedules with several work-groups per replica and the most
 // registers -- multi-CU speculative, prefetching tree -- where the loop around the body cost 30 - 40 vector registers, i.e. scratch,
 // and where a persistent launch is measured to lose against the launch boundary anyway).
-template <bool LOOP, class Body>
+// PIPE: the kernel carries the pipelined swap round (swap_handoff) beside the barrier round and takes it when the host says so
+// (PersistParams::pipeline) -- the one-CU packed kernels only; the others keep the code they had (with the branch compiled in, the
+// cooperative Ionosphere run was 1.9 % slower although it never took it).
+template <bool LOOP, bool PIPE = false, class Body>
 __device__ __forceinline__ void persistent_loop(const SegParams& p0, const int step_begin, Body body) {
     extern __shared__ __attribute__((aligned(16))) float smem[];
     if constexpr (!LOOP) {
@@ -207,6 +322,14 @@ __device__ __forceinline__ void persistent_loop(const SegParams& p0, const int s
         cur = stop;
         if (!handoff || !swap_inside) break;
         pp = persist_args();
+        if constexpr (PIPE) {
+            if (pp->pipeline) {                                       // no rendezvous of the whole grid: see swap_handoff
+                if (!swap_handoff(pp, flip, round, phase++, p.error_flag, smem)) { if (threadIdx.x == 0) atomicAdd(p.error_flag, 1); return; }
+                flip ^= 1;
+                round += 1;
+                continue;
+            }
+        }
         if (!grid_barrier(pp->barrier, pp->nblocks, ++phase, p.error_flag)) { if (threadIdx.x == 0) atomicAdd(p.error_flag, 1); return; }
         if (xcd_block(p.G) % p.G == 0) {                              // the bodies' own (replica, group) of this work-group
 #if defined(__HIP_DEVICE_COMPILE__)
@@ -251,7 +374,7 @@ __global__ void __launch_bounds__(MAX_THREADS) segment_spec_kernel(const SegPara
 }
 template <int TASK, int I, int O>
 __global__ void __launch_bounds__(PK_WAVES * WAVE) segment_pack_kernel(const SegParams p, const PersistParams pp, const int step_begin) {
-    persistent_loop<pack_has_loop<TASK, I, O>()>(p, step_begin, [](const SegParams& q, const SegDyn& d, int b, int n) {
+    persistent_loop<pack_has_loop<TASK, I, O>(), true>(p, step_begin, [](const SegParams& q, const SegDyn& d, int b, int n) {
         if (q.pk_nred == 4) segment_pack_body<TASK, I, O, 4>(q, d, b, n);
         else segment_pack_body<TASK, I, O, 3>(q, d, b, n);
     });
@@ -262,7 +385,7 @@ __global__ void __launch_bounds__(PK_WAVES * WAVE) segment_pack_kernel(const Seg
 template <int TASK, int I, int O, int HC>
 __global__ void __launch_bounds__(PK_WAVES * WAVE) segment_pack_kernel(const SegParams p, const PersistParams pp, const int step_begin) {
     static_assert(HC > 0 && HC <= 16, "a packed net has at most 16 hidden units");
-    persistent_loop<pack_has_loop<TASK, I, O>()>(p, step_begin, [](const SegParams& q, const SegDyn& d, int b, int n) {
+    persistent_loop<pack_has_loop<TASK, I, O>(), true>(p, step_begin, [](const SegParams& q, const SegDyn& d, int b, int n) {
         segment_pack_body<TASK, I, O, pack_nred(HC), false, HC>(q, d, b, n);
     });
 }

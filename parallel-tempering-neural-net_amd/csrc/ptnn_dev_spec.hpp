@@ -158,8 +158,10 @@ __host__ __device__ inline int xchg_row_floats(int PS) { return (2 * PS + 4 + 3)
 
 // sSrc has R + 1 ints: the last one carries the number of accepted swaps
 // have_L: sL already holds the R posted scalars (the tree's in-launch swap round reads them from granules)
-__device__ __forceinline__ int cascade_lds(const SwapParams& sp, int round, float* sL, float* sU, int* sSrc, bool have_L = false) {
-    const int R = sp.R;
+// Prefix form (R <= sp.R): the pass over the first R rungs only.  The uniforms are keyed by (pair, round) and the carried state only
+// moves up the ladder, so src[0 .. R-2] of a prefix run are the full run's; src[R-1] (the state still carried at the cut) and the
+// count in sSrc[R] are the prefix's own and no result of the round unless R == sp.R.
+__device__ __forceinline__ int cascade_lds_prefix(const SwapParams& sp, const int R, int round, float* sL, float* sU, int* sSrc, bool have_L) {
     for (int k = threadIdx.x; k < R; k += blockDim.x) {
         if (!have_L) sL[k] = sp.L[(size_t)(sp.label_mode ? sp.slot_cur[k] : k) * sp.L_stride];    // k is a temperature index
         if (k < R - 1) {
@@ -229,6 +231,9 @@ __device__ __forceinline__ int cascade_lds(const SwapParams& sp, int round, floa
     __syncthreads();
     return sSrc[R];
 }
+__device__ __forceinline__ int cascade_lds(const SwapParams& sp, int round, float* sL, float* sU, int* sSrc, bool have_L = false) {
+    return cascade_lds_prefix(sp, sp.R, round, sL, sU, sSrc, have_L);
+}
 
 // What a launch that spans several swap intervals needs to know (persistent_loop at the end of this file; the tree body runs its
 // own swap rounds and reads it too)
@@ -246,7 +251,19 @@ struct PersistParams {
     int* label[2];
     int* slot_of[2];
     SwapParams sp;           // everything of a round that does not flip
+    // pipelined swap rounds (one work-group per replica, cascade rule; swap_handoff in ptnn_dev_kernels.hpp): instead of meeting at
+    // the grid barrier, replica k posts its row into slot (round mod SWAP_RING_DEPTH) of a ring and waits for replicas 0 .. k+1 only
+    int pipeline;            // 1: the in-launch rounds take that path
+    int ring_row;            // floats per ring row: state PS | cached gradient PS | gd_valid | pad to a float4
+    float* ring;             // [SWAP_RING_DEPTH][R][ring_row]
+    float* ring_L;           // [SWAP_RING_DEPTH][R] the posted scalars, side by side: a prefix of them is a few lines to fetch
+    unsigned* ready;         // [R] rounds of this launch replica k has posted, zero at launch
+    unsigned* taken;         // [R] rounds of this launch replica k has taken its row of, zero at launch
+    int delay_replica;       // $PTNN_SWAP_DELAY (tests): this replica idles delay_ticks of the constant-rate counter before it posts; -1: none
+    unsigned delay_ticks;
 };
+constexpr unsigned SWAP_RING_DEPTH = 4;
+__host__ __device__ inline int swap_ring_row_floats(int PS) { return 2 * PS + 4; }     // PS is a multiple of 4: rows stay 16-byte aligned
 
 // The PersistParams of the launch, read from the kernel-argument segment where it lies (second argument, behind SegParams) through
 // a pointer the optimiser cannot see through: every use re-loads the few words it needs (scalar loads from the constant cache)

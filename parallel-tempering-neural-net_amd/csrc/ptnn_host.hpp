@@ -51,6 +51,9 @@ struct LaunchPlan {
     bool compact = false;           // wide nets with all trace rows resident: rejected steps record a row index, no pos_w row
     int blocks_per_cu = 0;          // occupancy of the segment kernel as the runtime reports it (0 = not queried)
     bool persistent = false;        // all work-groups of the grid are resident: ptnn_run queues ONE launch, swap rounds inside
+    bool swap_pipeline = false;     // ... and those rounds are pipelined (replica k waits for 0 .. k+1, no grid barrier): plan_persistent
+    int delay_replica = -1;         // $PTNN_SWAP_DELAY="r:t" (tests): replica r idles delay_us microseconds before it posts a pipelined round
+    int delay_us = 0;
     // bytes of the buffers the plan needs (0 = none): multi-group exchange slots / rows / verdicts, in-launch swap granules, wide scratch
     size_t xslots = 0, xw = 0, xverdict = 0, xswap = 0, wide_scratch = 0;
     bool wide() const { return kind == SEG_WIDE || kind == SEG_WIDE_RES; }
@@ -67,6 +70,9 @@ struct ptnn_handle {
     ptnn::LaunchPlan plan;
     unsigned* d_barrier = nullptr;  // grid barrier of the persistent launch: one slot per work-group
     int barrier_slots = 0;
+    float* d_swap_ring = nullptr;   // pipelined swap rounds: [SWAP_RING_DEPTH][R][ring row] posted rows ...
+    unsigned* d_swap_tags = nullptr;    // ... and ready[R] | taken[R], zeroed before every launch
+    int swap_ring_replicas = 0;
     float* d_wide_scratch = nullptr;
     float* d_xt = nullptr;          // transposed data image for the MFMA forward pass
     uint16_t* d_xs = nullptr;       // wide nets: the data image split into three bf16 levels (split-operand forward pass)
