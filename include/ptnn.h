@@ -684,6 +684,73 @@ typedef struct ptnn_calibration_spec {
 
 int ptnn_calibration(ptnn_handle *h, const ptnn_calibration_spec *spec);
 
+/* ---- forecast verification: proper scores of the recursive forecasts by lead time (nothing in the reference) ----
+ * Trajectories: exactly ptnn_forecast's -- the same sample selection, trajectory index i, Philox stream, counters and seed, so
+ * `samples` is bitwise ptnn_forecast's with the same arguments.  Noise on: every selected occurrence is its own trajectory, c_i
+ * = 1; noise off: one trajectory per distinct (w, eta) sample with multiplicity c (merged as ptnn_calibration merges them: equal
+ * w and eta bits).  mu_{i,r,k} = the fp32 sigmoid output of trajectory i at origin r, step k, before that step's noise is added
+ * (y = mu + exp(eta / 2) z; noise off: mu = y).  The predictive distribution of the series value at step k is the mixture
+ * (1/M) sum_i c_i N(mu_{i,r,k}, tau_i^2), tau_i^2 = exp(eta_i) (Rao-Blackwellised over the last step's noise; at k = 1 it is
+ * ptnn_calibration's mixture on the origin row).
+ * truth [n_origins, horizon] float32, always from the host: NaN = no observation at that column.  Per column with finite truth
+ * y, in double, ptnn_calibration's definitions: pit, pred_mean, pred_sd, crps (with pair_term), quantiles [k][column]; and
+ * log_score = log (1/M) sum_i c_i N(y; mu_i, tau_i^2) (pointwise terms as ptnn_elpd's ll, exact maximum, fixed-point sum).
+ * Columns without truth give NaN in every per-column output.
+ * energy != 0: per origin the energy score of the path (Gneiting et al. 2008) over K_r = the steps with finite truth, Y_i the
+ * fp32 noisy path restricted to K_r (noise off: the mean path, weighted by c):
+ *   es_r = (1/M) sum_i c_i |Y_i - y|_2 - (1 / (2 M^2)) sum_i sum_j c_i c_j |Y_i - Y_j|_2   (i = j included; double),
+ * NaN for an origin with empty K_r; with |K_r| = 1 it is the ensemble CRPS of that column.
+ * Every output is bitwise independent of the scratch budget, of repeated calls and of the form of the source (trace, host
+ * vectors, expanded or with multiplicities): every sum over trajectories is an exact integer sum of fixed-point terms.
+ * Outputs, any may be NULL, column c = origin * horizon + k: pit, crps, log_score, pred_mean, pred_sd [n_origins, horizon];
+ * quantiles [n_levels, n_origins, horizon]; energy_score [n_origins]; samples and means (mu) [M, n_origins, horizon] float32,
+ * chain-major as ptnn_forecast's samples; n_samples = M; n_trajectories = trajectories per origin.
+ * Refused: a classification net or n_out != 1; horizon < 1; more than 2^31 - 1 columns; truth NULL, containing +-inf or without
+ * a finite entry; n_levels outside [0, PTNN_CALIB_MAX_LEVELS], a level outside (0, 1), levels without quantiles; crps without
+ * pair_term; energy_score without energy; noise on without eta (ptnn_forecast's texts); pair_term or energy with more than
+ * PTNN_CALIB_MAX_DISTINCT trajectories; energy with horizon > PTNN_FSCORE_MAX_ENERGY_HORIZON or when one origin's whole
+ * horizon does not fit the scratch budget; an attached communicator.
+ * Runs on the handle's stream behind everything queued and returns when done; scratch stays under $PTNN_FSCORE_SCRATCH_BYTES
+ * (read per call, default 1 GiB): with energy a block is whole origins, else origins and horizon steps are blocked as
+ * ptnn_forecast blocks them.  Touches no chain state, tape, counter or trace row. */
+#define PTNN_FSCORE_MAX_ENERGY_HORIZON 2048
+
+typedef struct ptnn_forecast_score_spec {
+    int32_t struct_bytes;         /* = sizeof(ptnn_forecast_score_spec): ABI guard */
+    /* source 1: the trace (used when w == NULL) */
+    const int32_t *replicas;      /* local replica indices, or NULL = all */
+    int32_t n_replicas;           /* entries of replicas (ignored when NULL) */
+    int32_t step0, nsteps, thin;  /* trace rows step0, step0 + thin, ... < step0 + nsteps (thin >= 1) */
+    /* source 2: host vectors */
+    const float *w;               /* [n_w, P] or NULL */
+    const int32_t *multiplicity;  /* [n_w] >= 0, or NULL = 1 each */
+    const float *eta;             /* [n_w] log tau^2 */
+    int64_t n_w;
+    /* origins and truth */
+    int32_t origin_source;        /* PTNN_FORECAST_ORIGIN_HOST | _TRAIN | _TEST */
+    int32_t n_origins;
+    const float *origins;         /* [n_origins, n_in] (host origins only) */
+    const float *truth;           /* [n_origins, horizon], NaN = no observation */
+    int32_t horizon;              /* >= 1 */
+    int32_t noise;                /* 0 / 1 */
+    uint64_t seed;                /* noise on only */
+    /* quantile levels, the pair term of the CRPS, the energy score */
+    const double *levels_p;       /* [n_levels] in (0, 1) */
+    const double *levels_z;       /* [n_levels] Phi^-1(levels_p) */
+    int32_t n_levels;             /* <= PTNN_CALIB_MAX_LEVELS */
+    int32_t pair_term;            /* 0 / 1 */
+    int32_t energy;               /* 0 / 1 */
+    int32_t reserved_;            /* set 0 */
+    /* outputs */
+    double *pit, *crps, *log_score, *pred_mean, *pred_sd;
+    double *quantiles;
+    double *energy_score;
+    float *samples, *means;
+    int64_t *n_samples, *n_trajectories;
+} ptnn_forecast_score_spec;
+
+int ptnn_forecast_score(ptnn_handle *h, const ptnn_forecast_score_spec *spec);
+
 /* ---- input sensitivity (nothing in the reference: it reports no importance, sensitivity or saliency of its inputs) ----
  * Which inputs the sampled nets respond to: the Jacobian of the network output with respect to the inputs, per sample and data
  * row, reduced on the device.  With decode(w) = W1 [I,H], W2 [H,O], B1, B2, bias subtracted, sigmoid on both layers (REG:51-55):

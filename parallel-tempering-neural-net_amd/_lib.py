@@ -154,6 +154,24 @@ CALIB_MAX_LEVELS = 16
 CALIB_MAX_DISTINCT = 65536
 
 
+class ForecastScoreSpec(C.Structure):
+    """ptnn_forecast_score_spec (include/ptnn.h)."""
+    _fields_ = _SELECTION + [
+        ("w", C.POINTER(C.c_float)), ("multiplicity", C.POINTER(C.c_int32)), ("eta", C.POINTER(C.c_float)), ("n_w", C.c_int64),
+        ("origin_source", C.c_int32), ("n_origins", C.c_int32), ("origins", C.POINTER(C.c_float)), ("truth", C.POINTER(C.c_float)),
+        ("horizon", C.c_int32), ("noise", C.c_int32), ("seed", C.c_uint64),
+        ("levels_p", C.POINTER(C.c_double)), ("levels_z", C.POINTER(C.c_double)), ("n_levels", C.c_int32), ("pair_term", C.c_int32),
+        ("energy", C.c_int32), ("reserved_", C.c_int32),
+        ("pit", C.POINTER(C.c_double)), ("crps", C.POINTER(C.c_double)), ("log_score", C.POINTER(C.c_double)),
+        ("pred_mean", C.POINTER(C.c_double)), ("pred_sd", C.POINTER(C.c_double)), ("quantiles", C.POINTER(C.c_double)),
+        ("energy_score", C.POINTER(C.c_double)), ("samples", C.POINTER(C.c_float)), ("means", C.POINTER(C.c_float)),
+        ("n_samples", C.POINTER(C.c_int64)), ("n_trajectories", C.POINTER(C.c_int64)),
+    ]
+
+
+FSCORE_MAX_ENERGY_HORIZON = 2048
+
+
 class SensitivitySpec(C.Structure):
     """ptnn_sensitivity_spec (include/ptnn.h)."""
     _fields_ = _SELECTION + [
@@ -350,6 +368,7 @@ SYMBOLS = {
     "ptnn_forecast": (C.c_int, [C.c_void_p, C.POINTER(ForecastSpec)]),
     "ptnn_evidence": (C.c_int, [C.c_void_p, C.POINTER(EvidenceSpec)]),
     "ptnn_calibration": (C.c_int, [C.c_void_p, C.POINTER(CalibrationSpec)]),
+    "ptnn_forecast_score": (C.c_int, [C.c_void_p, C.POINTER(ForecastScoreSpec)]),
     "ptnn_sensitivity": (C.c_int, [C.c_void_p, C.POINTER(SensitivitySpec)]),
     "ptnn_partial_dependence": (C.c_int, [C.c_void_p, C.POINTER(PdSpec)]),
     "ptnn_ppc": (C.c_int, [C.c_void_p, C.POINTER(PpcSpec)]),
@@ -1192,6 +1211,44 @@ class Sampler:
                    samples=np.empty((max(M, 0), n_org, hz), np.float32) if samples else None)
         _bind(spec, out)
         return self._call(self.lib.ptnn_forecast, spec, out, counters=("n_samples", "n_trajectories"))
+
+    def forecast_score(self, horizon, origins, truth, *, replicas=None, step0=0, nsteps=None, thin=1, w=None, multiplicity=None,
+                       eta=None, noise=True, seed=0, quantiles=(), crps=True, energy=True, samples=False, means=False):
+        """ptnn_forecast_score: the recursive forecasts of ptnn_forecast scored against `truth` [n_origins, horizon] (NaN = no
+        observation) on the device.  Source, origins, noise and seed as forecast(); eta [n] always comes with host vectors.
+        -> dict(pit, pred_mean, pred_sd, log_score [n_origins, horizon] float64, crps [n_origins, horizon] (crps=True: the
+        all-pairs term), quantiles [len(quantiles), n_origins, horizon], energy_score [n_origins] (energy=True), samples and
+        means [M, n_origins, horizon] float32, n_samples, n_trajectories); what was not asked for is None."""
+        spec, keep = _spec(ForecastScoreSpec), []
+        dp = C.POINTER(C.c_double)
+        self._rows(spec, keep, origins, "origins", (self.cfg.n_in, "n_in columns"), ("origin_source", "n_origins", "origins"))
+        spec.horizon, spec.noise, spec.seed = int(horizon), 1 if noise else 0, int(seed) & 0xFFFFFFFFFFFFFFFF
+        n_org, hz = spec.n_origins, max(int(horizon), 0)
+        ta = _f32(truth)
+        if ta.shape != (n_org, hz):
+            raise ValueError(f"truth must be [n_origins, horizon] = ({n_org}, {hz}), got shape {ta.shape}")
+        keep.append(ta)
+        spec.truth = _ptr(ta)
+        M = self._samples(spec, keep, w=w, eta=eta, multiplicity=multiplicity, replicas=replicas, step0=step0, nsteps=nsteps, thin=thin,
+                          unit="vector")
+        lp = np.ascontiguousarray(quantiles, dtype=np.float64).reshape(-1)
+        if lp.size > CALIB_MAX_LEVELS:
+            raise ValueError(f"{lp.size} quantile levels: at most {CALIB_MAX_LEVELS} per call")
+        if lp.size and not (np.all(lp > 0.0) and np.all(lp < 1.0)):
+            raise ValueError(f"quantile levels must lie in (0, 1), got {lp.tolist()}")
+        lz = np.array([NormalDist().inv_cdf(float(p)) for p in lp], dtype=np.float64)
+        keep += [lp, lz]
+        if lp.size:
+            spec.levels_p, spec.levels_z, spec.n_levels = lp.ctypes.data_as(dp), lz.ctypes.data_as(dp), lp.size
+        spec.pair_term, spec.energy = 1 if crps else 0, 1 if energy else 0
+        col = lambda: np.empty((n_org, hz), np.float64)       # noqa: E731
+        out = dict(pit=col(), pred_mean=col(), pred_sd=col(), log_score=col(), crps=col() if crps else None,
+                   quantiles=np.empty((lp.size, n_org, hz), np.float64) if lp.size else None,
+                   energy_score=np.empty(n_org, np.float64) if energy else None,
+                   samples=np.empty((max(M, 0), n_org, hz), np.float32) if samples else None,
+                   means=np.empty((max(M, 0), n_org, hz), np.float32) if means else None)
+        _bind(spec, out)
+        return self._call(self.lib.ptnn_forecast_score, spec, out, counters=("n_samples", "n_trajectories"))
 
     def evidence(self, *, replicas=None, step0=0, nsteps=None, thin=1, w=None, u=None, multiplicity=None, d=None, n_prior=0, seed=0,
                  a=(), u_out=False, u_prior_out=False):

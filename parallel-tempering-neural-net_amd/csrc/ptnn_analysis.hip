@@ -1,5 +1,5 @@
 // ptnn_analysis.hip -- the posterior analysis calls of libptnn.so: predict, convergence, rank_convergence, elpd, lfo, forecast, evidence, calibration,
-// sensitivity, partial_dependence, ppc, powerscale, prior_predictive, and the sample-selection path they share.  The shape-independent analysis kernels are defined in this object: it includes them.
+// forecast_score, sensitivity, partial_dependence, ppc, powerscale, prior_predictive, and the sample-selection path they share.  The shape-independent analysis kernels are defined in this object: it includes them.
 #include "ptnn_shapes.hpp"
 namespace ptnn {
 #include "ptnn_dev_wg.hpp"                   // work-group reductions and scans of every kernel below (ptnn_device.hpp has included it: ladder_round)
@@ -9,6 +9,7 @@ namespace ptnn {
 #include "ptnn_dev_lfo.hpp"                  // leave-future-out cross-validation: running sums of ll, PSIS per origin
 #include "ptnn_dev_evidence.hpp"             // log evidence: per-rung statistics of the full-data log-likelihood, prior draws
 #include "ptnn_dev_calibration.hpp"          // calibration: PIT, quantiles and CRPS of the predictive mixture per data row
+#include "ptnn_dev_fscore.hpp"               // forecast verification: log score per column, energy score of the path per origin
 #include "ptnn_dev_ppc.hpp"                  // posterior predictive checks: replicated data and test quantities per occurrence
 #include "ptnn_dev_powerscale.hpp"           // power-scaling sensitivity: components, smoothed weights, order per quantity, distances
 #include "ptnn_dev_prior.hpp"                // prior predictive checks: saturation counts, statistics per drawn function and over the draws
@@ -1800,6 +1801,221 @@ int ptnn_calibration(ptnn_handle* h, const ptnn_calibration_spec* spec) {
     HIP_TRY(fetch(s.pred_sd, d_sd, (size_t)n_rows, st));
     HIP_TRY(fetch(s.quantiles, d_q, (size_t)s.n_levels * n_rows, st));
     HIP_TRY(fetch(s.crps, d_crps, (size_t)n_rows, st));
+    return wait_stream(h);
+}
+
+// ---- forecast verification (ptnn_dev_fscore.hpp) ----
+int ptnn_forecast_score(ptnn_handle* h, const ptnn_forecast_score_spec* spec) {
+    // argument checks first: none of them needs the handle or a device
+    if (int rc = check_spec(spec, "ptnn_forecast_score_spec")) return rc;
+    const ptnn_forecast_score_spec& s = *spec;
+    const bool host_src = s.w != nullptr, noise = s.noise != 0, pair = s.pair_term != 0, energy = s.energy != 0;
+    SampleSource src = source_of(s, host_src, s.eta);
+    const RowSource rows{s.origin_source, s.origins, s.n_origins, "origin_source", "PTNN_FORECAST_ORIGIN", "origins", "n_origins"};
+    if (int rc = check_source(src, "vectors")) return rc;
+    if (int rc = check_rows(rows)) return rc;
+    if (s.n_origins < 1) return fail(-1, "n_origins = %d must be >= 1", s.n_origins);
+    if (s.horizon < 1) return fail(-1, "horizon = %d must be >= 1", s.horizon);
+    const long long ncols = (long long)s.n_origins * s.horizon;
+    if (ncols > 0x7fffffffLL) return fail(-1, "%d origins x horizon %d = %lld columns: at most 2^31 - 1 per call", s.n_origins, s.horizon, ncols);
+    if (!s.truth) return fail(-1, "truth is NULL: forecast verification needs the observed values [n_origins, horizon] (NaN = none)");
+    const int hz = s.horizon, n_org = s.n_origins;
+    // the steps with truth of every origin
+    std::vector<int> klist((size_t)ncols, 0), nk((size_t)n_org, 0);
+    long long n_finite = 0;
+    for (long long c = 0; c < ncols; ++c) {
+        const float v = s.truth[c];
+        if (std::isinf(v)) return fail(-1, "truth[%lld, %lld] = %g is infinite: NaN marks a missing observation", c / hz, c % hz, (double)v);
+        if (v == v) { const size_t r = (size_t)(c / hz); klist[r * hz + nk[r]++] = (int)(c % hz); ++n_finite; }
+    }
+    if (n_finite == 0) return fail(-1, "truth holds no finite entry: nothing to score");
+    if (s.n_levels < 0 || s.n_levels > CALIB_MAX_LEVELS) return fail(-1, "n_levels = %d outside [0, %d]", s.n_levels, CALIB_MAX_LEVELS);
+    if (s.n_levels > 0 && (!s.levels_p || !s.levels_z || !s.quantiles))
+        return fail(-1, "n_levels = %d needs levels_p, levels_z and quantiles", s.n_levels);
+    if (s.quantiles && s.n_levels == 0) return fail(-1, "quantiles requested without levels");
+    for (int k = 0; k < s.n_levels; ++k)
+        if (!(s.levels_p[k] > 0.0 && s.levels_p[k] < 1.0) || !std::isfinite(s.levels_z[k]))
+            return fail(-1, "levels_p[%d] = %g (levels_z %g): a quantile level lies in (0, 1)", k, s.levels_p[k], s.levels_z[k]);
+    if (s.crps && !pair) return fail(-1, "crps requested without pair_term");
+    if (s.energy_score && !energy) return fail(-1, "energy_score requested without energy");
+    if (energy && hz > PTNN_FSCORE_MAX_ENERGY_HORIZON)
+        return fail(-1, "energy: horizon = %d, the energy score takes paths of at most %d steps (energy=False)", hz, PTNN_FSCORE_MAX_ENERGY_HORIZON);
+    if (noise && host_src && !s.eta) return fail(-1, "noise: host vectors need eta = log tau^2 (one per vector)");
+    if (int rc = count_host_samples(src)) return rc;
+    if (int rc = check_handle(h, "ptnn_forecast_score")) return rc;
+    if (h->cfg.task != PTNN_TASK_REG || h->cfg.n_out != 1)
+        return fail(-1, "forecast verification needs a regression net with n_out == 1 (a one-step map of one series); this handle is a "
+                        "%s net with n_out = %d", h->cfg.task == PTNN_TASK_REG ? "regression" : "classification", h->cfg.n_out);
+    const int I = h->cfg.n_in, P = h->P;
+    if (int rc = need_eta(h, src)) return rc;
+    if (int rc = fit_rows(h, rows)) return rc;
+    if (int rc = select_samples(h, src, true)) return rc;
+    const long long M = src.M;
+    if (s.n_samples) *s.n_samples = M;
+    const char* cap_text = "%lld trajectories: the pair term of the CRPS and the energy score take at most %d (U^2 / 2 terms per column or "
+                           "origin); select fewer samples (thin=, chains=) or leave them out (crps=False, energy=False)";
+    if ((pair || energy) && noise && M > CALIB_MAX_DISTINCT) return fail(-1, cap_text, M, CALIB_MAX_DISTINCT);
+
+    if (int rc = start_device(h)) return rc;
+    hipStream_t st = h->stream;
+    DeviceScratch mem;
+    const float* d_x = nullptr;
+    int xs = 0;
+    if (int rc = upload_rows(h, mem, rows, I, &d_x, &xs)) return rc;
+    // stage a, as ptnn_forecast: noise on -- every occurrence its own trajectory, host multiplicities expanded; noise off -- the
+    // distinct (w, eta) samples with their multiplicities
+    std::vector<float> w_exp, eta_exp;
+    if (noise && host_src && s.multiplicity) {
+        w_exp.reserve((size_t)M * P);
+        eta_exp.reserve((size_t)M);
+        for (int64_t k = 0; k < s.n_w; ++k)
+            for (int c = 0; c < s.multiplicity[k]; ++c) {
+                w_exp.insert(w_exp.end(), s.w + (size_t)k * P, s.w + (size_t)(k + 1) * P);
+                eta_exp.push_back(s.eta[k]);
+            }
+        src.w = w_exp.data(); src.eta = eta_exp.data(); src.multiplicity = nullptr;
+        src.n_items = M;
+    }
+    Distinct d;
+    if (int rc = distinct_samples(h, mem, src, true, !noise, &d)) return rc;
+    const int U = d.U;
+    if (s.n_trajectories) *s.n_trajectories = U;
+    if ((pair || energy) && U > CALIB_MAX_DISTINCT) return fail(-1, cap_text, (long long)U, CALIB_MAX_DISTINCT);
+    // blocks: 4 U bytes per column for the paths, as much again for mu when the noise makes them differ.  With the energy score a
+    // block is whole origins; else origins and horizon steps as ptnn_forecast blocks them (the windows carried)
+    const size_t budget = scratch_budget("PTNN_FSCORE_SCRATCH_BYTES");
+    const size_t col_bytes = (size_t)U * sizeof(float) * (noise ? 2 : 1);
+    long long ob = 1, hb = hz;
+    if (budget >= col_bytes * hz) {
+        ob = std::max(1LL, std::min<long long>((long long)(budget / (col_bytes * hz)), n_org));
+    } else {
+        if (energy)
+            return fail(-1, "energy: one origin's %d steps of %d trajectories need %zu bytes of scratch, PTNN_FSCORE_SCRATCH_BYTES allows %zu "
+                            "(energy=False scores the steps in blocks)", hz, U, col_bytes * hz, budget);
+        const long long fit = (long long)(budget / col_bytes) - I;
+        hb = std::max(1LL, std::min<long long>(fit, hz));
+    }
+    hb = std::min<long long>(hb, 65535LL);                                  // a block's columns are grid.y of calib_pair_kernel
+    ob = std::min<long long>({ob, 65535LL * WAVE, std::max(1LL, 65535LL / hb)});
+    const bool split_h = hb < hz;
+    float *d_fx = nullptr, *d_mu = nullptr, *d_win = nullptr, *d_truth = nullptr;
+    HIP_TRY(mem.alloc(&d_fx, (size_t)ob * hb * U));
+    if (noise) HIP_TRY(mem.alloc(&d_mu, (size_t)ob * hb * U));
+    if (split_h) HIP_TRY(mem.alloc(&d_win, (size_t)U * I));
+    HIP_TRY(mem.upload(&d_truth, s.truth, (size_t)ncols, st));
+    const int layout = P <= FC_LANE_MAX_P ? FC_LANE : FC_SPLIT;
+    const size_t lds = layout == FC_LANE ? (size_t)(FC_THREADS / WAVE) * P * WAVE * sizeof(float)
+                                         : (size_t)(round_up4(P) + 2 * (FC_THREADS / WAVE) * WAVE) * sizeof(float);
+    if (lds > LDS_CEILING) return fail(-3, "forecast: a %d-parameter vector does not fit in LDS", P);
+    if (int rc = raise_lds_limit(reinterpret_cast<const void*>(h->shape->forecast_fwd), lds)) return rc;
+    std::vector<int> item_run;
+    if (s.samples || s.means) if (int rc = item_runs(h, d, src.n_items, &item_run)) return rc;
+    // per-column and per-origin results: NaN (all bits set) wherever nothing is scored
+    double *d_tau2 = nullptr, *d_tau = nullptr, *d_itau = nullptr;
+    double *d_pit = nullptr, *d_crps = nullptr, *d_log = nullptr, *d_mean = nullptr, *d_sd = nullptr, *d_q = nullptr, *d_t1 = nullptr, *d_bound = nullptr;
+    double *d_es = nullptr, *d_et1 = nullptr, *d_eb = nullptr;
+    unsigned long long *d_limbs = nullptr, *d_elimbs = nullptr;
+    int *d_klist = nullptr, *d_nk = nullptr;
+    const auto nan_doubles = [&](double** p, size_t n) -> hipError_t {
+        const hipError_t e = mem.alloc(p, n);
+        return e != hipSuccess ? e : hipMemsetAsync(*p, 0xff, n * sizeof(double), st);
+    };
+    HIP_TRY(mem.alloc(&d_tau2, (size_t)U));
+    HIP_TRY(mem.alloc(&d_tau, (size_t)U));
+    HIP_TRY(mem.alloc(&d_itau, (size_t)U));
+    HIP_TRY(nan_doubles(&d_pit, (size_t)ncols));
+    HIP_TRY(nan_doubles(&d_mean, (size_t)ncols));
+    HIP_TRY(nan_doubles(&d_sd, (size_t)ncols));
+    HIP_TRY(nan_doubles(&d_log, (size_t)ncols));
+    if (s.n_levels) HIP_TRY(nan_doubles(&d_q, (size_t)s.n_levels * ncols));
+    if (pair) {
+        HIP_TRY(nan_doubles(&d_crps, (size_t)ncols));
+        HIP_TRY(nan_doubles(&d_t1, (size_t)ncols));
+        HIP_TRY(nan_doubles(&d_bound, (size_t)ncols));
+        HIP_TRY(mem.alloc(&d_limbs, (size_t)ncols * 4));
+        HIP_TRY(hipMemsetAsync(d_limbs, 0, (size_t)ncols * 4 * sizeof(unsigned long long), st));
+    }
+    const int n_tiles = (U + CALIB_THREADS - 1) / CALIB_THREADS;
+    const unsigned n_tri = (unsigned)((long long)n_tiles * (n_tiles + 1) / 2);
+    FscoreEnergy ea{};
+    size_t e_lds = 0;
+    if (energy) {
+        HIP_TRY(nan_doubles(&d_es, (size_t)n_org));
+        HIP_TRY(nan_doubles(&d_et1, (size_t)n_org));
+        HIP_TRY(nan_doubles(&d_eb, (size_t)n_org));
+        HIP_TRY(mem.alloc(&d_elimbs, (size_t)n_org * 4));
+        HIP_TRY(hipMemsetAsync(d_elimbs, 0, (size_t)n_org * 4 * sizeof(unsigned long long), st));
+        HIP_TRY(mem.upload(&d_klist, klist.data(), klist.size(), st));
+        HIP_TRY(mem.upload(&d_nk, nk.data(), nk.size(), st));
+        int JW = FSCORE_THREADS;                        // the j-paths staged at a time: all steps of JW paths within FSCORE_ENERGY_LDS
+        while (JW > FSCORE_JGROUP && (size_t)JW * hz * sizeof(float) > (size_t)FSCORE_ENERGY_LDS) JW >>= 1;
+        e_lds = (size_t)JW * hz * sizeof(float);
+        if (int rc = raise_lds_limit(reinterpret_cast<const void*>(fscore_energy_kernel), e_lds)) return rc;
+        ea.fx = d_fx; ea.cnt = d.run_cnt; ea.y = d_truth; ea.klist = d_klist; ea.nk = d_nk; ea.U = U; ea.hz = hz; ea.S = M;
+        ea.term1 = d_et1; ea.bound = d_eb; ea.n_tiles = n_tiles; ea.JW = JW; ea.limbs = d_elimbs;
+    }
+    HIP_TRY(launch(calib_tau_kernel, dim3((unsigned)((U + CALIB_THREADS - 1) / CALIB_THREADS)), dim3(CALIB_THREADS), 0, st, U, d.run_eta,
+                   d_tau2, d_tau, d_itau));
+    const float* d_m = noise ? d_mu : d_fx;            // mu of the block's columns
+    CalibRow ra{};
+    ra.fx = d_m; ra.tau2 = d_tau2; ra.tau = d_tau; ra.itau = d_itau; ra.cnt = d.run_cnt; ra.y = d_truth; ra.ys = 1; ra.U = U;
+    ra.n_rows = (int)ncols; ra.S = M; ra.n_levels = s.n_levels; ra.pair = pair ? 1 : 0; ra.skip_nan = 1;
+    for (int k = 0; k < s.n_levels; ++k) { ra.p[k] = s.levels_p[k]; ra.z[k] = s.levels_z[k]; }
+    ra.pit = d_pit; ra.pred_mean = d_mean; ra.pred_sd = d_sd; ra.quantiles = d_q; ra.term1 = d_t1; ra.pair_bound = d_bound;
+    CalibPair pa{d_m, d_tau2, d.run_cnt, d_bound, U, 0, 0, n_tiles, d_limbs, d_truth};
+    FscoreLog la{d_m, d.run_eta, d.run_cnt, d_truth, U, 0, M, d_log};
+    ForecastFwd fa{};
+    fa.base = d.base; fa.run_off = d.run_off; fa.eta = d.run_eta; fa.x = d_x; fa.xs = xs; fa.horizon = hz; fa.win = d_win;
+    fa.H = h->cfg.n_hidden; fa.P = P; fa.U = U; fa.layout = layout; fa.noise = noise ? 1 : 0;
+    fa.fx = d_fx; fa.mu = d_mu;
+    split_seed(s.seed, &fa.seed_lo, &fa.seed_hi);
+    for (long long r0 = 0; r0 < n_org; r0 += ob) {
+        const int nr = (int)std::min<long long>(ob, n_org - r0);
+        for (long long k0 = 0; k0 < hz; k0 += hb) {
+            const int nk_blk = (int)std::min<long long>(hb, hz - k0);
+            fa.r0 = (int)r0; fa.nr = nr; fa.k0 = (int)k0; fa.hb = nk_blk;
+            dim3 grid;
+            if (layout == FC_LANE) {
+                const long long gx = (U + FC_THREADS - 1) / FC_THREADS;
+                grid = dim3((unsigned)gx, (unsigned)std::max(1LL, std::min<long long>((512 + gx - 1) / gx, nr)));
+            } else {
+                grid = dim3((unsigned)U, (unsigned)((nr + WAVE - 1) / WAVE));
+            }
+            HIP_TRY(launch(h->shape->forecast_fwd, grid, dim3(FC_THREADS), lds, st, fa));
+            const long long col0 = r0 * hz + k0;             // the block's columns are contiguous (split_h: one origin per block)
+            const int nc = nr * nk_blk;                      // <= 65535
+            ra.row0 = (int)col0;
+            HIP_TRY(launch(calib_row_kernel, dim3((unsigned)nc), dim3(CALIB_THREADS), 0, st, ra));
+            if (pair) {
+                pa.row0 = (int)col0; pa.r0 = 0;
+                HIP_TRY(launch(calib_pair_kernel, dim3(n_tri, (unsigned)nc), dim3(CALIB_THREADS), 0, st, pa));
+            }
+            la.col0 = (int)col0;
+            HIP_TRY(launch(fscore_logscore_kernel, dim3((unsigned)nc), dim3(FSCORE_THREADS), 0, st, la));
+            if (energy) {                                    // hb == hz: whole origins
+                ea.r0 = (int)r0;
+                HIP_TRY(launch(fscore_energy_first_kernel, dim3((unsigned)nr), dim3(FSCORE_THREADS), 0, st, ea));
+                HIP_TRY(launch(fscore_energy_kernel, dim3(n_tri, (unsigned)nr), dim3(FSCORE_THREADS), e_lds, st, ea));
+            }
+            if (s.samples)
+                if (int rc = scatter_samples(h, d_fx, nc, U, item_run, src.weights(), s.samples, (size_t)ncols, (size_t)col0)) return rc;
+            if (s.means)
+                if (int rc = scatter_samples(h, d_m, nc, U, item_run, src.weights(), s.means, (size_t)ncols, (size_t)col0)) return rc;
+        }
+    }
+    if (pair)
+        HIP_TRY(launch(calib_finish_kernel, dim3((unsigned)((ncols + CALIB_THREADS - 1) / CALIB_THREADS)), dim3(CALIB_THREADS), 0, st, (int)ncols,
+                       d_limbs, d_t1, d_bound, M, d_crps));
+    if (energy)
+        HIP_TRY(launch(fscore_energy_finish_kernel, dim3((unsigned)((n_org + FSCORE_THREADS - 1) / FSCORE_THREADS)), dim3(FSCORE_THREADS), 0, st,
+                       n_org, d_nk, d_elimbs, d_et1, d_eb, M, d_es));
+    HIP_TRY(fetch(s.pit, d_pit, (size_t)ncols, st));
+    HIP_TRY(fetch(s.pred_mean, d_mean, (size_t)ncols, st));
+    HIP_TRY(fetch(s.pred_sd, d_sd, (size_t)ncols, st));
+    HIP_TRY(fetch(s.log_score, d_log, (size_t)ncols, st));
+    HIP_TRY(fetch(s.quantiles, d_q, (size_t)s.n_levels * ncols, st));
+    HIP_TRY(fetch(s.crps, d_crps, (size_t)ncols, st));
+    HIP_TRY(fetch(s.energy_score, d_es, (size_t)n_org, st));
     return wait_stream(h);
 }
 

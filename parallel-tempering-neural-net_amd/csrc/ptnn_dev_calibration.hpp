@@ -60,6 +60,7 @@ struct CalibRow {
     double* quantiles;          // [n_levels][n_rows]
     double* term1;              // [n_rows] (1/S) sum c A(y - f, tau^2)
     double* pair_bound;         // [n_rows] B >= every A(f_s - f_t, tau_s^2 + tau_t^2) of the row
+    int skip_nan;               // ptnn_forecast_score: a row whose target is NaN (no truth) is left alone, its outputs untouched
 };
 
 __global__ void __launch_bounds__(CALIB_THREADS) calib_row_kernel(const CalibRow a) {
@@ -67,6 +68,7 @@ __global__ void __launch_bounds__(CALIB_THREADS) calib_row_kernel(const CalibRow
     const int tid = threadIdx.x, r = blockIdx.x, n = a.row0 + r;
     const float* f = a.fx + (size_t)r * a.U;
     const double y = (double)a.y[(size_t)n * a.ys];
+    if (a.skip_nan && !(y == y)) return;                       // uniform over the work-group, before any barrier
     const double S = (double)a.S;
     const double INF = __longlong_as_double(0x7ff0000000000000ll);
 
@@ -150,6 +152,7 @@ struct CalibPair {
     int U, row0, r0;            // r0: first row of this launch inside the block
     int n_tiles;                // ceil(U / CALIB_THREADS)
     unsigned long long* limbs;  // [n_rows][4] sum c_s c_t floor(A / B 2^62), 32 bits per word (zeroed by the caller)
+    const float* y_skip;        // ptnn_forecast_score: targets [n_rows], a row whose target is NaN is left alone; else null
 };
 
 // grid: x = tile pairs (ti >= tj) of the triangle, y = rows.  Lane = one i-sample in registers; the j-tile in LDS, read as
@@ -160,6 +163,7 @@ __global__ void __launch_bounds__(CALIB_THREADS) calib_pair_kernel(const CalibPa
     __shared__ CalibShared sh;
     const int tid = threadIdx.x;
     const int r = a.r0 + blockIdx.y, n = a.row0 + r;
+    if (a.y_skip && !(a.y_skip[n] == a.y_skip[n])) return;     // uniform over the work-group, before any barrier
     // tile pair p -> (ti, tj), tj <= ti: p = ti (ti + 1) / 2 + tj
     const unsigned p = blockIdx.x;
     int ti = (int)((sqrt(8.0 * (double)p + 1.0) - 1.0) * 0.5);

@@ -5,6 +5,7 @@
 //      trajectory each); noise on -- sample_runs_kernel with the eta (every occurrence its own trajectory).  Both unchanged.
 //   b. forecast_forward_kernel<TASK, I, O> (per shape, Shape::forecast_fwd): fx[col][u] = y of trajectory u at column
 //      col = origin * hb + k of a block of origins and horizon steps; the windows are carried from one horizon block to the next.
+//      With ForecastFwd::mu (ptnn_forecast_score) it also stores the output before the step's noise.
 //   c. predict_reduce_kernel, unchanged.
 // The forward pass is ptnn_predict's, operation for operation: four partial sums over h = wave (mod 4), each accumulated in
 // ascending h, combined in the order 0, 1, 2, 3, then the output sigmoid -- so step 1 is bit-identical to ptnn_predict on the
@@ -29,6 +30,7 @@ struct ForecastFwd {
     int noise;
     uint32_t seed_lo, seed_hi;
     float* fx;                  // [nr * hb][U] column-major, column (r - r0) * hb + (k - k0)
+    float* mu;                  // [nr * hb][U] as fx: the sigmoid output before the step's noise is added (ptnn_forecast_score), or null
 };
 
 // z_k of trajectory i at origin r: normals(k + 1, i, r, STREAM_FORECAST, seed)[k] of philox.py
@@ -105,6 +107,7 @@ __global__ void __launch_bounds__(FC_THREADS) forecast_forward_kernel(const Fore
 #pragma unroll
                     for (int w = 1; w < NWAVE; ++w) s += acc[w];
                     float y = 1.0f / (1.0f + expf(-(s - B2)));                                           // Q2
+                    if (a.mu && live_u) a.mu[((size_t)rl * a.hb + (k - a.k0)) * U + u] = y;
                     if (a.noise) {
                         if (k == a.k0 || (k & 3) == 0) forecast_normals(k, u, r, a.seed_lo, a.seed_hi, z);
                         y = y + sd * forecast_pick(z, k);
@@ -167,6 +170,7 @@ __global__ void __launch_bounds__(FC_THREADS) forecast_forward_kernel(const Fore
                 for (int w = 1; w < NWAVE; ++w) s += red[(buf * NWAVE + w) * WAVE + lane];
                 buf ^= 1;
                 float y = 1.0f / (1.0f + expf(-(s - B2)));
+                if (a.mu && wave == 0 && live) a.mu[((size_t)rl * a.hb + (k - a.k0)) * U + u] = y;
                 if (a.noise) {
                     if (k == a.k0 || (k & 3) == 0) forecast_normals(k, u, r, a.seed_lo, a.seed_hi, z);
                     y = y + sd * forecast_pick(z, k);

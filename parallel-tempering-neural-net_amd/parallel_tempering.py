@@ -38,6 +38,11 @@ from .effects import PartialDependence, pd_grid  # noqa: F401
 # the classification report lives in report.py; the result tuple and its host helpers are importable from here
 from .report import ReportAnalysis
 from .report import ClassificationReport, auc_pairs, confusion_matrix, report_names, roc_curve, scores_from_confusion  # noqa: F401
+# forecast verification lives in verification.py; the result tuple, forecast_compare and the host helpers are importable from here
+from .verification import VerificationAnalysis
+from .verification import (  # noqa: F401
+    ForecastAccuracy, crps_gaussian, energy_score_ensemble, forecast_baselines, forecast_compare, forecast_skill, horizon_summary,
+    series_from_windows, windows_and_truth)
 
 
 def _text_round(a, fmt, threads=8):
@@ -131,7 +136,7 @@ def overlap_cuts(S, swap_interval, chunks):
     return sorted({min(S - 1, si * max(1, round(n_int * (c + 1) / K))) for c in range(K - 1)} | {S - 1})
 
 
-class ParallelTemperingBase(PosteriorAnalysis, PriorAnalysis, EffectAnalysis, ReportAnalysis):
+class ParallelTemperingBase(PosteriorAnalysis, PriorAnalysis, EffectAnalysis, ReportAnalysis, VerificationAnalysis):
     task = None                       # set by the two drop-in subclasses
     rmse_fmt = None                   # REG '%1.8f' (REG:462-464), CLS '%1.2f' (CLS:473-475)
 
