@@ -1168,6 +1168,62 @@ typedef struct ptnn_class_report_spec {
 
 int ptnn_class_report(ptnn_handle *h, const ptnn_class_report_spec *spec);
 
+/* ---- predictive uncertainty: aleatoric and epistemic (nothing in the reference) ----
+ * How uncertain the sampled nets are on a data row, and whether that is noise in the data or disagreement among the nets;
+ * DESIGN.md section 28.  Samples: the expanded multiset of S selected rows, U distinct vectors with integer counts c_u,
+ * selected, merged and refused exactly as ptnn_calibration's sources 1 and 2 (same rules and error texts: a regression's host
+ * vectors need eta, trace rows without a recorded eta are refused).  p_u[n, k] / f_u[n, o] = the fp32 outputs of ptnn_predict's
+ * forward pass; everything after it is double.  Rows: x_source _TRAIN / _TEST or _HOST with x [n_rows, n_in], as ptnn_predict;
+ * no target is read.
+ * Both tasks: mean [n_rows, n_out] = (1/S) sum c_u output_u, bitwise ptnn_predict's mean for the same selection.
+ * Classification (K = n_out), per row n, natural log, 0 log 0 = 0: vote [n_rows, K], bitwise ptnn_predict's;
+ * H_u[n] = -sum_k p_u[n, k] log p_u[n, k], each product and each sum rounded once, terms added in class order;
+ * entropy_mean[n] = (1/S) sum c_u H_u[n], the expected entropy (the aleatoric part), an exact fixed-point sum of the terms
+ * H_u / log K clamped to [0, 1] (fp32 probabilities may sum to a little over 1 and carry H_u an fp32 rounding above log K: such
+ * a term counts as log K); entropy_order_stats [n_ranks, n_rows] = exact fp32 order statistics of (float)H_u[n] over the expanded
+ * multiset (n_ranks <= 16, 0 <= rank < S); sample_entropy [S, n_rows] fp32 = (float)H_u[n], chain-major.
+ * Regression, per row n and output o: epistemic_var [n_rows, n_out] = (1/S) sum c_u (f_u - mean)^2 in two passes, centred on
+ * the mean above: an exact fixed-point sum of the terms d^2 / R^2 with R the range of f over the samples (R = 0: exactly 0);
+ * aleatoric_var [1] = (1/S) sum c_u exp((double)eta_u), an exact sum of the terms exp(eta_u) / max_u exp(eta_u).
+ * entropy_mean, epistemic_var and aleatoric_var depend on the multiset of samples only (bitwise: trace, host vectors, expanded or
+ * (distinct, multiplicity), any block size).
+ * Outputs, any may be NULL.  Refused: vote or an entropy output on a regression; a variance output on a classification;
+ * n_ranks > 16 or a rank outside [0, S); n_rows < 1.
+ * Runs on the handle's stream behind everything queued and returns when done; rows are processed in blocks whose scratch stays
+ * under $PTNN_UNC_SCRATCH_BYTES (read per call, default 1 GiB) and of at most 65535 x 64 rows, which changes no result.
+ * Touches no chain state, tape, counter or trace row.  Not with a communicator attached (one GPU only). */
+typedef struct ptnn_uncertainty_spec {
+    int32_t struct_bytes;         /* = sizeof(ptnn_uncertainty_spec): ABI guard */
+    /* source 1: the trace (used when w == NULL) */
+    const int32_t *replicas;      /* local replica indices, or NULL = all */
+    int32_t n_replicas;           /* entries of replicas (ignored when NULL) */
+    int32_t step0, nsteps, thin;  /* trace rows step0, step0 + thin, ... < step0 + nsteps (thin >= 1) */
+    /* source 2: host vectors */
+    const float *w;               /* [n_w, P] or NULL */
+    const float *eta;             /* [n_w] log tau^2 (regression) */
+    const int32_t *multiplicity;  /* [n_w] >= 0, or NULL = 1 each */
+    int64_t n_w;
+    /* data */
+    int32_t x_source;             /* PTNN_PREDICT_X_HOST | _TRAIN | _TEST */
+    int32_t n_rows;
+    const float *x;               /* [n_rows, n_in] (host rows only) */
+    /* order statistics of the per-sample entropy (classification) */
+    const int64_t *ranks;         /* [n_ranks] */
+    int32_t n_ranks;
+    int32_t reserved_;
+    /* outputs */
+    double *mean;                 /* [n_rows, n_out] */
+    double *vote;                 /* [n_rows, n_out] (classification) */
+    double *entropy_mean;         /* [n_rows] (classification) */
+    float *entropy_order_stats;   /* [n_ranks, n_rows] (classification) */
+    float *sample_entropy;        /* [S, n_rows] (classification) */
+    double *epistemic_var;        /* [n_rows, n_out] (regression) */
+    double *aleatoric_var;        /* [1] (regression) */
+    int64_t *n_samples, *n_distinct;
+} ptnn_uncertainty_spec;
+
+int ptnn_uncertainty(ptnn_handle *h, const ptnn_uncertainty_spec *spec);
+
 /* the HIP stream (hipStream_t) all of this handle's work is queued on: lets the caller order its collectives after the
  * segment / before the swap kernels on the device instead of synchronising the host */
 int ptnn_stream(ptnn_handle *h, void **hip_stream);

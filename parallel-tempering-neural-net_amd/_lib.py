@@ -275,6 +275,19 @@ class ClassReportSpec(C.Structure):
 REPORT_MAX_AUC_ROWS = 16384
 
 
+class UncertaintySpec(C.Structure):
+    """ptnn_uncertainty_spec (include/ptnn.h)."""
+    _fields_ = _SELECTION + [
+        ("w", C.POINTER(C.c_float)), ("eta", C.POINTER(C.c_float)), ("multiplicity", C.POINTER(C.c_int32)), ("n_w", C.c_int64),
+        ("x_source", C.c_int32), ("n_rows", C.c_int32), ("x", C.POINTER(C.c_float)),
+        ("ranks", C.POINTER(C.c_int64)), ("n_ranks", C.c_int32), ("reserved_", C.c_int32),
+        ("mean", C.POINTER(C.c_double)), ("vote", C.POINTER(C.c_double)), ("entropy_mean", C.POINTER(C.c_double)),
+        ("entropy_order_stats", C.POINTER(C.c_float)), ("sample_entropy", C.POINTER(C.c_float)),
+        ("epistemic_var", C.POINTER(C.c_double)), ("aleatoric_var", C.POINTER(C.c_double)),
+        ("n_samples", C.POINTER(C.c_int64)), ("n_distinct", C.POINTER(C.c_int64)),
+    ]
+
+
 class LadderAdaptSpec(C.Structure):
     """ptnn_ladder_adapt_spec (include/ptnn.h)."""
     _fields_ = [("struct_bytes", C.c_int32), ("rounds", C.c_int32), ("kappa0", C.c_double), ("t0", C.c_double)]
@@ -375,6 +388,7 @@ SYMBOLS = {
     "ptnn_powerscale": (C.c_int, [C.c_void_p, C.POINTER(PowerscaleSpec)]),
     "ptnn_prior_predictive": (C.c_int, [C.c_void_p, C.POINTER(PriorSpec)]),
     "ptnn_class_report": (C.c_int, [C.c_void_p, C.POINTER(ClassReportSpec)]),
+    "ptnn_uncertainty": (C.c_int, [C.c_void_p, C.POINTER(UncertaintySpec)]),
 }
 
 
@@ -1030,6 +1044,36 @@ class Sampler:
                    sample_confusion=np.empty((max(S, 0), K, K), np.int32) if sample_confusion else None)
         _bind(spec, out)
         return self._call(self.lib.ptnn_class_report, spec, out)
+
+    def uncertainty(self, x="test", *, replicas=None, step0=0, nsteps=None, thin=1, w=None, eta=None, multiplicity=None, ranks=(),
+                    samples=False):
+        """ptnn_uncertainty: the predictive uncertainty of every row split into its aleatoric and epistemic part, on the device.
+        Source: the trace rows step0, step0 + thin, ... < step0 + nsteps of `replicas` (None = all), or host vectors w [n, P]
+        with eta [n] (regression) and optional integer `multiplicity` [n].  x: "train", "test" or rows [n_rows, n_in].
+        Classification -> dict(mean, vote [n_rows, K] float64 (ptnn_predict's), entropy_mean [n_rows] float64 (the expected
+        entropy of a sample's class probabilities), entropy_order_stats [len(ranks), n_rows] float32 (exact values of those
+        0-based ranks of the per-sample entropies), sample_entropy [S, n_rows] float32 (samples=True)); regression ->
+        dict(mean, epistemic_var [n_rows, n_out] float64, aleatoric_var float); both n_samples, n_distinct; what does not
+        apply or was not asked for is None."""
+        spec, keep = _spec(UncertaintySpec), []
+        self._rows(spec, keep, x, "x", (self.cfg.n_in, "n_in columns"))
+        n_rows, O = spec.n_rows, self.cfg.n_out
+        S = self._samples(spec, keep, w=w, eta=eta, multiplicity=multiplicity, replicas=replicas, step0=step0, nsteps=nsteps, thin=thin,
+                          unit="sample")
+        out = dict(mean=np.empty((n_rows, O), np.float64), vote=None, entropy_mean=None, entropy_order_stats=None, sample_entropy=None,
+                   epistemic_var=None, aleatoric_var=None)
+        if self.cfg.task == TASK_REG:
+            out.update(epistemic_var=np.empty((n_rows, O), np.float64), aleatoric_var=np.empty(1, np.float64))
+        else:
+            n_rk = _ranks(spec, keep, ranks)
+            out.update(vote=np.empty((n_rows, O), np.float64), entropy_mean=np.empty(n_rows, np.float64),
+                       entropy_order_stats=np.empty((n_rk, n_rows), np.float32) if n_rk else None,
+                       sample_entropy=np.empty((max(S, 0), n_rows), np.float32) if samples else None)
+        _bind(spec, out)
+        self._call(self.lib.ptnn_uncertainty, spec, out)
+        if out["aleatoric_var"] is not None:
+            out["aleatoric_var"] = float(out["aleatoric_var"][0])
+        return out
 
     def sensitivity(self, x="test", *, replicas=None, step0=0, nsteps=None, thin=1, w=None, multiplicity=None, ranks=(), ranks2=(),
                     sample_abs=False, samples=False):

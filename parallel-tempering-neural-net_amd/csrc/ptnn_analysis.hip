@@ -19,6 +19,7 @@ namespace ptnn {
 #define PTNN_PD_REDUCTIONS
 #include "ptnn_dev_pd.hpp"                   // partial dependence, second part: row sums, ranges and the weighted means of the row means
 #include "ptnn_dev_report.hpp"               // classification report: confusion counts, Mann-Whitney counts and metric columns per sample
+#include "ptnn_dev_uncertainty.hpp"          // predictive uncertainty: entropy per sample and its mean per row, variance per column, mean noise
 }  // namespace ptnn
 #include "ptnn_host.hpp"
 #include "ptnn_rank_plan.hpp"               // the blocks of ptnn_rank_convergence: host arithmetic, checked on its own
@@ -2620,6 +2621,100 @@ int ptnn_class_report(ptnn_handle* h, const ptnn_class_report_spec* spec) {
         if (label_h[(size_t)n] < 0) return fail(-2, "row %d of the handle's data has no class in [0, %d) (internal error)", n, K);
     for (int c = 0; s.vote && c < ncols; ++c) s.vote[c] = (double)votes_h[(size_t)c] / (double)M;
     for (int n = 0; s.p_correct && n < N; ++n) s.p_correct[n] = (double)votes_h[(size_t)n * K + label_h[(size_t)n]] / (double)M;
+    return 0;
+}
+
+// ---- predictive uncertainty (ptnn_dev_uncertainty.hpp) ----
+int ptnn_uncertainty(ptnn_handle* h, const ptnn_uncertainty_spec* spec) {
+    // argument checks first: none of them needs the handle or a device
+    if (int rc = check_spec(spec, "ptnn_uncertainty_spec")) return rc;
+    const ptnn_uncertainty_spec& s = *spec;
+    SampleSource src = source_of(s, s.w != nullptr, s.eta);
+    const RowSource rows{s.x_source, s.x, s.n_rows, "x_source", "PTNN_PREDICT_X", "x", "n_rows"};
+    RankOutputs rk{s.n_ranks, s.ranks, s.entropy_order_stats};
+    if (int rc = check_source(src, "samples", true)) return rc;
+    if (int rc = check_rows(rows)) return rc;
+    if (s.n_rows < 1) return fail(-1, "n_rows = %d must be >= 1", s.n_rows);
+    if (int rc = rk.check()) return rc;
+    if (int rc = count_host_samples(src)) return rc;
+    if (int rc = check_handle(h, "ptnn_uncertainty")) return rc;
+    const int I = h->cfg.n_in, O = h->cfg.n_out, N = s.n_rows;
+    const bool reg = h->cfg.task == PTNN_TASK_REG;
+    if (reg && (s.vote || s.entropy_mean || s.entropy_order_stats || s.sample_entropy))
+        return fail(-1, "vote, entropy_mean, entropy_order_stats and sample_entropy: a regression has no class probabilities");
+    if (!reg && (s.epistemic_var || s.aleatoric_var))
+        return fail(-1, "epistemic_var and aleatoric_var: a classification has no output variance and no eta");
+    if (int rc = need_eta(h, src)) return rc;
+    if (int rc = fit_rows(h, rows)) return rc;
+    if (int rc = select_samples(h, src, true)) return rc;
+    const long long S = src.M;
+    if (int rc = rk.check_values(S)) return rc;
+    if (s.n_samples) *s.n_samples = S;
+
+    if (int rc = start_device(h)) return rc;
+    hipStream_t st = h->stream;
+    DeviceScratch mem;
+    const int ncols = N * O;
+    const float* d_x = nullptr;
+    int xs = 0;
+    if (int rc = upload_rows(h, mem, rows, I, &d_x, &xs)) return rc;
+    // stage a: items -> distinct (w, eta) samples (a classification's: distinct w, as ptnn_predict's)
+    Distinct d;
+    if (int rc = distinct_samples(h, mem, src, reg, true, &d)) return rc;
+    const int U = d.U;
+    if (s.n_distinct) *s.n_distinct = U;
+    // the pooled outputs of every column as ptnn_predict's; then per row the entropies, or per column the variance
+    const bool image = !reg && (s.n_ranks > 0 || s.sample_entropy);
+    double *d_mean = nullptr, *d_hmean = nullptr, *d_emean = nullptr, *d_var = nullptr, *d_noise = nullptr;
+    long long* d_votes = nullptr;
+    HIP_TRY(mem.alloc(&d_mean, (size_t)ncols));
+    if (reg) {
+        HIP_TRY(mem.alloc(&d_var, (size_t)ncols));
+        HIP_TRY(mem.alloc(&d_noise, 1));
+        HIP_TRY(launch(unc_noise_kernel, dim3(1), dim3(UNC_THREADS), 0, st, U, d.run_eta, d.run_cnt, S, d_noise));
+    } else {
+        HIP_TRY(mem.alloc(&d_votes, (size_t)ncols));
+        HIP_TRY(mem.alloc(&d_emean, (size_t)N));
+        if (image) HIP_TRY(mem.alloc(&d_hmean, (size_t)N));     // predict_reduce_kernel's mean of the fp32 image: not an output
+        if (int rc = rk.to_device(mem, (size_t)N, st)) return rc;
+    }
+    // stage b + c in blocks of rows: the forward image U x (rows x O) floats, and the entropy image U x rows, under the budget
+    const long long rows_blk = row_block(scratch_budget("PTNN_UNC_SCRATCH_BYTES"), (size_t)U * sizeof(float) * (O + (image ? 1 : 0)), N);
+    float *d_fx = nullptr, *d_img = nullptr;
+    HIP_TRY(mem.alloc(&d_fx, (size_t)rows_blk * O * U));
+    if (image) HIP_TRY(mem.alloc(&d_img, (size_t)rows_blk * U));
+    ForwardPlan fwd;
+    if (int rc = fwd.init(h, "predictive uncertainty")) return rc;
+    std::vector<int> item_run;
+    if (!reg && s.sample_entropy)
+        if (int rc = item_runs(h, d, src.n_items, &item_run)) return rc;
+    const double log_k = O > 1 ? std::log((double)O) : 0.0;
+    if (int rc = each_block(N, rows_blk, [&](long long r0, int nr) -> int {
+        if (int rc = fwd.run(h, d.base, d.run_off, d_x, xs, (int)r0, nr, U, d_fx)) return rc;
+        PredictRed ra{d_fx, d.run_cnt, U, O, (int)r0 * O, ncols, S, 0, nullptr, d_mean, nullptr, d_votes};
+        HIP_TRY(launch(predict_reduce_kernel, dim3((unsigned)(nr * O)), dim3(PRED_THREADS), 0, st, ra));
+        if (reg) {
+            UncVariance va{d_fx, d.run_cnt, U, (int)r0 * O, S, d_mean, d_var};
+            HIP_TRY(launch(unc_variance_kernel, dim3((unsigned)(nr * O)), dim3(UNC_THREADS), 0, st, va));
+            return 0;
+        }
+        UncEntropy ea{d_fx, d.run_cnt, U, O, (int)r0, S, log_k, d_img, d_emean};
+        HIP_TRY(launch(unc_entropy_kernel, dim3((unsigned)nr), dim3(UNC_THREADS), 0, st, ea));
+        if (s.n_ranks > 0) {        // the order statistics of (float)H_u, as ptnn_predict reduces a column of outputs
+            PredictRed qa{d_img, d.run_cnt, U, 1, (int)r0, N, S, s.n_ranks, rk.d_ranks, d_hmean, rk.d_stats, nullptr};
+            HIP_TRY(launch(predict_reduce_kernel, dim3((unsigned)nr), dim3(PRED_THREADS), 0, st, qa));
+        }
+        return s.sample_entropy ? scatter_samples(h, d_img, nr, U, item_run, src.weights(), s.sample_entropy, (size_t)N, (size_t)r0) : 0;
+    })) return rc;
+    std::vector<long long> votes_h(s.vote ? (size_t)ncols : 0);
+    HIP_TRY(fetch(s.mean, d_mean, (size_t)ncols, st));
+    HIP_TRY(fetch(s.vote ? votes_h.data() : nullptr, d_votes, (size_t)ncols, st));
+    HIP_TRY(fetch(s.entropy_mean, d_emean, (size_t)N, st));
+    HIP_TRY(fetch(s.entropy_order_stats, rk.d_stats, (size_t)s.n_ranks * N, st));
+    HIP_TRY(fetch(s.epistemic_var, d_var, (size_t)ncols, st));
+    HIP_TRY(fetch(s.aleatoric_var, d_noise, 1, st));
+    if (int rc = wait_stream(h)) return rc;
+    for (int c = 0; s.vote && c < ncols; ++c) s.vote[c] = (double)votes_h[(size_t)c] / (double)S;
     return 0;
 }
 

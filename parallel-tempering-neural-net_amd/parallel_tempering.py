@@ -38,6 +38,9 @@ from .effects import PartialDependence, pd_grid  # noqa: F401
 # the classification report lives in report.py; the result tuple and its host helpers are importable from here
 from .report import ReportAnalysis
 from .report import ClassificationReport, auc_pairs, confusion_matrix, report_names, roc_curve, scores_from_confusion  # noqa: F401
+# predictive uncertainty lives in uncertainty.py; the result tuple and its host helpers are importable from here
+from .uncertainty import UncertaintyAnalysis
+from .uncertainty import Uncertainty, risk_coverage, uncertainty_compare, uncertainty_scores  # noqa: F401
 # forecast verification lives in verification.py; the result tuple, forecast_compare and the host helpers are importable from here
 from .verification import VerificationAnalysis
 from .verification import (  # noqa: F401
@@ -136,7 +139,7 @@ def overlap_cuts(S, swap_interval, chunks):
     return sorted({min(S - 1, si * max(1, round(n_int * (c + 1) / K))) for c in range(K - 1)} | {S - 1})
 
 
-class ParallelTemperingBase(PosteriorAnalysis, PriorAnalysis, EffectAnalysis, ReportAnalysis, VerificationAnalysis):
+class ParallelTemperingBase(PosteriorAnalysis, PriorAnalysis, EffectAnalysis, ReportAnalysis, UncertaintyAnalysis, VerificationAnalysis):
     task = None                       # set by the two drop-in subclasses
     rmse_fmt = None                   # REG '%1.8f' (REG:462-464), CLS '%1.2f' (CLS:473-475)
 
