@@ -876,6 +876,77 @@ typedef struct ptnn_pd_spec {
 
 int ptnn_partial_dependence(ptnn_handle *h, const ptnn_pd_spec *spec);
 
+/* ---- coalition values: Shapley attributions of the sampled nets (nothing in the reference: it never splits a prediction among
+ * its inputs) ----
+ * How much of one prediction each input accounts for, against a background sample (Shapley 1953; Strumbelj & Kononenko 2014;
+ * Lundberg & Lee 2017: the interventional value function), per sample, so that the attribution gets a posterior band.  f is the
+ * output ptnn_predict returns.  For a selected sample s, explained row x_n, background rows b_1 .. b_B and a coalition S given as
+ * a 64-bit mask (bit i set: input i is taken from the explained row):
+ *   h(x, b, S)_i   = x_i if i in S else b_i                     the hybrid row: exact fp32 values, a select
+ *   v_s[n, S, o]   = (1 / B) sum_b f_o(w_s; h(x_n, b, S))       f in fp32; the sum over b in double, in one fixed order
+ *   out_s[n, o, t] = sum_c coef[c, t] v_s[n, S_c, o]            c = 0 .. C - 1 in table order, in double, stored as fp32 once
+ * The library does not know what a Shapley value is: it gets the coalition table masks [n_coalitions] and coef [n_coalitions,
+ * n_terms] and evaluates n_terms linear functionals of the game (the Python front builds the exact and the permutation tables).
+ * DESIGN.md section 29.  Sample set and rows: exactly as ptnn_partial_dependence (the two sample sources, x_source / n_rows / x).
+ * background [n_background, n_in] host floats.  ranks / n_ranks apply to out, ranks2 / n_ranks2 to a_s.
+ * Outputs, any may be NULL, and an output costs device work only when its pointer is given.  With O = n_out, T = n_terms and
+ * column (n O + o) T + t: mean [n_rows, O, T] (the weighted mean of out, accumulated in double); order_stats [n_ranks, n_rows, O,
+ * T] = the exact fp32 value of 0-based rank ranks[k] among the M values (ptnn_predict's rule); pos_count, neg_count [n_rows, O, T]
+ * = the samples with out > 0 and out < 0.  Per (o, t), with a_s[o, t] = (1 / n_rows) sum_n |out_s[n, o, t]| (the row sums in
+ * double, ascending row order, carried across row blocks): abs_mean [O, T] = the weighted mean of a_s over the samples;
+ * abs_order_stats [n_ranks2, O, T] = the exact rank ranks2[k] of the fp32-rounded a_s; sample_abs [M, O, T] = every selected
+ * row's a_s as fp32, chain-major; samples [M, n_rows, O, T] = every selected row's out, chain-major; n_samples = M, n_distinct.
+ * Refused: what ptnn_sensitivity refuses; background NULL or a value that is not finite; n_background outside [1,
+ * PTNN_SHAP_MAX_BACKGROUND], n_coalitions outside [1, PTNN_SHAP_MAX_COALITIONS], n_terms outside [1, PTNN_SHAP_MAX_TERMS]; masks
+ * or coef NULL; a coefficient that is not finite; with the handle: n_terms x n_out > PTNN_SHAP_MAX_ACC, a mask with a bit at or
+ * above n_in, n_rows x n_out x n_terms > 2^31 - 1 columns, an empty selection, a rank outside [0, M).  Runs on the handle's
+ * stream behind everything queued and returns when done; rows are processed in blocks whose scratch (4 U n_out n_terms bytes per
+ * row) stays under $PTNN_SHAP_SCRATCH_BYTES (read per call, default 1 GiB), which changes no result.  Touches no chain state,
+ * tape, counter or trace row.  Not with a communicator attached (one GPU only). */
+#define PTNN_SHAP_MAX_COALITIONS 4096
+#define PTNN_SHAP_MAX_BACKGROUND 256
+#define PTNN_SHAP_MAX_TERMS 64
+#define PTNN_SHAP_MAX_ACC 256
+
+typedef struct ptnn_shapley_spec {
+    int32_t struct_bytes;         /* = sizeof(ptnn_shapley_spec): ABI guard */
+    /* source 1: the trace (used when w == NULL) */
+    const int32_t *replicas;      /* local replica indices, or NULL = all */
+    int32_t n_replicas;           /* entries of replicas (ignored when NULL) */
+    int32_t step0, nsteps, thin;  /* trace rows step0, step0 + thin, ... < step0 + nsteps (thin >= 1) */
+    /* source 2: host vectors */
+    const float *w;               /* [n_w, P] or NULL */
+    const int32_t *multiplicity;  /* [n_w] >= 0, or NULL = 1 each */
+    int64_t n_w;
+    /* the explained rows */
+    int32_t x_source;             /* PTNN_PREDICT_X_HOST | _TRAIN | _TEST */
+    int32_t n_rows;
+    const float *x;               /* [n_rows, n_in] (host rows only) */
+    /* the background rows and the coalition table */
+    const float *background;      /* [n_background, n_in] finite */
+    const uint64_t *masks;        /* [n_coalitions] bit i set: input i from the explained row; no bit at or above n_in */
+    const double *coef;           /* [n_coalitions, n_terms] finite */
+    int32_t n_background;         /* B, 1 .. PTNN_SHAP_MAX_BACKGROUND */
+    int32_t n_coalitions;         /* C, 1 .. PTNN_SHAP_MAX_COALITIONS */
+    int32_t n_terms;              /* T, 1 .. PTNN_SHAP_MAX_TERMS, T x n_out <= PTNN_SHAP_MAX_ACC */
+    int32_t reserved_;            /* set 0 */
+    /* order statistics: of out per (row, output, term), and of a_s per (output, term) */
+    const int64_t *ranks;         /* [n_ranks] */
+    const int64_t *ranks2;        /* [n_ranks2] */
+    int32_t n_ranks, n_ranks2;    /* each <= PTNN_PREDICT_MAX_RANKS */
+    /* outputs */
+    double *mean;
+    float *order_stats;
+    int64_t *pos_count, *neg_count;
+    double *abs_mean;
+    float *abs_order_stats;
+    float *sample_abs;
+    float *samples;
+    int64_t *n_samples, *n_distinct;
+} ptnn_shapley_spec;
+
+int ptnn_coalition_values(ptnn_handle *h, const ptnn_shapley_spec *spec);
+
 /* ---- posterior predictive checks (nothing in the reference: it never simulates data from the fitted model) ----
  * Does data simulated from the fitted model look like the data?  (BDA3 ch. 6; Gelman, Meng & Stern 1996.)  Every selected
  * occurrence of a sample draws one replicated data set y_rep on the data rows; a test quantity T is evaluated on y_rep and on

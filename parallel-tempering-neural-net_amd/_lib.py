@@ -204,6 +204,25 @@ class PdSpec(C.Structure):
 PD_MAX_GRID = 64
 
 
+class ShapSpec(C.Structure):
+    """ptnn_shapley_spec (include/ptnn.h)."""
+    _fields_ = _SELECTION + [
+        ("w", C.POINTER(C.c_float)), ("multiplicity", C.POINTER(C.c_int32)), ("n_w", C.c_int64),
+        ("x_source", C.c_int32), ("n_rows", C.c_int32), ("x", C.POINTER(C.c_float)),
+        ("background", C.POINTER(C.c_float)), ("masks", C.POINTER(C.c_uint64)), ("coef", C.POINTER(C.c_double)),
+        ("n_background", C.c_int32), ("n_coalitions", C.c_int32), ("n_terms", C.c_int32), ("reserved_", C.c_int32),
+        ("ranks", C.POINTER(C.c_int64)), ("ranks2", C.POINTER(C.c_int64)), ("n_ranks", C.c_int32), ("n_ranks2", C.c_int32),
+        ("mean", C.POINTER(C.c_double)), ("order_stats", C.POINTER(C.c_float)),
+        ("pos_count", C.POINTER(C.c_int64)), ("neg_count", C.POINTER(C.c_int64)),
+        ("abs_mean", C.POINTER(C.c_double)), ("abs_order_stats", C.POINTER(C.c_float)),
+        ("sample_abs", C.POINTER(C.c_float)), ("samples", C.POINTER(C.c_float)),
+        ("n_samples", C.POINTER(C.c_int64)), ("n_distinct", C.POINTER(C.c_int64)),
+    ]
+
+
+SHAP_MAX_COALITIONS, SHAP_MAX_BACKGROUND, SHAP_MAX_TERMS, SHAP_MAX_ACC = 4096, 256, 64, 256
+
+
 class PpcSpec(C.Structure):
     """ptnn_ppc_spec (include/ptnn.h)."""
     _fields_ = _SELECTION + [
@@ -384,6 +403,7 @@ SYMBOLS = {
     "ptnn_forecast_score": (C.c_int, [C.c_void_p, C.POINTER(ForecastScoreSpec)]),
     "ptnn_sensitivity": (C.c_int, [C.c_void_p, C.POINTER(SensitivitySpec)]),
     "ptnn_partial_dependence": (C.c_int, [C.c_void_p, C.POINTER(PdSpec)]),
+    "ptnn_coalition_values": (C.c_int, [C.c_void_p, C.POINTER(ShapSpec)]),
     "ptnn_ppc": (C.c_int, [C.c_void_p, C.POINTER(PpcSpec)]),
     "ptnn_powerscale": (C.c_int, [C.c_void_p, C.POINTER(PowerscaleSpec)]),
     "ptnn_prior_predictive": (C.c_int, [C.c_void_p, C.POINTER(PriorSpec)]),
@@ -1137,6 +1157,44 @@ class Sampler:
                    samples=np.empty((max(M, 0), n_rows, A, G, O), np.float32) if samples else None)
         _bind(spec, out)
         return self._call(self.lib.ptnn_partial_dependence, spec, out)
+
+    def coalition_values(self, x="test", *, background, masks, coef, replicas=None, step0=0, nsteps=None, thin=1, w=None, multiplicity=None,
+                         ranks=(), ranks2=(), mean=True, counts=False, abs_mean=True, sample_abs=False, samples=False):
+        """ptnn_coalition_values: for the selected weight vectors and the rows `x`, the value v(S) of every coalition of the table
+        -- the mean over the `background` rows [B, n_in] of the output on the hybrid row (input i from the explained row where bit
+        i of masks[c] is set, else from the background row) -- and out = sum_c coef[c, t] v(S_c), reduced on the device.  Source
+        and x as predict().  masks [C] uint64, coef [C, T] float64.  ranks apply to out, ranks2 to the per-sample row mean of
+        |out|.  -> dict(mean [n_rows, O, T] float64, order_stats [len(ranks), n_rows, O, T] float32, pos_count, neg_count [n_rows,
+        O, T] int64 (counts), abs_mean [O, T] float64, abs_order_stats [len(ranks2), O, T] float32, sample_abs [M, O, T] float32,
+        samples [M, n_rows, O, T] float32, n_samples, n_distinct); what was not asked for is None."""
+        spec, keep = _spec(ShapSpec), []
+        self._rows(spec, keep, x, "x", (self.cfg.n_in, "n_in columns"))
+        n_rows, O, I = spec.n_rows, self.cfg.n_out, self.cfg.n_in
+        M = self._samples(spec, keep, w=w, multiplicity=multiplicity, replicas=replicas, step0=step0, nsteps=nsteps, thin=thin,
+                          unit="vector")
+        ba = _f32(background)
+        if ba.ndim != 2 or ba.shape[1] != I:
+            raise ValueError(f"background must be [n_background, {I}] (n_in columns), got shape {ba.shape}")
+        ma = np.ascontiguousarray(masks, dtype=np.uint64).reshape(-1)
+        ca = np.ascontiguousarray(coef, dtype=np.float64)
+        if ca.ndim != 2 or ca.shape[0] != ma.size:
+            raise ValueError(f"coef must be [{ma.size}, n_terms] (one row per coalition), got shape {ca.shape}")
+        keep += [ba, ma, ca]
+        spec.background, spec.n_background = _ptr(ba), ba.shape[0]
+        spec.masks, spec.coef = _ptr(ma, C.POINTER(C.c_uint64)), _ptr(ca, C.POINTER(C.c_double))
+        spec.n_coalitions, spec.n_terms = ca.shape
+        T = ca.shape[1]
+        n_rk, n_rk2 = _ranks(spec, keep, ranks), _ranks(spec, keep, ranks2, ("ranks2", "n_ranks2"))
+        out = dict(mean=np.empty((n_rows, O, T), np.float64) if mean else None,
+                   order_stats=np.empty((n_rk, n_rows, O, T), np.float32) if n_rk else None,
+                   pos_count=np.empty((n_rows, O, T), np.int64) if counts else None,
+                   neg_count=np.empty((n_rows, O, T), np.int64) if counts else None,
+                   abs_mean=np.empty((O, T), np.float64) if abs_mean else None,
+                   abs_order_stats=np.empty((n_rk2, O, T), np.float32) if n_rk2 else None,
+                   sample_abs=np.empty((max(M, 0), O, T), np.float32) if sample_abs else None,
+                   samples=np.empty((max(M, 0), n_rows, O, T), np.float32) if samples else None)
+        _bind(spec, out)
+        return self._call(self.lib.ptnn_coalition_values, spec, out)
 
     def ppc(self, data="train", *, replicas=None, step0=0, nsteps=None, thin=1, w=None, eta=None, multiplicity=None, lags=(), seed=0,
             samples=True, draws=False):

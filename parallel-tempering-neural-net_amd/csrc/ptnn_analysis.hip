@@ -1,5 +1,5 @@
 // ptnn_analysis.hip -- the posterior analysis calls of libptnn.so: predict, convergence, rank_convergence, elpd, lfo, forecast, evidence, calibration,
-// forecast_score, sensitivity, partial_dependence, ppc, powerscale, prior_predictive, and the sample-selection path they share.  The shape-independent analysis kernels are defined in this object: it includes them.
+// forecast_score, sensitivity, partial_dependence, coalition_values, ppc, powerscale, prior_predictive, and the sample-selection path they share.  The shape-independent analysis kernels are defined in this object: it includes them.
 #include "ptnn_shapes.hpp"
 namespace ptnn {
 #include "ptnn_dev_wg.hpp"                   // work-group reductions and scans of every kernel below (ptnn_device.hpp has included it: ladder_round)
@@ -786,6 +786,178 @@ int ptnn_partial_dependence(ptnn_handle* h, const ptnn_pd_spec* spec) {
     HIP_TRY(fetch(s.pd_order_stats, d_pd_stats, (size_t)nrk_pd * AGO, st));
     HIP_TRY(fetch(s.range_mean, d_range_mean, (size_t)AO, st));
     HIP_TRY(fetch(s.range_order_stats, d_range_stats, (size_t)nrk_range * AO, st));
+    return wait_stream(h);
+}
+
+// ---- coalition values: Shapley attributions (ptnn_dev_shapley.hpp) ----
+static_assert(PTNN_SHAP_MAX_COALITIONS == SHAP_MAX_COALITIONS && PTNN_SHAP_MAX_BACKGROUND == SHAP_MAX_BACKGROUND &&
+              PTNN_SHAP_MAX_TERMS == SHAP_MAX_TERMS && PTNN_SHAP_MAX_ACC == SHAP_MAX_ACC, "ptnn.h PTNN_SHAP limits");
+static_assert(SHAP_MAX_ACC % WAVE == 0 && sizeof(unsigned long long) == sizeof(uint64_t), "shapley_forward_kernel: accumulators per lane, masks");
+
+// the per-shape kernels, one code object each (ptnn_shape.hip with -DPTNN_SHAP)
+#define X_DECL(T, I, O) extern "C" const ptnn::ShapShape ptnn_shap_##T##_##I##_##O;
+PTNN_SHAPES(X_DECL)
+#undef X_DECL
+namespace {
+#define X_ENTRY(T, I, O) &ptnn_shap_##T##_##I##_##O,
+const ShapShape* const g_shap_shapes[] = {PTNN_SHAPES(X_ENTRY)};
+#undef X_ENTRY
+
+// Stage b of the coalition values: the per-shape kernel, NV distinct vectors staged in LDS per work-group -- as many as 64 KiB
+// hold, at most SHAP_MAX_NV -- and SHAP_ROWS explained rows; a wave takes (vector, row) pairs
+struct ShapPlan {
+    int PV = 0, NV = 0;
+    size_t lds = 0;
+    void (*fwd)(const ShapFwd) = nullptr;
+    int init(const ptnn_handle* h) {
+        for (const ShapShape* s : g_shap_shapes)
+            if (s->task == h->cfg.task && s->I == h->cfg.n_in && s->O == h->cfg.n_out) fwd = s->fwd;
+        if (!fwd) return fail(-3, "coalition values: no kernel compiled for task %d with %d inputs and %d outputs", h->cfg.task, h->cfg.n_in, h->cfg.n_out);
+        PV = round_up4(h->P);
+        NV = std::max(1, std::min(SHAP_MAX_NV, (64 * 1024 / 4) / PV));
+        lds = (size_t)NV * PV * sizeof(float);
+        if (lds > LDS_CEILING) return fail(-3, "coalition values: a %d-parameter vector does not fit in LDS", h->P);
+        return raise_lds_limit(reinterpret_cast<const void*>(fwd), lds);
+    }
+    // fx [nr * O * T][U] = the T functionals of vectors base + run_off[u] on rows [r0, r0 + nr) of x
+    int run(const ptnn_handle* h, const float* base, const long long* run_off, const float* x, int xs, int r0, int nr, int U,
+            const float* bg, int B, int C, int T, const unsigned long long* masks, const double* coef, float* fx) const {
+        ShapFwd fa{base, run_off, x, xs, r0, nr, h->cfg.n_hidden, h->P, PV, U, NV, bg, B, C, T, masks, coef, fx};
+        HIP_TRY(launch(fwd, dim3((unsigned)((U + NV - 1) / NV), (unsigned)((nr + SHAP_ROWS - 1) / SHAP_ROWS)), dim3(SHAP_THREADS), lds,
+                       h->stream, fa));
+        return 0;
+    }
+};
+}  // namespace
+
+int ptnn_coalition_values(ptnn_handle* h, const ptnn_shapley_spec* spec) {
+    // argument checks first: none of them needs the handle or a device (a mask's bits are looked at with the handle's n_in)
+    if (int rc = check_spec(spec, "ptnn_shapley_spec")) return rc;
+    const ptnn_shapley_spec& s = *spec;
+    SampleSource src = source_of(s, s.w != nullptr, nullptr);
+    const RowSource rows{s.x_source, s.x, s.n_rows, "x_source", "PTNN_PREDICT_X", "x", "n_rows"};
+    RankOutputs rk{s.n_ranks, s.ranks, s.order_stats}, rk2{s.n_ranks2, s.ranks2, s.abs_order_stats};
+    if (int rc = check_source(src, "vectors")) return rc;
+    if (int rc = check_rows(rows)) return rc;
+    if (s.n_rows < 1) return fail(-1, "n_rows = %d must be >= 1", s.n_rows);
+    if (int rc = rk.check()) return rc;
+    if (int rc = rk2.check()) return rc;
+    if (s.n_background < 1 || s.n_background > PTNN_SHAP_MAX_BACKGROUND)
+        return fail(-1, "n_background = %d outside [1, %d]", s.n_background, PTNN_SHAP_MAX_BACKGROUND);
+    if (s.n_coalitions < 1 || s.n_coalitions > PTNN_SHAP_MAX_COALITIONS)
+        return fail(-1, "n_coalitions = %d outside [1, %d]", s.n_coalitions, PTNN_SHAP_MAX_COALITIONS);
+    if (s.n_terms < 1 || s.n_terms > PTNN_SHAP_MAX_TERMS) return fail(-1, "n_terms = %d outside [1, %d]", s.n_terms, PTNN_SHAP_MAX_TERMS);
+    if (!s.background) return fail(-1, "background is NULL: n_background rows of n_in values");
+    if (!s.masks) return fail(-1, "masks is NULL: one 64-bit mask per coalition");
+    if (!s.coef) return fail(-1, "coef is NULL: one row of n_terms coefficients per coalition");
+    const int B = s.n_background, C = s.n_coalitions, T = s.n_terms;
+    for (int c = 0; c < C; ++c)
+        for (int t = 0; t < T; ++t)
+            if (!std::isfinite(s.coef[(size_t)c * T + t]))
+                return fail(-1, "coef[%d, %d] = %g (coalition %d, term %d) is not finite", c, t, s.coef[(size_t)c * T + t], c, t);
+    if (int rc = check_handle(h, "ptnn_coalition_values")) return rc;
+    const int I = h->cfg.n_in, O = h->cfg.n_out, OT = O * T;
+    if (int rc = fit_rows(h, rows)) return rc;
+    if (OT > PTNN_SHAP_MAX_ACC) return fail(-1, "n_terms = %d x n_out = %d = %d accumulators: at most %d", T, O, OT, PTNN_SHAP_MAX_ACC);
+    for (int b = 0; b < B; ++b)
+        for (int i = 0; i < I; ++i)
+            if (!std::isfinite(s.background[(size_t)b * I + i]))
+                return fail(-1, "background[%d, %d] = %g is not finite", b, i, (double)s.background[(size_t)b * I + i]);
+    for (int c = 0; c < C; ++c)
+        if (I < 64 && (s.masks[c] >> I) != 0)
+            return fail(-1, "masks[%d] = 0x%llx has a bit at or above n_in = %d", c, (unsigned long long)s.masks[c], I);
+    const long long ncols_all = (long long)s.n_rows * OT;
+    if (ncols_all > 0x7fffffffLL)
+        return fail(-1, "%d rows x %d outputs x %d terms = %lld columns: at most 2^31 - 1 per call", s.n_rows, O, T, ncols_all);
+    const int ncols = (int)ncols_all;
+    if (int rc = select_samples(h, src, false)) return rc;
+    const long long M = src.M;
+    if (int rc = rk.check_values(M)) return rc;
+    if (int rc = rk2.check_values(M)) return rc;
+    if (s.n_samples) *s.n_samples = M;
+
+    if (int rc = start_device(h)) return rc;
+    hipStream_t st = h->stream;
+    DeviceScratch mem;
+    const float* d_x = nullptr;
+    int xs = 0;
+    if (int rc = upload_rows(h, mem, rows, I, &d_x, &xs)) return rc;
+    float* d_bg = nullptr;
+    unsigned long long* d_masks = nullptr;
+    double* d_coef = nullptr;
+    HIP_TRY(mem.upload(&d_bg, s.background, (size_t)B * I, st));
+    HIP_TRY(mem.upload(&d_masks, (const unsigned long long*)s.masks, (size_t)C, st));
+    HIP_TRY(mem.upload(&d_coef, s.coef, (size_t)C * T, st));
+    Distinct d;
+    if (int rc = distinct_samples(h, mem, src, false, true, &d)) return rc;
+    const int U = d.U;
+    if (s.n_distinct) *s.n_distinct = U;
+    // an output costs device work only when its pointer is given
+    const bool col_red = s.mean || s.order_stats, signs = s.pos_count || s.neg_count;
+    const bool abs_red = s.abs_mean || s.abs_order_stats || s.sample_abs;
+    if (!s.order_stats) rk.n = 0;
+    if (!s.abs_order_stats) rk2.n = 0;
+    double *d_mean = nullptr, *d_acc_abs = nullptr, *d_acc_sq = nullptr, *d_abs_mean = nullptr, *d_sq_mean = nullptr, *d_a32_mean = nullptr;
+    float* d_a32 = nullptr;
+    long long *d_pos = nullptr, *d_neg = nullptr;
+    if (col_red) HIP_TRY(mem.alloc(&d_mean, (size_t)ncols));
+    if (signs) {
+        HIP_TRY(mem.alloc(&d_pos, (size_t)ncols));
+        HIP_TRY(mem.alloc(&d_neg, (size_t)ncols));
+    }
+    if (int rc = rk.to_device(mem, (size_t)ncols, st)) return rc;
+    if (int rc = rk2.to_device(mem, (size_t)OT, st)) return rc;
+    if (abs_red) {      // per (o, t) and distinct vector: the row sums of |out| (sensitivity_rows_kernel: and of out^2, not read), carried across the blocks
+        HIP_TRY(mem.alloc(&d_acc_abs, (size_t)OT * U));
+        HIP_TRY(mem.alloc(&d_acc_sq, (size_t)OT * U));
+        HIP_TRY(mem.alloc(&d_a32, (size_t)OT * U));
+        HIP_TRY(mem.alloc(&d_abs_mean, (size_t)OT));
+        HIP_TRY(mem.alloc(&d_sq_mean, (size_t)OT));
+        HIP_TRY(mem.alloc(&d_a32_mean, (size_t)OT));
+        HIP_TRY(hipMemsetAsync(d_acc_abs, 0, (size_t)OT * U * sizeof(double), st));
+        HIP_TRY(hipMemsetAsync(d_acc_sq, 0, (size_t)OT * U * sizeof(double), st));
+    }
+    // the forward pass, the column reductions and the row sums in blocks of rows: fx scratch U x (rows x O x T) floats under the budget
+    const long long rows_blk = row_block(scratch_budget("PTNN_SHAP_SCRATCH_BYTES"), (size_t)U * sizeof(float) * OT, s.n_rows);
+    float* d_fx = nullptr;
+    HIP_TRY(mem.alloc(&d_fx, (size_t)rows_blk * OT * U));
+    ShapPlan fwd;
+    if (int rc = fwd.init(h)) return rc;
+    std::vector<int> item_run;
+    if (s.samples || s.sample_abs) if (int rc = item_runs(h, d, src.n_items, &item_run)) return rc;
+    const dim3 rows_grid((unsigned)((U + PRED_THREADS - 1) / PRED_THREADS), (unsigned)OT);
+    if (int rc = each_block(s.n_rows, rows_blk, [&](long long r0, int nr) -> int {
+        if (int rc = fwd.run(h, d.base, d.run_off, d_x, xs, (int)r0, nr, U, d_bg, B, C, T, d_masks, d_coef, d_fx)) return rc;
+        if (col_red) {
+            PredictRed ra{d_fx, d.run_cnt, U, 1, (int)(r0 * OT), ncols, M, rk.n, rk.d_ranks, d_mean, rk.d_stats, nullptr};
+            HIP_TRY(launch(predict_reduce_kernel, dim3((unsigned)(nr * OT)), dim3(PRED_THREADS), 0, st, ra));
+        }
+        if (signs) {
+            SensSign sa{d_fx, d.run_cnt, U, r0 * OT, d_pos, d_neg};
+            HIP_TRY(launch(sensitivity_sign_kernel, dim3((unsigned)(nr * OT)), dim3(PRED_THREADS), 0, st, sa));
+        }
+        if (abs_red) {
+            SensRows rw{d_fx, U, OT, nr, r0 + nr == s.n_rows ? 1 : 0, (double)s.n_rows, d_acc_abs, d_acc_sq, d_a32};
+            HIP_TRY(launch(sensitivity_rows_kernel, rows_grid, dim3(PRED_THREADS), 0, st, rw));
+        }
+        return s.samples ? scatter_samples(h, d_fx, nr * OT, U, item_run, src.weights(), s.samples, (size_t)ncols, (size_t)r0 * OT) : 0;
+    })) return rc;
+    if (s.abs_mean) {
+        SensMean ma{d_acc_abs, d_acc_sq, d.run_cnt, U, (double)s.n_rows, M, d_abs_mean, d_sq_mean};
+        HIP_TRY(launch(sensitivity_mean_kernel, dim3((unsigned)OT), dim3(PRED_THREADS), 0, st, ma));
+    }
+    if (rk2.n) {
+        PredictRed ra{d_a32, d.run_cnt, U, 1, 0, OT, M, rk2.n, rk2.d_ranks, d_a32_mean, rk2.d_stats, nullptr};
+        HIP_TRY(launch(predict_reduce_kernel, dim3((unsigned)OT), dim3(PRED_THREADS), 0, st, ra));
+    }
+    if (s.sample_abs)
+        if (int rc = scatter_samples(h, d_a32, OT, U, item_run, src.weights(), s.sample_abs, (size_t)OT, 0)) return rc;
+    HIP_TRY(fetch(s.mean, d_mean, (size_t)ncols, st));
+    HIP_TRY(fetch(s.order_stats, rk.d_stats, (size_t)rk.n * ncols, st));
+    HIP_TRY(fetch((long long*)s.pos_count, d_pos, (size_t)ncols, st));
+    HIP_TRY(fetch((long long*)s.neg_count, d_neg, (size_t)ncols, st));
+    HIP_TRY(fetch(s.abs_mean, d_abs_mean, (size_t)OT, st));
+    HIP_TRY(fetch(s.abs_order_stats, rk2.d_stats, (size_t)rk2.n * OT, st));
     return wait_stream(h);
 }
 

@@ -16,6 +16,7 @@
 // lives in a part that exactly one translation unit includes, inside namespace ptnn after ptnn_shapes.hpp, and that object holds
 // it: ptnn_dev_swap.hpp in ptnn.hip; ptnn_dev_select.hpp, ptnn_dev_convergence.hpp, ptnn_dev_elpd.hpp, ptnn_dev_lfo.hpp, ptnn_dev_evidence.hpp,
 // ptnn_dev_calibration.hpp and the second parts of ptnn_dev_sensitivity.hpp and ptnn_dev_pd.hpp in ptnn_analysis.hip.
+// (ptnn_dev_shapley.hpp holds one template kernel and has no such part.)
 //
 // Written for gfx950 only: wave size 64, DPP row operations, v_permlane{16,32}_swap.
 #pragma once
@@ -158,5 +159,6 @@ struct SegDyn {
 #include "ptnn_dev_forecast.hpp"             // recursive multi-step forecasts: the per-shape recursive forward pass
 #include "ptnn_dev_sensitivity.hpp"          // input sensitivity: the per-shape forward pass that carries the derivative to the inputs (its second part: ptnn_analysis.hip)
 #include "ptnn_dev_pd.hpp"                   // partial dependence and ICE curves: the per-shape forward pass over substituted inputs (its second part: ptnn_analysis.hip)
+#include "ptnn_dev_shapley.hpp"              // coalition values (Shapley attributions): the per-shape forward pass over hybrid rows, a code object of its own per shape
 
 }  // namespace ptnn

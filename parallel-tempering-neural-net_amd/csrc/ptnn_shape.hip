@@ -8,7 +8,11 @@
 
 using namespace ptnn;
 
-#ifdef PTNN_HC
+#ifdef PTNN_SHAP
+// ... or, with -DPTNN_SHAP on top (and its own PTNN_SHAPE_SYMBOL, ptnn_shap_<T>_<I>_<O>), nothing but the shape's coalition-value
+// kernel (ptnn_dev_shapley.hpp): a code object of its own, so that the shape's other kernels keep their bytes
+extern "C" const ShapShape PTNN_SHAPE_SYMBOL = {PTNN_T, PTNN_I, PTNN_O, &shapley_forward_kernel<PTNN_T, PTNN_I, PTNN_O>};
+#elif defined(PTNN_HC)
 // ... or, with -DPTNN_HC=<n_hidden> on top (and its own PTNN_SHAPE_SYMBOL, ptnn_pack_fixed_<T>_<I>_<O>_<H>), nothing but the shape's
 // packed kernel with that hidden width compiled in
 // (-DPTNN_HC_MULTI, ptnn_packm_fixed_<T>_<I>_<O>_<H>: the kernel over several CUs)
