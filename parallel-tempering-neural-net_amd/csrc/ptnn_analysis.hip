@@ -1,6 +1,7 @@
 // ptnn_analysis.hip -- the posterior analysis calls of libptnn.so: predict, convergence, rank_convergence, elpd, lfo, forecast, evidence, calibration,
 // forecast_score, sensitivity, partial_dependence, coalition_values, ppc, powerscale, prior_predictive, and the sample-selection path they share.  The shape-independent analysis kernels are defined in this object: it includes them.
-#include "ptnn_shapes.hpp"
+#include "ptnn_shapes.hpp"                   // PTNN_SHAPES
+#include "ptnn_analysis_device.hpp"          // the per-shape forward kernels and their table, AnalysisShape
 namespace ptnn {
 #include "ptnn_dev_wg.hpp"                   // work-group reductions and scans of every kernel below (ptnn_device.hpp has included it: ladder_round)
 #include "ptnn_dev_select.hpp"               // sample selection (run-length pass over the selected rows) and the per-column predictive reduction
@@ -14,10 +15,8 @@ namespace ptnn {
 #include "ptnn_dev_powerscale.hpp"           // power-scaling sensitivity: components, smoothed weights, order per quantity, distances
 #include "ptnn_dev_prior.hpp"                // prior predictive checks: saturation counts, statistics per drawn function and over the draws
 #include "ptnn_dev_rank.hpp"                 // rank-normalised convergence: sort words, average ranks, z-scores, indicators, rank histograms
-#define PTNN_SENSITIVITY_REDUCTIONS
-#include "ptnn_dev_sensitivity.hpp"          // input sensitivity, second part: sign counts, row sums and their weighted means
-#define PTNN_PD_REDUCTIONS
-#include "ptnn_dev_pd.hpp"                   // partial dependence, second part: row sums, ranges and the weighted means of the row means
+#include "ptnn_dev_sensitivity_reduce.hpp"   // input sensitivity: sign counts, row sums and their weighted means
+#include "ptnn_dev_pd_reduce.hpp"            // partial dependence: row sums, ranges and the weighted means of the row means
 #include "ptnn_dev_report.hpp"               // classification report: confusion counts, Mann-Whitney counts and metric columns per sample
 #include "ptnn_dev_uncertainty.hpp"          // predictive uncertainty: entropy per sample and its mean per row, variance per column, mean noise
 }  // namespace ptnn
@@ -31,6 +30,21 @@ namespace ptnn {
 #include <vector>
 
 using namespace ptnn;
+
+// The per-shape analysis kernels (ptnn_analysis_device.hpp; a code object per shape, ptnn_analysis_shape.hip; unknown to the handle and
+// ptnn.hip) and the one lookup: *fwd = the kernel `which` of the handle's shape, allowed `lds` bytes of dynamic LDS; `what` names the call.
+#define X_DECL(T, I, O) extern "C" const ptnn::AnalysisShape ptnn_ashape_##T##_##I##_##O;
+PTNN_SHAPES(X_DECL)
+#undef X_DECL
+#define X_ENTRY(T, I, O) &ptnn_ashape_##T##_##I##_##O,
+static const AnalysisShape* const g_analysis_shapes[] = {PTNN_SHAPES(X_ENTRY)};
+#undef X_ENTRY
+template <class K> static int analysis_shape(const ptnn_handle* h, const char* what, K AnalysisShape::*which, size_t lds, K* fwd) {
+    for (const AnalysisShape* s : g_analysis_shapes)
+        if (s->task == h->cfg.task && s->I == h->cfg.n_in && s->O == h->cfg.n_out)
+            return raise_lds_limit(reinterpret_cast<const void*>(*fwd = s->*which), lds);
+    return fail(-3, "%s: no kernel compiled for task %d with %d inputs and %d outputs", what, h->cfg.task, h->cfg.n_in, h->cfg.n_out);
+}
 
 namespace {
 struct DeviceScratch {            // every buffer of one analysis call, released on every return path
@@ -346,6 +360,7 @@ int upload_rows(ptnn_handle* h, DeviceScratch& mem, const RowSource& r, int widt
 struct ForwardPlan {
     int PV = 0, NV = 0;
     size_t lds = 0;
+    void (*fwd)(const PredictFwd) = nullptr;
     int init(const ptnn_handle* h, const char* what) {
         const int P = h->P;
         PV = round_up4(P);
@@ -353,12 +368,12 @@ struct ForwardPlan {
         NV = std::max(1, std::min(PRED_MAX_NV, (48 * 1024 / 4) / per_vec));
         lds = (size_t)NV * per_vec * sizeof(float);
         if (lds > LDS_CEILING) return fail(-3, "%s: a %d-parameter vector does not fit in LDS", what, P);
-        return raise_lds_limit(reinterpret_cast<const void*>(h->shape->predict_fwd), lds);
+        return analysis_shape(h, what, &AnalysisShape::predict_fwd, lds, &fwd);
     }
     // fx [nr * O][U] = the outputs of vectors base + run_off[u] on rows [r0, r0 + nr) of x
     int run(const ptnn_handle* h, const float* base, const long long* run_off, const float* x, int xs, int r0, int nr, int U, float* fx) const {
         PredictFwd fa{base, run_off, x, xs, r0, nr, h->cfg.n_hidden, h->P, PV, U, NV, fx};
-        HIP_TRY(launch(h->shape->predict_fwd, dim3((unsigned)((U + NV - 1) / NV), (unsigned)((nr + WAVE - 1) / WAVE)), dim3(PRED_THREADS), lds,
+        HIP_TRY(launch(fwd, dim3((unsigned)((U + NV - 1) / NV), (unsigned)((nr + WAVE - 1) / WAVE)), dim3(PRED_THREADS), lds,
                        h->stream, fa));
         return 0;
     }
@@ -374,6 +389,7 @@ long long row_block(size_t budget, size_t row_bytes, long long n_rows) {
 struct SensPlan {
     int PV = 0, NV = 0, VS = 0;
     size_t lds = 0;
+    void (*fwd)(const SensFwd) = nullptr;
     int init(const ptnn_handle* h) {
         const int P = h->P, OI = h->cfg.n_out * h->cfg.n_in;
         PV = round_up4(P);
@@ -381,12 +397,12 @@ struct SensPlan {
         VS = OI * WAVE + std::max(1, WAVE / NV);        // the pad: the vectors of one column land in different LDS banks
         lds = (size_t)NV * (PV + VS) * sizeof(float);
         if (lds > LDS_CEILING) return fail(-3, "input sensitivity: a %d-parameter vector does not fit in LDS", P);
-        return raise_lds_limit(reinterpret_cast<const void*>(h->shape->sens_fwd), lds);
+        return analysis_shape(h, "input sensitivity", &AnalysisShape::sens_fwd, lds, &fwd);
     }
     // gx [nr * O * I][U] = the input gradients of vectors base + run_off[u] on rows [r0, r0 + nr) of x
     int run(const ptnn_handle* h, const float* base, const long long* run_off, const float* x, int xs, int r0, int nr, int U, float* gx) const {
         SensFwd fa{base, run_off, x, xs, r0, nr, h->cfg.n_hidden, h->P, PV, U, NV, VS, gx};
-        HIP_TRY(launch(h->shape->sens_fwd, dim3((unsigned)((U + NV - 1) / NV), (unsigned)((nr + WAVE - 1) / WAVE)), dim3(SENS_THREADS), lds,
+        HIP_TRY(launch(fwd, dim3((unsigned)((U + NV - 1) / NV), (unsigned)((nr + WAVE - 1) / WAVE)), dim3(SENS_THREADS), lds,
                        h->stream, fa));
         return 0;
     }
@@ -402,6 +418,7 @@ struct SensPlan {
 struct PdPlan {
     int PV = 0, NV = 0, VS = 0, GC = 0, NCH = 0, A = 0, G = 0;
     size_t lds = 0;
+    void (*fwd)(const PdFwd) = nullptr;
     int init(const ptnn_handle* h, int n_inputs, int n_grid) {
         const int P = h->P, O = h->cfg.n_out, GT = pd_grid_tile(O), tiles = (n_grid + GT - 1) / GT;
         A = n_inputs; G = n_grid;
@@ -415,17 +432,58 @@ struct PdPlan {
         VS = GC * O * WAVE + std::max(1, WAVE / NV);    // the pad: the vectors of one column land in different LDS banks
         lds = (size_t)NV * (PV + VS) * sizeof(float);
         if (lds > LDS_CEILING) return fail(-3, "partial dependence: a %d-parameter vector does not fit in LDS", P);
-        return raise_lds_limit(reinterpret_cast<const void*>(h->shape->pd_fwd), lds);
+        return analysis_shape(h, "partial dependence", &AnalysisShape::pd_fwd, lds, &fwd);
     }
     // fx [nr * A * G * O][U] = the outputs of vectors base + run_off[u] on rows [r0, r0 + nr) of x, input inputs[a] set to grid[a, k]
     int run(const ptnn_handle* h, const float* base, const long long* run_off, const float* x, int xs, int r0, int nr, int U,
             const int* inputs, const float* grid, float* fx) const {
         PdFwd fa{base, run_off, x, xs, r0, nr, h->cfg.n_hidden, h->P, PV, U, NV, VS, A, G, GC, NCH, inputs, grid, fx};
-        HIP_TRY(launch(h->shape->pd_fwd, dim3((unsigned)((U + NV - 1) / NV), (unsigned)((nr + WAVE - 1) / WAVE), (unsigned)(A * NCH)),
+        HIP_TRY(launch(fwd, dim3((unsigned)((U + NV - 1) / NV), (unsigned)((nr + WAVE - 1) / WAVE), (unsigned)(A * NCH)),
                        dim3(PD_THREADS), lds, h->stream, fa));
         return 0;
     }
 };
+
+// Stage b of forecast and forecast_score: the per-shape forecast_fwd.  The layout is a function of the shape alone (P), never of the
+// scratch budget: FC_LANE (a lane per trajectory, 4 x 64 vectors transposed in LDS) while a vector is short enough, else FC_SPLIT.
+struct ForecastPlan {
+    size_t lds = 0;
+    void (*fwd)(const ForecastFwd) = nullptr;
+    ForecastFwd fa{};
+    // what every block shares: the trajectories d from the origins x, the carried windows, the noise and its seed, the outputs
+    int init(const ptnn_handle* h, const Distinct& d, const float* x, int xs, int horizon, float* win, bool noise, uint64_t seed, float* fx, float* mu) {
+        const int P = h->P;
+        fa.base = d.base; fa.run_off = d.run_off; fa.eta = d.run_eta; fa.x = x; fa.xs = xs; fa.horizon = horizon; fa.win = win;
+        fa.H = h->cfg.n_hidden; fa.P = P; fa.U = d.U; fa.noise = noise ? 1 : 0; fa.fx = fx; fa.mu = mu;
+        split_seed(seed, &fa.seed_lo, &fa.seed_hi);
+        fa.layout = P <= FC_LANE_MAX_P ? FC_LANE : FC_SPLIT;
+        lds = fa.layout == FC_LANE ? (size_t)(FC_THREADS / WAVE) * P * WAVE * sizeof(float)
+                                   : (size_t)(round_up4(P) + 2 * (FC_THREADS / WAVE) * WAVE) * sizeof(float);
+        if (lds > LDS_CEILING) return fail(-3, "forecast: a %d-parameter vector does not fit in LDS", P);
+        return analysis_shape(h, "forecast", &AnalysisShape::forecast_fwd, lds, &fwd);
+    }
+    // fx [nr * nk][U] (and mu) = steps [k0, k0 + nk) of the trajectories from origins [r0, r0 + nr)
+    int run(const ptnn_handle* h, int r0, int nr, int k0, int nk) {
+        fa.r0 = r0; fa.nr = nr; fa.k0 = k0; fa.hb = nk;
+        const long long gx = (fa.U + FC_THREADS - 1) / FC_THREADS;      // FC_LANE
+        const dim3 grid = fa.layout == FC_LANE ? dim3((unsigned)gx, (unsigned)std::max(1LL, std::min<long long>((512 + gx - 1) / gx, nr)))
+                                               : dim3((unsigned)fa.U, (unsigned)((nr + WAVE - 1) / WAVE));
+        HIP_TRY(launch(fwd, grid, dim3(FC_THREADS), lds, h->stream, fa));
+        return 0;
+    }
+};
+// forecasts with noise: every occurrence is its own trajectory, so host multiplicities are expanded into w_exp / eta_exp, which
+// `src` then names
+void expand_occurrences(SampleSource& src, int P, std::vector<float>* w_exp, std::vector<float>* eta_exp) {
+    if (!src.host || !src.multiplicity) return;
+    w_exp->reserve((size_t)src.M * P); eta_exp->reserve((size_t)src.M);
+    for (int64_t k = 0; k < src.n_w; ++k)
+        for (int c = 0; c < src.multiplicity[k]; ++c) {
+            w_exp->insert(w_exp->end(), src.w + (size_t)k * P, src.w + (size_t)(k + 1) * P);
+            eta_exp->push_back(src.eta[k]);
+        }
+    src.w = w_exp->data(); src.eta = eta_exp->data(); src.multiplicity = nullptr; src.n_items = src.M;
+}
 
 // The order statistics of predict, sensitivity and forecast: ranks [n] in the expanded multiset of M samples, the values of those
 // ranks in every column to the caller's order_stats
@@ -794,15 +852,7 @@ static_assert(PTNN_SHAP_MAX_COALITIONS == SHAP_MAX_COALITIONS && PTNN_SHAP_MAX_B
               PTNN_SHAP_MAX_TERMS == SHAP_MAX_TERMS && PTNN_SHAP_MAX_ACC == SHAP_MAX_ACC, "ptnn.h PTNN_SHAP limits");
 static_assert(SHAP_MAX_ACC % WAVE == 0 && sizeof(unsigned long long) == sizeof(uint64_t), "shapley_forward_kernel: accumulators per lane, masks");
 
-// the per-shape kernels, one code object each (ptnn_shape.hip with -DPTNN_SHAP)
-#define X_DECL(T, I, O) extern "C" const ptnn::ShapShape ptnn_shap_##T##_##I##_##O;
-PTNN_SHAPES(X_DECL)
-#undef X_DECL
 namespace {
-#define X_ENTRY(T, I, O) &ptnn_shap_##T##_##I##_##O,
-const ShapShape* const g_shap_shapes[] = {PTNN_SHAPES(X_ENTRY)};
-#undef X_ENTRY
-
 // Stage b of the coalition values: the per-shape kernel, NV distinct vectors staged in LDS per work-group -- as many as 64 KiB
 // hold, at most SHAP_MAX_NV -- and SHAP_ROWS explained rows; a wave takes (vector, row) pairs
 struct ShapPlan {
@@ -810,14 +860,11 @@ struct ShapPlan {
     size_t lds = 0;
     void (*fwd)(const ShapFwd) = nullptr;
     int init(const ptnn_handle* h) {
-        for (const ShapShape* s : g_shap_shapes)
-            if (s->task == h->cfg.task && s->I == h->cfg.n_in && s->O == h->cfg.n_out) fwd = s->fwd;
-        if (!fwd) return fail(-3, "coalition values: no kernel compiled for task %d with %d inputs and %d outputs", h->cfg.task, h->cfg.n_in, h->cfg.n_out);
         PV = round_up4(h->P);
         NV = std::max(1, std::min(SHAP_MAX_NV, (64 * 1024 / 4) / PV));
         lds = (size_t)NV * PV * sizeof(float);
         if (lds > LDS_CEILING) return fail(-3, "coalition values: a %d-parameter vector does not fit in LDS", h->P);
-        return raise_lds_limit(reinterpret_cast<const void*>(fwd), lds);
+        return analysis_shape(h, "coalition values", &AnalysisShape::shap_fwd, lds, &fwd);
     }
     // fx [nr * O * T][U] = the T functionals of vectors base + run_off[u] on rows [r0, r0 + nr) of x
     int run(const ptnn_handle* h, const float* base, const long long* run_off, const float* x, int xs, int r0, int nr, int U,
@@ -1564,17 +1611,7 @@ int ptnn_forecast(ptnn_handle* h, const ptnn_forecast_spec* spec) {
     if (int rc = upload_rows(h, mem, rows, I, &d_x, &xs)) return rc;
     // stage a: items -> trajectories (noise off: distinct vectors; noise on: every occurrence, host multiplicities expanded)
     std::vector<float> w_exp, eta_exp;
-    if (noise && host_src && s.multiplicity) {
-        w_exp.reserve((size_t)M * P);
-        eta_exp.reserve((size_t)M);
-        for (int64_t k = 0; k < s.n_w; ++k)
-            for (int c = 0; c < s.multiplicity[k]; ++c) {
-                w_exp.insert(w_exp.end(), s.w + (size_t)k * P, s.w + (size_t)(k + 1) * P);
-                eta_exp.push_back(s.eta[k]);
-            }
-        src.w = w_exp.data(); src.eta = eta_exp.data(); src.multiplicity = nullptr;
-        src.n_items = M;
-    }
+    if (noise) expand_occurrences(src, P, &w_exp, &eta_exp);
     Distinct d;
     if (int rc = distinct_samples(h, mem, src, noise, !noise, &d)) return rc;
     const int U = d.U;
@@ -1599,33 +1636,16 @@ int ptnn_forecast(ptnn_handle* h, const ptnn_forecast_spec* spec) {
     float *d_fx = nullptr, *d_win = nullptr;
     HIP_TRY(mem.alloc(&d_fx, (size_t)ob * hb * U));
     if (split_h) HIP_TRY(mem.alloc(&d_win, (size_t)U * I));
-    // the layout: a function of the shape alone (P), never of the budget
-    const int layout = P <= FC_LANE_MAX_P ? FC_LANE : FC_SPLIT;
-    const size_t lds = layout == FC_LANE ? (size_t)(FC_THREADS / WAVE) * P * WAVE * sizeof(float)
-                                         : (size_t)(round_up4(P) + 2 * (FC_THREADS / WAVE) * WAVE) * sizeof(float);
-    if (lds > LDS_CEILING) return fail(-3, "forecast: a %d-parameter vector does not fit in LDS", P);
-    if (int rc = raise_lds_limit(reinterpret_cast<const void*>(h->shape->forecast_fwd), lds)) return rc;
+    ForecastPlan fwd;
+    if (int rc = fwd.init(h, d, d_x, xs, hz, d_win, noise, s.seed, d_fx, nullptr)) return rc;
     // samples: the trajectory of every selected row, chain-major
     std::vector<int> item_run;
     if (s.samples) if (int rc = item_runs(h, d, src.n_items, &item_run)) return rc;
-    ForecastFwd fa{};
-    fa.base = d.base; fa.run_off = d.run_off; fa.eta = d.run_eta; fa.x = d_x; fa.xs = xs; fa.horizon = hz; fa.win = d_win;
-    fa.H = h->cfg.n_hidden; fa.P = P; fa.U = U; fa.layout = layout; fa.noise = noise ? 1 : 0;
-    fa.fx = d_fx;
-    split_seed(s.seed, &fa.seed_lo, &fa.seed_hi);
     for (long long r0 = 0; r0 < s.n_origins; r0 += ob) {
         const int nr = (int)std::min<long long>(ob, s.n_origins - r0);
         for (long long k0 = 0; k0 < hz; k0 += hb) {
             const int nk = (int)std::min<long long>(hb, hz - k0);
-            fa.r0 = (int)r0; fa.nr = nr; fa.k0 = (int)k0; fa.hb = nk;
-            dim3 grid;
-            if (layout == FC_LANE) {
-                const long long gx = (U + FC_THREADS - 1) / FC_THREADS;
-                grid = dim3((unsigned)gx, (unsigned)std::max(1LL, std::min<long long>((512 + gx - 1) / gx, nr)));
-            } else {
-                grid = dim3((unsigned)U, (unsigned)((nr + WAVE - 1) / WAVE));
-            }
-            HIP_TRY(launch(h->shape->forecast_fwd, grid, dim3(FC_THREADS), lds, st, fa));
+            if (int rc = fwd.run(h, (int)r0, nr, (int)k0, nk)) return rc;
             const long long col0 = r0 * hz + k0;             // the block's columns are contiguous (see above)
             PredictRed ra{d_fx, d.run_cnt, U, 1, (int)col0, (int)ncols, M, s.n_ranks, rk.d_ranks, d_mean, rk.d_stats, nullptr};
             HIP_TRY(launch(predict_reduce_kernel, dim3((unsigned)(nr * nk)), dim3(PRED_THREADS), 0, st, ra));
@@ -2038,17 +2058,7 @@ int ptnn_forecast_score(ptnn_handle* h, const ptnn_forecast_score_spec* spec) {
     // stage a, as ptnn_forecast: noise on -- every occurrence its own trajectory, host multiplicities expanded; noise off -- the
     // distinct (w, eta) samples with their multiplicities
     std::vector<float> w_exp, eta_exp;
-    if (noise && host_src && s.multiplicity) {
-        w_exp.reserve((size_t)M * P);
-        eta_exp.reserve((size_t)M);
-        for (int64_t k = 0; k < s.n_w; ++k)
-            for (int c = 0; c < s.multiplicity[k]; ++c) {
-                w_exp.insert(w_exp.end(), s.w + (size_t)k * P, s.w + (size_t)(k + 1) * P);
-                eta_exp.push_back(s.eta[k]);
-            }
-        src.w = w_exp.data(); src.eta = eta_exp.data(); src.multiplicity = nullptr;
-        src.n_items = M;
-    }
+    if (noise) expand_occurrences(src, P, &w_exp, &eta_exp);
     Distinct d;
     if (int rc = distinct_samples(h, mem, src, true, !noise, &d)) return rc;
     const int U = d.U;
@@ -2076,11 +2086,8 @@ int ptnn_forecast_score(ptnn_handle* h, const ptnn_forecast_score_spec* spec) {
     if (noise) HIP_TRY(mem.alloc(&d_mu, (size_t)ob * hb * U));
     if (split_h) HIP_TRY(mem.alloc(&d_win, (size_t)U * I));
     HIP_TRY(mem.upload(&d_truth, s.truth, (size_t)ncols, st));
-    const int layout = P <= FC_LANE_MAX_P ? FC_LANE : FC_SPLIT;
-    const size_t lds = layout == FC_LANE ? (size_t)(FC_THREADS / WAVE) * P * WAVE * sizeof(float)
-                                         : (size_t)(round_up4(P) + 2 * (FC_THREADS / WAVE) * WAVE) * sizeof(float);
-    if (lds > LDS_CEILING) return fail(-3, "forecast: a %d-parameter vector does not fit in LDS", P);
-    if (int rc = raise_lds_limit(reinterpret_cast<const void*>(h->shape->forecast_fwd), lds)) return rc;
+    ForecastPlan fwd;
+    if (int rc = fwd.init(h, d, d_x, xs, hz, d_win, noise, s.seed, d_fx, d_mu)) return rc;
     std::vector<int> item_run;
     if (s.samples || s.means) if (int rc = item_runs(h, d, src.n_items, &item_run)) return rc;
     // per-column and per-origin results: NaN (all bits set) wherever nothing is scored
@@ -2137,24 +2144,11 @@ int ptnn_forecast_score(ptnn_handle* h, const ptnn_forecast_score_spec* spec) {
     ra.pit = d_pit; ra.pred_mean = d_mean; ra.pred_sd = d_sd; ra.quantiles = d_q; ra.term1 = d_t1; ra.pair_bound = d_bound;
     CalibPair pa{d_m, d_tau2, d.run_cnt, d_bound, U, 0, 0, n_tiles, d_limbs, d_truth};
     FscoreLog la{d_m, d.run_eta, d.run_cnt, d_truth, U, 0, M, d_log};
-    ForecastFwd fa{};
-    fa.base = d.base; fa.run_off = d.run_off; fa.eta = d.run_eta; fa.x = d_x; fa.xs = xs; fa.horizon = hz; fa.win = d_win;
-    fa.H = h->cfg.n_hidden; fa.P = P; fa.U = U; fa.layout = layout; fa.noise = noise ? 1 : 0;
-    fa.fx = d_fx; fa.mu = d_mu;
-    split_seed(s.seed, &fa.seed_lo, &fa.seed_hi);
     for (long long r0 = 0; r0 < n_org; r0 += ob) {
         const int nr = (int)std::min<long long>(ob, n_org - r0);
         for (long long k0 = 0; k0 < hz; k0 += hb) {
             const int nk_blk = (int)std::min<long long>(hb, hz - k0);
-            fa.r0 = (int)r0; fa.nr = nr; fa.k0 = (int)k0; fa.hb = nk_blk;
-            dim3 grid;
-            if (layout == FC_LANE) {
-                const long long gx = (U + FC_THREADS - 1) / FC_THREADS;
-                grid = dim3((unsigned)gx, (unsigned)std::max(1LL, std::min<long long>((512 + gx - 1) / gx, nr)));
-            } else {
-                grid = dim3((unsigned)U, (unsigned)((nr + WAVE - 1) / WAVE));
-            }
-            HIP_TRY(launch(h->shape->forecast_fwd, grid, dim3(FC_THREADS), lds, st, fa));
+            if (int rc = fwd.run(h, (int)r0, nr, (int)k0, nk_blk)) return rc;
             const long long col0 = r0 * hz + k0;             // the block's columns are contiguous (split_h: one origin per block)
             const int nc = nr * nk_blk;                      // <= 65535
             ra.row0 = (int)col0;

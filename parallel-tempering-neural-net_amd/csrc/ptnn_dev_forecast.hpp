@@ -3,7 +3,7 @@
 // trajectory is y_k = f_w(window_{k-1}) (+ exp(eta / 2) z_k with noise on), window_k = (window_{k-1}[1:], y_k).
 //   a. the selection: noise off -- sample_runs_kernel + predict_scan_kernel (distinct vectors with multiplicities, one
 //      trajectory each); noise on -- sample_runs_kernel with the eta (every occurrence its own trajectory).  Both unchanged.
-//   b. forecast_forward_kernel<TASK, I, O> (per shape, Shape::forecast_fwd): fx[col][u] = y of trajectory u at column
+//   b. forecast_forward_kernel<TASK, I, O> (per shape, AnalysisShape::forecast_fwd): fx[col][u] = y of trajectory u at column
 //      col = origin * hb + k of a block of origins and horizon steps; the windows are carried from one horizon block to the next.
 //      With ForecastFwd::mu (ptnn_forecast_score) it also stores the output before the step's noise.
 //   c. predict_reduce_kernel, unchanged.

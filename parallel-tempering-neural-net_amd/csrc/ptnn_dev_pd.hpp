@@ -1,4 +1,4 @@
-// ptnn_dev_pd.hpp -- part of ptnn_device.hpp (textually included there, inside namespace ptnn; not a stand-alone header):
+// ptnn_dev_pd.hpp -- part of ptnn_analysis_device.hpp (textually included there, inside namespace ptnn; not a stand-alone header):
 // partial dependence and individual conditional expectation curves of the sampled nets (ptnn_partial_dependence, include/ptnn.h;
 // DESIGN.md section 25; Friedman 2001, Goldstein et al. 2015).  Nothing of the kind is in the reference.
 //
@@ -8,7 +8,7 @@
 //   hid  = sigmoid(zk_h)   a_o = sum_h hid W2[h,o] - B2[o]   s_o = sigmoid(a_o)   classification: p = softmax(s) (CLS:108-110)
 //
 // The three stages of ptnn_dev_predict.hpp, with another stage b:
-//   b. pd_forward_kernel<TASK, I, O> (per shape, Shape::pd_fwd): fx[col][u] = ICE of distinct vector u, column
+//   b. pd_forward_kernel<TASK, I, O> (per shape, AnalysisShape::pd_fwd): fx[col][u] = ICE of distinct vector u, column
 //      col = ((row * A + a) * G + k) * O + o of a block of input rows -- the layout of PredictFwd::fx, so stage c
 //      (predict_reduce_kernel, with O = 1 and no votes) takes the ICE columns as it takes the outputs.
 //   then per block of rows pd_rows_kernel (ICE summed over the rows per vector and (a, k, o), in double, carried across the blocks;
@@ -20,11 +20,8 @@
 // units in ascending order into accumulators of its own, so it does not depend on NV, on how the grid is cut into chunks, on the
 // tile slot the value falls in, on the block of rows or on the wave that computed it.
 //
-// The file has two parts.  ptnn_device.hpp includes the first: the constants, PdFwd and the per-shape kernel, which the shape
-// translation units instantiate.  ptnn_analysis.hip includes the file again with PTNN_PD_REDUCTIONS defined and gets the second:
-// the shape-independent kernels, which that object holds.
-#ifndef PTNN_PD_REDUCTIONS
-
+// This file holds the constants, PdFwd and stage b, which ptnn_analysis_shape.hip instantiates per shape; the shape-independent
+// kernels are ptnn_dev_pd_reduce.hpp, which ptnn_analysis.hip alone includes.
 constexpr int PD_THREADS = 256;          // 4 waves
 constexpr int PD_MAX_NV = 16;            // distinct vectors per forward work-group
 constexpr int PD_MAX_GRID = 64;          // grid values per input (PTNN_PD_MAX_GRID)
@@ -152,74 +149,3 @@ __global__ void __launch_bounds__(PD_THREADS) pd_forward_kernel(const PdFwd a) {
             a.fx[((((size_t)(r0 + l) * a.A + ai) * GO) + (size_t)k0 * O + ko) * a.U + u0 + v] = fin[(size_t)v * VS + ko * WAVE + l];
     }
 }
-
-#else  // PTNN_PD_REDUCTIONS: the shape-independent kernels (ptnn_analysis.hip, after ptnn_dev_select.hpp)
-
-// per distinct vector u and column c = (a * G + k) * O + o of a row: ICE summed over the rows of a block in ascending order, in
-// double, onto what the earlier blocks left -- the sum over all rows is the same whatever the block size.  One thread per (u, c),
-// reads coalesced along u.  After the last block: PD32 = the mean over the n_total rows as fp32.
-struct PdRows {
-    const float* fx;            // [nrows * AGO][U]
-    int U, AGO, nrows, last;
-    double n_total;
-    double* acc;                // [AGO][U], zeroed by the caller before the first block
-    float* pd32;                // [AGO][U]
-};
-
-__global__ void __launch_bounds__(PRED_THREADS) pd_rows_kernel(const PdRows r) {
-    const int ublocks = (r.U + PRED_THREADS - 1) / PRED_THREADS;
-    const int u = (int)(blockIdx.x % ublocks) * PRED_THREADS + threadIdx.x, c = (int)(blockIdx.x / ublocks);
-    if (u >= r.U) return;
-    const size_t k = (size_t)c * r.U + u;
-    double s = r.acc[k];
-    const float* f = r.fx + k;
-    const size_t stride = (size_t)r.AGO * r.U;
-    for (int n = 0; n < r.nrows; ++n) s += (double)f[n * stride];
-    r.acc[k] = s;
-    if (r.last) r.pd32[k] = (float)(s / r.n_total);
-}
-
-// per distinct vector u and (a, o): range = max_k PD32 - min_k PD32, the difference formed in double (exact) and rounded once
-struct PdRange {
-    const float* pd32;          // [A * G * O][U]
-    int U, A, G, O;
-    float* range;               // [A * O][U]
-};
-
-__global__ void __launch_bounds__(PRED_THREADS) pd_range_kernel(const PdRange r) {
-    const int ublocks = (r.U + PRED_THREADS - 1) / PRED_THREADS;
-    const int u = (int)(blockIdx.x % ublocks) * PRED_THREADS + threadIdx.x, ao = (int)(blockIdx.x / ublocks);
-    if (u >= r.U) return;
-    const int ai = ao / r.O, o = ao % r.O;
-    const float* p = r.pd32 + ((size_t)ai * r.G * r.O + o) * r.U + u;
-    const size_t stride = (size_t)r.O * r.U;
-    float mx = p[0], mn = p[0];
-    for (int k = 1; k < r.G; ++k) {
-        const float v = p[k * stride];
-        mx = fmaxf(mx, v);
-        mn = fminf(mn, v);
-    }
-    r.range[(size_t)ao * r.U + u] = (float)((double)mx - (double)mn);
-}
-
-// per column c = (a * G + k) * O + o, one work-group: the weighted mean over the distinct vectors of the double row means, a
-// fixed summation order for a given U
-struct PdMean {
-    const double* acc;          // [AGO][U]
-    const int* cnt;             // [U]
-    int U;
-    double n_total;
-    long long M;
-    double* mean;               // [AGO]
-};
-
-__global__ void __launch_bounds__(PRED_THREADS) pd_mean_kernel(const PdMean r) {
-    __shared__ double buf[PRED_THREADS];
-    const int tid = threadIdx.x, c = blockIdx.x;
-    double s = 0.0;
-    for (int u = tid; u < r.U; u += PRED_THREADS) s += (double)r.cnt[u] * (r.acc[(size_t)c * r.U + u] / r.n_total);
-    s = wg_sum<PRED_THREADS>(buf, s);
-    if (tid == 0) r.mean[c] = s / (double)r.M;
-}
-
-#endif

@@ -1,4 +1,4 @@
-// ptnn_dev_predict.hpp -- part of ptnn_device.hpp (textually included there, inside namespace ptnn; not a stand-alone header):
+// ptnn_dev_predict.hpp -- part of ptnn_analysis_device.hpp (textually included there, inside namespace ptnn; not a stand-alone header):
 // posterior predictive over sampled weight vectors (ptnn_predict, include/ptnn.h).
 //
 // The reference's drafts take the network outputs of every post-burn-in sample on the train and test rows and reduce them to
@@ -7,12 +7,12 @@
 //   a. sample_runs_kernel + predict_scan_kernel (ptnn_dev_select.hpp): the selected rows (trace rows of a list of chains, or uploaded vectors) are
 //      collapsed into DISTINCT vectors with integer multiplicities -- a rejected MH step repeats the previous vector (REG:417),
 //      so most selected rows repeat the one before; the output depends on w only, so one evaluation per run is exact.
-//   b. predict_forward_kernel<TASK, I, O> (per shape, Shape::predict_fwd): fx[col][u] = ForwardPass of distinct vector u on
+//   b. predict_forward_kernel<TASK, I, O> (per shape, AnalysisShape::predict_fwd): fx[col][u] = ForwardPass of distinct vector u on
 //      output column col = row * O + o of a block of input rows (REG:51-55 / CLS:49-55; CLS: softmax of it, CLS:108-110).
 //   c. predict_reduce_kernel (ptnn_dev_select.hpp): one work-group per column -- weighted mean (double), exact weighted order statistics (radix select
 //      on the order-preserving key of the fp32 value), and for classification the class-vote counts.
-// Nothing here writes chain state, tapes, counters or trace rows.  This file holds the constants, PredictFwd and stage b, which the
-// shape translation units instantiate.
+// Nothing here writes chain state, tapes, counters or trace rows.  This file holds the constants, PredictFwd and stage b, which
+// ptnn_analysis_shape.hip instantiates per shape.
 
 constexpr int PRED_THREADS = 256;        // forward and reduce kernels: 4 waves
 constexpr int PRED_SCAN_THREADS = 1024;  // the scan: one work-group

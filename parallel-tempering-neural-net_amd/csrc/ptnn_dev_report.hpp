@@ -1,6 +1,6 @@
 // ptnn_dev_report.hpp -- part of ptnn_analysis.hip (textually included there, inside namespace ptnn, after ptnn_dev_select.hpp;
 // not a stand-alone header): the classification report (ptnn_class_report, include/ptnn.h).  Every kernel is
-// shape-independent and reads the fx [row * K + class][u] image that Shape::predict_fwd wrote for a block of distinct samples
+// shape-independent and reads the fx [row * K + class][u] image that AnalysisShape::predict_fwd wrote for a block of distinct samples
 // (stride = the samples of the block), and the class of every row as an integer.  Per distinct sample u, exact integers:
 //   1. report_labels_kernel: the class of every data row as an int (-1: not an integer in [0, K)).
 //   2. report_confusion_kernel: conf[i * K + j][u] = rows of class i whose argmax over the K probabilities -- first index on a tie,

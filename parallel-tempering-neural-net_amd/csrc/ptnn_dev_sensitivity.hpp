@@ -1,4 +1,4 @@
-// ptnn_dev_sensitivity.hpp -- part of ptnn_device.hpp (textually included there, inside namespace ptnn; not a stand-alone header):
+// ptnn_dev_sensitivity.hpp -- part of ptnn_analysis_device.hpp (textually included there, inside namespace ptnn; not a stand-alone header):
 // input sensitivity of the sampled nets (ptnn_sensitivity, include/ptnn.h) -- the Jacobian of the network
 // output with respect to the inputs, per distinct weight vector and data row.  Nothing of the kind is in the reference.
 //
@@ -8,7 +8,7 @@
 //   classification (p = softmax(s), CLS:108-110):                g[c,i] = p_c (J[c,i] - sum_o p_o J[o,i])
 //
 // The three stages of ptnn_dev_predict.hpp, with another stage b:
-//   b. sensitivity_forward_kernel<TASK, I, O> (per shape, Shape::sens_fwd): gx[col][u] = g of distinct vector u, column
+//   b. sensitivity_forward_kernel<TASK, I, O> (per shape, AnalysisShape::sens_fwd): gx[col][u] = g of distinct vector u, column
 //      col = (row * O + o) * I + i of a block of input rows -- the layout of PredictFwd::fx, so stage c (predict_reduce_kernel) takes
 //      the gradient columns as it takes the outputs.
 //   then per block of rows sensitivity_sign_kernel (the weighted counts of g > 0 and g < 0 per column) and
@@ -16,11 +16,8 @@
 //   at the end sensitivity_mean_kernel (the weighted means of those sums over the vectors).
 // Nothing here writes chain state, tapes, counters or trace rows.
 //
-// The file has two parts.  ptnn_device.hpp includes the first: the constants, SensFwd and the per-shape kernel, which the shape
-// translation units instantiate.  ptnn_analysis.hip includes the file again with PTNN_SENSITIVITY_REDUCTIONS defined and gets the
-// second: the shape-independent kernels, which that object holds.
-#ifndef PTNN_SENSITIVITY_REDUCTIONS
-
+// This file holds the constants, SensFwd and stage b, which ptnn_analysis_shape.hip instantiates per shape; the shape-independent
+// kernels are ptnn_dev_sensitivity_reduce.hpp, which ptnn_analysis.hip alone includes.
 constexpr int SENS_THREADS = 256;        // 4 waves
 constexpr int SENS_MAX_NV = 16;          // distinct vectors per forward work-group
 constexpr int SENS_ACC = 40;             // gradient accumulators a lane holds in one pass over the hidden units
@@ -149,93 +146,3 @@ __global__ void __launch_bounds__(SENS_THREADS) sensitivity_forward_kernel(const
         if (v < nv && r0 + l < a.nrows) a.gx[((size_t)(r0 + l) * OI + oi) * a.U + u0 + v] = fin[(size_t)v * VS + oi * WAVE + l];
     }
 }
-
-#else  // PTNN_SENSITIVITY_REDUCTIONS: the shape-independent kernels (ptnn_analysis.hip, after ptnn_dev_select.hpp)
-
-// per column of a block: the samples, multiplicities counted, whose gradient is > 0 and < 0.  Integer counts: exact in any order.
-struct SensSign {
-    const float* gx;            // [ncols][U]
-    const int* cnt;             // [U]
-    int U;
-    long long col0;             // global index of the block's first column
-    long long* pos;             // [ncols_total]
-    long long* neg;
-};
-
-__global__ void __launch_bounds__(PRED_THREADS) sensitivity_sign_kernel(const SensSign r) {
-    __shared__ long long psum[PRED_THREADS], nsum[PRED_THREADS];
-    const int tid = threadIdx.x, col = blockIdx.x;
-    const float* f = r.gx + (size_t)col * r.U;
-    long long p = 0, n = 0;
-    for (int u = tid; u < r.U; u += PRED_THREADS) {
-        const float g = f[u];
-        const int c = r.cnt[u];
-        if (g > 0.0f) p += c;
-        if (g < 0.0f) n += c;
-    }
-    psum[tid] = p;
-    nsum[tid] = n;
-    __syncthreads();
-    wg_tree<PRED_THREADS>([&](int i, int j) { psum[i] += psum[j]; nsum[i] += nsum[j]; });
-    if (tid == 0) { r.pos[r.col0 + col] = psum[0]; r.neg[r.col0 + col] = nsum[0]; }
-}
-
-// per distinct vector u and (o, i): |g| and g^2 summed over the rows of a block in ascending order, in double, onto what the
-// earlier blocks left -- the sum over all rows is the same whatever the block size.  One thread per (u, oi), reads coalesced
-// along u.  After the last block: a_s = the mean of |g| over the n_total rows as fp32, for the rank pass.
-struct SensRows {
-    const float* gx;            // [nrows * OI][U]
-    int U, OI, nrows, last;
-    double n_total;
-    double* acc_abs;            // [OI][U], zeroed by the caller before the first block
-    double* acc_sq;
-    float* a32;                 // [OI][U]
-};
-
-__global__ void __launch_bounds__(PRED_THREADS) sensitivity_rows_kernel(const SensRows r) {
-    const int u = blockIdx.x * PRED_THREADS + threadIdx.x, oi = blockIdx.y;
-    if (u >= r.U) return;
-    const size_t k = (size_t)oi * r.U + u;
-    double sa = r.acc_abs[k], sq = r.acc_sq[k];
-    const float* g = r.gx + k;
-    const size_t stride = (size_t)r.OI * r.U;
-    for (int n = 0; n < r.nrows; ++n) {
-        const double v = (double)g[n * stride];
-        sa += fabs(v);
-        sq += v * v;
-    }
-    r.acc_abs[k] = sa;
-    r.acc_sq[k] = sq;
-    if (r.last) r.a32[k] = (float)(sa / r.n_total);
-}
-
-// per (o, i), one work-group: the weighted means over the distinct vectors of a_s and q_s (the row sums / n_total), in double, a
-// fixed summation order for a given U
-struct SensMean {
-    const double* acc_abs;      // [OI][U]
-    const double* acc_sq;
-    const int* cnt;             // [U]
-    int U;
-    double n_total;
-    long long M;
-    double* abs_mean;           // [OI]
-    double* sq_mean;
-};
-
-__global__ void __launch_bounds__(PRED_THREADS) sensitivity_mean_kernel(const SensMean r) {
-    __shared__ double asum[PRED_THREADS], qsum[PRED_THREADS];
-    const int tid = threadIdx.x, oi = blockIdx.x;
-    double sa = 0.0, sq = 0.0;
-    for (int u = tid; u < r.U; u += PRED_THREADS) {
-        const double c = (double)r.cnt[u];
-        sa += c * (r.acc_abs[(size_t)oi * r.U + u] / r.n_total);
-        sq += c * (r.acc_sq[(size_t)oi * r.U + u] / r.n_total);
-    }
-    asum[tid] = sa;
-    qsum[tid] = sq;
-    __syncthreads();
-    wg_tree<PRED_THREADS>([&](int i, int j) { asum[i] += asum[j]; qsum[i] += qsum[j]; });
-    if (tid == 0) { r.abs_mean[oi] = asum[0] / (double)r.M; r.sq_mean[oi] = qsum[0] / (double)r.M; }
-}
-
-#endif

@@ -1,4 +1,4 @@
-// ptnn_dev_shapley.hpp -- part of ptnn_device.hpp (textually included there, inside namespace ptnn; not a stand-alone header):
+// ptnn_dev_shapley.hpp -- part of ptnn_analysis_device.hpp (textually included there, inside namespace ptnn; not a stand-alone header):
 // coalition values of the sampled nets and linear functionals of them (ptnn_coalition_values, include/ptnn.h; DESIGN.md section 29;
 // Shapley 1953, Strumbelj & Kononenko 2014, Lundberg & Lee 2017: the interventional value function).  Nothing of the kind is in
 // the reference.
@@ -11,7 +11,7 @@
 // functionals of the game v.  The host builds the table (effects.py: shapley_table).
 //
 // The three stages of ptnn_dev_predict.hpp, with another stage b:
-//   b. shapley_forward_kernel<TASK, I, O> (per shape, a code object of its own: ShapShape::fwd): fx[col][u] = out of distinct vector
+//   b. shapley_forward_kernel<TASK, I, O> (per shape, AnalysisShape::shap_fwd): fx[col][u] = out of distinct vector
 //      u, column col = (row * O + o) * T + t of a block of explained rows -- the layout of PredictFwd::fx, so stage c
 //      (predict_reduce_kernel, with O = 1 and no votes) takes the columns as it takes the outputs.
 //   then per block of rows sensitivity_sign_kernel (out > 0, out < 0 per column) and sensitivity_rows_kernel (|out| summed over the
@@ -28,8 +28,7 @@
 //     order, one fma per coalition, so out depends on the table's order and the background's order and on nothing else.
 //   - the reductions over the samples depend on the multiset of samples only, as in every other analysis call.
 //
-// The file would have two parts like ptnn_dev_pd.hpp -- the per-shape kernel here, shape-independent kernels for ptnn_analysis.hip --
-// but the second is empty: the predict and sensitivity reductions provide every reduction this call makes.
+// (No ptnn_dev_shapley_reduce.hpp beside this file: the predict and sensitivity reductions provide every reduction this call makes.)
 
 constexpr int SHAP_THREADS = 256;            // 4 waves
 constexpr int SHAP_MAX_NV = 8;               // distinct vectors per forward work-group
@@ -54,9 +53,6 @@ struct ShapFwd {
     const double* coef;                 // [C][T]
     float* fx;                          // [nrows * O * T][U] column-major
 };
-
-// the per-shape table entry: one code object per shape (ptnn_shape.hip with -DPTNN_SHAP, symbol ptnn_shap_<T>_<I>_<O>)
-struct ShapShape { int task, I, O; void (*fwd)(const ShapFwd); };
 
 // One wave per (distinct vector, explained row) pair, the lanes over the background rows in chunks of 64.  NV vectors staged in
 // LDS, every weight read wave-uniform (an LDS broadcast); the explained row and the mask are uniform, the lane's background row

@@ -14,9 +14,8 @@
 // next interval -- one launch per run.  ptnn_diag.hpp is included by diagnostic builds only.
 // Everything included here is a template or inline, so every translation unit may include it.  A non-template __global__ kernel
 // lives in a part that exactly one translation unit includes, inside namespace ptnn after ptnn_shapes.hpp, and that object holds
-// it: ptnn_dev_swap.hpp in ptnn.hip; ptnn_dev_select.hpp, ptnn_dev_convergence.hpp, ptnn_dev_elpd.hpp, ptnn_dev_lfo.hpp, ptnn_dev_evidence.hpp,
-// ptnn_dev_calibration.hpp and the second parts of ptnn_dev_sensitivity.hpp and ptnn_dev_pd.hpp in ptnn_analysis.hip.
-// (ptnn_dev_shapley.hpp holds one template kernel and has no such part.)
+// it: ptnn_dev_swap.hpp in ptnn.hip; ptnn_dev_select.hpp and the other shape-independent analysis parts in ptnn_analysis.hip.
+// No analysis code is included here (ptnn_analysis_device.hpp includes this file): editing an analysis part leaves every sampler object as it is.
 //
 // Written for gfx950 only: wave size 64, DPP row operations, v_permlane{16,32}_swap.
 #pragma once
@@ -155,10 +154,5 @@ struct SegDyn {
 #include "ptnn_dev_wide.hpp"                 // wide nets (64 < H <= 512): sgd_sweep_wide, matrix-core forward, segment_wide_body, model_wide_kernel; then swap_block
 #include "ptnn_dev_tree.hpp"                 // prefetching tree schedule (segment_tree_body), with its own swap rounds inside a launch
 #include "ptnn_dev_kernels.hpp"              // model_kernel, persistent_loop, the __global__ segment kernels, the per-shape table
-#include "ptnn_dev_predict.hpp"              // posterior predictive: the per-shape forward pass (selection and reduction: ptnn_dev_select.hpp)
-#include "ptnn_dev_forecast.hpp"             // recursive multi-step forecasts: the per-shape recursive forward pass
-#include "ptnn_dev_sensitivity.hpp"          // input sensitivity: the per-shape forward pass that carries the derivative to the inputs (its second part: ptnn_analysis.hip)
-#include "ptnn_dev_pd.hpp"                   // partial dependence and ICE curves: the per-shape forward pass over substituted inputs (its second part: ptnn_analysis.hip)
-#include "ptnn_dev_shapley.hpp"              // coalition values (Shapley attributions): the per-shape forward pass over hybrid rows, a code object of its own per shape
 
 }  // namespace ptnn

@@ -1,6 +1,6 @@
-// ptnn_shapes.hpp -- the compiled (task, n_in, n_out) shapes and the per-shape kernel table.
+// ptnn_shapes.hpp -- the compiled (task, n_in, n_out) shapes and the per-shape table of the sampler's kernels.
 // Every shape is its own translation unit (ptnn_shape.hip with -DPTNN_T/-DPTNN_I/-DPTNN_O), so that the build can compile them
-// in parallel; ptnn.hip only references the tables (ptnn_analysis.hip and ptnn_checkpoint.hip reach them through the handle).
+// in parallel; ptnn.hip only references the tables (ptnn_checkpoint.hip: through the handle).  The per-shape analysis kernels are not here: AnalysisShape (ptnn_analysis_device.hpp).
 // Every fixed-width packed kernel (PTNN_PACK_FIXED, PTNN_PACKM_FIXED below) is one more translation unit of ptnn_shape.hip, with -DPTNN_HC on top.
 //
 // REG: the shipped time series have 4 lag inputs (REG:916); 5 and 32 cover BASELINE.json's literal [5,H,1] and the synthetic
@@ -45,9 +45,5 @@ struct Shape {
     int loops;              // which kernels carry the interval loop of a persistent launch: bit 0 seg, bit 1 pack (wide: always; spec, tree: never)
     int split_ch, split_kr; // split-operand forward pass (SplitK<I>): 16-byte chunks per image row (0: not available for this n_in), fp32 k-steps
     seg_fn packm;           // 9 <= H <= 16: packed schedule over several CUs per replica
-    void (*predict_fwd)(const PredictFwd);   // posterior predictive: network outputs of distinct vectors x input rows (every H)
-    void (*forecast_fwd)(const ForecastFwd); // recursive forecasts: trajectories x origins x horizon steps (REG, n_out == 1; else empty)
-    void (*sens_fwd)(const SensFwd);         // input sensitivity: d output / d input of distinct vectors x input rows (every H)
-    void (*pd_fwd)(const PdFwd);             // partial dependence: outputs of distinct vectors x input rows x substituted grid values (every H)
 };
 }  // namespace ptnn

@@ -1,5 +1,5 @@
 # A/B of two builds on ONE box: ab_bench.sh <old.so> [workload] [reps] [extra bench flags]   (new = the in-tree library)
-set -e
+set -eo pipefail    # a run that fails or times out ends the series: nothing more is started on the GPU after it
 OLD=$1; WL=${2:-sunspot64}; REPS=${3:-3}; EXTRA=${4:-}
 for i in $(seq $REPS); do
   for v in old new; do

@@ -17,6 +17,8 @@ for U in ptnn ptnn_analysis ptnn_checkpoint ptnn_text; do
     HOST="$HOST /tmp/ptnn_stamps_$U.o"
 done
 /opt/rocm/bin/hipcc $F -DPTNN_T=$T -DPTNN_I=$I -DPTNN_O=$O -DPTNN_SHAPE_SYMBOL=ptnn_shape_${T}_${I}_${O} -c -o /tmp/ptnn_stamps_shape.o $C/ptnn_shape.hip
+# the shape's analysis kernels: ptnn_analysis.o refers to their table
+/opt/rocm/bin/hipcc $F -DPTNN_T=$T -DPTNN_I=$I -DPTNN_O=$O -DPTNN_SHAPE_SYMBOL=ptnn_ashape_${T}_${I}_${O} -c -o /tmp/ptnn_stamps_ashape.o $C/ptnn_analysis_shape.hip
 for KIND in pack packm; do
     [ $KIND = pack ] && { LIST=$FIXED; MULTI=; } || { LIST=$FIXEDM; MULTI=-DPTNN_HC_MULTI; }
     for HC in $(echo "$LIST" | grep -o ',[0-9]*)' | tr -d ',)'); do
@@ -24,5 +26,5 @@ for KIND in pack packm; do
         HOST="$HOST /tmp/ptnn_stamps_${KIND}_fixed_$HC.o"
     done
 done
-/opt/rocm/bin/hipcc --offload-arch=gfx950 -shared -fPIC -o profiles/tools/libptnn_stamps.so $HOST /tmp/ptnn_stamps_shape.o
+/opt/rocm/bin/hipcc --offload-arch=gfx950 -shared -fPIC -o profiles/tools/libptnn_stamps.so $HOST /tmp/ptnn_stamps_shape.o /tmp/ptnn_stamps_ashape.o
 echo built profiles/tools/libptnn_stamps.so

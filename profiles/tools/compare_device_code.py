@@ -85,7 +85,7 @@ def sections_digest(co, tmp):
 
 
 def scan(build_dir):
-    objects, kernels = {}, {}
+    objects, found = {}, {}
     with tempfile.TemporaryDirectory() as tmp:
         for name in sorted(os.listdir(build_dir)):
             if not name.endswith(".o"):
@@ -96,8 +96,9 @@ def scan(build_dir):
                 continue
             objects[name] = sections_digest(co, tmp)
             for k, v in kernels_of(co).items():
-                kernels[(k, name if name.startswith("ptnn_shape_") else "")] = (name, v)
-    return objects, kernels
+                found.setdefault(k, []).append((name, v))
+    # a kernel's name carries its template arguments (T, I, O): a kernel that moved is matched by it; only a name that several objects of one build define is keyed by its object too
+    return objects, {(k, name if len(at) > 1 else ""): (name, v) for k, at in found.items() for name, v in at}
 
 
 def main():

@@ -351,3 +351,29 @@ def test_recorded_bf16_study_meets_its_stated_bounds():
     m = study["modes"]
     assert m["split"]["flips"] == 0 and m["exact"]["flips"] == 0 and m["split"]["chains_identical_to_exact"] == 128
     assert m["bf16"]["chains_identical_to_exact"] < 128 and m["bf16"]["flips"] > 0
+
+
+def test_sampler_objects_see_no_analysis_code(pt):
+    """The dependency files build() wrote: the sampler's objects include none of the analysis device code, so an edit to an analysis
+    part recompiles ptnn_analysis.o and the ptnn_ashape_* objects alone; those list all five per-shape forward parts."""
+    import __graft_entry__
+    csrc = __graft_entry__.CSRC
+    forward = {"ptnn_dev_%s.hpp" % n for n in ("predict", "forecast", "sensitivity", "pd", "shapley")}
+    # the parts of the sampler (ptnn_device.hpp, and ptnn_dev_swap.hpp of ptnn.hip); every other ptnn_dev_*.hpp is analysis code
+    sampler = {"ptnn_dev_%s.hpp" % n for n in ("math", "wg", "sweep_forward", "coop", "spec", "pack", "wide", "ladder", "tree", "kernels", "swap")}
+    analysis_only = {f for f in os.listdir(csrc) if re.fullmatch(r"ptnn_dev_\w+\.hpp", f)} - sampler | {"ptnn_analysis_device.hpp"}
+    assert forward | {"ptnn_dev_sensitivity_reduce.hpp", "ptnn_dev_pd_reduce.hpp", "ptnn_dev_select.hpp"} <= analysis_only
+    deps = {f[:-2]: {os.path.basename(p) for p in __graft_entry__._listed(os.path.join(csrc, "build", f))}
+            for f in os.listdir(os.path.join(csrc, "build")) if f.endswith(".d")}
+    seen = {"sampler": 0, "ashape": 0}
+    for unit, listed in deps.items():
+        if unit in ("ptnn", "ptnn_checkpoint") or re.match(r"ptnn_(shape|pack_fixed|packm_fixed)_\d", unit):
+            assert not listed & analysis_only, (unit, sorted(listed & analysis_only))
+            assert "ptnn_device.hpp" in listed, unit
+            seen["sampler"] += 1
+        elif unit.startswith("ptnn_ashape_") or unit == "ptnn_analysis":
+            assert forward <= listed, (unit, sorted(forward - listed))
+            seen["ashape"] += unit != "ptnn_analysis"
+    n = len(__graft_entry__.SHAPES)
+    assert seen == {"sampler": 2 + n + len(__graft_entry__.PACK_FIXED) + len(__graft_entry__.PACKM_FIXED), "ashape": n}, seen
+    assert "ptnn_analysis" in deps
