@@ -177,6 +177,7 @@ __device__ __forceinline__ int poll_reached(const unsigned* words, int n, unsign
 // replicas 0 .. k+1 alone -- not for the slowest of all R.  n counts the rounds of this launch.
 //   post   into slot n mod D of a ring of D = SWAP_RING_DEPTH rounds; once n >= D only after every replica has TAKEN round n - D
 //          (taken[j] >= n - D + 1 for all j: the row this overwrites has no reader left).  Then release, ready[k] = n + 1.
+//   draw   the uniforms of pairs 0 .. min(k+1, R-1) - 1 (cascade_uniforms), ahead of the wait.
 //   wait   ready[j] >= n + 1 for j <= min(k+1, R-1), acquire.
 //   decide cascade_lds_prefix over those min(k+2, R) rungs: src[k] is the full cascade's.  Replica R-1 (and R-2) run all R rungs;
 //          replica R-1 keeps the books block 0 keeps on the barrier path.
@@ -184,6 +185,7 @@ __device__ __forceinline__ int poll_reached(const unsigned* words, int n, unsign
 // Nobody waits for a replica above k+1, and the posted scalars are read from the tagged slot, never from the single-buffered
 // L_handoff: the timing invariant of the barrier path is not needed here.  Progress: the replica furthest behind (round m) waits
 // for posts of round m, and a post of round m waits for takes of round m - D only, which everybody has behind them.
+// smem: 3 R + 1 words of LDS that nobody needs across the hand-off -- the packed body says where (SegDynPipe::scratch).
 __device__ __forceinline__ bool swap_handoff(persist_cptr pp, const int flip, const int round, const unsigned n, int* error_flag, float* smem) {
     const int R = pp->sp.R, PS = pp->sp.PS, ROW = pp->ring_row;
     const int k = blockIdx.x;
@@ -220,20 +222,25 @@ __device__ __forceinline__ bool swap_handoff(persist_cptr pp, const int flip, co
         asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
         __hip_atomic_store(pp->ready + k, n + 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
     }
+    PTNN_DIAG(bd_ready);
     const int Rp = min(k + 2, R);
-    const int bad = __syncthreads_or(poll_reached(pp->ready, Rp, n + 1u, error_flag));
-    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent");              // nothing cached from before the others posted
-    if (bad) return false;
     float* const sL = smem;
     float* const sU = smem + R;
     int* const sSrc = reinterpret_cast<int*>(smem + 2 * R);
-    for (int j = threadIdx.x; j < Rp; j += blockDim.x) sL[j] = slot_L[j];
 #if defined(__HIP_DEVICE_COMPILE__)
     const SwapParams sp = pp->sp;
 #else
     const SwapParams sp{};
 #endif
-    const int nsw = cascade_lds_prefix(sp, Rp, round, sL, sU, sSrc, true);
+    // the round's uniforms depend on (pair, round) only: formed here, where a replica that waits has nothing else to do (the scratch
+    // is free: the barrier at the top is behind every wave)
+    cascade_uniforms(sp, Rp, round, sU);
+    const int bad = __syncthreads_or(poll_reached(pp->ready, Rp, n + 1u, error_flag));
+    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent");              // nothing cached from before the others posted
+    if (bad) return false;
+    PTNN_DIAG(bd_polled);
+    for (int j = threadIdx.x; j < Rp; j += blockDim.x) sL[j] = slot_L[j];
+    const int nsw = cascade_lds_prefix<true>(sp, Rp, round, sL, sU, sSrc, true);
     if (k == R - 1) {                                               // the whole cascade: the books of the round
         if (sp.src_out) for (int j = threadIdx.x; j < R; j += blockDim.x) sp.src_out[j] = sSrc[j];
         if (sp.src_log && round < sp.log_capacity)
@@ -261,6 +268,7 @@ __device__ __forceinline__ bool swap_handoff(persist_cptr pp, const int flip, co
         asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
         __hip_atomic_store(pp->taken + k, n + 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
     }
+    PTNN_DIAG(bd_taken);
     return true;
 }
 
@@ -291,6 +299,10 @@ __device__ __forceinline__ void persistent_loop(const SegParams& p0, const int s
     // optimiser did exactly that, at 30 - 45 vector registers per kernel
     int flip, lflip, round, cur = step_begin;
     unsigned phase = 0, epoch_add = 0;
+    // PIPE: what an interval behind a pipelined hand-off keeps of the one before it (SegDynPipe); the other kernels see SegDyn
+    using Dyn = std::conditional_t<PIPE, SegDynPipe, SegDyn>;
+    [[maybe_unused]] int carried = 0, carry_restage4 = 0, carry_ring_hi = 0;
+    [[maybe_unused]] float* carry_scratch = smem;
     {
         persist_cptr pp = persist_args();
         flip = pp->flip0; lflip = pp->lflip0; round = pp->round0;
@@ -312,11 +324,13 @@ __device__ __forceinline__ void persistent_loop(const SegParams& p0, const int s
         const SegParams p = p0;                                       // host pass of the compiler: never executed
 #endif
         {
-            SegDyn dyn;
+            Dyn dyn;
             dyn.pp = pp;
             dyn.w_state = pp->state[flip]; dyn.gd_w = pp->gd[flip]; dyn.gd_valid = pp->gd_valid[flip];
             dyn.epoch_base = p.epoch_base + epoch_add;
+            if constexpr (PIPE) { dyn.carried = carried; dyn.scratch = smem; dyn.restage4 = carry_restage4; dyn.ring_hi = carry_ring_hi; }
             body(p, dyn, cur, stop - cur);
+            if constexpr (PIPE) { carry_scratch = dyn.scratch; carry_restage4 = dyn.restage4; carry_ring_hi = dyn.ring_hi; }
         }
         epoch_add += (unsigned)(stop - cur) + 1u;                     // granule tags never repeat across intervals
         cur = stop;
@@ -324,11 +338,13 @@ __device__ __forceinline__ void persistent_loop(const SegParams& p0, const int s
         pp = persist_args();
         if constexpr (PIPE) {
             if (pp->pipeline) {                                       // no rendezvous of the whole grid: see swap_handoff
-                if (!swap_handoff(pp, flip, round, phase++, p.error_flag, smem)) { if (threadIdx.x == 0) atomicAdd(p.error_flag, 1); return; }
+                if (!swap_handoff(pp, flip, round, phase++, p.error_flag, carry_scratch)) { if (threadIdx.x == 0) atomicAdd(p.error_flag, 1); return; }
                 flip ^= 1;
                 round += 1;
+                carried = 1;
                 continue;
             }
+            carried = 0;                                              // swap_block's scratch below is the base of LDS: the image
         }
         if (!grid_barrier(pp->barrier, pp->nblocks, ++phase, p.error_flag)) { if (threadIdx.x == 0) atomicAdd(p.error_flag, 1); return; }
         if (xcd_block(p.G) % p.G == 0) {                              // the bodies' own (replica, group) of this work-group
@@ -374,7 +390,7 @@ __global__ void __launch_bounds__(MAX_THREADS) segment_spec_kernel(const SegPara
 }
 template <int TASK, int I, int O>
 __global__ void __launch_bounds__(PK_WAVES * WAVE) segment_pack_kernel(const SegParams p, const PersistParams pp, const int step_begin) {
-    persistent_loop<pack_has_loop<TASK, I, O>(), true>(p, step_begin, [](const SegParams& q, const SegDyn& d, int b, int n) {
+    persistent_loop<pack_has_loop<TASK, I, O>(), true>(p, step_begin, [](const SegParams& q, auto& d, int b, int n) {
         if (q.pk_nred == 4) segment_pack_body<TASK, I, O, 4>(q, d, b, n);
         else segment_pack_body<TASK, I, O, 3>(q, d, b, n);
     });
@@ -385,7 +401,7 @@ __global__ void __launch_bounds__(PK_WAVES * WAVE) segment_pack_kernel(const Seg
 template <int TASK, int I, int O, int HC>
 __global__ void __launch_bounds__(PK_WAVES * WAVE) segment_pack_kernel(const SegParams p, const PersistParams pp, const int step_begin) {
     static_assert(HC > 0 && HC <= 16, "a packed net has at most 16 hidden units");
-    persistent_loop<pack_has_loop<TASK, I, O>(), true>(p, step_begin, [](const SegParams& q, const SegDyn& d, int b, int n) {
+    persistent_loop<pack_has_loop<TASK, I, O>(), true>(p, step_begin, [](const SegParams& q, auto& d, int b, int n) {
         segment_pack_body<TASK, I, O, pack_nred(HC), false, HC>(q, d, b, n);
     });
 }

@@ -50,9 +50,13 @@ struct PackDims {
 // lane-group exponent of a compiled-in width (the host's choice for a run-time one: plan_launch)
 __host__ __device__ constexpr int pack_nred(int H) { return H <= 8 ? 3 : 4; }
 
-template <int TASK, int I, int O, int PK_NRED, bool MULTI = false, int HC = 0>
-__device__ __forceinline__ void segment_pack_body(const SegParams& p, const SegDyn& dyn, const int step_begin, const int n_steps) {
+// Dyn: SegDyn, or SegDynPipe from a kernel whose launch may run its swap rounds pipelined (persistent_loop<true, true>).  Then (CARRY)
+// an interval entered behind swap_handoff finds the data image and the tape ring in LDS as the interval before it left them, and
+// only the state, which the round may have moved, is loaded again.
+template <int TASK, int I, int O, int PK_NRED, bool MULTI = false, int HC = 0, class Dyn = SegDyn>
+__device__ __forceinline__ void segment_pack_body(const SegParams& p, Dyn& dyn, const int step_begin, const int n_steps) {
     constexpr int PK_NG = WAVE >> PK_NRED, PK_SLOTS = pack_slots(PK_NRED);
+    constexpr bool CARRY = !MULTI && std::is_same_v<std::remove_const_t<Dyn>, SegDynPipe>;
     using D = PackDims<HC, I, O>;
     static_assert(HC == 0 || (HC <= (1 << PK_NRED) && pack_nred(HC) == PK_NRED), "a compiled-in width runs in its own lane-group size");
     extern __shared__ __attribute__((aligned(16))) float smem[];
@@ -99,10 +103,17 @@ __device__ __forceinline__ void segment_pack_body(const SegParams& p, const SegD
     auto s_prop = [&](int s_) { return sl0 + (size_t)s_ * SLF; };
     auto s_pgd = [&](int s_) { return sl0 + (size_t)s_ * SLF + PS; };
 
+    [[maybe_unused]] bool carried = false;                  // CARRY: the image and the ring are the previous interval's
     {
         const float4* src = reinterpret_cast<const float4*>(p.data);
         float4* dst = reinterpret_cast<float4*>(xy);
-        for (int e = tid; e < ((Nall + 2) * D::IPY(p)) >> 2; e += nthr) dst[e] = src[e];
+        if constexpr (CARRY) {                              // behind a hand-off only what its scratch overwrote (none, as a rule)
+            carried = dyn.carried != 0;
+            const int n4 = carried ? dyn.restage4 : ((Nall + 2) * D::IPY(p)) >> 2;
+            for (int e = tid; e < n4; e += nthr) dst[e] = src[e];
+        } else {
+            for (int e = tid; e < ((Nall + 2) * D::IPY(p)) >> 2; e += nthr) dst[e] = src[e];
+        }
     }
     float* gw = dyn.w_state + (size_t)r * PS;
     for (int j = tid; j < PS; j += nthr) {
@@ -111,6 +122,7 @@ __device__ __forceinline__ void segment_pack_body(const SegParams& p, const SegD
         w_gd[j] = dyn.gd_w[(size_t)r * PS + j];
     }
     __syncthreads();
+    PTNN_DIAG(bd_staged);
 
     const float T = uni_f(p.temps[r]);
     float eta = (TASK == TASK_REG) ? uni_f(w_cur[P]) : 0.0f;
@@ -175,8 +187,18 @@ __device__ __forceinline__ void segment_pack_body(const SegParams& p, const SegD
             for (int j = lo + wi; j < hi; j += nw) tape_step<true>(p, gid, j, ring_n + (size_t)(j % RING) * PS, ring_s + (j % RING) * 4);
         }
     };
-    fill_ring(step_begin, step_begin + RING, wave, nwaves);
+    // Behind a hand-off the ring still holds steps [step_begin, dyn.ring_hi) of this replica's tape: a window never crosses a hand-off
+    // and a swap moves states, not tapes.  What is missing up to step_begin + RING is at most what the last window committed, no
+    // window reaches it before the first one has refilled the ring (ring_hi >= step_begin + PK_SLOTS), and that refill is the
+    // forward waves' fill_ring(ring_hi, i + RING) below, beside the epochs: the loop goes on as if it had not been left.
+    if constexpr (CARRY) {
+        carried = carried && dyn.ring_hi >= step_begin + PK_SLOTS && dyn.ring_hi <= step_begin + RING;
+        if (!carried) fill_ring(step_begin, step_begin + RING, wave, nwaves);
+    } else {
+        fill_ring(step_begin, step_begin + RING, wave, nwaves);
+    }
     int ring_hi = step_begin + RING;                        // first step whose tape is not in the ring yet
+    if constexpr (CARRY) { if (carried) ring_hi = dyn.ring_hi; }
     // MULTI: when the work-groups of this replica share an XCD, the rounds' verdicts and the accepted step travel through that XCD's L2
     // (granule_*_xcd); asked once per launch (xcd_handshake; tag epoch_base: the rounds use epoch_base + 1 ...; granules 32 .. 32 + G of
     // the verdict row, which the rounds never touch)
@@ -185,6 +207,7 @@ __device__ __forceinline__ void segment_pack_body(const SegParams& p, const SegD
         if (p.xcd_granules) xcd_local = xcd_handshake(xv + 32, G, grp, dyn.epoch_base, gverd);
     }
     __syncthreads();
+    PTNN_DIAG(bd_loop_head);
     // MULTI, one launch for several swap intervals (PersistParams::swap_inside): the swap round after a hand-off step runs inside the
     // launch, at the end of the round loop below -- the same protocol as the tree's (segment_tree_body), with the cached gradient and
     // its flag travelling beside the state as swap_block moves them
@@ -552,11 +575,24 @@ __device__ __forceinline__ void segment_pack_body(const SegParams& p, const SegD
             }
         }
     }
+    PTNN_DIAG(bd_loop_end);
     PTNN_DIAG(pack_flush);
+    PTNN_DIAG(bd_flush);
 
     if (failed) {
         if (tid == 0) atomicAdd(p.error_flag, 1);           // a bounded spin ran out: the host reports it
         return;
+    }
+    if constexpr (CARRY) {
+        // where a pipelined hand-off behind this interval may keep its 3 R + 1 words (sL, sU, sSrc): in the slot area, whose
+        // proposals are dead between two rounds, when they fit there -- then the next entry finds the whole image.  Otherwise at
+        // the base of the image, as before this was carried: the next entry copies that prefix again, and where the words reach
+        // past the slot area into the ring, it draws the whole ring again too.
+        const int need = 3 * pp->sp.R + 1, image = (Nall + 2) * D::IPY(p);
+        const bool fits = need <= PK_SLOTS * (int)SLF;
+        dyn.scratch = fits ? sl0 : smem;
+        dyn.restage4 = fits ? 0 : min((need + 3) >> 2, image >> 2);
+        dyn.ring_hi = (fits || need <= (int)(ring_n - smem)) ? ring_hi : step_begin;      // step_begin: below any later interval, i.e. none
     }
     if (grp != 0) return;                                   // every work-group holds the same state: the first one writes it back
     const int fl_end = (pp->flip0 + nx) & 1;               // every in-launch round flips the host's buffers

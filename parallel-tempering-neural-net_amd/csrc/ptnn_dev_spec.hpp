@@ -161,15 +161,27 @@ __host__ __device__ inline int xchg_row_floats(int PS) { return (2 * PS + 4 + 3)
 // Prefix form (R <= sp.R): the pass over the first R rungs only.  The uniforms are keyed by (pair, round) and the carried state only
 // moves up the ladder, so src[0 .. R-2] of a prefix run are the full run's; src[R-1] (the state still carried at the cut) and the
 // count in sSrc[R] are the prefix's own and no result of the round unless R == sp.R.
+// HAVE_U: sU already holds the uniforms of pairs 0 .. R-2 (cascade_uniforms: the same values, formed ahead of a wait by a caller that
+// has nothing else to do there); what is left is the pass over sL.
+__device__ __forceinline__ void cascade_uniforms(const SwapParams& sp, const int R, int round, float* sU) {
+    for (int k = threadIdx.x; k < R - 1; k += blockDim.x) {
+        uint32_t x[4];
+        philox4x32_10((uint32_t)k, (uint32_t)round, 0u, STREAM_SWAP, sp.seed_lo, sp.seed_hi, x);
+        sU[k] = (sp.rule == 1) ? u23(x[0]) : logf_fast(2.0f * u23(x[0]));      // as in cascade_lds_prefix, to the letter
+    }
+}
+template <bool HAVE_U = false>
 __device__ __forceinline__ int cascade_lds_prefix(const SwapParams& sp, const int R, int round, float* sL, float* sU, int* sSrc, bool have_L) {
-    for (int k = threadIdx.x; k < R; k += blockDim.x) {
-        if (!have_L) sL[k] = sp.L[(size_t)(sp.label_mode ? sp.slot_cur[k] : k) * sp.L_stride];    // k is a temperature index
-        if (k < R - 1) {
-            uint32_t x[4];
-            philox4x32_10((uint32_t)k, (uint32_t)round, 0u, STREAM_SWAP, sp.seed_lo, sp.seed_hi, x);
-            // rule 0 compares in the log domain (below): ln(2 u) is computed here, by all threads at once, instead of an exp inside
-            // the sequential chain
-            sU[k] = (sp.rule == 1) ? u23(x[0]) : logf_fast(2.0f * u23(x[0]));
+    if constexpr (!HAVE_U) {
+        for (int k = threadIdx.x; k < R; k += blockDim.x) {
+            if (!have_L) sL[k] = sp.L[(size_t)(sp.label_mode ? sp.slot_cur[k] : k) * sp.L_stride];    // k is a temperature index
+            if (k < R - 1) {
+                uint32_t x[4];
+                philox4x32_10((uint32_t)k, (uint32_t)round, 0u, STREAM_SWAP, sp.seed_lo, sp.seed_hi, x);
+                // rule 0 compares in the log domain (below): ln(2 u) is computed here, by all threads at once, instead of an exp inside
+                // the sequential chain
+                sU[k] = (sp.rule == 1) ? u23(x[0]) : logf_fast(2.0f * u23(x[0]));
+            }
         }
     }
     __syncthreads();
@@ -263,6 +275,21 @@ struct PersistParams {
     unsigned delay_ticks;
 };
 constexpr unsigned SWAP_RING_DEPTH = 4;
+
+// What the one-CU packed body and persistent_loop<LOOP, PIPE> tell each other beside SegDyn, so that an interval entered behind a
+// pipelined hand-off (swap_handoff) keeps what the launch already holds in LDS instead of building it again: the data image, which
+// never changes inside a launch, and the random tape ring, whose entries are keyed by (seed, replica, step) and stay with the replica
+// when a swap moves states.  A type of its own: the bodies of every other kernel keep seeing SegDyn, and keep their code.
+struct SegDynPipe : SegDyn {
+    // persistent_loop -> body
+    int carried;             // 1: entered behind swap_handoff in this launch -- the fields below are the previous interval's; 0: the
+                             // launch's first interval, or behind a grid-barrier round (swap_block's scratch is the image): build everything
+    // body -> persistent_loop -> swap_handoff and the next interval
+    float* scratch;          // 3 R + 1 words of LDS the hand-off may use: the body's slot area, dead between two rounds, when they fit
+                             // there (nothing to restage), else the base of the image as before
+    int restage4;            // float4s at the base of the image which that scratch overwrites and the next entry copies again (0: none)
+    int ring_hi;             // first step whose tape the ring does not hold; below the next interval's first step: the ring was overwritten
+};
 __host__ __device__ inline int swap_ring_row_floats(int PS) { return 2 * PS + 4; }     // PS is a multiple of 4: rows stay 16-byte aligned
 
 // The PersistParams of the launch, read from the kernel-argument segment where it lies (second argument, behind SegParams) through

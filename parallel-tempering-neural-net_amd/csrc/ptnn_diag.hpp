@@ -164,6 +164,30 @@ static __device__ unsigned long long fw_dbg[8];
         atomicAdd(p.stamps + 17 + 2 * r, stamp_rounds); \
     }
 
+// The boundary between two swap intervals of the pipelined rounds (swap_handoff and the packed body around it), thread 0 of
+// replica 0: cycles from the end of the body's round loop to the release of `ready` (0: write-back, post, drain), on to the end of
+// the poll (1: the wait for replicas 0 and 1), to the release of `taken` (2: uniforms, cascade, take, drain), to the barrier behind
+// staging and the state load of the re-entered body (3) and to the head of its round loop (4: the tape ring); [5] counts the
+// boundaries, [6] is the last stamp, [7] says that a hand-off lies behind the entry.  Flushed with the body's other stamps into
+// stamps[154 .. 159]; profiles/tools/stamps_pack.py prints them.
+static __device__ unsigned long long bd_dbg[8];
+#define PTNN_BD_POINT(q_) \
+    if (blockIdx.x == 0 && threadIdx.x == 0) { \
+        const unsigned long long t_ = __builtin_amdgcn_s_memtime(); \
+        __builtin_amdgcn_s_waitcnt(0xC07F); \
+        if ((q_) >= 0) bd_dbg[(q_) < 0 ? 0 : (q_)] += t_ - bd_dbg[6]; \
+        bd_dbg[6] = t_; \
+    }
+#define PTNN_DIAG_bd_loop_end PTNN_BD_POINT(-1)
+#define PTNN_DIAG_bd_ready PTNN_BD_POINT(0)
+#define PTNN_DIAG_bd_polled PTNN_BD_POINT(1)
+#define PTNN_DIAG_bd_taken PTNN_BD_POINT(2) if (blockIdx.x == 0 && threadIdx.x == 0) { bd_dbg[5] += 1; bd_dbg[7] = 1; }
+#define PTNN_DIAG_bd_staged if (blockIdx.x == 0 && threadIdx.x == 0 && bd_dbg[7]) { PTNN_BD_POINT(3) }
+#define PTNN_DIAG_bd_loop_head if (blockIdx.x == 0 && threadIdx.x == 0 && bd_dbg[7]) { PTNN_BD_POINT(4) bd_dbg[7] = 0; }
+#define PTNN_DIAG_bd_flush \
+    if (blockIdx.x == 0 && threadIdx.x == 0 && p.stamps) \
+        for (int q_ = 0; q_ < 6; ++q_) { atomicAdd(p.stamps + 154 + q_, bd_dbg[q_]); bd_dbg[q_] = 0; }
+
 #define PTNN_DIAG_tree_begin \
     const bool stamp_on = (lb == 0 && tid < WAVE); \
     unsigned long long stamp_acc[10] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0}; \

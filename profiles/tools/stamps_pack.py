@@ -34,6 +34,15 @@ for n, v in zip(["sweep: first instruction of the asm block", "sweep: first inst
 slack = (int(st[152]) - int(st[153])) % (1 << 64)
 slack -= (1 << 64) if slack >= (1 << 63) else 0
 print(f"    forward wave 0 waits for sweep wave 0 at the barrier behind the forward passes: {slack/max(rounds,1):9.0f} cyc/round (negative: the sweep wave waits)")
+# the boundary between two swap intervals of the pipelined rounds (ptnn_diag.hpp: bd_dbg), replica 0, thread 0
+nb = int(st[159])
+if nb:
+    bd = ["loop end -> ready released (write-back, post, drain)", "-> poll ended (waiting for replicas 0, 1)", "-> taken released (uniforms, cascade, take)",
+          "-> barrier behind staging and state load", "-> head of the round loop (tape ring)"]
+    for n, v in zip(bd, st[154:159]):
+        print(f"    boundary: {n:56s} {v/nb:9.0f} cyc  {v/nb/2.4e3:6.2f} us")
+    own = sum(int(v) for v in st[154:159]) - int(st[155])
+    print(f"    boundary: {nb} stamped, {own/nb:9.0f} cyc = {own/nb/2.4e3:.2f} us each without the wait")
 per = np.array(st[16:16+128], dtype=np.float64).reshape(64, 2)
 print('   per-replica us/interval:', np.round(per[:, 0]/nint/2.4e3).astype(int).tolist())
 print('   per-replica rounds/interval:', np.round(per[:, 1]/nint, 1).tolist())
