@@ -1295,6 +1295,66 @@ typedef struct ptnn_uncertainty_spec {
 
 int ptnn_uncertainty(ptnn_handle *h, const ptnn_uncertainty_spec *spec);
 
+/* ---- case influence: which data rows drive a prediction (nothing in the reference) ----
+ * For a posterior p(theta) ~ prior x prod_i p(y_i | theta)^{w_i}, d E[g] / d w_i at w = 1 is Cov_post(g, l_i) with l_i = log p(y_i |
+ * x_i, theta): cov[a, b] = the covariance over the samples of target column a with the log-likelihood of case row b, minus it the
+ * first-order effect of deleting the case; DESIGN.md section 30.  Samples: the expanded multiset of M selected rows, U distinct
+ * (w, eta) samples with integer counts c_u, selected, merged and refused exactly as ptnn_elpd's sources 1 and 2 (same rules and
+ * error texts: a regression's host vectors need eta, trace rows without a recorded eta are refused); or source 3, host matrices
+ * target_values [n_w, n_a] float32 and loglik [n_w, n_b] double with multiplicity and no forward pass, every host row a sample.
+ * Cases (sources 1, 2): case_source _TRAIN / _TEST or _HOST with case_x [n_cases, n_in + 1] (last column the target); column b of
+ * B = l of case row b, formed as ptnn_elpd forms it; n_b = n_cases.  Targets: target_kind PTNN_INFLUENCE_OUTPUT: target_x
+ * [n_targets, n_in], the fp32 outputs of ptnn_predict's forward pass widened to double, n_a = n_targets x n_out, column n x n_out
+ * + o; PTNN_INFLUENCE_LOGLIK: target_x [n_targets, n_in + 1], l of the target rows, n_a = n_targets.
+ * With m_a = (1/M) sum c_u A[a, u] (the sum taken of A - min A):
+ *   cov[a, b] = sum_u c_u (A[a, u] - m_a)(B[b, u] - m_b) / (M - 1), every product and sum in double: fused multiply-adds in
+ *   ascending u within chunks of 512 distinct samples, the chunks added in ascending order (no atomics);
+ *   target_mean, target_var [n_a], case_mean, case_var [n_b]: m and sum c_u (. - m)^2 / (M - 1) (ddof 1 over the expanded multiset).
+ * A result's bits depend on the list of distinct samples and their counts only: not on the row blocks, the grid or the scratch.
+ * Outputs, any may be NULL.  Refused: n_a x n_b > 2^27; M < 2; U > 65535 x 512; a host loglik that is not finite; target_values without loglik or
+ * the reverse, or either with w; an unknown target_kind; n_cases or n_targets < 1.
+ * Runs on the handle's stream behind everything queued and returns when done; the rows of A and B are processed in blocks whose
+ * scratch stays under $PTNN_INFLUENCE_SCRATCH_BYTES (read per call, default 1 GiB; the output matrix lies beside it), which
+ * changes no result.  Touches no chain state, tape, counter or trace row.  Not with a communicator attached (one GPU only). */
+#define PTNN_INFLUENCE_OUTPUT 0
+#define PTNN_INFLUENCE_LOGLIK 1
+#define PTNN_INFLUENCE_MAX_ELEMENTS (1 << 27)
+#define PTNN_INFLUENCE_KCHUNK 512
+
+typedef struct ptnn_influence_spec {
+    int32_t struct_bytes;         /* = sizeof(ptnn_influence_spec): ABI guard */
+    /* source 1: the trace (used when w == NULL and loglik == NULL) */
+    const int32_t *replicas;      /* local replica indices, or NULL = all */
+    int32_t n_replicas;           /* entries of replicas (ignored when NULL) */
+    int32_t step0, nsteps, thin;  /* trace rows step0, step0 + thin, ... < step0 + nsteps (thin >= 1) */
+    /* source 2: host vectors */
+    const float *w;               /* [n_w, P] or NULL */
+    const float *eta;             /* [n_w] log tau^2 (regression) */
+    const int32_t *multiplicity;  /* [n_w] >= 0, or NULL = 1 each (sources 2 and 3) */
+    int64_t n_w;
+    /* source 3: host matrices */
+    const float *target_values;   /* [n_w, n_a] or NULL */
+    const double *loglik;         /* [n_w, n_b] or NULL */
+    int32_t n_a, n_b;             /* source 3 only */
+    /* cases (sources 1 and 2) */
+    int32_t case_source;          /* PTNN_PREDICT_X_HOST | _TRAIN | _TEST */
+    int32_t n_cases;
+    const float *case_x;          /* [n_cases, n_in + 1] (host rows only) */
+    /* targets (sources 1 and 2) */
+    int32_t target_kind;          /* PTNN_INFLUENCE_OUTPUT | _LOGLIK */
+    int32_t target_source;        /* PTNN_PREDICT_X_HOST | _TRAIN | _TEST */
+    int32_t n_targets;
+    int32_t reserved_;
+    const float *target_x;        /* [n_targets, n_in] (OUTPUT) or [n_targets, n_in + 1] (LOGLIK) (host rows only) */
+    /* outputs */
+    double *cov;                  /* [n_a, n_b] */
+    double *target_mean, *target_var;   /* [n_a] */
+    double *case_mean, *case_var;       /* [n_b] */
+    int64_t *n_samples, *n_distinct;
+} ptnn_influence_spec;
+
+int ptnn_influence(ptnn_handle *h, const ptnn_influence_spec *spec);
+
 /* the HIP stream (hipStream_t) all of this handle's work is queued on: lets the caller order its collectives after the
  * segment / before the swap kernels on the device instead of synchronising the host */
 int ptnn_stream(ptnn_handle *h, void **hip_stream);

@@ -307,6 +307,25 @@ class UncertaintySpec(C.Structure):
     ]
 
 
+class InfluenceSpec(C.Structure):
+    """ptnn_influence_spec (include/ptnn.h)."""
+    _fields_ = _SELECTION + [
+        ("w", C.POINTER(C.c_float)), ("eta", C.POINTER(C.c_float)), ("multiplicity", C.POINTER(C.c_int32)), ("n_w", C.c_int64),
+        ("target_values", C.POINTER(C.c_float)), ("loglik", C.POINTER(C.c_double)), ("n_a", C.c_int32), ("n_b", C.c_int32),
+        ("case_source", C.c_int32), ("n_cases", C.c_int32), ("case_x", C.POINTER(C.c_float)),
+        ("target_kind", C.c_int32), ("target_source", C.c_int32), ("n_targets", C.c_int32), ("reserved_", C.c_int32),
+        ("target_x", C.POINTER(C.c_float)),
+        ("cov", C.POINTER(C.c_double)), ("target_mean", C.POINTER(C.c_double)), ("target_var", C.POINTER(C.c_double)),
+        ("case_mean", C.POINTER(C.c_double)), ("case_var", C.POINTER(C.c_double)),
+        ("n_samples", C.POINTER(C.c_int64)), ("n_distinct", C.POINTER(C.c_int64)),
+    ]
+
+
+INFLUENCE_OUTPUT, INFLUENCE_LOGLIK = 0, 1
+INFLUENCE_MAX_ELEMENTS = 1 << 27
+INFLUENCE_KCHUNK = 512                   # distinct samples per partial sum (csrc/ptnn_dev_influence.hpp: INFL_KCHUNK)
+
+
 class LadderAdaptSpec(C.Structure):
     """ptnn_ladder_adapt_spec (include/ptnn.h)."""
     _fields_ = [("struct_bytes", C.c_int32), ("rounds", C.c_int32), ("kappa0", C.c_double), ("t0", C.c_double)]
@@ -409,6 +428,7 @@ SYMBOLS = {
     "ptnn_prior_predictive": (C.c_int, [C.c_void_p, C.POINTER(PriorSpec)]),
     "ptnn_class_report": (C.c_int, [C.c_void_p, C.POINTER(ClassReportSpec)]),
     "ptnn_uncertainty": (C.c_int, [C.c_void_p, C.POINTER(UncertaintySpec)]),
+    "ptnn_influence": (C.c_int, [C.c_void_p, C.POINTER(InfluenceSpec)]),
 }
 
 
@@ -1094,6 +1114,45 @@ class Sampler:
         if out["aleatoric_var"] is not None:
             out["aleatoric_var"] = float(out["aleatoric_var"][0])
         return out
+
+    def influence(self, x="test", cases="train", *, of="prediction", replicas=None, step0=0, nsteps=None, thin=1, w=None, eta=None,
+                  multiplicity=None, values=None, loglik=None, cov=True):
+        """ptnn_influence: the covariance over the samples of every target column with every case row's log-likelihood, on the
+        device.  Source: the trace rows step0, step0 + thin, ... < step0 + nsteps of `replicas` (None = all), host vectors w
+        [n, P] with eta [n] (regression), or host matrices values [n, n_a] float32 and loglik [n, n_b] float64 (no forward pass;
+        x, cases and of are ignored); sources 2 and 3 take optional integer `multiplicity` [n].  cases: "train", "test" or rows
+        [n_cases, n_in + 1] (last column the target).  of "prediction": x = "train", "test" or rows [n_x, n_in], the target
+        columns are the outputs, n_a = n_x * n_out (row-major); of "loglik": x rows have n_in + 1 columns, the target columns are
+        their log-likelihoods, n_a = n_x.  -> dict(cov [n_a, n_b] (cov=True), target_mean, target_var [n_a], case_mean, case_var
+        [n_b], all float64, variances with ddof 1 over the expanded samples; n_samples, n_distinct)."""
+        spec, keep = _spec(InfluenceSpec), []
+        if values is not None or loglik is not None:
+            if values is None or loglik is None:
+                raise ValueError("values and loglik come together")
+            va, la = _f32(values), np.ascontiguousarray(loglik, dtype=np.float64)
+            if va.ndim != 2 or la.ndim != 2 or va.shape[0] != la.shape[0]:
+                raise ValueError(f"values must be [n_samples, n_a] and loglik [n_samples, n_b], got shapes {va.shape} and {la.shape}")
+            keep += [va, la]
+            spec.target_values, spec.loglik, spec.n_w = _ptr(va), _ptr(la, C.POINTER(C.c_double)), va.shape[0]
+            n_a, n_b = spec.n_a, spec.n_b = va.shape[1], la.shape[1]
+            self._multiplicity(spec, keep, multiplicity, (va.shape[0],), "multiplicity must have one entry per sample")
+        else:
+            kind = {"prediction": INFLUENCE_OUTPUT, "loglik": INFLUENCE_LOGLIK}.get(of)
+            if kind is None:
+                raise ValueError(f"of must be 'prediction' or 'loglik', not {of!r}")
+            spec.target_kind = kind
+            width = (self.cfg.n_in, "n_in columns") if kind == INFLUENCE_OUTPUT else (self.cfg.n_in + 1, "n_in inputs and the target")
+            self._rows(spec, keep, x, "x", width, fields=("target_source", "n_targets", "target_x"))
+            self._rows(spec, keep, cases, "cases", (self.cfg.n_in + 1, "n_in inputs and the target"), fields=("case_source", "n_cases", "case_x"))
+            self._samples(spec, keep, w=w, eta=eta, multiplicity=multiplicity, replicas=replicas, step0=step0, nsteps=nsteps, thin=thin,
+                          unit="sample")
+            n_a, n_b = spec.n_targets * (self.cfg.n_out if kind == INFLUENCE_OUTPUT else 1), spec.n_cases
+        if n_a * n_b > INFLUENCE_MAX_ELEMENTS:
+            raise ValueError(f"{n_a} target columns x {n_b} cases: at most 2^27 elements per call")
+        out = dict(cov=np.empty((n_a, n_b), np.float64) if cov else None, target_mean=np.empty(n_a), target_var=np.empty(n_a),
+                   case_mean=np.empty(n_b), case_var=np.empty(n_b))
+        _bind(spec, out)
+        return self._call(self.lib.ptnn_influence, spec, out)
 
     def sensitivity(self, x="test", *, replicas=None, step0=0, nsteps=None, thin=1, w=None, multiplicity=None, ranks=(), ranks2=(),
                     sample_abs=False, samples=False):

@@ -1,5 +1,5 @@
 // ptnn_analysis.hip -- the posterior analysis calls of libptnn.so: predict, convergence, rank_convergence, elpd, lfo, forecast, evidence, calibration,
-// forecast_score, sensitivity, partial_dependence, coalition_values, ppc, powerscale, prior_predictive, and the sample-selection path they share.  The shape-independent analysis kernels are defined in this object: it includes them.
+// forecast_score, sensitivity, partial_dependence, coalition_values, ppc, powerscale, prior_predictive, influence, and the sample-selection path they share.  The shape-independent analysis kernels are defined in this object: it includes them.
 #include "ptnn_shapes.hpp"                   // PTNN_SHAPES
 #include "ptnn_analysis_device.hpp"          // the per-shape forward kernels and their table, AnalysisShape
 namespace ptnn {
@@ -19,6 +19,7 @@ namespace ptnn {
 #include "ptnn_dev_pd_reduce.hpp"            // partial dependence: row sums, ranges and the weighted means of the row means
 #include "ptnn_dev_report.hpp"               // classification report: confusion counts, Mann-Whitney counts and metric columns per sample
 #include "ptnn_dev_uncertainty.hpp"          // predictive uncertainty: entropy per sample and its mean per row, variance per column, mean noise
+#include "ptnn_dev_influence.hpp"            // case influence: column moments and the tiled FP64 cross-covariance over the samples
 }  // namespace ptnn
 #include "ptnn_host.hpp"
 #include "ptnn_rank_plan.hpp"               // the blocks of ptnn_rank_convergence: host arithmetic, checked on its own
@@ -2881,6 +2882,192 @@ int ptnn_uncertainty(ptnn_handle* h, const ptnn_uncertainty_spec* spec) {
     HIP_TRY(fetch(s.aleatoric_var, d_noise, 1, st));
     if (int rc = wait_stream(h)) return rc;
     for (int c = 0; s.vote && c < ncols; ++c) s.vote[c] = (double)votes_h[(size_t)c] / (double)S;
+    return 0;
+}
+
+// ---- case influence (ptnn_dev_influence.hpp) ----
+static_assert(PTNN_INFLUENCE_KCHUNK == INFL_KCHUNK, "ptnn.h chunk length");
+
+int ptnn_influence(ptnn_handle* h, const ptnn_influence_spec* spec) {
+    // argument checks first: none of them needs the handle or a device
+    if (int rc = check_spec(spec, "ptnn_influence_spec")) return rc;
+    const ptnn_influence_spec& s = *spec;
+    const bool mat = s.target_values != nullptr || s.loglik != nullptr;      // source 3
+    if (mat && !(s.target_values && s.loglik)) return fail(-1, "host matrices: target_values and loglik come together");
+    if (mat && s.w) return fail(-1, "give host vectors w or host matrices (target_values, loglik), not both");
+    SampleSource src = source_of(s, mat || s.w != nullptr, s.eta);
+    const bool ll_target = s.target_kind == PTNN_INFLUENCE_LOGLIK;
+    const RowSource cases{s.case_source, s.case_x, s.n_cases, "case_source", "PTNN_PREDICT_X", "case_x", "n_cases"};
+    const RowSource targets{s.target_source, s.target_x, s.n_targets, "target_source", "PTNN_PREDICT_X", "target_x", "n_targets"};
+    if (int rc = check_source(src, "samples", true, "target_values and loglik")) return rc;
+    if (mat) {
+        if (s.n_a < 1 || s.n_b < 1) return fail(-1, "n_a = %d and n_b = %d must be >= 1", s.n_a, s.n_b);
+        if ((long long)s.n_a * s.n_b > PTNN_INFLUENCE_MAX_ELEMENTS)
+            return fail(-1, "n_a x n_b = %d x %d: at most 2^27 elements per call", s.n_a, s.n_b);
+    } else {
+        if (s.target_kind != PTNN_INFLUENCE_OUTPUT && !ll_target)
+            return fail(-1, "target_kind = %d is not PTNN_INFLUENCE_OUTPUT or _LOGLIK", s.target_kind);
+        if (int rc = check_rows(cases)) return rc;
+        if (int rc = check_rows(targets)) return rc;
+        if (s.n_cases < 1 || s.n_targets < 1) return fail(-1, "n_cases = %d and n_targets = %d must be >= 1", s.n_cases, s.n_targets);
+    }
+    if (int rc = count_host_samples(src)) return rc;
+    if (mat)
+        for (long long k = 0; k < src.n_items * s.n_b; ++k)
+            if (!std::isfinite(s.loglik[k])) return fail(-1, "loglik[%lld, %lld] = %g is not finite", k / s.n_b, k % s.n_b, s.loglik[k]);
+    if (int rc = check_handle(h, "ptnn_influence")) return rc;
+    const int I = h->cfg.n_in, O = h->cfg.n_out;
+    const bool reg = h->cfg.task == PTNN_TASK_REG;
+    const int cpr = mat || ll_target ? 1 : O;                   // target columns per target row
+    const long long rows_a = mat ? s.n_a : s.n_targets, n_b = mat ? s.n_b : s.n_cases, n_a = rows_a * cpr;
+    if (!mat) {
+        if (int rc = need_eta(h, src)) return rc;
+        if (int rc = fit_rows(h, cases)) return rc;
+        if (int rc = fit_rows(h, targets)) return rc;
+        if (!reg && s.case_source == PTNN_PREDICT_X_HOST)
+            if (int rc = check_labels(s.case_x, s.n_cases, I, O)) return rc;
+        if (!reg && ll_target && s.target_source == PTNN_PREDICT_X_HOST)
+            if (int rc = check_labels(s.target_x, s.n_targets, I, O)) return rc;
+        if (n_a * n_b > PTNN_INFLUENCE_MAX_ELEMENTS)
+            return fail(-1, "n_a x n_b = %lld x %lld: at most 2^27 elements per call", n_a, n_b);
+    }
+    if (int rc = select_samples(h, src, true, "a covariance (ddof 1) needs at least 2")) return rc;
+    const long long M = src.M;
+    if (s.n_samples) *s.n_samples = M;
+
+    if (int rc = start_device(h)) return rc;
+    hipStream_t st = h->stream;
+    DeviceScratch mem;
+    // stage a: the distinct samples and their counts; every host row of source 3 is a sample of its own
+    Distinct d;
+    const float *d_xc = nullptr, *d_xt = nullptr;
+    int xsc = 0, xst = 0, U = 0;
+    const int* d_cnt = nullptr;
+    ForwardPlan fwd;
+    if (mat) {
+        U = (int)src.n_items;
+        int* cnt = nullptr;
+        std::vector<int32_t> ones(s.multiplicity ? 0 : (size_t)U, 1);
+        HIP_TRY(mem.upload(&cnt, s.multiplicity ? s.multiplicity : ones.data(), (size_t)U, st));
+        if (int rc = wait_stream(h)) return rc;                 // `ones` dies at the end of this block
+        d_cnt = cnt;
+    } else {
+        if (int rc = upload_rows(h, mem, cases, I + 1, &d_xc, &xsc)) return rc;
+        if (int rc = upload_rows(h, mem, targets, I + (ll_target ? 1 : 0), &d_xt, &xst)) return rc;
+        if (int rc = distinct_samples(h, mem, src, true, true, &d)) return rc;
+        U = d.U;
+        d_cnt = d.run_cnt;
+        if (int rc = fwd.init(h, "case influence")) return rc;
+    }
+    if (s.n_distinct) *s.n_distinct = U;
+    if (U > 65535LL * INFL_KCHUNK) return fail(-1, "%d distinct samples: at most 65535 x %d per call", U, INFL_KCHUNK);     // grid.y
+
+    // The scratch: a quarter of the budget for the block of A (its double columns and, with a forward pass, its fp32 outputs), a
+    // quarter for the block of B, half for the partial tiles.  Blocks are whole rows; no sum is split by them.
+    const size_t budget = scratch_budget("PTNN_INFLUENCE_SCRATCH_BYTES");
+    const size_t col = (size_t)U * sizeof(double), img = (size_t)U * sizeof(float) * O;
+    const long long blk_a = row_block(budget / 4, mat ? col : img + col * cpr, rows_a);
+    const long long blk_b = row_block(budget / 4, mat ? col : img + col, n_b);
+    const int nchunks = (U + INFL_KCHUNK - 1) / INFL_KCHUNK;
+    const size_t tile_bytes = (size_t)nchunks * INFL_TILE * INFL_TILE * sizeof(double);
+    const auto tiles_of = [](long long n) { return (n + INFL_TILE - 1) / INFL_TILE; };
+    const long long tiles_max = tiles_of(blk_a * cpr) * tiles_of(blk_b);
+    const long long tiles_launch = std::max(1LL, std::min<long long>({(long long)(budget / 2 / tile_bytes), tiles_max, 65535LL}));
+    double *d_A = nullptr, *d_B = nullptr, *d_part = nullptr, *d_cov = nullptr;
+    double *d_ma = nullptr, *d_sa = nullptr, *d_mb = nullptr, *d_sb = nullptr;
+    float* d_fx = nullptr;
+    HIP_TRY(mem.alloc(&d_A, (size_t)blk_a * cpr * U));
+    HIP_TRY(mem.alloc(&d_B, (size_t)blk_b * U));
+    if (!mat) HIP_TRY(mem.alloc(&d_fx, (size_t)std::max(blk_a, blk_b) * O * U));
+    if (s.cov) HIP_TRY(mem.alloc(&d_part, (size_t)tiles_launch * nchunks * INFL_TILE * INFL_TILE));
+    if (s.cov) HIP_TRY(mem.alloc(&d_cov, (size_t)(n_a * n_b)));
+    HIP_TRY(mem.alloc(&d_ma, (size_t)n_a));
+    HIP_TRY(mem.alloc(&d_sa, (size_t)n_a));
+    HIP_TRY(mem.alloc(&d_mb, (size_t)n_b));
+    HIP_TRY(mem.alloc(&d_sb, (size_t)n_b));
+
+    // the columns [c0, c0 + nc) of a host matrix [U][ld] as a block [nc][U] of doubles on the device
+    std::vector<double> stage;
+    auto host_columns = [&](auto* m, long long ld, long long c0, int nc, double* dst) -> int {
+        stage.resize((size_t)nc * U);
+        for (int c = 0; c < nc; ++c)
+            for (int u = 0; u < U; ++u) stage[(size_t)c * U + u] = (double)m[(size_t)u * ld + c0 + c];
+        HIP_TRY(hipMemcpyAsync(dst, stage.data(), stage.size() * sizeof(double), hipMemcpyHostToDevice, st));
+        return wait_stream(h);                                  // `stage` is written again for the next block
+    };
+    // l of the rows [r0, r0 + nr) of x on every distinct sample, as ptnn_elpd forms it -> dst [nr][U]
+    ElpdRed la{};
+    la.mode = reg ? ELPD_REG : ELPD_CLS; la.fx = d_fx; la.eta = d.run_eta; la.cnt = d_cnt; la.U = U; la.O = O; la.S = M;
+    auto loglik_rows = [&](const float* x, int xs, long long r0, int nr, double* dst) -> int {
+        if (int rc = fwd.run(h, d.base, d.run_off, x, xs, (int)r0, nr, U, d_fx)) return rc;
+        la.y = x + I; la.ys = xs; la.row0 = (int)r0; la.ll_out = dst;
+        const long long n_ll = (long long)nr * U;
+        HIP_TRY(launch(elpd_loglik_kernel, dim3((unsigned)((n_ll + ELPD_THREADS - 1) / ELPD_THREADS)), dim3(ELPD_THREADS), 0, st, la, nr));
+        return 0;
+    };
+    auto moments = [&](const double* v, int nc, double* mean, double* ssd) -> int {
+        InflMoments ma{v, d_cnt, U, M, mean, ssd};
+        HIP_TRY(launch(influence_moments_kernel, dim3((unsigned)nc), dim3(INFL_THREADS), 0, st, ma));
+        return 0;
+    };
+    auto block_a = [&](long long r0, int nr) -> int {
+        if (mat) {
+            if (int rc = host_columns(s.target_values, s.n_a, r0, nr, d_A)) return rc;
+        } else if (ll_target) {
+            if (int rc = loglik_rows(d_xt, xst, r0, nr, d_A)) return rc;
+        } else {
+            if (int rc = fwd.run(h, d.base, d.run_off, d_xt, xst, (int)r0, nr, U, d_fx)) return rc;
+            const long long n = (long long)nr * O * U;
+            HIP_TRY(launch(influence_widen_kernel, dim3((unsigned)((n + INFL_THREADS - 1) / INFL_THREADS)), dim3(INFL_THREADS), 0, st,
+                           d_fx, d_A, n));
+        }
+        return moments(d_A, nr * cpr, d_ma + r0 * cpr, d_sa + r0 * cpr);
+    };
+    auto block_b = [&](long long r0, int nr) -> int {
+        if (mat) {
+            if (int rc = host_columns(s.loglik, s.n_b, r0, nr, d_B)) return rc;
+        } else {
+            if (int rc = loglik_rows(d_xc, xsc, r0, nr, d_B)) return rc;
+        }
+        return moments(d_B, nr, d_mb + r0, d_sb + r0);
+    };
+    // the covariance of the two resident blocks: the tiles in launches of at most tiles_launch, each finished before the next
+    auto block_cov = [&](long long ra0, int nra, long long rb0, int nrb) -> int {
+        const int na = nra * cpr, tiles_b = (int)tiles_of(nrb);
+        const long long tiles = tiles_of(na) * tiles_b;
+        for (long long t0 = 0; t0 < tiles; t0 += tiles_launch) {
+            const unsigned nt = (unsigned)std::min(tiles_launch, tiles - t0);
+            InflCov ca{d_A, d_B, d_ma + ra0 * cpr, d_mb + rb0, d_cnt, na, nrb, U, tiles_b, (int)t0, nchunks, d_part};
+            HIP_TRY(launch(influence_cov_kernel, dim3(nt, (unsigned)nchunks), dim3(INFL_THREADS), 0, st, ca));
+            InflFinish fa{d_part, nchunks, tiles_b, (int)t0, na, nrb, n_b, (double)(M - 1), d_cov + (size_t)(ra0 * cpr) * n_b + rb0};
+            HIP_TRY(launch(influence_finish_kernel, dim3(nt, INFL_TILE * INFL_TILE / INFL_THREADS), dim3(INFL_THREADS), 0, st, fa));
+        }
+        return 0;
+    };
+    // B stays resident when one block holds it; else every block of A meets every block of B, formed again (the same bits)
+    const bool b_once = blk_b >= n_b;
+    if (b_once || !s.cov)                                       // (without cov: the case moments alone)
+        if (int rc = each_block(n_b, blk_b, block_b)) return rc;
+    if (s.cov || s.target_mean || s.target_var) {
+        if (int rc = each_block(rows_a, blk_a, [&](long long ra0, int nra) -> int {
+            if (int rc = block_a(ra0, nra)) return rc;
+            if (!s.cov) return 0;
+            return each_block(n_b, blk_b, [&](long long rb0, int nrb) -> int {
+                if (!b_once)
+                    if (int rc = block_b(rb0, nrb)) return rc;
+                return block_cov(ra0, nra, rb0, nrb);
+            });
+        })) return rc;
+    }
+    std::vector<double> ssd_a(s.target_var ? (size_t)n_a : 0), ssd_b(s.case_var ? (size_t)n_b : 0);
+    HIP_TRY(fetch(s.cov, d_cov, (size_t)(n_a * n_b), st));
+    HIP_TRY(fetch(s.target_mean, d_ma, (size_t)n_a, st));
+    HIP_TRY(fetch(s.case_mean, d_mb, (size_t)n_b, st));
+    HIP_TRY(fetch(s.target_var ? ssd_a.data() : nullptr, d_sa, (size_t)n_a, st));
+    HIP_TRY(fetch(s.case_var ? ssd_b.data() : nullptr, d_sb, (size_t)n_b, st));
+    if (int rc = wait_stream(h)) return rc;
+    for (size_t c = 0; c < ssd_a.size(); ++c) s.target_var[c] = ssd_a[c] / (double)(M - 1);
+    for (size_t c = 0; c < ssd_b.size(); ++c) s.case_var[c] = ssd_b[c] / (double)(M - 1);
     return 0;
 }
 

@@ -42,6 +42,9 @@ from .report import ClassificationReport, auc_pairs, confusion_matrix, report_na
 # predictive uncertainty lives in uncertainty.py; the result tuple and its host helpers are importable from here
 from .uncertainty import UncertaintyAnalysis
 from .uncertainty import Uncertainty, risk_coverage, uncertainty_compare, uncertainty_scores  # noqa: F401
+# case influence lives in influence.py; the result tuple and its host helper are importable from here
+from .influence import InfluenceAnalysis
+from .influence import CaseInfluence, influence_flagged  # noqa: F401
 # forecast verification lives in verification.py; the result tuple, forecast_compare and the host helpers are importable from here
 from .verification import VerificationAnalysis
 from .verification import (  # noqa: F401
@@ -140,7 +143,8 @@ def overlap_cuts(S, swap_interval, chunks):
     return sorted({min(S - 1, si * max(1, round(n_int * (c + 1) / K))) for c in range(K - 1)} | {S - 1})
 
 
-class ParallelTemperingBase(PosteriorAnalysis, PriorAnalysis, EffectAnalysis, ReportAnalysis, UncertaintyAnalysis, VerificationAnalysis):
+class ParallelTemperingBase(PosteriorAnalysis, PriorAnalysis, EffectAnalysis, ReportAnalysis, UncertaintyAnalysis, InfluenceAnalysis,
+                            VerificationAnalysis):
     task = None                       # set by the two drop-in subclasses
     rmse_fmt = None                   # REG '%1.8f' (REG:462-464), CLS '%1.2f' (CLS:473-475)
 
