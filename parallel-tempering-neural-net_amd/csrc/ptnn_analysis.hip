@@ -541,19 +541,211 @@ template <class Spec> int pointwise_fit(const ptnn_handle* h, const Spec& s, con
     if (s.x_source == PTNN_PREDICT_X_HOST && h->cfg.task != PTNN_TASK_REG) return check_labels(s.x, s.n_rows, I, O);
     return 0;
 }
+// the counts of n host samples that are each their own entry, on the device: their multiplicities, or ones
+int upload_counts(ptnn_handle* h, DeviceScratch& mem, const int32_t* multiplicity, size_t n, int** d_cnt) {
+    std::vector<int32_t> ones(multiplicity ? 0 : n, 1);
+    HIP_TRY(mem.upload(d_cnt, multiplicity ? multiplicity : ones.data(), n, h->stream));
+    return multiplicity ? 0 : wait_stream(h);            // `ones` dies at the end of this function
+}
 // the host loglik on the device: every host sample is its own entry of `ra` (repeats need no merging: the reductions depend on the
 // multiset only)
 template <class Spec> int upload_loglik(ptnn_handle* h, DeviceScratch& mem, const Spec& s, long long n_items, ElpdRed* ra) {
     double* d_ll = nullptr;
     int* d_cnt = nullptr;
     HIP_TRY(mem.upload(&d_ll, s.loglik, (size_t)n_items * s.n_rows, h->stream));
-    std::vector<int32_t> ones(s.multiplicity ? 0 : (size_t)n_items, 1);
-    HIP_TRY(mem.upload(&d_cnt, s.multiplicity ? s.multiplicity : ones.data(), (size_t)n_items, h->stream));
-    if (!s.multiplicity)
-        if (int rc = wait_stream(h)) return rc;          // `ones` dies at the end of this function
+    if (int rc = upload_counts(h, mem, s.multiplicity, (size_t)n_items, &d_cnt)) return rc;
     ra->mode = ELPD_HOST; ra->ll = d_ll; ra->ll_stride = s.n_rows; ra->cnt = d_cnt; ra->U = (int)n_items;
     return 0;
 }
+// elpd_loglik_kernel on the block of `nr` rows that `ra` names -> ra.ll_out [nr][U]
+int loglik_block(ptnn_handle* h, const ElpdRed& ra, int nr) {
+    const long long n_ll = (long long)nr * ra.U;
+    HIP_TRY(launch(elpd_loglik_kernel, dim3((unsigned)((n_ll + ELPD_THREADS - 1) / ELPD_THREADS)), dim3(ELPD_THREADS), 0, h->stream, ra, nr));
+    return 0;
+}
+
+// The log-likelihood of the rows [r0, r0 + nr) of x (the target behind the n_in inputs) on every distinct sample, as ptnn_elpd forms
+// it -> dst [nr][U]: the forward pass into fx, then elpd_loglik_kernel; the caller's `ra` names the task, eta and the counts
+int loglik_rows(ptnn_handle* h, const ForwardPlan& fwd, const Distinct& d, const float* x, int xs, long long r0, int nr, float* fx,
+                double* dst, ElpdRed ra) {
+    if (int rc = fwd.run(h, d.base, d.run_off, x, xs, (int)r0, nr, ra.U, fx)) return rc;
+    ra.fx = fx; ra.y = x + h->cfg.n_in; ra.ys = xs; ra.row0 = (int)r0; ra.ll_out = dst;
+    return loglik_block(h, ra, nr);
+}
+
+// The frame of the calls that take input rows x and weight vectors w -- predict, sensitivity, partial_dependence, coalition_values,
+// class_report -- in three steps, since the order of the refusals is kept and every call has checks of its own between them: the
+// checks before the handle, the samples selected with the handle, the rows and the distinct samples on the device.
+struct RowsByVectors {
+    SampleSource src;
+    RowSource rows;
+    RankOutputs rk, rk2;                    // rk2: the ranks of a second quantity, for the calls that have one
+    long long M = 0;                        // select: the samples, multiplicities counted
+    DeviceScratch mem;                      // stage: every buffer of the call
+    const float* d_x = nullptr;             // stage: row k at d_x + k * xs
+    int xs = 0, U = 0;
+    Distinct d;
+    std::vector<int> item_run;              // items: the sample of every item, for the selection-order outputs
+    template <class Spec> RowsByVectors(const Spec& s, RankOutputs rk, RankOutputs rk2 = RankOutputs{0, nullptr, nullptr})
+        : src(source_of(s, s.w != nullptr, nullptr)), rows{s.x_source, s.x, s.n_rows, "x_source", "PTNN_PREDICT_X", "x", "n_rows"},
+          rk(rk), rk2(rk2) {}
+    // no handle needed; `one_grid`: the rows are one dimension of a grid of WAVE-row work-groups
+    int check(bool one_grid = false) const {
+        if (int rc = check_source(src, "vectors")) return rc;
+        if (int rc = check_rows(rows)) return rc;
+        if (rows.n < 1) return fail(-1, "n_rows = %d must be >= 1", rows.n);
+        if (one_grid && rows.n > 65535 * WAVE) return fail(-1, "n_rows = %d: at most 65535 x 64 rows per call", rows.n);
+        if (int rc = rk.check()) return rc;
+        return rk2.check();
+    }
+    int select(const ptnn_handle* h, int64_t* n_samples) {
+        if (int rc = select_samples(h, src, false)) return rc;
+        M = src.M;
+        if (int rc = rk.check_values(M)) return rc;
+        if (int rc = rk2.check_values(M)) return rc;
+        if (n_samples) *n_samples = M;
+        return 0;
+    }
+    // rows of `width` floats; `uploads` queues the call's own tables between the rows and the run-length pass
+    template <class F> int stage(ptnn_handle* h, int width, int64_t* n_distinct, F uploads) {
+        if (int rc = start_device(h)) return rc;
+        if (int rc = upload_rows(h, mem, rows, width, &d_x, &xs)) return rc;
+        if (int rc = uploads()) return rc;
+        if (int rc = distinct_samples(h, mem, src, false, true, &d)) return rc;
+        U = d.U;
+        if (n_distinct) *n_distinct = U;
+        return 0;
+    }
+    int stage(ptnn_handle* h, int width, int64_t* n_distinct) { return stage(h, width, n_distinct, [] { return 0; }); }
+    int items(ptnn_handle* h, bool wanted) { return wanted ? item_runs(h, d, src.n_items, &item_run) : 0; }
+};
+
+// The columns of such a call, `ncols` in all, a block fx [nc][U] at a time: their weighted mean and the order statistics f.rk over the
+// samples, and the values of every selected sample in the selection's order.  An output costs device work only when its pointer
+// is given.
+struct Columns {
+    ptnn_handle* h;
+    RowsByVectors& f;
+    int ncols;
+    double* mean;                           // the caller's outputs, each may be null
+    float *order_stats, *samples;
+    double* d_mean = nullptr;
+    int alloc() {
+        if (!order_stats) f.rk.n = 0;
+        if (mean || order_stats) HIP_TRY(f.mem.alloc(&d_mean, (size_t)ncols));
+        return f.rk.to_device(f.mem, (size_t)ncols, h->stream);
+    }
+    int reduce(const float* fx, long long col0, long long nc) const {
+        if (!d_mean) return 0;
+        PredictRed ra{fx, f.d.run_cnt, f.U, 1, (int)col0, ncols, f.M, f.rk.n, f.rk.d_ranks, d_mean, f.rk.d_stats, nullptr};
+        HIP_TRY(launch(predict_reduce_kernel, dim3((unsigned)nc), dim3(PRED_THREADS), 0, h->stream, ra));
+        return 0;
+    }
+    int scatter(const float* fx, long long col0, long long nc) const {
+        return samples ? scatter_samples(h, fx, (int)nc, f.U, f.item_run, f.src.weights(), samples, (size_t)ncols, (size_t)col0) : 0;
+    }
+    int fetch() const {
+        HIP_TRY(::fetch(mean, d_mean, (size_t)ncols, h->stream));
+        HIP_TRY(::fetch(order_stats, f.rk.d_stats, (size_t)f.rk.n * ncols, h->stream));
+        return 0;
+    }
+};
+
+// What ptnn_sensitivity and ptnn_coalition_values make of C signed columns per row: per column the mean, order statistics and
+// sign counts over the samples; per column of a row (c < C) the weighted mean over the samples of the row means of |.| and (.)^2,
+// the exact ranks f.rk2 of the fp32 row mean a_s of |.|, and a_s of every selected sample.
+struct SignedColumns {
+    ptnn_handle* h;
+    RowsByVectors& f;
+    int n_rows, C;
+    Columns cols;
+    int64_t *pos_count, *neg_count;         // the caller's outputs, each may be null
+    double *abs_mean, *sq_mean;
+    float *abs_order_stats, *sample_abs;
+    long long rows_blk = 0;                 // alloc: rows per block, and the block fx [rows_blk * C][U]
+    float* fx = nullptr;
+    double *d_acc_abs = nullptr, *d_acc_sq = nullptr, *d_abs_mean = nullptr, *d_sq_mean = nullptr, *d_a32_mean = nullptr;
+    float* d_a32 = nullptr;
+    long long *d_pos = nullptr, *d_neg = nullptr;
+    bool signs() const { return pos_count || neg_count; }
+    bool sums() const { return abs_mean || sq_mean || abs_order_stats || sample_abs; }
+    // fx under the budget $budget_var; ends with the sample of every item queued, where a selection-order output is asked for
+    int alloc(const char* budget_var) {
+        hipStream_t st = h->stream;
+        const int U = f.U;
+        if (!abs_order_stats) f.rk2.n = 0;
+        HIP_TRY(f.mem.alloc(&d_pos, signs() ? (size_t)cols.ncols : 0));
+        HIP_TRY(f.mem.alloc(&d_neg, signs() ? (size_t)cols.ncols : 0));
+        if (int rc = cols.alloc()) return rc;
+        if (int rc = f.rk2.to_device(f.mem, (size_t)C, st)) return rc;
+        if (sums()) {       // per column c and distinct vector: the row sums of |.| and (.)^2, carried across the blocks of rows
+            HIP_TRY(f.mem.alloc(&d_acc_abs, (size_t)C * U));
+            HIP_TRY(f.mem.alloc(&d_acc_sq, (size_t)C * U));
+            HIP_TRY(f.mem.alloc(&d_a32, (size_t)C * U));
+            HIP_TRY(f.mem.alloc(&d_abs_mean, (size_t)C));
+            HIP_TRY(f.mem.alloc(&d_sq_mean, (size_t)C));
+            HIP_TRY(f.mem.alloc(&d_a32_mean, (size_t)C));
+            HIP_TRY(hipMemsetAsync(d_acc_abs, 0, (size_t)C * U * sizeof(double), st));
+            HIP_TRY(hipMemsetAsync(d_acc_sq, 0, (size_t)C * U * sizeof(double), st));
+        }
+        rows_blk = row_block(scratch_budget(budget_var), (size_t)U * sizeof(float) * C, n_rows);
+        HIP_TRY(f.mem.alloc(&fx, (size_t)rows_blk * C * U));
+        return f.items(h, cols.samples || sample_abs);
+    }
+    // rows [r0, r0 + nr), whose columns the forward pass has left in fx
+    int block(long long r0, int nr) const {
+        hipStream_t st = h->stream;
+        const int U = f.U;
+        if (int rc = cols.reduce(fx, r0 * C, (long long)nr * C)) return rc;
+        if (signs()) {
+            SensSign sa{fx, f.d.run_cnt, U, r0 * C, d_pos, d_neg};
+            HIP_TRY(launch(sensitivity_sign_kernel, dim3((unsigned)(nr * C)), dim3(PRED_THREADS), 0, st, sa));
+        }
+        if (sums()) {
+            SensRows rw{fx, U, C, nr, r0 + nr == n_rows ? 1 : 0, (double)n_rows, d_acc_abs, d_acc_sq, d_a32};
+            HIP_TRY(launch(sensitivity_rows_kernel, dim3((unsigned)((U + PRED_THREADS - 1) / PRED_THREADS), (unsigned)C), dim3(PRED_THREADS), 0, st, rw));
+        }
+        return cols.scatter(fx, r0 * C, (long long)nr * C);
+    }
+    // the weighted means of the row sums (double), the exact ranks of the fp32 a_s, and every output to the caller
+    int finish() {
+        hipStream_t st = h->stream;
+        const int U = f.U;
+        if (abs_mean || sq_mean) {
+            SensMean ma{d_acc_abs, d_acc_sq, f.d.run_cnt, U, (double)n_rows, f.M, d_abs_mean, d_sq_mean};
+            HIP_TRY(launch(sensitivity_mean_kernel, dim3((unsigned)C), dim3(PRED_THREADS), 0, st, ma));
+        }
+        if (f.rk2.n) {
+            PredictRed ra{d_a32, f.d.run_cnt, U, 1, 0, C, f.M, f.rk2.n, f.rk2.d_ranks, d_a32_mean, f.rk2.d_stats, nullptr};
+            HIP_TRY(launch(predict_reduce_kernel, dim3((unsigned)C), dim3(PRED_THREADS), 0, st, ra));
+        }
+        if (sample_abs)
+            if (int rc = scatter_samples(h, d_a32, C, U, f.item_run, f.src.weights(), sample_abs, (size_t)C, 0)) return rc;
+        if (int rc = cols.fetch()) return rc;
+        HIP_TRY(fetch((long long*)pos_count, d_pos, (size_t)cols.ncols, st));
+        HIP_TRY(fetch((long long*)neg_count, d_neg, (size_t)cols.ncols, st));
+        HIP_TRY(fetch(abs_mean, d_abs_mean, (size_t)C, st));
+        HIP_TRY(fetch(sq_mean, d_sq_mean, (size_t)C, st));
+        HIP_TRY(fetch(abs_order_stats, f.rk2.d_stats, (size_t)f.rk2.n * C, st));
+        return wait_stream(h);
+    }
+};
+
+// The votes of the pooled classifier (votes_h on the host): predict_reduce_kernel counts them per column as integers -- exact
+// whatever the order -- in `d`; the host divides by the samples.
+struct PooledVotes {
+    long long* d = nullptr;                 // [ncols], PredictRed's votes; null: a regression
+    std::vector<long long> counts;
+    hipError_t alloc(DeviceScratch& mem, size_t ncols) { return mem.alloc(&d, ncols); }
+    hipError_t fetch(bool wanted, size_t ncols, hipStream_t st) {      // queued: valid after the next wait_stream
+        counts.resize(wanted ? ncols : 0);
+        return ::fetch(wanted ? counts.data() : nullptr, d, ncols, st);
+    }
+    double share(size_t c, long long M) const { return (double)counts[c] / (double)M; }
+    void shares(double* vote, long long M) const {
+        for (size_t c = 0; vote && c < counts.size(); ++c) vote[c] = share(c, M);
+    }
+};
 }  // namespace
 
 extern "C" {
@@ -563,59 +755,45 @@ int ptnn_predict(ptnn_handle* h, const ptnn_predict_spec* spec) {
     // argument checks first: none of them needs the handle or a device
     if (int rc = check_spec(spec, "ptnn_predict_spec")) return rc;
     const ptnn_predict_spec& s = *spec;
-    SampleSource src = source_of(s, s.w != nullptr, nullptr);
-    const RowSource rows{s.x_source, s.x, s.n_rows, "x_source", "PTNN_PREDICT_X", "x", "n_rows"};
-    RankOutputs rk{s.n_ranks, s.ranks, s.order_stats};
-    if (int rc = check_source(src, "vectors")) return rc;
-    if (int rc = check_rows(rows)) return rc;
-    if (s.n_rows < 1) return fail(-1, "n_rows = %d must be >= 1", s.n_rows);
-    if (int rc = rk.check()) return rc;
+    RowsByVectors f(s, RankOutputs{s.n_ranks, s.ranks, s.order_stats});
+    if (int rc = f.check()) return rc;
     if (int rc = check_handle(h, "ptnn_predict")) return rc;
     const int I = h->cfg.n_in, O = h->cfg.n_out;
     if (s.vote && h->cfg.task != PTNN_TASK_CLS) return fail(-1, "vote: a regression has no classes");
-    if (int rc = fit_rows(h, rows)) return rc;
-    if (int rc = select_samples(h, src, false)) return rc;
-    const long long M = src.M;
-    if (int rc = rk.check_values(M)) return rc;
-    if (s.n_samples) *s.n_samples = M;
+    if (int rc = fit_rows(h, f.rows)) return rc;
+    if (int rc = f.select(h, s.n_samples)) return rc;
 
-    if (int rc = start_device(h)) return rc;
+    if (int rc = f.stage(h, I, s.n_distinct)) return rc;
     hipStream_t st = h->stream;
-    DeviceScratch mem;
-    const int ncols = s.n_rows * O;
-    const float* d_x = nullptr;
-    int xs = 0;
-    if (int rc = upload_rows(h, mem, rows, I, &d_x, &xs)) return rc;
-    Distinct d;
-    if (int rc = distinct_samples(h, mem, src, false, true, &d)) return rc;
-    const int U = d.U;
-    if (s.n_distinct) *s.n_distinct = U;
-    // outputs on the device for every column; votes as integer counts (exact whatever the order)
-    double* d_mean = nullptr; long long* d_votes = nullptr;
+    DeviceScratch& mem = f.mem;
+    const Distinct& d = f.d;
+    const RankOutputs& rk = f.rk;
+    const long long M = f.M;
+    const int U = f.U, ncols = s.n_rows * O;
+    // outputs on the device for every column
+    double* d_mean = nullptr;
+    PooledVotes votes;
     HIP_TRY(mem.alloc(&d_mean, (size_t)ncols));
-    if (int rc = rk.to_device(mem, (size_t)ncols, st)) return rc;
-    if (h->cfg.task == PTNN_TASK_CLS) HIP_TRY(mem.alloc(&d_votes, (size_t)ncols));
+    if (int rc = f.rk.to_device(mem, (size_t)ncols, st)) return rc;
+    if (h->cfg.task == PTNN_TASK_CLS) HIP_TRY(votes.alloc(mem, (size_t)ncols));
     // stage b + c in blocks of rows: fx scratch U x (rows x O) floats under the budget
     const long long rows_blk = row_block(scratch_budget("PTNN_PREDICT_SCRATCH_BYTES"), (size_t)U * sizeof(float) * O, s.n_rows);
     float* d_fx = nullptr;
     HIP_TRY(mem.alloc(&d_fx, (size_t)rows_blk * O * U));
     ForwardPlan fwd;
     if (int rc = fwd.init(h, "posterior predictive")) return rc;
-    std::vector<int> item_run;
-    if (s.samples) if (int rc = item_runs(h, d, src.n_items, &item_run)) return rc;
+    if (int rc = f.items(h, s.samples != nullptr)) return rc;
     if (int rc = each_block(s.n_rows, rows_blk, [&](long long r0, int nr) -> int {
-        if (int rc = fwd.run(h, d.base, d.run_off, d_x, xs, (int)r0, nr, U, d_fx)) return rc;
-        PredictRed ra{d_fx, d.run_cnt, U, O, (int)r0 * O, ncols, M, s.n_ranks, rk.d_ranks, d_mean, rk.d_stats, d_votes};
+        if (int rc = fwd.run(h, d.base, d.run_off, f.d_x, f.xs, (int)r0, nr, U, d_fx)) return rc;
+        PredictRed ra{d_fx, d.run_cnt, U, O, (int)r0 * O, ncols, M, s.n_ranks, rk.d_ranks, d_mean, rk.d_stats, votes.d};
         HIP_TRY(launch(predict_reduce_kernel, dim3((unsigned)(nr * O)), dim3(PRED_THREADS), 0, st, ra));
-        return s.samples ? scatter_samples(h, d_fx, nr * O, U, item_run, src.weights(), s.samples, (size_t)s.n_rows * O, (size_t)r0 * O) : 0;
+        return s.samples ? scatter_samples(h, d_fx, nr * O, U, f.item_run, f.src.weights(), s.samples, (size_t)s.n_rows * O, (size_t)r0 * O) : 0;
     })) return rc;
-    std::vector<long long> votes_h(s.vote ? (size_t)ncols : 0);
     HIP_TRY(fetch(s.mean, d_mean, (size_t)ncols, st));
     HIP_TRY(fetch(s.order_stats, rk.d_stats, (size_t)s.n_ranks * ncols, st));
-    HIP_TRY(fetch(s.vote ? votes_h.data() : nullptr, d_votes, (size_t)ncols, st));
+    HIP_TRY(votes.fetch(s.vote != nullptr, (size_t)ncols, st));
     if (int rc = wait_stream(h)) return rc;
-    if (s.vote)
-        for (int c = 0; c < ncols; ++c) s.vote[c] = (double)votes_h[(size_t)c] / (double)M;
+    votes.shares(s.vote, M);
     return 0;
 }
 
@@ -624,91 +802,28 @@ int ptnn_sensitivity(ptnn_handle* h, const ptnn_sensitivity_spec* spec) {
     // argument checks first: none of them needs the handle or a device
     if (int rc = check_spec(spec, "ptnn_sensitivity_spec")) return rc;
     const ptnn_sensitivity_spec& s = *spec;
-    SampleSource src = source_of(s, s.w != nullptr, nullptr);
-    const RowSource rows{s.x_source, s.x, s.n_rows, "x_source", "PTNN_PREDICT_X", "x", "n_rows"};
-    RankOutputs rk{s.n_ranks, s.ranks, s.order_stats}, rk2{s.n_ranks2, s.ranks2, s.abs_order_stats};
-    if (int rc = check_source(src, "vectors")) return rc;
-    if (int rc = check_rows(rows)) return rc;
-    if (s.n_rows < 1) return fail(-1, "n_rows = %d must be >= 1", s.n_rows);
-    if (int rc = rk.check()) return rc;
-    if (int rc = rk2.check()) return rc;
+    RowsByVectors f(s, RankOutputs{s.n_ranks, s.ranks, s.order_stats}, RankOutputs{s.n_ranks2, s.ranks2, s.abs_order_stats});
+    if (int rc = f.check()) return rc;
     if (int rc = check_handle(h, "ptnn_sensitivity")) return rc;
     const int I = h->cfg.n_in, O = h->cfg.n_out, OI = O * I;
-    if (int rc = fit_rows(h, rows)) return rc;
+    if (int rc = fit_rows(h, f.rows)) return rc;
     const long long ncols_all = (long long)s.n_rows * OI;
     if (ncols_all > 0x7fffffffLL)
         return fail(-1, "%d rows x %d outputs x %d inputs = %lld columns: at most 2^31 - 1 per call", s.n_rows, O, I, ncols_all);
-    const int ncols = (int)ncols_all;
-    if (int rc = select_samples(h, src, false)) return rc;
-    const long long M = src.M;
-    if (int rc = rk.check_values(M)) return rc;
-    if (int rc = rk2.check_values(M)) return rc;
-    if (s.n_samples) *s.n_samples = M;
+    if (int rc = f.select(h, s.n_samples)) return rc;
 
-    if (int rc = start_device(h)) return rc;
-    hipStream_t st = h->stream;
-    DeviceScratch mem;
-    const float* d_x = nullptr;
-    int xs = 0;
-    if (int rc = upload_rows(h, mem, rows, I, &d_x, &xs)) return rc;
-    Distinct d;
-    if (int rc = distinct_samples(h, mem, src, false, true, &d)) return rc;
-    const int U = d.U;
-    if (s.n_distinct) *s.n_distinct = U;
-    // outputs on the device for every column; the sign counts as integers (exact whatever the order)
-    double *d_mean = nullptr, *d_acc_abs = nullptr, *d_acc_sq = nullptr, *d_abs_mean = nullptr, *d_sq_mean = nullptr, *d_a32_mean = nullptr;
-    float* d_a32 = nullptr;
-    long long *d_pos = nullptr, *d_neg = nullptr;
-    HIP_TRY(mem.alloc(&d_mean, (size_t)ncols));
-    HIP_TRY(mem.alloc(&d_pos, (size_t)ncols));
-    HIP_TRY(mem.alloc(&d_neg, (size_t)ncols));
-    if (int rc = rk.to_device(mem, (size_t)ncols, st)) return rc;
-    if (int rc = rk2.to_device(mem, (size_t)OI, st)) return rc;
-    // per (o, i) and distinct vector: the row sums of |g| and g^2, carried across the blocks of rows
-    HIP_TRY(mem.alloc(&d_acc_abs, (size_t)OI * U));
-    HIP_TRY(mem.alloc(&d_acc_sq, (size_t)OI * U));
-    HIP_TRY(mem.alloc(&d_a32, (size_t)OI * U));
-    HIP_TRY(mem.alloc(&d_abs_mean, (size_t)OI));
-    HIP_TRY(mem.alloc(&d_sq_mean, (size_t)OI));
-    HIP_TRY(mem.alloc(&d_a32_mean, (size_t)OI));
-    HIP_TRY(hipMemsetAsync(d_acc_abs, 0, (size_t)OI * U * sizeof(double), st));
-    HIP_TRY(hipMemsetAsync(d_acc_sq, 0, (size_t)OI * U * sizeof(double), st));
-    // the forward pass, the column reductions and the row sums in blocks of rows: gx scratch U x (rows x O x I) floats under the budget
-    const long long rows_blk = row_block(scratch_budget("PTNN_SENSITIVITY_SCRATCH_BYTES"), (size_t)U * sizeof(float) * OI, s.n_rows);
-    float* d_gx = nullptr;
-    HIP_TRY(mem.alloc(&d_gx, (size_t)rows_blk * OI * U));
+    if (int rc = f.stage(h, I, s.n_distinct)) return rc;
     SensPlan fwd;
     if (int rc = fwd.init(h)) return rc;
-    std::vector<int> item_run;
-    if (s.samples || s.sample_abs) if (int rc = item_runs(h, d, src.n_items, &item_run)) return rc;
-    const dim3 rows_grid((unsigned)((U + PRED_THREADS - 1) / PRED_THREADS), (unsigned)OI);
-    if (int rc = each_block(s.n_rows, rows_blk, [&](long long r0, int nr) -> int {
-        if (int rc = fwd.run(h, d.base, d.run_off, d_x, xs, (int)r0, nr, U, d_gx)) return rc;
-        PredictRed ra{d_gx, d.run_cnt, U, 1, (int)(r0 * OI), ncols, M, s.n_ranks, rk.d_ranks, d_mean, rk.d_stats, nullptr};
-        HIP_TRY(launch(predict_reduce_kernel, dim3((unsigned)(nr * OI)), dim3(PRED_THREADS), 0, st, ra));
-        SensSign sa{d_gx, d.run_cnt, U, r0 * OI, d_pos, d_neg};
-        HIP_TRY(launch(sensitivity_sign_kernel, dim3((unsigned)(nr * OI)), dim3(PRED_THREADS), 0, st, sa));
-        SensRows rw{d_gx, U, OI, nr, r0 + nr == s.n_rows ? 1 : 0, (double)s.n_rows, d_acc_abs, d_acc_sq, d_a32};
-        HIP_TRY(launch(sensitivity_rows_kernel, rows_grid, dim3(PRED_THREADS), 0, st, rw));
-        return s.samples ? scatter_samples(h, d_gx, nr * OI, U, item_run, src.weights(), s.samples, (size_t)ncols, (size_t)r0 * OI) : 0;
+    // the forward pass, the column reductions and the row sums in blocks of rows: gx scratch U x (rows x O x I) floats under the budget
+    SignedColumns g{h, f, s.n_rows, OI, {h, f, (int)ncols_all, s.grad_mean, s.order_stats, s.samples},
+                    s.pos_count, s.neg_count, s.abs_mean, s.sq_mean, s.abs_order_stats, s.sample_abs};
+    if (int rc = g.alloc("PTNN_SENSITIVITY_SCRATCH_BYTES")) return rc;
+    if (int rc = each_block(s.n_rows, g.rows_blk, [&](long long r0, int nr) -> int {
+        if (int rc = fwd.run(h, f.d.base, f.d.run_off, f.d_x, f.xs, (int)r0, nr, f.U, g.fx)) return rc;
+        return g.block(r0, nr);
     })) return rc;
-    // the global relevance: weighted means of the row sums (double), exact ranks of the fp32 a_s
-    SensMean ma{d_acc_abs, d_acc_sq, d.run_cnt, U, (double)s.n_rows, M, d_abs_mean, d_sq_mean};
-    HIP_TRY(launch(sensitivity_mean_kernel, dim3((unsigned)OI), dim3(PRED_THREADS), 0, st, ma));
-    if (s.n_ranks2) {
-        PredictRed ra{d_a32, d.run_cnt, U, 1, 0, OI, M, s.n_ranks2, rk2.d_ranks, d_a32_mean, rk2.d_stats, nullptr};
-        HIP_TRY(launch(predict_reduce_kernel, dim3((unsigned)OI), dim3(PRED_THREADS), 0, st, ra));
-    }
-    if (s.sample_abs)
-        if (int rc = scatter_samples(h, d_a32, OI, U, item_run, src.weights(), s.sample_abs, (size_t)OI, 0)) return rc;
-    HIP_TRY(fetch(s.grad_mean, d_mean, (size_t)ncols, st));
-    HIP_TRY(fetch(s.order_stats, rk.d_stats, (size_t)s.n_ranks * ncols, st));
-    HIP_TRY(fetch((long long*)s.pos_count, d_pos, (size_t)ncols, st));
-    HIP_TRY(fetch((long long*)s.neg_count, d_neg, (size_t)ncols, st));
-    HIP_TRY(fetch(s.abs_mean, d_abs_mean, (size_t)OI, st));
-    HIP_TRY(fetch(s.sq_mean, d_sq_mean, (size_t)OI, st));
-    HIP_TRY(fetch(s.abs_order_stats, rk2.d_stats, (size_t)s.n_ranks2 * OI, st));
-    return wait_stream(h);
+    return g.finish();
 }
 
 // ---- partial dependence and ICE curves (ptnn_dev_pd.hpp) ----
@@ -726,15 +841,9 @@ int ptnn_partial_dependence(ptnn_handle* h, const ptnn_pd_spec* spec) {
     // argument checks first: none of them needs the handle or a device (the grid of inputs == NULL has n_in rows: checked with the handle)
     if (int rc = check_spec(spec, "ptnn_pd_spec")) return rc;
     const ptnn_pd_spec& s = *spec;
-    SampleSource src = source_of(s, s.w != nullptr, nullptr);
-    const RowSource rows{s.x_source, s.x, s.n_rows, "x_source", "PTNN_PREDICT_X", "x", "n_rows"};
-    RankOutputs rk{s.n_ranks, s.ranks, s.ice_order_stats};
-    RankOutputs rk2{s.n_ranks2, s.ranks2, s.pd_order_stats ? (const void*)s.pd_order_stats : (const void*)s.range_order_stats};
-    if (int rc = check_source(src, "vectors")) return rc;
-    if (int rc = check_rows(rows)) return rc;
-    if (s.n_rows < 1) return fail(-1, "n_rows = %d must be >= 1", s.n_rows);
-    if (int rc = rk.check()) return rc;
-    if (int rc = rk2.check()) return rc;
+    RowsByVectors f(s, RankOutputs{s.n_ranks, s.ranks, s.ice_order_stats},
+                    RankOutputs{s.n_ranks2, s.ranks2, s.pd_order_stats ? (const void*)s.pd_order_stats : (const void*)s.range_order_stats});
+    if (int rc = f.check()) return rc;
     if (s.n_grid < 1 || s.n_grid > PTNN_PD_MAX_GRID) return fail(-1, "n_grid = %d outside [1, %d]", s.n_grid, PTNN_PD_MAX_GRID);
     if (!s.grid) return fail(-1, "grid is NULL: one row of n_grid values per selected input");
     if (s.inputs && s.n_inputs < 1) return fail(-1, "n_inputs = %d with an input list", s.n_inputs);
@@ -742,7 +851,7 @@ int ptnn_partial_dependence(ptnn_handle* h, const ptnn_pd_spec* spec) {
         if (int rc = pd_check_grid(s.grid, s.n_inputs, s.n_grid)) return rc;
     if (int rc = check_handle(h, "ptnn_partial_dependence")) return rc;
     const int I = h->cfg.n_in, O = h->cfg.n_out, G = s.n_grid;
-    if (int rc = fit_rows(h, rows)) return rc;
+    if (int rc = fit_rows(h, f.rows)) return rc;
     std::vector<int32_t> inputs(s.inputs ? (size_t)s.n_inputs : (size_t)I);
     for (size_t a = 0; a < inputs.size(); ++a) inputs[a] = s.inputs ? s.inputs[a] : (int32_t)a;
     if (!s.inputs)
@@ -758,36 +867,28 @@ int ptnn_partial_dependence(ptnn_handle* h, const ptnn_pd_spec* spec) {
     if (ncols_all > 0x7fffffffLL)
         return fail(-1, "%d rows x %d inputs x %d grid values x %d outputs = %lld columns: at most 2^31 - 1 per call", s.n_rows, A, G, O, ncols_all);
     const int ncols = (int)ncols_all;
-    if (int rc = select_samples(h, src, false)) return rc;
-    const long long M = src.M;
-    if (int rc = rk.check_values(M)) return rc;
-    if (int rc = rk2.check_values(M)) return rc;
-    if (s.n_samples) *s.n_samples = M;
+    if (int rc = f.select(h, s.n_samples)) return rc;
 
-    if (int rc = start_device(h)) return rc;
     hipStream_t st = h->stream;
-    DeviceScratch mem;
-    const float* d_x = nullptr;
-    int xs = 0;
-    if (int rc = upload_rows(h, mem, rows, I, &d_x, &xs)) return rc;
+    DeviceScratch& mem = f.mem;
     int* d_inputs = nullptr;
     float* d_grid = nullptr;
-    HIP_TRY(mem.upload(&d_inputs, (const int*)inputs.data(), (size_t)A, st));
-    HIP_TRY(mem.upload(&d_grid, s.grid, (size_t)A * G, st));
-    Distinct d;
-    if (int rc = distinct_samples(h, mem, src, false, true, &d)) return rc;
-    const int U = d.U;
-    if (s.n_distinct) *s.n_distinct = U;
+    if (int rc = f.stage(h, I, s.n_distinct, [&]() -> int {
+        HIP_TRY(mem.upload(&d_inputs, (const int*)inputs.data(), (size_t)A, st));
+        HIP_TRY(mem.upload(&d_grid, s.grid, (size_t)A * G, st));
+        return 0;
+    })) return rc;
+    const Distinct& d = f.d;
+    const long long M = f.M;
+    const int U = f.U;
     // an output costs device work only when its pointer is given
-    const bool ice_red = s.ice_mean || s.ice_order_stats;
     const bool want_range = s.range_mean || s.range_order_stats || s.sample_range;
-    if (!s.ice_order_stats) rk.n = 0;
     const int nrk_pd = s.pd_order_stats ? s.n_ranks2 : 0, nrk_range = s.range_order_stats ? s.n_ranks2 : 0;
-    double *d_ice_mean = nullptr, *d_acc = nullptr, *d_pd_mean = nullptr, *d_pd32_mean = nullptr, *d_range_mean = nullptr;
+    double *d_acc = nullptr, *d_pd_mean = nullptr, *d_pd32_mean = nullptr, *d_range_mean = nullptr;
     float *d_pd32 = nullptr, *d_range = nullptr, *d_pd_stats = nullptr, *d_range_stats = nullptr;
     long long* d_ranks2 = nullptr;
-    if (ice_red) HIP_TRY(mem.alloc(&d_ice_mean, (size_t)ncols));
-    if (int rc = rk.to_device(mem, (size_t)ncols, st)) return rc;
+    Columns ice{h, f, ncols, s.ice_mean, s.ice_order_stats, s.samples};
+    if (int rc = ice.alloc()) return rc;
     if (nrk_pd || nrk_range) HIP_TRY(mem.upload(&d_ranks2, (const long long*)s.ranks2, (size_t)s.n_ranks2, st));
     // per (a, k, o) and distinct vector: the row sums of ICE, carried across the blocks of rows
     HIP_TRY(mem.alloc(&d_acc, (size_t)AGO * U));
@@ -799,18 +900,14 @@ int ptnn_partial_dependence(ptnn_handle* h, const ptnn_pd_spec* spec) {
     HIP_TRY(mem.alloc(&d_fx, (size_t)rows_blk * AGO * U));
     PdPlan fwd;
     if (int rc = fwd.init(h, A, G)) return rc;
-    std::vector<int> item_run;
-    if (s.samples || s.sample_pd || s.sample_range) if (int rc = item_runs(h, d, src.n_items, &item_run)) return rc;
+    if (int rc = f.items(h, s.samples || s.sample_pd || s.sample_range)) return rc;
     const unsigned ublocks = (unsigned)((U + PRED_THREADS - 1) / PRED_THREADS);
     if (int rc = each_block(s.n_rows, rows_blk, [&](long long r0, int nr) -> int {
-        if (int rc = fwd.run(h, d.base, d.run_off, d_x, xs, (int)r0, nr, U, d_inputs, d_grid, d_fx)) return rc;
-        if (ice_red) {
-            PredictRed ra{d_fx, d.run_cnt, U, 1, (int)(r0 * AGO), ncols, M, rk.n, rk.d_ranks, d_ice_mean, rk.d_stats, nullptr};
-            HIP_TRY(launch(predict_reduce_kernel, dim3((unsigned)((long long)nr * AGO)), dim3(PRED_THREADS), 0, st, ra));
-        }
+        if (int rc = fwd.run(h, d.base, d.run_off, f.d_x, f.xs, (int)r0, nr, U, d_inputs, d_grid, d_fx)) return rc;
+        if (int rc = ice.reduce(d_fx, r0 * AGO, (long long)nr * AGO)) return rc;
         PdRows rw{d_fx, U, AGO, nr, r0 + nr == s.n_rows ? 1 : 0, (double)s.n_rows, d_acc, d_pd32};
         HIP_TRY(launch(pd_rows_kernel, dim3(ublocks * (unsigned)AGO), dim3(PRED_THREADS), 0, st, rw));
-        return s.samples ? scatter_samples(h, d_fx, nr * AGO, U, item_run, src.weights(), s.samples, (size_t)ncols, (size_t)r0 * AGO) : 0;
+        return ice.scatter(d_fx, r0 * AGO, (long long)nr * AGO);
     })) return rc;
     // the curve: weighted means of the double row means, exact ranks of PD32; its range per (a, o)
     if (s.pd_mean) {
@@ -836,11 +933,10 @@ int ptnn_partial_dependence(ptnn_handle* h, const ptnn_pd_spec* spec) {
         }
     }
     if (s.sample_pd)
-        if (int rc = scatter_samples(h, d_pd32, AGO, U, item_run, src.weights(), s.sample_pd, (size_t)AGO, 0)) return rc;
+        if (int rc = scatter_samples(h, d_pd32, AGO, U, f.item_run, f.src.weights(), s.sample_pd, (size_t)AGO, 0)) return rc;
     if (s.sample_range)
-        if (int rc = scatter_samples(h, d_range, AO, U, item_run, src.weights(), s.sample_range, (size_t)AO, 0)) return rc;
-    HIP_TRY(fetch(s.ice_mean, d_ice_mean, (size_t)ncols, st));
-    HIP_TRY(fetch(s.ice_order_stats, rk.d_stats, (size_t)rk.n * ncols, st));
+        if (int rc = scatter_samples(h, d_range, AO, U, f.item_run, f.src.weights(), s.sample_range, (size_t)AO, 0)) return rc;
+    if (int rc = ice.fetch()) return rc;
     HIP_TRY(fetch(s.pd_mean, d_pd_mean, (size_t)AGO, st));
     HIP_TRY(fetch(s.pd_order_stats, d_pd_stats, (size_t)nrk_pd * AGO, st));
     HIP_TRY(fetch(s.range_mean, d_range_mean, (size_t)AO, st));
@@ -882,14 +978,8 @@ int ptnn_coalition_values(ptnn_handle* h, const ptnn_shapley_spec* spec) {
     // argument checks first: none of them needs the handle or a device (a mask's bits are looked at with the handle's n_in)
     if (int rc = check_spec(spec, "ptnn_shapley_spec")) return rc;
     const ptnn_shapley_spec& s = *spec;
-    SampleSource src = source_of(s, s.w != nullptr, nullptr);
-    const RowSource rows{s.x_source, s.x, s.n_rows, "x_source", "PTNN_PREDICT_X", "x", "n_rows"};
-    RankOutputs rk{s.n_ranks, s.ranks, s.order_stats}, rk2{s.n_ranks2, s.ranks2, s.abs_order_stats};
-    if (int rc = check_source(src, "vectors")) return rc;
-    if (int rc = check_rows(rows)) return rc;
-    if (s.n_rows < 1) return fail(-1, "n_rows = %d must be >= 1", s.n_rows);
-    if (int rc = rk.check()) return rc;
-    if (int rc = rk2.check()) return rc;
+    RowsByVectors f(s, RankOutputs{s.n_ranks, s.ranks, s.order_stats}, RankOutputs{s.n_ranks2, s.ranks2, s.abs_order_stats});
+    if (int rc = f.check()) return rc;
     if (s.n_background < 1 || s.n_background > PTNN_SHAP_MAX_BACKGROUND)
         return fail(-1, "n_background = %d outside [1, %d]", s.n_background, PTNN_SHAP_MAX_BACKGROUND);
     if (s.n_coalitions < 1 || s.n_coalitions > PTNN_SHAP_MAX_COALITIONS)
@@ -905,7 +995,7 @@ int ptnn_coalition_values(ptnn_handle* h, const ptnn_shapley_spec* spec) {
                 return fail(-1, "coef[%d, %d] = %g (coalition %d, term %d) is not finite", c, t, s.coef[(size_t)c * T + t], c, t);
     if (int rc = check_handle(h, "ptnn_coalition_values")) return rc;
     const int I = h->cfg.n_in, O = h->cfg.n_out, OT = O * T;
-    if (int rc = fit_rows(h, rows)) return rc;
+    if (int rc = fit_rows(h, f.rows)) return rc;
     if (OT > PTNN_SHAP_MAX_ACC) return fail(-1, "n_terms = %d x n_out = %d = %d accumulators: at most %d", T, O, OT, PTNN_SHAP_MAX_ACC);
     for (int b = 0; b < B; ++b)
         for (int i = 0; i < I; ++i)
@@ -917,96 +1007,29 @@ int ptnn_coalition_values(ptnn_handle* h, const ptnn_shapley_spec* spec) {
     const long long ncols_all = (long long)s.n_rows * OT;
     if (ncols_all > 0x7fffffffLL)
         return fail(-1, "%d rows x %d outputs x %d terms = %lld columns: at most 2^31 - 1 per call", s.n_rows, O, T, ncols_all);
-    const int ncols = (int)ncols_all;
-    if (int rc = select_samples(h, src, false)) return rc;
-    const long long M = src.M;
-    if (int rc = rk.check_values(M)) return rc;
-    if (int rc = rk2.check_values(M)) return rc;
-    if (s.n_samples) *s.n_samples = M;
+    if (int rc = f.select(h, s.n_samples)) return rc;
 
-    if (int rc = start_device(h)) return rc;
-    hipStream_t st = h->stream;
-    DeviceScratch mem;
-    const float* d_x = nullptr;
-    int xs = 0;
-    if (int rc = upload_rows(h, mem, rows, I, &d_x, &xs)) return rc;
     float* d_bg = nullptr;
     unsigned long long* d_masks = nullptr;
     double* d_coef = nullptr;
-    HIP_TRY(mem.upload(&d_bg, s.background, (size_t)B * I, st));
-    HIP_TRY(mem.upload(&d_masks, (const unsigned long long*)s.masks, (size_t)C, st));
-    HIP_TRY(mem.upload(&d_coef, s.coef, (size_t)C * T, st));
-    Distinct d;
-    if (int rc = distinct_samples(h, mem, src, false, true, &d)) return rc;
-    const int U = d.U;
-    if (s.n_distinct) *s.n_distinct = U;
-    // an output costs device work only when its pointer is given
-    const bool col_red = s.mean || s.order_stats, signs = s.pos_count || s.neg_count;
-    const bool abs_red = s.abs_mean || s.abs_order_stats || s.sample_abs;
-    if (!s.order_stats) rk.n = 0;
-    if (!s.abs_order_stats) rk2.n = 0;
-    double *d_mean = nullptr, *d_acc_abs = nullptr, *d_acc_sq = nullptr, *d_abs_mean = nullptr, *d_sq_mean = nullptr, *d_a32_mean = nullptr;
-    float* d_a32 = nullptr;
-    long long *d_pos = nullptr, *d_neg = nullptr;
-    if (col_red) HIP_TRY(mem.alloc(&d_mean, (size_t)ncols));
-    if (signs) {
-        HIP_TRY(mem.alloc(&d_pos, (size_t)ncols));
-        HIP_TRY(mem.alloc(&d_neg, (size_t)ncols));
-    }
-    if (int rc = rk.to_device(mem, (size_t)ncols, st)) return rc;
-    if (int rc = rk2.to_device(mem, (size_t)OT, st)) return rc;
-    if (abs_red) {      // per (o, t) and distinct vector: the row sums of |out| (sensitivity_rows_kernel: and of out^2, not read), carried across the blocks
-        HIP_TRY(mem.alloc(&d_acc_abs, (size_t)OT * U));
-        HIP_TRY(mem.alloc(&d_acc_sq, (size_t)OT * U));
-        HIP_TRY(mem.alloc(&d_a32, (size_t)OT * U));
-        HIP_TRY(mem.alloc(&d_abs_mean, (size_t)OT));
-        HIP_TRY(mem.alloc(&d_sq_mean, (size_t)OT));
-        HIP_TRY(mem.alloc(&d_a32_mean, (size_t)OT));
-        HIP_TRY(hipMemsetAsync(d_acc_abs, 0, (size_t)OT * U * sizeof(double), st));
-        HIP_TRY(hipMemsetAsync(d_acc_sq, 0, (size_t)OT * U * sizeof(double), st));
-    }
-    // the forward pass, the column reductions and the row sums in blocks of rows: fx scratch U x (rows x O x T) floats under the budget
-    const long long rows_blk = row_block(scratch_budget("PTNN_SHAP_SCRATCH_BYTES"), (size_t)U * sizeof(float) * OT, s.n_rows);
-    float* d_fx = nullptr;
-    HIP_TRY(mem.alloc(&d_fx, (size_t)rows_blk * OT * U));
+    if (int rc = f.stage(h, I, s.n_distinct, [&]() -> int {
+        HIP_TRY(f.mem.upload(&d_bg, s.background, (size_t)B * I, h->stream));
+        HIP_TRY(f.mem.upload(&d_masks, (const unsigned long long*)s.masks, (size_t)C, h->stream));
+        HIP_TRY(f.mem.upload(&d_coef, s.coef, (size_t)C * T, h->stream));
+        return 0;
+    })) return rc;
     ShapPlan fwd;
     if (int rc = fwd.init(h)) return rc;
-    std::vector<int> item_run;
-    if (s.samples || s.sample_abs) if (int rc = item_runs(h, d, src.n_items, &item_run)) return rc;
-    const dim3 rows_grid((unsigned)((U + PRED_THREADS - 1) / PRED_THREADS), (unsigned)OT);
-    if (int rc = each_block(s.n_rows, rows_blk, [&](long long r0, int nr) -> int {
-        if (int rc = fwd.run(h, d.base, d.run_off, d_x, xs, (int)r0, nr, U, d_bg, B, C, T, d_masks, d_coef, d_fx)) return rc;
-        if (col_red) {
-            PredictRed ra{d_fx, d.run_cnt, U, 1, (int)(r0 * OT), ncols, M, rk.n, rk.d_ranks, d_mean, rk.d_stats, nullptr};
-            HIP_TRY(launch(predict_reduce_kernel, dim3((unsigned)(nr * OT)), dim3(PRED_THREADS), 0, st, ra));
-        }
-        if (signs) {
-            SensSign sa{d_fx, d.run_cnt, U, r0 * OT, d_pos, d_neg};
-            HIP_TRY(launch(sensitivity_sign_kernel, dim3((unsigned)(nr * OT)), dim3(PRED_THREADS), 0, st, sa));
-        }
-        if (abs_red) {
-            SensRows rw{d_fx, U, OT, nr, r0 + nr == s.n_rows ? 1 : 0, (double)s.n_rows, d_acc_abs, d_acc_sq, d_a32};
-            HIP_TRY(launch(sensitivity_rows_kernel, rows_grid, dim3(PRED_THREADS), 0, st, rw));
-        }
-        return s.samples ? scatter_samples(h, d_fx, nr * OT, U, item_run, src.weights(), s.samples, (size_t)ncols, (size_t)r0 * OT) : 0;
+    // the forward pass, the column reductions and the row sums in blocks of rows: fx scratch U x (rows x O x T) floats under the budget
+    // (sensitivity_rows_kernel also sums out^2, which is not read: no sq_mean)
+    SignedColumns v{h, f, s.n_rows, OT, {h, f, (int)ncols_all, s.mean, s.order_stats, s.samples},
+                    s.pos_count, s.neg_count, s.abs_mean, nullptr, s.abs_order_stats, s.sample_abs};
+    if (int rc = v.alloc("PTNN_SHAP_SCRATCH_BYTES")) return rc;
+    if (int rc = each_block(s.n_rows, v.rows_blk, [&](long long r0, int nr) -> int {
+        if (int rc = fwd.run(h, f.d.base, f.d.run_off, f.d_x, f.xs, (int)r0, nr, f.U, d_bg, B, C, T, d_masks, d_coef, v.fx)) return rc;
+        return v.block(r0, nr);
     })) return rc;
-    if (s.abs_mean) {
-        SensMean ma{d_acc_abs, d_acc_sq, d.run_cnt, U, (double)s.n_rows, M, d_abs_mean, d_sq_mean};
-        HIP_TRY(launch(sensitivity_mean_kernel, dim3((unsigned)OT), dim3(PRED_THREADS), 0, st, ma));
-    }
-    if (rk2.n) {
-        PredictRed ra{d_a32, d.run_cnt, U, 1, 0, OT, M, rk2.n, rk2.d_ranks, d_a32_mean, rk2.d_stats, nullptr};
-        HIP_TRY(launch(predict_reduce_kernel, dim3((unsigned)OT), dim3(PRED_THREADS), 0, st, ra));
-    }
-    if (s.sample_abs)
-        if (int rc = scatter_samples(h, d_a32, OT, U, item_run, src.weights(), s.sample_abs, (size_t)OT, 0)) return rc;
-    HIP_TRY(fetch(s.mean, d_mean, (size_t)ncols, st));
-    HIP_TRY(fetch(s.order_stats, rk.d_stats, (size_t)rk.n * ncols, st));
-    HIP_TRY(fetch((long long*)s.pos_count, d_pos, (size_t)ncols, st));
-    HIP_TRY(fetch((long long*)s.neg_count, d_neg, (size_t)ncols, st));
-    HIP_TRY(fetch(s.abs_mean, d_abs_mean, (size_t)OT, st));
-    HIP_TRY(fetch(s.abs_order_stats, rk2.d_stats, (size_t)rk2.n * OT, st));
-    return wait_stream(h);
+    return v.finish();
 }
 
 // ---- convergence diagnostics (ptnn_dev_convergence.hpp) ----
@@ -1440,8 +1463,7 @@ int ptnn_elpd(ptnn_handle* h, const ptnn_elpd_spec* spec) {
         ra.row0 = (int)r0;
         HIP_TRY(launch(elpd_reduce_kernel, dim3((unsigned)nr), dim3(ELPD_THREADS), 0, st, ra));
         if (!s.loglik_out) return 0;
-        const long long n_ll = (long long)nr * U;
-        HIP_TRY(launch(elpd_loglik_kernel, dim3((unsigned)((n_ll + ELPD_THREADS - 1) / ELPD_THREADS)), dim3(ELPD_THREADS), 0, st, ra, nr));
+        if (int rc = loglik_block(h, ra, nr)) return rc;
         return scatter_samples(h, d_llb, nr, U, item_run, src.weights(), s.loglik_out, (size_t)n_rows, (size_t)r0);
     })) return rc;
     return copy_out();
@@ -1560,8 +1582,7 @@ int ptnn_lfo(ptnn_handle* h, const ptnn_lfo_spec* spec) {
             acc.nrows = nr;
             HIP_TRY(launch(lfo_accum_kernel, dim3(acc_blocks), dim3(ELPD_THREADS), 0, st, acc));
             if (!(s.loglik_out && o0 == 0)) return 0;
-            const long long n_ll = (long long)nr * U;
-            HIP_TRY(launch(elpd_loglik_kernel, dim3((unsigned)((n_ll + ELPD_THREADS - 1) / ELPD_THREADS)), dim3(ELPD_THREADS), 0, st, ra, nr));
+            if (int rc = loglik_block(h, ra, nr)) return rc;
             return scatter_samples(h, d_llb, nr, U, item_run, src.weights(), s.loglik_out, (size_t)n_rows, (size_t)r0);
         })) return rc;
         // stage d: one work-group per origin of the pass
@@ -2392,13 +2413,9 @@ int ptnn_powerscale(ptnn_handle* h, const ptnn_powerscale_spec* spec) {
         HIP_TRY(tmp.alloc(&d_fx, (size_t)rows_blk * O * U));
         HIP_TRY(tmp.alloc(&d_llb, (size_t)rows_blk * U));
         ElpdRed ra{};
-        ra.mode = reg ? ELPD_REG : ELPD_CLS; ra.fx = d_fx; ra.eta = d.run_eta; ra.y = h->d_data + I; ra.ys = h->IPY; ra.cnt = d.run_cnt;
-        ra.U = U; ra.O = O; ra.ll_out = d_llb;
+        ra.mode = reg ? ELPD_REG : ELPD_CLS; ra.eta = d.run_eta; ra.cnt = d.run_cnt; ra.U = U; ra.O = O;
         if (int rc = each_block(Ntr, rows_blk, [&](long long r0, int nr) -> int {
-            if (int rc = fwd.run(h, d.base, d.run_off, h->d_data, h->IPY, (int)r0, nr, U, d_fx)) return rc;
-            ra.row0 = (int)r0;
-            const long long n_ll = (long long)nr * U;
-            HIP_TRY(launch(elpd_loglik_kernel, dim3((unsigned)((n_ll + ELPD_THREADS - 1) / ELPD_THREADS)), dim3(ELPD_THREADS), 0, st, ra, nr));
+            if (int rc = loglik_rows(h, fwd, d, h->d_data, h->IPY, r0, nr, d_fx, d_llb, ra)) return rc;
             HIP_TRY(launch(powerscale_loglik_kernel, dim3((unsigned)((U + PS_THREADS - 1) / PS_THREADS)), dim3(PS_THREADS), 0, st, d_llb, nr, U, d_logp));
             return 0;
         })) return rc;
@@ -2570,7 +2587,7 @@ int ptnn_prior_predictive(ptnn_handle* h, const ptnn_prior_spec* spec) {
     const long long nb = std::max(1LL, std::min<long long>((long long)((budget - (size_t)ncols * ND * sizeof(float)) / per_draw), ND));
     if (s.n_blocks) *s.n_blocks = (ND + nb - 1) / nb;
     float *d_fx = nullptr, *d_fxb = nullptr, *d_pw = nullptr, *d_t32 = nullptr, *d_tos = nullptr;
-    long long *d_poff = nullptr, *d_votes = nullptr, *d_sat = nullptr, *d_cnt = nullptr, *d_tranks = nullptr;
+    long long *d_poff = nullptr, *d_sat = nullptr, *d_cnt = nullptr, *d_tranks = nullptr;
     int* d_ones = nullptr;
     double *d_mean = nullptr, *d_t = nullptr, *d_tobs = nullptr, *d_tm = nullptr, *d_tmean = nullptr;
     HIP_TRY(mem.alloc(&d_fx, (size_t)ncols * ND));
@@ -2581,7 +2598,8 @@ int ptnn_prior_predictive(ptnn_handle* h, const ptnn_prior_spec* spec) {
     HIP_TRY(hipMemsetD32Async(d_ones, 1, (size_t)ND, st));
     HIP_TRY(mem.alloc(&d_mean, (size_t)ncols));
     if (int rc = rk.to_device(mem, (size_t)ncols, st)) return rc;
-    if (!reg) HIP_TRY(mem.alloc(&d_votes, (size_t)ncols));
+    PooledVotes votes;
+    if (!reg) HIP_TRY(votes.alloc(mem, (size_t)ncols));
     HIP_TRY(mem.alloc(&d_sat, (size_t)ncols));
     HIP_TRY(mem.alloc(&d_t, (size_t)n_stats * ND));
     HIP_TRY(mem.alloc(&d_t32, (size_t)n_stats * ND));
@@ -2600,7 +2618,6 @@ int ptnn_prior_predictive(ptnn_handle* h, const ptnn_prior_spec* spec) {
     HIP_TRY(fetch(s.t_obs, d_tobs, (size_t)n_stats, st));
     std::vector<int> identity(s.samples || s.t_draw ? (size_t)ND : 0);
     for (size_t i = 0; i < identity.size(); ++i) identity[i] = (int)i;
-    std::vector<long long> votes_h(s.vote ? (size_t)ncols : 0);
 
     for (int k = 0; k < S; ++k) {
         const float sigma = (float)std::sqrt(s.n_scales ? s.sigma_squared[k] : (double)h->cfg.sigma_squared);
@@ -2619,7 +2636,7 @@ int ptnn_prior_predictive(ptnn_handle* h, const ptnn_prior_spec* spec) {
             })) return rc;
         }
         // stage c: every column over the draws
-        PredictRed ra{d_fx, d_ones, (int)ND, O, 0, ncols, ND, s.n_ranks, rk.d_ranks, d_mean, rk.d_stats, d_votes};
+        PredictRed ra{d_fx, d_ones, (int)ND, O, 0, ncols, ND, s.n_ranks, rk.d_ranks, d_mean, rk.d_stats, votes.d};
         HIP_TRY(launch(predict_reduce_kernel, dim3((unsigned)ncols), dim3(PRED_THREADS), 0, st, ra));
         HIP_TRY(launch(prior_saturation_kernel, dim3((unsigned)ncols), dim3(PRIOR_THREADS), 0, st, d_fx, ND, s.eps, d_sat));
         // stage d: every draw over the rows; the order statistics of the fp32 copy
@@ -2636,7 +2653,7 @@ int ptnn_prior_predictive(ptnn_handle* h, const ptnn_prior_spec* spec) {
         const size_t kc = (size_t)k * ncols, kt = (size_t)k * n_stats;
         HIP_TRY(fetch(s.mean ? s.mean + kc : nullptr, d_mean, (size_t)ncols, st));
         HIP_TRY(fetch(s.order_stats ? s.order_stats + kc * s.n_ranks : nullptr, rk.d_stats, (size_t)s.n_ranks * ncols, st));
-        HIP_TRY(fetch(s.vote ? votes_h.data() : nullptr, d_votes, (size_t)ncols, st));
+        HIP_TRY(votes.fetch(s.vote != nullptr, (size_t)ncols, st));
         HIP_TRY(fetch(s.sat_count ? (long long*)s.sat_count + kc : nullptr, d_sat, (size_t)ncols, st));
         HIP_TRY(fetch(s.stat_mean ? s.stat_mean + kt : nullptr, d_tm, (size_t)n_stats, st));
         HIP_TRY(fetch(s.stat_sd ? s.stat_sd + kt : nullptr, d_tm + n_stats, (size_t)n_stats, st));
@@ -2649,8 +2666,7 @@ int ptnn_prior_predictive(ptnn_handle* h, const ptnn_prior_spec* spec) {
         if (s.samples)
             if (int rc = scatter_samples(h, d_fx, ncols, (int)ND, identity, nullptr, s.samples + kc * ND, (size_t)ncols, 0)) return rc;
         if (int rc = wait_stream(h)) return rc;
-        if (s.vote)
-            for (int c = 0; c < ncols; ++c) s.vote[kc + c] = (double)votes_h[(size_t)c] / (double)ND;
+        if (s.vote) votes.shares(s.vote + kc, ND);
     }
     return 0;
 }
@@ -2662,39 +2678,27 @@ int ptnn_class_report(ptnn_handle* h, const ptnn_class_report_spec* spec) {
     // argument checks first: none of them needs the handle or a device
     if (int rc = check_spec(spec, "ptnn_class_report_spec")) return rc;
     const ptnn_class_report_spec& s = *spec;
-    SampleSource src = source_of(s, s.w != nullptr, nullptr);
-    const RowSource rows{s.x_source, s.x, s.n_rows, "x_source", "PTNN_PREDICT_X", "x", "n_rows"};
-    RankOutputs rk{s.n_ranks, s.ranks, s.metric_order_stats};
-    if (int rc = check_source(src, "vectors")) return rc;
-    if (int rc = check_rows(rows)) return rc;
-    if (s.n_rows < 1) return fail(-1, "n_rows = %d must be >= 1", s.n_rows);
-    if (s.n_rows > 65535 * WAVE) return fail(-1, "n_rows = %d: at most 65535 x 64 rows per call", s.n_rows);
-    if (int rc = rk.check()) return rc;
+    RowsByVectors f(s, RankOutputs{s.n_ranks, s.ranks, s.metric_order_stats});
+    if (int rc = f.check(true)) return rc;
     if (s.auc && s.n_rows > REPORT_MAX_AUC_ROWS)
         return fail(-1, "auc: %d rows, at most %d (the scores of one sample and class are ranked in LDS); auc = 0 (auc=False) has no cap",
                     s.n_rows, REPORT_MAX_AUC_ROWS);
     if (int rc = check_handle(h, "ptnn_class_report")) return rc;
     const int I = h->cfg.n_in, K = h->cfg.n_out, KK = K * K, N = s.n_rows;
     if (h->cfg.task != PTNN_TASK_CLS) return fail(-1, "ptnn_class_report: a regression has no classes");
-    if (int rc = fit_rows(h, rows)) return rc;
+    if (int rc = fit_rows(h, f.rows)) return rc;
     if (s.x_source == PTNN_PREDICT_X_HOST)
         if (int rc = check_labels(s.x, N, I, K)) return rc;
-    if (int rc = select_samples(h, src, false)) return rc;
-    const long long M = src.M;
-    if (int rc = rk.check_values(M)) return rc;
-    if (s.n_samples) *s.n_samples = M;
+    if (int rc = f.select(h, s.n_samples)) return rc;
 
-    if (int rc = start_device(h)) return rc;
+    if (int rc = f.stage(h, I + 1, s.n_distinct)) return rc;
     hipStream_t st = h->stream;
-    DeviceScratch mem;
-    const int ncols = N * K, Q = s.auc ? 4 + 4 * K : 3 + 3 * K;
-    const float* d_x = nullptr;
-    int xs = 0;
-    if (int rc = upload_rows(h, mem, rows, I + 1, &d_x, &xs)) return rc;
-    Distinct d;
-    if (int rc = distinct_samples(h, mem, src, false, true, &d)) return rc;
-    const int U = d.U;
-    if (s.n_distinct) *s.n_distinct = U;
+    DeviceScratch& mem = f.mem;
+    const Distinct& d = f.d;
+    RankOutputs& rk = f.rk;
+    const float* d_x = f.d_x;
+    const long long M = f.M;
+    const int xs = f.xs, U = f.U, ncols = N * K, Q = s.auc ? 4 + 4 * K : 3 + 3 * K;
     // the class of every row as an integer: the kernels' index, and on the host p_correct's
     int* d_label = nullptr;
     HIP_TRY(mem.alloc(&d_label, (size_t)N));
@@ -2704,11 +2708,12 @@ int ptnn_class_report(ptnn_handle* h, const ptnn_class_report_spec* spec) {
     HIP_TRY(hipMemcpyAsync(label_h.data(), d_label, (size_t)N * sizeof(int), hipMemcpyDeviceToHost, st));
     // per column of the pooled classifier, per sample, per metric
     double *d_mean = nullptr, *d_mmean = nullptr;
-    long long *d_votes = nullptr, *d_auc2 = nullptr, *d_csum = nullptr;
+    long long *d_auc2 = nullptr, *d_csum = nullptr;
+    PooledVotes votes;
     int* d_conf = nullptr;
     float* d_img = nullptr;
     HIP_TRY(mem.alloc(&d_mean, (size_t)ncols));
-    HIP_TRY(mem.alloc(&d_votes, (size_t)ncols));
+    HIP_TRY(votes.alloc(mem, (size_t)ncols));
     HIP_TRY(mem.alloc(&d_conf, (size_t)KK * U));
     HIP_TRY(hipMemsetAsync(d_conf, 0, (size_t)KK * U * sizeof(int), st));
     if (s.auc) HIP_TRY(mem.alloc(&d_auc2, (size_t)K * U));
@@ -2752,7 +2757,7 @@ int ptnn_class_report(ptnn_handle* h, const ptnn_class_report_spec* spec) {
     };
     if (int rc = each_block(N, rows_blk, [&](long long r0, int nr) -> int {
         if (int rc = fwd.run(h, d.base, d.run_off, d_x, xs, (int)r0, nr, U, d_fx)) return rc;
-        PredictRed ra{d_fx, d.run_cnt, U, K, (int)r0 * K, ncols, M, 0, nullptr, d_mean, nullptr, d_votes};
+        PredictRed ra{d_fx, d.run_cnt, U, K, (int)r0 * K, ncols, M, 0, nullptr, d_mean, nullptr, votes.d};
         HIP_TRY(launch(predict_reduce_kernel, dim3((unsigned)(nr * K)), dim3(PRED_THREADS), 0, st, ra));
         return one_pass ? count_block(0, U) : 0;
     })) return rc;
@@ -2767,27 +2772,24 @@ int ptnn_class_report(ptnn_handle* h, const ptnn_class_report_spec* spec) {
     PredictRed qa{d_img, d.run_cnt, U, 1, 0, Q, M, s.n_ranks, rk.d_ranks, d_mmean, rk.d_stats, nullptr};
     HIP_TRY(launch(predict_reduce_kernel, dim3((unsigned)Q), dim3(PRED_THREADS), 0, st, qa));
     HIP_TRY(launch(report_confusion_sum_kernel, dim3((unsigned)KK), dim3(REPORT_THREADS), 0, st, d_conf, d.run_cnt, U, d_csum));
-    const bool votes = s.vote || s.p_correct;
-    std::vector<long long> votes_h(votes ? (size_t)ncols : 0);
     HIP_TRY(fetch(s.p_mean, d_mean, (size_t)ncols, st));
-    HIP_TRY(fetch(votes ? votes_h.data() : nullptr, d_votes, (size_t)ncols, st));
+    HIP_TRY(votes.fetch(s.vote || s.p_correct, (size_t)ncols, st));
     HIP_TRY(fetch(s.metric_mean, d_mmean, (size_t)Q, st));
     HIP_TRY(fetch(s.metric_order_stats, rk.d_stats, (size_t)s.n_ranks * Q, st));
     HIP_TRY(fetch((long long*)s.confusion_sum, d_csum, (size_t)KK, st));
     if (s.sample_metrics || s.sample_confusion) {
-        std::vector<int> item_run;
-        if (int rc = item_runs(h, d, src.n_items, &item_run)) return rc;
+        if (int rc = f.items(h, true)) return rc;
         if (int rc = wait_stream(h)) return rc;
         if (s.sample_metrics)
-            if (int rc = scatter_samples(h, d_img, Q, U, item_run, src.weights(), s.sample_metrics, (size_t)Q, 0)) return rc;
+            if (int rc = scatter_samples(h, d_img, Q, U, f.item_run, f.src.weights(), s.sample_metrics, (size_t)Q, 0)) return rc;
         if (s.sample_confusion)
-            if (int rc = scatter_samples(h, d_conf, KK, U, item_run, src.weights(), s.sample_confusion, (size_t)KK, 0)) return rc;
+            if (int rc = scatter_samples(h, d_conf, KK, U, f.item_run, f.src.weights(), s.sample_confusion, (size_t)KK, 0)) return rc;
     }
     if (int rc = wait_stream(h)) return rc;
     for (int n = 0; n < N; ++n)
         if (label_h[(size_t)n] < 0) return fail(-2, "row %d of the handle's data has no class in [0, %d) (internal error)", n, K);
-    for (int c = 0; s.vote && c < ncols; ++c) s.vote[c] = (double)votes_h[(size_t)c] / (double)M;
-    for (int n = 0; s.p_correct && n < N; ++n) s.p_correct[n] = (double)votes_h[(size_t)n * K + label_h[(size_t)n]] / (double)M;
+    votes.shares(s.vote, M);
+    for (int n = 0; s.p_correct && n < N; ++n) s.p_correct[n] = votes.share((size_t)n * K + label_h[(size_t)n], M);
     return 0;
 }
 
@@ -2833,14 +2835,14 @@ int ptnn_uncertainty(ptnn_handle* h, const ptnn_uncertainty_spec* spec) {
     // the pooled outputs of every column as ptnn_predict's; then per row the entropies, or per column the variance
     const bool image = !reg && (s.n_ranks > 0 || s.sample_entropy);
     double *d_mean = nullptr, *d_hmean = nullptr, *d_emean = nullptr, *d_var = nullptr, *d_noise = nullptr;
-    long long* d_votes = nullptr;
+    PooledVotes votes;
     HIP_TRY(mem.alloc(&d_mean, (size_t)ncols));
     if (reg) {
         HIP_TRY(mem.alloc(&d_var, (size_t)ncols));
         HIP_TRY(mem.alloc(&d_noise, 1));
         HIP_TRY(launch(unc_noise_kernel, dim3(1), dim3(UNC_THREADS), 0, st, U, d.run_eta, d.run_cnt, S, d_noise));
     } else {
-        HIP_TRY(mem.alloc(&d_votes, (size_t)ncols));
+        HIP_TRY(votes.alloc(mem, (size_t)ncols));
         HIP_TRY(mem.alloc(&d_emean, (size_t)N));
         if (image) HIP_TRY(mem.alloc(&d_hmean, (size_t)N));     // predict_reduce_kernel's mean of the fp32 image: not an output
         if (int rc = rk.to_device(mem, (size_t)N, st)) return rc;
@@ -2858,7 +2860,7 @@ int ptnn_uncertainty(ptnn_handle* h, const ptnn_uncertainty_spec* spec) {
     const double log_k = O > 1 ? std::log((double)O) : 0.0;
     if (int rc = each_block(N, rows_blk, [&](long long r0, int nr) -> int {
         if (int rc = fwd.run(h, d.base, d.run_off, d_x, xs, (int)r0, nr, U, d_fx)) return rc;
-        PredictRed ra{d_fx, d.run_cnt, U, O, (int)r0 * O, ncols, S, 0, nullptr, d_mean, nullptr, d_votes};
+        PredictRed ra{d_fx, d.run_cnt, U, O, (int)r0 * O, ncols, S, 0, nullptr, d_mean, nullptr, votes.d};
         HIP_TRY(launch(predict_reduce_kernel, dim3((unsigned)(nr * O)), dim3(PRED_THREADS), 0, st, ra));
         if (reg) {
             UncVariance va{d_fx, d.run_cnt, U, (int)r0 * O, S, d_mean, d_var};
@@ -2873,15 +2875,14 @@ int ptnn_uncertainty(ptnn_handle* h, const ptnn_uncertainty_spec* spec) {
         }
         return s.sample_entropy ? scatter_samples(h, d_img, nr, U, item_run, src.weights(), s.sample_entropy, (size_t)N, (size_t)r0) : 0;
     })) return rc;
-    std::vector<long long> votes_h(s.vote ? (size_t)ncols : 0);
     HIP_TRY(fetch(s.mean, d_mean, (size_t)ncols, st));
-    HIP_TRY(fetch(s.vote ? votes_h.data() : nullptr, d_votes, (size_t)ncols, st));
+    HIP_TRY(votes.fetch(s.vote != nullptr, (size_t)ncols, st));
     HIP_TRY(fetch(s.entropy_mean, d_emean, (size_t)N, st));
     HIP_TRY(fetch(s.entropy_order_stats, rk.d_stats, (size_t)s.n_ranks * N, st));
     HIP_TRY(fetch(s.epistemic_var, d_var, (size_t)ncols, st));
     HIP_TRY(fetch(s.aleatoric_var, d_noise, 1, st));
     if (int rc = wait_stream(h)) return rc;
-    for (int c = 0; s.vote && c < ncols; ++c) s.vote[c] = (double)votes_h[(size_t)c] / (double)S;
+    votes.shares(s.vote, S);
     return 0;
 }
 
@@ -2947,9 +2948,7 @@ int ptnn_influence(ptnn_handle* h, const ptnn_influence_spec* spec) {
     if (mat) {
         U = (int)src.n_items;
         int* cnt = nullptr;
-        std::vector<int32_t> ones(s.multiplicity ? 0 : (size_t)U, 1);
-        HIP_TRY(mem.upload(&cnt, s.multiplicity ? s.multiplicity : ones.data(), (size_t)U, st));
-        if (int rc = wait_stream(h)) return rc;                 // `ones` dies at the end of this block
+        if (int rc = upload_counts(h, mem, s.multiplicity, (size_t)U, &cnt)) return rc;
         d_cnt = cnt;
     } else {
         if (int rc = upload_rows(h, mem, cases, I + 1, &d_xc, &xsc)) return rc;
@@ -2995,16 +2994,8 @@ int ptnn_influence(ptnn_handle* h, const ptnn_influence_spec* spec) {
         HIP_TRY(hipMemcpyAsync(dst, stage.data(), stage.size() * sizeof(double), hipMemcpyHostToDevice, st));
         return wait_stream(h);                                  // `stage` is written again for the next block
     };
-    // l of the rows [r0, r0 + nr) of x on every distinct sample, as ptnn_elpd forms it -> dst [nr][U]
     ElpdRed la{};
-    la.mode = reg ? ELPD_REG : ELPD_CLS; la.fx = d_fx; la.eta = d.run_eta; la.cnt = d_cnt; la.U = U; la.O = O; la.S = M;
-    auto loglik_rows = [&](const float* x, int xs, long long r0, int nr, double* dst) -> int {
-        if (int rc = fwd.run(h, d.base, d.run_off, x, xs, (int)r0, nr, U, d_fx)) return rc;
-        la.y = x + I; la.ys = xs; la.row0 = (int)r0; la.ll_out = dst;
-        const long long n_ll = (long long)nr * U;
-        HIP_TRY(launch(elpd_loglik_kernel, dim3((unsigned)((n_ll + ELPD_THREADS - 1) / ELPD_THREADS)), dim3(ELPD_THREADS), 0, st, la, nr));
-        return 0;
-    };
+    la.mode = reg ? ELPD_REG : ELPD_CLS; la.eta = d.run_eta; la.cnt = d_cnt; la.U = U; la.O = O; la.S = M;
     auto moments = [&](const double* v, int nc, double* mean, double* ssd) -> int {
         InflMoments ma{v, d_cnt, U, M, mean, ssd};
         HIP_TRY(launch(influence_moments_kernel, dim3((unsigned)nc), dim3(INFL_THREADS), 0, st, ma));
@@ -3014,7 +3005,7 @@ int ptnn_influence(ptnn_handle* h, const ptnn_influence_spec* spec) {
         if (mat) {
             if (int rc = host_columns(s.target_values, s.n_a, r0, nr, d_A)) return rc;
         } else if (ll_target) {
-            if (int rc = loglik_rows(d_xt, xst, r0, nr, d_A)) return rc;
+            if (int rc = loglik_rows(h, fwd, d, d_xt, xst, r0, nr, d_fx, d_A, la)) return rc;
         } else {
             if (int rc = fwd.run(h, d.base, d.run_off, d_xt, xst, (int)r0, nr, U, d_fx)) return rc;
             const long long n = (long long)nr * O * U;
@@ -3027,7 +3018,7 @@ int ptnn_influence(ptnn_handle* h, const ptnn_influence_spec* spec) {
         if (mat) {
             if (int rc = host_columns(s.loglik, s.n_b, r0, nr, d_B)) return rc;
         } else {
-            if (int rc = loglik_rows(d_xc, xsc, r0, nr, d_B)) return rc;
+            if (int rc = loglik_rows(h, fwd, d, d_xc, xsc, r0, nr, d_fx, d_B, la)) return rc;
         }
         return moments(d_B, nr, d_mb + r0, d_sb + r0);
     };

@@ -1,8 +1,11 @@
-"""Record tests/golden/analysis_bits_parent.npz: every output of the nine posterior-analysis calls that
-tests/test_gpu_analysis_bits.py holds bit for bit (and the digest of each case's inputs).  Run ONCE, on the commit BEFORE a change
-to the reductions and scans of the analysis kernels (csrc/ptnn_dev_wg.hpp and its callers), on the GPU:
+"""Record a golden file of tests/test_gpu_analysis_bits.py: every output of a list of posterior-analysis calls that the test holds
+bit for bit (and the digest of each case's inputs).  Run ONCE per list, on the commit BEFORE the change the list guards, on the GPU:
 
-    python3 profiles/tools/record_analysis_bits.py [out.npz]
+    python3 profiles/tools/record_analysis_bits.py first [out.npz]      tests/golden/analysis_bits_parent.npz: the nine calls recorded
+                                                                        before the reductions and scans of the analysis kernels
+                                                                        (csrc/ptnn_dev_wg.hpp and its callers) were gathered
+    python3 profiles/tools/record_analysis_bits.py second [out.npz]     tests/golden/analysis_bits_parent2.npz: the second list, recorded
+                                                                        before the host code of these calls was folded onto shared paths
 
 The cases live in the test module, so the recording and the test cannot drift apart."""
 import os
@@ -17,7 +20,10 @@ for p in (ROOT, os.path.join(ROOT, "oracle"), os.path.join(ROOT, "tests")):
 
 import test_gpu_analysis_bits as t  # noqa: E402
 
-out = sys.argv[1] if len(sys.argv) > 1 else os.path.join(ROOT, "tests", "golden", t.GOLDEN_FILE)
-rec = t.record()
+if len(sys.argv) < 2 or sys.argv[1] not in ("first", "second"):
+    sys.exit("usage: record_analysis_bits.py first|second [out.npz]")
+file, record = (t.GOLDEN_FILE, t.record) if sys.argv[1] == "first" else (t.GOLDEN_FILE2, t.record2)
+out = sys.argv[2] if len(sys.argv) > 2 else os.path.join(ROOT, "tests", "golden", file)
+rec = record()
 np.savez_compressed(out, **rec)
 print(f"{out}: {len(rec)} arrays, {os.path.getsize(out)} bytes")

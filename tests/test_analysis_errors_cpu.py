@@ -1,10 +1,10 @@
-"""The argument checks of the ten posterior analysis calls, characterised (no GPU): every call checks its spec before it looks
+"""The argument checks of fifteen posterior analysis calls, characterised (no GPU): every call checks its spec before it looks
 at the handle, so a NULL handle shows which fault a spec is refused for, with which return code and which ptnn_last_error()
 text.  CASES names, per call, faulty specs for every refusal that precedes the handle check -- pairs of simultaneous faults
 included, where the order of the checks decides which one is reported -- and valid specs, which reach the handle check.  One
 refusal is left out: ptnn_evidence's "more than 2^31 - 1 expanded draws" needs 8 GiB of host multiplicities to provoke.
 
-The expected values are tests/golden/analysis_errors.json, with the size and the (offset, size) of every field of the ten spec
+The expected values are tests/golden/analysis_errors.json, with the size and the (offset, size) of every field of their spec
 structures.  The file is recorded once, from a library built from the commit BEFORE a change to the analysis calls, never from the
 code under test:
 
@@ -59,6 +59,20 @@ PPC = dict(TRACE, **ROWS)
 PPC_W = dict(w=f32(3, 4), n_w=3, **ROWS)
 PS = dict(TRACE, groups=1 | 4, delta=0.01, r_eff=1.0, **ROWS)
 PS_W = dict(w=f32(3, 4), n_w=3, groups=1 | 4, delta=0.01, r_eff=1.0, **ROWS)
+PD_ARGS = dict(n_grid=3, grid=f32(2, 3), inputs=i32(0, 2), n_inputs=2)
+PD = dict(PREDICT, **PD_ARGS)
+PD_HOST = dict(PREDICT_HOST, **PD_ARGS)
+SHAP_ARGS = dict(n_background=2, background=f32(2, 4), n_coalitions=3, masks=np.array([0, 1, 3], np.uint64), n_terms=2, coef=f64(3, 2))
+SHAP = dict(PREDICT, **SHAP_ARGS)
+SHAP_HOST = dict(PREDICT_HOST, **SHAP_ARGS)
+REPORT = dict(PREDICT, auc=1)
+REPORT_HOST = dict(PREDICT_HOST, x=f32(5, 5), auc=1)
+UNC = dict(TRACE, **ROWS)
+UNC_W = dict(w=f32(3, 4), n_w=3, **ROWS)
+INFL_ROWS = dict(case_source=TRAIN, n_cases=5, target_source=TRAIN, n_targets=4)
+INFL = dict(TRACE, **INFL_ROWS)
+INFL_W = dict(w=f32(3, 4), n_w=3, **INFL_ROWS)
+INFL_MAT = dict(target_values=f32(4, 3), loglik=f64(4, 6), n_w=4, n_a=3, n_b=6)
 
 RANK_FAULTS = [
     ("n_ranks_negative", dict(n_ranks=-1)),
@@ -271,10 +285,141 @@ CASES = {
         ("thin_zero_and_n_rows_zero", PS, dict(thin=0, n_rows=0)),
         ("x_source_unknown_and_multiplicity_negative", PS_W, dict(MULT_NEGATIVE, x_source=7)),
     ]),
+    "partial_dependence": ("PdSpec", "ptnn_partial_dependence", [
+        ("valid_trace", PD, {}),
+        ("valid_host", PD_HOST, dict(ranks=i64(0, 2), n_ranks=2, ranks2=i64(1), n_ranks2=1)),
+        ("valid_all_inputs", PD, dict(inputs=None, n_inputs=0, grid=_nan_at(f32(2, 3), 0, 0))),     # that grid is checked with the handle
+        *[(n, PD, f) for n, f in TRACE_FAULTS + ROW_FAULTS],
+        ("n_w_zero", PD_HOST, dict(n_w=0)),
+        ("n_rows_zero", PD, dict(n_rows=0)),
+        ("n_ranks_negative", PD, dict(n_ranks=-1)),
+        ("n_ranks_above_max", PD, dict(n_ranks=17)),
+        ("ranks_null", PD, dict(n_ranks=2)),
+        ("ice_order_stats_without_ranks", PD, dict(ice_order_stats=f32(5))),
+        ("n_ranks2_negative", PD, dict(n_ranks2=-1)),
+        ("ranks2_null", PD, dict(n_ranks2=2)),
+        ("pd_order_stats_without_ranks2", PD, dict(pd_order_stats=f32(5))),
+        ("range_order_stats_without_ranks2", PD, dict(range_order_stats=f32(5))),
+        ("n_grid_zero", PD, dict(n_grid=0)),
+        ("n_grid_above_max", PD, dict(n_grid=65)),
+        ("grid_null", PD, dict(grid=None)),
+        ("input_list_empty", PD, dict(n_inputs=0)),
+        ("grid_not_finite", PD, dict(grid=_nan_at(f32(2, 3), 1, 2))),
+        ("x_source_unknown_and_n_rows_zero", PD, dict(x_source=7, n_rows=0)),
+        ("thin_zero_and_x_source_unknown", PD, dict(thin=0, x_source=7)),
+        ("n_rows_zero_and_n_ranks_negative", PD, dict(n_rows=0, n_ranks=-1)),
+        ("ranks_null_and_n_ranks2_negative", PD, dict(n_ranks=3, n_ranks2=-1)),
+        ("n_ranks_above_max_and_n_grid_zero", PD, dict(n_ranks=17, n_grid=0)),
+        ("n_ranks2_negative_and_grid_null", PD, dict(n_ranks2=-1, grid=None)),
+        ("n_grid_zero_and_grid_null", PD, dict(n_grid=0, grid=None)),
+        ("grid_null_and_input_list_empty", PD, dict(grid=None, n_inputs=0)),
+        ("input_list_empty_and_grid_not_finite", PD, dict(n_inputs=0, grid=_nan_at(f32(2, 3), 0, 0))),
+    ]),
+    "coalition_values": ("ShapSpec", "ptnn_coalition_values", [
+        ("valid_trace", SHAP, {}),
+        ("valid_host", SHAP_HOST, dict(ranks=i64(0, 2), n_ranks=2, ranks2=i64(1), n_ranks2=1)),
+        ("valid_mask_bit_above_n_in", SHAP, dict(masks=np.array([0, 1, 1 << 40], np.uint64))),      # a mask's bits are checked with the handle
+        *[(n, SHAP, f) for n, f in TRACE_FAULTS + ROW_FAULTS + RANK_FAULTS],
+        ("n_w_zero", SHAP_HOST, dict(n_w=0)),
+        ("n_rows_zero", SHAP, dict(n_rows=0)),
+        ("n_ranks2_negative", SHAP, dict(n_ranks2=-1)),
+        ("ranks2_null", SHAP, dict(n_ranks2=2)),
+        ("abs_order_stats_without_ranks2", SHAP, dict(abs_order_stats=f32(5))),
+        ("n_background_zero", SHAP, dict(n_background=0)),
+        ("n_background_above_max", SHAP, dict(n_background=257)),
+        ("n_coalitions_zero", SHAP, dict(n_coalitions=0)),
+        ("n_coalitions_above_max", SHAP, dict(n_coalitions=4097)),
+        ("n_terms_zero", SHAP, dict(n_terms=0)),
+        ("n_terms_above_max", SHAP, dict(n_terms=65)),
+        ("background_null", SHAP, dict(background=None)),
+        ("masks_null", SHAP, dict(masks=None)),
+        ("coef_null", SHAP, dict(coef=None)),
+        ("coef_not_finite", SHAP, dict(coef=_nan_at(f64(3, 2), 2, 1))),
+        ("x_source_unknown_and_n_rows_zero", SHAP, dict(x_source=7, n_rows=0)),
+        ("n_rows_zero_and_n_ranks_negative", SHAP, dict(n_rows=0, n_ranks=-1)),
+        ("ranks_null_and_n_ranks2_negative", SHAP, dict(n_ranks=3, n_ranks2=-1)),
+        ("n_ranks2_negative_and_n_background_zero", SHAP, dict(n_ranks2=-1, n_background=0)),
+        ("n_background_zero_and_n_coalitions_zero", SHAP, dict(n_background=0, n_coalitions=0)),
+        ("n_coalitions_zero_and_n_terms_zero", SHAP, dict(n_coalitions=0, n_terms=0)),
+        ("n_terms_zero_and_background_null", SHAP, dict(n_terms=0, background=None)),
+        ("background_null_and_masks_null", SHAP, dict(background=None, masks=None)),
+        ("masks_null_and_coef_null", SHAP, dict(masks=None, coef=None)),
+        ("masks_null_and_coef_not_finite", SHAP, dict(masks=None, coef=_nan_at(f64(3, 2), 0, 0))),
+    ]),
+    "class_report": ("ClassReportSpec", "ptnn_class_report", [
+        ("valid_trace", REPORT, {}),
+        ("valid_host", REPORT_HOST, dict(ranks=i64(0, 2), n_ranks=2)),
+        ("valid_without_auc_above_its_cap", REPORT, dict(auc=0, n_rows=16385)),
+        *[(n, REPORT, f) for n, f in TRACE_FAULTS + ROW_FAULTS],
+        ("n_w_zero", REPORT_HOST, dict(n_w=0)),
+        ("n_rows_zero", REPORT, dict(n_rows=0)),
+        ("n_rows_above_the_grid", REPORT, dict(auc=0, n_rows=65535 * 64 + 1)),
+        ("n_ranks_negative", REPORT, dict(n_ranks=-1)),
+        ("n_ranks_above_max", REPORT, dict(n_ranks=17)),
+        ("ranks_null", REPORT, dict(n_ranks=2)),
+        ("metric_order_stats_without_ranks", REPORT, dict(metric_order_stats=f32(5))),
+        ("auc_rows_above_cap", REPORT, dict(n_rows=16385)),
+        ("x_source_unknown_and_n_rows_zero", REPORT, dict(x_source=7, n_rows=0)),
+        ("thin_zero_and_x_source_unknown", REPORT, dict(thin=0, x_source=7)),
+        ("n_rows_above_the_grid_and_n_ranks_negative", REPORT, dict(n_rows=65535 * 64 + 1, n_ranks=-1)),
+        ("n_ranks_negative_and_auc_rows_above_cap", REPORT, dict(n_ranks=-1, n_rows=16385)),
+    ]),
+    "uncertainty": ("UncertaintySpec", "ptnn_uncertainty", [
+        ("valid_trace", UNC, {}),
+        ("valid_host", UNC_W, dict(multiplicity=i32(2, 0, 1), ranks=i64(0, 2), n_ranks=2)),
+        ("no_source", UNC, dict(nsteps=0)),
+        *[(n, UNC, f) for n, f in TRACE_FAULTS + ROW_FAULTS],
+        ("n_w_zero", UNC_W, dict(n_w=0)),
+        ("n_rows_zero", UNC, dict(n_rows=0)),
+        ("n_ranks_negative", UNC, dict(n_ranks=-1)),
+        ("n_ranks_above_max", UNC, dict(n_ranks=17)),
+        ("ranks_null", UNC, dict(n_ranks=2)),
+        ("entropy_order_stats_without_ranks", UNC, dict(entropy_order_stats=f32(5))),
+        ("multiplicity_negative", UNC_W, MULT_NEGATIVE),
+        ("no_source_and_thin_zero", UNC, dict(nsteps=0, thin=0)),
+        ("thin_zero_and_x_source_unknown", UNC, dict(thin=0, x_source=7)),
+        ("x_source_unknown_and_n_rows_zero", UNC, dict(x_source=7, n_rows=0)),
+        ("n_rows_zero_and_n_ranks_negative", UNC, dict(n_rows=0, n_ranks=-1)),
+        ("ranks_null_and_multiplicity_negative", UNC_W, dict(MULT_NEGATIVE, n_ranks=2)),
+    ]),
+    "influence": ("InfluenceSpec", "ptnn_influence", [
+        ("valid_trace", INFL, {}),
+        ("valid_host", INFL_W, dict(multiplicity=i32(2, 0, 1), target_kind=1)),
+        ("valid_matrices", INFL_MAT, dict(multiplicity=i32(1, 0, 2, 1), case_source=7, target_kind=9)),
+        ("target_values_without_loglik", INFL_MAT, dict(loglik=None)),
+        ("loglik_without_target_values", INFL_MAT, dict(target_values=None)),
+        ("w_and_matrices", INFL_MAT, dict(w=f32(4, 3))),
+        ("no_source", INFL, dict(nsteps=0)),
+        *[(n, INFL, f) for n, f in TRACE_FAULTS],
+        ("n_w_zero", INFL_W, dict(n_w=0)),
+        ("n_w_zero_matrices", INFL_MAT, dict(n_w=0)),
+        ("n_a_zero", INFL_MAT, dict(n_a=0)),
+        ("n_b_zero", INFL_MAT, dict(n_b=0)),
+        ("matrices_too_many_elements", INFL_MAT, dict(n_a=1 << 14, n_b=(1 << 13) + 1)),
+        ("target_kind_unknown", INFL, dict(target_kind=2)),
+        ("case_source_unknown", INFL, dict(case_source=7)),
+        ("case_x_null", INFL, dict(case_source=HOST)),
+        ("target_source_unknown", INFL, dict(target_source=-1)),
+        ("target_x_null", INFL, dict(target_source=HOST)),
+        ("n_cases_zero", INFL, dict(n_cases=0)),
+        ("n_targets_zero", INFL, dict(n_targets=0)),
+        ("multiplicity_negative", INFL_W, MULT_NEGATIVE),
+        ("loglik_not_finite", INFL_MAT, dict(loglik=_nan_at(f64(4, 6), 2, 5))),
+        ("target_values_without_loglik_and_w", INFL_MAT, dict(loglik=None, w=f32(4, 3))),
+        ("w_and_matrices_and_n_w_zero", INFL_MAT, dict(w=f32(4, 3), n_w=0)),
+        ("no_source_and_target_kind_unknown", INFL, dict(nsteps=0, target_kind=2)),
+        ("thin_zero_and_case_source_unknown", INFL, dict(thin=0, case_source=7)),
+        ("n_w_zero_and_n_a_zero", INFL_MAT, dict(n_w=0, n_a=0)),
+        ("target_kind_unknown_and_case_source_unknown", INFL, dict(target_kind=2, case_source=7)),
+        ("case_x_null_and_target_source_unknown", INFL, dict(case_source=HOST, target_source=-1)),
+        ("target_x_null_and_n_cases_zero", INFL, dict(target_source=HOST, n_cases=0)),
+        ("n_targets_zero_and_multiplicity_negative", INFL_W, dict(MULT_NEGATIVE, n_targets=0)),
+        ("multiplicity_negative_and_loglik_not_finite", INFL_MAT, dict(multiplicity=i32(1, 1, -1, 1), loglik=_nan_at(f64(4, 6), 0, 0))),
+    ]),
 }
 SPEC_FAULTS = ("null_spec", "struct_bytes_zero", "struct_bytes_off_by_one")       # the first check of every call
 POINTER_OF = {np.dtype(np.float32): C.c_float, np.dtype(np.float64): C.c_double, np.dtype(np.int32): C.c_int32,
-              np.dtype(np.int64): C.c_int64}
+              np.dtype(np.int64): C.c_int64, np.dtype(np.uint64): C.c_uint64}
 
 
 def _lib():

@@ -8,7 +8,15 @@ net (4-5-1) and a classification net (4-12-3) with 24 data rows, from host-given
 2 .. 4, U = 100 (threads of the 256-wide trees hold the identity), 256 (one item per thread) and 300 (the strided second pass;
 the ragged last chunk of powerscale's prefix sums).  Every output of every call is compared as bits, a NaN with a NaN.  One
 headline output per call is also held to the float64 reference of that analysis's own GPU test at that test's tolerance, so a
-golden recorded from a broken build fails here on its own account."""
+golden recorded from a broken build fails here on its own account.
+
+A second list of calls -- partial_dependence, coalition_values, class_report, uncertainty, influence (of the predictions and of
+the log-likelihoods), forecast, sensitivity with sample_abs and predict with samples -- is held in the same way to
+tests/golden/analysis_bits_parent2.npz, recorded on the commit before the host code of these calls was folded onto shared paths
+(the rows-by-vectors frame, the summary of signed columns, the pooled votes, the log-likelihood of rows): the same cases, every
+output as bits.  Each case runs a second time with every call's scratch budget at five rows' worth, so 24 rows take five blocks
+with a ragged last one, and is held to the same recorded bits: the shared helpers' `last` flag and row offsets live on that path,
+and no output depends on the blocking."""
 import hashlib
 import tempfile
 
@@ -47,6 +55,13 @@ STONES = (0.3, 0.0)                   # evidence: two rungs of U / 2 vectors eac
 PRIOR_A = (0.0, 0.5)
 SEED = 0x5EED_0000_0B17
 EPS = 0.01
+# the second list
+GOLDEN_FILE2 = "analysis_bits_parent2.npz"
+CALLS2 = ("partial_dependence", "coalition_values", "class_report", "uncertainty", "influence_prediction", "influence_loglik",
+          "forecast", "sensitivity_sample_abs", "predict_samples")
+CALLS2_OF = {"reg": tuple(c for c in CALLS2 if c != "class_report"), "cls": tuple(c for c in CALLS2 if c != "forecast")}
+N_GRID, N_BACKGROUND, N_TERMS, HORIZON = 5, 8, 4, 6
+BLOCK_ROWS = 5                        # rows per block of the blocked run: 24 rows in blocks of 5, 5, 5, 5 and 4
 
 _HANDLES = {}
 
@@ -98,6 +113,61 @@ def run_calls(pt, net, U):
     return out
 
 
+def scratch_budgets(net, U):
+    """{call of the second list: (its scratch variable, the bytes that hold BLOCK_ROWS rows of its block at U distinct vectors)}:
+    the row sizes are those of the calls' own budget arithmetic (fp32 columns per row and distinct vector; ptnn_influence gives a
+    quarter of its budget to the block of targets, whose rows carry their double columns beside the forward image)."""
+    task, (I, _, O) = NETS[net]
+    row = 4 * U
+    return {
+        "partial_dependence": ("PTNN_PD_SCRATCH_BYTES", BLOCK_ROWS * row * I * N_GRID * O),
+        "coalition_values": ("PTNN_SHAP_SCRATCH_BYTES", BLOCK_ROWS * row * O * N_TERMS),
+        "class_report": ("PTNN_REPORT_SCRATCH_BYTES", BLOCK_ROWS * row * O),
+        "uncertainty": ("PTNN_UNC_SCRATCH_BYTES", BLOCK_ROWS * row * (O + (task == CLS))),
+        "influence_prediction": ("PTNN_INFLUENCE_SCRATCH_BYTES", 4 * BLOCK_ROWS * (row * O + 8 * U * O)),
+        "influence_loglik": ("PTNN_INFLUENCE_SCRATCH_BYTES", 4 * BLOCK_ROWS * (row * O + 8 * U)),
+        "forecast": ("PTNN_FORECAST_SCRATCH_BYTES", BLOCK_ROWS * row * HORIZON),
+        "sensitivity_sample_abs": ("PTNN_SENSITIVITY_SCRATCH_BYTES", BLOCK_ROWS * row * O * I),
+        "predict_samples": ("PTNN_PREDICT_SCRATCH_BYTES", BLOCK_ROWS * row * O),
+    }
+
+
+def run_calls2(pt, net, U, setenv=None):
+    """{call: the binding's whole result} of the second list of one case; with `setenv` (monkeypatch.setenv) every call runs with
+    its scratch budget at BLOCK_ROWS rows."""
+    task, (I, _, O) = NETS[net]
+    s = pt._sampler
+    _, train = handle(net)
+    w, eta, mult = samples(net, U)
+    M = int(mult.sum())
+    ranks = (0, M // 2, M - 1)
+    src = dict(w=w, multiplicity=mult)
+    X = np.asarray(train, np.float32)[:, :I]
+    grid = np.percentile(X, np.linspace(5, 95, N_GRID), axis=0).T.astype(np.float32)                     # [I, N_GRID]
+    rng = np.random.default_rng(31 * U + task)
+    coef = rng.normal(0.0, 1.0, (1 << I, N_TERMS))
+    calls = {
+        "partial_dependence": lambda: s.partial_dependence("train", grid=grid, ranks=ranks, ranks2=ranks, ice_mean=True, sample_pd=True,
+                                                           sample_range=True, **src),
+        "coalition_values": lambda: s.coalition_values("train", background=X[:N_BACKGROUND], masks=np.arange(1 << I, dtype=np.uint64),
+                                                       coef=coef, ranks=ranks, ranks2=ranks, counts=True, sample_abs=True, **src),
+        "class_report": lambda: s.class_report("train", ranks=ranks, auc=True, sample_confusion=True, **src),
+        "uncertainty": lambda: s.uncertainty("train", eta=eta, ranks=ranks, samples=True, **src),
+        "influence_prediction": lambda: s.influence("test", "train", of="prediction", eta=eta, **src),
+        "influence_loglik": lambda: s.influence("test", "train", of="loglik", eta=eta, **src),
+        "forecast": lambda: s.forecast(HORIZON, "train", eta=eta, ranks=ranks, **src),
+        "sensitivity_sample_abs": lambda: s.sensitivity("train", ranks=ranks, ranks2=ranks, sample_abs=True, **src),
+        "predict_samples": lambda: s.predict("train", ranks=ranks, vote=task == CLS, samples=True, **src),
+    }
+    budgets = scratch_budgets(net, U)
+    out = {}
+    for call in CALLS2_OF[net]:
+        if setenv:
+            setenv(budgets[call][0], str(budgets[call][1]))
+        out[call] = calls[call]()
+    return out
+
+
 def key(net, U, call, name):
     return f"{net}_U{U}_{call}_{name}"
 
@@ -125,6 +195,19 @@ def record():
     return rec
 
 
+def record2():
+    """The second golden file: the digests again, and every output of the second list."""
+    rec = {}
+    for net, U in CASES:
+        pt, train = handle(net)
+        rec[key(net, U, "inputs", "sha256")] = digest(net, U, train)
+        for call, res in run_calls2(pt, net, U).items():
+            for name, v in res.items():
+                if v is not None:
+                    rec[key(net, U, call, name)] = np.asarray(v)
+    return rec
+
+
 def same_bits(got, want):
     """Element-wise: the same bits, or both NaN (a commuted fmax or add may pick the other payload)."""
     got, want = np.ascontiguousarray(got), np.ascontiguousarray(want)
@@ -136,14 +219,13 @@ def same_bits(got, want):
     return (got.view(u) == want.view(u)) | (np.isnan(got) & np.isnan(want))
 
 
-_GOLDEN = None
+_GOLDEN = {}
 
 
-def golden():
-    global _GOLDEN
-    if _GOLDEN is None:
-        _GOLDEN = parity.golden(GOLDEN_FILE)
-    return _GOLDEN
+def golden(file=GOLDEN_FILE):
+    if file not in _GOLDEN:
+        _GOLDEN[file] = parity.golden(file)
+    return _GOLDEN[file]
 
 
 def check_references(pt, net, U, train, out):
@@ -225,12 +307,9 @@ def check_references(pt, net, U, train, out):
     assert np.array_equal(got["sat_count"][0], np.sum((f32 < EPS) | (f32 > 1.0 - EPS), axis=0))
 
 
-@pytest.mark.parametrize("net,U", CASES, ids=[f"{n}-U{u}" for n, u in CASES])
-def test_outputs_equal_the_parent_commit(net, U):
-    g = golden()
-    pt, train = handle(net)
+def assert_recorded(g, net, U, train, out):
+    """Every output of `out` has the recorded bits, and nothing recorded for the case is missing."""
     assert np.array_equal(digest(net, U, train), g[key(net, U, "inputs", "sha256")]), "the inputs are not the recorded ones"
-    out = run_calls(pt, net, U)
     seen = set()
     for call, res in out.items():
         for name, v in res.items():
@@ -243,4 +322,48 @@ def test_outputs_equal_the_parent_commit(net, U):
             same = same_bits(got, want)
             assert same.all(), f"{k}: {int((~same).sum())} of {same.size} values differ, first at {np.argwhere(~same)[0]}"
     assert seen == {k for k in g if k.startswith(f"{net}_U{U}_") and "_inputs_" not in k}, "an output of the recording is missing"
+
+
+@pytest.mark.parametrize("net,U", CASES, ids=[f"{n}-U{u}" for n, u in CASES])
+def test_outputs_equal_the_parent_commit(net, U):
+    pt, train = handle(net)
+    out = run_calls(pt, net, U)
+    assert_recorded(golden(), net, U, train, out)
     check_references(pt, net, U, train, out)
+
+
+def check_references2(net, U, out):
+    """The second list against itself and against numpy: the three calls that pool the classifier agree on its mean and votes, a
+    mean is the mean of the samples beside it, the curve is the row mean of ICE."""
+    _, _, mult = samples(net, U)
+    M = int(mult.sum())
+    pred, unc = out["predict_samples"], out["uncertainty"]
+    assert pred["n_samples"] == M and pred["n_distinct"] == U
+    np.testing.assert_allclose(pred["mean"], pred["samples"].astype(np.float64).mean(axis=0), rtol=1e-12, atol=0)
+    assert same_bits(unc["mean"], pred["mean"]).all()
+    if NETS[net][0] == CLS:
+        rep = out["class_report"]
+        assert same_bits(rep["p_mean"], pred["mean"]).all()
+        assert np.array_equal(unc["vote"], pred["vote"]) and np.array_equal(rep["vote"], pred["vote"])
+        np.testing.assert_allclose(pred["vote"].sum(axis=1), 1.0, rtol=1e-12)
+        assert np.array_equal(rep["confusion_sum"], rep["sample_confusion"].astype(np.int64).sum(axis=0))
+    pd = out["partial_dependence"]
+    np.testing.assert_allclose(pd["pd_mean"], pd["ice_mean"].mean(axis=0), rtol=1e-12, atol=1e-300)
+    np.testing.assert_allclose(pd["range_mean"], pd["sample_range"].astype(np.float64).mean(axis=0), rtol=1e-12, atol=0)
+    for name in ("coalition_values", "sensitivity_sample_abs"):
+        r = out[name]
+        np.testing.assert_allclose(r["abs_mean"], r["sample_abs"].astype(np.float64).mean(axis=0), rtol=1e-6, atol=0)    # fp32 a_s
+
+
+@pytest.mark.parametrize("net,U", CASES, ids=[f"{n}-U{u}" for n, u in CASES])
+def test_second_list_equals_the_parent_commit(net, U):
+    pt, train = handle(net)
+    out = run_calls2(pt, net, U)
+    assert_recorded(golden(GOLDEN_FILE2), net, U, train, out)
+    check_references2(net, U, out)
+
+
+@pytest.mark.parametrize("net,U", CASES, ids=[f"{n}-U{u}" for n, u in CASES])
+def test_second_list_in_five_blocks_of_rows_equals_the_parent_commit(net, U, monkeypatch):
+    pt, train = handle(net)
+    assert_recorded(golden(GOLDEN_FILE2), net, U, train, run_calls2(pt, net, U, setenv=monkeypatch.setenv))
