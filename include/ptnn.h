@@ -1355,6 +1355,73 @@ typedef struct ptnn_influence_spec {
 
 int ptnn_influence(ptnn_handle *h, const ptnn_influence_spec *spec);
 
+/* ---- posterior modes: function-space clusters of the sampled nets (nothing in the reference) ----
+ * A one-hidden-layer net has H! x (sign) equivalent labelings of its hidden units, so sampled nets are compared by what they
+ * compute, not by where their weights lie; DESIGN.md section 31.
+ * Samples: ptnn_predict's selection, sources 1 (the trace) and 2 (host vectors w with multiplicity), no eta: a mode is a property of
+ *   the function.  It yields U distinct weight vectors with integer counts c_u, M = sum c_u, and per selected item the distinct
+ *   sample it belongs to (predict_scan_kernel's item_run).  Source 3: a host matrix values [n_w, n_a] float32 with multiplicity and
+ *   no forward pass; every host row is a sample, U = n_w.
+ * Outputs of the nets: F[u, j], j < n = n_rows x n_out, the fp32 outputs of ptnn_predict's forward pass on the rows x (source 3:
+ *   F = values, n = n_a).
+ * Squared distance: sq[u, v] = sum_j (F[u, j] - F[v, j])^2 in double: each difference is taken of the two values widened to
+ *   double, each term added by fma(d, d, acc), one accumulator per element, carried in the matrix across the column blocks, columns
+ *   ascending.  An element's bits depend on the two samples' output vectors and n only: not on the tile, the row blocks, the grid or
+ *   the scratch.  sq[u, u] = 0, sq[u, v] = sq[v, u] bit for bit, no atomics.  The distance a user sees is d = sqrt(sq / n), the RMS
+ *   difference of two nets' outputs in output units (both tasks put out values in [0, 1]).
+ * Density (density-peaks clustering, Rodriguez & Laio 2014; all comparisons on sq): near_sq = radius^2 x n, formed by the caller in
+ *   double.  rho_u = sum_v c_v [sq[u, v] <= near_sq] (includes v = u).  v precedes u iff rho_v > rho_u, or rho_v = rho_u and v < u.
+ *   delta_sq_u = min over the v that precede u of sq[u, v]; parent_u = the lowest such v that attains it.  The one sample nothing
+ *   precedes has parent -1 and delta_sq = max_v sq[u, v].  Samples with c_u = 0 (multiplicities of sources 2 and 3) are absent: they
+ *   count nowhere and come back with rho 0, delta_sq 0 and parent -1.  A non-finite sq (NaN or infinite outputs) among the present
+ *   samples is counted and the call refused with a text that names the first such sample.
+ * spread_sq = sum_u sum_v c_u c_v sq[u, v] / M^2 in double, in a fixed order (per row a strided partial and an LDS tree, the rows
+ *   added in ascending order).
+ * Outputs, any may be NULL (without sq_dist the matrix is still formed in device memory): rho, delta_sq, parent, count hold
+ *   n_items entries (n_items = the selected trace rows, or n_w), of which the first U = *n_distinct are written; item_sample
+ *   [n_items], items chain-major [n_chains, m] for the trace; sq_dist and outputs are written packed, [U, U] and [U, n], and must
+ *   hold min(n_items, 11585)^2 and min(n_items, 11585) x n entries.
+ * Refused: U x U > PTNN_MODES_MAX_ELEMENTS (the text gives U and names thin= / chains= as the way down); M < 1; near_sq not finite
+ *   or < 0; values together with w; room < n_items; a communicator attached (one GPU only).
+ * Runs on the handle's stream behind everything queued and returns when done; the columns are processed in blocks as ptnn_predict
+ *   cuts them, whose scratch stays under $PTNN_MODES_SCRATCH_BYTES (read per call, default 1 GiB; the matrix lies beside it), which
+ *   changes no result.  Touches no chain state, tape, counter or trace row. */
+#define PTNN_MODES_MAX_ELEMENTS (1 << 27)
+
+typedef struct ptnn_modes_spec {
+    int32_t struct_bytes;         /* = sizeof(ptnn_modes_spec): ABI guard */
+    /* source 1: the trace (used when w == NULL and values == NULL) */
+    const int32_t *replicas;      /* local replica indices, or NULL = all */
+    int32_t n_replicas;           /* entries of replicas (ignored when NULL) */
+    int32_t step0, nsteps, thin;  /* trace rows step0, step0 + thin, ... < step0 + nsteps (thin >= 1) */
+    /* source 2: host vectors */
+    const float *w;               /* [n_w, P] or NULL */
+    const int32_t *multiplicity;  /* [n_w] >= 0, or NULL = 1 each (sources 2 and 3) */
+    int64_t n_w;
+    /* input rows (sources 1 and 2) */
+    int32_t x_source;             /* PTNN_PREDICT_X_HOST | _TRAIN | _TEST */
+    int32_t n_rows;
+    const float *x;               /* [n_rows, n_in] (host rows only) */
+    /* source 3: a host matrix */
+    const float *values;          /* [n_w, n_a] or NULL */
+    int32_t n_a;
+    int32_t reserved_;
+    double near_sq;               /* radius^2 x n */
+    int64_t room;                 /* entries that rho, delta_sq, parent, count and item_sample each hold: >= n_items, else refused */
+    /* outputs */
+    int64_t *rho;                 /* [n_items], U written */
+    double *delta_sq;             /* [n_items], U written */
+    int32_t *parent;              /* [n_items], U written */
+    int32_t *count;               /* [n_items], U written */
+    int32_t *item_sample;         /* [n_items] */
+    double *spread_sq;            /* [1] */
+    double *sq_dist;              /* [U, U] packed */
+    float *outputs;               /* [U, n] packed */
+    int64_t *n_samples, *n_distinct;
+} ptnn_modes_spec;
+
+int ptnn_modes(ptnn_handle *h, const ptnn_modes_spec *spec);
+
 /* the HIP stream (hipStream_t) all of this handle's work is queued on: lets the caller order its collectives after the
  * segment / before the swap kernels on the device instead of synchronising the host */
 int ptnn_stream(ptnn_handle *h, void **hip_stream);

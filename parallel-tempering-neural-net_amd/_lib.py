@@ -326,6 +326,23 @@ INFLUENCE_MAX_ELEMENTS = 1 << 27
 INFLUENCE_KCHUNK = 512                   # distinct samples per partial sum (csrc/ptnn_dev_influence.hpp: INFL_KCHUNK)
 
 
+class ModesSpec(C.Structure):
+    """ptnn_modes_spec (include/ptnn.h)."""
+    _fields_ = _SELECTION + [
+        ("w", C.POINTER(C.c_float)), ("multiplicity", C.POINTER(C.c_int32)), ("n_w", C.c_int64),
+        ("x_source", C.c_int32), ("n_rows", C.c_int32), ("x", C.POINTER(C.c_float)),
+        ("values", C.POINTER(C.c_float)), ("n_a", C.c_int32), ("reserved_", C.c_int32), ("near_sq", C.c_double),
+        ("room", C.c_int64), ("rho", C.POINTER(C.c_int64)), ("delta_sq", C.POINTER(C.c_double)), ("parent", C.POINTER(C.c_int32)),
+        ("count", C.POINTER(C.c_int32)), ("item_sample", C.POINTER(C.c_int32)), ("spread_sq", C.POINTER(C.c_double)),
+        ("sq_dist", C.POINTER(C.c_double)), ("outputs", C.POINTER(C.c_float)),
+        ("n_samples", C.POINTER(C.c_int64)), ("n_distinct", C.POINTER(C.c_int64)),
+    ]
+
+
+MODES_MAX_ELEMENTS = 1 << 27
+MODES_MAX_DISTINCT = math.isqrt(MODES_MAX_ELEMENTS)      # 11585: the largest U with U * U <= MODES_MAX_ELEMENTS
+
+
 class LadderAdaptSpec(C.Structure):
     """ptnn_ladder_adapt_spec (include/ptnn.h)."""
     _fields_ = [("struct_bytes", C.c_int32), ("rounds", C.c_int32), ("kappa0", C.c_double), ("t0", C.c_double)]
@@ -429,6 +446,7 @@ SYMBOLS = {
     "ptnn_class_report": (C.c_int, [C.c_void_p, C.POINTER(ClassReportSpec)]),
     "ptnn_uncertainty": (C.c_int, [C.c_void_p, C.POINTER(UncertaintySpec)]),
     "ptnn_influence": (C.c_int, [C.c_void_p, C.POINTER(InfluenceSpec)]),
+    "ptnn_modes": (C.c_int, [C.c_void_p, C.POINTER(ModesSpec)]),
 }
 
 
@@ -1153,6 +1171,55 @@ class Sampler:
                    case_mean=np.empty(n_b), case_var=np.empty(n_b))
         _bind(spec, out)
         return self._call(self.lib.ptnn_influence, spec, out)
+
+    def modes(self, x=None, *, radius_sq_sum, values=None, multiplicity=None, sq_dist=False, outputs=False, **source):
+        """ptnn_modes: the squared function-space distance sq[u, v] = sum_j (F[u, j] - F[v, j])^2 (double) between the U distinct
+        selected samples, and the density-peaks stage on it, on the device.  Source (`source`: replicas, step0, nsteps, thin, or
+        w): the trace rows or host vectors w [n, P] as predict() takes them, F the fp32 network outputs on x ("train", "test" or
+        rows [n_rows, n_in]), n = n_rows * n_out; or a host matrix values [n, n_a] float32 (no forward pass, x is ignored; every
+        row is a sample, n = n_a).  `multiplicity` [n]: integer counts of the host items.  radius_sq_sum = radius^2 * n: rho_u
+        counts the samples with sq[u, v] <= it.  -> dict(rho [U] int64, delta_sq [U] float64, parent [U] int32, count [U] int32,
+        item_sample [n_items] int32 (the distinct sample of every selected item, chain-major for the trace), spread_sq,
+        sq_dist [U, U] float64 and outputs [U, n] float32 on request, n_samples, n_distinct)."""
+        spec, keep = _spec(ModesSpec), []
+        if values is not None:
+            if source.get("w") is not None:
+                raise ValueError("values takes the place of the samples: no w with it")
+            va = _f32(values)
+            if va.ndim != 2 or va.shape[1] < 1:
+                raise ValueError(f"values must be [n_samples, n_a], got shape {va.shape}")
+            keep.append(va)
+            spec.values, spec.n_w, spec.n_a = _ptr(va), va.shape[0], va.shape[1]
+            n_items, n = va.shape[0], va.shape[1]
+            self._multiplicity(spec, keep, multiplicity, (n_items,), "multiplicity must have one entry per sample")
+        else:
+            self._rows(spec, keep, x, "x", (self.cfg.n_in, "n_in columns"))
+            n = spec.n_rows * self.cfg.n_out
+            src = dict(dict(w=None, replicas=None, step0=0, nsteps=None, thin=1), **source)
+            self._samples(spec, keep, multiplicity=multiplicity, unit="vector", **src)
+            if src["w"] is not None:
+                n_items = int(spec.n_w)
+            else:
+                chains = self.R if src["replicas"] is None else int(spec.n_replicas)
+                n_items = max(0, chains * -(-spec.nsteps // max(1, spec.thin)))
+        spec.near_sq = float(radius_sq_sum)
+        room = spec.room = max(1, n_items)
+        big = min(room, MODES_MAX_DISTINCT)                 # sq_dist and outputs come back packed [U, U], [U, n]: U is known after the call
+        out = dict(rho=np.zeros(room, np.int64), delta_sq=np.zeros(room, np.float64), parent=np.full(room, -1, np.int32),
+                   count=np.zeros(room, np.int32), item_sample=np.zeros(room, np.int32), spread_sq=np.zeros(1, np.float64),
+                   sq_dist=np.empty(big * big, np.float64) if sq_dist else None, outputs=np.empty(big * n, np.float32) if outputs else None)
+        _bind(spec, out)
+        out = self._call(self.lib.ptnn_modes, spec, out)
+        U = out["n_distinct"]
+        for k in ("rho", "delta_sq", "parent", "count"):
+            out[k] = out[k][:U].copy()
+        out["item_sample"] = out["item_sample"][:n_items]
+        out["spread_sq"] = float(out["spread_sq"][0])
+        if sq_dist:
+            out["sq_dist"] = out["sq_dist"][:U * U].reshape(U, U).copy()
+        if outputs:
+            out["outputs"] = out["outputs"][:U * n].reshape(U, n).copy()
+        return out
 
     def sensitivity(self, x="test", *, replicas=None, step0=0, nsteps=None, thin=1, w=None, multiplicity=None, ranks=(), ranks2=(),
                     sample_abs=False, samples=False):

@@ -1,5 +1,5 @@
 // ptnn_analysis.hip -- the posterior analysis calls of libptnn.so: predict, convergence, rank_convergence, elpd, lfo, forecast, evidence, calibration,
-// forecast_score, sensitivity, partial_dependence, coalition_values, ppc, powerscale, prior_predictive, influence, and the sample-selection path they share.  The shape-independent analysis kernels are defined in this object: it includes them.
+// forecast_score, sensitivity, partial_dependence, coalition_values, ppc, powerscale, prior_predictive, influence, modes, and the sample-selection path they share.  The shape-independent analysis kernels are defined in this object: it includes them.
 #include "ptnn_shapes.hpp"                   // PTNN_SHAPES
 #include "ptnn_analysis_device.hpp"          // the per-shape forward kernels and their table, AnalysisShape
 namespace ptnn {
@@ -20,6 +20,7 @@ namespace ptnn {
 #include "ptnn_dev_report.hpp"               // classification report: confusion counts, Mann-Whitney counts and metric columns per sample
 #include "ptnn_dev_uncertainty.hpp"          // predictive uncertainty: entropy per sample and its mean per row, variance per column, mean noise
 #include "ptnn_dev_influence.hpp"            // case influence: column moments and the tiled FP64 cross-covariance over the samples
+#include "ptnn_dev_modes.hpp"                // posterior modes: the tiled FP64 all-pairs distance of the samples' outputs, density and parents
 }  // namespace ptnn
 #include "ptnn_host.hpp"
 #include "ptnn_rank_plan.hpp"               // the blocks of ptnn_rank_convergence: host arithmetic, checked on its own
@@ -3059,6 +3060,139 @@ int ptnn_influence(ptnn_handle* h, const ptnn_influence_spec* spec) {
     if (int rc = wait_stream(h)) return rc;
     for (size_t c = 0; c < ssd_a.size(); ++c) s.target_var[c] = ssd_a[c] / (double)(M - 1);
     for (size_t c = 0; c < ssd_b.size(); ++c) s.case_var[c] = ssd_b[c] / (double)(M - 1);
+    return 0;
+}
+
+// ---- posterior modes (ptnn_dev_modes.hpp) ----
+static int modes_cap(long long U) {
+    if (U * U > PTNN_MODES_MAX_ELEMENTS)
+        return fail(-1, "%lld distinct samples: the %lld x %lld distance matrix exceeds 2^27 elements per call; select fewer samples "
+                        "(thin=, chains=)", U, U, U);
+    return 0;
+}
+
+int ptnn_modes(ptnn_handle* h, const ptnn_modes_spec* spec) {
+    // argument checks first: none of them needs the handle or a device
+    if (int rc = check_spec(spec, "ptnn_modes_spec")) return rc;
+    const ptnn_modes_spec& s = *spec;
+    const bool mat = s.values != nullptr;                       // source 3
+    if (mat && s.w) return fail(-1, "give host vectors w or a host matrix values, not both");
+    if (!std::isfinite(s.near_sq) || s.near_sq < 0.0) return fail(-1, "near_sq = %g must be a finite number >= 0", s.near_sq);
+    RowsByVectors f(s, RankOutputs{0, nullptr, nullptr});
+    if (mat) {
+        f.src.host = true;
+        if (int rc = check_source(f.src, "samples")) return rc;
+        if (s.n_a < 1) return fail(-1, "n_a = %d must be >= 1", s.n_a);
+        if (int rc = modes_cap(s.n_w)) return rc;               // every host row is a sample
+    } else {
+        if (int rc = f.check()) return rc;
+    }
+    if (int rc = check_handle(h, "ptnn_modes")) return rc;
+    const int I = h->cfg.n_in, O = h->cfg.n_out;
+    if (!mat)
+        if (int rc = fit_rows(h, f.rows)) return rc;
+    if (int rc = f.select(h, s.n_samples)) return rc;
+    if (s.room < f.src.n_items)
+        return fail(-1, "room = %lld entries per output but the selection has %lld items", (long long)s.room, f.src.n_items);
+
+    ForwardPlan fwd;
+    int* d_cnt_own = nullptr;
+    if (mat) {
+        if (int rc = start_device(h)) return rc;
+        f.U = (int)f.src.n_items;
+        if (int rc = upload_counts(h, f.mem, s.multiplicity, (size_t)f.U, &d_cnt_own)) return rc;
+        if (s.n_distinct) *s.n_distinct = f.U;
+    } else {
+        if (int rc = f.stage(h, I, s.n_distinct)) return rc;
+        if (int rc = modes_cap(f.U)) return rc;
+        if (int rc = fwd.init(h, "posterior modes")) return rc;
+    }
+    hipStream_t st = h->stream;
+    DeviceScratch& mem = f.mem;
+    const int U = f.U, cpr = mat ? 1 : O;                       // columns per row of x (source 3: per column of values)
+    const int* d_cnt = mat ? d_cnt_own : f.d.run_cnt;
+    const long long rows = mat ? s.n_a : s.n_rows, n = rows * cpr;
+    const long long M = f.M;
+    const bool want_parent = s.parent || s.delta_sq;
+    const bool want_sq = want_parent || s.rho || s.spread_sq || s.sq_dist;
+    const bool want_out = s.outputs && !mat;
+    // the column blocks as ptnn_predict cuts them: fx scratch U x (rows x O) floats under the budget; the matrix lies beside it
+    const long long rows_blk = row_block(scratch_budget("PTNN_MODES_SCRATCH_BYTES"), (size_t)U * sizeof(float) * cpr, rows);
+    float *d_fx = nullptr, *d_out = nullptr;
+    double *d_sq = nullptr, *d_max = nullptr, *d_part = nullptr, *d_spread = nullptr, *d_delta = nullptr;
+    long long *d_rho = nullptr, *d_row_bad = nullptr, *d_bad = nullptr;
+    unsigned int* d_ticket = nullptr;
+    int* d_parent = nullptr;
+    if (want_sq || want_out) HIP_TRY(mem.alloc(&d_fx, (size_t)rows_blk * cpr * U));
+    if (want_out) HIP_TRY(mem.alloc(&d_out, (size_t)U * n));
+    if (want_sq) {
+        HIP_TRY(mem.alloc(&d_sq, (size_t)U * U));
+        HIP_TRY(mem.alloc(&d_rho, (size_t)U));
+        HIP_TRY(mem.alloc(&d_max, (size_t)U));
+        HIP_TRY(mem.alloc(&d_part, (size_t)U));
+        HIP_TRY(mem.alloc(&d_row_bad, (size_t)U));
+        HIP_TRY(mem.alloc(&d_spread, 1));
+        HIP_TRY(mem.alloc(&d_bad, 2));
+        HIP_TRY(mem.alloc(&d_ticket, 1));
+        HIP_TRY(hipMemsetAsync(d_ticket, 0, sizeof(unsigned int), st));
+    }
+    if (want_parent) {
+        HIP_TRY(mem.alloc(&d_parent, (size_t)U));
+        HIP_TRY(mem.alloc(&d_delta, (size_t)U));
+    }
+    if (int rc = f.items(h, s.item_sample != nullptr && !mat)) return rc;
+
+    // the columns [c0, c0 + nc) of the host matrix [U][n_a] as a block [nc][U] on the device
+    std::vector<float> stage;
+    auto host_columns = [&](long long c0, int nc) -> int {
+        stage.resize((size_t)nc * U);
+        for (int c = 0; c < nc; ++c)
+            for (int u = 0; u < U; ++u) stage[(size_t)c * U + u] = s.values[(size_t)u * s.n_a + c0 + c];
+        HIP_TRY(hipMemcpyAsync(d_fx, stage.data(), stage.size() * sizeof(float), hipMemcpyHostToDevice, st));
+        return wait_stream(h);                                  // `stage` is written again for the next block
+    };
+    const int T = (U + MODES_TILE - 1) / MODES_TILE;
+    if (want_sq || want_out)
+        if (int rc = each_block(rows, rows_blk, [&](long long r0, int nr) -> int {
+            const int nc = nr * cpr;
+            if (mat) {
+                if (int rc = host_columns(r0, nc)) return rc;
+            } else {
+                if (int rc = fwd.run(h, f.d.base, f.d.run_off, f.d_x, f.xs, (int)r0, nr, U, d_fx)) return rc;
+            }
+            if (want_out) {
+                const long long cells = (long long)nc * U;
+                HIP_TRY(launch(modes_outputs_kernel, dim3((unsigned)((cells + MODES_THREADS - 1) / MODES_THREADS)), dim3(MODES_THREADS), 0, st,
+                               d_fx, n, r0 * cpr, nc, U, d_out));
+            }
+            if (want_sq) {
+                ModesDist da{d_fx, nc, U, T, r0 == 0 ? 1 : 0, d_sq};
+                HIP_TRY(launch(modes_dist_kernel, dim3((unsigned)(T * (T + 1) / 2)), dim3(MODES_THREADS), 0, st, da));
+            }
+            return 0;
+        })) return rc;
+    long long bad[2] = {0, -1};
+    if (want_sq) {
+        ModesDensity na{d_sq, d_cnt, U, s.near_sq, (double)M * (double)M, d_rho, d_max, d_part, d_row_bad, d_ticket, d_spread, d_bad};
+        HIP_TRY(launch(modes_density_kernel, dim3((unsigned)U), dim3(MODES_THREADS), 0, st, na));
+        if (want_parent) {
+            ModesParent pa{d_sq, d_cnt, d_rho, d_max, U, d_parent, d_delta};
+            HIP_TRY(launch(modes_parent_kernel, dim3((unsigned)U), dim3(MODES_THREADS), 0, st, pa));
+        }
+        HIP_TRY(hipMemcpyAsync(bad, d_bad, sizeof bad, hipMemcpyDeviceToHost, st));
+    }
+    HIP_TRY(fetch((long long*)s.rho, d_rho, (size_t)U, st));
+    HIP_TRY(fetch(s.delta_sq, d_delta, (size_t)U, st));
+    HIP_TRY(fetch((int*)s.parent, d_parent, (size_t)U, st));
+    HIP_TRY(fetch((int*)s.count, d_cnt, (size_t)U, st));
+    HIP_TRY(fetch(s.spread_sq, d_spread, 1, st));
+    HIP_TRY(fetch(s.sq_dist, d_sq, (size_t)U * U, st));
+    if (want_out) HIP_TRY(fetch(s.outputs, d_out, (size_t)U * n, st));
+    if (int rc = wait_stream(h)) return rc;
+    if (bad[0] != 0)
+        return fail(-1, "%lld squared distances are not finite: sample %lld is the first whose outputs are NaN or infinite", bad[0], bad[1]);
+    if (s.outputs && mat) std::copy(s.values, s.values + (size_t)U * n, s.outputs);
+    for (long long k = 0; s.item_sample && k < f.src.n_items; ++k) s.item_sample[k] = mat ? (int32_t)k : f.item_run[(size_t)k];
     return 0;
 }
 

@@ -59,6 +59,19 @@ __device__ void wg_min_max(double* a, double* b, double& mn, double& mx) {      
     mn = a[0]; mx = b[0];
     __syncthreads();
 }
+// the lexicographically smallest pair (key, idx) of the work-group, as one 128-bit unsigned compare; every thread gets it
+template <int N>
+__device__ void wg_min_pair(unsigned long long* a, unsigned long long* b, unsigned long long& key, unsigned long long& idx) {
+    const int tid = threadIdx.x;
+    __syncthreads();
+    a[tid] = key; b[tid] = idx;
+    __syncthreads();
+    wg_tree<N>([&](int i, int j) {
+        if (a[j] < a[i] || (a[j] == a[i] && b[j] < b[i])) { a[i] = a[j]; b[i] = b[j]; }
+    });
+    key = a[0]; idx = b[0];
+    __syncthreads();
+}
 
 // inclusive scan in thread order of a [N] (and b [N] beside it), stored and synchronised by the caller: log2 N steps
 template <int N, class T>
