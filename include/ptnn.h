@@ -628,6 +628,92 @@ typedef struct ptnn_evidence_spec {
 
 int ptnn_evidence(ptnn_handle *h, const ptnn_evidence_spec *spec);
 
+/* ---- every rung at once: the multistate Bennett acceptance ratio (MBAR, Shirts & Chodera 2008; nothing in the reference) ----
+ * The free energy of every rung and a weight for every draw of every rung, from one fixed point over all draws (DESIGN.md section
+ * 32 states every formula).  States k = 0 .. K-1: an optional prior state first (beta = 0, reduced log density l_0 = 0), then the
+ * n_rungs rungs in the order given, `betas` [n_rungs] strictly ascending; K <= PTNN_MBAR_MAX_STATES.  Rung k has l_k(n) = b_n +
+ * beta_k U_n, U and b as ptnn_evidence defines them (a classification's b = 0).
+ * Sources of the rungs, as ptnn_evidence: (1) the trace, each listed replica one rung; (2) host vectors w [n_rungs, n_per_rung,
+ * P]; (3) host U [n_rungs, n_per_rung] with optional b of the same shape (NULL = 0): no forward pass.  Sources 2 and 3 take
+ * multiplicities [n_rungs, n_per_rung] >= 0.  The prior state is present when n_prior > 0: host u_prior / b_prior [n_prior]
+ * (b_prior NULL = 0), else the n_prior Philox draws of ptnn_evidence (same stream, counter and seed).
+ * Items: the n_prior prior draws, then the rungs' rows in source order (trace: chain-major in the order of `replicas`, rows step0,
+ * step0 + thin, ...); item n has weight c_n = its multiplicity (1 for trace rows and prior draws), and state k counts N_k = its
+ * expanded draws (every rung needs 4).  effective != 0: every item of rung k is scaled by ESS_k / n_k and N_k = ESS_k, the split-ESS
+ * of the rung's expanded U draws as ptnn_evidence's u_ess (not finite or not positive: 1); the prior draws are independent.
+ * Fixed point: f_k = -log sum_n c_n exp(l_k(n) - D_n), D_n = log sum_j N_j exp(f_j + l_j(n)), f_0 pinned to 0 after every sweep,
+ * from f = 0; sweeps are queued in batches of 8 and the largest |f_k - previous f_k| of the last sweep is read once per batch: the
+ * call stops when it is <= tol or once max_iter sweeps have run (no error: the caller compares *residual with tol).  Every exp is
+ * relative to an exact maximum; every sum is double in a fixed order, so that the sources give identical bits for the same draws.
+ * Outputs, any may be NULL: f [K]; gram [K, K] = W^T diag(c) W with W_nk = exp(f_k + l_k(n) - D_n); n_eff [K] = N_k; n_iter (the
+ * sweeps run, a multiple of 8); residual; u_out, b_out [n_items] every item's U and b; log_weight [n_items] = log(c_n W_n) at
+ * target_beta in [betas[0], betas[n_rungs - 1]], whose free energy is formed like a rung's (-inf where c_n = 0); of w =
+ * exp(log_weight): weight_sum, kish_ess = (sum w)^2 / sum (w^2 / c) (the Kish ESS of the draws behind the items: item n stands
+ * for c_n draws of weight W_n each) and max_weight_share = max w / sum w; n_items = n_prior + the rungs' rows; n_distinct as
+ * ptnn_evidence.
+ * The map of the items, [n_items] each: item_chain (the local replica of a trace row, the rung's index in `betas` of a host row, -1
+ * for a prior draw), item_step (the trace row's step, the host row's index in its rung, the prior draw's number),
+ * item_multiplicity (c_n before the ESS scaling); sse = exp(-b), the sum of squared errors of the item's vector (a regression).
+ * Systematic resampling (n_resample = m > 0): cum_weight [n_items] the running sum of w in item order; resample_u = the 23-bit
+ * uniform of word 0 of philox4x32_10(0, 0, 0, 7, resample_seed); resample_item [m]: draw i takes the first item whose running sum
+ * exceeds ((u + i) / m) * cum_weight[n_items - 1]; resample_w [m, P] the weight vector of every draw, a prior draw's as the device
+ * formed it (sources 1, 2 and Philox prior draws only).
+ * Expectations (mean or var given; sources 1, 2 and Philox prior draws only): the network outputs of every item's vector on the
+ * rows x (ptnn_predict's rows and forward pass), per (row, output) column the mean sum_n w_n f_n / sum_n w_n and the population
+ * variance sum_n w_n (f_n - mean)^2 / sum_n w_n under w = exp(log_weight), in double, two passes; the items are added in chunks
+ * of 256 (the rungs' rows first, then the prior draws), the chunks in order.
+ * Runs on the handle's stream behind everything queued and returns when done; scratch of the forward pass stays under
+ * $PTNN_EVIDENCE_SCRATCH_BYTES, which changes no result.  Touches no chain state, tape, counter or trace row.  Not with a
+ * communicator attached (one GPU only). */
+#define PTNN_MBAR_MAX_STATES 512
+
+typedef struct ptnn_mbar_spec {
+    int32_t struct_bytes;         /* = sizeof(ptnn_mbar_spec): ABI guard */
+    /* source 1: the trace (used when w == NULL and u == NULL); each replica is a rung */
+    const int32_t *replicas;      /* local replica indices, or NULL = all */
+    int32_t n_replicas;           /* entries of replicas (ignored when NULL) */
+    int32_t step0, nsteps, thin;  /* trace rows step0, step0 + thin, ... < step0 + nsteps (thin >= 1) */
+    /* source 2: host vectors; source 3: host U (and b) */
+    const float *w;               /* [n_rungs, n_per_rung, P] or NULL */
+    const double *u;              /* [n_rungs, n_per_rung] or NULL */
+    const double *b;              /* source 3: [n_rungs, n_per_rung] or NULL = 0 */
+    const int32_t *multiplicity;  /* sources 2, 3: [n_rungs, n_per_rung] >= 0, or NULL = 1 each */
+    int32_t n_rungs;              /* all sources: entries of betas */
+    int32_t effective;            /* != 0: ESS-scaled weights and counts */
+    int64_t n_per_rung;           /* sources 2, 3 */
+    const double *betas;          /* [n_rungs] strictly ascending, finite, > 0 */
+    /* the prior state */
+    int64_t n_prior;              /* 0 = no prior state */
+    uint64_t seed;                /* of the Philox prior draws */
+    const double *u_prior;        /* [n_prior] host U of the prior draws, or NULL = Philox draws */
+    const double *b_prior;        /* [n_prior] with u_prior, or NULL = 0 */
+    /* fixed point, target, resampling */
+    double target_beta, tol;
+    int32_t max_iter;
+    int32_t reserved_;            /* set 0 */
+    int64_t n_resample;
+    uint64_t resample_seed;
+    /* rows of the expectations (used when mean or var is asked for) */
+    int32_t x_source;             /* PTNN_PREDICT_X_HOST, _TRAIN or _TEST */
+    int32_t n_rows;
+    const float *x;               /* [n_rows, n_in] (PTNN_PREDICT_X_HOST) */
+    /* outputs */
+    double *f, *gram, *n_eff;                                   /* [K], [K, K], [K] */
+    int64_t *n_iter;
+    double *residual;
+    double *u_out, *b_out, *log_weight, *cum_weight;            /* [n_items] */
+    double *weight_sum, *kish_ess, *max_weight_share, *resample_u;
+    int64_t *resample_item;                                     /* [n_resample] */
+    float *resample_w;                                          /* [n_resample, P] */
+    double *mean, *var;                                         /* [n_rows, n_out] */
+    int32_t *item_chain, *item_multiplicity;                    /* [n_items] */
+    int64_t *item_step;                                         /* [n_items] */
+    double *sse;                                                /* [n_items], regression */
+    int64_t *n_items, *n_distinct;
+} ptnn_mbar_spec;
+
+int ptnn_mbar(ptnn_handle *h, const ptnn_mbar_spec *spec);
+
 /* ---- calibration and proper scores of the predictive distribution (nothing in the reference: it reports RMSE / accuracy) ----
  * Regression (n_out == 1): the predictive distribution of y on data row n is the mixture (1/S) sum_s c_s N(f_s, tau_s^2) over
  * the expanded multiset of S samples (a sample with multiplicity c counts c times), tau_s^2 = exp(eta_s); per row, with the

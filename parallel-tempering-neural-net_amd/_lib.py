@@ -138,6 +138,31 @@ class EvidenceSpec(C.Structure):
 EVIDENCE_MAX_A = 4
 
 
+class MbarSpec(C.Structure):
+    """ptnn_mbar_spec (include/ptnn.h)."""
+    _fields_ = _SELECTION + [
+        ("w", C.POINTER(C.c_float)), ("u", C.POINTER(C.c_double)), ("b", C.POINTER(C.c_double)), ("multiplicity", C.POINTER(C.c_int32)),
+        ("n_rungs", C.c_int32), ("effective", C.c_int32), ("n_per_rung", C.c_int64), ("betas", C.POINTER(C.c_double)),
+        ("n_prior", C.c_int64), ("seed", C.c_uint64), ("u_prior", C.POINTER(C.c_double)), ("b_prior", C.POINTER(C.c_double)),
+        ("target_beta", C.c_double), ("tol", C.c_double), ("max_iter", C.c_int32), ("reserved_", C.c_int32),
+        ("n_resample", C.c_int64), ("resample_seed", C.c_uint64),
+        ("x_source", C.c_int32), ("n_rows", C.c_int32), ("x", C.POINTER(C.c_float)),
+        ("f", C.POINTER(C.c_double)), ("gram", C.POINTER(C.c_double)), ("n_eff", C.POINTER(C.c_double)),
+        ("n_iter", C.POINTER(C.c_int64)), ("residual", C.POINTER(C.c_double)),
+        ("u_out", C.POINTER(C.c_double)), ("b_out", C.POINTER(C.c_double)), ("log_weight", C.POINTER(C.c_double)),
+        ("cum_weight", C.POINTER(C.c_double)),
+        ("weight_sum", C.POINTER(C.c_double)), ("kish_ess", C.POINTER(C.c_double)), ("max_weight_share", C.POINTER(C.c_double)),
+        ("resample_u", C.POINTER(C.c_double)), ("resample_item", C.POINTER(C.c_int64)), ("resample_w", C.POINTER(C.c_float)),
+        ("mean", C.POINTER(C.c_double)), ("var", C.POINTER(C.c_double)),
+        ("item_chain", C.POINTER(C.c_int32)), ("item_multiplicity", C.POINTER(C.c_int32)), ("item_step", C.POINTER(C.c_int64)),
+        ("sse", C.POINTER(C.c_double)),
+        ("n_items", C.POINTER(C.c_int64)), ("n_distinct", C.POINTER(C.c_int64)),
+    ]
+
+
+MBAR_MAX_STATES = 512
+
+
 class CalibrationSpec(C.Structure):
     """ptnn_calibration_spec (include/ptnn.h)."""
     _fields_ = _SELECTION + [
@@ -435,6 +460,7 @@ SYMBOLS = {
     "ptnn_lfo": (C.c_int, [C.c_void_p, C.POINTER(LfoSpec)]),
     "ptnn_forecast": (C.c_int, [C.c_void_p, C.POINTER(ForecastSpec)]),
     "ptnn_evidence": (C.c_int, [C.c_void_p, C.POINTER(EvidenceSpec)]),
+    "ptnn_mbar": (C.c_int, [C.c_void_p, C.POINTER(MbarSpec)]),
     "ptnn_calibration": (C.c_int, [C.c_void_p, C.POINTER(CalibrationSpec)]),
     "ptnn_forecast_score": (C.c_int, [C.c_void_p, C.POINTER(ForecastScoreSpec)]),
     "ptnn_sensitivity": (C.c_int, [C.c_void_p, C.POINTER(SensitivitySpec)]),
@@ -1531,6 +1557,93 @@ class Sampler:
         if d is None:
             spec.log_stone = spec.stone_relvar = None                   # no stones without exponents: they stay NaN
         return self._call(self.lib.ptnn_evidence, spec, out, counters=("n_distinct",))
+
+    def mbar(self, betas, *, replicas=None, step0=0, nsteps=None, thin=1, w=None, u=None, b=None, multiplicity=None, n_prior=0, seed=0,
+             u_prior=None, b_prior=None, effective=True, target_beta=1.0, tol=1e-10, max_iter=10000, n_resample=0, resample_seed=0,
+             gram=True, draws=False, x=None, resample_w=False, item_map=False, sse=False):
+        """ptnn_mbar: the multistate Bennett acceptance ratio over the rungs `betas` [K] (strictly ascending) and an optional prior
+        state, on the device.  Source of the rungs: the trace rows step0, step0 + thin, ... < step0 + nsteps of `replicas` (None =
+        all; one rung each, in the order of betas), host vectors w [K, n, P], or a host U [K, n] float64 with optional b [K, n];
+        sources 2 and 3 take optional integer `multiplicity` [K, n].  The prior state: n_prior draws of the prior (Philox stream
+        STREAM_PRIOR of `seed`), or host u_prior (and b_prior) [n_prior].  The items are the prior draws, then the rungs' rows.
+        -> dict(f, n_eff [K'] float64 and gram [K', K'] (K' = K plus the prior state), n_iter, residual, log_weight [n_items]
+        float64 at target_beta, weight_sum, kish_ess, max_weight_share, u and b [n_items] (draws), cum_weight [n_items], resample_u
+        and resample_item [n_resample] int64 (n_resample > 0), resample_w [n_resample, P] float32 the drawn weight vectors
+        (resample_w), mean and var [n_rows, O] float64 of the network outputs on the rows x ("train", "test" or [n_rows, n_in])
+        under the weights (x given; like resample_w not with u or u_prior), item_chain, item_multiplicity int32 and item_step
+        int64 [n_items] (item_map: chain or rung, step or row, -1 and the draw's number for a prior draw), sse [n_items] float64
+        (sse; a regression), n_items, n_distinct); what was not asked for is None."""
+        spec, keep = _spec(MbarSpec), []
+        if x is not None:
+            self._rows(spec, keep, x, "x", (self.cfg.n_in, "n_in columns"))
+        dp = C.POINTER(C.c_double)
+        ba = np.ascontiguousarray(betas, dtype=np.float64).reshape(-1)
+        keep.append(ba)
+        spec.betas, spec.n_rungs = ba.ctypes.data_as(dp), ba.size
+        if b is not None and u is None:
+            raise ValueError("b comes with a host U")
+        if u is not None:
+            ua = np.ascontiguousarray(u, dtype=np.float64)
+            if ua.ndim != 2 or ua.shape[0] != ba.size:
+                raise ValueError(f"u must be [n_rungs = {ba.size}, n_per_rung], got shape {ua.shape}")
+            keep.append(ua)
+            spec.u, spec.n_per_rung = ua.ctypes.data_as(dp), ua.shape[1]
+            if b is not None:
+                bb = np.ascontiguousarray(b, dtype=np.float64)
+                if bb.shape != ua.shape:
+                    raise ValueError(f"b must have the shape of u {ua.shape}, got {bb.shape}")
+                keep.append(bb)
+                spec.b = bb.ctypes.data_as(dp)
+            host = ua.shape
+        elif w is not None:
+            wa = _f32(w)
+            if wa.ndim != 3 or wa.shape[0] != ba.size or wa.shape[2] != self.P:
+                raise ValueError(f"w must be [n_rungs = {ba.size}, n_per_rung, {self.P}], got shape {wa.shape}")
+            keep.append(wa)
+            spec.w, spec.n_per_rung = _ptr(wa), wa.shape[1]
+            host = wa.shape[:2]
+        else:
+            host = None
+            K, per = self._trace_source(spec, keep, replicas, step0, nsteps, thin)
+            if K != ba.size:
+                raise ValueError(f"{K} chains selected for {ba.size} betas")
+            rows = K * per
+        if host is not None:
+            rows = int(np.prod(host))
+            self._multiplicity(spec, keep, multiplicity, tuple(host), "multiplicity must be [n_rungs, n_per_rung] = {want}, got shape {got}")
+        n_prior = int(n_prior)
+        if u_prior is not None:
+            up = np.ascontiguousarray(u_prior, dtype=np.float64).reshape(-1)
+            keep.append(up)
+            spec.u_prior, n_prior = up.ctypes.data_as(dp), up.size
+            if b_prior is not None:
+                bp = np.ascontiguousarray(b_prior, dtype=np.float64).reshape(-1)
+                if bp.size != up.size:
+                    raise ValueError(f"b_prior must have one entry per prior draw ({up.size}), got {bp.size}")
+                keep.append(bp)
+                spec.b_prior = bp.ctypes.data_as(dp)
+        elif b_prior is not None:
+            raise ValueError("b_prior comes with u_prior")
+        spec.n_prior, spec.seed, spec.effective = n_prior, int(seed) & 0xFFFFFFFFFFFFFFFF, 1 if effective else 0
+        spec.target_beta, spec.tol, spec.max_iter = float(target_beta), float(tol), int(max_iter)
+        m = int(n_resample)
+        spec.n_resample, spec.resample_seed = m, int(resample_seed) & 0xFFFFFFFFFFFFFFFF
+        K1, nt = ba.size + (1 if n_prior > 0 else 0), max(n_prior, 0) + max(rows, 0)
+        out = dict(f=np.full(K1, np.nan), gram=np.full((K1, K1), np.nan) if gram else None, n_eff=np.full(K1, np.nan),
+                   log_weight=np.empty(nt), u=np.empty(nt) if draws else None, b=np.empty(nt) if draws else None,
+                   cum_weight=np.empty(nt) if m > 0 else None, resample_item=np.empty(m, np.int64) if m > 0 else None,
+                   resample_w=np.empty((m, self.P), np.float32) if resample_w else None,
+                   mean=np.empty((spec.n_rows, self.cfg.n_out)) if x is not None else None,
+                   var=np.empty((spec.n_rows, self.cfg.n_out)) if x is not None else None,
+                   item_chain=np.empty(nt, np.int32) if item_map else None, item_multiplicity=np.empty(nt, np.int32) if item_map else None,
+                   item_step=np.empty(nt, np.int64) if item_map else None, sse=np.empty(nt) if sse else None)
+        _bind(spec, out, u="u_out", b="b_out")
+        scal = {k: C.c_double(float("nan")) for k in ("residual", "weight_sum", "kish_ess", "max_weight_share", "resample_u")}
+        for k, v in scal.items():
+            setattr(spec, k, C.pointer(v))
+        self._call(self.lib.ptnn_mbar, spec, out, counters=("n_iter", "n_items", "n_distinct"))
+        out.update((k, v.value) for k, v in scal.items())
+        return out
 
     def langevin_gradient(self, w):
         w = _f32(np.atleast_2d(w))

@@ -1097,29 +1097,12 @@ class PosteriorAnalysis:
         return Forecast(mean=out["mean"], percentiles=self._bands(out["order_stats"], pcts, spots, ranks), samples=out["samples"], n_samples=out["n_samples"],
                         n_trajectories=out["n_trajectories"])
 
-    # ------------------------------------------------------------------ log evidence (not in the reference)
-    def log_evidence(self, *, burn_in=None, thin=1, prior_draws=1 << 20, seed=None, weights=None, return_draws=False):
-        """The marginal likelihood log Z of the model, for Bayes factors between topologies (evidence_compare), computed on the GPU
-        from every rung of the ladder (DESIGN.md section 15).  Rung k samples the power posterior pi(w) L(w)^beta_k, beta_k =
-        1 / float32(T_k); with U(w) the untempered full-data log-likelihood (a regression's tau^2 integrated out), log Z is
-        estimated by thermodynamic integration over the rungs (trapezoid rule, the prior as beta = 0; ti_discretisation the
-        ptemcee estimate |TI - TI over every other rung|) and by stepping stones (Xie et al. 2011).  A regression's evidence is
-        relative to the improper 1 / tau^2 prior: it cancels in Bayes factors between models fitted to the same training rows.
-
-        The draws of rung k are its trace rows from int(NumSamples * burn_in) up to the temperature switch (the reference's
-        pt_samples = 0.6 NumSamples, after which every chain runs at T = 1) or to NumSamples; `thin`: every thin-th row.  The
-        prior's point and first stone come from `prior_draws` draws of N(0, sigma^2 I) (Philox stream STREAM_PRIOR of `seed`,
-        None = the object's seed).  `weights`: (betas [K], vectors [K, n, num_param]) instead of the trace.  Standard errors
-        take each rung's split-ESS of U; they assume independent rungs.  return_draws: also every draw's U.  -> Evidence.
-
-        The estimate is exact only when the tempered chains sample the power posterior: random-walk proposals, swap_rule=1,
-        shared_noise=False and a large integer maxtemp (so that the hottest rung is close to the prior); a warning names the
-        settings that break this."""
-        self._need_sampler("log_evidence")
+    def _rung_source(self, name, burn_in, thin, weights):
+        """The rungs of log_evidence and rung_reweighting: every chain's trace rows from int(NumSamples * burn_in) up to the
+        temperature switch, every thin-th, or `weights` = (betas [K], vectors [K, n, num_param]); the refusals, and the warning
+        (under `name`) about settings under which the chains do not sample the power posterior.  -> (betas ascending, Sampler
+        source keywords, the rungs' order: the chain or the row of `weights` of every beta)."""
         S = self.NumSamples
-        n_prior = int(prior_draws)
-        if n_prior < 2:
-            raise ValueError(f"prior_draws = {n_prior}: the prior's point needs at least 2 draws")
         if weights is not None:
             if not isinstance(weights, tuple) or len(weights) != 2:
                 raise ValueError("weights must be a pair (betas [K], vectors [K, n, num_param])")
@@ -1162,9 +1145,34 @@ class PosteriorAnalysis:
         if self.shared_noise:
             causes.append("shared_noise=True (the rungs are correlated, so the standard errors are not valid)")
         if causes:
-            warnings.warn("log_evidence: the tempered chains do not sample the power posterior exactly: " + "; ".join(causes)
+            warnings.warn(f"{name}: the tempered chains do not sample the power posterior exactly: " + "; ".join(causes)
                           + ". An exact estimate needs random-walk proposals, swap_rule=1, shared_noise=False and a large "
-                          "integer maxtemp", stacklevel=2)
+                          "integer maxtemp", stacklevel=3)
+        return bs, kw, order
+
+    # ------------------------------------------------------------------ log evidence (not in the reference)
+    def log_evidence(self, *, burn_in=None, thin=1, prior_draws=1 << 20, seed=None, weights=None, return_draws=False):
+        """The marginal likelihood log Z of the model, for Bayes factors between topologies (evidence_compare), computed on the GPU
+        from every rung of the ladder (DESIGN.md section 15).  Rung k samples the power posterior pi(w) L(w)^beta_k, beta_k =
+        1 / float32(T_k); with U(w) the untempered full-data log-likelihood (a regression's tau^2 integrated out), log Z is
+        estimated by thermodynamic integration over the rungs (trapezoid rule, the prior as beta = 0; ti_discretisation the
+        ptemcee estimate |TI - TI over every other rung|) and by stepping stones (Xie et al. 2011).  A regression's evidence is
+        relative to the improper 1 / tau^2 prior: it cancels in Bayes factors between models fitted to the same training rows.
+
+        The draws of rung k are its trace rows from int(NumSamples * burn_in) up to the temperature switch (the reference's
+        pt_samples = 0.6 NumSamples, after which every chain runs at T = 1) or to NumSamples; `thin`: every thin-th row.  The
+        prior's point and first stone come from `prior_draws` draws of N(0, sigma^2 I) (Philox stream STREAM_PRIOR of `seed`,
+        None = the object's seed).  `weights`: (betas [K], vectors [K, n, num_param]) instead of the trace.  Standard errors
+        take each rung's split-ESS of U; they assume independent rungs.  return_draws: also every draw's U.  -> Evidence.
+
+        The estimate is exact only when the tempered chains sample the power posterior: random-walk proposals, swap_rule=1,
+        shared_noise=False and a large integer maxtemp (so that the hottest rung is close to the prior); a warning names the
+        settings that break this."""
+        self._need_sampler("log_evidence")
+        n_prior = int(prior_draws)
+        if n_prior < 2:
+            raise ValueError(f"prior_draws = {n_prior}: the prior's point needs at least 2 draws")
+        bs, kw, _ = self._rung_source("log_evidence", burn_in, thin, weights)
         d = np.append(np.diff(bs), 0.0)
         out = self._sampler.evidence(d=d, n_prior=n_prior, seed=self.seed if seed is None else int(seed), a=[0.0, float(bs[0])],
                                      u_out=bool(return_draws), u_prior_out=bool(return_draws), **kw)

@@ -1,4 +1,4 @@
-// ptnn_analysis.hip -- the posterior analysis calls of libptnn.so: predict, convergence, rank_convergence, elpd, lfo, forecast, evidence, calibration,
+// ptnn_analysis.hip -- the posterior analysis calls of libptnn.so: predict, convergence, rank_convergence, elpd, lfo, forecast, evidence, mbar, calibration,
 // forecast_score, sensitivity, partial_dependence, coalition_values, ppc, powerscale, prior_predictive, influence, modes, and the sample-selection path they share.  The shape-independent analysis kernels are defined in this object: it includes them.
 #include "ptnn_shapes.hpp"                   // PTNN_SHAPES
 #include "ptnn_analysis_device.hpp"          // the per-shape forward kernels and their table, AnalysisShape
@@ -9,6 +9,7 @@ namespace ptnn {
 #include "ptnn_dev_elpd.hpp"                 // predictive accuracy: lppd, WAIC, PSIS-LOO per data row
 #include "ptnn_dev_lfo.hpp"                  // leave-future-out cross-validation: running sums of ll, PSIS per origin
 #include "ptnn_dev_evidence.hpp"             // log evidence: per-rung statistics of the full-data log-likelihood, prior draws
+#include "ptnn_dev_mbar.hpp"                 // MBAR over every rung: the free-energy fixed point, the Gram matrix of the weights, resampling
 #include "ptnn_dev_calibration.hpp"          // calibration: PIT, quantiles and CRPS of the predictive mixture per data row
 #include "ptnn_dev_fscore.hpp"               // forecast verification: log score per column, energy score of the path per origin
 #include "ptnn_dev_ppc.hpp"                  // posterior predictive checks: replicated data and test quantities per occurrence
@@ -1684,6 +1685,108 @@ int ptnn_forecast(ptnn_handle* h, const ptnn_forecast_spec* spec) {
 // ---- log evidence (ptnn_dev_evidence.hpp) ----
 static_assert(PTNN_EVIDENCE_MAX_A == EVID_MAX_A, "ptnn.h prior exponents");
 
+// Stages b and c of the evidence path (ptnn_dev_evidence.hpp), shared by ptnn_evidence and ptnn_mbar: U (and b) of weight vectors
+// on the training rows through the per-shape forward pass, and stage e's prior draws through the same two stages.
+struct EvidEval {
+    ptnn_handle* h = nullptr;
+    ForwardPlan fwd;
+    const float* d_x = nullptr;                        // training rows
+    int xs = 0, I = 0, O = 0, P = 0, N = 0;
+    bool reg = false;
+    int* d_sse0 = nullptr;                             // weight vectors with SSE = 0 (evid_finish_kernel)
+    int init(ptnn_handle* h_, DeviceScratch& mem, const char* what) {
+        h = h_;
+        I = h->cfg.n_in; O = h->cfg.n_out; P = h->P; N = h->Ntr;
+        reg = h->cfg.task == PTNN_TASK_REG;
+        if (int rc = fwd.init(h, what)) return rc;
+        d_x = h->d_data;
+        xs = h->IPY;
+        HIP_TRY(mem.alloc(&d_sse0, 1));
+        HIP_TRY(hipMemsetAsync(d_sse0, 0, sizeof(int), h->stream));
+        return 0;
+    }
+    // U (and b) of `nv` vectors at base + run_off[u]: rows in blocks of rows_blk, fx scratch `fx` of rows_blk x O x nv floats
+    int eval(const float* base, const long long* run_off, int nv, long long rows_blk, float* fx, double* acc, double* u_out, double* b_out) {
+        hipStream_t st = h->stream;
+        HIP_TRY(hipMemsetAsync(acc, 0, (size_t)nv * sizeof(double), st));
+        const unsigned ub = (unsigned)((nv + EVID_THREADS - 1) / EVID_THREADS);
+        if (int rc = each_block(N, rows_blk, [&](long long r0, int nr) -> int {
+            if (int rc = fwd.run(h, base, run_off, d_x, xs, (int)r0, nr, nv, fx)) return rc;
+            EvidRows ra{fx, d_x + (size_t)r0 * xs + I, xs, nr, O, nv, reg ? 1 : 0, acc};
+            HIP_TRY(launch(evid_rows_kernel, dim3(ub), dim3(EVID_THREADS), 0, st, ra));
+            return 0;
+        })) return rc;
+        HIP_TRY(launch(evid_finish_kernel, dim3(ub), dim3(EVID_THREADS), 0, st, nv, reg ? 1 : 0, N, acc, u_out, b_out, d_sse0));
+        return 0;
+    }
+    long long rows_for(long long nv, size_t avail) const { return row_block(avail, (size_t)nv * O * sizeof(float), N); }
+    int sse_check() {
+        int e = 0;
+        HIP_TRY(hipMemcpyAsync(&e, d_sse0, sizeof e, hipMemcpyDeviceToHost, h->stream));
+        if (int rc = wait_stream(h)) return rc;
+        if (e) return fail(-1, "%d weight vectors fit the %d training rows exactly (SSE = 0): U = -(N / 2) log SSE is infinite", e, N);
+        return 0;
+    }
+    // stage e: U and b of prior draws [0, NP) of `seed` into d_pu, d_pb [NP], in blocks of nb vectors (vector + forward scratch of
+    // every training row under the budget)
+    int prior_draws(DeviceScratch& mem, size_t budget, long long NP, uint64_t seed, double* d_pu, double* d_pb) {
+        hipStream_t st = h->stream;
+        const size_t per_draw = (size_t)P * sizeof(float) + 4 * sizeof(double) + (size_t)std::min<long long>(N, 65535LL * WAVE) * O * sizeof(float);
+        const long long nb = std::max(1LL, std::min<long long>((long long)(budget / per_draw), NP));
+        const size_t fixed = (size_t)nb * ((size_t)P * sizeof(float) + 4 * sizeof(double));
+        const long long rows_blk = rows_for(nb, budget > fixed ? budget - fixed : 0);
+        double* d_acc = nullptr;
+        float *d_pw = nullptr, *d_fx = nullptr;
+        long long* d_poff = nullptr;
+        HIP_TRY(mem.alloc(&d_pw, (size_t)nb * P));
+        HIP_TRY(mem.alloc(&d_poff, (size_t)nb));
+        HIP_TRY(mem.alloc(&d_acc, (size_t)nb));
+        HIP_TRY(mem.alloc(&d_fx, (size_t)rows_blk * O * nb));
+        const float sigma = (float)std::sqrt((double)h->cfg.sigma_squared);
+        uint32_t slo = 0, shi = 0;
+        split_seed(seed, &slo, &shi);
+        const int nq = (P + 3) / 4;
+        for (long long d0 = 0; d0 < NP; d0 += nb) {
+            const int b = (int)std::min<long long>(nb, NP - d0);
+            HIP_TRY(launch(evid_prior_kernel, dim3((unsigned)(((long long)b * nq + EVID_THREADS - 1) / EVID_THREADS)), dim3(EVID_THREADS), 0, st,
+                           d0, b, P, sigma, slo, shi, d_pw, d_poff));
+            if (int rc = eval(d_pw, d_poff, b, rows_blk, d_fx, d_acc, d_pu + d0, d_pb + d0)) return rc;
+        }
+        return 0;
+    }
+};
+
+// the split ESS of every rung's U draws (one chain each; rung k's at d_udraw + off[k]), by the convergence kernels: rungs of equal
+// length in one pass
+static int evid_rung_ess(ptnn_handle* h, const std::vector<long long>& off, const long long* d_off, const double* d_udraw, double* u_ess) {
+    hipStream_t st = h->stream;
+    const int K = (int)off.size() - 1;
+    std::vector<char> done((size_t)K, 0);
+    for (int k0 = 0; k0 < K; ++k0) {
+        if (done[(size_t)k0]) continue;
+        const long long nk = off[(size_t)k0 + 1] - off[(size_t)k0];
+        std::vector<int> rung, qcol;
+        for (int k = k0; k < K; ++k)
+            if (!done[(size_t)k] && off[(size_t)k + 1] - off[(size_t)k] == nk) { rung.push_back(k); done[(size_t)k] = 1; }
+        const int Q = (int)rung.size();
+        for (int q = 0; q < Q; ++q) qcol.push_back(q);
+        DeviceScratch cm;
+        int* d_rung = nullptr;
+        float* d_draws = nullptr;
+        HIP_TRY(cm.alloc(&d_rung, (size_t)Q));
+        HIP_TRY(hipMemcpyAsync(d_rung, rung.data(), (size_t)Q * sizeof(int), hipMemcpyHostToDevice, st));
+        HIP_TRY(cm.alloc(&d_draws, (size_t)Q * nk));
+        HIP_TRY(launch(evid_conv_kernel, dim3((unsigned)(((long long)Q * nk + EVID_THREADS - 1) / EVID_THREADS)), dim3(EVID_THREADS), 0, st,
+                       Q, (int)nk, d_off, d_rung, d_udraw, d_draws));
+        ConvGather ga{};
+        ga.host = 1; ga.draws = d_draws; ga.Qh = Q;
+        std::vector<double> ess((size_t)Q);
+        if (int rc = conv_drive(h, cm, ga, qcol, 1, (int)nk, 0, nullptr, nullptr, nullptr, ess.data(), nullptr, nullptr, nullptr)) return rc;
+        for (int q = 0; q < Q; ++q) u_ess[rung[(size_t)q]] = ess[(size_t)q];
+    }
+    return 0;
+}
+
 int ptnn_evidence(ptnn_handle* h, const ptnn_evidence_spec* spec) {
     // argument checks first: none of them needs the handle or a device
     if (int rc = check_spec(spec, "ptnn_evidence_spec")) return rc;
@@ -1731,8 +1834,7 @@ int ptnn_evidence(ptnn_handle* h, const ptnn_evidence_spec* spec) {
         }
     }
     if (int rc = check_handle(h, "ptnn_evidence")) return rc;
-    const int I = h->cfg.n_in, O = h->cfg.n_out, P = h->P, N = h->Ntr;
-    const bool reg = h->cfg.task == PTNN_TASK_REG;
+    const int O = h->cfg.n_out;
     // the trace selection: one rung per chain
     if (!u_src && !host_src) {
         if (int rc = count_samples(h, src)) return rc;
@@ -1756,36 +1858,8 @@ int ptnn_evidence(ptnn_handle* h, const ptnn_evidence_spec* spec) {
     hipStream_t st = h->stream;
     DeviceScratch mem;
     const size_t budget = scratch_budget("PTNN_EVIDENCE_SCRATCH_BYTES");
-    // the forward pass of predict_fwd on the training rows
-    ForwardPlan fwd;
-    if (int rc = fwd.init(h, "log evidence")) return rc;
-    const float* d_x = h->d_data;                      // training rows
-    const int xs = h->IPY;
-    int* d_sse0 = nullptr;                             // weight vectors with SSE = 0 (evid_finish_kernel)
-    HIP_TRY(mem.alloc(&d_sse0, 1));
-    HIP_TRY(hipMemsetAsync(d_sse0, 0, sizeof(int), st));
-    // U (and b) of `nv` vectors at base + run_off[u]: rows in blocks of rows_blk, fx scratch `fx` of rows_blk x O x nv floats
-    auto eval_u = [&](const float* base, const long long* run_off, int nv, long long rows_blk, float* fx, double* acc, double* u_out,
-                      double* b_out) -> int {
-        HIP_TRY(hipMemsetAsync(acc, 0, (size_t)nv * sizeof(double), st));
-        const unsigned ub = (unsigned)((nv + EVID_THREADS - 1) / EVID_THREADS);
-        if (int rc = each_block(N, rows_blk, [&](long long r0, int nr) -> int {
-            if (int rc = fwd.run(h, base, run_off, d_x, xs, (int)r0, nr, nv, fx)) return rc;
-            EvidRows ra{fx, d_x + (size_t)r0 * xs + I, xs, nr, O, nv, reg ? 1 : 0, acc};
-            HIP_TRY(launch(evid_rows_kernel, dim3(ub), dim3(EVID_THREADS), 0, st, ra));
-            return 0;
-        })) return rc;
-        HIP_TRY(launch(evid_finish_kernel, dim3(ub), dim3(EVID_THREADS), 0, st, nv, reg ? 1 : 0, N, acc, u_out, b_out, d_sse0));
-        return 0;
-    };
-    auto rows_for = [&](long long nv, size_t avail) { return row_block(avail, (size_t)nv * O * sizeof(float), N); };
-    auto sse_check = [&]() -> int {
-        int e = 0;
-        HIP_TRY(hipMemcpyAsync(&e, d_sse0, sizeof e, hipMemcpyDeviceToHost, st));
-        if (int rc = wait_stream(h)) return rc;
-        if (e) return fail(-1, "%d weight vectors fit the %d training rows exactly (SSE = 0): U = -(N / 2) log SSE is infinite", e, N);
-        return 0;
-    };
+    EvidEval ev;
+    if (int rc = ev.init(h, mem, "log evidence")) return rc;
 
     // ---- the rungs: U of every draw
     double* d_udraw = nullptr;
@@ -1804,15 +1878,15 @@ int ptnn_evidence(ptnn_handle* h, const ptnn_evidence_spec* spec) {
         const int U = d.U;
         if (s.n_distinct) *s.n_distinct = U;
         // stages b, c: U of every distinct vector, rows in blocks under the budget
-        const long long rows_blk = rows_for(U, budget);
+        const long long rows_blk = ev.rows_for(U, budget);
         float* d_fx = nullptr;
         double *d_acc = nullptr, *d_udist = nullptr;
         HIP_TRY(mem.alloc(&d_fx, (size_t)rows_blk * O * U));
         HIP_TRY(mem.alloc(&d_acc, (size_t)U));
         HIP_TRY(mem.alloc(&d_udist, (size_t)U));
-        if (int rc = eval_u(d.base, d.run_off, U, rows_blk, d_fx, d_acc, d_udist, nullptr)) return rc;
+        if (int rc = ev.eval(d.base, d.run_off, U, rows_blk, d_fx, d_acc, d_udist, nullptr)) return rc;
         HIP_TRY(launch(evid_expand_kernel, dim3(draw_blocks), dim3(EVID_THREADS), 0, st, n_draws, d_item_of, d.item_run, d_udist, d_udraw));
-        if (int rc = sse_check()) return rc;
+        if (int rc = ev.sse_check()) return rc;
     }
     // stage d: per-rung moments and stones
     long long* d_off = nullptr;
@@ -1834,58 +1908,16 @@ int ptnn_evidence(ptnn_handle* h, const ptnn_evidence_spec* spec) {
     HIP_TRY(fetch(s.u_out, d_udraw, (size_t)n_draws, st));
     if (int rc = wait_stream(h)) return rc;
     // the split ESS of every rung's U draws (one chain each), by the convergence kernels: rungs of equal length in one pass
-    if (s.u_ess) {
-        std::vector<char> done((size_t)K, 0);
-        for (int k0 = 0; k0 < K; ++k0) {
-            if (done[(size_t)k0]) continue;
-            const long long nk = off[(size_t)k0 + 1] - off[(size_t)k0];
-            std::vector<int> rung, qcol;
-            for (int k = k0; k < K; ++k)
-                if (!done[(size_t)k] && off[(size_t)k + 1] - off[(size_t)k] == nk) { rung.push_back(k); done[(size_t)k] = 1; }
-            const int Q = (int)rung.size();
-            for (int q = 0; q < Q; ++q) qcol.push_back(q);
-            DeviceScratch cm;
-            int* d_rung = nullptr;
-            float* d_draws = nullptr;
-            HIP_TRY(cm.alloc(&d_rung, (size_t)Q));
-            HIP_TRY(hipMemcpyAsync(d_rung, rung.data(), (size_t)Q * sizeof(int), hipMemcpyHostToDevice, st));
-            HIP_TRY(cm.alloc(&d_draws, (size_t)Q * nk));
-            HIP_TRY(launch(evid_conv_kernel, dim3((unsigned)(((long long)Q * nk + EVID_THREADS - 1) / EVID_THREADS)), dim3(EVID_THREADS), 0, st,
-                           Q, (int)nk, d_off, d_rung, d_udraw, d_draws));
-            ConvGather ga{};
-            ga.host = 1; ga.draws = d_draws; ga.Qh = Q;
-            std::vector<double> ess((size_t)Q);
-            if (int rc = conv_drive(h, cm, ga, qcol, 1, (int)nk, 0, nullptr, nullptr, nullptr, ess.data(), nullptr, nullptr, nullptr)) return rc;
-            for (int q = 0; q < Q; ++q) s.u_ess[rung[(size_t)q]] = ess[(size_t)q];
-        }
-    }
+    if (s.u_ess)
+        if (int rc = evid_rung_ess(h, off, d_off, d_udraw, s.u_ess)) return rc;
     if (s.n_prior == 0) return 0;
 
     // ---- stage e: prior draws in blocks of nb vectors (vector + forward scratch of every training row under the budget)
     const long long NP = s.n_prior;
-    const size_t per_draw = (size_t)P * sizeof(float) + 4 * sizeof(double) + (size_t)std::min<long long>(N, 65535LL * WAVE) * O * sizeof(float);
-    const long long nb = std::max(1LL, std::min<long long>((long long)(budget / per_draw), NP));
-    const size_t fixed = (size_t)nb * ((size_t)P * sizeof(float) + 4 * sizeof(double));
-    const long long rows_blk = rows_for(nb, budget > fixed ? budget - fixed : 0);
-    double *d_pu = nullptr, *d_pb = nullptr, *d_acc = nullptr, *d_a = nullptr;
-    float *d_pw = nullptr, *d_fx = nullptr;
-    long long* d_poff = nullptr;
+    double *d_pu = nullptr, *d_pb = nullptr, *d_a = nullptr;
     HIP_TRY(mem.alloc(&d_pu, (size_t)NP));
     HIP_TRY(mem.alloc(&d_pb, (size_t)NP));
-    HIP_TRY(mem.alloc(&d_pw, (size_t)nb * P));
-    HIP_TRY(mem.alloc(&d_poff, (size_t)nb));
-    HIP_TRY(mem.alloc(&d_acc, (size_t)nb));
-    HIP_TRY(mem.alloc(&d_fx, (size_t)rows_blk * O * nb));
-    const float sigma = (float)std::sqrt((double)h->cfg.sigma_squared);
-    uint32_t slo = 0, shi = 0;
-    split_seed(s.seed, &slo, &shi);
-    const int nq = (P + 3) / 4;
-    for (long long d0 = 0; d0 < NP; d0 += nb) {
-        const int b = (int)std::min<long long>(nb, NP - d0);
-        HIP_TRY(launch(evid_prior_kernel, dim3((unsigned)(((long long)b * nq + EVID_THREADS - 1) / EVID_THREADS)), dim3(EVID_THREADS), 0, st,
-                       d0, b, P, sigma, slo, shi, d_pw, d_poff));
-        if (int rc = eval_u(d_pw, d_poff, b, rows_blk, d_fx, d_acc, d_pu + d0, d_pb + d0)) return rc;
-    }
+    if (int rc = ev.prior_draws(mem, budget, NP, s.seed, d_pu, d_pb)) return rc;
     HIP_TRY(mem.alloc(&d_a, (size_t)s.n_a));
     HIP_TRY(hipMemcpyAsync(d_a, s.a, (size_t)s.n_a * sizeof(double), hipMemcpyHostToDevice, st));
     double* d_pr = nullptr;
@@ -1895,10 +1927,343 @@ int ptnn_evidence(ptnn_handle* h, const ptnn_evidence_spec* spec) {
     std::vector<double> prh((size_t)4 * s.n_a);
     HIP_TRY(hipMemcpyAsync(prh.data(), d_pr, prh.size() * sizeof(double), hipMemcpyDeviceToHost, st));
     HIP_TRY(fetch(s.u_prior_out, d_pu, (size_t)NP, st));
-    if (int rc = sse_check()) return rc;
+    if (int rc = ev.sse_check()) return rc;
     double* outs[4] = {s.prior_log_mean_exp, s.prior_kish_ess, s.prior_u_mean, s.prior_u_var};
     for (int o = 0; o < 4; ++o)
         if (outs[o]) std::copy(prh.begin() + (size_t)o * s.n_a, prh.begin() + (size_t)(o + 1) * s.n_a, outs[o]);
+    return 0;
+}
+
+// ---- MBAR over every rung (ptnn_dev_mbar.hpp) ----
+static_assert(PTNN_MBAR_MAX_STATES == MBAR_MAX_K, "ptnn.h MBAR states");
+
+int ptnn_mbar(ptnn_handle* h, const ptnn_mbar_spec* spec) {
+    // argument checks first: none of them needs the handle or a device
+    if (int rc = check_spec(spec, "ptnn_mbar_spec")) return rc;
+    const ptnn_mbar_spec& s = *spec;
+    const bool u_src = s.u != nullptr, host_src = s.w != nullptr;
+    SampleSource src{host_src, s.w, nullptr, (int64_t)s.n_rungs * s.n_per_rung, nullptr, s.replicas, s.n_replicas, s.step0, s.nsteps, s.thin};
+    if (u_src && host_src) return fail(-1, "give host vectors w or a host U, not both");
+    if (s.b && !u_src) return fail(-1, "b comes with a host U");
+    if (s.n_rungs < 1) return fail(-1, "n_rungs = %d must be >= 1", s.n_rungs);
+    if (!s.betas) return fail(-1, "betas [n_rungs] is required");
+    if (u_src || host_src) {
+        if (s.n_per_rung < 1) return fail(-1, "n_per_rung = %lld must be >= 1", (long long)s.n_per_rung);
+    } else {
+        if (int rc = check_source(src, "vectors", true, "U")) return rc;
+        if (s.replicas && s.n_replicas != s.n_rungs) return fail(-1, "n_replicas = %d but n_rungs = %d betas", s.n_replicas, s.n_rungs);
+    }
+    for (int k = 0; k < s.n_rungs; ++k) {
+        if (!std::isfinite(s.betas[k]) || !(s.betas[k] > 0.0)) return fail(-1, "betas[%d] = %g must be finite and > 0", k, s.betas[k]);
+        if (k > 0 && !(s.betas[k] > s.betas[k - 1])) return fail(-1, "betas must rise strictly: betas[%d] = %g after %g", k, s.betas[k], s.betas[k - 1]);
+    }
+    if (s.n_prior < 0) return fail(-1, "n_prior = %lld must be >= 0", (long long)s.n_prior);
+    if (s.n_prior > 0x7fffffffLL) return fail(-1, "n_prior = %lld: at most 2^31 - 1 prior draws per call", (long long)s.n_prior);
+    if (s.b_prior && !s.u_prior) return fail(-1, "b_prior comes with u_prior");
+    if (s.u_prior && s.n_prior < 1) return fail(-1, "u_prior given with n_prior = 0");
+    const long long NP = s.n_prior;
+    const int K = s.n_rungs + (NP > 0 ? 1 : 0), k0 = NP > 0 ? 1 : 0;
+    if (K > MBAR_MAX_K) return fail(-1, "%d states: at most %d per call", K, MBAR_MAX_K);
+    if (!std::isfinite(s.target_beta) || s.target_beta < s.betas[0] || s.target_beta > s.betas[s.n_rungs - 1])
+        return fail(-1, "target_beta = %g outside the ladder [%g, %g]", s.target_beta, s.betas[0], s.betas[s.n_rungs - 1]);
+    if (!(s.tol > 0.0) || !std::isfinite(s.tol)) return fail(-1, "tol = %g must be a finite number > 0", s.tol);
+    if (s.max_iter < 1) return fail(-1, "max_iter = %d must be >= 1", s.max_iter);
+    if (s.n_resample < 0 || s.n_resample > 0x7fffffffLL) return fail(-1, "n_resample = %lld outside [0, 2^31 - 1]", (long long)s.n_resample);
+    if (s.n_resample == 0 && (s.resample_item || s.cum_weight)) return fail(-1, "resample_item and cum_weight need n_resample > 0");
+    const bool expect = s.mean || s.var;
+    const RowSource xrows{s.x_source, s.x, s.n_rows, "x_source", "PTNN_PREDICT_X", "x", "n_rows"};
+    if ((expect || s.resample_w) && (u_src || s.u_prior))
+        return fail(-1, "mean, var and resample_w need the items' weight vectors: not with a host U or host prior draws");
+    if (s.resample_w && s.n_resample == 0) return fail(-1, "resample_w needs n_resample > 0");
+    if (expect) {
+        if (s.n_rows < 1) return fail(-1, "n_rows = %d must be >= 1", s.n_rows);
+        if (int rc = check_rows(xrows)) return rc;
+    }
+    for (long long i = 0; s.u_prior && i < NP; ++i)
+        if (!std::isfinite(s.u_prior[i]) || (s.b_prior && !std::isfinite(s.b_prior[i]))) return fail(-1, "u_prior / b_prior [%lld] is not finite", i);
+    if (u_src && s.n_distinct) *s.n_distinct = 0;
+    // host sources: items, their multiplicities, the draws of every rung
+    const int R = s.n_rungs;
+    std::vector<long long> off((size_t)R + 1, 0);      // expanded draws of rung k at [off[k], off[k + 1])
+    std::vector<int32_t> item_of;                      // expanded draw -> rung item (multiplicities only)
+    long long per = 0;                                 // rows per rung
+    if (u_src || host_src) {
+        per = s.n_per_rung;
+        if ((long long)R * per > 0x7fffffffLL) return fail(-1, "%lld host rows: at most 2^31 - 1 per call", (long long)R * per);
+        src.n_items = (long long)R * per;
+        for (long long k = 0; k < R; ++k) {
+            long long c = 0;
+            for (long long i = 0; i < per; ++i) {
+                const long long it = k * per + i;
+                const int mu = s.multiplicity ? s.multiplicity[it] : 1;
+                if (mu < 0) return fail(-1, "multiplicity[%lld, %lld] = %d is negative", k, i, mu);
+                c += mu;
+                if (s.multiplicity) for (int r = 0; r < mu; ++r) item_of.push_back((int32_t)it);
+                if (u_src && mu > 0 && (!std::isfinite(s.u[it]) || (s.b && !std::isfinite(s.b[it]))))
+                    return fail(-1, "u / b [%lld, %lld] is not finite", k, i);
+            }
+            off[(size_t)k + 1] = off[(size_t)k] + c;
+            if (off[(size_t)k + 1] > 0x7fffffffLL) return fail(-1, "more than 2^31 - 1 expanded draws");
+        }
+    }
+    if (int rc = check_handle(h, "ptnn_mbar")) return rc;
+    const int O = h->cfg.n_out;
+    if (expect)
+        if (int rc = fit_rows(h, xrows)) return rc;
+    if (s.sse && h->cfg.task != PTNN_TASK_REG) return fail(-1, "sse: a classification has no sum of squared errors");
+    if (!u_src && !host_src) {
+        if (int rc = count_samples(h, src)) return rc;
+        if (src.n_items > 0x7fffffffLL) return fail(-1, "%lld trace rows: at most 2^31 - 1 per call", src.n_items);
+        if ((int)src.reps.size() != R) return fail(-1, "%d chains selected but n_rungs = %d betas", (int)src.reps.size(), R);
+        per = src.m;
+        for (int k = 0; k < R; ++k) off[(size_t)k + 1] = off[(size_t)k] + per;
+    }
+    for (int k = 0; k < R; ++k)
+        if (off[(size_t)k + 1] - off[(size_t)k] < 4)
+            return fail(-1, "rung %d holds %lld draws: the split ESS needs at least 4 per rung", k, off[(size_t)k + 1] - off[(size_t)k]);
+    const long long n_rows = (long long)R * per, n_draws = off[(size_t)R], NT = NP + n_rows;
+    if (NT > 0x7fffffffLL) return fail(-1, "%lld items: at most 2^31 - 1 per call", NT);
+    if (s.n_items) *s.n_items = NT;
+
+    if (int rc = start_device(h)) return rc;
+    hipStream_t st = h->stream;
+    DeviceScratch mem;
+    const size_t budget = scratch_budget("PTNN_EVIDENCE_SCRATCH_BYTES");
+    const unsigned row_blocks = (unsigned)((n_rows + EVID_THREADS - 1) / EVID_THREADS);
+    // ---- U and b of every item: the prior draws first, then the rungs' rows
+    double *d_u = nullptr, *d_b = nullptr, *d_c = nullptr, *d_D = nullptr;
+    HIP_TRY(mem.alloc(&d_u, (size_t)NT));
+    HIP_TRY(mem.alloc(&d_b, (size_t)NT));
+    HIP_TRY(mem.alloc(&d_c, (size_t)NT));
+    HIP_TRY(mem.alloc(&d_D, (size_t)NT));
+    HIP_TRY(hipMemsetAsync(d_b, 0, (size_t)NT * sizeof(double), st));
+    EvidEval ev;
+    Distinct d;                                        // the rungs' distinct vectors (sources 1, 2)
+    const bool need_net = !u_src || (NP > 0 && !s.u_prior);
+    if (need_net)
+        if (int rc = ev.init(h, mem, "MBAR")) return rc;
+    if (u_src) {
+        HIP_TRY(hipMemcpyAsync(d_u + NP, s.u, (size_t)n_rows * sizeof(double), hipMemcpyHostToDevice, st));
+        if (s.b) HIP_TRY(hipMemcpyAsync(d_b + NP, s.b, (size_t)n_rows * sizeof(double), hipMemcpyHostToDevice, st));
+    } else {
+        // stages a to c of the evidence path: items -> distinct vectors -> their U and b -> every row's
+        if (int rc = distinct_samples(h, mem, src, false, true, &d)) return rc;
+        const int U = d.U;
+        if (s.n_distinct) *s.n_distinct = U;
+        const long long rows_blk = ev.rows_for(U, budget);
+        float* d_fx = nullptr;
+        double *d_acc = nullptr, *d_udist = nullptr, *d_bdist = nullptr;
+        HIP_TRY(mem.alloc(&d_fx, (size_t)rows_blk * O * U));
+        HIP_TRY(mem.alloc(&d_acc, (size_t)U));
+        HIP_TRY(mem.alloc(&d_udist, (size_t)U));
+        HIP_TRY(mem.alloc(&d_bdist, (size_t)U));
+        if (int rc = ev.eval(d.base, d.run_off, U, rows_blk, d_fx, d_acc, d_udist, d_bdist)) return rc;
+        HIP_TRY(launch(evid_expand_kernel, dim3(row_blocks), dim3(EVID_THREADS), 0, st, n_rows, nullptr, d.item_run, d_udist, d_u + NP));
+        HIP_TRY(launch(evid_expand_kernel, dim3(row_blocks), dim3(EVID_THREADS), 0, st, n_rows, nullptr, d.item_run, d_bdist, d_b + NP));
+        if (int rc = ev.sse_check()) return rc;
+    }
+    if (s.u_prior) {
+        HIP_TRY(hipMemcpyAsync(d_u, s.u_prior, (size_t)NP * sizeof(double), hipMemcpyHostToDevice, st));
+        if (s.b_prior) HIP_TRY(hipMemcpyAsync(d_b, s.b_prior, (size_t)NP * sizeof(double), hipMemcpyHostToDevice, st));
+    } else if (NP > 0) {
+        if (int rc = ev.prior_draws(mem, budget, NP, s.seed, d_u, d_b)) return rc;
+        if (int rc = ev.sse_check()) return rc;
+    }
+    // ---- N_k and c_n: counts, or the split ESS of every rung's expanded U draws (stage d of the evidence path)
+    std::vector<double> n_eff((size_t)K, 0.0), scale((size_t)R, 1.0);
+    if (NP > 0) n_eff[0] = (double)NP;
+    for (int k = 0; k < R; ++k) n_eff[(size_t)(k0 + k)] = (double)(off[(size_t)k + 1] - off[(size_t)k]);
+    if (s.effective) {
+        long long* d_off = nullptr;
+        HIP_TRY(mem.upload(&d_off, off.data(), off.size(), st));
+        const double* d_udraw = d_u + NP;
+        if (s.multiplicity) {
+            int* d_item_of = nullptr;
+            double* d_exp = nullptr;
+            HIP_TRY(mem.upload(&d_item_of, item_of.data(), item_of.size(), st));
+            HIP_TRY(mem.alloc(&d_exp, (size_t)n_draws));
+            HIP_TRY(launch(evid_expand_kernel, dim3((unsigned)((n_draws + EVID_THREADS - 1) / EVID_THREADS)), dim3(EVID_THREADS), 0, st, n_draws,
+                           d_item_of, nullptr, d_u + NP, d_exp));
+            d_udraw = d_exp;
+        }
+        std::vector<double> ess((size_t)R, 0.0);
+        if (int rc = evid_rung_ess(h, off, d_off, d_udraw, ess.data())) return rc;
+        for (int k = 0; k < R; ++k) {
+            const double e = std::isfinite(ess[(size_t)k]) && ess[(size_t)k] > 0.0 ? ess[(size_t)k] : 1.0;
+            scale[(size_t)k] = e / n_eff[(size_t)(k0 + k)];
+            n_eff[(size_t)(k0 + k)] = e;
+        }
+    }
+    {
+        std::vector<double> c((size_t)NT);
+        for (long long i = 0; i < NP; ++i) c[(size_t)i] = 1.0;
+        for (long long k = 0; k < R; ++k)
+            for (long long i = 0; i < per; ++i)
+                c[(size_t)(NP + k * per + i)] = (double)(s.multiplicity ? s.multiplicity[k * per + i] : 1) * scale[(size_t)k];
+        HIP_TRY(hipMemcpyAsync(d_c, c.data(), (size_t)NT * sizeof(double), hipMemcpyHostToDevice, st));
+        if (int rc = wait_stream(h)) return rc;        // c lives until the copy is done
+    }
+    // ---- the states and the fixed point
+    std::vector<double> hs((size_t)4 * K, 0.0);        // beta, g, ln N, f
+    for (int k = 0; k < K; ++k) {
+        hs[(size_t)k] = k < k0 ? 0.0 : s.betas[k - k0];
+        hs[(size_t)K + k] = k < k0 ? 0.0 : 1.0;
+        hs[(size_t)2 * K + k] = std::log(n_eff[(size_t)k]);
+    }
+    double *d_s = nullptr, *d_raw = nullptr, *d_res = nullptr;
+    HIP_TRY(mem.upload(&d_s, hs.data(), hs.size(), st));
+    HIP_TRY(mem.alloc(&d_raw, (size_t)K));
+    HIP_TRY(mem.alloc(&d_res, 1));
+    const MbarItems it{d_u, d_b, d_c, d_D, NT};
+    const MbarStates ms{K, d_s, d_s + K, d_s + 2 * K, d_s + 3 * K};
+    double* d_f = d_s + 3 * K;
+    const unsigned item_blocks = (unsigned)((NT + MBAR_THREADS - 1) / MBAR_THREADS);
+    long long n_iter = 0;
+    double resid = INFINITY;
+    while (n_iter < s.max_iter && !(resid <= s.tol)) {
+        for (int q = 0; q < 8; ++q) {
+            HIP_TRY(launch(mbar_denominator_kernel, dim3(item_blocks), dim3(MBAR_THREADS), 0, st, it, ms));
+            HIP_TRY(launch(mbar_free_energy_kernel, dim3((unsigned)K), dim3(MBAR_THREADS), 0, st, it, ms.beta, ms.g, d_raw));
+            HIP_TRY(launch(mbar_pin_kernel, dim3(1), dim3(MBAR_MAX_K), 0, st, K, d_raw, d_f, d_res));
+        }
+        n_iter += 8;
+        HIP_TRY(hipMemcpyAsync(&resid, d_res, sizeof resid, hipMemcpyDeviceToHost, st));
+        if (int rc = wait_stream(h)) return rc;
+    }
+    if (!std::isfinite(resid)) return fail(-2, "the MBAR iteration left the finite numbers after %lld sweeps", n_iter);
+    if (s.n_iter) *s.n_iter = n_iter;
+    if (s.residual) *s.residual = resid;
+    // D of the final f, for W, the Gram matrix and the weights
+    HIP_TRY(launch(mbar_denominator_kernel, dim3(item_blocks), dim3(MBAR_THREADS), 0, st, it, ms));
+    if (s.n_eff) std::copy(n_eff.begin(), n_eff.end(), s.n_eff);
+    HIP_TRY(fetch(s.f, (const double*)d_f, (size_t)K, st));
+    HIP_TRY(fetch(s.u_out, (const double*)d_u, (size_t)NT, st));
+    HIP_TRY(fetch(s.b_out, (const double*)d_b, (size_t)NT, st));
+    if (s.gram) {
+        const int nt = (K + MBAR_TILE - 1) / MBAR_TILE, npairs = nt * (nt + 1) / 2;
+        const int n_chunks = (int)((NT + MBAR_GRAM_CHUNK - 1) / MBAR_GRAM_CHUNK);
+        double *d_part = nullptr, *d_M = nullptr;
+        HIP_TRY(mem.alloc(&d_part, (size_t)n_chunks * npairs * MBAR_TILE * MBAR_TILE));
+        HIP_TRY(mem.alloc(&d_M, (size_t)K * K));
+        const MbarGram ga{it, ms, d_part};
+        HIP_TRY(launch(mbar_gram_kernel, dim3((unsigned)((long long)npairs * n_chunks)), dim3(MBAR_THREADS), 0, st, ga));
+        HIP_TRY(launch(mbar_gram_sum_kernel, dim3((unsigned)((K * K + MBAR_THREADS - 1) / MBAR_THREADS)), dim3(MBAR_THREADS), 0, st, K, n_chunks,
+                       d_part, d_M));
+        HIP_TRY(fetch(s.gram, (const double*)d_M, (size_t)K * K, st));
+    }
+    // ---- the weights at the target beta, their statistics, systematic resampling
+    double *d_t = nullptr, *d_lw = nullptr, *d_ws = nullptr;
+    const double tgt[3] = {s.target_beta, 1.0, 0.0};   // beta, g, its free energy
+    HIP_TRY(mem.upload(&d_t, tgt, 3, st));
+    HIP_TRY(mem.alloc(&d_lw, (size_t)NT));
+    HIP_TRY(mem.alloc(&d_ws, 4));
+    HIP_TRY(launch(mbar_free_energy_kernel, dim3(1), dim3(MBAR_THREADS), 0, st, it, d_t, d_t + 1, d_t + 2));
+    HIP_TRY(launch(mbar_weight_kernel, dim3(item_blocks), dim3(MBAR_THREADS), 0, st, it, d_t, d_t + 2, d_lw));
+    HIP_TRY(launch(mbar_weight_stats_kernel, dim3(1), dim3(MBAR_THREADS), 0, st, d_lw, d_c, NT, d_ws));
+    HIP_TRY(fetch(s.log_weight, (const double*)d_lw, (size_t)NT, st));
+    double ws[4] = {0, 0, 0, 0};
+    if (s.n_resample > 0) {
+        double* d_cum = nullptr;
+        long long* d_item = nullptr;
+        uint32_t slo = 0, shi = 0;
+        split_seed(s.resample_seed, &slo, &shi);
+        HIP_TRY(mem.alloc(&d_cum, (size_t)NT));
+        HIP_TRY(mem.alloc(&d_item, (size_t)s.n_resample));
+        HIP_TRY(launch(mbar_scan_kernel, dim3(1), dim3(MBAR_THREADS), 0, st, d_lw, NT, d_cum));
+        HIP_TRY(launch(mbar_resample_kernel, dim3((unsigned)((s.n_resample + MBAR_THREADS - 1) / MBAR_THREADS)), dim3(MBAR_THREADS), 0, st, d_cum,
+                       NT, (long long)s.n_resample, slo, shi, d_item, d_ws + 3));
+        HIP_TRY(fetch(s.cum_weight, (const double*)d_cum, (size_t)NT, st));
+        static_assert(sizeof(long long) == sizeof(int64_t), "resample_item");
+        HIP_TRY(fetch(reinterpret_cast<long long*>(s.resample_item), (const long long*)d_item, (size_t)s.n_resample, st));
+        if (s.resample_w) {
+            float* d_rw = nullptr;
+            const int P = h->P;
+            HIP_TRY(mem.alloc(&d_rw, (size_t)s.n_resample * P));
+            uint32_t plo = 0, phi = 0;
+            split_seed(s.seed, &plo, &phi);
+            const MbarGather ga{d_item, (long long)s.n_resample, NP, P, (float)std::sqrt((double)h->cfg.sigma_squared), plo, phi, d.base, d.run_off,
+                                d.item_run, d_rw};
+            const long long nth = (long long)s.n_resample * ((P + 3) / 4);
+            HIP_TRY(launch(mbar_gather_kernel, dim3((unsigned)((nth + MBAR_THREADS - 1) / MBAR_THREADS)), dim3(MBAR_THREADS), 0, st, ga));
+            HIP_TRY(fetch(s.resample_w, (const float*)d_rw, (size_t)s.n_resample * P, st));
+        }
+    }
+    // ---- expectations of the network outputs on the rows x under the target weights (mbar_expect_kernel)
+    if (expect) {
+        const int I = h->cfg.n_in, P = h->P, n_x = s.n_rows, ncols = n_x * O, U = d.U;
+        const float* d_x = nullptr;
+        int xs = 0;
+        if (int rc = upload_rows(h, mem, xrows, I, &d_x, &xs)) return rc;
+        double *d_acc = nullptr, *d_mean = nullptr, *d_var = nullptr;
+        HIP_TRY(mem.alloc(&d_acc, (size_t)ncols));
+        HIP_TRY(mem.alloc(&d_mean, (size_t)ncols));
+        HIP_TRY(mem.alloc(&d_var, (size_t)ncols));
+        // the rungs' distinct vectors on blocks of rows; prior draws in blocks of nb vectors, a multiple of the kernel's chunk
+        const long long rblk = row_block(budget, (size_t)U * O * sizeof(float), n_x);
+        float *d_fx = nullptr, *d_pw = nullptr, *d_pfx = nullptr;
+        long long* d_poff = nullptr;
+        HIP_TRY(mem.alloc(&d_fx, (size_t)rblk * O * U));
+        long long nb = 0, pblk = 0;
+        if (NP > 0) {
+            const size_t per_draw = (size_t)P * sizeof(float) + sizeof(long long) + (size_t)WAVE * O * sizeof(float);
+            nb = std::min<long long>(NP, std::max<long long>(MBAR_THREADS, (long long)(budget / per_draw) / MBAR_THREADS * MBAR_THREADS));
+            const size_t fixed = (size_t)nb * ((size_t)P * sizeof(float) + sizeof(long long));
+            pblk = row_block(budget > fixed ? budget - fixed : 0, (size_t)nb * O * sizeof(float), n_x);
+            HIP_TRY(mem.alloc(&d_pw, (size_t)nb * P));
+            HIP_TRY(mem.alloc(&d_poff, (size_t)nb));
+            HIP_TRY(mem.alloc(&d_pfx, (size_t)pblk * O * nb));
+        }
+        const float sigma = (float)std::sqrt((double)h->cfg.sigma_squared);
+        uint32_t slo = 0, shi = 0;
+        split_seed(s.seed, &slo, &shi);
+        const int nq = (P + 3) / 4;
+        auto pass = [&](const double* mean) -> int {
+            HIP_TRY(hipMemsetAsync(d_acc, 0, (size_t)ncols * sizeof(double), st));
+            if (int rc = each_block(n_x, rblk, [&](long long r0, int nr) -> int {
+                if (int rc = ev.fwd.run(h, d.base, d.run_off, d_x, xs, (int)r0, nr, U, d_fx)) return rc;
+                const MbarExpect ea{d_fx, U, d.item_run, d_lw + NP, n_rows, mean, d_acc, (int)r0 * O};
+                HIP_TRY(launch(mbar_expect_kernel, dim3((unsigned)(nr * O)), dim3(MBAR_THREADS), 0, st, ea));
+                return 0;
+            })) return rc;
+            for (long long d0 = 0; d0 < NP; d0 += nb) {
+                const int b = (int)std::min<long long>(nb, NP - d0);
+                HIP_TRY(launch(evid_prior_kernel, dim3((unsigned)(((long long)b * nq + EVID_THREADS - 1) / EVID_THREADS)), dim3(EVID_THREADS), 0, st,
+                               d0, b, P, sigma, slo, shi, d_pw, d_poff));
+                if (int rc = each_block(n_x, pblk, [&](long long r0, int nr) -> int {
+                    if (int rc = ev.fwd.run(h, d_pw, d_poff, d_x, xs, (int)r0, nr, b, d_pfx)) return rc;
+                    const MbarExpect ea{d_pfx, b, nullptr, d_lw + d0, (long long)b, mean, d_acc, (int)r0 * O};
+                    HIP_TRY(launch(mbar_expect_kernel, dim3((unsigned)(nr * O)), dim3(MBAR_THREADS), 0, st, ea));
+                    return 0;
+                })) return rc;
+            }
+            return 0;
+        };
+        const unsigned cb = (unsigned)((ncols + MBAR_THREADS - 1) / MBAR_THREADS);
+        if (int rc = pass(nullptr)) return rc;
+        HIP_TRY(launch(mbar_expect_finish_kernel, dim3(cb), dim3(MBAR_THREADS), 0, st, ncols, d_acc, d_ws, d_mean));
+        if (s.var) {
+            if (int rc = pass(d_mean)) return rc;
+            HIP_TRY(launch(mbar_expect_finish_kernel, dim3(cb), dim3(MBAR_THREADS), 0, st, ncols, d_acc, d_ws, d_var));
+        }
+        HIP_TRY(fetch(s.mean, (const double*)d_mean, (size_t)ncols, st));
+        HIP_TRY(fetch(s.var, (const double*)d_var, (size_t)ncols, st));
+    }
+    HIP_TRY(fetch(s.sse, (const double*)d_b, (size_t)NT, st));       // b = -log SSE; finished below
+    HIP_TRY(hipMemcpyAsync(ws, d_ws, sizeof ws, hipMemcpyDeviceToHost, st));
+    if (int rc = wait_stream(h)) return rc;
+    for (long long n = 0; s.sse && n < NT; ++n) s.sse[n] = std::exp(-s.sse[n]);
+    // the map of the items: prior draws, then every rung's rows
+    const bool trace = !u_src && !host_src;
+    for (long long n = 0; n < NT && (s.item_chain || s.item_step || s.item_multiplicity); ++n) {
+        const long long r = n - NP, k = r < 0 ? -1 : r / per, i = r < 0 ? n : r % per;
+        if (s.item_chain) s.item_chain[n] = r < 0 ? -1 : trace ? src.reps[(size_t)k] : (int32_t)k;
+        if (s.item_step) s.item_step[n] = r >= 0 && trace ? (int64_t)s.step0 + i * s.thin : i;
+        if (s.item_multiplicity) s.item_multiplicity[n] = r >= 0 && s.multiplicity ? s.multiplicity[r] : 1;
+    }
+    if (s.weight_sum) *s.weight_sum = ws[0];
+    if (s.kish_ess) *s.kish_ess = ws[1];
+    if (s.max_weight_share) *s.max_weight_share = ws[2];
+    if (s.resample_u) *s.resample_u = s.n_resample > 0 ? ws[3] : 0.0;
     return 0;
 }
 

@@ -109,6 +109,14 @@ __global__ void __launch_bounds__(EVID_THREADS) evid_rung_kernel(const EvidRung 
     if (tid == 0) { a.log_stone[k] = mx + log(me); a.relvar[k] = ve / (me * me); }
 }
 
+// the four standard normals of components 4 q .. 4 q + 3 of prior draw `draw`
+__device__ __forceinline__ void prior_normals(int q, long long draw, uint32_t slo, uint32_t shi, float (&z)[4]) {
+    uint32_t x[4];
+    philox4x32_10((uint32_t)q, (uint32_t)draw, 0u, STREAM_PRIOR, slo, shi, x);
+    box_muller(x[0], x[1], z[0], z[1]);
+    box_muller(x[2], x[3], z[2], z[3]);
+}
+
 // stage e: the vectors of prior draws [d0, d0 + nb): w[b][k] = sigma * normals(P, d0 + b, 0, STREAM_PRIOR, seed)[k] (philox.py)
 __global__ void __launch_bounds__(EVID_THREADS) evid_prior_kernel(long long d0, int nb, int P, float sigma, uint32_t slo, uint32_t shi,
                                                                   float* w, long long* run_off) {
@@ -116,11 +124,8 @@ __global__ void __launch_bounds__(EVID_THREADS) evid_prior_kernel(long long d0, 
     const long long j = (long long)blockIdx.x * EVID_THREADS + threadIdx.x;
     if (j >= (long long)nb * nq) return;
     const int b = (int)(j / nq), q = (int)(j % nq);
-    uint32_t x[4];
-    philox4x32_10((uint32_t)q, (uint32_t)(d0 + b), 0u, STREAM_PRIOR, slo, shi, x);
     float z[4];
-    box_muller(x[0], x[1], z[0], z[1]);
-    box_muller(x[2], x[3], z[2], z[3]);
+    prior_normals(q, d0 + b, slo, shi, z);
     float* dst = w + (size_t)b * P;
 #pragma unroll
     for (int c = 0; c < 4; ++c)

@@ -2,7 +2,7 @@
 
 Used by the host only for the initial weights w0 (stream 3), which the reference draws in the parent process
 with np.random.randn (pt_timeseries_regression.py:649).  Streams: 0 step scalars, 1 proposal noise, 2 swap
-uniforms, 3 initial weights, 4 the observation noise of forecasts (counter (step / 4, trajectory, origin, 4)), 5 prior draws of the log evidence (counter (k / 4, draw, 0, 5)), 6 the replicated data of posterior predictive checks (counter (row / 4, occurrence, 0, 6)); counter = (index, step|round, global replica, stream); key = (seed lo, seed hi);
+uniforms, 3 initial weights, 4 the observation noise of forecasts (counter (step / 4, trajectory, origin, 4)), 5 prior draws of the log evidence (counter (k / 4, draw, 0, 5)), 6 the replicated data of posterior predictive checks (counter (row / 4, occurrence, 0, 6)), 7 the offset of the systematic resampling of rung_reweighting (counter (0, 0, 0, 7), word 0); counter = (index, step|round, global replica, stream); key = (seed lo, seed hi);
 uniform u = ((x >> 9) + 0.5) * 2^-23; normals by Box-Muller on (x0,x1) and (x2,x3).
 """
 import numpy as np
@@ -12,7 +12,7 @@ _M1 = np.uint64(0xCD9E8D57)
 _W0 = 0x9E3779B9
 _W1 = 0xBB67AE85
 _MASK = np.uint64(0xFFFFFFFF)
-STREAM_STEP, STREAM_WNOISE, STREAM_SWAP, STREAM_INIT, STREAM_FORECAST, STREAM_PRIOR, STREAM_PPC = 0, 1, 2, 3, 4, 5, 6
+STREAM_STEP, STREAM_WNOISE, STREAM_SWAP, STREAM_INIT, STREAM_FORECAST, STREAM_PRIOR, STREAM_PPC, STREAM_RESAMPLE = 0, 1, 2, 3, 4, 5, 6, 7
 
 
 def philox4x32(c0, c1, c2, c3, seed):
@@ -50,3 +50,8 @@ def initial_weights(seed, replica, n):
 def prior_weights(seed, draw, n, sigma):
     """Prior draw `draw` of the log evidence: sigma * normals(n, draw, 0, STREAM_PRIOR, seed) (ptnn_evidence, float64 here)."""
     return normals(n, draw, 0, STREAM_PRIOR, seed) * sigma
+
+
+def resample_uniform(seed):
+    """The offset u in (0, 1) of ptnn_mbar's systematic resampling: the 23-bit uniform of word 0 of counter (0, 0, 0, STREAM_RESAMPLE)."""
+    return float(uniform23(philox4x32(0, 0, 0, STREAM_RESAMPLE, seed)[0]))
