@@ -962,6 +962,108 @@ typedef struct ptnn_pd_spec {
 
 int ptnn_partial_dependence(ptnn_handle *h, const ptnn_pd_spec *spec);
 
+/* ---- accumulated local effects, first order and of input pairs (nothing in the reference) ----
+ * Partial dependence sets an input to a grid value on every row, which for correlated inputs (the lags of one series) evaluates the
+ * net where no data lies.  Accumulated local effects (Apley & Zhu 2020) move an input only across the bin the row already lies
+ * in, average the local differences per bin, accumulate and centre them; the second-order effect of a pair of inputs is what the
+ * two do together beyond their main effects.  f is the output ptnn_predict returns; s a selected sample, n a row, o an output.
+ * First order, input slot a with index j = inputs[a] and edges z_0 .. z_K (K = n_edges - 1), strictly increasing up to some
+ * K* >= 1 and constant from there (the tail is padding: zero-width bins that are always empty):
+ *   b(n, a)        = the smallest k >= 1 with x_n[j] <= z_k, K* when there is none (x <= z_0: bin 1; x > z_K*: bin K*)
+ *   d_s[n, a, o]   = f_o(w_s; x_n with x_j := z_b) - f_o(w_s; x_n with x_j := z_{b-1})   both f in fp32 (z_h of the row as it is, then
+ *                    z_h + (z - x_j) W1[j,h]), the difference formed in double and rounded to fp32 once
+ *   m_s[a, k, o]   = (sum of d_s over the n_k rows of bin k) / n_k    double, ascending row order, carried across row blocks; 0
+ *                    for an empty bin
+ *   g_s[a, k, o]   = g_s[a, k-1, o] + m_s[a, k, o], g_s[a, 0, o] = 0;   c_s[a, o] = (sum_k n_k g_s[a, k, o]) / n_rows
+ *   ALE_s[a, k, o] = g_s[a, k, o] - c_s[a, o], k = 0 .. K;  ALE32 = that as fp32;  range_s[a, o] = max_k ALE32 - min_k ALE32 (the
+ *                    difference formed in double and rounded once)
+ * Second order, pair q = (j, l) with edges u_0 .. u_K2 of j and v_0 .. v_K2 of l (K2 = n_edges2 - 1, the same padding rule), the
+ * row in cell (k, m) = (b_j(n), b_l(n)), N(k, m) rows per cell, n^j_k = sum_m N(k, m), n^l_m = sum_k N(k, m):
+ *   D2_s[n, q, o]  = [f(u_k, v_m) - f(u_{k-1}, v_m)] - [f(u_k, v_{m-1}) - f(u_{k-1}, v_{m-1})]   x_j and x_l substituted; in double
+ *                    from the four fp32 values in this order, fp32 once (each f: the input with the larger index substituted
+ *                    first, so that the pair (l, j) evaluates the very corners of (j, l))
+ *   D_s[k, m]      = (sum of D2_s over the rows of the cell) / N(k, m), 0 for an empty cell (ALEPlot borrows from the nearest
+ *                    non-empty cell instead; cell_count tells how much of the surface rests on data)
+ *   h_s[k, m]      = h_s[k-1, m] + sum_{m' <= m} D_s[k, m'] (the running sum along m, ascending), h[0, .] = h[., 0] = 0
+ *   A_s[k]         = A_s[k-1] + (sum_m N(k, m) (h[k, m] - h[k-1, m])) / n^j_k;   B_s[m] = B_s[m-1] + (sum_k N(k, m) (h[k, m] -
+ *                    h[k, m-1])) / n^l_m;   A[0] = B[0] = 0, a term with a zero count is 0
+ *   g2_s[k, m]     = (h[k, m] - A[k]) - B[m];   ALE2_s[q, k, m, o] = g2[k, m] - (sum_{k, m >= 1} N(k, m) g2[k, m]) / n_rows, k-major,
+ *                    k, m = 0 .. K2;  ALE2_32 = that as fp32
+ *   inter_s[q, o]  = sqrt((sum_{k, m >= 1} N(k, m) ALE2_32^2) / n_rows)   as fp32: the count-weighted RMS at the cells' upper corners
+ * Every sum is taken in double in ascending order, products and sums rounded separately.  DESIGN.md section 33.
+ * Sample set and rows: exactly as ptnn_partial_dependence.  edges [A, n_edges], 2 <= n_edges <= PTNN_ALE_MAX_EDGES: one row per
+ * first-order input; inputs [n_inputs] = their indices in the caller's order, NULL = all n_in (n_inputs is then ignored); edges ==
+ * NULL: no first-order term (A = 0), allowed with pairs only.  pairs [n_pairs, 2] = (j, l), n_pairs <= PTNN_ALE_MAX_PAIRS, with
+ * edges2 [n_pairs, 2, n_edges2], 2 <= n_edges2 <= PTNN_ALE_MAX_EDGES2; n_pairs = 0 is allowed.  ranks / n_ranks apply to the local
+ * effects, ranks2 / n_ranks2 to ALE32, range_s, ALE2_32 and inter_s.
+ * Outputs, any may be NULL, and an output costs device work only when its pointer is given.  With E = n_edges, E2 = n_edges2, O =
+ * n_out, T = A + n_pairs: bin_count [A, E - 1] and cell_count [n_pairs, E2 - 1, E2 - 1] = the rows per bin and cell; over the
+ * expanded multiset of M samples the weighted mean (accumulated in double), the exact fp32 order statistics of ranks2 and every
+ * selected row's value, chain-major, of ALE32: ale_mean [A, E, O], ale_order_stats [n_ranks2, A, E, O], sample_ale [M, A, E, O]; of
+ * range_s: range_mean [A, O], range_order_stats, sample_range; of ALE2_32: ale2_mean [n_pairs, E2, E2, O], ale2_order_stats,
+ * sample_ale2; of inter_s: inter_mean [n_pairs, O], inter_order_stats, sample_inter; of the local effects d_s then D2_s, column (n T
+ * + t) O + o: local_mean [n_rows, T, O], local_order_stats [n_ranks, n_rows, T, O], samples [M, n_rows, T, O]; n_samples = M,
+ * n_distinct.
+ * Refused: what ptnn_partial_dependence refuses, n_edges or n_edges2 out of range, no term at all, a non-finite edge, edges not
+ * increasing and then constant or with z_1 <= z_0, a pair with j = l or given twice (in either order); with the handle: an index
+ * outside [0, n_in), n_rows x T x n_out > 2^31 - 1 columns, bin accumulators past the scratch budget.  Rows are processed in
+ * blocks whose scratch (4 U T n_out bytes per row) stays under $PTNN_ALE_SCRATCH_BYTES (read per call, default 1 GiB), which
+ * changes no result.  Touches no chain state, tape, counter or trace row.  Not with a communicator attached (one GPU only). */
+#define PTNN_ALE_MAX_EDGES 64
+#define PTNN_ALE_MAX_EDGES2 16
+#define PTNN_ALE_MAX_PAIRS 16
+
+typedef struct ptnn_ale_spec {
+    int32_t struct_bytes;         /* = sizeof(ptnn_ale_spec): ABI guard */
+    /* source 1: the trace (used when w == NULL) */
+    const int32_t *replicas;      /* local replica indices, or NULL = all */
+    int32_t n_replicas;           /* entries of replicas (ignored when NULL) */
+    int32_t step0, nsteps, thin;  /* trace rows step0, step0 + thin, ... < step0 + nsteps (thin >= 1) */
+    /* source 2: host vectors */
+    const float *w;               /* [n_w, P] or NULL */
+    const int32_t *multiplicity;  /* [n_w] >= 0, or NULL = 1 each */
+    int64_t n_w;
+    /* rows */
+    int32_t x_source;             /* PTNN_PREDICT_X_HOST | _TRAIN | _TEST */
+    int32_t n_rows;
+    const float *x;               /* [n_rows, n_in] (host rows only) */
+    /* first order: the selected inputs and their edges */
+    const int32_t *inputs;        /* [n_inputs] distinct indices in [0, n_in), or NULL = 0 .. n_in - 1 */
+    int32_t n_inputs;             /* entries of inputs (ignored when NULL) */
+    int32_t n_edges;              /* E, 2 .. PTNN_ALE_MAX_EDGES */
+    const float *edges;           /* [A, n_edges] finite, increasing then constant; NULL = no first-order term */
+    /* second order: the pairs and their edges */
+    const int32_t *pairs;         /* [n_pairs, 2] (j, l), j != l */
+    int32_t n_pairs;              /* Q, 0 .. PTNN_ALE_MAX_PAIRS */
+    int32_t n_edges2;             /* E2, 2 .. PTNN_ALE_MAX_EDGES2 */
+    const float *edges2;          /* [n_pairs, 2, n_edges2]: the edges of j, then of l */
+    /* order statistics: of the local effects per (row, term, output), and of the curves, surfaces, ranges and interactions */
+    const int64_t *ranks;         /* [n_ranks] */
+    const int64_t *ranks2;        /* [n_ranks2] */
+    int32_t n_ranks, n_ranks2;    /* each <= PTNN_PREDICT_MAX_RANKS */
+    /* outputs */
+    int64_t *bin_count;
+    int64_t *cell_count;
+    double *ale_mean;
+    float *ale_order_stats;
+    double *range_mean;
+    float *range_order_stats;
+    float *sample_ale;
+    float *sample_range;
+    double *ale2_mean;
+    float *ale2_order_stats;
+    double *inter_mean;
+    float *inter_order_stats;
+    float *sample_ale2;
+    float *sample_inter;
+    double *local_mean;
+    float *local_order_stats;
+    float *samples;
+    int64_t *n_samples, *n_distinct;
+} ptnn_ale_spec;
+
+int ptnn_accumulated_effects(ptnn_handle *h, const ptnn_ale_spec *spec);
+
 /* ---- coalition values: Shapley attributions of the sampled nets (nothing in the reference: it never splits a prediction among
  * its inputs) ----
  * How much of one prediction each input accounts for, against a background sample (Shapley 1953; Strumbelj & Kononenko 2014;

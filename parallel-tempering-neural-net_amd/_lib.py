@@ -229,6 +229,29 @@ class PdSpec(C.Structure):
 PD_MAX_GRID = 64
 
 
+class AleSpec(C.Structure):
+    """ptnn_ale_spec (include/ptnn.h)."""
+    _fields_ = _SELECTION + [
+        ("w", C.POINTER(C.c_float)), ("multiplicity", C.POINTER(C.c_int32)), ("n_w", C.c_int64),
+        ("x_source", C.c_int32), ("n_rows", C.c_int32), ("x", C.POINTER(C.c_float)),
+        ("inputs", C.POINTER(C.c_int32)), ("n_inputs", C.c_int32), ("n_edges", C.c_int32), ("edges", C.POINTER(C.c_float)),
+        ("pairs", C.POINTER(C.c_int32)), ("n_pairs", C.c_int32), ("n_edges2", C.c_int32), ("edges2", C.POINTER(C.c_float)),
+        ("ranks", C.POINTER(C.c_int64)), ("ranks2", C.POINTER(C.c_int64)), ("n_ranks", C.c_int32), ("n_ranks2", C.c_int32),
+        ("bin_count", C.POINTER(C.c_int64)), ("cell_count", C.POINTER(C.c_int64)),
+        ("ale_mean", C.POINTER(C.c_double)), ("ale_order_stats", C.POINTER(C.c_float)),
+        ("range_mean", C.POINTER(C.c_double)), ("range_order_stats", C.POINTER(C.c_float)),
+        ("sample_ale", C.POINTER(C.c_float)), ("sample_range", C.POINTER(C.c_float)),
+        ("ale2_mean", C.POINTER(C.c_double)), ("ale2_order_stats", C.POINTER(C.c_float)),
+        ("inter_mean", C.POINTER(C.c_double)), ("inter_order_stats", C.POINTER(C.c_float)),
+        ("sample_ale2", C.POINTER(C.c_float)), ("sample_inter", C.POINTER(C.c_float)),
+        ("local_mean", C.POINTER(C.c_double)), ("local_order_stats", C.POINTER(C.c_float)), ("samples", C.POINTER(C.c_float)),
+        ("n_samples", C.POINTER(C.c_int64)), ("n_distinct", C.POINTER(C.c_int64)),
+    ]
+
+
+ALE_MAX_EDGES, ALE_MAX_EDGES2, ALE_MAX_PAIRS = 64, 16, 16
+
+
 class ShapSpec(C.Structure):
     """ptnn_shapley_spec (include/ptnn.h)."""
     _fields_ = _SELECTION + [
@@ -465,6 +488,7 @@ SYMBOLS = {
     "ptnn_forecast_score": (C.c_int, [C.c_void_p, C.POINTER(ForecastScoreSpec)]),
     "ptnn_sensitivity": (C.c_int, [C.c_void_p, C.POINTER(SensitivitySpec)]),
     "ptnn_partial_dependence": (C.c_int, [C.c_void_p, C.POINTER(PdSpec)]),
+    "ptnn_accumulated_effects": (C.c_int, [C.c_void_p, C.POINTER(AleSpec)]),
     "ptnn_coalition_values": (C.c_int, [C.c_void_p, C.POINTER(ShapSpec)]),
     "ptnn_ppc": (C.c_int, [C.c_void_p, C.POINTER(PpcSpec)]),
     "ptnn_powerscale": (C.c_int, [C.c_void_p, C.POINTER(PowerscaleSpec)]),
@@ -1309,6 +1333,71 @@ class Sampler:
                    samples=np.empty((max(M, 0), n_rows, A, G, O), np.float32) if samples else None)
         _bind(spec, out)
         return self._call(self.lib.ptnn_partial_dependence, spec, out)
+
+    def accumulated_effects(self, x="train", *, inputs=None, edges=None, pairs=None, edges2=None, replicas=None, step0=0, nsteps=None,
+                            thin=1, w=None, multiplicity=None, ranks=(), ranks2=(), local_mean=False, sample_ale=False, sample_range=False,
+                            sample_ale2=False, sample_inter=False, samples=False):
+        """ptnn_accumulated_effects: the accumulated local effects of the selected weight vectors on the rows `x`, reduced on the
+        device.  Source and x as predict().  edges [A, E] float32, one row of bin edges per first-order input (increasing, the
+        tail may repeat the last edge), None = no first-order term; inputs: their indices (None = all n_in).  pairs [Q, 2] with
+        edges2 [Q, 2, E2].  ranks apply to the local effects (their mean and order statistics are computed only with local_mean
+        or ranks), ranks2 to the curves, surfaces, ranges and interactions.  With T = A + Q -> dict(bin_count [A, E - 1],
+        cell_count [Q, E2 - 1, E2 - 1] int64, ale_mean [A, E, O] float64, ale_order_stats [len(ranks2), A, E, O] float32,
+        range_mean [A, O], range_order_stats, ale2_mean [Q, E2, E2, O], ale2_order_stats, inter_mean [Q, O], inter_order_stats,
+        sample_ale [M, A, E, O], sample_range [M, A, O], sample_ale2 [M, Q, E2, E2, O], sample_inter [M, Q, O], local_mean
+        [n_rows, T, O], local_order_stats [len(ranks), n_rows, T, O], samples [M, n_rows, T, O] float32, n_samples, n_distinct);
+        what was not asked for, or has no term, is None."""
+        spec, keep = _spec(AleSpec), []
+        self._rows(spec, keep, x, "x", (self.cfg.n_in, "n_in columns"))
+        n_rows, O = spec.n_rows, self.cfg.n_out
+        M = self._samples(spec, keep, w=w, multiplicity=multiplicity, replicas=replicas, step0=step0, nsteps=nsteps, thin=thin,
+                          unit="vector")
+        A = E = Q = E2 = 0
+        if edges is not None:
+            A = self.cfg.n_in
+            if inputs is not None:
+                ia = np.ascontiguousarray(inputs, dtype=np.int32).reshape(-1)
+                keep.append(ia)
+                spec.inputs, spec.n_inputs = _ptr(ia, _ip), ia.size
+                A = ia.size
+            ea = _f32(edges)
+            if ea.ndim != 2 or ea.shape[0] != A:
+                raise ValueError(f"edges must be [{A}, n_edges] (one row per selected input), got shape {ea.shape}")
+            keep.append(ea)
+            spec.edges, spec.n_edges = _ptr(ea), ea.shape[1]
+            E = ea.shape[1]
+        if pairs is not None and np.size(pairs):
+            pa = np.ascontiguousarray(pairs, dtype=np.int32)
+            if pa.ndim != 2 or pa.shape[1] != 2:
+                raise ValueError(f"pairs must be [n_pairs, 2], got shape {pa.shape}")
+            Q = pa.shape[0]
+            ea2 = _f32(edges2) if edges2 is not None else np.zeros((0,), np.float32)
+            if ea2.ndim != 3 or ea2.shape[:2] != (Q, 2):
+                raise ValueError(f"edges2 must be [{Q}, 2, n_edges2] (the edges of each pair's two inputs), got shape {ea2.shape}")
+            keep += [pa, ea2]
+            spec.pairs, spec.n_pairs, spec.edges2, spec.n_edges2 = _ptr(pa, _ip), Q, _ptr(ea2), ea2.shape[2]
+            E2 = ea2.shape[2]
+        T, Mx = A + Q, max(M, 0)
+        n_rk, n_rk2 = _ranks(spec, keep, ranks), _ranks(spec, keep, ranks2, ("ranks2", "n_ranks2"))
+        out = dict(bin_count=np.empty((A, E - 1), np.int64) if A else None,
+                   cell_count=np.empty((Q, E2 - 1, E2 - 1), np.int64) if Q else None,
+                   ale_mean=np.empty((A, E, O), np.float64) if A else None,
+                   ale_order_stats=np.empty((n_rk2, A, E, O), np.float32) if A and n_rk2 else None,
+                   range_mean=np.empty((A, O), np.float64) if A else None,
+                   range_order_stats=np.empty((n_rk2, A, O), np.float32) if A and n_rk2 else None,
+                   sample_ale=np.empty((Mx, A, E, O), np.float32) if A and sample_ale else None,
+                   sample_range=np.empty((Mx, A, O), np.float32) if A and sample_range else None,
+                   ale2_mean=np.empty((Q, E2, E2, O), np.float64) if Q else None,
+                   ale2_order_stats=np.empty((n_rk2, Q, E2, E2, O), np.float32) if Q and n_rk2 else None,
+                   inter_mean=np.empty((Q, O), np.float64) if Q else None,
+                   inter_order_stats=np.empty((n_rk2, Q, O), np.float32) if Q and n_rk2 else None,
+                   sample_ale2=np.empty((Mx, Q, E2, E2, O), np.float32) if Q and sample_ale2 else None,
+                   sample_inter=np.empty((Mx, Q, O), np.float32) if Q and sample_inter else None,
+                   local_mean=np.empty((n_rows, T, O), np.float64) if local_mean else None,
+                   local_order_stats=np.empty((n_rk, n_rows, T, O), np.float32) if n_rk else None,
+                   samples=np.empty((Mx, n_rows, T, O), np.float32) if samples else None)
+        _bind(spec, out)
+        return self._call(self.lib.ptnn_accumulated_effects, spec, out)
 
     def coalition_values(self, x="test", *, background, masks, coef, replicas=None, step0=0, nsteps=None, thin=1, w=None, multiplicity=None,
                          ranks=(), ranks2=(), mean=True, counts=False, abs_mean=True, sample_abs=False, samples=False):

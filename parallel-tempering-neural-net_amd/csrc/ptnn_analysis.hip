@@ -1,5 +1,5 @@
 // ptnn_analysis.hip -- the posterior analysis calls of libptnn.so: predict, convergence, rank_convergence, elpd, lfo, forecast, evidence, mbar, calibration,
-// forecast_score, sensitivity, partial_dependence, coalition_values, ppc, powerscale, prior_predictive, influence, modes, and the sample-selection path they share.  The shape-independent analysis kernels are defined in this object: it includes them.
+// forecast_score, sensitivity, partial_dependence, accumulated_effects, coalition_values, ppc, powerscale, prior_predictive, influence, modes, and the sample-selection path they share.  The shape-independent analysis kernels are defined in this object: it includes them.
 #include "ptnn_shapes.hpp"                   // PTNN_SHAPES
 #include "ptnn_analysis_device.hpp"          // the per-shape forward kernels and their table, AnalysisShape
 namespace ptnn {
@@ -18,6 +18,7 @@ namespace ptnn {
 #include "ptnn_dev_rank.hpp"                 // rank-normalised convergence: sort words, average ranks, z-scores, indicators, rank histograms
 #include "ptnn_dev_sensitivity_reduce.hpp"   // input sensitivity: sign counts, row sums and their weighted means
 #include "ptnn_dev_pd_reduce.hpp"            // partial dependence: row sums, ranges and the weighted means of the row means
+#include "ptnn_dev_ale_reduce.hpp"           // accumulated local effects: bin sums and counts, the centred curves and surfaces
 #include "ptnn_dev_report.hpp"               // classification report: confusion counts, Mann-Whitney counts and metric columns per sample
 #include "ptnn_dev_uncertainty.hpp"          // predictive uncertainty: entropy per sample and its mean per row, variance per column, mean noise
 #include "ptnn_dev_influence.hpp"            // case influence: column moments and the tiled FP64 cross-covariance over the samples
@@ -944,6 +945,223 @@ int ptnn_partial_dependence(ptnn_handle* h, const ptnn_pd_spec* spec) {
     HIP_TRY(fetch(s.range_mean, d_range_mean, (size_t)AO, st));
     HIP_TRY(fetch(s.range_order_stats, d_range_stats, (size_t)nrk_range * AO, st));
     return wait_stream(h);
+}
+
+// ---- accumulated local effects (ptnn_dev_ale.hpp) ----
+static_assert(PTNN_ALE_MAX_EDGES == ALE_MAX_EDGES && PTNN_ALE_MAX_EDGES2 == ALE_MAX_EDGES2 && PTNN_ALE_MAX_PAIRS == ALE_MAX_PAIRS,
+              "ptnn.h PTNN_ALE limits");
+
+namespace {
+// Stage b of the accumulated local effects: the per-shape ale_fwd.  A work-group stages NV distinct vectors in LDS beside their
+// finished tiles of one chunk of whole terms: ale_chunk_slots(n_out) slots of two values each, 2 * n_out * 64 floats per slot
+// (10 KiB per vector; 18 KiB at n_out = 18, where a pair's two slots are two passes), and once per work-group the chunk's slot
+// table (ale_slot_floats); NV = as many vectors as 64 KiB hold (two work-groups share a CU), at most 16.  The largest compiled
+// request is 34-512-2: one vector of 18948 floats, a 10-slot chunk and its table, 94 048 B.
+struct AlePlan {
+    int PV = 0, NV = 0, VS = 0, NCH1 = 0, NCH2 = 0;
+    size_t lds = 0;
+    void (*fwd)(const AleFwd) = nullptr;
+    int init(const ptnn_handle* h, int A, int Q) {
+        const int O = h->cfg.n_out, CS = ale_chunk_slots(O);
+        PV = round_up4(h->P);
+        const int tile = CS * 2 * O * WAVE;
+        NV = std::max(1, std::min(ALE_MAX_NV, (64 * 1024 / 4 - ale_slot_floats(O)) / (PV + tile + WAVE)));
+        VS = tile + std::max(1, WAVE / NV);             // the pad: the vectors of one column land in different LDS banks
+        NCH1 = (A + CS - 1) / CS;
+        NCH2 = (Q + CS / 2 - 1) / (CS / 2);
+        lds = ((size_t)NV * (PV + VS) + ale_slot_floats(O)) * sizeof(float);
+        if (lds > LDS_CEILING) return fail(-3, "accumulated effects: a %d-parameter vector does not fit in LDS", h->P);
+        return analysis_shape(h, "accumulated effects", &AnalysisShape::ale_fwd, lds, &fwd);
+    }
+    int run(const ptnn_handle* h, AleFwd fa, int r0, int nr) const {
+        fa.row0 = r0; fa.nrows = nr; fa.H = h->cfg.n_hidden; fa.P = h->P; fa.PV = PV; fa.NV = NV; fa.VS = VS; fa.NCH1 = NCH1;
+        HIP_TRY(launch(fwd, dim3((unsigned)((fa.U + NV - 1) / NV), (unsigned)((nr + WAVE - 1) / WAVE), (unsigned)(NCH1 + NCH2)),
+                       dim3(ALE_THREADS), lds, h->stream, fa));
+        return 0;
+    }
+};
+
+// `rows` rows of E edges each: finite, z_1 > z_0, strictly increasing and then constant
+int ale_check_edges(const char* name, const float* e, int rows, int E) {
+    for (int r = 0; r < rows; ++r) {
+        const float* z = e + (size_t)r * E;
+        for (int k = 0; k < E; ++k)
+            if (!std::isfinite(z[k])) return fail(-1, "%s[%d, %d] = %g (row %d, position %d) is not finite", name, r, k, (double)z[k], r, k);
+        if (!(z[1] > z[0])) return fail(-1, "%s[%d, 1] = %g <= %s[%d, 0] = %g: the first bin needs a width", name, r, (double)z[1], name, r, (double)z[0]);
+        bool flat = false;
+        for (int k = 2; k < E; ++k) {
+            if (z[k] < z[k - 1]) return fail(-1, "%s[%d, %d] = %g < %s[%d, %d] = %g: edges increase", name, r, k, (double)z[k], name, r, k - 1, (double)z[k - 1]);
+            if (z[k] > z[k - 1] && flat)
+                return fail(-1, "%s[%d, %d] = %g increases after repeated edges: only the tail may repeat the last edge", name, r, k, (double)z[k]);
+            flat = flat || z[k] == z[k - 1];
+        }
+    }
+    return 0;
+}
+
+// the columns cols [ncols][U] of the call's second kind: weighted mean, the exact ranks ranks2 and every selected sample's values
+int ale_reduce(ptnn_handle* h, RowsByVectors& f, const long long* d_ranks2, int n_ranks2, const float* cols, int ncols, double* mean,
+               float* order_stats, float* samples) {
+    hipStream_t st = h->stream;
+    const int nrk = order_stats ? n_ranks2 : 0;
+    if (mean || nrk) {
+        double* d_mean = nullptr;
+        float* d_stats = nullptr;
+        HIP_TRY(f.mem.alloc(&d_mean, (size_t)ncols));
+        HIP_TRY(f.mem.alloc(&d_stats, (size_t)nrk * ncols));
+        PredictRed ra{cols, f.d.run_cnt, f.U, 1, 0, ncols, f.M, nrk, d_ranks2, d_mean, d_stats, nullptr};
+        HIP_TRY(launch(predict_reduce_kernel, dim3((unsigned)ncols), dim3(PRED_THREADS), 0, st, ra));
+        HIP_TRY(fetch(mean, d_mean, (size_t)ncols, st));
+        HIP_TRY(fetch(order_stats, d_stats, (size_t)nrk * ncols, st));
+    }
+    return samples ? scatter_samples(h, cols, ncols, f.U, f.item_run, f.src.weights(), samples, (size_t)ncols, 0) : 0;
+}
+}  // namespace
+
+int ptnn_accumulated_effects(ptnn_handle* h, const ptnn_ale_spec* spec) {
+    // argument checks first: none of them needs the handle or a device (the edges of inputs == NULL have n_in rows: checked with the handle)
+    if (int rc = check_spec(spec, "ptnn_ale_spec")) return rc;
+    const ptnn_ale_spec& s = *spec;
+    const void* stats2 = s.ale_order_stats ? (const void*)s.ale_order_stats : s.range_order_stats ? (const void*)s.range_order_stats
+                       : s.ale2_order_stats ? (const void*)s.ale2_order_stats : (const void*)s.inter_order_stats;
+    RowsByVectors f(s, RankOutputs{s.n_ranks, s.ranks, s.local_order_stats}, RankOutputs{s.n_ranks2, s.ranks2, stats2});
+    if (int rc = f.check()) return rc;
+    const int Q = s.n_pairs, E = s.n_edges, E2 = s.n_edges2;
+    if (Q < 0 || Q > PTNN_ALE_MAX_PAIRS) return fail(-1, "n_pairs = %d outside [0, %d]", Q, PTNN_ALE_MAX_PAIRS);
+    if (!s.edges && Q == 0) return fail(-1, "no term: edges is NULL (no first-order input) and n_pairs = 0");
+    if (s.edges && (E < 2 || E > PTNN_ALE_MAX_EDGES)) return fail(-1, "n_edges = %d outside [2, %d]", E, PTNN_ALE_MAX_EDGES);
+    if (s.edges && s.inputs && s.n_inputs < 1) return fail(-1, "n_inputs = %d with an input list", s.n_inputs);
+    if (s.edges && s.inputs)
+        if (int rc = ale_check_edges("edges", s.edges, s.n_inputs, E)) return rc;
+    if (Q > 0) {
+        if (!s.pairs) return fail(-1, "n_pairs = %d but pairs is NULL", Q);
+        if (E2 < 2 || E2 > PTNN_ALE_MAX_EDGES2) return fail(-1, "n_edges2 = %d outside [2, %d]", E2, PTNN_ALE_MAX_EDGES2);
+        if (!s.edges2) return fail(-1, "edges2 is NULL: two rows of n_edges2 edges per pair");
+        if (int rc = ale_check_edges("edges2", s.edges2, 2 * Q, E2)) return rc;
+        for (int q = 0; q < Q; ++q) {
+            const int j = s.pairs[2 * q], l = s.pairs[2 * q + 1];
+            if (j == l) return fail(-1, "pairs[%d] = (%d, %d): a pair needs two different inputs", q, j, l);
+            for (int p = 0; p < q; ++p)
+                if ((s.pairs[2 * p] == j && s.pairs[2 * p + 1] == l) || (s.pairs[2 * p] == l && s.pairs[2 * p + 1] == j))
+                    return fail(-1, "pairs[%d] = (%d, %d) is given twice (pairs[%d])", q, j, l, p);
+        }
+    }
+    if (int rc = check_handle(h, "ptnn_accumulated_effects")) return rc;
+    const int I = h->cfg.n_in, O = h->cfg.n_out;
+    if (int rc = fit_rows(h, f.rows)) return rc;
+    std::vector<int32_t> inputs(!s.edges ? (size_t)0 : s.inputs ? (size_t)s.n_inputs : (size_t)I);
+    for (size_t a = 0; a < inputs.size(); ++a) inputs[a] = s.inputs ? s.inputs[a] : (int32_t)a;
+    if (s.edges && !s.inputs)
+        if (int rc = ale_check_edges("edges", s.edges, I, E)) return rc;
+    std::vector<char> seen((size_t)I, 0);
+    for (size_t a = 0; a < inputs.size(); ++a) {
+        if (inputs[a] < 0 || inputs[a] >= I) return fail(-1, "inputs[%d] = %d outside [0, %d)", (int)a, inputs[a], I);
+        if (seen[(size_t)inputs[a]]) return fail(-1, "inputs[%d] = %d is given twice", (int)a, inputs[a]);
+        seen[(size_t)inputs[a]] = 1;
+    }
+    for (int q = 0; q < 2 * Q; ++q)
+        if (s.pairs[q] < 0 || s.pairs[q] >= I) return fail(-1, "pairs[%d, %d] = %d outside [0, %d)", q / 2, q % 2, s.pairs[q], I);
+    const int A = (int)inputs.size(), T = A + Q, K = A ? E - 1 : 0, K2 = Q ? E2 - 1 : 0, KK = K2 * K2, NB = A * K + Q * KK;
+    const int AEO = A * (K + 1) * O, AO = A * O, QEO = Q * (K2 + 1) * (K2 + 1) * O, QO = Q * O;
+    const long long ncols_all = (long long)s.n_rows * T * O;
+    if (ncols_all > 0x7fffffffLL)
+        return fail(-1, "%d rows x %d terms x %d outputs = %lld columns: at most 2^31 - 1 per call", s.n_rows, T, O, ncols_all);
+    const int ncols = (int)ncols_all;
+    if (int rc = f.select(h, s.n_samples)) return rc;
+
+    hipStream_t st = h->stream;
+    DeviceScratch& mem = f.mem;
+    int *d_inputs = nullptr, *d_pairs = nullptr;
+    float *d_edges = nullptr, *d_edges2 = nullptr;
+    if (int rc = f.stage(h, I, s.n_distinct, [&]() -> int {
+        if (A) {
+            HIP_TRY(mem.upload(&d_inputs, (const int*)inputs.data(), (size_t)A, st));
+            HIP_TRY(mem.upload(&d_edges, s.edges, (size_t)A * E, st));
+        }
+        if (Q) {
+            HIP_TRY(mem.upload(&d_pairs, (const int*)s.pairs, (size_t)2 * Q, st));
+            HIP_TRY(mem.upload(&d_edges2, s.edges2, (size_t)2 * Q * E2, st));
+        }
+        return 0;
+    })) return rc;
+    const Distinct& d = f.d;
+    const int U = f.U;
+    // an output costs device work only when its pointer is given
+    const bool want1 = A && (s.ale_mean || s.ale_order_stats || s.sample_ale || s.range_mean || s.range_order_stats || s.sample_range);
+    const bool want2 = Q && (s.ale2_mean || s.ale2_order_stats || s.sample_ale2 || s.inter_mean || s.inter_order_stats || s.sample_inter);
+    const bool want_count = s.bin_count || s.cell_count || want1 || want2;
+    // what no block size shrinks: the bin accumulators and the surfaces' running sums, per distinct vector
+    const size_t budget = scratch_budget("PTNN_ALE_SCRATCH_BYTES");
+    const double fixed_bytes = ((want1 || want2 ? (double)NB : 0.0) + (want2 ? (double)QEO / O : 0.0)) * O * U * sizeof(double);
+    if (fixed_bytes > (double)std::max(budget, (size_t)1 << 30))
+        return fail(-1, "%d bins and cells x %d outputs x %d distinct vectors: the accumulators need %.0f bytes, more than the larger of "
+                        "$PTNN_ALE_SCRATCH_BYTES and 1 GiB", NB, O, U, fixed_bytes);
+    Columns local{h, f, ncols, s.local_mean, s.local_order_stats, s.samples};
+    if (int rc = local.alloc()) return rc;
+    long long* d_ranks2 = nullptr;
+    if (s.n_ranks2) HIP_TRY(mem.upload(&d_ranks2, (const long long*)s.ranks2, (size_t)s.n_ranks2, st));
+    double* d_acc = nullptr;
+    int *d_bins = nullptr, *d_count = nullptr;
+    HIP_TRY(mem.alloc(&d_bins, (size_t)s.n_rows * T));
+    if (want1 || want2) {
+        HIP_TRY(mem.alloc(&d_acc, (size_t)NB * O * U));
+        HIP_TRY(hipMemsetAsync(d_acc, 0, (size_t)NB * O * U * sizeof(double), st));
+    }
+    // the forward pass, the column reductions and the bin sums in blocks of rows: fx scratch U x (rows x T x O) floats under the budget
+    const long long rows_blk = row_block(budget, (size_t)U * sizeof(float) * T * O, s.n_rows);
+    float* d_fx = nullptr;
+    HIP_TRY(mem.alloc(&d_fx, (size_t)rows_blk * T * O * U));
+    AlePlan fwd;
+    if (int rc = fwd.init(h, A, Q)) return rc;
+    if (int rc = f.items(h, s.samples || s.sample_ale || s.sample_range || s.sample_ale2 || s.sample_inter)) return rc;
+    const unsigned ublocks = (unsigned)((U + PRED_THREADS - 1) / PRED_THREADS);
+    AleFwd fa{};
+    fa.base = d.base; fa.run_off = d.run_off; fa.x = f.d_x; fa.xs = f.xs; fa.U = U; fa.A = A; fa.Q = Q; fa.E = E; fa.E2 = E2;
+    fa.inputs = d_inputs; fa.edges = d_edges; fa.pairs = d_pairs; fa.edges2 = d_edges2; fa.fx = d_fx; fa.bins = d_bins;
+    if (int rc = each_block(s.n_rows, rows_blk, [&](long long r0, int nr) -> int {
+        if (int rc = fwd.run(h, fa, (int)r0, nr)) return rc;
+        if (int rc = local.reduce(d_fx, r0 * T * O, (long long)nr * T * O)) return rc;
+        if (d_acc) {
+            AleBins ba{d_fx, d_bins, U, T, O, A, K, KK, (int)r0, nr, d_acc};
+            HIP_TRY(launch(ale_bins_kernel, dim3(ublocks * (unsigned)(T * O)), dim3(PRED_THREADS), 0, st, ba));
+        }
+        return local.scatter(d_fx, r0 * T * O, (long long)nr * T * O);
+    })) return rc;
+    std::vector<int32_t> count;
+    if (want_count) {       // the rows per bin and cell, once per call
+        HIP_TRY(mem.alloc(&d_count, (size_t)NB));
+        AleCount ca{d_bins, s.n_rows, T, A, K, KK, NB, d_count};
+        HIP_TRY(launch(ale_count_kernel, dim3((unsigned)((NB + PRED_THREADS - 1) / PRED_THREADS)), dim3(PRED_THREADS), 0, st, ca));
+        if (s.bin_count || s.cell_count) {
+            count.resize((size_t)NB);
+            HIP_TRY(fetch(count.data(), (const int32_t*)d_count, (size_t)NB, st));
+        }
+    }
+    if (want1) {            // the curves and their ranges
+        float *d_ale32 = nullptr, *d_range = nullptr;
+        HIP_TRY(mem.alloc(&d_ale32, (size_t)AEO * U));
+        HIP_TRY(mem.alloc(&d_range, (size_t)AO * U));
+        AleCurve ca{d_acc, d_count, U, A, K, O, (double)s.n_rows, d_ale32, d_range};
+        HIP_TRY(launch(ale_curve_kernel, dim3(ublocks * (unsigned)AO), dim3(PRED_THREADS), 0, st, ca));
+        if (int rc = ale_reduce(h, f, d_ranks2, s.n_ranks2, d_ale32, AEO, s.ale_mean, s.ale_order_stats, s.sample_ale)) return rc;
+        if (int rc = ale_reduce(h, f, d_ranks2, s.n_ranks2, d_range, AO, s.range_mean, s.range_order_stats, s.sample_range)) return rc;
+    }
+    if (want2) {            // the surfaces and their interaction strengths
+        float *d_ale2 = nullptr, *d_inter = nullptr;
+        double* d_work = nullptr;
+        HIP_TRY(mem.alloc(&d_ale2, (size_t)QEO * U));
+        HIP_TRY(mem.alloc(&d_inter, (size_t)QO * U));
+        HIP_TRY(mem.alloc(&d_work, (size_t)QEO * U));
+        AleSurface sa{d_acc + (size_t)A * K * O * U, d_count + A * K, U, Q, K2, O, (double)s.n_rows, d_work, d_ale2, d_inter};
+        HIP_TRY(launch(ale2_surface_kernel, dim3(ublocks * (unsigned)QO), dim3(PRED_THREADS), 0, st, sa));
+        if (int rc = ale_reduce(h, f, d_ranks2, s.n_ranks2, d_ale2, QEO, s.ale2_mean, s.ale2_order_stats, s.sample_ale2)) return rc;
+        if (int rc = ale_reduce(h, f, d_ranks2, s.n_ranks2, d_inter, QO, s.inter_mean, s.inter_order_stats, s.sample_inter)) return rc;
+    }
+    if (int rc = local.fetch()) return rc;
+    if (int rc = wait_stream(h)) return rc;
+    for (int k = 0; s.bin_count && k < A * K; ++k) s.bin_count[k] = count[(size_t)k];
+    for (int k = 0; s.cell_count && k < Q * KK; ++k) s.cell_count[k] = count[(size_t)(A * K + k)];
+    return 0;
 }
 
 // ---- coalition values: Shapley attributions (ptnn_dev_shapley.hpp) ----

@@ -14,6 +14,7 @@ namespace ptnn {
 #include "ptnn_dev_sensitivity.hpp"          // input sensitivity: the forward pass that carries the derivative to the inputs
 #include "ptnn_dev_pd.hpp"                   // partial dependence and ICE curves: the forward pass over substituted inputs
 #include "ptnn_dev_shapley.hpp"              // coalition values (Shapley attributions): the forward pass over hybrid rows
+#include "ptnn_dev_ale.hpp"                  // accumulated local effects: the forward pass over each row's own bin edges
 
 struct AnalysisShape {
     int task, I, O;
@@ -22,5 +23,6 @@ struct AnalysisShape {
     void (*sens_fwd)(const SensFwd);         // input sensitivity: d output / d input of distinct vectors x input rows (every H)
     void (*pd_fwd)(const PdFwd);             // partial dependence: outputs of distinct vectors x input rows x substituted grid values (every H)
     void (*shap_fwd)(const ShapFwd);         // coalition values: linear functionals of the game, distinct vectors x explained rows (every H)
+    void (*ale_fwd)(const AleFwd);           // accumulated local effects: first and second differences across each row's own bin (every H)
 };
 }  // namespace ptnn

@@ -7,4 +7,4 @@ using namespace ptnn;
 extern "C" const AnalysisShape PTNN_SHAPE_SYMBOL = {PTNN_T, PTNN_I, PTNN_O,
                                                     &predict_forward_kernel<PTNN_T, PTNN_I, PTNN_O>, &forecast_forward_kernel<PTNN_T, PTNN_I, PTNN_O>,
                                                     &sensitivity_forward_kernel<PTNN_T, PTNN_I, PTNN_O>, &pd_forward_kernel<PTNN_T, PTNN_I, PTNN_O>,
-                                                    &shapley_forward_kernel<PTNN_T, PTNN_I, PTNN_O>};
+                                                    &shapley_forward_kernel<PTNN_T, PTNN_I, PTNN_O>, &ale_forward_kernel<PTNN_T, PTNN_I, PTNN_O>};

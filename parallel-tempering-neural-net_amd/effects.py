@@ -1,7 +1,7 @@
 """Partial dependence and ICE curves of the drop-in (not in the reference): what the sampled nets do as one input goes over a grid
 of values, the other inputs held at the data rows (Friedman 2001; Goldstein et al. 2015); and Shapley attributions: how much of
 one prediction each input accounts for against a background sample (Shapley 1953; Strumbelj & Kononenko 2014; Lundberg & Lee
-2017; the helpers, the result tuple and the method's body live in shapley.py).  The host-only grid helper, the result tuple, and
+2017; the helpers, the result tuple and the method's body live in shapley.py; accumulated local effects likewise in ale.py).  The host-only grid helper, the result tuple, and
 the mixin that holds the public methods.  A method checks its arguments, makes one low-level call of `_lib.Sampler` (the device
 does the work) and finishes the result with host arithmetic.
 """
@@ -10,7 +10,9 @@ from collections import namedtuple
 import numpy as np
 
 from . import _lib
+from . import ale as _ale
 from . import shapley as _shapley
+from .ale import AccumulatedEffects, ale_edges  # noqa: F401
 from .analysis import check_percentiles, top_share
 from .shapley import ShapleyValues, shapley_table  # noqa: F401
 
@@ -67,7 +69,7 @@ def pd_grid(rows, inputs, grid, grid_range=(5, 95)):
 
 
 class EffectAnalysis:
-    """partial_dependence() and shapley_values(), for `ParallelTemperingBase` to inherit next to `PosteriorAnalysis`, whose row, sample-source and
+    """partial_dependence(), accumulated_effects() and shapley_values(), for `ParallelTemperingBase` to inherit next to `PosteriorAnalysis`, whose row, sample-source and
     percentile helpers it uses.  It reads the constructor's attributes `task`, `topology` and `_sampler`."""
 
     def partial_dependence(self, x="train", *, inputs=None, grid=16, grid_range=(5, 95), percentiles=(5, 95), ice=False, burn_in=None,
@@ -108,6 +110,9 @@ class EffectAnalysis:
             ice_mean=out["ice_mean"] if ice else None,
             ice_percentiles=self._bands(out["ice_order_stats"], pcts, spots, ranks) if ice and has else {},
             sample_pd=sp, samples=out["samples"], n_samples=out["n_samples"], n_distinct=out["n_distinct"])
+
+    # accumulated local effects, first order and of input pairs, with their posterior bands (ale.py holds the body and the docstring)
+    accumulated_effects = _ale.accumulated_effects
 
     # Shapley attributions of single predictions with their posterior bands (shapley.py holds the body and the docstring)
     shapley_values = _shapley.shapley_values

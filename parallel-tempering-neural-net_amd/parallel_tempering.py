@@ -35,6 +35,7 @@ from .prior import PriorPredictive, prior_flagged  # noqa: F401
 # partial dependence and ICE curves live in effects.py; the result tuple and pd_grid are importable from here
 from .effects import EffectAnalysis
 from .effects import PartialDependence, pd_grid  # noqa: F401
+from .effects import AccumulatedEffects, ale_edges  # noqa: F401    (accumulated local effects: the same module)
 from .effects import ShapleyValues, shapley_table  # noqa: F401    (Shapley attributions: the same module)
 # the classification report lives in report.py; the result tuple and its host helpers are importable from here
 from .report import ReportAnalysis
