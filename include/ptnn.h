@@ -1610,6 +1610,76 @@ typedef struct ptnn_modes_spec {
 
 int ptnn_modes(ptnn_handle *h, const ptnn_modes_spec *spec);
 
+/* ---- posterior compression: a small ensemble that stands for all the sampled nets (nothing in the reference) ----
+ * Kernel herding with the energy-distance kernel ("support points", Mak & Joseph 2018; Chen, Welling & Smola 2010) on the
+ * function-space distance of ptnn_modes; DESIGN.md section 34.
+ * Samples: exactly those of ptnn_modes -- sources 1 (the trace), 2 (host vectors w with multiplicity) and 3 (a host matrix values
+ *   [n_w, n_a]).  A selection yields U distinct samples with integer counts c_u, M = sum c_u, and item_sample maps every selected
+ *   item to its distinct sample.  Samples with c_u = 0 are absent: never chosen, counted nowhere.
+ * sq[u, v]: ptnn_modes' matrix, formed by the same kernels (modes_outputs_kernel, modes_dist_kernel): the same bits, the same
+ *   PTNN_MODES_MAX_ELEMENTS cap with the same refusal text, the same $PTNN_MODES_SCRATCH_BYTES column blocks.  A non-finite sq among
+ *   the present samples is refused with a text that names the first such sample.
+ * Arithmetic: double throughout, every operation rounded once, none contracted with its neighbour, in the orders given here, so that
+ *   a float64 replay in the same order reproduces every bit.
+ * Distance: d[u, v] = sqrt(sq[u, v]), correctly rounded, taken on the fly (the matrix is not modified).  d / sqrt(n) is the RMS
+ *   output difference of two nets, the unit of posterior_modes.
+ * Mean distance: mu_u = (sum_v (double)c_v d[u, v]) / M over the present v: thread t of 256 adds v = t, t + 256, ... in ascending
+ *   order, the 256 partials go down the LDS tree (pairs i, i + 128; i, i + 64; ...; 0, 1).  mu of an absent sample is 0.
+ * Spread: D0 = (sum_u (double)c_u mu_u) / M, the rows added in ascending order: the energy-distance self term of the full weighted
+ *   sample, E d(X, X').
+ * Herding, m picks without replacement among the present samples: r_c = 0; for j = 0 .. m - 1: score_c = mu_c - r_c / (j + 1) over
+ *   the present, not yet chosen c; x_{j+1} = the c with the smallest score, the lowest c on a tie (compared as the order-preserving
+ *   bit map of the signed double, then c); then r_c += d[c, x_{j+1}] for every remaining c.  pick_score[j] = the winning score.
+ * Energy curve, for every prefix n = 1 .. m: musum_n = musum_{n-1} + mu_{x_n}; pair_n = pair_{n-1} + 2 r_{x_n} (r before x_n's own
+ *   column is added); energy_n = ((2 musum_n) / n - pair_n / (n n)) - D0: the energy distance between the n chosen nets with equal
+ *   weights and the full weighted sample.  >= 0 up to rounding; NOT monotone in n.  A random n-subset drawn with replacement has
+ *   expected energy exactly D0 / n.
+ * Subset evaluation: row b of subset_items [n_subsets, subset_size] holds item indices, repeats allowed; its measure is
+ *   (1 / m_b) sum_k delta(item_sample[s_k]).  energy = ((2 sum_k mu) / m_b - (sum_{k, l} d) / (m_b m_b)) - D0; thread t of 256 adds
+ *   k = t, t + 256, ... and the ordered pairs p = t, t + 256, ... -> (p / m_b, p % m_b), ascending, each down the LDS tree.
+ * Outputs, any may be NULL: picks, energy, pick_score [m]; mu, count hold `room` entries of which U = *n_distinct are written;
+ *   d0 [1]; subset_energy [n_subsets]; item_sample, sq_dist, outputs, n_samples, n_distinct exactly as ptnn_modes.
+ * Refused: as ptnn_modes (the cap, M < 1, values together with w, room < n_items, a communicator attached); m < 0 or m > the present
+ *   samples (the text gives both); n_subsets < 0; n_subsets > 0 without subset_items or with subset_size outside [1, 65536]; a
+ *   subset entry outside [0, n_items); a subset that holds an absent sample.
+ * Runs on the handle's stream behind everything queued and returns when done.  Touches no chain state, tape, counter or trace row. */
+typedef struct ptnn_compress_spec {
+    int32_t struct_bytes;         /* = sizeof(ptnn_compress_spec): ABI guard */
+    /* source 1: the trace (used when w == NULL and values == NULL) */
+    const int32_t *replicas;      /* local replica indices, or NULL = all */
+    int32_t n_replicas;           /* entries of replicas (ignored when NULL) */
+    int32_t step0, nsteps, thin;  /* trace rows step0, step0 + thin, ... < step0 + nsteps (thin >= 1) */
+    /* source 2: host vectors */
+    const float *w;               /* [n_w, P] or NULL */
+    const int32_t *multiplicity;  /* [n_w] >= 0, or NULL = 1 each (sources 2 and 3) */
+    int64_t n_w;
+    /* input rows (sources 1 and 2) */
+    int32_t x_source;             /* PTNN_PREDICT_X_HOST | _TRAIN | _TEST */
+    int32_t n_rows;
+    const float *x;               /* [n_rows, n_in] (host rows only) */
+    /* source 3: a host matrix */
+    const float *values;          /* [n_w, n_a] or NULL */
+    int32_t n_a;
+    int32_t m;                    /* picks: 0 <= m <= the present samples */
+    const int32_t *subset_items;  /* [n_subsets, subset_size] item indices, or NULL */
+    int32_t n_subsets, subset_size;
+    int64_t room;                 /* entries that mu, count and item_sample each hold: >= n_items, else refused */
+    /* outputs */
+    int32_t *picks;               /* [m] distinct-sample indices, in herding order */
+    double *energy;               /* [m] */
+    double *pick_score;           /* [m] */
+    double *mu;                   /* [n_items], U written */
+    double *d0;                   /* [1] */
+    double *subset_energy;        /* [n_subsets] */
+    int32_t *count;               /* [n_items], U written */
+    int32_t *item_sample;         /* [n_items] */
+    double *sq_dist;              /* [U, U] packed */
+    float *outputs;               /* [U, n] packed */
+    int64_t *n_samples, *n_distinct;
+} ptnn_compress_spec;
+
+int ptnn_compress(ptnn_handle *h, const ptnn_compress_spec *spec);
+
 /* the HIP stream (hipStream_t) all of this handle's work is queued on: lets the caller order its collectives after the
  * segment / before the swap kernels on the device instead of synchronising the host */
 int ptnn_stream(ptnn_handle *h, void **hip_stream);

@@ -391,6 +391,24 @@ MODES_MAX_ELEMENTS = 1 << 27
 MODES_MAX_DISTINCT = math.isqrt(MODES_MAX_ELEMENTS)      # 11585: the largest U with U * U <= MODES_MAX_ELEMENTS
 
 
+class CompressSpec(C.Structure):
+    """ptnn_compress_spec (include/ptnn.h)."""
+    _fields_ = _SELECTION + [
+        ("w", C.POINTER(C.c_float)), ("multiplicity", C.POINTER(C.c_int32)), ("n_w", C.c_int64),
+        ("x_source", C.c_int32), ("n_rows", C.c_int32), ("x", C.POINTER(C.c_float)),
+        ("values", C.POINTER(C.c_float)), ("n_a", C.c_int32), ("m", C.c_int32),
+        ("subset_items", C.POINTER(C.c_int32)), ("n_subsets", C.c_int32), ("subset_size", C.c_int32),
+        ("room", C.c_int64), ("picks", C.POINTER(C.c_int32)), ("energy", C.POINTER(C.c_double)), ("pick_score", C.POINTER(C.c_double)),
+        ("mu", C.POINTER(C.c_double)), ("d0", C.POINTER(C.c_double)), ("subset_energy", C.POINTER(C.c_double)),
+        ("count", C.POINTER(C.c_int32)), ("item_sample", C.POINTER(C.c_int32)),
+        ("sq_dist", C.POINTER(C.c_double)), ("outputs", C.POINTER(C.c_float)),
+        ("n_samples", C.POINTER(C.c_int64)), ("n_distinct", C.POINTER(C.c_int64)),
+    ]
+
+
+COMPRESS_MAX_SUBSET = 65536              # entries of one evaluated subset (include/ptnn.h: subset_size)
+
+
 class LadderAdaptSpec(C.Structure):
     """ptnn_ladder_adapt_spec (include/ptnn.h)."""
     _fields_ = [("struct_bytes", C.c_int32), ("rounds", C.c_int32), ("kappa0", C.c_double), ("t0", C.c_double)]
@@ -497,6 +515,7 @@ SYMBOLS = {
     "ptnn_uncertainty": (C.c_int, [C.c_void_p, C.POINTER(UncertaintySpec)]),
     "ptnn_influence": (C.c_int, [C.c_void_p, C.POINTER(InfluenceSpec)]),
     "ptnn_modes": (C.c_int, [C.c_void_p, C.POINTER(ModesSpec)]),
+    "ptnn_compress": (C.c_int, [C.c_void_p, C.POINTER(CompressSpec)]),
 }
 
 
@@ -1265,6 +1284,68 @@ class Sampler:
             out[k] = out[k][:U].copy()
         out["item_sample"] = out["item_sample"][:n_items]
         out["spread_sq"] = float(out["spread_sq"][0])
+        if sq_dist:
+            out["sq_dist"] = out["sq_dist"][:U * U].reshape(U, U).copy()
+        if outputs:
+            out["outputs"] = out["outputs"][:U * n].reshape(U, n).copy()
+        return out
+
+    def compress(self, x=None, *, m, subsets=None, values=None, multiplicity=None, sq_dist=False, outputs=False, **source):
+        """ptnn_compress: kernel herding with the energy-distance kernel on ptnn_modes' squared function-space distance of the U
+        distinct selected samples, on the device.  Source, x, values and multiplicity as modes().  m: the picks, 0 <= m <= the
+        present samples (count > 0).  subsets [B, k] int32: item indices (repeats allowed) of B subsets whose energy distance to
+        the full weighted sample is evaluated.  -> dict(picks [m] int32 (distinct-sample indices in herding order), energy [m],
+        pick_score [m], mu [U], d0, subset_energy [B] (None without subsets), all float64 in the units of sqrt(sq); count [U]
+        int32, item_sample [n_items] int32, sq_dist [U, U] float64 and outputs [U, n] float32 on request, n_samples,
+        n_distinct)."""
+        spec, keep = _spec(CompressSpec), []
+        if values is not None:
+            if source.get("w") is not None:
+                raise ValueError("values takes the place of the samples: no w with it")
+            va = _f32(values)
+            if va.ndim != 2 or va.shape[1] < 1:
+                raise ValueError(f"values must be [n_samples, n_a], got shape {va.shape}")
+            keep.append(va)
+            spec.values, spec.n_w, spec.n_a = _ptr(va), va.shape[0], va.shape[1]
+            n_items, n = va.shape[0], va.shape[1]
+            self._multiplicity(spec, keep, multiplicity, (n_items,), "multiplicity must have one entry per sample")
+        else:
+            self._rows(spec, keep, x, "x", (self.cfg.n_in, "n_in columns"))
+            n = spec.n_rows * self.cfg.n_out
+            src = dict(dict(w=None, replicas=None, step0=0, nsteps=None, thin=1), **source)
+            self._samples(spec, keep, multiplicity=multiplicity, unit="vector", **src)
+            if src["w"] is not None:
+                n_items = int(spec.n_w)
+            else:
+                chains = self.R if src["replicas"] is None else int(spec.n_replicas)
+                n_items = max(0, chains * -(-spec.nsteps // max(1, spec.thin)))
+        m = int(m)
+        if m < 0:
+            raise ValueError(f"m = {m} picks: must be >= 0")
+        spec.m = m
+        B = 0
+        if subsets is not None:
+            sub = np.ascontiguousarray(subsets, dtype=np.int32)
+            if sub.ndim != 2 or sub.shape[1] < 1 or sub.shape[1] > COMPRESS_MAX_SUBSET:
+                raise ValueError(f"subsets must be [n_subsets, k] item indices with 1 <= k <= {COMPRESS_MAX_SUBSET}, got shape {sub.shape}")
+            keep.append(sub)
+            B = sub.shape[0]
+            spec.subset_items, spec.n_subsets, spec.subset_size = (_ptr(sub, _ip) if B else None), B, sub.shape[1]
+        room = spec.room = max(1, n_items)
+        big = min(room, MODES_MAX_DISTINCT)                 # sq_dist and outputs come back packed [U, U], [U, n]: U is known after the call
+        out = dict(picks=np.zeros(max(1, m), np.int32), energy=np.zeros(max(1, m), np.float64), pick_score=np.zeros(max(1, m), np.float64),
+                   mu=np.zeros(room, np.float64), d0=np.zeros(1, np.float64), subset_energy=np.zeros(B, np.float64) if B else None,
+                   count=np.zeros(room, np.int32), item_sample=np.zeros(room, np.int32),
+                   sq_dist=np.empty(big * big, np.float64) if sq_dist else None, outputs=np.empty(big * n, np.float32) if outputs else None)
+        _bind(spec, out)
+        out = self._call(self.lib.ptnn_compress, spec, out)
+        U = out["n_distinct"]
+        for k in ("picks", "energy", "pick_score"):
+            out[k] = out[k][:m].copy()
+        for k in ("mu", "count"):
+            out[k] = out[k][:U].copy()
+        out["item_sample"] = out["item_sample"][:n_items]
+        out["d0"] = float(out["d0"][0])
         if sq_dist:
             out["sq_dist"] = out["sq_dist"][:U * U].reshape(U, U).copy()
         if outputs:

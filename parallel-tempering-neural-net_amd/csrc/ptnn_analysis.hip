@@ -1,5 +1,5 @@
 // ptnn_analysis.hip -- the posterior analysis calls of libptnn.so: predict, convergence, rank_convergence, elpd, lfo, forecast, evidence, mbar, calibration,
-// forecast_score, sensitivity, partial_dependence, accumulated_effects, coalition_values, ppc, powerscale, prior_predictive, influence, modes, and the sample-selection path they share.  The shape-independent analysis kernels are defined in this object: it includes them.
+// forecast_score, sensitivity, partial_dependence, accumulated_effects, coalition_values, ppc, powerscale, prior_predictive, influence, modes, compress, and the sample-selection path they share.  The shape-independent analysis kernels are defined in this object: it includes them.
 #include "ptnn_shapes.hpp"                   // PTNN_SHAPES
 #include "ptnn_analysis_device.hpp"          // the per-shape forward kernels and their table, AnalysisShape
 namespace ptnn {
@@ -23,6 +23,7 @@ namespace ptnn {
 #include "ptnn_dev_uncertainty.hpp"          // predictive uncertainty: entropy per sample and its mean per row, variance per column, mean noise
 #include "ptnn_dev_influence.hpp"            // case influence: column moments and the tiled FP64 cross-covariance over the samples
 #include "ptnn_dev_modes.hpp"                // posterior modes: the tiled FP64 all-pairs distance of the samples' outputs, density and parents
+#include "ptnn_dev_compress.hpp"             // posterior compression: mean distances, the herding walk and subset energies on that matrix
 }  // namespace ptnn
 #include "ptnn_host.hpp"
 #include "ptnn_rank_plan.hpp"               // the blocks of ptnn_rank_convergence: host arithmetic, checked on its own
@@ -747,6 +748,122 @@ struct PooledVotes {
     double share(size_t c, long long M) const { return (double)counts[c] / (double)M; }
     void shares(double* vote, long long M) const {
         for (size_t c = 0; vote && c < counts.size(); ++c) vote[c] = share(c, M);
+    }
+};
+
+int modes_cap(long long U) {
+    if (U * U > PTNN_MODES_MAX_ELEMENTS)
+        return fail(-1, "%lld distinct samples: the %lld x %lld distance matrix exceeds 2^27 elements per call; select fewer samples "
+                        "(thin=, chains=)", U, U, U);
+    return 0;
+}
+
+// What ptnn_modes and ptnn_compress share (include/ptnn.h: ptnn_modes): the three sample sources, the distinct samples' outputs
+// F [U][n] and their all-pairs squared distance sq [U][U] (ptnn_dev_modes.hpp), in steps, since the order of the refusals is kept
+// and each call has checks and buffers of its own between them.  Spec: the fields the two specs name alike.
+template <class Spec> struct SampleDistances {
+    const Spec& s;
+    const bool mat;                         // source 3
+    RowsByVectors f;
+    ForwardPlan fwd;
+    int U = 0, cpr = 1;                     // cpr: columns per row of x (source 3: per column of values)
+    const int* d_cnt = nullptr;             // [U] the counts
+    long long rows = 0, n = 0, M = 0, rows_blk = 0;
+    bool want_sq = false, want_out = false;
+    float *d_fx = nullptr, *d_out = nullptr;
+    double* d_sq = nullptr;
+    explicit SampleDistances(const Spec& spec) : s(spec), mat(spec.values != nullptr), f(spec, RankOutputs{0, nullptr, nullptr}) {}
+    // no handle needed
+    int check() {
+        if (mat) {
+            f.src.host = true;
+            if (int rc = check_source(f.src, "samples")) return rc;
+            if (s.n_a < 1) return fail(-1, "n_a = %d must be >= 1", s.n_a);
+            return modes_cap(s.n_w);                            // every host row is a sample
+        }
+        return f.check();
+    }
+    // the samples selected and on the device; `what` names the call
+    int stage(ptnn_handle* h, const char* what) {
+        if (!mat)
+            if (int rc = fit_rows(h, f.rows)) return rc;
+        if (int rc = f.select(h, s.n_samples)) return rc;
+        if (s.room < f.src.n_items)
+            return fail(-1, "room = %lld entries per output but the selection has %lld items", (long long)s.room, f.src.n_items);
+        if (mat) {
+            int* d_cnt_own = nullptr;
+            if (int rc = start_device(h)) return rc;
+            f.U = (int)f.src.n_items;
+            if (int rc = upload_counts(h, f.mem, s.multiplicity, (size_t)f.U, &d_cnt_own)) return rc;
+            if (s.n_distinct) *s.n_distinct = f.U;
+            d_cnt = d_cnt_own;
+        } else {
+            if (int rc = f.stage(h, h->cfg.n_in, s.n_distinct)) return rc;
+            if (int rc = modes_cap(f.U)) return rc;
+            if (int rc = fwd.init(h, what)) return rc;
+            d_cnt = f.d.run_cnt;
+        }
+        U = f.U; cpr = mat ? 1 : h->cfg.n_out;
+        rows = mat ? s.n_a : s.n_rows; n = rows * cpr;
+        M = f.M;
+        return 0;
+    }
+    // the column blocks as ptnn_predict cuts them: fx scratch U x (rows x O) floats under the budget; the matrix lies beside it
+    int alloc(bool sq) {
+        want_sq = sq; want_out = s.outputs && !mat;
+        rows_blk = row_block(scratch_budget("PTNN_MODES_SCRATCH_BYTES"), (size_t)U * sizeof(float) * cpr, rows);
+        if (want_sq || want_out) HIP_TRY(f.mem.alloc(&d_fx, (size_t)rows_blk * cpr * U));
+        if (want_out) HIP_TRY(f.mem.alloc(&d_out, (size_t)U * n));
+        if (want_sq) HIP_TRY(f.mem.alloc(&d_sq, (size_t)U * U));
+        return 0;
+    }
+    // `with_items`: the sample of every item is wanted on the host; queues the forward pass and the matrix, block by block
+    int form(ptnn_handle* h, bool with_items) {
+        hipStream_t st = h->stream;
+        if (int rc = f.items(h, with_items && !mat)) return rc;
+        // the columns [c0, c0 + nc) of the host matrix [U][n_a] as a block [nc][U] on the device
+        std::vector<float> stage;
+        auto host_columns = [&](long long c0, int nc) -> int {
+            stage.resize((size_t)nc * U);
+            for (int c = 0; c < nc; ++c)
+                for (int u = 0; u < U; ++u) stage[(size_t)c * U + u] = s.values[(size_t)u * s.n_a + c0 + c];
+            HIP_TRY(hipMemcpyAsync(d_fx, stage.data(), stage.size() * sizeof(float), hipMemcpyHostToDevice, st));
+            return wait_stream(h);                              // `stage` is written again for the next block
+        };
+        const int T = (U + MODES_TILE - 1) / MODES_TILE;
+        if (!(want_sq || want_out)) return 0;
+        return each_block(rows, rows_blk, [&](long long r0, int nr) -> int {
+            const int nc = nr * cpr;
+            if (mat) {
+                if (int rc = host_columns(r0, nc)) return rc;
+            } else {
+                if (int rc = fwd.run(h, f.d.base, f.d.run_off, f.d_x, f.xs, (int)r0, nr, U, d_fx)) return rc;
+            }
+            if (want_out) {
+                const long long cells = (long long)nc * U;
+                HIP_TRY(launch(modes_outputs_kernel, dim3((unsigned)((cells + MODES_THREADS - 1) / MODES_THREADS)), dim3(MODES_THREADS), 0, st,
+                               d_fx, n, r0 * cpr, nc, U, d_out));
+            }
+            if (want_sq) {
+                ModesDist da{d_fx, nc, U, T, r0 == 0 ? 1 : 0, d_sq};
+                HIP_TRY(launch(modes_dist_kernel, dim3((unsigned)(T * (T + 1) / 2)), dim3(MODES_THREADS), 0, st, da));
+            }
+            return 0;
+        });
+    }
+    // the sample of item k (after the wait that follows form(with_items))
+    int sample_of(long long k) const { return mat ? (int)k : f.item_run[(size_t)k]; }
+    // count, sq_dist and outputs queued to the caller
+    int fetch_common(hipStream_t st) const {
+        HIP_TRY(fetch((int*)s.count, d_cnt, (size_t)U, st));
+        HIP_TRY(fetch(s.sq_dist, (const double*)d_sq, (size_t)U * U, st));
+        if (want_out) HIP_TRY(fetch(s.outputs, (const float*)d_out, (size_t)U * n, st));
+        return 0;
+    }
+    // behind the last wait: the outputs that are host copies
+    void finish() const {
+        if (s.outputs && mat) std::copy(s.values, s.values + (size_t)U * n, s.outputs);
+        for (long long k = 0; s.item_sample && k < f.src.n_items; ++k) s.item_sample[k] = (int32_t)sample_of(k);
     }
 };
 }  // namespace
@@ -3647,69 +3764,30 @@ int ptnn_influence(ptnn_handle* h, const ptnn_influence_spec* spec) {
 }
 
 // ---- posterior modes (ptnn_dev_modes.hpp) ----
-static int modes_cap(long long U) {
-    if (U * U > PTNN_MODES_MAX_ELEMENTS)
-        return fail(-1, "%lld distinct samples: the %lld x %lld distance matrix exceeds 2^27 elements per call; select fewer samples "
-                        "(thin=, chains=)", U, U, U);
-    return 0;
-}
-
 int ptnn_modes(ptnn_handle* h, const ptnn_modes_spec* spec) {
     // argument checks first: none of them needs the handle or a device
     if (int rc = check_spec(spec, "ptnn_modes_spec")) return rc;
     const ptnn_modes_spec& s = *spec;
-    const bool mat = s.values != nullptr;                       // source 3
-    if (mat && s.w) return fail(-1, "give host vectors w or a host matrix values, not both");
+    if (s.values && s.w) return fail(-1, "give host vectors w or a host matrix values, not both");
     if (!std::isfinite(s.near_sq) || s.near_sq < 0.0) return fail(-1, "near_sq = %g must be a finite number >= 0", s.near_sq);
-    RowsByVectors f(s, RankOutputs{0, nullptr, nullptr});
-    if (mat) {
-        f.src.host = true;
-        if (int rc = check_source(f.src, "samples")) return rc;
-        if (s.n_a < 1) return fail(-1, "n_a = %d must be >= 1", s.n_a);
-        if (int rc = modes_cap(s.n_w)) return rc;               // every host row is a sample
-    } else {
-        if (int rc = f.check()) return rc;
-    }
+    SampleDistances<ptnn_modes_spec> sd(s);
+    if (int rc = sd.check()) return rc;
     if (int rc = check_handle(h, "ptnn_modes")) return rc;
-    const int I = h->cfg.n_in, O = h->cfg.n_out;
-    if (!mat)
-        if (int rc = fit_rows(h, f.rows)) return rc;
-    if (int rc = f.select(h, s.n_samples)) return rc;
-    if (s.room < f.src.n_items)
-        return fail(-1, "room = %lld entries per output but the selection has %lld items", (long long)s.room, f.src.n_items);
-
-    ForwardPlan fwd;
-    int* d_cnt_own = nullptr;
-    if (mat) {
-        if (int rc = start_device(h)) return rc;
-        f.U = (int)f.src.n_items;
-        if (int rc = upload_counts(h, f.mem, s.multiplicity, (size_t)f.U, &d_cnt_own)) return rc;
-        if (s.n_distinct) *s.n_distinct = f.U;
-    } else {
-        if (int rc = f.stage(h, I, s.n_distinct)) return rc;
-        if (int rc = modes_cap(f.U)) return rc;
-        if (int rc = fwd.init(h, "posterior modes")) return rc;
-    }
+    if (int rc = sd.stage(h, "posterior modes")) return rc;
     hipStream_t st = h->stream;
-    DeviceScratch& mem = f.mem;
-    const int U = f.U, cpr = mat ? 1 : O;                       // columns per row of x (source 3: per column of values)
-    const int* d_cnt = mat ? d_cnt_own : f.d.run_cnt;
-    const long long rows = mat ? s.n_a : s.n_rows, n = rows * cpr;
-    const long long M = f.M;
+    DeviceScratch& mem = sd.f.mem;
+    const int U = sd.U;
+    const int* d_cnt = sd.d_cnt;
+    const long long M = sd.M;
     const bool want_parent = s.parent || s.delta_sq;
     const bool want_sq = want_parent || s.rho || s.spread_sq || s.sq_dist;
-    const bool want_out = s.outputs && !mat;
-    // the column blocks as ptnn_predict cuts them: fx scratch U x (rows x O) floats under the budget; the matrix lies beside it
-    const long long rows_blk = row_block(scratch_budget("PTNN_MODES_SCRATCH_BYTES"), (size_t)U * sizeof(float) * cpr, rows);
-    float *d_fx = nullptr, *d_out = nullptr;
-    double *d_sq = nullptr, *d_max = nullptr, *d_part = nullptr, *d_spread = nullptr, *d_delta = nullptr;
+    double *d_max = nullptr, *d_part = nullptr, *d_spread = nullptr, *d_delta = nullptr;
     long long *d_rho = nullptr, *d_row_bad = nullptr, *d_bad = nullptr;
     unsigned int* d_ticket = nullptr;
     int* d_parent = nullptr;
-    if (want_sq || want_out) HIP_TRY(mem.alloc(&d_fx, (size_t)rows_blk * cpr * U));
-    if (want_out) HIP_TRY(mem.alloc(&d_out, (size_t)U * n));
+    if (int rc = sd.alloc(want_sq)) return rc;
+    const double* d_sq = sd.d_sq;
     if (want_sq) {
-        HIP_TRY(mem.alloc(&d_sq, (size_t)U * U));
         HIP_TRY(mem.alloc(&d_rho, (size_t)U));
         HIP_TRY(mem.alloc(&d_max, (size_t)U));
         HIP_TRY(mem.alloc(&d_part, (size_t)U));
@@ -3723,37 +3801,7 @@ int ptnn_modes(ptnn_handle* h, const ptnn_modes_spec* spec) {
         HIP_TRY(mem.alloc(&d_parent, (size_t)U));
         HIP_TRY(mem.alloc(&d_delta, (size_t)U));
     }
-    if (int rc = f.items(h, s.item_sample != nullptr && !mat)) return rc;
-
-    // the columns [c0, c0 + nc) of the host matrix [U][n_a] as a block [nc][U] on the device
-    std::vector<float> stage;
-    auto host_columns = [&](long long c0, int nc) -> int {
-        stage.resize((size_t)nc * U);
-        for (int c = 0; c < nc; ++c)
-            for (int u = 0; u < U; ++u) stage[(size_t)c * U + u] = s.values[(size_t)u * s.n_a + c0 + c];
-        HIP_TRY(hipMemcpyAsync(d_fx, stage.data(), stage.size() * sizeof(float), hipMemcpyHostToDevice, st));
-        return wait_stream(h);                                  // `stage` is written again for the next block
-    };
-    const int T = (U + MODES_TILE - 1) / MODES_TILE;
-    if (want_sq || want_out)
-        if (int rc = each_block(rows, rows_blk, [&](long long r0, int nr) -> int {
-            const int nc = nr * cpr;
-            if (mat) {
-                if (int rc = host_columns(r0, nc)) return rc;
-            } else {
-                if (int rc = fwd.run(h, f.d.base, f.d.run_off, f.d_x, f.xs, (int)r0, nr, U, d_fx)) return rc;
-            }
-            if (want_out) {
-                const long long cells = (long long)nc * U;
-                HIP_TRY(launch(modes_outputs_kernel, dim3((unsigned)((cells + MODES_THREADS - 1) / MODES_THREADS)), dim3(MODES_THREADS), 0, st,
-                               d_fx, n, r0 * cpr, nc, U, d_out));
-            }
-            if (want_sq) {
-                ModesDist da{d_fx, nc, U, T, r0 == 0 ? 1 : 0, d_sq};
-                HIP_TRY(launch(modes_dist_kernel, dim3((unsigned)(T * (T + 1) / 2)), dim3(MODES_THREADS), 0, st, da));
-            }
-            return 0;
-        })) return rc;
+    if (int rc = sd.form(h, s.item_sample != nullptr)) return rc;
     long long bad[2] = {0, -1};
     if (want_sq) {
         ModesDensity na{d_sq, d_cnt, U, s.near_sq, (double)M * (double)M, d_rho, d_max, d_part, d_row_bad, d_ticket, d_spread, d_bad};
@@ -3767,15 +3815,98 @@ int ptnn_modes(ptnn_handle* h, const ptnn_modes_spec* spec) {
     HIP_TRY(fetch((long long*)s.rho, d_rho, (size_t)U, st));
     HIP_TRY(fetch(s.delta_sq, d_delta, (size_t)U, st));
     HIP_TRY(fetch((int*)s.parent, d_parent, (size_t)U, st));
-    HIP_TRY(fetch((int*)s.count, d_cnt, (size_t)U, st));
     HIP_TRY(fetch(s.spread_sq, d_spread, 1, st));
-    HIP_TRY(fetch(s.sq_dist, d_sq, (size_t)U * U, st));
-    if (want_out) HIP_TRY(fetch(s.outputs, d_out, (size_t)U * n, st));
+    if (int rc = sd.fetch_common(st)) return rc;
     if (int rc = wait_stream(h)) return rc;
     if (bad[0] != 0)
         return fail(-1, "%lld squared distances are not finite: sample %lld is the first whose outputs are NaN or infinite", bad[0], bad[1]);
-    if (s.outputs && mat) std::copy(s.values, s.values + (size_t)U * n, s.outputs);
-    for (long long k = 0; s.item_sample && k < f.src.n_items; ++k) s.item_sample[k] = mat ? (int32_t)k : f.item_run[(size_t)k];
+    sd.finish();
+    return 0;
+}
+
+// ---- posterior compression (ptnn_dev_compress.hpp) ----
+int ptnn_compress(ptnn_handle* h, const ptnn_compress_spec* spec) {
+    // argument checks first: none of them needs the handle or a device
+    if (int rc = check_spec(spec, "ptnn_compress_spec")) return rc;
+    const ptnn_compress_spec& s = *spec;
+    if (s.values && s.w) return fail(-1, "give host vectors w or a host matrix values, not both");
+    if (s.m < 0) return fail(-1, "m = %d picks: must be >= 0", s.m);
+    if (s.n_subsets < 0) return fail(-1, "n_subsets = %d must be >= 0", s.n_subsets);
+    if (s.n_subsets > 0) {
+        if (!s.subset_items) return fail(-1, "n_subsets = %d but subset_items is NULL", s.n_subsets);
+        if (s.subset_size < 1 || s.subset_size > 65536) return fail(-1, "subset_size = %d outside [1, 65536]", s.subset_size);
+    }
+    SampleDistances<ptnn_compress_spec> sd(s);
+    if (int rc = sd.check()) return rc;
+    if (int rc = check_handle(h, "ptnn_compress")) return rc;
+    if (int rc = sd.stage(h, "posterior compression")) return rc;
+    const long long n_items = sd.f.src.n_items, n_sub = (long long)s.n_subsets * s.subset_size;
+    for (long long k = 0; k < n_sub; ++k)
+        if (s.subset_items[k] < 0 || s.subset_items[k] >= n_items)
+            return fail(-1, "subset %lld holds item %d outside [0, %lld)", k / s.subset_size, s.subset_items[k], n_items);
+    hipStream_t st = h->stream;
+    DeviceScratch& mem = sd.f.mem;
+    const int U = sd.U;
+    const int* d_cnt = sd.d_cnt;
+    // the present samples, before any further allocation: the counts are on the device since the selection
+    std::vector<int> cnt((size_t)U);
+    HIP_TRY(hipMemcpyAsync(cnt.data(), d_cnt, (size_t)U * sizeof(int), hipMemcpyDeviceToHost, st));
+    if (int rc = wait_stream(h)) return rc;
+    const long long present = (long long)std::count_if(cnt.begin(), cnt.end(), [](int c) { return c != 0; });
+    if (s.m > present) return fail(-1, "m = %d picks but the selection has %lld present distinct samples", s.m, present);
+    const bool want_sq = s.m > 0 || s.n_subsets > 0 || s.mu || s.d0 || s.sq_dist;
+    double *d_mu = nullptr, *d_part = nullptr, *d_d0 = nullptr, *d_energy = nullptr, *d_score = nullptr, *d_sub = nullptr;
+    long long *d_row_bad = nullptr, *d_bad = nullptr;
+    unsigned int* d_ticket = nullptr;
+    int *d_picks = nullptr, *d_items = nullptr;
+    if (int rc = sd.alloc(want_sq)) return rc;
+    if (want_sq) {
+        HIP_TRY(mem.alloc(&d_mu, (size_t)U));
+        HIP_TRY(mem.alloc(&d_part, (size_t)U));
+        HIP_TRY(mem.alloc(&d_row_bad, (size_t)U));
+        HIP_TRY(mem.alloc(&d_d0, 1));
+        HIP_TRY(mem.alloc(&d_bad, 2));
+        HIP_TRY(mem.alloc(&d_ticket, 1));
+        HIP_TRY(hipMemsetAsync(d_ticket, 0, sizeof(unsigned int), st));
+        HIP_TRY(mem.alloc(&d_picks, (size_t)s.m));
+        HIP_TRY(mem.alloc(&d_energy, (size_t)s.m));
+        HIP_TRY(mem.alloc(&d_score, (size_t)s.m));
+        HIP_TRY(mem.alloc(&d_sub, (size_t)s.n_subsets));
+    }
+    if (int rc = sd.form(h, s.item_sample != nullptr || s.n_subsets > 0)) return rc;
+    long long bad[2] = {0, -1};
+    if (want_sq) {
+        CompressMean ma{sd.d_sq, d_cnt, U, (double)sd.M, d_mu, d_part, d_row_bad, d_ticket, d_d0, d_bad};
+        HIP_TRY(launch(compress_mean_kernel, dim3((unsigned)U), dim3(COMPRESS_THREADS), 0, st, ma));
+        HIP_TRY(hipMemcpyAsync(bad, d_bad, sizeof bad, hipMemcpyDeviceToHost, st));
+        if (int rc = wait_stream(h)) return rc;                 // the items' samples are on the host now, too
+        if (bad[0] != 0)
+            return fail(-1, "%lld squared distances are not finite: sample %lld is the first whose outputs are NaN or infinite", bad[0], bad[1]);
+    }
+    if (s.n_subsets > 0) {
+        for (long long k = 0; k < n_sub; ++k)
+            if (cnt[(size_t)sd.sample_of(s.subset_items[k])] == 0)
+                return fail(-1, "subset %lld holds item %d, whose sample %d is absent (count 0)", k / s.subset_size, s.subset_items[k],
+                            sd.sample_of(s.subset_items[k]));
+        HIP_TRY(mem.upload(&d_items, (const int*)s.subset_items, (size_t)n_sub, st));
+        CompressSubset sa{sd.d_sq, d_mu, d_d0, sd.mat ? nullptr : sd.f.d.item_run, d_items, U, s.subset_size, d_sub};
+        HIP_TRY(launch(compress_subset_kernel, dim3((unsigned)s.n_subsets), dim3(COMPRESS_THREADS), 0, st, sa));
+    }
+    if (s.m > 0) {
+        CompressHerd ha{sd.d_sq, d_cnt, d_mu, d_d0, U, s.m, d_picks, d_energy, d_score};
+        HIP_TRY(launch(compress_herd_kernel, dim3(1), dim3(COMPRESS_HERD_THREADS), 0, st, ha));
+    }
+    if (s.m > 0) {
+        HIP_TRY(fetch((int*)s.picks, (const int*)d_picks, (size_t)s.m, st));
+        HIP_TRY(fetch(s.energy, (const double*)d_energy, (size_t)s.m, st));
+        HIP_TRY(fetch(s.pick_score, (const double*)d_score, (size_t)s.m, st));
+    }
+    HIP_TRY(fetch(s.mu, (const double*)d_mu, (size_t)U, st));
+    HIP_TRY(fetch(s.d0, (const double*)d_d0, 1, st));
+    if (s.n_subsets > 0) HIP_TRY(fetch(s.subset_energy, (const double*)d_sub, (size_t)s.n_subsets, st));
+    if (int rc = sd.fetch_common(st)) return rc;
+    if (int rc = wait_stream(h)) return rc;                     // also keeps subset_items alive until its copy is done
+    sd.finish();
     return 0;
 }
 

@@ -49,6 +49,9 @@ from .influence import CaseInfluence, influence_flagged  # noqa: F401
 # posterior modes live in modes.py; the result tuple and its host helpers are importable from here
 from .modes import ModesAnalysis
 from .modes import PosteriorModes, chain_hops, mode_labels, modes_stuck  # noqa: F401
+# posterior compression lives in compress.py; the result tuple and its host helpers are importable from here
+from .compress import CompressAnalysis
+from .compress import PosteriorCompression, moment_match, thinned_items  # noqa: F401
 # MBAR over every rung lives in rungs.py; the result tuple and its host helpers are importable from here
 from .rungs import RungAnalysis
 from .rungs import RungWeights, mbar_compare, mbar_covariance, redraw_eta  # noqa: F401
@@ -151,7 +154,7 @@ def overlap_cuts(S, swap_interval, chunks):
 
 
 class ParallelTemperingBase(PosteriorAnalysis, PriorAnalysis, EffectAnalysis, ReportAnalysis, UncertaintyAnalysis, InfluenceAnalysis,
-                            ModesAnalysis, RungAnalysis, VerificationAnalysis):
+                            ModesAnalysis, CompressAnalysis, RungAnalysis, VerificationAnalysis):
     task = None                       # set by the two drop-in subclasses
     rmse_fmt = None                   # REG '%1.8f' (REG:462-464), CLS '%1.2f' (CLS:473-475)
 
