@@ -1,5 +1,10 @@
-// ptnn_analysis.hip -- the posterior analysis calls of libptnn.so: predict, convergence, rank_convergence, elpd, lfo, forecast, evidence, mbar, calibration,
-// forecast_score, sensitivity, partial_dependence, accumulated_effects, coalition_values, ppc, powerscale, prior_predictive, influence, modes, compress, and the sample-selection path they share.  The shape-independent analysis kernels are defined in this object: it includes them.
+// ptnn_analysis.hip -- the 22 posterior analysis calls of libptnn.so: predict, sensitivity, partial_dependence, accumulated_effects,
+// coalition_values, convergence, rank_convergence, elpd, lfo, forecast, evidence, mbar, calibration, forecast_score, ppc, powerscale,
+// prior_predictive, class_report, uncertainty, influence, modes, compress, with the sample-selection path they share (SampleSource,
+// distinct_samples) and their frames: RowsByVectors (input rows x weight vectors: the eight calls that read w and the eight scored
+// calls that read (w, eta)), Columns and SignedColumns (summaries per column), MixtureColumns (calibration, forecast_score),
+// SampleDistances (modes, compress), RungLayout and EvidEval (evidence, mbar).  The shape-independent analysis kernels are defined
+// in this object: it includes them.
 #include "ptnn_shapes.hpp"                   // PTNN_SHAPES
 #include "ptnn_analysis_device.hpp"          // the per-shape forward kernels and their table, AnalysisShape
 namespace ptnn {
@@ -328,6 +333,9 @@ struct RowSource {
     int n;
     const char *field, *prefix, *arg, *count;   // names in the messages: "x_source", "PTNN_PREDICT_X", "x", "n_rows"
 };
+template <class Spec> RowSource x_rows(const Spec& s) {     // the rows most specs name alike
+    return RowSource{s.x_source, s.x, s.n_rows, "x_source", "PTNN_PREDICT_X", "x", "n_rows"};
+}
 int check_rows(const RowSource& r) {        // no handle needed
     if (r.source != PTNN_PREDICT_X_HOST && r.source != PTNN_PREDICT_X_TRAIN && r.source != PTNN_PREDICT_X_TEST)
         return fail(-1, "%s = %d is not %s_HOST, _TRAIN or _TEST", r.field, r.source, r.prefix);
@@ -517,34 +525,6 @@ struct RankOutputs {
     }
 };
 
-// The pointwise log-likelihood of ptnn_elpd and ptnn_lfo (one Spec's fields are the other's): trace rows, host vectors (w, eta), or
-// a host loglik [n_w][n_rows].  The argument checks the two share, in three parts, since the order of the refusals is kept and
-// ptnn_lfo has checks of its own between them.
-template <class Spec> int pointwise_source(const Spec& s, const SampleSource& src) {
-    if (s.loglik && s.w) return fail(-1, "give host vectors w or a host loglik, not both");
-    if (int rc = check_r_eff(s.r_eff)) return rc;
-    if (int rc = check_source(src, "samples", true, "loglik")) return rc;
-    if (s.n_rows < 1) return fail(-1, "n_rows = %d must be >= 1", s.n_rows);
-    return 0;
-}
-template <class Spec> int pointwise_rows(const Spec& s, SampleSource& src, const RowSource& rows) {   // ends with the host samples counted
-    if (!s.loglik)
-        if (int rc = check_rows(rows)) return rc;
-    if (s.loglik && s.loglik_out) return fail(-1, "loglik_out: the log-likelihood is the input of this source");
-    if (int rc = count_host_samples(src)) return rc;
-    if (s.loglik)
-        for (long long k = 0; k < src.n_items * s.n_rows; ++k)
-            if (!std::isfinite(s.loglik[k])) return fail(-1, "loglik[%lld, %lld] = %g is not finite", k / s.n_rows, k % s.n_rows, s.loglik[k]);
-    return 0;
-}
-template <class Spec> int pointwise_fit(const ptnn_handle* h, const Spec& s, const SampleSource& src, const RowSource& rows) {  // with the handle
-    const int I = h->cfg.n_in, O = h->cfg.n_out;
-    if (int rc = need_eta(h, src)) return rc;
-    if (s.loglik) return 0;
-    if (int rc = fit_rows(h, rows)) return rc;
-    if (s.x_source == PTNN_PREDICT_X_HOST && h->cfg.task != PTNN_TASK_REG) return check_labels(s.x, s.n_rows, I, O);
-    return 0;
-}
 // the counts of n host samples that are each their own entry, on the device: their multiplicities, or ones
 int upload_counts(ptnn_handle* h, DeviceScratch& mem, const int32_t* multiplicity, size_t n, int** d_cnt) {
     std::vector<int32_t> ones(multiplicity ? 0 : n, 1);
@@ -577,52 +557,135 @@ int loglik_rows(ptnn_handle* h, const ForwardPlan& fwd, const Distinct& d, const
     return loglik_block(h, ra, nr);
 }
 
-// The frame of the calls that take input rows x and weight vectors w -- predict, sensitivity, partial_dependence, coalition_values,
-// class_report -- in three steps, since the order of the refusals is kept and every call has checks of its own between them: the
-// checks before the handle, the samples selected with the handle, the rows and the distinct samples on the device.
+// The frame of the calls that take input rows x and weight vectors w, in three steps, since the order of the refusals is kept and
+// every call has checks of its own between them: the checks before the handle, the samples selected with the handle, the rows and
+// the distinct samples on the device.  Two kinds of call stand on it.  predict, sensitivity, partial_dependence,
+// accumulated_effects, coalition_values, class_report, modes and compress read vectors w: check(), select(), stage().  The scored
+// calls -- elpd, lfo, calibration, forecast_score, ppc, powerscale, uncertainty, influence -- read samples (w, eta) and mostly a
+// target column behind the inputs: their host items are counted before the handle, so they name the parts of check() one by one
+// (check_source(), ::check_rows(rows), count_host()) around their own checks, then fit(), select() and stage() alike.
 struct RowsByVectors {
     SampleSource src;
     RowSource rows;
     RankOutputs rk, rk2;                    // rk2: the ranks of a second quantity, for the calls that have one
+    const bool scored = false;              // a scored call: (w, eta) samples, the host items counted before the handle
+    bool eta = false, merge = true;         // stage: distinct_samples' flags; a scored call sets them first
+    bool started = false;
     long long M = 0;                        // select: the samples, multiplicities counted
     DeviceScratch mem;                      // stage: every buffer of the call
     const float* d_x = nullptr;             // stage: row k at d_x + k * xs
     int xs = 0, U = 0;
     Distinct d;
     std::vector<int> item_run;              // items: the sample of every item, for the selection-order outputs
+    ForwardPlan fwd;                        // forward: the forward pass and its scratch d_fx [rows_blk * O][U]
+    long long rows_blk = 0;
+    float* d_fx = nullptr;
     template <class Spec> RowsByVectors(const Spec& s, RankOutputs rk, RankOutputs rk2 = RankOutputs{0, nullptr, nullptr})
-        : src(source_of(s, s.w != nullptr, nullptr)), rows{s.x_source, s.x, s.n_rows, "x_source", "PTNN_PREDICT_X", "x", "n_rows"},
-          rk(rk), rk2(rk2) {}
+        : src(source_of(s, s.w != nullptr, nullptr)), rows(x_rows(s)), rk(rk), rk2(rk2) {}
+    // a scored call; `host`: host items -- vectors w, or the call's third source
+    template <class Spec> RowsByVectors(const Spec& s, const RowSource& rows, bool host, RankOutputs rk = RankOutputs{0, nullptr, nullptr})
+        : src(source_of(s, host, s.eta)), rows(rows), rk(rk), rk2{0, nullptr, nullptr}, scored(true) {}
     // no handle needed; `one_grid`: the rows are one dimension of a grid of WAVE-row work-groups
     int check(bool one_grid = false) const {
-        if (int rc = check_source(src, "vectors")) return rc;
+        if (int rc = ::check_source(src, "vectors")) return rc;
         if (int rc = check_rows(rows)) return rc;
         if (rows.n < 1) return fail(-1, "n_rows = %d must be >= 1", rows.n);
         if (one_grid && rows.n > 65535 * WAVE) return fail(-1, "n_rows = %d: at most 65535 x 64 rows per call", rows.n);
         if (int rc = rk.check()) return rc;
         return rk2.check();
     }
-    int select(const ptnn_handle* h, int64_t* n_samples) {
-        if (int rc = select_samples(h, src, false)) return rc;
+    int check_source(const char* third = nullptr) const { return ::check_source(src, "samples", true, third); }
+    int count_host() { return count_host_samples(src); }
+    // with the handle: a regression's host vectors bring eta, the rows are the data set's
+    int fit(const ptnn_handle* h, bool with_rows = true) const {
+        if (int rc = need_eta(h, src)) return rc;
+        return with_rows ? fit_rows(h, rows) : 0;
+    }
+    int select(const ptnn_handle* h, int64_t* n_samples, const char* needs_two = nullptr) {
+        if (int rc = select_samples(h, src, scored, needs_two)) return rc;
         M = src.M;
         if (int rc = rk.check_values(M)) return rc;
         if (int rc = rk2.check_values(M)) return rc;
         if (n_samples) *n_samples = M;
         return 0;
     }
-    // rows of `width` floats; `uploads` queues the call's own tables between the rows and the run-length pass
+    // the device work starts once: stage() starts it, or a call with buffers or a source of its own before the rows
+    int start(ptnn_handle* h) { return started ? 0 : (started = true, start_device(h)); }
+    // rows of `width` floats (0: none); `uploads` queues the call's own tables between the rows and the run-length pass
     template <class F> int stage(ptnn_handle* h, int width, int64_t* n_distinct, F uploads) {
-        if (int rc = start_device(h)) return rc;
-        if (int rc = upload_rows(h, mem, rows, width, &d_x, &xs)) return rc;
+        if (int rc = start(h)) return rc;
+        if (width)
+            if (int rc = upload_rows(h, mem, rows, width, &d_x, &xs)) return rc;
         if (int rc = uploads()) return rc;
-        if (int rc = distinct_samples(h, mem, src, false, true, &d)) return rc;
+        if (int rc = distinct_samples(h, mem, src, eta, merge, &d)) return rc;
         U = d.U;
         if (n_distinct) *n_distinct = U;
         return 0;
     }
     int stage(ptnn_handle* h, int width, int64_t* n_distinct) { return stage(h, width, n_distinct, [] { return 0; }); }
     int items(ptnn_handle* h, bool wanted) { return wanted ? item_runs(h, d, src.n_items, &item_run) : 0; }
+    // The forward scratch: blocks of the `n` rows under $budget_var -- `part` of it, at `row_bytes` per row, the fp32 outputs and
+    // what the call keeps beside them -- and the plan; `what` names the call
+    int forward(ptnn_handle* h, const char* budget_var, size_t part, size_t row_bytes, long long n, const char* what) {
+        rows_blk = row_block(scratch_budget(budget_var) / part, row_bytes, n);
+        HIP_TRY(mem.alloc(&d_fx, (size_t)rows_blk * h->cfg.n_out * U));
+        return fwd.init(h, what);
+    }
+    // the blocks of rows [0, n), ascending: the forward pass of [r0, r0 + nr) into d_fx, then body(r0, nr)
+    template <class F> int each_rows(ptnn_handle* h, long long n, F body) {
+        return each_block(n, rows_blk, [&](long long r0, int nr) -> int {
+            if (int rc = fwd.run(h, d.base, d.run_off, d_x, xs, (int)r0, nr, U, d_fx)) return rc;
+            return body(r0, nr);
+        });
+    }
 };
+
+// The pointwise log-likelihood of ptnn_elpd and ptnn_lfo (one Spec's fields are the other's): the frame's sources -- trace rows or
+// host vectors (w, eta) -- or a host loglik [n_w][n_rows], a branch of the two calls' own.  The argument checks they share, in three
+// parts, since the order of the refusals is kept and ptnn_lfo has checks of its own between them.
+template <class Spec> int pointwise_source(const Spec& s, const RowsByVectors& f) {
+    if (s.loglik && s.w) return fail(-1, "give host vectors w or a host loglik, not both");
+    if (int rc = check_r_eff(s.r_eff)) return rc;
+    if (int rc = f.check_source("loglik")) return rc;
+    if (s.n_rows < 1) return fail(-1, "n_rows = %d must be >= 1", s.n_rows);
+    return 0;
+}
+template <class Spec> int pointwise_rows(const Spec& s, RowsByVectors& f) {   // ends with the host samples counted
+    if (!s.loglik)
+        if (int rc = check_rows(f.rows)) return rc;
+    if (s.loglik && s.loglik_out) return fail(-1, "loglik_out: the log-likelihood is the input of this source");
+    if (int rc = f.count_host()) return rc;
+    if (s.loglik)
+        for (long long k = 0; k < f.src.n_items * s.n_rows; ++k)
+            if (!std::isfinite(s.loglik[k])) return fail(-1, "loglik[%lld, %lld] = %g is not finite", k / s.n_rows, k % s.n_rows, s.loglik[k]);
+    return 0;
+}
+template <class Spec> int pointwise_fit(const ptnn_handle* h, const Spec& s, const RowsByVectors& f) {  // with the handle
+    if (int rc = f.fit(h, !s.loglik)) return rc;
+    if (!s.loglik && s.x_source == PTNN_PREDICT_X_HOST && h->cfg.task != PTNN_TASK_REG)
+        return check_labels(s.x, s.n_rows, h->cfg.n_in, h->cfg.n_out);
+    return 0;
+}
+// The frame's sources on the device: rows with their target, the distinct (w, eta) samples, the forward scratch under `part` of
+// $budget_var -- U x (rows x O) floats, + U x rows doubles for loglik_out -- and the sample of every item for loglik_out -> ra
+template <class Spec>
+int pointwise_stage(ptnn_handle* h, const Spec& s, RowsByVectors& f, const char* budget_var, size_t part, const char* what, ElpdRed* ra) {
+    const int I = h->cfg.n_in, O = h->cfg.n_out;
+    double* d_llb = nullptr;
+    f.eta = true;
+    if (int rc = f.stage(h, I + 1, s.n_distinct)) return rc;
+    if (int rc = f.forward(h, budget_var, part, (size_t)f.U * (sizeof(float) * O + (s.loglik_out ? sizeof(double) : 0)), s.n_rows, what)) return rc;
+    if (s.loglik_out) HIP_TRY(f.mem.alloc(&d_llb, (size_t)f.rows_blk * f.U));
+    if (int rc = f.items(h, s.loglik_out != nullptr)) return rc;
+    ra->mode = h->cfg.task == PTNN_TASK_REG ? ELPD_REG : ELPD_CLS;
+    ra->fx = f.d_fx; ra->eta = f.d.run_eta; ra->y = f.d_x + I; ra->ys = f.xs; ra->cnt = f.d.run_cnt; ra->U = f.U; ra->ll_out = d_llb;
+    return 0;
+}
+// loglik_out of the block of `nr` rows from r0 that `ra` names, in the selection's order
+template <class Spec> int pointwise_out(ptnn_handle* h, const Spec& s, const RowsByVectors& f, const ElpdRed& ra, long long r0, int nr) {
+    if (int rc = loglik_block(h, ra, nr)) return rc;
+    return scatter_samples(h, ra.ll_out, nr, ra.U, f.item_run, f.src.weights(), s.loglik_out, (size_t)s.n_rows, (size_t)r0);
+}
 
 // The columns of such a call, `ncols` in all, a block fx [nc][U] at a time: their weighted mean and the order statistics f.rk over the
 // samples, and the values of every selected sample in the selection's order.  An output costs device work only when its pointer
@@ -732,6 +795,96 @@ struct SignedColumns {
         HIP_TRY(fetch(sq_mean, d_sq_mean, (size_t)C, st));
         HIP_TRY(fetch(abs_order_stats, f.rk2.d_stats, (size_t)f.rk2.n * C, st));
         return wait_stream(h);
+    }
+};
+
+// The columns of the predictive mixture (ptnn_dev_calibration.hpp) that ptnn_calibration makes of a regression's data rows and
+// ptnn_forecast_score of origins x steps: per column the PIT, mean, sd and quantiles of sum_u c_u N(mu_u, tau_u^2) / S, and its
+// CRPS with the all-pairs term.  Spec: the fields the two specs name alike.  With `forecast` the observations are a table of
+// their own where NaN marks a column without one: such a column is skipped and keeps the NaN its outputs are filled with first.
+template <class Spec> struct MixtureColumns {
+    ptnn_handle* h;
+    RowsByVectors& f;
+    const Spec& s;
+    long long ncols;
+    bool forecast;
+    double *d_tau2 = nullptr, *d_tau = nullptr, *d_itau = nullptr;
+    double *d_pit = nullptr, *d_crps = nullptr, *d_mean = nullptr, *d_sd = nullptr, *d_q = nullptr, *d_t1 = nullptr, *d_bound = nullptr;
+    unsigned long long* d_limbs = nullptr;
+    int n_tiles = 0;
+    unsigned n_tri = 0;
+    CalibRow ra{};
+    CalibPair pa{};
+    static int check(const Spec& s) {           // no handle needed
+        if (s.n_levels < 0 || s.n_levels > CALIB_MAX_LEVELS) return fail(-1, "n_levels = %d outside [0, %d]", s.n_levels, CALIB_MAX_LEVELS);
+        if (s.n_levels > 0 && (!s.levels_p || !s.levels_z || !s.quantiles))
+            return fail(-1, "n_levels = %d needs levels_p, levels_z and quantiles", s.n_levels);
+        if (s.quantiles && s.n_levels == 0) return fail(-1, "quantiles requested without levels");
+        for (int k = 0; k < s.n_levels; ++k)
+            if (!(s.levels_p[k] > 0.0 && s.levels_p[k] < 1.0) || !std::isfinite(s.levels_z[k]))
+                return fail(-1, "levels_p[%d] = %g (levels_z %g): a quantile level lies in (0, 1)", k, s.levels_p[k], s.levels_z[k]);
+        if (s.crps && !s.pair_term) return fail(-1, "crps requested without pair_term");
+        return 0;
+    }
+    hipError_t column(double** p, size_t n) const {                     // a per-column result
+        const hipError_t e = f.mem.alloc(p, n);
+        return e != hipSuccess || !forecast ? e : hipMemsetAsync(*p, 0xff, n * sizeof(double), h->stream);
+    }
+    // the results and tau of every distinct sample; mu [nc][U] is the block's image, y the observation of column c at y[c * ys]
+    int alloc(const float* mu, const float* y, int ys) {
+        hipStream_t st = h->stream;
+        const int U = f.U;
+        const size_t n = (size_t)ncols;
+        HIP_TRY(f.mem.alloc(&d_tau2, (size_t)U));
+        HIP_TRY(f.mem.alloc(&d_tau, (size_t)U));
+        HIP_TRY(f.mem.alloc(&d_itau, (size_t)U));
+        HIP_TRY(column(&d_pit, n));
+        HIP_TRY(column(&d_mean, n));
+        HIP_TRY(column(&d_sd, n));
+        if (s.n_levels) HIP_TRY(column(&d_q, (size_t)s.n_levels * n));
+        if (s.pair_term) {
+            HIP_TRY(column(&d_crps, n));
+            HIP_TRY(column(&d_t1, n));
+            HIP_TRY(column(&d_bound, n));
+            HIP_TRY(f.mem.alloc(&d_limbs, n * 4));
+            HIP_TRY(hipMemsetAsync(d_limbs, 0, n * 4 * sizeof(unsigned long long), st));
+        }
+        HIP_TRY(launch(calib_tau_kernel, dim3((unsigned)((U + CALIB_THREADS - 1) / CALIB_THREADS)), dim3(CALIB_THREADS), 0, st, U, f.d.run_eta,
+                       d_tau2, d_tau, d_itau));
+        ra.fx = mu; ra.tau2 = d_tau2; ra.tau = d_tau; ra.itau = d_itau; ra.cnt = f.d.run_cnt; ra.y = y; ra.ys = ys; ra.U = U;
+        ra.n_rows = (int)ncols; ra.S = f.M; ra.n_levels = s.n_levels; ra.pair = s.pair_term ? 1 : 0; ra.skip_nan = forecast ? 1 : 0;
+        for (int k = 0; k < s.n_levels; ++k) { ra.p[k] = s.levels_p[k]; ra.z[k] = s.levels_z[k]; }
+        ra.pit = d_pit; ra.pred_mean = d_mean; ra.pred_sd = d_sd; ra.quantiles = d_q; ra.term1 = d_t1; ra.pair_bound = d_bound;
+        n_tiles = (U + CALIB_THREADS - 1) / CALIB_THREADS;
+        n_tri = (unsigned)((long long)n_tiles * (n_tiles + 1) / 2);
+        pa = CalibPair{mu, d_tau2, f.d.run_cnt, d_bound, U, 0, 0, n_tiles, d_limbs, forecast ? y : nullptr};
+        return 0;
+    }
+    // the columns [col0, col0 + nc), whose image the forward pass has left in mu
+    int block(long long col0, int nc) {
+        ra.row0 = (int)col0;
+        HIP_TRY(launch(calib_row_kernel, dim3((unsigned)nc), dim3(CALIB_THREADS), 0, h->stream, ra));
+        // the pair term of this block's columns, at most 65535 (grid.y) per launch
+        for (int q0 = 0; s.pair_term && q0 < nc; q0 += 65535) {
+            pa.row0 = (int)col0; pa.r0 = q0;
+            HIP_TRY(launch(calib_pair_kernel, dim3(n_tri, (unsigned)std::min(65535, nc - q0)), dim3(CALIB_THREADS), 0, h->stream, pa));
+        }
+        return 0;
+    }
+    int finish() const {
+        if (s.pair_term)
+            HIP_TRY(launch(calib_finish_kernel, dim3((unsigned)((ncols + CALIB_THREADS - 1) / CALIB_THREADS)), dim3(CALIB_THREADS), 0, h->stream,
+                           (int)ncols, d_limbs, d_t1, d_bound, f.M, d_crps));
+        return 0;
+    }
+    int fetch() const {
+        hipStream_t st = h->stream;
+        HIP_TRY(::fetch(s.pit, d_pit, (size_t)ncols, st));
+        HIP_TRY(::fetch(s.pred_mean, d_mean, (size_t)ncols, st));
+        HIP_TRY(::fetch(s.pred_sd, d_sd, (size_t)ncols, st));
+        HIP_TRY(::fetch(s.quantiles, d_q, (size_t)s.n_levels * ncols, st));
+        HIP_TRY(::fetch(s.crps, d_crps, (size_t)ncols, st));
+        return 0;
     }
 };
 
@@ -897,17 +1050,12 @@ int ptnn_predict(ptnn_handle* h, const ptnn_predict_spec* spec) {
     if (int rc = f.rk.to_device(mem, (size_t)ncols, st)) return rc;
     if (h->cfg.task == PTNN_TASK_CLS) HIP_TRY(votes.alloc(mem, (size_t)ncols));
     // stage b + c in blocks of rows: fx scratch U x (rows x O) floats under the budget
-    const long long rows_blk = row_block(scratch_budget("PTNN_PREDICT_SCRATCH_BYTES"), (size_t)U * sizeof(float) * O, s.n_rows);
-    float* d_fx = nullptr;
-    HIP_TRY(mem.alloc(&d_fx, (size_t)rows_blk * O * U));
-    ForwardPlan fwd;
-    if (int rc = fwd.init(h, "posterior predictive")) return rc;
+    if (int rc = f.forward(h, "PTNN_PREDICT_SCRATCH_BYTES", 1, (size_t)U * sizeof(float) * O, s.n_rows, "posterior predictive")) return rc;
     if (int rc = f.items(h, s.samples != nullptr)) return rc;
-    if (int rc = each_block(s.n_rows, rows_blk, [&](long long r0, int nr) -> int {
-        if (int rc = fwd.run(h, d.base, d.run_off, f.d_x, f.xs, (int)r0, nr, U, d_fx)) return rc;
-        PredictRed ra{d_fx, d.run_cnt, U, O, (int)r0 * O, ncols, M, s.n_ranks, rk.d_ranks, d_mean, rk.d_stats, votes.d};
+    if (int rc = f.each_rows(h, s.n_rows, [&](long long r0, int nr) -> int {
+        PredictRed ra{f.d_fx, d.run_cnt, U, O, (int)r0 * O, ncols, M, s.n_ranks, rk.d_ranks, d_mean, rk.d_stats, votes.d};
         HIP_TRY(launch(predict_reduce_kernel, dim3((unsigned)(nr * O)), dim3(PRED_THREADS), 0, st, ra));
-        return s.samples ? scatter_samples(h, d_fx, nr * O, U, f.item_run, f.src.weights(), s.samples, (size_t)s.n_rows * O, (size_t)r0 * O) : 0;
+        return s.samples ? scatter_samples(h, f.d_fx, nr * O, U, f.item_run, f.src.weights(), s.samples, (size_t)s.n_rows * O, (size_t)r0 * O) : 0;
     })) return rc;
     HIP_TRY(fetch(s.mean, d_mean, (size_t)ncols, st));
     HIP_TRY(fetch(s.order_stats, rk.d_stats, (size_t)s.n_ranks * ncols, st));
@@ -1729,23 +1877,20 @@ int ptnn_elpd(ptnn_handle* h, const ptnn_elpd_spec* spec) {
     if (int rc = check_spec(spec, "ptnn_elpd_spec")) return rc;
     const ptnn_elpd_spec& s = *spec;
     const bool ll_src = s.loglik != nullptr;
-    SampleSource src = source_of(s, ll_src || s.w != nullptr, s.eta);
-    const RowSource rows{s.x_source, s.x, s.n_rows, "x_source", "PTNN_PREDICT_X", "x", "n_rows"};
-    if (int rc = pointwise_source(s, src)) return rc;
-    if (int rc = pointwise_rows(s, src, rows)) return rc;
+    RowsByVectors f(s, x_rows(s), ll_src || s.w != nullptr);
+    if (int rc = pointwise_source(s, f)) return rc;
+    if (int rc = pointwise_rows(s, f)) return rc;
     if (int rc = check_handle(h, "ptnn_elpd")) return rc;
-    const int I = h->cfg.n_in, O = h->cfg.n_out;
-    const bool reg = h->cfg.task == PTNN_TASK_REG;
-    if (int rc = pointwise_fit(h, s, src, rows)) return rc;
-    if (int rc = select_samples(h, src, true, "p_waic (a variance, ddof 1) needs at least 2")) return rc;
-    const long long n_items = src.n_items, S = src.M;
+    if (int rc = pointwise_fit(h, s, f)) return rc;
+    if (int rc = f.select(h, nullptr, "p_waic (a variance, ddof 1) needs at least 2")) return rc;
+    const long long n_items = f.src.n_items, S = f.M;
     long long M = 0;
     if (int rc = psis_tail(S, s.r_eff, &M)) return rc;
     if (s.n_samples) *s.n_samples = S;
 
-    if (int rc = start_device(h)) return rc;
+    if (int rc = f.start(h)) return rc;
     hipStream_t st = h->stream;
-    DeviceScratch mem;
+    DeviceScratch& mem = f.mem;
     const int n_rows = s.n_rows;
     double *d_lppd = nullptr, *d_pwaic = nullptr, *d_loo = nullptr, *d_khat = nullptr;
     long long* d_tail = nullptr;
@@ -1755,7 +1900,7 @@ int ptnn_elpd(ptnn_handle* h, const ptnn_elpd_spec* spec) {
     HIP_TRY(mem.alloc(&d_khat, (size_t)n_rows));
     HIP_TRY(mem.alloc(&d_tail, (size_t)n_rows));
     ElpdRed ra{};
-    ra.O = O; ra.S = S; ra.M = (int)M;
+    ra.O = h->cfg.n_out; ra.S = S; ra.M = (int)M;
     ra.lppd = d_lppd; ra.p_waic = d_pwaic; ra.elpd_loo = d_loo; ra.khat = d_khat; ra.tail_len = d_tail;
     auto copy_out = [&]() -> int {
         HIP_TRY(fetch(s.lppd, d_lppd, (size_t)n_rows, st));
@@ -1773,35 +1918,12 @@ int ptnn_elpd(ptnn_handle* h, const ptnn_elpd_spec* spec) {
         return copy_out();
     }
 
-    // data rows and targets
-    const float* d_x = nullptr;
-    int xs = 0;
-    if (int rc = upload_rows(h, mem, rows, I + 1, &d_x, &xs)) return rc;
-    // stage a: items -> distinct (w, eta) samples
-    Distinct d;
-    if (int rc = distinct_samples(h, mem, src, true, true, &d)) return rc;
-    const int U = d.U;
-    if (s.n_distinct) *s.n_distinct = U;
-    // stage b + c in blocks of rows: fx scratch U x (rows x O) floats (+ U x rows doubles for loglik_out) under the budget
-    const long long rows_blk = row_block(scratch_budget("PTNN_ELPD_SCRATCH_BYTES"),
-                                         (size_t)U * (sizeof(float) * O + (s.loglik_out ? sizeof(double) : 0)), n_rows);
-    float* d_fx = nullptr;
-    double* d_llb = nullptr;
-    HIP_TRY(mem.alloc(&d_fx, (size_t)rows_blk * O * U));
-    if (s.loglik_out) HIP_TRY(mem.alloc(&d_llb, (size_t)rows_blk * U));
-    ForwardPlan fwd;
-    if (int rc = fwd.init(h, "predictive accuracy")) return rc;
-    std::vector<int> item_run;
-    if (s.loglik_out) if (int rc = item_runs(h, d, n_items, &item_run)) return rc;
-    ra.mode = reg ? ELPD_REG : ELPD_CLS; ra.fx = d_fx; ra.eta = d.run_eta; ra.y = d_x + I; ra.ys = xs; ra.cnt = d.run_cnt; ra.U = U;
-    ra.ll_out = d_llb;
-    if (int rc = each_block(n_rows, rows_blk, [&](long long r0, int nr) -> int {
-        if (int rc = fwd.run(h, d.base, d.run_off, d_x, xs, (int)r0, nr, U, d_fx)) return rc;
+    // stage a: the rows with their targets, items -> distinct (w, eta) samples; stages b + c in blocks of rows
+    if (int rc = pointwise_stage(h, s, f, "PTNN_ELPD_SCRATCH_BYTES", 1, "predictive accuracy", &ra)) return rc;
+    if (int rc = f.each_rows(h, n_rows, [&](long long r0, int nr) -> int {
         ra.row0 = (int)r0;
         HIP_TRY(launch(elpd_reduce_kernel, dim3((unsigned)nr), dim3(ELPD_THREADS), 0, st, ra));
-        if (!s.loglik_out) return 0;
-        if (int rc = loglik_block(h, ra, nr)) return rc;
-        return scatter_samples(h, d_llb, nr, U, item_run, src.weights(), s.loglik_out, (size_t)n_rows, (size_t)r0);
+        return s.loglik_out ? pointwise_out(h, s, f, ra, r0, nr) : 0;
     })) return rc;
     return copy_out();
 }
@@ -1812,9 +1934,8 @@ int ptnn_lfo(ptnn_handle* h, const ptnn_lfo_spec* spec) {
     if (int rc = check_spec(spec, "ptnn_lfo_spec")) return rc;
     const ptnn_lfo_spec& s = *spec;
     const bool ll_src = s.loglik != nullptr;
-    SampleSource src = source_of(s, ll_src || s.w != nullptr, s.eta);
-    const RowSource rows{s.x_source, s.x, s.n_rows, "x_source", "PTNN_PREDICT_X", "x", "n_rows"};
-    if (int rc = pointwise_source(s, src)) return rc;
+    RowsByVectors f(s, x_rows(s), ll_src || s.w != nullptr);
+    if (int rc = pointwise_source(s, f)) return rc;
     if (s.block < 1) return fail(-1, "block = %d must be >= 1", s.block);
     if (s.n_fit < 1 || s.n_fit > s.n_rows)
         return fail(-1, "n_fit = %d outside [1, %d]: the samples are conditioned on rows [0, n_fit) of the %d rows", s.n_fit, s.n_rows, s.n_rows);
@@ -1825,20 +1946,18 @@ int ptnn_lfo(ptnn_handle* h, const ptnn_lfo_spec* spec) {
         if (i + s.block > s.n_rows)
             return fail(-1, "origin %lld (origins[%d]) with block = %d: i + block > n_rows = %d", i, k, s.block, s.n_rows);
     }
-    if (int rc = pointwise_rows(s, src, rows)) return rc;
+    if (int rc = pointwise_rows(s, f)) return rc;
     if (int rc = check_handle(h, "ptnn_lfo")) return rc;
-    const int I = h->cfg.n_in, O = h->cfg.n_out;
-    const bool reg = h->cfg.task == PTNN_TASK_REG;
-    if (int rc = pointwise_fit(h, s, src, rows)) return rc;
-    if (int rc = select_samples(h, src, true, "importance weights need at least 2")) return rc;
-    const long long n_items = src.n_items, S = src.M;
+    if (int rc = pointwise_fit(h, s, f)) return rc;
+    if (int rc = f.select(h, nullptr, "importance weights need at least 2")) return rc;
+    const long long n_items = f.src.n_items, S = f.M;
     long long M = 0;
     if (int rc = psis_tail(S, s.r_eff, &M)) return rc;
     if (s.n_samples) *s.n_samples = S;
 
-    if (int rc = start_device(h)) return rc;
+    if (int rc = f.start(h)) return rc;
     hipStream_t st = h->stream;
-    DeviceScratch mem;
+    DeviceScratch& mem = f.mem;
     const int n_rows = s.n_rows, n_org = s.n_origins;
     double *d_lfo = nullptr, *d_khat = nullptr;
     long long* d_tail = nullptr;
@@ -1847,43 +1966,21 @@ int ptnn_lfo(ptnn_handle* h, const ptnn_lfo_spec* spec) {
     HIP_TRY(mem.alloc(&d_tail, (size_t)n_org));
     if (int rc = raise_lds_limit(reinterpret_cast<const void*>(lfo_reduce_kernel), LFO_LDS_BYTES)) return rc;
 
-    // the samples: source 3 as it is (every host sample its own entry), else stage a
+    // The samples: source 3 as it is (every host sample its own entry), else stage a.  The budget: half for the sums C (the columns
+    // n_fit, i and i + block of a pass of origins), half for a block of rows
     LfoAcc acc{};
     ElpdRed& ra = acc.a;
-    ra.O = O; ra.S = S; ra.M = (int)M;
-    const float* d_x = nullptr;
-    int xs = 0, U = 0;
-    Distinct d;
+    ra.O = h->cfg.n_out; ra.S = S; ra.M = (int)M;
     if (ll_src) {
         if (int rc = upload_loglik(h, mem, s, n_items, &ra)) return rc;
-        U = ra.U;
+        if (s.n_distinct) *s.n_distinct = ra.U;
     } else {
-        if (int rc = upload_rows(h, mem, rows, I + 1, &d_x, &xs)) return rc;
-        if (int rc = distinct_samples(h, mem, src, true, true, &d)) return rc;
-        U = d.U;
-        ra.mode = reg ? ELPD_REG : ELPD_CLS; ra.eta = d.run_eta; ra.y = d_x + I; ra.ys = xs; ra.cnt = d.run_cnt;
+        if (int rc = pointwise_stage(h, s, f, "PTNN_LFO_SCRATCH_BYTES", 2, "leave-future-out", &ra)) return rc;
     }
-    ra.U = U;
-    if (s.n_distinct) *s.n_distinct = U;
-
-    // the budget: half for the sums C (the columns n_fit, i and i + block of a pass of origins), half for a block of rows
-    const size_t budget = scratch_budget("PTNN_LFO_SCRATCH_BYTES");
-    const long long cols_fit = (long long)((budget / 2) / ((size_t)U * sizeof(double)));
+    const int U = ra.U;
+    const long long cols_fit = (long long)((scratch_budget("PTNN_LFO_SCRATCH_BYTES") / 2) / ((size_t)U * sizeof(double)));
     const int org_pass = (int)std::max(1LL, std::min<long long>((cols_fit - 1) / 2, n_org));
     const int max_slots = 2 * org_pass + 1;
-    long long rows_blk = n_rows;
-    float* d_fx = nullptr;
-    double* d_llb = nullptr;
-    ForwardPlan fwd;
-    std::vector<int> item_run;
-    if (!ll_src) {
-        rows_blk = row_block(budget / 2, (size_t)U * (sizeof(float) * O + (s.loglik_out ? sizeof(double) : 0)), n_rows);
-        HIP_TRY(mem.alloc(&d_fx, (size_t)rows_blk * O * U));
-        if (s.loglik_out) HIP_TRY(mem.alloc(&d_llb, (size_t)rows_blk * U));
-        if (int rc = fwd.init(h, "leave-future-out")) return rc;
-        if (s.loglik_out) if (int rc = item_runs(h, d, n_items, &item_run)) return rc;
-        ra.fx = d_fx; ra.ll_out = d_llb;
-    }
     double *d_C = nullptr, *d_carry = nullptr;
     int *d_slot_of = nullptr, *d_org_slot = nullptr;
     HIP_TRY(mem.alloc(&d_C, (size_t)max_slots * U));
@@ -1911,17 +2008,14 @@ int ptnn_lfo(ptnn_handle* h, const ptnn_lfo_spec* spec) {
         HIP_TRY(hipMemcpyAsync(d_slot_of, slot_of.data(), slot_of.size() * sizeof(int), hipMemcpyHostToDevice, st));
         HIP_TRY(hipMemcpyAsync(d_org_slot, org_slot.data(), (size_t)2 * no * sizeof(int), hipMemcpyHostToDevice, st));
         HIP_TRY(hipMemsetAsync(d_carry, 0, (size_t)U * sizeof(double), st));
-        // stage b + c in blocks of rows, ascending
-        if (int rc = each_block(n_end, rows_blk, [&](long long r0, int nr) -> int {
-            if (!ll_src)
-                if (int rc = fwd.run(h, d.base, d.run_off, d_x, xs, (int)r0, nr, U, d_fx)) return rc;
+        // stage b + c in blocks of rows, ascending (source 3: one block)
+        auto block = [&](long long r0, int nr) -> int {
             ra.row0 = (int)r0;
             acc.nrows = nr;
             HIP_TRY(launch(lfo_accum_kernel, dim3(acc_blocks), dim3(ELPD_THREADS), 0, st, acc));
-            if (!(s.loglik_out && o0 == 0)) return 0;
-            if (int rc = loglik_block(h, ra, nr)) return rc;
-            return scatter_samples(h, d_llb, nr, U, item_run, src.weights(), s.loglik_out, (size_t)n_rows, (size_t)r0);
-        })) return rc;
+            return s.loglik_out && o0 == 0 ? pointwise_out(h, s, f, ra, r0, nr) : 0;
+        };
+        if (int rc = ll_src ? each_block(n_end, n_rows, block) : f.each_rows(h, n_end, block)) return rc;
         // stage d: one work-group per origin of the pass
         LfoRed lr{d_C, ra.cnt, d_org_slot, fit_slot, U, (int)M, S, d_lfo + o0, d_khat + o0, d_tail + o0};
         HIP_TRY(launch(lfo_reduce_kernel, dim3((unsigned)no), dim3(ELPD_THREADS), LFO_LDS_BYTES, st, lr));
@@ -2122,13 +2216,96 @@ static int evid_rung_ess(ptnn_handle* h, const std::vector<long long>& off, cons
     return 0;
 }
 
+// The rungs of ptnn_evidence and ptnn_mbar (Spec: the fields the two specs name alike), from a host U [K][n], host vectors
+// [K][n][P] -- one list of K n items, whose [K, n] multiplicities are applied to U -- or the trace, one rung per chain: the expanded
+// draws of rung k at [off[k], off[k + 1]), and stages a to c of the evidence path.  In steps, since the order of the refusals is
+// kept and each call has checks of its own between them.
+extern "C++" {
+template <class Spec> struct RungLayout {
+    const Spec& s;
+    const bool u_src, host_src;
+    SampleSource src;
+    std::vector<long long> off;                        // [K + 1]
+    std::vector<int32_t> item_of;                      // expanded draw -> item (multiplicities only)
+    long long per = 0;                                 // rows per rung
+    Distinct d;                                        // eval: the distinct vectors
+    explicit RungLayout(const Spec& spec)
+        : s(spec), u_src(spec.u != nullptr), host_src(spec.w != nullptr),
+          src{host_src, spec.w, nullptr, (int64_t)spec.n_rungs * spec.n_per_rung, nullptr, spec.replicas, spec.n_replicas, spec.step0, spec.nsteps, spec.thin} {}
+    bool trace() const { return !u_src && !host_src; }
+    int K() const { return (int)off.size() - 1; }
+    long long n_draws() const { return off.back(); }
+    // the host sources, no handle needed: items, their multiplicities, the draws of every rung; not_finite(item, k, i) refuses a
+    // counted item whose host U is not finite, in the call's words
+    template <class F> int host(F not_finite) {
+        if (trace()) return 0;
+        const long long K = s.n_rungs, n = per = s.n_per_rung;
+        if (K * n > 0x7fffffffLL) return fail(-1, "%lld host rows: at most 2^31 - 1 per call", K * n);
+        src.n_items = K * n;
+        off.assign((size_t)K + 1, 0);
+        for (long long k = 0; k < K; ++k) {
+            long long c = 0;
+            for (long long i = 0; i < n; ++i) {
+                const long long it = k * n + i;
+                const int mu = s.multiplicity ? s.multiplicity[it] : 1;
+                if (mu < 0) return fail(-1, "multiplicity[%lld, %lld] = %d is negative", k, i, mu);
+                c += mu;
+                if (s.multiplicity) for (int r = 0; r < mu; ++r) item_of.push_back((int32_t)it);
+                if (u_src && mu > 0)
+                    if (int rc = not_finite(it, k, i)) return rc;
+            }
+            off[(size_t)k + 1] = off[(size_t)k] + c;
+            if (off[(size_t)k + 1] > 0x7fffffffLL) return fail(-1, "more than 2^31 - 1 expanded draws");
+        }
+        return 0;
+    }
+    // the trace selection, with the handle: the rows counted, then -- behind the call's own checks -- one rung per chain
+    int count_trace(const ptnn_handle* h) {
+        if (int rc = count_samples(h, src)) return rc;
+        if (src.n_items > 0x7fffffffLL) return fail(-1, "%lld trace rows: at most 2^31 - 1 per call", src.n_items);
+        return 0;
+    }
+    void trace_rungs() {
+        per = src.m;
+        off.assign(src.reps.size() + 1, 0);
+        for (size_t k = 0; k < src.reps.size(); ++k) off[k + 1] = off[k] + per;
+    }
+    int four_per_rung() const {
+        for (int k = 0; k < K(); ++k)
+            if (off[(size_t)k + 1] - off[(size_t)k] < 4)
+                return fail(-1, "rung %d holds %lld draws: the split ESS needs at least 4 per rung", k, off[(size_t)k + 1] - off[(size_t)k]);
+        return 0;
+    }
+    // Stages a to c: items -> distinct vectors -> their U (and b, where b_out is given), rows in blocks under the budget -> the U
+    // (and b) of n entries at u_out (b_out): the items, or with `d_item_of` the expanded draws
+    int eval(ptnn_handle* h, DeviceScratch& mem, EvidEval& ev, size_t budget, long long n, const int* d_item_of, double* u_out, double* b_out) {
+        hipStream_t st = h->stream;
+        if (int rc = distinct_samples(h, mem, src, false, true, &d)) return rc;
+        const int U = d.U;
+        if (s.n_distinct) *s.n_distinct = U;
+        const long long rows_blk = ev.rows_for(U, budget);
+        float* d_fx = nullptr;
+        double *d_acc = nullptr, *d_udist = nullptr, *d_bdist = nullptr;
+        HIP_TRY(mem.alloc(&d_fx, (size_t)rows_blk * ev.O * U));
+        HIP_TRY(mem.alloc(&d_acc, (size_t)U));
+        HIP_TRY(mem.alloc(&d_udist, (size_t)U));
+        if (b_out) HIP_TRY(mem.alloc(&d_bdist, (size_t)U));
+        if (int rc = ev.eval(d.base, d.run_off, U, rows_blk, d_fx, d_acc, d_udist, d_bdist)) return rc;
+        const unsigned blocks = (unsigned)((n + EVID_THREADS - 1) / EVID_THREADS);
+        HIP_TRY(launch(evid_expand_kernel, dim3(blocks), dim3(EVID_THREADS), 0, st, n, d_item_of, d.item_run, d_udist, u_out));
+        if (b_out) HIP_TRY(launch(evid_expand_kernel, dim3(blocks), dim3(EVID_THREADS), 0, st, n, d_item_of, d.item_run, d_bdist, b_out));
+        return ev.sse_check();
+    }
+};
+}  // extern "C++"
+
 int ptnn_evidence(ptnn_handle* h, const ptnn_evidence_spec* spec) {
     // argument checks first: none of them needs the handle or a device
     if (int rc = check_spec(spec, "ptnn_evidence_spec")) return rc;
     const ptnn_evidence_spec& s = *spec;
-    const bool u_src = s.u != nullptr, host_src = s.w != nullptr;
-    // host vectors [K][n][P] as one list of K n items (their [K, n] multiplicities are applied to U, below), or one rung per chain
-    SampleSource src{host_src, s.w, nullptr, (int64_t)s.n_rungs * s.n_per_rung, nullptr, s.replicas, s.n_replicas, s.step0, s.nsteps, s.thin};
+    RungLayout<ptnn_evidence_spec> rungs(s);
+    const bool u_src = rungs.u_src, host_src = rungs.host_src;
+    SampleSource& src = rungs.src;
     if (u_src && host_src) return fail(-1, "give host vectors w or a host U, not both");
     if (u_src || host_src) {
         if (s.n_rungs < 1) return fail(-1, "n_rungs = %d must be >= 1", s.n_rungs);
@@ -2146,46 +2323,21 @@ int ptnn_evidence(ptnn_handle* h, const ptnn_evidence_spec* spec) {
     if (s.n_prior == 0 && s.u_prior_out) return fail(-1, "u_prior_out requested with n_prior = 0");
     if (u_src && s.u_out) return fail(-1, "u_out: U is the input of this source");
     if (u_src && s.n_distinct) *s.n_distinct = 0;
-    // host sources: items, their multiplicities, the draws of every rung
-    std::vector<long long> off;                        // [K + 1] expanded draws of rung k at [off[k], off[k + 1])
-    std::vector<int32_t> item_of;                      // expanded draw -> item (multiplicities only)
-    if (u_src || host_src) {
-        const long long K = s.n_rungs, n = s.n_per_rung;
-        if (K * n > 0x7fffffffLL) return fail(-1, "%lld host rows: at most 2^31 - 1 per call", K * n);
-        src.n_items = K * n;
-        off.assign((size_t)K + 1, 0);
-        for (long long k = 0; k < K; ++k) {
-            long long c = 0;
-            for (long long i = 0; i < n; ++i) {
-                const long long it = k * n + i;
-                const int mu = s.multiplicity ? s.multiplicity[it] : 1;
-                if (mu < 0) return fail(-1, "multiplicity[%lld, %lld] = %d is negative", k, i, mu);
-                c += mu;
-                if (s.multiplicity) for (int r = 0; r < mu; ++r) item_of.push_back((int32_t)it);
-                if (u_src && mu > 0 && !std::isfinite(s.u[it])) return fail(-1, "u[%lld, %lld] = %g is not finite", k, i, s.u[it]);
-            }
-            off[(size_t)k + 1] = off[(size_t)k] + c;
-            if (off[(size_t)k + 1] > 0x7fffffffLL) return fail(-1, "more than 2^31 - 1 expanded draws");
-        }
-    }
+    if (int rc = rungs.host([&](long long it, long long k, long long i) {
+        return std::isfinite(s.u[it]) ? 0 : fail(-1, "u[%lld, %lld] = %g is not finite", k, i, s.u[it]);
+    })) return rc;
     if (int rc = check_handle(h, "ptnn_evidence")) return rc;
-    const int O = h->cfg.n_out;
-    // the trace selection: one rung per chain
-    if (!u_src && !host_src) {
-        if (int rc = count_samples(h, src)) return rc;
-        if (src.n_items > 0x7fffffffLL) return fail(-1, "%lld trace rows: at most 2^31 - 1 per call", src.n_items);
-        off.assign(src.reps.size() + 1, 0);
-        for (size_t k = 0; k < src.reps.size(); ++k) off[k + 1] = off[k] + src.m;
+    if (rungs.trace()) {
+        if (int rc = rungs.count_trace(h)) return rc;
+        rungs.trace_rungs();
     }
-    const long long n_items = src.n_items;
-    const int K = (int)off.size() - 1;
-    for (int k = 0; k < K; ++k)
-        if (off[(size_t)k + 1] - off[(size_t)k] < 4)
-            return fail(-1, "rung %d holds %lld draws: the split ESS needs at least 4 per rung", k, off[(size_t)k + 1] - off[(size_t)k]);
+    const std::vector<long long>& off = rungs.off;
+    const long long n_items = src.n_items, n_draws = rungs.n_draws();
+    const int K = rungs.K();
+    if (int rc = rungs.four_per_rung()) return rc;
     if (s.d)
         for (int k = 0; k < K; ++k)
             if (!std::isfinite(s.d[k])) return fail(-1, "d[%d] = %g is not finite", k, s.d[k]);
-    const long long n_draws = off[(size_t)K];
     if (s.n_draws)
         for (int k = 0; k < K; ++k) s.n_draws[k] = off[(size_t)k + 1] - off[(size_t)k];
 
@@ -2200,28 +2352,14 @@ int ptnn_evidence(ptnn_handle* h, const ptnn_evidence_spec* spec) {
     double* d_udraw = nullptr;
     if (K > 0) HIP_TRY(mem.alloc(&d_udraw, (size_t)n_draws));
     int* d_item_of = nullptr;
-    if (!item_of.empty()) HIP_TRY(mem.upload(&d_item_of, item_of.data(), item_of.size(), st));
-    const unsigned draw_blocks = (unsigned)((n_draws + EVID_THREADS - 1) / EVID_THREADS);
+    if (!rungs.item_of.empty()) HIP_TRY(mem.upload(&d_item_of, rungs.item_of.data(), rungs.item_of.size(), st));
     if (u_src) {
         double* d_u = nullptr;
         HIP_TRY(mem.upload(&d_u, s.u, (size_t)n_items, st));
-        HIP_TRY(launch(evid_expand_kernel, dim3(draw_blocks), dim3(EVID_THREADS), 0, st, n_draws, d_item_of, nullptr, d_u, d_udraw));
+        HIP_TRY(launch(evid_expand_kernel, dim3((unsigned)((n_draws + EVID_THREADS - 1) / EVID_THREADS)), dim3(EVID_THREADS), 0, st, n_draws,
+                       d_item_of, nullptr, d_u, d_udraw));
     } else {
-        // stage a: items -> distinct vectors
-        Distinct d;
-        if (int rc = distinct_samples(h, mem, src, false, true, &d)) return rc;
-        const int U = d.U;
-        if (s.n_distinct) *s.n_distinct = U;
-        // stages b, c: U of every distinct vector, rows in blocks under the budget
-        const long long rows_blk = ev.rows_for(U, budget);
-        float* d_fx = nullptr;
-        double *d_acc = nullptr, *d_udist = nullptr;
-        HIP_TRY(mem.alloc(&d_fx, (size_t)rows_blk * O * U));
-        HIP_TRY(mem.alloc(&d_acc, (size_t)U));
-        HIP_TRY(mem.alloc(&d_udist, (size_t)U));
-        if (int rc = ev.eval(d.base, d.run_off, U, rows_blk, d_fx, d_acc, d_udist, nullptr)) return rc;
-        HIP_TRY(launch(evid_expand_kernel, dim3(draw_blocks), dim3(EVID_THREADS), 0, st, n_draws, d_item_of, d.item_run, d_udist, d_udraw));
-        if (int rc = ev.sse_check()) return rc;
+        if (int rc = rungs.eval(h, mem, ev, budget, n_draws, d_item_of, d_udraw, nullptr)) return rc;
     }
     // stage d: per-rung moments and stones
     long long* d_off = nullptr;
@@ -2276,8 +2414,9 @@ int ptnn_mbar(ptnn_handle* h, const ptnn_mbar_spec* spec) {
     // argument checks first: none of them needs the handle or a device
     if (int rc = check_spec(spec, "ptnn_mbar_spec")) return rc;
     const ptnn_mbar_spec& s = *spec;
-    const bool u_src = s.u != nullptr, host_src = s.w != nullptr;
-    SampleSource src{host_src, s.w, nullptr, (int64_t)s.n_rungs * s.n_per_rung, nullptr, s.replicas, s.n_replicas, s.step0, s.nsteps, s.thin};
+    RungLayout<ptnn_mbar_spec> rungs(s);
+    const bool u_src = rungs.u_src, host_src = rungs.host_src;
+    SampleSource& src = rungs.src;
     if (u_src && host_src) return fail(-1, "give host vectors w or a host U, not both");
     if (s.b && !u_src) return fail(-1, "b comes with a host U");
     if (s.n_rungs < 1) return fail(-1, "n_rungs = %d must be >= 1", s.n_rungs);
@@ -2306,7 +2445,7 @@ int ptnn_mbar(ptnn_handle* h, const ptnn_mbar_spec* spec) {
     if (s.n_resample < 0 || s.n_resample > 0x7fffffffLL) return fail(-1, "n_resample = %lld outside [0, 2^31 - 1]", (long long)s.n_resample);
     if (s.n_resample == 0 && (s.resample_item || s.cum_weight)) return fail(-1, "resample_item and cum_weight need n_resample > 0");
     const bool expect = s.mean || s.var;
-    const RowSource xrows{s.x_source, s.x, s.n_rows, "x_source", "PTNN_PREDICT_X", "x", "n_rows"};
+    const RowSource xrows = x_rows(s);
     if ((expect || s.resample_w) && (u_src || s.u_prior))
         return fail(-1, "mean, var and resample_w need the items' weight vectors: not with a host U or host prior draws");
     if (s.resample_w && s.n_resample == 0) return fail(-1, "resample_w needs n_resample > 0");
@@ -2317,46 +2456,24 @@ int ptnn_mbar(ptnn_handle* h, const ptnn_mbar_spec* spec) {
     for (long long i = 0; s.u_prior && i < NP; ++i)
         if (!std::isfinite(s.u_prior[i]) || (s.b_prior && !std::isfinite(s.b_prior[i]))) return fail(-1, "u_prior / b_prior [%lld] is not finite", i);
     if (u_src && s.n_distinct) *s.n_distinct = 0;
-    // host sources: items, their multiplicities, the draws of every rung
     const int R = s.n_rungs;
-    std::vector<long long> off((size_t)R + 1, 0);      // expanded draws of rung k at [off[k], off[k + 1])
-    std::vector<int32_t> item_of;                      // expanded draw -> rung item (multiplicities only)
-    long long per = 0;                                 // rows per rung
-    if (u_src || host_src) {
-        per = s.n_per_rung;
-        if ((long long)R * per > 0x7fffffffLL) return fail(-1, "%lld host rows: at most 2^31 - 1 per call", (long long)R * per);
-        src.n_items = (long long)R * per;
-        for (long long k = 0; k < R; ++k) {
-            long long c = 0;
-            for (long long i = 0; i < per; ++i) {
-                const long long it = k * per + i;
-                const int mu = s.multiplicity ? s.multiplicity[it] : 1;
-                if (mu < 0) return fail(-1, "multiplicity[%lld, %lld] = %d is negative", k, i, mu);
-                c += mu;
-                if (s.multiplicity) for (int r = 0; r < mu; ++r) item_of.push_back((int32_t)it);
-                if (u_src && mu > 0 && (!std::isfinite(s.u[it]) || (s.b && !std::isfinite(s.b[it]))))
-                    return fail(-1, "u / b [%lld, %lld] is not finite", k, i);
-            }
-            off[(size_t)k + 1] = off[(size_t)k] + c;
-            if (off[(size_t)k + 1] > 0x7fffffffLL) return fail(-1, "more than 2^31 - 1 expanded draws");
-        }
-    }
+    if (int rc = rungs.host([&](long long it, long long k, long long i) {
+        return std::isfinite(s.u[it]) && !(s.b && !std::isfinite(s.b[it])) ? 0 : fail(-1, "u / b [%lld, %lld] is not finite", k, i);
+    })) return rc;
     if (int rc = check_handle(h, "ptnn_mbar")) return rc;
     const int O = h->cfg.n_out;
     if (expect)
         if (int rc = fit_rows(h, xrows)) return rc;
     if (s.sse && h->cfg.task != PTNN_TASK_REG) return fail(-1, "sse: a classification has no sum of squared errors");
-    if (!u_src && !host_src) {
-        if (int rc = count_samples(h, src)) return rc;
-        if (src.n_items > 0x7fffffffLL) return fail(-1, "%lld trace rows: at most 2^31 - 1 per call", src.n_items);
+    if (rungs.trace()) {
+        if (int rc = rungs.count_trace(h)) return rc;
         if ((int)src.reps.size() != R) return fail(-1, "%d chains selected but n_rungs = %d betas", (int)src.reps.size(), R);
-        per = src.m;
-        for (int k = 0; k < R; ++k) off[(size_t)k + 1] = off[(size_t)k] + per;
+        rungs.trace_rungs();
     }
-    for (int k = 0; k < R; ++k)
-        if (off[(size_t)k + 1] - off[(size_t)k] < 4)
-            return fail(-1, "rung %d holds %lld draws: the split ESS needs at least 4 per rung", k, off[(size_t)k + 1] - off[(size_t)k]);
-    const long long n_rows = (long long)R * per, n_draws = off[(size_t)R], NT = NP + n_rows;
+    if (int rc = rungs.four_per_rung()) return rc;
+    const std::vector<long long>& off = rungs.off;
+    const std::vector<int32_t>& item_of = rungs.item_of;
+    const long long per = rungs.per, n_rows = (long long)R * per, n_draws = rungs.n_draws(), NT = NP + n_rows;
     if (NT > 0x7fffffffLL) return fail(-1, "%lld items: at most 2^31 - 1 per call", NT);
     if (s.n_items) *s.n_items = NT;
 
@@ -2364,7 +2481,6 @@ int ptnn_mbar(ptnn_handle* h, const ptnn_mbar_spec* spec) {
     hipStream_t st = h->stream;
     DeviceScratch mem;
     const size_t budget = scratch_budget("PTNN_EVIDENCE_SCRATCH_BYTES");
-    const unsigned row_blocks = (unsigned)((n_rows + EVID_THREADS - 1) / EVID_THREADS);
     // ---- U and b of every item: the prior draws first, then the rungs' rows
     double *d_u = nullptr, *d_b = nullptr, *d_c = nullptr, *d_D = nullptr;
     HIP_TRY(mem.alloc(&d_u, (size_t)NT));
@@ -2373,7 +2489,7 @@ int ptnn_mbar(ptnn_handle* h, const ptnn_mbar_spec* spec) {
     HIP_TRY(mem.alloc(&d_D, (size_t)NT));
     HIP_TRY(hipMemsetAsync(d_b, 0, (size_t)NT * sizeof(double), st));
     EvidEval ev;
-    Distinct d;                                        // the rungs' distinct vectors (sources 1, 2)
+    const Distinct& d = rungs.d;                       // the rungs' distinct vectors (sources 1, 2)
     const bool need_net = !u_src || (NP > 0 && !s.u_prior);
     if (need_net)
         if (int rc = ev.init(h, mem, "MBAR")) return rc;
@@ -2382,20 +2498,7 @@ int ptnn_mbar(ptnn_handle* h, const ptnn_mbar_spec* spec) {
         if (s.b) HIP_TRY(hipMemcpyAsync(d_b + NP, s.b, (size_t)n_rows * sizeof(double), hipMemcpyHostToDevice, st));
     } else {
         // stages a to c of the evidence path: items -> distinct vectors -> their U and b -> every row's
-        if (int rc = distinct_samples(h, mem, src, false, true, &d)) return rc;
-        const int U = d.U;
-        if (s.n_distinct) *s.n_distinct = U;
-        const long long rows_blk = ev.rows_for(U, budget);
-        float* d_fx = nullptr;
-        double *d_acc = nullptr, *d_udist = nullptr, *d_bdist = nullptr;
-        HIP_TRY(mem.alloc(&d_fx, (size_t)rows_blk * O * U));
-        HIP_TRY(mem.alloc(&d_acc, (size_t)U));
-        HIP_TRY(mem.alloc(&d_udist, (size_t)U));
-        HIP_TRY(mem.alloc(&d_bdist, (size_t)U));
-        if (int rc = ev.eval(d.base, d.run_off, U, rows_blk, d_fx, d_acc, d_udist, d_bdist)) return rc;
-        HIP_TRY(launch(evid_expand_kernel, dim3(row_blocks), dim3(EVID_THREADS), 0, st, n_rows, nullptr, d.item_run, d_udist, d_u + NP));
-        HIP_TRY(launch(evid_expand_kernel, dim3(row_blocks), dim3(EVID_THREADS), 0, st, n_rows, nullptr, d.item_run, d_bdist, d_b + NP));
-        if (int rc = ev.sse_check()) return rc;
+        if (int rc = rungs.eval(h, mem, ev, budget, n_rows, nullptr, d_u + NP, d_b + NP)) return rc;
     }
     if (s.u_prior) {
         HIP_TRY(hipMemcpyAsync(d_u, s.u_prior, (size_t)NP * sizeof(double), hipMemcpyHostToDevice, st));
@@ -2609,20 +2712,12 @@ int ptnn_calibration(ptnn_handle* h, const ptnn_calibration_spec* spec) {
     // argument checks first: none of them needs the handle or a device
     if (int rc = check_spec(spec, "ptnn_calibration_spec")) return rc;
     const ptnn_calibration_spec& s = *spec;
-    SampleSource src = source_of(s, s.w != nullptr, s.eta);
-    const RowSource rows{s.x_source, s.x, s.n_rows, "x_source", "PTNN_PREDICT_X", "x", "n_rows"};
-    if (int rc = check_source(src, "samples", true)) return rc;
+    RowsByVectors f(s, x_rows(s), s.w != nullptr);
+    if (int rc = f.check_source()) return rc;
     if (s.n_rows < 1) return fail(-1, "n_rows = %d must be >= 1", s.n_rows);
-    if (int rc = check_rows(rows)) return rc;
-    if (s.n_levels < 0 || s.n_levels > CALIB_MAX_LEVELS) return fail(-1, "n_levels = %d outside [0, %d]", s.n_levels, CALIB_MAX_LEVELS);
-    if (s.n_levels > 0 && (!s.levels_p || !s.levels_z || !s.quantiles))
-        return fail(-1, "n_levels = %d needs levels_p, levels_z and quantiles", s.n_levels);
-    if (s.quantiles && s.n_levels == 0) return fail(-1, "quantiles requested without levels");
-    for (int k = 0; k < s.n_levels; ++k)
-        if (!(s.levels_p[k] > 0.0 && s.levels_p[k] < 1.0) || !std::isfinite(s.levels_z[k]))
-            return fail(-1, "levels_p[%d] = %g (levels_z %g): a quantile level lies in (0, 1)", k, s.levels_p[k], s.levels_z[k]);
-    if (s.crps && !s.pair_term) return fail(-1, "crps requested without pair_term");
-    if (int rc = count_host_samples(src)) return rc;
+    if (int rc = check_rows(f.rows)) return rc;
+    if (int rc = MixtureColumns<ptnn_calibration_spec>::check(s)) return rc;
+    if (int rc = f.count_host()) return rc;
     if (int rc = check_handle(h, "ptnn_calibration")) return rc;
     const int I = h->cfg.n_in, O = h->cfg.n_out;
     const bool reg = h->cfg.task == PTNN_TASK_REG;
@@ -2631,39 +2726,24 @@ int ptnn_calibration(ptnn_handle* h, const ptnn_calibration_spec* spec) {
         return fail(-1, "pit, crps, pred_mean, pred_sd and quantiles need a regression net with n_out == 1; this handle is a %s net "
                         "with n_out = %d", reg ? "regression" : "classification", O);
     if (s.p_mean && reg) return fail(-1, "p_mean: a regression has no class probabilities");
-    if (int rc = need_eta(h, src)) return rc;
-    if (int rc = fit_rows(h, rows)) return rc;
-    if (int rc = select_samples(h, src, true)) return rc;
-    const long long S = src.M;
-    if (s.n_samples) *s.n_samples = S;
+    if (int rc = f.fit(h)) return rc;
+    if (int rc = f.select(h, s.n_samples)) return rc;
 
-    if (int rc = start_device(h)) return rc;
-    hipStream_t st = h->stream;
-    DeviceScratch mem;
-    const int n_rows = s.n_rows;
-    const float* d_x = nullptr;
-    int xs = 0;
-    if (int rc = upload_rows(h, mem, rows, I + 1, &d_x, &xs)) return rc;
     // stage a: items -> distinct (w, eta) samples (a classification's: distinct w, as ptnn_predict's)
-    Distinct d;
-    if (int rc = distinct_samples(h, mem, src, reg, true, &d)) return rc;
-    const int U = d.U;
-    if (s.n_distinct) *s.n_distinct = U;
+    f.eta = reg;
+    if (int rc = f.stage(h, I + 1, s.n_distinct)) return rc;
+    hipStream_t st = h->stream;
+    const int n_rows = s.n_rows, U = f.U;
     if (s.pair_term && U > CALIB_MAX_DISTINCT)
         return fail(-1, "%d distinct samples: the pair term of the CRPS takes at most %d (U^2 / 2 terms per data row); select fewer "
                         "samples (thin=, chains=) or leave the CRPS out (crps=False)", U, CALIB_MAX_DISTINCT);
-    const long long rows_blk = row_block(scratch_budget("PTNN_CALIB_SCRATCH_BYTES"), (size_t)U * sizeof(float) * O, n_rows);
-    float* d_fx = nullptr;
-    HIP_TRY(mem.alloc(&d_fx, (size_t)rows_blk * O * U));
-    ForwardPlan fwd;
-    if (int rc = fwd.init(h, "calibration")) return rc;
+    if (int rc = f.forward(h, "PTNN_CALIB_SCRATCH_BYTES", 1, (size_t)U * sizeof(float) * O, n_rows, "calibration")) return rc;
 
     if (!reg) {
         double* d_mean = nullptr;
-        HIP_TRY(mem.alloc(&d_mean, (size_t)n_rows * O));
-        if (int rc = each_block(n_rows, rows_blk, [&](long long r0, int nr) -> int {
-            if (int rc = fwd.run(h, d.base, d.run_off, d_x, xs, (int)r0, nr, U, d_fx)) return rc;
-            PredictRed ra{d_fx, d.run_cnt, U, O, (int)r0 * O, n_rows * O, S, 0, nullptr, d_mean, nullptr, nullptr};
+        HIP_TRY(f.mem.alloc(&d_mean, (size_t)n_rows * O));
+        if (int rc = f.each_rows(h, n_rows, [&](long long r0, int nr) -> int {
+            PredictRed ra{f.d_fx, f.d.run_cnt, U, O, (int)r0 * O, n_rows * O, f.M, 0, nullptr, d_mean, nullptr, nullptr};
             HIP_TRY(launch(predict_reduce_kernel, dim3((unsigned)(nr * O)), dim3(PRED_THREADS), 0, st, ra));
             return 0;
         })) return rc;
@@ -2671,52 +2751,11 @@ int ptnn_calibration(ptnn_handle* h, const ptnn_calibration_spec* spec) {
         return wait_stream(h);
     }
 
-    double *d_tau2 = nullptr, *d_tau = nullptr, *d_itau = nullptr;
-    double *d_pit = nullptr, *d_crps = nullptr, *d_mean = nullptr, *d_sd = nullptr, *d_q = nullptr, *d_t1 = nullptr, *d_bound = nullptr;
-    unsigned long long* d_limbs = nullptr;
-    HIP_TRY(mem.alloc(&d_tau2, (size_t)U));
-    HIP_TRY(mem.alloc(&d_tau, (size_t)U));
-    HIP_TRY(mem.alloc(&d_itau, (size_t)U));
-    HIP_TRY(mem.alloc(&d_pit, (size_t)n_rows));
-    HIP_TRY(mem.alloc(&d_mean, (size_t)n_rows));
-    HIP_TRY(mem.alloc(&d_sd, (size_t)n_rows));
-    if (s.n_levels) HIP_TRY(mem.alloc(&d_q, (size_t)s.n_levels * n_rows));
-    if (s.pair_term) {
-        HIP_TRY(mem.alloc(&d_crps, (size_t)n_rows));
-        HIP_TRY(mem.alloc(&d_t1, (size_t)n_rows));
-        HIP_TRY(mem.alloc(&d_bound, (size_t)n_rows));
-        HIP_TRY(mem.alloc(&d_limbs, (size_t)n_rows * 4));
-        HIP_TRY(hipMemsetAsync(d_limbs, 0, (size_t)n_rows * 4 * sizeof(unsigned long long), st));
-    }
-    HIP_TRY(launch(calib_tau_kernel, dim3((unsigned)((U + CALIB_THREADS - 1) / CALIB_THREADS)), dim3(CALIB_THREADS), 0, st, U, d.run_eta,
-                   d_tau2, d_tau, d_itau));
-    CalibRow ra{};
-    ra.fx = d_fx; ra.tau2 = d_tau2; ra.tau = d_tau; ra.itau = d_itau; ra.cnt = d.run_cnt; ra.y = d_x + I; ra.ys = xs; ra.U = U;
-    ra.n_rows = n_rows; ra.S = S; ra.n_levels = s.n_levels; ra.pair = s.pair_term ? 1 : 0;
-    for (int k = 0; k < s.n_levels; ++k) { ra.p[k] = s.levels_p[k]; ra.z[k] = s.levels_z[k]; }
-    ra.pit = d_pit; ra.pred_mean = d_mean; ra.pred_sd = d_sd; ra.quantiles = d_q; ra.term1 = d_t1; ra.pair_bound = d_bound;
-    const int n_tiles = (U + CALIB_THREADS - 1) / CALIB_THREADS;
-    CalibPair pa{d_fx, d_tau2, d.run_cnt, d_bound, U, 0, 0, n_tiles, d_limbs};
-    const unsigned n_tri = (unsigned)((long long)n_tiles * (n_tiles + 1) / 2);
-    if (int rc = each_block(n_rows, rows_blk, [&](long long r0, int nr) -> int {
-        if (int rc = fwd.run(h, d.base, d.run_off, d_x, xs, (int)r0, nr, U, d_fx)) return rc;
-        ra.row0 = (int)r0;
-        HIP_TRY(launch(calib_row_kernel, dim3((unsigned)nr), dim3(CALIB_THREADS), 0, st, ra));
-        // the pair term of this block's rows, at most 65535 rows (grid.y) per launch
-        for (int q0 = 0; s.pair_term && q0 < nr; q0 += 65535) {
-            pa.row0 = (int)r0; pa.r0 = q0;
-            HIP_TRY(launch(calib_pair_kernel, dim3(n_tri, (unsigned)std::min(65535, nr - q0)), dim3(CALIB_THREADS), 0, st, pa));
-        }
-        return 0;
-    })) return rc;
-    if (s.pair_term)
-        HIP_TRY(launch(calib_finish_kernel, dim3((unsigned)((n_rows + CALIB_THREADS - 1) / CALIB_THREADS)), dim3(CALIB_THREADS), 0, st, n_rows,
-                       d_limbs, d_t1, d_bound, S, d_crps));
-    HIP_TRY(fetch(s.pit, d_pit, (size_t)n_rows, st));
-    HIP_TRY(fetch(s.pred_mean, d_mean, (size_t)n_rows, st));
-    HIP_TRY(fetch(s.pred_sd, d_sd, (size_t)n_rows, st));
-    HIP_TRY(fetch(s.quantiles, d_q, (size_t)s.n_levels * n_rows, st));
-    HIP_TRY(fetch(s.crps, d_crps, (size_t)n_rows, st));
+    MixtureColumns<ptnn_calibration_spec> mc{h, f, s, n_rows, false};
+    if (int rc = mc.alloc(f.d_fx, f.d_x + I, f.xs)) return rc;
+    if (int rc = f.each_rows(h, n_rows, [&](long long r0, int nr) { return mc.block(r0, nr); })) return rc;
+    if (int rc = mc.finish()) return rc;
+    if (int rc = mc.fetch()) return rc;
     return wait_stream(h);
 }
 
@@ -2726,10 +2765,11 @@ int ptnn_forecast_score(ptnn_handle* h, const ptnn_forecast_score_spec* spec) {
     if (int rc = check_spec(spec, "ptnn_forecast_score_spec")) return rc;
     const ptnn_forecast_score_spec& s = *spec;
     const bool host_src = s.w != nullptr, noise = s.noise != 0, pair = s.pair_term != 0, energy = s.energy != 0;
-    SampleSource src = source_of(s, host_src, s.eta);
-    const RowSource rows{s.origin_source, s.origins, s.n_origins, "origin_source", "PTNN_FORECAST_ORIGIN", "origins", "n_origins"};
-    if (int rc = check_source(src, "vectors")) return rc;
-    if (int rc = check_rows(rows)) return rc;
+    RowsByVectors f(s, RowSource{s.origin_source, s.origins, s.n_origins, "origin_source", "PTNN_FORECAST_ORIGIN", "origins", "n_origins"},
+                    host_src);
+    SampleSource& src = f.src;
+    if (int rc = check_source(src, "vectors")) return rc;      // (an empty trace selection is refused with the handle)
+    if (int rc = check_rows(f.rows)) return rc;
     if (s.n_origins < 1) return fail(-1, "n_origins = %d must be >= 1", s.n_origins);
     if (s.horizon < 1) return fail(-1, "horizon = %d must be >= 1", s.horizon);
     const long long ncols = (long long)s.n_origins * s.horizon;
@@ -2745,47 +2785,33 @@ int ptnn_forecast_score(ptnn_handle* h, const ptnn_forecast_score_spec* spec) {
         if (v == v) { const size_t r = (size_t)(c / hz); klist[r * hz + nk[r]++] = (int)(c % hz); ++n_finite; }
     }
     if (n_finite == 0) return fail(-1, "truth holds no finite entry: nothing to score");
-    if (s.n_levels < 0 || s.n_levels > CALIB_MAX_LEVELS) return fail(-1, "n_levels = %d outside [0, %d]", s.n_levels, CALIB_MAX_LEVELS);
-    if (s.n_levels > 0 && (!s.levels_p || !s.levels_z || !s.quantiles))
-        return fail(-1, "n_levels = %d needs levels_p, levels_z and quantiles", s.n_levels);
-    if (s.quantiles && s.n_levels == 0) return fail(-1, "quantiles requested without levels");
-    for (int k = 0; k < s.n_levels; ++k)
-        if (!(s.levels_p[k] > 0.0 && s.levels_p[k] < 1.0) || !std::isfinite(s.levels_z[k]))
-            return fail(-1, "levels_p[%d] = %g (levels_z %g): a quantile level lies in (0, 1)", k, s.levels_p[k], s.levels_z[k]);
-    if (s.crps && !pair) return fail(-1, "crps requested without pair_term");
+    if (int rc = MixtureColumns<ptnn_forecast_score_spec>::check(s)) return rc;
     if (s.energy_score && !energy) return fail(-1, "energy_score requested without energy");
     if (energy && hz > PTNN_FSCORE_MAX_ENERGY_HORIZON)
         return fail(-1, "energy: horizon = %d, the energy score takes paths of at most %d steps (energy=False)", hz, PTNN_FSCORE_MAX_ENERGY_HORIZON);
     if (noise && host_src && !s.eta) return fail(-1, "noise: host vectors need eta = log tau^2 (one per vector)");
-    if (int rc = count_host_samples(src)) return rc;
+    if (int rc = f.count_host()) return rc;
     if (int rc = check_handle(h, "ptnn_forecast_score")) return rc;
     if (h->cfg.task != PTNN_TASK_REG || h->cfg.n_out != 1)
         return fail(-1, "forecast verification needs a regression net with n_out == 1 (a one-step map of one series); this handle is a "
                         "%s net with n_out = %d", h->cfg.task == PTNN_TASK_REG ? "regression" : "classification", h->cfg.n_out);
     const int I = h->cfg.n_in, P = h->P;
-    if (int rc = need_eta(h, src)) return rc;
-    if (int rc = fit_rows(h, rows)) return rc;
-    if (int rc = select_samples(h, src, true)) return rc;
-    const long long M = src.M;
-    if (s.n_samples) *s.n_samples = M;
+    if (int rc = f.fit(h)) return rc;
+    if (int rc = f.select(h, s.n_samples)) return rc;
+    const long long M = f.M;
     const char* cap_text = "%lld trajectories: the pair term of the CRPS and the energy score take at most %d (U^2 / 2 terms per column or "
                            "origin); select fewer samples (thin=, chains=) or leave them out (crps=False, energy=False)";
     if ((pair || energy) && noise && M > CALIB_MAX_DISTINCT) return fail(-1, cap_text, M, CALIB_MAX_DISTINCT);
 
-    if (int rc = start_device(h)) return rc;
-    hipStream_t st = h->stream;
-    DeviceScratch mem;
-    const float* d_x = nullptr;
-    int xs = 0;
-    if (int rc = upload_rows(h, mem, rows, I, &d_x, &xs)) return rc;
     // stage a, as ptnn_forecast: noise on -- every occurrence its own trajectory, host multiplicities expanded; noise off -- the
     // distinct (w, eta) samples with their multiplicities
     std::vector<float> w_exp, eta_exp;
-    if (noise) expand_occurrences(src, P, &w_exp, &eta_exp);
-    Distinct d;
-    if (int rc = distinct_samples(h, mem, src, true, !noise, &d)) return rc;
-    const int U = d.U;
-    if (s.n_trajectories) *s.n_trajectories = U;
+    f.eta = true; f.merge = !noise;
+    if (int rc = f.stage(h, I, s.n_trajectories, [&] { if (noise) expand_occurrences(src, P, &w_exp, &eta_exp); return 0; })) return rc;
+    hipStream_t st = h->stream;
+    DeviceScratch& mem = f.mem;
+    const Distinct& d = f.d;
+    const int U = f.U;
     if ((pair || energy) && U > CALIB_MAX_DISTINCT) return fail(-1, cap_text, (long long)U, CALIB_MAX_DISTINCT);
     // blocks: 4 U bytes per column for the paths, as much again for mu when the noise makes them differ.  With the energy score a
     // block is whole origins; else origins and horizon steps as ptnn_forecast blocks them (the windows carried)
@@ -2810,42 +2836,25 @@ int ptnn_forecast_score(ptnn_handle* h, const ptnn_forecast_score_spec* spec) {
     if (split_h) HIP_TRY(mem.alloc(&d_win, (size_t)U * I));
     HIP_TRY(mem.upload(&d_truth, s.truth, (size_t)ncols, st));
     ForecastPlan fwd;
-    if (int rc = fwd.init(h, d, d_x, xs, hz, d_win, noise, s.seed, d_fx, d_mu)) return rc;
-    std::vector<int> item_run;
-    if (s.samples || s.means) if (int rc = item_runs(h, d, src.n_items, &item_run)) return rc;
-    // per-column and per-origin results: NaN (all bits set) wherever nothing is scored
-    double *d_tau2 = nullptr, *d_tau = nullptr, *d_itau = nullptr;
-    double *d_pit = nullptr, *d_crps = nullptr, *d_log = nullptr, *d_mean = nullptr, *d_sd = nullptr, *d_q = nullptr, *d_t1 = nullptr, *d_bound = nullptr;
-    double *d_es = nullptr, *d_et1 = nullptr, *d_eb = nullptr;
-    unsigned long long *d_limbs = nullptr, *d_elimbs = nullptr;
+    if (int rc = fwd.init(h, d, f.d_x, f.xs, hz, d_win, noise, s.seed, d_fx, d_mu)) return rc;
+    if (int rc = f.items(h, s.samples || s.means)) return rc;
+    // per-column and per-origin results: NaN (all bits set) wherever nothing is scored.  The mixture's columns read mu of the
+    // block's columns; the log score and the energy score are this call's own
+    const float* d_m = noise ? d_mu : d_fx;
+    MixtureColumns<ptnn_forecast_score_spec> mc{h, f, s, ncols, true};
+    if (int rc = mc.alloc(d_m, d_truth, 1)) return rc;
+    double *d_log = nullptr, *d_es = nullptr, *d_et1 = nullptr, *d_eb = nullptr;
+    unsigned long long* d_elimbs = nullptr;
     int *d_klist = nullptr, *d_nk = nullptr;
-    const auto nan_doubles = [&](double** p, size_t n) -> hipError_t {
-        const hipError_t e = mem.alloc(p, n);
-        return e != hipSuccess ? e : hipMemsetAsync(*p, 0xff, n * sizeof(double), st);
-    };
-    HIP_TRY(mem.alloc(&d_tau2, (size_t)U));
-    HIP_TRY(mem.alloc(&d_tau, (size_t)U));
-    HIP_TRY(mem.alloc(&d_itau, (size_t)U));
-    HIP_TRY(nan_doubles(&d_pit, (size_t)ncols));
-    HIP_TRY(nan_doubles(&d_mean, (size_t)ncols));
-    HIP_TRY(nan_doubles(&d_sd, (size_t)ncols));
-    HIP_TRY(nan_doubles(&d_log, (size_t)ncols));
-    if (s.n_levels) HIP_TRY(nan_doubles(&d_q, (size_t)s.n_levels * ncols));
-    if (pair) {
-        HIP_TRY(nan_doubles(&d_crps, (size_t)ncols));
-        HIP_TRY(nan_doubles(&d_t1, (size_t)ncols));
-        HIP_TRY(nan_doubles(&d_bound, (size_t)ncols));
-        HIP_TRY(mem.alloc(&d_limbs, (size_t)ncols * 4));
-        HIP_TRY(hipMemsetAsync(d_limbs, 0, (size_t)ncols * 4 * sizeof(unsigned long long), st));
-    }
-    const int n_tiles = (U + CALIB_THREADS - 1) / CALIB_THREADS;
-    const unsigned n_tri = (unsigned)((long long)n_tiles * (n_tiles + 1) / 2);
+    HIP_TRY(mc.column(&d_log, (size_t)ncols));
+    const int n_tiles = mc.n_tiles;
+    const unsigned n_tri = mc.n_tri;
     FscoreEnergy ea{};
     size_t e_lds = 0;
     if (energy) {
-        HIP_TRY(nan_doubles(&d_es, (size_t)n_org));
-        HIP_TRY(nan_doubles(&d_et1, (size_t)n_org));
-        HIP_TRY(nan_doubles(&d_eb, (size_t)n_org));
+        HIP_TRY(mc.column(&d_es, (size_t)n_org));
+        HIP_TRY(mc.column(&d_et1, (size_t)n_org));
+        HIP_TRY(mc.column(&d_eb, (size_t)n_org));
         HIP_TRY(mem.alloc(&d_elimbs, (size_t)n_org * 4));
         HIP_TRY(hipMemsetAsync(d_elimbs, 0, (size_t)n_org * 4 * sizeof(unsigned long long), st));
         HIP_TRY(mem.upload(&d_klist, klist.data(), klist.size(), st));
@@ -2857,15 +2866,6 @@ int ptnn_forecast_score(ptnn_handle* h, const ptnn_forecast_score_spec* spec) {
         ea.fx = d_fx; ea.cnt = d.run_cnt; ea.y = d_truth; ea.klist = d_klist; ea.nk = d_nk; ea.U = U; ea.hz = hz; ea.S = M;
         ea.term1 = d_et1; ea.bound = d_eb; ea.n_tiles = n_tiles; ea.JW = JW; ea.limbs = d_elimbs;
     }
-    HIP_TRY(launch(calib_tau_kernel, dim3((unsigned)((U + CALIB_THREADS - 1) / CALIB_THREADS)), dim3(CALIB_THREADS), 0, st, U, d.run_eta,
-                   d_tau2, d_tau, d_itau));
-    const float* d_m = noise ? d_mu : d_fx;            // mu of the block's columns
-    CalibRow ra{};
-    ra.fx = d_m; ra.tau2 = d_tau2; ra.tau = d_tau; ra.itau = d_itau; ra.cnt = d.run_cnt; ra.y = d_truth; ra.ys = 1; ra.U = U;
-    ra.n_rows = (int)ncols; ra.S = M; ra.n_levels = s.n_levels; ra.pair = pair ? 1 : 0; ra.skip_nan = 1;
-    for (int k = 0; k < s.n_levels; ++k) { ra.p[k] = s.levels_p[k]; ra.z[k] = s.levels_z[k]; }
-    ra.pit = d_pit; ra.pred_mean = d_mean; ra.pred_sd = d_sd; ra.quantiles = d_q; ra.term1 = d_t1; ra.pair_bound = d_bound;
-    CalibPair pa{d_m, d_tau2, d.run_cnt, d_bound, U, 0, 0, n_tiles, d_limbs, d_truth};
     FscoreLog la{d_m, d.run_eta, d.run_cnt, d_truth, U, 0, M, d_log};
     for (long long r0 = 0; r0 < n_org; r0 += ob) {
         const int nr = (int)std::min<long long>(ob, n_org - r0);
@@ -2874,12 +2874,7 @@ int ptnn_forecast_score(ptnn_handle* h, const ptnn_forecast_score_spec* spec) {
             if (int rc = fwd.run(h, (int)r0, nr, (int)k0, nk_blk)) return rc;
             const long long col0 = r0 * hz + k0;             // the block's columns are contiguous (split_h: one origin per block)
             const int nc = nr * nk_blk;                      // <= 65535
-            ra.row0 = (int)col0;
-            HIP_TRY(launch(calib_row_kernel, dim3((unsigned)nc), dim3(CALIB_THREADS), 0, st, ra));
-            if (pair) {
-                pa.row0 = (int)col0; pa.r0 = 0;
-                HIP_TRY(launch(calib_pair_kernel, dim3(n_tri, (unsigned)nc), dim3(CALIB_THREADS), 0, st, pa));
-            }
+            if (int rc = mc.block(col0, nc)) return rc;
             la.col0 = (int)col0;
             HIP_TRY(launch(fscore_logscore_kernel, dim3((unsigned)nc), dim3(FSCORE_THREADS), 0, st, la));
             if (energy) {                                    // hb == hz: whole origins
@@ -2888,23 +2883,17 @@ int ptnn_forecast_score(ptnn_handle* h, const ptnn_forecast_score_spec* spec) {
                 HIP_TRY(launch(fscore_energy_kernel, dim3(n_tri, (unsigned)nr), dim3(FSCORE_THREADS), e_lds, st, ea));
             }
             if (s.samples)
-                if (int rc = scatter_samples(h, d_fx, nc, U, item_run, src.weights(), s.samples, (size_t)ncols, (size_t)col0)) return rc;
+                if (int rc = scatter_samples(h, d_fx, nc, U, f.item_run, src.weights(), s.samples, (size_t)ncols, (size_t)col0)) return rc;
             if (s.means)
-                if (int rc = scatter_samples(h, d_m, nc, U, item_run, src.weights(), s.means, (size_t)ncols, (size_t)col0)) return rc;
+                if (int rc = scatter_samples(h, d_m, nc, U, f.item_run, src.weights(), s.means, (size_t)ncols, (size_t)col0)) return rc;
         }
     }
-    if (pair)
-        HIP_TRY(launch(calib_finish_kernel, dim3((unsigned)((ncols + CALIB_THREADS - 1) / CALIB_THREADS)), dim3(CALIB_THREADS), 0, st, (int)ncols,
-                       d_limbs, d_t1, d_bound, M, d_crps));
+    if (int rc = mc.finish()) return rc;
     if (energy)
         HIP_TRY(launch(fscore_energy_finish_kernel, dim3((unsigned)((n_org + FSCORE_THREADS - 1) / FSCORE_THREADS)), dim3(FSCORE_THREADS), 0, st,
                        n_org, d_nk, d_elimbs, d_et1, d_eb, M, d_es));
-    HIP_TRY(fetch(s.pit, d_pit, (size_t)ncols, st));
-    HIP_TRY(fetch(s.pred_mean, d_mean, (size_t)ncols, st));
-    HIP_TRY(fetch(s.pred_sd, d_sd, (size_t)ncols, st));
+    if (int rc = mc.fetch()) return rc;
     HIP_TRY(fetch(s.log_score, d_log, (size_t)ncols, st));
-    HIP_TRY(fetch(s.quantiles, d_q, (size_t)s.n_levels * ncols, st));
-    HIP_TRY(fetch(s.crps, d_crps, (size_t)ncols, st));
     HIP_TRY(fetch(s.energy_score, d_es, (size_t)n_org, st));
     return wait_stream(h);
 }
@@ -2916,11 +2905,10 @@ int ptnn_ppc(ptnn_handle* h, const ptnn_ppc_spec* spec) {
     // argument checks first: none of them needs the handle or a device
     if (int rc = check_spec(spec, "ptnn_ppc_spec")) return rc;
     const ptnn_ppc_spec& s = *spec;
-    SampleSource src = source_of(s, s.w != nullptr, s.eta);
-    const RowSource rows{s.x_source, s.x, s.n_rows, "x_source", "PTNN_PREDICT_X", "x", "n_rows"};
-    if (int rc = check_source(src, "samples", true)) return rc;
+    RowsByVectors f(s, x_rows(s), s.w != nullptr);
+    if (int rc = f.check_source()) return rc;
     if (s.n_rows < 2) return fail(-1, "n_rows = %d: a posterior predictive check needs at least 2 data rows", s.n_rows);
-    if (int rc = check_rows(rows)) return rc;
+    if (int rc = check_rows(f.rows)) return rc;
     if (s.n_lags < 0 || s.n_lags > PPC_MAX_LAGS) return fail(-1, "n_lags = %d outside [0, %d]", s.n_lags, PPC_MAX_LAGS);
     if (s.n_lags > 0 && !s.lags) return fail(-1, "n_lags = %d but lags is NULL", s.n_lags);
     for (int k = 0; k < s.n_lags; ++k) {
@@ -2929,7 +2917,7 @@ int ptnn_ppc(ptnn_handle* h, const ptnn_ppc_spec* spec) {
         for (int j = 0; j < k; ++j)
             if (s.lags[j] == s.lags[k]) return fail(-1, "lags[%d] = lags[%d] = %d: a lag may be listed once", j, k, s.lags[k]);
     }
-    if (int rc = count_host_samples(src)) return rc;
+    if (int rc = f.count_host()) return rc;
     if (int rc = check_handle(h, "ptnn_ppc")) return rc;
     const int I = h->cfg.n_in, O = h->cfg.n_out;
     const bool reg = h->cfg.task == PTNN_TASK_REG;
@@ -2937,10 +2925,9 @@ int ptnn_ppc(ptnn_handle* h, const ptnn_ppc_spec* spec) {
     if (!reg && s.n_lags > 0) return fail(-1, "lags: a classification has no residual autocorrelation");
     if (!reg && s.z) return fail(-1, "z: a classification draws classes, not normal deviates");
     if (reg && s.y_rep) return fail(-1, "y_rep: a regression's replicate is f + tau z; request z");
-    if (int rc = need_eta(h, src)) return rc;
-    if (int rc = fit_rows(h, rows)) return rc;
-    if (int rc = select_samples(h, src, true)) return rc;
-    const long long M = src.M;
+    if (int rc = f.fit(h)) return rc;
+    if (int rc = f.select(h, nullptr)) return rc;
+    const long long M = f.M;
     const int N = s.n_rows;
     const int n_stats = reg ? PPC_REG_FIXED + s.n_lags : PPC_CLS_FIXED + O;
     // a wave keeps its series in LDS: N doubles (regression), one counter per class (classification)
@@ -2951,24 +2938,20 @@ int ptnn_ppc(ptnn_handle* h, const ptnn_ppc_spec* spec) {
     if ((long long)N > 65535LL * WAVE) return fail(-1, "n_rows = %d: at most %lld rows per call", N, 65535LL * WAVE);
     if (s.n_samples) *s.n_samples = M;
 
-    if (int rc = start_device(h)) return rc;
-    hipStream_t st = h->stream;
-    DeviceScratch mem;
-    const float* d_x = nullptr;
-    int xs = 0;
-    if (int rc = upload_rows(h, mem, rows, I + 1, &d_x, &xs)) return rc;
     // stage a: items -> distinct (w, eta) samples (a classification's: distinct w, as ptnn_predict's)
-    Distinct d;
-    if (int rc = distinct_samples(h, mem, src, reg, true, &d)) return rc;
-    const int U = d.U;
-    if (s.n_distinct) *s.n_distinct = U;
+    f.eta = reg;
+    if (int rc = f.stage(h, I + 1, s.n_distinct)) return rc;
+    hipStream_t st = h->stream;
+    DeviceScratch& mem = f.mem;
+    const Distinct& d = f.d;
+    const std::vector<int>& item_run = f.item_run;
+    const int U = f.U;
     // the distinct vector of every occurrence, chain-major with the multiplicities expanded: non-decreasing
-    std::vector<int> item_run;
-    if (int rc = item_runs(h, d, src.n_items, &item_run)) return rc;
+    if (int rc = f.items(h, true)) return rc;
     if (int rc = wait_stream(h)) return rc;
     std::vector<int> occ_u;
     occ_u.reserve((size_t)M);
-    const int32_t* mult = src.weights();
+    const int32_t* mult = f.src.weights();
     for (size_t k = 0; k < item_run.size(); ++k) {
         if (item_run[k] < 0 || item_run[k] >= U || (!occ_u.empty() && item_run[k] < occ_u.back()))
             return fail(-2, "run-length pass: item %lld belongs to run %d of %d (internal error)", (long long)k, item_run[k], U);
@@ -2990,14 +2973,14 @@ int ptnn_ppc(ptnn_handle* h, const ptnn_ppc_spec* spec) {
                                                                             ((size_t)N * O * sizeof(float))), U));
     float* d_fx = nullptr;
     HIP_TRY(mem.alloc(&d_fx, (size_t)vec_blk * N * O));
-    ForwardPlan fwd;
-    if (int rc = fwd.init(h, "posterior predictive check")) return rc;
+    const ForwardPlan& fwd = f.fwd;
+    if (int rc = f.fwd.init(h, "posterior predictive check")) return rc;
     const int waves = (int)std::max<size_t>(1, std::min<size_t>(PPC_THREADS / WAVE, (64 * 1024) / (wave_doubles * sizeof(double))));
     const size_t lds = (size_t)waves * wave_doubles * sizeof(double);
     const auto kernel = reg ? ppc_occurrence_kernel<true> : ppc_occurrence_kernel<false>;
     if (int rc = raise_lds_limit(reinterpret_cast<const void*>(kernel), lds)) return rc;
     PpcJob ja{};
-    ja.n_rows = N; ja.O = O; ja.fx = d_fx; ja.eta = d.run_eta; ja.y = d_x + I; ja.ys = xs;
+    ja.n_rows = N; ja.O = O; ja.fx = d_fx; ja.eta = d.run_eta; ja.y = f.d_x + I; ja.ys = f.xs;
     ja.n_lags = s.n_lags;
     for (int k = 0; k < s.n_lags; ++k) ja.lags[k] = s.lags[k];
     split_seed(s.seed, &ja.seed_lo, &ja.seed_hi);
@@ -3005,7 +2988,7 @@ int ptnn_ppc(ptnn_handle* h, const ptnn_ppc_spec* spec) {
     ja.t_obs = d_tobs; ja.t_rep = d_trep; ja.z = d_z; ja.y_rep = d_yrep;
     for (long long u0 = 0; u0 < U; u0 += vec_blk) {
         const int nu = (int)std::min<long long>(vec_blk, U - u0);
-        if (int rc = fwd.run(h, d.base, d.run_off + u0, d_x, xs, 0, N, nu, d_fx)) return rc;
+        if (int rc = fwd.run(h, d.base, d.run_off + u0, f.d_x, f.xs, 0, N, nu, d_fx)) return rc;
         const long long i0 = std::lower_bound(occ_u.begin(), occ_u.end(), (int)u0) - occ_u.begin();
         const long long i1 = std::lower_bound(occ_u.begin(), occ_u.end(), (int)(u0 + nu)) - occ_u.begin();
         ja.nu = nu; ja.u0 = (int)u0; ja.i0 = i0; ja.n_occ = (int)(i1 - i0);
@@ -3054,8 +3037,7 @@ int ptnn_powerscale(ptnn_handle* h, const ptnn_powerscale_spec* spec) {
     // argument checks first: none of them needs the handle or a device
     if (int rc = check_spec(spec, "ptnn_powerscale_spec")) return rc;
     const ptnn_powerscale_spec& s = *spec;
-    SampleSource src = source_of(s, s.w != nullptr, s.eta);
-    const RowSource rows{s.x_source, s.x, s.n_rows, "x_source", "PTNN_PREDICT_X", "x", "n_rows"};
+    RowsByVectors f(s, x_rows(s), s.w != nullptr);
     constexpr int all_groups = PTNN_POWERSCALE_WEIGHTS | PTNN_POWERSCALE_ETA | PTNN_POWERSCALE_PREDICTIONS | PTNN_POWERSCALE_LOGLIK;
     const bool g_w = s.groups & PTNN_POWERSCALE_WEIGHTS, g_eta = s.groups & PTNN_POWERSCALE_ETA,
                g_pred = s.groups & PTNN_POWERSCALE_PREDICTIONS, g_ll = s.groups & PTNN_POWERSCALE_LOGLIK;
@@ -3063,21 +3045,19 @@ int ptnn_powerscale(ptnn_handle* h, const ptnn_powerscale_spec* spec) {
     if (int rc = check_r_eff(s.r_eff)) return rc;
     if (s.groups == 0 || (s.groups & ~all_groups))
         return fail(-1, "groups = 0x%x: choose among PTNN_POWERSCALE_WEIGHTS, _ETA, _PREDICTIONS and _LOGLIK", (unsigned)s.groups);
-    if (int rc = check_source(src, "samples", true)) return rc;
+    if (int rc = f.check_source()) return rc;
     if (g_pred) {
         if (s.n_rows < 1) return fail(-1, "n_rows = %d must be >= 1", s.n_rows);
-        if (int rc = check_rows(rows)) return rc;
+        if (int rc = check_rows(f.rows)) return rc;
     }
-    if (int rc = count_host_samples(src)) return rc;
+    if (int rc = f.count_host()) return rc;
     if (int rc = check_handle(h, "ptnn_powerscale")) return rc;
     const int I = h->cfg.n_in, H = h->cfg.n_hidden, O = h->cfg.n_out, P = h->P, Ntr = h->Ntr;
     const bool reg = h->cfg.task == PTNN_TASK_REG;
     if (g_eta && !reg) return fail(-1, "PTNN_POWERSCALE_ETA: a classification has no eta");
-    if (int rc = need_eta(h, src)) return rc;
-    if (g_pred)
-        if (int rc = fit_rows(h, rows)) return rc;
-    if (int rc = select_samples(h, src, true, "importance weights need at least 2")) return rc;
-    const long long M = src.M;
+    if (int rc = f.fit(h, g_pred)) return rc;
+    if (int rc = f.select(h, nullptr, "importance weights need at least 2")) return rc;
+    const long long M = f.M;
     long long Mt = 0;
     if (int rc = psis_tail(M, s.r_eff, &Mt)) return rc;
     const long long n_pred = g_pred ? (long long)s.n_rows * O : 0;
@@ -3087,20 +3067,19 @@ int ptnn_powerscale(ptnn_handle* h, const ptnn_powerscale_spec* spec) {
     if (s.n_samples) *s.n_samples = M;
     if (s.n_quantities) *s.n_quantities = Q;
 
-    if (int rc = start_device(h)) return rc;
+    // stage a: items -> distinct (w, eta) samples (a classification's: distinct w); the rows follow with the predictions
+    f.eta = reg;
+    if (int rc = f.stage(h, 0, s.n_distinct)) return rc;
     hipStream_t st = h->stream;
-    DeviceScratch mem;
-    // stage a: items -> distinct (w, eta) samples (a classification's: distinct w)
-    Distinct d;
-    if (int rc = distinct_samples(h, mem, src, reg, true, &d)) return rc;
-    const int U = d.U;
-    if (s.n_distinct) *s.n_distinct = U;
+    DeviceScratch& mem = f.mem;
+    const Distinct& d = f.d;
+    const int U = f.U;
     if (U > PS_MAX_DISTINCT)
         return fail(-1, "%d distinct samples: power-scaling orders every quantity over all of them, at most %d; thin= lowers the "
                         "number of distinct samples", U, PS_MAX_DISTINCT);
     const size_t budget = scratch_budget("PTNN_POWERSCALE_SCRATCH_BYTES");
-    ForwardPlan fwd;
-    if (int rc = fwd.init(h, "power-scaling sensitivity")) return rc;
+    const ForwardPlan& fwd = f.fwd;
+    if (int rc = f.fwd.init(h, "power-scaling sensitivity")) return rc;
 
     // 1. the components: l_u over the training rows in blocks of rows, pi_u from w and eta
     double* d_logp = nullptr;
@@ -3194,13 +3173,9 @@ int ptnn_powerscale(ptnn_handle* h, const ptnn_powerscale_spec* spec) {
         q_at += 1;
     }
     if (g_pred) {
-        const float* d_x = nullptr;
-        int xs = 0;
-        if (int rc = upload_rows(h, mem, rows, I, &d_x, &xs)) return rc;
-        if (int rc = each_block(s.n_rows, rows_q, [&](long long r0, int nr) -> int {
-            if (int rc = fwd.run(h, d.base, d.run_off, d_x, xs, (int)r0, nr, U, d_fx)) return rc;
-            return plain(d_fx, nullptr, nr * O, q_at + (int)r0 * O);
-        })) return rc;
+        if (int rc = upload_rows(h, mem, f.rows, I, &f.d_x, &f.xs)) return rc;
+        f.rows_blk = rows_q; f.d_fx = d_fx;              // the predictions' blocks share the budget of the quantities
+        if (int rc = f.each_rows(h, s.n_rows, [&](long long r0, int nr) { return plain(d_fx, nullptr, nr * O, q_at + (int)r0 * O); })) return rc;
         q_at += (int)n_pred;
     }
     if (g_ll)
@@ -3499,14 +3474,13 @@ int ptnn_uncertainty(ptnn_handle* h, const ptnn_uncertainty_spec* spec) {
     // argument checks first: none of them needs the handle or a device
     if (int rc = check_spec(spec, "ptnn_uncertainty_spec")) return rc;
     const ptnn_uncertainty_spec& s = *spec;
-    SampleSource src = source_of(s, s.w != nullptr, s.eta);
-    const RowSource rows{s.x_source, s.x, s.n_rows, "x_source", "PTNN_PREDICT_X", "x", "n_rows"};
-    RankOutputs rk{s.n_ranks, s.ranks, s.entropy_order_stats};
-    if (int rc = check_source(src, "samples", true)) return rc;
-    if (int rc = check_rows(rows)) return rc;
+    RowsByVectors f(s, x_rows(s), s.w != nullptr, RankOutputs{s.n_ranks, s.ranks, s.entropy_order_stats});
+    RankOutputs& rk = f.rk;
+    if (int rc = f.check_source()) return rc;
+    if (int rc = check_rows(f.rows)) return rc;
     if (s.n_rows < 1) return fail(-1, "n_rows = %d must be >= 1", s.n_rows);
     if (int rc = rk.check()) return rc;
-    if (int rc = count_host_samples(src)) return rc;
+    if (int rc = f.count_host()) return rc;
     if (int rc = check_handle(h, "ptnn_uncertainty")) return rc;
     const int I = h->cfg.n_in, O = h->cfg.n_out, N = s.n_rows;
     const bool reg = h->cfg.task == PTNN_TASK_REG;
@@ -3514,25 +3488,17 @@ int ptnn_uncertainty(ptnn_handle* h, const ptnn_uncertainty_spec* spec) {
         return fail(-1, "vote, entropy_mean, entropy_order_stats and sample_entropy: a regression has no class probabilities");
     if (!reg && (s.epistemic_var || s.aleatoric_var))
         return fail(-1, "epistemic_var and aleatoric_var: a classification has no output variance and no eta");
-    if (int rc = need_eta(h, src)) return rc;
-    if (int rc = fit_rows(h, rows)) return rc;
-    if (int rc = select_samples(h, src, true)) return rc;
-    const long long S = src.M;
-    if (int rc = rk.check_values(S)) return rc;
-    if (s.n_samples) *s.n_samples = S;
+    if (int rc = f.fit(h)) return rc;
+    if (int rc = f.select(h, s.n_samples)) return rc;
+    const long long S = f.M;
 
-    if (int rc = start_device(h)) return rc;
-    hipStream_t st = h->stream;
-    DeviceScratch mem;
-    const int ncols = N * O;
-    const float* d_x = nullptr;
-    int xs = 0;
-    if (int rc = upload_rows(h, mem, rows, I, &d_x, &xs)) return rc;
     // stage a: items -> distinct (w, eta) samples (a classification's: distinct w, as ptnn_predict's)
-    Distinct d;
-    if (int rc = distinct_samples(h, mem, src, reg, true, &d)) return rc;
-    const int U = d.U;
-    if (s.n_distinct) *s.n_distinct = U;
+    f.eta = reg;
+    if (int rc = f.stage(h, I, s.n_distinct)) return rc;
+    hipStream_t st = h->stream;
+    DeviceScratch& mem = f.mem;
+    const Distinct& d = f.d;
+    const int ncols = N * O, U = f.U;
     // the pooled outputs of every column as ptnn_predict's; then per row the entropies, or per column the variance
     const bool image = !reg && (s.n_ranks > 0 || s.sample_entropy);
     double *d_mean = nullptr, *d_hmean = nullptr, *d_emean = nullptr, *d_var = nullptr, *d_noise = nullptr;
@@ -3549,18 +3515,12 @@ int ptnn_uncertainty(ptnn_handle* h, const ptnn_uncertainty_spec* spec) {
         if (int rc = rk.to_device(mem, (size_t)N, st)) return rc;
     }
     // stage b + c in blocks of rows: the forward image U x (rows x O) floats, and the entropy image U x rows, under the budget
-    const long long rows_blk = row_block(scratch_budget("PTNN_UNC_SCRATCH_BYTES"), (size_t)U * sizeof(float) * (O + (image ? 1 : 0)), N);
-    float *d_fx = nullptr, *d_img = nullptr;
-    HIP_TRY(mem.alloc(&d_fx, (size_t)rows_blk * O * U));
-    if (image) HIP_TRY(mem.alloc(&d_img, (size_t)rows_blk * U));
-    ForwardPlan fwd;
-    if (int rc = fwd.init(h, "predictive uncertainty")) return rc;
-    std::vector<int> item_run;
-    if (!reg && s.sample_entropy)
-        if (int rc = item_runs(h, d, src.n_items, &item_run)) return rc;
+    if (int rc = f.forward(h, "PTNN_UNC_SCRATCH_BYTES", 1, (size_t)U * sizeof(float) * (O + (image ? 1 : 0)), N, "predictive uncertainty")) return rc;
+    float *const d_fx = f.d_fx, *d_img = nullptr;
+    if (image) HIP_TRY(mem.alloc(&d_img, (size_t)f.rows_blk * U));
+    if (int rc = f.items(h, !reg && s.sample_entropy)) return rc;
     const double log_k = O > 1 ? std::log((double)O) : 0.0;
-    if (int rc = each_block(N, rows_blk, [&](long long r0, int nr) -> int {
-        if (int rc = fwd.run(h, d.base, d.run_off, d_x, xs, (int)r0, nr, U, d_fx)) return rc;
+    if (int rc = f.each_rows(h, N, [&](long long r0, int nr) -> int {
         PredictRed ra{d_fx, d.run_cnt, U, O, (int)r0 * O, ncols, S, 0, nullptr, d_mean, nullptr, votes.d};
         HIP_TRY(launch(predict_reduce_kernel, dim3((unsigned)(nr * O)), dim3(PRED_THREADS), 0, st, ra));
         if (reg) {
@@ -3574,7 +3534,7 @@ int ptnn_uncertainty(ptnn_handle* h, const ptnn_uncertainty_spec* spec) {
             PredictRed qa{d_img, d.run_cnt, U, 1, (int)r0, N, S, s.n_ranks, rk.d_ranks, d_hmean, rk.d_stats, nullptr};
             HIP_TRY(launch(predict_reduce_kernel, dim3((unsigned)nr), dim3(PRED_THREADS), 0, st, qa));
         }
-        return s.sample_entropy ? scatter_samples(h, d_img, nr, U, item_run, src.weights(), s.sample_entropy, (size_t)N, (size_t)r0) : 0;
+        return s.sample_entropy ? scatter_samples(h, d_img, nr, U, f.item_run, f.src.weights(), s.sample_entropy, (size_t)N, (size_t)r0) : 0;
     })) return rc;
     HIP_TRY(fetch(s.mean, d_mean, (size_t)ncols, st));
     HIP_TRY(votes.fetch(s.vote != nullptr, (size_t)ncols, st));
@@ -3597,11 +3557,13 @@ int ptnn_influence(ptnn_handle* h, const ptnn_influence_spec* spec) {
     const bool mat = s.target_values != nullptr || s.loglik != nullptr;      // source 3
     if (mat && !(s.target_values && s.loglik)) return fail(-1, "host matrices: target_values and loglik come together");
     if (mat && s.w) return fail(-1, "give host vectors w or host matrices (target_values, loglik), not both");
-    SampleSource src = source_of(s, mat || s.w != nullptr, s.eta);
     const bool ll_target = s.target_kind == PTNN_INFLUENCE_LOGLIK;
-    const RowSource cases{s.case_source, s.case_x, s.n_cases, "case_source", "PTNN_PREDICT_X", "case_x", "n_cases"};
+    // the frame's rows are the cases; the targets are a second set of rows beside them
+    RowsByVectors f(s, RowSource{s.case_source, s.case_x, s.n_cases, "case_source", "PTNN_PREDICT_X", "case_x", "n_cases"}, mat || s.w != nullptr);
+    const RowSource& cases = f.rows;
     const RowSource targets{s.target_source, s.target_x, s.n_targets, "target_source", "PTNN_PREDICT_X", "target_x", "n_targets"};
-    if (int rc = check_source(src, "samples", true, "target_values and loglik")) return rc;
+    const SampleSource& src = f.src;
+    if (int rc = f.check_source("target_values and loglik")) return rc;
     if (mat) {
         if (s.n_a < 1 || s.n_b < 1) return fail(-1, "n_a = %d and n_b = %d must be >= 1", s.n_a, s.n_b);
         if ((long long)s.n_a * s.n_b > PTNN_INFLUENCE_MAX_ELEMENTS)
@@ -3613,7 +3575,7 @@ int ptnn_influence(ptnn_handle* h, const ptnn_influence_spec* spec) {
         if (int rc = check_rows(targets)) return rc;
         if (s.n_cases < 1 || s.n_targets < 1) return fail(-1, "n_cases = %d and n_targets = %d must be >= 1", s.n_cases, s.n_targets);
     }
-    if (int rc = count_host_samples(src)) return rc;
+    if (int rc = f.count_host()) return rc;
     if (mat)
         for (long long k = 0; k < src.n_items * s.n_b; ++k)
             if (!std::isfinite(s.loglik[k])) return fail(-1, "loglik[%lld, %lld] = %g is not finite", k / s.n_b, k % s.n_b, s.loglik[k]);
@@ -3623,8 +3585,7 @@ int ptnn_influence(ptnn_handle* h, const ptnn_influence_spec* spec) {
     const int cpr = mat || ll_target ? 1 : O;                   // target columns per target row
     const long long rows_a = mat ? s.n_a : s.n_targets, n_b = mat ? s.n_b : s.n_cases, n_a = rows_a * cpr;
     if (!mat) {
-        if (int rc = need_eta(h, src)) return rc;
-        if (int rc = fit_rows(h, cases)) return rc;
+        if (int rc = f.fit(h)) return rc;
         if (int rc = fit_rows(h, targets)) return rc;
         if (!reg && s.case_source == PTNN_PREDICT_X_HOST)
             if (int rc = check_labels(s.case_x, s.n_cases, I, O)) return rc;
@@ -3633,32 +3594,32 @@ int ptnn_influence(ptnn_handle* h, const ptnn_influence_spec* spec) {
         if (n_a * n_b > PTNN_INFLUENCE_MAX_ELEMENTS)
             return fail(-1, "n_a x n_b = %lld x %lld: at most 2^27 elements per call", n_a, n_b);
     }
-    if (int rc = select_samples(h, src, true, "a covariance (ddof 1) needs at least 2")) return rc;
-    const long long M = src.M;
-    if (s.n_samples) *s.n_samples = M;
+    if (int rc = f.select(h, s.n_samples, "a covariance (ddof 1) needs at least 2")) return rc;
+    const long long M = f.M;
 
-    if (int rc = start_device(h)) return rc;
-    hipStream_t st = h->stream;
-    DeviceScratch mem;
     // stage a: the distinct samples and their counts; every host row of source 3 is a sample of its own
-    Distinct d;
-    const float *d_xc = nullptr, *d_xt = nullptr;
-    int xsc = 0, xst = 0, U = 0;
+    hipStream_t st = h->stream;
+    DeviceScratch& mem = f.mem;
+    const Distinct& d = f.d;
+    const ForwardPlan& fwd = f.fwd;
+    const float* d_xt = nullptr;
+    int xst = 0, U = 0;
     const int* d_cnt = nullptr;
-    ForwardPlan fwd;
     if (mat) {
+        if (int rc = f.start(h)) return rc;
         U = (int)src.n_items;
         int* cnt = nullptr;
         if (int rc = upload_counts(h, mem, s.multiplicity, (size_t)U, &cnt)) return rc;
         d_cnt = cnt;
     } else {
-        if (int rc = upload_rows(h, mem, cases, I + 1, &d_xc, &xsc)) return rc;
-        if (int rc = upload_rows(h, mem, targets, I + (ll_target ? 1 : 0), &d_xt, &xst)) return rc;
-        if (int rc = distinct_samples(h, mem, src, true, true, &d)) return rc;
-        U = d.U;
+        f.eta = true;
+        if (int rc = f.stage(h, I + 1, nullptr, [&] { return upload_rows(h, mem, targets, I + (ll_target ? 1 : 0), &d_xt, &xst); })) return rc;
+        U = f.U;
         d_cnt = d.run_cnt;
-        if (int rc = fwd.init(h, "case influence")) return rc;
+        if (int rc = f.fwd.init(h, "case influence")) return rc;
     }
+    const float* const d_xc = f.d_x;
+    const int xsc = f.xs;
     if (s.n_distinct) *s.n_distinct = U;
     if (U > 65535LL * INFL_KCHUNK) return fail(-1, "%d distinct samples: at most 65535 x %d per call", U, INFL_KCHUNK);     // grid.y
 

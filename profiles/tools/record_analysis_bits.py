@@ -6,7 +6,11 @@ bit for bit (and the digest of each case's inputs).  Run ONCE per list, on the c
                                                                         (csrc/ptnn_dev_wg.hpp and its callers) were gathered
     python3 profiles/tools/record_analysis_bits.py second [out.npz]     tests/golden/analysis_bits_parent2.npz: the second list, recorded
                                                                         before the host code of these calls was folded onto shared paths
+    python3 profiles/tools/record_analysis_bits.py third [out.npz]      tests/golden/analysis_bits_parent3.npz: the third list, recorded
+                                                                        before the scored calls, the predictive-mixture columns and
+                                                                        the rung layout were folded onto shared frames
 
+PTNN_LIBRARY=<the parent commit's libptnn.so> selects the library where the Python tree is the new commit's.
 The cases live in the test module, so the recording and the test cannot drift apart."""
 import os
 import sys
@@ -20,9 +24,10 @@ for p in (ROOT, os.path.join(ROOT, "oracle"), os.path.join(ROOT, "tests")):
 
 import test_gpu_analysis_bits as t  # noqa: E402
 
-if len(sys.argv) < 2 or sys.argv[1] not in ("first", "second"):
-    sys.exit("usage: record_analysis_bits.py first|second [out.npz]")
-file, record = (t.GOLDEN_FILE, t.record) if sys.argv[1] == "first" else (t.GOLDEN_FILE2, t.record2)
+LISTS = {"first": (t.GOLDEN_FILE, t.record), "second": (t.GOLDEN_FILE2, t.record2), "third": (t.GOLDEN_FILE3, t.record3)}
+if len(sys.argv) < 2 or sys.argv[1] not in LISTS:
+    sys.exit("usage: record_analysis_bits.py first|second|third [out.npz]")
+file, record = LISTS[sys.argv[1]]
 out = sys.argv[2] if len(sys.argv) > 2 else os.path.join(ROOT, "tests", "golden", file)
 rec = record()
 np.savez_compressed(out, **rec)

@@ -1,4 +1,4 @@
-"""The argument checks of fifteen posterior analysis calls, characterised (no GPU): every call checks its spec before it looks
+"""The argument checks of seventeen posterior analysis calls, characterised (no GPU): every call checks its spec before it looks
 at the handle, so a NULL handle shows which fault a spec is refused for, with which return code and which ptnn_last_error()
 text.  CASES names, per call, faulty specs for every refusal that precedes the handle check -- pairs of simultaneous faults
 included, where the order of the checks decides which one is reported -- and valid specs, which reach the handle check.  One
@@ -73,6 +73,15 @@ INFL_ROWS = dict(case_source=TRAIN, n_cases=5, target_source=TRAIN, n_targets=4)
 INFL = dict(TRACE, **INFL_ROWS)
 INFL_W = dict(w=f32(3, 4), n_w=3, **INFL_ROWS)
 INFL_MAT = dict(target_values=f32(4, 3), loglik=f64(4, 6), n_w=4, n_a=3, n_b=6)
+FSCORE = dict(TRACE, origin_source=TRAIN, n_origins=3, horizon=2, truth=f32(3, 2))
+FSCORE_W = dict(FSCORE, w=f32(3, 4), n_w=3, eta=f32(3), origin_source=HOST, origins=f32(3, 4))
+FSCORE_LEVELS = dict(n_levels=2, levels_p=np.array([0.1, 0.9]), levels_z=np.array([-1.28, 1.28]), quantiles=f64(2, 6))
+MBAR_ARGS = dict(n_rungs=2, betas=np.array([0.5, 1.0]), target_beta=1.0, tol=1e-8, max_iter=100)
+MBAR = dict(TRACE, **MBAR_ARGS)
+MBAR_U = dict(MBAR_ARGS, u=f64(2, 4), n_per_rung=4)
+MBAR_W = dict(MBAR_ARGS, w=f32(2, 4, 3), n_per_rung=4)
+MBAR_PRIOR = dict(n_prior=3, u_prior=f64(3))
+MBAR_MULT_NEGATIVE = dict(multiplicity=np.array([[1, 1, 1, 1], [1, -3, 1, 1]], np.int32))
 
 RANK_FAULTS = [
     ("n_ranks_negative", dict(n_ranks=-1)),
@@ -415,6 +424,103 @@ CASES = {
         ("target_x_null_and_n_cases_zero", INFL, dict(target_source=HOST, n_cases=0)),
         ("n_targets_zero_and_multiplicity_negative", INFL_W, dict(MULT_NEGATIVE, n_targets=0)),
         ("multiplicity_negative_and_loglik_not_finite", INFL_MAT, dict(multiplicity=i32(1, 1, -1, 1), loglik=_nan_at(f64(4, 6), 0, 0))),
+    ]),
+    "forecast_score": ("ForecastScoreSpec", "ptnn_forecast_score", [
+        ("valid_trace", FSCORE, dict(FSCORE_LEVELS, pair_term=1, crps=f64(6), energy=1, energy_score=f64(3), noise=1)),
+        ("valid_host", FSCORE_W, dict(multiplicity=i32(2, 0, 1), noise=1, truth=_nan_at(f32(3, 2), 1, 0))),
+        ("valid_trace_without_rows", FSCORE, dict(nsteps=0)),                      # an empty selection is refused with the handle
+        *[(n, FSCORE, f) for n, f in TRACE_FAULTS],
+        ("n_w_zero", FSCORE_W, dict(n_w=0)),
+        ("origin_source_unknown", FSCORE, dict(origin_source=-1)),
+        ("origins_host_null", FSCORE, dict(origin_source=HOST)),
+        ("n_origins_zero", FSCORE, dict(n_origins=0)),
+        ("horizon_zero", FSCORE, dict(horizon=0)),
+        ("too_many_columns", FSCORE, dict(n_origins=70000, horizon=70000)),
+        ("truth_null", FSCORE, dict(truth=None)),
+        ("truth_infinite", FSCORE, dict(truth=np.array([[0, 0], [0, -math.inf], [0, 0]], np.float32))),
+        ("truth_all_nan", FSCORE, dict(truth=np.full((3, 2), math.nan, np.float32))),
+        ("n_levels_negative", FSCORE, dict(n_levels=-1)),
+        ("n_levels_above_max", FSCORE, dict(FSCORE_LEVELS, n_levels=17)),
+        ("levels_z_null", FSCORE, dict(FSCORE_LEVELS, levels_z=None)),
+        ("quantiles_null", FSCORE, dict(FSCORE_LEVELS, quantiles=None)),
+        ("quantiles_without_levels", FSCORE, dict(quantiles=f64(6))),
+        ("level_one", FSCORE, dict(FSCORE_LEVELS, levels_p=np.array([0.1, 1.0]))),
+        ("level_z_infinite", FSCORE, dict(FSCORE_LEVELS, levels_z=np.array([-math.inf, 1.28]))),
+        ("crps_without_pair_term", FSCORE, dict(crps=f64(6))),
+        ("energy_score_without_energy", FSCORE, dict(energy_score=f64(3))),
+        ("energy_horizon_above_max", FSCORE, dict(energy=1, n_origins=1, horizon=2049, truth=f32(1, 2049))),
+        ("noise_without_eta", FSCORE_W, dict(eta=None, noise=1)),
+        ("multiplicity_negative", FSCORE_W, MULT_NEGATIVE),
+        ("thin_zero_and_origin_source_unknown", FSCORE, dict(thin=0, origin_source=-1)),
+        ("origins_host_null_and_n_origins_zero", FSCORE, dict(origin_source=HOST, n_origins=0)),
+        ("n_origins_zero_and_horizon_zero", FSCORE, dict(n_origins=0, horizon=0)),
+        ("horizon_zero_and_truth_null", FSCORE, dict(horizon=0, truth=None)),
+        ("horizon_zero_and_n_levels_negative", FSCORE, dict(horizon=0, n_levels=-1)),
+        ("truth_null_and_n_levels_negative", FSCORE, dict(truth=None, n_levels=-1)),
+        ("truth_infinite_and_level_one", FSCORE, dict(FSCORE_LEVELS, truth=np.full((3, 2), math.inf, np.float32), levels_p=np.array([0.1, 1.0]))),
+        ("truth_all_nan_and_quantiles_without_levels", FSCORE, dict(truth=np.full((3, 2), math.nan, np.float32), quantiles=f64(6))),
+        ("level_one_and_crps_without_pair_term", FSCORE, dict(FSCORE_LEVELS, levels_p=np.array([0.1, 1.0]), crps=f64(6))),
+        ("crps_without_pair_term_and_energy_score_without_energy", FSCORE, dict(crps=f64(6), energy_score=f64(3))),
+        ("energy_score_without_energy_and_noise_without_eta", FSCORE_W, dict(energy_score=f64(3), eta=None, noise=1)),
+        ("noise_without_eta_and_multiplicity_negative", FSCORE_W, dict(MULT_NEGATIVE, eta=None, noise=1)),
+    ]),
+    "mbar": ("MbarSpec", "ptnn_mbar", [
+        ("valid_trace", MBAR, dict(n_prior=10, replicas=i32(0, 1), n_replicas=2)),
+        ("valid_host", MBAR_W, dict(multiplicity=np.array([[1, 0, 2, 1], [4, 0, 0, 0]], np.int32), x_source=TRAIN, n_rows=5, mean=f64(5),
+                                    n_resample=4, resample_item=i64(0, 0, 0, 0), resample_w=f32(4, 3), n_prior=3, effective=1)),
+        ("valid_u", MBAR_U, dict(MBAR_PRIOR, b=f64(2, 4), b_prior=f64(3), multiplicity=np.array([[1, 0, 2, 1], [4, 0, 0, 0]], np.int32),
+                                 u=_nan_at(f64(2, 4), 1, 2), x_source=7)),
+        ("w_and_u", MBAR_U, dict(w=f32(2, 4, 3))),
+        ("b_without_u", MBAR_W, dict(b=f64(2, 4))),
+        ("n_rungs_zero", MBAR_U, dict(n_rungs=0)),
+        ("betas_null", MBAR_U, dict(betas=None)),
+        ("n_per_rung_zero", MBAR_W, dict(n_per_rung=0)),
+        ("no_source", MBAR, dict(nsteps=0)),
+        *[(n, MBAR, f) for n, f in TRACE_FAULTS],
+        ("n_replicas_not_n_rungs", MBAR, dict(replicas=i32(0, 1, 2), n_replicas=3)),
+        ("beta_zero", MBAR_U, dict(betas=np.array([0.0, 1.0]))),
+        ("beta_not_finite", MBAR_U, dict(betas=np.array([0.5, math.inf]))),
+        ("betas_not_rising", MBAR_U, dict(betas=np.array([0.5, 0.5]))),
+        ("n_prior_negative", MBAR, dict(n_prior=-1)),
+        ("n_prior_above_int32", MBAR, dict(n_prior=1 << 31)),
+        ("b_prior_without_u_prior", MBAR_U, dict(n_prior=3, b_prior=f64(3))),
+        ("u_prior_without_n_prior", MBAR_U, dict(u_prior=f64(3))),
+        ("too_many_states", MBAR_U, dict(n_prior=1, n_rungs=512, betas=np.arange(1, 513) / 512.0, u=f64(512, 4))),
+        ("target_beta_below_the_ladder", MBAR_U, dict(target_beta=0.25)),
+        ("target_beta_nan", MBAR_U, dict(target_beta=math.nan)),
+        ("tol_zero", MBAR_U, dict(tol=0.0)),
+        ("tol_inf", MBAR_U, dict(tol=math.inf)),
+        ("max_iter_zero", MBAR_U, dict(max_iter=0)),
+        ("n_resample_negative", MBAR_U, dict(n_resample=-1)),
+        ("resample_item_without_n_resample", MBAR_U, dict(resample_item=i64(0, 0))),
+        ("cum_weight_without_n_resample", MBAR_U, dict(cum_weight=f64(8))),
+        ("mean_with_u", MBAR_U, dict(mean=f64(5), x_source=TRAIN, n_rows=5)),
+        ("var_with_u_prior", MBAR_W, dict(MBAR_PRIOR, var=f64(5), x_source=TRAIN, n_rows=5)),
+        ("resample_w_with_u", MBAR_U, dict(n_resample=2, resample_w=f32(2, 3))),
+        ("resample_w_without_n_resample", MBAR_W, dict(resample_w=f32(2, 3))),
+        ("mean_n_rows_zero", MBAR_W, dict(mean=f64(5), x_source=TRAIN)),
+        ("mean_x_source_unknown", MBAR_W, dict(mean=f64(5), x_source=7, n_rows=5)),
+        ("mean_x_host_null", MBAR_W, dict(mean=f64(5), x_source=HOST, n_rows=5)),
+        ("u_prior_not_finite", MBAR_U, dict(MBAR_PRIOR, u_prior=_nan_at(f64(3), 1))),
+        ("b_prior_not_finite", MBAR_U, dict(MBAR_PRIOR, b_prior=_nan_at(f64(3), 2))),
+        ("too_many_host_rows", MBAR_W, dict(n_per_rung=1 << 30)),
+        ("multiplicity_negative", MBAR_U, MBAR_MULT_NEGATIVE),
+        ("u_not_finite", MBAR_U, dict(u=_nan_at(f64(2, 4), 1, 2))),
+        ("b_not_finite", MBAR_U, dict(b=_nan_at(f64(2, 4), 0, 3))),
+        ("w_and_u_and_b_without_u", MBAR_U, dict(w=f32(2, 4, 3), b=f64(2, 4))),
+        ("n_rungs_zero_and_betas_null", MBAR_U, dict(n_rungs=0, betas=None)),
+        ("betas_null_and_n_per_rung_zero", MBAR_U, dict(betas=None, n_per_rung=0)),
+        ("n_per_rung_zero_and_betas_not_rising", MBAR_U, dict(n_per_rung=0, betas=np.array([0.5, 0.5]))),
+        ("no_source_and_beta_zero", MBAR, dict(nsteps=0, betas=np.array([0.0, 1.0]))),
+        ("betas_not_rising_and_multiplicity_negative", MBAR_U, dict(MBAR_MULT_NEGATIVE, betas=np.array([0.5, 0.5]))),
+        ("betas_not_rising_and_u_prior_not_finite", MBAR_U, dict(MBAR_PRIOR, betas=np.array([1.0, 0.5]), u_prior=_nan_at(f64(3), 0))),
+        ("beta_zero_and_n_prior_negative", MBAR_U, dict(betas=np.array([0.0, 1.0]), n_prior=-1)),
+        ("n_per_rung_zero_and_u_prior_without_n_prior", MBAR_U, dict(n_per_rung=0, u_prior=f64(3))),
+        ("u_prior_without_n_prior_and_target_beta_nan", MBAR_U, dict(u_prior=f64(3), target_beta=math.nan)),
+        ("mean_with_u_and_u_prior_not_finite", MBAR_U, dict(MBAR_PRIOR, mean=f64(5), x_source=TRAIN, n_rows=5, u_prior=_nan_at(f64(3), 0))),
+        ("u_prior_not_finite_and_multiplicity_negative", MBAR_U, dict(MBAR_PRIOR, **MBAR_MULT_NEGATIVE, u_prior=_nan_at(f64(3), 1))),
+        ("u_prior_not_finite_and_n_per_rung_above_int32", MBAR_U, dict(MBAR_PRIOR, u_prior=_nan_at(f64(3), 1), n_per_rung=1 << 30)),
+        ("multiplicity_negative_and_u_not_finite", MBAR_U, dict(MBAR_MULT_NEGATIVE, u=_nan_at(f64(2, 4), 0, 0))),
     ]),
 }
 SPEC_FAULTS = ("null_spec", "struct_bytes_zero", "struct_bytes_off_by_one")       # the first check of every call

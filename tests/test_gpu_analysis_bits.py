@@ -16,7 +16,21 @@ tests/golden/analysis_bits_parent2.npz, recorded on the commit before the host c
 (the rows-by-vectors frame, the summary of signed columns, the pooled votes, the log-likelihood of rows): the same cases, every
 output as bits.  Each case runs a second time with every call's scratch budget at five rows' worth, so 24 rows take five blocks
 with a ragged last one, and is held to the same recorded bits: the shared helpers' `last` flag and row offsets live on that path,
-and no output depends on the blocking."""
+and no output depends on the blocking.
+
+A third list is held to tests/golden/analysis_bits_parent3.npz, recorded on the commit before the scored calls (elpd, lfo,
+calibration, forecast_score, ppc, powerscale, uncertainty, influence) were given the rows-by-vectors frame, calibration and
+forecast_score one body for the predictive-mixture columns, and evidence and mbar one rung layout.  forecast_score (regression
+net) in four runs: noise off with the pair term, the energy score, three levels, samples and means; noise on; noise off with the
+scratch at five origins' worth; and with the scratch below one origin's horizon and the energy score off, which splits the
+horizon.  mbar from host vectors [2, U / 2, P] with multiplicities, U prior draws, effective sample sizes, mean and var on the
+train rows and resampling, and from a host u / b.  And elpd (with loglik_out), lfo, calibration, ppc, powerscale and evidence of
+the first list again with their scratch at five rows' worth (ppc: 64 vectors' worth, so U = 100 takes two blocks, the second
+ragged): where the blocking changes the order of a sum (powerscale's l_u, evidence's U) these bits need not be the unblocked
+ones, so they are recorded as arrays of their own.  The outputs in the selection's order (elpd's loglik, forecast_score's samples
+and means) are asked for in every case and recorded at U = 100 only, samples and means not with the noise on (every occurrence is
+a trajectory of its own there: two incompressible [M, 24, 6] arrays), to keep the file within the size of the second golden; the
+per-row and per-column outputs beside them are functions of every one of their entries."""
 import hashlib
 import tempfile
 
@@ -33,6 +47,8 @@ from parity import orc
 from test_gpu_analysis_shapes import _data, _vectors
 from test_gpu_calibration import _check_oracle_forward
 from test_gpu_elpd import ATOL, _oracle_ll
+from test_gpu_fscore import _check_against_ref as fscore_check_against_ref
+from test_gpu_mbar import TOL as MBAR_TOL, _dev as mbar_dev, _reference as mbar_reference
 from test_gpu_powerscale import check_oracle as powerscale_check_oracle
 from test_gpu_ppc import check_occurrences
 from test_gpu_predict import _outputs, _pt
@@ -62,6 +78,17 @@ CALLS2 = ("partial_dependence", "coalition_values", "class_report", "uncertainty
 CALLS2_OF = {"reg": tuple(c for c in CALLS2 if c != "class_report"), "cls": tuple(c for c in CALLS2 if c != "forecast")}
 N_GRID, N_BACKGROUND, N_TERMS, HORIZON = 5, 8, 4, 6
 BLOCK_ROWS = 5                        # rows per block of the blocked run: 24 rows in blocks of 5, 5, 5, 5 and 4
+# the third list
+GOLDEN_FILE3 = "analysis_bits_parent3.npz"
+FSCORE_RUNS = ("fscore_noise_off", "fscore_noise_on", "fscore_origin_blocks", "fscore_split_horizon")
+MBAR_RUNS = ("mbar_vectors", "mbar_host_u")
+BLOCKED = ("elpd", "lfo", "calibration", "ppc", "powerscale", "evidence")
+CALLS3_OF = {"reg": FSCORE_RUNS + MBAR_RUNS + tuple(c + "_blocked" for c in BLOCKED),
+             "cls": MBAR_RUNS + tuple(c + "_blocked" for c in BLOCKED)}
+BETAS = (0.5, 1.0)                    # mbar: two rungs of U / 2 vectors each
+N_RESAMPLE = 64
+PPC_BLOCK_VECTORS = 64
+U_WITH_SAMPLES = 100                  # the outputs in the selection's order are recorded at this U only
 
 _HANDLES = {}
 
@@ -168,6 +195,93 @@ def run_calls2(pt, net, U, setenv=None):
     return out
 
 
+def truth_of(U):
+    """forecast_score's observations [N_ROWS, HORIZON] fp32: one in seven missing, the last origin with its first step only."""
+    rng = np.random.default_rng(97 * U)
+    truth = rng.normal(0.5, 0.2, (N_ROWS, HORIZON)).astype(np.float32)
+    truth[rng.random((N_ROWS, HORIZON)) < 1.0 / 7.0] = np.nan
+    truth[-1, 0], truth[-1, 1:] = 0.5, np.nan
+    return truth
+
+
+def host_u_of(U):
+    """mbar's host source: (u, b [2, U / 2], u_prior, b_prior [U]) float64."""
+    rng = np.random.default_rng(53 * U)
+    return (rng.normal(-30.0, 2.0, (2, U // 2)), rng.normal(1.0, 0.3, (2, U // 2)), rng.normal(-60.0, 8.0, U), rng.normal(0.0, 0.5, U))
+
+
+def scratch_budgets3(net, U):
+    """{call of the third list that runs blocked: (its scratch variable, the bytes of its blocks)}, by the calls' own budget
+    arithmetic: BLOCK_ROWS rows of fp32 outputs per distinct vector (elpd with loglik_out and powerscale: and a double beside
+    them; lfo gives half of its budget to the rows), ppc PPC_BLOCK_VECTORS vectors with all rows, forecast_score BLOCK_ROWS
+    origins of HORIZON steps, or one step less than a vector's window and one step hold (the horizon splits into single steps)."""
+    task, (I, _, O) = NETS[net]
+    row = 4 * U
+    return {
+        "elpd_blocked": ("PTNN_ELPD_SCRATCH_BYTES", BLOCK_ROWS * U * (4 * O + 8)),
+        "lfo_blocked": ("PTNN_LFO_SCRATCH_BYTES", 2 * BLOCK_ROWS * row * O),
+        "calibration_blocked": ("PTNN_CALIB_SCRATCH_BYTES", BLOCK_ROWS * row * O),
+        "ppc_blocked": ("PTNN_PPC_SCRATCH_BYTES", PPC_BLOCK_VECTORS * N_ROWS * O * 4),
+        "powerscale_blocked": ("PTNN_POWERSCALE_SCRATCH_BYTES", BLOCK_ROWS * U * (4 * O + 8)),
+        "evidence_blocked": ("PTNN_EVIDENCE_SCRATCH_BYTES", BLOCK_ROWS * row * O),
+        "fscore_origin_blocks": ("PTNN_FSCORE_SCRATCH_BYTES", BLOCK_ROWS * row * HORIZON),
+        "fscore_split_horizon": ("PTNN_FSCORE_SCRATCH_BYTES", row * (I + 1)),
+    }
+
+
+def run_calls3(pt, net, U, setenv, delenv):
+    """{call: the binding's whole result} of the third list of one case; every scratch variable is set for its call alone."""
+    task, (I, _, O) = NETS[net]
+    s = pt._sampler
+    w, eta, mult = samples(net, U)
+    src = dict(w=w, eta=eta, multiplicity=mult)
+    groups = [g for g in ("weights", "eta", "predictions", "loglik") if g != "eta" or task == REG]
+    truth = truth_of(U)
+    fscore = dict(quantiles=QUANTILES, seed=SEED, samples=True, means=True, **src)
+    u, b, u_prior, b_prior = host_u_of(U)
+    mult2 = mult.reshape(2, U // 2)
+    calls = {
+        "fscore_noise_off": lambda: s.forecast_score(HORIZON, "train", truth, noise=False, **fscore),
+        "fscore_noise_on": lambda: s.forecast_score(HORIZON, "train", truth, noise=True, **fscore),
+        "fscore_origin_blocks": lambda: s.forecast_score(HORIZON, "train", truth, noise=False, **fscore),
+        "fscore_split_horizon": lambda: s.forecast_score(HORIZON, "train", truth, noise=False, energy=False, **fscore),
+        "mbar_vectors": lambda: s.mbar(BETAS, w=w.reshape(2, U // 2, -1), multiplicity=mult2, n_prior=U, seed=SEED, effective=True, x="train",
+                                       n_resample=N_RESAMPLE, resample_seed=SEED + 1, resample_w=True, draws=True, item_map=True,
+                                       sse=task == REG),
+        "mbar_host_u": lambda: s.mbar(BETAS, u=u, b=b, multiplicity=mult2, u_prior=u_prior, b_prior=b_prior, effective=True,
+                                      n_resample=N_RESAMPLE, resample_seed=SEED + 1, draws=True, item_map=True),
+        "elpd_blocked": lambda: s.elpd("train", loglik_out=True, **src),
+        "lfo_blocked": lambda: s.lfo("train", n_fit=N_FIT, origins=ORIGINS, block=BLOCK, **src),
+        "calibration_blocked": lambda: s.calibration("train", quantiles=QUANTILES if task == REG else (), **src),
+        "ppc_blocked": lambda: s.ppc("train", lags=LAGS if task == REG else (), seed=SEED, samples=False, **src),
+        "powerscale_blocked": lambda: s.powerscale("train", groups=groups, **src),
+        "evidence_blocked": lambda: s.evidence(w=w.reshape(2, U // 2, -1), multiplicity=mult2, d=STONES, n_prior=U, seed=SEED, a=PRIOR_A,
+                                               u_out=True, u_prior_out=True),
+    }
+    budgets = scratch_budgets3(net, U)
+    out = {}
+    for call in CALLS3_OF[net]:
+        if call in budgets:
+            setenv(budgets[call][0], str(budgets[call][1]))
+        out[call] = calls[call]()
+        if call in budgets:
+            delenv(budgets[call][0])
+    return out
+
+
+def recorded3(out, U):
+    """`out` as the third golden file holds it: the outputs in the selection's order at U_WITH_SAMPLES only -- elpd's loglik, and
+    forecast_score's samples and means: never with the noise on, and of the blocked runs the samples alone."""
+    out = {call: dict(res) for call, res in out.items()}
+    for call in FSCORE_RUNS:
+        if call in out:
+            keep = () if U != U_WITH_SAMPLES or call == "fscore_noise_on" else ("samples", "means") if call == "fscore_noise_off" else ("samples",)
+            out[call].update((k, None) for k in ("samples", "means") if k not in keep)
+    if U != U_WITH_SAMPLES:
+        out["elpd_blocked"]["loglik"] = None
+    return out
+
+
 def key(net, U, call, name):
     return f"{net}_U{U}_{call}_{name}"
 
@@ -202,6 +316,20 @@ def record2():
         pt, train = handle(net)
         rec[key(net, U, "inputs", "sha256")] = digest(net, U, train)
         for call, res in run_calls2(pt, net, U).items():
+            for name, v in res.items():
+                if v is not None:
+                    rec[key(net, U, call, name)] = np.asarray(v)
+    return rec
+
+
+def record3():
+    """The third golden file: the digests again, and every output of the third list."""
+    import os
+    rec = {}
+    for net, U in CASES:
+        pt, train = handle(net)
+        rec[key(net, U, "inputs", "sha256")] = digest(net, U, train)
+        for call, res in recorded3(run_calls3(pt, net, U, os.environ.__setitem__, os.environ.__delitem__), U).items():
             for name, v in res.items():
                 if v is not None:
                     rec[key(net, U, call, name)] = np.asarray(v)
@@ -367,3 +495,40 @@ def test_second_list_equals_the_parent_commit(net, U):
 def test_second_list_in_five_blocks_of_rows_equals_the_parent_commit(net, U, monkeypatch):
     pt, train = handle(net)
     assert_recorded(golden(GOLDEN_FILE2), net, U, train, run_calls2(pt, net, U, setenv=monkeypatch.setenv))
+
+
+def check_references3(net, U, train, out):
+    """One headline output per call of the third list against the float64 reference of that call's own GPU test, at its tolerance
+    (test_gpu_fscore.py: _check_against_ref on the device's own means and samples; test_gpu_mbar.py: _reference on the device's own
+    N_k and sweep count, f within TOL; the U of the vectors as test_gpu_evidence.py holds them)."""
+    task, topo = NETS[net]
+    w, eta, mult = samples(net, U)
+    at = np.cumsum(mult) - mult                                              # the first occurrence of every distinct vector
+    if task == REG:
+        off = out["fscore_noise_off"]
+        assert off["n_samples"] == int(mult.sum()) and off["n_trajectories"] == U
+        assert np.array_equal(off["samples"], off["means"])
+        one_each = dict(off, samples=off["samples"][at], means=off["means"][at])
+        fscore_check_against_ref(one_each, eta, truth_of(U), mult, f"{net} U={U} noise off", levels=QUANTILES)
+    u, b, u_prior, b_prior = host_u_of(U)
+    mult2 = mult.reshape(2, U // 2)
+    hu = out["mbar_host_u"]
+    r = mbar_reference(dict(betas=np.asarray(BETAS), u=u, b=b, multiplicity=mult2, u_prior=u_prior, b_prior=b_prior), hu, 1.0)
+    mv = out["mbar_vectors"]
+    assert mv["n_items"] == 2 * U and mv["n_distinct"] == U
+    np.testing.assert_allclose(mv["u"][U:], evidence_ref.u_and_b_batched(task, train, w, topo)[0], rtol=1e-5, atol=1e-4)
+    rv = mbar_reference(dict(betas=np.asarray(BETAS), u=mv["u"][U:].reshape(2, -1), b=mv["b"][U:].reshape(2, -1), multiplicity=mult2,
+                             u_prior=mv["u"][:U], b_prior=mv["b"][:U]), mv, 1.0)
+    dev = dict(host_u_f=mbar_dev(hu["f"], r["f"]), host_u_log_weight=mbar_dev(hu["log_weight"], r["lw"]),
+               vectors_f=mbar_dev(mv["f"], rv["f"]), vectors_log_weight=mbar_dev(mv["log_weight"], rv["lw"]))
+    print(f"{net} U={U} mbar: sweeps {hu['n_iter']} / {mv['n_iter']}, deviations " + ", ".join(f"{k} {v:.2e}" for k, v in dev.items()))
+    for k, v in dev.items():
+        assert v <= MBAR_TOL, (k, v)
+
+
+@pytest.mark.parametrize("net,U", CASES, ids=[f"{n}-U{u}" for n, u in CASES])
+def test_third_list_equals_the_parent_commit(net, U, monkeypatch):
+    pt, train = handle(net)
+    out = run_calls3(pt, net, U, monkeypatch.setenv, monkeypatch.delenv)
+    assert_recorded(golden(GOLDEN_FILE3), net, U, train, recorded3(out, U))
+    check_references3(net, U, train, out)
