@@ -369,26 +369,47 @@ int upload_rows(ptnn_handle* h, DeviceScratch& mem, const RowSource& r, int widt
     return 0;
 }
 
-// Stage b of predict, elpd and evidence: the per-shape predict_fwd, NV distinct vectors staged in LDS per work-group
-struct ForwardPlan {
-    int PV = 0, NV = 0;
+// Stage b of every call whose per-shape forward kernel stages distinct vectors in LDS (Fwd = PredictFwd, SensFwd, PdFwd, AleFwd,
+// ShapFwd; ptnn_dev_net.hpp): what the five plans share.  A plan's own init() is its budget arithmetic -- vectors(), then fit().
+template <class Fwd> struct StagedPlan {
+    int PV = 0, NV = 0, VS = 0;
     size_t lds = 0;
-    void (*fwd)(const PredictFwd) = nullptr;
+    void (*fwd)(const Fwd) = nullptr;
+    // NV: as many vectors as `budget` floats of LDS hold at PV + `beside` floats each, at most max_nv
+    void vectors(const ptnn_handle* h, int max_nv, int budget, int beside) {
+        PV = round_up4(h->P);
+        NV = std::max(1, std::min(max_nv, budget / (PV + beside)));
+    }
+    // The LDS request: per vector PV floats and its finished tile of `tile` floats (none: 0) with the pad that lands the vectors of
+    // one column in different LDS banks, and `once` floats per work-group; the refusal in `what`'s name; the kernel of the shape.
+    int fit(const ptnn_handle* h, const char* what, void (*AnalysisShape::*which)(const Fwd), int tile, size_t once = 0) {
+        VS = tile ? tile + std::max(1, WAVE / NV) : 0;
+        lds = ((size_t)NV * (PV + VS) + once) * sizeof(float);
+        if (lds > LDS_CEILING) return fail(-3, "%s: a %d-parameter vector does not fit in LDS", what, h->P);
+        return analysis_shape(h, what, which, lds, &fwd);
+    }
+    FwdCommon common(const ptnn_handle* h, const float* base, const long long* run_off, const float* x, int xs, int r0, int nr, int U) const {
+        return FwdCommon{base, run_off, x, xs, r0, nr, h->cfg.n_hidden, h->P, PV, U, NV};
+    }
+    // groups of NV vectors x groups of `rows` rows (x nz)
+    int launch_groups(const ptnn_handle* h, const Fwd& fa, int threads, int rows = WAVE, int nz = 1) const {
+        HIP_TRY(launch(fwd, dim3((unsigned)((fa.c.U + NV - 1) / NV), (unsigned)((fa.c.nrows + rows - 1) / rows), (unsigned)nz),
+                       dim3(threads), lds, h->stream, fa));
+        return 0;
+    }
+};
+
+// predict, elpd, evidence, ...: the per-shape predict_fwd.  48 KiB of LDS; beside a staged vector the four waves' partial sums and
+// the transposed tile, which need no pad
+struct ForwardPlan : StagedPlan<PredictFwd> {
     int init(const ptnn_handle* h, const char* what) {
-        const int P = h->P;
-        PV = round_up4(P);
-        const int per_vec = PV + (PRED_THREADS / WAVE + 1) * h->cfg.n_out * WAVE;   // staged vector + partial sums + transposed tile
-        NV = std::max(1, std::min(PRED_MAX_NV, (48 * 1024 / 4) / per_vec));
-        lds = (size_t)NV * per_vec * sizeof(float);
-        if (lds > LDS_CEILING) return fail(-3, "%s: a %d-parameter vector does not fit in LDS", what, P);
-        return analysis_shape(h, what, &AnalysisShape::predict_fwd, lds, &fwd);
+        const int beside = (PRED_THREADS / WAVE + 1) * h->cfg.n_out * WAVE;
+        vectors(h, PRED_MAX_NV, 48 * 1024 / 4, beside);
+        return fit(h, what, &AnalysisShape::predict_fwd, 0, (size_t)NV * beside);
     }
     // fx [nr * O][U] = the outputs of vectors base + run_off[u] on rows [r0, r0 + nr) of x
     int run(const ptnn_handle* h, const float* base, const long long* run_off, const float* x, int xs, int r0, int nr, int U, float* fx) const {
-        PredictFwd fa{base, run_off, x, xs, r0, nr, h->cfg.n_hidden, h->P, PV, U, NV, fx};
-        HIP_TRY(launch(fwd, dim3((unsigned)((U + NV - 1) / NV), (unsigned)((nr + WAVE - 1) / WAVE)), dim3(PRED_THREADS), lds,
-                       h->stream, fa));
-        return 0;
+        return launch_groups(h, PredictFwd{common(h, base, run_off, x, xs, r0, nr, U), fx}, PRED_THREADS);
     }
 };
 // rows per block of the forward pass: `budget` bytes of scratch at `row_bytes` per row, and at most 65535 work-groups of WAVE
@@ -399,25 +420,15 @@ long long row_block(size_t budget, size_t row_bytes, long long n_rows) {
 
 // Stage b of sensitivity: the per-shape sens_fwd, NV distinct vectors staged in LDS per work-group beside their finished 64-row
 // gradient tiles (n_out * n_in * 64 floats each): as many vectors as 64 KiB hold, so that two work-groups share a CU
-struct SensPlan {
-    int PV = 0, NV = 0, VS = 0;
-    size_t lds = 0;
-    void (*fwd)(const SensFwd) = nullptr;
+struct SensPlan : StagedPlan<SensFwd> {
     int init(const ptnn_handle* h) {
-        const int P = h->P, OI = h->cfg.n_out * h->cfg.n_in;
-        PV = round_up4(P);
-        NV = std::max(1, std::min(SENS_MAX_NV, (64 * 1024 / 4) / (PV + (OI + 1) * WAVE)));
-        VS = OI * WAVE + std::max(1, WAVE / NV);        // the pad: the vectors of one column land in different LDS banks
-        lds = (size_t)NV * (PV + VS) * sizeof(float);
-        if (lds > LDS_CEILING) return fail(-3, "input sensitivity: a %d-parameter vector does not fit in LDS", P);
-        return analysis_shape(h, "input sensitivity", &AnalysisShape::sens_fwd, lds, &fwd);
+        const int tile = h->cfg.n_out * h->cfg.n_in * WAVE;
+        vectors(h, SENS_MAX_NV, 64 * 1024 / 4, tile + WAVE);
+        return fit(h, "input sensitivity", &AnalysisShape::sens_fwd, tile);
     }
     // gx [nr * O * I][U] = the input gradients of vectors base + run_off[u] on rows [r0, r0 + nr) of x
     int run(const ptnn_handle* h, const float* base, const long long* run_off, const float* x, int xs, int r0, int nr, int U, float* gx) const {
-        SensFwd fa{base, run_off, x, xs, r0, nr, h->cfg.n_hidden, h->P, PV, U, NV, VS, gx};
-        HIP_TRY(launch(fwd, dim3((unsigned)((U + NV - 1) / NV), (unsigned)((nr + WAVE - 1) / WAVE)), dim3(SENS_THREADS), lds,
-                       h->stream, fa));
-        return 0;
+        return launch_groups(h, SensFwd{common(h, base, run_off, x, xs, r0, nr, U), VS, gx}, SENS_THREADS);
     }
 };
 
@@ -428,32 +439,23 @@ struct SensPlan {
 // that leaves fewer than four (vector, tile) pairs for the four waves -- a vector above 16 KiB -- the chunk grows tile by tile
 // while the grid has more and the request stays under LDS_CEILING.  The largest compiled request is 34-512-2 with 64 grid values:
 // one vector of 18948 floats and a 64-value chunk, 108 816 B.
-struct PdPlan {
-    int PV = 0, NV = 0, VS = 0, GC = 0, NCH = 0, A = 0, G = 0;
-    size_t lds = 0;
-    void (*fwd)(const PdFwd) = nullptr;
+struct PdPlan : StagedPlan<PdFwd> {
+    int GC = 0, NCH = 0, A = 0, G = 0;
     int init(const ptnn_handle* h, int n_inputs, int n_grid) {
-        const int P = h->P, O = h->cfg.n_out, GT = pd_grid_tile(O), tiles = (n_grid + GT - 1) / GT;
+        const int O = h->cfg.n_out, GT = pd_grid_tile(O), tiles = (n_grid + GT - 1) / GT;
         A = n_inputs; G = n_grid;
-        PV = round_up4(P);
         int ct = std::min(tiles, std::max(1, PD_ACC / (O * GT)));
-        const auto per_vec = [&](int t) { return PV + (std::min(t * GT, G) * O + 1) * WAVE; };
-        NV = std::max(1, std::min(PD_MAX_NV, (64 * 1024 / 4) / per_vec(ct)));
-        while (NV * ct < PD_THREADS / WAVE && ct < tiles && (size_t)NV * per_vec(ct + 1) * sizeof(float) <= LDS_CEILING) ++ct;
+        const auto tile = [&](int t) { return std::min(t * GT, G) * O * WAVE; };
+        vectors(h, PD_MAX_NV, 64 * 1024 / 4, tile(ct) + WAVE);
+        while (NV * ct < PD_THREADS / WAVE && ct < tiles && (size_t)NV * (PV + tile(ct + 1) + WAVE) * sizeof(float) <= LDS_CEILING) ++ct;
         GC = std::min(ct * GT, G);
         NCH = (G + GC - 1) / GC;
-        VS = GC * O * WAVE + std::max(1, WAVE / NV);    // the pad: the vectors of one column land in different LDS banks
-        lds = (size_t)NV * (PV + VS) * sizeof(float);
-        if (lds > LDS_CEILING) return fail(-3, "partial dependence: a %d-parameter vector does not fit in LDS", P);
-        return analysis_shape(h, "partial dependence", &AnalysisShape::pd_fwd, lds, &fwd);
+        return fit(h, "partial dependence", &AnalysisShape::pd_fwd, tile(ct));
     }
     // fx [nr * A * G * O][U] = the outputs of vectors base + run_off[u] on rows [r0, r0 + nr) of x, input inputs[a] set to grid[a, k]
     int run(const ptnn_handle* h, const float* base, const long long* run_off, const float* x, int xs, int r0, int nr, int U,
             const int* inputs, const float* grid, float* fx) const {
-        PdFwd fa{base, run_off, x, xs, r0, nr, h->cfg.n_hidden, h->P, PV, U, NV, VS, A, G, GC, NCH, inputs, grid, fx};
-        HIP_TRY(launch(fwd, dim3((unsigned)((U + NV - 1) / NV), (unsigned)((nr + WAVE - 1) / WAVE), (unsigned)(A * NCH)),
-                       dim3(PD_THREADS), lds, h->stream, fa));
-        return 0;
+        return launch_groups(h, PdFwd{common(h, base, run_off, x, xs, r0, nr, U), VS, A, G, GC, NCH, inputs, grid, fx}, PD_THREADS, WAVE, A * NCH);
     }
 };
 
@@ -1222,27 +1224,20 @@ namespace {
 // (10 KiB per vector; 18 KiB at n_out = 18, where a pair's two slots are two passes), and once per work-group the chunk's slot
 // table (ale_slot_floats); NV = as many vectors as 64 KiB hold (two work-groups share a CU), at most 16.  The largest compiled
 // request is 34-512-2: one vector of 18948 floats, a 10-slot chunk and its table, 94 048 B.
-struct AlePlan {
-    int PV = 0, NV = 0, VS = 0, NCH1 = 0, NCH2 = 0;
-    size_t lds = 0;
-    void (*fwd)(const AleFwd) = nullptr;
+struct AlePlan : StagedPlan<AleFwd> {
+    int NCH1 = 0, NCH2 = 0;
     int init(const ptnn_handle* h, int A, int Q) {
-        const int O = h->cfg.n_out, CS = ale_chunk_slots(O);
-        PV = round_up4(h->P);
-        const int tile = CS * 2 * O * WAVE;
-        NV = std::max(1, std::min(ALE_MAX_NV, (64 * 1024 / 4 - ale_slot_floats(O)) / (PV + tile + WAVE)));
-        VS = tile + std::max(1, WAVE / NV);             // the pad: the vectors of one column land in different LDS banks
+        const int O = h->cfg.n_out, CS = ale_chunk_slots(O), tile = CS * 2 * O * WAVE;
+        vectors(h, ALE_MAX_NV, 64 * 1024 / 4 - ale_slot_floats(O), tile + WAVE);
         NCH1 = (A + CS - 1) / CS;
         NCH2 = (Q + CS / 2 - 1) / (CS / 2);
-        lds = ((size_t)NV * (PV + VS) + ale_slot_floats(O)) * sizeof(float);
-        if (lds > LDS_CEILING) return fail(-3, "accumulated effects: a %d-parameter vector does not fit in LDS", h->P);
-        return analysis_shape(h, "accumulated effects", &AnalysisShape::ale_fwd, lds, &fwd);
+        return fit(h, "accumulated effects", &AnalysisShape::ale_fwd, tile, (size_t)ale_slot_floats(O));
     }
-    int run(const ptnn_handle* h, AleFwd fa, int r0, int nr) const {
-        fa.row0 = r0; fa.nrows = nr; fa.H = h->cfg.n_hidden; fa.P = h->P; fa.PV = PV; fa.NV = NV; fa.VS = VS; fa.NCH1 = NCH1;
-        HIP_TRY(launch(fwd, dim3((unsigned)((fa.U + NV - 1) / NV), (unsigned)((nr + WAVE - 1) / WAVE), (unsigned)(NCH1 + NCH2)),
-                       dim3(ALE_THREADS), lds, h->stream, fa));
-        return 0;
+    // rows [r0, r0 + nr) of x with the terms, edges and outputs `fa` names
+    int run(const ptnn_handle* h, AleFwd fa, const float* base, const long long* run_off, const float* x, int xs, int r0, int nr, int U) const {
+        fa.c = common(h, base, run_off, x, xs, r0, nr, U);
+        fa.VS = VS; fa.NCH1 = NCH1;
+        return launch_groups(h, fa, ALE_THREADS, WAVE, NCH1 + NCH2);
     }
 };
 
@@ -1381,10 +1376,10 @@ int ptnn_accumulated_effects(ptnn_handle* h, const ptnn_ale_spec* spec) {
     if (int rc = f.items(h, s.samples || s.sample_ale || s.sample_range || s.sample_ale2 || s.sample_inter)) return rc;
     const unsigned ublocks = (unsigned)((U + PRED_THREADS - 1) / PRED_THREADS);
     AleFwd fa{};
-    fa.base = d.base; fa.run_off = d.run_off; fa.x = f.d_x; fa.xs = f.xs; fa.U = U; fa.A = A; fa.Q = Q; fa.E = E; fa.E2 = E2;
+    fa.A = A; fa.Q = Q; fa.E = E; fa.E2 = E2;
     fa.inputs = d_inputs; fa.edges = d_edges; fa.pairs = d_pairs; fa.edges2 = d_edges2; fa.fx = d_fx; fa.bins = d_bins;
     if (int rc = each_block(s.n_rows, rows_blk, [&](long long r0, int nr) -> int {
-        if (int rc = fwd.run(h, fa, (int)r0, nr)) return rc;
+        if (int rc = fwd.run(h, fa, d.base, d.run_off, f.d_x, f.xs, (int)r0, nr, U)) return rc;
         if (int rc = local.reduce(d_fx, r0 * T * O, (long long)nr * T * O)) return rc;
         if (d_acc) {
             AleBins ba{d_fx, d_bins, U, T, O, A, K, KK, (int)r0, nr, d_acc};
@@ -1437,24 +1432,15 @@ static_assert(SHAP_MAX_ACC % WAVE == 0 && sizeof(unsigned long long) == sizeof(u
 namespace {
 // Stage b of the coalition values: the per-shape kernel, NV distinct vectors staged in LDS per work-group -- as many as 64 KiB
 // hold, at most SHAP_MAX_NV -- and SHAP_ROWS explained rows; a wave takes (vector, row) pairs
-struct ShapPlan {
-    int PV = 0, NV = 0;
-    size_t lds = 0;
-    void (*fwd)(const ShapFwd) = nullptr;
+struct ShapPlan : StagedPlan<ShapFwd> {
     int init(const ptnn_handle* h) {
-        PV = round_up4(h->P);
-        NV = std::max(1, std::min(SHAP_MAX_NV, (64 * 1024 / 4) / PV));
-        lds = (size_t)NV * PV * sizeof(float);
-        if (lds > LDS_CEILING) return fail(-3, "coalition values: a %d-parameter vector does not fit in LDS", h->P);
-        return analysis_shape(h, "coalition values", &AnalysisShape::shap_fwd, lds, &fwd);
+        vectors(h, SHAP_MAX_NV, 64 * 1024 / 4, 0);
+        return fit(h, "coalition values", &AnalysisShape::shap_fwd, 0);
     }
     // fx [nr * O * T][U] = the T functionals of vectors base + run_off[u] on rows [r0, r0 + nr) of x
     int run(const ptnn_handle* h, const float* base, const long long* run_off, const float* x, int xs, int r0, int nr, int U,
             const float* bg, int B, int C, int T, const unsigned long long* masks, const double* coef, float* fx) const {
-        ShapFwd fa{base, run_off, x, xs, r0, nr, h->cfg.n_hidden, h->P, PV, U, NV, bg, B, C, T, masks, coef, fx};
-        HIP_TRY(launch(fwd, dim3((unsigned)((U + NV - 1) / NV), (unsigned)((nr + SHAP_ROWS - 1) / SHAP_ROWS)), dim3(SHAP_THREADS), lds,
-                       h->stream, fa));
-        return 0;
+        return launch_groups(h, ShapFwd{common(h, base, run_off, x, xs, r0, nr, U), bg, B, C, T, masks, coef, fx}, SHAP_THREADS, SHAP_ROWS);
     }
 };
 }  // namespace

@@ -9,6 +9,7 @@
 #include "ptnn_device.hpp"
 
 namespace ptnn {
+#include "ptnn_dev_net.hpp"                  // the network itself, stated once: arguments, staging, row load, decode, sigmoids, output head
 #include "ptnn_dev_predict.hpp"              // posterior predictive: the forward pass (selection and reduction: ptnn_dev_select.hpp)
 #include "ptnn_dev_forecast.hpp"             // recursive multi-step forecasts: the recursive forward pass
 #include "ptnn_dev_sensitivity.hpp"          // input sensitivity: the forward pass that carries the derivative to the inputs

@@ -40,13 +40,7 @@ constexpr int ale_slot_floats(int O) { return ale_chunk_slots(O) * (3 * 64 + 2);
 
 // what the forward kernel needs (the host fills it; ptnn_analysis.hip: AlePlan)
 struct AleFwd {
-    const float* base;          // vectors: d_pos_w rows or the uploaded host vectors
-    const long long* run_off;   // [U] float offset of distinct vector u in base
-    const float* x;             // input rows, x_0 .. x_{I-1} at x + row * xs
-    int xs;                     // row stride of x (floats)
-    int row0, nrows;            // rows [row0, row0 + nrows) of x form this block of columns
-    int H, P, PV;               // hidden units, parameters, LDS stride of a staged vector (P rounded up to 4)
-    int U, NV;                  // distinct vectors, vectors staged per work-group
+    FwdCommon c;
     int VS;                     // LDS stride of a vector's finished tile: chunk slots * 2 * O * 64 + a pad
     int A, Q;                   // first-order terms, pairs
     int E, E2;                  // edges per first-order input, edges per input of a pair
@@ -69,8 +63,8 @@ __device__ __forceinline__ int ale_bin(const float* __restrict__ e, int K, float
 }
 
 // One lane per input row with the row's inputs in registers, NV vectors staged in LDS, every weight read wave-uniform (an LDS
-// broadcast), as in pd_forward_kernel.  A work-group takes 64 rows, NV vectors and one chunk of whole terms.  First the four waves
-// share the chunk's slots: per slot the lane's bin from its own x_j (x_l), the deltas to the bin's edges, the offsets of the two
+// broadcast): the pieces of ptnn_dev_net.hpp.  A work-group takes 64 rows, NV vectors and one chunk of whole terms.  First the four
+// waves share the chunk's slots: per slot the lane's bin from its own x_j (x_l), the deltas to the bin's edges, the offsets of the two
 // W1 rows -- into LDS, since every (vector, tile) pair of the work-group reads them -- and, in the work-groups of the first vectors,
 // the bin (cell) index of the row into the plane.  Then the work is the nv x nt (vector, slot tile) pairs; wave w takes the pairs
 // w, w + 4, ...  A pair is one pass over ALL hidden units in ascending order: z_h from the row as it is (I FMAs, once for the whole
@@ -82,9 +76,10 @@ __global__ void __launch_bounds__(ALE_THREADS) ale_forward_kernel(const AleFwd a
     constexpr int ST = ale_slot_tile(O), CS = ale_chunk_slots(O), NWAVE = ALE_THREADS / WAVE;
     const int tid = threadIdx.x, lane = tid & (WAVE - 1);
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-    const int NV = a.NV, PV = a.PV, H = a.H, VS = a.VS, T = a.A + a.Q;
+    const FwdCommon& cm = a.c;
+    const int NV = cm.NV, PV = cm.PV, H = cm.H, VS = a.VS, T = a.A + a.Q;
     const int u0 = blockIdx.x * NV;
-    const int nv = min(NV, a.U - u0);
+    const int nv = min(NV, cm.U - u0);
     const int r0 = blockIdx.y * WAVE;
     const bool second = (int)blockIdx.z >= a.NCH1;      // a chunk of pairs
     const int term0 = second ? ((int)blockIdx.z - a.NCH1) * (CS / 2) : (int)blockIdx.z * CS;      // first term of the chunk, within its kind
@@ -95,18 +90,12 @@ __global__ void __launch_bounds__(ALE_THREADS) ale_forward_kernel(const AleFwd a
     float* fin = sv + (size_t)NV * PV;                  // [NV][VS] finished values: fin[v * VS + ((slot * 2 + lo) * O + o) * 64 + lane]
     float* sd = fin + (size_t)NV * VS;                  // [CS][3][64] per slot and lane: z_b - x_j, z_{b-1} - x_j, v - x_l
     int* so = reinterpret_cast<int*>(sd + CS * 3 * WAVE);   // [CS][2] per slot: the offsets of W1[j,:] and W1[l,:]
-    for (int v = 0; v < nv; ++v) {
-        const float* src = a.base + a.run_off[u0 + v];
-        for (int k = tid; k < a.P; k += ALE_THREADS) sv[v * PV + k] = src[k];
-    }
-    // a lane past the last row computes row 0 and stores nothing
+    stage_vectors<ALE_THREADS>(sv, cm, u0, nv, tid);
     const int row = r0 + lane;
-    const bool live = row < a.nrows;
-    const float* xr = a.x + (size_t)(a.row0 + (live ? row : 0)) * a.xs;
     float x[I];
-#pragma unroll
-    for (int i = 0; i < I; ++i) x[i] = xr[i];
-    const bool plane = live && blockIdx.x == 0;         // this work-group writes the rows' bins
+    const RowRef rr = load_row<I>(cm, row, x);
+    const float* xr = rr.xr;
+    const bool plane = rr.live && blockIdx.x == 0;      // this work-group writes the rows' bins
     for (int s = wave; s < ns; s += NWAVE) {
         int j, l = 0, bin;
         float dhi, dlo, dl = 0.0f;                      // fmaf(0, w, z) = z: no second input
@@ -126,7 +115,7 @@ __global__ void __launch_bounds__(ALE_THREADS) ale_forward_kernel(const AleFwd a
                 const int t = j; j = l; l = t;
             }
             bin = (bk - 1) * K2 + (bm - 1);
-            if (plane && (s & 1) == 0) a.bins[(size_t)(a.row0 + row) * T + a.A + q] = bin;
+            if (plane && (s & 1) == 0) a.bins[(size_t)(cm.row0 + row) * T + a.A + q] = bin;
         } else {
             const int t = term0 + s;
             j = a.inputs[t];
@@ -134,7 +123,7 @@ __global__ void __launch_bounds__(ALE_THREADS) ale_forward_kernel(const AleFwd a
             const float xj = xr[j];
             bin = ale_bin(e, a.E - 1, xj);
             dhi = e[bin] - xj; dlo = e[bin - 1] - xj;
-            if (plane) a.bins[(size_t)(a.row0 + row) * T + t] = bin - 1;
+            if (plane) a.bins[(size_t)(cm.row0 + row) * T + t] = bin - 1;
         }
         sd[(s * 3) * WAVE + lane] = dhi;
         sd[(s * 3 + 1) * WAVE + lane] = dlo;
@@ -144,10 +133,8 @@ __global__ void __launch_bounds__(ALE_THREADS) ale_forward_kernel(const AleFwd a
     __syncthreads();
     for (int p = wave; p < nv * nt; p += NWAVE) {
         const int v = p / nt, t0 = (p % nt) * ST;       // wave-uniform
-        const float* W1 = sv + v * PV;                  // [I][H]  (decode: w = W1, W2, B1, B2)
-        const float* W2 = W1 + I * H;                   // [H][O]
-        const float* B1 = W2 + H * O;
-        const float* B2 = B1 + H;
+        const NetView n = net_view<I, O>(sv + v * PV, H);
+        const float* W1 = n.W1;
         int oj[ST], ol[ST];
         float dhi[ST], dlo[ST], dl[ST], acc[O][ST][2];
 #pragma unroll
@@ -161,27 +148,24 @@ __global__ void __launch_bounds__(ALE_THREADS) ale_forward_kernel(const AleFwd a
         for (int h = 0; h < H; ++h) {
             float z = 0.0f;
             if constexpr (I > 16 && I < 32) {
-                // 20 inputs: the compiler keeps the I row offsets i * H in scalar registers and then spills 17 of them; a weight
-                // pointer it must hold in a vector register (the empty asm) costs one add per FMA here and no spill.  The same
-                // FMAs in the same order.
+                // 20 inputs: hidden_preact's form keeps the I row offsets i * H in scalar registers and the compiler then spills 17
+                // of them; a weight pointer it must hold in a vector register (the empty asm) costs one add per FMA here and no
+                // spill.  The same FMAs in the same order.
                 const float* wp = W1 + h;
 #pragma unroll
                 for (int i = 0; i < I; ++i) { z = fmaf(x[i], *wp, z); wp += H; asm volatile("" : "+v"(wp)); }
             } else {
-#pragma unroll
-                for (int i = 0; i < I; ++i) z = fmaf(x[i], W1[i * H + h], z);
+                z = hidden_preact<I>(x, W1, H, h);
             }
-            z -= B1[h];                                                     // bias subtracted (Q1)
+            z -= n.B1[h];                                                   // Q1
             float w2[O];
 #pragma unroll
-            for (int o = 0; o < O; ++o) w2[o] = W2[h * O + o];
+            for (int o = 0; o < O; ++o) w2[o] = n.W2[h * O + o];
 #pragma unroll
             for (int k = 0; k < ST; ++k) {
                 const float w1j = W1[oj[k] + h];
                 const float zb = fmaf(dl[k], W1[ol[k] + h], z);
-                const float zh = fmaf(dhi[k], w1j, zb), zl = fmaf(dlo[k], w1j, zb);
-                const float eh = expf(-fabsf(zh)), el = expf(-fabsf(zl));   // as sigmoid_and_slope forms it: e <= 1
-                const float hh = (zh >= 0.0f ? 1.0f : eh) / (1.0f + eh), hl = (zl >= 0.0f ? 1.0f : el) / (1.0f + el);
+                const float hh = sigmoid_sat(fmaf(dhi[k], w1j, zb)), hl = sigmoid_sat(fmaf(dlo[k], w1j, zb));
 #pragma unroll
                 for (int o = 0; o < O; ++o) {
                     acc[o][k][0] = fmaf(hh, w2[o], acc[o][k][0]);
@@ -189,7 +173,6 @@ __global__ void __launch_bounds__(ALE_THREADS) ale_forward_kernel(const AleFwd a
                 }
             }
         }
-        // the output sigmoid (Q2); classification: p = softmax(s) (CLS:108-110)
         float* out = fin + (size_t)v * VS + lane;
 #pragma unroll
         for (int k = 0; k < ST; ++k) {
@@ -197,18 +180,8 @@ __global__ void __launch_bounds__(ALE_THREADS) ale_forward_kernel(const AleFwd a
             for (int e2 = 0; e2 < 2; ++e2) {
                 float f[O];
 #pragma unroll
-                for (int o = 0; o < O; ++o) {
-                    const float zo = acc[o][k][e2] - B2[o];
-                    const float e = expf(-fabsf(zo));
-                    f[o] = (zo >= 0.0f ? 1.0f : e) / (1.0f + e);
-                }
-                if (TASK == TASK_CLS) {
-                    float sum = 0.0f;
-#pragma unroll
-                    for (int o = 0; o < O; ++o) { f[o] = expf(f[o]); sum += f[o]; }
-#pragma unroll
-                    for (int o = 0; o < O; ++o) f[o] = f[o] / sum;
-                }
+                for (int o = 0; o < O; ++o) f[o] = acc[o][k][e2];
+                output_head<TASK, O>(f, n.B2);
                 if (t0 + k < ns) {
 #pragma unroll
                     for (int o = 0; o < O; ++o) out[(((t0 + k) * 2 + e2) * O + o) * WAVE] = f[o];
@@ -222,7 +195,7 @@ __global__ void __launch_bounds__(ALE_THREADS) ale_forward_kernel(const AleFwd a
     const int tbase = second ? a.A + term0 : term0;
     for (int idx = tid; idx < nterm * O * WAVE * NV; idx += ALE_THREADS) {
         const int v = idx % NV, c = idx / NV, l = c % WAVE, to = c / WAVE, tt = to / O, o = to % O;
-        if (v < nv && r0 + l < a.nrows) {
+        if (v < nv && r0 + l < cm.nrows) {
             const float* fv = fin + (size_t)v * VS + l;
             const int s = second ? 2 * tt : tt;
             const double f0 = (double)fv[((s * 2) * O + o) * WAVE], f1 = (double)fv[((s * 2 + 1) * O + o) * WAVE];
@@ -233,7 +206,7 @@ __global__ void __launch_bounds__(ALE_THREADS) ale_forward_kernel(const AleFwd a
                 // the stated order [f(u_k, v_m) - f(u_{k-1}, v_m)] - [f(u_k, v_{m-1}) - f(u_{k-1}, v_{m-1})], whichever input the slots hold
                 d = a.pairs[2 * q] < a.pairs[2 * q + 1] ? (f0 - f1) - (f2 - f3) : (f0 - f2) - (f1 - f3);
             }
-            a.fx[(((size_t)(r0 + l) * T + tbase + tt) * O + o) * a.U + u0 + v] = (float)d;
+            a.fx[(((size_t)(r0 + l) * T + tbase + tt) * O + o) * cm.U + u0 + v] = (float)d;
         }
     }
 }

@@ -7,8 +7,9 @@
 //      col = origin * hb + k of a block of origins and horizon steps; the windows are carried from one horizon block to the next.
 //      With ForecastFwd::mu (ptnn_forecast_score) it also stores the output before the step's noise.
 //   c. predict_reduce_kernel, unchanged.
-// The forward pass is ptnn_predict's, operation for operation: four partial sums over h = wave (mod 4), each accumulated in
-// ascending h, combined in the order 0, 1, 2, 3, then the output sigmoid -- so step 1 is bit-identical to ptnn_predict on the
+// The forward pass is ptnn_predict's, operation for operation (the pieces of ptnn_dev_net.hpp where a line is the same operation;
+// the lane layout's transposed vectors have a decode and a pre-activation of their own): four partial sums over h = wave (mod 4),
+// each accumulated in ascending h, combined in the order 0, 1, 2, 3, then the output sigmoid -- so step 1 is bit-identical to ptnn_predict on the
 // origin rows, whichever layout runs it.  Nothing here writes chain state, tapes, counters or trace rows.
 
 constexpr int FC_THREADS = 256;          // 4 waves
@@ -98,7 +99,7 @@ __global__ void __launch_bounds__(FC_THREADS) forecast_forward_kernel(const Fore
                                 float zz = 0.0f;
 #pragma unroll
                                 for (int i = 0; i < I; ++i) zz = fmaf(x[i], W1[(i * H + h) * WAVE + lane], zz);
-                                const float hid = 1.0f / (1.0f + expf(-(zz - B1[h * WAVE + lane])));      // bias subtracted (Q1)
+                                const float hid = sigmoid_plain(zz - B1[h * WAVE + lane]);      // Q1
                                 acc[w] = fmaf(hid, W2[h * WAVE + lane], acc[w]);
                             }
                         }
@@ -106,7 +107,7 @@ __global__ void __launch_bounds__(FC_THREADS) forecast_forward_kernel(const Fore
                     float s = acc[0];
 #pragma unroll
                     for (int w = 1; w < NWAVE; ++w) s += acc[w];
-                    float y = 1.0f / (1.0f + expf(-(s - B2)));                                           // Q2
+                    float y = sigmoid_plain(s - B2);                                  // Q2
                     if (a.mu && live_u) a.mu[((size_t)rl * a.hb + (k - a.k0)) * U + u] = y;
                     if (a.noise) {
                         if (k == a.k0 || (k & 3) == 0) forecast_normals(k, u, r, a.seed_lo, a.seed_hi, z);
@@ -147,21 +148,16 @@ __global__ void __launch_bounds__(FC_THREADS) forecast_forward_kernel(const Fore
                 for (int i = 0; i < I; ++i) x[i] = wr[i];
             }
             __syncthreads();
-            const float* W1 = sv;
-            const float* W2 = W1 + I * H;
-            const float* B1 = W2 + H;
-            const float B2 = B1[H];
+            const NetView n = net_view<I, O>(sv, H);
+            const float B2 = n.B2[0];
             const float sd = a.noise ? expf(0.5f * a.eta[u]) : 0.0f;
             float z[4] = {0.0f, 0.0f, 0.0f, 0.0f};
             int buf = 0;
             for (int k = a.k0; k < a.k0 + a.hb; ++k) {
                 float acc = 0.0f;
                 for (int h = wave; h < H; h += NWAVE) {
-                    float zz = 0.0f;
-#pragma unroll
-                    for (int i = 0; i < I; ++i) zz = fmaf(x[i], W1[i * H + h], zz);
-                    const float hid = 1.0f / (1.0f + expf(-(zz - B1[h])));
-                    acc = fmaf(hid, W2[h], acc);
+                    const float hid = sigmoid_plain(hidden_preact<I>(x, n.W1, H, h) - n.B1[h]);
+                    acc = fmaf(hid, n.W2[h], acc);
                 }
                 red[(buf * NWAVE + wave) * WAVE + lane] = acc;
                 __syncthreads();
@@ -169,7 +165,7 @@ __global__ void __launch_bounds__(FC_THREADS) forecast_forward_kernel(const Fore
 #pragma unroll
                 for (int w = 1; w < NWAVE; ++w) s += red[(buf * NWAVE + w) * WAVE + lane];
                 buf ^= 1;
-                float y = 1.0f / (1.0f + expf(-(s - B2)));
+                float y = sigmoid_plain(s - B2);
                 if (a.mu && wave == 0 && live) a.mu[((size_t)rl * a.hb + (k - a.k0)) * U + u] = y;
                 if (a.noise) {
                     if (k == a.k0 || (k & 3) == 0) forecast_normals(k, u, r, a.seed_lo, a.seed_hi, z);

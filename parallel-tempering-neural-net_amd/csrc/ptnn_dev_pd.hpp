@@ -34,13 +34,7 @@ constexpr int pd_grid_tile(int O) { return PD_ACC / O < 1 ? 1 : (PD_ACC / O < PD
 
 // what the forward kernel needs (the host fills it; ptnn_analysis.hip: PdPlan)
 struct PdFwd {
-    const float* base;          // vectors: d_pos_w rows or the uploaded host vectors
-    const long long* run_off;   // [U] float offset of distinct vector u in base
-    const float* x;             // input rows, x_0 .. x_{I-1} at x + row * xs
-    int xs;                     // row stride of x (floats)
-    int row0, nrows;            // rows [row0, row0 + nrows) of x form this block of columns
-    int H, P, PV;               // hidden units, parameters, LDS stride of a staged vector (P rounded up to 4)
-    int U, NV;                  // distinct vectors, vectors staged per work-group
+    FwdCommon c;
     int VS;                     // LDS stride of a vector's finished tile: GC * O * 64 + a pad that spreads the vectors over the banks
     int A, G;                   // selected inputs, grid values per input
     int GC, NCH;                // grid values per chunk, chunks per input: blockIdx.z = a * NCH + chunk
@@ -50,7 +44,7 @@ struct PdFwd {
 };
 
 // One lane per input row with the row's inputs in registers, NV vectors staged in LDS, every weight read wave-uniform (an LDS
-// broadcast), as in sensitivity_forward_kernel.  A work-group takes 64 rows, NV vectors and one chunk: a selected input with a run
+// broadcast): the pieces of ptnn_dev_net.hpp.  A work-group takes 64 rows, NV vectors and one chunk: a selected input with a run
 // of its grid values.  Its work is the nv x nt (vector, grid tile) pairs; wave w takes the pairs w, w + 4, ...  A pair is one pass
 // over ALL hidden units in ascending order: z_h from the row as it is (I FMAs), then per grid value of the tile one FMA, one
 // sigmoid and O FMAs.  A tile slot past the chunk's last grid value recomputes that value and stores nothing.
@@ -60,9 +54,10 @@ __global__ void __launch_bounds__(PD_THREADS) pd_forward_kernel(const PdFwd a) {
     constexpr int GT = pd_grid_tile(O), NWAVE = PD_THREADS / WAVE;
     const int tid = threadIdx.x, lane = tid & (WAVE - 1);
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-    const int NV = a.NV, PV = a.PV, H = a.H, VS = a.VS, G = a.G;
+    const FwdCommon& cm = a.c;
+    const int NV = cm.NV, PV = cm.PV, H = cm.H, VS = a.VS, G = a.G;
     const int u0 = blockIdx.x * NV;
-    const int nv = min(NV, a.U - u0);
+    const int nv = min(NV, cm.U - u0);
     const int r0 = blockIdx.y * WAVE;
     const int ai = blockIdx.z / a.NCH, k0 = (blockIdx.z % a.NCH) * a.GC;
     const int kc = min(a.GC, G - k0);                   // grid values of this chunk, >= 1
@@ -71,26 +66,14 @@ __global__ void __launch_bounds__(PD_THREADS) pd_forward_kernel(const PdFwd a) {
     const float* gv = a.grid + (size_t)ai * G + k0;
     float* sv = smem;                                   // [NV][PV] the staged vectors
     float* fin = sv + (size_t)NV * PV;                  // [NV][VS] finished values: fin[v * VS + (kk * O + o) * 64 + lane]
-    for (int v = 0; v < nv; ++v) {
-        const float* src = a.base + a.run_off[u0 + v];
-        for (int k = tid; k < a.P; k += PD_THREADS) sv[v * PV + k] = src[k];
-    }
-    // a lane past the last row computes row 0 and stores nothing
-    const int row = r0 + lane;
-    const bool live = row < a.nrows;
-    const float* xr = a.x + (size_t)(a.row0 + (live ? row : 0)) * a.xs;
+    stage_vectors<PD_THREADS>(sv, cm, u0, nv, tid);
     float x[I];
-#pragma unroll
-    for (int i = 0; i < I; ++i) x[i] = xr[i];
-    const float xj = xr[j];                             // the run-time index goes to memory, not to the register array
+    const float xj = load_row<I>(cm, r0 + lane, x).xr[j];
     __syncthreads();
     for (int p = wave; p < nv * nt; p += NWAVE) {
         const int v = p / nt, t0 = (p % nt) * GT;       // wave-uniform
-        const float* W1 = sv + v * PV;                  // [I][H]  (decode: w = W1, W2, B1, B2)
-        const float* W2 = W1 + I * H;                   // [H][O]
-        const float* B1 = W2 + H * O;
-        const float* B2 = B1 + H;
-        const float* W1j = W1 + j * H;
+        const NetView n = net_view<I, O>(sv + v * PV, H);
+        const float* W1j = n.W1 + j * H;
         float dv[GT], acc[O][GT];
 #pragma unroll
         for (int k = 0; k < GT; ++k) {
@@ -99,41 +82,25 @@ __global__ void __launch_bounds__(PD_THREADS) pd_forward_kernel(const PdFwd a) {
             for (int o = 0; o < O; ++o) acc[o][k] = 0.0f;
         }
         for (int h = 0; h < H; ++h) {
-            float z = 0.0f;
-#pragma unroll
-            for (int i = 0; i < I; ++i) z = fmaf(x[i], W1[i * H + h], z);
-            z -= B1[h];                                                     // bias subtracted (Q1)
+            const float z = hidden_preact<I>(x, n.W1, H, h) - n.B1[h];      // Q1
             const float w1j = W1j[h];
             float w2[O];
 #pragma unroll
-            for (int o = 0; o < O; ++o) w2[o] = W2[h * O + o];
+            for (int o = 0; o < O; ++o) w2[o] = n.W2[h * O + o];
 #pragma unroll
             for (int k = 0; k < GT; ++k) {
-                const float zk = fmaf(dv[k], w1j, z);
-                const float e = expf(-fabsf(zk));                           // as sigmoid_and_slope forms it: e <= 1
-                const float hid = (zk >= 0.0f ? 1.0f : e) / (1.0f + e);
+                const float hid = sigmoid_sat(fmaf(dv[k], w1j, z));
 #pragma unroll
                 for (int o = 0; o < O; ++o) acc[o][k] = fmaf(hid, w2[o], acc[o][k]);
             }
         }
-        // the output sigmoid (Q2); classification: p = softmax(s) (CLS:108-110)
         float* out = fin + (size_t)v * VS + lane;
 #pragma unroll
         for (int k = 0; k < GT; ++k) {
             float f[O];
 #pragma unroll
-            for (int o = 0; o < O; ++o) {
-                const float zo = acc[o][k] - B2[o];
-                const float e = expf(-fabsf(zo));
-                f[o] = (zo >= 0.0f ? 1.0f : e) / (1.0f + e);
-            }
-            if (TASK == TASK_CLS) {
-                float sum = 0.0f;
-#pragma unroll
-                for (int o = 0; o < O; ++o) { f[o] = expf(f[o]); sum += f[o]; }
-#pragma unroll
-                for (int o = 0; o < O; ++o) f[o] = f[o] / sum;
-            }
+            for (int o = 0; o < O; ++o) f[o] = acc[o][k];
+            output_head<TASK, O>(f, n.B2);
             if (t0 + k < kc) {
 #pragma unroll
                 for (int o = 0; o < O; ++o) out[((t0 + k) * O + o) * WAVE] = f[o];
@@ -145,7 +112,7 @@ __global__ void __launch_bounds__(PD_THREADS) pd_forward_kernel(const PdFwd a) {
     const size_t GO = (size_t)G * O;
     for (int idx = tid; idx < kc * O * WAVE * NV; idx += PD_THREADS) {
         const int v = idx % NV, c = idx / NV, l = c % WAVE, ko = c / WAVE;
-        if (v < nv && r0 + l < a.nrows)
-            a.fx[((((size_t)(r0 + l) * a.A + ai) * GO) + (size_t)k0 * O + ko) * a.U + u0 + v] = fin[(size_t)v * VS + ko * WAVE + l];
+        if (v < nv && r0 + l < cm.nrows)
+            a.fx[((((size_t)(r0 + l) * a.A + ai) * GO) + (size_t)k0 * O + ko) * cm.U + u0 + v] = fin[(size_t)v * VS + ko * WAVE + l];
     }
 }

@@ -19,15 +19,9 @@ constexpr int PRED_SCAN_THREADS = 1024;  // the scan: one work-group
 constexpr int PRED_MAX_RANKS = 16;
 constexpr int PRED_MAX_NV = 16;          // distinct vectors per forward work-group
 
-// what the forward kernel needs (the host fills it; ptnn_analysis.hip: ptnn_predict)
+// what the forward kernel needs (the host fills it; ptnn_analysis.hip: ForwardPlan)
 struct PredictFwd {
-    const float* base;          // vectors: d_pos_w rows or the uploaded host vectors
-    const long long* run_off;   // [U] float offset of distinct vector u in base
-    const float* x;             // input rows, x_0 .. x_{I-1} at x + row * xs
-    int xs;                     // row stride of x (floats)
-    int row0, nrows;            // rows [row0, row0 + nrows) of x form this block of columns
-    int H, P, PV;               // hidden units, parameters, LDS stride of a staged vector (P rounded up to 4)
-    int U, NV;                  // distinct vectors, vectors staged per work-group
+    FwdCommon c;
     float* fx;                  // [nrows * O][U] column-major
 };
 
@@ -37,64 +31,46 @@ __global__ void __launch_bounds__(PRED_THREADS) predict_forward_kernel(const Pre
     const int tid = threadIdx.x, lane = tid & (WAVE - 1);
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     constexpr int NWAVE = PRED_THREADS / WAVE;
-    const int NV = a.NV, PV = a.PV, H = a.H;
+    const FwdCommon& cm = a.c;
+    const int NV = cm.NV, PV = cm.PV, H = cm.H;
     const int u0 = blockIdx.x * NV;
-    const int nv = min(NV, a.U - u0);
+    const int nv = min(NV, cm.U - u0);
     const int r0 = blockIdx.y * WAVE;
     float* sv = smem;                                   // [NV][PV] the staged vectors
     float* red = sv + (size_t)NV * PV;                  // [NWAVE][NV][O][64] partial output sums, one per wave's hidden slice
     float* fin = red + (size_t)NWAVE * NV * O * WAVE;   // [64 * O][NV] finished outputs, the tile transposed for the store
-    for (int v = 0; v < nv; ++v) {
-        const float* src = a.base + a.run_off[u0 + v];
-        for (int k = tid; k < a.P; k += PRED_THREADS) sv[v * PV + k] = src[k];
-    }
-    // one lane per input row, the row's inputs in registers (a lane past the last row computes row 0 and stores nothing)
-    const int row = r0 + lane;
-    const bool live = row < a.nrows;
-    const float* xr = a.x + (size_t)(a.row0 + (live ? row : 0)) * a.xs;
+    stage_vectors<PRED_THREADS>(sv, cm, u0, nv, tid);
     float x[I];
-#pragma unroll
-    for (int i = 0; i < I; ++i) x[i] = xr[i];
+    load_row<I>(cm, r0 + lane, x);
     __syncthreads();
     // wave `wave` takes the hidden units h = wave, wave + 4, ...: every weight read is wave-uniform (an LDS broadcast)
     for (int v = 0; v < nv; ++v) {
-        const float* W1 = sv + v * PV;                  // [I][H]  (decode: w = W1, W2, B1, B2)
-        const float* W2 = W1 + I * H;                   // [H][O]
-        const float* B1 = W2 + H * O;
+        const NetView n = net_view<I, O>(sv + v * PV, H);
         float acc[O];
 #pragma unroll
         for (int o = 0; o < O; ++o) acc[o] = 0.0f;
         for (int h = wave; h < H; h += NWAVE) {
-            float z = 0.0f;
+            const float hid = sigmoid_plain(hidden_preact<I>(x, n.W1, H, h) - n.B1[h]);      // Q1
 #pragma unroll
-            for (int i = 0; i < I; ++i) z = fmaf(x[i], W1[i * H + h], z);
-            const float hid = 1.0f / (1.0f + expf(-(z - B1[h])));        // bias subtracted (Q1)
-#pragma unroll
-            for (int o = 0; o < O; ++o) acc[o] = fmaf(hid, W2[h * O + o], acc[o]);
+            for (int o = 0; o < O; ++o) acc[o] = fmaf(hid, n.W2[h * O + o], acc[o]);
         }
 #pragma unroll
         for (int o = 0; o < O; ++o) red[(((size_t)wave * NV + v) * O + o) * WAVE + lane] = acc[o];
     }
     __syncthreads();
-    // the four partial sums in a fixed order, the output sigmoid (Q2), classification: softmax (CLS:108-110)
+    // the four partial sums in a fixed order, the plain output sigmoid (Q2), the softmax
     for (int idx = tid; idx < nv * WAVE; idx += PRED_THREADS) {
         const int v = idx / WAVE, l = idx % WAVE;
-        const float* B2 = sv + v * PV + I * a.H + a.H * O + a.H;
+        const float* B2 = net_view<I, O>(sv + v * PV, H).B2;
         float out[O];
 #pragma unroll
         for (int o = 0; o < O; ++o) {
             float s = red[(((size_t)0 * NV + v) * O + o) * WAVE + l];
 #pragma unroll
             for (int w = 1; w < NWAVE; ++w) s += red[(((size_t)w * NV + v) * O + o) * WAVE + l];
-            out[o] = 1.0f / (1.0f + expf(-(s - B2[o])));
+            out[o] = sigmoid_plain(s - B2[o]);
         }
-        if (TASK == TASK_CLS) {
-            float e[O], sum = 0.0f;
-#pragma unroll
-            for (int o = 0; o < O; ++o) { e[o] = expf(out[o]); sum += e[o]; }
-#pragma unroll
-            for (int o = 0; o < O; ++o) out[o] = e[o] / sum;
-        }
+        softmax_head<TASK, O>(out);
 #pragma unroll
         for (int o = 0; o < O; ++o) fin[(size_t)(l * O + o) * NV + v] = out[o];
     }
@@ -102,6 +78,6 @@ __global__ void __launch_bounds__(PRED_THREADS) predict_forward_kernel(const Pre
     // column-major store: column r0 * O + c of the block gets NV consecutive floats
     for (int idx = tid; idx < WAVE * O * NV; idx += PRED_THREADS) {
         const int c = idx / NV, v = idx % NV;
-        if (v < nv && r0 + c / O < a.nrows) a.fx[(size_t)(r0 * O + c) * a.U + u0 + v] = fin[idx];
+        if (v < nv && r0 + c / O < cm.nrows) a.fx[(size_t)(r0 * O + c) * cm.U + u0 + v] = fin[idx];
     }
 }

@@ -31,29 +31,15 @@ template <int I, int O> struct SensTile {
     static constexpr int IT = (I + NT - 1) / NT;
 };
 
-// what the forward kernel needs (the host fills it; ptnn_analysis.hip: ptnn_sensitivity)
+// what the forward kernel needs (the host fills it; ptnn_analysis.hip: SensPlan)
 struct SensFwd {
-    const float* base;          // vectors: d_pos_w rows or the uploaded host vectors
-    const long long* run_off;   // [U] float offset of distinct vector u in base
-    const float* x;             // input rows, x_0 .. x_{I-1} at x + row * xs
-    int xs;                     // row stride of x (floats)
-    int row0, nrows;            // rows [row0, row0 + nrows) of x form this block of columns
-    int H, P, PV;               // hidden units, parameters, LDS stride of a staged vector (P rounded up to 4)
-    int U, NV;                  // distinct vectors, vectors staged per work-group
+    FwdCommon c;
     int VS;                     // LDS stride of a vector's finished tile: O * I * 64 + a pad that spreads the vectors over the banks
     float* gx;                  // [nrows * O * I][U] column-major
 };
 
-// sigmoid(z) and its derivative without the cancellation 1 - sigmoid(z) of a saturated unit: e = exp(-|z|) <= 1,
-// sigmoid = (z >= 0 ? 1 : e) / (1 + e), derivative = e / (1 + e)^2 -- a few ulp at any saturation
-__device__ __forceinline__ void sigmoid_and_slope(float z, float* s, float* d) {
-    const float e = expf(-fabsf(z)), q = 1.0f + e;
-    *s = (z >= 0.0f ? 1.0f : e) / q;
-    *d = e / (q * q);
-}
-
 // One lane per input row with the row's inputs in registers, NV vectors staged in LDS, every weight read wave-uniform (an LDS
-// broadcast), as in predict_forward_kernel.  The work of a group is the nv x NT (vector, input tile) pairs; wave w takes the pairs
+// broadcast): the pieces of ptnn_dev_net.hpp.  The work of a group is the nv x NT (vector, input tile) pairs; wave w takes the pairs
 // w, w + 4, ...  A pair is one pass over ALL hidden units in ascending order -- z_h and a_o are recomputed per tile, the sums are
 // never split across waves -- so a value does not depend on NV, on the block of rows or on which wave computed it.
 template <int TASK, int I, int O>
@@ -62,30 +48,21 @@ __global__ void __launch_bounds__(SENS_THREADS) sensitivity_forward_kernel(const
     constexpr int IT = SensTile<I, O>::IT, NT = SensTile<I, O>::NT, NWAVE = SENS_THREADS / WAVE, OI = O * I;
     const int tid = threadIdx.x, lane = tid & (WAVE - 1);
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-    const int NV = a.NV, PV = a.PV, H = a.H, VS = a.VS;
+    const FwdCommon& cm = a.c;
+    const int NV = cm.NV, PV = cm.PV, H = cm.H, VS = a.VS;
     const int u0 = blockIdx.x * NV;
-    const int nv = min(NV, a.U - u0);
+    const int nv = min(NV, cm.U - u0);
     const int r0 = blockIdx.y * WAVE;
     float* sv = smem;                                   // [NV][PV] the staged vectors
     float* fin = sv + (size_t)NV * PV;                  // [NV][VS] finished gradients: fin[v * VS + (o * I + i) * 64 + lane]
-    for (int v = 0; v < nv; ++v) {
-        const float* src = a.base + a.run_off[u0 + v];
-        for (int k = tid; k < a.P; k += SENS_THREADS) sv[v * PV + k] = src[k];
-    }
-    // a lane past the last row computes row 0 and stores nothing
-    const int row = r0 + lane;
-    const bool live = row < a.nrows;
-    const float* xr = a.x + (size_t)(a.row0 + (live ? row : 0)) * a.xs;
+    stage_vectors<SENS_THREADS>(sv, cm, u0, nv, tid);
     float x[I];
-#pragma unroll
-    for (int i = 0; i < I; ++i) x[i] = xr[i];
+    load_row<I>(cm, r0 + lane, x);
     __syncthreads();
     for (int p = wave; p < nv * NT; p += NWAVE) {
         const int v = p / NT, i0 = (p % NT) * IT;      // wave-uniform
-        const float* W1 = sv + v * PV;                  // [I][H]  (decode: w = W1, W2, B1, B2)
-        const float* W2 = W1 + I * H;                   // [H][O]
-        const float* B1 = W2 + H * O;
-        const float* B2 = B1 + H;
+        const NetView n = net_view<I, O>(sv + v * PV, H);
+        const float *W1 = n.W1, *W2 = n.W2;
         int w1row[IT];                                  // W1 rows of this tile; past the last input (11 = 4 + 4 + 3): the last row again, not stored
 #pragma unroll
         for (int k = 0; k < IT; ++k) w1row[k] = min(i0 + k, I - 1) * H;
@@ -97,11 +74,8 @@ __global__ void __launch_bounds__(SENS_THREADS) sensitivity_forward_kernel(const
             for (int k = 0; k < IT; ++k) S[o][k] = 0.0f;
         }
         for (int h = 0; h < H; ++h) {
-            float z = 0.0f;
-#pragma unroll
-            for (int i = 0; i < I; ++i) z = fmaf(x[i], W1[i * H + h], z);
             float hid, d;
-            sigmoid_and_slope(z - B1[h], &hid, &d);                       // bias subtracted (Q1)
+            sigmoid_and_slope(hidden_preact<I>(x, W1, H, h) - n.B1[h], &hid, &d);       // Q1
             float dw[IT];
 #pragma unroll
             for (int k = 0; k < IT; ++k) dw[k] = d * W1[w1row[k] + h];
@@ -113,17 +87,11 @@ __global__ void __launch_bounds__(SENS_THREADS) sensitivity_forward_kernel(const
                 for (int k = 0; k < IT; ++k) S[o][k] = fmaf(w2, dw[k], S[o][k]);
             }
         }
-        // the output sigmoid (Q2) and its slope; classification: p = softmax(s) (CLS:108-110)
+        // the output sigmoid (Q2) and its slope, the softmax
         float ds[O], pc[O];
 #pragma unroll
-        for (int o = 0; o < O; ++o) sigmoid_and_slope(acc[o] - B2[o], &pc[o], &ds[o]);
-        if (TASK == TASK_CLS) {
-            float sum = 0.0f;
-#pragma unroll
-            for (int o = 0; o < O; ++o) { pc[o] = expf(pc[o]); sum += pc[o]; }
-#pragma unroll
-            for (int o = 0; o < O; ++o) pc[o] = pc[o] / sum;
-        }
+        for (int o = 0; o < O; ++o) sigmoid_and_slope(acc[o] - n.B2[o], &pc[o], &ds[o]);
+        softmax_head<TASK, O>(pc);
         float* out = fin + (size_t)v * VS + lane;
 #pragma unroll
         for (int k = 0; k < IT; ++k) {
@@ -143,6 +111,6 @@ __global__ void __launch_bounds__(SENS_THREADS) sensitivity_forward_kernel(const
     // column-major store: column (r0 + l) * O * I + oi of the block gets NV consecutive floats
     for (int idx = tid; idx < OI * WAVE * NV; idx += SENS_THREADS) {
         const int v = idx % NV, c = idx / NV, l = c % WAVE, oi = c / WAVE;
-        if (v < nv && r0 + l < a.nrows) a.gx[((size_t)(r0 + l) * OI + oi) * a.U + u0 + v] = fin[(size_t)v * VS + oi * WAVE + l];
+        if (v < nv && r0 + l < cm.nrows) a.gx[((size_t)(r0 + l) * OI + oi) * cm.U + u0 + v] = fin[(size_t)v * VS + oi * WAVE + l];
     }
 }

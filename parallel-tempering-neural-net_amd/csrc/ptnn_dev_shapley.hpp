@@ -40,13 +40,7 @@ constexpr int SHAP_MAX_ACC = 256;            // n_terms * n_out: four accumulato
 
 // what the forward kernel needs (the host fills it; ptnn_analysis.hip: ShapPlan)
 struct ShapFwd {
-    const float* base;                  // vectors: d_pos_w rows or the uploaded host vectors
-    const long long* run_off;           // [U] float offset of distinct vector u in base
-    const float* x;                     // explained rows, x_0 .. x_{I-1} at x + row * xs
-    int xs;                             // row stride of x (floats)
-    int row0, nrows;                    // rows [row0, row0 + nrows) of x form this block of columns
-    int H, P, PV;                       // hidden units, parameters, LDS stride of a staged vector (P rounded up to 4)
-    int U, NV;                          // distinct vectors, vectors staged per work-group
+    FwdCommon c;                        // x: the explained rows
     const float* bg;                    // [B][I] background rows
     int B, C, T;                        // background rows, coalitions, terms
     const unsigned long long* masks;    // [C] bit i set: input i from the explained row
@@ -57,25 +51,23 @@ struct ShapFwd {
 // One wave per (distinct vector, explained row) pair, the lanes over the background rows in chunks of 64.  NV vectors staged in
 // LDS, every weight read wave-uniform (an LDS broadcast); the explained row and the mask are uniform, the lane's background row
 // sits in I registers, the hybrid input is a select.  A work-group takes NV vectors and SHAP_ROWS rows; wave w takes the pairs w,
-// w + 4, ...  Per coalition and chunk: one pass over ALL hidden units in ascending order, the output sigmoids as pd_forward_kernel
-// forms them, the O outputs summed over the lanes in double by the butterfly.  The T * O <= 256 accumulators are spread over the
-// lanes: lane l owns q = l, l + 64, ... with q = o * T + t, and adds coef[c, t] * v[o] with one fma.
+// w + 4, ...  Per coalition and chunk: one pass over ALL hidden units in ascending order, the output head of ptnn_dev_net.hpp
+// (the saturating sigmoids), the O outputs summed over the lanes in double by the butterfly.  The T * O <= 256 accumulators are
+// spread over the lanes: lane l owns q = l, l + 64, ... with q = o * T + t, and adds coef[c, t] * v[o] with one fma.
 template <int TASK, int I, int O>
 __global__ void __launch_bounds__(SHAP_THREADS) shapley_forward_kernel(const ShapFwd a) {
     extern __shared__ __attribute__((aligned(16))) float smem[];
     constexpr int NWAVE = SHAP_THREADS / WAVE, NACC = SHAP_MAX_ACC / WAVE;
     const int tid = threadIdx.x, lane = tid & (WAVE - 1);
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-    const int NV = a.NV, PV = a.PV, H = a.H, B = a.B, C = a.C, T = a.T, OT = O * T;
+    const FwdCommon& cm = a.c;
+    const int NV = cm.NV, PV = cm.PV, H = cm.H, B = a.B, C = a.C, T = a.T, OT = O * T;
     const int u0 = blockIdx.x * NV;
-    const int nv = min(NV, a.U - u0);
+    const int nv = min(NV, cm.U - u0);
     const int r0 = blockIdx.y * SHAP_ROWS;
-    const int nr = min(SHAP_ROWS, a.nrows - r0);
+    const int nr = min(SHAP_ROWS, cm.nrows - r0);
     float* sv = smem;                                   // [NV][PV] the staged vectors
-    for (int v = 0; v < nv; ++v) {
-        const float* src = a.base + a.run_off[u0 + v];
-        for (int k = tid; k < a.P; k += SHAP_THREADS) sv[v * PV + k] = src[k];
-    }
+    stage_vectors<SHAP_THREADS>(sv, cm, u0, nv, tid);
     __syncthreads();
     const int nch = (B + WAVE - 1) / WAVE;              // chunks of background rows
     const double nb = (double)B;
@@ -89,11 +81,8 @@ __global__ void __launch_bounds__(SHAP_THREADS) shapley_forward_kernel(const Sha
     }
     for (int p = wave; p < nv * nr; p += NWAVE) {
         const int v = p / nr, r = r0 + p % nr;          // wave-uniform
-        const float* W1 = sv + v * PV;                  // [I][H]  (decode: w = W1, W2, B1, B2)
-        const float* W2 = W1 + I * H;                   // [H][O]
-        const float* B1 = W2 + H * O;
-        const float* B2 = B1 + H;
-        const float* xr = a.x + (size_t)(a.row0 + r) * a.xs;
+        const NetView n = net_view<I, O>(sv + v * PV, H);
+        const float* xr = cm.x + (size_t)(cm.row0 + r) * cm.xs;     // the explained row: wave-uniform, not load_row's row per lane
         float x[I], bg[I];
 #pragma unroll
         for (int i = 0; i < I; ++i) x[i] = xr[i];
@@ -117,36 +106,17 @@ __global__ void __launch_bounds__(SHAP_THREADS) shapley_forward_kernel(const Sha
 #pragma unroll
                     for (int i = 0; i < I; ++i) bg[i] = br[i];
                 }
-                float hx[I], s[O];
+                float hx[I], f[O];
 #pragma unroll
                 for (int i = 0; i < I; ++i) hx[i] = ((mask >> i) & 1ull) ? x[i] : bg[i];
 #pragma unroll
-                for (int o = 0; o < O; ++o) s[o] = 0.0f;
+                for (int o = 0; o < O; ++o) f[o] = 0.0f;
                 for (int h = 0; h < H; ++h) {
-                    float z = 0.0f;
+                    const float hid = sigmoid_sat(hidden_preact<I>(hx, n.W1, H, h) - n.B1[h]);      // Q1
 #pragma unroll
-                    for (int i = 0; i < I; ++i) z = fmaf(hx[i], W1[i * H + h], z);
-                    z -= B1[h];                                                 // bias subtracted (Q1)
-                    const float e = expf(-fabsf(z));                            // as sigmoid_and_slope forms it: e <= 1
-                    const float hid = (z >= 0.0f ? 1.0f : e) / (1.0f + e);
-#pragma unroll
-                    for (int o = 0; o < O; ++o) s[o] = fmaf(hid, W2[h * O + o], s[o]);
+                    for (int o = 0; o < O; ++o) f[o] = fmaf(hid, n.W2[h * O + o], f[o]);
                 }
-                // the output sigmoid (Q2); classification: p = softmax(s) (CLS:108-110)
-                float f[O];
-#pragma unroll
-                for (int o = 0; o < O; ++o) {
-                    const float zo = s[o] - B2[o];
-                    const float e = expf(-fabsf(zo));
-                    f[o] = (zo >= 0.0f ? 1.0f : e) / (1.0f + e);
-                }
-                if (TASK == TASK_CLS) {
-                    float sum = 0.0f;
-#pragma unroll
-                    for (int o = 0; o < O; ++o) { f[o] = expf(f[o]); sum += f[o]; }
-#pragma unroll
-                    for (int o = 0; o < O; ++o) f[o] = f[o] / sum;
-                }
+                output_head<TASK, O>(f, n.B2);
 #pragma unroll
                 for (int o = 0; o < O; ++o) vs[o] += wave_sum(b < B ? (double)f[o] : 0.0);
             }
@@ -167,7 +137,7 @@ __global__ void __launch_bounds__(SHAP_THREADS) shapley_forward_kernel(const Sha
 #pragma unroll
         for (int k = 0; k < NACC; ++k) {
             const int q = lane + WAVE * k;
-            if (q < OT) a.fx[((size_t)r * OT + q) * a.U + u0 + v] = (float)acc[k];
+            if (q < OT) a.fx[((size_t)r * OT + q) * cm.U + u0 + v] = (float)acc[k];
         }
     }
 }

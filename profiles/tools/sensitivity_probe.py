@@ -1,4 +1,5 @@
-"""Cost probe: sensitivity_forward_kernel beside predict_forward_kernel, Ionosphere shape 34-50-2, same (U, rows)."""
+"""Cost probe: sensitivity_forward_kernel beside predict_forward_kernel, Ionosphere shape 34-50-2, same (U, rows).  The library must
+have been built (PTNN_LIBRARY selects another one, as in every probe)."""
 import os
 import sys
 import tempfile
@@ -7,8 +8,6 @@ import time
 ROOT = os.path.dirname(os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 sys.path.insert(0, ROOT)
 sys.path.insert(0, os.path.join(ROOT, "tests"))
-import __graft_entry__  # noqa: E402
-__graft_entry__.build()
 import numpy as np  # noqa: E402
 from parity import orc  # noqa: E402
 from test_gpu_analysis_shapes import _data, _vectors  # noqa: E402
