@@ -3,6 +3,8 @@ the model evaluation (Sampler.evaluate: build_fw + eval_rows, the wide forward) 
 compiled shape: shapes, hidden sizes, generators, the seed of every case, the error unit and its bound, a float32 restatement of the
 epoch and the wrong epochs the bound must tell from the right one.  tests/test_gpu_model_shapes.py runs the cases on the device;
 tests/test_model_cases_cpu.py proves, from the oracle alone, that the bound leaves room for float32 and none for the wrong epochs.
+The tiled family (TILED) holds the matrix-core forward passes of the wide nets: tests/test_gpu_tiled_forward.py, with float32
+restatements of their summations, a bf16 operand model and the wrong forwards the evaluation's tolerances must refuse.
 Nothing here reads anything but the oracle."""
 import numpy as np
 
@@ -294,6 +296,185 @@ def tie_free(shape, H, ws, rows):
             if (zs[:, -1] - zs[:, -2]).min() < TIE_GAP:
                 return False
     return True
+
+
+# ---- the tiled family: wide nets whose hidden layer is a multiple of 32 take a matrix-core forward pass (wide_forward of
+# csrc/ptnn_dev_wide.hpp): H / 32 tiles, ceil(H / 64) waves.  96: 3 tiles on 2 waves, the two-stage tile pipeline of the split pass
+# ends on its odd tail; 128: 4 tiles, the even tail; 160: 5 tiles on 3 waves; 512: 16 tiles on 8 waves, more waves than the small row
+# sets have row blocks, and the widest net there is.  The evaluation rows and EVAL_SPLITS stay: Nall = 2, 36, 65, 600 are 1, 2, 3
+# and 19 blocks of 32 rows, and Ntr = 31, 60, 420 each fall inside a block.  NOT in FAMILIES: the epoch does not depend on tiling.
+TILED = (96, 128, 160, 512)
+# forward_bf16: 0 the default (split bf16 operands where SplitK<n_in> has them, else the exact fp32 instruction), 2 exact fp32, 1 bf16
+TILED_MODES = (0, 2, 1)
+# weight seeds of the tiled evaluation cases, by the rule of SEED_MOVES: the smallest k that is usable() ...
+TILED_SEED_MOVES = {((0, 4, 1), 96): 1, ((0, 4, 1), 160): 1, ((0, 32, 1), 96): 1, ((1, 34, 2), 512): 1, ((1, 16, 10), 160): 2,
+                    ((1, 6, 18), 160): 1}
+# ... and, for the cases with bf16 operands (forward_bf16 = 1), usable() on the rounded operands as well as on the plain ones
+TILED_BF16_SEED_MOVES = {((0, 4, 1), 96): 1, ((0, 4, 1), 160): 1, ((0, 32, 1), 96): 1, ((1, 34, 2), 512): 1, ((1, 20, 2), 96): 2,
+                         ((1, 16, 10), 96): 3, ((1, 16, 10), 128): 1, ((1, 16, 10), 160): 2, ((1, 6, 18), 160): 3}
+
+
+def tiled_weights(shape, H, bf16=False):
+    moves = TILED_BF16_SEED_MOVES if bf16 else TILED_SEED_MOVES
+    return weights(shape, H, seed=weight_seed(shape, H) + 100000 * moves.get((shape, H), 0))
+
+
+def split_k(I):
+    """SplitK<I> of csrc/ptnn_dev_coop.hpp -> (KB bf16 k-steps of 16, KR fp32 k-steps of 2 behind them, whether the split pass exists)."""
+    kb, rem = divmod(I, 16)
+    if rem >= 7:                    # PADLAST: a zero-padded bf16 k-step
+        kb, rem = kb + 1, 0
+    return kb, (rem + 1) // 2, kb in (1, 2, 4)
+
+
+def tiled_pass(I, mode):
+    """The forward pass a tiled wide net of I inputs takes under forward_bf16 = mode: "split", "exact" or "bf16"."""
+    return "bf16" if mode == 1 else "split" if mode == 0 and split_k(I)[2] else "exact"
+
+
+def bf16_round(a):
+    """float32 -> the nearest bf16 (ties to even) as float32: the integer form of f32_to_bf16 (csrc/ptnn_dev_coop.hpp); finite inputs."""
+    u = np.ascontiguousarray(a, dtype=np.float32).view(np.uint32)
+    u = (u + np.uint32(0x7FFF) + ((u >> np.uint32(16)) & np.uint32(1))) >> np.uint32(16)
+    return (u << np.uint32(16)).view(np.float32)
+
+
+def bf16_operands(topo, rows, w):
+    """What eval_rows_mfma<..., true> rounds: the input columns of the rows and W1; B1, W2, B2 and the targets stay.  float64 copies."""
+    I, H, _ = topo
+    rows, w = np.array(rows, dtype=np.float64), np.array(w, dtype=np.float64)
+    rows[:, :I] = bf16_round(rows[:, :I])
+    w[..., :I * H] = bf16_round(w[..., :I * H])
+    return rows, w
+
+
+def evaluate_bf16(task, topo, train, test, w, tau_sq=None):
+    """evaluate() of a net whose forward product has bf16 operands; the prior is that of the vector as it is."""
+    tr, wr = bf16_operands(topo, train, w)
+    te, _ = bf16_operands(topo, test, w)
+    out = evaluate(task, topo, tr, te, wr, tau_sq)
+    w = np.asarray(w, dtype=np.float64)
+    out["prior"] = (orc.prior_reg(SIGMA_SQUARED, NU_1, NU_2, w, tau_sq, topo) if task == orc.TASK_REG
+                    else orc.prior_cls(SIGMA_SQUARED, w, topo))
+    return out
+
+
+def usable_bf16(shape, H, ws, rows, splits=None):
+    """usable() on the operands as given and as forward_bf16 = 1 rounds them."""
+    rr, wr = bf16_operands((shape[1], H, shape[2]), rows, ws)
+    return usable(shape, H, ws, rows, splits) and usable(shape, H, wr, rr, splits)
+
+
+def split3(x):
+    """x = hi + mid + lo, three bf16 roundings of a float32 array (x - hi and x - hi - mid are exact in float32)."""
+    x = np.asarray(x, dtype=np.float32)
+    hi = bf16_round(x)
+    r = x - hi
+    mid = bf16_round(r)
+    return hi, mid, bf16_round(r - mid)
+
+
+def hidden_sums_f32(X, W1, how, two_terms=False):
+    """A float32 restatement of the hidden pre-activation sums X @ W1 of one matrix-core pass: X [N, I], W1 [B, I, H] -> [B, N, H]
+    float32, one float32 accumulator per element, one rounding per product added.
+    "exact": k ascending, fused multiply-add (the product is exact in float64).  "bf16": operands rounded to bf16 (products exact in
+    float32), k ascending.  "split": per bf16 k-step the six products in the kernel's order, small terms first -- W1.lo X.hi,
+    W1.hi X.lo, W1.mid X.mid of every k-step, then W1.mid X.hi, W1.hi X.mid, then W1.hi X.hi -- and the columns k >= 16 KB behind
+    them as in "exact".  two_terms: the split reduced to hi + mid (the four products without a lo term): a WRONG pass."""
+    X, W1 = np.asarray(X, dtype=np.float32), np.asarray(W1, dtype=np.float32)
+    I = X.shape[1]
+    acc = np.zeros((W1.shape[0], X.shape[0], W1.shape[2]), dtype=np.float32)
+
+    def add(xk, wk, fused=False):
+        nonlocal acc
+        if fused:
+            acc = (acc + xk.astype(np.float64)[None, :, None] * wk.astype(np.float64)[:, None, :]).astype(np.float32)
+        else:
+            acc += xk[None, :, None] * wk[:, None, :]
+    if how == "exact":
+        for k in range(I):
+            add(X[:, k], W1[:, k], fused=True)
+        return acc
+    if how == "bf16":
+        Xb, Wb = bf16_round(X), bf16_round(W1)
+        for k in range(I):
+            add(Xb[:, k], Wb[:, k])
+        return acc
+    assert how == "split", how
+    KB = split_k(I)[0]
+    xs, ws = split3(X), split3(W1)                                   # (hi, mid, lo)
+    HI, MID, LO = 0, 1, 2
+    groups = (((LO, HI), (HI, LO), (MID, MID)), ((MID, HI), (HI, MID)), ((HI, HI),))
+    for group in groups:
+        for s in range(KB):
+            for a, b in group:
+                if two_terms and LO in (a, b):
+                    continue
+                for k in range(16 * s, min(16 * s + 16, I)):
+                    add(xs[b][:, k], ws[a][:, k])
+    for k in range(16 * KB, I):
+        add(X[:, k], W1[:, k], fused=True)
+    return acc
+
+
+def outputs_f32(Z, w, topo):
+    """The rest of the forward pass in float32 from the hidden sums Z [N, H]: -> (output pre-activations, outputs) [N, O] float32."""
+    I, H, O = topo
+    w, one = np.asarray(w, dtype=np.float32), np.float32(1)
+    a, b = I * H, I * H + H * O
+    hid = one / (one + np.exp(-(np.asarray(Z, dtype=np.float32) - w[b:b + H])))
+    z = hid @ w[a:b].reshape(H, O) - w[b + H:]
+    return z, one / (one + np.exp(-z))
+
+
+def outputs_wrong(X, w, topo, mutant):
+    """float64 (output pre-activations, outputs) of a structurally wrong forward pass: "input_last" (input column I - 1 never
+    multiplied), "remainder" (the columns k >= 16 KB behind the bf16 k-steps never multiplied), "unit_last" (hidden unit H - 1, the
+    last of the last tile, left out of the product with W2); None: the right one."""
+    I, H, O = topo
+    W1, W2, B1, B2 = orc.decode(np.asarray(w, dtype=np.float64), topo)
+    keep = np.ones(I)
+    if mutant == "input_last":
+        keep[I - 1] = 0
+    elif mutant == "remainder":
+        keep[16 * split_k(I)[0]:] = 0
+        assert keep.sum() < I
+    hid = orc.sigmoid((X * keep) @ W1 - B1)
+    if mutant == "unit_last":
+        hid[:, H - 1] = 0
+    z = hid @ W2 - B2
+    return z, orc.sigmoid(z)
+
+
+def scores(task, topo, z, out, rows, ntr, nte, w, tau_sq=None, twice=None):
+    """One vector's row of Sampler.evaluate (log-likelihood, RMSE train / test, accuracy train / test, prior, log-likelihood of the
+    test rows, 0) from the outputs of a forward pass over `rows` = the ntr + nte rows: out [N, O], and z, the output pre-activations
+    the class is taken from (tie_free: no row's argmax is a matter of rounding).  The sums over rows in float64, as the model kernel
+    forms them (finish_eval): per-row terms, N = the row count.  twice: a row that is scored twice (a WRONG evaluation)."""
+    I = topo[0]
+    y = rows[:ntr + nte, I]
+    out = np.asarray(out, dtype=np.float64)[:ntr + nte]
+    cnt = np.ones(ntr + nte)
+    if twice is not None:
+        cnt[twice] += 1
+    parts = (slice(0, ntr), slice(ntr, ntr + nte))
+    ev = np.zeros(8)
+    if task == orc.TASK_REG:
+        a = (y - out[:, 0]) ** 2 * cnt
+        ssq = [float(a[p].sum()) for p in parts]
+        n = (ntr, nte)
+        lik = [-0.5 * n[j] * np.log(2.0 * np.pi * tau_sq) - 0.5 * ssq[j] / tau_sq for j in range(2)]
+        ev[0], ev[6] = lik
+        ev[1], ev[2] = np.sqrt(ssq[0] / ntr), np.sqrt(ssq[1] / nte)
+        ev[5] = orc.prior_reg(SIGMA_SQUARED, NU_1, NU_2, np.asarray(w, dtype=np.float64), tau_sq, topo)
+        return ev
+    arg = np.argmax(np.asarray(z)[:ntr + nte], axis=1).astype(np.float64)
+    a = (out[np.arange(ntr + nte), y.astype(np.int64)] - np.log(np.exp(out).sum(axis=1))) * cnt
+    ev[0], ev[6] = (float(a[p].sum()) for p in parts)
+    ev[1], ev[2] = (np.sqrt(float((((arg - y) ** 2) * cnt)[p].sum()) / n) for p, n in zip(parts, (ntr, nte)))
+    ev[3], ev[4] = (100.0 * float(((arg == y) * cnt)[p].sum()) / n for p, n in zip(parts, (ntr, nte)))
+    ev[5] = orc.prior_cls(SIGMA_SQUARED, np.asarray(w, dtype=np.float64), topo)
+    return ev
 
 
 # ---- the regimes of np.argmax over float64 sigmoid outputs (argmax_key of the device): cases for two small nets, a few rows ----------------

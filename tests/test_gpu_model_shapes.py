@@ -167,18 +167,20 @@ def test_argmax_follows_float64_outputs_in_every_regime(shape, H):
 LANGEVIN_TOPOS = [(9, 12, 2), (11, 12, 10), (20, 50, 2), (16, 30, 10), (6, 9, 18)]
 
 
-def langevin_chains(topo, train, test, schedule, label):
+def langevin_chains(topo, train, test, schedule, label, task=orc.TASK_CLS, groups=0, committed=None):
     """Four replicas, 26 samples, swaps every 6, Langevin proposals with probability 0.5 at lr 0.01, against the oracle on the same
-    tape exactly as test_classification_shapes_of_the_problem_table does -> the handle's description."""
+    tape exactly as test_classification_shapes_of_the_problem_table does -> the handle's description.  The ladder tops out at 10 for
+    a classification and at 2 for a regression, as everywhere in the suite.  committed: a dict that receives what the run committed
+    (traces, swap statistics, swap log, state), for a caller that compares runs with each other."""
     I, H, O = topo
     R, S, si, seed = 4, 26, 6, 90 + H
-    pt = orc.PTOracle(orc.TASK_CLS, topo, train, test, R, 10, R * S, si, use_lg=True, l_prob=0.5, lr=0.01, seed=seed)
+    pt = orc.PTOracle(task, topo, train, test, R, 10 if task == orc.TASK_CLS else 2, R * S, si, use_lg=True, l_prob=0.5, lr=0.01, seed=seed)
     w0 = (0.5 * np.stack([rep.w for rep in pt.replicas])).astype(np.float32)
     for rep, w in zip(pt.replicas, w0):
-        rep.__init__(orc.TASK_CLS, topo, pt.train, pt.test, w.astype(np.float64), rep.T, S, True, 0.5, 0.01, pt.tape, rep.gid)
+        rep.__init__(task, topo, pt.train, pt.test, w.astype(np.float64), rep.T, S, True, 0.5, 0.01, pt.tape, rep.gid)
     o = parity.OracleRun(pt).run()
-    s = parity.make_sampler(orc.TASK_CLS, topo, train, test, R_local=R, R_global=R, first=0, S=S, si=si, use_lg=True, lr=0.01,
-                            seed=seed, l_prob=0.5, schedule=schedule)
+    s = parity.make_sampler(task, topo, train, test, R_local=R, R_global=R, first=0, S=S, si=si, use_lg=True, lr=0.01,
+                            seed=seed, l_prob=0.5, schedule=schedule, groups=groups)
     s.set_state(w0, np.array(pt.temperatures, dtype=np.float32))
     what = s.describe()
     s.run(-1)
@@ -189,6 +191,8 @@ def langevin_chains(topo, train, test, schedule, label):
     parity.check_run_against_oracle(s, tr, o, label)
     lg = s.state()["langevin_count"]
     assert (lg > 0).all() and sum(rep.langevin_count for rep in pt.replicas) > 0, lg
+    if committed is not None:
+        committed.update(traces=tr, swap_stats=(nsw, tot, rounds), swap_log=s.swap_log().copy(), state=s.state())
     s.close()
     return what
 

@@ -228,3 +228,188 @@ def test_argmax_regime_cases_are_what_they_claim(shape, H):
             for part in (train, test):
                 y = part[:, I]
                 assert np.count_nonzero(y == arg[0]) != np.count_nonzero(y == wrong) or np.sum((y - arg[0]) ** 2) != np.sum((y - wrong) ** 2)
+
+
+# ---- the tiled family: the matrix-core forward passes of the wide nets (tests/test_gpu_tiled_forward.py) -------------------------------
+#
+# From float64 alone, over the ten shapes x TILED x the four row sets x the three vectors (x two tau for regression): a float32
+# restatement of each pass's summation -- exact fp32 and bf16 operands k ascending, the split pass in the kernel's order of its six
+# products -- stays inside check_evaluation's tolerances (the golden-vector ones, class counts as integers), and the structurally
+# wrong forwards fall outside them on at least one row set of every (shape, H): the last input column never multiplied, the fp32
+# remainder columns never multiplied (20 and 34 inputs), the last hidden unit of the last tile left out, row Nall - 1 scored twice
+# (the repeated block of an odd block count).  Measured here, largest |log-likelihood - float64| of the restatements over the grid
+# in units of the tolerance 1e-3 + 2e-5 |lik|: exact 0.017, bf16 (against the oracle on rounded operands) 0.019, split 0.004.
+# The split reduced to two terms (hi + mid) is measured and printed, not asserted: 0.077 at worst, refused in none of the 24
+# (shape, H) that have a split pass -- these tolerances cannot see a 2^-16 relative error in a product.
+from test_gpu_model_shapes import check_evaluation  # noqa: E402
+
+_TILED = {}
+
+
+def tiled_cell(shape, H):
+    """(rows, {bf16: three vectors}, {bf16: {(split, tau, k): the oracle's figures}}, {pass: [(z, out) of each vector] float32})"""
+    if (shape, H) not in _TILED:
+        task, I, O = shape
+        topo = (I, H, O)
+        rows = mc.eval_data(shape)
+        ws = {False: mc.tiled_weights(shape, H), True: mc.tiled_weights(shape, H, bf16=True)}
+        want = {False: {}, True: {}}
+        for bf, fn in ((False, mc.evaluate), (True, mc.evaluate_bf16)):
+            for ntr, nte in mc.EVAL_SPLITS:
+                for tau in taus(task):
+                    for k in range(3):
+                        want[bf][(ntr, nte), tau, k] = fn(task, topo, rows[:ntr], rows[ntr:ntr + nte], ws[bf][k], tau)
+        passes = {}
+        hows = ["exact", "bf16"] + (["split", "two_terms"] if mc.split_k(I)[2] else [])
+        for how in hows:
+            w3 = ws[how == "bf16"]
+            Z = mc.hidden_sums_f32(rows[:, :I], w3[:, :I * H].reshape(3, I, H), "split" if how == "two_terms" else how,
+                                   two_terms=how == "two_terms")
+            passes[how] = [mc.outputs_f32(Z[k], w3[k], topo) for k in range(3)]
+        _TILED[shape, H] = (rows, ws, want, passes)
+    return _TILED[shape, H]
+
+
+def taus(task):
+    return mc.TAUS if task == orc.TASK_REG else (None,)
+
+
+def outside(shape, H, zo, bf16=False, twice=False):
+    """[(units of the log-likelihood tolerance, (split, tau, k))] of one forward pass' outputs zo = [(z, out) of each vector] over
+    the 600 rows, and the cells in which check_evaluation refuses them."""
+    task, I, O = shape
+    rows, ws, want, _ = tiled_cell(shape, H)
+    units, refused = [], []
+    for ntr, nte in mc.EVAL_SPLITS:
+        for tau in taus(task):
+            for k in range(3):
+                z, out = zo[k]
+                ev = mc.scores(task, (I, H, O), z, out, rows, ntr, nte, ws[bf16][k], tau, twice=ntr + nte - 1 if twice else None)
+                ref = want[bf16][(ntr, nte), tau, k]
+                units.append((max(abs(ev[0] - ref["lik"]) / (1e-3 + 2e-5 * abs(ref["lik"])),
+                                  abs(ev[6] - ref["lik_test"]) / (1e-3 + 2e-5 * abs(ref["lik_test"]))), ((ntr, nte), tau, k)))
+                try:
+                    check_evaluation(ev, ref, task, ntr, nte, f"{shape} {H} {ntr} {nte} {tau} w{k}")
+                except AssertionError:
+                    refused.append(((ntr, nte), tau, k))
+    return units, refused
+
+
+def test_tiled_list_is_what_the_matrix_core_passes_can_run():
+    """Every entry a multiple of 32 in (64, 512] (wide_mfma; MAX_HIDDEN = 8 waves of 64), an odd and an even tile count (the tail of
+    the two-stage tile pipeline), more waves than row blocks somewhere, waves without a group of two row blocks, an odd block count
+    (the repeated block), uneven work over the waves at 600 rows, and a training set that ends inside a block in three row sets."""
+    text = open(os.path.join(ROOT, "parallel-tempering-neural-net_amd", "csrc", "ptnn.hip")).read()
+    assert re.search(r"MAX_HIDDEN = MAX_WAVES \* WAVE;", text)
+    assert mc.TILED == (96, 128, 160, 512) and "tiled" not in mc.FAMILIES and not set(mc.TILED) & set(HIDDEN)
+    assert all(64 < H <= 512 and H % 32 == 0 for H in mc.TILED)
+    tiles = [H // 32 for H in mc.TILED]
+    nw = [-(-H // 64) for H in mc.TILED]
+    assert tiles == [3, 4, 5, 16] and nw == [2, 2, 3, 8]
+    assert any(t % 2 for t in tiles) and any(t % 2 == 0 for t in tiles)
+    nrb = [-(-(a + b) // 32) for a, b in mc.EVAL_SPLITS]
+    assert nrb == [1, 2, 3, 19]
+    assert any(w > b for w in nw for b in nrb) and any(b % 2 for b in nrb[1:]) and all(nrb[-1] % w for w in nw)
+    assert all(a % 32 for a, _ in mc.EVAL_SPLITS[1:])
+    # SplitK<n_in> as the header has it: which shapes have the split pass, their bf16 k-steps and fp32 remainder steps
+    assert {s[1]: mc.split_k(s[1]) for s in mc.SHAPES} == {4: (0, 2, False), 5: (0, 3, False), 6: (0, 3, False), 9: (1, 0, True),
+                                                           11: (1, 0, True), 16: (1, 0, True), 20: (1, 2, True), 32: (2, 0, True),
+                                                           34: (2, 1, True)}
+    coop = open(os.path.join(ROOT, "parallel-tempering-neural-net_amd", "csrc", "ptnn_dev_coop.hpp")).read()
+    for line in ("PADLAST = REM0 >= 7;", "KB = KB0 + (PADLAST ? 1 : 0);", "KR = (REM + 1) / 2;", "OK = (KB == 1 || KB == 2 || KB == 4);"):
+        assert line in coop, line
+
+
+def test_bf16_round_is_nearest_even():
+    x = np.array([1.0, 1.0 + 2.0 ** -8, 1.0 + 3 * 2.0 ** -8, 1.0 + 2.0 ** -8 + 2.0 ** -20, -0.3, 0.0, 3.0e38 / 2], dtype=np.float32)
+    r = mc.bf16_round(x)
+    assert r.dtype == np.float32 and r[0] == 1.0 and r[1] == 1.0 and r[2] == 1.0 + 2.0 ** -6 and r[3] == 1.0 + 2.0 ** -7 and r[5] == 0.0
+    assert (r.view(np.uint32) & 0xFFFF == 0).all() and np.all(np.abs(r - x) <= np.abs(x) * 2.0 ** -8)
+    hi, mid, lo = mc.split3(x)
+    assert np.all(np.abs((hi.astype(np.float64) + mid + lo) - x) <= np.abs(x) * 2.0 ** -24)
+
+
+def test_tiled_seeds_are_the_smallest_usable_moves():
+    for shape in mc.SHAPES:
+        rows = mc.eval_data(shape)
+        for H in mc.TILED:
+            for moves, ok, bf in ((mc.TILED_SEED_MOVES, mc.usable, False), (mc.TILED_BF16_SEED_MOVES, mc.usable_bf16, True)):
+                ws = mc.tiled_weights(shape, H, bf16=bf)
+                assert ok(shape, H, ws, rows), (shape, H, bf)
+                assert np.array_equal(ws, ws.astype(np.float32).astype(np.float64))
+                for lower in range(moves.get((shape, H), 0)):
+                    assert not ok(shape, H, mc.weights(shape, H, seed=mc.weight_seed(shape, H) + 100000 * lower), rows), (shape, H, lower)
+    assert all(H in mc.TILED and s in mc.SHAPES for s, H in list(mc.TILED_SEED_MOVES) + list(mc.TILED_BF16_SEED_MOVES))
+
+
+def test_scores_restate_the_oracles_evaluation():
+    """model_cases.scores on the float64 forward pass is model_cases.evaluate, to float64 round-off, on a regression and a
+    many-class cell; and evaluate_bf16 is evaluate but for the rounded operands (the prior excepted)."""
+    for shape, H in (((0, 5, 1), 96), ((1, 11, 10), 160)):
+        task, I, O = shape
+        rows, ws, want, _ = tiled_cell(shape, H)
+        for ntr, nte in mc.EVAL_SPLITS:
+            for tau in taus(task):
+                z, out = mc.outputs_wrong(rows[:, :I], ws[False][1], (I, H, O), None)
+                ev = mc.scores(task, (I, H, O), z, out, rows, ntr, nte, ws[False][1], tau)
+                ref = want[False][(ntr, nte), tau, 1]
+                names = ("lik", "rmse_train", "rmse_test", "acc_train", "acc_test", "prior", "lik_test")
+                for j, nm in enumerate(names):
+                    if nm in ref:
+                        assert ev[j] == pytest.approx(ref[nm], rel=1e-12, abs=1e-12), (shape, ntr, nm)
+                bf = want[True][(ntr, nte), tau, 1]
+                if np.array_equal(ws[True][1], ws[False][1]):
+                    assert bf["prior"] == ref["prior"] and bf["lik"] != ref["lik"]
+
+
+def test_float32_restatements_of_the_tiled_passes_stay_inside_the_tolerances():
+    worst = {}
+    for shape in mc.SHAPES:
+        for H in mc.TILED:
+            passes = tiled_cell(shape, H)[3]
+            for how in ("exact", "bf16", "split"):
+                if how in passes:
+                    units, refused = outside(shape, H, passes[how], bf16=how == "bf16")
+                    assert not refused, (how, shape, H, refused)
+                    worst[how] = max(worst.get(how, (0.0,)), (max(units)[0], shape, H, max(units)[1]))
+    print("MODEL_SHAPES tiled float32 restatements, worst |lik - float64| / (1e-3 + 2e-5 |lik|): "
+          + "; ".join(f"{how} {v[0]:.4f} at {v[1:]}" for how, v in worst.items()))
+    assert set(worst) == {"exact", "bf16", "split"}
+
+
+TILED_MUTANTS = ("input_last", "remainder", "unit_last", "row_twice")
+
+
+@pytest.mark.parametrize("mutant", TILED_MUTANTS)
+def test_structurally_wrong_tiled_forwards_fall_outside_the_tolerances(mutant):
+    """... in at least one row set of every (shape, H) the mutant applies to, under every one of the three vectors."""
+    seen = 0
+    for shape in mc.SHAPES:
+        task, I, O = shape
+        if mutant == "remainder" and mc.split_k(I)[1:] not in ((1, True), (2, True)):
+            continue
+        for H in mc.TILED:
+            rows, ws, _, _ = tiled_cell(shape, H)
+            kind = None if mutant == "row_twice" else mutant
+            zo = [mc.outputs_wrong(rows[:, :I], ws[False][k], (I, H, O), kind) for k in range(3)]
+            _, refused = outside(shape, H, zo, twice=mutant == "row_twice")
+            assert {k for _, _, k in refused} == {0, 1, 2}, (mutant, shape, H, refused)
+            seen += 1
+    assert seen == (2 if mutant == "remainder" else len(mc.SHAPES)) * len(mc.TILED)
+
+
+def test_two_term_split_is_measured_not_promised():
+    """The split pass reduced to hi + mid (16 significant bits an operand, products good to 2^-16) against float64: how many cells of
+    the grid the tolerances refuse, and how far the log-likelihood is off.  Printed; DESIGN.md has the figures and what follows."""
+    cells, caught, worst = 0, 0, (0.0,)
+    for shape in mc.SHAPES:
+        for H in mc.TILED:
+            passes = tiled_cell(shape, H)[3]
+            if "two_terms" in passes:
+                units, refused = outside(shape, H, passes["two_terms"])
+                cells += 1
+                caught += bool(refused)
+                worst = max(worst, (max(units)[0], shape, H, max(units)[1]))
+    print(f"MODEL_SHAPES tiled two-term split: refused in {caught} of {cells} (shape, H); worst |lik - float64| / (1e-3 + 2e-5 |lik|) "
+          f"{worst[0]:.3f} at {worst[1:]}")
+    assert cells == 6 * len(mc.TILED)
